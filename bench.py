@@ -17,10 +17,14 @@ Rank 0 prints ONE JSON line (contract in the task statement) with extra objects:
                   which one binds (`binding`).  Every frac can be recomputed from the printed definitions + profiles/.
   roofline_all  — the same for the GEMM (MFMA; frac on SURVEY 8d's each-unordered-pair-once flops, `executed_tflops`
                   beside it), the re-rank and the prediction kernel.
+  step_ms       — mean / population sigma / min / max over the timed steps (shared/predictions.scala:18-25).
+With --full (one GPU) the line also carries what the headline figure does not need, measured after the timed steps:
+  bf16_filter   — the same steps with bf16 instead of fp16 GEMM operands (--no-bf16-leg leaves it out).
   cpu_baseline  — the fp64 CPU restatement (oracle, 1 thread like the reference's local[1]) timed on a bounded sample
                   of the same workload on this host; cpu_baseline_all_cores — the oracle's threaded bulk form on all
-                  host cores (cores stated), same bounded-sample protocol.
-  step_ms       — mean / population sigma / min / max over the timed steps (shared/predictions.scala:18-25).
+                  host cores (cores stated), same bounded-sample protocol (--no-cpu-baseline leaves them out).
+--dump-outputs DIR writes what the last timed step computed as DIR/*.npy (see dump_outputs) for output-for-output
+comparisons of two builds on the same seeded inputs.
 """
 import argparse
 import importlib
@@ -39,6 +43,13 @@ HBM_PEAK_TBPS = 8.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 LDS_ATOMIC_UPDATES_PER_CLK_PER_CU = 9.6
 CUS, CLOCK_GHZ = 256, 2.4
 PMC_PROFILE = "r03_pmc_traffic_syn25m_1gpu.json"  # profiles/: the PMC passes of this exact workload (scripts/profile_round.sh)
+# --dump-outputs stays under 64 MB: up to 6 M predictions (48 MB), beyond that a seeded sample of 3 M with its row
+# indices; neighbour lists of at most 1 M (user, neighbour) cells (16 MB of ids + similarities)
+DUMP_MAX_PREDICTIONS = 6_000_000
+DUMP_SAMPLE_PREDICTIONS = 3_000_000
+DUMP_MAX_NEIGHBOR_USERS = 1024
+DUMP_MAX_NEIGHBOR_CELLS = 1_000_000
+DUMP_SEED = 20251016
 
 
 def log(*a):
@@ -134,6 +145,52 @@ def cpu_baseline(split, k, budget_s, n_test_total):
     return one, all_cores
 
 
+def dump_outputs(out_dir, kn, sharded, eng, dist, rank, world, device, tr, te, d_te, mae, n_pred):
+    """What the last timed step computed, as float64 .npy files (untimed; every rank takes part, rank 0 writes):
+      mae.npy               [mae, number of predictions] the step returned
+      predictions.npy       the kNN prediction of every test rating, in test-set order (the prediction stage re-run on the
+                            step's neighbourhoods, which is deterministic); beyond DUMP_MAX_PREDICTIONS rows a seeded sample,
+                            whose rows prediction_index.npy names
+      neighbor_users.npy    one GPU only: a seeded sample of training users (raw ids) ...
+      neighbor_ids.npy      ... their neighbour ids, best first (-1 past a user's count) ...
+      neighbor_sims.npy     ... and the fp64 similarities (nan past the count)"""
+    import numpy as np
+    import torch
+
+    preds = torch.zeros(len(te), dtype=torch.float64, device=device)
+    s, c = eng.mae_device(kn.PRED_KNN, *d_te, pred_out=preds)
+    if dist is not None:
+        sharded._all_reduce(dist, preds)  # each rank wrote only the rows of its users; the others' cells are 0
+    torch.cuda.synchronize()
+    if world == 1 and (c != n_pred or s / c != mae):
+        raise RuntimeError(f"--dump-outputs: the re-run prediction stage gave MAE {s / c} over {c} rows, the step {mae} over {n_pred}")
+    if rank != 0:
+        return
+    out = {"mae": np.array([mae, n_pred], dtype=np.float64)}
+    p = preds.cpu().numpy()
+    rng = np.random.default_rng(DUMP_SEED)
+    if len(p) > DUMP_MAX_PREDICTIONS:
+        idx = np.sort(rng.choice(len(p), DUMP_SAMPLE_PREDICTIONS, replace=False))
+        out["prediction_index"] = idx.astype(np.float64)
+        p = p[idx]
+    out["predictions"] = p
+    if world == 1:  # a shard handle answers for its own users only
+        users = np.unique(tr.users)
+        n = min(len(users), DUMP_MAX_NEIGHBOR_USERS, max(1, DUMP_MAX_NEIGHBOR_CELLS // max(1, eng.k)))
+        users = np.sort(rng.choice(users, n, replace=False))
+        ids, sims, _ = eng.neighbors_batch(users)
+        out["neighbor_users"] = users.astype(np.float64)
+        out["neighbor_ids"] = ids.astype(np.float64)
+        out["neighbor_sims"] = sims
+    total = sum(a.nbytes for a in out.values())
+    if total > 64_000_000:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the 64 MB budget")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    log(f"[rank 0] --dump-outputs: {', '.join(sorted(out))} ({total / 1e6:.1f} MB) -> {out_dir}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -152,7 +209,14 @@ def main():
     ap.add_argument("--head-items", type=int, default=0, help="dense head width of the hybrid similarity (0 = cost model)")
     ap.add_argument("--workspace-bytes", type=int, default=0, help="cap of the similarity-panel workspace (0 = auto); small values = small row blocks")
     ap.add_argument("--engine-flags", type=int, default=0, help="KNNCF_FLAG_* bits (1 verify bound, 2 overlap, 4 bf16 filter operands instead of fp16)")
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need: the bf16-operand leg and the "
+                    "CPU baselines (each can still be left out with --no-bf16-leg / --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed "
+                    "as DIR/<name>.npy (float64): mae, every test prediction (a seeded sample beyond %d rows) and the neighbour "
+                    "lists of a seeded sample of users (one GPU)" % DUMP_MAX_PREDICTIONS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit(f"--steps must be >= 1 and --warmup >= 0 (got {args.steps}, {args.warmup})")
 
     import numpy as np
     import torch
@@ -230,9 +294,11 @@ def main():
         elapsed = float(tmax.item())
     step_ms = np.diff(np.array([t_start] + step_end)) * 1e3
     tm = eng.timings()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, kn, sharded, eng, dist, rank, world, device, tr, te, d_te, mae, n_pred)
 
     if rank == 0:
-        steps = max(1, args.steps)
+        steps = args.steps
         n_test = len(te)
         ms_per_step = elapsed / steps * 1e3
         gemm_launches = max(1, tm["gemm_launches"])          # ONE per neighbour build on the symmetric path, else one per row block
@@ -354,7 +420,7 @@ def main():
             "reference_published": {"value": 763.0, "unit": "predictions/s", "workload": "ml-100k u2 kNN k=300 (knn-100k.json:53-58)",
                                     "hardware": "unstated"},
         }
-        if world == 1 and not args.no_bf16_leg and not (args.engine_flags & 4):
+        if args.full and world == 1 and not args.no_bf16_leg and not (args.engine_flags & 4):
             # north_star says bf16 operands; the default is fp16 (same MFMA rate, 8x narrower error band, identical
             # results).  The bf16 number of the same build, outside the timed region (the fp16 handle is closed first: two
             # handles of this shape do not both fit the one-block configuration in 288 GB, and the leg should measure what a
@@ -378,7 +444,7 @@ def main():
                                   "note": "KNNCF_FLAG_BF16_FILTER (bf16 GEMM operands as north_star words it): same neighbours and MAE, "
                                           "wider error band -> longer shortlists -> more re-rank work"}
             eb.close()
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             one, all_cores = cpu_baseline(split, args.k, args.cpu_baseline_seconds, n_test)
             out["cpu_baseline"] = one
             if all_cores:

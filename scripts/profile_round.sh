@@ -6,7 +6,7 @@ TAG=${1:-rXX}
 R=$(pwd)
 O=$R/gpurun_out/$TAG
 mkdir -p $O
-timeout -k 10 300 python bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 300 python bench.py --full > $O/bench.json 2> $O/bench.err
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o $TAG -- python3 $R/bench.py --no-cpu-baseline --no-bf16-leg --steps 5 --warmup 2 > $O/bench_prof.json 2> $O/prof.err
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -o f -- python3 $R/bench.py --no-cpu-baseline --no-bf16-leg --steps 1 --warmup 1 > $O/pmc_fetch.json 2> $O/pmc_fetch.err

@@ -9,6 +9,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -20,8 +21,9 @@ def _line(out):
     return json.loads(out.strip().splitlines()[-1])
 
 
-def test_two_ranks_on_one_gpu_reproduce_the_single_process_line():
-    one = subprocess.run([sys.executable, "bench.py"] + WORKLOAD, cwd=ROOT, capture_output=True, text=True, timeout=600)
+def test_two_ranks_on_one_gpu_reproduce_the_single_process_line(tmp_path):
+    one = subprocess.run([sys.executable, "bench.py"] + WORKLOAD + ["--dump-outputs", str(tmp_path / "one")], cwd=ROOT,
+                         capture_output=True, text=True, timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
     a = _line(one.stdout)
     s = socket.socket()
@@ -29,14 +31,18 @@ def test_two_ranks_on_one_gpu_reproduce_the_single_process_line():
     port = s.getsockname()[1]
     s.close()
     two = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                          "--master-port", str(port), "bench.py", "--gpus", "2", "--backend", "gloo"] + WORKLOAD,
-                         cwd=ROOT, capture_output=True, text=True, timeout=900)
+                          "--master-port", str(port), "bench.py", "--gpus", "2", "--backend", "gloo"] + WORKLOAD
+                         + ["--dump-outputs", str(tmp_path / "two")], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert two.returncode == 0, two.stderr[-3000:]
     b = _line(two.stdout)
     assert (a["n_gpus"], b["n_gpus"]) == (1, 2) and b["steps"] == 2 and b["scaling"] == "strong"
     assert abs(a["mae"] - b["mae"]) <= 1e-12          # only the order of the final all-reduce differs
     assert b["value"] > 0 and "roofline" in b and b["config"]["parallelism"].endswith("x2")
     assert len([l for l in two.stdout.strip().splitlines() if l.startswith("{")]) == 1   # rank 0 alone prints the line
+    # every rank predicts its own users' rows: gathered, they are the single process's predictions bit for bit
+    p1, p2 = (np.load(os.path.join(tmp_path, d, "predictions.npy")) for d in ("one", "two"))
+    assert np.array_equal(p1.view(np.int64), p2.view(np.int64))
+    assert np.load(os.path.join(tmp_path, "two", "mae.npy"))[1] == np.load(os.path.join(tmp_path, "one", "mae.npy"))[1]
 
 
 def test_one_rank_nccl_process_group_runs_every_collective_of_the_multi_gpu_path():
