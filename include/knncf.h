@@ -160,6 +160,30 @@ int knncf_predict(knncf_handle* h, int predictor, int32_t user, int32_t item, do
 int knncf_recommend(knncf_handle* h, int predictor, int32_t user, int32_t n, int32_t* items,
                     double* predictions, int32_t* count);
 
+/* ---- fold-in queries: one user that is NOT in the fitted training set ------
+ * recommend/Recommender.scala:64-88 appends a person's ratings to the data (data.union(personal), :68) and asks for
+ * that person's recommendations.  These calls answer for such a query user `user` (a raw id absent from train) with
+ * ratings (items[j], ratings[j]), j < n_ratings, WITHOUT a refit: every result equals, bit for bit, the reference's on
+ * aug = train ++ [Rating(user, items[j], ratings[j]) for j in order] with fresh closures whose first evaluation is the
+ * query user's:
+ *   knncf_query_neighbors  getNeighbors(aug, k, sim)(user) :603-616 — min(k, U) entries, *count of them, the first
+ *                          min(cap, *count) written;
+ *   knncf_query_predict    predictor(aug, weightedSumDeviation(aug, getSimilarity(aug, k, sim)))(user, pred_items[j])
+ *                          :489-585 for any item id (rated by the user, unknown to train, ...);
+ *   knncf_query_recommend  recommendations(aug, that predictor)(user, n) :651-674.
+ * KNNCF_SIM_COSINE / KNNCF_SIM_JACCARD handles with predictor KNNCF_PRED_KNN, single shard, >= 5 train users, at most
+ * 65536 query ratings (KNNCF_E_UNSUPPORTED otherwise, also for a query whose mean rating is negative); KNNCF_E_STATE
+ * before a fit; KNNCF_E_INVALID if `user` occurs in train, a pointer is null or n_ratings <= 0; KNNCF_E_DUPLICATE if
+ * the query repeats an item; KNNCF_E_NONFINITE for a non-finite deviation (as knncf_fit).  Read-only on the handle:
+ * the neighbour table, its build history and everything knncf_neighbors / knncf_mae / knncf_neighbors_save observe
+ * stay as they were. */
+int knncf_query_neighbors(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
+                          int32_t cap, int32_t* ids, double* sims, int32_t* count);
+int knncf_query_predict(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
+                        int64_t n_ratings, const int32_t* pred_items, int64_t m, double* out);
+int knncf_query_recommend(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
+                          int64_t n_ratings, int32_t n, int32_t* out_items, double* out_preds, int32_t* count);
+
 /* ---- batch ---------------------------------------------------------------- */
 int knncf_predict_batch(knncf_handle* h, int predictor, const int32_t* users,
                         const int32_t* items, int64_t n, double* out);

@@ -70,6 +70,7 @@ struct knncf_handle {
     DArr<int32_t> reco_users, reco_items, reco_out_items;
     DArr<double> reco_pred, reco_out_preds;
     DArr<uint8_t> reco_rated;
+    QueryScratch query;  // fold-in queries (foldin.hip)
     DArr<int32_t> build_list, build_count;
     DArr<uint32_t> first_row;
     // test scratch
@@ -835,6 +836,78 @@ void do_recommend(knncf_handle* h, int predictor, int32_t user, int32_t n, int32
     *count = m;
 }
 
+// ---- fold-in queries: one user outside the fit (foldin.hip) -----------------------------------------------------------
+// Every answer is the reference's on aug = train ++ the query rows with fresh closures whose first evaluation is the
+// query user's.  Read-only on the handle: the neighbour table, its sequence numbers and epoch are not touched.
+constexpr int64_t QUERY_MAX_RATINGS = 65536;
+
+QueryInfo query_prepare(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
+                        int64_t n_ratings) {
+    require_fitted(h, false);
+    KN_REQUIRE(items && ratings && n_ratings > 0, KNNCF_E_INVALID, "query: null ratings or n_ratings <= 0");
+    KN_REQUIRE(predictor == KNNCF_PRED_KNN, KNNCF_E_UNSUPPORTED, "query: only KNNCF_PRED_KNN");
+    KN_REQUIRE(h->cfg.similarity != KNNCF_SIM_ONE, KNNCF_E_UNSUPPORTED, "query: adjusted cosine or Jaccard");
+    KN_REQUIRE(h->cfg.shard_count == 1, KNNCF_E_UNSUPPORTED, "query: single-shard handles only");
+    KN_REQUIRE(h->tr.U >= 5, KNNCF_E_UNSUPPORTED, "query: fewer than 5 train users (the user set changes iteration class)");
+    KN_REQUIRE(n_ratings <= QUERY_MAX_RATINGS, KNNCF_E_UNSUPPORTED, "query: more than 65536 ratings");
+    KN_REQUIRE(dense_user(h, user) < 0, KNNCF_E_INVALID, "query: the user occurs in the training set");
+    h->prep.join_commit(h->stream);
+    return foldin_neighbors(h->tr, h->query, h->prep.sort, user, items, ratings, (int32_t)n_ratings, h->cfg.k, h->stream);
+}
+
+void do_query_neighbors(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
+                        int32_t cap, int32_t* ids, double* sims, int32_t* count) {
+    KN_REQUIRE(count && cap >= 0 && (cap == 0 || (ids && sims)), KNNCF_E_INVALID, "bad output arguments");
+    const QueryInfo qi = query_prepare(h, KNNCF_PRED_KNN, user, items, ratings, n_ratings);
+    const int32_t c = std::min(qi.take, cap);
+    std::vector<int32_t> di(c);
+    if (c > 0) {
+        KN_HIP(hipMemcpyAsync(di.data(), h->query.nbr_idx.p, (size_t)c * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        KN_HIP(hipMemcpyAsync(sims, h->query.nbr_sim.p, (size_t)c * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        KN_HIP(hipStreamSynchronize(h->stream));
+    }
+    for (int32_t j = 0; j < c; ++j) ids[j] = h->h_uid[di[j]];
+    *count = qi.take;
+}
+
+void do_query_predict(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
+                      int64_t n_ratings, const int32_t* pred_items, int64_t m, double* out) {
+    KN_REQUIRE(m >= 0 && (m == 0 || (pred_items && out)), KNNCF_E_INVALID, "bad prediction arguments");
+    const QueryInfo qi = query_prepare(h, predictor, user, items, ratings, n_ratings);
+    if (m == 0) return;
+    hipStream_t st = h->stream;
+    QueryScratch& qs = h->query;
+    foldin_predictions(h->tr, qs, h->prep.sort, qi, st);
+    qs.pick_items.ensure(m); qs.pick_out.ensure(m);
+    KN_HIP(hipMemcpyAsync(qs.pick_items.p, pred_items, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    foldin_pick(h->tr, qs, qs.pick_items.p, m, qs.pick_out.p, st);
+    KN_HIP(hipMemcpyAsync(out, qs.pick_out.p, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
+    KN_HIP(hipStreamSynchronize(st));
+}
+
+// recommendations(aug, predictor)(q, n) :651-674: the train items q has not rated (the query's items unknown to train
+// are rated by q), ordered by reco.hip
+void do_query_recommend(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
+                        int64_t n_ratings, int32_t n, int32_t* out_items, double* out_preds, int32_t* count) {
+    KN_REQUIRE(count && n >= 0 && (n == 0 || (out_items && out_preds)), KNNCF_E_INVALID, "bad arguments");
+    *count = 0;
+    const QueryInfo qi = query_prepare(h, predictor, user, items, ratings, n_ratings);
+    Train& tr = h->tr;
+    const int32_t m = (int32_t)std::min<int64_t>(n, (int64_t)tr.I - qi.known);
+    if (m <= 0) return;
+    hipStream_t st = h->stream;
+    QueryScratch& qs = h->query;
+    foldin_predictions(tr, qs, h->prep.sort, qi, st);
+    qs.k64_a.ensure(tr.I); qs.k64_b.ensure(tr.I); qs.v32_a.ensure(tr.I); qs.v32_b.ensure(tr.I);
+    launch_reco_order(tr, h->prep.sort, qs.pred.p, qs.rated.p, qs.k64_a.p, qs.k64_b.p, qs.v32_a.p, qs.v32_b.p, st);
+    qs.out_items.ensure(m); qs.out_preds.ensure(m);
+    launch_reco_take(tr, m, qs.v32_b.p, qs.pred.p, qs.out_items.p, qs.out_preds.p, st);
+    KN_HIP(hipMemcpyAsync(out_items, qs.out_items.p, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    KN_HIP(hipMemcpyAsync(out_preds, qs.out_preds.p, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
+    KN_HIP(hipStreamSynchronize(st));
+    *count = m;
+}
+
 // ---- checkpoint / resume of the neighbour table ------------------------------------------------------
 struct NbrFileHeader {
     char magic[8];  // "KNNCFNB1"
@@ -1270,6 +1343,21 @@ int knncf_predict(knncf_handle* h, int predictor, int32_t user, int32_t item, do
 
 int knncf_recommend(knncf_handle* h, int predictor, int32_t user, int32_t n, int32_t* items, double* predictions, int32_t* count) {
     return guarded(h, [&] { do_recommend(h, predictor, user, n, items, predictions, count); });
+}
+
+int knncf_query_neighbors(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
+                          int32_t cap, int32_t* ids, double* sims, int32_t* count) {
+    return guarded(h, [&] { do_query_neighbors(h, user, items, ratings, n_ratings, cap, ids, sims, count); });
+}
+
+int knncf_query_predict(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
+                        int64_t n_ratings, const int32_t* pred_items, int64_t m, double* out) {
+    return guarded(h, [&] { do_query_predict(h, predictor, user, items, ratings, n_ratings, pred_items, m, out); });
+}
+
+int knncf_query_recommend(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
+                          int64_t n_ratings, int32_t n, int32_t* out_items, double* out_preds, int32_t* count) {
+    return guarded(h, [&] { do_query_recommend(h, predictor, user, items, ratings, n_ratings, n, out_items, out_preds, count); });
 }
 
 int knncf_neighbors_save(knncf_handle* h, const char* path) {

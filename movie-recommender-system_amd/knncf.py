@@ -115,7 +115,8 @@ EXPORTS = [
     "knncf_version", "knncf_status_string", "knncf_create", "knncf_destroy", "knncf_last_error",
     "knncf_fit", "knncf_fit_device", "knncf_num_users", "knncf_num_items", "knncf_global_avg",
     "knncf_user_avg", "knncf_item_avg", "knncf_item_avg_dev", "knncf_item_avg_dev_rdd", "knncf_similarity",
-    "knncf_knn_similarity", "knncf_neighbors", "knncf_neighbors_batch", "knncf_predict", "knncf_recommend", "knncf_predict_batch",
+    "knncf_knn_similarity", "knncf_neighbors", "knncf_neighbors_batch", "knncf_predict", "knncf_recommend",
+    "knncf_query_neighbors", "knncf_query_predict", "knncf_query_recommend", "knncf_predict_batch",
     "knncf_predict_batch_device", "knncf_mae", "knncf_mae_device", "knncf_shard_view_get",
     "knncf_shard_commit", "knncf_get_timings", "knncf_reset_timings", "knncf_reset_neighbors",
     "knncf_set_k", "knncf_load_file", "knncf_load_file_cached", "knncf_free_ratings", "knncf_load_personal", "knncf_free_personal", "knncf_neighbors_save", "knncf_neighbors_load",
@@ -194,6 +195,9 @@ def load_library():
     L.knncf_neighbors_batch.argtypes = [C.c_void_p, _i32p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p]
     L.knncf_predict.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int32, _f64p]
     L.knncf_recommend.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int32, _i32p, _f64p, C.POINTER(C.c_int32)]
+    L.knncf_query_neighbors.argtypes = [C.c_void_p, C.c_int32, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p]
+    L.knncf_query_predict.argtypes = [C.c_void_p, C.c_int, C.c_int32, _i32p, _f64p, C.c_int64, _i32p, C.c_int64, _f64p]
+    L.knncf_query_recommend.argtypes = [C.c_void_p, C.c_int, C.c_int32, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p]
     L.knncf_predict_batch.argtypes = [C.c_void_p, C.c_int, _i32p, _i32p, C.c_int64, _f64p]
     L.knncf_predict_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.knncf_mae.argtypes = [C.c_void_p, C.c_int, _i32p, _i32p, _f64p, C.c_int64, _f64p]
@@ -382,6 +386,65 @@ class Engine:
         c = C.c_int32()
         self._check(self._lib.knncf_recommend(self._h, predictor, user, n, ids.ctypes.data_as(_i32p),
                                               preds.ctypes.data_as(_f64p), C.byref(c)))
+        return ids[:c.value].copy(), preds[:c.value].copy()
+
+    # ---- fold-in queries: a user outside the fit (knncf_query_*) ---------------------------
+    @staticmethod
+    def _query_rows(user, items, ratings):
+        """validated (user, items, ratings) of a fold-in query: ValueError before any C call"""
+        if isinstance(user, (bool, np.bool_)) or not isinstance(user, (int, np.integer)) or not -2**31 <= int(user) < 2**31:
+            raise ValueError("user must be a 32-bit integer id")
+        it = np.asarray(items)
+        rt = np.asarray(ratings)
+        if it.ndim != 1 or rt.ndim != 1 or len(it) != len(rt):
+            raise ValueError("items and ratings must be 1-D and of the same length")
+        if len(it) == 0:
+            raise ValueError("a query needs at least one rating")
+        if it.dtype.kind not in "iu" or (len(it) and (it.min() < -2**31 or it.max() >= 2**31)):
+            raise ValueError("items must be 32-bit integer ids")
+        if rt.dtype.kind not in "iuf":
+            raise ValueError("ratings must be numbers")
+        return int(user), _i32(it), _f64(rt)
+
+    def neighbors_for(self, user, items, ratings, cap=None):
+        """getNeighbors(train ++ user's ratings, k, sim)(user) for a user outside the fit: (ids, sims)"""
+        q, it, rt = self._query_rows(user, items, ratings)
+        if cap is None:
+            cap = max(1, self.k)
+        if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or cap < 0:
+            raise ValueError("cap must be a non-negative integer")
+        cap = int(cap)
+        ids = np.empty(max(1, cap), dtype=np.int32)
+        sims = np.empty(max(1, cap), dtype=np.float64)
+        c = C.c_int32()
+        self._check(self._lib.knncf_query_neighbors(self._h, q, it.ctypes.data_as(_i32p), rt.ctypes.data_as(_f64p), len(it), cap,
+                                                    ids.ctypes.data_as(_i32p), sims.ctypes.data_as(_f64p), C.byref(c)))
+        m = min(c.value, cap)
+        return ids[:m].copy(), sims[:m].copy()
+
+    def predict_for(self, user, items, ratings, pred_items):
+        """kNN predictions (PRED_KNN) of a user outside the fit, given its ratings, for every id of pred_items"""
+        q, it, rt = self._query_rows(user, items, ratings)
+        pi = np.asarray(pred_items)
+        if pi.ndim != 1 or (len(pi) and pi.dtype.kind not in "iu"):
+            raise ValueError("pred_items must be a 1-D array of integer ids")
+        pi = _i32(pi)
+        out = np.empty(max(1, len(pi)), dtype=np.float64)
+        self._check(self._lib.knncf_query_predict(self._h, PRED_KNN, q, it.ctypes.data_as(_i32p), rt.ctypes.data_as(_f64p), len(it),
+                                                  pi.ctypes.data_as(_i32p), len(pi), out.ctypes.data_as(_f64p)))
+        return out[:len(pi)].copy()
+
+    def recommend_for(self, user, items, ratings, n):
+        """recommendations(train ++ user's ratings, kNN predictor)(user, n) for a user outside the fit: (item ids, predictions)"""
+        q, it, rt = self._query_rows(user, items, ratings)
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0 or n >= 2**31:
+            raise ValueError("n must be a non-negative 32-bit integer")
+        n = int(n)
+        ids = np.empty(max(1, n), dtype=np.int32)
+        preds = np.empty(max(1, n), dtype=np.float64)
+        c = C.c_int32()
+        self._check(self._lib.knncf_query_recommend(self._h, PRED_KNN, q, it.ctypes.data_as(_i32p), rt.ctypes.data_as(_f64p), len(it),
+                                                    n, ids.ctypes.data_as(_i32p), preds.ctypes.data_as(_f64p), C.byref(c)))
         return ids[:c.value].copy(), preds[:c.value].copy()
 
     # ---- batch -------------------------------------------------------------------------
