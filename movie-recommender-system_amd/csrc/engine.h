@@ -14,10 +14,7 @@ typedef __bf16 bf16_t;
 // columns of a similarity row that select.hip holds in LDS at a time (prep.hip tabulates the tile crossings)
 // provisional store of select.hip per similarity row: groups of 8 columns (36 B each); the capacity scales with k
 inline int32_t select_gcap(int32_t k) { return 8192 * (int32_t)((k + 511) / 512 > 1 ? (k + 511) / 512 : 1); }
-#ifndef KNNCF_TCOLS
-#define KNNCF_TCOLS 16384  // (A/B switch: 8192 = half-size tiles, three workgroups of k_tail_select per CU)
-#endif
-static constexpr int SELECT_TCOLS = KNNCF_TCOLS;  // <= 2^14: it_pack keeps the BYTE address of the column's LDS cell inside its tile in 16 bits
+static constexpr int SELECT_TCOLS = 16384;  // <= 2^14: it_pack keeps the BYTE address of the column's LDS cell inside its tile in 16 bits
 static_assert(SELECT_TCOLS <= 16384 && (SELECT_TCOLS & (SELECT_TCOLS - 1)) == 0, "it_pack: 16-bit cell byte address");
 
 // ---- sort_util.hip (stable LSD radix sort / sorted-unique, hand-written; K0 plumbing) ----
@@ -144,7 +141,7 @@ void launch_densify(const Train& tr, const int32_t* d_rows, int32_t row_begin, i
                     hipStream_t st);
 // colmap[item] = column of the dense head panel (popularity rank < H) or -1 (tail)
 void launch_colmap(const Train& tr, int32_t H, int32_t* d_colmap, hipStream_t st);
-// C[M][ldc] (fp32 or fp16) = A[M][K] * B[N][K]^T, 16-bit in / fp32 accumulate; M, N multiples of 128, K of 64
+// C[M][ldc] (fp32 or fp16) = A[M][K] * B[N][K]^T, 16-bit in / fp32 accumulate; M, N multiples of 256, K of 64
 // clamp: fp16 C entries are clamped to [-1, 1] before rounding (adjusted cosine: the exact value lies there); false for
 // the counting GEMM of the Jaccard path (counts <= 2048 are exact in fp16)
 void launch_gemm_nt(const bf16_t* A, const bf16_t* B, void* C, bool c_fp16, int64_t M, int64_t N, int64_t K,
@@ -152,9 +149,9 @@ void launch_gemm_nt(const bf16_t* A, const bf16_t* B, void* C, bool c_fp16, int6
 
 // the whole symmetric matrix at once: C[N][ldc] = B B^T computed on and above the diagonal (256 x 256 tiles in the order of
 // the tile list) and mirrored below it; the stored values are bit for bit those of launch_gemm_nt(B, B, ...)
-void gemm_sym_tile_list(int32_t n_tiles, std::vector<uint32_t>& out, int32_t group = 8);
+void gemm_sym_tile_list(int32_t n_tiles, std::vector<uint32_t>& out);
 void launch_gemm_sym(const bf16_t* B, void* C, bool c_fp16, int64_t N, int64_t K, int64_t ldb, int64_t ldc, bool fp16, bool clamp,
-                     const uint32_t* d_tile_list, int64_t n_listed, hipStream_t st, int tile = 256);
+                     const uint32_t* d_tile_list, int64_t n_listed, hipStream_t st);
 
 // ---- select.hip: K6 + K6b --------------------------------------------------------------
 struct NeighborTable {

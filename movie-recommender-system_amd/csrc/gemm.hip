@@ -7,16 +7,15 @@
 // The 16-bit result only has to be a FILTER: select.hip keeps every candidate within a rigorous
 // error band of the k-th value and the fp64 re-rank decides.
 //
-// Kernel structure: BK = 64, each wave owns a (WM*32) x 64 sub-tile of v_mfma_f32_32x32x16_{f16,bf16}
-// accumulators; 128x128 tile / 4 waves or 256x256 tile / 8 waves.  Operand tiles go
+// Kernel structure: BK = 64, 256x256 tile, 8 waves (2 x 4), each wave owns a 128 x 64 sub-tile of
+// v_mfma_f32_32x32x16_{f16,bf16} accumulators.  Two kernels: k_gemm_nt_ov for fp16 panels (the
+// tile's stores overlap the next tile's MFMA steps) and k_gemm_nt_bf16 for fp32 panels
+// (KNNCF_FLAG_F32_PANEL: a workgroup-wide epilogue at the tile's end).  Operand tiles go
 // HBM -> LDS by LDS-DMA (global_load_lds_dwordx4, 1 KiB per wave-instruction) into a 2-deep
 // ring; the LDS image is lane-linear as the DMA requires, with the bank swizzle applied on the
 // SOURCE address (16-B chunk c of row r sits in slot c ^ ((r >> 1) & 7), conflict-free for
 // ds_read_b128: the 16 lanes of a read group hit 16 distinct slots of the 256-B bank row).
 // Tile t+1 stays in flight across the barrier behind a counted vmcnt.
-#include <stdio.h>
-#include <stdlib.h>
-
 #include <algorithm>
 #include <type_traits>
 #include <vector>
@@ -136,10 +135,9 @@ void launch_colmap(const Train& tr, int32_t H, int32_t* d_colmap, hipStream_t st
 }
 
 // ---- GEMM --------------------------------------------------------------------------------
-// Tile configurations (BK = 64 for both; a wave always owns a WM*32 x 64 sub-tile):
-//   small: 128 x 128, 4 waves (2 x 2), WM = WN = 2, 64 KiB LDS, 2 workgroups per CU
-//   large: 256 x 256, 8 waves (2 x 4), WM = 4, WN = 2, 132 KiB LDS, 1 workgroup per CU — half the L2 -> LDS operand
-//          traffic per flop (at the MFMA peak the 128 x 128 tile asks the L2 for ~39 TB/s, more than it has)
+// One tile configuration for both kernels: 256 x 256, BK = 64, 8 waves (2 x 4), WM = 4, WN = 2 (a wave owns WM x WN
+// blocks of 32 x 32), 1 workgroup per CU — half the L2 -> LDS operand traffic per flop of a 128 x 128 tile (at the MFMA
+// peak that one asks the L2 for ~39 TB/s, more than it has)
 static constexpr int BK = 64;
 
 template <int ROWS>
@@ -174,20 +172,20 @@ __device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
-// LDS plan of the persistent kernel: [PAD][slot 0][slot 1][PAD]; a slot = one k-tile of A and of B.  The epilogue image
-// of a tile reuses the slot that was consumed last (the other one already receives the next tile's first k-tile) and
-// may spill into the PAD next to it.
-template <class OT, int WM, int WAVES_M, int TB>
+// k_gemm_nt_bf16's LDS plan: [PAD][slot 0][slot 1][PAD]; a slot = one k-tile of A and of B.  The epilogue image of a tile
+// reuses the slot that was consumed last (the other one already receives the next tile's first k-tile) and may spill into
+// the PAD next to it.  The panel is fp32.
 struct EpiGeom {
-    static constexpr int ESZ = (int)sizeof(OT);
-    static constexpr int IPP = ESZ == 2 ? WM : (WM >= 2 ? WM / 2 : 1);   // 32-row MFMA blocks of a wave per pass
+    static constexpr int WM = 4, WN = 2, WAVES_M = 2, WAVES_N = 4, TB = 256;
+    static constexpr int ESZ = (int)sizeof(float);
+    static constexpr int IPP = WM / 2;                                   // 32-row MFMA blocks of a wave per pass
     static constexpr int PASS_ROWS = IPP * 32;
     static constexpr int PASSES = WAVES_M * (WM / IPP);
     static constexpr int RS = TB * ESZ + 16;                             // LDS row stride of the image
     static constexpr int IMAGE_N = PASS_ROWS * RS;
     // symmetric launches also write the tile's mirror image: the pass's PASS_ROWS rows become PASS_ROWS columns of all TB
-    // rows of the transposed tile.  Row stride 272 B for both element sizes: the two 32-lane halves of a wave (columns c
-    // and c + 4 of the tile = rows 4 apart of this image) then sit 16 banks apart.
+    // rows of the transposed tile.  Row stride 272 B: the two 32-lane halves of a wave (columns c and c + 4 of the tile =
+    // rows 4 apart of this image) then sit 16 banks apart.
     static constexpr int RS_T = PASS_ROWS * ESZ + 16;
     static constexpr int IMAGE_T = TB * RS_T;
     static constexpr int IMAGE = IMAGE_N > IMAGE_T ? IMAGE_N : IMAGE_T;
@@ -206,17 +204,15 @@ struct EpiGeom {
 // the low 16 bits, tile column in the high 16); every off-diagonal tile is stored twice, as it is and mirrored — S is
 // symmetric and its mirror is the same sum of the same products in the same order, so the stored values are bit for bit
 // what the full-square launch stores, for half the MFMA work.
-template <bool F16, class OT, int WM, int WN, int WAVES_M, int WAVES_N, bool SYM>
-__global__ void __launch_bounds__(WAVES_M * WAVES_N * 64)
-k_gemm_nt_bf16(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, OT* __restrict__ C, int tiles_m,
-               int tiles_n, int k_tiles, int64_t lda, int64_t ldb, int64_t ldc, const uint32_t* __restrict__ tile_list, int n_listed,
-               float clamp_hi) {
-    constexpr int WAVES = WAVES_M * WAVES_N;
-    constexpr int TBM = WAVES_M * WM * 32, TBN = WAVES_N * WN * 32;
-    static_assert(TBM == TBN, "square block tiles: both operand tiles share one staging routine");
-    typedef EpiGeom<OT, WM, WAVES_M, TBM> EG;
-    constexpr int TILE_BYTES = TileGeom<TBM>::TILE_BYTES, STAGE_BYTES = TileGeom<TBM>::STAGE_BYTES;
-    constexpr int LOADS_PER_STAGE = 2 * (TBM / 8 / WAVES);  // LDS-DMA instructions per wave per stage
+template <bool F16, bool SYM>
+__global__ void __launch_bounds__(EpiGeom::WAVES_M * EpiGeom::WAVES_N * 64)
+k_gemm_nt_bf16(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, float* __restrict__ C, int tiles_m,
+               int tiles_n, int k_tiles, int64_t lda, int64_t ldb, int64_t ldc, const uint32_t* __restrict__ tile_list, int n_listed) {
+    typedef EpiGeom EG;
+    constexpr int WM = EG::WM, WN = EG::WN, WAVES_N = EG::WAVES_N, WAVES = EG::WAVES_M * EG::WAVES_N, TB = EG::TB;
+    constexpr int TILE_BYTES = TileGeom<TB>::TILE_BYTES, STAGE_BYTES = TileGeom<TB>::STAGE_BYTES;
+    constexpr int LOADS_PER_STAGE = 2 * (TB / 8 / WAVES);  // LDS-DMA instructions per wave per stage
+    static_assert(LOADS_PER_STAGE == 8, "the counted vmcnt below assumes 8 LDS-DMA instructions per wave per stage");
     extern __shared__ __attribute__((aligned(1024))) char lds[];
     char* const ring = lds + EG::PAD;
 
@@ -256,10 +252,10 @@ k_gemm_nt_bf16(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, OT* _
 
     int tm, tn;
     tile_of(t, tm, tn);
-    const bf16_t* Ag = A + (int64_t)tm * TBM * lda;
-    const bf16_t* Bg = B + (int64_t)tn * TBN * ldb;
-    stage_tile<TBM, WAVES>(Ag, lda, ring, wave, lane);
-    stage_tile<TBN, WAVES>(Bg, ldb, ring + TILE_BYTES, wave, lane);
+    const bf16_t* Ag = A + (int64_t)tm * TB * lda;
+    const bf16_t* Bg = B + (int64_t)tn * TB * ldb;
+    stage_tile<TB, WAVES>(Ag, lda, ring, wave, lane);
+    stage_tile<TB, WAVES>(Bg, ldb, ring + TILE_BYTES, wave, lane);
     int slot = 0;
     bool landed = false;  // the current slot's k-tile was already waited for (at the previous tile's epilogue)
 
@@ -268,8 +264,8 @@ k_gemm_nt_bf16(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, OT* _
         const bool more = t_next < xcd_end;
         int tm2 = 0, tn2 = 0;
         if (more) tile_of(t_next, tm2, tn2);
-        const bf16_t* Ag2 = A + (int64_t)tm2 * TBM * lda;
-        const bf16_t* Bg2 = B + (int64_t)tn2 * TBN * ldb;
+        const bf16_t* Ag2 = A + (int64_t)tm2 * TB * lda;
+        const bf16_t* Bg2 = B + (int64_t)tn2 * TB * ldb;
 
         f32x16 acc[WM][WN];
 #pragma unroll
@@ -284,23 +280,17 @@ k_gemm_nt_bf16(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, OT* _
             char* nxt = ring + (slot ^ 1) * STAGE_BYTES;
             const bool in_tile = kt + 1 < k_tiles;
             if (in_tile) {
-                stage_tile<TBM, WAVES>(Ag + (int64_t)(kt + 1) * BK, lda, nxt, wave, lane);
-                stage_tile<TBN, WAVES>(Bg + (int64_t)(kt + 1) * BK, ldb, nxt + TILE_BYTES, wave, lane);
+                stage_tile<TB, WAVES>(Ag + (int64_t)(kt + 1) * BK, lda, nxt, wave, lane);
+                stage_tile<TB, WAVES>(Bg + (int64_t)(kt + 1) * BK, ldb, nxt + TILE_BYTES, wave, lane);
             } else if (more) {
-                stage_tile<TBM, WAVES>(Ag2, lda, nxt, wave, lane);
-                stage_tile<TBN, WAVES>(Bg2, ldb, nxt + TILE_BYTES, wave, lane);
+                stage_tile<TB, WAVES>(Ag2, lda, nxt, wave, lane);
+                stage_tile<TB, WAVES>(Bg2, ldb, nxt + TILE_BYTES, wave, lane);
             }
             if (!landed) {
                 // k-tile `cur` landed; the one just issued (LOADS_PER_STAGE DMAs of this wave) stays in flight across
                 // the barrier.  (vmcnt also counts the previous tile's stores, all older than the DMAs waited for.)
-                static_assert(LOADS_PER_STAGE == 4 || LOADS_PER_STAGE == 8 || LOADS_PER_STAGE == 16, "the counted vmcnt below assumes 4, 8 or 16 LDS-DMA instructions per wave per stage");
-                if (in_tile || more) {
-                    if (LOADS_PER_STAGE == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                    else if (LOADS_PER_STAGE == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-                    else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-                } else {
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                }
+                if (in_tile || more) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
             landed = false;
             __builtin_amdgcn_s_barrier();
@@ -329,16 +319,16 @@ k_gemm_nt_bf16(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, OT* _
         // ---- epilogue: through LDS, so that C leaves in full 16-byte pieces of contiguous rows ----------------
         // D layout of v_mfma_f32_32x32x16 with the operands swapped: lane (frow, fhalf) holds row frow of the 32 x 32
         // block, register e holds column (e & 3) + 8 (e >> 2) + 4 fhalf: four groups of 4 consecutive columns.  Each
-        // group is converted and written to an LDS image of PASS_ROWS rows of the tile ([row][col], rows padded by
-        // 16 B); then every thread copies 16-byte pieces of rows to global memory (one wave instruction = 1 KiB of
-        // contiguous C).  Storing the accumulators directly costs one 2-byte store per element: 1024 wave-wide store
-        // instructions per 256 x 256 tile, as long as the tile's MFMA work.
+        // group is written to an LDS image of PASS_ROWS rows of the tile ([row][col], rows padded by 16 B); then every
+        // thread copies 16-byte pieces of rows to global memory (one wave instruction = 1 KiB of contiguous C).  Storing
+        // the accumulators directly costs one store per element: 1024 wave-wide store instructions per 256 x 256 tile of
+        // an fp16 panel, as long as the tile's MFMA work.
         {
             // the next tile's first k-tile (issued one MFMA step ago) lands before any store is queued behind it
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             landed = more;
             constexpr int ESZ = EG::ESZ, RS = EG::RS, IPP = EG::IPP, PASS_ROWS = EG::PASS_ROWS, PASSES = EG::PASSES;
-            constexpr int CH = TBN * ESZ / 16;                              // 16-byte pieces per row
+            constexpr int CH = TB * ESZ / 16;                              // 16-byte pieces per row
             // the consumed slot is slot ^ 1; its image may extend into the PAD on its outer side
             char* const img = (slot ^ 1) ? ring + STAGE_BYTES : lds;
 #pragma unroll
@@ -353,19 +343,11 @@ k_gemm_nt_bf16(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, OT* _
                             for (int g = 0; g < 4; ++g) {
                                 const int i = i0 + ii;
                                 char* dst = img + (ii * 32 + frow) * RS + (wc * (WN * 32) + j * 32 + 8 * g + 4 * fhalf) * ESZ;
-                                if (ESZ == 2) {
-                                    typedef __attribute__((ext_vector_type(4))) _Float16 h4;
-                                    h4 v;
-#pragma unroll
-                                    for (int e = 0; e < 4; ++e) v[e] = (_Float16)fminf(fmaxf(acc[i][j][4 * g + e], -clamp_hi), clamp_hi);  // (1.0: see api.cpp eps_rest; 65504 for counts)
-                                    *reinterpret_cast<h4*>(dst) = v;
-                                } else {
-                                    *reinterpret_cast<float4*>(dst) = make_float4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]);
-                                }
+                                *reinterpret_cast<float4*>(dst) = make_float4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]);
                             }
                 }
                 __syncthreads();
-                OT* Cg = C + ((int64_t)tm * TBM + wrp * (WM * 32) + i0 * 32) * ldc + (int64_t)tn * TBN;
+                float* Cg = C + ((int64_t)tm * TB + wrp * (WM * 32) + i0 * 32) * ldc + (int64_t)tn * TB;
                 for (int idx = threadIdx.x; idx < PASS_ROWS * CH; idx += WAVES * 64) {
                     const int row = idx / CH, ch = idx - row * CH;
                     const uint4 v = *reinterpret_cast<const uint4*>(img + row * RS + ch * 16);
@@ -391,14 +373,13 @@ k_gemm_nt_bf16(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, OT* _
                                     for (int e = 0; e < 4; ++e) {
                                         const int i = i0 + ii;
                                         const int col = wc * (WN * 32) + j * 32 + 8 * g + 4 * fhalf + e;
-                                        OT* dst = reinterpret_cast<OT*>(img + col * RS_T) + (ii * 32 + frow);
-                                        if (ESZ == 2) *dst = (OT)fminf(fmaxf(acc[i][j][4 * g + e], -clamp_hi), clamp_hi);
-                                        else *dst = (OT)acc[i][j][4 * g + e];
+                                        float* dst = reinterpret_cast<float*>(img + col * RS_T) + (ii * 32 + frow);
+                                        *dst = acc[i][j][4 * g + e];
                                     }
                     }
                     __syncthreads();
-                    OT* Ct = C + (int64_t)tn * TBN * ldc + (int64_t)tm * TBM + wrp * (WM * 32) + i0 * 32;
-                    for (int idx = threadIdx.x; idx < TBN * CHT; idx += WAVES * 64) {
+                    float* Ct = C + (int64_t)tn * TB * ldc + (int64_t)tm * TB + wrp * (WM * 32) + i0 * 32;
+                    for (int idx = threadIdx.x; idx < TB * CHT; idx += WAVES * 64) {
                         const int row = idx / CHT, ch = idx - row * CHT;
                         const uint4 v = *reinterpret_cast<const uint4*>(img + row * RS_T + ch * 16);
                         typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
@@ -453,14 +434,10 @@ __device__ __forceinline__ void stage_tile_u(const bf16_t* g_uniform, uint32_t l
 #define KN_OV_STORE
 #define KN_OV_STORES 4
 #endif
-#define KN_OV_POLICY "nt"  // (measured at H = 384: nt 14.3 ms per launch, plain stores and sc1 17.9 ms)
-#ifndef KN_OV_POLICY
-#define KN_OV_POLICY "nt"  // (A/B switch: -DKN_OV_POLICY='""' plain, '"sc1"' write-through)
-#endif
 // ---- the overlapped form (fp16 panel, 256 x 256 tiles) ---------------------------------------------------------------
-// k_gemm_nt_bf16 above ADDS a tile's stores to its MFMA work: every store of the epilogue is queued in front of the next
-// tile's operand loads, and on gfx9 vmcnt counts loads and stores together and retires them in order, so the counted wait
-// for the second k-tile of the next tile also waits for every store of this one.  At K = 384 that is ~5 us of MFMA steps
+// An epilogue at the tile's end (k_gemm_nt_bf16 above) ADDS a tile's stores to its MFMA work: every store of the epilogue
+// is queued in front of the next tile's operand loads, and on gfx9 vmcnt counts loads and stores together and retires them
+// in order, so the counted wait for the second k-tile of the next tile also waits for every store of this one.  At K = 384 that is ~5 us of MFMA steps
 // plus ~10 us of stores (256 KB per off-diagonal tile at the CU's share of the HBM write rate) per tile.
 //
 // Here the finished tile does not leave through a workgroup-wide epilogue at all.  Its accumulators are converted to
@@ -474,8 +451,9 @@ __device__ __forceinline__ void stage_tile_u(const bf16_t* g_uniform, uint32_t l
 //                  transposed image, 4 global stores of 16 rows x 64 contiguous bytes, into tile (tn, tm).
 // The stores are spread evenly over the k-steps and the counted waits allow the stores of the previous k-step to stay
 // in flight (vmcnt(loads of the next stage + stores issued since)): the launch takes max(MFMA, stores) per tile instead
-// of their sum.  LDS: the 128 KiB operand ring + 8 x 4 KiB = all 160 KiB.  The stored values are bit for bit those of
-// k_gemm_nt_bf16 (same MFMA order, same clamp, same round-to-nearest-even conversion).
+// of their sum.  LDS: the 128 KiB operand ring + 8 x 4 KiB = all 160 KiB.  The stored values are k_gemm_nt_bf16's fp32
+// sums (same MFMA order) clamped to [-clamp_hi, clamp_hi] and rounded to the nearest even fp16.
+// The global stores are non-temporal ("nt"; measured at H = 384: 14.3 ms per launch, plain stores and sc1 17.9 ms).
 template <bool F16, bool SYM, bool SPREAD>
 __global__ void __launch_bounds__(512)
 k_gemm_nt_ov(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, _Float16* __restrict__ C, int tiles_m, int tiles_n,
@@ -526,7 +504,6 @@ k_gemm_nt_ov(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, _Float1
 
     typedef __attribute__((ext_vector_type(2))) _Float16 h2;
     typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-    typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
     // the previous tile, converted: P[i][j][2 g + h] = columns 8 g + 4 fhalf + 2 h, + 1 of block (i, j), row frow
     // the wave's row blocks 2 and 3 wait in P (32 registers) and leave under the next tile; blocks 0 and 1 leave at the tile's end
     constexpr int NP = 2, UNITS = 4;
@@ -538,8 +515,8 @@ k_gemm_nt_ov(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, _Float1
 #pragma unroll
             for (int h = 0; h < 8; ++h) P[i][j][h] = 0u;
     // Register plan (2 waves per SIMD: 256 registers each, one unified file on gfx950): the 128 accumulators of the running
-    // tile in the ACCUMULATION half, P + one fragment set + the addressing in the 128 architectural registers.  hipcc puts
-    // MFMA results into accumulation registers only when the kernel is known to use them; this (empty) statement says so.
+    // tile, P, one fragment set and the addressing.  hipcc allocates all of them as architectural VGPRs (the code object
+    // reports 220 - 227 VGPRs and agpr_count 0); nothing spills.
     int ptm = 0, ptn = 0;
     int unit = 1000;  // next unit of the previous tile to drain (>= UNITS: none left)
 
@@ -585,10 +562,10 @@ k_gemm_nt_ov(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, _Float1
                 "ds_read_b128 %[q1], %[lr] offset:1024\n\t"
                 "ds_read_b128 %[q2], %[lr] offset:2048\n\t"
                 "ds_read_b128 %[q3], %[lr] offset:3072\n\t"
-                "s_waitcnt lgkmcnt(3)\n\t" KN_OV_STORE "buffer_store_dwordx4 %[q0], %[vo], %[rs], %[so0] offen " KN_OV_POLICY "\n\t"
-                "s_waitcnt lgkmcnt(2)\n\t" KN_OV_STORE "buffer_store_dwordx4 %[q1], %[vo], %[rs], %[so1] offen " KN_OV_POLICY "\n\t"
-                "s_waitcnt lgkmcnt(1)\n\t" KN_OV_STORE "buffer_store_dwordx4 %[q2], %[vo], %[rs], %[so2] offen " KN_OV_POLICY "\n\t"
-                "s_waitcnt lgkmcnt(0)\n\t" KN_OV_STORE "buffer_store_dwordx4 %[q3], %[vo], %[rs], %[so3] offen " KN_OV_POLICY "\n\t"
+                "s_waitcnt lgkmcnt(3)\n\t" KN_OV_STORE "buffer_store_dwordx4 %[q0], %[vo], %[rs], %[so0] offen nt\n\t"
+                "s_waitcnt lgkmcnt(2)\n\t" KN_OV_STORE "buffer_store_dwordx4 %[q1], %[vo], %[rs], %[so1] offen nt\n\t"
+                "s_waitcnt lgkmcnt(1)\n\t" KN_OV_STORE "buffer_store_dwordx4 %[q2], %[vo], %[rs], %[so2] offen nt\n\t"
+                "s_waitcnt lgkmcnt(0)\n\t" KN_OV_STORE "buffer_store_dwordx4 %[q3], %[vo], %[rs], %[so3] offen nt\n\t"
                 "s_nop 1"
             : [t] "=&v"(tmp_a), [q0] "=&v"(q0), [q1] "=&v"(q1), [q2] "=&v"(q2), [q3] "=&v"(q3)
             : [aw] "v"(aw_n), [lr] "v"(lra_n), [vo] "v"(vo_n), [rs] "s"(rs), [so0] "s"(0u), [so1] "s"(so_1), [so2] "s"(2u * so_1), [so3] "s"(3u * so_1),
@@ -624,10 +601,10 @@ k_gemm_nt_ov(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, _Float1
                 "ds_read_b128 %[q1], %[lr] offset:1024\n\t"
                 "ds_read_b128 %[q2], %[lr] offset:2048\n\t"
                 "ds_read_b128 %[q3], %[lr] offset:3072\n\t"
-                "s_waitcnt lgkmcnt(3)\n\t" KN_OV_STORE "buffer_store_dwordx4 %[q0], %[vo], %[rs], %[so0] offen " KN_OV_POLICY "\n\t"
-                "s_waitcnt lgkmcnt(2)\n\t" KN_OV_STORE "buffer_store_dwordx4 %[q1], %[vo], %[rs], %[so1] offen " KN_OV_POLICY "\n\t"
-                "s_waitcnt lgkmcnt(1)\n\t" KN_OV_STORE "buffer_store_dwordx4 %[q2], %[vo], %[rs], %[so2] offen " KN_OV_POLICY "\n\t"
-                "s_waitcnt lgkmcnt(0)\n\t" KN_OV_STORE "buffer_store_dwordx4 %[q3], %[vo], %[rs], %[so3] offen " KN_OV_POLICY "\n\t"
+                "s_waitcnt lgkmcnt(3)\n\t" KN_OV_STORE "buffer_store_dwordx4 %[q0], %[vo], %[rs], %[so0] offen nt\n\t"
+                "s_waitcnt lgkmcnt(2)\n\t" KN_OV_STORE "buffer_store_dwordx4 %[q1], %[vo], %[rs], %[so1] offen nt\n\t"
+                "s_waitcnt lgkmcnt(1)\n\t" KN_OV_STORE "buffer_store_dwordx4 %[q2], %[vo], %[rs], %[so2] offen nt\n\t"
+                "s_waitcnt lgkmcnt(0)\n\t" KN_OV_STORE "buffer_store_dwordx4 %[q3], %[vo], %[rs], %[so3] offen nt\n\t"
                 "s_nop 1"
             : [q0] "=&v"(q0), [q1] "=&v"(q1), [q2] "=&v"(q2), [q3] "=&v"(q3)
             : [aw] "v"(aw_m), [lr] "v"(lra_t), [vo] "v"(vo_n), [rs] "s"(rs), [so0] "s"(0u), [so1] "s"(so_1), [so2] "s"(2u * so_1), [so3] "s"(3u * so_1),
@@ -779,8 +756,8 @@ k_gemm_nt_ov(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, _Float1
         }
         ptm = tm;
         ptn = tn;
-        // this tile -> fp16 (clamp, round to nearest even: the values k_gemm_nt_bf16 stores).  Row blocks 0 and 1 leave right
-        // away (16 stores: they drain under the next tile's first two k-steps), blocks 2 and 3 wait in P
+        // this tile -> fp16 (clamp, round to nearest even).  Row blocks 0 and 1 leave right away (16 stores: they drain under
+        // the next tile's first two k-steps), blocks 2 and 3 wait in P
         auto convert = [&](uint32_t (&R)[WN][8], auto I_) {
             constexpr int I = decltype(I_)::value;
 #pragma unroll
@@ -789,7 +766,7 @@ k_gemm_nt_ov(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, _Float1
                 for (int h = 0; h < 8; ++h) {
                     h2 v;
                     // (v_med3_f32: one instruction per value where fminf(fmaxf()) costs three — its operands are canonicalised
-                    // for NaNs first; no NaN can occur here, so the clamp is the one k_gemm_nt_bf16 applies)
+                    // for NaNs first; no NaN can occur here, so the result is that of fminf(fmaxf()))
                     v[0] = (_Float16)__builtin_amdgcn_fmed3f(acc[I][j][2 * h], -clamp_hi, clamp_hi);
                     v[1] = (_Float16)__builtin_amdgcn_fmed3f(acc[I][j][2 * h + 1], -clamp_hi, clamp_hi);
                     R[j][h] = __builtin_bit_cast(uint32_t, v);
@@ -845,154 +822,64 @@ static void launch_gemm_ov_t(const bf16_t* A, const bf16_t* B, _Float16* C, int6
 template <bool F16, bool SYM>
 static void launch_gemm_ov(const bf16_t* A, const bf16_t* B, _Float16* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
                            int64_t ldc, const uint32_t* tile_list, int64_t n_listed, bool clamp, hipStream_t st) {
-    static const bool no_spread = getenv("KNNCF_GEMM_NO_SPREAD") != nullptr;  // A/B switch for measurements
-    if (K / BK >= 6 && !no_spread) launch_gemm_ov_t<F16, SYM, true>(A, B, C, M, N, K, lda, ldb, ldc, tile_list, n_listed, clamp, st);
+    if (K / BK >= 6) launch_gemm_ov_t<F16, SYM, true>(A, B, C, M, N, K, lda, ldb, ldc, tile_list, n_listed, clamp, st);
     else launch_gemm_ov_t<F16, SYM, false>(A, B, C, M, N, K, lda, ldb, ldc, tile_list, n_listed, clamp, st);
 }
 
-// (A/B switch for measurements: KNNCF_GEMM_NO_OVERLAP=1 takes the epilogue-at-the-end kernel for fp16 panels too)
-static bool gemm_overlap_enabled() {
-    static const bool off = getenv("KNNCF_GEMM_NO_OVERLAP") != nullptr;
-    return !off;
-}
-
-template <bool F16, class OT, int WM, int WN, int WAVES_M, int WAVES_N, bool SYM>
-static void launch_gemm_cfg(const bf16_t* A, const bf16_t* B, OT* C, int64_t M, int64_t N, int64_t K, int64_t lda,
-                            int64_t ldb, int64_t ldc, const uint32_t* tile_list, int64_t n_listed, bool clamp, hipStream_t st) {
-    constexpr int TB = WAVES_M * WM * 32;
-    constexpr int SMEM = EpiGeom<OT, WM, WAVES_M, TB>::SMEM;
+template <bool F16, bool SYM>
+static void launch_gemm_f32(const bf16_t* A, const bf16_t* B, float* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
+                            int64_t ldc, const uint32_t* tile_list, int64_t n_listed, hipStream_t st) {
+    constexpr int TB = EpiGeom::TB, THREADS = EpiGeom::WAVES_M * EpiGeom::WAVES_N * 64, SMEM = EpiGeom::SMEM;
     static_assert(SMEM <= 160 * 1024, "gemm: LDS plan exceeds the CU's 160 KiB");
     const int64_t tiles = SYM ? n_listed : (M / TB) * (N / TB);
     KN_REQUIRE(tiles > 0 && tiles < (1ll << 31), KNNCF_E_INVALID, "gemm: grid too large");
     // resident workgroups of this kernel on the CURRENT device (dynamic-LDS attribute, CU count, occupancy): per device
     static PerDeviceState state;
     const int64_t slots = (int64_t)per_device_at_least(state, 1, [&](size_t) {
-        KN_HIP(hipFuncSetAttribute((const void*)k_gemm_nt_bf16<F16, OT, WM, WN, WAVES_M, WAVES_N, SYM>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
+        KN_HIP(hipFuncSetAttribute((const void*)k_gemm_nt_bf16<F16, SYM>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
         int dev = 0, cus = 0, per_cu = 0;
         KN_HIP(hipGetDevice(&dev));
         KN_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        KN_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_gemm_nt_bf16<F16, OT, WM, WN, WAVES_M, WAVES_N, SYM>,
-                                                            WAVES_M * WAVES_N * 64, SMEM));
+        KN_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_gemm_nt_bf16<F16, SYM>, THREADS, SMEM));
         return (size_t)std::max(1, cus * (per_cu > 0 ? per_cu : 1));
     });
     const unsigned grid = (unsigned)(tiles < slots ? tiles : slots);
-    k_gemm_nt_bf16<F16, OT, WM, WN, WAVES_M, WAVES_N, SYM><<<grid, WAVES_M * WAVES_N * 64, SMEM, st>>>(
-        A, B, C, (int)(M / TB), (int)(N / TB), (int)(K / BK), lda, ldb, ldc, tile_list, (int)n_listed, clamp ? 1.0f : 65504.0f);
+    k_gemm_nt_bf16<F16, SYM><<<grid, THREADS, SMEM, st>>>(A, B, C, (int)(M / TB), (int)(N / TB), (int)(K / BK), lda, ldb, ldc, tile_list,
+                                                          (int)n_listed);
     KN_HIP(hipGetLastError());
 }
 
-template <bool F16, class OT>
-static void launch_gemm_t(const bf16_t* A, const bf16_t* B, OT* C, int64_t M, int64_t N, int64_t K, int64_t lda,
-                          int64_t ldb, int64_t ldc, bool clamp, hipStream_t st) {
-    // (a 4-wave variant of the large tile, each wave a 128 x 128 sub-tile in 256 accumulator registers — a third
-    // less LDS read traffic per flop — measured the same: 30.6 vs 30.7 ms at K = 448, 52.8 vs 51.9 ms at K = 1024)
-    static const bool force_small = getenv("KNNCF_GEMM_TILE128") != nullptr;  // A/B switch for measurements
-    // (16 waves on the 256 x 256 tile, each a 64 x 64 sub-tile, 4 waves per SIMD: 8.3 vs 6.9 ms per launch at K = 256)
-    if (M % 256 == 0 && N % 256 == 0 && !force_small) launch_gemm_cfg<F16, OT, 4, 2, 2, 4, false>(A, B, C, M, N, K, lda, ldb, ldc, nullptr, 0, clamp, st);
-    else launch_gemm_cfg<F16, OT, 2, 2, 2, 2, false>(A, B, C, M, N, K, lda, ldb, ldc, nullptr, 0, clamp, st);
-}
-
-// C is fp16 (c_fp16) or fp32; operands fp16 (fp16) or bf16.  M, N multiples of 128 (256 selects the large tile)
+// C is fp16 (c_fp16: k_gemm_nt_ov) or fp32 (k_gemm_nt_bf16); operands fp16 (fp16) or bf16.  M, N multiples of 256
 void launch_gemm_nt(const bf16_t* A, const bf16_t* B, void* C, bool c_fp16, int64_t M, int64_t N, int64_t K, int64_t lda,
                     int64_t ldb, int64_t ldc, bool fp16, bool clamp, hipStream_t st) {
-    KN_REQUIRE(M % 128 == 0 && N % 128 == 0 && K % BK == 0 && K > 0, KNNCF_E_INVALID, "gemm: shape not tile-aligned");
+    KN_REQUIRE(M % 256 == 0 && N % 256 == 0 && K % BK == 0 && K > 0, KNNCF_E_INVALID, "gemm: shape not tile-aligned");
     KN_REQUIRE(lda % 8 == 0 && ldb % 8 == 0, KNNCF_E_INVALID, "gemm: leading dimensions must be multiples of 8");
-    static const bool force_small = getenv("KNNCF_GEMM_TILE128") != nullptr;
-    if (c_fp16 && M % 256 == 0 && N % 256 == 0 && !force_small && gemm_overlap_enabled()) {
-        if (fp16) launch_gemm_ov<true, false>(A, B, static_cast<_Float16*>(C), M, N, K, lda, ldb, ldc, nullptr, 0, clamp, st);
-        else launch_gemm_ov<false, false>(A, B, static_cast<_Float16*>(C), M, N, K, lda, ldb, ldc, nullptr, 0, clamp, st);
-        return;
-    }
-    if (fp16 && c_fp16) launch_gemm_t<true, _Float16>(A, B, static_cast<_Float16*>(C), M, N, K, lda, ldb, ldc, clamp, st);
-    else if (fp16) launch_gemm_t<true, float>(A, B, static_cast<float*>(C), M, N, K, lda, ldb, ldc, clamp, st);
-    else if (c_fp16) launch_gemm_t<false, _Float16>(A, B, static_cast<_Float16*>(C), M, N, K, lda, ldb, ldc, clamp, st);
-    else launch_gemm_t<false, float>(A, B, static_cast<float*>(C), M, N, K, lda, ldb, ldc, clamp, st);
+    if (c_fp16 && fp16) launch_gemm_ov<true, false>(A, B, static_cast<_Float16*>(C), M, N, K, lda, ldb, ldc, nullptr, 0, clamp, st);
+    else if (c_fp16) launch_gemm_ov<false, false>(A, B, static_cast<_Float16*>(C), M, N, K, lda, ldb, ldc, nullptr, 0, clamp, st);
+    else if (fp16) launch_gemm_f32<true, false>(A, B, static_cast<float*>(C), M, N, K, lda, ldb, ldc, nullptr, 0, st);
+    else launch_gemm_f32<false, false>(A, B, static_cast<float*>(C), M, N, K, lda, ldb, ldc, nullptr, 0, st);
 }
 
 // the 256 x 256 tiles on and above the diagonal of an n_tiles x n_tiles grid, 8 tile rows at a time and column by
 // column inside such a group (the group's operand rows stay in the L2 while its columns stream): tile row | column << 16
-void gemm_sym_tile_list(int32_t n_tiles, std::vector<uint32_t>& out, int32_t group) {
+void gemm_sym_tile_list(int32_t n_tiles, std::vector<uint32_t>& out) {
+    constexpr int32_t GROUP = 8;
     out.clear();
     out.reserve((size_t)n_tiles * (n_tiles + 1) / 2);
-    for (int32_t g = 0; g < n_tiles; g += group)
+    for (int32_t g = 0; g < n_tiles; g += GROUP)
         for (int32_t tn = g; tn < n_tiles; ++tn)
-            for (int32_t tm = g; tm < std::min(g + group, n_tiles) && tm <= tn; ++tm) out.push_back((uint32_t)tm | ((uint32_t)tn << 16));
+            for (int32_t tm = g; tm < std::min(g + GROUP, n_tiles) && tm <= tn; ++tm) out.push_back((uint32_t)tm | ((uint32_t)tn << 16));
 }
 
-// S[N x N] = B B^T for all N rows at once, N a multiple of 256, computed on and above the diagonal and mirrored
-// (fp16 panel storage only: the path that holds the whole similarity matrix)
+// S[N x N] = B B^T for all N rows at once, N a multiple of 256, computed on and above the diagonal and mirrored (the path
+// that holds the whole similarity matrix)
 void launch_gemm_sym(const bf16_t* B, void* C, bool c_fp16, int64_t N, int64_t K, int64_t ldb, int64_t ldc, bool fp16, bool clamp,
-                     const uint32_t* d_tile_list, int64_t n_listed, hipStream_t st, int tile) {
+                     const uint32_t* d_tile_list, int64_t n_listed, hipStream_t st) {
     KN_REQUIRE(N % 256 == 0 && N / 128 < 65536 && K % BK == 0 && K > 0 && ldb % 8 == 0 && ldc % 8 == 0, KNNCF_E_INVALID, "symmetric gemm: shape not tile-aligned");
-    if (tile == 128) {  // two workgroups per CU: one's stores run under the other's MFMA steps
-        KN_REQUIRE(fp16 && c_fp16, KNNCF_E_INVALID, "symmetric gemm: the 128-tile form is built for fp16 operands and panel");
-        launch_gemm_cfg<true, _Float16, 2, 2, 2, 2, true>(B, B, static_cast<_Float16*>(C), N, N, K, ldb, ldb, ldc, d_tile_list, n_listed, clamp, st);
-        return;
-    }
-    if (c_fp16 && gemm_overlap_enabled()) {
-        if (fp16) launch_gemm_ov<true, true>(B, B, static_cast<_Float16*>(C), N, N, K, ldb, ldb, ldc, d_tile_list, n_listed, clamp, st);
-        else launch_gemm_ov<false, true>(B, B, static_cast<_Float16*>(C), N, N, K, ldb, ldb, ldc, d_tile_list, n_listed, clamp, st);
-        return;
-    }
-    if (fp16 && c_fp16) launch_gemm_cfg<true, _Float16, 4, 2, 2, 4, true>(B, B, static_cast<_Float16*>(C), N, N, K, ldb, ldb, ldc, d_tile_list, n_listed, clamp, st);
-    else if (fp16) launch_gemm_cfg<true, float, 4, 2, 2, 4, true>(B, B, static_cast<float*>(C), N, N, K, ldb, ldb, ldc, d_tile_list, n_listed, clamp, st);
-    else if (c_fp16) launch_gemm_cfg<false, _Float16, 4, 2, 2, 4, true>(B, B, static_cast<_Float16*>(C), N, N, K, ldb, ldb, ldc, d_tile_list, n_listed, clamp, st);
-    else launch_gemm_cfg<false, float, 4, 2, 2, 4, true>(B, B, static_cast<float*>(C), N, N, K, ldb, ldb, ldc, d_tile_list, n_listed, clamp, st);
+    if (c_fp16 && fp16) launch_gemm_ov<true, true>(B, B, static_cast<_Float16*>(C), N, N, K, ldb, ldb, ldc, d_tile_list, n_listed, clamp, st);
+    else if (c_fp16) launch_gemm_ov<false, true>(B, B, static_cast<_Float16*>(C), N, N, K, ldb, ldb, ldc, d_tile_list, n_listed, clamp, st);
+    else if (fp16) launch_gemm_f32<true, true>(B, B, static_cast<float*>(C), N, N, K, ldb, ldb, ldc, d_tile_list, n_listed, st);
+    else launch_gemm_f32<false, true>(B, B, static_cast<float*>(C), N, N, K, ldb, ldb, ldc, d_tile_list, n_listed, st);
 }
 
 }  // namespace knncf
-
-// ---- measurement hook (not part of include/knncf.h): the similarity GEMM alone on a synthetic panel ----------------------
-// scripts/microbench/gemm_bench.py: milliseconds per launch of the symmetric (sym = 1) or the row-block (sym = 0, M rows)
-// form at N users x K head columns, fp16 operands and panel; the operand panel is filled with a cheap pattern (values in
-// [-1/16, 1/16]: the MFMA rate does not depend on the data, the chip's clock under load does a little).
-__global__ void k_debug_fill(knncf::bf16_t* p, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) reinterpret_cast<_Float16*>(p)[i] = (_Float16)((float)((int)((i * 2654435761u) >> 20 & 255) - 128) * (1.0f / 2048.0f));
-}
-
-extern "C" int knncf_debug_gemm_bench(int device, int64_t N, int64_t K, int64_t M, int sym, int iters, double* ms_per_launch) {
-    using namespace knncf;
-    try {
-        KN_HIP(hipSetDevice(device));
-        KN_REQUIRE(N % 256 == 0 && K % 64 == 0 && M % 256 == 0 && iters > 0 && ms_per_launch, KNNCF_E_INVALID, "bad shape");
-        DArr<bf16_t> B;
-        DArr<_Float16> C;
-        DArr<uint32_t> tiles;
-        B.alloc((size_t)N * K);
-        const int64_t rows = sym ? N : M;
-        C.alloc((size_t)rows * N);
-        k_debug_fill<<<(unsigned)ceil_div(N * K, 256), 256>>>(B.p, N * K);
-        std::vector<uint32_t> list;
-        int64_t n_listed = 0;
-        if (sym) {
-            gemm_sym_tile_list((int32_t)(N / 256), list, 8);
-            n_listed = (int64_t)list.size();
-            tiles.alloc(list.size());
-            KN_HIP(hipMemcpy(tiles.p, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        }
-        hipEvent_t a, b;
-        KN_HIP(hipEventCreate(&a));
-        KN_HIP(hipEventCreate(&b));
-        auto once = [&] {
-            if (sym) launch_gemm_sym(B.p, C.p, true, N, K, K, N, true, true, tiles.p, n_listed, nullptr, 256);
-            else launch_gemm_nt(B.p, B.p, C.p, true, M, N, K, K, K, N, true, true, nullptr);
-        };
-        once();
-        KN_HIP(hipDeviceSynchronize());
-        KN_HIP(hipEventRecord(a, nullptr));
-        for (int i = 0; i < iters; ++i) once();
-        KN_HIP(hipEventRecord(b, nullptr));
-        KN_HIP(hipEventSynchronize(b));
-        float ms = 0.f;
-        KN_HIP(hipEventElapsedTime(&ms, a, b));
-        *ms_per_launch = (double)ms / iters;
-        (void)hipEventDestroy(a);
-        (void)hipEventDestroy(b);
-        return KNNCF_OK;
-    } catch (const knncf::Error& e) {
-        fprintf(stderr, "knncf_debug_gemm_bench: %s\n", e.what());
-        return e.status;
-    }
-}

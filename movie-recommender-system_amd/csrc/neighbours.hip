@@ -5,8 +5,6 @@
 
 #include <algorithm>
 
-#include <stdlib.h>
-
 #include "engine.h"
 
 namespace knncf {
@@ -239,7 +237,7 @@ void launch_sort_neighbors(NeighborTable& nt, int32_t n_rows, const int32_t* d_r
         const int64_t U = (int64_t)nt.cnt.n;  // (one count per user)
         const int32_t words = (int32_t)ceil_div(U, 64);
         const size_t lds = (size_t)words * 12;
-        if (lds <= 48 * 1024 && !getenv("KNNCF_DEBUG_BITONIC_ID_SORT")) {
+        if (lds <= 48 * 1024) {
             k_rank_neighbors_by_id<<<n_rows, 256, lds, st>>>(n_rows, d_row_user, nt.kcap, words, nt.idx.p, nt.sim.p, nt.cnt.p, nt.uidx.p, nt.usim.p);
             KN_HIP(hipGetLastError());
             return;

@@ -417,12 +417,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_rows(PredArgs A, int
     }
 }
 
-#ifndef KNNCF_PRED_G5
-#define KNNCF_PRED_G5 2  // rows in flight per wave of k_predict_knn_items at 257 .. 320 neighbours (A/B switch)
-#endif
-#ifndef KNNCF_PRED_CHUNK
-#define KNNCF_PRED_CHUNK 64  // test rows per workgroup of k_predict_knn_items (A/B switch; at most 256)
-#endif
+static constexpr int PRED_CHUNK = 64;  // test rows per workgroup of k_predict_knn_items (at most 256)
 #ifdef KNNCF_PREDICT_PROFILE  /* in-kernel cycle counters of k_predict_knn_items' phases (thread 0 of every workgroup) */
 __device__ unsigned long long g_pphase[8];
 #define PPH(i) do { if (threadIdx.x == 0) { const long long now_ = clock64(); atomicAdd(&g_pphase[i], (unsigned long long)(now_ - ph_t)); ph_t = now_; } } while (0)
@@ -448,7 +443,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_items(PredArgs A, in
     // CAP per wave (26 KB per workgroup at k = 300) held the kernel at three workgroups per CU; with 9 KB it runs four, and
     // it waits on gather latency most of the time: 7.25 -> 6.3 ms
     constexpr int MCAP = 64;
-    constexpr int CHUNK = KNNCF_PRED_CHUNK;  // rows per workgroup
+    constexpr int CHUNK = PRED_CHUNK;  // rows per workgroup
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int ibw = (int)A.ib_words;
     const int ibw2 = (ibw + 1) >> 1;  // pairs of bitmap words
@@ -820,7 +815,7 @@ void launch_predict(const Train& tr, NeighborTable* nt, int predictor, int64_t n
         if (items_path) {
             A.n_bytes4 = (uint32_t)(tr.n * 4);
             const int trips = (nt->kcap + 63) / 64;
-            const unsigned blocks = (unsigned)ceil_div(n, KNNCF_PRED_CHUNK);
+            const unsigned blocks = (unsigned)ceil_div(n, PRED_CHUNK);
 #define KN_LAUNCH_ITEMS(TRV, GV)                                                                                          \
     do {                                                                                                                  \
         const size_t ibw2 = (size_t)(tr.ib_words + 1) / 2;                                                                  \
@@ -832,7 +827,7 @@ void launch_predict(const Train& tr, NeighborTable* nt, int predictor, int64_t n
             if (trips <= 1) KN_LAUNCH_ITEMS(1, 4);
             else if (trips <= 2) KN_LAUNCH_ITEMS(2, 4);
             else if (trips <= 4) KN_LAUNCH_ITEMS(4, 2);
-            else if (trips <= 5) KN_LAUNCH_ITEMS(5, KNNCF_PRED_G5);
+            else if (trips <= 5) KN_LAUNCH_ITEMS(5, 2);
             else KN_LAUNCH_ITEMS(8, 1);
 #undef KN_LAUNCH_ITEMS
             KN_HIP(hipGetLastError());

@@ -20,7 +20,7 @@
 // S[u][v] >= a_k - 2 eps (a_k = k-th largest value of the row), so the shortlist provably contains
 // the exact top-k; rerank.hip decides.  The panel S is read exactly once (it was written by the GEMM: the round trip
 // through HBM is the cost of keeping GEMM and select separate kernels); the kernel itself is bound by
-// VALU issue in the tail drain, not by that traffic.
+// the memory latencies of the tail drain's windows, not by that traffic.
 #include <math.h>
 
 #include <type_traits>
@@ -44,24 +44,19 @@ __device__ unsigned long long g_phase[16];
 // 10 % slower (and a 48 KiB-tile variant of an earlier version of this kernel 1.7x slower: tiles cost per tile).
 // __launch_bounds__(2 * TPB) caps the kernel at 128 VGPRs so that both workgroups fit.
 static constexpr int TPB = 512;
-#ifndef KNNCF_REFRESH_MASK
-#define KNNCF_REFRESH_MASK 0x80008000u  // tiles after which the threshold is refreshed from the stored values (A/B switch): after
-                                        // 16 and 32 tiles — none at the ml-25m shape's ten tiles: with the anticipated thresholds
-                                        // a refresh there costs more than the groups it saves; the store's fill
-                                        // level still triggers one whenever it grows
-#endif
+// tiles after which the threshold is refreshed from the stored values: after 16 and 32 tiles — none at the ml-25m shape's
+// ten tiles: with the anticipated thresholds a refresh there costs more than the groups it saves; the store's
+// fill level still triggers one whenever it grows
+static constexpr uint32_t REFRESH_MASK = 0x80008000u;
 static constexpr int NBINS = 1024;
 static constexpr int TCOLS = SELECT_TCOLS;  // columns of the row held in LDS at a time (64 KiB)
 static constexpr int CPT = TCOLS / TPB;  // columns per thread per tile (32 = 4 groups of 8)
 static constexpr int NG = CPT / 8;
 static_assert(CPT <= 32, "the survivor mask of a thread is one 32-bit word");
 static constexpr int EMAX = 256;     // row positions whose tail entries (16 B each) are held in LDS at a time
-#ifndef KNNCF_PMAX
-#define KNNCF_PMAX 1024
-#endif
-static constexpr int PMAX = KNNCF_PMAX;    // pieces per (chunk, tile) with a direct piece -> entry table in LDS (A/B switch: 0 = always the binary search)
-static constexpr int MAXT = TCOLS >= 16384 ? 12 : 24;  // tiles whose per-entry rater counts are packed into registers (12 x 16 384 columns: up to 196 608 users)
-static constexpr int WAVES_PER_EU = TCOLS >= 16384 ? 4 : 6;  // two / three 512-thread workgroups per CU (LDS: 79 / 47 KiB each)
+static constexpr int PMAX = 1024;          // pieces per (chunk, tile) with a direct piece -> entry table in LDS (more: a binary search)
+static constexpr int MAXT = 12;            // tiles whose per-entry rater counts are packed into registers (12 x 16 384 columns: up to 196 608 users)
+static constexpr int WAVES_PER_EU = 4;     // two 512-thread workgroups per CU (LDS: 79 KiB each)
 static constexpr int TAIL_G = 8;           // pieces per group of the drain (two groups in flight per wave)
 // the tail is accumulated in Q7.24 fixed point with integer LDS atomics (ds_add_u32; the float form
 // ds_add_f32 measured ~1.4x slower here): |sum| <= 1, each product is quantised with error <= 2^-25,
@@ -431,16 +426,11 @@ __global__ void __launch_bounds__(TPB, WAVES_PER_EU) k_tail_select(const ST* __r
         P = __builtin_amdgcn_readfirstlane(P);
         ne = __builtin_amdgcn_readfirstlane(ne);
         const uint32_t wv = __builtin_amdgcn_readfirstlane(wave);
-#ifdef KNNCF_TAIL_EVEN_PIECES  /* A/B switch: the pieces dealt evenly, every wave rounds its share up to whole groups itself */
-        p_lo = (uint32_t)(((uint64_t)P * wv) / (TPB / 64));
-        p_hi = (uint32_t)(((uint64_t)P * (wv + 1)) / (TPB / 64));
-#else
         // whole GROUPS of TAIL_G pieces are dealt, so that only the last wave's last group is padded with null pieces (every
         // wave rounding its own share up padded ~4 of ~27 pieces per wave and tile)
         const uint32_t n_groups = (P + TAIL_G - 1) / TAIL_G;
         p_lo = min(P, (uint32_t)(((uint64_t)n_groups * wv) / (TPB / 64)) * TAIL_G);
         p_hi = min(P, (uint32_t)(((uint64_t)n_groups * (wv + 1)) / (TPB / 64)) * TAIL_G);
-#endif
     };
     auto use_tables = [&](int buf) {
         e_b = e_b0 + buf * EMAX;
@@ -807,7 +797,7 @@ __global__ void __launch_bounds__(TPB, WAVES_PER_EU) k_tail_select(const ST* __r
         // the store is filling up (wide error bands, e.g. bf16 operands)
         {
             const uint32_t prov = s_count;  // (block-uniform after the barrier)
-            if (((tile_no < 32 && ((KNNCF_REFRESH_MASK >> tile_no) & 1u)) || prov > next_refresh) && prov <= (uint32_t)GCAP && t0 + TCOLS < U) {
+            if (((tile_no < 32 && ((REFRESH_MASK >> tile_no) & 1u)) || prov > next_refresh) && prov <= (uint32_t)GCAP && t0 + TCOLS < U) {
                 count_new_groups(s_thr);
                 block_threshold(hist, wtot, &s_thr, &s_bin, rank_after(tile_no + 1), eps);
                 bin_used = max(bin_used, s_bin);
@@ -941,12 +931,8 @@ static void launch_tail_select_t(const TailArgs& T, const ST* S, bool s_by_user,
     ensure_dynamic_lds(lds_state, (const void*)k_tail_select<ST, JAC>, smem);
     // (KNNCF_DEBUG_ANTICIPATE_SIGMA: test hook — a small margin makes the anticipated thresholds overshoot in some rows, which
     // must then be caught by the final check and rebuilt exactly; a negative one switches the anticipation off)
-#ifdef KNNCF_NO_ANTICIPATION
-    const float ant_sigma = -1.0f;
-#else
     const char* sg = getenv("KNNCF_DEBUG_ANTICIPATE_SIGMA");
     const float ant_sigma = !anticipate ? -1.0f : sg ? (float)atof(sg) : 7.0f;
-#endif
     k_tail_select<ST, JAC><<<n_rows, TPB, smem, st>>>(S, s_by_user ? 1 : 0, lds, n_rows, d_row_user, d_row_srow, T, U, kk, eps_opnd, eps_rest, cap, cand_idx, cand_approx, cand_cnt, cand_eps, grp_v0, grp_x, gcap, ant_sigma);
     KN_HIP(hipGetLastError());
 #ifdef KNNCF_SELECT_PROFILE
@@ -965,10 +951,10 @@ void launch_tail_select(const Train& tr, const int32_t* d_colmap, const TailEntr
     int32_t kk = k < U - 1 ? k : U - 1;
     if (kk < 1) kk = 1;
     KN_REQUIRE(!has_tail || tr.tile_stride == (int32_t)ceil_div(U, TCOLS) + 1, KNNCF_E_STATE, "select: tile table missing");
-    // (KNNCF_DEBUG_SKIP_TAIL: timing-only hook — drops the sparse tail, so the neighbours are WRONG; it measures what the
-    // kernel costs without the tail machinery: the panel scan, the thresholds, the group store)
-    static const bool skip_tail = getenv("KNNCF_DEBUG_SKIP_TAIL") != nullptr;
-    if (skip_tail) has_tail = false;
+#ifdef KNNCF_ABL_NOTAIL  /* timing-only ablation (results are wrong): no sparse tail — what the kernel costs without the tail
+                            machinery: the panel scan, the thresholds, the group store */
+    has_tail = false;
+#endif
     KN_REQUIRE(!has_tail || (te.cnt && te.item && te.x && te.tail_abs && te.head_sq), KNNCF_E_STATE, "select: tail entry lists missing");
     TailArgs T{tr.u_ptr.p, tr.s_col.p, tr.s_pre.p, d_colmap, tr.i_ptr.p, tr.it_pack.p, (uint32_t)(tr.n * 4), tr.it_tile.p, tr.tile_stride, has_tail ? 1 : 0,
                te.cnt, te.item, te.x, te.tail_abs, te.head_sq, te.row_len};

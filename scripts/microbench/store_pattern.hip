@@ -2,7 +2,7 @@
 // A persistent grid (one 512-thread workgroup per CU) walks the 256 x 256 fp16 tiles of an N x N panel (row stride
 // 2 N bytes) and writes every tile with 16-byte nontemporal stores in one of the shapes the GEMM epilogues use:
 //   0: linear          — the panel as one stream (upper bound)
-//   1: 2 rows x 512 B  — a wave instruction covers 2 whole tile rows (k_gemm_nt_bf16's workgroup-wide image, normal)
+//   1: 2 rows x 512 B  — a wave instruction covers 2 whole tile rows (a workgroup-wide epilogue image, normal)
 //   2: 4 rows x 256 B  — its mirror image (128-row passes)
 //   3: 8 rows x 128 B  — a wave's private 32 x 64 block, as it is (k_gemm_nt_ov)
 //   4: 16 rows x 64 B  — the same block mirrored (k_gemm_nt_ov)
