@@ -143,7 +143,12 @@ int knncf_item_avg_dev_rdd(knncf_handle* h, int32_t item, double* out); /* items
 int knncf_similarity(knncf_handle* h, int32_t u, int32_t v, double* out);
 /* getSimilarity(train, k, sim)(u, v): sim if v is one of u's k nearest, else 0 :634-648 */
 int knncf_knn_similarity(knncf_handle* h, int32_t u, int32_t v, double* out);
-/* getNeighbors(train, k, sim)(u): ids and similarities in reference order :603-616 */
+/* getNeighbors(train, k, sim)(u): ids and similarities in reference order :603-616.
+ * Shard handles (shard_count > 1) whose train set has a user with <= 4 ratings: KNNCF_E_UNSUPPORTED for a user whose
+ * neighbourhood knncf_mae* / knncf_predict_batch* have not built yet.  Such a build would be numbered on this shard only,
+ * and a <= 4-rating pair is summed in the order that numbering decides: the shards could disagree with each
+ * other and with a single handle.  Query after the replicated mae / predict call, which numbers every user on every shard.
+ * The same holds for knncf_neighbors_batch. */
 int knncf_neighbors(knncf_handle* h, int32_t u, int32_t cap, int32_t* ids, double* sims,
                     int32_t* count);
 /* getNeighbors for users[0..n) at once ("as if called in this order"): row j of ids / sims ([n * cap]) receives
@@ -291,8 +296,9 @@ void knncf_free_personal(knncf_personal* p);
 
 /* Checkpoint / resume of the expensive part of a fit: the U x k neighbour table (ids, fp64 similarities, build
  * sequence numbers).  save: every neighbourhood built so far.  load: the handle must be fitted on the same training
- * rows with the same k and similarity (checked with a fingerprint of the users, row extents and means:
- * KNNCF_E_STATE otherwise); afterwards getNeighbors / getSimilarity / predictions use the loaded lists and only
+ * rows with the same k and similarity (checked with a fingerprint of the users, row extents and means and of every
+ * rating's item and value in row order: KNNCF_E_STATE otherwise; a file of the older format "KNNCFNB1", whose fingerprint
+ * left out the ratings, is refused with KNNCF_E_INVALID); afterwards getNeighbors / getSimilarity / predictions use the loaded lists and only
  * users that were not built at save time are built on demand. */
 int knncf_neighbors_save(knncf_handle* h, const char* path);
 int knncf_neighbors_load(knncf_handle* h, const char* path);

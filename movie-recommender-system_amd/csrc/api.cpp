@@ -38,6 +38,7 @@ struct knncf_handle {
     Train tr;
     PrepScratch prep;
     bool fitted = false, committed = false;
+    int8_t short_rows = -1;  // the train set has a user with <= 4 ratings (1 / 0; -1 = not looked up since the fit)
     NeighborTable nt;
     int64_t epoch = 1;
     // panels
@@ -192,6 +193,26 @@ int32_t dense_user(knncf_handle* h, int32_t raw) {
 int32_t dense_item(knncf_handle* h, int32_t raw) {
     load_host_ids(h);
     return dense_lookup(h->h_ikeys.data(), h->tr.I, raw);
+}
+
+// A neighbour query that builds a list numbers that build on the queried shard only (the other shards never see the call).
+// With a <= 4-rating user in train the owner rule of rerank.hip (pair_sim: seq_v < seq_u) reads those numbers on every shard,
+// so such a query would let the shards disagree on a pair's summation order: refused.  The mae / predict path
+// numbers every user on every shard (ensure_neighbors_for_rows) and stays open.
+void require_shard_numbering(knncf_handle* h) {
+    if (h->cfg.shard_count == 1) return;
+    if (h->short_rows < 0) {
+        Train& tr = h->tr;
+        std::vector<int64_t> ptr((size_t)tr.U + 1);
+        KN_HIP(hipMemcpyAsync(ptr.data(), tr.u_ptr.p, ptr.size() * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+        KN_HIP(hipStreamSynchronize(h->stream));
+        h->short_rows = 0;
+        for (int32_t u = 0; u < tr.U; ++u)
+            if (ptr[u + 1] - ptr[u] <= 4) { h->short_rows = 1; break; }
+    }
+    KN_REQUIRE(h->short_rows == 0, KNNCF_E_UNSUPPORTED,
+               "neighbours: on a shard handle whose train set has a user with <= 4 ratings, a neighbourhood that knncf_mae / "
+               "knncf_predict_batch has not built yet cannot be built by a query (its build number would exist on this shard only)");
 }
 
 template <class T>
@@ -772,6 +793,7 @@ void do_fit_device(knncf_handle* h, const int32_t* d_users, const int32_t* d_ite
     Train& tr = h->tr;
     hipStream_t st = h->stream;
     h->fitted = h->committed = false;
+    h->short_rows = -1;
     h->b_ready = false;
     h->pt_ready = false;
     h->h_ukeys.clear(); h->h_ikeys.clear(); h->h_uid.clear();
@@ -906,22 +928,27 @@ void do_query_recommend(knncf_handle* h, int predictor, int32_t user, const int3
 
 // ---- checkpoint / resume of the neighbour table ------------------------------------------------------
 struct NbrFileHeader {
-    char magic[8];  // "KNNCFNB1"
+    char magic[8];  // "KNNCFNB2" (NB1: the fingerprint without the ratings; refused)
     int32_t U, kcap, k, similarity;
     int64_t n;
     uint64_t fingerprint;
     int64_t epoch;
 };
 
-// FNV-1a over what identifies "the same fit": raw user ids in dense order, row extents, user means
+// FNV-1a over what identifies "the same fit": raw user ids in dense order, row extents, user means, and what decides the
+// similarities — every rating's raw item id and value in row order (user-major, items ascending).  (Without the last two a fit
+// that moved a rating to another item of the same user, or swapped two of a user's ratings, passed for the same.)
 uint64_t fit_fingerprint(knncf_handle* h) {
     Train& tr = h->tr;
-    std::vector<int32_t> uid(tr.U);
+    std::vector<int32_t> uid(tr.U), iid(tr.I), col((size_t)tr.n);
     std::vector<int64_t> ptr((size_t)tr.U + 1);
-    std::vector<double> avg(tr.U);
+    std::vector<double> avg(tr.U), rating((size_t)tr.n);
     KN_HIP(hipMemcpyAsync(uid.data(), tr.uid.p, (size_t)tr.U * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     KN_HIP(hipMemcpyAsync(ptr.data(), tr.u_ptr.p, ((size_t)tr.U + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     KN_HIP(hipMemcpyAsync(avg.data(), tr.user_avg.p, (size_t)tr.U * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    KN_HIP(hipMemcpyAsync(iid.data(), tr.iid.p, (size_t)tr.I * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    KN_HIP(hipMemcpyAsync(col.data(), tr.s_col.p, (size_t)tr.n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    KN_HIP(hipMemcpyAsync(rating.data(), tr.s_rating.p, (size_t)tr.n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     KN_HIP(hipStreamSynchronize(h->stream));
     uint64_t x = 1469598103934665603ull;
     auto mix = [&](const void* p, size_t bytes) {
@@ -931,6 +958,11 @@ uint64_t fit_fingerprint(knncf_handle* h) {
     mix(uid.data(), uid.size() * sizeof(int32_t));
     mix(ptr.data(), ptr.size() * sizeof(int64_t));
     mix(avg.data(), avg.size() * sizeof(double));
+    for (size_t p = 0; p < col.size(); ++p) {
+        const int32_t item = iid[col[p]];
+        mix(&item, sizeof item);
+        mix(&rating[p], sizeof(double));
+    }
     return x;
 }
 
@@ -941,7 +973,7 @@ void do_neighbors_save(knncf_handle* h, const char* path) {
     Train& tr = h->tr;
     NeighborTable& nt = h->nt;
     NbrFileHeader hd{};
-    memcpy(hd.magic, "KNNCFNB1", 8);
+    memcpy(hd.magic, "KNNCFNB2", 8);
     hd.U = tr.U; hd.kcap = nt.kcap; hd.k = nt.k; hd.similarity = h->cfg.similarity; hd.n = tr.n;
     hd.fingerprint = fit_fingerprint(h);
     hd.epoch = h->epoch;
@@ -973,8 +1005,13 @@ void do_neighbors_load(knncf_handle* h, const char* path) {
     FILE* f = fopen(path, "rb");
     KN_REQUIRE(f, KNNCF_E_INVALID, std::string("cannot open ") + path);
     NbrFileHeader hd{};
-    bool ok = fread(&hd, sizeof hd, 1, f) == 1 && memcmp(hd.magic, "KNNCFNB1", 8) == 0;
-    if (!ok) { fclose(f); throw Error(KNNCF_E_INVALID, std::string(path) + ": not a neighbour checkpoint"); }
+    bool ok = fread(&hd, sizeof hd, 1, f) == 1 && memcmp(hd.magic, "KNNCFNB2", 8) == 0;
+    if (!ok) {
+        const bool v1 = memcmp(hd.magic, "KNNCFNB1", 8) == 0;
+        fclose(f);
+        throw Error(KNNCF_E_INVALID, std::string(path) + (v1 ? ": neighbour checkpoint of the older format (its fingerprint does not cover the ratings): rebuild it"
+                                                               : ": not a neighbour checkpoint"));
+    }
     if (hd.U != tr.U || hd.kcap != nt.kcap || hd.k != nt.k || hd.similarity != h->cfg.similarity || hd.n != tr.n ||
         hd.fingerprint != fit_fingerprint(h)) {
         fclose(f);
@@ -1172,6 +1209,7 @@ static void neighbors_of(knncf_handle* h, int32_t du, std::vector<int32_t>& ids,
     if (tr.U < 2 || nt.kcap <= 0) return;
     int64_t seq = fetch(h, nt.seq.p, du);
     if (seq < 0) {
+        require_shard_numbering(h);
         h->build_list.ensure(tr.U);
         int64_t new_seq = h->epoch << 32;
         h->epoch += 1;
@@ -1239,6 +1277,7 @@ static void do_neighbors_batch(knncf_handle* h, const int32_t* users, int64_t n,
                 fresh.push_back(du[j]);
             }
         if (!fresh.empty()) {
+            require_shard_numbering(h);
             h->epoch += 1;
             h->build_list.ensure(tr.U);
             KN_HIP(hipMemcpyAsync(nt.seq.p, seq.data(), seq.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));

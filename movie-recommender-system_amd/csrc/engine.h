@@ -235,7 +235,7 @@ void launch_exact_pair(const Train& tr, int32_t u, int32_t v, double* d_out, hip
 // per test row: prediction of `predictor`; rows whose user is outside [own_lo, own_hi) are
 // skipped (unknown users belong to shard 0).  d_abs_err[t] = |r - p| or 0 for skipped rows.
 // id-sorted copies of the lists of the given users (d_row_user == nullptr: of every user)
-void launch_sort_neighbors(NeighborTable& nt, int32_t n_rows, const int32_t* d_row_user, hipStream_t st);
+void launch_sort_neighbors(NeighborTable& nt, int32_t U, int32_t n_rows, const int32_t* d_row_user, hipStream_t st);
 void launch_predict(const Train& tr, NeighborTable* nt, int predictor, int64_t n,
                     const int32_t* d_du, const int32_t* d_di, const double* d_ratings,
                     const uint32_t* d_order, bool order_by_item, double* d_pred, double* d_abs_err, uint8_t* d_owned,

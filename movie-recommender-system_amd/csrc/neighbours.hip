@@ -228,14 +228,16 @@ __global__ void __launch_bounds__(256) k_rank_neighbors_by_id(int32_t n_rows, co
     }
 }
 
-void launch_sort_neighbors(NeighborTable& nt, int32_t n_rows, const int32_t* d_row_user, hipStream_t st) {
+// U: the users of the current fit.  (nt.cnt.n is the buffer's capacity, which a re-fit with fewer users does not shrink: the rows
+// past U hold a previous fit's counts, sized for its k.)
+void launch_sort_neighbors(NeighborTable& nt, int32_t U, int32_t n_rows, const int32_t* d_row_user, hipStream_t st) {
     if (n_rows <= 0 || nt.kcap <= 0) return;
-    const size_t cells = nt.cnt.n * (size_t)nt.kcap;
+    KN_REQUIRE(U > 0 && (size_t)U <= nt.cnt.n && (d_row_user || n_rows <= U), KNNCF_E_INVALID, "sort neighbours: bad row count");
+    const size_t cells = (size_t)U * (size_t)nt.kcap;
     nt.uidx.ensure(cells);
     nt.usim.ensure(cells);
     {
-        const int64_t U = (int64_t)nt.cnt.n;  // (one count per user)
-        const int32_t words = (int32_t)ceil_div(U, 64);
+        const int32_t words = (int32_t)ceil_div((int64_t)U, 64);
         const size_t lds = (size_t)words * 12;
         if (lds <= 48 * 1024) {
             k_rank_neighbors_by_id<<<n_rows, 256, lds, st>>>(n_rows, d_row_user, nt.kcap, words, nt.idx.p, nt.sim.p, nt.cnt.p, nt.uidx.p, nt.usim.p);

@@ -804,7 +804,7 @@ void launch_predict(const Train& tr, NeighborTable* nt, int predictor, int64_t n
             A.nbr_uidx = nt->idx.p; A.nbr_usim = nt->sim.p;
         } else {
             if (!nt->by_id_valid) {
-                launch_sort_neighbors(*nt, (int32_t)nt->cnt.n, nullptr, st);
+                launch_sort_neighbors(*nt, tr.U, tr.U, nullptr, st);
                 nt->by_id_valid = true;
             }
             A.nbr_uidx = nt->uidx.p; A.nbr_usim = nt->usim.p;

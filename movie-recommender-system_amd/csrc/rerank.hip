@@ -645,7 +645,6 @@ static void launch_rerank_plan(const Rows& R, const Train& tr, NeighborTable& nt
     const int32_t grid = n_rows + sl.n_heavy * (sl.P - 1);
     k_rerank<TILE, JAC, WIDE><<<grid, TPB, smem, st>>>(R, nt.seq.p, n_rows, d_row_user, cap, cand_idx, cand_approx, cand_cnt, nt.kcap,
                                             nt.kcap, nt.idx.p, nt.sim.p, nt.cnt.p, cand_eps, d_stats, d_row_entries, words, sl);
-    k_sum_row_entries<<<(unsigned)ceil_div(n_rows, 1024), 1024, 0, st>>>(n_rows, d_row_entries, cand_cnt, cap, reinterpret_cast<unsigned long long*>(d_stats) + 1);
     KN_HIP(hipGetLastError());
 #ifdef KNNCF_RERANK_PROFILE
     KN_HIP(hipStreamSynchronize(st));
@@ -779,6 +778,9 @@ void launch_rerank(const Train& tr, NeighborTable& nt, int32_t n_rows, const int
         else if (mt <= 4096) launch_merge<4096>(cap, d_row_user, cand_cnt, sl, d_row_entries, nt, st);
         else launch_merge<8192>(cap, d_row_user, cand_cnt, sl, d_row_entries, nt, st);
     }
+    // after the merge: it writes the entry counts of the first n_heavy rows (their slices' counts are in sl.entries until then)
+    k_sum_row_entries<<<(unsigned)ceil_div(n_rows, 1024), 1024, 0, st>>>(n_rows, d_row_entries, cand_cnt, cap, reinterpret_cast<unsigned long long*>(d_stats) + 1);
+    KN_HIP(hipGetLastError());
 }
 
 // exact similarities of one user against everyone (out[user] = -inf): the fallback for rows whose

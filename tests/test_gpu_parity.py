@@ -778,7 +778,8 @@ def test_heavy_rows_reranked_as_slices(kn, oracle, synth, syn100k, monkeypatch, 
     blocks of 4096 .. 65 536 rows: the eight-shard test of the ml-25m shape runs it that way): forced on here for the first
     200 rows — or for ALL rows, where most slices of the short shortlists are empty — and compared on every third user with
     the oracle, lists and predictions bit for bit"""
-    monkeypatch.setenv("KNNCF_DEBUG_SLICE_ROWS", "100000" if case == "empty_slices" else "200")
+    sliced_rows = "100000" if case == "empty_slices" else "200"
+    monkeypatch.setenv("KNNCF_DEBUG_SLICE_ROWS", sliced_rows)
     if case == "k1500":
         d = synth.syn_scaled(2400, 500, 160_000, seed=43, half_stars=True, shuffle=True)
         tr = (d.train.users, d.train.items, d.train.ratings)
@@ -797,6 +798,7 @@ def test_heavy_rows_reranked_as_slices(kn, oracle, synth, syn100k, monkeypatch, 
         p = m.pipeline(sim_o, k)
         want, preds = p.mae(*te, True)
         np.testing.assert_array_equal(e.predict_batch(kn.PRED_KNN, te[0], te[1]), preds)
+        sliced_bytes = e.timings()["rerank_row_bytes"]
         assert abs(e.mae(kn.PRED_KNN, *te) - want) <= MAE_TOL
         ids, sims, counts = e.neighbors_batch(users[::3])
         for row, u in enumerate(users[::3]):
@@ -806,7 +808,20 @@ def test_heavy_rows_reranked_as_slices(kn, oracle, synth, syn100k, monkeypatch, 
             assert sims[row, : counts[row]].tolist() == osims.tolist()
         t = e.timings()
         assert t["max_bound_violation"] <= 0.0 and t["fallback_rows"] == 0
+        # the re-rank traffic statistic counts a sliced row's entries once its slices are merged: equal to the unsliced
+        # build's, and to a second build on the same handle
+        e.reset_timings()
+        e.reset_neighbors()
+        np.testing.assert_array_equal(e.predict_batch(kn.PRED_KNN, te[0], te[1]), preds)
+        assert e.timings()["rerank_row_bytes"] == sliced_bytes
         e.close()
+        monkeypatch.setenv("KNNCF_DEBUG_SLICE_ROWS", "0")
+        plain = _engine(kn, tr, k=k, sim=sim_k, flags=kn.FLAG_VERIFY_BOUND)
+        np.testing.assert_array_equal(plain.predict_batch(kn.PRED_KNN, te[0], te[1]), preds)
+        plain_bytes = plain.timings()["rerank_row_bytes"]
+        plain.close()
+        monkeypatch.setenv("KNNCF_DEBUG_SLICE_ROWS", sliced_rows)
+        assert plain_bytes > 0 and sliced_bytes == plain_bytes, (k, sliced_bytes, plain_bytes)
 
 
 def test_group_of_one_device_equals_plain_handle(kn, oracle, syn100k):

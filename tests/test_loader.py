@@ -151,5 +151,23 @@ def test_neighbour_checkpoint_round_trip(kn, oracle, synth, tmp_path):
     e = kn.Engine(k=k + 1).fit(*tr)
     with pytest.raises(kn.KnncfError):
         e.neighbors_load(path)
+    # re-fits with the same users, row lengths and means (the same U, n, k and extents) but other similarities: a user's
+    # two ratings swapped between their items, and one item of a user replaced by an item they did not rate
+    u0 = tr[0][0]
+    rows = np.flatnonzero(tr[0] == u0)
+    j1 = rows[0]
+    j2 = next(j for j in rows[1:] if tr[2][j] != tr[2][j1])
+    swapped = tr[2].copy()
+    swapped[j1], swapped[j2] = tr[2][j2], tr[2][j1]
+    others = np.setdiff1d(np.unique(tr[1]), tr[1][rows])
+    moved = tr[1].copy()
+    moved[rows[-1]] = others[len(others) // 2]
+    for alt in ((tr[0], tr[1], swapped), (tr[0], moved, tr[2])):
+        g = kn.Engine(k=k).fit(*alt)
+        assert g.num_users == a.num_users and g.user_avg(int(u0)) == a.user_avg(int(u0))
+        with pytest.raises(kn.KnncfError) as ex:
+            g.neighbors_load(path)
+        assert ex.value.status == kn.E_STATE
+        g.close()
     for eng in (a, b, c, e):
         eng.close()
