@@ -57,8 +57,16 @@ extern "C" {
                                      sim = the handle's similarity: the adjusted cosine or the Jaccard coefficient (any number of users:
                                      both go through the MFMA GEMM + sparse tail + exact re-rank); similarityOne: KNNCF_E_UNSUPPORTED */
 #define KNNCF_PRED_PERSONALIZED 6 /* predictor(train, weightedSumDeviation(train, sim)) predict/Personalized.scala:61-72, sim = the
-                                     handle's similarity itself, no neighbourhood cut.  Cosine / Jaccard keep U x U values: U <= 2048;
-                                     cosine additionally needs > 4 ratings per user, else KNNCF_E_UNSUPPORTED */
+                                     handle's similarity itself, no neighbourhood cut, at any number of users.  Cosine / Jaccard:
+                                     U <= 2048 keeps a U x U table of the non-zero similarities (built once per fit); beyond, each
+                                     call builds the exact fp64 similarity rows of the test users block by block (row scratch:
+                                     R x U x 8 B, R sized from workspace_bytes / 2 or a quarter of free memory) and folds each
+                                     test row over its item's raters in file order; the first such call after a fit also keeps
+                                     20 B x n of per-rating copies (rater + deviation in file order, fp64 preprocessed rating in
+                                     item order), charged to prep_ms.  Timings: the row build counts as rerank_ms, the row sort
+                                     and the folds as predict_ms.  Cosine needs > 4 ratings per user, and shard
+                                     handles are refused: KNNCF_E_UNSUPPORTED.  The kNN state (neighbour lists, their build
+                                     numbers) is not touched. */
 
 #define KNNCF_FLAG_VERIFY_BOUND 1u /* check |approx - exact| <= eps on every re-ranked pair (debug) */
 /* The similarity GEMM is only a filter in front of the exact fp64 re-rank.  Default operand type is fp16

@@ -68,6 +68,8 @@ struct knncf_handle {
     SliceScratch slices;
     NeighborTable pt;       // Personalized (no k): every non-zero similarity of every user (ids ascending, self included)
     bool pt_ready = false;
+    PersonalRows prow;      // Personalized (no k) beyond the table: first-use copies + the row scratch (personalized.hip)
+    bool prow_ready = false;
     DArr<int32_t> reco_users, reco_items, reco_out_items;
     DArr<double> reco_pred, reco_out_preds;
     DArr<uint8_t> reco_rated;
@@ -676,13 +678,15 @@ void ensure_neighbors_for_rows(knncf_handle* h, int64_t n) {
 }
 
 // predictor(train, weightedSumDeviation(train, sim)) with sim = adjustedCosineSimilarityFunction(train) or
-// jaccardCoefficient(train) (predict/Personalized.scala:61-72): the table of every non-zero similarity, built once per fit
-void ensure_personalized_table(knncf_handle* h) {
-    if (h->pt_ready) return;
+// jaccardCoefficient(train) (predict/Personalized.scala:61-72).  U <= 2048: the table of every non-zero similarity, built once
+// per fit, through the kNN prediction kernels with k = U.  Beyond (or with KNNCF_DEBUG_PERSONALIZED_STREAM, a test hook that
+// takes this path at any U): exact similarity rows built per block of test users and folded in file order (personalized.hip).
+bool personalized_streams(const knncf_handle* h) { return h->tr.U > 2048 || getenv("KNNCF_DEBUG_PERSONALIZED_STREAM"); }
+
+// the refusals of both forms
+void require_personalized(knncf_handle* h) {
     Train& tr = h->tr;
     KN_REQUIRE(h->cfg.shard_count == 1, KNNCF_E_UNSUPPORTED, "PERSONALIZED is not sharded");
-    KN_REQUIRE(tr.U <= 2048, KNNCF_E_UNSUPPORTED,
-               "PERSONALIZED with the adjusted cosine / Jaccard similarity keeps U x U similarities: built for U <= 2048 (the reference runs it at ml-100k scale)");
     if (h->cfg.similarity == KNNCF_SIM_COSINE) {
         std::vector<int64_t> ptr((size_t)tr.U + 1);
         KN_HIP(hipMemcpyAsync(ptr.data(), tr.u_ptr.p, ptr.size() * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
@@ -691,6 +695,12 @@ void ensure_personalized_table(knncf_handle* h) {
             KN_REQUIRE(ptr[u + 1] - ptr[u] > 4, KNNCF_E_UNSUPPORTED,
                        "PERSONALIZED with the adjusted cosine: a user with <= 4 ratings makes the reference's summation order depend on its memo history pair by pair (SURVEY N6); not modelled");
     }
+}
+
+void ensure_personalized_table(knncf_handle* h) {
+    if (h->pt_ready) return;
+    Train& tr = h->tr;
+    require_personalized(h);
     NeighborTable& pt = h->pt;
     pt.k = pt.kcap = tr.U;
     const size_t cells = (size_t)tr.U * (size_t)tr.U;
@@ -700,6 +710,80 @@ void ensure_personalized_table(knncf_handle* h) {
     launch_full_rows(tr, h->cfg.similarity == KNNCF_SIM_JACCARD, pt.uidx.p, pt.usim.p, pt.cnt.p, h->stream);
     pt.by_id_valid = true;
     h->pt_ready = true;
+}
+
+// the item-major fp64 pre values, the raters in file order and the tile table: built on the first streamed call, charged to
+// prep_ms (knncf_fit does not build them: the kNN step never reads them)
+void ensure_personal_rows(knncf_handle* h) {
+    if (h->prow_ready) return;
+    require_personalized(h);
+    Stage s(h, &h->tm.prep_ms);
+    h->prep.join_commit(h->stream);
+    personalized_prepare(h->tr, h->prep, h->prow, h->stream);
+    h->prow_ready = true;
+}
+
+// The streamed form over the test rows whose dense ids are in t_du / t_di: rows sorted by (user, item), the distinct users
+// that have a row on a train item cut into blocks of R; per block the users' exact rows (rerank_ms), then the folds of the
+// block's rows (predict_ms).  Read-only on the kNN state.
+void predict_personal_rows(knncf_handle* h, const double* d_ratings, int64_t n, double* d_pred) {
+    Train& tr = h->tr;
+    PersonalRows& pr = h->prow;
+    PrepScratch& sc = h->prep;
+    hipStream_t st = h->stream;
+    KN_REQUIRE(n < (int64_t)0xffffffffll, KNNCF_E_UNSUPPORTED, "more than 2^32-1 test rows");
+    sc.k64_a.ensure(n); sc.k64_b.ensure(n); sc.v32_a.ensure(n); sc.v32_b.ensure(n);
+    const int ibits = bits_for((uint64_t)tr.I);
+    std::vector<uint64_t> keys((size_t)n);
+    {
+        Stage s(h, &h->tm.predict_ms);
+        launch_personal_row_keys(tr, n, h->t_du.p, h->t_di.p, sc.k64_a.p, sc.v32_a.p, st);
+        sort_pairs_u64_u32(sc.sort, sc.k64_a.p, sc.k64_b.p, sc.v32_a.p, sc.v32_b.p, n, ibits + bits_for((uint64_t)tr.U), st);
+        KN_HIP(hipMemcpyAsync(keys.data(), sc.k64_b.p, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        KN_HIP(hipStreamSynchronize(st));
+    }
+    // the users whose rows are built: a known user with a row on a train item (its rows sort by item, absent item last)
+    std::vector<int32_t> users;
+    std::vector<int64_t> first_row;  // sorted row where each such user's rows begin
+    for (int64_t r = 0; r < n; ++r) {
+        const uint64_t u = keys[r] >> ibits, i = keys[r] & ((1ull << ibits) - 1ull);
+        if (u < (uint64_t)tr.U && i < (uint64_t)tr.I && (users.empty() || users.back() != (int32_t)u)) {
+            users.push_back((int32_t)u);
+            first_row.push_back(r);
+        }
+    }
+    const int64_t nu = (int64_t)users.size();
+    int64_t R = 1;
+    if (nu > 0) {
+        size_t free_b = 0, total_b = 0;
+        KN_HIP(hipMemGetInfo(&free_b, &total_b));
+        const int64_t row_bytes = (int64_t)tr.U * 8;
+        const int64_t budget = h->cfg.workspace_bytes > 0 ? h->cfg.workspace_bytes / 2
+                                                          : (int64_t)std::min<size_t>((size_t)48 << 30, (free_b + pr.S.bytes()) / 4);
+        R = std::min<int64_t>(std::max<int64_t>(1, budget / row_bytes), nu);
+        R = ceil_div(nu, ceil_div(nu, R));  // equal blocks
+        pr.S.ensure((size_t)R * tr.U);
+        std::vector<int32_t> slot((size_t)tr.U, -1);
+        for (int64_t k = 0; k < nu; ++k) slot[users[k]] = (int32_t)(k % R);
+        pr.users.ensure(nu);
+        pr.slot.ensure(tr.U);
+        KN_HIP(hipMemcpyAsync(pr.users.p, users.data(), (size_t)nu * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        KN_HIP(hipMemcpyAsync(pr.slot.p, slot.data(), (size_t)tr.U * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        KN_HIP(hipStreamSynchronize(st));  // (the host vectors go out of scope)
+    }
+    // block b: users [b R, (b + 1) R), sorted rows from its first user's first row (block 0: from row 0) to the next block's
+    const int64_t n_blocks = std::max<int64_t>(1, ceil_div(nu, R));
+    for (int64_t b = 0; b < n_blocks; ++b) {
+        const int64_t u0 = b * R, u1 = std::min<int64_t>(nu, u0 + R);
+        const int64_t r0 = b == 0 ? 0 : first_row[u0], r1 = b + 1 < n_blocks ? first_row[u1] : n;
+        if (u1 > u0) {
+            Stage s(h, &h->tm.rerank_ms);
+            launch_sim_rows(tr, pr, pr.users.p + u0, (int32_t)(u1 - u0), pr.S.p, st);
+        }
+        Stage s(h, &h->tm.predict_ms);
+        launch_fold_rows(tr, pr, r1 - r0, sc.v32_b.p + r0, h->t_du.p, h->t_di.p, d_ratings, pr.slot.p, pr.S.p, d_pred, h->t_err.p,
+                         h->t_owned.p, st);
+    }
 }
 
 // K4 on first use: computeItemAvg :141, computeItemAvgDev :193 and the Spark forms build their item maps when the predictor is
@@ -723,16 +807,20 @@ void run_predict(knncf_handle* h, int predictor, const int32_t* d_users, const i
     KN_REQUIRE(d_users && d_items, KNNCF_E_INVALID, "null test arrays");
     int kind = predictor;
     NeighborTable* table = &h->nt;
+    bool stream = false;  // PERSONALIZED by streamed similarity rows
     if (predictor == KNNCF_PRED_PERSONALIZED) {
         if (h->cfg.similarity == KNNCF_SIM_ONE) {
             kind = KNNCF_PRED_BASELINE_RDD;  // num/den = file-order mean of the item's deviations (see predict.hip)
+        } else if (personalized_streams(h)) {
+            ensure_personal_rows(h);
+            stream = true;
         } else {  // the adjusted cosine / the Jaccard coefficient themselves: every user is a "neighbour"
             ensure_personalized_table(h);
             kind = KNNCF_PRED_KNN;
             table = &h->pt;
         }
     }
-    KN_REQUIRE(kind >= KNNCF_PRED_GLOBAL_AVG && kind <= KNNCF_PRED_KNN, KNNCF_E_INVALID, "unknown predictor");
+    KN_REQUIRE(stream || (kind >= KNNCF_PRED_GLOBAL_AVG && kind <= KNNCF_PRED_KNN), KNNCF_E_INVALID, "unknown predictor");
     if (kind == KNNCF_PRED_ITEM_AVG || kind == KNNCF_PRED_BASELINE || kind == KNNCF_PRED_BASELINE_RDD) ensure_item_stats(h);
     ensure_test_scratch(h, n);
     {
@@ -741,9 +829,10 @@ void run_predict(knncf_handle* h, int predictor, const int32_t* d_users, const i
     }
     if (kind == KNNCF_PRED_KNN && table == &h->nt) ensure_neighbors_for_rows(h, n);
     h->prep.join_commit(st);  // the item-major copies and the rater bitmaps (second part of prep_commit)
+    double* pred = d_pred_out ? d_pred_out : h->t_pred.p;
+    if (stream) predict_personal_rows(h, d_ratings, n, pred);
     {
         Stage s(h, &h->tm.predict_ms);
-        double* pred = d_pred_out ? d_pred_out : h->t_pred.p;
         const uint32_t* d_order = nullptr;
         const bool by_item = tr.ib_words > 0 && tr.ib_words * 12 <= 48 * 1024;
         int64_t n_rows = n;  // rows the prediction kernel walks
@@ -768,7 +857,7 @@ void run_predict(knncf_handle* h, int predictor, const int32_t* d_users, const i
             }
             d_order = sc.v32_b.p;
         }
-        if (n_rows > 0)
+        if (n_rows > 0 && !stream)
             launch_predict(tr, table, kind, n_rows, h->t_du.p, h->t_di.p, d_ratings, d_order, by_item, pred, h->t_err.p, h->t_owned.p,
                            h->cfg.shard_rank == 0, st);
         if (sum_abs_err || count) {
@@ -796,6 +885,7 @@ void do_fit_device(knncf_handle* h, const int32_t* d_users, const int32_t* d_ite
     h->short_rows = -1;
     h->b_ready = false;
     h->pt_ready = false;
+    h->prow_ready = false;
     h->h_ukeys.clear(); h->h_ikeys.clear(); h->h_uid.clear();
     tr.n = n;
     tr.jaccard = h->cfg.similarity == KNNCF_SIM_JACCARD;

@@ -78,6 +78,8 @@ __host__ __device__ inline double scale_fn(double x, double y) {
     else if (x < y) return y - 1;
     else return 1;
 }
+// predictor :568-585 given the user's mean and the weighted-sum deviation
+__host__ __device__ inline double combine(double ua, double wsd) { return ua + wsd * scale_fn(ua + wsd, ua); }
 
 // raw id -> dense index.  keys[] holds the trie keys of the distinct ids in DENSE order:
 // ascending (binary search) when count > 4, first-occurrence order (linear scan) otherwise.

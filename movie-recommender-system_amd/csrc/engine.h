@@ -251,6 +251,33 @@ void launch_owned_keys(int64_t n, const int32_t* d_src, const int32_t* d_du, int
 void launch_reduce_err(const double* d_abs_err, const uint8_t* d_owned, int64_t n, double* d_partials,
                        int64_t* d_counts, int32_t n_blocks, hipStream_t st);
 
+// ---- personalized.hip: PERSONALIZED (no k) with the adjusted cosine / the Jaccard coefficient beyond the U x U table ----
+// columns of a similarity row that k_sim_rows accumulates in LDS at a time (fp64: 64 KiB)
+static constexpr int PERSONAL_TCOLS = 8192;
+// per-handle copies built on the first streamed PERSONALIZED call (api.cpp: ensure_personal_rows), dropped by a re-fit
+struct PersonalRows {
+    DArr<double> pi_pre;     // [n] preprocessed rating of the q-th entry in (item, user ascending) order (it_user's order)
+    DArr<int32_t> pf_user;   // [n] dense rater of the k-th entry in (item, train file row) order (ratedI(i) :508-517)
+    DArr<double> pf_dev;     // [n] that rating's normalized deviation
+    int32_t tiles = 0;       // ceil(U / PERSONAL_TCOLS)
+    DArr<uint32_t> tile;     // [I * (tiles + 1)] tile[i][t] = first entry q of item i with it_user[q] >= t * PERSONAL_TCOLS
+    DArr<double> S;          // [R * U] row scratch: the exact similarity rows of one block of users
+    DArr<int32_t> users;     // [U] the users whose rows are built, in test-row order
+    DArr<int32_t> slot;      // [U] row of S of each built user inside its block
+};
+// pi_pre, pf_user / pf_dev and the tile table (after prep_commit's second part)
+void personalized_prepare(const Train& tr, PrepScratch& sc, PersonalRows& pr, hipStream_t st);
+// key = (dense user or U when absent) << bits_for(I) | (dense item or I when absent), value = row
+void launch_personal_row_keys(const Train& tr, int64_t n, const int32_t* d_du, const int32_t* d_di, uint64_t* d_key,
+                              uint32_t* d_val, hipStream_t st);
+// S[r][v] = s(d_users[r], v) for r < n_users and every dense user v
+void launch_sim_rows(const Train& tr, const PersonalRows& pr, const int32_t* d_users, int32_t n_users, double* d_S, hipStream_t st);
+// predictions of the test rows d_order[0 .. n_rows): a row of a known user on a known item reads the user's row
+// d_S[d_slot[user]]
+void launch_fold_rows(const Train& tr, const PersonalRows& pr, int64_t n_rows, const uint32_t* d_order, const int32_t* d_du,
+                      const int32_t* d_di, const double* d_ratings, const int32_t* d_slot, const double* d_S, double* d_pred,
+                      double* d_abs_err, uint8_t* d_owned, hipStream_t st);
+
 // ---- reco.hip: recommendations :651-674 -------------------------------------------------------------------------
 // rows (user, every train item) for the prediction batch + the mask of the items the user rated
 void launch_reco_rows(const Train& tr, int32_t user_raw, int32_t du, int32_t* d_users, int32_t* d_items, uint8_t* d_rated, hipStream_t st);

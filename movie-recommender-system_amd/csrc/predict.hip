@@ -47,9 +47,6 @@ struct PredArgs {
     uint32_t n_bytes4;    // 4 * number of training ratings
 };
 
-// predictor :568-585 given the user's mean and the weighted-sum deviation
-__device__ __forceinline__ double combine(double ua, double wsd) { return ua + wsd * scale_fn(ua + wsd, ua); }
-
 __device__ __forceinline__ void wave_sync() {
     // lanes of one wave exchange data through LDS: order the accesses for the compiler (the LDS
     // queue itself is in order per wave)
