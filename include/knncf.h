@@ -213,6 +213,28 @@ int knncf_mae_device(knncf_handle* h, int predictor, const int32_t* d_users,
                      const int32_t* d_items, const double* d_ratings, int64_t n,
                      double* sum_abs_err, int64_t* count, double* d_pred);
 
+/* ---- MAE at many k from one neighbour build (predict/kNN.scala:73) -------------------------------------------------
+ * predict/kNN.scala:73 maps List(10, 30, 50, 100, 200, 300, 400, 800, 943) to
+ * MAE(predictor(train, weightedSumDeviation(train, getSimilarity(train, k, sim))), test), fresh closures per k.
+ * getNeighbors :603-616 is a stable sort followed by take(k), so every k's lists are prefixes of the lists at the largest k,
+ * built in the same order: one build at kcap = min(max(ks), U-1) answers every k.
+ * maes[q] == (knncf_set_k(h, ks[q]), knncf_mae(h, KNNCF_PRED_KNN, ...)), bit for bit.  predictions (optional, may be NULL):
+ * [n_k * n], row q holds the per-row predictions at ks[q].
+ * ks: strictly ascending, 1 <= ks[q] <= 2048, 1 <= n_k <= 64 (KNNCF_E_INVALID otherwise); values at or above U-1 all give
+ * the same column.  KNNCF_E_STATE before a fit and, for the host form, on a shard handle; KNNCF_E_UNSUPPORTED for
+ * KNNCF_SIM_ONE.  n == 0: NaN for every k.
+ * Handle state: the call ignores the neighbour lists the handle holds (from knncf_mae, knncf_neighbors_load, ...) and builds
+ * its own.  On return the neighbour memo is dropped, as knncf_reset_neighbors drops it, and the handle's k is unchanged — the
+ * state a knncf_set_k + knncf_mae loop over the same ks would leave behind, except for k.  knncf_get_timings: the one build's
+ * stage times, the sweep kernel as predict_ms. */
+int knncf_mae_sweep(knncf_handle* h, const int32_t* ks, int32_t n_k, const int32_t* users, const int32_t* items,
+                    const double* ratings, int64_t n, double* maes, double* predictions);
+/* device form, as knncf_mae_device: per-k partial sums over the rows this shard owns (sum_abs_err[n_k], one count),
+ * d_pred optional [n_k * n] (owned rows only) */
+int knncf_mae_sweep_device(knncf_handle* h, const int32_t* ks, int32_t n_k, const int32_t* d_users,
+                           const int32_t* d_items, const double* d_ratings, int64_t n, double* sum_abs_err,
+                           int64_t* count, double* d_pred);
+
 /* ---- multi-GPU exchange (one handle per GPU, collectives done by the host) - */
 /* After knncf_fit* on every shard, each shard holds the per-user means / norms
  * (the order-sensitive fp64 folds of K2 / K3) of ITS users only.  The host

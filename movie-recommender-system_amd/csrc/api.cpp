@@ -82,6 +82,7 @@ struct knncf_handle {
     DArr<unsigned long long> scalar_u64;
     DArr<uint8_t> t_owned;
     DArr<int64_t> t_counts;
+    DArr<int32_t> sweep_ks;  // [64] the k values of knncf_mae_sweep*
     // host mirrors for scalar queries
     std::vector<uint32_t> h_ukeys, h_ikeys;
     std::vector<int32_t> h_uid;
@@ -795,6 +796,54 @@ void ensure_item_stats(knncf_handle* h) {
     prep_item_stats(h->tr, h->prep, h->stream);
 }
 
+// The kNN kernels' row order over the test rows whose dense ids are in t_du / t_di: sorted by item (by_item) or by user,
+// the rows the train set cannot place last; the order is left in prep.v32_b.  On a shard handle the test set is replicated on
+// every shard and the work is not: this shard's rows sort first and only they are predicted; the other rows' error cells
+// (cols columns of n in t_err) and ownership cells are cleared here instead of by the kernel.  Returns the rows to predict.
+int64_t order_test_rows(knncf_handle* h, int64_t n, bool by_item, int32_t cols) {
+    Train& tr = h->tr;
+    hipStream_t st = h->stream;
+    PrepScratch& sc = h->prep;
+    sc.k64_a.ensure(n); sc.k64_b.ensure(n); sc.v32_a.ensure(n); sc.v32_b.ensure(n);
+    const uint32_t key_limit = (uint32_t)(by_item ? tr.I : tr.U);  // the key of a row whose item / user the train set lacks
+    if (h->cfg.shard_count > 1) {
+        h->scalar_u64.ensure(1);
+        KN_HIP(hipMemsetAsync(h->scalar_u64.p, 0, sizeof(unsigned long long), st));
+        KN_HIP(hipMemsetAsync(h->t_err.p, 0, (size_t)cols * (size_t)n * sizeof(double), st));
+        KN_HIP(hipMemsetAsync(h->t_owned.p, 0, (size_t)n, st));
+        launch_owned_keys(n, by_item ? h->t_di.p : h->t_du.p, h->t_du.p, tr.own_lo, tr.own_hi, h->cfg.shard_rank == 0, key_limit,
+                          sc.k64_a.p, sc.v32_a.p, h->scalar_u64.p, st);
+        sort_pairs_u64_u32(sc.sort, sc.k64_a.p, sc.k64_b.p, sc.v32_a.p, sc.v32_b.p, n, bits_for((uint64_t)key_limit + 1), st);
+        return (int64_t)fetch(h, h->scalar_u64.p, 0);
+    }
+    launch_user_keys(n, by_item ? h->t_di.p : h->t_du.p, key_limit, sc.k64_a.p, sc.v32_a.p, st);
+    sort_pairs_u64_u32(sc.sort, sc.k64_a.p, sc.k64_b.p, sc.v32_a.p, sc.v32_b.p, n, bits_for((uint64_t)key_limit), st);
+    return n;
+}
+
+// sum |r - p| of each of the cols columns of n cells in t_err (the deterministic fixed-shape reduction, one launch per column)
+// and the count of t_owned; sums[c] per column (either pointer may be null)
+void reduce_errors(knncf_handle* h, int64_t n, int32_t cols, double* sums, int64_t* count) {
+    hipStream_t st = h->stream;
+    const int32_t nb = 1024;
+    h->t_partial.ensure((size_t)nb * cols);
+    h->t_counts.ensure((size_t)nb * cols);
+    for (int32_t c = 0; c < cols; ++c)
+        launch_reduce_err(h->t_err.p + (size_t)c * n, h->t_owned.p, n, h->t_partial.p + (size_t)c * nb, h->t_counts.p + (size_t)c * nb, nb, st);
+    std::vector<double> hp((size_t)nb * cols);
+    std::vector<int64_t> hc((size_t)nb * cols);
+    KN_HIP(hipMemcpyAsync(hp.data(), h->t_partial.p, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    KN_HIP(hipMemcpyAsync(hc.data(), h->t_counts.p, hc.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    KN_HIP(hipStreamSynchronize(st));
+    for (int32_t c = 0; c < cols; ++c) {
+        double s_ = 0.0;
+        int64_t c_ = 0;
+        for (int32_t b = 0; b < nb; ++b) { s_ += hp[(size_t)c * nb + b]; c_ += hc[(size_t)c * nb + b]; }
+        if (sums) sums[c] = s_;
+        if (count && c == 0) *count = c_;
+    }
+}
+
 void run_predict(knncf_handle* h, int predictor, const int32_t* d_users, const int32_t* d_items,
                  const double* d_ratings, int64_t n, double* sum_abs_err, int64_t* count, double* d_pred_out) {
     require_fitted(h);
@@ -837,43 +886,71 @@ void run_predict(knncf_handle* h, int predictor, const int32_t* d_users, const i
         const bool by_item = tr.ib_words > 0 && tr.ib_words * 12 <= 48 * 1024;
         int64_t n_rows = n;  // rows the prediction kernel walks
         if (kind == KNNCF_PRED_KNN) {  // rows sorted by item (the item's rater bitmap lives in LDS) or else by user
-            PrepScratch& sc = h->prep;
-            sc.k64_a.ensure(n); sc.k64_b.ensure(n); sc.v32_a.ensure(n); sc.v32_b.ensure(n);
-            const uint32_t key_limit = (uint32_t)(by_item ? tr.I : tr.U);  // the key of a row whose item / user the train set lacks
-            if (h->cfg.shard_count > 1) {
-                // the test set is replicated on every shard, the work is not: this shard's rows sort first and only they are
-                // predicted; the other rows' error / ownership cells are cleared here instead of by the kernel
-                h->scalar_u64.ensure(1);
-                KN_HIP(hipMemsetAsync(h->scalar_u64.p, 0, sizeof(unsigned long long), st));
-                KN_HIP(hipMemsetAsync(h->t_err.p, 0, (size_t)n * sizeof(double), st));
-                KN_HIP(hipMemsetAsync(h->t_owned.p, 0, (size_t)n, st));
-                launch_owned_keys(n, by_item ? h->t_di.p : h->t_du.p, h->t_du.p, tr.own_lo, tr.own_hi, h->cfg.shard_rank == 0, key_limit,
-                                  sc.k64_a.p, sc.v32_a.p, h->scalar_u64.p, st);
-                sort_pairs_u64_u32(sc.sort, sc.k64_a.p, sc.k64_b.p, sc.v32_a.p, sc.v32_b.p, n, bits_for((uint64_t)key_limit + 1), st);
-                n_rows = (int64_t)fetch(h, h->scalar_u64.p, 0);
-            } else {
-                launch_user_keys(n, by_item ? h->t_di.p : h->t_du.p, key_limit, sc.k64_a.p, sc.v32_a.p, st);
-                sort_pairs_u64_u32(sc.sort, sc.k64_a.p, sc.k64_b.p, sc.v32_a.p, sc.v32_b.p, n, bits_for((uint64_t)key_limit), st);
-            }
-            d_order = sc.v32_b.p;
+            n_rows = order_test_rows(h, n, by_item, 1);
+            d_order = h->prep.v32_b.p;
         }
         if (n_rows > 0 && !stream)
             launch_predict(tr, table, kind, n_rows, h->t_du.p, h->t_di.p, d_ratings, d_order, by_item, pred, h->t_err.p, h->t_owned.p,
                            h->cfg.shard_rank == 0, st);
-        if (sum_abs_err || count) {
-            const int32_t nb = 1024;
-            launch_reduce_err(h->t_err.p, h->t_owned.p, n, h->t_partial.p, h->t_counts.p, nb, st);
-            std::vector<double> hp(nb);
-            std::vector<int64_t> hc(nb);
-            KN_HIP(hipMemcpyAsync(hp.data(), h->t_partial.p, nb * sizeof(double), hipMemcpyDeviceToHost, st));
-            KN_HIP(hipMemcpyAsync(hc.data(), h->t_counts.p, nb * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-            KN_HIP(hipStreamSynchronize(st));
-            double s_ = 0.0;
-            int64_t c_ = 0;
-            for (int32_t b = 0; b < nb; ++b) { s_ += hp[b]; c_ += hc[b]; }
-            if (sum_abs_err) *sum_abs_err = s_;
-            if (count) *count = c_;
+        if (sum_abs_err || count) reduce_errors(h, n, 1, sum_abs_err, count);
+    }
+}
+
+// ks of knncf_mae_sweep*: 1 .. 64 values, strictly ascending, each in [1, 2048]
+void check_sweep_ks(const int32_t* ks, int32_t n_k) {
+    KN_REQUIRE(ks && n_k >= 1 && n_k <= 64, KNNCF_E_INVALID, "sweep: 1 .. 64 values of k");
+    for (int32_t q = 0; q < n_k; ++q)
+        KN_REQUIRE(ks[q] >= 1 && ks[q] <= 2048 && (q == 0 || ks[q] > ks[q - 1]), KNNCF_E_INVALID,
+                   "sweep: k must be strictly ascending in [1, 2048]");
+}
+
+// predict/kNN.scala:73 — the MAE at every k of ks[0 .. n_k) with fresh closures for each k, from ONE neighbour build: the lists
+// at kmax = ks[n_k - 1] are built in the order ensure_neighbors_for_rows builds them (a user's list at its first test row on an
+// item with raters: the same order, hence the same memo history, for every k) and k_predict_knn_sweep folds each k over the
+// first k entries of them.  Whatever lists the handle held are ignored; on every return path the memo is dropped (as
+// knncf_reset_neighbors) and the handle's k is the caller's.  sums[q] / *count: as run_predict; d_pred (may be null):
+// [n_k * n] (row q: the predictions at ks[q]).
+void run_mae_sweep(knncf_handle* h, const int32_t* ks, int32_t n_k, const int32_t* d_users, const int32_t* d_items,
+                   const double* d_ratings, int64_t n, double* sums, int64_t* count, double* d_pred) {
+    check_sweep_ks(ks, n_k);
+    require_fitted(h);
+    KN_REQUIRE(h->cfg.similarity != KNNCF_SIM_ONE, KNNCF_E_UNSUPPORTED,
+               "kNN neighbourhoods with similarityOne: every similarity is 1.0, the neighbourhood is the first k users in Set order — not built");
+    KN_REQUIRE(n >= 0, KNNCF_E_INVALID, "negative row count");
+    for (int32_t q = 0; q < n_k; ++q) sums[q] = 0.0;
+    *count = 0;
+    if (n == 0) return;
+    KN_REQUIRE(d_users && d_items && d_ratings, KNNCF_E_INVALID, "null test arrays");
+    Train& tr = h->tr;
+    hipStream_t st = h->stream;
+    struct Restore {  // the caller's k and a dropped memo, whichever way the call ends
+        knncf_handle* h;
+        int32_t k;
+        ~Restore() {
+            h->cfg.k = k;
+            try { reset_neighbors(h); } catch (const Error&) {}
         }
+    } restore{h, h->cfg.k};
+    h->cfg.k = ks[n_k - 1];
+    reset_neighbors(h);  // fresh closures at kcap = min(kmax, U - 1)
+    ensure_test_scratch(h, n);
+    h->t_err.ensure((size_t)n_k * n);
+    {
+        Stage s(h, &h->tm.predict_ms);
+        launch_dense_ids(tr, d_users, d_items, n, h->t_du.p, h->t_di.p, st);
+    }
+    ensure_neighbors_for_rows(h, n);
+    h->prep.join_commit(st);  // the item-major copies and the rater bitmaps (second part of prep_commit)
+    std::vector<int32_t> hk(ks, ks + n_k);
+    h->sweep_ks.ensure(64);
+    KN_HIP(hipMemcpyAsync(h->sweep_ks.p, hk.data(), (size_t)n_k * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    {
+        Stage s(h, &h->tm.predict_ms);
+        const int64_t n_rows = order_test_rows(h, n, /*by_item=*/true, n_k);
+        if (n_rows > 0)  // (one train user: kcap = 0, every row is predicted without neighbours, as run_predict does)
+            launch_predict_sweep(tr, h->nt, h->sweep_ks.p, n_k, n_rows, n, h->t_du.p, h->t_di.p, d_ratings, h->prep.v32_b.p, d_pred,
+                                 h->t_err.p, h->t_owned.p, h->cfg.shard_rank == 0, st);
+        reduce_errors(h, n, n_k, sums, count);
     }
 }
 
@@ -1515,6 +1592,42 @@ int knncf_mae(knncf_handle* h, int predictor, const int32_t* users, const int32_
         int64_t c = 0;
         run_predict(h, predictor, h->t_users.p, h->t_items.p, h->t_ratings.p, n, &s, &c, nullptr);
         *mae = s / (double)n;
+    });
+}
+
+int knncf_mae_sweep_device(knncf_handle* h, const int32_t* ks, int32_t n_k, const int32_t* d_users, const int32_t* d_items,
+                           const double* d_ratings, int64_t n, double* sum_abs_err, int64_t* count, double* d_pred) {
+    return guarded(h, [&] {
+        KN_REQUIRE(sum_abs_err && count, KNNCF_E_INVALID, "bad arguments");
+        run_mae_sweep(h, ks, n_k, d_users, d_items, d_ratings, n, sum_abs_err, count, d_pred);
+    });
+}
+
+int knncf_mae_sweep(knncf_handle* h, const int32_t* ks, int32_t n_k, const int32_t* users, const int32_t* items,
+                    const double* ratings, int64_t n, double* maes, double* predictions) {
+    return guarded(h, [&] {
+        check_sweep_ks(ks, n_k);
+        KN_REQUIRE(maes && n >= 0 && (n == 0 || (users && items && ratings)), KNNCF_E_INVALID, "bad arguments");
+        KN_REQUIRE(h->cfg.shard_count == 1, KNNCF_E_STATE, "sharded handle: use knncf_mae_sweep_device and all-reduce the partial sums");
+        require_fitted(h);
+        KN_REQUIRE(h->cfg.similarity != KNNCF_SIM_ONE, KNNCF_E_UNSUPPORTED, "kNN predictor with similarityOne");
+        if (n == 0) {  // 0.0 / 0 in applyAndMean :85
+            for (int32_t q = 0; q < n_k; ++q) maes[q] = NAN;
+            return;
+        }
+        h->t_users.ensure(n); h->t_items.ensure(n); h->t_ratings.ensure(n);
+        KN_HIP(hipMemcpyAsync(h->t_users.p, users, n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+        KN_HIP(hipMemcpyAsync(h->t_items.p, items, n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+        KN_HIP(hipMemcpyAsync(h->t_ratings.p, ratings, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        if (predictions) h->t_pred.ensure((size_t)n_k * n);
+        std::vector<double> s(n_k);
+        int64_t c = 0;
+        run_mae_sweep(h, ks, n_k, h->t_users.p, h->t_items.p, h->t_ratings.p, n, s.data(), &c, predictions ? h->t_pred.p : nullptr);
+        for (int32_t q = 0; q < n_k; ++q) maes[q] = s[q] / (double)n;
+        if (predictions) {
+            KN_HIP(hipMemcpyAsync(predictions, h->t_pred.p, (size_t)n_k * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            KN_HIP(hipStreamSynchronize(h->stream));
+        }
     });
 }
 

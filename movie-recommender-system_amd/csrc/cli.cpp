@@ -281,11 +281,14 @@ Json run_knn(const Args& a, const Ratings& train, const Ratings& test) {  // pre
     check(e.h, knncf_reset_neighbors(e.h), "reset");
     n1.set("4.PredUser1Item1", Json::Num(e.predict(KNNCF_PRED_KNN, 1, 1)));
     out.set("N.1", n1);
+    // every k from one neighbour build (knncf_mae_sweep: the same values as knncf_set_k + knncf_mae per k)
+    const int32_t ks[] = {10, 30, 50, 100, 200, 300, 400, 800, 943};
+    const int32_t n_k = (int32_t)(sizeof(ks) / sizeof(ks[0]));
+    double kmae[sizeof(ks) / sizeof(ks[0])];
+    check(e.h, knncf_mae_sweep(e.h, ks, n_k, test.users.data(), test.items.data(), test.ratings.data(), test.size(), kmae, nullptr),
+          "mae_sweep");
     Json maes = Json::Arr();
-    for (int k : {10, 30, 50, 100, 200, 300, 400, 800, 943}) {
-        check(e.h, knncf_set_k(e.h, k), "set_k");
-        maes.push(Json::Arr().push(Json::Num(k)).push(Json::Num(e.mae(KNNCF_PRED_KNN, test))));
-    }
+    for (int32_t q = 0; q < n_k; ++q) maes.push(Json::Arr().push(Json::Num(ks[q])).push(Json::Num(kmae[q])));
     out.set("N.2", Json::Obj().set("1.kNN-Mae", maes));
     out.set("N.3", Json::Obj().set("1.kNN", timing_obj(times)));
     return out;

@@ -251,6 +251,14 @@ void launch_owned_keys(int64_t n, const int32_t* d_src, const int32_t* d_du, int
 void launch_reduce_err(const double* d_abs_err, const uint8_t* d_owned, int64_t n, double* d_partials,
                        int64_t* d_counts, int32_t n_blocks, hipStream_t st);
 
+// ---- ksweep.hip: the kNN prediction at several k from one neighbour table (knncf_mae_sweep) ----------------------
+// per test row d_order[0 .. n): the kNN prediction at every k = d_ks[q] (ascending, q < n_k <= 64) from the first k entries of the
+// row user's reference-order list in nt (kcap <= 2048); rows sorted by dense item.  Cell q * n_total + row of d_pred (may be
+// null) / d_abs_err; rows of other shards' users: abs_err 0 in every column, owned 0
+void launch_predict_sweep(const Train& tr, const NeighborTable& nt, const int32_t* d_ks, int32_t n_k, int64_t n_rows, int64_t n_total,
+                          const int32_t* d_du, const int32_t* d_di, const double* d_ratings, const uint32_t* d_order,
+                          double* d_pred, double* d_abs_err, uint8_t* d_owned, bool unknown_users_owned, hipStream_t st);
+
 // ---- personalized.hip: PERSONALIZED (no k) with the adjusted cosine / the Jaccard coefficient beyond the U x U table ----
 // columns of a similarity row that k_sim_rows accumulates in LDS at a time (fp64: 64 KiB)
 static constexpr int PERSONAL_TCOLS = 8192;

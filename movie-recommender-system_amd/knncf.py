@@ -117,7 +117,7 @@ EXPORTS = [
     "knncf_user_avg", "knncf_item_avg", "knncf_item_avg_dev", "knncf_item_avg_dev_rdd", "knncf_similarity",
     "knncf_knn_similarity", "knncf_neighbors", "knncf_neighbors_batch", "knncf_predict", "knncf_recommend",
     "knncf_query_neighbors", "knncf_query_predict", "knncf_query_recommend", "knncf_predict_batch",
-    "knncf_predict_batch_device", "knncf_mae", "knncf_mae_device", "knncf_shard_view_get",
+    "knncf_predict_batch_device", "knncf_mae", "knncf_mae_device", "knncf_mae_sweep", "knncf_mae_sweep_device", "knncf_shard_view_get",
     "knncf_shard_commit", "knncf_get_timings", "knncf_reset_timings", "knncf_reset_neighbors",
     "knncf_set_k", "knncf_load_file", "knncf_load_file_cached", "knncf_free_ratings", "knncf_load_personal", "knncf_free_personal", "knncf_neighbors_save", "knncf_neighbors_load",
     "knncf_group_create", "knncf_group_destroy", "knncf_group_last_error", "knncf_group_size", "knncf_group_handle",
@@ -203,6 +203,9 @@ def load_library():
     L.knncf_mae.argtypes = [C.c_void_p, C.c_int, _i32p, _i32p, _f64p, C.c_int64, _f64p]
     L.knncf_mae_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                    _f64p, C.POINTER(C.c_int64), C.c_void_p]
+    L.knncf_mae_sweep.argtypes = [C.c_void_p, _i32p, C.c_int32, _i32p, _i32p, _f64p, C.c_int64, _f64p, _f64p]
+    L.knncf_mae_sweep_device.argtypes = [C.c_void_p, _i32p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, _f64p,
+                                         C.POINTER(C.c_int64), C.c_void_p]
     L.knncf_shard_view_get.argtypes = [C.c_void_p, C.POINTER(ShardView)]
     L.knncf_shard_commit.argtypes = [C.c_void_p]
     L.knncf_get_timings.argtypes = [C.c_void_p, C.POINTER(Timings)]
@@ -470,6 +473,31 @@ class Engine:
         self._check(self._lib.knncf_mae_device(self._h, predictor, _dev_ptr(users, "int32"), _dev_ptr(items, "int32"),
                                                _dev_ptr(ratings, "float64"), users.numel(), C.byref(s), C.byref(c), p))
         return s.value, c.value
+
+    def mae_sweep(self, ks, users, items, ratings, predictions=False):
+        """MAE of PRED_KNN at every k of ks (strictly ascending) from one neighbour build (predict/kNN.scala:73):
+        float64 [n_k]; with predictions=True also the per-row predictions [n_k, n].  The handle's k is unchanged and its
+        neighbour memo dropped afterwards."""
+        kk, u, i, r = _i32(ks), _i32(users), _i32(items), _f64(ratings)
+        out = np.empty(len(kk), dtype=np.float64)
+        per = np.empty((len(kk), len(u)), dtype=np.float64) if predictions else None
+        self._check(self._lib.knncf_mae_sweep(self._h, kk.ctypes.data_as(_i32p), len(kk), u.ctypes.data_as(_i32p),
+                                              i.ctypes.data_as(_i32p), r.ctypes.data_as(_f64p), len(u),
+                                              out.ctypes.data_as(_f64p),
+                                              per.ctypes.data_as(_f64p) if per is not None else None))
+        return (out, per) if predictions else out
+
+    def mae_sweep_device(self, ks, users, items, ratings, pred_out=None):
+        """Per-k partial sums (sums[n_k], count) over the rows this shard owns; tensors on the device, pred_out [n_k, n]."""
+        kk = _i32(ks)
+        sums = np.zeros(len(kk), dtype=np.float64)
+        c = C.c_int64()
+        p = _dev_ptr(pred_out, "float64") if pred_out is not None else None
+        _producer_done(users)
+        self._check(self._lib.knncf_mae_sweep_device(self._h, kk.ctypes.data_as(_i32p), len(kk), _dev_ptr(users, "int32"),
+                                                     _dev_ptr(items, "int32"), _dev_ptr(ratings, "float64"), users.numel(),
+                                                     sums.ctypes.data_as(_f64p), C.byref(c), p))
+        return sums, c.value
 
     # ---- sharding ----------------------------------------------------------------------
     def shard_view(self):
