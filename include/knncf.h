@@ -197,6 +197,42 @@ int knncf_query_predict(knncf_handle* h, int predictor, int32_t user, const int3
 int knncf_query_recommend(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
                           int64_t n_ratings, int32_t n, int32_t* out_items, double* out_preds, int32_t* count);
 
+/* ---- Batched fold-in queries: many users outside the fit in one call -------------------------------------------------------
+ * n_queries independent queries, CSR-style: query b is (users[b], items[offsets[b] .. offsets[b + 1]), ratings[...]) with
+ * offsets[0] == 0, offsets non-decreasing, fewer than 2^31 ratings in all.
+ *   knncf_query_neighbors_batch   ids / sims [n_queries * cap]: row b = knncf_query_neighbors of query b, counts[b] its *count;
+ *   knncf_query_predict_batch     out[pred_offsets[b] .. pred_offsets[b + 1]) = knncf_query_predict of query b on
+ *                                 pred_items[pred_offsets[b] ..) (pred_offsets: a CSR like offsets);
+ *   knncf_query_recommend_batch   out_items / out_preds [n_queries * n]: row b = knncf_query_recommend of query b, counts[b] its
+ *                                 *count.
+ * Row b is the single call's answer, bit for bit.  The queries are independent: each is answered on aug_b = train ++ the rows
+ * of query b alone, fresh closures, first evaluation the query user's; the other queries of the batch are not part of aug_b, so
+ * the same raw user id may occur in several queries, and permuting the queries permutes the rows and changes nothing else.
+ * statuses[b] is the status the single call would return for query b: KNNCF_OK, KNNCF_E_INVALID (the user occurs in train, or
+ * the query is empty), KNNCF_E_DUPLICATE, KNNCF_E_NONFINITE, KNNCF_E_UNSUPPORTED (negative mean, more than 65536 ratings).  A
+ * failed query gets counts[b] = 0, its output row is left untouched, and it does not disturb the other queries.
+ * The return value reports what is wrong with the call or the handle, as the single calls do: KNNCF_E_STATE before a fit;
+ * KNNCF_E_UNSUPPORTED for KNNCF_SIM_ONE, a shard handle, fewer than 5 train users or a predictor other than KNNCF_PRED_KNN;
+ * KNNCF_E_INVALID for a null pointer, n_queries < 0, cap or n < 0, or offsets that are not a CSR.  n_queries == 0 is KNNCF_OK
+ * and touches nothing.  After a call with failed queries knncf_last_error names the first failed query and its reason.
+ * Read-only on the handle, as the single calls.
+ * Chunks.  The batch is answered in chunks of consecutive queries, [0, C), [C, 2 C), ..., the last one possibly shorter:
+ *     C = max(1, min(64, budget / (64 * num_users + 96 * num_items), (2^31 - 1) / max(num_users, num_items)))
+ *     budget = workspace_bytes / 2 if workspace_bytes > 0, else min(48 GiB, free device memory / 4)
+ * so a call makes ceil(n_queries / C) chunks.  (The gathered neighbour ratings of a chunk are allocated beside that as they
+ * are needed; a chunk whose neighbours hold 2^32 - 1 ratings or more fails the call with KNNCF_E_UNSUPPORTED.)  Failed queries
+ * keep their place in their chunk.  A chunk with fewer than 32 answerable queries runs the single-query similarity kernel once
+ * per query; larger ones read every train row once for the whole chunk.  The results do not depend on C. */
+int knncf_query_neighbors_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                                const double* ratings, int64_t n_queries, int32_t cap, int32_t* ids, double* sims, int32_t* counts,
+                                int32_t* statuses);
+int knncf_query_predict_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                              const double* ratings, int64_t n_queries, const int64_t* pred_offsets, const int32_t* pred_items,
+                              double* out, int32_t* statuses);
+int knncf_query_recommend_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                                const double* ratings, int64_t n_queries, int32_t n, int32_t* out_items, double* out_preds,
+                                int32_t* counts, int32_t* statuses);
+
 /* ---- batch ---------------------------------------------------------------- */
 int knncf_predict_batch(knncf_handle* h, int predictor, const int32_t* users,
                         const int32_t* items, int64_t n, double* out);

@@ -74,6 +74,7 @@ struct knncf_handle {
     DArr<double> reco_pred, reco_out_preds;
     DArr<uint8_t> reco_rated;
     QueryScratch query;  // fold-in queries (foldin.hip)
+    QueryBatchScratch query_batch;
     DArr<int32_t> build_list, build_count;
     DArr<uint32_t> first_row;
     // test scratch
@@ -1093,6 +1094,174 @@ void do_query_recommend(knncf_handle* h, int predictor, int32_t user, const int3
     *count = m;
 }
 
+// ---- batched fold-in queries: B independent queries, answered chunk by chunk (foldin.hip, "batched") -----------------------
+enum QueryBatchMode { QB_NEIGHBORS, QB_PREDICT, QB_RECOMMEND };
+
+// queries per chunk: the rule of knncf.h ("Batched fold-in queries")
+int64_t query_batch_chunk(knncf_handle* h) {
+    const Train& tr = h->tr;
+    int64_t budget = h->cfg.workspace_bytes / 2;
+    if (h->cfg.workspace_bytes <= 0) {
+        size_t free_b = 0, total_b = 0;
+        KN_HIP(hipMemGetInfo(&free_b, &total_b));
+        budget = (int64_t)std::min<size_t>((size_t)48 << 30, free_b / 4);
+    }
+    int64_t C = std::min<int64_t>(QB_MAX_CHUNK, budget / query_batch_bytes(tr.U, tr.I));
+    C = std::min<int64_t>(C, (int64_t)0x7fffffff / std::max(tr.U, tr.I));  // slot * U + user and slot * I + item are 31-bit cells
+    return std::max<int64_t>(C, 1);
+}
+
+// mode QB_NEIGHBORS: width = cap, out_i / out_d = ids / sims [B * cap]; QB_RECOMMEND: width = n, out_i / out_d = items /
+// predictions [B * n]; QB_PREDICT: out_d [pred_offsets[B]]
+void do_query_batch(knncf_handle* h, QueryBatchMode mode, int predictor, const int32_t* users, const int64_t* offsets,
+                    const int32_t* items, const double* ratings, int64_t B, int32_t width, const int64_t* pred_offsets,
+                    const int32_t* pred_items, int32_t* out_i, double* out_d, int32_t* counts, int32_t* statuses) {
+    require_fitted(h, false);
+    KN_REQUIRE(B >= 0, KNNCF_E_INVALID, "query batch: n_queries < 0");
+    KN_REQUIRE(mode == QB_PREDICT || width >= 0, KNNCF_E_INVALID, "query batch: cap or n < 0");
+    KN_REQUIRE(predictor == KNNCF_PRED_KNN, KNNCF_E_UNSUPPORTED, "query: only KNNCF_PRED_KNN");
+    KN_REQUIRE(h->cfg.similarity != KNNCF_SIM_ONE, KNNCF_E_UNSUPPORTED, "query: adjusted cosine or Jaccard");
+    KN_REQUIRE(h->cfg.shard_count == 1, KNNCF_E_UNSUPPORTED, "query: single-shard handles only");
+    KN_REQUIRE(h->tr.U >= 5, KNNCF_E_UNSUPPORTED, "query: fewer than 5 train users (the user set changes iteration class)");
+    if (B == 0) return;
+    KN_REQUIRE(users && offsets && statuses && (mode == QB_PREDICT || counts), KNNCF_E_INVALID, "query batch: null argument");
+    KN_REQUIRE(offsets[0] == 0, KNNCF_E_INVALID, "query batch: offsets[0] != 0");
+    for (int64_t b = 0; b < B; ++b) KN_REQUIRE(offsets[b] <= offsets[b + 1], KNNCF_E_INVALID, "query batch: offsets decrease");
+    KN_REQUIRE(offsets[B] < ((int64_t)1 << 31), KNNCF_E_INVALID, "query batch: 2^31 or more ratings in one call");
+    KN_REQUIRE(offsets[B] == 0 || (items && ratings), KNNCF_E_INVALID, "query batch: null ratings");
+    if (mode == QB_PREDICT) {
+        KN_REQUIRE(pred_offsets && pred_offsets[0] == 0, KNNCF_E_INVALID, "query batch: pred_offsets null or not starting at 0");
+        for (int64_t b = 0; b < B; ++b)
+            KN_REQUIRE(pred_offsets[b] <= pred_offsets[b + 1], KNNCF_E_INVALID, "query batch: pred_offsets decrease");
+        KN_REQUIRE(pred_offsets[B] == 0 || (pred_items && out_d), KNNCF_E_INVALID, "query batch: null prediction arguments");
+    } else {
+        KN_REQUIRE(width == 0 || (out_i && out_d), KNNCF_E_INVALID, "query batch: null output");
+    }
+    h->prep.join_commit(h->stream);
+    const Train& tr = h->tr;
+    QueryBatchScratch& bs = h->query_batch;
+    hipStream_t st = h->stream;
+    const int64_t chunk = query_batch_chunk(h);
+    const int32_t take = std::max(0, std::min(h->cfg.k, tr.U));
+    int64_t first_failed = -1;
+    const char* first_reason = "";
+    auto fail = [&](int64_t b, int status, const char* why) {
+        statuses[b] = status;
+        if (counts) counts[b] = 0;
+        if (first_failed < 0 || b < first_failed) { first_failed = b; first_reason = why; }
+    };
+    std::vector<int64_t> slot_query, qo, ebase;
+    std::vector<int32_t> s_users, s_items, h_idx, h_items, pick_slot, pick_items;
+    std::vector<double> s_ratings, h_vals;
+    std::vector<long long> info;
+    for (int64_t c0 = 0; c0 < B; c0 += chunk) {
+        const int64_t c1 = std::min(B, c0 + chunk);
+        // the chunk's answerable queries, slot after slot
+        slot_query.clear(); s_users.clear(); s_items.clear(); s_ratings.clear();
+        qo.assign(1, 0);
+        for (int64_t b = c0; b < c1; ++b) {
+            const int64_t nb = offsets[b + 1] - offsets[b];
+            if (nb <= 0) { fail(b, KNNCF_E_INVALID, "null ratings or n_ratings <= 0"); continue; }
+            if (nb > QUERY_MAX_RATINGS) { fail(b, KNNCF_E_UNSUPPORTED, "more than 65536 ratings"); continue; }
+            if (dense_user(h, users[b]) >= 0) { fail(b, KNNCF_E_INVALID, "the user occurs in the training set"); continue; }
+            slot_query.push_back(b);
+            s_users.push_back(users[b]);
+            s_items.insert(s_items.end(), items + offsets[b], items + offsets[b + 1]);
+            s_ratings.insert(s_ratings.end(), ratings + offsets[b], ratings + offsets[b + 1]);
+            qo.push_back((int64_t)s_items.size());
+        }
+        const int32_t C = (int32_t)slot_query.size();
+        if (C == 0) continue;
+        info.assign((size_t)4 * C, 0);
+        foldin_batch_neighbors(tr, bs, h->prep.sort, C, s_users.data(), qo.data(), s_items.data(), s_ratings.data(), h->cfg.k,
+                               info.data(), st);
+        int32_t good = 0;
+        for (int32_t s = 0; s < C; ++s) {
+            const uint64_t bits = (uint64_t)info[4 * s];
+            const int64_t b = slot_query[s];
+            if (bits & ST_DUPLICATE) fail(b, KNNCF_E_DUPLICATE, "the ratings repeat an item");
+            else if (bits & ST_NONFINITE) fail(b, KNNCF_E_NONFINITE, "scale() == 0 gives a non-finite deviation");
+            else if (bits & QUERY_ST_NEG_MEAN) fail(b, KNNCF_E_UNSUPPORTED, "a negative mean rating (the predictor would answer aug's global average)");
+            else { statuses[b] = KNNCF_OK; ++good; }
+        }
+        if (good == 0) continue;
+        if (mode == QB_NEIGHBORS) {
+            const int32_t c = std::min(take, width);
+            if (c > 0) {
+                h_idx.resize((size_t)C * take); h_vals.resize((size_t)C * take);
+                KN_HIP(hipMemcpyAsync(h_idx.data(), bs.nbr_idx.p, h_idx.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+                KN_HIP(hipMemcpyAsync(h_vals.data(), bs.nbr_sim.p, h_vals.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+                KN_HIP(hipStreamSynchronize(st));
+                load_host_ids(h);
+            }
+            for (int32_t s = 0; s < C; ++s) {
+                const int64_t b = slot_query[s];
+                if (statuses[b] != KNNCF_OK) continue;
+                for (int32_t j = 0; j < c; ++j) {
+                    out_i[b * width + j] = h->h_uid[h_idx[(size_t)s * take + j]];
+                    out_d[b * width + j] = h_vals[(size_t)s * take + j];
+                }
+                counts[b] = take;
+            }
+            continue;
+        }
+        ebase.assign((size_t)C + 1, 0);
+        for (int32_t s = 0; s < C; ++s) ebase[s + 1] = ebase[s] + info[4 * s + 2];
+        if (mode == QB_PREDICT) {
+            pick_slot.clear(); pick_items.clear();
+            for (int32_t s = 0; s < C; ++s) {
+                const int64_t b = slot_query[s];
+                if (statuses[b] != KNNCF_OK) continue;
+                pick_items.insert(pick_items.end(), pred_items + pred_offsets[b], pred_items + pred_offsets[b + 1]);
+                pick_slot.insert(pick_slot.end(), (size_t)(pred_offsets[b + 1] - pred_offsets[b]), s);
+            }
+            const int64_t m = (int64_t)pick_items.size();
+            if (m == 0) continue;
+            foldin_batch_predictions(tr, bs, h->prep.sort, C, take, ebase.data(), st);
+            bs.pick_items.ensure(m); bs.pick_slot.ensure(m); bs.pick_out.ensure(m);
+            KN_HIP(hipMemcpyAsync(bs.pick_items.p, pick_items.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            KN_HIP(hipMemcpyAsync(bs.pick_slot.p, pick_slot.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            foldin_batch_pick(tr, bs, bs.pick_items.p, bs.pick_slot.p, m, bs.pick_out.p, st);
+            h_vals.resize((size_t)m);
+            KN_HIP(hipMemcpyAsync(h_vals.data(), bs.pick_out.p, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
+            KN_HIP(hipStreamSynchronize(st));
+            int64_t at = 0;
+            for (int32_t s = 0; s < C; ++s) {
+                const int64_t b = slot_query[s];
+                if (statuses[b] != KNNCF_OK) continue;
+                const int64_t mb = pred_offsets[b + 1] - pred_offsets[b];
+                std::copy(h_vals.begin() + at, h_vals.begin() + at + mb, out_d + pred_offsets[b]);
+                at += mb;
+            }
+            continue;
+        }
+        // QB_RECOMMEND
+        int32_t widest = 0;
+        for (int32_t s = 0; s < C; ++s) {
+            const int64_t b = slot_query[s];
+            if (statuses[b] != KNNCF_OK) continue;
+            counts[b] = (int32_t)std::max<int64_t>(0, std::min<int64_t>(width, (int64_t)tr.I - info[4 * s + 1]));
+            widest = std::max(widest, counts[b]);
+        }
+        if (widest == 0) continue;
+        foldin_batch_predictions(tr, bs, h->prep.sort, C, take, ebase.data(), st);
+        const size_t cells = (size_t)C * widest;
+        bs.out_items.ensure(cells); bs.out_preds.ensure(cells);
+        foldin_batch_recommend(tr, bs, h->prep.sort, C, widest, bs.out_items.p, bs.out_preds.p, st);
+        h_items.resize(cells); h_vals.resize(cells);
+        KN_HIP(hipMemcpyAsync(h_items.data(), bs.out_items.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        KN_HIP(hipMemcpyAsync(h_vals.data(), bs.out_preds.p, cells * sizeof(double), hipMemcpyDeviceToHost, st));
+        KN_HIP(hipStreamSynchronize(st));
+        for (int32_t s = 0; s < C; ++s) {
+            const int64_t b = slot_query[s];
+            if (statuses[b] != KNNCF_OK) continue;
+            std::copy(h_items.begin() + (size_t)s * widest, h_items.begin() + (size_t)s * widest + counts[b], out_i + b * width);
+            std::copy(h_vals.begin() + (size_t)s * widest, h_vals.begin() + (size_t)s * widest + counts[b], out_d + b * width);
+        }
+    }
+    if (first_failed >= 0) h->err = "query batch: query " + std::to_string(first_failed) + ": " + first_reason;
+}
+
 // ---- checkpoint / resume of the neighbour table ------------------------------------------------------
 struct NbrFileHeader {
     char magic[8];  // "KNNCFNB2" (NB1: the fingerprint without the ratings; refused)
@@ -1555,6 +1724,33 @@ int knncf_query_neighbors(knncf_handle* h, int32_t user, const int32_t* items, c
 int knncf_query_predict(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
                         int64_t n_ratings, const int32_t* pred_items, int64_t m, double* out) {
     return guarded(h, [&] { do_query_predict(h, predictor, user, items, ratings, n_ratings, pred_items, m, out); });
+}
+
+int knncf_query_neighbors_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                                const double* ratings, int64_t n_queries, int32_t cap, int32_t* ids, double* sims, int32_t* counts,
+                                int32_t* statuses) {
+    return guarded(h, [&] {
+        do_query_batch(h, QB_NEIGHBORS, KNNCF_PRED_KNN, users, offsets, items, ratings, n_queries, cap, nullptr, nullptr, ids, sims,
+                       counts, statuses);
+    });
+}
+
+int knncf_query_predict_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                              const double* ratings, int64_t n_queries, const int64_t* pred_offsets, const int32_t* pred_items,
+                              double* out, int32_t* statuses) {
+    return guarded(h, [&] {
+        do_query_batch(h, QB_PREDICT, predictor, users, offsets, items, ratings, n_queries, 0, pred_offsets, pred_items, nullptr, out,
+                       nullptr, statuses);
+    });
+}
+
+int knncf_query_recommend_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                                const double* ratings, int64_t n_queries, int32_t n, int32_t* out_items, double* out_preds,
+                                int32_t* counts, int32_t* statuses) {
+    return guarded(h, [&] {
+        do_query_batch(h, QB_RECOMMEND, predictor, users, offsets, items, ratings, n_queries, n, nullptr, nullptr, out_items,
+                       out_preds, counts, statuses);
+    });
 }
 
 int knncf_query_recommend(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,

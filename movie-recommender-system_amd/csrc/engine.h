@@ -292,6 +292,8 @@ void launch_reco_rows(const Train& tr, int32_t user_raw, int32_t du, int32_t* d_
 // v_b = dense items ordered by (prediction descending, raw id ascending), rated items last
 void launch_reco_order(const Train& tr, SortWorkspace& ws, const double* d_pred, const uint8_t* d_rated, uint64_t* k_a, uint64_t* k_b,
                        uint32_t* v_a, uint32_t* v_b, hipStream_t st);
+// by_id = dense items by ascending raw id (the first of launch_reco_order's two sorts; k_a / k_b / v_a hold I entries)
+void launch_reco_id_order(const Train& tr, SortWorkspace& ws, uint64_t* k_a, uint64_t* k_b, uint32_t* v_a, uint32_t* by_id, hipStream_t st);
 void launch_reco_take(const Train& tr, int32_t m, const uint32_t* d_order, const double* d_pred, int32_t* d_items, double* d_preds, hipStream_t st);
 
 // ---- foldin.hip: kNN queries of one user outside the fit (DESIGN.md "Fold-in queries") --------------------------
@@ -331,5 +333,50 @@ QueryInfo foldin_neighbors(const Train& tr, QueryScratch& qs, SortWorkspace& ws,
 void foldin_predictions(const Train& tr, QueryScratch& qs, SortWorkspace& ws, const QueryInfo& qi, hipStream_t st);
 // d_out[j] = prediction of raw item d_items[j] (after foldin_predictions)
 void foldin_pick(const Train& tr, QueryScratch& qs, const int32_t* d_items, int64_t m, double* d_out, hipStream_t st);
+
+// ---- foldin.hip, batched: chunks of independent queries, every stage one launch over the chunk ---------------------
+static constexpr uint32_t QUERY_ST_NEG_MEAN = 1u << 8;  // status bit beside ST_NONFINITE / ST_DUPLICATE: the query's mean is negative
+static constexpr int QB_MAX_CHUNK = 64;  // queries per chunk: one lane of k_query_sim_dual's waves each
+static constexpr int QB_DUAL_MIN = 32;   // smaller chunks run k_query_sim once per query instead: measured crossover
+// device bytes per query of a chunk that the chunk rule of knncf.h counts
+inline int64_t query_batch_bytes(int32_t U, int32_t I) { return 64 * (int64_t)U + 96 * (int64_t)I; }
+struct QueryBatchScratch {
+    DArr<int32_t> users;               // [C] raw user of each slot
+    DArr<int64_t> qo;                  // [C + 1] first row of each slot
+    DArr<int32_t> items, slot, di, given_d;  // [n] rows of the chunk, slot after slot
+    DArr<double> ratings, dev, pre, pre_d, dev_d;
+    DArr<uint64_t> bits;               // [C][ceil(I / 64)]
+    DArr<int64_t> rank;                // [C][ceil(I / 64) + 1]
+    DArr<uint32_t> tbits, trank;       // [2 ceil(I / 64)][64] the bitmaps and prefixes side by side (k_qb_transpose)
+    DArr<int64_t> info;                // [C][4] status bits, known items, neighbour ratings
+    DArr<double> scal;                 // [C][2] mean, norm
+    DArr<double> sim;                  // [C][U]
+    DArr<uint64_t> k64_a, k64_b;       // [C * max(U, I)]
+    DArr<uint32_t> v32_a, v32_b, s32_a, s32_b;
+    DArr<int32_t> nbr_idx;             // [C][take]
+    DArr<double> nbr_sim;
+    DArr<int64_t> off, ebase;          // [C][take + 1], [C + 1]
+    DArr<uint64_t> e_k64_a, e_k64_b;   // [entries of the chunk]
+    DArr<uint32_t> e_v32_a, e_v32_b;
+    DArr<double> e_dev, e_sim;
+    DArr<double> num, den, pred;       // [C][I]
+    DArr<uint8_t> rated;
+    DArr<uint32_t> by_id;              // [I]
+    DArr<int32_t> pick_items, pick_slot, out_items;
+    DArr<double> pick_out, out_preds;
+};
+// prep + similarities + top-k (bs.nbr_idx / nbr_sim [C][min(k, U)]) of C >= 1 non-empty queries; h_info[4 b ..] = status
+// bits, known items, neighbour ratings (0 for a slot whose status is set) of slot b.  Synchronises the stream once.
+void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, const int32_t* h_users,
+                            const int64_t* h_qo, const int32_t* h_items, const double* h_ratings, int32_t k, long long* h_info,
+                            hipStream_t st);
+// bs.pred / bs.rated [C][I]; h_ebase[C + 1] = exclusive prefix of the slots' neighbour ratings
+void foldin_batch_predictions(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, int32_t take,
+                              const int64_t* h_ebase, hipStream_t st);
+void foldin_batch_pick(const Train& tr, QueryBatchScratch& bs, const int32_t* d_items, const int32_t* d_slot, int64_t m,
+                       double* d_out, hipStream_t st);
+// d_items / d_preds [C][n]: slot b's first min(n, I - known) recommendations (the rest untouched)
+void foldin_batch_recommend(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, int32_t n, int32_t* d_items,
+                            double* d_preds, hipStream_t st);
 
 }  // namespace knncf

@@ -31,7 +31,7 @@ static constexpr int ONE_BLOCK = 1024;
 // beyond that the waves probe them in global memory (L2-resident)
 static constexpr int64_t SIM_LDS_WORDS = 4096;
 // the predictor answers aug's global average for a user mean < 0 (:571-574): not served by a fold-in query
-static constexpr uint32_t ST_NEG_MEAN = 1u << 8;
+static constexpr uint32_t ST_NEG_MEAN = QUERY_ST_NEG_MEAN;
 
 // raw -> dense item through the fit's tables (dense_lookup beyond them); key of the norm's fold order: the trie order of
 // the (q, item) tuple hash (usersWeights :474, N4).  tuple_trie_key(q, .) is a bijection of the item id, so two rows have
@@ -413,6 +413,464 @@ void foldin_pick(const Train& tr, QueryScratch& qs, const int32_t* d_items, int6
     if (m <= 0) return;
     k_q_pick<<<(unsigned)ceil_div(m, TPB), TPB, 0, st>>>(m, d_items, tr.i_table.p, table_cells(tr), tr.ikeys.p, tr.I, qs.pred.p,
                                                          qs.scal.p, d_out);
+    KN_HIP(hipGetLastError());
+}
+
+// ---- batched fold-in queries (knncf_query_*_batch) ------------------------------------------------------------------------
+// A chunk of C <= QB_MAX_CHUNK independent queries goes through the same stages as one query, every stage as ONE launch (or
+// one sort) over the chunk.  Rows of the chunk are concatenated in slot order: slot b owns rows [qo[b], qo[b + 1]).  Each
+// slot's arithmetic is that of the single-query kernels above, in the same order, so row b equals the single call bit for
+// bit; nothing of one slot enters another.
+//   k_qb_keys / sort (slot, trie key) / k_qb_prep / k_qb_rank / k_qb_scatter   query prep, one workgroup per slot
+//   k_qb_transpose + k_query_sim_dual   (C >= QB_DUAL_MIN) every train row read once for the whole chunk, lane b = slot b
+//   k_query_sim per slot                (C <  QB_DUAL_MIN)
+//   fallback keys over [C][U] / sort 64 bits / stable sort by slot / k_qb_write   top-k of every slot
+//   k_qb_offsets / k_qb_gather / sort (slot * I + item, file row) / k_q_fold / k_qb_pred
+//   k_qb_reco_keys / sort 64 bits / stable sort by slot / k_qb_take              recommendations
+
+// slot of chunk row j: the last b with qo[b] <= j
+__device__ __forceinline__ int32_t qb_slot(const int64_t* __restrict__ qo, int32_t C, int64_t j) {
+    int32_t lo = 0, hi = C - 1;
+    while (lo < hi) {
+        const int32_t mid = (lo + hi + 1) >> 1;
+        if (qo[mid] <= j) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+__global__ void k_qb_keys(int64_t n, int32_t C, const int64_t* __restrict__ qo, const int32_t* __restrict__ users,
+                          const int32_t* __restrict__ items, const int32_t* __restrict__ i_table, int32_t i_cells,
+                          const uint32_t* __restrict__ ikeys, int32_t I, int32_t* __restrict__ slot, int32_t* __restrict__ di,
+                          uint64_t* __restrict__ key, uint32_t* __restrict__ val) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const int32_t b = qb_slot(qo, C, j);
+    const int32_t it = items[j];
+    int32_t d;
+    if (i_cells > 0) d = (it >= 0 && it < i_cells) ? i_table[it] : -1;
+    else d = dense_lookup(ikeys, I, it);
+    slot[j] = b;
+    di[j] = d;
+    key[j] = ((uint64_t)(uint32_t)b << 32) | (uint64_t)tuple_trie_key(users[b], it);
+    val[j] = (uint32_t)j;
+}
+
+// k_q_prep of slot blockIdx.x: info[4 b] |= status bits, info[4 b + 1] = known items; scal[2 b] = mean, scal[2 b + 1] = norm
+__global__ void k_qb_prep(const int64_t* __restrict__ qo, const double* __restrict__ r, const uint64_t* __restrict__ skey,
+                          const uint32_t* __restrict__ sval, const int32_t* __restrict__ di, int64_t W, double* __restrict__ dev,
+                          double* __restrict__ pre, unsigned long long* __restrict__ bits, long long* __restrict__ info,
+                          double* __restrict__ scal) {
+    __shared__ double s_avg, s_norm;
+    __shared__ int32_t s_known;
+    const int32_t b = blockIdx.x;
+    const int64_t o = qo[b];
+    const int32_t n = (int32_t)(qo[b + 1] - o);
+    bits += (int64_t)b * W;
+    info += 4 * b;
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int32_t j = 0; j < n; ++j) s = s + r[o + j];
+        const double avg = s / (double)n;
+        double w = 0.0;
+        for (int32_t p = 0; p < n; ++p) {
+            const double x = r[sval[o + p]];
+            const double d = (x - avg) / scale_fn(x, avg);
+            w = w + d * d;
+        }
+        s_avg = avg;
+        s_norm = sqrt(w);
+        s_known = 0;
+    }
+    __syncthreads();
+    const double avg = s_avg, norm = s_norm;
+    unsigned long long st = 0;
+    int32_t known = 0;
+    for (int32_t j = threadIdx.x; j < n; j += blockDim.x) {
+        const double x = r[o + j];
+        const double d = (x - avg) / scale_fn(x, avg);
+        if (!isfinite(d)) st |= ST_NONFINITE;
+        dev[o + j] = d;
+        pre[o + j] = (norm != 0) ? d / norm : 0.0;
+        const int32_t c = di[o + j];
+        if (c >= 0) {
+            atomicOr(bits + (c >> 6), 1ull << (c & 63));
+            ++known;
+        }
+        if (j > 0 && skey[o + j] == skey[o + j - 1]) st |= ST_DUPLICATE;
+    }
+    if (st) atomicOr((unsigned long long*)info, st);
+    if (known) atomicAdd(&s_known, known);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        info[1] = s_known;
+        scal[2 * b] = avg;
+        scal[2 * b + 1] = norm;
+        if (avg < 0.0) atomicOr((unsigned long long*)info, (unsigned long long)ST_NEG_MEAN);
+    }
+}
+
+__global__ void __launch_bounds__(ONE_BLOCK) k_qb_rank(int64_t W, const unsigned long long* __restrict__ bits,
+                                                       int64_t* __restrict__ rank) {
+    const unsigned long long* mine = bits + (int64_t)blockIdx.x * W;
+    block_exclusive_scan(W, [&](int64_t w) { return (int64_t)__popcll(mine[w]); }, rank + (int64_t)blockIdx.x * (W + 1));
+}
+
+__global__ void k_qb_scatter(int64_t n, const int64_t* __restrict__ qo, const int32_t* __restrict__ slot,
+                             const int32_t* __restrict__ di, const double* __restrict__ pre, const double* __restrict__ dev,
+                             int64_t W, const unsigned long long* __restrict__ bits, const int64_t* __restrict__ rank,
+                             double* __restrict__ pre_d, double* __restrict__ dev_d, int32_t* __restrict__ given_d) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const int32_t c = di[j];
+    if (c < 0) return;
+    const int32_t b = slot[j];
+    const int64_t o = qo[b];
+    const int32_t r = bit_rank(bits + (int64_t)b * W, rank + (int64_t)b * (W + 1), c);
+    pre_d[o + r] = pre[j];
+    dev_d[o + r] = dev[j];
+    given_d[o + r] = (int32_t)(j - o);
+}
+
+// the chunk's bitmaps side by side for k_query_sim_dual: word x of 32 items, lane b -> tb[x * 64 + b] (the bits of slot b)
+// and tr[x * 64 + b] (the number of slot b's known items below item 32 x); lanes >= C hold zeros
+__global__ void k_qb_transpose(int64_t W, int32_t C, const unsigned long long* __restrict__ bits,
+                               const int64_t* __restrict__ rank, uint32_t* __restrict__ tb, uint32_t* __restrict__ tr) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= 2 * W * QB_MAX_CHUNK) return;
+    const int32_t b = (int32_t)(g % QB_MAX_CHUNK);
+    const int64_t x = g / QB_MAX_CHUNK, w = x >> 1;
+    uint32_t word = 0, below = 0;
+    if (b < C) {
+        const unsigned long long full = bits[(int64_t)b * W + w];
+        below = (uint32_t)rank[(int64_t)b * (W + 1) + w];
+        if (x & 1) {
+            word = (uint32_t)(full >> 32);
+            below += __popc((uint32_t)full);
+        } else {
+            word = (uint32_t)full;
+        }
+    }
+    tb[g] = word;
+    tr[g] = below;
+}
+
+// The similarity pass of a chunk: a wave owns a train row and walks its entries in row order; LANE b OWNS SLOT b.  The row
+// is fetched once for the whole chunk (64 entries per coalesced load, then one wave-uniform entry at a time); every lane
+// probes its own slot's bitmap word (one coalesced 256-byte read of tb per entry) and folds its own fp64 accumulator, so the
+// left fold in row order = dense item order is exact by construction.  A slot of <= 4 ratings keeps its <= 4 products by given
+// position and folds them at the end, as k_query_sim does; Jaccard counts.  out[b * U + v].
+__global__ void __launch_bounds__(TPB) k_query_sim_dual(int32_t U, int32_t C, bool jaccard, const int64_t* __restrict__ u_ptr,
+                                                        const int32_t* __restrict__ s_col, const double* __restrict__ s_pre,
+                                                        const uint32_t* __restrict__ tb, const uint32_t* __restrict__ tr,
+                                                        const int64_t* __restrict__ qo, const double* __restrict__ pre_d,
+                                                        const int32_t* __restrict__ given_d, double* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const bool live = lane < C;
+    const int64_t o = live ? qo[lane] : 0;
+    const int32_t nq = live ? (int32_t)(qo[lane + 1] - o) : 0;
+    const bool small = nq <= 4;
+    const int64_t waves = (int64_t)gridDim.x * (TPB / 64);
+    for (int64_t v = (int64_t)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6); v < U; v += waves) {
+        const int64_t b = u_ptr[v], e = u_ptr[v + 1];
+        double s = 0.0, x0 = 0.0, x1 = 0.0, x2 = 0.0, x3 = 0.0;
+        uint32_t found = 0;
+        int64_t both = 0;
+        for (int64_t base = b; base < e; base += 64) {
+            const int cnt = (int)min((int64_t)64, e - base);
+            const int32_t mine = lane < cnt ? s_col[base + lane] : 0;
+#pragma unroll 4
+            for (int l = 0; l < cnt; ++l) {
+                const int32_t c = __builtin_amdgcn_readlane(mine, l);
+                const int64_t cell = (int64_t)(c >> 5) * QB_MAX_CHUNK + lane;
+                const uint32_t word = tb[cell];
+                const uint32_t bit = 1u << (c & 31);
+                if (word & bit) {
+                    if (jaccard) {
+                        ++both;
+                    } else {
+                        const int32_t r = (int32_t)(tr[cell] + __popc(word & (bit - 1u)));
+                        const double xv = pre_d[o + r] * s_pre[base + l];
+                        if (small) {
+                            const int gg = given_d[o + r];
+                            if (gg == 0) x0 = xv;
+                            else if (gg == 1) x1 = xv;
+                            else if (gg == 2) x2 = xv;
+                            else x3 = xv;
+                            found |= 1u << gg;
+                        } else {
+                            s = s + xv;
+                        }
+                    }
+                }
+            }
+        }
+        if (jaccard) {
+            s = (double)both / (double)((int64_t)nq + (e - b) - both);
+        } else if (small) {
+            if (found & 1u) s = s + x0;
+            if (found & 2u) s = s + x1;
+            if (found & 4u) s = s + x2;
+            if (found & 8u) s = s + x3;
+        }
+        if (live) out[(int64_t)lane * U + v] = s;
+    }
+}
+
+// key of the stable second sort that groups a (value-ordered) list by slot: val = slot * stride + index
+__global__ void k_qb_slot_keys(int64_t n, uint32_t stride, const uint32_t* __restrict__ val, uint32_t* __restrict__ key) {
+    const int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x < n) key[x] = val[x] / stride;
+}
+
+// the first `take` of slot b's sorted list -> nbr_idx / nbr_sim [b][take]
+__global__ void k_qb_write(int32_t C, int32_t take, int32_t U, const uint32_t* __restrict__ sorted_val,
+                           const double* __restrict__ sim, int32_t* __restrict__ nbr_idx, double* __restrict__ nbr_sim) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (int64_t)C * take) return;
+    const int32_t b = (int32_t)(g / take), j = (int32_t)(g - (int64_t)b * take);
+    const uint32_t x = sorted_val[(int64_t)b * U + j];
+    nbr_idx[g] = (int32_t)(x - (uint32_t)b * (uint32_t)U);
+    nbr_sim[g] = sim[x];
+}
+
+// off[b][0 .. take]: first entry of each neighbour's ratings inside slot b's part of the gathered list; info[4 b + 2] = their
+// number.  A slot whose status is already set takes no part in the prediction pass (0 entries).
+__global__ void __launch_bounds__(ONE_BLOCK) k_qb_offsets(int32_t take, const int32_t* __restrict__ nbr,
+                                                          const int64_t* __restrict__ u_ptr, int64_t* __restrict__ off,
+                                                          long long* __restrict__ info) {
+    const int32_t b = blockIdx.x;
+    const int32_t* mine = nbr + (int64_t)b * take;
+    const bool failed = info[4 * b] != 0;
+    const int64_t total = block_exclusive_scan(
+        take, [&](int64_t j) { return failed ? (int64_t)0 : u_ptr[mine[j] + 1] - u_ptr[mine[j]]; }, off + (int64_t)b * (take + 1));
+    if (threadIdx.x == 0) info[4 * b + 2] = total;
+}
+
+// k_q_gather over the chunk: one wave per (slot, neighbour); key = (slot * I + item, train file row)
+__global__ void __launch_bounds__(TPB) k_qb_gather(int32_t C, int32_t take, int32_t I, const int32_t* __restrict__ nbr,
+                                                   const double* __restrict__ nsim, const int64_t* __restrict__ off,
+                                                   const int64_t* __restrict__ ebase, const int64_t* __restrict__ u_ptr,
+                                                   const int32_t* __restrict__ s_col, const uint32_t* __restrict__ s_t,
+                                                   const double* __restrict__ s_dev, uint64_t* __restrict__ key,
+                                                   uint32_t* __restrict__ val, double* __restrict__ edev, double* __restrict__ esim) {
+    const int64_t g = (int64_t)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
+    if (g >= (int64_t)C * take) return;
+    const int32_t sb = (int32_t)(g / take), j = (int32_t)(g - (int64_t)sb * take);
+    const int64_t lo = off[(int64_t)sb * (take + 1) + j], hi = off[(int64_t)sb * (take + 1) + j + 1];
+    if (hi == lo) return;  // (a failed slot, or a neighbour without ratings)
+    const int32_t v = nbr[g];
+    const int64_t b = u_ptr[v], e = u_ptr[v + 1], o = ebase[sb] + lo;
+    const double sj = nsim[g];
+    for (int64_t p = b + (threadIdx.x & 63); p < e; p += 64) {
+        const int64_t x = o + (p - b);
+        key[x] = ((uint64_t)((uint32_t)sb * (uint32_t)I + (uint32_t)s_col[p]) << 32) | (uint64_t)s_t[p];
+        val[x] = (uint32_t)x;
+        edev[x] = s_dev[p];
+        esim[x] = sj;
+    }
+}
+
+// k_q_pred over [C][I]
+__global__ void k_qb_pred(int32_t C, int32_t I, int64_t W, const double* __restrict__ num, const double* __restrict__ den,
+                          const unsigned long long* __restrict__ bits, const int64_t* __restrict__ rank,
+                          const int64_t* __restrict__ qo, const double* __restrict__ dev_d, const double* __restrict__ scal,
+                          double* __restrict__ pred, uint8_t* __restrict__ rated) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (int64_t)C * I) return;
+    const int32_t b = (int32_t)(g / I), i = (int32_t)(g - (int64_t)b * I);
+    const unsigned long long* mb = bits + (int64_t)b * W;
+    double a = num[g], d = den[g];
+    const bool mine = (mb[i >> 6] >> (i & 63)) & 1ull;
+    if (mine) {
+        const double s = 0.0;
+        a = a + dev_d[qo[b] + bit_rank(mb, rank + (int64_t)b * (W + 1), i)] * s;
+        d = d + fabs(s);
+    }
+    const double avg = scal[2 * b];
+    const double w = d > 0 ? a / d : 0.0;
+    pred[g] = avg + w * scale_fn(avg + w, avg);
+    rated[g] = mine ? 1 : 0;
+}
+
+// k_q_pick with the slot of every requested row
+__global__ void k_qb_pick(int64_t m, const int32_t* __restrict__ items, const int32_t* __restrict__ slot,
+                          const int32_t* __restrict__ i_table, int32_t i_cells, const uint32_t* __restrict__ ikeys, int32_t I,
+                          const double* __restrict__ pred, const double* __restrict__ scal, double* __restrict__ out) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const int32_t it = items[j], b = slot[j];
+    int32_t c;
+    if (i_cells > 0) c = (it >= 0 && it < i_cells) ? i_table[it] : -1;
+    else c = dense_lookup(ikeys, I, it);
+    if (c >= 0) {
+        out[j] = pred[(int64_t)b * I + c];
+    } else {
+        const double avg = scal[2 * b], w = 0.0;
+        out[j] = avg + w * scale_fn(avg + w, avg);
+    }
+}
+
+// k_reco_pred_keys (reco.hip) over [C][I]: ascending key <=> descending prediction, rated items last, -0.0 == +0.0;
+// the input order inside a slot is ascending raw id (by_id), val = slot * I + dense item
+__global__ void k_qb_reco_keys(int32_t C, int32_t I, const uint32_t* __restrict__ by_id, const double* __restrict__ pred,
+                               const uint8_t* __restrict__ rated, uint64_t* __restrict__ key, uint32_t* __restrict__ val) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (int64_t)C * I) return;
+    const int32_t b = (int32_t)(g / I);
+    const int64_t cell = (int64_t)b * I + by_id[g - (int64_t)b * I];
+    double p = pred[cell];
+    if (p == 0.0) p = 0.0;
+    const uint64_t bits = (uint64_t)__double_as_longlong(p);
+    const uint64_t asc = (bits >> 63) ? ~bits : (bits | 0x8000000000000000ull);
+    key[g] = rated[cell] ? ~0ull : ~asc;
+    val[g] = (uint32_t)cell;
+}
+
+// slot b's first min(n, I - known) entries -> out_items / out_preds [b][n]
+__global__ void k_qb_take(int32_t C, int32_t n, int32_t I, const long long* __restrict__ info,
+                          const uint32_t* __restrict__ order, const int32_t* __restrict__ iid, const double* __restrict__ pred,
+                          int32_t* __restrict__ out_items, double* __restrict__ out_preds) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (int64_t)C * n) return;
+    const int32_t b = (int32_t)(g / n), j = (int32_t)(g - (int64_t)b * n);
+    if (j >= (int64_t)I - info[4 * b + 1]) return;
+    const uint32_t cell = order[(int64_t)b * I + j];
+    out_items[g] = iid[cell - (uint32_t)b * (uint32_t)I];
+    out_preds[g] = pred[cell];
+}
+
+// [C][stride] cells ordered by (slot, 64-bit key, input order): one stable sort by the key, then one by the slot; returns
+// the ordered values (val = slot * stride + index)
+static const uint32_t* qb_segmented_sort(QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, int64_t stride, hipStream_t st) {
+    const size_t m = (size_t)C * (size_t)stride;
+    sort_pairs_u64_u32(ws, bs.k64_a.p, bs.k64_b.p, bs.v32_a.p, bs.v32_b.p, m, 64, st);
+    if (C == 1) return bs.v32_b.p;
+    k_qb_slot_keys<<<(unsigned)ceil_div((int64_t)m, TPB), TPB, 0, st>>>((int64_t)m, (uint32_t)stride, bs.v32_b.p, bs.s32_a.p);
+    sort_pairs_u32_u32(ws, bs.s32_a.p, bs.s32_b.p, bs.v32_b.p, bs.v32_a.p, m, bits_for((uint64_t)(C - 1)), st);
+    return bs.v32_a.p;
+}
+
+void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, const int32_t* h_users,
+                            const int64_t* h_qo, const int32_t* h_items, const double* h_ratings, int32_t k, long long* h_info,
+                            hipStream_t st) {
+    const int32_t U = tr.U, I = tr.I;
+    const int64_t W = ceil_div(I, 64), n = h_qo[C];
+    const int64_t cells = (int64_t)C * std::max(U, I);
+    const int32_t take = std::max(0, std::min(k, U));
+    bs.users.ensure(C); bs.qo.ensure((size_t)C + 1);
+    bs.items.ensure(n); bs.ratings.ensure(n); bs.slot.ensure(n); bs.di.ensure(n); bs.dev.ensure(n); bs.pre.ensure(n);
+    bs.pre_d.ensure(n); bs.dev_d.ensure(n); bs.given_d.ensure(n);
+    bs.bits.ensure((size_t)C * W); bs.rank.ensure((size_t)C * (W + 1));
+    const int64_t keys = std::max<int64_t>(n, cells);
+    bs.k64_a.ensure(keys); bs.k64_b.ensure(keys); bs.v32_a.ensure(keys); bs.v32_b.ensure(keys);
+    bs.s32_a.ensure(cells); bs.s32_b.ensure(cells);
+    bs.sim.ensure((size_t)C * U);
+    bs.info.ensure((size_t)4 * C); bs.scal.ensure((size_t)2 * C);
+    bs.nbr_idx.ensure(std::max<size_t>((size_t)C * take, 1)); bs.nbr_sim.ensure(std::max<size_t>((size_t)C * take, 1));
+    bs.off.ensure((size_t)C * ((size_t)take + 1));
+
+    // one upload of the chunk
+    KN_HIP(hipMemcpyAsync(bs.users.p, h_users, (size_t)C * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    KN_HIP(hipMemcpyAsync(bs.qo.p, h_qo, ((size_t)C + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    KN_HIP(hipMemcpyAsync(bs.items.p, h_items, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    KN_HIP(hipMemcpyAsync(bs.ratings.p, h_ratings, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    KN_HIP(hipMemsetAsync(bs.bits.p, 0, (size_t)C * W * sizeof(uint64_t), st));
+    KN_HIP(hipMemsetAsync(bs.info.p, 0, (size_t)4 * C * sizeof(int64_t), st));
+    unsigned long long* bits = (unsigned long long*)bs.bits.p;
+    long long* info = (long long*)bs.info.p;
+    // query prep
+    k_qb_keys<<<(unsigned)ceil_div(n, TPB), TPB, 0, st>>>(n, C, bs.qo.p, bs.users.p, bs.items.p, tr.i_table.p, table_cells(tr),
+                                                          tr.ikeys.p, I, bs.slot.p, bs.di.p, bs.k64_a.p, bs.v32_a.p);
+    sort_pairs_u64_u32(ws, bs.k64_a.p, bs.k64_b.p, bs.v32_a.p, bs.v32_b.p, (size_t)n, 32 + (C > 1 ? bits_for((uint64_t)(C - 1)) : 0), st);
+    k_qb_prep<<<C, ONE_BLOCK, 0, st>>>(bs.qo.p, bs.ratings.p, bs.k64_b.p, bs.v32_b.p, bs.di.p, W, bs.dev.p, bs.pre.p, bits, info,
+                                       bs.scal.p);
+    k_qb_rank<<<C, ONE_BLOCK, 0, st>>>(W, bits, bs.rank.p);
+    k_qb_scatter<<<(unsigned)ceil_div(n, TPB), TPB, 0, st>>>(n, bs.qo.p, bs.slot.p, bs.di.p, bs.pre.p, bs.dev.p, W, bits, bs.rank.p,
+                                                             bs.pre_d.p, bs.dev_d.p, bs.given_d.p);
+    KN_HIP(hipGetLastError());
+    // similarities [C][U]
+    const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(U, TPB / 64), 2048);
+    if (C >= QB_DUAL_MIN) {
+        const int64_t cellsT = 2 * W * QB_MAX_CHUNK;
+        bs.tbits.ensure(cellsT); bs.trank.ensure(cellsT);
+        k_qb_transpose<<<(unsigned)ceil_div(cellsT, TPB), TPB, 0, st>>>(W, C, bits, bs.rank.p, bs.tbits.p, bs.trank.p);
+        k_query_sim_dual<<<grid, TPB, 0, st>>>(U, C, tr.jaccard, tr.u_ptr.p, tr.s_col.p, tr.s_pre.p, bs.tbits.p, bs.trank.p,
+                                               bs.qo.p, bs.pre_d.p, bs.given_d.p, bs.sim.p);
+    } else {
+        const size_t lds = (size_t)W * (sizeof(uint64_t) + sizeof(int64_t));
+        if (W <= SIM_LDS_WORDS) ensure_dynamic_lds(g_sim_lds, (const void*)k_query_sim<true>, lds);
+        for (int32_t b = 0; b < C; ++b) {
+            const int32_t nq = (int32_t)(h_qo[b + 1] - h_qo[b]);
+            const unsigned long long* bb = bits + (int64_t)b * W;
+            const int64_t* rb = bs.rank.p + (int64_t)b * (W + 1);
+            if (W <= SIM_LDS_WORDS) {
+                k_query_sim<true><<<grid, TPB, lds, st>>>(U, nq, tr.jaccard, tr.u_ptr.p, tr.s_col.p, tr.s_pre.p, W, bb, rb,
+                                                          bs.pre_d.p + h_qo[b], bs.given_d.p + h_qo[b], bs.sim.p + (int64_t)b * U);
+            } else {
+                k_query_sim<false><<<grid, TPB, 0, st>>>(U, nq, tr.jaccard, tr.u_ptr.p, tr.s_col.p, tr.s_pre.p, W, bb, rb,
+                                                         bs.pre_d.p + h_qo[b], bs.given_d.p + h_qo[b], bs.sim.p + (int64_t)b * U);
+            }
+        }
+    }
+    KN_HIP(hipGetLastError());
+    // top-k of every slot: (similarity desc, dense user asc)
+    launch_fallback_keys((int32_t)((int64_t)C * U), bs.sim.p, bs.k64_a.p, bs.v32_a.p, st);
+    const uint32_t* order = qb_segmented_sort(bs, ws, C, U, st);
+    if (take > 0) {
+        k_qb_write<<<(unsigned)ceil_div((int64_t)C * take, TPB), TPB, 0, st>>>(C, take, U, order, bs.sim.p, bs.nbr_idx.p,
+                                                                               bs.nbr_sim.p);
+    }
+    k_qb_offsets<<<C, ONE_BLOCK, 0, st>>>(take, bs.nbr_idx.p, tr.u_ptr.p, bs.off.p, info);
+    KN_HIP(hipGetLastError());
+    // the chunk's one round trip: statuses, known items and the sizes of the prediction pass
+    KN_HIP(hipMemcpyAsync(h_info, bs.info.p, (size_t)4 * C * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    KN_HIP(hipStreamSynchronize(st));
+}
+
+void foldin_batch_predictions(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, int32_t take,
+                              const int64_t* h_ebase, hipStream_t st) {
+    const int32_t I = tr.I;
+    const int64_t W = ceil_div(I, 64), E = h_ebase[C], cells = (int64_t)C * I;
+    bs.num.ensure(cells); bs.den.ensure(cells); bs.pred.ensure(cells); bs.rated.ensure(cells);
+    KN_HIP(hipMemsetAsync(bs.num.p, 0, (size_t)cells * sizeof(double), st));  // +0.0
+    KN_HIP(hipMemsetAsync(bs.den.p, 0, (size_t)cells * sizeof(double), st));
+    if (E > 0) {
+        KN_REQUIRE(E < (int64_t)0xffffffffll, KNNCF_E_UNSUPPORTED, "query batch: more than 2^32-1 neighbour ratings in a chunk");
+        bs.ebase.ensure((size_t)C + 1);
+        bs.e_k64_a.ensure(E); bs.e_k64_b.ensure(E); bs.e_v32_a.ensure(E); bs.e_v32_b.ensure(E);
+        bs.e_dev.ensure(E); bs.e_sim.ensure(E);
+        KN_HIP(hipMemcpyAsync(bs.ebase.p, h_ebase, ((size_t)C + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        k_qb_gather<<<(unsigned)ceil_div((int64_t)C * take, TPB / 64), TPB, 0, st>>>(
+            C, take, I, bs.nbr_idx.p, bs.nbr_sim.p, bs.off.p, bs.ebase.p, tr.u_ptr.p, tr.s_col.p, tr.s_t.p, tr.s_dev.p, bs.e_k64_a.p,
+            bs.e_v32_a.p, bs.e_dev.p, bs.e_sim.p);
+        sort_pairs_u64_u32(ws, bs.e_k64_a.p, bs.e_k64_b.p, bs.e_v32_a.p, bs.e_v32_b.p, (size_t)E, 32 + bits_for((uint64_t)cells), st);
+        k_q_fold<<<(unsigned)ceil_div(E, TPB), TPB, 0, st>>>(E, bs.e_k64_b.p, bs.e_v32_b.p, bs.e_dev.p, bs.e_sim.p, bs.num.p, bs.den.p);
+    }
+    k_qb_pred<<<(unsigned)ceil_div(cells, TPB), TPB, 0, st>>>(C, I, W, bs.num.p, bs.den.p, (const unsigned long long*)bs.bits.p,
+                                                              bs.rank.p, bs.qo.p, bs.dev_d.p, bs.scal.p, bs.pred.p, bs.rated.p);
+    KN_HIP(hipGetLastError());
+}
+
+void foldin_batch_pick(const Train& tr, QueryBatchScratch& bs, const int32_t* d_items, const int32_t* d_slot, int64_t m,
+                       double* d_out, hipStream_t st) {
+    if (m <= 0) return;
+    k_qb_pick<<<(unsigned)ceil_div(m, TPB), TPB, 0, st>>>(m, d_items, d_slot, tr.i_table.p, table_cells(tr), tr.ikeys.p, tr.I,
+                                                          bs.pred.p, bs.scal.p, d_out);
+    KN_HIP(hipGetLastError());
+}
+
+void foldin_batch_recommend(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, int32_t n, int32_t* d_items,
+                            double* d_preds, hipStream_t st) {
+    const int32_t I = tr.I;
+    const int64_t cells = (int64_t)C * I;
+    // dense items by ascending raw id: the same for every slot
+    bs.by_id.ensure(I);
+    launch_reco_id_order(tr, ws, bs.k64_a.p, bs.k64_b.p, bs.v32_a.p, bs.by_id.p, st);
+    k_qb_reco_keys<<<(unsigned)ceil_div(cells, TPB), TPB, 0, st>>>(C, I, bs.by_id.p, bs.pred.p, bs.rated.p, bs.k64_a.p, bs.v32_a.p);
+    const uint32_t* order = qb_segmented_sort(bs, ws, C, I, st);
+    k_qb_take<<<(unsigned)ceil_div((int64_t)C * n, TPB), TPB, 0, st>>>(C, n, I, (const long long*)bs.info.p, order, tr.iid.p,
+                                                                       bs.pred.p, d_items, d_preds);
     KN_HIP(hipGetLastError());
 }
 

@@ -71,6 +71,12 @@ void launch_reco_order(const Train& tr, SortWorkspace& ws, const double* d_pred,
     KN_HIP(hipGetLastError());
 }
 
+void launch_reco_id_order(const Train& tr, SortWorkspace& ws, uint64_t* k_a, uint64_t* k_b, uint32_t* v_a, uint32_t* by_id, hipStream_t st) {
+    k_reco_id_keys<<<(unsigned)ceil_div(tr.I, TPB), TPB, 0, st>>>(tr.I, tr.iid.p, k_a, v_a);
+    sort_pairs_u64_u32(ws, k_a, k_b, v_a, by_id, tr.I, 32, st);
+    KN_HIP(hipGetLastError());
+}
+
 void launch_reco_take(const Train& tr, int32_t m, const uint32_t* d_order, const double* d_pred, int32_t* d_items, double* d_preds, hipStream_t st) {
     if (m <= 0) return;
     k_reco_take<<<(unsigned)ceil_div(m, TPB), TPB, 0, st>>>(m, d_order, tr.iid.p, d_pred, d_items, d_preds);

@@ -23,6 +23,7 @@ FLAG_F32_PANEL = 8    # default similarity panel storage is fp16
 HEAD_ALL = 0xFFFFFFFF
 
 _i32p = C.POINTER(C.c_int32)
+_i64p = C.POINTER(C.c_int64)
 _f64p = C.POINTER(C.c_double)
 
 
@@ -116,7 +117,8 @@ EXPORTS = [
     "knncf_fit", "knncf_fit_device", "knncf_num_users", "knncf_num_items", "knncf_global_avg",
     "knncf_user_avg", "knncf_item_avg", "knncf_item_avg_dev", "knncf_item_avg_dev_rdd", "knncf_similarity",
     "knncf_knn_similarity", "knncf_neighbors", "knncf_neighbors_batch", "knncf_predict", "knncf_recommend",
-    "knncf_query_neighbors", "knncf_query_predict", "knncf_query_recommend", "knncf_predict_batch",
+    "knncf_query_neighbors", "knncf_query_predict", "knncf_query_recommend",
+    "knncf_query_neighbors_batch", "knncf_query_predict_batch", "knncf_query_recommend_batch", "knncf_predict_batch",
     "knncf_predict_batch_device", "knncf_mae", "knncf_mae_device", "knncf_mae_sweep", "knncf_mae_sweep_device", "knncf_shard_view_get",
     "knncf_shard_commit", "knncf_get_timings", "knncf_reset_timings", "knncf_reset_neighbors",
     "knncf_set_k", "knncf_load_file", "knncf_load_file_cached", "knncf_free_ratings", "knncf_load_personal", "knncf_free_personal", "knncf_neighbors_save", "knncf_neighbors_load",
@@ -198,6 +200,10 @@ def load_library():
     L.knncf_query_neighbors.argtypes = [C.c_void_p, C.c_int32, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p]
     L.knncf_query_predict.argtypes = [C.c_void_p, C.c_int, C.c_int32, _i32p, _f64p, C.c_int64, _i32p, C.c_int64, _f64p]
     L.knncf_query_recommend.argtypes = [C.c_void_p, C.c_int, C.c_int32, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p]
+    L.knncf_query_neighbors_batch.argtypes = [C.c_void_p, _i32p, _i64p, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p, _i32p]
+    L.knncf_query_predict_batch.argtypes = [C.c_void_p, C.c_int, _i32p, _i64p, _i32p, _f64p, C.c_int64, _i64p, _i32p, _f64p, _i32p]
+    L.knncf_query_recommend_batch.argtypes = [C.c_void_p, C.c_int, _i32p, _i64p, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p,
+                                              _i32p, _i32p]
     L.knncf_predict_batch.argtypes = [C.c_void_p, C.c_int, _i32p, _i32p, C.c_int64, _f64p]
     L.knncf_predict_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.knncf_mae.argtypes = [C.c_void_p, C.c_int, _i32p, _i32p, _f64p, C.c_int64, _f64p]
@@ -449,6 +455,95 @@ class Engine:
         self._check(self._lib.knncf_query_recommend(self._h, PRED_KNN, q, it.ctypes.data_as(_i32p), rt.ctypes.data_as(_f64p), len(it),
                                                     n, ids.ctypes.data_as(_i32p), preds.ctypes.data_as(_f64p), C.byref(c)))
         return ids[:c.value].copy(), preds[:c.value].copy()
+
+    # ---- batched fold-in queries (knncf_query_*_batch) -------------------------------------
+    @staticmethod
+    def _query_batch(queries):
+        """validated CSR (users, offsets, items, ratings) of a sequence of (user, items, ratings): ValueError before any C
+        call.  An empty query is allowed here: it gets its own status (E_INVALID), like every per-query failure."""
+        users, its, rts, offsets = [], [], [], [0]
+        for q in queries:
+            if not isinstance(q, (tuple, list)) or len(q) != 3:
+                raise ValueError("a query is (user, items, ratings)")
+            user, items, ratings = q
+            if isinstance(user, (bool, np.bool_)) or not isinstance(user, (int, np.integer)) or not -2**31 <= int(user) < 2**31:
+                raise ValueError("user must be a 32-bit integer id")
+            it, rt = np.asarray(items), np.asarray(ratings)
+            if it.ndim != 1 or rt.ndim != 1 or len(it) != len(rt):
+                raise ValueError("items and ratings must be 1-D and of the same length")
+            if len(it):
+                if it.dtype.kind not in "iu" or it.min() < -2**31 or it.max() >= 2**31:
+                    raise ValueError("items must be 32-bit integer ids")
+                if rt.dtype.kind not in "iuf":
+                    raise ValueError("ratings must be numbers")
+            users.append(int(user))
+            its.append(it.astype(np.int32))
+            rts.append(rt.astype(np.float64))
+            offsets.append(offsets[-1] + len(it))
+        if offsets[-1] >= 2**31:
+            raise ValueError("fewer than 2^31 query ratings per call")
+        cat = lambda parts, dt: np.ascontiguousarray(np.concatenate(parts) if parts else np.empty(0), dtype=dt)
+        return (np.asarray(users, dtype=np.int32), np.asarray(offsets, dtype=np.int64), cat(its, np.int32), cat(rts, np.float64))
+
+    @staticmethod
+    def _ptr(a, t):
+        return a.ctypes.data_as(t) if len(a) else C.cast(None, t)
+
+    def neighbors_for_batch(self, queries, cap=None):
+        """neighbors_for of every (user, items, ratings) of `queries`, answered in chunks on the device:
+        ([(ids, sims)] per query, statuses int32 [B]).  A failed query (status != OK) has empty arrays."""
+        us, off, it, rt = self._query_batch(queries)
+        if cap is None:
+            cap = max(1, self.k)
+        if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or cap < 0:
+            raise ValueError("cap must be a non-negative integer")
+        cap, B = int(cap), len(us)
+        ids = np.empty((B, cap), dtype=np.int32)
+        sims = np.empty((B, cap), dtype=np.float64)
+        counts = np.zeros(B, dtype=np.int32)
+        st = np.zeros(B, dtype=np.int32)
+        p = self._ptr
+        self._check(self._lib.knncf_query_neighbors_batch(self._h, p(us, _i32p), p(off, _i64p), p(it, _i32p), p(rt, _f64p), B, cap,
+                                                          p(ids.reshape(-1), _i32p), p(sims.reshape(-1), _f64p), p(counts, _i32p),
+                                                          p(st, _i32p)))
+        return [(ids[b, :min(counts[b], cap)].copy(), sims[b, :min(counts[b], cap)].copy()) for b in range(B)], st
+
+    def predict_for_batch(self, queries, pred_items):
+        """predict_for of every query; pred_items is one sequence of item ids per query: ([float64 array] per query, statuses).
+        A failed query's array holds NaN."""
+        us, off, it, rt = self._query_batch(queries)
+        B = len(us)
+        pis = [np.asarray(x) for x in pred_items]
+        if len(pis) != B:
+            raise ValueError("one pred_items sequence per query")
+        for x in pis:
+            if x.ndim != 1 or (len(x) and x.dtype.kind not in "iu"):
+                raise ValueError("pred_items must be 1-D arrays of integer ids")
+        poff = np.zeros(B + 1, dtype=np.int64)
+        poff[1:] = np.cumsum([len(x) for x in pis])
+        pi = np.ascontiguousarray(np.concatenate(pis) if B and poff[-1] else np.empty(0), dtype=np.int32)
+        out = np.full(int(poff[-1]), np.nan, dtype=np.float64)
+        st = np.zeros(B, dtype=np.int32)
+        p = self._ptr
+        self._check(self._lib.knncf_query_predict_batch(self._h, PRED_KNN, p(us, _i32p), p(off, _i64p), p(it, _i32p), p(rt, _f64p), B,
+                                                        p(poff, _i64p), p(pi, _i32p), p(out, _f64p), p(st, _i32p)))
+        return [out[poff[b]:poff[b + 1]].copy() for b in range(B)], st
+
+    def recommend_for_batch(self, queries, n):
+        """recommend_for(n) of every query: ([(item ids, predictions)] per query, statuses).  A failed query has empty arrays."""
+        us, off, it, rt = self._query_batch(queries)
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0 or n >= 2**31:
+            raise ValueError("n must be a non-negative 32-bit integer")
+        n, B = int(n), len(us)
+        ids = np.empty((B, n), dtype=np.int32)
+        preds = np.empty((B, n), dtype=np.float64)
+        counts = np.zeros(B, dtype=np.int32)
+        st = np.zeros(B, dtype=np.int32)
+        p = self._ptr
+        self._check(self._lib.knncf_query_recommend_batch(self._h, PRED_KNN, p(us, _i32p), p(off, _i64p), p(it, _i32p), p(rt, _f64p), B,
+                                                          n, p(ids.reshape(-1), _i32p), p(preds.reshape(-1), _f64p), p(counts, _i32p),
+                                                          p(st, _i32p)))
+        return [(ids[b, :counts[b]].copy(), preds[b, :counts[b]].copy()) for b in range(B)], st
 
     # ---- batch -------------------------------------------------------------------------
     def predict_batch(self, predictor, users, items):
