@@ -75,6 +75,7 @@ struct knncf_handle {
     DArr<uint8_t> reco_rated;
     QueryScratch query;  // fold-in queries (foldin.hip)
     QueryBatchScratch query_batch;
+    RecoBatchScratch reco_batch;  // knncf_recommend_batch (reco_batch.hip); lends query_batch's prediction and sort buffers
     DArr<int32_t> build_list, build_count;
     DArr<uint32_t> first_row;
     // test scratch
@@ -1585,6 +1586,33 @@ int knncf_neighbors(knncf_handle* h, int32_t u, int32_t cap, int32_t* ids, doubl
     });
 }
 
+// the neighbourhoods of the dense users du[0 .. n) (-1: absent from train) that do not exist yet, built in ONE batch and
+// numbered (call epoch, position in du): the memo history of calls for du[0], du[1], ... in this order
+static void build_missing_neighbors(knncf_handle* h, const std::vector<int32_t>& du) {
+    Train& tr = h->tr;
+    NeighborTable& nt = h->nt;
+    hipStream_t st = h->stream;
+    if (tr.U < 2 || nt.kcap <= 0) return;
+    const int64_t n = (int64_t)du.size();
+    std::vector<int64_t> seq((size_t)tr.U);
+    KN_HIP(hipMemcpyAsync(seq.data(), nt.seq.p, seq.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    KN_HIP(hipStreamSynchronize(st));
+    std::vector<int32_t> fresh;
+    for (int64_t j = 0; j < n; ++j)
+        if (du[j] >= 0 && seq[du[j]] < 0) {
+            seq[du[j]] = (h->epoch << 32) | (int64_t)std::min<int64_t>(j, 0xffffffffll);
+            fresh.push_back(du[j]);
+        }
+    if (fresh.empty()) return;
+    require_shard_numbering(h);
+    h->epoch += 1;
+    h->build_list.ensure(tr.U);
+    KN_HIP(hipMemcpyAsync(nt.seq.p, seq.data(), seq.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    KN_HIP(hipMemcpyAsync(h->build_list.p, fresh.data(), fresh.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    KN_HIP(hipStreamSynchronize(st));
+    build_neighbors(h, (int32_t)fresh.size());
+}
+
 // getNeighbors(train, k, sim) for many users: the missing neighbourhoods are built in ONE batch (memo history: as if the
 // closure had been called for users[0], users[1], ... in this order), then the lists are copied out
 static void do_neighbors_batch(knncf_handle* h, const int32_t* users, int64_t n, int32_t cap, int32_t* ids, double* sims, int32_t* counts) {
@@ -1602,26 +1630,7 @@ static void do_neighbors_batch(knncf_handle* h, const int32_t* users, int64_t n,
         KN_REQUIRE(du[j] < 0 || (du[j] >= tr.own_lo && du[j] < tr.own_hi), KNNCF_E_INVALID, "user belongs to another shard");
     }
     const bool have_lists = tr.U >= 2 && nt.kcap > 0;
-    if (have_lists) {
-        std::vector<int64_t> seq((size_t)tr.U);
-        KN_HIP(hipMemcpyAsync(seq.data(), nt.seq.p, seq.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        KN_HIP(hipStreamSynchronize(st));
-        std::vector<int32_t> fresh;
-        for (int64_t j = 0; j < n; ++j)
-            if (du[j] >= 0 && seq[du[j]] < 0) {
-                seq[du[j]] = (h->epoch << 32) | (int64_t)std::min<int64_t>(j, 0xffffffffll);
-                fresh.push_back(du[j]);
-            }
-        if (!fresh.empty()) {
-            require_shard_numbering(h);
-            h->epoch += 1;
-            h->build_list.ensure(tr.U);
-            KN_HIP(hipMemcpyAsync(nt.seq.p, seq.data(), seq.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
-            KN_HIP(hipMemcpyAsync(h->build_list.p, fresh.data(), fresh.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            KN_HIP(hipStreamSynchronize(st));
-            build_neighbors(h, (int32_t)fresh.size());
-        }
-    }
+    build_missing_neighbors(h, du);
     const size_t kc = (size_t)std::max(nt.kcap, 1);
     std::vector<int32_t> h_cnt, h_idx;
     std::vector<double> h_sim;
@@ -1668,6 +1677,116 @@ static void do_neighbors_batch(knncf_handle* h, const int32_t* users, int64_t n,
 
 int knncf_neighbors_batch(knncf_handle* h, const int32_t* users, int64_t n, int32_t cap, int32_t* ids, double* sims, int32_t* counts) {
     return guarded(h, [&] { do_neighbors_batch(h, users, n, cap, ids, sims, counts); });
+}
+
+// users per chunk of knncf_recommend_batch: the rule of knncf.h ("Batched recommendations")
+static int64_t recommend_batch_chunk(knncf_handle* h) {
+    int64_t budget = h->cfg.workspace_bytes / 2;
+    if (h->cfg.workspace_bytes <= 0) {
+        size_t free_b = 0, total_b = 0;
+        KN_HIP(hipMemGetInfo(&free_b, &total_b));
+        budget = (int64_t)std::min<size_t>((size_t)48 << 30, free_b / 4);
+    }
+    int64_t C = std::min<int64_t>(RB_MAX_CHUNK, budget / reco_batch_bytes(h->tr.I));
+    C = std::min<int64_t>(C, (int64_t)0x7fffffff / h->tr.I);  // slot * I + item is a 31-bit cell
+    return std::max<int64_t>(C, 1);
+}
+
+// recommendations(train, predictor)(users[b], n) :651-674 for b = 0 .. n_users-1, "as if knncf_recommend had been called in
+// this order": the missing neighbourhoods are built in one batch (build_missing_neighbors: knncf_neighbors_batch's state),
+// then chunks of users go through reco_batch.hip
+static void do_recommend_batch(knncf_handle* h, int predictor, const int32_t* users, int64_t B, int32_t n, int32_t* out_items,
+                               double* out_preds, int32_t* counts) {
+    require_fitted(h);
+    KN_REQUIRE(B >= 0 && n >= 0, KNNCF_E_INVALID, "recommend batch: n_users or n < 0");
+    if (B == 0) return;
+    KN_REQUIRE(users && counts && (n == 0 || (out_items && out_preds)), KNNCF_E_INVALID, "recommend batch: null argument");
+    if (n == 0) {
+        std::fill(counts, counts + B, 0);
+        return;
+    }
+    KN_REQUIRE(predictor >= KNNCF_PRED_GLOBAL_AVG && predictor <= KNNCF_PRED_PERSONALIZED, KNNCF_E_INVALID, "unknown predictor");
+    Train& tr = h->tr;
+    NeighborTable& nt = h->nt;
+    hipStream_t st = h->stream;
+    const int32_t I = tr.I;
+    load_host_ids(h);
+    std::vector<int32_t> du((size_t)B);
+    bool any_known = false;
+    for (int64_t b = 0; b < B; ++b) {
+        du[b] = dense_lookup(h->h_ukeys.data(), tr.U, users[b]);
+        KN_REQUIRE(du[b] < 0 ? h->cfg.shard_rank == 0 : (du[b] >= tr.own_lo && du[b] < tr.own_hi), KNNCF_E_STATE,
+                   "recommend batch: a user belongs to another shard");
+        any_known = any_known || du[b] >= 0;
+    }
+    const bool knn = predictor == KNNCF_PRED_KNN;
+    if (knn && any_known && tr.U >= 2 && nt.kcap > 0) {
+        KN_REQUIRE(h->cfg.similarity != KNNCF_SIM_ONE, KNNCF_E_UNSUPPORTED,
+                   "kNN neighbourhoods with similarityOne: every similarity is 1.0, the neighbourhood is the first k users in Set order — not built");
+        build_missing_neighbors(h, du);
+    }
+    // the kNN fold of reco_batch.hip reads the lists as they are; longer lists (and the other predictors) take the general batch
+    const bool fold = knn && h->cfg.similarity != KNNCF_SIM_ONE && nt.kcap <= RB_MAX_K && tr.n < (int64_t)0xffffffffll;
+    const bool fast_select = n <= RB_FAST_N;
+    const int32_t width = (int32_t)std::min<int64_t>(n, I);  // cells of a row that can be filled
+    QueryBatchScratch& bs = h->query_batch;
+    RecoBatchScratch& rb = h->reco_batch;
+    h->prep.join_commit(st);
+    const int64_t chunk = recommend_batch_chunk(h);
+    if (fast_select) {
+        Stage s(h, &h->tm.predict_ms);
+        reco_batch_id_rank(tr, bs, rb, h->prep.sort, st);
+    }
+    std::vector<int32_t> h_items, h_counts;
+    std::vector<double> h_preds;
+    for (int64_t c0 = 0; c0 < B; c0 += chunk) {
+        const int32_t C = (int32_t)std::min<int64_t>(chunk, B - c0);
+        const size_t cells = (size_t)C * (size_t)I;
+        rb.slot_user.ensure(C); rb.slot_raw.ensure(C); rb.counts.ensure(C);
+        bs.pred.ensure(cells); bs.rated.ensure(cells); bs.info.ensure((size_t)4 * C);
+        bs.out_items.ensure((size_t)C * width); bs.out_preds.ensure((size_t)C * width);
+        KN_HIP(hipMemcpyAsync(rb.slot_user.p, du.data() + c0, (size_t)C * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        KN_HIP(hipMemcpyAsync(rb.slot_raw.p, users + c0, (size_t)C * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if (fold) {
+            Stage s(h, &h->tm.predict_ms);
+            reco_batch_fold(tr, nt, rb, C, bs.pred.p, st);
+        } else {
+            rb.row_users.ensure(cells); rb.row_items.ensure(cells);
+            reco_batch_rows(tr, rb, C, rb.row_users.p, rb.row_items.p, st);
+            // (every list the rows need exists: the general batch numbers nothing, and its call epoch is given back)
+            const int64_t epoch = h->epoch;
+            run_predict(h, predictor, rb.row_users.p, rb.row_items.p, nullptr, (int64_t)cells, nullptr, nullptr, bs.pred.p);
+            if (knn) h->epoch = epoch;
+        }
+        {
+            Stage s(h, &h->tm.predict_ms);
+            reco_batch_mark(tr, rb, C, n, bs.rated.p, (long long*)bs.info.p, st);
+            if (fast_select) {
+                reco_batch_select(tr, rb, C, width, bs.pred.p, bs.rated.p, bs.out_items.p, bs.out_preds.p, st);
+            } else {
+                bs.k64_a.ensure(cells); bs.k64_b.ensure(cells); bs.v32_a.ensure(cells); bs.v32_b.ensure(cells);
+                bs.s32_a.ensure(cells); bs.s32_b.ensure(cells);
+                foldin_batch_recommend(tr, bs, h->prep.sort, C, width, bs.out_items.p, bs.out_preds.p, st);
+            }
+        }
+        h_items.resize((size_t)C * width); h_preds.resize((size_t)C * width); h_counts.resize(C);
+        KN_HIP(hipMemcpyAsync(h_items.data(), bs.out_items.p, h_items.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        KN_HIP(hipMemcpyAsync(h_preds.data(), bs.out_preds.p, h_preds.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        KN_HIP(hipMemcpyAsync(h_counts.data(), rb.counts.p, (size_t)C * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        KN_HIP(hipStreamSynchronize(st));
+        for (int32_t s = 0; s < C; ++s) {
+            const int64_t b = c0 + s;
+            const int32_t m = h_counts[s];
+            std::copy(h_items.begin() + (size_t)s * width, h_items.begin() + (size_t)s * width + m, out_items + b * n);
+            std::copy(h_preds.begin() + (size_t)s * width, h_preds.begin() + (size_t)s * width + m, out_preds + b * n);
+            counts[b] = m;
+        }
+    }
+}
+
+int knncf_recommend_batch(knncf_handle* h, int predictor, const int32_t* users, int64_t n_users, int32_t n, int32_t* out_items,
+                          double* out_preds, int32_t* counts) {
+    return guarded(h, [&] { do_recommend_batch(h, predictor, users, n_users, n, out_items, out_preds, counts); });
 }
 
 int knncf_knn_similarity(knncf_handle* h, int32_t u, int32_t v, double* out) {

@@ -379,4 +379,32 @@ void foldin_batch_pick(const Train& tr, QueryBatchScratch& bs, const int32_t* d_
 void foldin_batch_recommend(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, int32_t n, int32_t* d_items,
                             double* d_preds, hipStream_t st);
 
+// ---- reco_batch.hip: recommendations for many users of the fit (knncf_recommend_batch; DESIGN.md "Batched recommendations") ----
+static constexpr int RB_TPB = 256;
+static constexpr int RB_TILE = 2048;      // items per workgroup of the fold and of the tile selection
+static constexpr int RB_CAP = 2560;       // gathered neighbour ratings a fold workgroup holds in LDS at a time (16 B each)
+static constexpr int RB_MAX_K = 2048;     // neighbour lists beyond this take the general prediction batch
+static constexpr int RB_FAST_N = 32;      // n up to here: arg-min selection; beyond: the segmented full order of foldin.hip
+static constexpr int RB_MAX_CHUNK = 1024; // users per chunk at most
+// device bytes per user of a chunk that the chunk rule of knncf.h counts
+inline int64_t reco_batch_bytes(int32_t I) { return 96 * (int64_t)I; }
+struct RecoBatchScratch {
+    DArr<int32_t> slot_user, slot_raw;  // [C] dense user (-1: absent from train) and raw id of each slot
+    DArr<int32_t> counts;               // [C] min(n, I - #rated)
+    DArr<uint32_t> id_rank;             // [I] place of each dense item in ascending raw-id order
+    DArr<uint64_t> p_key;               // [C][tiles][n] the tiles' winners: order key, raw-id rank, dense item
+    DArr<uint32_t> p_rank, p_item;
+    DArr<int32_t> row_users, row_items; // [C][I] rows of the general prediction batch (predictors other than the kNN fold)
+};
+// rb.id_rank (bs lends its key buffers and keeps by_id)
+void reco_batch_id_rank(const Train& tr, QueryBatchScratch& bs, RecoBatchScratch& rb, SortWorkspace& ws, hipStream_t st);
+// d_pred [C][I] = the kNN predictor of every (slot, item) from nt's lists (kcap <= RB_MAX_K, every slot's list built)
+void reco_batch_fold(const Train& tr, const NeighborTable& nt, const RecoBatchScratch& rb, int32_t C, double* d_pred, hipStream_t st);
+void reco_batch_rows(const Train& tr, const RecoBatchScratch& rb, int32_t C, int32_t* d_users, int32_t* d_items, hipStream_t st);
+// d_rated [C][I], d_info [C][4] (k_qb_take's layout: [1] = rated items), rb.counts
+void reco_batch_mark(const Train& tr, const RecoBatchScratch& rb, int32_t C, int32_t n, uint8_t* d_rated, long long* d_info, hipStream_t st);
+// n <= RB_FAST_N: d_items / d_preds [C][n], the first rb.counts[s] cells of row s
+void reco_batch_select(const Train& tr, RecoBatchScratch& rb, int32_t C, int32_t n, const double* d_pred, const uint8_t* d_rated,
+                       int32_t* d_items, double* d_preds, hipStream_t st);
+
 }  // namespace knncf

@@ -116,7 +116,7 @@ EXPORTS = [
     "knncf_version", "knncf_status_string", "knncf_create", "knncf_destroy", "knncf_last_error",
     "knncf_fit", "knncf_fit_device", "knncf_num_users", "knncf_num_items", "knncf_global_avg",
     "knncf_user_avg", "knncf_item_avg", "knncf_item_avg_dev", "knncf_item_avg_dev_rdd", "knncf_similarity",
-    "knncf_knn_similarity", "knncf_neighbors", "knncf_neighbors_batch", "knncf_predict", "knncf_recommend",
+    "knncf_knn_similarity", "knncf_neighbors", "knncf_neighbors_batch", "knncf_predict", "knncf_recommend", "knncf_recommend_batch",
     "knncf_query_neighbors", "knncf_query_predict", "knncf_query_recommend",
     "knncf_query_neighbors_batch", "knncf_query_predict_batch", "knncf_query_recommend_batch", "knncf_predict_batch",
     "knncf_predict_batch_device", "knncf_mae", "knncf_mae_device", "knncf_mae_sweep", "knncf_mae_sweep_device", "knncf_shard_view_get",
@@ -197,6 +197,7 @@ def load_library():
     L.knncf_neighbors_batch.argtypes = [C.c_void_p, _i32p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p]
     L.knncf_predict.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int32, _f64p]
     L.knncf_recommend.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int32, _i32p, _f64p, C.POINTER(C.c_int32)]
+    L.knncf_recommend_batch.argtypes = [C.c_void_p, C.c_int, _i32p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p]
     L.knncf_query_neighbors.argtypes = [C.c_void_p, C.c_int32, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p]
     L.knncf_query_predict.argtypes = [C.c_void_p, C.c_int, C.c_int32, _i32p, _f64p, C.c_int64, _i32p, C.c_int64, _f64p]
     L.knncf_query_recommend.argtypes = [C.c_void_p, C.c_int, C.c_int32, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p]
@@ -396,6 +397,27 @@ class Engine:
         self._check(self._lib.knncf_recommend(self._h, predictor, user, n, ids.ctypes.data_as(_i32p),
                                               preds.ctypes.data_as(_f64p), C.byref(c)))
         return ids[:c.value].copy(), preds[:c.value].copy()
+
+    def recommend_batch(self, predictor, users, n):
+        """recommend(predictor, users[b], n) for every b, as if called in this order (knncf_recommend_batch): (items [B, n]
+        int32, preds [B, n] float64, counts [B] int32); cells past a row's count are -1 / nan.  Missing neighbourhoods are
+        built in one batch; the handle is left as neighbors_batch(users) leaves it."""
+        u = np.asarray(users)
+        if u.ndim != 1:
+            raise ValueError("users must be a 1-D array of ids")
+        if len(u) and (u.dtype.kind not in "iu" or u.min() < -2**31 or u.max() >= 2**31):
+            raise ValueError("users must be 32-bit integer ids")
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0 or n >= 2**31:
+            raise ValueError("n must be a non-negative 32-bit integer")
+        u, n = _i32(u), int(n)
+        B = len(u)
+        items = np.full((B, n), -1, dtype=np.int32)
+        preds = np.full((B, n), np.nan, dtype=np.float64)
+        counts = np.zeros(B, dtype=np.int32)
+        p = self._ptr
+        self._check(self._lib.knncf_recommend_batch(self._h, predictor, p(u, _i32p), B, n, p(items.reshape(-1), _i32p),
+                                                    p(preds.reshape(-1), _f64p), p(counts, _i32p)))
+        return items, preds, counts
 
     # ---- fold-in queries: a user outside the fit (knncf_query_*) ---------------------------
     @staticmethod
