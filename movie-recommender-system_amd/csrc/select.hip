@@ -72,7 +72,9 @@ static constexpr float TAIL_UNFIX = 1.0f / 16777216.0f;
 
 // The histogram covers [HIST_LO, HIST_LO + 1) with NBINS bins of width 1/NBINS; values outside land in the end
 // bins.  (A k-th largest value below HIST_LO puts the threshold in bin 0 = "everything qualifies" and the row takes
-// the exact fallback; one above the range only loosens the threshold to the top bin's edge.)
+// the exact fallback; one above the range only loosens the threshold to the top bin's edge.)  Both ends, the shortlist and
+// store overflows below and the rebuilds they lead to are pinned to the oracle by tests/test_gpu_degenerate_rows.py; HIST_LO
+// and the two capacities appear as literals in tests/test_degenerate_premises.py: move them together.
 static constexpr float HIST_LO = -0.125f;
 __device__ __forceinline__ int sim_bin(float x) {
     int b = (int)floorf((x - HIST_LO) * (float)NBINS);
