@@ -885,7 +885,7 @@ void run_predict(knncf_handle* h, int predictor, const int32_t* d_users, const i
     {
         Stage s(h, &h->tm.predict_ms);
         const uint32_t* d_order = nullptr;
-        const bool by_item = tr.ib_words > 0 && tr.ib_words * 12 <= 48 * 1024;
+        const bool by_item = tr.ib_words > 0 && lds_bitmap_fits(tr.ib_words);
         int64_t n_rows = n;  // rows the prediction kernel walks
         if (kind == KNNCF_PRED_KNN) {  // rows sorted by item (the item's rater bitmap lives in LDS) or else by user
             n_rows = order_test_rows(h, n, by_item, 1);

@@ -3,6 +3,8 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
 
 #include <mutex>
 #include <stdexcept>
@@ -181,5 +183,20 @@ inline int bits_for(uint64_t max_value) {
 }
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int64_t round_up(int64_t a, int64_t b) { return ceil_div(a, b) * b; }
+
+// A bitmap over the users (`words` 64-bit words, 12 B of LDS each with its rank prefix) fits the 48 KiB that the item-grouped
+// prediction kernel, the sweep kernel and the rank id-sort give it: up to 262 144 users.  The order of the test rows
+// (api.cpp: run_predict), launch_predict, launch_predict_sweep and launch_sort_neighbors all ask here, so they cannot disagree.
+// (KNNCF_DEBUG_NO_LDS_BITMAPS: test hook, answers "no" at every shape — the handle then takes the paths of more than
+// 262 144 users: test rows ordered by user, k_predict_knn_rows, k_sort_neighbors_by_id, the sweep probing global memory.)
+inline bool lds_bitmap_fits(int64_t words) { return words * 12 <= 48 * 1024 && !getenv("KNNCF_DEBUG_NO_LDS_BITMAPS"); }
+
+// (KNNCF_DEBUG_TRACE_DISPATCH: test hook — launch_predict (kNN kinds), launch_predict_sweep, launch_rerank and
+// launch_sort_neighbors write "knncf-dispatch <stage> <variant>" to stderr, one line per launch, so that a test can tell
+// which instantiation ran.  Unset: nothing is written.)
+#define KN_TRACE_DISPATCH(fmt, ...)                                                                                 \
+    do {                                                                                                            \
+        if (getenv("KNNCF_DEBUG_TRACE_DISPATCH")) fprintf(stderr, "knncf-dispatch " fmt "\n", ##__VA_ARGS__);         \
+    } while (0)
 
 }  // namespace knncf

@@ -230,7 +230,7 @@ void launch_predict_sweep(const Train& tr, const NeighborTable& nt, const int32_
     A.i_ptr = tr.i_ptr.p; A.it_user = tr.it_user.p; A.it_dev = tr.it_dev.p; A.it_t = tr.it_t.p;
     A.ks = d_ks; A.n_k = n_k;
     // the item's bitmap in LDS when it is built and small enough (the bound of the item-grouped one-k kernel)
-    const bool bits = tr.ib_words > 0 && tr.ib_words * 12 <= 48 * 1024;
+    const bool bits = tr.ib_words > 0 && lds_bitmap_fits(tr.ib_words);
     A.ib_words = bits ? (int32_t)tr.ib_words : 0;
     A.item_bits = reinterpret_cast<const unsigned long long*>(tr.item_bits.p); A.item_rank = tr.item_rank.p;
     const unsigned blocks = (unsigned)ceil_div(n, SWEEP_CHUNK);
@@ -238,6 +238,7 @@ void launch_predict_sweep(const Train& tr, const NeighborTable& nt, const int32_
     const int uo = unknown_users_owned ? 1 : 0;
 #define KN_LAUNCH_SWEEP(CAPV, WV)                                                                                              \
     do {                                                                                                                       \
+        KN_TRACE_DISPATCH("sweep CAP=%d bits=%d", CAPV, bits ? 1 : 0);                                                         \
         if (bits) {                                                                                                            \
             KN_HIP(hipFuncSetAttribute((const void*)k_predict_knn_sweep<CAPV, WV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
             k_predict_knn_sweep<CAPV, WV, true><<<blocks, WV * 64, smem, st>>>(A, n, n_total, d_du, d_di, d_ratings, d_order, d_pred, d_abs_err, d_owned, uo); \

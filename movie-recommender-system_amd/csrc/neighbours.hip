@@ -239,7 +239,8 @@ void launch_sort_neighbors(NeighborTable& nt, int32_t U, int32_t n_rows, const i
     {
         const int32_t words = (int32_t)ceil_div((int64_t)U, 64);
         const size_t lds = (size_t)words * 12;
-        if (lds <= 48 * 1024) {
+        if (lds_bitmap_fits(words)) {
+            KN_TRACE_DISPATCH("idsort rank");
             k_rank_neighbors_by_id<<<n_rows, 256, lds, st>>>(n_rows, d_row_user, nt.kcap, words, nt.idx.p, nt.sim.p, nt.cnt.p, nt.uidx.p, nt.usim.p);
             KN_HIP(hipGetLastError());
             return;
@@ -248,6 +249,7 @@ void launch_sort_neighbors(NeighborTable& nt, int32_t U, int32_t n_rows, const i
     int32_t m = 128;
     while (m < nt.kcap) m <<= 1;
     const size_t smem = (size_t)m * 8;
+    KN_TRACE_DISPATCH("idsort bitonic m=%d", m);
     k_sort_neighbors_by_id<<<n_rows, 256, smem, st>>>(n_rows, d_row_user, nt.kcap, nt.idx.p, nt.sim.p, nt.cnt.p, nt.uidx.p, nt.usim.p);
     KN_HIP(hipGetLastError());
 }

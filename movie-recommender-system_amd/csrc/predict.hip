@@ -796,7 +796,7 @@ void launch_predict(const Train& tr, NeighborTable* nt, int predictor, int64_t n
         // matter to it, and it streams the lists as the re-rank left them (reference order).  The kernels that probe in global
         // memory want neighbouring lanes on neighbouring ids (cache sectors): they take the id-sorted copies, made here on
         // first need (0.7 ms per step at the ml-25m shape when it was part of every build).
-        const bool items_path = d_order && order_by_item && tr.ib_words > 0 && tr.ib_words * 12 <= 48 * 1024 && nt->kcap <= 512;
+        const bool items_path = d_order && order_by_item && tr.ib_words > 0 && lds_bitmap_fits(tr.ib_words) && nt->kcap <= 512;
         if (items_path && nt->idx.p != nullptr) {
             A.nbr_uidx = nt->idx.p; A.nbr_usim = nt->sim.p;
         } else {
@@ -817,6 +817,7 @@ void launch_predict(const Train& tr, NeighborTable* nt, int predictor, int64_t n
     do {                                                                                                                  \
         const size_t ibw2 = (size_t)(tr.ib_words + 1) / 2;                                                                  \
         const size_t smem = ibw2 * 16 + ((ibw2 + 1) & ~(size_t)1) * 4 + (size_t)4 * (64 * 16 + (TRV * 64) * 4);               \
+        KN_TRACE_DISPATCH("predict items TR=%d G=%d", TRV, GV);                                                           \
         KN_HIP(hipFuncSetAttribute((const void*)k_predict_knn_items<TRV, GV, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
         k_predict_knn_items<TRV, GV, 4><<<blocks, 256, smem, st>>>(A, n, d_du, d_di, d_ratings, d_order, d_pred, d_abs_err,  \
                                                                   d_owned, unknown_users_owned ? 1 : 0);                \
@@ -839,9 +840,12 @@ void launch_predict(const Train& tr, NeighborTable* nt, int predictor, int64_t n
             A.n_bytes4 = (uint32_t)(tr.n * 4);
             const int trips = (nt->kcap + 63) / 64;
             const unsigned blocks = (unsigned)ceil_div(ceil_div(n, 32), 4);
-#define KN_LAUNCH_ROWS(TRV, GV)                                                                                   \
-    k_predict_knn_rows<TRV, GV, 4><<<blocks, 256, 0, st>>>(A, n, d_du, d_di, d_ratings, d_order, d_pred, d_abs_err, \
-                                                           d_owned, unknown_users_owned ? 1 : 0)
+#define KN_LAUNCH_ROWS(TRV, GV)                                                                                       \
+    do {                                                                                                              \
+        KN_TRACE_DISPATCH("predict rows TR=%d G=%d", TRV, GV);                                                        \
+        k_predict_knn_rows<TRV, GV, 4><<<blocks, 256, 0, st>>>(A, n, d_du, d_di, d_ratings, d_order, d_pred, d_abs_err, \
+                                                               d_owned, unknown_users_owned ? 1 : 0);                 \
+    } while (0)
             if (trips <= 1) KN_LAUNCH_ROWS(1, 4);
             else if (trips <= 2) KN_LAUNCH_ROWS(2, 4);
             else if (trips <= 4) KN_LAUNCH_ROWS(4, 2);
@@ -851,9 +855,12 @@ void launch_predict(const Train& tr, NeighborTable* nt, int predictor, int64_t n
             KN_HIP(hipGetLastError());
             return;
         }
-#define KN_LAUNCH_KNN(CAPV, WV)                                                                        \
-    k_predict_knn<CAPV, WV><<<(unsigned)ceil_div(n, WV), WV * 64, 0, st>>>(                              \
-        A, n, d_du, d_di, d_ratings, d_order, d_pred, d_abs_err, d_owned, unknown_users_owned ? 1 : 0)
+#define KN_LAUNCH_KNN(CAPV, WV)                                                                            \
+    do {                                                                                                   \
+        KN_TRACE_DISPATCH("predict general CAP=%d", CAPV);                                                 \
+        k_predict_knn<CAPV, WV><<<(unsigned)ceil_div(n, WV), WV * 64, 0, st>>>(                              \
+            A, n, d_du, d_di, d_ratings, d_order, d_pred, d_abs_err, d_owned, unknown_users_owned ? 1 : 0); \
+    } while (0)
         if (nt->kcap <= 64) KN_LAUNCH_KNN(64, 4);
         else if (nt->kcap <= 128) KN_LAUNCH_KNN(128, 4);
         else if (nt->kcap <= 256) KN_LAUNCH_KNN(256, 4);

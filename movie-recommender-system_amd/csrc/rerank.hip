@@ -756,7 +756,11 @@ void launch_rerank(const Train& tr, NeighborTable& nt, int32_t n_rows, const int
     }
     Rows R{tr.u_ptr.p, tr.s_col.p, tr.s_t.p, tr.s_pre.p, (uint32_t)(tr.n * 4), (uint32_t)(tr.n * 8)};
     const float* apx = verify ? cand_approx : nullptr;
-#define KN_RERANK(TILEV, JACV) launch_rerank_tile<TILEV, JACV>(R, tr, nt, n_rows, d_row_user, cap, cand_idx, apx, cand_cnt, cand_eps, d_stats, d_row_entries, st, sl)
+#define KN_RERANK(TILEV, JACV)                                                                                                                  \
+    do {                                                                                                                                        \
+        KN_TRACE_DISPATCH("rerank TILE=%d jaccard=%d", TILEV, JACV ? 1 : 0);                                                                    \
+        launch_rerank_tile<TILEV, JACV>(R, tr, nt, n_rows, d_row_user, cap, cand_idx, apx, cand_cnt, cand_eps, d_stats, d_row_entries, st, sl); \
+    } while (0)
     if (tr.jaccard) {
         if (nt.kcap <= 384) KN_RERANK(512, true);
         else if (nt.kcap <= 512) KN_RERANK(1024, true);

@@ -402,11 +402,18 @@ def test_two_shards_on_one_gpu_equal_single_engine(kn, pkg, oracle, synth, monke
     assert total / count == pytest.approx(want, abs=MAE_TOL)
 
 
-def test_wide_shape_takes_the_large_u_paths(kn, oracle, synth):
+def test_wide_shape_takes_the_large_u_paths(kn, oracle, synth, monkeypatch, capfd):
     """U = 300 000 users: the similarity row spans 19 column tiles (more than the per-entry counts held in
     registers: select.hip reads the tile table per tile) and the item bitmaps no longer fit in LDS (prediction falls
-    back to k_predict_knn_rows: bitmaps in global memory, rows sorted by user).  Sampled users bit for bit."""
+    back to k_predict_knn_rows: bitmaps in global memory, rows sorted by user).  Sampled users bit for bit.
+    Then the default k = 300 on the same handle: the (5,2) form of that kernel and the bitonic id-sort at m = 512, taken
+    here by the shape itself (tests/test_gpu_k_classes.py reaches them at a small shape through a test hook)."""
     import torch
+
+    monkeypatch.setenv("KNNCF_DEBUG_TRACE_DISPATCH", "1")
+
+    def dispatched():
+        return {ln[len("knncf-dispatch "):] for ln in capfd.readouterr().err.splitlines() if ln.startswith("knncf-dispatch ")}
 
     d = synth.syn_scaled(300_000, 4_000, 6_000_000, seed=77, half_stars=False)
     dev = torch.device("cuda", 0)
@@ -432,6 +439,25 @@ def test_wide_shape_takes_the_large_u_paths(kn, oracle, synth):
         rows = np.nonzero(d.test.users == u)[0]
         for r_ in rows[:8]:
             assert preds[r_] == p.predict(int(u), int(d.test.items[r_]))
+    assert "predict rows TR=1 G=4" in dispatched()
+    k = 300
+    e.set_k(k)
+    e.reset_timings()
+    preds = torch.zeros(len(d.test.users), dtype=torch.float64, device=dev)
+    s, c = e.mae_device(kn.PRED_KNN, *te, pred_out=preds)
+    preds = preds.cpu().numpy()
+    assert c == len(d.test.users) and np.isfinite(preds).all()
+    assert e.timings()["max_bound_violation"] <= 0.0
+    p = m.pipeline(oracle.SIM_COSINE, k)
+    for u in users[:: len(users) // 12][:12]:
+        ids, sims = e.neighbors(int(u))
+        oids, osims = p.neighbors(int(u))
+        assert len(ids) == k and ids.tolist() == oids.tolist(), f"user {u}"
+        assert np.array_equal(sims.view(np.int64), osims.view(np.int64)), f"user {u}"
+        for r_ in np.nonzero(d.test.users == u)[0]:
+            want = p.predict(int(u), int(d.test.items[r_]))
+            assert preds[r_:r_ + 1].view(np.int64)[0] == np.float64(want).view(np.int64), (int(u), int(r_), preds[r_], want)
+    assert {"predict rows TR=5 G=2", "idsort bitonic m=512"} <= dispatched()
     e.close()
 
 
