@@ -221,7 +221,8 @@ int knncf_recommend_batch(knncf_handle* h, int predictor, const int32_t* users, 
  * before a fit; KNNCF_E_INVALID if `user` occurs in train, a pointer is null or n_ratings <= 0; KNNCF_E_DUPLICATE if
  * the query repeats an item; KNNCF_E_NONFINITE for a non-finite deviation (as knncf_fit).  Read-only on the handle:
  * the neighbour table, its build history and everything knncf_neighbors / knncf_mae / knncf_neighbors_save observe
- * stay as they were. */
+ * stay as they were.  Each call is the batched call below with one query (a chunk of one, no chunk rule), except that the
+ * query's status is the call's return value and knncf_last_error reads "query: <reason>". */
 int knncf_query_neighbors(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
                           int32_t cap, int32_t* ids, double* sims, int32_t* count);
 int knncf_query_predict(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
@@ -253,7 +254,7 @@ int knncf_query_recommend(knncf_handle* h, int predictor, int32_t user, const in
  *     budget = workspace_bytes / 2 if workspace_bytes > 0, else min(48 GiB, free device memory / 4)
  * so a call makes ceil(n_queries / C) chunks.  (The gathered neighbour ratings of a chunk are allocated beside that as they
  * are needed; a chunk whose neighbours hold 2^32 - 1 ratings or more fails the call with KNNCF_E_UNSUPPORTED.)  Failed queries
- * keep their place in their chunk.  A chunk with fewer than 32 answerable queries runs the single-query similarity kernel once
+ * keep their place in their chunk.  A chunk with fewer than 32 answerable queries runs the one-query similarity kernel once
  * per query; larger ones read every train row once for the whole chunk.  The results do not depend on C. */
 int knncf_query_neighbors_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
                                 const double* ratings, int64_t n_queries, int32_t cap, int32_t* ids, double* sims, int32_t* counts,

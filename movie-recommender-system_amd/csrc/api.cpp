@@ -73,8 +73,7 @@ struct knncf_handle {
     DArr<int32_t> reco_users, reco_items, reco_out_items;
     DArr<double> reco_pred, reco_out_preds;
     DArr<uint8_t> reco_rated;
-    QueryScratch query;  // fold-in queries (foldin.hip)
-    QueryBatchScratch query_batch;
+    QueryBatchScratch query_batch;  // fold-in queries (foldin.hip)
     RecoBatchScratch reco_batch;  // knncf_recommend_batch (reco_batch.hip); lends query_batch's prediction and sort buffers
     DArr<int32_t> build_list, build_count;
     DArr<uint32_t> first_row;
@@ -1023,80 +1022,20 @@ void do_recommend(knncf_handle* h, int predictor, int32_t user, int32_t n, int32
     *count = m;
 }
 
-// ---- fold-in queries: one user outside the fit (foldin.hip) -----------------------------------------------------------
+// ---- fold-in queries: users outside the fit, answered chunk by chunk (foldin.hip) ------------------------------------------
 // Every answer is the reference's on aug = train ++ the query rows with fresh closures whose first evaluation is the
 // query user's.  Read-only on the handle: the neighbour table, its sequence numbers and epoch are not touched.
+// knncf_query_*_batch take B independent queries; a single call is a chunk of one.
 constexpr int64_t QUERY_MAX_RATINGS = 65536;
+enum QueryBatchMode { QB_NEIGHBORS, QB_PREDICT, QB_RECOMMEND };
 
-QueryInfo query_prepare(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
-                        int64_t n_ratings) {
-    require_fitted(h, false);
-    KN_REQUIRE(items && ratings && n_ratings > 0, KNNCF_E_INVALID, "query: null ratings or n_ratings <= 0");
+// what the handle must be for any fold-in query, single or batched
+void require_query_support(knncf_handle* h, int predictor) {
     KN_REQUIRE(predictor == KNNCF_PRED_KNN, KNNCF_E_UNSUPPORTED, "query: only KNNCF_PRED_KNN");
     KN_REQUIRE(h->cfg.similarity != KNNCF_SIM_ONE, KNNCF_E_UNSUPPORTED, "query: adjusted cosine or Jaccard");
     KN_REQUIRE(h->cfg.shard_count == 1, KNNCF_E_UNSUPPORTED, "query: single-shard handles only");
     KN_REQUIRE(h->tr.U >= 5, KNNCF_E_UNSUPPORTED, "query: fewer than 5 train users (the user set changes iteration class)");
-    KN_REQUIRE(n_ratings <= QUERY_MAX_RATINGS, KNNCF_E_UNSUPPORTED, "query: more than 65536 ratings");
-    KN_REQUIRE(dense_user(h, user) < 0, KNNCF_E_INVALID, "query: the user occurs in the training set");
-    h->prep.join_commit(h->stream);
-    return foldin_neighbors(h->tr, h->query, h->prep.sort, user, items, ratings, (int32_t)n_ratings, h->cfg.k, h->stream);
 }
-
-void do_query_neighbors(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
-                        int32_t cap, int32_t* ids, double* sims, int32_t* count) {
-    KN_REQUIRE(count && cap >= 0 && (cap == 0 || (ids && sims)), KNNCF_E_INVALID, "bad output arguments");
-    const QueryInfo qi = query_prepare(h, KNNCF_PRED_KNN, user, items, ratings, n_ratings);
-    const int32_t c = std::min(qi.take, cap);
-    std::vector<int32_t> di(c);
-    if (c > 0) {
-        KN_HIP(hipMemcpyAsync(di.data(), h->query.nbr_idx.p, (size_t)c * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        KN_HIP(hipMemcpyAsync(sims, h->query.nbr_sim.p, (size_t)c * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        KN_HIP(hipStreamSynchronize(h->stream));
-    }
-    for (int32_t j = 0; j < c; ++j) ids[j] = h->h_uid[di[j]];
-    *count = qi.take;
-}
-
-void do_query_predict(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
-                      int64_t n_ratings, const int32_t* pred_items, int64_t m, double* out) {
-    KN_REQUIRE(m >= 0 && (m == 0 || (pred_items && out)), KNNCF_E_INVALID, "bad prediction arguments");
-    const QueryInfo qi = query_prepare(h, predictor, user, items, ratings, n_ratings);
-    if (m == 0) return;
-    hipStream_t st = h->stream;
-    QueryScratch& qs = h->query;
-    foldin_predictions(h->tr, qs, h->prep.sort, qi, st);
-    qs.pick_items.ensure(m); qs.pick_out.ensure(m);
-    KN_HIP(hipMemcpyAsync(qs.pick_items.p, pred_items, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    foldin_pick(h->tr, qs, qs.pick_items.p, m, qs.pick_out.p, st);
-    KN_HIP(hipMemcpyAsync(out, qs.pick_out.p, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
-    KN_HIP(hipStreamSynchronize(st));
-}
-
-// recommendations(aug, predictor)(q, n) :651-674: the train items q has not rated (the query's items unknown to train
-// are rated by q), ordered by reco.hip
-void do_query_recommend(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
-                        int64_t n_ratings, int32_t n, int32_t* out_items, double* out_preds, int32_t* count) {
-    KN_REQUIRE(count && n >= 0 && (n == 0 || (out_items && out_preds)), KNNCF_E_INVALID, "bad arguments");
-    *count = 0;
-    const QueryInfo qi = query_prepare(h, predictor, user, items, ratings, n_ratings);
-    Train& tr = h->tr;
-    const int32_t m = (int32_t)std::min<int64_t>(n, (int64_t)tr.I - qi.known);
-    if (m <= 0) return;
-    hipStream_t st = h->stream;
-    QueryScratch& qs = h->query;
-    foldin_predictions(tr, qs, h->prep.sort, qi, st);
-    qs.k64_a.ensure(tr.I); qs.k64_b.ensure(tr.I); qs.v32_a.ensure(tr.I); qs.v32_b.ensure(tr.I);
-    launch_reco_order(tr, h->prep.sort, qs.pred.p, qs.rated.p, qs.k64_a.p, qs.k64_b.p, qs.v32_a.p, qs.v32_b.p, st);
-    qs.out_items.ensure(m); qs.out_preds.ensure(m);
-    launch_reco_take(tr, m, qs.v32_b.p, qs.pred.p, qs.out_items.p, qs.out_preds.p, st);
-    KN_HIP(hipMemcpyAsync(out_items, qs.out_items.p, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    KN_HIP(hipMemcpyAsync(out_preds, qs.out_preds.p, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
-    KN_HIP(hipStreamSynchronize(st));
-    *count = m;
-}
-
-// ---- batched fold-in queries: B independent queries, answered chunk by chunk (foldin.hip, "batched") -----------------------
-enum QueryBatchMode { QB_NEIGHBORS, QB_PREDICT, QB_RECOMMEND };
 
 // queries per chunk: the rule of knncf.h ("Batched fold-in queries")
 int64_t query_batch_chunk(knncf_handle* h) {
@@ -1112,44 +1051,28 @@ int64_t query_batch_chunk(knncf_handle* h) {
     return std::max<int64_t>(C, 1);
 }
 
+// the first query that was refused (-1: none) and why
+struct QueryFailure {
+    int64_t query = -1;
+    const char* reason = "";
+};
+
+// The B validated queries in chunks of `chunk`: statuses[b] and, where it is KNNCF_OK, query b's answer.
 // mode QB_NEIGHBORS: width = cap, out_i / out_d = ids / sims [B * cap]; QB_RECOMMEND: width = n, out_i / out_d = items /
 // predictions [B * n]; QB_PREDICT: out_d [pred_offsets[B]]
-void do_query_batch(knncf_handle* h, QueryBatchMode mode, int predictor, const int32_t* users, const int64_t* offsets,
-                    const int32_t* items, const double* ratings, int64_t B, int32_t width, const int64_t* pred_offsets,
-                    const int32_t* pred_items, int32_t* out_i, double* out_d, int32_t* counts, int32_t* statuses) {
-    require_fitted(h, false);
-    KN_REQUIRE(B >= 0, KNNCF_E_INVALID, "query batch: n_queries < 0");
-    KN_REQUIRE(mode == QB_PREDICT || width >= 0, KNNCF_E_INVALID, "query batch: cap or n < 0");
-    KN_REQUIRE(predictor == KNNCF_PRED_KNN, KNNCF_E_UNSUPPORTED, "query: only KNNCF_PRED_KNN");
-    KN_REQUIRE(h->cfg.similarity != KNNCF_SIM_ONE, KNNCF_E_UNSUPPORTED, "query: adjusted cosine or Jaccard");
-    KN_REQUIRE(h->cfg.shard_count == 1, KNNCF_E_UNSUPPORTED, "query: single-shard handles only");
-    KN_REQUIRE(h->tr.U >= 5, KNNCF_E_UNSUPPORTED, "query: fewer than 5 train users (the user set changes iteration class)");
-    if (B == 0) return;
-    KN_REQUIRE(users && offsets && statuses && (mode == QB_PREDICT || counts), KNNCF_E_INVALID, "query batch: null argument");
-    KN_REQUIRE(offsets[0] == 0, KNNCF_E_INVALID, "query batch: offsets[0] != 0");
-    for (int64_t b = 0; b < B; ++b) KN_REQUIRE(offsets[b] <= offsets[b + 1], KNNCF_E_INVALID, "query batch: offsets decrease");
-    KN_REQUIRE(offsets[B] < ((int64_t)1 << 31), KNNCF_E_INVALID, "query batch: 2^31 or more ratings in one call");
-    KN_REQUIRE(offsets[B] == 0 || (items && ratings), KNNCF_E_INVALID, "query batch: null ratings");
-    if (mode == QB_PREDICT) {
-        KN_REQUIRE(pred_offsets && pred_offsets[0] == 0, KNNCF_E_INVALID, "query batch: pred_offsets null or not starting at 0");
-        for (int64_t b = 0; b < B; ++b)
-            KN_REQUIRE(pred_offsets[b] <= pred_offsets[b + 1], KNNCF_E_INVALID, "query batch: pred_offsets decrease");
-        KN_REQUIRE(pred_offsets[B] == 0 || (pred_items && out_d), KNNCF_E_INVALID, "query batch: null prediction arguments");
-    } else {
-        KN_REQUIRE(width == 0 || (out_i && out_d), KNNCF_E_INVALID, "query batch: null output");
-    }
+QueryFailure run_query_chunks(knncf_handle* h, QueryBatchMode mode, int64_t chunk, const int32_t* users, const int64_t* offsets,
+                              const int32_t* items, const double* ratings, int64_t B, int32_t width, const int64_t* pred_offsets,
+                              const int32_t* pred_items, int32_t* out_i, double* out_d, int32_t* counts, int32_t* statuses) {
     h->prep.join_commit(h->stream);
     const Train& tr = h->tr;
     QueryBatchScratch& bs = h->query_batch;
     hipStream_t st = h->stream;
-    const int64_t chunk = query_batch_chunk(h);
     const int32_t take = std::max(0, std::min(h->cfg.k, tr.U));
-    int64_t first_failed = -1;
-    const char* first_reason = "";
+    QueryFailure first;
     auto fail = [&](int64_t b, int status, const char* why) {
         statuses[b] = status;
         if (counts) counts[b] = 0;
-        if (first_failed < 0 || b < first_failed) { first_failed = b; first_reason = why; }
+        if (first.query < 0 || b < first.query) first = {b, why};
     };
     std::vector<int64_t> slot_query, qo, ebase;
     std::vector<int32_t> s_users, s_items, h_idx, h_items, pick_slot, pick_items;
@@ -1260,7 +1183,49 @@ void do_query_batch(knncf_handle* h, QueryBatchMode mode, int predictor, const i
             std::copy(h_vals.begin() + (size_t)s * widest, h_vals.begin() + (size_t)s * widest + counts[b], out_d + b * width);
         }
     }
-    if (first_failed >= 0) h->err = "query batch: query " + std::to_string(first_failed) + ": " + first_reason;
+    return first;
+}
+
+void do_query_batch(knncf_handle* h, QueryBatchMode mode, int predictor, const int32_t* users, const int64_t* offsets,
+                    const int32_t* items, const double* ratings, int64_t B, int32_t width, const int64_t* pred_offsets,
+                    const int32_t* pred_items, int32_t* out_i, double* out_d, int32_t* counts, int32_t* statuses) {
+    require_fitted(h, false);
+    KN_REQUIRE(B >= 0, KNNCF_E_INVALID, "query batch: n_queries < 0");
+    KN_REQUIRE(mode == QB_PREDICT || width >= 0, KNNCF_E_INVALID, "query batch: cap or n < 0");
+    require_query_support(h, predictor);
+    if (B == 0) return;
+    KN_REQUIRE(users && offsets && statuses && (mode == QB_PREDICT || counts), KNNCF_E_INVALID, "query batch: null argument");
+    KN_REQUIRE(offsets[0] == 0, KNNCF_E_INVALID, "query batch: offsets[0] != 0");
+    for (int64_t b = 0; b < B; ++b) KN_REQUIRE(offsets[b] <= offsets[b + 1], KNNCF_E_INVALID, "query batch: offsets decrease");
+    KN_REQUIRE(offsets[B] < ((int64_t)1 << 31), KNNCF_E_INVALID, "query batch: 2^31 or more ratings in one call");
+    KN_REQUIRE(offsets[B] == 0 || (items && ratings), KNNCF_E_INVALID, "query batch: null ratings");
+    if (mode == QB_PREDICT) {
+        KN_REQUIRE(pred_offsets && pred_offsets[0] == 0, KNNCF_E_INVALID, "query batch: pred_offsets null or not starting at 0");
+        for (int64_t b = 0; b < B; ++b)
+            KN_REQUIRE(pred_offsets[b] <= pred_offsets[b + 1], KNNCF_E_INVALID, "query batch: pred_offsets decrease");
+        KN_REQUIRE(pred_offsets[B] == 0 || (pred_items && out_d), KNNCF_E_INVALID, "query batch: null prediction arguments");
+    } else {
+        KN_REQUIRE(width == 0 || (out_i && out_d), KNNCF_E_INVALID, "query batch: null output");
+    }
+    const QueryFailure f = run_query_chunks(h, mode, query_batch_chunk(h), users, offsets, items, ratings, B, width, pred_offsets,
+                                            pred_items, out_i, out_d, counts, statuses);
+    if (f.query >= 0) h->err = "query batch: query " + std::to_string(f.query) + ": " + f.reason;
+}
+
+// One query as a chunk of one: the query's status is the call's.  The entry points check their own output arguments first;
+// *count (neighbours: min(k, U); recommendations: min(n, I - known items)) is written on success.
+void do_query_single(knncf_handle* h, QueryBatchMode mode, int predictor, int32_t user, const int32_t* items,
+                     const double* ratings, int64_t n_ratings, int32_t width, const int32_t* pred_items, int64_t m, int32_t* out_i,
+                     double* out_d, int32_t* count) {
+    require_fitted(h, false);
+    KN_REQUIRE(items && ratings && n_ratings > 0, KNNCF_E_INVALID, "query: null ratings or n_ratings <= 0");
+    require_query_support(h, predictor);
+    const int64_t offsets[2] = {0, n_ratings}, pred_offsets[2] = {0, m};
+    int32_t status = KNNCF_OK, c = 0;
+    const QueryFailure f = run_query_chunks(h, mode, 1, &user, offsets, items, ratings, 1, width, pred_offsets, pred_items, out_i,
+                                            out_d, &c, &status);
+    if (f.query >= 0) throw Error(status, std::string("query: ") + f.reason);
+    if (count) *count = c;
 }
 
 // ---- checkpoint / resume of the neighbour table ------------------------------------------------------
@@ -1837,12 +1802,18 @@ int knncf_recommend(knncf_handle* h, int predictor, int32_t user, int32_t n, int
 
 int knncf_query_neighbors(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
                           int32_t cap, int32_t* ids, double* sims, int32_t* count) {
-    return guarded(h, [&] { do_query_neighbors(h, user, items, ratings, n_ratings, cap, ids, sims, count); });
+    return guarded(h, [&] {
+        KN_REQUIRE(count && cap >= 0 && (cap == 0 || (ids && sims)), KNNCF_E_INVALID, "bad output arguments");
+        do_query_single(h, QB_NEIGHBORS, KNNCF_PRED_KNN, user, items, ratings, n_ratings, cap, nullptr, 0, ids, sims, count);
+    });
 }
 
 int knncf_query_predict(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
                         int64_t n_ratings, const int32_t* pred_items, int64_t m, double* out) {
-    return guarded(h, [&] { do_query_predict(h, predictor, user, items, ratings, n_ratings, pred_items, m, out); });
+    return guarded(h, [&] {
+        KN_REQUIRE(m >= 0 && (m == 0 || (pred_items && out)), KNNCF_E_INVALID, "bad prediction arguments");
+        do_query_single(h, QB_PREDICT, predictor, user, items, ratings, n_ratings, 0, pred_items, m, nullptr, out, nullptr);
+    });
 }
 
 int knncf_query_neighbors_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
@@ -1874,7 +1845,11 @@ int knncf_query_recommend_batch(knncf_handle* h, int predictor, const int32_t* u
 
 int knncf_query_recommend(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
                           int64_t n_ratings, int32_t n, int32_t* out_items, double* out_preds, int32_t* count) {
-    return guarded(h, [&] { do_query_recommend(h, predictor, user, items, ratings, n_ratings, n, out_items, out_preds, count); });
+    return guarded(h, [&] {
+        KN_REQUIRE(count && n >= 0 && (n == 0 || (out_items && out_preds)), KNNCF_E_INVALID, "bad arguments");
+        *count = 0;
+        do_query_single(h, QB_RECOMMEND, predictor, user, items, ratings, n_ratings, n, nullptr, 0, out_items, out_preds, count);
+    });
 }
 
 int knncf_neighbors_save(knncf_handle* h, const char* path) {

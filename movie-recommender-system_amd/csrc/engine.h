@@ -296,45 +296,9 @@ void launch_reco_order(const Train& tr, SortWorkspace& ws, const double* d_pred,
 void launch_reco_id_order(const Train& tr, SortWorkspace& ws, uint64_t* k_a, uint64_t* k_b, uint32_t* v_a, uint32_t* by_id, hipStream_t st);
 void launch_reco_take(const Train& tr, int32_t m, const uint32_t* d_order, const double* d_pred, int32_t* d_items, double* d_preds, hipStream_t st);
 
-// ---- foldin.hip: kNN queries of one user outside the fit (DESIGN.md "Fold-in queries") --------------------------
-// handle-owned scratch of the query path; the fit, its neighbour table and its sequence numbers are only read
-struct QueryScratch {
-    DArr<int32_t> items, di, given_d;  // [n] raw items, their dense items; [known] given position of the r-th known item
-    DArr<double> ratings, dev, pre;    // [n] given order
-    DArr<double> pre_d, dev_d;         // [known] dense item order
-    DArr<uint64_t> bits;               // [ceil(I / 64)] the query's known items over the dense item index
-    DArr<int64_t> rank;                // [ceil(I / 64) + 1] exclusive popcount prefixes of `bits`
-    DArr<int64_t> info;                // [4] status bits, known items, neighbour ratings
-    DArr<double> scal;                 // [2] mean, norm
-    DArr<double> sim;                  // [U] exact similarities
-    DArr<uint64_t> k64_a, k64_b;
-    DArr<uint32_t> v32_a, v32_b;
-    DArr<int32_t> nbr_idx, nbr_cnt;    // [k] dense neighbours, reference order
-    DArr<double> nbr_sim;
-    DArr<int64_t> off;                 // [k + 1] first entry of each neighbour's ratings in the gathered list
-    DArr<uint64_t> e_k64_a, e_k64_b;   // [entries] (item, file row) keys
-    DArr<uint32_t> e_v32_a, e_v32_b;
-    DArr<double> e_dev, e_sim;
-    DArr<double> num, den, pred;       // [I]
-    DArr<uint8_t> rated;               // [I]
-    DArr<int32_t> pick_items, out_items;
-    DArr<double> pick_out, out_preds;
-};
-struct QueryInfo {
-    int32_t take = 0;     // neighbours: min(k, U)
-    int32_t known = 0;    // query items present in train
-    int64_t entries = 0;  // ratings of the neighbours
-};
-// query prep + similarity row + top-k (qs.nbr_idx / nbr_sim) + the sizes of the prediction pass; throws the query's
-// KNNCF_E_DUPLICATE / KNNCF_E_NONFINITE
-QueryInfo foldin_neighbors(const Train& tr, QueryScratch& qs, SortWorkspace& ws, int32_t q, const int32_t* h_items,
-                           const double* h_ratings, int32_t n, int32_t k, hipStream_t st);
-// qs.pred / qs.rated over every dense item (after foldin_neighbors)
-void foldin_predictions(const Train& tr, QueryScratch& qs, SortWorkspace& ws, const QueryInfo& qi, hipStream_t st);
-// d_out[j] = prediction of raw item d_items[j] (after foldin_predictions)
-void foldin_pick(const Train& tr, QueryScratch& qs, const int32_t* d_items, int64_t m, double* d_out, hipStream_t st);
-
-// ---- foldin.hip, batched: chunks of independent queries, every stage one launch over the chunk ---------------------
+// ---- foldin.hip: kNN queries of users outside the fit (DESIGN.md "Fold-in queries") ----------------------------------
+// Chunks of independent queries, every stage one launch over the chunk; a single call is a chunk of one.  The scratch is
+// handle-owned; the fit, its neighbour table and its sequence numbers are only read.
 static constexpr uint32_t QUERY_ST_NEG_MEAN = 1u << 8;  // status bit beside ST_NONFINITE / ST_DUPLICATE: the query's mean is negative
 static constexpr int QB_MAX_CHUNK = 64;  // queries per chunk: one lane of k_query_sim_dual's waves each
 static constexpr int QB_DUAL_MIN = 32;   // smaller chunks run k_query_sim once per query instead: measured crossover

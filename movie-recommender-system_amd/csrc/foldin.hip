@@ -1,17 +1,25 @@
-// foldin.hip — fold-in kNN queries: the neighbourhood, predictions and recommendations of ONE user that is not in the
-// fitted training set, given its ratings, without a refit (DESIGN.md "Fold-in queries").
+// foldin.hip — fold-in kNN queries: the neighbourhood, predictions and recommendations of users that are not in the
+// fitted training set, given their ratings, without a refit (DESIGN.md "Fold-in queries").
 //
 // The answers are those of the reference on aug = train ++ query rows (data.union(personal), recommend/Recommender.scala:68)
 // with fresh closures whose first evaluation is the query user's: adding the user changes no existing user's mean,
 // deviations or preprocessed ratings (usersAvg :113, preprocessedRating :470-481), and (allUsers - q).toSeq is the
-// train user order.  So only the query's own quantities are computed here; everything else is read from the fit:
-//   k_q_keys / k_q_prep / k_q_rank / k_q_scatter   query prep: dense items, mean, deviations, hash-ordered norm,
-//                                                  preprocessed values, a dense-item bitmap with rank prefixes
-//   k_query_sim                                     one exact fp64 similarity per train user (one streaming pass of s_col)
-//   fallback keys + radix sort + fallback write     top-k (similarity desc, dense user asc), into query scratch
-//   k_q_offsets / k_q_gather / sort / k_q_fold      the neighbours' ratings grouped by (item, file row): the left folds
-//                                                  of weightedSumDeviation :504-548
-//   k_q_pred                                        predictor :568-585 for every dense item
+// train user order.  So only the query's own quantities are computed here; everything else is read from the fit.
+//
+// There is one path.  A chunk of C <= QB_MAX_CHUNK independent queries goes through the stages below, every stage as ONE
+// launch (or one sort) over the chunk; a single call is a chunk of one.  Rows of the chunk are concatenated in slot order:
+// slot b owns rows [qo[b], qo[b + 1]).  Nothing of one slot enters another, and each slot's arithmetic and its order do not
+// depend on C, so a query's answer is the same bit for bit in whatever chunk it travels.
+//   k_qb_keys / sort (slot, trie key) / k_qb_prep / k_qb_rank / k_qb_scatter   query prep, one workgroup per slot: dense
+//                                       items, mean, deviations, hash-ordered norm, preprocessed values, a dense-item
+//                                       bitmap with rank prefixes
+//   k_qb_transpose + k_query_sim_dual   (C >= QB_DUAL_MIN) every train row read once for the whole chunk, lane b = slot b
+//   k_query_sim per slot                (C <  QB_DUAL_MIN) one exact fp64 similarity per train user (one streaming pass of s_col)
+//   fallback keys over [C][U] / sort 64 bits / stable sort by slot / k_qb_write   top-k (similarity desc, dense user asc)
+//   k_qb_offsets / k_qb_gather / sort (slot * I + item, file row) / k_q_fold      the neighbours' ratings grouped by (item,
+//                                       file row): the left folds of weightedSumDeviation :504-548
+//   k_qb_pred                           predictor :568-585 for every (slot, dense item)
+//   k_qb_reco_keys / sort 64 bits / stable sort by slot / k_qb_take               recommendations
 #include <math.h>
 
 #include <algorithm>
@@ -22,8 +30,6 @@ namespace knncf {
 
 // neighbours.hip
 void launch_fallback_keys(int32_t U, const double* d_exact, uint64_t* d_keys, uint32_t* d_vals, hipStream_t st);
-void launch_fallback_write(int32_t user, int32_t take, int32_t kcap, const uint32_t* d_sorted_vals,
-                           const double* d_exact, int32_t* nbr_idx, double* nbr_sim, int32_t* nbr_cnt, hipStream_t st);
 
 static constexpr int TPB = 256;
 static constexpr int ONE_BLOCK = 1024;
@@ -32,74 +38,6 @@ static constexpr int ONE_BLOCK = 1024;
 static constexpr int64_t SIM_LDS_WORDS = 4096;
 // the predictor answers aug's global average for a user mean < 0 (:571-574): not served by a fold-in query
 static constexpr uint32_t ST_NEG_MEAN = QUERY_ST_NEG_MEAN;
-
-// raw -> dense item through the fit's tables (dense_lookup beyond them); key of the norm's fold order: the trie order of
-// the (q, item) tuple hash (usersWeights :474, N4).  tuple_trie_key(q, .) is a bijection of the item id, so two rows have
-// equal keys only when they repeat an item: after the sort, equal neighbours are the duplicates.
-__global__ void k_q_keys(int32_t n, int32_t q, const int32_t* __restrict__ items, const int32_t* __restrict__ i_table,
-                         int32_t i_cells, const uint32_t* __restrict__ ikeys, int32_t I, int32_t* __restrict__ di,
-                         uint64_t* __restrict__ key, uint32_t* __restrict__ val) {
-    const int32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    const int32_t it = items[j];
-    int32_t d;
-    if (i_cells > 0) d = (it >= 0 && it < i_cells) ? i_table[it] : -1;
-    else d = dense_lookup(ikeys, I, it);
-    di[j] = d;
-    key[j] = tuple_trie_key(q, it);
-    val[j] = (uint32_t)j;
-}
-
-// one workgroup: mean (left fold in the given order, usersAvg :113), deviations (computeNormalizeDeviation :155-169),
-// norm (sqrt of the left fold of dev^2 in tuple-hash order), preprocessed ratings, the bitmap of the known items.
-// info[0] |= status bits, info[1] = number of known items; scal[0] = mean, scal[1] = norm
-__global__ void k_q_prep(int32_t n, const double* __restrict__ r, const uint64_t* __restrict__ skey,
-                         const uint32_t* __restrict__ sval, const int32_t* __restrict__ di, double* __restrict__ dev,
-                         double* __restrict__ pre, unsigned long long* __restrict__ bits, long long* __restrict__ info,
-                         double* __restrict__ scal) {
-    __shared__ double s_avg, s_norm;
-    __shared__ int32_t s_known;
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int32_t j = 0; j < n; ++j) s = s + r[j];
-        const double avg = s / (double)n;
-        double w = 0.0;
-        for (int32_t p = 0; p < n; ++p) {
-            const double x = r[sval[p]];
-            const double d = (x - avg) / scale_fn(x, avg);
-            w = w + d * d;
-        }
-        s_avg = avg;
-        s_norm = sqrt(w);
-        s_known = 0;
-    }
-    __syncthreads();
-    const double avg = s_avg, norm = s_norm;
-    unsigned long long st = 0;
-    int32_t known = 0;
-    for (int32_t j = threadIdx.x; j < n; j += blockDim.x) {
-        const double x = r[j];
-        const double d = (x - avg) / scale_fn(x, avg);
-        if (!isfinite(d)) st |= ST_NONFINITE;
-        dev[j] = d;
-        pre[j] = (norm != 0) ? d / norm : 0.0;
-        const int32_t c = di[j];
-        if (c >= 0) {
-            atomicOr(bits + (c >> 6), 1ull << (c & 63));
-            ++known;
-        }
-        if (j > 0 && skey[j] == skey[j - 1]) st |= ST_DUPLICATE;
-    }
-    if (st) atomicOr((unsigned long long*)info, st);
-    if (known) atomicAdd(&s_known, known);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        info[1] = s_known;
-        scal[0] = avg;
-        scal[1] = norm;
-        if (avg < 0.0) atomicOr((unsigned long long*)info, (unsigned long long)ST_NEG_MEAN);
-    }
-}
 
 // one workgroup: exclusive prefix of cnt(i) over i < m (cnt = popcount of a bitmap word, or a neighbour's row length);
 // out[m] = the total, which every thread returns
@@ -128,29 +66,9 @@ __device__ int64_t block_exclusive_scan(int64_t m, F cnt, int64_t* __restrict__ 
     return part[ONE_BLOCK - 1];
 }
 
-__global__ void __launch_bounds__(ONE_BLOCK) k_q_rank(int64_t W, const unsigned long long* __restrict__ bits,
-                                                      int64_t* __restrict__ rank) {
-    block_exclusive_scan(W, [&](int64_t w) { return (int64_t)__popcll(bits[w]); }, rank);
-}
-
 __device__ __forceinline__ int32_t bit_rank(const unsigned long long* bits, const int64_t* rank, int32_t c) {
     const unsigned long long below = bits[c >> 6] & ((1ull << (c & 63)) - 1ull);
     return (int32_t)rank[c >> 6] + __popcll(below);
-}
-
-// the known items in dense order: preprocessed value, deviation, position in the given order
-__global__ void k_q_scatter(int32_t n, const int32_t* __restrict__ di, const double* __restrict__ pre,
-                            const double* __restrict__ dev, const unsigned long long* __restrict__ bits,
-                            const int64_t* __restrict__ rank, double* __restrict__ pre_d, double* __restrict__ dev_d,
-                            int32_t* __restrict__ given_d) {
-    const int32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    const int32_t c = di[j];
-    if (c < 0) return;
-    const int32_t r = bit_rank(bits, rank, c);
-    pre_d[r] = pre[j];
-    dev_d[r] = dev[j];
-    given_d[r] = j;
 }
 
 // exact similarity of q (first argument, fresh closure: it owns every pair) against every train user, one wave per
@@ -234,33 +152,6 @@ __global__ void __launch_bounds__(TPB) k_query_sim(int32_t U, int32_t nq, bool j
     }
 }
 
-__global__ void __launch_bounds__(ONE_BLOCK) k_q_offsets(int32_t take, const int32_t* __restrict__ nbr,
-                                                         const int64_t* __restrict__ u_ptr, int64_t* __restrict__ off,
-                                                         long long* __restrict__ info) {
-    const int64_t total = block_exclusive_scan(take, [&](int64_t j) { return u_ptr[nbr[j] + 1] - u_ptr[nbr[j]]; }, off);
-    if (threadIdx.x == 0) info[2] = total;
-}
-
-// the neighbours' ratings as (item, train file row) keys: ratedI(i) :508-517 is in file order
-__global__ void __launch_bounds__(TPB) k_q_gather(int32_t take, const int32_t* __restrict__ nbr, const double* __restrict__ nsim,
-                                                  const int64_t* __restrict__ off, const int64_t* __restrict__ u_ptr,
-                                                  const int32_t* __restrict__ s_col, const uint32_t* __restrict__ s_t,
-                                                  const double* __restrict__ s_dev, uint64_t* __restrict__ key,
-                                                  uint32_t* __restrict__ val, double* __restrict__ edev, double* __restrict__ esim) {
-    const int32_t j = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
-    if (j >= take) return;
-    const int32_t v = nbr[j];
-    const int64_t b = u_ptr[v], e = u_ptr[v + 1], o = off[j];
-    const double sj = nsim[j];
-    for (int64_t p = b + (threadIdx.x & 63); p < e; p += 64) {
-        const int64_t x = o + (p - b);
-        key[x] = ((uint64_t)(uint32_t)s_col[p] << 32) | (uint64_t)s_t[p];
-        val[x] = (uint32_t)x;
-        edev[x] = s_dev[p];
-        esim[x] = sj;
-    }
-}
-
 // weightedSumDeviation :517-545 per item: num += dev * s, den += |s| over the item's neighbour ratings in file order
 // (the other raters add dev * 0.0 and 0.0, which change neither sum: num starts at +0.0 and never becomes -0.0)
 __global__ void k_q_fold(int64_t E, const uint64_t* __restrict__ key, const uint32_t* __restrict__ val,
@@ -280,153 +171,9 @@ __global__ void k_q_fold(int64_t E, const uint64_t* __restrict__ key, const uint
     den[item] = d;
 }
 
-// predictor :568-585 for every dense item; q's own row of the item comes last in aug with s(q, q) = 0 (q is not in its
-// own neighbour list)
-__global__ void k_q_pred(int32_t I, const double* __restrict__ num, const double* __restrict__ den,
-                         const unsigned long long* __restrict__ bits, const int64_t* __restrict__ rank,
-                         const double* __restrict__ dev_d, const double* __restrict__ scal, double* __restrict__ pred,
-                         uint8_t* __restrict__ rated) {
-    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= I) return;
-    double a = num[i], d = den[i];
-    const bool mine = (bits[i >> 6] >> (i & 63)) & 1ull;
-    if (mine) {
-        const double s = 0.0;
-        a = a + dev_d[bit_rank(bits, rank, i)] * s;
-        d = d + fabs(s);
-    }
-    const double avg = scal[0];
-    const double w = d > 0 ? a / d : 0.0;
-    pred[i] = avg + w * scale_fn(avg + w, avg);
-    rated[i] = mine ? 1 : 0;
-}
-
-// requested raw items: the dense item's prediction; an item without a train rater has den = 0 (avg exactly)
-__global__ void k_q_pick(int64_t m, const int32_t* __restrict__ items, const int32_t* __restrict__ i_table, int32_t i_cells,
-                         const uint32_t* __restrict__ ikeys, int32_t I, const double* __restrict__ pred,
-                         const double* __restrict__ scal, double* __restrict__ out) {
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= m) return;
-    const int32_t it = items[j];
-    int32_t c;
-    if (i_cells > 0) c = (it >= 0 && it < i_cells) ? i_table[it] : -1;
-    else c = dense_lookup(ikeys, I, it);
-    if (c >= 0) {
-        out[j] = pred[c];
-    } else {
-        const double avg = scal[0], w = 0.0;
-        out[j] = avg + w * scale_fn(avg + w, avg);
-    }
-}
-
 static PerDeviceState g_sim_lds;
 
 static int32_t table_cells(const Train& tr) { return (tr.u_table_n > 0 && tr.i_table_n > 0) ? tr.i_table_n : 0; }
-
-QueryInfo foldin_neighbors(const Train& tr, QueryScratch& qs, SortWorkspace& ws, int32_t q, const int32_t* h_items,
-                           const double* h_ratings, int32_t n, int32_t k, hipStream_t st) {
-    const int32_t U = tr.U, I = tr.I;
-    const int64_t W = ceil_div(I, 64);
-    const int64_t keys = std::max<int64_t>(n, U);
-    qs.items.ensure(n); qs.ratings.ensure(n); qs.di.ensure(n); qs.dev.ensure(n); qs.pre.ensure(n);
-    qs.pre_d.ensure(n); qs.dev_d.ensure(n); qs.given_d.ensure(n);
-    qs.bits.ensure(W); qs.rank.ensure(W + 1);
-    qs.k64_a.ensure(keys); qs.k64_b.ensure(keys); qs.v32_a.ensure(keys); qs.v32_b.ensure(keys);
-    qs.sim.ensure(U);
-    qs.info.ensure(4); qs.scal.ensure(2);
-    const int32_t take = std::max(0, std::min(k, U));
-    qs.nbr_idx.ensure(std::max(take, 1)); qs.nbr_sim.ensure(std::max(take, 1)); qs.nbr_cnt.ensure(1);
-    qs.off.ensure((size_t)take + 1);
-
-    KN_HIP(hipMemcpyAsync(qs.items.p, h_items, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    KN_HIP(hipMemcpyAsync(qs.ratings.p, h_ratings, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-    KN_HIP(hipMemsetAsync(qs.bits.p, 0, (size_t)W * sizeof(uint64_t), st));
-    KN_HIP(hipMemsetAsync(qs.info.p, 0, 4 * sizeof(int64_t), st));
-    // query prep
-    k_q_keys<<<(unsigned)ceil_div(n, TPB), TPB, 0, st>>>(n, q, qs.items.p, tr.i_table.p, table_cells(tr), tr.ikeys.p, I, qs.di.p,
-                                                         qs.k64_a.p, qs.v32_a.p);
-    sort_pairs_u64_u32(ws, qs.k64_a.p, qs.k64_b.p, qs.v32_a.p, qs.v32_b.p, (size_t)n, 32, st);
-    unsigned long long* bits = (unsigned long long*)qs.bits.p;
-    long long* info = (long long*)qs.info.p;
-    k_q_prep<<<1, ONE_BLOCK, 0, st>>>(n, qs.ratings.p, qs.k64_b.p, qs.v32_b.p, qs.di.p, qs.dev.p, qs.pre.p, bits, info, qs.scal.p);
-    k_q_rank<<<1, ONE_BLOCK, 0, st>>>(W, bits, qs.rank.p);
-    k_q_scatter<<<(unsigned)ceil_div(n, TPB), TPB, 0, st>>>(n, qs.di.p, qs.pre.p, qs.dev.p, bits, qs.rank.p, qs.pre_d.p,
-                                                            qs.dev_d.p, qs.given_d.p);
-    KN_HIP(hipGetLastError());
-    // one exact similarity per train user: a few waves per CU walk all rows, each block holds the bitmap once
-    const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(U, TPB / 64), 2048);
-    if (W <= SIM_LDS_WORDS) {
-        const size_t lds = (size_t)W * (sizeof(uint64_t) + sizeof(int64_t));
-        ensure_dynamic_lds(g_sim_lds, (const void*)k_query_sim<true>, lds);
-        k_query_sim<true><<<grid, TPB, lds, st>>>(U, n, tr.jaccard, tr.u_ptr.p, tr.s_col.p, tr.s_pre.p, W, bits, qs.rank.p,
-                                                  qs.pre_d.p, qs.given_d.p, qs.sim.p);
-    } else {
-        k_query_sim<false><<<grid, TPB, 0, st>>>(U, n, tr.jaccard, tr.u_ptr.p, tr.s_col.p, tr.s_pre.p, W, bits, qs.rank.p,
-                                                 qs.pre_d.p, qs.given_d.p, qs.sim.p);
-    }
-    KN_HIP(hipGetLastError());
-    // top-k: (similarity desc, dense user asc) = sortWith(_._2 > _._2) over (allUsers - q).toSeq :608-610
-    launch_fallback_keys(U, qs.sim.p, qs.k64_a.p, qs.v32_a.p, st);
-    sort_pairs_u64_u32(ws, qs.k64_a.p, qs.k64_b.p, qs.v32_a.p, qs.v32_b.p, (size_t)U, 64, st);
-    launch_fallback_write(0, take, take, qs.v32_b.p, qs.sim.p, qs.nbr_idx.p, qs.nbr_sim.p, qs.nbr_cnt.p, st);
-    // sizes of the prediction pass, fetched with the status in the one round trip
-    k_q_offsets<<<1, ONE_BLOCK, 0, st>>>(take, qs.nbr_idx.p, tr.u_ptr.p, qs.off.p, info);
-    KN_HIP(hipGetLastError());
-    long long h_info[4];
-    KN_HIP(hipMemcpyAsync(h_info, qs.info.p, sizeof(h_info), hipMemcpyDeviceToHost, st));
-    KN_HIP(hipStreamSynchronize(st));
-    const uint64_t status = (uint64_t)h_info[0];
-    KN_REQUIRE(!(status & ST_DUPLICATE), KNNCF_E_DUPLICATE, "query: the ratings repeat an item");
-    KN_REQUIRE(!(status & ST_NONFINITE), KNNCF_E_NONFINITE, "query: scale() == 0 gives a non-finite deviation");
-    KN_REQUIRE(!(status & ST_NEG_MEAN), KNNCF_E_UNSUPPORTED,
-               "query: a negative mean rating (the predictor would answer aug's global average)");
-    QueryInfo r;
-    r.take = take;
-    r.known = (int32_t)h_info[1];
-    r.entries = h_info[2];
-    return r;
-}
-
-void foldin_predictions(const Train& tr, QueryScratch& qs, SortWorkspace& ws, const QueryInfo& qi, hipStream_t st) {
-    const int32_t I = tr.I;
-    const int64_t E = qi.entries;
-    qs.num.ensure(I); qs.den.ensure(I); qs.pred.ensure(I); qs.rated.ensure(I);
-    KN_HIP(hipMemsetAsync(qs.num.p, 0, (size_t)I * sizeof(double), st));  // +0.0
-    KN_HIP(hipMemsetAsync(qs.den.p, 0, (size_t)I * sizeof(double), st));
-    if (E > 0) {
-        KN_REQUIRE(E < (int64_t)0xffffffffll, KNNCF_E_UNSUPPORTED, "query: more than 2^32-1 neighbour ratings");
-        qs.e_k64_a.ensure(E); qs.e_k64_b.ensure(E); qs.e_v32_a.ensure(E); qs.e_v32_b.ensure(E);
-        qs.e_dev.ensure(E); qs.e_sim.ensure(E);
-        k_q_gather<<<(unsigned)ceil_div(qi.take, TPB / 64), TPB, 0, st>>>(qi.take, qs.nbr_idx.p, qs.nbr_sim.p, qs.off.p, tr.u_ptr.p,
-                                                                          tr.s_col.p, tr.s_t.p, tr.s_dev.p, qs.e_k64_a.p,
-                                                                          qs.e_v32_a.p, qs.e_dev.p, qs.e_sim.p);
-        sort_pairs_u64_u32(ws, qs.e_k64_a.p, qs.e_k64_b.p, qs.e_v32_a.p, qs.e_v32_b.p, (size_t)E, 32 + bits_for((uint64_t)I), st);
-        k_q_fold<<<(unsigned)ceil_div(E, TPB), TPB, 0, st>>>(E, qs.e_k64_b.p, qs.e_v32_b.p, qs.e_dev.p, qs.e_sim.p, qs.num.p,
-                                                              qs.den.p);
-    }
-    k_q_pred<<<(unsigned)ceil_div(I, TPB), TPB, 0, st>>>(I, qs.num.p, qs.den.p, (const unsigned long long*)qs.bits.p, qs.rank.p,
-                                                         qs.dev_d.p, qs.scal.p, qs.pred.p, qs.rated.p);
-    KN_HIP(hipGetLastError());
-}
-
-void foldin_pick(const Train& tr, QueryScratch& qs, const int32_t* d_items, int64_t m, double* d_out, hipStream_t st) {
-    if (m <= 0) return;
-    k_q_pick<<<(unsigned)ceil_div(m, TPB), TPB, 0, st>>>(m, d_items, tr.i_table.p, table_cells(tr), tr.ikeys.p, tr.I, qs.pred.p,
-                                                         qs.scal.p, d_out);
-    KN_HIP(hipGetLastError());
-}
-
-// ---- batched fold-in queries (knncf_query_*_batch) ------------------------------------------------------------------------
-// A chunk of C <= QB_MAX_CHUNK independent queries goes through the same stages as one query, every stage as ONE launch (or
-// one sort) over the chunk.  Rows of the chunk are concatenated in slot order: slot b owns rows [qo[b], qo[b + 1]).  Each
-// slot's arithmetic is that of the single-query kernels above, in the same order, so row b equals the single call bit for
-// bit; nothing of one slot enters another.
-//   k_qb_keys / sort (slot, trie key) / k_qb_prep / k_qb_rank / k_qb_scatter   query prep, one workgroup per slot
-//   k_qb_transpose + k_query_sim_dual   (C >= QB_DUAL_MIN) every train row read once for the whole chunk, lane b = slot b
-//   k_query_sim per slot                (C <  QB_DUAL_MIN)
-//   fallback keys over [C][U] / sort 64 bits / stable sort by slot / k_qb_write   top-k of every slot
-//   k_qb_offsets / k_qb_gather / sort (slot * I + item, file row) / k_q_fold / k_qb_pred
-//   k_qb_reco_keys / sort 64 bits / stable sort by slot / k_qb_take              recommendations
 
 // slot of chunk row j: the last b with qo[b] <= j
 __device__ __forceinline__ int32_t qb_slot(const int64_t* __restrict__ qo, int32_t C, int64_t j) {
@@ -439,6 +186,9 @@ __device__ __forceinline__ int32_t qb_slot(const int64_t* __restrict__ qo, int32
     return lo;
 }
 
+// raw -> dense item through the fit's tables (dense_lookup beyond them); key of the norm's fold order: the slot, then the
+// trie order of the (q, item) tuple hash (usersWeights :474, N4).  tuple_trie_key(q, .) is a bijection of the item id, so two
+// rows of a slot have equal keys only when they repeat an item: after the sort, equal neighbours are the duplicates.
 __global__ void k_qb_keys(int64_t n, int32_t C, const int64_t* __restrict__ qo, const int32_t* __restrict__ users,
                           const int32_t* __restrict__ items, const int32_t* __restrict__ i_table, int32_t i_cells,
                           const uint32_t* __restrict__ ikeys, int32_t I, int32_t* __restrict__ slot, int32_t* __restrict__ di,
@@ -456,7 +206,9 @@ __global__ void k_qb_keys(int64_t n, int32_t C, const int64_t* __restrict__ qo, 
     val[j] = (uint32_t)j;
 }
 
-// k_q_prep of slot blockIdx.x: info[4 b] |= status bits, info[4 b + 1] = known items; scal[2 b] = mean, scal[2 b + 1] = norm
+// one workgroup per slot b: mean (left fold in the given order, usersAvg :113), deviations (computeNormalizeDeviation
+// :155-169), norm (sqrt of the left fold of dev^2 in tuple-hash order), preprocessed ratings, the bitmap of the known items.
+// info[4 b] |= status bits, info[4 b + 1] = known items; scal[2 b] = mean, scal[2 b + 1] = norm
 __global__ void k_qb_prep(const int64_t* __restrict__ qo, const double* __restrict__ r, const uint64_t* __restrict__ skey,
                           const uint32_t* __restrict__ sval, const int32_t* __restrict__ di, int64_t W, double* __restrict__ dev,
                           double* __restrict__ pre, unsigned long long* __restrict__ bits, long long* __restrict__ info,
@@ -516,6 +268,7 @@ __global__ void __launch_bounds__(ONE_BLOCK) k_qb_rank(int64_t W, const unsigned
     block_exclusive_scan(W, [&](int64_t w) { return (int64_t)__popcll(mine[w]); }, rank + (int64_t)blockIdx.x * (W + 1));
 }
 
+// the known items of every slot in dense order: preprocessed value, deviation, position in the given order
 __global__ void k_qb_scatter(int64_t n, const int64_t* __restrict__ qo, const int32_t* __restrict__ slot,
                              const int32_t* __restrict__ di, const double* __restrict__ pre, const double* __restrict__ dev,
                              int64_t W, const unsigned long long* __restrict__ bits, const int64_t* __restrict__ rank,
@@ -647,7 +400,8 @@ __global__ void __launch_bounds__(ONE_BLOCK) k_qb_offsets(int32_t take, const in
     if (threadIdx.x == 0) info[4 * b + 2] = total;
 }
 
-// k_q_gather over the chunk: one wave per (slot, neighbour); key = (slot * I + item, train file row)
+// the neighbours' ratings, one wave per (slot, neighbour); key = (slot * I + item, train file row): ratedI(i) :508-517 is in
+// file order
 __global__ void __launch_bounds__(TPB) k_qb_gather(int32_t C, int32_t take, int32_t I, const int32_t* __restrict__ nbr,
                                                    const double* __restrict__ nsim, const int64_t* __restrict__ off,
                                                    const int64_t* __restrict__ ebase, const int64_t* __restrict__ u_ptr,
@@ -671,7 +425,8 @@ __global__ void __launch_bounds__(TPB) k_qb_gather(int32_t C, int32_t take, int3
     }
 }
 
-// k_q_pred over [C][I]
+// predictor :568-585 over [C][I]; q's own row of the item comes last in aug with s(q, q) = 0 (q is not in its own
+// neighbour list)
 __global__ void k_qb_pred(int32_t C, int32_t I, int64_t W, const double* __restrict__ num, const double* __restrict__ den,
                           const unsigned long long* __restrict__ bits, const int64_t* __restrict__ rank,
                           const int64_t* __restrict__ qo, const double* __restrict__ dev_d, const double* __restrict__ scal,
@@ -693,7 +448,7 @@ __global__ void k_qb_pred(int32_t C, int32_t I, int64_t W, const double* __restr
     rated[g] = mine ? 1 : 0;
 }
 
-// k_q_pick with the slot of every requested row
+// requested raw items with their slot: the dense item's prediction; an item without a train rater has den = 0 (avg exactly)
 __global__ void k_qb_pick(int64_t m, const int32_t* __restrict__ items, const int32_t* __restrict__ slot,
                           const int32_t* __restrict__ i_table, int32_t i_cells, const uint32_t* __restrict__ ikeys, int32_t I,
                           const double* __restrict__ pred, const double* __restrict__ scal, double* __restrict__ out) {
@@ -836,7 +591,7 @@ void foldin_batch_predictions(const Train& tr, QueryBatchScratch& bs, SortWorksp
     KN_HIP(hipMemsetAsync(bs.num.p, 0, (size_t)cells * sizeof(double), st));  // +0.0
     KN_HIP(hipMemsetAsync(bs.den.p, 0, (size_t)cells * sizeof(double), st));
     if (E > 0) {
-        KN_REQUIRE(E < (int64_t)0xffffffffll, KNNCF_E_UNSUPPORTED, "query batch: more than 2^32-1 neighbour ratings in a chunk");
+        KN_REQUIRE(E < (int64_t)0xffffffffll, KNNCF_E_UNSUPPORTED, "query: more than 2^32-1 neighbour ratings in a chunk");
         bs.ebase.ensure((size_t)C + 1);
         bs.e_k64_a.ensure(E); bs.e_k64_b.ensure(E); bs.e_v32_a.ensure(E); bs.e_v32_b.ensure(E);
         bs.e_dev.ensure(E); bs.e_sim.ensure(E);

@@ -1,4 +1,4 @@
-"""Throughput of batched fold-in recommendations (Engine.recommend_for_batch, csrc/foldin.hip "batched") at the ml-25m shape,
+"""Throughput of batched fold-in recommendations (Engine.recommend_for_batch, csrc/foldin.hip) at the ml-25m shape,
 next to the host loop of single recommend_for calls.
 
 The workload is that of scripts/fold_in_latency.py: syn-25m, k = 300, the same `_queries` draw with seed 11,

@@ -1,7 +1,8 @@
 """Fold-in kNN queries (knncf_query_neighbors / _predict / _recommend, csrc/foldin.hip): the neighbourhood, predictions and
 recommendations of a user that is NOT in the fit, given its ratings, without a refit.  Every answer is compared bit for
 bit with the oracle on aug = train ++ the query rows (data.union(personal), recommend/Recommender.scala:68), on a fresh
-pipeline whose first call is the query user's neighbourhood."""
+pipeline whose first call is the query user's neighbourhood.  A single call is a chunk of one of the batched path
+(tests/test_gpu_fold_in_batch.py has the larger chunks), on the scratch that the batch calls and recommend_batch use too."""
 import importlib
 import os
 
@@ -200,6 +201,9 @@ def test_status_codes(kn, syn100k):
         with pytest.raises(kn.KnncfError) as ex:
             call()
         assert ex.value.status == status
+        # the single call's own text, not the batch's "query batch: query 0: ..."
+        text = lib.knncf_last_error(e._h).decode()
+        assert text.startswith("query:") and "query batch" not in text, text
     out = np.empty(4, dtype=np.float64)
     c = C.c_int32()
     ptr = lambda a, t: a.ctypes.data_as(t)
@@ -211,6 +215,11 @@ def test_status_codes(kn, syn100k):
     ids = np.empty(4, dtype=np.int32)
     assert lib.knncf_query_recommend(e._h, kn.PRED_BASELINE, 5000, ptr(its, i32p), ptr(rts, f64p), 4, 4, ptr(ids, i32p),
                                      ptr(out, f64p), C.byref(c)) == kn.E_UNSUPPORTED
+    # several refusals at once: the predictor is checked before the user, the null pointer before the predictor
+    assert lib.knncf_query_recommend(e._h, kn.PRED_BASELINE, int(train[0][0]), ptr(its, i32p), ptr(rts, f64p), 4, 4, ptr(ids, i32p),
+                                     ptr(out, f64p), C.byref(c)) == kn.E_UNSUPPORTED
+    assert lib.knncf_query_recommend(e._h, kn.PRED_BASELINE, 5000, None, ptr(rts, f64p), 4, 4, ptr(ids, i32p),
+                                     ptr(out, f64p), C.byref(c)) == kn.E_INVALID
     e.close()
     # similarityOne, sharded handles are refused; fewer than 5 train users
     e1 = kn.Engine(k=10, similarity=kn.SIM_ONE)
@@ -226,6 +235,76 @@ def test_status_codes(kn, syn100k):
         e4.recommend_for(5000, its, rts, 3)
     assert ex.value.status == kn.E_UNSUPPORTED
     e4.close()
+
+
+def test_counts_at_the_edges(kn, syn100k):
+    """n = 0 and an empty pred_items still run the query's prep and report its status; *count of the neighbours is
+    min(k, U) whatever cap is"""
+    import ctypes as C
+
+    d = syn100k
+    train = (d.train.users, d.train.items, d.train.ratings)
+    lib = kn.load_library()
+    e = kn.Engine(k=40)
+    e.fit(*train)
+    its = np.array([1, 2, 3, 50], dtype=np.int32)
+    rts = np.array([4.0, 3.0, 5.0, 1.0])
+    gi, gp = e.recommend_for(5000, its, rts, 0)
+    assert len(gi) == 0 and len(gp) == 0
+    assert len(e.predict_for(5000, its, rts, np.empty(0, dtype=np.int32))) == 0
+    for call in (lambda: e.recommend_for(5000, [1, 2, 1], [4.0, 3.0, 2.0], 0),
+                 lambda: e.predict_for(5000, [1, 2, 1], [4.0, 3.0, 2.0], np.empty(0, dtype=np.int32))):
+        with pytest.raises(kn.KnncfError) as ex:
+            call()
+        assert ex.value.status == kn.E_DUPLICATE
+    # recommend's *count at the C boundary: 0 for n = 0 (set from a sentinel)
+    i32p, f64p = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+    ptr = lambda a, t: a.ctypes.data_as(t)
+    c = C.c_int32(-7)
+    assert lib.knncf_query_recommend(e._h, kn.PRED_KNN, 5000, ptr(its, i32p), ptr(rts, f64p), 4, 0, None, None, C.byref(c)) == kn.OK
+    assert c.value == 0
+    c = C.c_int32(-7)
+    assert lib.knncf_query_neighbors(e._h, 5000, ptr(its, i32p), ptr(rts, f64p), 4, 0, None, None, C.byref(c)) == kn.OK
+    assert c.value == min(40, e.num_users) == 40
+    e.close()
+
+
+def test_single_calls_on_the_shared_scratch(kn, oracle, syn100k):
+    """The single calls, the batch calls and recommend_batch (n > 32: the segmented full order on lent buffers) use one
+    scratch set of the handle.  After a 40-query chunk (k_query_sim_dual) and a recommend_batch have sized and filled it,
+    the single calls still answer as the oracle does, and they leave nothing behind that changes recommend_batch."""
+    d = syn100k
+    train = (d.train.users, d.train.items, d.train.ratings)
+    all_items = np.unique(train[1])
+    rng = np.random.default_rng(29)
+    queries = []
+    for j in range(40):
+        m = int(rng.integers(1, 120))
+        its = rng.choice(np.arange(1, 1700, dtype=np.int32), m, replace=False)
+        queries.append((10_000 + j, its, rng.integers(1, 6, m).astype(np.float64)))
+    fitted = np.unique(train[0])[[3, 77, 400, 650, 900]]
+    long_row = train[0] == int(fitted[2])
+    singles = [(5001, train[1][long_row][:3], np.array([5.0, 1.0, 3.0])),
+               (5002, all_items[::20][:70], np.round(np.linspace(0.7, 4.9, 70), 1))]
+    assert len(singles[1][1]) >= 60
+
+    def same(a, b):
+        return all(np.array_equal(np.asarray(x).view(np.uint8), np.asarray(y).view(np.uint8)) for x, y in zip(a, b))
+
+    e = kn.Engine(k=40)
+    e.fit(*train)
+    _, st = e.recommend_for_batch(queries, 3)
+    assert st.tolist() == [kn.OK] * len(queries)
+    before = e.recommend_batch(kn.PRED_KNN, fitted, 40)
+    for q, it, rt in singles:
+        _check(kn, oracle, e, train, q, it, rt, oracle.SIM_COSINE, 40, np.concatenate([all_items, it, [UNKNOWN_ITEM]]))
+    after = e.recommend_batch(kn.PRED_KNN, fitted, 40)
+    e.close()
+    fresh = kn.Engine(k=40)
+    fresh.fit(*train)
+    alone = fresh.recommend_batch(kn.PRED_KNN, fitted, 40)
+    fresh.close()
+    assert same(before, after) and same(before, alone)
 
 
 def test_queries_leave_the_handle_untouched(kn, syn100k, tmp_path):

@@ -1,8 +1,10 @@
-"""Batched fold-in queries (knncf_query_neighbors_batch / _predict_batch / _recommend_batch, csrc/foldin.hip "batched"): B
+"""Batched fold-in queries (knncf_query_neighbors_batch / _predict_batch / _recommend_batch, csrc/foldin.hip): B
 independent queries per call, answered chunk by chunk.  Row b is compared bit for bit with the oracle on
 aug_b = train ++ the rows of query b (fresh pipeline, the query user's neighbourhood first), and with the single calls
-neighbors_for / predict_for / recommend_for on the same handle, across chunk boundaries and on both sides of every
-size-dependent switch of the path:
+neighbors_for / predict_for / recommend_for on the same handle.  The single calls run the same code as a chunk of one, so
+that second comparison is a chunk of C against chunks of one: it checks the slot indexing, the segmented sorts and
+k_query_sim_dual against k_query_sim, not one implementation against another.  It runs across chunk boundaries and on both
+sides of every size-dependent switch of the path:
   * chunk size C from the rule of include/knncf.h (64 at most; a small workspace_bytes makes it smaller),
   * C < 32 answerable queries: k_query_sim once per query (itself switching at 262 144 items), C >= 32: k_query_sim_dual,
   * fewer than 64 and exactly 64 live lanes in k_query_sim_dual.
@@ -66,7 +68,7 @@ def _same_pair(a, b, what):
 
 
 def _batch_vs_singles(kn, e, queries, pred_items, ns=(3,)):
-    """the three batch calls against the single calls of the same handle; returns the batch answers"""
+    """the three batch calls against the single calls (chunks of one) of the same handle; returns the batch answers"""
     nb, st = e.neighbors_for_batch(queries)
     assert st.tolist() == [kn.OK] * len(queries)
     pr, st = e.predict_for_batch(queries, [pred_items] * len(queries))
@@ -158,7 +160,7 @@ def test_batch_against_the_oracle(kn, oracle, syn100k, sim_name, k):
 
 
 def test_chunks_against_the_single_calls(kn, syn100k, latency_script):
-    """13 queries at 5 per chunk: chunks of 5, 5 and 3; the reversed batch gives the reversed rows"""
+    """13 queries at 5 per chunk: chunks of 5, 5 and 3 against 13 chunks of one; the reversed batch gives the reversed rows"""
     d = syn100k
     train = (d.train.users, d.train.items, d.train.ratings)
     n_users, n_items = len(np.unique(train[0])), len(np.unique(train[1]))
@@ -183,7 +185,7 @@ def test_chunks_against_the_single_calls(kn, syn100k, latency_script):
 @pytest.mark.parametrize("chunk,count", [(1, 2), (31, 31), (32, 32), (64, 70)])
 def test_switches_of_the_similarity_pass(kn, syn100k, latency_script, chunk, count):
     """chunks of 1 and 31 (k_query_sim per query), of 32 (the smallest k_query_sim_dual), of 64 + 6 (every lane live, then 6
-    through k_query_sim)"""
+    through k_query_sim), each against the single calls' chunks of one (k_query_sim)"""
     d = syn100k
     train = (d.train.users, d.train.items, d.train.ratings)
     n_users, n_items = len(np.unique(train[0])), len(np.unique(train[1]))
@@ -249,7 +251,7 @@ def test_per_query_statuses(kn, syn100k, latency_script):
         ((7003, np.arange(1, 65_539, dtype=np.int32), np.full(65_538, 3.0)), kn.E_UNSUPPORTED),
         ((7004, np.empty(0, dtype=np.int32), np.empty(0)), kn.E_INVALID),
     ]
-    # the single calls' statuses (the empty query is refused by the wrapper: asked at the C boundary)
+    # the single calls return the query's status as their own (the empty query is refused by the wrapper: asked at the C boundary)
     for (q, it, rt), status in bad[:-1]:
         with pytest.raises(kn.KnncfError) as ex:
             e.recommend_for(q, it, rt, 3)
