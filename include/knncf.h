@@ -266,6 +266,48 @@ int knncf_query_recommend_batch(knncf_handle* h, int predictor, const int32_t* u
                                 const double* ratings, int64_t n_queries, int32_t n, int32_t* out_items, double* out_preds,
                                 int32_t* counts, int32_t* statuses);
 
+/* ---- Update queries: a user that may be IN the fit, with additional ratings ------------------------------------------------
+ * The fold-in calls above refuse a user that occurs in train.  These answer for any `user`: (items[j], ratings[j]), j <
+ * n_ratings, are the rows the user has rated IN ADDITION to whatever train holds for it, and with
+ *     aug = train ++ [Rating(user, items[j], ratings[j]) for j in order]
+ * (data.union(personal), recommend/Recommender.scala:68 — nothing there requires the person to be new) every result equals,
+ * bit for bit, the reference's on aug with fresh closures whose first evaluation is `user`'s, WITHOUT a refit:
+ *   knncf_update_neighbors  getNeighbors(aug, k, sim)(user) :603-616.  (allUsers - u) :608 drops a user of the fit from its
+ *                           own candidates, so *count is min(k, U - 1) for a user of the fit and min(k, U) for any other;
+ *   knncf_update_predict    predictor(aug, weightedSumDeviation(aug, getSimilarity(aug, k, sim)))(user, pred_items[j]) :489-585;
+ *   knncf_update_recommend  recommendations(aug, that predictor)(user, n) :651-674: the user's own items, train and
+ *                           additional, are the rated ones.
+ * The argument lists, the batched forms (CSR offsets, per-query statuses, counts, untouched rows of failed queries, the
+ * handle-level return values), the chunk rule with its formula, the split at 32 answerable queries between the two similarity
+ * kernels and "the results do not depend on C" are exactly those of knncf_query_* / knncf_query_*_batch; a batch may mix users
+ * of the fit and others and may name the same user several times with different additional rows (each query has its own aug).
+ * For a user absent from train the answer is the knncf_query_* answer bit for bit: the same code runs.
+ * n_ratings == 0 (items / ratings may then be null) is valid for a user of the fit: the fresh-closure answer on train itself,
+ * whatever the handle has memoised for that user (after other calls knncf_neighbors(user) may own fewer of its pairs and
+ * differ in the last bits).  For a user absent from train it stays KNNCF_E_INVALID.
+ * Statuses: KNNCF_E_DUPLICATE if an additional item repeats another additional item or an item the user rated in train (the
+ * reference has no operation that replaces a rating); KNNCF_E_NONFINITE for a non-finite deviation; KNNCF_E_UNSUPPORTED for
+ * a negative mean of the combined rows or more than 65536 combined rows (the user's train rows plus the additional ones); and
+ * as for knncf_query_*: KNNCF_SIM_COSINE / KNNCF_SIM_JACCARD, KNNCF_PRED_KNN, single shard, >= 5 train users
+ * (KNNCF_E_UNSUPPORTED), KNNCF_E_STATE before a fit, KNNCF_E_INVALID for null pointers, negative sizes or bad CSR offsets.
+ * Read-only on the handle: the neighbour table, its build numbers and epoch and what knncf_neighbors_save writes stay as they
+ * were; the user's own stored list is neither read nor replaced, and the additional rows do not enter the fit. */
+int knncf_update_neighbors(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
+                           int32_t cap, int32_t* ids, double* sims, int32_t* count);
+int knncf_update_predict(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
+                         int64_t n_ratings, const int32_t* pred_items, int64_t m, double* out);
+int knncf_update_recommend(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
+                           int64_t n_ratings, int32_t n, int32_t* out_items, double* out_preds, int32_t* count);
+int knncf_update_neighbors_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                                 const double* ratings, int64_t n_queries, int32_t cap, int32_t* ids, double* sims, int32_t* counts,
+                                 int32_t* statuses);
+int knncf_update_predict_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                               const double* ratings, int64_t n_queries, const int64_t* pred_offsets, const int32_t* pred_items,
+                               double* out, int32_t* statuses);
+int knncf_update_recommend_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                                 const double* ratings, int64_t n_queries, int32_t n, int32_t* out_items, double* out_preds,
+                                 int32_t* counts, int32_t* statuses);
+
 /* ---- batch ---------------------------------------------------------------- */
 int knncf_predict_batch(knncf_handle* h, int predictor, const int32_t* users,
                         const int32_t* items, int64_t n, double* out);

@@ -87,6 +87,7 @@ struct knncf_handle {
     // host mirrors for scalar queries
     std::vector<uint32_t> h_ukeys, h_ikeys;
     std::vector<int32_t> h_uid;
+    std::vector<int64_t> h_uptr;  // row extents (update queries)
     knncf_timings tm{};
     std::vector<StageTimer> pending;
     std::vector<hipEvent_t> event_pool;
@@ -193,6 +194,15 @@ void load_host_ids(knncf_handle* h) {
 int32_t dense_user(knncf_handle* h, int32_t raw) {
     load_host_ids(h);
     return dense_lookup(h->h_ukeys.data(), h->tr.U, raw);
+}
+// ratings of dense user du in train
+int64_t train_row_length(knncf_handle* h, int32_t du) {
+    if (h->h_uptr.empty()) {
+        h->h_uptr.resize((size_t)h->tr.U + 1);
+        KN_HIP(hipMemcpyAsync(h->h_uptr.data(), h->tr.u_ptr.p, h->h_uptr.size() * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+        KN_HIP(hipStreamSynchronize(h->stream));
+    }
+    return h->h_uptr[du + 1] - h->h_uptr[du];
 }
 int32_t dense_item(knncf_handle* h, int32_t raw) {
     load_host_ids(h);
@@ -964,7 +974,7 @@ void do_fit_device(knncf_handle* h, const int32_t* d_users, const int32_t* d_ite
     h->b_ready = false;
     h->pt_ready = false;
     h->prow_ready = false;
-    h->h_ukeys.clear(); h->h_ikeys.clear(); h->h_uid.clear();
+    h->h_ukeys.clear(); h->h_ikeys.clear(); h->h_uid.clear(); h->h_uptr.clear();
     tr.n = n;
     tr.jaccard = h->cfg.similarity == KNNCF_SIM_JACCARD;
     {
@@ -1026,8 +1036,11 @@ void do_recommend(knncf_handle* h, int predictor, int32_t user, int32_t n, int32
 // Every answer is the reference's on aug = train ++ the query rows with fresh closures whose first evaluation is the
 // query user's.  Read-only on the handle: the neighbour table, its sequence numbers and epoch are not touched.
 // knncf_query_*_batch take B independent queries; a single call is a chunk of one.
+// Update queries (knncf_update_*) are the same calls for a user that may be in the fit: the rows given are then ADDITIONAL to
+// the user's train rows, which foldin.hip seeds on the device, and the user is left out of its own candidates.
 constexpr int64_t QUERY_MAX_RATINGS = 65536;
 enum QueryBatchMode { QB_NEIGHBORS, QB_PREDICT, QB_RECOMMEND };
+enum QueryFamily { QF_FOLD_IN, QF_UPDATE };
 
 // what the handle must be for any fold-in query, single or batched
 void require_query_support(knncf_handle* h, int predictor) {
@@ -1060,8 +1073,8 @@ struct QueryFailure {
 // The B validated queries in chunks of `chunk`: statuses[b] and, where it is KNNCF_OK, query b's answer.
 // mode QB_NEIGHBORS: width = cap, out_i / out_d = ids / sims [B * cap]; QB_RECOMMEND: width = n, out_i / out_d = items /
 // predictions [B * n]; QB_PREDICT: out_d [pred_offsets[B]]
-QueryFailure run_query_chunks(knncf_handle* h, QueryBatchMode mode, int64_t chunk, const int32_t* users, const int64_t* offsets,
-                              const int32_t* items, const double* ratings, int64_t B, int32_t width, const int64_t* pred_offsets,
+QueryFailure run_query_chunks(knncf_handle* h, QueryFamily family, QueryBatchMode mode, int64_t chunk, const int32_t* users,
+                              const int64_t* offsets, const int32_t* items, const double* ratings, int64_t B, int32_t width, const int64_t* pred_offsets,
                               const int32_t* pred_items, int32_t* out_i, double* out_d, int32_t* counts, int32_t* statuses) {
     h->prep.join_commit(h->stream);
     const Train& tr = h->tr;
@@ -1074,31 +1087,40 @@ QueryFailure run_query_chunks(knncf_handle* h, QueryBatchMode mode, int64_t chun
         if (counts) counts[b] = 0;
         if (first.query < 0 || b < first.query) first = {b, why};
     };
-    std::vector<int64_t> slot_query, qo, ebase;
-    std::vector<int32_t> s_users, s_items, h_idx, h_items, pick_slot, pick_items;
+    const bool update = family == QF_UPDATE;
+    std::vector<int64_t> slot_query, qo, ao, ebase;
+    std::vector<int32_t> s_users, s_items, s_self, h_idx, h_items, pick_slot, pick_items;
     std::vector<double> s_ratings, h_vals;
     std::vector<long long> info;
     for (int64_t c0 = 0; c0 < B; c0 += chunk) {
         const int64_t c1 = std::min(B, c0 + chunk);
         // the chunk's answerable queries, slot after slot
-        slot_query.clear(); s_users.clear(); s_items.clear(); s_ratings.clear();
+        slot_query.clear(); s_users.clear(); s_items.clear(); s_ratings.clear(); s_self.clear();
         qo.assign(1, 0);
+        ao.assign(1, 0);
         for (int64_t b = c0; b < c1; ++b) {
             const int64_t nb = offsets[b + 1] - offsets[b];
-            if (nb <= 0) { fail(b, KNNCF_E_INVALID, "null ratings or n_ratings <= 0"); continue; }
-            if (nb > QUERY_MAX_RATINGS) { fail(b, KNNCF_E_UNSUPPORTED, "more than 65536 ratings"); continue; }
-            if (dense_user(h, users[b]) >= 0) { fail(b, KNNCF_E_INVALID, "the user occurs in the training set"); continue; }
+            const int32_t du = dense_user(h, users[b]);
+            // rows of the user in aug: its train rows (update queries) and the given ones
+            const int64_t rows = nb + (update && du >= 0 ? train_row_length(h, du) : 0);
+            if (rows <= 0) { fail(b, KNNCF_E_INVALID, "null ratings or n_ratings <= 0"); continue; }
+            if (rows > QUERY_MAX_RATINGS) { fail(b, KNNCF_E_UNSUPPORTED, "more than 65536 ratings"); continue; }
+            if (!update && du >= 0) { fail(b, KNNCF_E_INVALID, "the user occurs in the training set"); continue; }
             slot_query.push_back(b);
             s_users.push_back(users[b]);
+            s_self.push_back(du);
             s_items.insert(s_items.end(), items + offsets[b], items + offsets[b + 1]);
             s_ratings.insert(s_ratings.end(), ratings + offsets[b], ratings + offsets[b + 1]);
-            qo.push_back((int64_t)s_items.size());
+            ao.push_back((int64_t)s_items.size());
+            qo.push_back(qo.back() + rows);
         }
         const int32_t C = (int32_t)slot_query.size();
         if (C == 0) continue;
         info.assign((size_t)4 * C, 0);
-        foldin_batch_neighbors(tr, bs, h->prep.sort, C, s_users.data(), qo.data(), s_items.data(), s_ratings.data(), h->cfg.k,
-                               info.data(), st);
+        foldin_batch_neighbors(tr, bs, h->prep.sort, C, s_users.data(), qo.data(), s_items.data(), s_ratings.data(),
+                               update ? s_self.data() : nullptr, update ? ao.data() : nullptr, h->cfg.k, info.data(), st);
+        // neighbours of slot s: (allUsers - u) :608 drops a user of the fit
+        auto take_of = [&](int32_t s) { return update && s_self[s] >= 0 ? std::min(take, tr.U - 1) : take; };
         int32_t good = 0;
         for (int32_t s = 0; s < C; ++s) {
             const uint64_t bits = (uint64_t)info[4 * s];
@@ -1121,11 +1143,11 @@ QueryFailure run_query_chunks(knncf_handle* h, QueryBatchMode mode, int64_t chun
             for (int32_t s = 0; s < C; ++s) {
                 const int64_t b = slot_query[s];
                 if (statuses[b] != KNNCF_OK) continue;
-                for (int32_t j = 0; j < c; ++j) {
+                for (int32_t j = 0; j < std::min(c, take_of(s)); ++j) {
                     out_i[b * width + j] = h->h_uid[h_idx[(size_t)s * take + j]];
                     out_d[b * width + j] = h_vals[(size_t)s * take + j];
                 }
-                counts[b] = take;
+                counts[b] = take_of(s);
             }
             continue;
         }
@@ -1186,8 +1208,8 @@ QueryFailure run_query_chunks(knncf_handle* h, QueryBatchMode mode, int64_t chun
     return first;
 }
 
-void do_query_batch(knncf_handle* h, QueryBatchMode mode, int predictor, const int32_t* users, const int64_t* offsets,
-                    const int32_t* items, const double* ratings, int64_t B, int32_t width, const int64_t* pred_offsets,
+void do_query_batch(knncf_handle* h, QueryFamily family, QueryBatchMode mode, int predictor, const int32_t* users,
+                    const int64_t* offsets, const int32_t* items, const double* ratings, int64_t B, int32_t width, const int64_t* pred_offsets,
                     const int32_t* pred_items, int32_t* out_i, double* out_d, int32_t* counts, int32_t* statuses) {
     require_fitted(h, false);
     KN_REQUIRE(B >= 0, KNNCF_E_INVALID, "query batch: n_queries < 0");
@@ -1207,23 +1229,28 @@ void do_query_batch(knncf_handle* h, QueryBatchMode mode, int predictor, const i
     } else {
         KN_REQUIRE(width == 0 || (out_i && out_d), KNNCF_E_INVALID, "query batch: null output");
     }
-    const QueryFailure f = run_query_chunks(h, mode, query_batch_chunk(h), users, offsets, items, ratings, B, width, pred_offsets,
-                                            pred_items, out_i, out_d, counts, statuses);
+    const QueryFailure f = run_query_chunks(h, family, mode, query_batch_chunk(h), users, offsets, items, ratings, B, width,
+                                            pred_offsets, pred_items, out_i, out_d, counts, statuses);
     if (f.query >= 0) h->err = "query batch: query " + std::to_string(f.query) + ": " + f.reason;
 }
 
 // One query as a chunk of one: the query's status is the call's.  The entry points check their own output arguments first;
-// *count (neighbours: min(k, U); recommendations: min(n, I - known items)) is written on success.
-void do_query_single(knncf_handle* h, QueryBatchMode mode, int predictor, int32_t user, const int32_t* items,
+// *count (neighbours: min(k, U), min(k, U - 1) for a user of the fit; recommendations: min(n, I - known items)) is written on
+// success.  An update query may come without rows (whether the user is in the fit is the chunk loop's to say).
+void do_query_single(knncf_handle* h, QueryFamily family, QueryBatchMode mode, int predictor, int32_t user, const int32_t* items,
                      const double* ratings, int64_t n_ratings, int32_t width, const int32_t* pred_items, int64_t m, int32_t* out_i,
                      double* out_d, int32_t* count) {
     require_fitted(h, false);
-    KN_REQUIRE(items && ratings && n_ratings > 0, KNNCF_E_INVALID, "query: null ratings or n_ratings <= 0");
+    if (family == QF_UPDATE) {
+        KN_REQUIRE(n_ratings >= 0 && (n_ratings == 0 || (items && ratings)), KNNCF_E_INVALID, "query: null ratings or n_ratings < 0");
+    } else {
+        KN_REQUIRE(items && ratings && n_ratings > 0, KNNCF_E_INVALID, "query: null ratings or n_ratings <= 0");
+    }
     require_query_support(h, predictor);
     const int64_t offsets[2] = {0, n_ratings}, pred_offsets[2] = {0, m};
     int32_t status = KNNCF_OK, c = 0;
-    const QueryFailure f = run_query_chunks(h, mode, 1, &user, offsets, items, ratings, 1, width, pred_offsets, pred_items, out_i,
-                                            out_d, &c, &status);
+    const QueryFailure f = run_query_chunks(h, family, mode, 1, &user, offsets, items, ratings, 1, width, pred_offsets, pred_items,
+                                            out_i, out_d, &c, &status);
     if (f.query >= 0) throw Error(status, std::string("query: ") + f.reason);
     if (count) *count = c;
 }
@@ -1804,7 +1831,7 @@ int knncf_query_neighbors(knncf_handle* h, int32_t user, const int32_t* items, c
                           int32_t cap, int32_t* ids, double* sims, int32_t* count) {
     return guarded(h, [&] {
         KN_REQUIRE(count && cap >= 0 && (cap == 0 || (ids && sims)), KNNCF_E_INVALID, "bad output arguments");
-        do_query_single(h, QB_NEIGHBORS, KNNCF_PRED_KNN, user, items, ratings, n_ratings, cap, nullptr, 0, ids, sims, count);
+        do_query_single(h, QF_FOLD_IN, QB_NEIGHBORS, KNNCF_PRED_KNN, user, items, ratings, n_ratings, cap, nullptr, 0, ids, sims, count);
     });
 }
 
@@ -1812,7 +1839,7 @@ int knncf_query_predict(knncf_handle* h, int predictor, int32_t user, const int3
                         int64_t n_ratings, const int32_t* pred_items, int64_t m, double* out) {
     return guarded(h, [&] {
         KN_REQUIRE(m >= 0 && (m == 0 || (pred_items && out)), KNNCF_E_INVALID, "bad prediction arguments");
-        do_query_single(h, QB_PREDICT, predictor, user, items, ratings, n_ratings, 0, pred_items, m, nullptr, out, nullptr);
+        do_query_single(h, QF_FOLD_IN, QB_PREDICT, predictor, user, items, ratings, n_ratings, 0, pred_items, m, nullptr, out, nullptr);
     });
 }
 
@@ -1820,7 +1847,7 @@ int knncf_query_neighbors_batch(knncf_handle* h, const int32_t* users, const int
                                 const double* ratings, int64_t n_queries, int32_t cap, int32_t* ids, double* sims, int32_t* counts,
                                 int32_t* statuses) {
     return guarded(h, [&] {
-        do_query_batch(h, QB_NEIGHBORS, KNNCF_PRED_KNN, users, offsets, items, ratings, n_queries, cap, nullptr, nullptr, ids, sims,
+        do_query_batch(h, QF_FOLD_IN, QB_NEIGHBORS, KNNCF_PRED_KNN, users, offsets, items, ratings, n_queries, cap, nullptr, nullptr, ids, sims,
                        counts, statuses);
     });
 }
@@ -1829,7 +1856,7 @@ int knncf_query_predict_batch(knncf_handle* h, int predictor, const int32_t* use
                               const double* ratings, int64_t n_queries, const int64_t* pred_offsets, const int32_t* pred_items,
                               double* out, int32_t* statuses) {
     return guarded(h, [&] {
-        do_query_batch(h, QB_PREDICT, predictor, users, offsets, items, ratings, n_queries, 0, pred_offsets, pred_items, nullptr, out,
+        do_query_batch(h, QF_FOLD_IN, QB_PREDICT, predictor, users, offsets, items, ratings, n_queries, 0, pred_offsets, pred_items, nullptr, out,
                        nullptr, statuses);
     });
 }
@@ -1838,7 +1865,7 @@ int knncf_query_recommend_batch(knncf_handle* h, int predictor, const int32_t* u
                                 const double* ratings, int64_t n_queries, int32_t n, int32_t* out_items, double* out_preds,
                                 int32_t* counts, int32_t* statuses) {
     return guarded(h, [&] {
-        do_query_batch(h, QB_RECOMMEND, predictor, users, offsets, items, ratings, n_queries, n, nullptr, nullptr, out_items,
+        do_query_batch(h, QF_FOLD_IN, QB_RECOMMEND, predictor, users, offsets, items, ratings, n_queries, n, nullptr, nullptr, out_items,
                        out_preds, counts, statuses);
     });
 }
@@ -1848,7 +1875,60 @@ int knncf_query_recommend(knncf_handle* h, int predictor, int32_t user, const in
     return guarded(h, [&] {
         KN_REQUIRE(count && n >= 0 && (n == 0 || (out_items && out_preds)), KNNCF_E_INVALID, "bad arguments");
         *count = 0;
-        do_query_single(h, QB_RECOMMEND, predictor, user, items, ratings, n_ratings, n, nullptr, 0, out_items, out_preds, count);
+        do_query_single(h, QF_FOLD_IN, QB_RECOMMEND, predictor, user, items, ratings, n_ratings, n, nullptr, 0, out_items, out_preds, count);
+    });
+}
+
+// update queries: the same calls for a user that may be in the fit (the rows are additional to its train rows)
+int knncf_update_neighbors(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
+                           int32_t cap, int32_t* ids, double* sims, int32_t* count) {
+    return guarded(h, [&] {
+        KN_REQUIRE(count && cap >= 0 && (cap == 0 || (ids && sims)), KNNCF_E_INVALID, "bad output arguments");
+        do_query_single(h, QF_UPDATE, QB_NEIGHBORS, KNNCF_PRED_KNN, user, items, ratings, n_ratings, cap, nullptr, 0, ids, sims, count);
+    });
+}
+
+int knncf_update_predict(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
+                         int64_t n_ratings, const int32_t* pred_items, int64_t m, double* out) {
+    return guarded(h, [&] {
+        KN_REQUIRE(m >= 0 && (m == 0 || (pred_items && out)), KNNCF_E_INVALID, "bad prediction arguments");
+        do_query_single(h, QF_UPDATE, QB_PREDICT, predictor, user, items, ratings, n_ratings, 0, pred_items, m, nullptr, out, nullptr);
+    });
+}
+
+int knncf_update_neighbors_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                                 const double* ratings, int64_t n_queries, int32_t cap, int32_t* ids, double* sims, int32_t* counts,
+                                 int32_t* statuses) {
+    return guarded(h, [&] {
+        do_query_batch(h, QF_UPDATE, QB_NEIGHBORS, KNNCF_PRED_KNN, users, offsets, items, ratings, n_queries, cap, nullptr, nullptr, ids, sims,
+                       counts, statuses);
+    });
+}
+
+int knncf_update_predict_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                               const double* ratings, int64_t n_queries, const int64_t* pred_offsets, const int32_t* pred_items,
+                               double* out, int32_t* statuses) {
+    return guarded(h, [&] {
+        do_query_batch(h, QF_UPDATE, QB_PREDICT, predictor, users, offsets, items, ratings, n_queries, 0, pred_offsets, pred_items, nullptr, out,
+                       nullptr, statuses);
+    });
+}
+
+int knncf_update_recommend_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                                 const double* ratings, int64_t n_queries, int32_t n, int32_t* out_items, double* out_preds,
+                                 int32_t* counts, int32_t* statuses) {
+    return guarded(h, [&] {
+        do_query_batch(h, QF_UPDATE, QB_RECOMMEND, predictor, users, offsets, items, ratings, n_queries, n, nullptr, nullptr, out_items,
+                       out_preds, counts, statuses);
+    });
+}
+
+int knncf_update_recommend(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
+                           int64_t n_ratings, int32_t n, int32_t* out_items, double* out_preds, int32_t* count) {
+    return guarded(h, [&] {
+        KN_REQUIRE(count && n >= 0 && (n == 0 || (out_items && out_preds)), KNNCF_E_INVALID, "bad arguments");
+        *count = 0;
+        do_query_single(h, QF_UPDATE, QB_RECOMMEND, predictor, user, items, ratings, n_ratings, n, nullptr, 0, out_items, out_preds, count);
     });
 }
 

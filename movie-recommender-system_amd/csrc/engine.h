@@ -309,6 +309,10 @@ struct QueryBatchScratch {
     DArr<int64_t> qo;                  // [C + 1] first row of each slot
     DArr<int32_t> items, slot, di, given_d;  // [n] rows of the chunk, slot after slot
     DArr<double> ratings, dev, pre, pre_d, dev_d;
+    DArr<int32_t> self;                // [C] update queries: dense index of the slot's user in the fit, -1 when it is not there
+    DArr<int64_t> ao;                  // [C + 1] update queries: first additional row of each slot
+    DArr<int32_t> add_items;           // [ao[C]] the additional rows as uploaded (items / ratings hold train rows + these)
+    DArr<double> add_ratings;
     DArr<uint64_t> bits;               // [C][ceil(I / 64)]
     DArr<int64_t> rank;                // [C][ceil(I / 64) + 1]
     DArr<uint32_t> tbits, trank;       // [2 ceil(I / 64)][64] the bitmaps and prefixes side by side (k_qb_transpose)
@@ -331,9 +335,13 @@ struct QueryBatchScratch {
 };
 // prep + similarities + top-k (bs.nbr_idx / nbr_sim [C][min(k, U)]) of C >= 1 non-empty queries; h_info[4 b ..] = status
 // bits, known items, neighbour ratings (0 for a slot whose status is set) of slot b.  Synchronises the stream once.
+// h_self == nullptr (fold-in queries): h_items / h_ratings are the chunk's rows [h_qo[C]].  Otherwise (update queries) h_self[b]
+// is the dense index of slot b's user in the fit or -1, h_items / h_ratings are the additional rows [h_ao[C]] only, and slot b
+// has h_qo[b + 1] - h_qo[b] = (train rows of h_self[b]) + (h_ao[b + 1] - h_ao[b]) rows: the train rows are seeded on the
+// device, a fitted user is left out of its own candidates and gets min(k, U - 1) neighbours.
 void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, const int32_t* h_users,
-                            const int64_t* h_qo, const int32_t* h_items, const double* h_ratings, int32_t k, long long* h_info,
-                            hipStream_t st);
+                            const int64_t* h_qo, const int32_t* h_items, const double* h_ratings, const int32_t* h_self,
+                            const int64_t* h_ao, int32_t k, long long* h_info, hipStream_t st);
 // bs.pred / bs.rated [C][I]; h_ebase[C + 1] = exclusive prefix of the slots' neighbour ratings
 void foldin_batch_predictions(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, int32_t take,
                               const int64_t* h_ebase, hipStream_t st);

@@ -10,12 +10,15 @@
 // launch (or one sort) over the chunk; a single call is a chunk of one.  Rows of the chunk are concatenated in slot order:
 // slot b owns rows [qo[b], qo[b + 1]).  Nothing of one slot enters another, and each slot's arithmetic and its order do not
 // depend on C, so a query's answer is the same bit for bit in whatever chunk it travels.
+//   k_qb_seed_keys / sort / k_qb_seed   (update queries only) the rows of a slot whose user is in the fit: the user's train
+//                                       rows in file order, then the additional rows
 //   k_qb_keys / sort (slot, trie key) / k_qb_prep / k_qb_rank / k_qb_scatter   query prep, one workgroup per slot: dense
 //                                       items, mean, deviations, hash-ordered norm, preprocessed values, a dense-item
 //                                       bitmap with rank prefixes
 //   k_qb_transpose + k_query_sim_dual   (C >= QB_DUAL_MIN) every train row read once for the whole chunk, lane b = slot b
 //   k_query_sim per slot                (C <  QB_DUAL_MIN) one exact fp64 similarity per train user (one streaming pass of s_col)
-//   fallback keys over [C][U] / sort 64 bits / stable sort by slot / k_qb_write   top-k (similarity desc, dense user asc)
+//   fallback keys over [C][U] / sort 64 bits / stable sort by slot / k_qb_write   top-k (similarity desc, dense user asc);
+//                                       k_qb_mask_self keys a fitted user's own cell behind every other: (allUsers - u) :608
 //   k_qb_offsets / k_qb_gather / sort (slot * I + item, file row) / k_q_fold      the neighbours' ratings grouped by (item,
 //                                       file row): the left folds of weightedSumDeviation :504-548
 //   k_qb_pred                           predictor :568-585 for every (slot, dense item)
@@ -184,6 +187,54 @@ __device__ __forceinline__ int32_t qb_slot(const int64_t* __restrict__ qo, int32
         else hi = mid - 1;
     }
     return lo;
+}
+
+// ---- update queries (knncf_update_*): the query user may be in the fit.  self[b] = its dense index, -1 when it is not.
+// neighbours a slot returns: (allUsers - u) :608 has U - 1 users for a user of the fit.  self == nullptr: fold-in queries.
+__device__ __forceinline__ int32_t qb_take(const int32_t* __restrict__ self, int32_t b, int32_t take, int32_t U) {
+    return (self && self[b] >= 0) ? min(take, U - 1) : take;
+}
+
+// Chunk row j of slot b is row r = j - qo[b] of the slot: r < (train row length of self[b]) is the user's train entry at
+// position u_ptr[self] + r, the others are the additional rows in their given order.  The key orders a slot's rows as aug
+// holds them: train rows by file row (s_t), then the additional ones.
+__global__ void k_qb_seed_keys(int64_t n, int32_t C, const int64_t* __restrict__ qo, const int32_t* __restrict__ self,
+                               const int64_t* __restrict__ u_ptr, const uint32_t* __restrict__ s_t, uint64_t* __restrict__ key,
+                               uint32_t* __restrict__ val) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const int32_t b = qb_slot(qo, C, j), sd = self[b];
+    const int64_t r = j - qo[b], p0 = sd >= 0 ? u_ptr[sd] : 0, tl = sd >= 0 ? u_ptr[sd + 1] - p0 : 0;
+    const uint64_t in_slot = r < tl ? (uint64_t)s_t[p0 + r] : ((1ull << 32) | (uint64_t)(r - tl));
+    key[j] = ((uint64_t)(uint32_t)b << 33) | in_slot;
+    val[j] = (uint32_t)j;
+}
+
+// items / ratings of the chunk in that order: raw item iid[s_col], rating s_rating of a train entry; the additional rows
+// (add_* rows [ao[b], ao[b + 1]) of slot b) behind them
+__global__ void k_qb_seed(int64_t n, int32_t C, const int64_t* __restrict__ qo, const int64_t* __restrict__ ao,
+                          const int32_t* __restrict__ self, const int64_t* __restrict__ u_ptr, const int32_t* __restrict__ s_col,
+                          const double* __restrict__ s_rating, const int32_t* __restrict__ iid, const int32_t* __restrict__ add_items,
+                          const double* __restrict__ add_ratings, const uint32_t* __restrict__ sval, int32_t* __restrict__ items,
+                          double* __restrict__ ratings) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const int32_t b = qb_slot(qo, C, j), sd = self[b];
+    const int64_t r = (int64_t)sval[j] - qo[b], p0 = sd >= 0 ? u_ptr[sd] : 0, tl = sd >= 0 ? u_ptr[sd + 1] - p0 : 0;
+    if (r < tl) {
+        items[j] = iid[s_col[p0 + r]];
+        ratings[j] = s_rating[p0 + r];
+    } else {
+        items[j] = add_items[ao[b] + (r - tl)];
+        ratings[j] = add_ratings[ao[b] + (r - tl)];
+    }
+}
+
+// the user's own cell of [C][U] gets the last key of all (the bit pattern no similarity has), so it sorts behind every other
+// user of its slot whatever s(u, u) is, and the first min(k, U - 1) of the slot are getNeighbors' (allUsers - u) :608
+__global__ void k_qb_mask_self(int32_t C, int32_t U, const int32_t* __restrict__ self, uint64_t* __restrict__ key) {
+    const int32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < C && self[b] >= 0) key[(int64_t)b * U + self[b]] = ~0ull;
 }
 
 // raw -> dense item through the fit's tables (dense_lookup beyond them); key of the norm's fold order: the slot, then the
@@ -376,27 +427,30 @@ __global__ void k_qb_slot_keys(int64_t n, uint32_t stride, const uint32_t* __res
     if (x < n) key[x] = val[x] / stride;
 }
 
-// the first `take` of slot b's sorted list -> nbr_idx / nbr_sim [b][take]
-__global__ void k_qb_write(int32_t C, int32_t take, int32_t U, const uint32_t* __restrict__ sorted_val,
-                           const double* __restrict__ sim, int32_t* __restrict__ nbr_idx, double* __restrict__ nbr_sim) {
+// the first qb_take of slot b's sorted list -> nbr_idx / nbr_sim [b][take]
+__global__ void k_qb_write(int32_t C, int32_t take, int32_t U, const int32_t* __restrict__ self,
+                           const uint32_t* __restrict__ sorted_val, const double* __restrict__ sim, int32_t* __restrict__ nbr_idx,
+                           double* __restrict__ nbr_sim) {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= (int64_t)C * take) return;
     const int32_t b = (int32_t)(g / take), j = (int32_t)(g - (int64_t)b * take);
+    if (j >= qb_take(self, b, take, U)) return;
     const uint32_t x = sorted_val[(int64_t)b * U + j];
     nbr_idx[g] = (int32_t)(x - (uint32_t)b * (uint32_t)U);
     nbr_sim[g] = sim[x];
 }
 
 // off[b][0 .. take]: first entry of each neighbour's ratings inside slot b's part of the gathered list; info[4 b + 2] = their
-// number.  A slot whose status is already set takes no part in the prediction pass (0 entries).
-__global__ void __launch_bounds__(ONE_BLOCK) k_qb_offsets(int32_t take, const int32_t* __restrict__ nbr,
-                                                          const int64_t* __restrict__ u_ptr, int64_t* __restrict__ off,
-                                                          long long* __restrict__ info) {
+// number.  A slot whose status is already set takes no part in the prediction pass (0 entries), nor do the cells of a slot
+// beyond its qb_take.
+__global__ void __launch_bounds__(ONE_BLOCK) k_qb_offsets(int32_t take, int32_t U, const int32_t* __restrict__ self,
+                                                          const int32_t* __restrict__ nbr, const int64_t* __restrict__ u_ptr,
+                                                          int64_t* __restrict__ off, long long* __restrict__ info) {
     const int32_t b = blockIdx.x;
     const int32_t* mine = nbr + (int64_t)b * take;
-    const bool failed = info[4 * b] != 0;
+    const int64_t live = info[4 * b] != 0 ? 0 : qb_take(self, b, take, U);
     const int64_t total = block_exclusive_scan(
-        take, [&](int64_t j) { return failed ? (int64_t)0 : u_ptr[mine[j] + 1] - u_ptr[mine[j]]; }, off + (int64_t)b * (take + 1));
+        take, [&](int64_t j) { return j >= live ? (int64_t)0 : u_ptr[mine[j] + 1] - u_ptr[mine[j]]; }, off + (int64_t)b * (take + 1));
     if (threadIdx.x == 0) info[4 * b + 2] = total;
 }
 
@@ -412,7 +466,7 @@ __global__ void __launch_bounds__(TPB) k_qb_gather(int32_t C, int32_t take, int3
     if (g >= (int64_t)C * take) return;
     const int32_t sb = (int32_t)(g / take), j = (int32_t)(g - (int64_t)sb * take);
     const int64_t lo = off[(int64_t)sb * (take + 1) + j], hi = off[(int64_t)sb * (take + 1) + j + 1];
-    if (hi == lo) return;  // (a failed slot, or a neighbour without ratings)
+    if (hi == lo) return;  // (a failed slot, a cell beyond the slot's qb_take, or a neighbour without ratings)
     const int32_t v = nbr[g];
     const int64_t b = u_ptr[v], e = u_ptr[v + 1], o = ebase[sb] + lo;
     const double sj = nsim[g];
@@ -507,8 +561,8 @@ static const uint32_t* qb_segmented_sort(QueryBatchScratch& bs, SortWorkspace& w
 }
 
 void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, const int32_t* h_users,
-                            const int64_t* h_qo, const int32_t* h_items, const double* h_ratings, int32_t k, long long* h_info,
-                            hipStream_t st) {
+                            const int64_t* h_qo, const int32_t* h_items, const double* h_ratings, const int32_t* h_self,
+                            const int64_t* h_ao, int32_t k, long long* h_info, hipStream_t st) {
     const int32_t U = tr.U, I = tr.I;
     const int64_t W = ceil_div(I, 64), n = h_qo[C];
     const int64_t cells = (int64_t)C * std::max(U, I);
@@ -528,8 +582,28 @@ void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspac
     // one upload of the chunk
     KN_HIP(hipMemcpyAsync(bs.users.p, h_users, (size_t)C * sizeof(int32_t), hipMemcpyHostToDevice, st));
     KN_HIP(hipMemcpyAsync(bs.qo.p, h_qo, ((size_t)C + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    KN_HIP(hipMemcpyAsync(bs.items.p, h_items, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    KN_HIP(hipMemcpyAsync(bs.ratings.p, h_ratings, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    const int32_t* self = nullptr;
+    if (!h_self) {
+        KN_HIP(hipMemcpyAsync(bs.items.p, h_items, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        KN_HIP(hipMemcpyAsync(bs.ratings.p, h_ratings, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    } else {
+        // update queries: only the additional rows travel; the train rows of the fitted users are seeded on the device
+        const int64_t na = h_ao[C];
+        bs.self.ensure(C); bs.ao.ensure((size_t)C + 1);
+        bs.add_items.ensure(std::max<int64_t>(na, 1)); bs.add_ratings.ensure(std::max<int64_t>(na, 1));
+        KN_HIP(hipMemcpyAsync(bs.self.p, h_self, (size_t)C * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        KN_HIP(hipMemcpyAsync(bs.ao.p, h_ao, ((size_t)C + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        if (na > 0) {
+            KN_HIP(hipMemcpyAsync(bs.add_items.p, h_items, (size_t)na * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            KN_HIP(hipMemcpyAsync(bs.add_ratings.p, h_ratings, (size_t)na * sizeof(double), hipMemcpyHostToDevice, st));
+        }
+        self = bs.self.p;
+        k_qb_seed_keys<<<(unsigned)ceil_div(n, TPB), TPB, 0, st>>>(n, C, bs.qo.p, self, tr.u_ptr.p, tr.s_t.p, bs.k64_a.p, bs.v32_a.p);
+        sort_pairs_u64_u32(ws, bs.k64_a.p, bs.k64_b.p, bs.v32_a.p, bs.v32_b.p, (size_t)n, 33 + (C > 1 ? bits_for((uint64_t)(C - 1)) : 0), st);
+        k_qb_seed<<<(unsigned)ceil_div(n, TPB), TPB, 0, st>>>(n, C, bs.qo.p, bs.ao.p, self, tr.u_ptr.p, tr.s_col.p, tr.s_rating.p,
+                                                              tr.iid.p, bs.add_items.p, bs.add_ratings.p, bs.v32_b.p, bs.items.p,
+                                                              bs.ratings.p);
+    }
     KN_HIP(hipMemsetAsync(bs.bits.p, 0, (size_t)C * W * sizeof(uint64_t), st));
     KN_HIP(hipMemsetAsync(bs.info.p, 0, (size_t)4 * C * sizeof(int64_t), st));
     unsigned long long* bits = (unsigned long long*)bs.bits.p;
@@ -571,12 +645,13 @@ void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspac
     KN_HIP(hipGetLastError());
     // top-k of every slot: (similarity desc, dense user asc)
     launch_fallback_keys((int32_t)((int64_t)C * U), bs.sim.p, bs.k64_a.p, bs.v32_a.p, st);
+    if (self) k_qb_mask_self<<<(unsigned)ceil_div(C, 64), 64, 0, st>>>(C, U, self, bs.k64_a.p);
     const uint32_t* order = qb_segmented_sort(bs, ws, C, U, st);
     if (take > 0) {
-        k_qb_write<<<(unsigned)ceil_div((int64_t)C * take, TPB), TPB, 0, st>>>(C, take, U, order, bs.sim.p, bs.nbr_idx.p,
+        k_qb_write<<<(unsigned)ceil_div((int64_t)C * take, TPB), TPB, 0, st>>>(C, take, U, self, order, bs.sim.p, bs.nbr_idx.p,
                                                                                bs.nbr_sim.p);
     }
-    k_qb_offsets<<<C, ONE_BLOCK, 0, st>>>(take, bs.nbr_idx.p, tr.u_ptr.p, bs.off.p, info);
+    k_qb_offsets<<<C, ONE_BLOCK, 0, st>>>(take, U, self, bs.nbr_idx.p, tr.u_ptr.p, bs.off.p, info);
     KN_HIP(hipGetLastError());
     // the chunk's one round trip: statuses, known items and the sizes of the prediction pass
     KN_HIP(hipMemcpyAsync(h_info, bs.info.p, (size_t)4 * C * sizeof(int64_t), hipMemcpyDeviceToHost, st));

@@ -118,7 +118,9 @@ EXPORTS = [
     "knncf_user_avg", "knncf_item_avg", "knncf_item_avg_dev", "knncf_item_avg_dev_rdd", "knncf_similarity",
     "knncf_knn_similarity", "knncf_neighbors", "knncf_neighbors_batch", "knncf_predict", "knncf_recommend", "knncf_recommend_batch",
     "knncf_query_neighbors", "knncf_query_predict", "knncf_query_recommend",
-    "knncf_query_neighbors_batch", "knncf_query_predict_batch", "knncf_query_recommend_batch", "knncf_predict_batch",
+    "knncf_query_neighbors_batch", "knncf_query_predict_batch", "knncf_query_recommend_batch",
+    "knncf_update_neighbors", "knncf_update_predict", "knncf_update_recommend",
+    "knncf_update_neighbors_batch", "knncf_update_predict_batch", "knncf_update_recommend_batch", "knncf_predict_batch",
     "knncf_predict_batch_device", "knncf_mae", "knncf_mae_device", "knncf_mae_sweep", "knncf_mae_sweep_device", "knncf_shard_view_get",
     "knncf_shard_commit", "knncf_get_timings", "knncf_reset_timings", "knncf_reset_neighbors",
     "knncf_set_k", "knncf_load_file", "knncf_load_file_cached", "knncf_free_ratings", "knncf_load_personal", "knncf_free_personal", "knncf_neighbors_save", "knncf_neighbors_load",
@@ -198,13 +200,15 @@ def load_library():
     L.knncf_predict.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int32, _f64p]
     L.knncf_recommend.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int32, _i32p, _f64p, C.POINTER(C.c_int32)]
     L.knncf_recommend_batch.argtypes = [C.c_void_p, C.c_int, _i32p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p]
-    L.knncf_query_neighbors.argtypes = [C.c_void_p, C.c_int32, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p]
-    L.knncf_query_predict.argtypes = [C.c_void_p, C.c_int, C.c_int32, _i32p, _f64p, C.c_int64, _i32p, C.c_int64, _f64p]
-    L.knncf_query_recommend.argtypes = [C.c_void_p, C.c_int, C.c_int32, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p]
-    L.knncf_query_neighbors_batch.argtypes = [C.c_void_p, _i32p, _i64p, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p, _i32p]
-    L.knncf_query_predict_batch.argtypes = [C.c_void_p, C.c_int, _i32p, _i64p, _i32p, _f64p, C.c_int64, _i64p, _i32p, _f64p, _i32p]
-    L.knncf_query_recommend_batch.argtypes = [C.c_void_p, C.c_int, _i32p, _i64p, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p,
-                                              _i32p, _i32p]
+    for fam in ("query", "update"):  # fold-in queries and update queries share their argument lists
+        f = lambda name: getattr(L, f"knncf_{fam}_{name}")
+        f("neighbors").argtypes = [C.c_void_p, C.c_int32, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p]
+        f("predict").argtypes = [C.c_void_p, C.c_int, C.c_int32, _i32p, _f64p, C.c_int64, _i32p, C.c_int64, _f64p]
+        f("recommend").argtypes = [C.c_void_p, C.c_int, C.c_int32, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p]
+        f("neighbors_batch").argtypes = [C.c_void_p, _i32p, _i64p, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p, _i32p]
+        f("predict_batch").argtypes = [C.c_void_p, C.c_int, _i32p, _i64p, _i32p, _f64p, C.c_int64, _i64p, _i32p, _f64p, _i32p]
+        f("recommend_batch").argtypes = [C.c_void_p, C.c_int, _i32p, _i64p, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p,
+                                         _i32p, _i32p]
     L.knncf_predict_batch.argtypes = [C.c_void_p, C.c_int, _i32p, _i32p, C.c_int64, _f64p]
     L.knncf_predict_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.knncf_mae.argtypes = [C.c_void_p, C.c_int, _i32p, _i32p, _f64p, C.c_int64, _f64p]
@@ -419,10 +423,11 @@ class Engine:
                                                     p(preds.reshape(-1), _f64p), p(counts, _i32p)))
         return items, preds, counts
 
-    # ---- fold-in queries: a user outside the fit (knncf_query_*) ---------------------------
+    # ---- fold-in queries: a user outside the fit (knncf_query_*), and update queries: any user, the rows being additional
+    # to its train rows (knncf_update_*).  The two families share their argument lists; `fam` picks the entry points. ----
     @staticmethod
-    def _query_rows(user, items, ratings):
-        """validated (user, items, ratings) of a fold-in query: ValueError before any C call"""
+    def _query_rows(user, items, ratings, allow_empty=False):
+        """validated (user, items, ratings) of a query: ValueError before any C call"""
         if isinstance(user, (bool, np.bool_)) or not isinstance(user, (int, np.integer)) or not -2**31 <= int(user) < 2**31:
             raise ValueError("user must be a 32-bit integer id")
         it = np.asarray(items)
@@ -430,16 +435,21 @@ class Engine:
         if it.ndim != 1 or rt.ndim != 1 or len(it) != len(rt):
             raise ValueError("items and ratings must be 1-D and of the same length")
         if len(it) == 0:
-            raise ValueError("a query needs at least one rating")
+            if not allow_empty:
+                raise ValueError("a query needs at least one rating")
+            return int(user), np.empty(0, dtype=np.int32), np.empty(0, dtype=np.float64)
         if it.dtype.kind not in "iu" or (len(it) and (it.min() < -2**31 or it.max() >= 2**31)):
             raise ValueError("items must be 32-bit integer ids")
         if rt.dtype.kind not in "iuf":
             raise ValueError("ratings must be numbers")
         return int(user), _i32(it), _f64(rt)
 
-    def neighbors_for(self, user, items, ratings, cap=None):
-        """getNeighbors(train ++ user's ratings, k, sim)(user) for a user outside the fit: (ids, sims)"""
-        q, it, rt = self._query_rows(user, items, ratings)
+    @staticmethod
+    def _ptr(a, t):
+        return a.ctypes.data_as(t) if len(a) else C.cast(None, t)
+
+    def _neighbors_q(self, fam, user, items, ratings, cap):
+        q, it, rt = self._query_rows(user, items, ratings, allow_empty=fam == "update")
         if cap is None:
             cap = max(1, self.k)
         if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or cap < 0:
@@ -448,41 +458,68 @@ class Engine:
         ids = np.empty(max(1, cap), dtype=np.int32)
         sims = np.empty(max(1, cap), dtype=np.float64)
         c = C.c_int32()
-        self._check(self._lib.knncf_query_neighbors(self._h, q, it.ctypes.data_as(_i32p), rt.ctypes.data_as(_f64p), len(it), cap,
-                                                    ids.ctypes.data_as(_i32p), sims.ctypes.data_as(_f64p), C.byref(c)))
+        p = self._ptr
+        self._check(getattr(self._lib, f"knncf_{fam}_neighbors")(self._h, q, p(it, _i32p), p(rt, _f64p), len(it), cap,
+                                                                 ids.ctypes.data_as(_i32p), sims.ctypes.data_as(_f64p), C.byref(c)))
         m = min(c.value, cap)
         return ids[:m].copy(), sims[:m].copy()
 
-    def predict_for(self, user, items, ratings, pred_items):
-        """kNN predictions (PRED_KNN) of a user outside the fit, given its ratings, for every id of pred_items"""
-        q, it, rt = self._query_rows(user, items, ratings)
+    def _predict_q(self, fam, user, items, ratings, pred_items):
+        q, it, rt = self._query_rows(user, items, ratings, allow_empty=fam == "update")
         pi = np.asarray(pred_items)
         if pi.ndim != 1 or (len(pi) and pi.dtype.kind not in "iu"):
             raise ValueError("pred_items must be a 1-D array of integer ids")
         pi = _i32(pi)
         out = np.empty(max(1, len(pi)), dtype=np.float64)
-        self._check(self._lib.knncf_query_predict(self._h, PRED_KNN, q, it.ctypes.data_as(_i32p), rt.ctypes.data_as(_f64p), len(it),
-                                                  pi.ctypes.data_as(_i32p), len(pi), out.ctypes.data_as(_f64p)))
+        p = self._ptr
+        self._check(getattr(self._lib, f"knncf_{fam}_predict")(self._h, PRED_KNN, q, p(it, _i32p), p(rt, _f64p), len(it),
+                                                               pi.ctypes.data_as(_i32p), len(pi), out.ctypes.data_as(_f64p)))
         return out[:len(pi)].copy()
 
-    def recommend_for(self, user, items, ratings, n):
-        """recommendations(train ++ user's ratings, kNN predictor)(user, n) for a user outside the fit: (item ids, predictions)"""
-        q, it, rt = self._query_rows(user, items, ratings)
+    def _recommend_q(self, fam, user, items, ratings, n):
+        q, it, rt = self._query_rows(user, items, ratings, allow_empty=fam == "update")
         if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0 or n >= 2**31:
             raise ValueError("n must be a non-negative 32-bit integer")
         n = int(n)
         ids = np.empty(max(1, n), dtype=np.int32)
         preds = np.empty(max(1, n), dtype=np.float64)
         c = C.c_int32()
-        self._check(self._lib.knncf_query_recommend(self._h, PRED_KNN, q, it.ctypes.data_as(_i32p), rt.ctypes.data_as(_f64p), len(it),
-                                                    n, ids.ctypes.data_as(_i32p), preds.ctypes.data_as(_f64p), C.byref(c)))
+        p = self._ptr
+        self._check(getattr(self._lib, f"knncf_{fam}_recommend")(self._h, PRED_KNN, q, p(it, _i32p), p(rt, _f64p), len(it), n,
+                                                                 ids.ctypes.data_as(_i32p), preds.ctypes.data_as(_f64p), C.byref(c)))
         return ids[:c.value].copy(), preds[:c.value].copy()
 
-    # ---- batched fold-in queries (knncf_query_*_batch) -------------------------------------
+    def neighbors_for(self, user, items, ratings, cap=None):
+        """getNeighbors(train ++ user's ratings, k, sim)(user) for a user outside the fit: (ids, sims)"""
+        return self._neighbors_q("query", user, items, ratings, cap)
+
+    def predict_for(self, user, items, ratings, pred_items):
+        """kNN predictions (PRED_KNN) of a user outside the fit, given its ratings, for every id of pred_items"""
+        return self._predict_q("query", user, items, ratings, pred_items)
+
+    def recommend_for(self, user, items, ratings, n):
+        """recommendations(train ++ user's ratings, kNN predictor)(user, n) for a user outside the fit: (item ids, predictions)"""
+        return self._recommend_q("query", user, items, ratings, n)
+
+    def neighbors_with(self, user, items, ratings, cap=None):
+        """getNeighbors(train ++ the additional ratings, k, sim)(user) for any user, of the fit or not: (ids, sims).  A user
+        of the fit is not its own neighbour; items / ratings may be empty for it."""
+        return self._neighbors_q("update", user, items, ratings, cap)
+
+    def predict_with(self, user, items, ratings, pred_items):
+        """kNN predictions (PRED_KNN) of a user with additional ratings (beside its train rows, if any) for every id of pred_items"""
+        return self._predict_q("update", user, items, ratings, pred_items)
+
+    def recommend_with(self, user, items, ratings, n):
+        """recommendations(train ++ the additional ratings, kNN predictor)(user, n) for any user: (item ids, predictions)"""
+        return self._recommend_q("update", user, items, ratings, n)
+
+    # ---- batched forms (knncf_query_*_batch, knncf_update_*_batch) ------------------------------
     @staticmethod
     def _query_batch(queries):
         """validated CSR (users, offsets, items, ratings) of a sequence of (user, items, ratings): ValueError before any C
-        call.  An empty query is allowed here: it gets its own status (E_INVALID), like every per-query failure."""
+        call.  An empty query is allowed here: it gets its own status (E_INVALID for a fold-in query or a user outside the
+        fit), like every per-query failure."""
         users, its, rts, offsets = [], [], [], [0]
         for q in queries:
             if not isinstance(q, (tuple, list)) or len(q) != 3:
@@ -507,13 +544,7 @@ class Engine:
         cat = lambda parts, dt: np.ascontiguousarray(np.concatenate(parts) if parts else np.empty(0), dtype=dt)
         return (np.asarray(users, dtype=np.int32), np.asarray(offsets, dtype=np.int64), cat(its, np.int32), cat(rts, np.float64))
 
-    @staticmethod
-    def _ptr(a, t):
-        return a.ctypes.data_as(t) if len(a) else C.cast(None, t)
-
-    def neighbors_for_batch(self, queries, cap=None):
-        """neighbors_for of every (user, items, ratings) of `queries`, answered in chunks on the device:
-        ([(ids, sims)] per query, statuses int32 [B]).  A failed query (status != OK) has empty arrays."""
+    def _neighbors_qb(self, fam, queries, cap):
         us, off, it, rt = self._query_batch(queries)
         if cap is None:
             cap = max(1, self.k)
@@ -525,14 +556,12 @@ class Engine:
         counts = np.zeros(B, dtype=np.int32)
         st = np.zeros(B, dtype=np.int32)
         p = self._ptr
-        self._check(self._lib.knncf_query_neighbors_batch(self._h, p(us, _i32p), p(off, _i64p), p(it, _i32p), p(rt, _f64p), B, cap,
-                                                          p(ids.reshape(-1), _i32p), p(sims.reshape(-1), _f64p), p(counts, _i32p),
-                                                          p(st, _i32p)))
+        self._check(getattr(self._lib, f"knncf_{fam}_neighbors_batch")(
+            self._h, p(us, _i32p), p(off, _i64p), p(it, _i32p), p(rt, _f64p), B, cap, p(ids.reshape(-1), _i32p),
+            p(sims.reshape(-1), _f64p), p(counts, _i32p), p(st, _i32p)))
         return [(ids[b, :min(counts[b], cap)].copy(), sims[b, :min(counts[b], cap)].copy()) for b in range(B)], st
 
-    def predict_for_batch(self, queries, pred_items):
-        """predict_for of every query; pred_items is one sequence of item ids per query: ([float64 array] per query, statuses).
-        A failed query's array holds NaN."""
+    def _predict_qb(self, fam, queries, pred_items):
         us, off, it, rt = self._query_batch(queries)
         B = len(us)
         pis = [np.asarray(x) for x in pred_items]
@@ -547,12 +576,12 @@ class Engine:
         out = np.full(int(poff[-1]), np.nan, dtype=np.float64)
         st = np.zeros(B, dtype=np.int32)
         p = self._ptr
-        self._check(self._lib.knncf_query_predict_batch(self._h, PRED_KNN, p(us, _i32p), p(off, _i64p), p(it, _i32p), p(rt, _f64p), B,
-                                                        p(poff, _i64p), p(pi, _i32p), p(out, _f64p), p(st, _i32p)))
+        self._check(getattr(self._lib, f"knncf_{fam}_predict_batch")(
+            self._h, PRED_KNN, p(us, _i32p), p(off, _i64p), p(it, _i32p), p(rt, _f64p), B, p(poff, _i64p), p(pi, _i32p),
+            p(out, _f64p), p(st, _i32p)))
         return [out[poff[b]:poff[b + 1]].copy() for b in range(B)], st
 
-    def recommend_for_batch(self, queries, n):
-        """recommend_for(n) of every query: ([(item ids, predictions)] per query, statuses).  A failed query has empty arrays."""
+    def _recommend_qb(self, fam, queries, n):
         us, off, it, rt = self._query_batch(queries)
         if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0 or n >= 2**31:
             raise ValueError("n must be a non-negative 32-bit integer")
@@ -562,10 +591,38 @@ class Engine:
         counts = np.zeros(B, dtype=np.int32)
         st = np.zeros(B, dtype=np.int32)
         p = self._ptr
-        self._check(self._lib.knncf_query_recommend_batch(self._h, PRED_KNN, p(us, _i32p), p(off, _i64p), p(it, _i32p), p(rt, _f64p), B,
-                                                          n, p(ids.reshape(-1), _i32p), p(preds.reshape(-1), _f64p), p(counts, _i32p),
-                                                          p(st, _i32p)))
+        self._check(getattr(self._lib, f"knncf_{fam}_recommend_batch")(
+            self._h, PRED_KNN, p(us, _i32p), p(off, _i64p), p(it, _i32p), p(rt, _f64p), B, n, p(ids.reshape(-1), _i32p),
+            p(preds.reshape(-1), _f64p), p(counts, _i32p), p(st, _i32p)))
         return [(ids[b, :counts[b]].copy(), preds[b, :counts[b]].copy()) for b in range(B)], st
+
+    def neighbors_for_batch(self, queries, cap=None):
+        """neighbors_for of every (user, items, ratings) of `queries`, answered in chunks on the device:
+        ([(ids, sims)] per query, statuses int32 [B]).  A failed query (status != OK) has empty arrays."""
+        return self._neighbors_qb("query", queries, cap)
+
+    def predict_for_batch(self, queries, pred_items):
+        """predict_for of every query; pred_items is one sequence of item ids per query: ([float64 array] per query, statuses).
+        A failed query's array holds NaN."""
+        return self._predict_qb("query", queries, pred_items)
+
+    def recommend_for_batch(self, queries, n):
+        """recommend_for(n) of every query: ([(item ids, predictions)] per query, statuses).  A failed query has empty arrays."""
+        return self._recommend_qb("query", queries, n)
+
+    def neighbors_with_batch(self, queries, cap=None):
+        """neighbors_with of every (user, additional items, additional ratings) of `queries`, users of the fit and others
+        mixed: ([(ids, sims)] per query, statuses int32 [B]).  A failed query (status != OK) has empty arrays."""
+        return self._neighbors_qb("update", queries, cap)
+
+    def predict_with_batch(self, queries, pred_items):
+        """predict_with of every query; pred_items is one sequence of item ids per query: ([float64 array] per query, statuses).
+        A failed query's array holds NaN."""
+        return self._predict_qb("update", queries, pred_items)
+
+    def recommend_with_batch(self, queries, n):
+        """recommend_with(n) of every query: ([(item ids, predictions)] per query, statuses).  A failed query has empty arrays."""
+        return self._recommend_qb("update", queries, n)
 
     # ---- batch -------------------------------------------------------------------------
     def predict_batch(self, predictor, users, items):
