@@ -308,6 +308,61 @@ int knncf_update_recommend_batch(knncf_handle* h, int predictor, const int32_t* 
                                  const double* ratings, int64_t n_queries, int32_t n, int32_t* out_items, double* out_preds,
                                  int32_t* counts, int32_t* statuses);
 
+/* ---- Revise queries: a user of the fit who REMOVED or RE-RATED items, possibly with additional ratings -----------------------
+ * The update calls above can only add rows.  These take, in front of the additional rows, the raw ids of train items of `user`
+ * whose rows are taken out: removed_items[0 .. n_removed) (batched: the CSR removed_offsets / removed_items, like offsets:
+ * removed_offsets[0] == 0, non-decreasing, fewer than 2^31 removed items in all).  With
+ *     aug = [r for r in train, in file order, unless r.user == user and r.item is in removed_items]
+ *           ++ [Rating(user, items[j], ratings[j]) for j in order]
+ * every result equals, bit for bit, the reference's on aug with fresh closures whose first evaluation is `user`'s, WITHOUT a
+ * refit: knncf_revise_neighbors = getNeighbors(aug, k, sim)(user) :603-616, knncf_revise_predict = the kNN predictor :489-585,
+ * knncf_revise_recommend = recommendations :651-674.  Removing rows of `user` changes only that user's mean, deviations, norm
+ * and preprocessed ratings; nobody else's quantities move.
+ *   The user set of aug.  A user of the fit that keeps at least one row, train or additional, stays in allUsers: *count of
+ *     the neighbours is min(k, U - 1).  A user of the fit whose train rows are all removed and who gives no additional row is
+ *     not in aug: KNNCF_E_INVALID, like an empty fold-in query.
+ *   Row-size class.  The <= 4-rating regime (given-order folding) is decided by the user's row count in aug: train rows minus
+ *     removed plus additional.  The surviving train rows come first, in file order; the additional rows come behind them.
+ *   An item that leaves aug: the user was its only rater in train, it is removed and not given again.  It is no longer in
+ *     ratings.map(_.item).toSet :667, so it is no candidate of the recommendations, whose *count is
+ *     min(n, #items of aug - #items the user rates in aug); knncf_revise_predict on it answers the user's mean exactly (no
+ *     raters, den = 0), as for any item unknown to aug.
+ *   A removed item that other users rate becomes an unrated item of the user: it is a candidate again, and its prediction folds
+ *     the neighbours' ratings as for any other item.
+ *   Re-rating.  An item may occur in removed_items and among the additional rows of the same query: its train row is replaced.
+ *     An additional row on a train item of the user that is NOT removed stays KNNCF_E_DUPLICATE, as does a repeat inside the
+ *     additional rows.
+ *   Per-query refusals beyond those of knncf_update_*, status KNNCF_E_INVALID: a removed item that the user did not rate in
+ *     train (this includes an id unknown to train, and any removal for a user absent from train), and a removed item listed
+ *     twice.  knncf_last_error names the query and the reason, like the other per-query failures.
+ * Everything else is as knncf_update_* documents it, read on the rows the user has in aug: KNNCF_E_NONFINITE, KNNCF_E_UNSUPPORTED
+ * for a negative mean of the user's rows in aug; the cap of 65536 rows, which counts the user's train rows, REMOVED ONES
+ * INCLUDED, plus the additional rows, because all of them are seeded; the handle-level return values, the CSR checks (for
+ * removed_offsets too), n_queries == 0, untouched rows and counts[b] = 0 for failed queries; the chunk rule with its formula
+ *     C = max(1, min(64, budget / (64 * num_users + 96 * num_items), (2^31 - 1) / max(num_users, num_items)))
+ * and the split at 32 answerable queries between the two similarity kernels.  The results do not depend on C.  Read-only on
+ * the handle: the neighbour table, its build numbers and epoch and what knncf_neighbors_save writes stay as they were.
+ * n_removed == 0 (removed_items may then be null) gives the knncf_update_* answer bit for bit: the same code runs. */
+int knncf_revise_neighbors(knncf_handle* h, int32_t user, const int32_t* removed_items, int64_t n_removed, const int32_t* items,
+                           const double* ratings, int64_t n_ratings, int32_t cap, int32_t* ids, double* sims, int32_t* count);
+int knncf_revise_predict(knncf_handle* h, int predictor, int32_t user, const int32_t* removed_items, int64_t n_removed,
+                         const int32_t* items, const double* ratings, int64_t n_ratings, const int32_t* pred_items, int64_t m,
+                         double* out);
+int knncf_revise_recommend(knncf_handle* h, int predictor, int32_t user, const int32_t* removed_items, int64_t n_removed,
+                           const int32_t* items, const double* ratings, int64_t n_ratings, int32_t n, int32_t* out_items,
+                           double* out_preds, int32_t* count);
+int knncf_revise_neighbors_batch(knncf_handle* h, const int32_t* users, const int64_t* removed_offsets, const int32_t* removed_items,
+                                 const int64_t* offsets, const int32_t* items, const double* ratings, int64_t n_queries, int32_t cap,
+                                 int32_t* ids, double* sims, int32_t* counts, int32_t* statuses);
+int knncf_revise_predict_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* removed_offsets,
+                               const int32_t* removed_items, const int64_t* offsets, const int32_t* items, const double* ratings,
+                               int64_t n_queries, const int64_t* pred_offsets, const int32_t* pred_items, double* out,
+                               int32_t* statuses);
+int knncf_revise_recommend_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* removed_offsets,
+                                 const int32_t* removed_items, const int64_t* offsets, const int32_t* items, const double* ratings,
+                                 int64_t n_queries, int32_t n, int32_t* out_items, double* out_preds, int32_t* counts,
+                                 int32_t* statuses);
+
 /* ---- batch ---------------------------------------------------------------- */
 int knncf_predict_batch(knncf_handle* h, int predictor, const int32_t* users,
                         const int32_t* items, int64_t n, double* out);

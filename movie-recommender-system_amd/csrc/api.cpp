@@ -1038,9 +1038,11 @@ void do_recommend(knncf_handle* h, int predictor, int32_t user, int32_t n, int32
 // knncf_query_*_batch take B independent queries; a single call is a chunk of one.
 // Update queries (knncf_update_*) are the same calls for a user that may be in the fit: the rows given are then ADDITIONAL to
 // the user's train rows, which foldin.hip seeds on the device, and the user is left out of its own candidates.
+// Revise queries (knncf_revise_*) are update queries that also name train items of the user to REMOVE from aug: the seeding
+// leaves their rows out.  A chunk without removals is an update chunk.
 constexpr int64_t QUERY_MAX_RATINGS = 65536;
 enum QueryBatchMode { QB_NEIGHBORS, QB_PREDICT, QB_RECOMMEND };
-enum QueryFamily { QF_FOLD_IN, QF_UPDATE };
+enum QueryFamily { QF_FOLD_IN, QF_UPDATE, QF_REVISE };
 
 // what the handle must be for any fold-in query, single or batched
 void require_query_support(knncf_handle* h, int predictor) {
@@ -1072,8 +1074,10 @@ struct QueryFailure {
 
 // The B validated queries in chunks of `chunk`: statuses[b] and, where it is KNNCF_OK, query b's answer.
 // mode QB_NEIGHBORS: width = cap, out_i / out_d = ids / sims [B * cap]; QB_RECOMMEND: width = n, out_i / out_d = items /
-// predictions [B * n]; QB_PREDICT: out_d [pred_offsets[B]]
+// predictions [B * n]; QB_PREDICT: out_d [pred_offsets[B]].  QF_REVISE: removed_items [removed_offsets[b], removed_offsets[b + 1])
+// are the train items query b's user drops (null for the other families)
 QueryFailure run_query_chunks(knncf_handle* h, QueryFamily family, QueryBatchMode mode, int64_t chunk, const int32_t* users,
+                              const int64_t* removed_offsets, const int32_t* removed_items,
                               const int64_t* offsets, const int32_t* items, const double* ratings, int64_t B, int32_t width, const int64_t* pred_offsets,
                               const int32_t* pred_items, int32_t* out_i, double* out_d, int32_t* counts, int32_t* statuses) {
     h->prep.join_commit(h->stream);
@@ -1087,25 +1091,33 @@ QueryFailure run_query_chunks(knncf_handle* h, QueryFamily family, QueryBatchMod
         if (counts) counts[b] = 0;
         if (first.query < 0 || b < first.query) first = {b, why};
     };
-    const bool update = family == QF_UPDATE;
-    std::vector<int64_t> slot_query, qo, ao, ebase;
-    std::vector<int32_t> s_users, s_items, s_self, h_idx, h_items, pick_slot, pick_items;
+    const bool update = family != QF_FOLD_IN, revise = family == QF_REVISE;
+    std::vector<int64_t> slot_query, qo, ao, ro, ebase;
+    std::vector<int32_t> s_users, s_items, s_self, s_removed, h_idx, h_items, pick_slot, pick_items;
     std::vector<double> s_ratings, h_vals;
     std::vector<long long> info;
     for (int64_t c0 = 0; c0 < B; c0 += chunk) {
         const int64_t c1 = std::min(B, c0 + chunk);
         // the chunk's answerable queries, slot after slot
-        slot_query.clear(); s_users.clear(); s_items.clear(); s_ratings.clear(); s_self.clear();
+        slot_query.clear(); s_users.clear(); s_items.clear(); s_ratings.clear(); s_self.clear(); s_removed.clear();
         qo.assign(1, 0);
         ao.assign(1, 0);
+        ro.assign(1, 0);
         for (int64_t b = c0; b < c1; ++b) {
             const int64_t nb = offsets[b + 1] - offsets[b];
+            const int64_t nr = revise ? removed_offsets[b + 1] - removed_offsets[b] : 0;
             const int32_t du = dense_user(h, users[b]);
-            // rows of the user in aug: its train rows (update queries) and the given ones
-            const int64_t rows = nb + (update && du >= 0 ? train_row_length(h, du) : 0);
-            if (rows <= 0) { fail(b, KNNCF_E_INVALID, "null ratings or n_ratings <= 0"); continue; }
-            if (rows > QUERY_MAX_RATINGS) { fail(b, KNNCF_E_UNSUPPORTED, "more than 65536 ratings"); continue; }
+            // rows of the user in aug: its train rows (update queries) without the removed ones (revise queries), and the
+            // given ones; every train row is seeded, so all of them count against the cap
+            const int64_t seeded = nb + (update && du >= 0 ? train_row_length(h, du) : 0);
+            if (nr > 0 && du < 0) { fail(b, KNNCF_E_INVALID, "a removed item for a user that is not in the training set"); continue; }
+            if (nr > seeded - nb) { fail(b, KNNCF_E_INVALID, "more removed items than the user has train rows (one is not rated in train or listed twice)"); continue; }
+            const int64_t rows = seeded - nr;
+            if (rows <= 0) { fail(b, KNNCF_E_INVALID, nr > 0 ? "the removals leave the user without a row" : "null ratings or n_ratings <= 0"); continue; }
+            if (seeded > QUERY_MAX_RATINGS) { fail(b, KNNCF_E_UNSUPPORTED, "more than 65536 ratings"); continue; }
             if (!update && du >= 0) { fail(b, KNNCF_E_INVALID, "the user occurs in the training set"); continue; }
+            if (nr > 0) s_removed.insert(s_removed.end(), removed_items + removed_offsets[b], removed_items + removed_offsets[b + 1]);
+            ro.push_back((int64_t)s_removed.size());
             slot_query.push_back(b);
             s_users.push_back(users[b]);
             s_self.push_back(du);
@@ -1118,14 +1130,17 @@ QueryFailure run_query_chunks(knncf_handle* h, QueryFamily family, QueryBatchMod
         if (C == 0) continue;
         info.assign((size_t)4 * C, 0);
         foldin_batch_neighbors(tr, bs, h->prep.sort, C, s_users.data(), qo.data(), s_items.data(), s_ratings.data(),
-                               update ? s_self.data() : nullptr, update ? ao.data() : nullptr, h->cfg.k, info.data(), st);
+                               update ? s_self.data() : nullptr, update ? ao.data() : nullptr, h->cfg.k, info.data(), st,
+                               revise ? ro.data() : nullptr, revise ? s_removed.data() : nullptr);
         // neighbours of slot s: (allUsers - u) :608 drops a user of the fit
         auto take_of = [&](int32_t s) { return update && s_self[s] >= 0 ? std::min(take, tr.U - 1) : take; };
         int32_t good = 0;
         for (int32_t s = 0; s < C; ++s) {
             const uint64_t bits = (uint64_t)info[4 * s];
             const int64_t b = slot_query[s];
-            if (bits & ST_DUPLICATE) fail(b, KNNCF_E_DUPLICATE, "the ratings repeat an item");
+            if (bits & QUERY_ST_RM_UNRATED) fail(b, KNNCF_E_INVALID, "a removed item that the user did not rate in train");
+            else if (bits & QUERY_ST_RM_TWICE) fail(b, KNNCF_E_INVALID, "a removed item listed twice");
+            else if (bits & ST_DUPLICATE) fail(b, KNNCF_E_DUPLICATE, "the ratings repeat an item");
             else if (bits & ST_NONFINITE) fail(b, KNNCF_E_NONFINITE, "scale() == 0 gives a non-finite deviation");
             else if (bits & QUERY_ST_NEG_MEAN) fail(b, KNNCF_E_UNSUPPORTED, "a negative mean rating (the predictor would answer aug's global average)");
             else { statuses[b] = KNNCF_OK; ++good; }
@@ -1209,7 +1224,7 @@ QueryFailure run_query_chunks(knncf_handle* h, QueryFamily family, QueryBatchMod
 }
 
 void do_query_batch(knncf_handle* h, QueryFamily family, QueryBatchMode mode, int predictor, const int32_t* users,
-                    const int64_t* offsets, const int32_t* items, const double* ratings, int64_t B, int32_t width, const int64_t* pred_offsets,
+                    const int64_t* removed_offsets, const int32_t* removed_items, const int64_t* offsets, const int32_t* items, const double* ratings, int64_t B, int32_t width, const int64_t* pred_offsets,
                     const int32_t* pred_items, int32_t* out_i, double* out_d, int32_t* counts, int32_t* statuses) {
     require_fitted(h, false);
     KN_REQUIRE(B >= 0, KNNCF_E_INVALID, "query batch: n_queries < 0");
@@ -1221,6 +1236,13 @@ void do_query_batch(knncf_handle* h, QueryFamily family, QueryBatchMode mode, in
     for (int64_t b = 0; b < B; ++b) KN_REQUIRE(offsets[b] <= offsets[b + 1], KNNCF_E_INVALID, "query batch: offsets decrease");
     KN_REQUIRE(offsets[B] < ((int64_t)1 << 31), KNNCF_E_INVALID, "query batch: 2^31 or more ratings in one call");
     KN_REQUIRE(offsets[B] == 0 || (items && ratings), KNNCF_E_INVALID, "query batch: null ratings");
+    if (family == QF_REVISE) {
+        KN_REQUIRE(removed_offsets && removed_offsets[0] == 0, KNNCF_E_INVALID, "query batch: removed_offsets null or not starting at 0");
+        for (int64_t b = 0; b < B; ++b)
+            KN_REQUIRE(removed_offsets[b] <= removed_offsets[b + 1], KNNCF_E_INVALID, "query batch: removed_offsets decrease");
+        KN_REQUIRE(removed_offsets[B] < ((int64_t)1 << 31), KNNCF_E_INVALID, "query batch: 2^31 or more removed items in one call");
+        KN_REQUIRE(removed_offsets[B] == 0 || removed_items, KNNCF_E_INVALID, "query batch: null removed items");
+    }
     if (mode == QB_PREDICT) {
         KN_REQUIRE(pred_offsets && pred_offsets[0] == 0, KNNCF_E_INVALID, "query batch: pred_offsets null or not starting at 0");
         for (int64_t b = 0; b < B; ++b)
@@ -1229,27 +1251,29 @@ void do_query_batch(knncf_handle* h, QueryFamily family, QueryBatchMode mode, in
     } else {
         KN_REQUIRE(width == 0 || (out_i && out_d), KNNCF_E_INVALID, "query batch: null output");
     }
-    const QueryFailure f = run_query_chunks(h, family, mode, query_batch_chunk(h), users, offsets, items, ratings, B, width,
-                                            pred_offsets, pred_items, out_i, out_d, counts, statuses);
+    const QueryFailure f = run_query_chunks(h, family, mode, query_batch_chunk(h), users, removed_offsets, removed_items, offsets, items,
+                                            ratings, B, width, pred_offsets, pred_items, out_i, out_d, counts, statuses);
     if (f.query >= 0) h->err = "query batch: query " + std::to_string(f.query) + ": " + f.reason;
 }
 
 // One query as a chunk of one: the query's status is the call's.  The entry points check their own output arguments first;
 // *count (neighbours: min(k, U), min(k, U - 1) for a user of the fit; recommendations: min(n, I - known items)) is written on
 // success.  An update query may come without rows (whether the user is in the fit is the chunk loop's to say).
-void do_query_single(knncf_handle* h, QueryFamily family, QueryBatchMode mode, int predictor, int32_t user, const int32_t* items,
-                     const double* ratings, int64_t n_ratings, int32_t width, const int32_t* pred_items, int64_t m, int32_t* out_i,
+void do_query_single(knncf_handle* h, QueryFamily family, QueryBatchMode mode, int predictor, int32_t user,
+                     const int32_t* removed_items, int64_t n_removed, const int32_t* items, const double* ratings, int64_t n_ratings, int32_t width, const int32_t* pred_items, int64_t m, int32_t* out_i,
                      double* out_d, int32_t* count) {
     require_fitted(h, false);
-    if (family == QF_UPDATE) {
+    if (family == QF_REVISE)
+        KN_REQUIRE(n_removed >= 0 && (n_removed == 0 || removed_items), KNNCF_E_INVALID, "query: null removed items or n_removed < 0");
+    if (family != QF_FOLD_IN) {
         KN_REQUIRE(n_ratings >= 0 && (n_ratings == 0 || (items && ratings)), KNNCF_E_INVALID, "query: null ratings or n_ratings < 0");
     } else {
         KN_REQUIRE(items && ratings && n_ratings > 0, KNNCF_E_INVALID, "query: null ratings or n_ratings <= 0");
     }
     require_query_support(h, predictor);
-    const int64_t offsets[2] = {0, n_ratings}, pred_offsets[2] = {0, m};
+    const int64_t offsets[2] = {0, n_ratings}, pred_offsets[2] = {0, m}, removed_offsets[2] = {0, family == QF_REVISE ? n_removed : 0};
     int32_t status = KNNCF_OK, c = 0;
-    const QueryFailure f = run_query_chunks(h, family, mode, 1, &user, offsets, items, ratings, 1, width, pred_offsets, pred_items,
+    const QueryFailure f = run_query_chunks(h, family, mode, 1, &user, removed_offsets, removed_items, offsets, items, ratings, 1, width, pred_offsets, pred_items,
                                             out_i, out_d, &c, &status);
     if (f.query >= 0) throw Error(status, std::string("query: ") + f.reason);
     if (count) *count = c;
@@ -1831,7 +1855,7 @@ int knncf_query_neighbors(knncf_handle* h, int32_t user, const int32_t* items, c
                           int32_t cap, int32_t* ids, double* sims, int32_t* count) {
     return guarded(h, [&] {
         KN_REQUIRE(count && cap >= 0 && (cap == 0 || (ids && sims)), KNNCF_E_INVALID, "bad output arguments");
-        do_query_single(h, QF_FOLD_IN, QB_NEIGHBORS, KNNCF_PRED_KNN, user, items, ratings, n_ratings, cap, nullptr, 0, ids, sims, count);
+        do_query_single(h, QF_FOLD_IN, QB_NEIGHBORS, KNNCF_PRED_KNN, user, nullptr, 0, items, ratings, n_ratings, cap, nullptr, 0, ids, sims, count);
     });
 }
 
@@ -1839,7 +1863,7 @@ int knncf_query_predict(knncf_handle* h, int predictor, int32_t user, const int3
                         int64_t n_ratings, const int32_t* pred_items, int64_t m, double* out) {
     return guarded(h, [&] {
         KN_REQUIRE(m >= 0 && (m == 0 || (pred_items && out)), KNNCF_E_INVALID, "bad prediction arguments");
-        do_query_single(h, QF_FOLD_IN, QB_PREDICT, predictor, user, items, ratings, n_ratings, 0, pred_items, m, nullptr, out, nullptr);
+        do_query_single(h, QF_FOLD_IN, QB_PREDICT, predictor, user, nullptr, 0, items, ratings, n_ratings, 0, pred_items, m, nullptr, out, nullptr);
     });
 }
 
@@ -1847,7 +1871,7 @@ int knncf_query_neighbors_batch(knncf_handle* h, const int32_t* users, const int
                                 const double* ratings, int64_t n_queries, int32_t cap, int32_t* ids, double* sims, int32_t* counts,
                                 int32_t* statuses) {
     return guarded(h, [&] {
-        do_query_batch(h, QF_FOLD_IN, QB_NEIGHBORS, KNNCF_PRED_KNN, users, offsets, items, ratings, n_queries, cap, nullptr, nullptr, ids, sims,
+        do_query_batch(h, QF_FOLD_IN, QB_NEIGHBORS, KNNCF_PRED_KNN, users, nullptr, nullptr, offsets, items, ratings, n_queries, cap, nullptr, nullptr, ids, sims,
                        counts, statuses);
     });
 }
@@ -1856,7 +1880,7 @@ int knncf_query_predict_batch(knncf_handle* h, int predictor, const int32_t* use
                               const double* ratings, int64_t n_queries, const int64_t* pred_offsets, const int32_t* pred_items,
                               double* out, int32_t* statuses) {
     return guarded(h, [&] {
-        do_query_batch(h, QF_FOLD_IN, QB_PREDICT, predictor, users, offsets, items, ratings, n_queries, 0, pred_offsets, pred_items, nullptr, out,
+        do_query_batch(h, QF_FOLD_IN, QB_PREDICT, predictor, users, nullptr, nullptr, offsets, items, ratings, n_queries, 0, pred_offsets, pred_items, nullptr, out,
                        nullptr, statuses);
     });
 }
@@ -1865,7 +1889,7 @@ int knncf_query_recommend_batch(knncf_handle* h, int predictor, const int32_t* u
                                 const double* ratings, int64_t n_queries, int32_t n, int32_t* out_items, double* out_preds,
                                 int32_t* counts, int32_t* statuses) {
     return guarded(h, [&] {
-        do_query_batch(h, QF_FOLD_IN, QB_RECOMMEND, predictor, users, offsets, items, ratings, n_queries, n, nullptr, nullptr, out_items,
+        do_query_batch(h, QF_FOLD_IN, QB_RECOMMEND, predictor, users, nullptr, nullptr, offsets, items, ratings, n_queries, n, nullptr, nullptr, out_items,
                        out_preds, counts, statuses);
     });
 }
@@ -1875,7 +1899,7 @@ int knncf_query_recommend(knncf_handle* h, int predictor, int32_t user, const in
     return guarded(h, [&] {
         KN_REQUIRE(count && n >= 0 && (n == 0 || (out_items && out_preds)), KNNCF_E_INVALID, "bad arguments");
         *count = 0;
-        do_query_single(h, QF_FOLD_IN, QB_RECOMMEND, predictor, user, items, ratings, n_ratings, n, nullptr, 0, out_items, out_preds, count);
+        do_query_single(h, QF_FOLD_IN, QB_RECOMMEND, predictor, user, nullptr, 0, items, ratings, n_ratings, n, nullptr, 0, out_items, out_preds, count);
     });
 }
 
@@ -1884,7 +1908,7 @@ int knncf_update_neighbors(knncf_handle* h, int32_t user, const int32_t* items, 
                            int32_t cap, int32_t* ids, double* sims, int32_t* count) {
     return guarded(h, [&] {
         KN_REQUIRE(count && cap >= 0 && (cap == 0 || (ids && sims)), KNNCF_E_INVALID, "bad output arguments");
-        do_query_single(h, QF_UPDATE, QB_NEIGHBORS, KNNCF_PRED_KNN, user, items, ratings, n_ratings, cap, nullptr, 0, ids, sims, count);
+        do_query_single(h, QF_UPDATE, QB_NEIGHBORS, KNNCF_PRED_KNN, user, nullptr, 0, items, ratings, n_ratings, cap, nullptr, 0, ids, sims, count);
     });
 }
 
@@ -1892,7 +1916,7 @@ int knncf_update_predict(knncf_handle* h, int predictor, int32_t user, const int
                          int64_t n_ratings, const int32_t* pred_items, int64_t m, double* out) {
     return guarded(h, [&] {
         KN_REQUIRE(m >= 0 && (m == 0 || (pred_items && out)), KNNCF_E_INVALID, "bad prediction arguments");
-        do_query_single(h, QF_UPDATE, QB_PREDICT, predictor, user, items, ratings, n_ratings, 0, pred_items, m, nullptr, out, nullptr);
+        do_query_single(h, QF_UPDATE, QB_PREDICT, predictor, user, nullptr, 0, items, ratings, n_ratings, 0, pred_items, m, nullptr, out, nullptr);
     });
 }
 
@@ -1900,7 +1924,7 @@ int knncf_update_neighbors_batch(knncf_handle* h, const int32_t* users, const in
                                  const double* ratings, int64_t n_queries, int32_t cap, int32_t* ids, double* sims, int32_t* counts,
                                  int32_t* statuses) {
     return guarded(h, [&] {
-        do_query_batch(h, QF_UPDATE, QB_NEIGHBORS, KNNCF_PRED_KNN, users, offsets, items, ratings, n_queries, cap, nullptr, nullptr, ids, sims,
+        do_query_batch(h, QF_UPDATE, QB_NEIGHBORS, KNNCF_PRED_KNN, users, nullptr, nullptr, offsets, items, ratings, n_queries, cap, nullptr, nullptr, ids, sims,
                        counts, statuses);
     });
 }
@@ -1909,7 +1933,7 @@ int knncf_update_predict_batch(knncf_handle* h, int predictor, const int32_t* us
                                const double* ratings, int64_t n_queries, const int64_t* pred_offsets, const int32_t* pred_items,
                                double* out, int32_t* statuses) {
     return guarded(h, [&] {
-        do_query_batch(h, QF_UPDATE, QB_PREDICT, predictor, users, offsets, items, ratings, n_queries, 0, pred_offsets, pred_items, nullptr, out,
+        do_query_batch(h, QF_UPDATE, QB_PREDICT, predictor, users, nullptr, nullptr, offsets, items, ratings, n_queries, 0, pred_offsets, pred_items, nullptr, out,
                        nullptr, statuses);
     });
 }
@@ -1918,7 +1942,7 @@ int knncf_update_recommend_batch(knncf_handle* h, int predictor, const int32_t* 
                                  const double* ratings, int64_t n_queries, int32_t n, int32_t* out_items, double* out_preds,
                                  int32_t* counts, int32_t* statuses) {
     return guarded(h, [&] {
-        do_query_batch(h, QF_UPDATE, QB_RECOMMEND, predictor, users, offsets, items, ratings, n_queries, n, nullptr, nullptr, out_items,
+        do_query_batch(h, QF_UPDATE, QB_RECOMMEND, predictor, users, nullptr, nullptr, offsets, items, ratings, n_queries, n, nullptr, nullptr, out_items,
                        out_preds, counts, statuses);
     });
 }
@@ -1928,7 +1952,64 @@ int knncf_update_recommend(knncf_handle* h, int predictor, int32_t user, const i
     return guarded(h, [&] {
         KN_REQUIRE(count && n >= 0 && (n == 0 || (out_items && out_preds)), KNNCF_E_INVALID, "bad arguments");
         *count = 0;
-        do_query_single(h, QF_UPDATE, QB_RECOMMEND, predictor, user, items, ratings, n_ratings, n, nullptr, 0, out_items, out_preds, count);
+        do_query_single(h, QF_UPDATE, QB_RECOMMEND, predictor, user, nullptr, 0, items, ratings, n_ratings, n, nullptr, 0, out_items, out_preds, count);
+    });
+}
+
+// revise queries: update queries that also remove train rows of the user (removed_items) from aug
+int knncf_revise_neighbors(knncf_handle* h, int32_t user, const int32_t* removed_items, int64_t n_removed, const int32_t* items,
+                           const double* ratings, int64_t n_ratings, int32_t cap, int32_t* ids, double* sims, int32_t* count) {
+    return guarded(h, [&] {
+        KN_REQUIRE(count && cap >= 0 && (cap == 0 || (ids && sims)), KNNCF_E_INVALID, "bad output arguments");
+        do_query_single(h, QF_REVISE, QB_NEIGHBORS, KNNCF_PRED_KNN, user, removed_items, n_removed, items, ratings, n_ratings, cap, nullptr, 0,
+                        ids, sims, count);
+    });
+}
+
+int knncf_revise_predict(knncf_handle* h, int predictor, int32_t user, const int32_t* removed_items, int64_t n_removed,
+                         const int32_t* items, const double* ratings, int64_t n_ratings, const int32_t* pred_items, int64_t m, double* out) {
+    return guarded(h, [&] {
+        KN_REQUIRE(m >= 0 && (m == 0 || (pred_items && out)), KNNCF_E_INVALID, "bad prediction arguments");
+        do_query_single(h, QF_REVISE, QB_PREDICT, predictor, user, removed_items, n_removed, items, ratings, n_ratings, 0, pred_items, m,
+                        nullptr, out, nullptr);
+    });
+}
+
+int knncf_revise_recommend(knncf_handle* h, int predictor, int32_t user, const int32_t* removed_items, int64_t n_removed,
+                           const int32_t* items, const double* ratings, int64_t n_ratings, int32_t n, int32_t* out_items,
+                           double* out_preds, int32_t* count) {
+    return guarded(h, [&] {
+        KN_REQUIRE(count && n >= 0 && (n == 0 || (out_items && out_preds)), KNNCF_E_INVALID, "bad arguments");
+        *count = 0;
+        do_query_single(h, QF_REVISE, QB_RECOMMEND, predictor, user, removed_items, n_removed, items, ratings, n_ratings, n, nullptr, 0,
+                        out_items, out_preds, count);
+    });
+}
+
+int knncf_revise_neighbors_batch(knncf_handle* h, const int32_t* users, const int64_t* removed_offsets, const int32_t* removed_items,
+                                 const int64_t* offsets, const int32_t* items, const double* ratings, int64_t n_queries, int32_t cap,
+                                 int32_t* ids, double* sims, int32_t* counts, int32_t* statuses) {
+    return guarded(h, [&] {
+        do_query_batch(h, QF_REVISE, QB_NEIGHBORS, KNNCF_PRED_KNN, users, removed_offsets, removed_items, offsets, items, ratings, n_queries,
+                       cap, nullptr, nullptr, ids, sims, counts, statuses);
+    });
+}
+
+int knncf_revise_predict_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* removed_offsets,
+                               const int32_t* removed_items, const int64_t* offsets, const int32_t* items, const double* ratings,
+                               int64_t n_queries, const int64_t* pred_offsets, const int32_t* pred_items, double* out, int32_t* statuses) {
+    return guarded(h, [&] {
+        do_query_batch(h, QF_REVISE, QB_PREDICT, predictor, users, removed_offsets, removed_items, offsets, items, ratings, n_queries, 0,
+                       pred_offsets, pred_items, nullptr, out, nullptr, statuses);
+    });
+}
+
+int knncf_revise_recommend_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* removed_offsets,
+                                 const int32_t* removed_items, const int64_t* offsets, const int32_t* items, const double* ratings,
+                                 int64_t n_queries, int32_t n, int32_t* out_items, double* out_preds, int32_t* counts, int32_t* statuses) {
+    return guarded(h, [&] {
+        do_query_batch(h, QF_REVISE, QB_RECOMMEND, predictor, users, removed_offsets, removed_items, offsets, items, ratings, n_queries, n,
+                       nullptr, nullptr, out_items, out_preds, counts, statuses);
     });
 }
 

@@ -300,6 +300,8 @@ void launch_reco_take(const Train& tr, int32_t m, const uint32_t* d_order, const
 // Chunks of independent queries, every stage one launch over the chunk; a single call is a chunk of one.  The scratch is
 // handle-owned; the fit, its neighbour table and its sequence numbers are only read.
 static constexpr uint32_t QUERY_ST_NEG_MEAN = 1u << 8;  // status bit beside ST_NONFINITE / ST_DUPLICATE: the query's mean is negative
+// revise queries: a removed item that is not a train item of the slot's user / a removed item listed twice
+static constexpr uint32_t QUERY_ST_RM_UNRATED = 1u << 9, QUERY_ST_RM_TWICE = 1u << 10;
 static constexpr int QB_MAX_CHUNK = 64;  // queries per chunk: one lane of k_query_sim_dual's waves each
 static constexpr int QB_DUAL_MIN = 32;   // smaller chunks run k_query_sim once per query instead: measured crossover
 // device bytes per query of a chunk that the chunk rule of knncf.h counts
@@ -313,6 +315,12 @@ struct QueryBatchScratch {
     DArr<int64_t> ao;                  // [C + 1] update queries: first additional row of each slot
     DArr<int32_t> add_items;           // [ao[C]] the additional rows as uploaded (items / ratings hold train rows + these)
     DArr<double> add_ratings;
+    // revise queries (a chunk with removed items; n_removed = their number in the chunk answered last, 0: none)
+    int64_t n_removed = 0;
+    DArr<int64_t> ro, so;              // [C + 1] first removed item / first source row (train rows + additional rows) of each slot
+    std::vector<int64_t> h_so;         // host copy of so
+    DArr<int32_t> rm_items, rm_slot, rm_gone;  // [ro[C]] raw item, slot, dense item if it leaves aug (else -1) of each removed item
+    DArr<uint32_t> rm_mark;            // [so[C]] 1 = this train row of the slot's user is removed
     DArr<uint64_t> bits;               // [C][ceil(I / 64)]
     DArr<int64_t> rank;                // [C][ceil(I / 64) + 1]
     DArr<uint32_t> tbits, trank;       // [2 ceil(I / 64)][64] the bitmaps and prefixes side by side (k_qb_transpose)
@@ -339,9 +347,14 @@ struct QueryBatchScratch {
 // is the dense index of slot b's user in the fit or -1, h_items / h_ratings are the additional rows [h_ao[C]] only, and slot b
 // has h_qo[b + 1] - h_qo[b] = (train rows of h_self[b]) + (h_ao[b + 1] - h_ao[b]) rows: the train rows are seeded on the
 // device, a fitted user is left out of its own candidates and gets min(k, U - 1) neighbours.
+// h_ro != nullptr with h_ro[C] > 0 (revise queries): h_removed [h_ro[b], h_ro[b + 1]) are raw items whose train rows slot b's
+// user drops, at most as many as it has train rows, none for a slot with h_self[b] < 0; slot b then has (train rows) -
+// (removed items) + (additional rows) rows.  A removal that names no train row of the user, or one twice, sets
+// QUERY_ST_RM_UNRATED / QUERY_ST_RM_TWICE in the slot's status bits.  The known items of h_info count the items that left aug.
 void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, const int32_t* h_users,
                             const int64_t* h_qo, const int32_t* h_items, const double* h_ratings, const int32_t* h_self,
-                            const int64_t* h_ao, int32_t k, long long* h_info, hipStream_t st);
+                            const int64_t* h_ao, int32_t k, long long* h_info, hipStream_t st, const int64_t* h_ro = nullptr,
+                            const int32_t* h_removed = nullptr);
 // bs.pred / bs.rated [C][I]; h_ebase[C + 1] = exclusive prefix of the slots' neighbour ratings
 void foldin_batch_predictions(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, int32_t take,
                               const int64_t* h_ebase, hipStream_t st);

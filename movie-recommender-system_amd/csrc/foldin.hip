@@ -12,6 +12,11 @@
 // depend on C, so a query's answer is the same bit for bit in whatever chunk it travels.
 //   k_qb_seed_keys / sort / k_qb_seed   (update queries only) the rows of a slot whose user is in the fit: the user's train
 //                                       rows in file order, then the additional rows
+//   k_qb_mark / k_qb_seed_keys_rv / sort / k_qb_seed_rv   (revise queries with removals, instead) the removed items are
+//                                       found in the user's train row and marked; the marked rows sort behind the slot's
+//                                       live rows, and the slot takes its declared number of rows from the front
+//   k_qb_gone (after k_qb_prep) / k_qb_gone_rated (after k_qb_pred)   (revise) removed items that nobody else rates have
+//                                       left aug: not candidates, counted with the slot's known items
 //   k_qb_keys / sort (slot, trie key) / k_qb_prep / k_qb_rank / k_qb_scatter   query prep, one workgroup per slot: dense
 //                                       items, mean, deviations, hash-ordered norm, preprocessed values, a dense-item
 //                                       bitmap with rank prefixes
@@ -41,6 +46,8 @@ static constexpr int ONE_BLOCK = 1024;
 static constexpr int64_t SIM_LDS_WORDS = 4096;
 // the predictor answers aug's global average for a user mean < 0 (:571-574): not served by a fold-in query
 static constexpr uint32_t ST_NEG_MEAN = QUERY_ST_NEG_MEAN;
+// revise queries: a removed item that is no train item of the user / that is listed twice
+static constexpr uint32_t ST_RM_UNRATED = QUERY_ST_RM_UNRATED, ST_RM_TWICE = QUERY_ST_RM_TWICE;
 
 // one workgroup: exclusive prefix of cnt(i) over i < m (cnt = popcount of a bitmap word, or a neighbour's row length);
 // out[m] = the total, which every thread returns
@@ -228,6 +235,108 @@ __global__ void k_qb_seed(int64_t n, int32_t C, const int64_t* __restrict__ qo, 
         items[j] = add_items[ao[b] + (r - tl)];
         ratings[j] = add_ratings[ao[b] + (r - tl)];
     }
+}
+
+// ---- revise queries (knncf_revise_*): an update query that also REMOVES train rows of the user.  rm_items rows [ro[b],
+// ro[b + 1]) are the raw items slot b drops.  The slot's SOURCE rows [so[b], so[b + 1]) are all its train rows followed by
+// its additional rows; the host declares qo[b + 1] - qo[b] = source rows - removed items, which is right when every removal
+// names a different train row of the user.
+// One thread per removed item: raw -> dense item through the fit's tables (as k_qb_keys), binary search in the user's s_col
+// row (sorted by dense item), mark[source row] = 1.  Not found: ST_RM_UNRATED; marked before: ST_RM_TWICE.  gone[j] = the
+// dense item when the user was its only train rater (it may leave aug: k_qb_gone), else -1.
+__global__ void k_qb_mark(int64_t m, int32_t C, const int64_t* __restrict__ ro, const int64_t* __restrict__ so,
+                          const int32_t* __restrict__ self, const int32_t* __restrict__ rm_items,
+                          const int32_t* __restrict__ i_table, int32_t i_cells, const uint32_t* __restrict__ ikeys, int32_t I,
+                          const int64_t* __restrict__ u_ptr, const int32_t* __restrict__ s_col, const int64_t* __restrict__ i_ptr,
+                          uint32_t* __restrict__ mark, int32_t* __restrict__ rm_slot, int32_t* __restrict__ gone,
+                          long long* __restrict__ info) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const int32_t b = qb_slot(ro, C, j), sd = self[b], it = rm_items[j];
+    rm_slot[j] = b;
+    gone[j] = -1;
+    int32_t d;
+    if (i_cells > 0) d = (it >= 0 && it < i_cells) ? i_table[it] : -1;
+    else d = dense_lookup(ikeys, I, it);
+    int64_t at = -1;
+    if (sd >= 0 && d >= 0) {
+        const int64_t p0 = u_ptr[sd];
+        int64_t lo = p0, hi = u_ptr[sd + 1];
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (s_col[mid] < d) lo = mid + 1;
+            else hi = mid;
+        }
+        if (lo < u_ptr[sd + 1] && s_col[lo] == d) at = lo - p0;
+    }
+    unsigned long long* st = (unsigned long long*)(info + 4 * b);
+    if (at < 0) {
+        atomicOr(st, (unsigned long long)ST_RM_UNRATED);
+    } else if (atomicExch(mark + so[b] + at, 1u) != 0u) {
+        atomicOr(st, (unsigned long long)ST_RM_TWICE);
+    } else if (i_ptr[d + 1] - i_ptr[d] == 1) {
+        gone[j] = d;
+    }
+}
+
+// k_qb_seed_keys over the SOURCE rows: a marked train row gets the bit above the in-slot order, so a slot's rows sort as
+// [live train rows by file row, additional rows, dropped train rows]
+__global__ void k_qb_seed_keys_rv(int64_t ns, int32_t C, const int64_t* __restrict__ so, const int32_t* __restrict__ self,
+                                  const int64_t* __restrict__ u_ptr, const uint32_t* __restrict__ s_t,
+                                  const uint32_t* __restrict__ mark, uint64_t* __restrict__ key, uint32_t* __restrict__ val) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= ns) return;
+    const int32_t b = qb_slot(so, C, j), sd = self[b];
+    const int64_t r = j - so[b], p0 = sd >= 0 ? u_ptr[sd] : 0, tl = sd >= 0 ? u_ptr[sd + 1] - p0 : 0;
+    const uint64_t in_slot = r < tl ? (uint64_t)s_t[p0 + r] : ((1ull << 32) | (uint64_t)(r - tl));
+    const uint64_t dropped = (r < tl && mark[j] != 0u) ? 1ull : 0ull;
+    key[j] = ((uint64_t)(uint32_t)b << 34) | (dropped << 33) | in_slot;
+    val[j] = (uint32_t)j;
+}
+
+// k_qb_seed for chunk row j of slot b: the (j - qo[b])-th of the slot's sorted source rows.  At most (removed items) rows
+// of a slot are marked, so the slot's first qo[b + 1] - qo[b] sorted rows are live ones whatever the removals were, and
+// they lie inside [so[b], so[b + 1]): a slot with a bad removal (its status bit is set) reads its own rows and writes its
+// own extent only.
+__global__ void k_qb_seed_rv(int64_t n, int32_t C, const int64_t* __restrict__ qo, const int64_t* __restrict__ so,
+                             const int64_t* __restrict__ ao, const int32_t* __restrict__ self, const int64_t* __restrict__ u_ptr,
+                             const int32_t* __restrict__ s_col, const double* __restrict__ s_rating, const int32_t* __restrict__ iid,
+                             const int32_t* __restrict__ add_items, const double* __restrict__ add_ratings,
+                             const uint32_t* __restrict__ sval, int32_t* __restrict__ items, double* __restrict__ ratings) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const int32_t b = qb_slot(qo, C, j), sd = self[b];
+    const int64_t r = (int64_t)sval[so[b] + (j - qo[b])] - so[b], p0 = sd >= 0 ? u_ptr[sd] : 0, tl = sd >= 0 ? u_ptr[sd + 1] - p0 : 0;
+    if (r < tl) {
+        items[j] = iid[s_col[p0 + r]];
+        ratings[j] = s_rating[p0 + r];
+    } else {
+        items[j] = add_items[ao[b] + (r - tl)];
+        ratings[j] = add_ratings[ao[b] + (r - tl)];
+    }
+}
+
+// after k_qb_prep: a removed item whose only train rater was the user has left aug unless an additional row gives it again
+// (its bit of the slot's bitmap).  Such an item is no member of ratings.map(_.item).toSet :667: info[4 b + 1] counts it
+// with the slot's known items (k_qb_take and the host take I - info[4 b + 1] candidates), gone[j] keeps it for k_qb_gone_rated
+__global__ void k_qb_gone(int64_t m, int64_t W, const int32_t* __restrict__ rm_slot, int32_t* __restrict__ gone,
+                          const unsigned long long* __restrict__ bits, long long* __restrict__ info) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const int32_t d = gone[j];
+    if (d < 0) return;
+    const int32_t b = rm_slot[j];
+    if ((bits[(int64_t)b * W + (d >> 6)] >> (d & 63)) & 1ull) gone[j] = -1;
+    else atomicAdd((unsigned long long*)(info + 4 * b + 1), 1ull);
+}
+
+// after k_qb_pred: the items that left aug sort with the rated ones, behind every candidate
+__global__ void k_qb_gone_rated(int64_t m, int32_t I, const int32_t* __restrict__ rm_slot, const int32_t* __restrict__ gone,
+                                uint8_t* __restrict__ rated) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const int32_t d = gone[j];
+    if (d >= 0) rated[(int64_t)rm_slot[j] * I + d] = 1;
 }
 
 // the user's own cell of [C][U] gets the last key of all (the bit pattern no similarity has), so it sorts behind every other
@@ -562,7 +671,8 @@ static const uint32_t* qb_segmented_sort(QueryBatchScratch& bs, SortWorkspace& w
 
 void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, const int32_t* h_users,
                             const int64_t* h_qo, const int32_t* h_items, const double* h_ratings, const int32_t* h_self,
-                            const int64_t* h_ao, int32_t k, long long* h_info, hipStream_t st) {
+                            const int64_t* h_ao, int32_t k, long long* h_info, hipStream_t st, const int64_t* h_ro,
+                            const int32_t* h_removed) {
     const int32_t U = tr.U, I = tr.I;
     const int64_t W = ceil_div(I, 64), n = h_qo[C];
     const int64_t cells = (int64_t)C * std::max(U, I);
@@ -571,7 +681,10 @@ void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspac
     bs.items.ensure(n); bs.ratings.ensure(n); bs.slot.ensure(n); bs.di.ensure(n); bs.dev.ensure(n); bs.pre.ensure(n);
     bs.pre_d.ensure(n); bs.dev_d.ensure(n); bs.given_d.ensure(n);
     bs.bits.ensure((size_t)C * W); bs.rank.ensure((size_t)C * (W + 1));
-    const int64_t keys = std::max<int64_t>(n, cells);
+    // revise queries: the removed items of the chunk; a chunk without any is an update chunk
+    const int64_t nrm = (h_self && h_ro) ? h_ro[C] : 0;
+    bs.n_removed = nrm;
+    const int64_t keys = std::max<int64_t>(n + nrm, cells);
     bs.k64_a.ensure(keys); bs.k64_b.ensure(keys); bs.v32_a.ensure(keys); bs.v32_b.ensure(keys);
     bs.s32_a.ensure(cells); bs.s32_b.ensure(cells);
     bs.sim.ensure((size_t)C * U);
@@ -582,6 +695,9 @@ void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspac
     // one upload of the chunk
     KN_HIP(hipMemcpyAsync(bs.users.p, h_users, (size_t)C * sizeof(int32_t), hipMemcpyHostToDevice, st));
     KN_HIP(hipMemcpyAsync(bs.qo.p, h_qo, ((size_t)C + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    // (the status words are cleared before the seeding: k_qb_mark sets bits in them)
+    KN_HIP(hipMemsetAsync(bs.info.p, 0, (size_t)4 * C * sizeof(int64_t), st));
+    long long* info = (long long*)bs.info.p;
     const int32_t* self = nullptr;
     if (!h_self) {
         KN_HIP(hipMemcpyAsync(bs.items.p, h_items, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -598,22 +714,45 @@ void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspac
             KN_HIP(hipMemcpyAsync(bs.add_ratings.p, h_ratings, (size_t)na * sizeof(double), hipMemcpyHostToDevice, st));
         }
         self = bs.self.p;
-        k_qb_seed_keys<<<(unsigned)ceil_div(n, TPB), TPB, 0, st>>>(n, C, bs.qo.p, self, tr.u_ptr.p, tr.s_t.p, bs.k64_a.p, bs.v32_a.p);
-        sort_pairs_u64_u32(ws, bs.k64_a.p, bs.k64_b.p, bs.v32_a.p, bs.v32_b.p, (size_t)n, 33 + (C > 1 ? bits_for((uint64_t)(C - 1)) : 0), st);
-        k_qb_seed<<<(unsigned)ceil_div(n, TPB), TPB, 0, st>>>(n, C, bs.qo.p, bs.ao.p, self, tr.u_ptr.p, tr.s_col.p, tr.s_rating.p,
-                                                              tr.iid.p, bs.add_items.p, bs.add_ratings.p, bs.v32_b.p, bs.items.p,
-                                                              bs.ratings.p);
+        const int slot_bits = C > 1 ? bits_for((uint64_t)(C - 1)) : 0;
+        if (nrm == 0) {
+            k_qb_seed_keys<<<(unsigned)ceil_div(n, TPB), TPB, 0, st>>>(n, C, bs.qo.p, self, tr.u_ptr.p, tr.s_t.p, bs.k64_a.p, bs.v32_a.p);
+            sort_pairs_u64_u32(ws, bs.k64_a.p, bs.k64_b.p, bs.v32_a.p, bs.v32_b.p, (size_t)n, 33 + slot_bits, st);
+            k_qb_seed<<<(unsigned)ceil_div(n, TPB), TPB, 0, st>>>(n, C, bs.qo.p, bs.ao.p, self, tr.u_ptr.p, tr.s_col.p, tr.s_rating.p,
+                                                                  tr.iid.p, bs.add_items.p, bs.add_ratings.p, bs.v32_b.p, bs.items.p,
+                                                                  bs.ratings.p);
+        } else {
+            // source rows of slot b: every train row of its user + its additional rows = its declared rows + its removed items
+            std::vector<int64_t>& so = bs.h_so;  // (outlives the asynchronous upload)
+            so.assign((size_t)C + 1, 0);
+            for (int32_t b = 0; b < C; ++b) so[b + 1] = so[b] + (h_qo[b + 1] - h_qo[b]) + (h_ro[b + 1] - h_ro[b]);
+            const int64_t ns = so[C];  // == n + nrm
+            bs.ro.ensure((size_t)C + 1); bs.so.ensure((size_t)C + 1);
+            bs.rm_items.ensure(nrm); bs.rm_slot.ensure(nrm); bs.rm_gone.ensure(nrm); bs.rm_mark.ensure(ns);
+            KN_HIP(hipMemcpyAsync(bs.ro.p, h_ro, ((size_t)C + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+            KN_HIP(hipMemcpyAsync(bs.so.p, so.data(), ((size_t)C + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+            KN_HIP(hipMemcpyAsync(bs.rm_items.p, h_removed, (size_t)nrm * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            KN_HIP(hipMemsetAsync(bs.rm_mark.p, 0, (size_t)ns * sizeof(uint32_t), st));
+            k_qb_mark<<<(unsigned)ceil_div(nrm, TPB), TPB, 0, st>>>(nrm, C, bs.ro.p, bs.so.p, self, bs.rm_items.p, tr.i_table.p,
+                                                                    table_cells(tr), tr.ikeys.p, I, tr.u_ptr.p, tr.s_col.p, tr.i_ptr.p,
+                                                                    bs.rm_mark.p, bs.rm_slot.p, bs.rm_gone.p, info);
+            k_qb_seed_keys_rv<<<(unsigned)ceil_div(ns, TPB), TPB, 0, st>>>(ns, C, bs.so.p, self, tr.u_ptr.p, tr.s_t.p, bs.rm_mark.p,
+                                                                           bs.k64_a.p, bs.v32_a.p);
+            sort_pairs_u64_u32(ws, bs.k64_a.p, bs.k64_b.p, bs.v32_a.p, bs.v32_b.p, (size_t)ns, 34 + slot_bits, st);
+            k_qb_seed_rv<<<(unsigned)ceil_div(n, TPB), TPB, 0, st>>>(n, C, bs.qo.p, bs.so.p, bs.ao.p, self, tr.u_ptr.p, tr.s_col.p,
+                                                                     tr.s_rating.p, tr.iid.p, bs.add_items.p, bs.add_ratings.p,
+                                                                     bs.v32_b.p, bs.items.p, bs.ratings.p);
+        }
     }
     KN_HIP(hipMemsetAsync(bs.bits.p, 0, (size_t)C * W * sizeof(uint64_t), st));
-    KN_HIP(hipMemsetAsync(bs.info.p, 0, (size_t)4 * C * sizeof(int64_t), st));
     unsigned long long* bits = (unsigned long long*)bs.bits.p;
-    long long* info = (long long*)bs.info.p;
     // query prep
     k_qb_keys<<<(unsigned)ceil_div(n, TPB), TPB, 0, st>>>(n, C, bs.qo.p, bs.users.p, bs.items.p, tr.i_table.p, table_cells(tr),
                                                           tr.ikeys.p, I, bs.slot.p, bs.di.p, bs.k64_a.p, bs.v32_a.p);
     sort_pairs_u64_u32(ws, bs.k64_a.p, bs.k64_b.p, bs.v32_a.p, bs.v32_b.p, (size_t)n, 32 + (C > 1 ? bits_for((uint64_t)(C - 1)) : 0), st);
     k_qb_prep<<<C, ONE_BLOCK, 0, st>>>(bs.qo.p, bs.ratings.p, bs.k64_b.p, bs.v32_b.p, bs.di.p, W, bs.dev.p, bs.pre.p, bits, info,
                                        bs.scal.p);
+    if (nrm > 0) k_qb_gone<<<(unsigned)ceil_div(nrm, TPB), TPB, 0, st>>>(nrm, W, bs.rm_slot.p, bs.rm_gone.p, bits, info);
     k_qb_rank<<<C, ONE_BLOCK, 0, st>>>(W, bits, bs.rank.p);
     k_qb_scatter<<<(unsigned)ceil_div(n, TPB), TPB, 0, st>>>(n, bs.qo.p, bs.slot.p, bs.di.p, bs.pre.p, bs.dev.p, W, bits, bs.rank.p,
                                                              bs.pre_d.p, bs.dev_d.p, bs.given_d.p);
@@ -679,6 +818,8 @@ void foldin_batch_predictions(const Train& tr, QueryBatchScratch& bs, SortWorksp
     }
     k_qb_pred<<<(unsigned)ceil_div(cells, TPB), TPB, 0, st>>>(C, I, W, bs.num.p, bs.den.p, (const unsigned long long*)bs.bits.p,
                                                               bs.rank.p, bs.qo.p, bs.dev_d.p, bs.scal.p, bs.pred.p, bs.rated.p);
+    if (bs.n_removed > 0)
+        k_qb_gone_rated<<<(unsigned)ceil_div(bs.n_removed, TPB), TPB, 0, st>>>(bs.n_removed, I, bs.rm_slot.p, bs.rm_gone.p, bs.rated.p);
     KN_HIP(hipGetLastError());
 }
 

@@ -120,7 +120,9 @@ EXPORTS = [
     "knncf_query_neighbors", "knncf_query_predict", "knncf_query_recommend",
     "knncf_query_neighbors_batch", "knncf_query_predict_batch", "knncf_query_recommend_batch",
     "knncf_update_neighbors", "knncf_update_predict", "knncf_update_recommend",
-    "knncf_update_neighbors_batch", "knncf_update_predict_batch", "knncf_update_recommend_batch", "knncf_predict_batch",
+    "knncf_update_neighbors_batch", "knncf_update_predict_batch", "knncf_update_recommend_batch",
+    "knncf_revise_neighbors", "knncf_revise_predict", "knncf_revise_recommend",
+    "knncf_revise_neighbors_batch", "knncf_revise_predict_batch", "knncf_revise_recommend_batch", "knncf_predict_batch",
     "knncf_predict_batch_device", "knncf_mae", "knncf_mae_device", "knncf_mae_sweep", "knncf_mae_sweep_device", "knncf_shard_view_get",
     "knncf_shard_commit", "knncf_get_timings", "knncf_reset_timings", "knncf_reset_neighbors",
     "knncf_set_k", "knncf_load_file", "knncf_load_file_cached", "knncf_free_ratings", "knncf_load_personal", "knncf_free_personal", "knncf_neighbors_save", "knncf_neighbors_load",
@@ -209,6 +211,11 @@ def load_library():
         f("predict_batch").argtypes = [C.c_void_p, C.c_int, _i32p, _i64p, _i32p, _f64p, C.c_int64, _i64p, _i32p, _f64p, _i32p]
         f("recommend_batch").argtypes = [C.c_void_p, C.c_int, _i32p, _i64p, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p,
                                          _i32p, _i32p]
+    # revise queries: the update argument lists with the removals in front of the additional rows
+    for name, at, single in (("neighbors", 2, True), ("predict", 3, True), ("recommend", 3, True),
+                             ("neighbors_batch", 2, False), ("predict_batch", 3, False), ("recommend_batch", 3, False)):
+        base = getattr(L, f"knncf_update_{name}").argtypes
+        getattr(L, f"knncf_revise_{name}").argtypes = base[:at] + ([_i32p, C.c_int64] if single else [_i64p, _i32p]) + base[at:]
     L.knncf_predict_batch.argtypes = [C.c_void_p, C.c_int, _i32p, _i32p, C.c_int64, _f64p]
     L.knncf_predict_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.knncf_mae.argtypes = [C.c_void_p, C.c_int, _i32p, _i32p, _f64p, C.c_int64, _f64p]
@@ -448,8 +455,28 @@ class Engine:
     def _ptr(a, t):
         return a.ctypes.data_as(t) if len(a) else C.cast(None, t)
 
-    def _neighbors_q(self, fam, user, items, ratings, cap):
-        q, it, rt = self._query_rows(user, items, ratings, allow_empty=fam == "update")
+    @staticmethod
+    def _removed(removed):
+        """validated removed item ids of a revise query: ValueError before any C call"""
+        rm = np.asarray(removed)
+        if rm.ndim != 1:
+            raise ValueError("removed items must be 1-D")
+        if len(rm) == 0:
+            return np.empty(0, dtype=np.int32)
+        if rm.dtype.kind not in "iu" or rm.min() < -2**31 or rm.max() >= 2**31:
+            raise ValueError("removed items must be 32-bit integer ids")
+        return _i32(rm)
+
+    def _rm_args(self, fam, removed):
+        """the removals of a single revise call as C arguments (nothing for the other families)"""
+        if fam != "revise":
+            return ()
+        rm = self._removed(removed)
+        return (self._ptr(rm, _i32p), len(rm))
+
+    def _neighbors_q(self, fam, user, items, ratings, cap, removed=None):
+        q, it, rt = self._query_rows(user, items, ratings, allow_empty=fam != "query")
+        rm = self._rm_args(fam, removed)
         if cap is None:
             cap = max(1, self.k)
         if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or cap < 0:
@@ -459,25 +486,27 @@ class Engine:
         sims = np.empty(max(1, cap), dtype=np.float64)
         c = C.c_int32()
         p = self._ptr
-        self._check(getattr(self._lib, f"knncf_{fam}_neighbors")(self._h, q, p(it, _i32p), p(rt, _f64p), len(it), cap,
+        self._check(getattr(self._lib, f"knncf_{fam}_neighbors")(self._h, q, *rm, p(it, _i32p), p(rt, _f64p), len(it), cap,
                                                                  ids.ctypes.data_as(_i32p), sims.ctypes.data_as(_f64p), C.byref(c)))
         m = min(c.value, cap)
         return ids[:m].copy(), sims[:m].copy()
 
-    def _predict_q(self, fam, user, items, ratings, pred_items):
-        q, it, rt = self._query_rows(user, items, ratings, allow_empty=fam == "update")
+    def _predict_q(self, fam, user, items, ratings, pred_items, removed=None):
+        q, it, rt = self._query_rows(user, items, ratings, allow_empty=fam != "query")
+        rm = self._rm_args(fam, removed)
         pi = np.asarray(pred_items)
         if pi.ndim != 1 or (len(pi) and pi.dtype.kind not in "iu"):
             raise ValueError("pred_items must be a 1-D array of integer ids")
         pi = _i32(pi)
         out = np.empty(max(1, len(pi)), dtype=np.float64)
         p = self._ptr
-        self._check(getattr(self._lib, f"knncf_{fam}_predict")(self._h, PRED_KNN, q, p(it, _i32p), p(rt, _f64p), len(it),
+        self._check(getattr(self._lib, f"knncf_{fam}_predict")(self._h, PRED_KNN, q, *rm, p(it, _i32p), p(rt, _f64p), len(it),
                                                                pi.ctypes.data_as(_i32p), len(pi), out.ctypes.data_as(_f64p)))
         return out[:len(pi)].copy()
 
-    def _recommend_q(self, fam, user, items, ratings, n):
-        q, it, rt = self._query_rows(user, items, ratings, allow_empty=fam == "update")
+    def _recommend_q(self, fam, user, items, ratings, n, removed=None):
+        q, it, rt = self._query_rows(user, items, ratings, allow_empty=fam != "query")
+        rm = self._rm_args(fam, removed)
         if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0 or n >= 2**31:
             raise ValueError("n must be a non-negative 32-bit integer")
         n = int(n)
@@ -485,7 +514,7 @@ class Engine:
         preds = np.empty(max(1, n), dtype=np.float64)
         c = C.c_int32()
         p = self._ptr
-        self._check(getattr(self._lib, f"knncf_{fam}_recommend")(self._h, PRED_KNN, q, p(it, _i32p), p(rt, _f64p), len(it), n,
+        self._check(getattr(self._lib, f"knncf_{fam}_recommend")(self._h, PRED_KNN, q, *rm, p(it, _i32p), p(rt, _f64p), len(it), n,
                                                                  ids.ctypes.data_as(_i32p), preds.ctypes.data_as(_f64p), C.byref(c)))
         return ids[:c.value].copy(), preds[:c.value].copy()
 
@@ -514,7 +543,40 @@ class Engine:
         """recommendations(train ++ the additional ratings, kNN predictor)(user, n) for any user: (item ids, predictions)"""
         return self._recommend_q("update", user, items, ratings, n)
 
-    # ---- batched forms (knncf_query_*_batch, knncf_update_*_batch) ------------------------------
+    def neighbors_revised(self, user, removed, items, ratings, cap=None):
+        """getNeighbors(aug, k, sim)(user) where aug is train without the user's rows on the `removed` items, plus the additional
+        (items, ratings): (ids, sims).  An item both removed and given again is re-rated."""
+        return self._neighbors_q("revise", user, items, ratings, cap, removed)
+
+    def predict_revised(self, user, removed, items, ratings, pred_items):
+        """kNN predictions (PRED_KNN) of a user that removed the `removed` train items and rated (items, ratings) in addition"""
+        return self._predict_q("revise", user, items, ratings, pred_items, removed)
+
+    def recommend_revised(self, user, removed, items, ratings, n):
+        """recommendations(aug, kNN predictor)(user, n) on that aug: (item ids, predictions)"""
+        return self._recommend_q("revise", user, items, ratings, n, removed)
+
+    # ---- batched forms (knncf_query_*_batch, knncf_update_*_batch, knncf_revise_*_batch) --------
+    def _batch_args(self, fam, queries):
+        """the validated queries of a batched call as C arguments: users, [the CSR of the removals,] the CSR of the rows, B"""
+        p = self._ptr
+        if fam != "revise":
+            us, off, it, rt = self._query_batch(queries)
+            return (p(us, _i32p), p(off, _i64p), p(it, _i32p), p(rt, _f64p), len(us)), (us, off, it, rt)
+        rms, roff, triples = [], [0], []
+        for q in queries:
+            if not isinstance(q, (tuple, list)) or len(q) != 4:
+                raise ValueError("a revise query is (user, removed_items, items, ratings)")
+            rms.append(self._removed(q[1]))
+            roff.append(roff[-1] + len(rms[-1]))
+            triples.append((q[0], q[2], q[3]))
+        if roff[-1] >= 2**31:
+            raise ValueError("fewer than 2^31 removed items per call")
+        us, off, it, rt = self._query_batch(triples)
+        roff = np.asarray(roff, dtype=np.int64)
+        rm = np.ascontiguousarray(np.concatenate(rms) if rms else np.empty(0), dtype=np.int32)
+        return (p(us, _i32p), p(roff, _i64p), p(rm, _i32p), p(off, _i64p), p(it, _i32p), p(rt, _f64p), len(us)), (us, roff, rm, off, it, rt)
+
     @staticmethod
     def _query_batch(queries):
         """validated CSR (users, offsets, items, ratings) of a sequence of (user, items, ratings): ValueError before any C
@@ -545,25 +607,25 @@ class Engine:
         return (np.asarray(users, dtype=np.int32), np.asarray(offsets, dtype=np.int64), cat(its, np.int32), cat(rts, np.float64))
 
     def _neighbors_qb(self, fam, queries, cap):
-        us, off, it, rt = self._query_batch(queries)
+        qargs, keep = self._batch_args(fam, queries)
         if cap is None:
             cap = max(1, self.k)
         if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or cap < 0:
             raise ValueError("cap must be a non-negative integer")
-        cap, B = int(cap), len(us)
+        cap, B = int(cap), qargs[-1]
         ids = np.empty((B, cap), dtype=np.int32)
         sims = np.empty((B, cap), dtype=np.float64)
         counts = np.zeros(B, dtype=np.int32)
         st = np.zeros(B, dtype=np.int32)
         p = self._ptr
         self._check(getattr(self._lib, f"knncf_{fam}_neighbors_batch")(
-            self._h, p(us, _i32p), p(off, _i64p), p(it, _i32p), p(rt, _f64p), B, cap, p(ids.reshape(-1), _i32p),
+            self._h, *qargs, cap, p(ids.reshape(-1), _i32p),
             p(sims.reshape(-1), _f64p), p(counts, _i32p), p(st, _i32p)))
         return [(ids[b, :min(counts[b], cap)].copy(), sims[b, :min(counts[b], cap)].copy()) for b in range(B)], st
 
     def _predict_qb(self, fam, queries, pred_items):
-        us, off, it, rt = self._query_batch(queries)
-        B = len(us)
+        qargs, keep = self._batch_args(fam, queries)
+        B = qargs[-1]
         pis = [np.asarray(x) for x in pred_items]
         if len(pis) != B:
             raise ValueError("one pred_items sequence per query")
@@ -577,22 +639,22 @@ class Engine:
         st = np.zeros(B, dtype=np.int32)
         p = self._ptr
         self._check(getattr(self._lib, f"knncf_{fam}_predict_batch")(
-            self._h, PRED_KNN, p(us, _i32p), p(off, _i64p), p(it, _i32p), p(rt, _f64p), B, p(poff, _i64p), p(pi, _i32p),
+            self._h, PRED_KNN, *qargs, p(poff, _i64p), p(pi, _i32p),
             p(out, _f64p), p(st, _i32p)))
         return [out[poff[b]:poff[b + 1]].copy() for b in range(B)], st
 
     def _recommend_qb(self, fam, queries, n):
-        us, off, it, rt = self._query_batch(queries)
+        qargs, keep = self._batch_args(fam, queries)
         if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0 or n >= 2**31:
             raise ValueError("n must be a non-negative 32-bit integer")
-        n, B = int(n), len(us)
+        n, B = int(n), qargs[-1]
         ids = np.empty((B, n), dtype=np.int32)
         preds = np.empty((B, n), dtype=np.float64)
         counts = np.zeros(B, dtype=np.int32)
         st = np.zeros(B, dtype=np.int32)
         p = self._ptr
         self._check(getattr(self._lib, f"knncf_{fam}_recommend_batch")(
-            self._h, PRED_KNN, p(us, _i32p), p(off, _i64p), p(it, _i32p), p(rt, _f64p), B, n, p(ids.reshape(-1), _i32p),
+            self._h, PRED_KNN, *qargs, n, p(ids.reshape(-1), _i32p),
             p(preds.reshape(-1), _f64p), p(counts, _i32p), p(st, _i32p)))
         return [(ids[b, :counts[b]].copy(), preds[b, :counts[b]].copy()) for b in range(B)], st
 
@@ -623,6 +685,20 @@ class Engine:
     def recommend_with_batch(self, queries, n):
         """recommend_with(n) of every query: ([(item ids, predictions)] per query, statuses).  A failed query has empty arrays."""
         return self._recommend_qb("update", queries, n)
+
+    def neighbors_revised_batch(self, queries, cap=None):
+        """neighbors_revised of every (user, removed_items, additional items, additional ratings) of `queries`:
+        ([(ids, sims)] per query, statuses int32 [B]).  A failed query (status != OK) has empty arrays."""
+        return self._neighbors_qb("revise", queries, cap)
+
+    def predict_revised_batch(self, queries, pred_items):
+        """predict_revised of every query; pred_items is one sequence of item ids per query: ([float64 array] per query, statuses).
+        A failed query's array holds NaN."""
+        return self._predict_qb("revise", queries, pred_items)
+
+    def recommend_revised_batch(self, queries, n):
+        """recommend_revised(n) of every query: ([(item ids, predictions)] per query, statuses).  A failed query has empty arrays."""
+        return self._recommend_qb("revise", queries, n)
 
     # ---- batch -------------------------------------------------------------------------
     def predict_batch(self, predictor, users, items):
