@@ -331,7 +331,7 @@ void build_neighbors(knncf_handle* h, int32_t count) {
     KN_REQUIRE(h->cfg.similarity != KNNCF_SIM_ONE, KNNCF_E_UNSUPPORTED,
                "kNN neighbourhoods with similarityOne: every similarity is 1.0, the neighbourhood is the first k users in Set order — not built");
     hipStream_t st = h->stream;
-    if (count > 256) {
+    if (count > 256) {  // (tests/test_boundary_premises.py holds this 256 and the `count * 2 >= U` below as literals: move together)
         // longest rows first (LPT): one workgroup per row in select and re-rank, and the row lengths are heavy-tailed
         // (ml-25m shape: mean 123 ratings, maximum 7485) — a long row dispatched last holds the launch open alone.
         // The order of the list carries no meaning (the users' build sequence numbers are already assigned).
@@ -360,6 +360,7 @@ void build_neighbors(knncf_handle* h, int32_t count) {
     // 53 GB panel in its second build and spent 1.5 s re-allocating)
     size_t own = h->S_full.bytes() + h->sel.cand_idx.bytes() + h->sel.cand_approx.bytes() + h->sel.grp_v0.bytes() + h->sel.grp_x.bytes();
     for (int s = 0; s < 2; ++s) own += h->S[s].bytes() + h->Apanel[s].bytes();
+    // (`count * 2 >= U`: a literal of tests/test_boundary_premises.py — move together)
     bool use_sym = h->cfg.shard_count == 1 && (int64_t)count * 2 >= tr.U && U_pad / 256 < 65536 &&
                    sym_bytes <= (free_b + own) / 3 && !getenv("KNNCF_DEBUG_NO_SYMMETRIC_GEMM");
     if (use_sym) {

@@ -14,6 +14,7 @@ typedef __bf16 bf16_t;
 // columns of a similarity row that select.hip holds in LDS at a time (prep.hip tabulates the tile crossings)
 // provisional store of select.hip per similarity row: groups of 8 columns (36 B each); the capacity scales with k
 inline int32_t select_gcap(int32_t k) { return 8192 * (int32_t)((k + 511) / 512 > 1 ? (k + 511) / 512 : 1); }
+// (SELECT_TCOLS appears as a literal in tests/test_boundary_premises.py and tests/boundary_shapes.py: move together)
 static constexpr int SELECT_TCOLS = 16384;  // <= 2^14: it_pack keeps the BYTE address of the column's LDS cell inside its tile in 16 bits
 static_assert(SELECT_TCOLS <= 16384 && (SELECT_TCOLS & (SELECT_TCOLS - 1)) == 0, "it_pack: 16-bit cell byte address");
 

@@ -53,6 +53,7 @@ static constexpr int TCOLS = SELECT_TCOLS;  // columns of the row held in LDS at
 static constexpr int CPT = TCOLS / TPB;  // columns per thread per tile (32 = 4 groups of 8)
 static constexpr int NG = CPT / 8;
 static_assert(CPT <= 32, "the survivor mask of a thread is one 32-bit word");
+// (EMAX, PMAX and MAXT appear as literals in tests/test_boundary_premises.py, whose cases sit on them: move together)
 static constexpr int EMAX = 256;     // row positions whose tail entries (16 B each) are held in LDS at a time
 static constexpr int PMAX = 1024;          // pieces per (chunk, tile) with a direct piece -> entry table in LDS (more: a binary search)
 static constexpr int MAXT = 12;            // tiles whose per-entry rater counts are packed into registers (12 x 16 384 columns: up to 196 608 users)
