@@ -205,6 +205,50 @@ int knncf_recommend(knncf_handle* h, int predictor, int32_t user, int32_t n, int
 int knncf_recommend_batch(knncf_handle* h, int predictor, const int32_t* users, int64_t n_users, int32_t n,
                           int32_t* out_items, double* out_preds, int32_t* counts);
 
+/* ---- Explanations: the neighbour terms behind KNNCF_PRED_KNN predictions ---------------------------------------------------
+ * A kNN prediction is a short sum over the neighbours who rated the item: weightedSumDeviation shared/predictions.scala:504-548
+ * maps the item's raters x, in training file order, to simVal :513-517 and folds (num + dev * sim, den + |sim|) from
+ * (0.0, 0.0) :520-524.  The TERMS of row j = (users[j], items[j]) are the elements of simVal whose similarity is non-zero, each
+ * with three parts: the rater's raw id x.user, getSimilarity(train, k, sim)(users[j], x.user) :634-648, and x's normalized
+ * deviation on the item.  A neighbour of the list whose similarity is exactly 0.0 (k >= num_users - 1, disjoint users) is NOT a
+ * term, and the user is never its own term.
+ * Outputs per row: counts[j] = the number of terms (it may exceed cap); the first min(counts[j], cap) terms, in `order`, in
+ * row j of raters / sims / devs ([n * cap], row stride cap; cells beyond them are left untouched); sums[2 j], sums[2 j + 1] =
+ * num and den of the fold over ALL terms in summation order (independent of order and cap); predictions[j] =
+ * knncf_predict(h, KNNCF_PRED_KNN, users[j], items[j]) bit for bit.  sums and predictions may be null; with cap == 0 the three
+ * term arrays may be null.
+ * Row kinds.  A user unknown to train (or one whose mean is negative, :573): count 0, sums (0, 0), prediction = the global
+ * average.  A known user on an item that is unknown to train or that no neighbour rated: count 0, sums (0, 0), wsd = 0.0
+ * :527-529.
+ * Properties.  With counts[j] <= cap and KNNCF_EXPLAIN_SUM_ORDER the caller's left fold of the returned terms,
+ * (num + devs * sims, den + |sims|) from (0.0, 0.0), gives sums bit for bit (no fused multiply-add).  With ua = knncf_user_avg
+ * and wsd = den > 0 ? num / den : 0.0, the combine :578, ua + wsd * scale(ua + wsd, ua), gives predictions[j] bit for bit.
+ * KNNCF_EXPLAIN_BY_WEIGHT returns a permutation of the same terms.
+ * Handle state.  Neighbourhoods that do not exist yet are built by the call exactly as
+ * knncf_predict_batch(h, KNNCF_PRED_KNN, users, items, n, ...) builds them — once for the whole call, before any chunk — and
+ * THE HANDLE IS LEFT IN THE STATE THAT knncf_predict_batch OVER THE SAME ROWS LEAVES IT IN: the same lists, the same build
+ * numbers, the same knncf_neighbors_save file.  knncf_explain is the batch of one row.  knncf_get_timings: builds are charged
+ * as usual, the explain kernel as predict_ms.
+ * Status: KNNCF_E_STATE before a fit; KNNCF_E_UNSUPPORTED for a KNNCF_SIM_ONE handle (as knncf_predict) and for a shard
+ * handle (shard_count > 1): SHARDED EXPLANATIONS ARE OUT OF SCOPE, as are explanations of fold-in / update / revise queries
+ * and of KNNCF_PRED_PERSONALIZED; KNNCF_E_INVALID for a null pointer that is needed, n < 0, cap < 0, an unknown order or
+ * n >= 2^32 - 1.  n == 0 is KNNCF_OK and touches nothing.  A call that fails these checks builds nothing and writes nothing.
+ * Chunks.  The device form is one pass into the caller's buffers (every pointer on the handle's device, inputs complete at
+ * the call, outputs complete on return).  The host form answers consecutive row ranges [0, C), [C, 2 C), ... through
+ * handle-owned device scratch:
+ *     C = max(1, budget / (20 * cap + 28))
+ *     budget = workspace_bytes / 2 if workspace_bytes > 0, else min(48 GiB, free device memory / 4)
+ * The results do not depend on C, and a call on a handle that has answered the same shape before allocates no device memory. */
+#define KNNCF_EXPLAIN_SUM_ORDER 0  /* the order of the fold :520-524 = training file order of the item's raters */
+#define KNNCF_EXPLAIN_BY_WEIGHT 1  /* |similarity| descending, equal magnitudes in summation order */
+int knncf_explain(knncf_handle* h, int32_t user, int32_t item, int32_t order, int32_t cap, int32_t* raters, double* sims,
+                  double* devs, int32_t* count, double* sums, double* prediction);
+int knncf_explain_batch(knncf_handle* h, const int32_t* users, const int32_t* items, int64_t n, int32_t order, int32_t cap,
+                        int32_t* raters, double* sims, double* devs, int32_t* counts, double* sums, double* predictions);
+int knncf_explain_batch_device(knncf_handle* h, const int32_t* d_users, const int32_t* d_items, int64_t n, int32_t order,
+                               int32_t cap, int32_t* d_raters, double* d_sims, double* d_devs, int32_t* d_counts,
+                               double* d_sums, double* d_predictions);
+
 /* ---- fold-in queries: one user that is NOT in the fitted training set ------
  * recommend/Recommender.scala:64-88 appends a person's ratings to the data (data.union(personal), :68) and asks for
  * that person's recommendations.  These calls answer for such a query user `user` (a raw id absent from train) with

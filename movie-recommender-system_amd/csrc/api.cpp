@@ -84,6 +84,9 @@ struct knncf_handle {
     DArr<uint8_t> t_owned;
     DArr<int64_t> t_counts;
     DArr<int32_t> sweep_ks;  // [64] the k values of knncf_mae_sweep*
+    // one chunk of knncf_explain_batch's host form: [C * cap] terms, [C] counts and predictions, [2 C] sums
+    DArr<int32_t> ex_raters, ex_counts;
+    DArr<double> ex_sims, ex_devs, ex_sums, ex_pred;
     // host mirrors for scalar queries
     std::vector<uint32_t> h_ukeys, h_ikeys;
     std::vector<int32_t> h_uid;
@@ -1846,6 +1849,104 @@ int knncf_predict_batch(knncf_handle* h, int predictor, const int32_t* users, co
 
 int knncf_predict(knncf_handle* h, int predictor, int32_t user, int32_t item, double* out) {
     return knncf_predict_batch(h, predictor, &user, &item, 1, out);
+}
+
+// ---- explanations (explain.hip; include/knncf.h "Explanations") ---------------------------------------------------------
+// the refusals of every form, before anything is built or written
+static void explain_require(knncf_handle* h, const void* users, const void* items, int64_t n, int32_t order, int32_t cap,
+                            const void* raters, const void* sims, const void* devs, const void* counts) {
+    require_fitted(h, false);  // (a shard handle is refused below, committed or not)
+    KN_REQUIRE(n >= 0 && cap >= 0, KNNCF_E_INVALID, "explain: n or cap < 0");
+    KN_REQUIRE(order == KNNCF_EXPLAIN_SUM_ORDER || order == KNNCF_EXPLAIN_BY_WEIGHT, KNNCF_E_INVALID, "explain: unknown order");
+    KN_REQUIRE(n < (int64_t)0xffffffffll, KNNCF_E_INVALID, "explain: 2^32-1 rows or more");
+    KN_REQUIRE(h->cfg.similarity != KNNCF_SIM_ONE, KNNCF_E_UNSUPPORTED,
+               "kNN neighbourhoods with similarityOne: every similarity is 1.0, the neighbourhood is the first k users in Set order — not built");
+    KN_REQUIRE(h->cfg.shard_count == 1, KNNCF_E_UNSUPPORTED, "explain: single-shard handles only");
+    KN_REQUIRE(n == 0 || (users && items && counts && (cap == 0 || (raters && sims && devs))), KNNCF_E_INVALID, "explain: null argument");
+}
+
+// what run_predict does in front of its kNN kernel, once for the whole call: the rows' dense ids in t_du / t_di and the
+// neighbourhoods they need, built and numbered by ensure_neighbors_for_rows
+static void explain_prepare(knncf_handle* h, const int32_t* d_users, const int32_t* d_items, int64_t n) {
+    ensure_test_scratch(h, n);
+    {
+        Stage s(h, &h->tm.predict_ms);
+        launch_dense_ids(h->tr, d_users, d_items, n, h->t_du.p, h->t_di.p, h->stream);
+    }
+    ensure_neighbors_for_rows(h, n);
+    h->prep.join_commit(h->stream);  // the item-major copies and the rater bitmaps (second part of prep_commit)
+}
+
+// rows per chunk of knncf_explain_batch: the rule of knncf.h ("Explanations")
+static int64_t explain_batch_chunk(knncf_handle* h, int32_t cap) {
+    int64_t budget = h->cfg.workspace_bytes / 2;
+    if (h->cfg.workspace_bytes <= 0) {
+        size_t free_b = 0, total_b = 0;
+        KN_HIP(hipMemGetInfo(&free_b, &total_b));
+        budget = (int64_t)std::min<size_t>((size_t)48 << 30, free_b / 4);
+    }
+    return std::max<int64_t>(budget / (20 * (int64_t)cap + 28), 1);
+}
+
+int knncf_explain_batch_device(knncf_handle* h, const int32_t* d_users, const int32_t* d_items, int64_t n, int32_t order,
+                               int32_t cap, int32_t* d_raters, double* d_sims, double* d_devs, int32_t* d_counts,
+                               double* d_sums, double* d_predictions) {
+    return guarded(h, [&] {
+        explain_require(h, d_users, d_items, n, order, cap, d_raters, d_sims, d_devs, d_counts);
+        if (n == 0) return;
+        explain_prepare(h, d_users, d_items, n);
+        Stage s(h, &h->tm.predict_ms);
+        launch_explain(h->tr, h->nt, n, h->t_du.p, h->t_di.p, order, cap, d_raters, d_sims, d_devs, d_counts, d_sums, d_predictions,
+                       h->stream);
+    });
+}
+
+int knncf_explain_batch(knncf_handle* h, const int32_t* users, const int32_t* items, int64_t n, int32_t order, int32_t cap,
+                        int32_t* raters, double* sims, double* devs, int32_t* counts, double* sums, double* predictions) {
+    return guarded(h, [&] {
+        explain_require(h, users, items, n, order, cap, raters, sims, devs, counts);
+        if (n == 0) return;
+        hipStream_t st = h->stream;
+        h->t_users.ensure(n); h->t_items.ensure(n);
+        KN_HIP(hipMemcpyAsync(h->t_users.p, users, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        KN_HIP(hipMemcpyAsync(h->t_items.p, items, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        explain_prepare(h, h->t_users.p, h->t_items.p, n);
+        const int64_t chunk = std::min<int64_t>(explain_batch_chunk(h, cap), n);
+        const size_t cells = (size_t)chunk * (size_t)cap;
+        h->ex_raters.ensure(cells); h->ex_sims.ensure(cells); h->ex_devs.ensure(cells);
+        h->ex_counts.ensure(chunk); h->ex_sums.ensure((size_t)2 * chunk); h->ex_pred.ensure(chunk);
+        std::vector<int32_t> h_raters(cells);
+        std::vector<double> h_sims(cells), h_devs(cells);
+        for (int64_t c0 = 0; c0 < n; c0 += chunk) {
+            const int64_t C = std::min<int64_t>(chunk, n - c0);
+            {
+                Stage s(h, &h->tm.predict_ms);
+                launch_explain(h->tr, h->nt, C, h->t_du.p + c0, h->t_di.p + c0, order, cap, h->ex_raters.p, h->ex_sims.p, h->ex_devs.p,
+                               h->ex_counts.p, h->ex_sums.p, h->ex_pred.p, st);
+            }
+            KN_HIP(hipMemcpyAsync(counts + c0, h->ex_counts.p, (size_t)C * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            if (sums) KN_HIP(hipMemcpyAsync(sums + 2 * c0, h->ex_sums.p, (size_t)2 * C * sizeof(double), hipMemcpyDeviceToHost, st));
+            if (predictions) KN_HIP(hipMemcpyAsync(predictions + c0, h->ex_pred.p, (size_t)C * sizeof(double), hipMemcpyDeviceToHost, st));
+            if (cap > 0) {
+                KN_HIP(hipMemcpyAsync(h_raters.data(), h->ex_raters.p, (size_t)C * cap * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+                KN_HIP(hipMemcpyAsync(h_sims.data(), h->ex_sims.p, (size_t)C * cap * sizeof(double), hipMemcpyDeviceToHost, st));
+                KN_HIP(hipMemcpyAsync(h_devs.data(), h->ex_devs.p, (size_t)C * cap * sizeof(double), hipMemcpyDeviceToHost, st));
+            }
+            KN_HIP(hipStreamSynchronize(st));
+            for (int64_t r = 0; r < C && cap > 0; ++r) {  // (the cells of a row beyond its terms stay as the caller left them)
+                const size_t from = (size_t)r * cap, to = (size_t)(c0 + r) * cap;
+                const int32_t m = std::min(counts[c0 + r], cap);
+                std::copy(h_raters.begin() + from, h_raters.begin() + from + m, raters + to);
+                std::copy(h_sims.begin() + from, h_sims.begin() + from + m, sims + to);
+                std::copy(h_devs.begin() + from, h_devs.begin() + from + m, devs + to);
+            }
+        }
+    });
+}
+
+int knncf_explain(knncf_handle* h, int32_t user, int32_t item, int32_t order, int32_t cap, int32_t* raters, double* sims,
+                  double* devs, int32_t* count, double* sums, double* prediction) {
+    return knncf_explain_batch(h, &user, &item, 1, order, cap, raters, sims, devs, count, sums, prediction);
 }
 
 int knncf_recommend(knncf_handle* h, int predictor, int32_t user, int32_t n, int32_t* items, double* predictions, int32_t* count) {

@@ -252,6 +252,15 @@ void launch_owned_keys(int64_t n, const int32_t* d_src, const int32_t* d_du, int
 void launch_reduce_err(const double* d_abs_err, const uint8_t* d_owned, int64_t n, double* d_partials,
                        int64_t* d_counts, int32_t n_blocks, hipStream_t st);
 
+// ---- explain.hip: the neighbour terms behind kNN predictions (knncf_explain*; DESIGN.md "Explanations") ---------------
+// per row (d_du[t], d_di[t]), t < n: d_counts[t] = number of terms (neighbours of the user with a non-zero similarity that
+// rated the item), the first min(count, cap) of them in `order` (KNNCF_EXPLAIN_*) in row t of d_raters / d_sims / d_devs
+// (row stride cap; unused with cap == 0), d_sums[2 t ..] = (num, den) of the fold over all terms and d_pred[t] = the
+// KNNCF_PRED_KNN prediction (either may be null).  nt.kcap <= 2048; makes nt's id-sorted copies when they are not current.
+void launch_explain(const Train& tr, NeighborTable& nt, int64_t n, const int32_t* d_du, const int32_t* d_di, int32_t order,
+                    int32_t cap, int32_t* d_raters, double* d_sims, double* d_devs, int32_t* d_counts, double* d_sums,
+                    double* d_pred, hipStream_t st);
+
 // ---- ksweep.hip: the kNN prediction at several k from one neighbour table (knncf_mae_sweep) ----------------------
 // per test row d_order[0 .. n): the kNN prediction at every k = d_ks[q] (ascending, q < n_k <= 64) from the first k entries of the
 // row user's reference-order list in nt (kcap <= 2048); rows sorted by dense item.  Cell q * n_total + row of d_pred (may be

@@ -21,6 +21,7 @@ FLAG_OVERLAP = 2
 FLAG_BF16_FILTER = 4  # default filter operand type is fp16 (narrower error band, same MFMA rate)
 FLAG_F32_PANEL = 8    # default similarity panel storage is fp16
 HEAD_ALL = 0xFFFFFFFF
+EXPLAIN_SUM_ORDER, EXPLAIN_BY_WEIGHT = 0, 1  # KNNCF_EXPLAIN_*: the order of the terms of Engine.explain*
 
 _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
@@ -117,6 +118,7 @@ EXPORTS = [
     "knncf_fit", "knncf_fit_device", "knncf_num_users", "knncf_num_items", "knncf_global_avg",
     "knncf_user_avg", "knncf_item_avg", "knncf_item_avg_dev", "knncf_item_avg_dev_rdd", "knncf_similarity",
     "knncf_knn_similarity", "knncf_neighbors", "knncf_neighbors_batch", "knncf_predict", "knncf_recommend", "knncf_recommend_batch",
+    "knncf_explain", "knncf_explain_batch", "knncf_explain_batch_device",
     "knncf_query_neighbors", "knncf_query_predict", "knncf_query_recommend",
     "knncf_query_neighbors_batch", "knncf_query_predict_batch", "knncf_query_recommend_batch",
     "knncf_update_neighbors", "knncf_update_predict", "knncf_update_recommend",
@@ -202,6 +204,10 @@ def load_library():
     L.knncf_predict.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int32, _f64p]
     L.knncf_recommend.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int32, _i32p, _f64p, C.POINTER(C.c_int32)]
     L.knncf_recommend_batch.argtypes = [C.c_void_p, C.c_int, _i32p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p]
+    L.knncf_explain.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i32p, _f64p, _f64p, _i32p, _f64p, _f64p]
+    L.knncf_explain_batch.argtypes = [C.c_void_p, _i32p, _i32p, C.c_int64, C.c_int32, C.c_int32, _i32p, _f64p, _f64p, _i32p, _f64p,
+                                      _f64p]
+    L.knncf_explain_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 6
     for fam in ("query", "update"):  # fold-in queries and update queries share their argument lists
         f = lambda name: getattr(L, f"knncf_{fam}_{name}")
         f("neighbors").argtypes = [C.c_void_p, C.c_int32, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p]
@@ -429,6 +435,74 @@ class Engine:
         self._check(self._lib.knncf_recommend_batch(self._h, predictor, p(u, _i32p), B, n, p(items.reshape(-1), _i32p),
                                                     p(preds.reshape(-1), _f64p), p(counts, _i32p)))
         return items, preds, counts
+
+    # ---- explanations: the neighbour terms behind kNN predictions (knncf_explain*) ----------
+    @staticmethod
+    def _explain_args(cap, order):
+        if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or cap < 0 or cap >= 2**31:
+            raise ValueError("cap must be a non-negative 32-bit integer")
+        if order not in (EXPLAIN_SUM_ORDER, EXPLAIN_BY_WEIGHT):
+            raise ValueError("order must be EXPLAIN_SUM_ORDER or EXPLAIN_BY_WEIGHT")
+        return int(cap), int(order)
+
+    def explain(self, user, item, cap=None, order=EXPLAIN_SUM_ORDER):
+        """The terms behind predict(PRED_KNN, user, item) (knncf_explain): (raters int32, sims, devs, count, (num, den),
+        prediction) — the neighbours of `user` with a non-zero similarity that rated `item`, in `order`; the arrays hold
+        min(count, cap) terms.  cap=None: the handle's min(k, U - 1), which every row fits."""
+        if cap is None:
+            cap = max(0, min(self.k, self.num_users - 1))
+        cap, order = self._explain_args(cap, order)
+        raters = np.empty(max(1, cap), dtype=np.int32)
+        sims = np.empty(max(1, cap), dtype=np.float64)
+        devs = np.empty(max(1, cap), dtype=np.float64)
+        c, sums, pred = C.c_int32(), np.zeros(2, dtype=np.float64), C.c_double()
+        p = self._ptr
+        self._check(self._lib.knncf_explain(self._h, user, item, order, cap, p(raters, _i32p), p(sims, _f64p), p(devs, _f64p),
+                                            C.byref(c), p(sums, _f64p), C.byref(pred)))
+        m = min(c.value, cap)
+        return raters[:m].copy(), sims[:m].copy(), devs[:m].copy(), c.value, (float(sums[0]), float(sums[1])), pred.value
+
+    def explain_batch(self, users, items, cap, order=EXPLAIN_SUM_ORDER):
+        """explain for every row (users[j], items[j]) (knncf_explain_batch): (raters [n, cap] int32, sims [n, cap], devs
+        [n, cap], counts [n] int32, sums [n, 2], predictions [n]); cells past a row's min(count, cap) terms are -1 / nan.
+        Missing neighbourhoods are built as predict_batch(PRED_KNN, users, items) builds them."""
+        cap, order = self._explain_args(cap, order)
+        u, i = _i32(users), _i32(items)
+        if u.ndim != 1 or u.shape != i.shape:
+            raise ValueError("users and items must be 1-D arrays of one length")
+        n = len(u)
+        raters = np.full((n, cap), -1, dtype=np.int32)
+        sims = np.full((n, cap), np.nan, dtype=np.float64)
+        devs = np.full((n, cap), np.nan, dtype=np.float64)
+        counts = np.zeros(n, dtype=np.int32)
+        sums = np.zeros((n, 2), dtype=np.float64)
+        preds = np.empty(n, dtype=np.float64)
+        p = self._ptr
+        self._check(self._lib.knncf_explain_batch(self._h, p(u, _i32p), p(i, _i32p), n, order, cap, p(raters.reshape(-1), _i32p),
+                                                  p(sims.reshape(-1), _f64p), p(devs.reshape(-1), _f64p), p(counts, _i32p),
+                                                  p(sums.reshape(-1), _f64p), p(preds, _f64p)))
+        return raters, sims, devs, counts, sums, preds
+
+    def explain_batch_device(self, users, items, cap, raters, sims, devs, counts, sums=None, predictions=None,
+                             order=EXPLAIN_SUM_ORDER):
+        """explain_batch in one pass on contiguous torch tensors of this engine's device (knncf_explain_batch_device): users /
+        items int32 [n]; raters int32, sims / devs float64 [n, cap] (None with cap == 0); counts int32 [n]; sums float64
+        [n, 2] and predictions float64 [n] optional.  Cells past a row's terms are left as they are."""
+        cap, order = self._explain_args(cap, order)
+        n = users.numel()
+        if items.numel() != n or counts.numel() != n:
+            raise ValueError("users, items and counts must have one length")
+        for t, width in ((raters, cap), (sims, cap), (devs, cap), (sums, 2), (predictions, 1)):
+            if t is not None and t.numel() != n * width:
+                raise ValueError("an output tensor does not hold n rows")
+        if cap > 0 and (raters is None or sims is None or devs is None):
+            raise ValueError("cap > 0 needs raters, sims and devs")
+        opt = lambda t, name: _dev_ptr(t, name) if t is not None else None
+        _producer_done(users)
+        self._check(self._lib.knncf_explain_batch_device(
+            self._h, _dev_ptr(users, "int32"), _dev_ptr(items, "int32"), n, order, cap, opt(raters, "int32"),
+            opt(sims, "float64"), opt(devs, "float64"), _dev_ptr(counts, "int32"), opt(sums, "float64"),
+            opt(predictions, "float64")))
 
     # ---- fold-in queries: a user outside the fit (knncf_query_*), and update queries: any user, the rows being additional
     # to its train rows (knncf_update_*).  The two families share their argument lists; `fam` picks the entry points. ----
