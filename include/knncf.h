@@ -230,8 +230,9 @@ int knncf_recommend_batch(knncf_handle* h, int predictor, const int32_t* users, 
  * numbers, the same knncf_neighbors_save file.  knncf_explain is the batch of one row.  knncf_get_timings: builds are charged
  * as usual, the explain kernel as predict_ms.
  * Status: KNNCF_E_STATE before a fit; KNNCF_E_UNSUPPORTED for a KNNCF_SIM_ONE handle (as knncf_predict) and for a shard
- * handle (shard_count > 1): SHARDED EXPLANATIONS ARE OUT OF SCOPE, as are explanations of fold-in / update / revise queries
- * and of KNNCF_PRED_PERSONALIZED; KNNCF_E_INVALID for a null pointer that is needed, n < 0, cap < 0, an unknown order or
+ * handle (shard_count > 1): SHARDED EXPLANATIONS ARE OUT OF SCOPE, as are explanations of KNNCF_PRED_PERSONALIZED (the
+ * explanations of fold-in / update / revise queries are the knncf_*_explain* calls below, "Explanations of query
+ * predictions"); KNNCF_E_INVALID for a null pointer that is needed, n < 0, cap < 0, an unknown order or
  * n >= 2^32 - 1.  n == 0 is KNNCF_OK and touches nothing.  A call that fails these checks builds nothing and writes nothing.
  * Chunks.  The device form is one pass into the caller's buffers (every pointer on the handle's device, inputs complete at
  * the call, outputs complete on return).  The host form answers consecutive row ranges [0, C), [C, 2 C), ... through
@@ -406,6 +407,67 @@ int knncf_revise_recommend_batch(knncf_handle* h, int predictor, const int32_t* 
                                  const int32_t* removed_items, const int64_t* offsets, const int32_t* items, const double* ratings,
                                  int64_t n_queries, int32_t n, int32_t* out_items, double* out_preds, int32_t* counts,
                                  int32_t* statuses);
+
+/* ---- Explanations of query predictions: the terms behind knncf_query_predict / knncf_update_predict / knncf_revise_predict ---
+ * knncf_explain* above explains a prediction for a user as the fit holds it.  These explain what the three query families
+ * predict: for a person whose ratings are not, or no longer, what the fit holds, WITHOUT a refit.  One implementation serves
+ * the six calls: a revise query without removals is an update query, an update query for a user absent from train is a
+ * fold-in query.
+ * Arguments.  The query arguments are exactly those of the matching knncf_*_predict / knncf_*_predict_batch call, the
+ * pred_offsets / pred_items CSR included.  Row j of the call is one requested (query, raw item): m rows in the single forms,
+ * m = pred_offsets[n_queries] in the batched ones, in the order of pred_items.  order, cap and the outputs are those of
+ * knncf_explain_batch: counts[j] = the number of terms of row j (it may exceed cap); the first min(counts[j], cap) terms, in
+ * `order`, in row j of raters / sims / devs ([m * cap], row stride cap; the cells beyond them are left untouched);
+ * sums[2 j], sums[2 j + 1] = num and den of the fold over ALL terms; predictions[j] = the matching knncf_*_predict answer for
+ * that row, bit for bit.  sums and predictions may be null; with cap == 0 the three term arrays may be null.
+ * Terms.  With aug as the family defines it, the terms of row (query user u, item i) are the elements of simVal :513-517 on
+ * aug — fresh closures, first evaluation u's — whose similarity is non-zero: (rater's raw id, getSimilarity(aug, k, sim)(u,
+ * rater), the rater's normalized deviation on i).  KNNCF_EXPLAIN_SUM_ORDER is aug's file order of the item's raters; every
+ * term is a train user, so that is train file order.  KNNCF_EXPLAIN_BY_WEIGHT is |similarity| descending, equal magnitudes in
+ * summation order.  It follows that the user is never its own term, even when it rates i itself in aug; that a listed
+ * neighbour whose similarity is exactly 0.0 is no term; and that an item unknown to train, an item that leaves aug under a
+ * revise query and an item no neighbour rated get count 0, sums (0, 0) and the query's mean, exactly, as prediction.
+ * Properties, as for knncf_explain: with counts[j] <= cap and KNNCF_EXPLAIN_SUM_ORDER the caller's left fold of the returned
+ * terms (num + dev * sim, den + |sim| from (0.0, 0.0), no fused multiply-add) gives sums bit for bit, and the combine :578 of
+ * the query's mean with (den > 0 ? num / den : 0.0) gives predictions[j]; the query's mean is the answer for an unknown item.
+ * KNNCF_EXPLAIN_BY_WEIGHT returns a permutation of the same terms.
+ * Statuses.  Per-query statuses, the handle-level return values, the CSR checks and n_queries == 0 are those of the
+ * knncf_*_predict_batch call of the same family; so are the chunk rule C, the split at 32 answerable queries, "read-only on
+ * the handle" and "the results do not depend on C".  In addition: KNNCF_E_INVALID for cap < 0, an unknown order, or a needed
+ * output pointer that is null; a failed query gets counts[j] = 0 on each of its rows and nothing else of those rows is written;
+ * a single call returns the query's status (and has set counts = 0 on every row when that is a per-query refusal).
+ * Row sub-ranges inside a chunk.  The term scratch of one launch holds
+ *     R = max(1, budget / (20 * cap + 28))
+ *     budget = workspace_bytes / 2 if workspace_bytes > 0, else min(48 GiB, free device memory / 4)
+ * rows (the budget of the other batched calls).  A chunk with more requested rows runs the explain kernel over consecutive
+ * sub-ranges of R rows; the chunk's fold results stay in place between the launches.  The results do not depend on R, and a
+ * call on a handle that has answered the same shape before allocates no device memory.
+ * OUT OF SCOPE here as above: KNNCF_PRED_PERSONALIZED explanations (KNNCF_E_UNSUPPORTED, as the query calls answer for any
+ * predictor but KNNCF_PRED_KNN), sharded explanations (a shard handle: KNNCF_E_UNSUPPORTED), and a fused "recommend and
+ * explain in one pass" call: explain the items knncf_*_recommend returned with a second call. */
+int knncf_query_explain(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
+                        const int32_t* pred_items, int64_t m, int32_t order, int32_t cap, int32_t* raters, double* sims, double* devs,
+                        int32_t* counts, double* sums, double* predictions);
+int knncf_update_explain(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
+                         const int32_t* pred_items, int64_t m, int32_t order, int32_t cap, int32_t* raters, double* sims, double* devs,
+                         int32_t* counts, double* sums, double* predictions);
+int knncf_revise_explain(knncf_handle* h, int predictor, int32_t user, const int32_t* removed_items, int64_t n_removed,
+                         const int32_t* items, const double* ratings, int64_t n_ratings, const int32_t* pred_items, int64_t m,
+                         int32_t order, int32_t cap, int32_t* raters, double* sims, double* devs, int32_t* counts, double* sums,
+                         double* predictions);
+int knncf_query_explain_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                              const double* ratings, int64_t n_queries, const int64_t* pred_offsets, const int32_t* pred_items,
+                              int32_t order, int32_t cap, int32_t* raters, double* sims, double* devs, int32_t* counts, double* sums,
+                              double* predictions, int32_t* statuses);
+int knncf_update_explain_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                               const double* ratings, int64_t n_queries, const int64_t* pred_offsets, const int32_t* pred_items,
+                               int32_t order, int32_t cap, int32_t* raters, double* sims, double* devs, int32_t* counts, double* sums,
+                               double* predictions, int32_t* statuses);
+int knncf_revise_explain_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* removed_offsets,
+                               const int32_t* removed_items, const int64_t* offsets, const int32_t* items, const double* ratings,
+                               int64_t n_queries, const int64_t* pred_offsets, const int32_t* pred_items, int32_t order, int32_t cap,
+                               int32_t* raters, double* sims, double* devs, int32_t* counts, double* sums, double* predictions,
+                               int32_t* statuses);
 
 /* ---- batch ---------------------------------------------------------------- */
 int knncf_predict_batch(knncf_handle* h, int predictor, const int32_t* users,

@@ -87,6 +87,9 @@ struct knncf_handle {
     // one chunk of knncf_explain_batch's host form: [C * cap] terms, [C] counts and predictions, [2 C] sums
     DArr<int32_t> ex_raters, ex_counts;
     DArr<double> ex_sims, ex_devs, ex_sums, ex_pred;
+    // one launch of the query explanations (QB_EXPLAIN): the same outputs of its rows in ONE block, 20 * cap + 28 bytes per
+    // row, so that one copy brings a sub-range back
+    DArr<double> ex_pack;
     // host mirrors for scalar queries
     std::vector<uint32_t> h_ukeys, h_ikeys;
     std::vector<int32_t> h_uid;
@@ -1045,7 +1048,7 @@ void do_recommend(knncf_handle* h, int predictor, int32_t user, int32_t n, int32
 // Revise queries (knncf_revise_*) are update queries that also name train items of the user to REMOVE from aug: the seeding
 // leaves their rows out.  A chunk without removals is an update chunk.
 constexpr int64_t QUERY_MAX_RATINGS = 65536;
-enum QueryBatchMode { QB_NEIGHBORS, QB_PREDICT, QB_RECOMMEND };
+enum QueryBatchMode { QB_NEIGHBORS, QB_PREDICT, QB_RECOMMEND, QB_EXPLAIN };
 enum QueryFamily { QF_FOLD_IN, QF_UPDATE, QF_REVISE };
 
 // what the handle must be for any fold-in query, single or batched
@@ -1056,19 +1059,25 @@ void require_query_support(knncf_handle* h, int predictor) {
     KN_REQUIRE(h->tr.U >= 5, KNNCF_E_UNSUPPORTED, "query: fewer than 5 train users (the user set changes iteration class)");
 }
 
+// what the chunk rules of knncf.h divide: workspace_bytes / 2, else min(48 GiB, free device memory / 4)
+int64_t batch_budget(knncf_handle* h) {
+    if (h->cfg.workspace_bytes > 0) return h->cfg.workspace_bytes / 2;
+    size_t free_b = 0, total_b = 0;
+    KN_HIP(hipMemGetInfo(&free_b, &total_b));
+    return (int64_t)std::min<size_t>((size_t)48 << 30, free_b / 4);
+}
+
 // queries per chunk: the rule of knncf.h ("Batched fold-in queries")
-int64_t query_batch_chunk(knncf_handle* h) {
+int64_t query_batch_chunk(knncf_handle* h, int64_t budget) {
     const Train& tr = h->tr;
-    int64_t budget = h->cfg.workspace_bytes / 2;
-    if (h->cfg.workspace_bytes <= 0) {
-        size_t free_b = 0, total_b = 0;
-        KN_HIP(hipMemGetInfo(&free_b, &total_b));
-        budget = (int64_t)std::min<size_t>((size_t)48 << 30, free_b / 4);
-    }
     int64_t C = std::min<int64_t>(QB_MAX_CHUNK, budget / query_batch_bytes(tr.U, tr.I));
     C = std::min<int64_t>(C, (int64_t)0x7fffffff / std::max(tr.U, tr.I));  // slot * U + user and slot * I + item are 31-bit cells
     return std::max<int64_t>(C, 1);
 }
+
+// rows per chunk of knncf_explain_batch, and per launch of the query explanations: the rule of knncf.h ("Explanations")
+int64_t explain_rows(int64_t budget, int32_t cap) { return std::max<int64_t>(budget / (20 * (int64_t)cap + 28), 1); }
+int64_t explain_batch_chunk(knncf_handle* h, int32_t cap) { return explain_rows(batch_budget(h), cap); }
 
 // the first query that was refused (-1: none) and why
 struct QueryFailure {
@@ -1076,14 +1085,28 @@ struct QueryFailure {
     const char* reason = "";
 };
 
+// where QB_EXPLAIN writes: row j of the call is requested item j of the pred_offsets / pred_items CSR
+struct ExplainOut {
+    int32_t order, cap;
+    int64_t rows;     // R: rows per launch (filled in by do_query_batch / do_query_single)
+    int32_t* raters;  // [m * cap], row stride cap (unused with cap == 0)
+    double* sims;
+    double* devs;
+    int32_t* counts;  // [m]
+    double* sums;     // [2 m] or null
+    double* pred;     // [m] or null
+};
+
 // The B validated queries in chunks of `chunk`: statuses[b] and, where it is KNNCF_OK, query b's answer.
 // mode QB_NEIGHBORS: width = cap, out_i / out_d = ids / sims [B * cap]; QB_RECOMMEND: width = n, out_i / out_d = items /
 // predictions [B * n]; QB_PREDICT: out_d [pred_offsets[B]].  QF_REVISE: removed_items [removed_offsets[b], removed_offsets[b + 1])
-// are the train items query b's user drops (null for the other families)
+// are the train items query b's user drops (null for the other families).  QB_EXPLAIN: the rows of pred_offsets / pred_items
+// as QB_PREDICT takes them, answered into *ex; a refused query gets ex->counts = 0 on its rows
 QueryFailure run_query_chunks(knncf_handle* h, QueryFamily family, QueryBatchMode mode, int64_t chunk, const int32_t* users,
                               const int64_t* removed_offsets, const int32_t* removed_items,
                               const int64_t* offsets, const int32_t* items, const double* ratings, int64_t B, int32_t width, const int64_t* pred_offsets,
-                              const int32_t* pred_items, int32_t* out_i, double* out_d, int32_t* counts, int32_t* statuses) {
+                              const int32_t* pred_items, int32_t* out_i, double* out_d, int32_t* counts, int32_t* statuses,
+                              const ExplainOut* ex = nullptr) {
     h->prep.join_commit(h->stream);
     const Train& tr = h->tr;
     QueryBatchScratch& bs = h->query_batch;
@@ -1093,6 +1116,7 @@ QueryFailure run_query_chunks(knncf_handle* h, QueryFamily family, QueryBatchMod
     auto fail = [&](int64_t b, int status, const char* why) {
         statuses[b] = status;
         if (counts) counts[b] = 0;
+        if (mode == QB_EXPLAIN) std::fill(ex->counts + pred_offsets[b], ex->counts + pred_offsets[b + 1], 0);
         if (first.query < 0 || b < first.query) first = {b, why};
     };
     const bool update = family != QF_FOLD_IN, revise = family == QF_REVISE;
@@ -1100,6 +1124,8 @@ QueryFailure run_query_chunks(knncf_handle* h, QueryFamily family, QueryBatchMod
     std::vector<int32_t> s_users, s_items, s_self, s_removed, h_idx, h_items, pick_slot, pick_items;
     std::vector<double> s_ratings, h_vals;
     std::vector<long long> info;
+    std::vector<int64_t> pick_row;
+    const int64_t ex_rows = mode == QB_EXPLAIN ? ex->rows : 0;
     for (int64_t c0 = 0; c0 < B; c0 += chunk) {
         const int64_t c1 = std::min(B, c0 + chunk);
         // the chunk's answerable queries, slot after slot
@@ -1200,6 +1226,58 @@ QueryFailure run_query_chunks(knncf_handle* h, QueryFamily family, QueryBatchMod
             }
             continue;
         }
+        if (mode == QB_EXPLAIN) {
+            // the chunk's requested rows as QB_PREDICT uploads them; pick_row = the row of the call behind each
+            pick_slot.clear(); pick_items.clear(); pick_row.clear();
+            for (int32_t s = 0; s < C; ++s) {
+                const int64_t b = slot_query[s];
+                if (statuses[b] != KNNCF_OK) continue;
+                pick_items.insert(pick_items.end(), pred_items + pred_offsets[b], pred_items + pred_offsets[b + 1]);
+                pick_slot.insert(pick_slot.end(), (size_t)(pred_offsets[b + 1] - pred_offsets[b]), s);
+                for (int64_t j = pred_offsets[b]; j < pred_offsets[b + 1]; ++j) pick_row.push_back(j);
+            }
+            const int64_t m = (int64_t)pick_items.size();
+            if (m == 0) continue;
+            foldin_batch_predictions(tr, bs, h->prep.sort, C, take, ebase.data(), st);
+            bs.pick_items.ensure(m); bs.pick_slot.ensure(m);
+            KN_HIP(hipMemcpyAsync(bs.pick_items.p, pick_items.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            KN_HIP(hipMemcpyAsync(bs.pick_slot.p, pick_slot.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            // sub-ranges of R rows: the chunk's fold results stay where they are between the launches.  The outputs of a
+            // launch of nr rows lie in one block — sims, devs [nr * cap], sums [2 nr], predictions [nr] as doubles, then
+            // raters [nr * cap] and counts [nr] as int32: nr * (20 * cap + 28) bytes — and come back in one copy
+            const int32_t cap = ex->cap;
+            const int64_t R = std::min(ex_rows, m);
+            const size_t pack = ((size_t)R * (20 * (size_t)cap + 28) + 7) / 8;
+            h->ex_pack.ensure(pack);
+            h_vals.resize(pack);
+            for (int64_t r0 = 0; r0 < m; r0 += R) {
+                const int64_t nr = std::min(R, m - r0);
+                const size_t cells = (size_t)nr * (size_t)cap, doubles = 2 * cells + 3 * (size_t)nr;
+                auto lay = [&](double* base) {
+                    ExplainOut o = *ex;
+                    o.sims = base; o.devs = base + cells; o.sums = base + 2 * cells; o.pred = o.sums + 2 * nr;
+                    o.raters = reinterpret_cast<int32_t*>(base + doubles); o.counts = o.raters + cells;
+                    return o;
+                };
+                const ExplainOut d = lay(h->ex_pack.p), g = lay(h_vals.data());
+                foldin_batch_explain(tr, bs, C, take, ebase[C], bs.pick_items.p, bs.pick_slot.p, r0, nr, ex->order, cap, d.raters, d.sims,
+                                     d.devs, d.counts, d.sums, d.pred, st);
+                KN_HIP(hipMemcpyAsync(h_vals.data(), h->ex_pack.p, (size_t)nr * (20 * (size_t)cap + 28), hipMemcpyDeviceToHost, st));
+                KN_HIP(hipStreamSynchronize(st));
+                for (int64_t r = 0; r < nr; ++r) {  // (the cells of a row beyond its terms stay as the caller left them)
+                    const int64_t j = pick_row[(size_t)(r0 + r)];
+                    ex->counts[j] = g.counts[r];
+                    if (ex->sums) { ex->sums[2 * j] = g.sums[2 * r]; ex->sums[2 * j + 1] = g.sums[2 * r + 1]; }
+                    if (ex->pred) ex->pred[j] = g.pred[r];
+                    const size_t from = (size_t)r * cap, to = (size_t)j * cap;
+                    const int32_t t = std::min(g.counts[r], cap);
+                    std::copy(g.raters + from, g.raters + from + t, ex->raters + to);
+                    std::copy(g.sims + from, g.sims + from + t, ex->sims + to);
+                    std::copy(g.devs + from, g.devs + from + t, ex->devs + to);
+                }
+            }
+            continue;
+        }
         // QB_RECOMMEND
         int32_t widest = 0;
         for (int32_t s = 0; s < C; ++s) {
@@ -1227,15 +1305,29 @@ QueryFailure run_query_chunks(knncf_handle* h, QueryFamily family, QueryBatchMod
     return first;
 }
 
+// the refusals the explain forms add to those of the predict forms (knncf.h "Explanations of query predictions")
+void require_explain_order(const ExplainOut* ex) {
+    KN_REQUIRE(ex->cap >= 0, KNNCF_E_INVALID, "query explain: cap < 0");
+    KN_REQUIRE(ex->order == KNNCF_EXPLAIN_SUM_ORDER || ex->order == KNNCF_EXPLAIN_BY_WEIGHT, KNNCF_E_INVALID,
+               "query explain: unknown order");
+}
+void require_explain_outputs(const ExplainOut* ex, int64_t m) {
+    KN_REQUIRE(m == 0 || (ex->counts && (ex->cap == 0 || (ex->raters && ex->sims && ex->devs))), KNNCF_E_INVALID,
+               "query explain: null output");
+}
+
 void do_query_batch(knncf_handle* h, QueryFamily family, QueryBatchMode mode, int predictor, const int32_t* users,
                     const int64_t* removed_offsets, const int32_t* removed_items, const int64_t* offsets, const int32_t* items, const double* ratings, int64_t B, int32_t width, const int64_t* pred_offsets,
-                    const int32_t* pred_items, int32_t* out_i, double* out_d, int32_t* counts, int32_t* statuses) {
+                    const int32_t* pred_items, int32_t* out_i, double* out_d, int32_t* counts, int32_t* statuses,
+                    const ExplainOut* ex = nullptr) {
     require_fitted(h, false);
     KN_REQUIRE(B >= 0, KNNCF_E_INVALID, "query batch: n_queries < 0");
-    KN_REQUIRE(mode == QB_PREDICT || width >= 0, KNNCF_E_INVALID, "query batch: cap or n < 0");
+    KN_REQUIRE(mode == QB_PREDICT || mode == QB_EXPLAIN || width >= 0, KNNCF_E_INVALID, "query batch: cap or n < 0");
+    if (mode == QB_EXPLAIN) require_explain_order(ex);
     require_query_support(h, predictor);
     if (B == 0) return;
-    KN_REQUIRE(users && offsets && statuses && (mode == QB_PREDICT || counts), KNNCF_E_INVALID, "query batch: null argument");
+    KN_REQUIRE(users && offsets && statuses && (mode == QB_PREDICT || mode == QB_EXPLAIN || counts), KNNCF_E_INVALID,
+               "query batch: null argument");
     KN_REQUIRE(offsets[0] == 0, KNNCF_E_INVALID, "query batch: offsets[0] != 0");
     for (int64_t b = 0; b < B; ++b) KN_REQUIRE(offsets[b] <= offsets[b + 1], KNNCF_E_INVALID, "query batch: offsets decrease");
     KN_REQUIRE(offsets[B] < ((int64_t)1 << 31), KNNCF_E_INVALID, "query batch: 2^31 or more ratings in one call");
@@ -1252,11 +1344,24 @@ void do_query_batch(knncf_handle* h, QueryFamily family, QueryBatchMode mode, in
         for (int64_t b = 0; b < B; ++b)
             KN_REQUIRE(pred_offsets[b] <= pred_offsets[b + 1], KNNCF_E_INVALID, "query batch: pred_offsets decrease");
         KN_REQUIRE(pred_offsets[B] == 0 || (pred_items && out_d), KNNCF_E_INVALID, "query batch: null prediction arguments");
+    } else if (mode == QB_EXPLAIN) {
+        KN_REQUIRE(pred_offsets && pred_offsets[0] == 0, KNNCF_E_INVALID, "query batch: pred_offsets null or not starting at 0");
+        for (int64_t b = 0; b < B; ++b)
+            KN_REQUIRE(pred_offsets[b] <= pred_offsets[b + 1], KNNCF_E_INVALID, "query batch: pred_offsets decrease");
+        KN_REQUIRE(pred_offsets[B] == 0 || pred_items, KNNCF_E_INVALID, "query batch: null prediction arguments");
+        require_explain_outputs(ex, pred_offsets[B]);
     } else {
         KN_REQUIRE(width == 0 || (out_i && out_d), KNNCF_E_INVALID, "query batch: null output");
     }
-    const QueryFailure f = run_query_chunks(h, family, mode, query_batch_chunk(h), users, removed_offsets, removed_items, offsets, items,
-                                            ratings, B, width, pred_offsets, pred_items, out_i, out_d, counts, statuses);
+    const int64_t budget = batch_budget(h);  // (one hipMemGetInfo for both rules)
+    ExplainOut rows_known;
+    if (mode == QB_EXPLAIN) {
+        rows_known = *ex;
+        rows_known.rows = explain_rows(budget, ex->cap);
+        ex = &rows_known;
+    }
+    const QueryFailure f = run_query_chunks(h, family, mode, query_batch_chunk(h, budget), users, removed_offsets, removed_items, offsets,
+                                            items, ratings, B, width, pred_offsets, pred_items, out_i, out_d, counts, statuses, ex);
     if (f.query >= 0) h->err = "query batch: query " + std::to_string(f.query) + ": " + f.reason;
 }
 
@@ -1265,8 +1370,13 @@ void do_query_batch(knncf_handle* h, QueryFamily family, QueryBatchMode mode, in
 // success.  An update query may come without rows (whether the user is in the fit is the chunk loop's to say).
 void do_query_single(knncf_handle* h, QueryFamily family, QueryBatchMode mode, int predictor, int32_t user,
                      const int32_t* removed_items, int64_t n_removed, const int32_t* items, const double* ratings, int64_t n_ratings, int32_t width, const int32_t* pred_items, int64_t m, int32_t* out_i,
-                     double* out_d, int32_t* count) {
+                     double* out_d, int32_t* count, const ExplainOut* ex = nullptr) {
     require_fitted(h, false);
+    if (mode == QB_EXPLAIN) {
+        require_explain_order(ex);
+        KN_REQUIRE(m >= 0 && (m == 0 || pred_items), KNNCF_E_INVALID, "bad prediction arguments");
+        require_explain_outputs(ex, m);
+    }
     if (family == QF_REVISE)
         KN_REQUIRE(n_removed >= 0 && (n_removed == 0 || removed_items), KNNCF_E_INVALID, "query: null removed items or n_removed < 0");
     if (family != QF_FOLD_IN) {
@@ -1277,8 +1387,14 @@ void do_query_single(knncf_handle* h, QueryFamily family, QueryBatchMode mode, i
     require_query_support(h, predictor);
     const int64_t offsets[2] = {0, n_ratings}, pred_offsets[2] = {0, m}, removed_offsets[2] = {0, family == QF_REVISE ? n_removed : 0};
     int32_t status = KNNCF_OK, c = 0;
+    ExplainOut rows_known;
+    if (mode == QB_EXPLAIN) {
+        rows_known = *ex;
+        rows_known.rows = explain_batch_chunk(h, ex->cap);
+        ex = &rows_known;
+    }
     const QueryFailure f = run_query_chunks(h, family, mode, 1, &user, removed_offsets, removed_items, offsets, items, ratings, 1, width, pred_offsets, pred_items,
-                                            out_i, out_d, &c, &status);
+                                            out_i, out_d, mode == QB_EXPLAIN ? nullptr : &c, &status, ex);
     if (f.query >= 0) throw Error(status, std::string("query: ") + f.reason);
     if (count) *count = c;
 }
@@ -1877,17 +1993,6 @@ static void explain_prepare(knncf_handle* h, const int32_t* d_users, const int32
     h->prep.join_commit(h->stream);  // the item-major copies and the rater bitmaps (second part of prep_commit)
 }
 
-// rows per chunk of knncf_explain_batch: the rule of knncf.h ("Explanations")
-static int64_t explain_batch_chunk(knncf_handle* h, int32_t cap) {
-    int64_t budget = h->cfg.workspace_bytes / 2;
-    if (h->cfg.workspace_bytes <= 0) {
-        size_t free_b = 0, total_b = 0;
-        KN_HIP(hipMemGetInfo(&free_b, &total_b));
-        budget = (int64_t)std::min<size_t>((size_t)48 << 30, free_b / 4);
-    }
-    return std::max<int64_t>(budget / (20 * (int64_t)cap + 28), 1);
-}
-
 int knncf_explain_batch_device(knncf_handle* h, const int32_t* d_users, const int32_t* d_items, int64_t n, int32_t order,
                                int32_t cap, int32_t* d_raters, double* d_sims, double* d_devs, int32_t* d_counts,
                                double* d_sums, double* d_predictions) {
@@ -2112,6 +2217,72 @@ int knncf_revise_recommend_batch(knncf_handle* h, int predictor, const int32_t* 
     return guarded(h, [&] {
         do_query_batch(h, QF_REVISE, QB_RECOMMEND, predictor, users, removed_offsets, removed_items, offsets, items, ratings, n_queries, n,
                        nullptr, nullptr, out_items, out_preds, counts, statuses);
+    });
+}
+
+// explanations of query predictions: the *_predict calls' arguments, the terms behind every requested row
+int knncf_query_explain(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
+                        const int32_t* pred_items, int64_t m, int32_t order, int32_t cap, int32_t* raters, double* sims, double* devs,
+                        int32_t* counts, double* sums, double* predictions) {
+    return guarded(h, [&] {
+        const ExplainOut ex{order, cap, 0, raters, sims, devs, counts, sums, predictions};
+        do_query_single(h, QF_FOLD_IN, QB_EXPLAIN, predictor, user, nullptr, 0, items, ratings, n_ratings, 0, pred_items, m, nullptr, nullptr,
+                        nullptr, &ex);
+    });
+}
+
+int knncf_update_explain(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
+                         const int32_t* pred_items, int64_t m, int32_t order, int32_t cap, int32_t* raters, double* sims, double* devs,
+                         int32_t* counts, double* sums, double* predictions) {
+    return guarded(h, [&] {
+        const ExplainOut ex{order, cap, 0, raters, sims, devs, counts, sums, predictions};
+        do_query_single(h, QF_UPDATE, QB_EXPLAIN, predictor, user, nullptr, 0, items, ratings, n_ratings, 0, pred_items, m, nullptr, nullptr,
+                        nullptr, &ex);
+    });
+}
+
+int knncf_revise_explain(knncf_handle* h, int predictor, int32_t user, const int32_t* removed_items, int64_t n_removed,
+                         const int32_t* items, const double* ratings, int64_t n_ratings, const int32_t* pred_items, int64_t m,
+                         int32_t order, int32_t cap, int32_t* raters, double* sims, double* devs, int32_t* counts, double* sums,
+                         double* predictions) {
+    return guarded(h, [&] {
+        const ExplainOut ex{order, cap, 0, raters, sims, devs, counts, sums, predictions};
+        do_query_single(h, QF_REVISE, QB_EXPLAIN, predictor, user, removed_items, n_removed, items, ratings, n_ratings, 0, pred_items, m,
+                        nullptr, nullptr, nullptr, &ex);
+    });
+}
+
+int knncf_query_explain_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                              const double* ratings, int64_t n_queries, const int64_t* pred_offsets, const int32_t* pred_items,
+                              int32_t order, int32_t cap, int32_t* raters, double* sims, double* devs, int32_t* counts, double* sums,
+                              double* predictions, int32_t* statuses) {
+    return guarded(h, [&] {
+        const ExplainOut ex{order, cap, 0, raters, sims, devs, counts, sums, predictions};
+        do_query_batch(h, QF_FOLD_IN, QB_EXPLAIN, predictor, users, nullptr, nullptr, offsets, items, ratings, n_queries, 0, pred_offsets,
+                       pred_items, nullptr, nullptr, nullptr, statuses, &ex);
+    });
+}
+
+int knncf_update_explain_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                               const double* ratings, int64_t n_queries, const int64_t* pred_offsets, const int32_t* pred_items,
+                               int32_t order, int32_t cap, int32_t* raters, double* sims, double* devs, int32_t* counts, double* sums,
+                               double* predictions, int32_t* statuses) {
+    return guarded(h, [&] {
+        const ExplainOut ex{order, cap, 0, raters, sims, devs, counts, sums, predictions};
+        do_query_batch(h, QF_UPDATE, QB_EXPLAIN, predictor, users, nullptr, nullptr, offsets, items, ratings, n_queries, 0, pred_offsets,
+                       pred_items, nullptr, nullptr, nullptr, statuses, &ex);
+    });
+}
+
+int knncf_revise_explain_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* removed_offsets,
+                               const int32_t* removed_items, const int64_t* offsets, const int32_t* items, const double* ratings,
+                               int64_t n_queries, const int64_t* pred_offsets, const int32_t* pred_items, int32_t order, int32_t cap,
+                               int32_t* raters, double* sims, double* devs, int32_t* counts, double* sums, double* predictions,
+                               int32_t* statuses) {
+    return guarded(h, [&] {
+        const ExplainOut ex{order, cap, 0, raters, sims, devs, counts, sums, predictions};
+        do_query_batch(h, QF_REVISE, QB_EXPLAIN, predictor, users, removed_offsets, removed_items, offsets, items, ratings, n_queries, 0,
+                       pred_offsets, pred_items, nullptr, nullptr, nullptr, statuses, &ex);
     });
 }
 

@@ -370,6 +370,13 @@ void foldin_batch_predictions(const Train& tr, QueryBatchScratch& bs, SortWorksp
                               const int64_t* h_ebase, hipStream_t st);
 void foldin_batch_pick(const Train& tr, QueryBatchScratch& bs, const int32_t* d_items, const int32_t* d_slot, int64_t m,
                        double* d_out, hipStream_t st);
+// after foldin_batch_predictions: the terms behind the predictions of the chunk's rows [r0, r0 + n) of d_items / d_slot (E =
+// h_ebase[C], the chunk's gathered entries).  Output cell 0 is row r0: d_counts [n] = number of terms, the first min(count, cap)
+// in `order` (KNNCF_EXPLAIN_*) in d_raters / d_sims / d_devs [n * cap] (unused with cap == 0), d_sums [2 n] = the cell's num /
+// den and d_pred [n] = its prediction (either may be null).  One launch.
+void foldin_batch_explain(const Train& tr, QueryBatchScratch& bs, int32_t C, int32_t take, int64_t E, const int32_t* d_items,
+                          const int32_t* d_slot, int64_t r0, int64_t n, int32_t order, int32_t cap, int32_t* d_raters,
+                          double* d_sims, double* d_devs, int32_t* d_counts, double* d_sums, double* d_pred, hipStream_t st);
 // d_items / d_preds [C][n]: slot b's first min(n, I - known) recommendations (the rest untouched)
 void foldin_batch_recommend(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, int32_t n, int32_t* d_items,
                             double* d_preds, hipStream_t st);

@@ -28,6 +28,8 @@
 //                                       file row): the left folds of weightedSumDeviation :504-548
 //   k_qb_pred                           predictor :568-585 for every (slot, dense item)
 //   k_qb_reco_keys / sort 64 bits / stable sort by slot / k_qb_take               recommendations
+//   k_qb_explain                        (knncf_*_explain*) the elements of those folds for requested (slot, item) rows: one
+//                                       wave per row reads the row's segment of the sorted list that k_q_fold folded
 #include <math.h>
 
 #include <algorithm>
@@ -629,6 +631,184 @@ __global__ void k_qb_pick(int64_t m, const int32_t* __restrict__ items, const in
     }
 }
 
+// ---- explanations of query predictions (knncf_query_explain* / knncf_update_explain* / knncf_revise_explain*) ------------
+// After foldin_batch_predictions the chunk's gathered neighbour ratings lie sorted by (slot * I + item, train file row) in
+// key / val, with edev / esim behind the permutation val.  The entries whose key's high word is slot * I + item are, one for
+// one and in summation order, simVal :513-517 of that (query user, item) on aug restricted to the slot's neighbours — the
+// other raters' elements have similarity 0.0, as do the listed neighbours whose similarity is exactly 0.0: neither is a term.
+// k_q_fold folded exactly this segment into num / den (the zero elements add +-0.0: identities), k_qb_pred combined them.
+struct QbExplainArgs {
+    const int32_t* items;  // [rows of the chunk] requested raw item and slot, as k_qb_pick takes them
+    const int32_t* slot;
+    const int32_t* i_table;
+    int32_t i_cells;
+    const uint32_t* ikeys;
+    int32_t I, take, order, cap;
+    int64_t E;             // entries of the chunk's sorted list (0: key .. ebase are not read)
+    const uint64_t* key;
+    const uint32_t* val;
+    const double* edev;
+    const double* esim;
+    const int64_t* ebase;  // [C + 1]
+    const int64_t* off;    // [C][take + 1]
+    const int32_t* nbr;    // [C][take] dense neighbours
+    const int32_t* uid;    // raw id of a dense user
+    const double* num;     // [C][I]
+    const double* den;
+    const double* pred;
+    const double* scal;    // [C][2]
+    // outputs of the launch's rows [r0, r0 + n): cell 0 is row r0.  Terms [n * cap] (unused with cap == 0), counts [n],
+    // sums [2 n], pred [n]
+    int32_t* raters;
+    double* sims;
+    double* devs;
+    int32_t* counts;
+    double* sums;
+    double* out_pred;
+};
+
+// the raw id of the neighbour whose ratings k_qb_gather wrote at position t of the gathered list: slot b's part starts at
+// ebase[b], neighbour j's extent inside it is [off[b][j], off[b][j + 1])
+__device__ __forceinline__ int32_t qb_rater(const QbExplainArgs& A, int32_t b, uint32_t t) {
+    const int64_t* mine = A.off + (int64_t)b * (A.take + 1);
+    const int64_t r = (int64_t)t - A.ebase[b];
+    int32_t lo = 0, hi = A.take;  // first j with mine[j] > r: mine[take] = the slot's entries > r, so 1 <= j <= take
+    while (lo < hi) {
+        const int32_t mid = (lo + hi) >> 1;
+        if (mine[mid] > r) hi = mid;
+        else lo = mid + 1;
+    }
+    return A.uid[A.nbr[(int64_t)b * A.take + (lo - 1)]];
+}
+
+// One wave per requested row.  No LDS and no tile: a segment of any length is walked 64 entries per trip, and BY_WEIGHT
+// ranks each term by counting against the whole segment, which the wave re-reads 64 entries at a time and broadcasts lane by
+// lane (v_readlane), QBX_OWN terms per lane and pass.
+// Bounds.  rows: the host uploads items / slot for every row of [r0, r0 + n) and sizes the outputs for n rows of cap cells; a
+// term is stored only at a place < cap.  slot < C.  c is a dense item of [0, I) or -1.  Segment positions x lie in [lo, hi)
+// within [0, E); val is a permutation of [0, E).  The slot is the major part of the key, so every entry of the segment was
+// gathered for slot b: ebase[b] <= t < ebase[b + 1], hence 0 <= r < off[b][take] in qb_rater, whose answer j has a non-empty
+// extent — a cell k_qb_write filled with a dense user of [0, U).
+static constexpr int QBX_WAVES = 4;  // waves (rows) per workgroup
+static constexpr int QBX_OWN = 4;    // BY_WEIGHT: terms a lane ranks per pass over the segment
+__global__ void __launch_bounds__(QBX_WAVES * 64) k_qb_explain(QbExplainArgs A, int64_t r0, int64_t n) {
+    const int lane = threadIdx.x & 63;
+    const int64_t jj = (int64_t)blockIdx.x * QBX_WAVES + (threadIdx.x >> 6);
+    if (jj >= n) return;
+    const int64_t j = r0 + jj;
+    const int32_t it = A.items[j], b = A.slot[j];
+    int32_t c;
+    if (A.i_cells > 0) c = (it >= 0 && it < A.i_cells) ? A.i_table[it] : -1;
+    else c = dense_lookup(A.ikeys, A.I, it);
+    if (c < 0) {  // unknown to train: no rater (k_qb_pick's expression)
+        if (lane == 0) {
+            A.counts[jj] = 0;
+            if (A.sums) A.sums[2 * jj] = A.sums[2 * jj + 1] = 0.0;
+            if (A.out_pred) {
+                const double avg = A.scal[2 * b], w = 0.0;
+                A.out_pred[jj] = avg + w * scale_fn(avg + w, avg);
+            }
+        }
+        return;
+    }
+    // the segment [lo, hi) of key high word slot * I + item (every lane runs the same search; E < 2^32 - 1)
+    const uint32_t want = (uint32_t)b * (uint32_t)A.I + (uint32_t)c;
+    uint32_t lo = 0, hi = 0;
+    if (A.E > 0) {
+        int64_t a = 0, z = A.E;
+        while (a < z) {
+            const int64_t mid = (a + z) >> 1;
+            if ((uint32_t)(A.key[mid] >> 32) < want) a = mid + 1;
+            else z = mid;
+        }
+        lo = (uint32_t)a;
+        z = A.E;
+        while (a < z) {
+            const int64_t mid = (a + z) >> 1;
+            if ((uint32_t)(A.key[mid] >> 32) <= want) a = mid + 1;
+            else z = mid;
+        }
+        hi = (uint32_t)a;
+    }
+    lo = __builtin_amdgcn_readfirstlane(lo);
+    hi = __builtin_amdgcn_readfirstlane(hi);
+    const int64_t ob = jj * (int64_t)A.cap;
+    const bool by_weight = A.order == KNNCF_EXPLAIN_BY_WEIGHT;
+    // walk and compact: the running place of a term is its place in the fold
+    int32_t total = 0;
+    for (uint32_t base = lo; base < hi; base += 64) {
+        const uint32_t x = base + lane;
+        uint32_t t = 0;
+        double s = 0.0;
+        if (x < hi) {
+            t = A.val[x];
+            s = A.esim[t];
+        }
+        const bool keep = s != 0.0;
+        const unsigned long long hit = __ballot(keep);
+        if (keep && !by_weight) {
+            const int32_t place = total + (int32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(hit >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hit, 0u));
+            if (place < A.cap) {
+                A.raters[ob + place] = qb_rater(A, b, t);
+                A.sims[ob + place] = s;
+                A.devs[ob + place] = A.edev[t];
+            }
+        }
+        total += __popcll(hit);
+    }
+    if (by_weight && A.cap > 0 && total > 0) {
+        // place = the number of terms that go first under (|similarity| descending, summation place ascending); segment
+        // position orders the terms as the summation place does.  An entry with similarity 0.0, or past the segment,
+        // broadcasts magnitude 0.0, which goes before no term (a term's magnitude is > 0) and is counted by none.
+        for (uint32_t own = lo; own < hi; own += 64 * QBX_OWN) {
+            uint32_t x[QBX_OWN], t[QBX_OWN], rank[QBX_OWN];
+            double s[QBX_OWN], a[QBX_OWN];
+#pragma unroll
+            for (int q = 0; q < QBX_OWN; ++q) {
+                x[q] = own + 64u * q + lane;
+                t[q] = 0;
+                s[q] = 0.0;
+                rank[q] = 0;
+                if (x[q] < hi) {
+                    t[q] = A.val[x[q]];
+                    s[q] = A.esim[t[q]];
+                }
+                a[q] = fabs(s[q]);
+            }
+            for (uint32_t yb = lo; yb < hi; yb += 64) {
+                const uint32_t y = yb + lane;
+                const double sy = y < hi ? fabs(A.esim[A.val[y]]) : 0.0;
+                const int32_t sy_lo = __double2loint(sy), sy_hi = __double2hiint(sy);
+                const int cnt = (int)min(64u, hi - yb);
+                for (int l = 0; l < cnt; ++l) {
+                    const double m = __hiloint2double(__builtin_amdgcn_readlane(sy_hi, l), __builtin_amdgcn_readlane(sy_lo, l));
+                    const uint32_t yl = yb + (uint32_t)l;
+#pragma unroll
+                    for (int q = 0; q < QBX_OWN; ++q) rank[q] += (uint32_t)(m > a[q] || (m == a[q] && yl < x[q]));
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < QBX_OWN; ++q) {
+                if (s[q] != 0.0 && rank[q] < (uint32_t)A.cap) {
+                    A.raters[ob + rank[q]] = qb_rater(A, b, t[q]);
+                    A.sims[ob + rank[q]] = s[q];
+                    A.devs[ob + rank[q]] = A.edev[t[q]];
+                }
+            }
+        }
+    }
+    if (lane == 0) {
+        // what k_q_fold and k_qb_pred wrote for the cell: the fold over all terms and the predict call's answer
+        const int64_t cell = (int64_t)b * A.I + c;
+        A.counts[jj] = total;
+        if (A.sums) {
+            A.sums[2 * jj] = A.num[cell];
+            A.sums[2 * jj + 1] = A.den[cell];
+        }
+        if (A.out_pred) A.out_pred[jj] = A.pred[cell];
+    }
+}
+
 // k_reco_pred_keys (reco.hip) over [C][I]: ascending key <=> descending prediction, rated items last, -0.0 == +0.0;
 // the input order inside a slot is ascending raw id (by_id), val = slot * I + dense item
 __global__ void k_qb_reco_keys(int32_t C, int32_t I, const uint32_t* __restrict__ by_id, const double* __restrict__ pred,
@@ -828,6 +1008,25 @@ void foldin_batch_pick(const Train& tr, QueryBatchScratch& bs, const int32_t* d_
     if (m <= 0) return;
     k_qb_pick<<<(unsigned)ceil_div(m, TPB), TPB, 0, st>>>(m, d_items, d_slot, tr.i_table.p, table_cells(tr), tr.ikeys.p, tr.I,
                                                           bs.pred.p, bs.scal.p, d_out);
+    KN_HIP(hipGetLastError());
+}
+
+void foldin_batch_explain(const Train& tr, QueryBatchScratch& bs, int32_t C, int32_t take, int64_t E, const int32_t* d_items,
+                          const int32_t* d_slot, int64_t r0, int64_t n, int32_t order, int32_t cap, int32_t* d_raters,
+                          double* d_sims, double* d_devs, int32_t* d_counts, double* d_sums, double* d_pred, hipStream_t st) {
+    if (n <= 0) return;
+    (void)C;
+    QbExplainArgs A{};
+    A.items = d_items; A.slot = d_slot;
+    A.i_table = tr.i_table.p; A.i_cells = table_cells(tr); A.ikeys = tr.ikeys.p;
+    A.I = tr.I; A.take = take; A.order = order; A.cap = cap;
+    A.E = E;
+    A.key = bs.e_k64_b.p; A.val = bs.e_v32_b.p; A.edev = bs.e_dev.p; A.esim = bs.e_sim.p;
+    A.ebase = bs.ebase.p; A.off = bs.off.p; A.nbr = bs.nbr_idx.p; A.uid = tr.uid.p;
+    A.num = bs.num.p; A.den = bs.den.p; A.pred = bs.pred.p; A.scal = bs.scal.p;
+    A.raters = d_raters; A.sims = d_sims; A.devs = d_devs; A.counts = d_counts; A.sums = d_sums; A.out_pred = d_pred;
+    KN_TRACE_DISPATCH("qb_explain order=%d", (int)order);
+    k_qb_explain<<<(unsigned)ceil_div(n, QBX_WAVES), QBX_WAVES * 64, 0, st>>>(A, r0, n);
     KN_HIP(hipGetLastError());
 }
 
