@@ -88,7 +88,7 @@ struct knncf_handle {
     DArr<int32_t> ex_raters, ex_counts;
     DArr<double> ex_sims, ex_devs, ex_sums, ex_pred;
     // one launch of the query explanations (QB_EXPLAIN): the same outputs of its rows in ONE block, 20 * cap + 28 bytes per
-    // row, so that one copy brings a sub-range back
+    // row, so that one copy brings a sub-range back (explain_pack)
     DArr<double> ex_pack;
     // host mirrors for scalar queries
     std::vector<uint32_t> h_ukeys, h_ikeys;
@@ -1076,7 +1076,8 @@ int64_t query_batch_chunk(knncf_handle* h, int64_t budget) {
 }
 
 // rows per chunk of knncf_explain_batch, and per launch of the query explanations: the rule of knncf.h ("Explanations")
-int64_t explain_rows(int64_t budget, int32_t cap) { return std::max<int64_t>(budget / (20 * (int64_t)cap + 28), 1); }
+size_t explain_row_bytes(int32_t cap) { return 20 * (size_t)cap + 28; }
+int64_t explain_rows(int64_t budget, int32_t cap) { return std::max<int64_t>(budget / (int64_t)explain_row_bytes(cap), 1); }
 int64_t explain_batch_chunk(knncf_handle* h, int32_t cap) { return explain_rows(batch_budget(h), cap); }
 
 // the first query that was refused (-1: none) and why
@@ -1085,319 +1086,384 @@ struct QueryFailure {
     const char* reason = "";
 };
 
-// where QB_EXPLAIN writes: row j of the call is requested item j of the pred_offsets / pred_items CSR
-struct ExplainOut {
-    int32_t order, cap;
-    int64_t rows;     // R: rows per launch (filled in by do_query_batch / do_query_single)
-    int32_t* raters;  // [m * cap], row stride cap (unused with cap == 0)
-    double* sims;
-    double* devs;
-    int32_t* counts;  // [m]
-    double* sums;     // [2 m] or null
-    double* pred;     // [m] or null
+// ---- the explain outputs of a launch as one block (QB_EXPLAIN) -----------------------------------------------------------------
+// The rows of a launch lie in one device block, so that one copy brings them back: sims, devs [nr * cap], sums [2 nr],
+// predictions [nr] as doubles, then raters [nr * cap] and counts [nr] as int32 — the 20 * cap + 28 bytes per row that both chunk
+// rules of knncf.h ("Explanations") divide by (explain_row_bytes).
+// `like`'s order and cap over the block of nr rows at base (a device or a host address)
+ExplainCells explain_pack(double* base, int64_t nr, const ExplainCells& like) {
+    const size_t cells = (size_t)nr * (size_t)like.cap;
+    ExplainCells o = like;
+    o.sims = base; o.devs = base + cells; o.sums = base + 2 * cells; o.pred = o.sums + 2 * nr;
+    o.raters = reinterpret_cast<int32_t*>(o.pred + nr); o.counts = o.raters + cells;
+    return o;
+}
+// rows [0, nr) of a block on the host into the caller's arrays: row r goes to row rows[r].  The cells of a row beyond its
+// terms stay as the caller left them
+void explain_scatter(const ExplainCells& from, int64_t nr, const ExplainCells& to, const int64_t* rows) {
+    for (int64_t r = 0, cap = to.cap; r < nr; ++r) {
+        const int64_t j = rows[r];
+        to.counts[j] = from.counts[r];
+        if (to.sums) { to.sums[2 * j] = from.sums[2 * r]; to.sums[2 * j + 1] = from.sums[2 * r + 1]; }
+        if (to.pred) to.pred[j] = from.pred[r];
+        const size_t at = (size_t)r * cap, dst = (size_t)j * cap;
+        const int64_t t = std::min<int64_t>(from.counts[r], cap);
+        std::copy(from.raters + at, from.raters + at + t, to.raters + dst);
+        std::copy(from.sims + at, from.sims + at + t, to.sims + dst);
+        std::copy(from.devs + at, from.devs + at + t, to.devs + dst);
+    }
+}
+
+// ---- one request type for every family, mode and form ---------------------------------------------------------------------
+// A batch form fills users, B and the offsets arrays and leaves the last four fields 0.  A single form fills user, n_ratings,
+// n_removed and m instead and leaves users, B and the three offsets arrays 0: do_query_single makes them (a chunk of one); its
+// counts is the caller's *count.
+struct QueryCall {
+    QueryFamily family;
+    QueryBatchMode mode;
+    int predictor;
+    const int32_t* users;            // [B]
+    int64_t B;
+    const int64_t* offsets;          // [B + 1] query b's rows are items / ratings [offsets[b], offsets[b + 1])
+    const int32_t* items;
+    const double* ratings;
+    const int64_t* removed_offsets;  // QF_REVISE (null otherwise): [B + 1] into removed_items
+    const int32_t* removed_items;    // QF_REVISE: the train items each query's user drops
+    const int64_t* pred_offsets;     // QB_PREDICT, QB_EXPLAIN: [B + 1] into pred_items; row j of the call is pred_items[j]
+    const int32_t* pred_items;       // QB_PREDICT, QB_EXPLAIN: the requested items
+    int32_t width;                   // QB_NEIGHBORS: cap; QB_RECOMMEND: n
+    int32_t* out_i;                  // QB_NEIGHBORS: ids [B * cap]; QB_RECOMMEND: items [B * n]; unused otherwise
+    double* out_d;                   // QB_NEIGHBORS: sims [B * cap]; QB_RECOMMEND: predictions [B * n]; QB_PREDICT: [pred_offsets[B]]
+    int32_t* counts;                 // QB_NEIGHBORS, QB_RECOMMEND: [B]
+    int32_t* statuses;               // [B]
+    ExplainCells ex;                 // QB_EXPLAIN: pred_offsets[B] rows
+    int32_t user;                    // single forms only, from here on
+    int64_t n_ratings, n_removed, m;
 };
 
-// The B validated queries in chunks of `chunk`: statuses[b] and, where it is KNNCF_OK, query b's answer.
-// mode QB_NEIGHBORS: width = cap, out_i / out_d = ids / sims [B * cap]; QB_RECOMMEND: width = n, out_i / out_d = items /
-// predictions [B * n]; QB_PREDICT: out_d [pred_offsets[B]].  QF_REVISE: removed_items [removed_offsets[b], removed_offsets[b + 1])
-// are the train items query b's user drops (null for the other families).  QB_EXPLAIN: the rows of pred_offsets / pred_items
-// as QB_PREDICT takes them, answered into *ex; a refused query gets ex->counts = 0 on its rows
-QueryFailure run_query_chunks(knncf_handle* h, QueryFamily family, QueryBatchMode mode, int64_t chunk, const int32_t* users,
-                              const int64_t* removed_offsets, const int32_t* removed_items,
-                              const int64_t* offsets, const int32_t* items, const double* ratings, int64_t B, int32_t width, const int64_t* pred_offsets,
-                              const int32_t* pred_items, int32_t* out_i, double* out_d, int32_t* counts, int32_t* statuses,
-                              const ExplainOut* ex = nullptr) {
-    h->prep.join_commit(h->stream);
-    const Train& tr = h->tr;
+// One builder per mode: `rows` names the family and the queries (either form), the rest is what the mode answers into
+QueryCall neighbors_call(QueryCall rows, int32_t cap, int32_t* ids, double* sims, int32_t* counts) {
+    rows.mode = QB_NEIGHBORS; rows.predictor = KNNCF_PRED_KNN; rows.width = cap;
+    rows.out_i = ids; rows.out_d = sims; rows.counts = counts;
+    return rows;
+}
+QueryCall predict_call(QueryCall rows, int predictor, double* out) {
+    rows.mode = QB_PREDICT; rows.predictor = predictor; rows.out_d = out;
+    return rows;
+}
+QueryCall recommend_call(QueryCall rows, int predictor, int32_t n, int32_t* out_items, double* out_preds, int32_t* counts) {
+    rows.mode = QB_RECOMMEND; rows.predictor = predictor; rows.width = n;
+    rows.out_i = out_items; rows.out_d = out_preds; rows.counts = counts;
+    return rows;
+}
+QueryCall explain_call(QueryCall rows, int predictor, const ExplainCells& ex) {
+    rows.mode = QB_EXPLAIN; rows.predictor = predictor; rows.ex = ex;
+    return rows;
+}
+bool wants_rows(QueryBatchMode mode) { return mode == QB_PREDICT || mode == QB_EXPLAIN; }
+
+// ---- the chunk loop ---------------------------------------------------------------------------------------------------------
+// what one call's chunks share: the host vectors are reused from chunk to chunk
+struct ChunkState {
+    QueryFailure first;
+    int32_t take = 0, C = 0;  // min(k, U); pack_chunk: the chunk's C answerable queries, slot after slot
+    std::vector<int64_t> slot_query, qo, ao, ro;
+    std::vector<int32_t> s_users, s_items, s_self, s_removed;
+    std::vector<double> s_ratings;
+    std::vector<long long> info;  // [4 C] of foldin_batch_neighbors
+    std::vector<int32_t> good;    // settle_statuses: the slots whose query is KNNCF_OK
+    std::vector<int64_t> ebase;   // [C + 1] of foldin_batch_predictions
+    // the answers on their way back
+    std::vector<int32_t> h_idx, h_items, pick_slot, pick_items;
+    std::vector<int64_t> pick_row;
+    std::vector<double> h_vals;
+};
+
+void fail(const QueryCall& q, ChunkState& cs, int64_t b, int status, const char* why) {
+    q.statuses[b] = status;
+    if (q.counts) q.counts[b] = 0;
+    if (q.mode == QB_EXPLAIN) std::fill(q.ex.counts + q.pred_offsets[b], q.ex.counts + q.pred_offsets[b + 1], 0);
+    if (cs.first.query < 0 || b < cs.first.query) cs.first = {b, why};
+}
+
+// the per-query admission checks of queries [c0, c1) and the slots of those that pass; returns their number
+int32_t pack_chunk(knncf_handle* h, const QueryCall& q, ChunkState& cs, int64_t c0, int64_t c1) {
+    const bool update = q.family != QF_FOLD_IN, revise = q.family == QF_REVISE;
+    cs.slot_query.clear(); cs.s_users.clear(); cs.s_items.clear(); cs.s_ratings.clear(); cs.s_self.clear(); cs.s_removed.clear();
+    cs.qo.assign(1, 0); cs.ao.assign(1, 0); cs.ro.assign(1, 0);
+    for (int64_t b = c0; b < c1; ++b) {
+        const int64_t nb = q.offsets[b + 1] - q.offsets[b];
+        const int64_t nr = revise ? q.removed_offsets[b + 1] - q.removed_offsets[b] : 0;
+        const int32_t du = dense_user(h, q.users[b]);
+        // rows of the user in aug: its train rows (update queries) without the removed ones (revise queries), and the
+        // given ones; every train row is seeded, so all of them count against the cap
+        const int64_t seeded = nb + (update && du >= 0 ? train_row_length(h, du) : 0);
+        if (nr > 0 && du < 0) { fail(q, cs, b, KNNCF_E_INVALID, "a removed item for a user that is not in the training set"); continue; }
+        if (nr > seeded - nb) { fail(q, cs, b, KNNCF_E_INVALID, "more removed items than the user has train rows (one is not rated in train or listed twice)"); continue; }
+        const int64_t rows = seeded - nr;
+        if (rows <= 0) { fail(q, cs, b, KNNCF_E_INVALID, nr > 0 ? "the removals leave the user without a row" : "null ratings or n_ratings <= 0"); continue; }
+        if (seeded > QUERY_MAX_RATINGS) { fail(q, cs, b, KNNCF_E_UNSUPPORTED, "more than 65536 ratings"); continue; }
+        if (!update && du >= 0) { fail(q, cs, b, KNNCF_E_INVALID, "the user occurs in the training set"); continue; }
+        if (nr > 0) cs.s_removed.insert(cs.s_removed.end(), q.removed_items + q.removed_offsets[b], q.removed_items + q.removed_offsets[b + 1]);
+        cs.ro.push_back((int64_t)cs.s_removed.size());
+        cs.slot_query.push_back(b);
+        cs.s_users.push_back(q.users[b]);
+        cs.s_self.push_back(du);
+        cs.s_items.insert(cs.s_items.end(), q.items + q.offsets[b], q.items + q.offsets[b + 1]);
+        cs.s_ratings.insert(cs.s_ratings.end(), q.ratings + q.offsets[b], q.ratings + q.offsets[b + 1]);
+        cs.ao.push_back((int64_t)cs.s_items.size());
+        cs.qo.push_back(cs.qo.back() + rows);
+    }
+    return cs.C = (int32_t)cs.slot_query.size();
+}
+
+// the device's status bits of every slot as the query's status, in this order of precedence; cs.good = the slots left to
+// answer, returns their number
+size_t settle_statuses(const QueryCall& q, ChunkState& cs) {
+    cs.good.clear();
+    for (int32_t s = 0; s < cs.C; ++s) {
+        const uint64_t bits = (uint64_t)cs.info[4 * s];
+        const int64_t b = cs.slot_query[s];
+        if (bits & QUERY_ST_RM_UNRATED) fail(q, cs, b, KNNCF_E_INVALID, "a removed item that the user did not rate in train");
+        else if (bits & QUERY_ST_RM_TWICE) fail(q, cs, b, KNNCF_E_INVALID, "a removed item listed twice");
+        else if (bits & ST_DUPLICATE) fail(q, cs, b, KNNCF_E_DUPLICATE, "the ratings repeat an item");
+        else if (bits & ST_NONFINITE) fail(q, cs, b, KNNCF_E_NONFINITE, "scale() == 0 gives a non-finite deviation");
+        else if (bits & QUERY_ST_NEG_MEAN) fail(q, cs, b, KNNCF_E_UNSUPPORTED, "a negative mean rating (the predictor would answer aug's global average)");
+        else { q.statuses[b] = KNNCF_OK; cs.good.push_back(s); }
+    }
+    return cs.good.size();
+}
+
+void answer_neighbors(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
+    const QueryBatchScratch& bs = h->query_batch;
+    const int32_t take = cs.take, width = q.width, c = std::min(take, width);
+    if (c > 0) {
+        cs.h_idx.resize((size_t)cs.C * take); cs.h_vals.resize((size_t)cs.C * take);
+        KN_HIP(hipMemcpyAsync(cs.h_idx.data(), bs.nbr_idx.p, cs.h_idx.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        KN_HIP(hipMemcpyAsync(cs.h_vals.data(), bs.nbr_sim.p, cs.h_vals.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        KN_HIP(hipStreamSynchronize(h->stream));
+        load_host_ids(h);
+    }
+    for (const int32_t s : cs.good) {
+        const int64_t b = cs.slot_query[s];
+        // neighbours of slot s: (allUsers - u) :608 drops a user of the fit
+        const int32_t mine = q.family != QF_FOLD_IN && cs.s_self[s] >= 0 ? std::min(take, h->tr.U - 1) : take;
+        for (int32_t j = 0; j < std::min(c, mine); ++j) {
+            q.out_i[b * width + j] = h->h_uid[cs.h_idx[(size_t)s * take + j]];
+            q.out_d[b * width + j] = cs.h_vals[(size_t)s * take + j];
+        }
+        q.counts[b] = mine;
+    }
+}
+
+// bs.pred / bs.rated of the chunk: launched only when the chunk has something to answer
+void fold_chunk(knncf_handle* h, ChunkState& cs) {
+    cs.ebase.assign((size_t)cs.C + 1, 0);
+    for (int32_t s = 0; s < cs.C; ++s) cs.ebase[s + 1] = cs.ebase[s] + cs.info[4 * s + 2];
+    foldin_batch_predictions(h->tr, h->query_batch, h->prep.sort, cs.C, cs.take, cs.ebase.data(), h->stream);
+}
+
+// QB_PREDICT, QB_EXPLAIN: the requested rows of the chunk's good queries, (item, slot) each, folded and uploaded to
+// bs.pick_items / bs.pick_slot; QB_EXPLAIN: cs.pick_row = the row of the call behind each.  Returns their number m (0: nothing
+// was launched)
+int64_t upload_picks(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
+    cs.pick_slot.clear(); cs.pick_items.clear(); cs.pick_row.clear();
+    for (const int32_t s : cs.good) {
+        const int64_t b = cs.slot_query[s];
+        cs.pick_items.insert(cs.pick_items.end(), q.pred_items + q.pred_offsets[b], q.pred_items + q.pred_offsets[b + 1]);
+        cs.pick_slot.insert(cs.pick_slot.end(), (size_t)(q.pred_offsets[b + 1] - q.pred_offsets[b]), s);
+        if (q.mode == QB_EXPLAIN)
+            for (int64_t j = q.pred_offsets[b]; j < q.pred_offsets[b + 1]; ++j) cs.pick_row.push_back(j);
+    }
+    const int64_t m = (int64_t)cs.pick_items.size();
+    if (m == 0) return 0;
+    fold_chunk(h, cs);
+    QueryBatchScratch& bs = h->query_batch;
+    bs.pick_items.ensure(m); bs.pick_slot.ensure(m);
+    if (q.mode == QB_PREDICT) bs.pick_out.ensure(m);
+    KN_HIP(hipMemcpyAsync(bs.pick_items.p, cs.pick_items.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    KN_HIP(hipMemcpyAsync(bs.pick_slot.p, cs.pick_slot.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    return m;
+}
+
+void answer_predict(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
+    const int64_t m = upload_picks(h, q, cs);
+    if (m == 0) return;
     QueryBatchScratch& bs = h->query_batch;
     hipStream_t st = h->stream;
-    const int32_t take = std::max(0, std::min(h->cfg.k, tr.U));
-    QueryFailure first;
-    auto fail = [&](int64_t b, int status, const char* why) {
-        statuses[b] = status;
-        if (counts) counts[b] = 0;
-        if (mode == QB_EXPLAIN) std::fill(ex->counts + pred_offsets[b], ex->counts + pred_offsets[b + 1], 0);
-        if (first.query < 0 || b < first.query) first = {b, why};
-    };
-    const bool update = family != QF_FOLD_IN, revise = family == QF_REVISE;
-    std::vector<int64_t> slot_query, qo, ao, ro, ebase;
-    std::vector<int32_t> s_users, s_items, s_self, s_removed, h_idx, h_items, pick_slot, pick_items;
-    std::vector<double> s_ratings, h_vals;
-    std::vector<long long> info;
-    std::vector<int64_t> pick_row;
-    const int64_t ex_rows = mode == QB_EXPLAIN ? ex->rows : 0;
-    for (int64_t c0 = 0; c0 < B; c0 += chunk) {
-        const int64_t c1 = std::min(B, c0 + chunk);
-        // the chunk's answerable queries, slot after slot
-        slot_query.clear(); s_users.clear(); s_items.clear(); s_ratings.clear(); s_self.clear(); s_removed.clear();
-        qo.assign(1, 0);
-        ao.assign(1, 0);
-        ro.assign(1, 0);
-        for (int64_t b = c0; b < c1; ++b) {
-            const int64_t nb = offsets[b + 1] - offsets[b];
-            const int64_t nr = revise ? removed_offsets[b + 1] - removed_offsets[b] : 0;
-            const int32_t du = dense_user(h, users[b]);
-            // rows of the user in aug: its train rows (update queries) without the removed ones (revise queries), and the
-            // given ones; every train row is seeded, so all of them count against the cap
-            const int64_t seeded = nb + (update && du >= 0 ? train_row_length(h, du) : 0);
-            if (nr > 0 && du < 0) { fail(b, KNNCF_E_INVALID, "a removed item for a user that is not in the training set"); continue; }
-            if (nr > seeded - nb) { fail(b, KNNCF_E_INVALID, "more removed items than the user has train rows (one is not rated in train or listed twice)"); continue; }
-            const int64_t rows = seeded - nr;
-            if (rows <= 0) { fail(b, KNNCF_E_INVALID, nr > 0 ? "the removals leave the user without a row" : "null ratings or n_ratings <= 0"); continue; }
-            if (seeded > QUERY_MAX_RATINGS) { fail(b, KNNCF_E_UNSUPPORTED, "more than 65536 ratings"); continue; }
-            if (!update && du >= 0) { fail(b, KNNCF_E_INVALID, "the user occurs in the training set"); continue; }
-            if (nr > 0) s_removed.insert(s_removed.end(), removed_items + removed_offsets[b], removed_items + removed_offsets[b + 1]);
-            ro.push_back((int64_t)s_removed.size());
-            slot_query.push_back(b);
-            s_users.push_back(users[b]);
-            s_self.push_back(du);
-            s_items.insert(s_items.end(), items + offsets[b], items + offsets[b + 1]);
-            s_ratings.insert(s_ratings.end(), ratings + offsets[b], ratings + offsets[b + 1]);
-            ao.push_back((int64_t)s_items.size());
-            qo.push_back(qo.back() + rows);
-        }
-        const int32_t C = (int32_t)slot_query.size();
-        if (C == 0) continue;
-        info.assign((size_t)4 * C, 0);
-        foldin_batch_neighbors(tr, bs, h->prep.sort, C, s_users.data(), qo.data(), s_items.data(), s_ratings.data(),
-                               update ? s_self.data() : nullptr, update ? ao.data() : nullptr, h->cfg.k, info.data(), st,
-                               revise ? ro.data() : nullptr, revise ? s_removed.data() : nullptr);
-        // neighbours of slot s: (allUsers - u) :608 drops a user of the fit
-        auto take_of = [&](int32_t s) { return update && s_self[s] >= 0 ? std::min(take, tr.U - 1) : take; };
-        int32_t good = 0;
-        for (int32_t s = 0; s < C; ++s) {
-            const uint64_t bits = (uint64_t)info[4 * s];
-            const int64_t b = slot_query[s];
-            if (bits & QUERY_ST_RM_UNRATED) fail(b, KNNCF_E_INVALID, "a removed item that the user did not rate in train");
-            else if (bits & QUERY_ST_RM_TWICE) fail(b, KNNCF_E_INVALID, "a removed item listed twice");
-            else if (bits & ST_DUPLICATE) fail(b, KNNCF_E_DUPLICATE, "the ratings repeat an item");
-            else if (bits & ST_NONFINITE) fail(b, KNNCF_E_NONFINITE, "scale() == 0 gives a non-finite deviation");
-            else if (bits & QUERY_ST_NEG_MEAN) fail(b, KNNCF_E_UNSUPPORTED, "a negative mean rating (the predictor would answer aug's global average)");
-            else { statuses[b] = KNNCF_OK; ++good; }
-        }
-        if (good == 0) continue;
-        if (mode == QB_NEIGHBORS) {
-            const int32_t c = std::min(take, width);
-            if (c > 0) {
-                h_idx.resize((size_t)C * take); h_vals.resize((size_t)C * take);
-                KN_HIP(hipMemcpyAsync(h_idx.data(), bs.nbr_idx.p, h_idx.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-                KN_HIP(hipMemcpyAsync(h_vals.data(), bs.nbr_sim.p, h_vals.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-                KN_HIP(hipStreamSynchronize(st));
-                load_host_ids(h);
-            }
-            for (int32_t s = 0; s < C; ++s) {
-                const int64_t b = slot_query[s];
-                if (statuses[b] != KNNCF_OK) continue;
-                for (int32_t j = 0; j < std::min(c, take_of(s)); ++j) {
-                    out_i[b * width + j] = h->h_uid[h_idx[(size_t)s * take + j]];
-                    out_d[b * width + j] = h_vals[(size_t)s * take + j];
-                }
-                counts[b] = take_of(s);
-            }
-            continue;
-        }
-        ebase.assign((size_t)C + 1, 0);
-        for (int32_t s = 0; s < C; ++s) ebase[s + 1] = ebase[s] + info[4 * s + 2];
-        if (mode == QB_PREDICT) {
-            pick_slot.clear(); pick_items.clear();
-            for (int32_t s = 0; s < C; ++s) {
-                const int64_t b = slot_query[s];
-                if (statuses[b] != KNNCF_OK) continue;
-                pick_items.insert(pick_items.end(), pred_items + pred_offsets[b], pred_items + pred_offsets[b + 1]);
-                pick_slot.insert(pick_slot.end(), (size_t)(pred_offsets[b + 1] - pred_offsets[b]), s);
-            }
-            const int64_t m = (int64_t)pick_items.size();
-            if (m == 0) continue;
-            foldin_batch_predictions(tr, bs, h->prep.sort, C, take, ebase.data(), st);
-            bs.pick_items.ensure(m); bs.pick_slot.ensure(m); bs.pick_out.ensure(m);
-            KN_HIP(hipMemcpyAsync(bs.pick_items.p, pick_items.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            KN_HIP(hipMemcpyAsync(bs.pick_slot.p, pick_slot.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            foldin_batch_pick(tr, bs, bs.pick_items.p, bs.pick_slot.p, m, bs.pick_out.p, st);
-            h_vals.resize((size_t)m);
-            KN_HIP(hipMemcpyAsync(h_vals.data(), bs.pick_out.p, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
-            KN_HIP(hipStreamSynchronize(st));
-            int64_t at = 0;
-            for (int32_t s = 0; s < C; ++s) {
-                const int64_t b = slot_query[s];
-                if (statuses[b] != KNNCF_OK) continue;
-                const int64_t mb = pred_offsets[b + 1] - pred_offsets[b];
-                std::copy(h_vals.begin() + at, h_vals.begin() + at + mb, out_d + pred_offsets[b]);
-                at += mb;
-            }
-            continue;
-        }
-        if (mode == QB_EXPLAIN) {
-            // the chunk's requested rows as QB_PREDICT uploads them; pick_row = the row of the call behind each
-            pick_slot.clear(); pick_items.clear(); pick_row.clear();
-            for (int32_t s = 0; s < C; ++s) {
-                const int64_t b = slot_query[s];
-                if (statuses[b] != KNNCF_OK) continue;
-                pick_items.insert(pick_items.end(), pred_items + pred_offsets[b], pred_items + pred_offsets[b + 1]);
-                pick_slot.insert(pick_slot.end(), (size_t)(pred_offsets[b + 1] - pred_offsets[b]), s);
-                for (int64_t j = pred_offsets[b]; j < pred_offsets[b + 1]; ++j) pick_row.push_back(j);
-            }
-            const int64_t m = (int64_t)pick_items.size();
-            if (m == 0) continue;
-            foldin_batch_predictions(tr, bs, h->prep.sort, C, take, ebase.data(), st);
-            bs.pick_items.ensure(m); bs.pick_slot.ensure(m);
-            KN_HIP(hipMemcpyAsync(bs.pick_items.p, pick_items.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            KN_HIP(hipMemcpyAsync(bs.pick_slot.p, pick_slot.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            // sub-ranges of R rows: the chunk's fold results stay where they are between the launches.  The outputs of a
-            // launch of nr rows lie in one block — sims, devs [nr * cap], sums [2 nr], predictions [nr] as doubles, then
-            // raters [nr * cap] and counts [nr] as int32: nr * (20 * cap + 28) bytes — and come back in one copy
-            const int32_t cap = ex->cap;
-            const int64_t R = std::min(ex_rows, m);
-            const size_t pack = ((size_t)R * (20 * (size_t)cap + 28) + 7) / 8;
-            h->ex_pack.ensure(pack);
-            h_vals.resize(pack);
-            for (int64_t r0 = 0; r0 < m; r0 += R) {
-                const int64_t nr = std::min(R, m - r0);
-                const size_t cells = (size_t)nr * (size_t)cap, doubles = 2 * cells + 3 * (size_t)nr;
-                auto lay = [&](double* base) {
-                    ExplainOut o = *ex;
-                    o.sims = base; o.devs = base + cells; o.sums = base + 2 * cells; o.pred = o.sums + 2 * nr;
-                    o.raters = reinterpret_cast<int32_t*>(base + doubles); o.counts = o.raters + cells;
-                    return o;
-                };
-                const ExplainOut d = lay(h->ex_pack.p), g = lay(h_vals.data());
-                foldin_batch_explain(tr, bs, C, take, ebase[C], bs.pick_items.p, bs.pick_slot.p, r0, nr, ex->order, cap, d.raters, d.sims,
-                                     d.devs, d.counts, d.sums, d.pred, st);
-                KN_HIP(hipMemcpyAsync(h_vals.data(), h->ex_pack.p, (size_t)nr * (20 * (size_t)cap + 28), hipMemcpyDeviceToHost, st));
-                KN_HIP(hipStreamSynchronize(st));
-                for (int64_t r = 0; r < nr; ++r) {  // (the cells of a row beyond its terms stay as the caller left them)
-                    const int64_t j = pick_row[(size_t)(r0 + r)];
-                    ex->counts[j] = g.counts[r];
-                    if (ex->sums) { ex->sums[2 * j] = g.sums[2 * r]; ex->sums[2 * j + 1] = g.sums[2 * r + 1]; }
-                    if (ex->pred) ex->pred[j] = g.pred[r];
-                    const size_t from = (size_t)r * cap, to = (size_t)j * cap;
-                    const int32_t t = std::min(g.counts[r], cap);
-                    std::copy(g.raters + from, g.raters + from + t, ex->raters + to);
-                    std::copy(g.sims + from, g.sims + from + t, ex->sims + to);
-                    std::copy(g.devs + from, g.devs + from + t, ex->devs + to);
-                }
-            }
-            continue;
-        }
-        // QB_RECOMMEND
-        int32_t widest = 0;
-        for (int32_t s = 0; s < C; ++s) {
-            const int64_t b = slot_query[s];
-            if (statuses[b] != KNNCF_OK) continue;
-            counts[b] = (int32_t)std::max<int64_t>(0, std::min<int64_t>(width, (int64_t)tr.I - info[4 * s + 1]));
-            widest = std::max(widest, counts[b]);
-        }
-        if (widest == 0) continue;
-        foldin_batch_predictions(tr, bs, h->prep.sort, C, take, ebase.data(), st);
-        const size_t cells = (size_t)C * widest;
-        bs.out_items.ensure(cells); bs.out_preds.ensure(cells);
-        foldin_batch_recommend(tr, bs, h->prep.sort, C, widest, bs.out_items.p, bs.out_preds.p, st);
-        h_items.resize(cells); h_vals.resize(cells);
-        KN_HIP(hipMemcpyAsync(h_items.data(), bs.out_items.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        KN_HIP(hipMemcpyAsync(h_vals.data(), bs.out_preds.p, cells * sizeof(double), hipMemcpyDeviceToHost, st));
+    foldin_batch_pick(h->tr, bs, bs.pick_items.p, bs.pick_slot.p, m, bs.pick_out.p, st);
+    cs.h_vals.resize((size_t)m);
+    KN_HIP(hipMemcpyAsync(cs.h_vals.data(), bs.pick_out.p, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
+    KN_HIP(hipStreamSynchronize(st));
+    int64_t at = 0;
+    for (const int32_t s : cs.good) {
+        const int64_t b = cs.slot_query[s];
+        const int64_t mb = q.pred_offsets[b + 1] - q.pred_offsets[b];
+        std::copy(cs.h_vals.begin() + at, cs.h_vals.begin() + at + mb, q.out_d + q.pred_offsets[b]);
+        at += mb;
+    }
+}
+
+// sub-ranges of at most ex_rows rows: the chunk's fold results stay where they are between the launches, and every launch's
+// block comes back in one copy
+void answer_explain(knncf_handle* h, const QueryCall& q, ChunkState& cs, int64_t ex_rows) {
+    const int64_t m = upload_picks(h, q, cs);
+    if (m == 0) return;
+    QueryBatchScratch& bs = h->query_batch;
+    hipStream_t st = h->stream;
+    const int64_t R = std::min(ex_rows, m);
+    const size_t pack = ((size_t)R * explain_row_bytes(q.ex.cap) + 7) / 8;  // doubles
+    h->ex_pack.ensure(pack);
+    cs.h_vals.resize(pack);
+    for (int64_t r0 = 0; r0 < m; r0 += R) {
+        const int64_t nr = std::min(R, m - r0);
+        const QbExplainRows rows{cs.take, cs.ebase[cs.C], bs.pick_items.p, bs.pick_slot.p, r0, nr};
+        foldin_batch_explain(h->tr, bs, rows, explain_pack(h->ex_pack.p, nr, q.ex), st);
+        KN_HIP(hipMemcpyAsync(cs.h_vals.data(), h->ex_pack.p, (size_t)nr * explain_row_bytes(q.ex.cap), hipMemcpyDeviceToHost, st));
         KN_HIP(hipStreamSynchronize(st));
-        for (int32_t s = 0; s < C; ++s) {
-            const int64_t b = slot_query[s];
-            if (statuses[b] != KNNCF_OK) continue;
-            std::copy(h_items.begin() + (size_t)s * widest, h_items.begin() + (size_t)s * widest + counts[b], out_i + b * width);
-            std::copy(h_vals.begin() + (size_t)s * widest, h_vals.begin() + (size_t)s * widest + counts[b], out_d + b * width);
+        explain_scatter(explain_pack(cs.h_vals.data(), nr, q.ex), nr, q.ex, cs.pick_row.data() + r0);
+    }
+}
+
+void answer_recommend(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
+    QueryBatchScratch& bs = h->query_batch;
+    hipStream_t st = h->stream;
+    const int32_t width = q.width;
+    int32_t widest = 0;
+    for (const int32_t s : cs.good) {
+        const int64_t b = cs.slot_query[s];
+        q.counts[b] = (int32_t)std::max<int64_t>(0, std::min<int64_t>(width, (int64_t)h->tr.I - cs.info[4 * s + 1]));
+        widest = std::max(widest, q.counts[b]);
+    }
+    if (widest == 0) return;
+    fold_chunk(h, cs);
+    const size_t cells = (size_t)cs.C * widest;
+    bs.out_items.ensure(cells); bs.out_preds.ensure(cells);
+    foldin_batch_recommend(h->tr, bs, h->prep.sort, cs.C, widest, bs.out_items.p, bs.out_preds.p, st);
+    cs.h_items.resize(cells); cs.h_vals.resize(cells);
+    KN_HIP(hipMemcpyAsync(cs.h_items.data(), bs.out_items.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    KN_HIP(hipMemcpyAsync(cs.h_vals.data(), bs.out_preds.p, cells * sizeof(double), hipMemcpyDeviceToHost, st));
+    KN_HIP(hipStreamSynchronize(st));
+    for (const int32_t s : cs.good) {
+        const int64_t b = cs.slot_query[s];
+        std::copy(cs.h_items.begin() + (size_t)s * widest, cs.h_items.begin() + (size_t)s * widest + q.counts[b], q.out_i + b * width);
+        std::copy(cs.h_vals.begin() + (size_t)s * widest, cs.h_vals.begin() + (size_t)s * widest + q.counts[b], q.out_d + b * width);
+    }
+}
+
+// The validated queries of q in chunks of `chunk`: statuses[b] and, where it is KNNCF_OK, query b's answer in q's outputs.  A
+// refused query gets ex.counts = 0 on its rows (QB_EXPLAIN, answered ex_rows rows per launch)
+QueryFailure run_query_chunks(knncf_handle* h, const QueryCall& q, int64_t chunk, int64_t ex_rows) {
+    h->prep.join_commit(h->stream);
+    const bool update = q.family != QF_FOLD_IN, revise = q.family == QF_REVISE;
+    ChunkState cs;
+    cs.take = std::max(0, std::min(h->cfg.k, h->tr.U));
+    for (int64_t c0 = 0; c0 < q.B; c0 += chunk) {
+        if (pack_chunk(h, q, cs, c0, std::min(q.B, c0 + chunk)) == 0) continue;
+        cs.info.assign((size_t)4 * cs.C, 0);
+        foldin_batch_neighbors(h->tr, h->query_batch, h->prep.sort, cs.C, cs.s_users.data(), cs.qo.data(), cs.s_items.data(), cs.s_ratings.data(),
+                               update ? cs.s_self.data() : nullptr, update ? cs.ao.data() : nullptr, h->cfg.k, cs.info.data(), h->stream,
+                               revise ? cs.ro.data() : nullptr, revise ? cs.s_removed.data() : nullptr);
+        if (settle_statuses(q, cs) == 0) continue;
+        switch (q.mode) {
+            case QB_NEIGHBORS: answer_neighbors(h, q, cs); break;
+            case QB_PREDICT: answer_predict(h, q, cs); break;
+            case QB_EXPLAIN: answer_explain(h, q, cs, ex_rows); break;
+            case QB_RECOMMEND: answer_recommend(h, q, cs); break;
         }
     }
-    return first;
+    return cs.first;
 }
 
 // the refusals the explain forms add to those of the predict forms (knncf.h "Explanations of query predictions")
-void require_explain_order(const ExplainOut* ex) {
-    KN_REQUIRE(ex->cap >= 0, KNNCF_E_INVALID, "query explain: cap < 0");
-    KN_REQUIRE(ex->order == KNNCF_EXPLAIN_SUM_ORDER || ex->order == KNNCF_EXPLAIN_BY_WEIGHT, KNNCF_E_INVALID,
+void require_explain_order(const ExplainCells& ex) {
+    KN_REQUIRE(ex.cap >= 0, KNNCF_E_INVALID, "query explain: cap < 0");
+    KN_REQUIRE(ex.order == KNNCF_EXPLAIN_SUM_ORDER || ex.order == KNNCF_EXPLAIN_BY_WEIGHT, KNNCF_E_INVALID,
                "query explain: unknown order");
 }
-void require_explain_outputs(const ExplainOut* ex, int64_t m) {
-    KN_REQUIRE(m == 0 || (ex->counts && (ex->cap == 0 || (ex->raters && ex->sims && ex->devs))), KNNCF_E_INVALID,
+void require_explain_outputs(const ExplainCells& ex, int64_t m) {
+    KN_REQUIRE(m == 0 || (ex.counts && (ex.cap == 0 || (ex.raters && ex.sims && ex.devs))), KNNCF_E_INVALID,
                "query explain: null output");
 }
 
-void do_query_batch(knncf_handle* h, QueryFamily family, QueryBatchMode mode, int predictor, const int32_t* users,
-                    const int64_t* removed_offsets, const int32_t* removed_items, const int64_t* offsets, const int32_t* items, const double* ratings, int64_t B, int32_t width, const int64_t* pred_offsets,
-                    const int32_t* pred_items, int32_t* out_i, double* out_d, int32_t* counts, int32_t* statuses,
-                    const ExplainOut* ex = nullptr) {
+// a CSR's offsets as the batch forms take them: B + 1 of them, from 0, never decreasing; the two refusals' texts
+void require_offsets(const int64_t* o, int64_t B, const char* no_start, const char* decrease) {
+    KN_REQUIRE(o && o[0] == 0, KNNCF_E_INVALID, no_start);
+    for (int64_t b = 0; b < B; ++b) KN_REQUIRE(o[b] <= o[b + 1], KNNCF_E_INVALID, decrease);
+}
+
+void do_query_batch(knncf_handle* h, const QueryCall& q) {
+    const int64_t B = q.B;
     require_fitted(h, false);
     KN_REQUIRE(B >= 0, KNNCF_E_INVALID, "query batch: n_queries < 0");
-    KN_REQUIRE(mode == QB_PREDICT || mode == QB_EXPLAIN || width >= 0, KNNCF_E_INVALID, "query batch: cap or n < 0");
-    if (mode == QB_EXPLAIN) require_explain_order(ex);
-    require_query_support(h, predictor);
+    KN_REQUIRE(wants_rows(q.mode) || q.width >= 0, KNNCF_E_INVALID, "query batch: cap or n < 0");
+    if (q.mode == QB_EXPLAIN) require_explain_order(q.ex);
+    require_query_support(h, q.predictor);
     if (B == 0) return;
-    KN_REQUIRE(users && offsets && statuses && (mode == QB_PREDICT || mode == QB_EXPLAIN || counts), KNNCF_E_INVALID,
-               "query batch: null argument");
-    KN_REQUIRE(offsets[0] == 0, KNNCF_E_INVALID, "query batch: offsets[0] != 0");
-    for (int64_t b = 0; b < B; ++b) KN_REQUIRE(offsets[b] <= offsets[b + 1], KNNCF_E_INVALID, "query batch: offsets decrease");
-    KN_REQUIRE(offsets[B] < ((int64_t)1 << 31), KNNCF_E_INVALID, "query batch: 2^31 or more ratings in one call");
-    KN_REQUIRE(offsets[B] == 0 || (items && ratings), KNNCF_E_INVALID, "query batch: null ratings");
-    if (family == QF_REVISE) {
-        KN_REQUIRE(removed_offsets && removed_offsets[0] == 0, KNNCF_E_INVALID, "query batch: removed_offsets null or not starting at 0");
-        for (int64_t b = 0; b < B; ++b)
-            KN_REQUIRE(removed_offsets[b] <= removed_offsets[b + 1], KNNCF_E_INVALID, "query batch: removed_offsets decrease");
-        KN_REQUIRE(removed_offsets[B] < ((int64_t)1 << 31), KNNCF_E_INVALID, "query batch: 2^31 or more removed items in one call");
-        KN_REQUIRE(removed_offsets[B] == 0 || removed_items, KNNCF_E_INVALID, "query batch: null removed items");
+    KN_REQUIRE(q.users && q.offsets && q.statuses && (wants_rows(q.mode) || q.counts), KNNCF_E_INVALID, "query batch: null argument");
+    require_offsets(q.offsets, B, "query batch: offsets[0] != 0", "query batch: offsets decrease");
+    KN_REQUIRE(q.offsets[B] < ((int64_t)1 << 31), KNNCF_E_INVALID, "query batch: 2^31 or more ratings in one call");
+    KN_REQUIRE(q.offsets[B] == 0 || (q.items && q.ratings), KNNCF_E_INVALID, "query batch: null ratings");
+    if (q.family == QF_REVISE) {
+        require_offsets(q.removed_offsets, B, "query batch: removed_offsets null or not starting at 0", "query batch: removed_offsets decrease");
+        KN_REQUIRE(q.removed_offsets[B] < ((int64_t)1 << 31), KNNCF_E_INVALID, "query batch: 2^31 or more removed items in one call");
+        KN_REQUIRE(q.removed_offsets[B] == 0 || q.removed_items, KNNCF_E_INVALID, "query batch: null removed items");
     }
-    if (mode == QB_PREDICT) {
-        KN_REQUIRE(pred_offsets && pred_offsets[0] == 0, KNNCF_E_INVALID, "query batch: pred_offsets null or not starting at 0");
-        for (int64_t b = 0; b < B; ++b)
-            KN_REQUIRE(pred_offsets[b] <= pred_offsets[b + 1], KNNCF_E_INVALID, "query batch: pred_offsets decrease");
-        KN_REQUIRE(pred_offsets[B] == 0 || (pred_items && out_d), KNNCF_E_INVALID, "query batch: null prediction arguments");
-    } else if (mode == QB_EXPLAIN) {
-        KN_REQUIRE(pred_offsets && pred_offsets[0] == 0, KNNCF_E_INVALID, "query batch: pred_offsets null or not starting at 0");
-        for (int64_t b = 0; b < B; ++b)
-            KN_REQUIRE(pred_offsets[b] <= pred_offsets[b + 1], KNNCF_E_INVALID, "query batch: pred_offsets decrease");
-        KN_REQUIRE(pred_offsets[B] == 0 || pred_items, KNNCF_E_INVALID, "query batch: null prediction arguments");
-        require_explain_outputs(ex, pred_offsets[B]);
+    if (wants_rows(q.mode)) {
+        require_offsets(q.pred_offsets, B, "query batch: pred_offsets null or not starting at 0", "query batch: pred_offsets decrease");
+        KN_REQUIRE(q.pred_offsets[B] == 0 || (q.pred_items && (q.mode == QB_EXPLAIN || q.out_d)), KNNCF_E_INVALID,
+                   "query batch: null prediction arguments");
+        if (q.mode == QB_EXPLAIN) require_explain_outputs(q.ex, q.pred_offsets[B]);
     } else {
-        KN_REQUIRE(width == 0 || (out_i && out_d), KNNCF_E_INVALID, "query batch: null output");
+        KN_REQUIRE(q.width == 0 || (q.out_i && q.out_d), KNNCF_E_INVALID, "query batch: null output");
     }
     const int64_t budget = batch_budget(h);  // (one hipMemGetInfo for both rules)
-    ExplainOut rows_known;
-    if (mode == QB_EXPLAIN) {
-        rows_known = *ex;
-        rows_known.rows = explain_rows(budget, ex->cap);
-        ex = &rows_known;
-    }
-    const QueryFailure f = run_query_chunks(h, family, mode, query_batch_chunk(h, budget), users, removed_offsets, removed_items, offsets,
-                                            items, ratings, B, width, pred_offsets, pred_items, out_i, out_d, counts, statuses, ex);
+    const QueryFailure f = run_query_chunks(h, q, query_batch_chunk(h, budget), q.mode == QB_EXPLAIN ? explain_rows(budget, q.ex.cap) : 0);
     if (f.query >= 0) h->err = "query batch: query " + std::to_string(f.query) + ": " + f.reason;
 }
 
-// One query as a chunk of one: the query's status is the call's.  The entry points check their own output arguments first;
-// *count (neighbours: min(k, U), min(k, U - 1) for a user of the fit; recommendations: min(n, I - known items)) is written on
-// success.  An update query may come without rows (whether the user is in the fit is the chunk loop's to say).
-void do_query_single(knncf_handle* h, QueryFamily family, QueryBatchMode mode, int predictor, int32_t user,
-                     const int32_t* removed_items, int64_t n_removed, const int32_t* items, const double* ratings, int64_t n_ratings, int32_t width, const int32_t* pred_items, int64_t m, int32_t* out_i,
-                     double* out_d, int32_t* count, const ExplainOut* ex = nullptr) {
-    require_fitted(h, false);
-    if (mode == QB_EXPLAIN) {
-        require_explain_order(ex);
-        KN_REQUIRE(m >= 0 && (m == 0 || pred_items), KNNCF_E_INVALID, "bad prediction arguments");
-        require_explain_outputs(ex, m);
-    }
-    if (family == QF_REVISE)
-        KN_REQUIRE(n_removed >= 0 && (n_removed == 0 || removed_items), KNNCF_E_INVALID, "query: null removed items or n_removed < 0");
-    if (family != QF_FOLD_IN) {
-        KN_REQUIRE(n_ratings >= 0 && (n_ratings == 0 || (items && ratings)), KNNCF_E_INVALID, "query: null ratings or n_ratings < 0");
-    } else {
-        KN_REQUIRE(items && ratings && n_ratings > 0, KNNCF_E_INVALID, "query: null ratings or n_ratings <= 0");
-    }
-    require_query_support(h, predictor);
-    const int64_t offsets[2] = {0, n_ratings}, pred_offsets[2] = {0, m}, removed_offsets[2] = {0, family == QF_REVISE ? n_removed : 0};
-    int32_t status = KNNCF_OK, c = 0;
-    ExplainOut rows_known;
-    if (mode == QB_EXPLAIN) {
-        rows_known = *ex;
-        rows_known.rows = explain_batch_chunk(h, ex->cap);
-        ex = &rows_known;
-    }
-    const QueryFailure f = run_query_chunks(h, family, mode, 1, &user, removed_offsets, removed_items, offsets, items, ratings, 1, width, pred_offsets, pred_items,
-                                            out_i, out_d, mode == QB_EXPLAIN ? nullptr : &c, &status, ex);
-    if (f.query >= 0) throw Error(status, std::string("query: ") + f.reason);
-    if (count) *count = c;
+// the single forms' own output arguments, checked in front of everything else (the explain forms check theirs after
+// require_fitted, in do_query_single); a recommend form's *count is 0 whatever fails later
+void require_single_outputs(const QueryCall& q) {
+    if (q.mode == QB_PREDICT) KN_REQUIRE(q.m >= 0 && (q.m == 0 || (q.pred_items && q.out_d)), KNNCF_E_INVALID, "bad prediction arguments");
+    if (q.mode == QB_NEIGHBORS || q.mode == QB_RECOMMEND)
+        KN_REQUIRE(q.counts && q.width >= 0 && (q.width == 0 || (q.out_i && q.out_d)), KNNCF_E_INVALID,
+                   q.mode == QB_NEIGHBORS ? "bad output arguments" : "bad arguments");
+    if (q.mode == QB_RECOMMEND) *q.counts = 0;
 }
+
+// One query as a chunk of one: the query's status is the call's.  *count (neighbours: min(k, U), min(k, U - 1) for a user of
+// the fit; recommendations: min(n, I - known items)) is written on success.  An update query may come without rows (whether
+// the user is in the fit is the chunk loop's to say).
+void do_query_single(knncf_handle* h, const QueryCall& call) {
+    require_single_outputs(call);
+    require_fitted(h, false);
+    if (call.mode == QB_EXPLAIN) {
+        require_explain_order(call.ex);
+        KN_REQUIRE(call.m >= 0 && (call.m == 0 || call.pred_items), KNNCF_E_INVALID, "bad prediction arguments");
+        require_explain_outputs(call.ex, call.m);
+    }
+    if (call.family == QF_REVISE)
+        KN_REQUIRE(call.n_removed >= 0 && (call.n_removed == 0 || call.removed_items), KNNCF_E_INVALID, "query: null removed items or n_removed < 0");
+    if (call.family != QF_FOLD_IN) {
+        KN_REQUIRE(call.n_ratings >= 0 && (call.n_ratings == 0 || (call.items && call.ratings)), KNNCF_E_INVALID,
+                   "query: null ratings or n_ratings < 0");
+    } else {
+        KN_REQUIRE(call.items && call.ratings && call.n_ratings > 0, KNNCF_E_INVALID, "query: null ratings or n_ratings <= 0");
+    }
+    require_query_support(h, call.predictor);
+    const int64_t offsets[2] = {0, call.n_ratings}, pred_offsets[2] = {0, call.m}, removed_offsets[2] = {0, call.n_removed};
+    int32_t status = KNNCF_OK, c = 0;
+    QueryCall q = call;
+    q.users = &call.user; q.B = 1; q.counts = &c; q.statuses = &status;
+    q.offsets = offsets; q.removed_offsets = removed_offsets; q.pred_offsets = pred_offsets;
+    const QueryFailure f = run_query_chunks(h, q, 1, q.mode == QB_EXPLAIN ? explain_batch_chunk(h, q.ex.cap) : 0);
+    if (f.query >= 0) throw Error(status, std::string("query: ") + f.reason);
+    if (call.counts) *call.counts = c;
+}
+
+int query_batch(knncf_handle* h, const QueryCall& q) { return guarded(h, [&] { do_query_batch(h, q); }); }
+int query_single(knncf_handle* h, const QueryCall& q) { return guarded(h, [&] { do_query_single(h, q); }); }
 
 // ---- checkpoint / resume of the neighbour table ------------------------------------------------------
 struct NbrFileHeader {
@@ -2001,7 +2067,7 @@ int knncf_explain_batch_device(knncf_handle* h, const int32_t* d_users, const in
         if (n == 0) return;
         explain_prepare(h, d_users, d_items, n);
         Stage s(h, &h->tm.predict_ms);
-        launch_explain(h->tr, h->nt, n, h->t_du.p, h->t_di.p, order, cap, d_raters, d_sims, d_devs, d_counts, d_sums, d_predictions,
+        launch_explain(h->tr, h->nt, n, h->t_du.p, h->t_di.p, {order, cap, d_raters, d_sims, d_devs, d_counts, d_sums, d_predictions},
                        h->stream);
     });
 }
@@ -2020,14 +2086,14 @@ int knncf_explain_batch(knncf_handle* h, const int32_t* users, const int32_t* it
         const size_t cells = (size_t)chunk * (size_t)cap;
         h->ex_raters.ensure(cells); h->ex_sims.ensure(cells); h->ex_devs.ensure(cells);
         h->ex_counts.ensure(chunk); h->ex_sums.ensure((size_t)2 * chunk); h->ex_pred.ensure(chunk);
+        const ExplainCells d_out{order, cap, h->ex_raters.p, h->ex_sims.p, h->ex_devs.p, h->ex_counts.p, h->ex_sums.p, h->ex_pred.p};
         std::vector<int32_t> h_raters(cells);
         std::vector<double> h_sims(cells), h_devs(cells);
         for (int64_t c0 = 0; c0 < n; c0 += chunk) {
             const int64_t C = std::min<int64_t>(chunk, n - c0);
             {
                 Stage s(h, &h->tm.predict_ms);
-                launch_explain(h->tr, h->nt, C, h->t_du.p + c0, h->t_di.p + c0, order, cap, h->ex_raters.p, h->ex_sims.p, h->ex_devs.p,
-                               h->ex_counts.p, h->ex_sums.p, h->ex_pred.p, st);
+                launch_explain(h->tr, h->nt, C, h->t_du.p + c0, h->t_di.p + c0, d_out, st);
             }
             KN_HIP(hipMemcpyAsync(counts + c0, h->ex_counts.p, (size_t)C * sizeof(int32_t), hipMemcpyDeviceToHost, st));
             if (sums) KN_HIP(hipMemcpyAsync(sums + 2 * c0, h->ex_sums.p, (size_t)2 * C * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -2058,220 +2124,177 @@ int knncf_recommend(knncf_handle* h, int predictor, int32_t user, int32_t n, int
     return guarded(h, [&] { do_recommend(h, predictor, user, n, items, predictions, count); });
 }
 
+// ---- the 24 query entry points: the rows of the call by name, then the mode's builder (api.cpp "one request type") ----------
+// fold-in queries: a user outside the fit
 int knncf_query_neighbors(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
                           int32_t cap, int32_t* ids, double* sims, int32_t* count) {
-    return guarded(h, [&] {
-        KN_REQUIRE(count && cap >= 0 && (cap == 0 || (ids && sims)), KNNCF_E_INVALID, "bad output arguments");
-        do_query_single(h, QF_FOLD_IN, QB_NEIGHBORS, KNNCF_PRED_KNN, user, nullptr, 0, items, ratings, n_ratings, cap, nullptr, 0, ids, sims, count);
-    });
+    return query_single(h, neighbors_call({.family = QF_FOLD_IN, .items = items, .ratings = ratings, .user = user, .n_ratings = n_ratings},
+                                          cap, ids, sims, count));
 }
 
 int knncf_query_predict(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
                         int64_t n_ratings, const int32_t* pred_items, int64_t m, double* out) {
-    return guarded(h, [&] {
-        KN_REQUIRE(m >= 0 && (m == 0 || (pred_items && out)), KNNCF_E_INVALID, "bad prediction arguments");
-        do_query_single(h, QF_FOLD_IN, QB_PREDICT, predictor, user, nullptr, 0, items, ratings, n_ratings, 0, pred_items, m, nullptr, out, nullptr);
-    });
+    return query_single(h, predict_call({.family = QF_FOLD_IN, .items = items, .ratings = ratings, .pred_items = pred_items, .user = user,
+                                        .n_ratings = n_ratings, .m = m}, predictor, out));
 }
 
 int knncf_query_neighbors_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
                                 const double* ratings, int64_t n_queries, int32_t cap, int32_t* ids, double* sims, int32_t* counts,
                                 int32_t* statuses) {
-    return guarded(h, [&] {
-        do_query_batch(h, QF_FOLD_IN, QB_NEIGHBORS, KNNCF_PRED_KNN, users, nullptr, nullptr, offsets, items, ratings, n_queries, cap, nullptr, nullptr, ids, sims,
-                       counts, statuses);
-    });
+    return query_batch(h, neighbors_call({.family = QF_FOLD_IN, .users = users, .B = n_queries, .offsets = offsets, .items = items,
+                                         .ratings = ratings, .statuses = statuses}, cap, ids, sims, counts));
 }
 
 int knncf_query_predict_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets, const int32_t* items,
                               const double* ratings, int64_t n_queries, const int64_t* pred_offsets, const int32_t* pred_items,
                               double* out, int32_t* statuses) {
-    return guarded(h, [&] {
-        do_query_batch(h, QF_FOLD_IN, QB_PREDICT, predictor, users, nullptr, nullptr, offsets, items, ratings, n_queries, 0, pred_offsets, pred_items, nullptr, out,
-                       nullptr, statuses);
-    });
+    return query_batch(h, predict_call({.family = QF_FOLD_IN, .users = users, .B = n_queries, .offsets = offsets, .items = items,
+                                       .ratings = ratings, .pred_offsets = pred_offsets, .pred_items = pred_items, .statuses = statuses},
+                                       predictor, out));
 }
 
 int knncf_query_recommend_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets, const int32_t* items,
                                 const double* ratings, int64_t n_queries, int32_t n, int32_t* out_items, double* out_preds,
                                 int32_t* counts, int32_t* statuses) {
-    return guarded(h, [&] {
-        do_query_batch(h, QF_FOLD_IN, QB_RECOMMEND, predictor, users, nullptr, nullptr, offsets, items, ratings, n_queries, n, nullptr, nullptr, out_items,
-                       out_preds, counts, statuses);
-    });
+    return query_batch(h, recommend_call({.family = QF_FOLD_IN, .users = users, .B = n_queries, .offsets = offsets, .items = items,
+                                         .ratings = ratings, .statuses = statuses}, predictor, n, out_items, out_preds, counts));
 }
 
 int knncf_query_recommend(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
                           int64_t n_ratings, int32_t n, int32_t* out_items, double* out_preds, int32_t* count) {
-    return guarded(h, [&] {
-        KN_REQUIRE(count && n >= 0 && (n == 0 || (out_items && out_preds)), KNNCF_E_INVALID, "bad arguments");
-        *count = 0;
-        do_query_single(h, QF_FOLD_IN, QB_RECOMMEND, predictor, user, nullptr, 0, items, ratings, n_ratings, n, nullptr, 0, out_items, out_preds, count);
-    });
+    return query_single(h, recommend_call({.family = QF_FOLD_IN, .items = items, .ratings = ratings, .user = user, .n_ratings = n_ratings},
+                                          predictor, n, out_items, out_preds, count));
 }
 
 // update queries: the same calls for a user that may be in the fit (the rows are additional to its train rows)
 int knncf_update_neighbors(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
                            int32_t cap, int32_t* ids, double* sims, int32_t* count) {
-    return guarded(h, [&] {
-        KN_REQUIRE(count && cap >= 0 && (cap == 0 || (ids && sims)), KNNCF_E_INVALID, "bad output arguments");
-        do_query_single(h, QF_UPDATE, QB_NEIGHBORS, KNNCF_PRED_KNN, user, nullptr, 0, items, ratings, n_ratings, cap, nullptr, 0, ids, sims, count);
-    });
+    return query_single(h, neighbors_call({.family = QF_UPDATE, .items = items, .ratings = ratings, .user = user, .n_ratings = n_ratings},
+                                          cap, ids, sims, count));
 }
 
 int knncf_update_predict(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
                          int64_t n_ratings, const int32_t* pred_items, int64_t m, double* out) {
-    return guarded(h, [&] {
-        KN_REQUIRE(m >= 0 && (m == 0 || (pred_items && out)), KNNCF_E_INVALID, "bad prediction arguments");
-        do_query_single(h, QF_UPDATE, QB_PREDICT, predictor, user, nullptr, 0, items, ratings, n_ratings, 0, pred_items, m, nullptr, out, nullptr);
-    });
+    return query_single(h, predict_call({.family = QF_UPDATE, .items = items, .ratings = ratings, .pred_items = pred_items, .user = user,
+                                        .n_ratings = n_ratings, .m = m}, predictor, out));
 }
 
 int knncf_update_neighbors_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
                                  const double* ratings, int64_t n_queries, int32_t cap, int32_t* ids, double* sims, int32_t* counts,
                                  int32_t* statuses) {
-    return guarded(h, [&] {
-        do_query_batch(h, QF_UPDATE, QB_NEIGHBORS, KNNCF_PRED_KNN, users, nullptr, nullptr, offsets, items, ratings, n_queries, cap, nullptr, nullptr, ids, sims,
-                       counts, statuses);
-    });
+    return query_batch(h, neighbors_call({.family = QF_UPDATE, .users = users, .B = n_queries, .offsets = offsets, .items = items,
+                                         .ratings = ratings, .statuses = statuses}, cap, ids, sims, counts));
 }
 
 int knncf_update_predict_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets, const int32_t* items,
                                const double* ratings, int64_t n_queries, const int64_t* pred_offsets, const int32_t* pred_items,
                                double* out, int32_t* statuses) {
-    return guarded(h, [&] {
-        do_query_batch(h, QF_UPDATE, QB_PREDICT, predictor, users, nullptr, nullptr, offsets, items, ratings, n_queries, 0, pred_offsets, pred_items, nullptr, out,
-                       nullptr, statuses);
-    });
+    return query_batch(h, predict_call({.family = QF_UPDATE, .users = users, .B = n_queries, .offsets = offsets, .items = items,
+                                       .ratings = ratings, .pred_offsets = pred_offsets, .pred_items = pred_items, .statuses = statuses},
+                                       predictor, out));
 }
 
 int knncf_update_recommend_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets, const int32_t* items,
                                  const double* ratings, int64_t n_queries, int32_t n, int32_t* out_items, double* out_preds,
                                  int32_t* counts, int32_t* statuses) {
-    return guarded(h, [&] {
-        do_query_batch(h, QF_UPDATE, QB_RECOMMEND, predictor, users, nullptr, nullptr, offsets, items, ratings, n_queries, n, nullptr, nullptr, out_items,
-                       out_preds, counts, statuses);
-    });
+    return query_batch(h, recommend_call({.family = QF_UPDATE, .users = users, .B = n_queries, .offsets = offsets, .items = items,
+                                         .ratings = ratings, .statuses = statuses}, predictor, n, out_items, out_preds, counts));
 }
 
 int knncf_update_recommend(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
                            int64_t n_ratings, int32_t n, int32_t* out_items, double* out_preds, int32_t* count) {
-    return guarded(h, [&] {
-        KN_REQUIRE(count && n >= 0 && (n == 0 || (out_items && out_preds)), KNNCF_E_INVALID, "bad arguments");
-        *count = 0;
-        do_query_single(h, QF_UPDATE, QB_RECOMMEND, predictor, user, nullptr, 0, items, ratings, n_ratings, n, nullptr, 0, out_items, out_preds, count);
-    });
+    return query_single(h, recommend_call({.family = QF_UPDATE, .items = items, .ratings = ratings, .user = user, .n_ratings = n_ratings},
+                                          predictor, n, out_items, out_preds, count));
 }
 
 // revise queries: update queries that also remove train rows of the user (removed_items) from aug
 int knncf_revise_neighbors(knncf_handle* h, int32_t user, const int32_t* removed_items, int64_t n_removed, const int32_t* items,
                            const double* ratings, int64_t n_ratings, int32_t cap, int32_t* ids, double* sims, int32_t* count) {
-    return guarded(h, [&] {
-        KN_REQUIRE(count && cap >= 0 && (cap == 0 || (ids && sims)), KNNCF_E_INVALID, "bad output arguments");
-        do_query_single(h, QF_REVISE, QB_NEIGHBORS, KNNCF_PRED_KNN, user, removed_items, n_removed, items, ratings, n_ratings, cap, nullptr, 0,
-                        ids, sims, count);
-    });
+    return query_single(h, neighbors_call({.family = QF_REVISE, .items = items, .ratings = ratings, .removed_items = removed_items,
+                                          .user = user, .n_ratings = n_ratings, .n_removed = n_removed}, cap, ids, sims, count));
 }
 
 int knncf_revise_predict(knncf_handle* h, int predictor, int32_t user, const int32_t* removed_items, int64_t n_removed,
                          const int32_t* items, const double* ratings, int64_t n_ratings, const int32_t* pred_items, int64_t m, double* out) {
-    return guarded(h, [&] {
-        KN_REQUIRE(m >= 0 && (m == 0 || (pred_items && out)), KNNCF_E_INVALID, "bad prediction arguments");
-        do_query_single(h, QF_REVISE, QB_PREDICT, predictor, user, removed_items, n_removed, items, ratings, n_ratings, 0, pred_items, m,
-                        nullptr, out, nullptr);
-    });
+    return query_single(h, predict_call({.family = QF_REVISE, .items = items, .ratings = ratings, .removed_items = removed_items,
+                                        .pred_items = pred_items, .user = user, .n_ratings = n_ratings, .n_removed = n_removed, .m = m},
+                                        predictor, out));
 }
 
 int knncf_revise_recommend(knncf_handle* h, int predictor, int32_t user, const int32_t* removed_items, int64_t n_removed,
                            const int32_t* items, const double* ratings, int64_t n_ratings, int32_t n, int32_t* out_items,
                            double* out_preds, int32_t* count) {
-    return guarded(h, [&] {
-        KN_REQUIRE(count && n >= 0 && (n == 0 || (out_items && out_preds)), KNNCF_E_INVALID, "bad arguments");
-        *count = 0;
-        do_query_single(h, QF_REVISE, QB_RECOMMEND, predictor, user, removed_items, n_removed, items, ratings, n_ratings, n, nullptr, 0,
-                        out_items, out_preds, count);
-    });
+    return query_single(h, recommend_call({.family = QF_REVISE, .items = items, .ratings = ratings, .removed_items = removed_items,
+                                          .user = user, .n_ratings = n_ratings, .n_removed = n_removed}, predictor, n, out_items, out_preds,
+                                          count));
 }
 
 int knncf_revise_neighbors_batch(knncf_handle* h, const int32_t* users, const int64_t* removed_offsets, const int32_t* removed_items,
                                  const int64_t* offsets, const int32_t* items, const double* ratings, int64_t n_queries, int32_t cap,
                                  int32_t* ids, double* sims, int32_t* counts, int32_t* statuses) {
-    return guarded(h, [&] {
-        do_query_batch(h, QF_REVISE, QB_NEIGHBORS, KNNCF_PRED_KNN, users, removed_offsets, removed_items, offsets, items, ratings, n_queries,
-                       cap, nullptr, nullptr, ids, sims, counts, statuses);
-    });
+    return query_batch(h, neighbors_call({.family = QF_REVISE, .users = users, .B = n_queries, .offsets = offsets, .items = items,
+                                         .ratings = ratings, .removed_offsets = removed_offsets, .removed_items = removed_items,
+                                         .statuses = statuses}, cap, ids, sims, counts));
 }
 
 int knncf_revise_predict_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* removed_offsets,
                                const int32_t* removed_items, const int64_t* offsets, const int32_t* items, const double* ratings,
                                int64_t n_queries, const int64_t* pred_offsets, const int32_t* pred_items, double* out, int32_t* statuses) {
-    return guarded(h, [&] {
-        do_query_batch(h, QF_REVISE, QB_PREDICT, predictor, users, removed_offsets, removed_items, offsets, items, ratings, n_queries, 0,
-                       pred_offsets, pred_items, nullptr, out, nullptr, statuses);
-    });
+    return query_batch(h, predict_call({.family = QF_REVISE, .users = users, .B = n_queries, .offsets = offsets, .items = items,
+                                       .ratings = ratings, .removed_offsets = removed_offsets, .removed_items = removed_items,
+                                       .pred_offsets = pred_offsets, .pred_items = pred_items, .statuses = statuses}, predictor, out));
 }
 
 int knncf_revise_recommend_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* removed_offsets,
                                  const int32_t* removed_items, const int64_t* offsets, const int32_t* items, const double* ratings,
                                  int64_t n_queries, int32_t n, int32_t* out_items, double* out_preds, int32_t* counts, int32_t* statuses) {
-    return guarded(h, [&] {
-        do_query_batch(h, QF_REVISE, QB_RECOMMEND, predictor, users, removed_offsets, removed_items, offsets, items, ratings, n_queries, n,
-                       nullptr, nullptr, out_items, out_preds, counts, statuses);
-    });
+    return query_batch(h, recommend_call({.family = QF_REVISE, .users = users, .B = n_queries, .offsets = offsets, .items = items,
+                                         .ratings = ratings, .removed_offsets = removed_offsets, .removed_items = removed_items,
+                                         .statuses = statuses}, predictor, n, out_items, out_preds, counts));
 }
 
 // explanations of query predictions: the *_predict calls' arguments, the terms behind every requested row
 int knncf_query_explain(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
                         const int32_t* pred_items, int64_t m, int32_t order, int32_t cap, int32_t* raters, double* sims, double* devs,
                         int32_t* counts, double* sums, double* predictions) {
-    return guarded(h, [&] {
-        const ExplainOut ex{order, cap, 0, raters, sims, devs, counts, sums, predictions};
-        do_query_single(h, QF_FOLD_IN, QB_EXPLAIN, predictor, user, nullptr, 0, items, ratings, n_ratings, 0, pred_items, m, nullptr, nullptr,
-                        nullptr, &ex);
-    });
+    return query_single(h, explain_call({.family = QF_FOLD_IN, .items = items, .ratings = ratings, .pred_items = pred_items, .user = user,
+                                        .n_ratings = n_ratings, .m = m},
+                                        predictor, {order, cap, raters, sims, devs, counts, sums, predictions}));
 }
 
 int knncf_update_explain(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
                          const int32_t* pred_items, int64_t m, int32_t order, int32_t cap, int32_t* raters, double* sims, double* devs,
                          int32_t* counts, double* sums, double* predictions) {
-    return guarded(h, [&] {
-        const ExplainOut ex{order, cap, 0, raters, sims, devs, counts, sums, predictions};
-        do_query_single(h, QF_UPDATE, QB_EXPLAIN, predictor, user, nullptr, 0, items, ratings, n_ratings, 0, pred_items, m, nullptr, nullptr,
-                        nullptr, &ex);
-    });
+    return query_single(h, explain_call({.family = QF_UPDATE, .items = items, .ratings = ratings, .pred_items = pred_items, .user = user,
+                                        .n_ratings = n_ratings, .m = m},
+                                        predictor, {order, cap, raters, sims, devs, counts, sums, predictions}));
 }
 
 int knncf_revise_explain(knncf_handle* h, int predictor, int32_t user, const int32_t* removed_items, int64_t n_removed,
                          const int32_t* items, const double* ratings, int64_t n_ratings, const int32_t* pred_items, int64_t m,
                          int32_t order, int32_t cap, int32_t* raters, double* sims, double* devs, int32_t* counts, double* sums,
                          double* predictions) {
-    return guarded(h, [&] {
-        const ExplainOut ex{order, cap, 0, raters, sims, devs, counts, sums, predictions};
-        do_query_single(h, QF_REVISE, QB_EXPLAIN, predictor, user, removed_items, n_removed, items, ratings, n_ratings, 0, pred_items, m,
-                        nullptr, nullptr, nullptr, &ex);
-    });
+    return query_single(h, explain_call({.family = QF_REVISE, .items = items, .ratings = ratings, .removed_items = removed_items,
+                                        .pred_items = pred_items, .user = user, .n_ratings = n_ratings, .n_removed = n_removed, .m = m},
+                                        predictor, {order, cap, raters, sims, devs, counts, sums, predictions}));
 }
 
 int knncf_query_explain_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets, const int32_t* items,
                               const double* ratings, int64_t n_queries, const int64_t* pred_offsets, const int32_t* pred_items,
                               int32_t order, int32_t cap, int32_t* raters, double* sims, double* devs, int32_t* counts, double* sums,
                               double* predictions, int32_t* statuses) {
-    return guarded(h, [&] {
-        const ExplainOut ex{order, cap, 0, raters, sims, devs, counts, sums, predictions};
-        do_query_batch(h, QF_FOLD_IN, QB_EXPLAIN, predictor, users, nullptr, nullptr, offsets, items, ratings, n_queries, 0, pred_offsets,
-                       pred_items, nullptr, nullptr, nullptr, statuses, &ex);
-    });
+    return query_batch(h, explain_call({.family = QF_FOLD_IN, .users = users, .B = n_queries, .offsets = offsets, .items = items,
+                                       .ratings = ratings, .pred_offsets = pred_offsets, .pred_items = pred_items, .statuses = statuses},
+                                       predictor, {order, cap, raters, sims, devs, counts, sums, predictions}));
 }
 
 int knncf_update_explain_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets, const int32_t* items,
                                const double* ratings, int64_t n_queries, const int64_t* pred_offsets, const int32_t* pred_items,
                                int32_t order, int32_t cap, int32_t* raters, double* sims, double* devs, int32_t* counts, double* sums,
                                double* predictions, int32_t* statuses) {
-    return guarded(h, [&] {
-        const ExplainOut ex{order, cap, 0, raters, sims, devs, counts, sums, predictions};
-        do_query_batch(h, QF_UPDATE, QB_EXPLAIN, predictor, users, nullptr, nullptr, offsets, items, ratings, n_queries, 0, pred_offsets,
-                       pred_items, nullptr, nullptr, nullptr, statuses, &ex);
-    });
+    return query_batch(h, explain_call({.family = QF_UPDATE, .users = users, .B = n_queries, .offsets = offsets, .items = items,
+                                       .ratings = ratings, .pred_offsets = pred_offsets, .pred_items = pred_items, .statuses = statuses},
+                                       predictor, {order, cap, raters, sims, devs, counts, sums, predictions}));
 }
 
 int knncf_revise_explain_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* removed_offsets,
@@ -2279,11 +2302,10 @@ int knncf_revise_explain_batch(knncf_handle* h, int predictor, const int32_t* us
                                int64_t n_queries, const int64_t* pred_offsets, const int32_t* pred_items, int32_t order, int32_t cap,
                                int32_t* raters, double* sims, double* devs, int32_t* counts, double* sums, double* predictions,
                                int32_t* statuses) {
-    return guarded(h, [&] {
-        const ExplainOut ex{order, cap, 0, raters, sims, devs, counts, sums, predictions};
-        do_query_batch(h, QF_REVISE, QB_EXPLAIN, predictor, users, removed_offsets, removed_items, offsets, items, ratings, n_queries, 0,
-                       pred_offsets, pred_items, nullptr, nullptr, nullptr, statuses, &ex);
-    });
+    return query_batch(h, explain_call({.family = QF_REVISE, .users = users, .B = n_queries, .offsets = offsets, .items = items,
+                                       .ratings = ratings, .removed_offsets = removed_offsets, .removed_items = removed_items,
+                                       .pred_offsets = pred_offsets, .pred_items = pred_items, .statuses = statuses}, predictor, {order,
+                                       cap, raters, sims, devs, counts, sums, predictions}));
 }
 
 int knncf_neighbors_save(knncf_handle* h, const char* path) {

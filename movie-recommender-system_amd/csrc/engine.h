@@ -253,13 +253,23 @@ void launch_reduce_err(const double* d_abs_err, const uint8_t* d_owned, int64_t 
                        int64_t* d_counts, int32_t n_blocks, hipStream_t st);
 
 // ---- explain.hip: the neighbour terms behind kNN predictions (knncf_explain*; DESIGN.md "Explanations") ---------------
-// per row (d_du[t], d_di[t]), t < n: d_counts[t] = number of terms (neighbours of the user with a non-zero similarity that
-// rated the item), the first min(count, cap) of them in `order` (KNNCF_EXPLAIN_*) in row t of d_raters / d_sims / d_devs
-// (row stride cap; unused with cap == 0), d_sums[2 t ..] = (num, den) of the fold over all terms and d_pred[t] = the
-// KNNCF_PRED_KNN prediction (either may be null).  nt.kcap <= 2048; makes nt's id-sorted copies when they are not current.
-void launch_explain(const Train& tr, NeighborTable& nt, int64_t n, const int32_t* d_du, const int32_t* d_di, int32_t order,
-                    int32_t cap, int32_t* d_raters, double* d_sims, double* d_devs, int32_t* d_counts, double* d_sums,
-                    double* d_pred, hipStream_t st);
+// Where the explanations of a set of rows are written, by explain.hip for rows of the fit and by foldin.hip for query rows;
+// device pointers for a launch, host pointers for the caller's arrays.  Row t: counts[t] = number of terms, the first
+// min(count, cap) of them in `order` (KNNCF_EXPLAIN_*) in row t of raters / sims / devs (row stride cap; unused with cap ==
+// 0), sums[2 t ..] = (num, den) of the fold over all terms and pred[t] = the KNNCF_PRED_KNN prediction (either may be null).
+struct ExplainCells {
+    int32_t order, cap;
+    int32_t* raters;
+    double* sims;
+    double* devs;
+    int32_t* counts;
+    double* sums;
+    double* pred;
+};
+// per row (d_du[t], d_di[t]), t < n: row t of `out` (terms: neighbours of the user with a non-zero similarity that rated the
+// item).  nt.kcap <= 2048; makes nt's id-sorted copies when they are not current.
+void launch_explain(const Train& tr, NeighborTable& nt, int64_t n, const int32_t* d_du, const int32_t* d_di, const ExplainCells& out,
+                    hipStream_t st);
 
 // ---- ksweep.hip: the kNN prediction at several k from one neighbour table (knncf_mae_sweep) ----------------------
 // per test row d_order[0 .. n): the kNN prediction at every k = d_ks[q] (ascending, q < n_k <= 64) from the first k entries of the
@@ -370,13 +380,16 @@ void foldin_batch_predictions(const Train& tr, QueryBatchScratch& bs, SortWorksp
                               const int64_t* h_ebase, hipStream_t st);
 void foldin_batch_pick(const Train& tr, QueryBatchScratch& bs, const int32_t* d_items, const int32_t* d_slot, int64_t m,
                        double* d_out, hipStream_t st);
-// after foldin_batch_predictions: the terms behind the predictions of the chunk's rows [r0, r0 + n) of d_items / d_slot (E =
-// h_ebase[C], the chunk's gathered entries).  Output cell 0 is row r0: d_counts [n] = number of terms, the first min(count, cap)
-// in `order` (KNNCF_EXPLAIN_*) in d_raters / d_sims / d_devs [n * cap] (unused with cap == 0), d_sums [2 n] = the cell's num /
-// den and d_pred [n] = its prediction (either may be null).  One launch.
-void foldin_batch_explain(const Train& tr, QueryBatchScratch& bs, int32_t C, int32_t take, int64_t E, const int32_t* d_items,
-                          const int32_t* d_slot, int64_t r0, int64_t n, int32_t order, int32_t cap, int32_t* d_raters,
-                          double* d_sims, double* d_devs, int32_t* d_counts, double* d_sums, double* d_pred, hipStream_t st);
+// after foldin_batch_predictions: the terms behind the predictions of the chunk's rows [r0, r0 + n) of d_items / d_slot, into
+// rows [0, n) of `out`: cell 0 is row r0.  One launch.
+struct QbExplainRows {
+    int32_t take;   // as foldin_batch_predictions took it
+    int64_t E;      // h_ebase[C], the chunk's gathered entries
+    const int32_t* d_items;
+    const int32_t* d_slot;
+    int64_t r0, n;
+};
+void foldin_batch_explain(const Train& tr, QueryBatchScratch& bs, const QbExplainRows& rows, const ExplainCells& out, hipStream_t st);
 // d_items / d_preds [C][n]: slot b's first min(n, I - known) recommendations (the rest untouched)
 void foldin_batch_recommend(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, int32_t n, int32_t* d_items,
                             double* d_preds, hipStream_t st);

@@ -263,9 +263,8 @@ __global__ void __launch_bounds__(WAVES * 64) k_explain(ExplainArgs A, int64_t n
     }
 }
 
-void launch_explain(const Train& tr, NeighborTable& nt, int64_t n, const int32_t* d_du, const int32_t* d_di, int32_t order,
-                    int32_t cap, int32_t* d_raters, double* d_sims, double* d_devs, int32_t* d_counts, double* d_sums,
-                    double* d_pred, hipStream_t st) {
+void launch_explain(const Train& tr, NeighborTable& nt, int64_t n, const int32_t* d_du, const int32_t* d_di, const ExplainCells& out,
+                    hipStream_t st) {
     if (n <= 0) return;
     ExplainArgs A{};
     A.user_avg = tr.user_avg.p; A.global_avg = tr.global_avg;
@@ -278,11 +277,11 @@ void launch_explain(const Train& tr, NeighborTable& nt, int64_t n, const int32_t
     A.i_ptr = tr.i_ptr.p; A.it_user = tr.it_user.p; A.it_dev = tr.it_dev.p; A.it_t = tr.it_t.p;
     A.ib_words = tr.ib_words; A.item_bits = reinterpret_cast<const unsigned long long*>(tr.item_bits.p); A.item_rank = tr.item_rank.p;
     A.uid = tr.uid.p;
-    A.order = order; A.cap = cap;
-    A.raters = d_raters; A.sims = d_sims; A.devs = d_devs; A.counts = d_counts; A.sums = d_sums; A.pred = d_pred;
+    A.order = out.order; A.cap = out.cap;
+    A.raters = out.raters; A.sims = out.sims; A.devs = out.devs; A.counts = out.counts; A.sums = out.sums; A.pred = out.pred;
 #define KN_LAUNCH_EXPLAIN(CAPV, WV)                                                                           \
     do {                                                                                                      \
-        KN_TRACE_DISPATCH("explain CAP=%d bits=%d order=%d", CAPV, tr.ib_words > 0 ? 1 : 0, (int)order);      \
+        KN_TRACE_DISPATCH("explain CAP=%d bits=%d order=%d", CAPV, tr.ib_words > 0 ? 1 : 0, (int)out.order);  \
         k_explain<CAPV, WV><<<(unsigned)ceil_div(n, WV), WV * 64, 0, st>>>(A, n, d_du, d_di);                \
     } while (0)
     if (nt.kcap <= 64) KN_LAUNCH_EXPLAIN(64, 4);

@@ -1011,22 +1011,20 @@ void foldin_batch_pick(const Train& tr, QueryBatchScratch& bs, const int32_t* d_
     KN_HIP(hipGetLastError());
 }
 
-void foldin_batch_explain(const Train& tr, QueryBatchScratch& bs, int32_t C, int32_t take, int64_t E, const int32_t* d_items,
-                          const int32_t* d_slot, int64_t r0, int64_t n, int32_t order, int32_t cap, int32_t* d_raters,
-                          double* d_sims, double* d_devs, int32_t* d_counts, double* d_sums, double* d_pred, hipStream_t st) {
+void foldin_batch_explain(const Train& tr, QueryBatchScratch& bs, const QbExplainRows& rows, const ExplainCells& out, hipStream_t st) {
+    const int64_t n = rows.n;
     if (n <= 0) return;
-    (void)C;
     QbExplainArgs A{};
-    A.items = d_items; A.slot = d_slot;
+    A.items = rows.d_items; A.slot = rows.d_slot;
     A.i_table = tr.i_table.p; A.i_cells = table_cells(tr); A.ikeys = tr.ikeys.p;
-    A.I = tr.I; A.take = take; A.order = order; A.cap = cap;
-    A.E = E;
+    A.I = tr.I; A.take = rows.take; A.order = out.order; A.cap = out.cap;
+    A.E = rows.E;
     A.key = bs.e_k64_b.p; A.val = bs.e_v32_b.p; A.edev = bs.e_dev.p; A.esim = bs.e_sim.p;
     A.ebase = bs.ebase.p; A.off = bs.off.p; A.nbr = bs.nbr_idx.p; A.uid = tr.uid.p;
     A.num = bs.num.p; A.den = bs.den.p; A.pred = bs.pred.p; A.scal = bs.scal.p;
-    A.raters = d_raters; A.sims = d_sims; A.devs = d_devs; A.counts = d_counts; A.sums = d_sums; A.out_pred = d_pred;
-    KN_TRACE_DISPATCH("qb_explain order=%d", (int)order);
-    k_qb_explain<<<(unsigned)ceil_div(n, QBX_WAVES), QBX_WAVES * 64, 0, st>>>(A, r0, n);
+    A.raters = out.raters; A.sims = out.sims; A.devs = out.devs; A.counts = out.counts; A.sums = out.sums; A.out_pred = out.pred;
+    KN_TRACE_DISPATCH("qb_explain order=%d", (int)out.order);
+    k_qb_explain<<<(unsigned)ceil_div(n, QBX_WAVES), QBX_WAVES * 64, 0, st>>>(A, rows.r0, n);
     KN_HIP(hipGetLastError());
 }
 

@@ -9,10 +9,11 @@ import os
 import numpy as np
 import pytest
 
+from tests.query_helpers import UNKNOWN_ITEM, _aug, _bits
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "personal.csv")
-UNKNOWN_ITEM = 999_999
 
 
 @pytest.fixture(scope="module")
@@ -20,18 +21,6 @@ def kn(pkg):
     mod = importlib.import_module(pkg.__name__ + ".knncf")
     mod.load_library()
     return mod
-
-
-def _bits(a):
-    return np.ascontiguousarray(np.asarray(a, dtype=np.float64)).view(np.int64).tolist()
-
-
-def _aug(train, q, items, ratings):
-    u, i, r = train
-    n = len(items)
-    return (np.concatenate([u, np.full(n, q, dtype=np.int32)]).astype(np.int32),
-            np.concatenate([i, np.asarray(items, dtype=np.int32)]).astype(np.int32),
-            np.concatenate([r, np.asarray(ratings, dtype=np.float64)]))
 
 
 def _check(kn, oracle, eng, train, q, items, ratings, sim, k, pred_items, ns=(3, None)):

@@ -17,12 +17,12 @@ import os
 import numpy as np
 import pytest
 
+from tests.query_helpers import MAX_CHUNK, UNKNOWN_ITEM, _aug, _bits, _chunk, _same_pair, _workspace_for
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "personal.csv")
-UNKNOWN_ITEM = 999_999
-MAX_CHUNK = 64
 
 
 @pytest.fixture(scope="module")
@@ -38,33 +38,6 @@ def latency_script():
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
-
-
-def _bits(a):
-    return np.ascontiguousarray(np.asarray(a, dtype=np.float64)).view(np.int64).tolist()
-
-
-def _aug(train, q, items, ratings):
-    u, i, r = train
-    n = len(items)
-    return (np.concatenate([u, np.full(n, q, dtype=np.int32)]).astype(np.int32),
-            np.concatenate([i, np.asarray(items, dtype=np.int32)]).astype(np.int32),
-            np.concatenate([r, np.asarray(ratings, dtype=np.float64)]))
-
-
-def _chunk(e, workspace_bytes):
-    """the chunk rule of include/knncf.h for a handle created with workspace_bytes > 0"""
-    per = 64 * e.num_users + 96 * e.num_items
-    return max(1, min(MAX_CHUNK, (workspace_bytes // 2) // per, (2**31 - 1) // max(e.num_users, e.num_items)))
-
-
-def _workspace_for(chunk, n_users, n_items):
-    return 2 * chunk * (64 * n_users + 96 * n_items) + 2
-
-
-def _same_pair(a, b, what):
-    assert a[0].tolist() == b[0].tolist(), what
-    assert _bits(a[1]) == _bits(b[1]), what
 
 
 def _batch_vs_singles(kn, e, queries, pred_items, ns=(3,)):

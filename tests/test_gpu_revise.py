@@ -9,11 +9,10 @@ import numpy as np
 import pytest
 
 from tests import revise_cases as rc
+from tests.query_helpers import MAX_CHUNK, UNKNOWN_ITEM, _bits, _chunk, _same_pair, _workspace_for
 
 pytestmark = pytest.mark.gpu
 
-UNKNOWN_ITEM = rc.UNKNOWN_ITEM
-MAX_CHUNK = 64
 NONE_I, NONE_R = np.empty(0, dtype=np.int32), np.empty(0)
 
 
@@ -22,15 +21,6 @@ def kn(pkg):
     mod = importlib.import_module(pkg.__name__ + ".knncf")
     mod.load_library()
     return mod
-
-
-def _bits(a):
-    return np.ascontiguousarray(np.asarray(a, dtype=np.float64)).view(np.int64).tolist()
-
-
-def _same_pair(a, b, what):
-    assert a[0].tolist() == b[0].tolist(), what
-    assert _bits(a[1]) == _bits(b[1]), what
 
 
 def _oracle_answers(oracle, train, q, removed, items, ratings, sim, k, pred_items, ns):
@@ -124,16 +114,6 @@ def test_row_size_classes_and_lone_items(kn, oracle, sim_name):
 
 
 # ---- 4: batches in large and small chunks -----------------------------------------------------------------------------------------
-def _workspace_for(chunk, n_users, n_items):
-    return 2 * chunk * (64 * n_users + 96 * n_items) + 2
-
-
-def _chunk(e, workspace_bytes):
-    """the chunk rule of include/knncf.h for a handle created with workspace_bytes > 0"""
-    per = 64 * e.num_users + 96 * e.num_items
-    return max(1, min(MAX_CHUNK, (workspace_bytes // 2) // per, (2**31 - 1) // max(e.num_users, e.num_items)))
-
-
 def _mixed_batch(train):
     """40 answerable queries: users of the fit with removals (one of them twice, with different removals), users of the fit
     without removals, users outside the fit; interleaved"""

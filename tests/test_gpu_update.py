@@ -10,11 +10,11 @@ import os
 import numpy as np
 import pytest
 
+from tests.query_helpers import MAX_CHUNK, UNKNOWN_ITEM, _aug, _bits, _chunk, _same_pair, _workspace_for
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-UNKNOWN_ITEM = 999_999
-MAX_CHUNK = 64
 
 
 @pytest.fixture(scope="module")
@@ -22,23 +22,6 @@ def kn(pkg):
     mod = importlib.import_module(pkg.__name__ + ".knncf")
     mod.load_library()
     return mod
-
-
-def _bits(a):
-    return np.ascontiguousarray(np.asarray(a, dtype=np.float64)).view(np.int64).tolist()
-
-
-def _aug(train, q, items, ratings):
-    u, i, r = train
-    n = len(items)
-    return (np.concatenate([u, np.full(n, q, dtype=np.int32)]).astype(np.int32),
-            np.concatenate([i, np.asarray(items, dtype=np.int32)]).astype(np.int32),
-            np.concatenate([r, np.asarray(ratings, dtype=np.float64)]))
-
-
-def _same_pair(a, b, what):
-    assert a[0].tolist() == b[0].tolist(), what
-    assert _bits(a[1]) == _bits(b[1]), what
 
 
 def _hold_out(full, users, m):
@@ -374,16 +357,6 @@ def test_handle_level_refusals(kn, syn100k):
     assert status_of(lambda: e4.neighbors_with(q, it, rt)) == kn.E_UNSUPPORTED  # fewer than 5 train users
     assert status_of(lambda: e4.neighbors_with_batch(good)) == kn.E_UNSUPPORTED
     e4.close()
-
-
-def _workspace_for(chunk, n_users, n_items):
-    return 2 * chunk * (64 * n_users + 96 * n_items) + 2
-
-
-def _chunk(e, workspace_bytes):
-    """the chunk rule of include/knncf.h for a handle created with workspace_bytes > 0"""
-    per = 64 * e.num_users + 96 * e.num_items
-    return max(1, min(MAX_CHUNK, (workspace_bytes // 2) // per, (2**31 - 1) // max(e.num_users, e.num_items)))
 
 
 @pytest.mark.parametrize("sim_name", ["cosine", "jaccard"])
