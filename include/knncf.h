@@ -132,7 +132,11 @@ const char* knncf_last_error(const knncf_handle* h);
  * reference builds those maps when computeItemAvg / computePrediction / the Spark
  * forms are constructed, and the handle builds them on the first call that reads
  * them (knncf_item_avg*, KNNCF_PRED_ITEM_AVG / BASELINE / BASELINE_RDD, and
- * PERSONALIZED with similarityOne), charged to prep_ms of that call. */
+ * PERSONALIZED with similarityOne), charged to prep_ms of that call.
+ * Rating domain: any finite double is accepted (the loader's toDouble yields any); nothing assumes the star scale [0.5, 5].
+ * A non-finite rating (NaN, +inf, -inf) gives a non-finite deviation and the fit returns KNNCF_E_NONFINITE, like a zero
+ * scale().  A fitted user whose mean is negative is predicted as the global average by every predictor, exactly like a
+ * user unknown to train: usersAvg.getOrElse(u, -1.0) < 0.0 at :572-573 (and :226 for the baseline) does not tell them apart. */
 int knncf_fit(knncf_handle* h, const int32_t* users, const int32_t* items,
               const double* ratings, int64_t n);
 int knncf_fit_device(knncf_handle* h, const int32_t* d_users, const int32_t* d_items,

@@ -14,7 +14,7 @@ using namespace knncf;
 
 namespace knncf {
 // small kernels of the orchestrator (neighbours.hip)
-void launch_first_rows(int64_t n, const int32_t* d_du, const int32_t* d_di, int32_t own_lo, int32_t own_hi,
+void launch_first_rows(int64_t n, const int32_t* d_du, const int32_t* d_di, const double* d_user_avg, int32_t own_lo, int32_t own_hi,
                        uint32_t* d_first, hipStream_t st);
 void launch_length_keys(int32_t count, const int32_t* d_list, const int64_t* d_u_ptr, int32_t max_len, uint64_t* d_key, hipStream_t st);
 void launch_collect_new(int32_t U, const uint32_t* d_first, int64_t* d_seq, int64_t epoch, int32_t own_lo, int32_t own_hi,
@@ -689,7 +689,7 @@ void ensure_neighbors_for_rows(knncf_handle* h, int64_t n) {
     KN_HIP(hipMemsetAsync(h->first_row.p, 0xff, tr.U * sizeof(uint32_t), st));
     KN_HIP(hipMemsetAsync(h->build_count.p, 0, sizeof(int32_t), st));
     // (every user's first row, whoever owns it: a shard needs the build sequence numbers of the other shards' users too)
-    launch_first_rows(n, h->t_du.p, h->t_di.p, 0, tr.U, h->first_row.p, st);
+    launch_first_rows(n, h->t_du.p, h->t_di.p, tr.user_avg.p, 0, tr.U, h->first_row.p, st);
     launch_collect_new(tr.U, h->first_row.p, h->nt.seq.p, h->epoch, tr.own_lo, tr.own_hi, h->build_list.p, h->build_count.p, st);
     h->epoch += 1;
     int32_t count = fetch(h, h->build_count.p, 0);

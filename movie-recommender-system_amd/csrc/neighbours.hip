@@ -11,15 +11,16 @@ namespace knncf {
 
 static constexpr int TPB = 256;
 
-// first test row (file order) at which the reference would call nn(u): the user is in train and
-// the item has at least one rater (weightedSumDeviation :508-517 only then evaluates similarities)
+// first test row (file order) at which the reference would call nn(u): the user is in train, its mean is not negative
+// (the predictor answers the global average at :573 before weightedSumDeviation runs) and the item has at least one rater
+// (weightedSumDeviation :508-517 only then evaluates similarities)
 __global__ void k_first_rows(int64_t n, const int32_t* __restrict__ du, const int32_t* __restrict__ di,
-                             int32_t own_lo, int32_t own_hi, uint32_t* __restrict__ first) {
+                             const double* __restrict__ user_avg, int32_t own_lo, int32_t own_hi, uint32_t* __restrict__ first) {
     int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int32_t u = -1;
     if (t < n) {
         u = du[t];
-        if (u < own_lo || u >= own_hi || di[t] < 0) u = -1;
+        if (u < 0 || u < own_lo || u >= own_hi || di[t] < 0 || user_avg[u] < 0.0) u = -1;
     }
     // test files list a user's rows together: of a run of equal users inside the wave only the first row (the smallest t)
     // goes to memory — 5 M atomics on 162 541 addresses became ~0.3 M
@@ -27,10 +28,10 @@ __global__ void k_first_rows(int64_t n, const int32_t* __restrict__ du, const in
     if (u >= 0 && ((threadIdx.x & 63) == 0 || prev != u)) atomicMin(&first[u], (uint32_t)t);
 }
 
-void launch_first_rows(int64_t n, const int32_t* d_du, const int32_t* d_di, int32_t own_lo, int32_t own_hi,
+void launch_first_rows(int64_t n, const int32_t* d_du, const int32_t* d_di, const double* d_user_avg, int32_t own_lo, int32_t own_hi,
                        uint32_t* d_first, hipStream_t st) {
     if (n <= 0) return;
-    k_first_rows<<<(unsigned)ceil_div(n, TPB), TPB, 0, st>>>(n, d_du, d_di, own_lo, own_hi, d_first);
+    k_first_rows<<<(unsigned)ceil_div(n, TPB), TPB, 0, st>>>(n, d_du, d_di, d_user_avg, own_lo, own_hi, d_first);
     KN_HIP(hipGetLastError());
 }
 

@@ -1,7 +1,9 @@
 """Randomised GPU-vs-oracle parity sweep (run on an MI355X): many small shapes, random engine flags / head widths / k /
 similarity (adjusted cosine, Jaccard) / GEMM form (symmetric, row blocks), then a few shapes that cross the 16 384-column
 tile of select.hip (sampled users).
-usage: python scripts/fuzz_parity.py [first_seed] [count] [scale] [big_cases]"""
+usage: python scripts/fuzz_parity.py [--rating-domain NAME] [first_seed] [count] [scale] [big_cases]
+--rating-domain: draw the small cases' ratings from a domain of tests/rating_scales.py (tenths, sixteenths, thirtyseconds,
+wide, neg_users) instead of whole or half stars."""
 import importlib
 import os
 import sys
@@ -9,12 +11,21 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tests import rating_scales  # noqa: E402
 from tests.test_oracle_semantics import _cols, _no_zero_scale, _random_case  # noqa: E402
 
 kn = importlib.import_module("movie-recommender-system_amd.knncf")
 oracle = importlib.import_module("oracle.knncf_oracle")
 kn.load_library()
 
+domain = None
+if "--rating-domain" in sys.argv:
+    at = sys.argv.index("--rating-domain")
+    domain = sys.argv[at + 1]
+    if domain not in rating_scales.DOMAINS:
+        sys.exit(f"--rating-domain: one of {', '.join(rating_scales.DOMAINS)}")
+    del sys.argv[at:at + 2]
+mae_tol = (lambda want: 1e-9) if domain is None else (lambda want: 1e-9 * max(1.0, want))  # (errors off the scale are not O(1))
 first = int(sys.argv[1]) if len(sys.argv) > 1 else 1000
 count = int(sys.argv[2]) if len(sys.argv) > 2 else 200
 scale = int(sys.argv[3]) if len(sys.argv) > 3 else 1  # multiplies the shape ranges
@@ -27,8 +38,12 @@ for seed in range(first, first + count):
     n_users = int(rng.integers(3, 400 * scale))
     n_items = int(rng.integers(6, 300 * scale))
     n_ratings = int(rng.integers(max(n_users, 10), min(n_users * n_items // 2 + 11, 12000 * scale * scale)))
-    rows = _random_case(rng, n_users=n_users, n_items=n_items, n_ratings=n_ratings, half=bool(rng.integers(0, 2)),
-                        tiny_rows=int(rng.integers(0, 4)))
+    if domain is None:
+        rows = _random_case(rng, n_users=n_users, n_items=n_items, n_ratings=n_ratings, half=bool(rng.integers(0, 2)),
+                            tiny_rows=int(rng.integers(0, 4)))
+    else:
+        rows = rating_scales.small_case(rng, domain, n_users=n_users, n_items=n_items, n_ratings=n_ratings,
+                                        tiny_rows=int(rng.integers(0, 4)))
     cut = len(rows) * 4 // 5
     train, test = rows[:cut], rows[cut:]
     if len(train) < 4 or not _no_zero_scale(train):
@@ -51,7 +66,7 @@ for seed in range(first, first + count):
         e = kn.Engine(k=k, similarity=sim, flags=flags, head_items=head).fit(*tr)
         want, preds = p.mae(*te, True)
         got = e.predict_batch(kn.PRED_KNN, te[0], te[1])
-        ok = np.array_equal(got, preds) and abs(e.mae(kn.PRED_KNN, *te) - want) <= 1e-9
+        ok = np.array_equal(got, preds) and abs(e.mae(kn.PRED_KNN, *te) - want) <= mae_tol(want)
         users = sorted(set(tr[0].tolist()))
         p2 = m.pipeline(sim, k)
         e.reset_neighbors()
