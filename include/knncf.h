@@ -265,7 +265,8 @@ int knncf_explain_batch_device(knncf_handle* h, const int32_t* d_users, const in
  *   knncf_query_predict    predictor(aug, weightedSumDeviation(aug, getSimilarity(aug, k, sim)))(user, pred_items[j])
  *                          :489-585 for any item id (rated by the user, unknown to train, ...);
  *   knncf_query_recommend  recommendations(aug, that predictor)(user, n) :651-674.
- * KNNCF_SIM_COSINE / KNNCF_SIM_JACCARD handles with predictor KNNCF_PRED_KNN, single shard, >= 5 train users, at most
+ * KNNCF_SIM_COSINE / KNNCF_SIM_JACCARD handles with predictor KNNCF_PRED_KNN (above) or KNNCF_PRED_PERSONALIZED (no
+ * neighbourhood cut: "Personalized queries" below), single shard, >= 5 train users, at most
  * 65536 query ratings (KNNCF_E_UNSUPPORTED otherwise, also for a query whose mean rating is negative); KNNCF_E_STATE
  * before a fit; KNNCF_E_INVALID if `user` occurs in train, a pointer is null or n_ratings <= 0; KNNCF_E_DUPLICATE if
  * the query repeats an item; KNNCF_E_NONFINITE for a non-finite deviation (as knncf_fit).  Read-only on the handle:
@@ -294,7 +295,8 @@ int knncf_query_recommend(knncf_handle* h, int predictor, int32_t user, const in
  * the query is empty), KNNCF_E_DUPLICATE, KNNCF_E_NONFINITE, KNNCF_E_UNSUPPORTED (negative mean, more than 65536 ratings).  A
  * failed query gets counts[b] = 0, its output row is left untouched, and it does not disturb the other queries.
  * The return value reports what is wrong with the call or the handle, as the single calls do: KNNCF_E_STATE before a fit;
- * KNNCF_E_UNSUPPORTED for KNNCF_SIM_ONE, a shard handle, fewer than 5 train users or a predictor other than KNNCF_PRED_KNN;
+ * KNNCF_E_UNSUPPORTED for KNNCF_SIM_ONE, a shard handle, fewer than 5 train users or a predictor other than KNNCF_PRED_KNN
+ * and KNNCF_PRED_PERSONALIZED;
  * KNNCF_E_INVALID for a null pointer, n_queries < 0, cap or n < 0, or offsets that are not a CSR.  n_queries == 0 is KNNCF_OK
  * and touches nothing.  After a call with failed queries knncf_last_error names the first failed query and its reason.
  * Read-only on the handle, as the single calls.
@@ -302,7 +304,9 @@ int knncf_query_recommend(knncf_handle* h, int predictor, int32_t user, const in
  *     C = max(1, min(64, budget / (64 * num_users + 96 * num_items), (2^31 - 1) / max(num_users, num_items)))
  *     budget = workspace_bytes / 2 if workspace_bytes > 0, else min(48 GiB, free device memory / 4)
  * so a call makes ceil(n_queries / C) chunks.  (The gathered neighbour ratings of a chunk are allocated beside that as they
- * are needed; a chunk whose neighbours hold 2^32 - 1 ratings or more fails the call with KNNCF_E_UNSUPPORTED.)  Failed queries
+ * are needed; a chunk whose neighbours hold 2^32 - 1 ratings or more fails the call with KNNCF_E_UNSUPPORTED.  With
+ * KNNCF_PRED_PERSONALIZED nothing is gathered; the transposed similarities of a chunk, 8 * num_users * (the power of two >= C)
+ * bytes, and the handle's file-order rater copies, 20 bytes per train rating, are allocated beside the budget instead.)  Failed queries
  * keep their place in their chunk.  A chunk with fewer than 32 answerable queries runs the one-query similarity kernel once
  * per query; larger ones read every train row once for the whole chunk.  The results do not depend on C. */
 int knncf_query_neighbors_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
@@ -337,8 +341,8 @@ int knncf_query_recommend_batch(knncf_handle* h, int predictor, const int32_t* u
  * Statuses: KNNCF_E_DUPLICATE if an additional item repeats another additional item or an item the user rated in train (the
  * reference has no operation that replaces a rating); KNNCF_E_NONFINITE for a non-finite deviation; KNNCF_E_UNSUPPORTED for
  * a negative mean of the combined rows or more than 65536 combined rows (the user's train rows plus the additional ones); and
- * as for knncf_query_*: KNNCF_SIM_COSINE / KNNCF_SIM_JACCARD, KNNCF_PRED_KNN, single shard, >= 5 train users
- * (KNNCF_E_UNSUPPORTED), KNNCF_E_STATE before a fit, KNNCF_E_INVALID for null pointers, negative sizes or bad CSR offsets.
+ * as for knncf_query_*: KNNCF_SIM_COSINE / KNNCF_SIM_JACCARD, KNNCF_PRED_KNN or KNNCF_PRED_PERSONALIZED ("Personalized queries"
+ * below), single shard, >= 5 train users (KNNCF_E_UNSUPPORTED), KNNCF_E_STATE before a fit, KNNCF_E_INVALID for null pointers, negative sizes or bad CSR offsets.
  * Read-only on the handle: the neighbour table, its build numbers and epoch and what knncf_neighbors_save writes stay as they
  * were; the user's own stored list is neither read nor replaced, and the additional rows do not enter the fit. */
 int knncf_update_neighbors(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
@@ -391,7 +395,8 @@ int knncf_update_recommend_batch(knncf_handle* h, int predictor, const int32_t* 
  *     C = max(1, min(64, budget / (64 * num_users + 96 * num_items), (2^31 - 1) / max(num_users, num_items)))
  * and the split at 32 answerable queries between the two similarity kernels.  The results do not depend on C.  Read-only on
  * the handle: the neighbour table, its build numbers and epoch and what knncf_neighbors_save writes stay as they were.
- * n_removed == 0 (removed_items may then be null) gives the knncf_update_* answer bit for bit: the same code runs. */
+ * n_removed == 0 (removed_items may then be null) gives the knncf_update_* answer bit for bit: the same code runs.
+ * predictor: KNNCF_PRED_KNN as described here, or KNNCF_PRED_PERSONALIZED ("Personalized queries" below) on the same aug. */
 int knncf_revise_neighbors(knncf_handle* h, int32_t user, const int32_t* removed_items, int64_t n_removed, const int32_t* items,
                            const double* ratings, int64_t n_ratings, int32_t cap, int32_t* ids, double* sims, int32_t* count);
 int knncf_revise_predict(knncf_handle* h, int predictor, int32_t user, const int32_t* removed_items, int64_t n_removed,
@@ -411,6 +416,46 @@ int knncf_revise_recommend_batch(knncf_handle* h, int predictor, const int32_t* 
                                  const int32_t* removed_items, const int64_t* offsets, const int32_t* items, const double* ratings,
                                  int64_t n_queries, int32_t n, int32_t* out_items, double* out_preds, int32_t* counts,
                                  int32_t* statuses);
+
+/* ---- Personalized queries: KNNCF_PRED_PERSONALIZED on the query families -----------------------------------------------------
+ * knncf_query_predict / _recommend, knncf_update_predict / _recommend, knncf_revise_predict / _recommend and their _batch
+ * forms accept predictor == KNNCF_PRED_PERSONALIZED on KNNCF_SIM_COSINE and KNNCF_SIM_JACCARD handles.  With aug exactly as
+ * each family defines it above, every result equals, bit for bit, the reference's
+ *     predictor(aug, weightedSumDeviation(aug, S))(user, item)   and   recommendations(aug, that predictor)(user, n)
+ * with S = adjustedCosineSimilarityFunction(aug) or jaccardCoefficient(aug) (predict/Personalized.scala:61-72,
+ * shared/predictions.scala:407-464, :489-585, :651-674) on fresh closures on which only the query user u is ever the first
+ * argument.  No neighbourhood cut and no refit.
+ *   Terms of a row (u, i).  ALL ratings of i in aug, in aug's file order (:508-524), each adding num = num + dev * s and
+ *     den = den + |s| from (0.0, 0.0) — the multiply and the add are separate, no fused multiply-add.  Raters with s == 0 add
+ *     +-0 and are not skipped.
+ *   The user's own rating is a term.  Unlike KNNCF_PRED_KNN, where getSimilarity(u, u) is 0, S(u, u) is not zero.  Its value is
+ *     S(u, u) on aug: for the cosine the left fold from 0.0 of pre(u, j) * pre(u, j) over u's items of aug in u's item-set
+ *     order (:418-426: the trie order of the item ids, the given order when u has at most 4 rows in aug) — close to but not
+ *     1.0 (1.0000000000000002, 0.9999999999999869, ...); for Jaccard exactly 1.0 (:454-458).
+ *   Where the own term sits.  At its place in aug's file order: a surviving train row of a fitted user at its train file
+ *     position, with u's deviation ON AUG (the mean changed); an additional row, or any row of a fold-in user, last; a removed
+ *     row is no term; a re-rated item has its train row taken out and its additional row at the end.  The position shows in
+ *     the last bits of (num, den).
+ *   An item that only u rates in aug (unknown to train, given in the additional rows) has exactly one term: num = 0.0 +
+ *     dev(u, i) * S(u, u), den = 0.0 + |S(u, u)|.  knncf_*_predict on it therefore does not answer the mean, as KNNCF_PRED_KNN
+ *     does there.  An item unknown to aug (an id never seen, or the item that leaves aug under a revise query) answers the
+ *     mean exactly, as does an item nobody rates with a non-zero similarity (den > 0 fails :527, the deviation is 0.0).
+ *   Train users with 4 or fewer ratings are accepted.  (The fitted KNNCF_PRED_PERSONALIZED refuses them for the adjusted cosine
+ *     because a pair's summation order there depends on the call history; here the closures are fresh and u is the first
+ *     argument of every pair, so the order is u's, as in the kNN queries.)
+ *   The handle's k plays no part: two handles that differ only in k give the same bits.  knncf_update_* with n_ratings == 0
+ *     for a fitted user gives the fresh-closure Personalized answer on train itself.
+ * Everything else stays as the families document it: per-query statuses, handle-level return values, CSR checks, n_queries ==
+ * 0, the cap of 65536 rows, the negative-mean refusal, >= 5 train users, KNNCF_SIM_ONE and shard handles refused, untouched
+ * rows of failed queries, the chunk rule C with its formula, the split at 32 answerable queries between the two similarity
+ * kernels, and "the results do not depend on C".  Read-only on the handle in the sense of the other families: the neighbour
+ * table, its build numbers, its epoch and the knncf_neighbors_save bytes stay as they were.  The first such call after a fit
+ * builds the handle's file-order rater copies (20 bytes per train rating, charged to prep_ms as the fitted
+ * KNNCF_PRED_PERSONALIZED path charges them; a refit drops them); they and the transposed similarities of a chunk (8 *
+ * num_users * the power of two >= C bytes) are allocated beside the chunk budget.  knncf_get_timings: the new fold is charged
+ * to predict_ms.  A repeated call of the same shape allocates nothing.
+ * Not part of this: knncf_*_explain* with KNNCF_PRED_PERSONALIZED (KNNCF_E_UNSUPPORTED, below), the *_neighbors calls (they
+ * have no predictor), every other predictor (KNNCF_E_UNSUPPORTED). */
 
 /* ---- Explanations of query predictions: the terms behind knncf_query_predict / knncf_update_predict / knncf_revise_predict ---
  * knncf_explain* above explains a prediction for a user as the fit holds it.  These explain what the three query families
@@ -446,7 +491,7 @@ int knncf_revise_recommend_batch(knncf_handle* h, int predictor, const int32_t* 
  * rows (the budget of the other batched calls).  A chunk with more requested rows runs the explain kernel over consecutive
  * sub-ranges of R rows; the chunk's fold results stay in place between the launches.  The results do not depend on R, and a
  * call on a handle that has answered the same shape before allocates no device memory.
- * OUT OF SCOPE here as above: KNNCF_PRED_PERSONALIZED explanations (KNNCF_E_UNSUPPORTED, as the query calls answer for any
+ * OUT OF SCOPE here as above: KNNCF_PRED_PERSONALIZED explanations (KNNCF_E_UNSUPPORTED, as the explain calls answer for any
  * predictor but KNNCF_PRED_KNN), sharded explanations (a shard handle: KNNCF_E_UNSUPPORTED), and a fused "recommend and
  * explain in one pass" call: explain the items knncf_*_recommend returned with a second call. */
 int knncf_query_explain(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,

@@ -69,7 +69,7 @@ struct knncf_handle {
     NeighborTable pt;       // Personalized (no k): every non-zero similarity of every user (ids ascending, self included)
     bool pt_ready = false;
     PersonalRows prow;      // Personalized (no k) beyond the table: first-use copies + the row scratch (personalized.hip)
-    bool prow_ready = false;
+    bool prow_ready = false, prow_checked = false;  // the copies are built; the fitted path's refusals were checked
     DArr<int32_t> reco_users, reco_items, reco_out_items;
     DArr<double> reco_pred, reco_out_preds;
     DArr<uint8_t> reco_rated;
@@ -733,9 +733,14 @@ void ensure_personalized_table(knncf_handle* h) {
 
 // the item-major fp64 pre values, the raters in file order and the tile table: built on the first streamed call, charged to
 // prep_ms (knncf_fit does not build them: the kNN step never reads them)
-void ensure_personal_rows(knncf_handle* h) {
+// (fitted = false: the Personalized QUERIES — fresh closures owned by the query user — take the copies without the fitted
+// path's refusal of users with <= 4 ratings; the fitted path still checks on its own first use)
+void ensure_personal_rows(knncf_handle* h, bool fitted = true) {
+    if (fitted && !h->prow_checked) {
+        require_personalized(h);
+        h->prow_checked = true;
+    }
     if (h->prow_ready) return;
-    require_personalized(h);
     Stage s(h, &h->tm.prep_ms);
     h->prep.join_commit(h->stream);
     personalized_prepare(h->tr, h->prep, h->prow, h->stream);
@@ -981,6 +986,7 @@ void do_fit_device(knncf_handle* h, const int32_t* d_users, const int32_t* d_ite
     h->b_ready = false;
     h->pt_ready = false;
     h->prow_ready = false;
+    h->prow_checked = false;
     h->h_ukeys.clear(); h->h_ikeys.clear(); h->h_uid.clear(); h->h_uptr.clear();
     tr.n = n;
     tr.jaccard = h->cfg.similarity == KNNCF_SIM_JACCARD;
@@ -1052,8 +1058,9 @@ enum QueryBatchMode { QB_NEIGHBORS, QB_PREDICT, QB_RECOMMEND, QB_EXPLAIN };
 enum QueryFamily { QF_FOLD_IN, QF_UPDATE, QF_REVISE };
 
 // what the handle must be for any fold-in query, single or batched
-void require_query_support(knncf_handle* h, int predictor) {
-    KN_REQUIRE(predictor == KNNCF_PRED_KNN, KNNCF_E_UNSUPPORTED, "query: only KNNCF_PRED_KNN");
+void require_query_support(knncf_handle* h, int predictor, QueryBatchMode mode) {
+    KN_REQUIRE(predictor == KNNCF_PRED_KNN || (predictor == KNNCF_PRED_PERSONALIZED && mode != QB_EXPLAIN), KNNCF_E_UNSUPPORTED,
+               mode == QB_EXPLAIN ? "query explain: only KNNCF_PRED_KNN" : "query: only KNNCF_PRED_KNN and KNNCF_PRED_PERSONALIZED");
     KN_REQUIRE(h->cfg.similarity != KNNCF_SIM_ONE, KNNCF_E_UNSUPPORTED, "query: adjusted cosine or Jaccard");
     KN_REQUIRE(h->cfg.shard_count == 1, KNNCF_E_UNSUPPORTED, "query: single-shard handles only");
     KN_REQUIRE(h->tr.U >= 5, KNNCF_E_UNSUPPORTED, "query: fewer than 5 train users (the user set changes iteration class)");
@@ -1257,7 +1264,12 @@ void answer_neighbors(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
 }
 
 // bs.pred / bs.rated of the chunk: launched only when the chunk has something to answer
-void fold_chunk(knncf_handle* h, ChunkState& cs) {
+void fold_chunk(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
+    if (q.predictor == KNNCF_PRED_PERSONALIZED) {  // every rater of every item is a term: no neighbour list, no gather (predict_ms)
+        Stage s(h, &h->tm.predict_ms);
+        foldin_batch_fold_all(h->tr, h->prow, h->query_batch, h->prep.sort, cs.C, cs.qo[cs.C], q.family != QF_FOLD_IN, h->stream);
+        return;
+    }
     cs.ebase.assign((size_t)cs.C + 1, 0);
     for (int32_t s = 0; s < cs.C; ++s) cs.ebase[s + 1] = cs.ebase[s] + cs.info[4 * s + 2];
     foldin_batch_predictions(h->tr, h->query_batch, h->prep.sort, cs.C, cs.take, cs.ebase.data(), h->stream);
@@ -1277,7 +1289,7 @@ int64_t upload_picks(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
     }
     const int64_t m = (int64_t)cs.pick_items.size();
     if (m == 0) return 0;
-    fold_chunk(h, cs);
+    fold_chunk(h, q, cs);
     QueryBatchScratch& bs = h->query_batch;
     bs.pick_items.ensure(m); bs.pick_slot.ensure(m);
     if (q.mode == QB_PREDICT) bs.pick_out.ensure(m);
@@ -1291,7 +1303,8 @@ void answer_predict(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
     if (m == 0) return;
     QueryBatchScratch& bs = h->query_batch;
     hipStream_t st = h->stream;
-    foldin_batch_pick(h->tr, bs, bs.pick_items.p, bs.pick_slot.p, m, bs.pick_out.p, st);
+    if (q.predictor == KNNCF_PRED_PERSONALIZED) foldin_batch_pick_all(h->tr, bs, bs.pick_items.p, bs.pick_slot.p, m, bs.pick_out.p, st);
+    else foldin_batch_pick(h->tr, bs, bs.pick_items.p, bs.pick_slot.p, m, bs.pick_out.p, st);
     cs.h_vals.resize((size_t)m);
     KN_HIP(hipMemcpyAsync(cs.h_vals.data(), bs.pick_out.p, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
     KN_HIP(hipStreamSynchronize(st));
@@ -1336,7 +1349,7 @@ void answer_recommend(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
         widest = std::max(widest, q.counts[b]);
     }
     if (widest == 0) return;
-    fold_chunk(h, cs);
+    fold_chunk(h, q, cs);
     const size_t cells = (size_t)cs.C * widest;
     bs.out_items.ensure(cells); bs.out_preds.ensure(cells);
     foldin_batch_recommend(h->tr, bs, h->prep.sort, cs.C, widest, bs.out_items.p, bs.out_preds.p, st);
@@ -1356,6 +1369,8 @@ void answer_recommend(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
 QueryFailure run_query_chunks(knncf_handle* h, const QueryCall& q, int64_t chunk, int64_t ex_rows) {
     h->prep.join_commit(h->stream);
     const bool update = q.family != QF_FOLD_IN, revise = q.family == QF_REVISE;
+    const bool personalized = q.predictor == KNNCF_PRED_PERSONALIZED;
+    if (personalized) ensure_personal_rows(h, false);
     ChunkState cs;
     cs.take = std::max(0, std::min(h->cfg.k, h->tr.U));
     for (int64_t c0 = 0; c0 < q.B; c0 += chunk) {
@@ -1363,7 +1378,7 @@ QueryFailure run_query_chunks(knncf_handle* h, const QueryCall& q, int64_t chunk
         cs.info.assign((size_t)4 * cs.C, 0);
         foldin_batch_neighbors(h->tr, h->query_batch, h->prep.sort, cs.C, cs.s_users.data(), cs.qo.data(), cs.s_items.data(), cs.s_ratings.data(),
                                update ? cs.s_self.data() : nullptr, update ? cs.ao.data() : nullptr, h->cfg.k, cs.info.data(), h->stream,
-                               revise ? cs.ro.data() : nullptr, revise ? cs.s_removed.data() : nullptr);
+                               revise ? cs.ro.data() : nullptr, revise ? cs.s_removed.data() : nullptr, !personalized);
         if (settle_statuses(q, cs) == 0) continue;
         switch (q.mode) {
             case QB_NEIGHBORS: answer_neighbors(h, q, cs); break;
@@ -1398,7 +1413,7 @@ void do_query_batch(knncf_handle* h, const QueryCall& q) {
     KN_REQUIRE(B >= 0, KNNCF_E_INVALID, "query batch: n_queries < 0");
     KN_REQUIRE(wants_rows(q.mode) || q.width >= 0, KNNCF_E_INVALID, "query batch: cap or n < 0");
     if (q.mode == QB_EXPLAIN) require_explain_order(q.ex);
-    require_query_support(h, q.predictor);
+    require_query_support(h, q.predictor, q.mode);
     if (B == 0) return;
     KN_REQUIRE(q.users && q.offsets && q.statuses && (wants_rows(q.mode) || q.counts), KNNCF_E_INVALID, "query batch: null argument");
     require_offsets(q.offsets, B, "query batch: offsets[0] != 0", "query batch: offsets decrease");
@@ -1451,7 +1466,7 @@ void do_query_single(knncf_handle* h, const QueryCall& call) {
     } else {
         KN_REQUIRE(call.items && call.ratings && call.n_ratings > 0, KNNCF_E_INVALID, "query: null ratings or n_ratings <= 0");
     }
-    require_query_support(h, call.predictor);
+    require_query_support(h, call.predictor, call.mode);
     const int64_t offsets[2] = {0, call.n_ratings}, pred_offsets[2] = {0, call.m}, removed_offsets[2] = {0, call.n_removed};
     int32_t status = KNNCF_OK, c = 0;
     QueryCall q = call;

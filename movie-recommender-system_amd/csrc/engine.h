@@ -347,6 +347,7 @@ struct QueryBatchScratch {
     DArr<int64_t> info;                // [C][4] status bits, known items, neighbour ratings
     DArr<double> scal;                 // [C][2] mean, norm
     DArr<double> sim;                  // [C][U]
+    DArr<double> suu, simT;            // KNNCF_PRED_PERSONALIZED: [C] S(u, u) on aug; [U][stride] sim transposed, stride = 2^ceil(log2 C)
     DArr<uint64_t> k64_a, k64_b;       // [C * max(U, I)]
     DArr<uint32_t> v32_a, v32_b, s32_a, s32_b;
     DArr<int32_t> nbr_idx;             // [C][take]
@@ -374,12 +375,22 @@ struct QueryBatchScratch {
 void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, const int32_t* h_users,
                             const int64_t* h_qo, const int32_t* h_items, const double* h_ratings, const int32_t* h_self,
                             const int64_t* h_ao, int32_t k, long long* h_info, hipStream_t st, const int64_t* h_ro = nullptr,
-                            const int32_t* h_removed = nullptr);
+                            const int32_t* h_removed = nullptr, bool topk = true);
+// (topk = false, the Personalized mode: stops after the similarities — no keys, no sorts, bs.nbr_idx / nbr_sim / off are not
+// written and the neighbour ratings of h_info are 0)
 // bs.pred / bs.rated [C][I]; h_ebase[C + 1] = exclusive prefix of the slots' neighbour ratings
 void foldin_batch_predictions(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, int32_t take,
                               const int64_t* h_ebase, hipStream_t st);
 void foldin_batch_pick(const Train& tr, QueryBatchScratch& bs, const int32_t* d_items, const int32_t* d_slot, int64_t m,
                        double* d_out, hipStream_t st);
+// KNNCF_PRED_PERSONALIZED instead of foldin_batch_predictions, after foldin_batch_neighbors(topk = false) on the chunk of n rows
+// (update: it was given h_self): S(u, u) per slot, the transposed similarities, one fold per (slot, item) over all of the
+// item's raters in file order (pr: personalized_prepare's pf_user / pf_dev), then bs.pred / bs.rated [C][I].  No round trip.
+void foldin_batch_fold_all(const Train& tr, const PersonalRows& pr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, int64_t n,
+                           bool update, hipStream_t st);
+// foldin_batch_pick after foldin_batch_fold_all: an additional item unknown to train has the slot's own term
+void foldin_batch_pick_all(const Train& tr, QueryBatchScratch& bs, const int32_t* d_items, const int32_t* d_slot, int64_t m,
+                           double* d_out, hipStream_t st);
 // after foldin_batch_predictions: the terms behind the predictions of the chunk's rows [r0, r0 + n) of d_items / d_slot, into
 // rows [0, n) of `out`: cell 0 is row r0.  One launch.
 struct QbExplainRows {

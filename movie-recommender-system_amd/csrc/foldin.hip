@@ -30,6 +30,9 @@
 //   k_qb_reco_keys / sort 64 bits / stable sort by slot / k_qb_take               recommendations
 //   k_qb_explain                        (knncf_*_explain*) the elements of those folds for requested (slot, item) rows: one
 //                                       wave per row reads the row's segment of the sorted list that k_q_fold folded
+//   k_qb_self_keys / sort / k_qb_self_sim / k_qb_sim_transpose / k_qb_fold_all / k_qb_pred<false> / k_qb_pick_all
+//                                       (KNNCF_PRED_PERSONALIZED, instead of everything from the top-k to k_qb_pred) S(u, u), the
+//                                       similarities side by side, one fold per (slot, item) over ALL raters of the item
 #include <math.h>
 
 #include <algorithm>
@@ -591,7 +594,8 @@ __global__ void __launch_bounds__(TPB) k_qb_gather(int32_t C, int32_t take, int3
 }
 
 // predictor :568-585 over [C][I]; q's own row of the item comes last in aug with s(q, q) = 0 (q is not in its own
-// neighbour list)
+// neighbour list).  SELF_ZERO = false (the Personalized mode): k_qb_fold_all has folded q's own term at its place already
+template <bool SELF_ZERO>
 __global__ void k_qb_pred(int32_t C, int32_t I, int64_t W, const double* __restrict__ num, const double* __restrict__ den,
                           const unsigned long long* __restrict__ bits, const int64_t* __restrict__ rank,
                           const int64_t* __restrict__ qo, const double* __restrict__ dev_d, const double* __restrict__ scal,
@@ -602,7 +606,7 @@ __global__ void k_qb_pred(int32_t C, int32_t I, int64_t W, const double* __restr
     const unsigned long long* mb = bits + (int64_t)b * W;
     double a = num[g], d = den[g];
     const bool mine = (mb[i >> 6] >> (i & 63)) & 1ull;
-    if (mine) {
+    if (SELF_ZERO && mine) {
         const double s = 0.0;
         a = a + dev_d[qo[b] + bit_rank(mb, rank + (int64_t)b * (W + 1), i)] * s;
         d = d + fabs(s);
@@ -852,7 +856,7 @@ static const uint32_t* qb_segmented_sort(QueryBatchScratch& bs, SortWorkspace& w
 void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, const int32_t* h_users,
                             const int64_t* h_qo, const int32_t* h_items, const double* h_ratings, const int32_t* h_self,
                             const int64_t* h_ao, int32_t k, long long* h_info, hipStream_t st, const int64_t* h_ro,
-                            const int32_t* h_removed) {
+                            const int32_t* h_removed, bool topk) {
     const int32_t U = tr.U, I = tr.I;
     const int64_t W = ceil_div(I, 64), n = h_qo[C];
     const int64_t cells = (int64_t)C * std::max(U, I);
@@ -962,16 +966,18 @@ void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspac
         }
     }
     KN_HIP(hipGetLastError());
-    // top-k of every slot: (similarity desc, dense user asc)
-    launch_fallback_keys((int32_t)((int64_t)C * U), bs.sim.p, bs.k64_a.p, bs.v32_a.p, st);
-    if (self) k_qb_mask_self<<<(unsigned)ceil_div(C, 64), 64, 0, st>>>(C, U, self, bs.k64_a.p);
-    const uint32_t* order = qb_segmented_sort(bs, ws, C, U, st);
-    if (take > 0) {
-        k_qb_write<<<(unsigned)ceil_div((int64_t)C * take, TPB), TPB, 0, st>>>(C, take, U, self, order, bs.sim.p, bs.nbr_idx.p,
-                                                                               bs.nbr_sim.p);
+    if (topk) {  // (the Personalized mode has no neighbourhood cut: foldin_batch_fold_all reads bs.sim as it is)
+        // top-k of every slot: (similarity desc, dense user asc)
+        launch_fallback_keys((int32_t)((int64_t)C * U), bs.sim.p, bs.k64_a.p, bs.v32_a.p, st);
+        if (self) k_qb_mask_self<<<(unsigned)ceil_div(C, 64), 64, 0, st>>>(C, U, self, bs.k64_a.p);
+        const uint32_t* order = qb_segmented_sort(bs, ws, C, U, st);
+        if (take > 0) {
+            k_qb_write<<<(unsigned)ceil_div((int64_t)C * take, TPB), TPB, 0, st>>>(C, take, U, self, order, bs.sim.p, bs.nbr_idx.p,
+                                                                                   bs.nbr_sim.p);
+        }
+        k_qb_offsets<<<C, ONE_BLOCK, 0, st>>>(take, U, self, bs.nbr_idx.p, tr.u_ptr.p, bs.off.p, info);
+        KN_HIP(hipGetLastError());
     }
-    k_qb_offsets<<<C, ONE_BLOCK, 0, st>>>(take, U, self, bs.nbr_idx.p, tr.u_ptr.p, bs.off.p, info);
-    KN_HIP(hipGetLastError());
     // the chunk's one round trip: statuses, known items and the sizes of the prediction pass
     KN_HIP(hipMemcpyAsync(h_info, bs.info.p, (size_t)4 * C * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     KN_HIP(hipStreamSynchronize(st));
@@ -996,10 +1002,234 @@ void foldin_batch_predictions(const Train& tr, QueryBatchScratch& bs, SortWorksp
         sort_pairs_u64_u32(ws, bs.e_k64_a.p, bs.e_k64_b.p, bs.e_v32_a.p, bs.e_v32_b.p, (size_t)E, 32 + bits_for((uint64_t)cells), st);
         k_q_fold<<<(unsigned)ceil_div(E, TPB), TPB, 0, st>>>(E, bs.e_k64_b.p, bs.e_v32_b.p, bs.e_dev.p, bs.e_sim.p, bs.num.p, bs.den.p);
     }
-    k_qb_pred<<<(unsigned)ceil_div(cells, TPB), TPB, 0, st>>>(C, I, W, bs.num.p, bs.den.p, (const unsigned long long*)bs.bits.p,
-                                                              bs.rank.p, bs.qo.p, bs.dev_d.p, bs.scal.p, bs.pred.p, bs.rated.p);
+    k_qb_pred<true><<<(unsigned)ceil_div(cells, TPB), TPB, 0, st>>>(C, I, W, bs.num.p, bs.den.p, (const unsigned long long*)bs.bits.p,
+                                                                    bs.rank.p, bs.qo.p, bs.dev_d.p, bs.scal.p, bs.pred.p, bs.rated.p);
     if (bs.n_removed > 0)
         k_qb_gone_rated<<<(unsigned)ceil_div(bs.n_removed, TPB), TPB, 0, st>>>(bs.n_removed, I, bs.rm_slot.p, bs.rm_gone.p, bs.rated.p);
+    KN_HIP(hipGetLastError());
+}
+
+// ---- the Personalized predictor of a chunk (KNNCF_PRED_PERSONALIZED on the query families; DESIGN.md "Personalized queries")
+// predictor(aug, weightedSumDeviation(aug, S)) with no neighbourhood cut: every rating of an item in aug is a term of its
+// fold :508-524, the query user's own included, with S(u, u) != 0 as its weight.  bs.sim[C][U] holds S(u, v) for every train
+// user v already (the query user owns every pair); what is added here is S(u, u), the transposed similarities and ONE fold
+// per (slot, item) over the item's raters in file order.  No top-k, no gather, no sort of neighbour ratings.
+
+// key of u's item-set order (ratedByUsers(u).map(_.item).toSet :418): the slot, then the trie order of the item id — every
+// item of the slot's rows, the ones unknown to train included
+__global__ void k_qb_self_keys(int64_t n, const int32_t* __restrict__ slot, const int32_t* __restrict__ items,
+                               uint64_t* __restrict__ key, uint32_t* __restrict__ val) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    key[j] = ((uint64_t)(uint32_t)slot[j] << 32) | (uint64_t)int_trie_key(items[j]);
+    val[j] = (uint32_t)j;
+}
+
+// S(u, u) on aug, one wave per slot.  Cosine :424-426: ratedByBoth = u's item set, so the value is the left fold from 0.0 of
+// pre(u, j) * pre(u, j) in the set's iteration order: the trie order (sval, sorted by k_qb_self_keys) for more than 4 rows,
+// the given order (Set1..Set4) otherwise.  The products are formed 64 at a time, the additions run one by one in order.
+// Jaccard :454-458: n / (n + n - n) = 1.0.  A fitted user's cell of [C][U] was computed against its OLD train row: replaced.
+__global__ void __launch_bounds__(64) k_qb_self_sim(int32_t U, bool jaccard, const int64_t* __restrict__ qo,
+                                                    const double* __restrict__ pre, const uint32_t* __restrict__ sval,
+                                                    const int32_t* __restrict__ self, double* __restrict__ suu,
+                                                    double* __restrict__ sim) {
+    const int32_t b = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int64_t o = qo[b];
+    const int32_t n = (int32_t)(qo[b + 1] - o);
+    const bool small = n <= 4;
+    double s = 0.0;
+    if (jaccard) {
+        s = 1.0;
+    } else {
+        for (int32_t base = 0; base < n; base += 64) {
+            const int cnt = min(64, n - base);
+            double x = 0.0;
+            if (lane < cnt) {
+                const double v = small ? pre[o + base + lane] : pre[sval[o + base + lane]];
+                x = v * v;
+            }
+            const int32_t x_lo = __double2loint(x), x_hi = __double2hiint(x);
+            for (int l = 0; l < cnt; ++l)
+                s = s + __hiloint2double(__builtin_amdgcn_readlane(x_hi, l), __builtin_amdgcn_readlane(x_lo, l));
+        }
+    }
+    if (lane == 0) {
+        suu[b] = s;
+        if (self && self[b] >= 0) sim[(int64_t)b * U + self[b]] = s;
+    }
+}
+
+// [C][U] -> [U][stride]: one train user's similarities to all slots of the chunk side by side (stride = a power of two >= C;
+// the cells of slots >= C hold 0.0 and are never folded).  64 x 64 tiles through LDS: both sides coalesced.
+__global__ void __launch_bounds__(TPB) k_qb_sim_transpose(int32_t U, int32_t C, int32_t stride, const double* __restrict__ sim,
+                                                          double* __restrict__ simT) {
+    __shared__ double tile[64][65];
+    const int x = threadIdx.x & 63, y = threadIdx.x >> 6;
+    const int64_t v0 = (int64_t)blockIdx.x * 64;
+    for (int b = y; b < 64; b += TPB / 64) tile[b][x] = (b < C && v0 + x < U) ? sim[(int64_t)b * U + v0 + x] : 0.0;
+    __syncthreads();
+    if (x >= stride) return;
+    for (int vv = y; vv < 64 && v0 + vv < U; vv += TPB / 64) simT[(v0 + vv) * stride + x] = tile[x][vv];
+}
+
+// The fold of a chunk: ONE WAVE PER TRAIN ITEM, LANE b OWNS SLOT b (the layout of k_query_sim_dual).  The wave walks the item's
+// raters in file order (pf_user / pf_dev, 64 per coalesced load), one wave-uniform entry at a time; every lane reads its own
+// similarity to that rater from the transposed row (one coalesced read per entry) and runs num = num + dev * s, den = den +
+// |s| in its own registers: the left folds of :520-524, multiply and add separate.  The similarity loads do not depend on the
+// add chains, so FA_AHEAD of them are issued before the adds that use them.
+// The slot's own user as a rater (self[b]): its train row SURVIVES in aug when the slot rates the item at a given position
+// below its number of surviving train rows (they come first: k_qb_seed / k_qb_seed_rv) — the term is then the slot's
+// deviation ON AUG (the mean changed) with S(u, u), at the row's file place.  A removed or re-rated train row is no term: it
+// adds dev 0.0 * s 0.0, an identity (the sums start at +0.0 and cannot become -0.0).  A slot that rates the item through an
+// additional row has that term last, after every train row.  Longest items first (pop_item).
+// Bounds.  w < I, i = pop_item[w] is a dense item of [0, I); entries lie in [i_ptr[i], i_ptr[i + 1]) within [0, n); pf_user is
+// a dense user of [0, U), col < stride, so the read cell is inside simT [U][stride].  bit_rank of a set bit of slot b is below
+// the slot's number of known items <= its rows, so o + r is inside the slot's extent of dev_d / given_d.  Lanes >= C read
+// column 0 and write nothing.
+static constexpr int FA_WAVES = 4;  // waves (items) per workgroup
+static constexpr int FA_AHEAD = 8;  // similarity loads in flight per lane
+__global__ void __launch_bounds__(FA_WAVES * 64) k_qb_fold_all(int32_t I, int32_t C, int32_t stride, int64_t W,
+                                                               const int32_t* __restrict__ pop_item, const int64_t* __restrict__ i_ptr,
+                                                               const int32_t* __restrict__ pf_user, const double* __restrict__ pf_dev,
+                                                               const double* __restrict__ simT,
+                                                               const unsigned long long* __restrict__ bits,
+                                                               const int64_t* __restrict__ rank, const int64_t* __restrict__ qo,
+                                                               const int64_t* __restrict__ ao, const int32_t* __restrict__ self,
+                                                               const double* __restrict__ dev_d, const int32_t* __restrict__ given_d,
+                                                               const double* __restrict__ suu, double* __restrict__ num,
+                                                               double* __restrict__ den) {
+    const int lane = threadIdx.x & 63;
+    const int64_t w = (int64_t)blockIdx.x * FA_WAVES + (threadIdx.x >> 6);
+    if (w >= I) return;
+    const int32_t i = __builtin_amdgcn_readfirstlane(pop_item[w]);  // (wave-uniform: the list bounds and the trip counts are scalars)
+    const bool live = lane < C;
+    const int col = live ? lane : 0;
+    int32_t me = -1;
+    double own_s = 0.0, own_dev = 0.0, last_s = 0.0, last_dev = 0.0;
+    bool last = false;
+    if (live) {
+        if (self) me = self[lane];
+        const unsigned long long* mb = bits + (int64_t)lane * W;
+        if ((mb[i >> 6] >> (i & 63)) & 1ull) {
+            const int64_t o = qo[lane];
+            const int32_t r = bit_rank(mb, rank + (int64_t)lane * (W + 1), i);
+            const int64_t survivors = ao ? (qo[lane + 1] - o) - (ao[lane + 1] - ao[lane]) : 0;
+            if (given_d[o + r] < survivors) {
+                own_s = suu[lane];
+                own_dev = dev_d[o + r];
+            } else {
+                last = true;
+                last_s = suu[lane];
+                last_dev = dev_d[o + r];
+            }
+        }
+    }
+    double a = 0.0, d = 0.0;
+    const int64_t rb = i_ptr[i], re = i_ptr[i + 1];
+    for (int64_t base = rb; base < re; base += 64) {
+        const int cnt = (int)min((int64_t)64, re - base);
+        const int32_t mv = lane < cnt ? pf_user[base + lane] : 0;
+        const double md = lane < cnt ? pf_dev[base + lane] : 0.0;
+        const int32_t md_lo = __double2loint(md), md_hi = __double2hiint(md);
+        // (wave-uniform l: the rater and its deviation come out of the lanes' registers, v_readlane)
+        auto term = [&](int32_t v, double sl, int l) {
+            const double dv = __hiloint2double(__builtin_amdgcn_readlane(md_hi, l), __builtin_amdgcn_readlane(md_lo, l));
+            const bool mine = v == me;
+            const double sv = mine ? own_s : sl;
+            const double dd = mine ? own_dev : dv;
+            a = a + dd * sv;
+            d = d + fabs(sv);
+        };
+        int l0 = 0;
+        for (; l0 + FA_AHEAD <= cnt; l0 += FA_AHEAD) {
+            int32_t v[FA_AHEAD];
+            double s[FA_AHEAD];
+#pragma unroll
+            for (int q = 0; q < FA_AHEAD; ++q) {
+                v[q] = __builtin_amdgcn_readlane(mv, l0 + q);
+                s[q] = simT[(int64_t)v[q] * stride + col];
+            }
+#pragma unroll
+            for (int q = 0; q < FA_AHEAD; ++q) term(v[q], s[q], l0 + q);
+        }
+        for (; l0 < cnt; ++l0) {
+            const int32_t v = __builtin_amdgcn_readlane(mv, l0);
+            term(v, simT[(int64_t)v * stride + col], l0);
+        }
+    }
+    if (last) {
+        a = a + last_dev * last_s;
+        d = d + fabs(last_s);
+    }
+    if (live) {
+        num[(int64_t)lane * I + i] = a;
+        den[(int64_t)lane * I + i] = d;
+    }
+}
+
+// k_qb_pick of the Personalized mode: an item that has no dense id but is one of the slot's rows (an additional item unknown
+// to train) has exactly one term in aug, the slot's own: num = 0.0 + dev(u, i) * S(u, u), den = 0.0 + |S(u, u)|.  Any other
+// item without a dense id is unknown to aug: the mean exactly.
+__global__ void k_qb_pick_all(int64_t m, const int32_t* __restrict__ items, const int32_t* __restrict__ slot,
+                              const int32_t* __restrict__ i_table, int32_t i_cells, const uint32_t* __restrict__ ikeys, int32_t I,
+                              const double* __restrict__ pred, const double* __restrict__ scal, const int64_t* __restrict__ qo,
+                              const int32_t* __restrict__ q_items, const double* __restrict__ q_dev, const double* __restrict__ suu,
+                              double* __restrict__ out) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const int32_t it = items[j], b = slot[j];
+    int32_t c;
+    if (i_cells > 0) c = (it >= 0 && it < i_cells) ? i_table[it] : -1;
+    else c = dense_lookup(ikeys, I, it);
+    if (c >= 0) {
+        out[j] = pred[(int64_t)b * I + c];
+        return;
+    }
+    double a = 0.0, d = 0.0;
+    for (int64_t x = qo[b]; x < qo[b + 1]; ++x) {
+        if (q_items[x] == it) {
+            const double s = suu[b];
+            a = a + q_dev[x] * s;
+            d = d + fabs(s);
+            break;
+        }
+    }
+    const double avg = scal[2 * b];
+    const double w = d > 0 ? a / d : 0.0;
+    out[j] = avg + w * scale_fn(avg + w, avg);
+}
+
+void foldin_batch_fold_all(const Train& tr, const PersonalRows& pr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, int64_t n,
+                           bool update, hipStream_t st) {
+    const int32_t U = tr.U, I = tr.I;
+    const int64_t W = ceil_div(I, 64), cells = (int64_t)C * I;
+    int32_t stride = 1;
+    while (stride < C) stride <<= 1;
+    bs.suu.ensure(C); bs.simT.ensure((size_t)U * stride);
+    bs.num.ensure(cells); bs.den.ensure(cells); bs.pred.ensure(cells); bs.rated.ensure(cells);
+    const int32_t* self = update ? bs.self.p : nullptr;
+    // S(u, u) of every slot (and the own cell of a fitted user), then the similarities side by side
+    k_qb_self_keys<<<(unsigned)ceil_div(n, TPB), TPB, 0, st>>>(n, bs.slot.p, bs.items.p, bs.k64_a.p, bs.v32_a.p);
+    sort_pairs_u64_u32(ws, bs.k64_a.p, bs.k64_b.p, bs.v32_a.p, bs.v32_b.p, (size_t)n, 32 + (C > 1 ? bits_for((uint64_t)(C - 1)) : 0), st);
+    k_qb_self_sim<<<C, 64, 0, st>>>(U, tr.jaccard, bs.qo.p, bs.pre.p, bs.v32_b.p, self, bs.suu.p, bs.sim.p);
+    k_qb_sim_transpose<<<(unsigned)ceil_div(U, 64), TPB, 0, st>>>(U, C, stride, bs.sim.p, bs.simT.p);
+    KN_TRACE_DISPATCH("qb_fold_all stride=%d", (int)stride);
+    k_qb_fold_all<<<(unsigned)ceil_div(I, FA_WAVES), FA_WAVES * 64, 0, st>>>(
+        I, C, stride, W, tr.pop_item.p, tr.i_ptr.p, pr.pf_user.p, pr.pf_dev.p, bs.simT.p, (const unsigned long long*)bs.bits.p, bs.rank.p,
+        bs.qo.p, update ? bs.ao.p : nullptr, self, bs.dev_d.p, bs.given_d.p, bs.suu.p, bs.num.p, bs.den.p);
+    k_qb_pred<false><<<(unsigned)ceil_div(cells, TPB), TPB, 0, st>>>(C, I, W, bs.num.p, bs.den.p, (const unsigned long long*)bs.bits.p,
+                                                                     bs.rank.p, bs.qo.p, bs.dev_d.p, bs.scal.p, bs.pred.p, bs.rated.p);
+    if (bs.n_removed > 0)
+        k_qb_gone_rated<<<(unsigned)ceil_div(bs.n_removed, TPB), TPB, 0, st>>>(bs.n_removed, I, bs.rm_slot.p, bs.rm_gone.p, bs.rated.p);
+    KN_HIP(hipGetLastError());
+}
+
+void foldin_batch_pick_all(const Train& tr, QueryBatchScratch& bs, const int32_t* d_items, const int32_t* d_slot, int64_t m,
+                           double* d_out, hipStream_t st) {
+    if (m <= 0) return;
+    k_qb_pick_all<<<(unsigned)ceil_div(m, TPB), TPB, 0, st>>>(m, d_items, d_slot, tr.i_table.p, table_cells(tr), tr.ikeys.p, tr.I,
+                                                              bs.pred.p, bs.scal.p, bs.qo.p, bs.items.p, bs.dev.p, bs.suu.p, d_out);
     KN_HIP(hipGetLastError());
 }
 

@@ -513,6 +513,8 @@ class Engine:
 
     # ---- fold-in queries: a user outside the fit (knncf_query_*), and update queries: any user, the rows being additional
     # to its train rows (knncf_update_*).  The two families share their argument lists; `fam` picks the entry points. ----
+    # The predict / recommend forms take predictor=PRED_KNN (the default) or PRED_PERSONALIZED: the Personalized predictor on
+    # aug, every rating of an item a term and the handle's k without a part (include/knncf.h "Personalized queries").
     @staticmethod
     def _query_rows(user, items, ratings, allow_empty=False):
         """validated (user, items, ratings) of a query: ValueError before any C call"""
@@ -572,7 +574,7 @@ class Engine:
         m = min(c.value, cap)
         return ids[:m].copy(), sims[:m].copy()
 
-    def _predict_q(self, fam, user, items, ratings, pred_items, removed=None):
+    def _predict_q(self, fam, user, items, ratings, pred_items, removed=None, predictor=PRED_KNN):
         q, it, rt = self._query_rows(user, items, ratings, allow_empty=fam != "query")
         rm = self._rm_args(fam, removed)
         pi = np.asarray(pred_items)
@@ -581,11 +583,11 @@ class Engine:
         pi = _i32(pi)
         out = np.empty(max(1, len(pi)), dtype=np.float64)
         p = self._ptr
-        self._check(getattr(self._lib, f"knncf_{fam}_predict")(self._h, PRED_KNN, q, *rm, p(it, _i32p), p(rt, _f64p), len(it),
+        self._check(getattr(self._lib, f"knncf_{fam}_predict")(self._h, predictor, q, *rm, p(it, _i32p), p(rt, _f64p), len(it),
                                                                pi.ctypes.data_as(_i32p), len(pi), out.ctypes.data_as(_f64p)))
         return out[:len(pi)].copy()
 
-    def _recommend_q(self, fam, user, items, ratings, n, removed=None):
+    def _recommend_q(self, fam, user, items, ratings, n, removed=None, predictor=PRED_KNN):
         q, it, rt = self._query_rows(user, items, ratings, allow_empty=fam != "query")
         rm = self._rm_args(fam, removed)
         if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0 or n >= 2**31:
@@ -595,7 +597,7 @@ class Engine:
         preds = np.empty(max(1, n), dtype=np.float64)
         c = C.c_int32()
         p = self._ptr
-        self._check(getattr(self._lib, f"knncf_{fam}_recommend")(self._h, PRED_KNN, q, *rm, p(it, _i32p), p(rt, _f64p), len(it), n,
+        self._check(getattr(self._lib, f"knncf_{fam}_recommend")(self._h, predictor, q, *rm, p(it, _i32p), p(rt, _f64p), len(it), n,
                                                                  ids.ctypes.data_as(_i32p), preds.ctypes.data_as(_f64p), C.byref(c)))
         return ids[:c.value].copy(), preds[:c.value].copy()
 
@@ -603,39 +605,39 @@ class Engine:
         """getNeighbors(train ++ user's ratings, k, sim)(user) for a user outside the fit: (ids, sims)"""
         return self._neighbors_q("query", user, items, ratings, cap)
 
-    def predict_for(self, user, items, ratings, pred_items):
+    def predict_for(self, user, items, ratings, pred_items, predictor=PRED_KNN):
         """kNN predictions (PRED_KNN) of a user outside the fit, given its ratings, for every id of pred_items"""
-        return self._predict_q("query", user, items, ratings, pred_items)
+        return self._predict_q("query", user, items, ratings, pred_items, predictor=predictor)
 
-    def recommend_for(self, user, items, ratings, n):
+    def recommend_for(self, user, items, ratings, n, predictor=PRED_KNN):
         """recommendations(train ++ user's ratings, kNN predictor)(user, n) for a user outside the fit: (item ids, predictions)"""
-        return self._recommend_q("query", user, items, ratings, n)
+        return self._recommend_q("query", user, items, ratings, n, predictor=predictor)
 
     def neighbors_with(self, user, items, ratings, cap=None):
         """getNeighbors(train ++ the additional ratings, k, sim)(user) for any user, of the fit or not: (ids, sims).  A user
         of the fit is not its own neighbour; items / ratings may be empty for it."""
         return self._neighbors_q("update", user, items, ratings, cap)
 
-    def predict_with(self, user, items, ratings, pred_items):
+    def predict_with(self, user, items, ratings, pred_items, predictor=PRED_KNN):
         """kNN predictions (PRED_KNN) of a user with additional ratings (beside its train rows, if any) for every id of pred_items"""
-        return self._predict_q("update", user, items, ratings, pred_items)
+        return self._predict_q("update", user, items, ratings, pred_items, predictor=predictor)
 
-    def recommend_with(self, user, items, ratings, n):
+    def recommend_with(self, user, items, ratings, n, predictor=PRED_KNN):
         """recommendations(train ++ the additional ratings, kNN predictor)(user, n) for any user: (item ids, predictions)"""
-        return self._recommend_q("update", user, items, ratings, n)
+        return self._recommend_q("update", user, items, ratings, n, predictor=predictor)
 
     def neighbors_revised(self, user, removed, items, ratings, cap=None):
         """getNeighbors(aug, k, sim)(user) where aug is train without the user's rows on the `removed` items, plus the additional
         (items, ratings): (ids, sims).  An item both removed and given again is re-rated."""
         return self._neighbors_q("revise", user, items, ratings, cap, removed)
 
-    def predict_revised(self, user, removed, items, ratings, pred_items):
+    def predict_revised(self, user, removed, items, ratings, pred_items, predictor=PRED_KNN):
         """kNN predictions (PRED_KNN) of a user that removed the `removed` train items and rated (items, ratings) in addition"""
-        return self._predict_q("revise", user, items, ratings, pred_items, removed)
+        return self._predict_q("revise", user, items, ratings, pred_items, removed, predictor)
 
-    def recommend_revised(self, user, removed, items, ratings, n):
+    def recommend_revised(self, user, removed, items, ratings, n, predictor=PRED_KNN):
         """recommendations(aug, kNN predictor)(user, n) on that aug: (item ids, predictions)"""
-        return self._recommend_q("revise", user, items, ratings, n, removed)
+        return self._recommend_q("revise", user, items, ratings, n, removed, predictor)
 
     @staticmethod
     def _pred_items(pred_items):
@@ -749,7 +751,7 @@ class Engine:
             p(sims.reshape(-1), _f64p), p(counts, _i32p), p(st, _i32p)))
         return [(ids[b, :min(counts[b], cap)].copy(), sims[b, :min(counts[b], cap)].copy()) for b in range(B)], st
 
-    def _predict_qb(self, fam, queries, pred_items):
+    def _predict_qb(self, fam, queries, pred_items, predictor=PRED_KNN):
         qargs, keep = self._batch_args(fam, queries)
         B = qargs[-1]
         pis = [np.asarray(x) for x in pred_items]
@@ -765,11 +767,11 @@ class Engine:
         st = np.zeros(B, dtype=np.int32)
         p = self._ptr
         self._check(getattr(self._lib, f"knncf_{fam}_predict_batch")(
-            self._h, PRED_KNN, *qargs, p(poff, _i64p), p(pi, _i32p),
+            self._h, predictor, *qargs, p(poff, _i64p), p(pi, _i32p),
             p(out, _f64p), p(st, _i32p)))
         return [out[poff[b]:poff[b + 1]].copy() for b in range(B)], st
 
-    def _recommend_qb(self, fam, queries, n):
+    def _recommend_qb(self, fam, queries, n, predictor=PRED_KNN):
         qargs, keep = self._batch_args(fam, queries)
         if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0 or n >= 2**31:
             raise ValueError("n must be a non-negative 32-bit integer")
@@ -780,7 +782,7 @@ class Engine:
         st = np.zeros(B, dtype=np.int32)
         p = self._ptr
         self._check(getattr(self._lib, f"knncf_{fam}_recommend_batch")(
-            self._h, PRED_KNN, *qargs, n, p(ids.reshape(-1), _i32p),
+            self._h, predictor, *qargs, n, p(ids.reshape(-1), _i32p),
             p(preds.reshape(-1), _f64p), p(counts, _i32p), p(st, _i32p)))
         return [(ids[b, :counts[b]].copy(), preds[b, :counts[b]].copy()) for b in range(B)], st
 
@@ -789,42 +791,42 @@ class Engine:
         ([(ids, sims)] per query, statuses int32 [B]).  A failed query (status != OK) has empty arrays."""
         return self._neighbors_qb("query", queries, cap)
 
-    def predict_for_batch(self, queries, pred_items):
+    def predict_for_batch(self, queries, pred_items, predictor=PRED_KNN):
         """predict_for of every query; pred_items is one sequence of item ids per query: ([float64 array] per query, statuses).
         A failed query's array holds NaN."""
-        return self._predict_qb("query", queries, pred_items)
+        return self._predict_qb("query", queries, pred_items, predictor)
 
-    def recommend_for_batch(self, queries, n):
+    def recommend_for_batch(self, queries, n, predictor=PRED_KNN):
         """recommend_for(n) of every query: ([(item ids, predictions)] per query, statuses).  A failed query has empty arrays."""
-        return self._recommend_qb("query", queries, n)
+        return self._recommend_qb("query", queries, n, predictor)
 
     def neighbors_with_batch(self, queries, cap=None):
         """neighbors_with of every (user, additional items, additional ratings) of `queries`, users of the fit and others
         mixed: ([(ids, sims)] per query, statuses int32 [B]).  A failed query (status != OK) has empty arrays."""
         return self._neighbors_qb("update", queries, cap)
 
-    def predict_with_batch(self, queries, pred_items):
+    def predict_with_batch(self, queries, pred_items, predictor=PRED_KNN):
         """predict_with of every query; pred_items is one sequence of item ids per query: ([float64 array] per query, statuses).
         A failed query's array holds NaN."""
-        return self._predict_qb("update", queries, pred_items)
+        return self._predict_qb("update", queries, pred_items, predictor)
 
-    def recommend_with_batch(self, queries, n):
+    def recommend_with_batch(self, queries, n, predictor=PRED_KNN):
         """recommend_with(n) of every query: ([(item ids, predictions)] per query, statuses).  A failed query has empty arrays."""
-        return self._recommend_qb("update", queries, n)
+        return self._recommend_qb("update", queries, n, predictor)
 
     def neighbors_revised_batch(self, queries, cap=None):
         """neighbors_revised of every (user, removed_items, additional items, additional ratings) of `queries`:
         ([(ids, sims)] per query, statuses int32 [B]).  A failed query (status != OK) has empty arrays."""
         return self._neighbors_qb("revise", queries, cap)
 
-    def predict_revised_batch(self, queries, pred_items):
+    def predict_revised_batch(self, queries, pred_items, predictor=PRED_KNN):
         """predict_revised of every query; pred_items is one sequence of item ids per query: ([float64 array] per query, statuses).
         A failed query's array holds NaN."""
-        return self._predict_qb("revise", queries, pred_items)
+        return self._predict_qb("revise", queries, pred_items, predictor)
 
-    def recommend_revised_batch(self, queries, n):
+    def recommend_revised_batch(self, queries, n, predictor=PRED_KNN):
         """recommend_revised(n) of every query: ([(item ids, predictions)] per query, statuses).  A failed query has empty arrays."""
-        return self._recommend_qb("revise", queries, n)
+        return self._recommend_qb("revise", queries, n, predictor)
 
     def _explain_qb(self, fam, queries, pred_items, cap, order):
         cap, order = self._explain_args(cap, order)
