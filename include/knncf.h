@@ -173,7 +173,11 @@ int knncf_predict(knncf_handle* h, int predictor, int32_t user, int32_t item, do
 /* recommendations(train, predictor)(user, n) shared/predictions.scala:651-674 (called by
  * recommend/Recommender.scala:85-88 with n = 3): every train item `user` has not rated, predicted with `predictor`,
  * ordered by (prediction descending, raw item id ascending); the first min(n, #unrated) are written, *count of them.
- * An unknown user has rated nothing (every prediction is the global average: pure id order). */
+ * An unknown user has rated nothing (every prediction is the global average: pure id order).
+ * This is knncf_recommend_batch over the one user (*count = its counts[0]): the same code, the same handle state afterwards and
+ * the same statuses, shard handles included.  An unfitted handle (KNNCF_E_STATE) and a bad argument (count null, n < 0, a null
+ * output with n > 0: KNNCF_E_INVALID) leave *count alone; past these two checks *count = 0 is written before anything else
+ * can fail. */
 int knncf_recommend(knncf_handle* h, int predictor, int32_t user, int32_t n, int32_t* items,
                     double* predictions, int32_t* count);
 
@@ -186,26 +190,29 @@ int knncf_recommend(knncf_handle* h, int predictor, int32_t user, int32_t n, int
  * (KNNCF_PRED_KNN on a KNNCF_SIM_ONE handle: KNNCF_E_UNSUPPORTED, ...).
  * Order and handle state.  The call behaves as if knncf_recommend had been called for users[0], users[1], ... in this order
  * on this handle: a neighbourhood that does not exist yet is built and numbered by the call, and a pair with a <= 4-rating
- * user is summed in the order that numbering decides.  The missing neighbourhoods are built in ONE batch, and THE
- * HANDLE IS LEFT IN THE STATE THAT knncf_neighbors_batch OVER THE SAME users LEAVES IT IN (KNNCF_PRED_KNN; the other
- * predictors leave the neighbour table alone, as the single call does): the same lists, the same build numbers
- * (call, position in users), the same knncf_neighbors_save file.  (A loop of single calls numbers its builds (call, 0), one
- * call each: the same order, hence the same lists and sums, under different numbers.)
+ * user is summed in the order that numbering decides.  KNNCF_PRED_KNN builds and numbers the neighbourhood of
+ * users[b] only where the reference evaluates it: the user is in train and its mean is not negative (the predictor answers a
+ * negative mean with the global average, :573, before it looks at a neighbour).  The missing neighbourhoods are built in ONE
+ * batch, and THE HANDLE IS LEFT IN THE STATE THAT knncf_neighbors_batch OVER THE SAME users LEAVES IT IN ONCE THOSE WHOSE MEAN
+ * IS NEGATIVE ARE TAKEN OUT OF THEM (the other predictors leave the neighbour table alone): the same lists, the same build
+ * numbers (call, position in users), the same knncf_neighbors_save file.  knncf_neighbors_batch itself numbers every user it
+ * is asked about.  (A loop of single calls numbers its builds (call, 0), one call each: the same order, hence the same lists
+ * and sums, under different numbers.)
  * Status: KNNCF_E_STATE before a fit; KNNCF_E_INVALID for a null pointer with n_users > 0, n_users < 0, n < 0 or an unknown
  * predictor; n_users == 0 or n == 0 is KNNCF_OK (n == 0: counts[b] = 0 for every b) and touches nothing else.  Shard
  * handles: every known user must be owned by the shard and an unknown user is answered by shard 0 only (KNNCF_E_STATE
  * otherwise, for the whole call, before anything is built); a neighbourhood that is not built yet is refused on a shard
- * whose train set has a <= 4-rating user, as knncf_neighbors_batch refuses it.  A call that fails these checks builds
- * nothing and writes nothing.
+ * whose train set has a <= 4-rating user, as knncf_neighbors_batch refuses it (KNNCF_E_UNSUPPORTED) — by knncf_recommend
+ * too: such a list would be built under a number that the other shards never see.  A call that fails
+ * these checks builds nothing and writes nothing.
  * Chunks.  The users are answered in chunks of consecutive rows, [0, C), [C, 2 C), ..., the last one possibly shorter:
  *     C = max(1, min(1024, budget / (96 * num_items), (2^31 - 1) / num_items))
  *     budget = workspace_bytes / 2 if workspace_bytes > 0, else min(48 GiB, free device memory / 4)
  * The results do not depend on C, and a call on a handle that has answered the same shape before allocates no device memory.
- * KNNCF_PRED_KNN with k <= 2048 folds every (user, item) prediction from the user's neighbour list in one launch per chunk
- * (the neighbours' ratings are merged per item in LDS, in training-file order); longer lists and the other predictors send
- * the chunk's C x num_items rows through the general prediction batch.  n <= 32 then selects each row's n best without
- * sorting; larger n (up to and beyond num_items) orders each row completely.  knncf_get_timings: neighbour builds are charged
- * as in knncf_neighbors_batch, everything else as predict_ms. */
+ * Every predictor sends the chunk's C x num_items rows through the prediction batch that knncf_predict_batch runs (there is no
+ * threshold on the chunk size: a chunk of one, which is what knncf_recommend asks for, takes the same path).  n <= 32 then
+ * selects each row's n best without sorting; larger n (up to and beyond num_items) orders each row completely.
+ * knncf_get_timings: neighbour builds are charged as in knncf_neighbors_batch, everything else as predict_ms. */
 int knncf_recommend_batch(knncf_handle* h, int predictor, const int32_t* users, int64_t n_users, int32_t n,
                           int32_t* out_items, double* out_preds, int32_t* counts);
 

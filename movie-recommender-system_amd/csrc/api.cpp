@@ -70,11 +70,8 @@ struct knncf_handle {
     bool pt_ready = false;
     PersonalRows prow;      // Personalized (no k) beyond the table: first-use copies + the row scratch (personalized.hip)
     bool prow_ready = false, prow_checked = false;  // the copies are built; the fitted path's refusals were checked
-    DArr<int32_t> reco_users, reco_items, reco_out_items;
-    DArr<double> reco_pred, reco_out_preds;
-    DArr<uint8_t> reco_rated;
     QueryBatchScratch query_batch;  // fold-in queries (foldin.hip)
-    RecoBatchScratch reco_batch;  // knncf_recommend_batch (reco_batch.hip); lends query_batch's prediction and sort buffers
+    RecoBatchScratch reco_batch;  // knncf_recommend / knncf_recommend_batch (reco_batch.hip); lends query_batch's prediction and sort buffers
     DArr<int32_t> build_list, build_count;
     DArr<uint32_t> first_row;
     // test scratch
@@ -94,6 +91,7 @@ struct knncf_handle {
     std::vector<uint32_t> h_ukeys, h_ikeys;
     std::vector<int32_t> h_uid;
     std::vector<int64_t> h_uptr;  // row extents (update queries)
+    std::vector<double> h_uavg;   // user means (recommendations: whose neighbourhood the reference builds)
     knncf_timings tm{};
     std::vector<StageTimer> pending;
     std::vector<hipEvent_t> event_pool;
@@ -209,6 +207,15 @@ int64_t train_row_length(knncf_handle* h, int32_t du) {
         KN_HIP(hipStreamSynchronize(h->stream));
     }
     return h->h_uptr[du + 1] - h->h_uptr[du];
+}
+// mean of dense user du in train
+double train_user_avg(knncf_handle* h, int32_t du) {
+    if (h->h_uavg.empty()) {
+        h->h_uavg.resize((size_t)h->tr.U);
+        KN_HIP(hipMemcpyAsync(h->h_uavg.data(), h->tr.user_avg.p, h->h_uavg.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        KN_HIP(hipStreamSynchronize(h->stream));
+    }
+    return h->h_uavg[du];
 }
 int32_t dense_item(knncf_handle* h, int32_t raw) {
     load_host_ids(h);
@@ -987,7 +994,7 @@ void do_fit_device(knncf_handle* h, const int32_t* d_users, const int32_t* d_ite
     h->pt_ready = false;
     h->prow_ready = false;
     h->prow_checked = false;
-    h->h_ukeys.clear(); h->h_ikeys.clear(); h->h_uid.clear(); h->h_uptr.clear();
+    h->h_ukeys.clear(); h->h_ikeys.clear(); h->h_uid.clear(); h->h_uptr.clear(); h->h_uavg.clear();
     tr.n = n;
     tr.jaccard = h->cfg.similarity == KNNCF_SIM_JACCARD;
     {
@@ -1007,42 +1014,6 @@ void do_fit_device(knncf_handle* h, const int32_t* d_users, const int32_t* d_ite
         prep_commit(tr, h->prep, st);
         h->committed = true;
     }
-}
-
-// recommendations(ratings, predictor)(user, n) shared/predictions.scala:651-674
-void do_recommend(knncf_handle* h, int predictor, int32_t user, int32_t n, int32_t* out_items, double* out_preds, int32_t* count) {
-    require_fitted(h);
-    KN_REQUIRE(count && n >= 0 && (n == 0 || (out_items && out_preds)), KNNCF_E_INVALID, "bad arguments");
-    *count = 0;
-    Train& tr = h->tr;
-    if (n == 0 || tr.I == 0) return;
-    hipStream_t st = h->stream;
-    const int32_t du = dense_user(h, user);
-    KN_REQUIRE(du < 0 ? h->cfg.shard_rank == 0 : (du >= tr.own_lo && du < tr.own_hi), KNNCF_E_STATE,
-               "recommend: the user belongs to another shard");
-    const int32_t I = tr.I;
-    h->reco_users.ensure(I); h->reco_items.ensure(I); h->reco_pred.ensure(I); h->reco_rated.ensure(I);
-    launch_reco_rows(tr, user, du, h->reco_users.p, h->reco_items.p, h->reco_rated.p, st);
-    // one prediction batch over every train item (the rated ones are dropped by the ordering below)
-    run_predict(h, predictor, h->reco_users.p, h->reco_items.p, nullptr, I, nullptr, nullptr, h->reco_pred.p);
-    PrepScratch& sc = h->prep;
-    sc.k64_a.ensure(I); sc.k64_b.ensure(I); sc.v32_a.ensure(I); sc.v32_b.ensure(I);
-    launch_reco_order(tr, sc.sort, h->reco_pred.p, h->reco_rated.p, sc.k64_a.p, sc.k64_b.p, sc.v32_a.p, sc.v32_b.p, st);
-    int64_t n_rated = 0;
-    if (du >= 0) {
-        int64_t two[2];
-        KN_HIP(hipMemcpyAsync(two, tr.u_ptr.p + du, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        KN_HIP(hipStreamSynchronize(st));
-        n_rated = two[1] - two[0];
-    }
-    const int32_t m = (int32_t)std::min<int64_t>(n, (int64_t)I - n_rated);
-    if (m <= 0) return;
-    h->reco_out_items.ensure(m); h->reco_out_preds.ensure(m);
-    launch_reco_take(tr, m, sc.v32_b.p, h->reco_pred.p, h->reco_out_items.p, h->reco_out_preds.p, st);
-    KN_HIP(hipMemcpyAsync(out_items, h->reco_out_items.p, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    KN_HIP(hipMemcpyAsync(out_preds, h->reco_out_preds.p, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
-    KN_HIP(hipStreamSynchronize(st));
-    *count = m;
 }
 
 // ---- fold-in queries: users outside the fit, answered chunk by chunk (foldin.hip) ------------------------------------------
@@ -1898,20 +1869,14 @@ int knncf_neighbors_batch(knncf_handle* h, const int32_t* users, int64_t n, int3
 
 // users per chunk of knncf_recommend_batch: the rule of knncf.h ("Batched recommendations")
 static int64_t recommend_batch_chunk(knncf_handle* h) {
-    int64_t budget = h->cfg.workspace_bytes / 2;
-    if (h->cfg.workspace_bytes <= 0) {
-        size_t free_b = 0, total_b = 0;
-        KN_HIP(hipMemGetInfo(&free_b, &total_b));
-        budget = (int64_t)std::min<size_t>((size_t)48 << 30, free_b / 4);
-    }
-    int64_t C = std::min<int64_t>(RB_MAX_CHUNK, budget / reco_batch_bytes(h->tr.I));
+    int64_t C = std::min<int64_t>(RB_MAX_CHUNK, batch_budget(h) / reco_batch_bytes(h->tr.I));
     C = std::min<int64_t>(C, (int64_t)0x7fffffff / h->tr.I);  // slot * I + item is a 31-bit cell
     return std::max<int64_t>(C, 1);
 }
 
-// recommendations(train, predictor)(users[b], n) :651-674 for b = 0 .. n_users-1, "as if knncf_recommend had been called in
-// this order": the missing neighbourhoods are built in one batch (build_missing_neighbors: knncf_neighbors_batch's state),
-// then chunks of users go through reco_batch.hip
+// recommendations(train, predictor)(users[b], n) shared/predictions.scala:651-674 for b = 0 .. n_users-1, as if asked in this
+// order; knncf_recommend is the call over one user.  The missing neighbourhoods are built in one batch (build_missing_neighbors,
+// as knncf_neighbors_batch numbers them), then chunks of users go through reco_batch.hip
 static void do_recommend_batch(knncf_handle* h, int predictor, const int32_t* users, int64_t B, int32_t n, int32_t* out_items,
                                double* out_preds, int32_t* counts) {
     require_fitted(h);
@@ -1929,21 +1894,27 @@ static void do_recommend_batch(knncf_handle* h, int predictor, const int32_t* us
     const int32_t I = tr.I;
     load_host_ids(h);
     std::vector<int32_t> du((size_t)B);
-    bool any_known = false;
     for (int64_t b = 0; b < B; ++b) {
         du[b] = dense_lookup(h->h_ukeys.data(), tr.U, users[b]);
         KN_REQUIRE(du[b] < 0 ? h->cfg.shard_rank == 0 : (du[b] >= tr.own_lo && du[b] < tr.own_hi), KNNCF_E_STATE,
                    "recommend batch: a user belongs to another shard");
-        any_known = any_known || du[b] >= 0;
     }
     const bool knn = predictor == KNNCF_PRED_KNN;
-    if (knn && any_known && tr.U >= 2 && nt.kcap > 0) {
-        KN_REQUIRE(h->cfg.similarity != KNNCF_SIM_ONE, KNNCF_E_UNSUPPORTED,
-                   "kNN neighbourhoods with similarityOne: every similarity is 1.0, the neighbourhood is the first k users in Set order — not built");
-        build_missing_neighbors(h, du);
+    if (knn && tr.U >= 2 && nt.kcap > 0) {
+        // the reference evaluates weightedSumDeviation, hence getNeighbors, only for a train user whose mean is not negative
+        // (:573 answers the global average otherwise): nobody else's list is built or numbered here
+        std::vector<int32_t> wanted(du);
+        bool any = false;
+        for (int32_t& u : wanted) {
+            if (u >= 0 && train_user_avg(h, u) < 0.0) u = -1;
+            any = any || u >= 0;
+        }
+        if (any) {
+            KN_REQUIRE(h->cfg.similarity != KNNCF_SIM_ONE, KNNCF_E_UNSUPPORTED,
+                       "kNN neighbourhoods with similarityOne: every similarity is 1.0, the neighbourhood is the first k users in Set order — not built");
+            build_missing_neighbors(h, wanted);
+        }
     }
-    // the kNN fold of reco_batch.hip reads the lists as they are; longer lists (and the other predictors) take the general batch
-    const bool fold = knn && h->cfg.similarity != KNNCF_SIM_ONE && nt.kcap <= RB_MAX_K && tr.n < (int64_t)0xffffffffll;
     const bool fast_select = n <= RB_FAST_N;
     const int32_t width = (int32_t)std::min<int64_t>(n, I);  // cells of a row that can be filled
     QueryBatchScratch& bs = h->query_batch;
@@ -1964,17 +1935,13 @@ static void do_recommend_batch(knncf_handle* h, int predictor, const int32_t* us
         bs.out_items.ensure((size_t)C * width); bs.out_preds.ensure((size_t)C * width);
         KN_HIP(hipMemcpyAsync(rb.slot_user.p, du.data() + c0, (size_t)C * sizeof(int32_t), hipMemcpyHostToDevice, st));
         KN_HIP(hipMemcpyAsync(rb.slot_raw.p, users + c0, (size_t)C * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        if (fold) {
-            Stage s(h, &h->tm.predict_ms);
-            reco_batch_fold(tr, nt, rb, C, bs.pred.p, st);
-        } else {
-            rb.row_users.ensure(cells); rb.row_items.ensure(cells);
-            reco_batch_rows(tr, rb, C, rb.row_users.p, rb.row_items.p, st);
-            // (every list the rows need exists: the general batch numbers nothing, and its call epoch is given back)
-            const int64_t epoch = h->epoch;
-            run_predict(h, predictor, rb.row_users.p, rb.row_items.p, nullptr, (int64_t)cells, nullptr, nullptr, bs.pred.p);
-            if (knn) h->epoch = epoch;
-        }
+        rb.row_users.ensure(cells); rb.row_items.ensure(cells);
+        reco_batch_rows(tr, rb, C, rb.row_users.p, rb.row_items.p, st);
+        // one prediction batch over the chunk's C x I rows (every list the rows need exists: the batch numbers nothing, and its
+        // call epoch is given back)
+        const int64_t epoch = h->epoch;
+        run_predict(h, predictor, rb.row_users.p, rb.row_items.p, nullptr, (int64_t)cells, nullptr, nullptr, bs.pred.p);
+        if (knn) h->epoch = epoch;
         {
             Stage s(h, &h->tm.predict_ms);
             reco_batch_mark(tr, rb, C, n, bs.rated.p, (long long*)bs.info.p, st);
@@ -2136,7 +2103,12 @@ int knncf_explain(knncf_handle* h, int32_t user, int32_t item, int32_t order, in
 }
 
 int knncf_recommend(knncf_handle* h, int predictor, int32_t user, int32_t n, int32_t* items, double* predictions, int32_t* count) {
-    return guarded(h, [&] { do_recommend(h, predictor, user, n, items, predictions, count); });
+    return guarded(h, [&] {
+        require_fitted(h);
+        KN_REQUIRE(count && n >= 0 && (n == 0 || (items && predictions)), KNNCF_E_INVALID, "bad arguments");
+        *count = 0;
+        do_recommend_batch(h, predictor, &user, 1, n, items, predictions, count);
+    });
 }
 
 // ---- the 24 query entry points: the rows of the call by name, then the mode's builder (api.cpp "one request type") ----------
@@ -2418,6 +2390,7 @@ int knncf_shard_commit(knncf_handle* h) {
         if (h->cfg.shard_count > 1) prep_complete_rows(h->tr, h->prep, h->stream);
         prep_commit(h->tr, h->prep, h->stream);
         h->committed = true;
+        h->h_uavg.clear();  // (the exchange before the commit wrote the other shards' means)
     });
 }
 

@@ -306,16 +306,6 @@ void launch_fold_rows(const Train& tr, const PersonalRows& pr, int64_t n_rows, c
                       const int32_t* d_di, const double* d_ratings, const int32_t* d_slot, const double* d_S, double* d_pred,
                       double* d_abs_err, uint8_t* d_owned, hipStream_t st);
 
-// ---- reco.hip: recommendations :651-674 -------------------------------------------------------------------------
-// rows (user, every train item) for the prediction batch + the mask of the items the user rated
-void launch_reco_rows(const Train& tr, int32_t user_raw, int32_t du, int32_t* d_users, int32_t* d_items, uint8_t* d_rated, hipStream_t st);
-// v_b = dense items ordered by (prediction descending, raw id ascending), rated items last
-void launch_reco_order(const Train& tr, SortWorkspace& ws, const double* d_pred, const uint8_t* d_rated, uint64_t* k_a, uint64_t* k_b,
-                       uint32_t* v_a, uint32_t* v_b, hipStream_t st);
-// by_id = dense items by ascending raw id (the first of launch_reco_order's two sorts; k_a / k_b / v_a hold I entries)
-void launch_reco_id_order(const Train& tr, SortWorkspace& ws, uint64_t* k_a, uint64_t* k_b, uint32_t* v_a, uint32_t* by_id, hipStream_t st);
-void launch_reco_take(const Train& tr, int32_t m, const uint32_t* d_order, const double* d_pred, int32_t* d_items, double* d_preds, hipStream_t st);
-
 // ---- foldin.hip: kNN queries of users outside the fit (DESIGN.md "Fold-in queries") ----------------------------------
 // Chunks of independent queries, every stage one launch over the chunk; a single call is a chunk of one.  The scratch is
 // handle-owned; the fit, its neighbour table and its sequence numbers are only read.
@@ -405,11 +395,10 @@ void foldin_batch_explain(const Train& tr, QueryBatchScratch& bs, const QbExplai
 void foldin_batch_recommend(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, int32_t n, int32_t* d_items,
                             double* d_preds, hipStream_t st);
 
-// ---- reco_batch.hip: recommendations for many users of the fit (knncf_recommend_batch; DESIGN.md "Batched recommendations") ----
+// ---- reco_batch.hip: recommendations :651-674 for users of the fit (knncf_recommend, knncf_recommend_batch; DESIGN.md "Batched
+// recommendations") ----
 static constexpr int RB_TPB = 256;
-static constexpr int RB_TILE = 2048;      // items per workgroup of the fold and of the tile selection
-static constexpr int RB_CAP = 2560;       // gathered neighbour ratings a fold workgroup holds in LDS at a time (16 B each)
-static constexpr int RB_MAX_K = 2048;     // neighbour lists beyond this take the general prediction batch
+static constexpr int RB_TILE = 2048;      // items per workgroup of the tile selection
 static constexpr int RB_FAST_N = 32;      // n up to here: arg-min selection; beyond: the segmented full order of foldin.hip
 static constexpr int RB_MAX_CHUNK = 1024; // users per chunk at most
 // device bytes per user of a chunk that the chunk rule of knncf.h counts
@@ -420,12 +409,12 @@ struct RecoBatchScratch {
     DArr<uint32_t> id_rank;             // [I] place of each dense item in ascending raw-id order
     DArr<uint64_t> p_key;               // [C][tiles][n] the tiles' winners: order key, raw-id rank, dense item
     DArr<uint32_t> p_rank, p_item;
-    DArr<int32_t> row_users, row_items; // [C][I] rows of the general prediction batch (predictors other than the kNN fold)
+    DArr<int32_t> row_users, row_items; // [C][I] (user, item) rows of the prediction batch
 };
+// by_id = dense items by ascending raw id (k_a / k_b / v_a hold I entries); foldin.hip orders its chunks with it too
+void launch_reco_id_order(const Train& tr, SortWorkspace& ws, uint64_t* k_a, uint64_t* k_b, uint32_t* v_a, uint32_t* by_id, hipStream_t st);
 // rb.id_rank (bs lends its key buffers and keeps by_id)
 void reco_batch_id_rank(const Train& tr, QueryBatchScratch& bs, RecoBatchScratch& rb, SortWorkspace& ws, hipStream_t st);
-// d_pred [C][I] = the kNN predictor of every (slot, item) from nt's lists (kcap <= RB_MAX_K, every slot's list built)
-void reco_batch_fold(const Train& tr, const NeighborTable& nt, const RecoBatchScratch& rb, int32_t C, double* d_pred, hipStream_t st);
 void reco_batch_rows(const Train& tr, const RecoBatchScratch& rb, int32_t C, int32_t* d_users, int32_t* d_items, hipStream_t st);
 // d_rated [C][I], d_info [C][4] (k_qb_take's layout: [1] = rated items), rb.counts
 void reco_batch_mark(const Train& tr, const RecoBatchScratch& rb, int32_t C, int32_t n, uint8_t* d_rated, long long* d_info, hipStream_t st);

@@ -813,8 +813,9 @@ __global__ void __launch_bounds__(QBX_WAVES * 64) k_qb_explain(QbExplainArgs A, 
     }
 }
 
-// k_reco_pred_keys (reco.hip) over [C][I]: ascending key <=> descending prediction, rated items last, -0.0 == +0.0;
-// the input order inside a slot is ascending raw id (by_id), val = slot * I + dense item
+// the order key of recommendations :651-674 over [C][I]: ascending key <=> descending prediction, rated items last; -0.0 and
+// +0.0 compare equal in the reference's `x._2 == y._2`, so both map to the same key (k_rb_select_tile of reco_batch.hip
+// computes the same key).  The input order inside a slot is ascending raw id (by_id), val = slot * I + dense item
 __global__ void k_qb_reco_keys(int32_t C, int32_t I, const uint32_t* __restrict__ by_id, const double* __restrict__ pred,
                                const uint8_t* __restrict__ rated, uint64_t* __restrict__ key, uint32_t* __restrict__ val) {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -1,14 +1,11 @@
-// reco_batch.hip — recommendations :651-674 for MANY users of the fit in one pass (knncf_recommend_batch; DESIGN.md
-// "Batched recommendations").  A chunk of C users ("slots") is answered by a few launches over the chunk:
-//   k_rb_fold          kNN predictor (:489-585) of every (slot, item) from the slot's neighbour list, one workgroup per
-//                      (slot, tile of RB_TILE items): the neighbours' rows are item-ascending, so the tile's part of each is
-//                      found by one binary search; the entries are counted per item in LDS, prefixed, scattered into
-//                      per-item LDS lists and folded per item in training-file order (fp64, left to right, no FMA) —
-//                      bit for bit the fold of predict.hip
-//   k_rb_rows          the other predictors: the chunk's C x I (user, item) rows for the general prediction batch
+// reco_batch.hip — recommendations shared/predictions.scala:651-674 for users of the fit (knncf_recommend_batch, and
+// knncf_recommend as the call over one user; DESIGN.md "Batched recommendations"): every train item a user has not rated,
+// ordered by (prediction descending, raw item id ascending), first n.  A chunk of C users ("slots") is answered by a few
+// launches over the chunk:
+//   k_rb_rows          the chunk's C x I (user, item) rows for the prediction batch of predict.hip, whatever the predictor
 //   k_rb_mark / k_rb_info   the items each slot has rated; the slots' counts min(n, I - #rated)
-//   k_rb_select_tile / k_rb_merge   n <= RB_FAST_N: the n best of every tile by repeated workgroup arg-min on the
-//                      (order key, raw-id rank) pair, then the n best of a slot's tile winners.  Nothing is sorted.
+//   k_rb_select_tile / k_rb_merge   n <= RB_FAST_N: the n best of every tile of RB_TILE items by repeated workgroup arg-min on
+//                      the (order key, raw-id rank) pair, then the n best of a slot's tile winners.  Nothing is sorted.
 //   larger n           the segmented full order of foldin.hip (foldin_batch_recommend)
 #include <math.h>
 
@@ -19,143 +16,6 @@
 namespace knncf {
 
 static constexpr int TPB = RB_TPB;
-static_assert(RB_MAX_K <= RB_CAP, "one item's list (at most one entry per neighbour) must fit the LDS entry store");
-static_assert(RB_TILE % TPB == 0 && RB_TILE / TPB == 8, "k_rb_fold: 8 consecutive items per thread in the prefix");
-static_assert(RB_TILE <= 65535, "seg_len is 16 bits");
-
-// first position p in [b, e) with col[p] >= x (the row is item-ascending)
-__device__ __forceinline__ int64_t rb_lower_bound(const int32_t* __restrict__ col, int64_t b, int64_t e, int32_t x) {
-    while (b < e) {
-        const int64_t mid = (b + e) >> 1;
-        if (col[mid] < x) b = mid + 1;
-        else e = mid;
-    }
-    return b;
-}
-
-// grid (tiles, C).  slot_user[s] = dense user of slot s, -1 for a raw id absent from train (every prediction is the
-// global average :571-574, as for a user whose mean is negative).  LDS: 4 (RB_TILE + 1) + 6 RB_MAX_K + 16 RB_CAP + 16 B =
-// 61 468 B, so two workgroups share a CU's 160 KB.
-__global__ void __launch_bounds__(TPB) k_rb_fold(int32_t I, int32_t kcap, const int32_t* __restrict__ slot_user,
-                                                 const int64_t* __restrict__ u_ptr, const int32_t* __restrict__ s_col,
-                                                 const uint32_t* __restrict__ s_t, const double* __restrict__ s_dev,
-                                                 const double* __restrict__ user_avg, double global_avg,
-                                                 const int32_t* __restrict__ nbr_idx, const double* __restrict__ nbr_sim,
-                                                 const int32_t* __restrict__ nbr_cnt, double* __restrict__ pred) {
-    __shared__ uint32_t off[RB_TILE + 1];          // per item: entries (count), then first entry (prefix), then cursor (scatter)
-    __shared__ uint32_t seg_b[RB_MAX_K];           // per neighbour: first position of its row inside the tile
-    __shared__ uint16_t seg_len[RB_MAX_K];         //                and the number of its entries there
-    __shared__ unsigned long long e_key[RB_CAP];   // (train file row << 32) | neighbour slot
-    __shared__ double e_dev[RB_CAP];
-    __shared__ uint32_t wave_tot[TPB / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int32_t slot = blockIdx.y;
-    const int32_t i0 = (int32_t)blockIdx.x * RB_TILE;
-    const int32_t T = min(RB_TILE, I - i0);
-    if (T <= 0) return;
-    const int32_t i1 = i0 + T;
-    const int32_t u = slot_user[slot];
-    const double ua = (u >= 0) ? user_avg[u] : -1.0;  // usersAvgValue.getOrElse(u, -1.0) :572
-    const bool flat = ua < 0.0;
-    const int32_t cnt = (flat || kcap <= 0) ? 0 : min(min(nbr_cnt[u], kcap), RB_MAX_K);
-    const int64_t nb = (u >= 0) ? (int64_t)u * kcap : 0;
-    double* out = pred + (int64_t)slot * I;
-
-    for (int32_t c = tid; c <= RB_TILE; c += TPB) off[c] = 0;
-    __syncthreads();
-    // the tile's part of every neighbour's row, counted per item
-    for (int32_t j = tid; j < cnt; j += TPB) {
-        const int32_t v = nbr_idx[nb + j];
-        const int64_t b = u_ptr[v], e = u_ptr[v + 1];
-        const int64_t pb = rb_lower_bound(s_col, b, e, i0);
-        int64_t p = pb;
-        for (; p < e; ++p) {
-            const int32_t c = s_col[p];
-            if (c >= i1) break;
-            atomicAdd(&off[c - i0], 1u);
-        }
-        seg_b[j] = (uint32_t)pb;
-        seg_len[j] = (uint16_t)(p - pb);
-    }
-    __syncthreads();
-    // exclusive prefix over the items: 8 consecutive items per thread, DPP scan inside the wave, the waves' totals through LDS
-    {
-        uint32_t mine[8], sum = 0;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            mine[q] = off[tid * 8 + q];
-            sum += mine[q];
-        }
-        const uint32_t incl = wave_incl_scan(sum);
-        if (lane == 63) wave_tot[wave] = incl;
-        __syncthreads();
-        uint32_t run = incl - sum;
-        for (int w = 0; w < wave; ++w) run += wave_tot[w];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            off[tid * 8 + q] = run;
-            run += mine[q];
-        }
-        if (tid == TPB - 1) off[RB_TILE] = run;
-    }
-    __syncthreads();
-    // item ranges [a, b) whose lists fit the entry store together (one range when the tile holds <= RB_CAP entries: the usual case)
-    int32_t a = 0;
-    while (a < T) {
-        const uint32_t base = off[a];  // (cells from a on still hold their prefix: only cells below a have been cursors)
-        int32_t lo = a + 1, hi = T;
-        while (lo < hi) {              // largest b in (a, T] with off[b] - base <= RB_CAP; one item's list always fits
-            const int32_t mid = (lo + hi + 1) >> 1;
-            if (off[mid] - base <= (uint32_t)RB_CAP) lo = mid;
-            else hi = mid - 1;
-        }
-        const int32_t b = lo;
-        const uint32_t next_base = off[b];
-        __syncthreads();
-        if (next_base != base) {
-            for (int32_t j = tid; j < cnt; j += TPB) {
-                const int64_t pb = seg_b[j];
-                const int32_t len = seg_len[j];
-                for (int32_t x = 0; x < len; ++x) {
-                    const int32_t c = s_col[pb + x] - i0;
-                    if (c >= b) break;
-                    if (c < a) continue;
-                    const uint32_t pos = atomicAdd(&off[c], 1u) - base;
-                    if (pos < (uint32_t)RB_CAP) {  // (always: the range was sized for it)
-                        e_key[pos] = ((unsigned long long)s_t[pb + x] << 32) | (unsigned long long)(uint32_t)j;
-                        e_dev[pos] = s_dev[pb + x];
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        // weightedSumDeviation :517-545 per item: the list in ascending key = training-file order, smallest remaining key first
-        for (int32_t c = a + tid; c < b; c += TPB) {
-            const uint32_t start = ((c == a) ? base : off[c - 1]) - base, end = min(off[c] - base, (uint32_t)RB_CAP);
-            double num = 0.0, den = 0.0;
-            unsigned long long prev = 0;
-            for (uint32_t r = start; r < end; ++r) {
-                unsigned long long best = ~0ull;
-                uint32_t bx = start;
-                for (uint32_t x = start; x < end; ++x) {
-                    const unsigned long long k = e_key[x];
-                    if ((r == start || k > prev) && k < best) {
-                        best = k;
-                        bx = x;
-                    }
-                }
-                const double s = nbr_sim[nb + (uint32_t)best];
-                num = num + e_dev[bx] * s;
-                den = den + fabs(s);
-                prev = best;
-            }
-            const double w = (den > 0) ? num / den : 0.0;
-            out[i0 + c] = flat ? global_avg : combine(ua, w);
-        }
-        __syncthreads();
-        a = b;
-    }
-}
 
 // the chunk's prediction rows for the general batch: row s * I + i = (raw user of slot s, raw id of dense item i)
 __global__ void k_rb_rows(int32_t C, int32_t I, const int32_t* __restrict__ slot_raw, const int32_t* __restrict__ iid,
@@ -192,6 +52,13 @@ __global__ void k_rb_info(int32_t C, int32_t I, int32_t n, const int32_t* __rest
     counts[s] = left <= 0 ? 0 : (left < (int64_t)n ? (int32_t)left : n);
 }
 
+__global__ void k_reco_id_keys(int32_t I, const int32_t* __restrict__ iid, uint64_t* __restrict__ key, uint32_t* __restrict__ val) {
+    const int32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= I) return;
+    key[j] = (uint64_t)(uint32_t)(iid[j] ^ 0x80000000);  // signed ids in ascending order
+    val[j] = (uint32_t)j;
+}
+
 // id_rank[dense item] = its place in ascending raw-id order (the inverse of launch_reco_id_order's list)
 __global__ void k_rb_inverse(int32_t I, const uint32_t* __restrict__ by_id, uint32_t* __restrict__ id_rank) {
     const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -199,7 +66,7 @@ __global__ void k_rb_inverse(int32_t I, const uint32_t* __restrict__ by_id, uint
 }
 
 // Workgroup arg-min over m candidates (key, rank), smallest key first and the smaller rank among equal keys — the reference's
-// (prediction descending, raw id ascending) on k_reco_pred_keys' key.  Returns the candidate's index, the same in every
+// (prediction descending, raw id ascending) on k_qb_reco_keys' key (foldin.hip).  Returns the candidate's index, the same in every
 // thread, or 0xffffffff when only spent candidates (key ~0, rank 0xffffffff) are left.  Ends on a barrier.
 __device__ uint32_t rb_argmin(const unsigned long long* key, const uint32_t* rank, int32_t m, unsigned long long* w_key,
                               uint32_t* w_rank, uint32_t* w_idx) {
@@ -319,21 +186,18 @@ __global__ void __launch_bounds__(TPB) k_rb_merge(int32_t I, int32_t n, int32_t 
     }
 }
 
+void launch_reco_id_order(const Train& tr, SortWorkspace& ws, uint64_t* k_a, uint64_t* k_b, uint32_t* v_a, uint32_t* by_id, hipStream_t st) {
+    k_reco_id_keys<<<(unsigned)ceil_div(tr.I, TPB), TPB, 0, st>>>(tr.I, tr.iid.p, k_a, v_a);
+    sort_pairs_u64_u32(ws, k_a, k_b, v_a, by_id, tr.I, 32, st);
+    KN_HIP(hipGetLastError());
+}
+
 void reco_batch_id_rank(const Train& tr, QueryBatchScratch& bs, RecoBatchScratch& rb, SortWorkspace& ws, hipStream_t st) {
     const int32_t I = tr.I;
     bs.k64_a.ensure(I); bs.k64_b.ensure(I); bs.v32_a.ensure(I); bs.by_id.ensure(I);
     rb.id_rank.ensure(I);
     launch_reco_id_order(tr, ws, bs.k64_a.p, bs.k64_b.p, bs.v32_a.p, bs.by_id.p, st);
     k_rb_inverse<<<(unsigned)ceil_div(I, TPB), TPB, 0, st>>>(I, bs.by_id.p, rb.id_rank.p);
-    KN_HIP(hipGetLastError());
-}
-
-void reco_batch_fold(const Train& tr, const NeighborTable& nt, const RecoBatchScratch& rb, int32_t C, double* d_pred,
-                     hipStream_t st) {
-    KN_REQUIRE(nt.kcap <= RB_MAX_K && C >= 1 && C <= RB_MAX_CHUNK, KNNCF_E_INVALID, "recommend batch: fold out of range");
-    const dim3 grid((unsigned)ceil_div(tr.I, RB_TILE), (unsigned)C);
-    k_rb_fold<<<grid, TPB, 0, st>>>(tr.I, nt.kcap, rb.slot_user.p, tr.u_ptr.p, tr.s_col.p, tr.s_t.p, tr.s_dev.p, tr.user_avg.p,
-                                    tr.global_avg, nt.idx.p, nt.sim.p, nt.cnt.p, d_pred);
     KN_HIP(hipGetLastError());
 }
 

@@ -414,7 +414,8 @@ class Engine:
         self._check(self._lib.knncf_neighbors_load(self._h, os.fsencode(path)))
 
     def recommend(self, predictor, user, n):
-        """recommendations(train, predictor)(user, n) shared/predictions.scala:651-674: (item ids, predictions)"""
+        """recommendations(train, predictor)(user, n) shared/predictions.scala:651-674: (item ids, predictions).  The
+        batched call over one user (knncf_recommend)"""
         ids = np.empty(max(1, n), dtype=np.int32)
         preds = np.empty(max(1, n), dtype=np.float64)
         c = C.c_int32()
@@ -425,7 +426,7 @@ class Engine:
     def recommend_batch(self, predictor, users, n):
         """recommend(predictor, users[b], n) for every b, as if called in this order (knncf_recommend_batch): (items [B, n]
         int32, preds [B, n] float64, counts [B] int32); cells past a row's count are -1 / nan.  Missing neighbourhoods are
-        built in one batch; the handle is left as neighbors_batch(users) leaves it."""
+        built in one batch; PRED_KNN leaves the handle as neighbors_batch over the users whose mean is not negative leaves it."""
         u = np.asarray(users)
         if u.ndim != 1:
             raise ValueError("users must be a 1-D array of ids")

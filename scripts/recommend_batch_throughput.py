@@ -1,10 +1,10 @@
 """Throughput of Engine.recommend_batch (knncf_recommend_batch, csrc/reco_batch.hip) at the ml-25m shape next to the host loop
-of single Engine.recommend calls: syn-25m, k = 300, n = 3, KNNCF_PRED_KNN.
+of single Engine.recommend calls (the same call over one user): syn-25m, k = 300, n = 3, KNNCF_PRED_KNN.
 
 Every leg runs in a child process that fits once and builds the neighbour table of ALL users first (neighbors_batch), so the
 legs time recommendation, not the fit.  Legs: the single-call loop over 256 users — with `--parent-tree DIR` also on a
 checkout of the parent commit built in DIR (`single_loop_parent`; it uses only entry points that exist there) — and
-recommend_batch issued 1, 64, 1024, 16 384 and all users at a time.  Each figure is the median over `--repeats` passes with
+recommend_batch issued 1, 2, 4, ... 512, 1024, 16 384 and all users at a time.  Each figure is the median over `--repeats` passes with
 min and standard deviation beside it.  Then one batch of 1024 users is repeated under `rocprofv3 --kernel-trace --stats` in
 two child processes of their own — set-up alone, and set-up plus the batch — and the per-user device time of each kernel is
 their difference over 1024.  Prints one JSON line.
@@ -24,9 +24,10 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = "movie-recommender-system_amd"
 LOOP_USERS = 256
-BATCHES = ((1, 256), (64, 1024), (1024, 4096), (16384, 16384), (0, 0))  # (users per call, users per pass); 0 = all
+# (users per call, users per pass); 0 = all
+BATCHES = ((1, 256), (2, 256), (4, 256), (8, 256), (16, 256), (32, 256), (64, 1024), (128, 1024), (256, 1024), (512, 2048),
+           (1024, 4096), (16384, 16384), (0, 0))
 PROFILE_BATCH = 1024
-HBM_BYTES_PER_S = 8e12
 
 
 def _summary(seconds, n_users):
@@ -48,7 +49,7 @@ def inner(args):
     e = kn.Engine(k=300)
     e.fit(d.train.users, d.train.items, d.train.ratings)
     known = np.unique(d.train.users).astype(np.int32)
-    ids, _, cnt = e.neighbors_batch(known)
+    e.neighbors_batch(known)
     U, I = e.num_users, e.num_items
     res = {"U": U, "I": I, "train_ratings": len(d.train.users), "k": 300, "n": 3}
     stride = lambda m: known[::max(1, len(known) // m)][:m].copy()
@@ -56,14 +57,9 @@ def inner(args):
         if args.profile_batch > 0:
             users = stride(args.profile_batch)
             e.recommend_batch(kn.PRED_KNN, users, 3)
-            # the ratings a user's neighbours hold: what the fold gathers
-            rows = np.bincount(d.train.users, minlength=int(known.max()) + 1)
-            pos = np.searchsorted(known, users)
-            res["gathered_entries_per_user"] = float(rows[ids[pos]].sum(axis=1).mean())
         e.close()
         print(json.dumps(res), flush=True)
         return
-    del ids, cnt
     users = stride(LOOP_USERS)
     for u in users[:16]:
         e.recommend(kn.PRED_KNN, int(u), 3)
@@ -133,11 +129,10 @@ def main():
         prof = {}
         for tag, batch in (("setup", 0), ("calls", PROFILE_BATCH)):
             d = os.path.join(args.out, "prof_" + tag)
-            out = _child(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "rb", "--"] + me +
-                         ["--profile-batch", str(batch)], 600, os.path.join(args.out, f"prof_{tag}.log"))
+            _child(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "rb", "--"] + me +
+                   ["--profile-batch", str(batch)], 600, os.path.join(args.out, f"prof_{tag}.log"))
             found = [os.path.join(r, f) for r, _, fs in os.walk(d) for f in fs if f.endswith("kernel_stats.csv")]
             prof[tag] = _stats(found[0])
-            res.update({k: v for k, v in out.items() if k == "gathered_entries_per_user"})
         per_kernel = {}
         for name, (calls, ns) in prof["calls"].items():
             c0, ns0 = prof["setup"].get(name, (0, 0.0))
@@ -146,12 +141,6 @@ def main():
         res["profile_batch"] = PROFILE_BATCH
         res["device_us_per_user"] = sum(v["us_per_user"] for v in per_kernel.values())
         res["kernels"] = per_kernel
-        # algorithmic bytes per user: every gathered neighbour rating is read as (item twice, file row, deviation) = 20 B;
-        # every item's prediction is written and read once (16 B), with its rated flag (2 B) and raw-id rank (4 B)
-        if "gathered_entries_per_user" in res:
-            b = 20.0 * res["gathered_entries_per_user"] + 22.0 * res["I"]
-            res["algorithmic_bytes_per_user"] = b
-            res["fraction_of_hbm_8TBps"] = b / (res["device_us_per_user"] * 1e-6) / HBM_BYTES_PER_S
     with open(os.path.join(args.out, "recommend_batch_throughput.json"), "w") as f:
         json.dump(res, f, indent=1)
     print(json.dumps(res))

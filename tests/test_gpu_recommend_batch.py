@@ -1,9 +1,11 @@
 """knncf_recommend_batch (csrc/reco_batch.hip): recommendations for many users of the fit in one call.  Everything is compared
 with == on the int32 ids and on the fp64 bit patterns: against the oracle's recommend(user, n) on fresh closures evaluated in
-the batch's order, and against a loop of knncf_recommend on a twin handle.
+the batch's order, and against a loop of knncf_recommend on a twin handle.  The single call IS the batch over one user, so the
+loop twins pin only what differs between the two shapes of call — chunking, the order and numbering of the builds, the output
+layout — and the values are pinned by the oracle comparisons alone.
 
-Handle state.  include/knncf.h pins the state after the call to knncf_neighbors_batch over the same users, and that is compared
-through knncf_neighbors_save: header (with the call epoch), list lengths, build numbers and every built list, byte for byte.
+Handle state.  include/knncf.h pins the state after the call to knncf_neighbors_batch over the users of the call whose mean is
+not negative, and that is compared through knncf_neighbors_save: header (with the call epoch), list lengths, build numbers and every built list, byte for byte.
 (Lists that were never built are not compared: their cells are whatever the allocation held.)  A LOOP of single calls numbers
 its builds (call, 0), one call each, where the batch numbers them (call, position): the same order under different numbers.
 So against the loop twin the lengths and the built lists are compared byte for byte, the build numbers by the ORDER they put the
@@ -14,6 +16,7 @@ import importlib
 import numpy as np
 import pytest
 
+from tests import rating_scales as rs
 from tests.test_oracle_semantics import _cols, _no_zero_scale, _random_case
 
 pytestmark = pytest.mark.gpu
@@ -194,6 +197,60 @@ def test_order_of_the_batch_is_the_order_of_the_calls(kn, oracle, tmp_path):
             b.close()
 
 
+def _oracle_rows(p, users, n):
+    """the pipeline's recommend(u, n) for every user in order: [(item ids, prediction bits)]"""
+    out = []
+    for u in users:
+        ids, preds = p.recommend(int(u), n)
+        out.append((ids.tolist(), preds.view(np.int64).tolist()))
+    return out
+
+
+def _rows(got):
+    return [(got[0][b, :got[2][b]].tolist(), got[1][b, :got[2][b]].view(np.int64).tolist()) for b in range(len(got[2]))]
+
+
+def test_history_is_the_reference_s(kn, oracle):
+    """rating_scales.history_case, cosine, k = 5: user 17's mean is negative, so recommend(17, 3) is answered at :573 and builds
+    no neighbourhood (test_rating_scale_premises: building it changes the bits of other lists).  One chunk, chunks of 7 with a
+    remainder, and a loop of single calls all leave the lists the oracle's pipeline holds after the same calls"""
+    train, _ = rs.history_case()
+    tr = rs.cols(train)
+    fitted = np.unique(tr[0]).astype(np.int32)
+    users = np.asarray(([17] + fitted.tolist()) * 2, dtype=np.int32)  # (repeats of listed users change no history)
+    n_items = len(np.unique(tr[1]))
+    p = oracle.Model(*tr).pipeline(oracle.SIM_COSINE, 5)
+    rows = _oracle_rows(p, users, 3)
+    after = [(i.tolist(), s.view(np.int64).tolist()) for i, s in (p.neighbors(int(u)) for u in fitted)]
+    batch = lambda e: e.recommend_batch(kn.PRED_KNN, users, 3)
+    for name, workspace, ask in (("one chunk", 0, batch), ("chunks of 7", _workspace_for(7, n_items), batch),
+                                 ("loop", 0, lambda e: _loop(e, kn.PRED_KNN, users, 3))):
+        e = kn.Engine(k=5, workspace_bytes=workspace).fit(*tr)
+        assert _rows(ask(e)) == rows, name
+        ids, sims, cnt = e.neighbors_batch(fitted)
+        assert [(ids[j, :cnt[j]].tolist(), sims[j, :cnt[j]].view(np.int64).tolist()) for j in range(len(fitted))] == after, name
+        e.close()
+
+
+def test_small_and_large_batches_on_the_order_dependent_case(kn, oracle):
+    """B = 1 (the single call's shape), 2 and beyond the number of users, on the tiny case with <= 4-rating users: the batch is the
+    loop of single calls and the oracle, for both selections"""
+    train = _tiny_case(_first_tiny_seed())
+    tr = _cols(train)
+    known = np.unique(np.asarray(tr[0], dtype=np.int32))
+    pool = np.concatenate([known[::-1], [31_337], np.random.default_rng(9).permutation(known)]).astype(np.int32)
+    m = oracle.Model(*tr)
+    for B in (1, 2, len(known), len(pool)):
+        users = pool[:B]
+        for n in (3, FAST_N + 5):
+            a, b = kn.Engine(k=5).fit(*tr), kn.Engine(k=5).fit(*tr)
+            got = a.recommend_batch(kn.PRED_KNN, users, n)
+            _same(got, _loop(b, kn.PRED_KNN, users, n), (B, n))
+            assert _rows(got) == _oracle_rows(m.pipeline(oracle.SIM_COSINE, 5), users, n), (B, n)
+            a.close()
+            b.close()
+
+
 # ---- 4. chunk independence ------------------------------------------------------------------------------------------------------
 def _workspace_for(chunk, n_items):
     """workspace_bytes that makes the chunk rule of include/knncf.h give `chunk`"""
@@ -206,7 +263,7 @@ def test_results_do_not_depend_on_the_chunk(kn, syn100k):
     n_items = len(np.unique(train[1]))
     users = _mixed_users(train, 45, seed=5)
     answers = []
-    for chunk in (1, 7, None):
+    for chunk in (1, 7, 44, None):  # 45 users; 44: a remainder of one
         e = kn.Engine(k=30, workspace_bytes=0 if chunk is None else _workspace_for(chunk, n_items))
         e.fit(*train)
         answers.append([e.recommend_batch(kn.PRED_KNN, users, n) for n in (3, FAST_N + 5)] +
@@ -248,18 +305,18 @@ def test_selection_switch_and_edges(kn, syn100k):
 
 
 # ---- 6. shard handles ------------------------------------------------------------------------------------------------------------
-def test_shard_handles_answer_their_own_users(kn, pkg):
+def _shard_case(rows):
+    c = _cols(rows)
+    return tuple(np.ascontiguousarray(a) for a in (np.asarray(c[0], np.int32), np.asarray(c[1], np.int32), np.asarray(c[2], np.float64)))
+
+
+def _committed_shards(kn, pkg, trc, world, k):
+    """`world` shard handles of device 0 fitted on trc, the means and norms exchanged, committed: (engines, device tensors)"""
     import torch
 
     sharded = importlib.import_module(pkg.__name__ + ".sharded")
-    rng = np.random.default_rng(77)
-    rows = _random_case(rng, n_users=40, n_items=30, n_ratings=800, half=True, tiny_rows=0)
-    trc = tuple(np.ascontiguousarray(a) for a in (np.asarray(_cols(rows)[0], np.int32), np.asarray(_cols(rows)[1], np.int32),
-                                                   np.asarray(_cols(rows)[2], np.float64)))
-    assert min(np.bincount(np.unique(trc[0], return_inverse=True)[1])) > 4
     dev = torch.device("cuda", 0)
     tr = tuple(torch.from_numpy(a).to(dev) for a in trc)
-    world, k, n = 3, 6, 4
     engines = [kn.Engine(k=k, shard_rank=rk, shard_count=world) for rk in range(world)]
     views = []
     for e in engines:
@@ -274,6 +331,16 @@ def test_shard_handles_answer_their_own_users(kn, pkg):
     torch.cuda.synchronize()
     for e in engines:
         e.shard_commit()
+    return engines, tr
+
+
+def test_shard_handles_answer_their_own_users(kn, pkg):
+    rng = np.random.default_rng(77)
+    trc = _shard_case(_random_case(rng, n_users=40, n_items=30, n_ratings=800, half=True, tiny_rows=0))
+    assert min(np.bincount(np.unique(trc[0], return_inverse=True)[1])) > 4
+    world, k, n = 3, 6, 4
+    engines, tr = _committed_shards(kn, pkg, trc, world, k)
+    for e in engines:
         e.mae_device(kn.PRED_KNN, *tr)  # the replicated call numbers every user on every shard
     single = kn.Engine(k=k)
     single.fit(*trc)
@@ -308,6 +375,52 @@ def test_shard_handles_answer_their_own_users(kn, pkg):
                                           p(counts, C.c_int32))
         assert st == kn.E_STATE
         assert (items == -7).all() and (preds == -7.0).all() and (counts == -7).all()
+    for e in engines + [single]:
+        e.close()
+
+
+def test_single_call_on_a_shard_takes_the_batch_s_numbering_rule(kn, pkg):
+    """a train set with <= 4-rating users on two shard handles: a recommendation that would have to build (and number, on this
+    shard only) a neighbourhood is refused, by the single call as by the batch; after the replicated mae has numbered every user
+    on every shard, the single call answers what a single handle answers"""
+    rng = np.random.default_rng(78)
+    trc = _shard_case(_random_case(rng, n_users=20, n_items=19, n_ratings=200, half=True, tiny_rows=4))
+    assert min(np.bincount(np.unique(trc[0], return_inverse=True)[1])) <= 4
+    world, k, n = 2, 5, 3
+    engines, tr = _committed_shards(kn, pkg, trc, world, k)
+    known = np.unique(trc[0]).astype(np.int32)
+    p = lambda arr, t: arr.ctypes.data_as(C.POINTER(t))
+
+    def owner_of(u):  # GLOBAL_AVG builds nothing: E_STATE off the owning shard
+        mine = []
+        for rk, e in enumerate(engines):
+            try:
+                e.recommend(kn.PRED_GLOBAL_AVG, int(u), 1)
+                mine.append(rk)
+            except kn.KnncfError as ex:
+                assert ex.status == kn.E_STATE
+        assert len(mine) == 1
+        return mine[0]
+
+    owner = [owner_of(u) for u in known]
+    assert set(owner) == {0, 1}
+    for rk, e in enumerate(engines):
+        u = int(known[owner.index(rk)])
+        items, preds, count = np.full(n, -7, dtype=np.int32), np.full(n, -7.0), C.c_int32(-7)
+        st = e._lib.knncf_recommend(e._h, kn.PRED_KNN, u, n, p(items, C.c_int32), p(preds, C.c_double), C.byref(count))
+        assert st == kn.E_UNSUPPORTED
+        assert count.value == 0 and (items == -7).all() and (preds == -7.0).all()
+        with pytest.raises(kn.KnncfError) as ex:
+            e.recommend_batch(kn.PRED_KNN, [u], n)
+        assert ex.value.status == kn.E_UNSUPPORTED
+    for e in engines:
+        e.mae_device(kn.PRED_KNN, *tr)
+    single = kn.Engine(k=k).fit(*trc)
+    single.mae(kn.PRED_KNN, *trc)
+    for u, rk in zip(known, owner):
+        gi, gp = engines[rk].recommend(kn.PRED_KNN, int(u), n)
+        wi, wp = single.recommend(kn.PRED_KNN, int(u), n)
+        assert gi.tolist() == wi.tolist() and _bits(gp) == _bits(wp), int(u)
     for e in engines + [single]:
         e.close()
 

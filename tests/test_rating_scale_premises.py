@@ -158,6 +158,28 @@ def test_history_case_tells_the_two_build_histories_apart(oracle):
     assert differing >= 2
 
 
+def test_history_case_tells_a_recommendation_from_a_neighbour_query(oracle):
+    """recommend(u, n) for a negative-mean user is answered at :573 and builds no neighbourhood; neighbors(u) builds one, and
+    the lists queried afterwards then differ in their bits.  tests/test_gpu_recommend_batch.py's history test relies on user
+    17 showing this at k = 5"""
+    train, _ = rs.history_case()
+    tr = rs.cols(train)
+    m = oracle.Model(*tr)
+    users = np.unique(tr[0]).tolist()
+    assert len(users) == 18 and len(np.unique(tr[1])) == 15
+    assert [u for u in users if m.users_avg(u) < 0.0] == [10, 17, 24]
+
+    def lists(first):
+        p = m.pipeline(oracle.SIM_COSINE, 5)
+        first(p)
+        return [(ids.tolist(), sims.view(np.int64).tolist()) for ids, sims in (p.neighbors(u) for u in users)]
+
+    untouched = lists(lambda p: None)
+    assert lists(lambda p: p.recommend(17, 3)) == untouched
+    built = lists(lambda p: p.neighbors(17))
+    assert sum(a != b for a, b in zip(built, untouched)) >= 1
+
+
 # ---- wide100k ---------------------------------------------------------------------------------------------------------------
 def test_wide100k_is_off_the_scale_where_it_claims(oracle):
     tr, te = rs.wide100k()
