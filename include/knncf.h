@@ -241,9 +241,10 @@ int knncf_recommend_batch(knncf_handle* h, int predictor, const int32_t* users, 
  * numbers, the same knncf_neighbors_save file.  knncf_explain is the batch of one row.  knncf_get_timings: builds are charged
  * as usual, the explain kernel as predict_ms.
  * Status: KNNCF_E_STATE before a fit; KNNCF_E_UNSUPPORTED for a KNNCF_SIM_ONE handle (as knncf_predict) and for a shard
- * handle (shard_count > 1): SHARDED EXPLANATIONS ARE OUT OF SCOPE, as are explanations of KNNCF_PRED_PERSONALIZED (the
- * explanations of fold-in / update / revise queries are the knncf_*_explain* calls below, "Explanations of query
- * predictions"); KNNCF_E_INVALID for a null pointer that is needed, n < 0, cap < 0, an unknown order or
+ * handle (shard_count > 1): SHARDED EXPLANATIONS ARE OUT OF SCOPE, as are explanations of KNNCF_PRED_PERSONALIZED by these
+ * calls: knncf_explain* has no predictor argument and explains KNNCF_PRED_KNN only; the Personalized predictions of fitted users
+ * have knncf_explain_personalized* ("Explanations of Personalized predictions" below), and the explanations of fold-in /
+ * update / revise queries are the knncf_*_explain* calls below ("Explanations of query predictions"); KNNCF_E_INVALID for a null pointer that is needed, n < 0, cap < 0, an unknown order or
  * n >= 2^32 - 1.  n == 0 is KNNCF_OK and touches nothing.  A call that fails these checks builds nothing and writes nothing.
  * Chunks.  The device form is one pass into the caller's buffers (every pointer on the handle's device, inputs complete at
  * the call, outputs complete on return).  The host form answers consecutive row ranges [0, C), [C, 2 C), ... through
@@ -260,6 +261,58 @@ int knncf_explain_batch(knncf_handle* h, const int32_t* users, const int32_t* it
 int knncf_explain_batch_device(knncf_handle* h, const int32_t* d_users, const int32_t* d_items, int64_t n, int32_t order,
                                int32_t cap, int32_t* d_raters, double* d_sims, double* d_devs, int32_t* d_counts,
                                double* d_sums, double* d_predictions);
+
+/* ---- Explanations of Personalized predictions: the terms behind KNNCF_PRED_PERSONALIZED for users as the fit holds them ------
+ * KNNCF_PRED_PERSONALIZED, predictor(train, weightedSumDeviation(train, sim)) predict/Personalized.scala:61-72, has no
+ * neighbourhood cut: its prediction folds EVERY rating of the item, 10^4 .. 10^5 terms for a popular one.  These calls answer
+ * "which few users carried this prediction".  order (KNNCF_EXPLAIN_SUM_ORDER / KNNCF_EXPLAIN_BY_WEIGHT), cap and the outputs
+ * are those of knncf_explain_batch: counts[j] = the number of terms of row j (it may exceed cap); the first min(counts[j], cap)
+ * terms, in `order`, in row j of raters / sims / devs ([n * cap], row stride cap; cells beyond them are left untouched);
+ * sums and predictions may be null; with cap == 0 the three term arrays may be null.  knncf_explain_personalized is the batch
+ * of one row.
+ * Terms of row j = (u, i) = (users[j], items[j]).  The elements of simVal shared/predictions.scala:513-517, built with S = the
+ * handle's similarity itself (adjustedCosineSimilarityFunction(train) or jaccardCoefficient(train)), whose similarity is not
+ * exactly 0.0: (the rater's raw id, S(u, rater), the rater's normalized deviation on i), over all ratings of i in train, in file
+ * order.  Unlike the kNN explanations THE USER IS ITS OWN TERM when (u, i) is a training pair: weight S(u, u), at its file
+ * place.  KNNCF_EXPLAIN_BY_WEIGHT is |similarity| descending, equal magnitudes in summation order.
+ * Properties.  sums[2 j], sums[2 j + 1] = num and den of the fold :520-524 over ALL terms in summation order (independent of
+ * order and cap).  With counts[j] <= cap and KNNCF_EXPLAIN_SUM_ORDER the caller's left fold of the returned terms,
+ * (num + dev * sim, den + |sim|) from (0.0, 0.0) with the multiply and the add separate (no fused multiply-add), gives sums bit
+ * for bit: the raters that are no terms add +-0.0 to sums that start at +0.0.  predictions[j] equals
+ * knncf_predict(h, KNNCF_PRED_PERSONALIZED, users[j], items[j]) bit for bit, at every number of users; the combine :578 of
+ * knncf_user_avg with (den > 0 ? num / den : 0.0) gives predictions[j].  KNNCF_EXPLAIN_BY_WEIGHT returns the first
+ * min(count, cap) elements of its total order, a permutation of the KNNCF_EXPLAIN_SUM_ORDER terms when count <= cap; among
+ * equal magnitudes that the cap cuts through, the earliest in summation order are kept.  It selects the cap heaviest terms
+ * without ordering the item's raters and ranks only those, so its cost grows with the raters and with min(count, cap)^2 / 256,
+ * not with the square of the raters; cap >= count ranks every term, which is the caller's choice.
+ * Row kinds.  A user unknown to train, or one whose mean is negative (:573): count 0, sums (0, 0), prediction = the global
+ * average.  A known user on an item unknown to train, or on an item whose raters all have similarity 0.0: count 0, sums
+ * (0, 0), prediction = the user's mean.
+ * Status: KNNCF_E_STATE before a fit; KNNCF_E_UNSUPPORTED exactly where the fitted KNNCF_PRED_PERSONALIZED refuses — a shard
+ * handle (SHARDED EXPLANATIONS ARE OUT OF SCOPE), or the adjusted cosine with a train user of 4 or fewer ratings — and on a
+ * KNNCF_SIM_ONE handle: every weight is 1.0 there and every rater is a term, so there is nothing to explain;
+ * KNNCF_E_INVALID for a null pointer that is needed, n < 0, cap < 0, an unknown order or n >= 2^32 - 1.  n == 0 is KNNCF_OK and
+ * touches nothing.  A call that fails these checks writes nothing.
+ * Handle state.  Read-only on the kNN state: the neighbour table, the build numbers, the epoch and the knncf_neighbors_save
+ * bytes stay as they were.  The first call after a fit builds the handle's file-order rater copies (20 bytes per train rating,
+ * charged to prep_ms as the streamed KNNCF_PRED_PERSONALIZED path charges them; a refit drops them).  knncf_get_timings: the
+ * similarity rows are charged as rerank_ms, everything else as predict_ms.
+ * Blocks and sub-ranges.  One path at every number of users: the rows are sorted by (user, item) and the distinct users that
+ * have a row on a train item are cut into equal blocks of at most budget / (8 * num_users) users, whose exact fp64 similarity
+ * rows are built per block (as knncf_predict_batch does beyond 2048 users).  Within a block the explain kernel runs over
+ * consecutive sub-ranges of
+ *     R = max(1, budget / (40 * cap + 28))
+ *     budget = workspace_bytes / 2 if workspace_bytes > 0, else min(48 GiB, free device memory / 4)
+ * rows: 20 * cap + 28 bytes of outputs per row, which come back in one copy, and 20 * cap bytes in which
+ * KNNCF_EXPLAIN_BY_WEIGHT stages the selected terms before it ranks them.  The results depend neither on the blocks nor on R,
+ * and a call on a handle that has answered the same shape before allocates no device memory.
+ * OUT OF SCOPE: a device-pointer form, shard handles, KNNCF_SIM_ONE, and Personalized explanations of fold-in / update / revise
+ * queries (knncf_*_explain* below keep refusing KNNCF_PRED_PERSONALIZED). */
+int knncf_explain_personalized(knncf_handle* h, int32_t user, int32_t item, int32_t order, int32_t cap, int32_t* raters, double* sims,
+                               double* devs, int32_t* count, double* sums, double* prediction);
+int knncf_explain_personalized_batch(knncf_handle* h, const int32_t* users, const int32_t* items, int64_t n, int32_t order,
+                                     int32_t cap, int32_t* raters, double* sims, double* devs, int32_t* counts, double* sums,
+                                     double* predictions);
 
 /* ---- fold-in queries: one user that is NOT in the fitted training set ------
  * recommend/Recommender.scala:64-88 appends a person's ratings to the data (data.union(personal), :68) and asks for
@@ -500,7 +553,8 @@ int knncf_revise_recommend_batch(knncf_handle* h, int predictor, const int32_t* 
  * call on a handle that has answered the same shape before allocates no device memory.
  * OUT OF SCOPE here as above: KNNCF_PRED_PERSONALIZED explanations (KNNCF_E_UNSUPPORTED, as the explain calls answer for any
  * predictor but KNNCF_PRED_KNN), sharded explanations (a shard handle: KNNCF_E_UNSUPPORTED), and a fused "recommend and
- * explain in one pass" call: explain the items knncf_*_recommend returned with a second call. */
+ * explain in one pass" call: explain the items knncf_*_recommend returned with a second call.  (Users as the fit holds them have
+ * knncf_explain_personalized* above for KNNCF_PRED_PERSONALIZED.) */
 int knncf_query_explain(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
                         const int32_t* pred_items, int64_t m, int32_t order, int32_t cap, int32_t* raters, double* sims, double* devs,
                         int32_t* counts, double* sums, double* predictions);

@@ -87,6 +87,9 @@ struct knncf_handle {
     // one launch of the query explanations (QB_EXPLAIN): the same outputs of its rows in ONE block, 20 * cap + 28 bytes per
     // row, so that one copy brings a sub-range back (explain_pack)
     DArr<double> ex_pack;
+    // knncf_explain_personalized* with KNNCF_EXPLAIN_BY_WEIGHT: the selected terms of a launch's rows before they are ranked, 20 *
+    // cap bytes per row (explain_all.hip)
+    DArr<double> ex_stage;
     // host mirrors for scalar queries
     std::vector<uint32_t> h_ukeys, h_ikeys;
     std::vector<int32_t> h_uid;
@@ -754,10 +757,17 @@ void ensure_personal_rows(knncf_handle* h, bool fitted = true) {
     h->prow_ready = true;
 }
 
-// The streamed form over the test rows whose dense ids are in t_du / t_di: rows sorted by (user, item), the distinct users
-// that have a row on a train item cut into blocks of R; per block the users' exact rows (rerank_ms), then the folds of the
-// block's rows (predict_ms).  Read-only on the kNN state.
-void predict_personal_rows(knncf_handle* h, const double* d_ratings, int64_t n, double* d_pred) {
+// The plan of the streamed form over the rows whose dense ids are in t_du / t_di: rows sorted by (user, item) — the order is left
+// in prep.v32_b — and the distinct users that have a row on a train item cut into equal blocks of R (their ids in prow.users,
+// each one's row of its block in prow.slot, prow.S sized for a block).  Block b is users [b R, (b + 1) R) and the sorted rows
+// from its first user's first row (block 0: from row 0) to the next block's (the last block: to n).
+struct PersonalPlan {
+    std::vector<int64_t> first_row;  // sorted row where each such user's rows begin
+    int64_t nu = 0, R = 1, n_blocks = 1;
+    int64_t row_begin(int64_t b) const { return b == 0 ? 0 : first_row[b * R]; }
+    int64_t row_end(int64_t b, int64_t n) const { return b + 1 < n_blocks ? first_row[(b + 1) * R] : n; }
+};
+PersonalPlan plan_personal_rows(knncf_handle* h, int64_t n) {
     Train& tr = h->tr;
     PersonalRows& pr = h->prow;
     PrepScratch& sc = h->prep;
@@ -774,25 +784,24 @@ void predict_personal_rows(knncf_handle* h, const double* d_ratings, int64_t n, 
         KN_HIP(hipStreamSynchronize(st));
     }
     // the users whose rows are built: a known user with a row on a train item (its rows sort by item, absent item last)
+    PersonalPlan plan;
     std::vector<int32_t> users;
-    std::vector<int64_t> first_row;  // sorted row where each such user's rows begin
     for (int64_t r = 0; r < n; ++r) {
         const uint64_t u = keys[r] >> ibits, i = keys[r] & ((1ull << ibits) - 1ull);
         if (u < (uint64_t)tr.U && i < (uint64_t)tr.I && (users.empty() || users.back() != (int32_t)u)) {
             users.push_back((int32_t)u);
-            first_row.push_back(r);
+            plan.first_row.push_back(r);
         }
     }
-    const int64_t nu = (int64_t)users.size();
-    int64_t R = 1;
+    const int64_t nu = plan.nu = (int64_t)users.size();
     if (nu > 0) {
         size_t free_b = 0, total_b = 0;
         KN_HIP(hipMemGetInfo(&free_b, &total_b));
         const int64_t row_bytes = (int64_t)tr.U * 8;
         const int64_t budget = h->cfg.workspace_bytes > 0 ? h->cfg.workspace_bytes / 2
                                                           : (int64_t)std::min<size_t>((size_t)48 << 30, (free_b + pr.S.bytes()) / 4);
-        R = std::min<int64_t>(std::max<int64_t>(1, budget / row_bytes), nu);
-        R = ceil_div(nu, ceil_div(nu, R));  // equal blocks
+        int64_t R = std::min<int64_t>(std::max<int64_t>(1, budget / row_bytes), nu);
+        R = plan.R = ceil_div(nu, ceil_div(nu, R));  // equal blocks
         pr.S.ensure((size_t)R * tr.U);
         std::vector<int32_t> slot((size_t)tr.U, -1);
         for (int64_t k = 0; k < nu; ++k) slot[users[k]] = (int32_t)(k % R);
@@ -802,17 +811,26 @@ void predict_personal_rows(knncf_handle* h, const double* d_ratings, int64_t n, 
         KN_HIP(hipMemcpyAsync(pr.slot.p, slot.data(), (size_t)tr.U * sizeof(int32_t), hipMemcpyHostToDevice, st));
         KN_HIP(hipStreamSynchronize(st));  // (the host vectors go out of scope)
     }
-    // block b: users [b R, (b + 1) R), sorted rows from its first user's first row (block 0: from row 0) to the next block's
-    const int64_t n_blocks = std::max<int64_t>(1, ceil_div(nu, R));
-    for (int64_t b = 0; b < n_blocks; ++b) {
-        const int64_t u0 = b * R, u1 = std::min<int64_t>(nu, u0 + R);
-        const int64_t r0 = b == 0 ? 0 : first_row[u0], r1 = b + 1 < n_blocks ? first_row[u1] : n;
+    plan.n_blocks = std::max<int64_t>(1, ceil_div(nu, plan.R));
+    return plan;
+}
+
+// The streamed form over the test rows whose dense ids are in t_du / t_di: per block of the plan the users' exact rows
+// (rerank_ms), then the folds of the block's rows (predict_ms).  Read-only on the kNN state.
+void predict_personal_rows(knncf_handle* h, const double* d_ratings, int64_t n, double* d_pred) {
+    Train& tr = h->tr;
+    PersonalRows& pr = h->prow;
+    hipStream_t st = h->stream;
+    const PersonalPlan plan = plan_personal_rows(h, n);
+    for (int64_t b = 0; b < plan.n_blocks; ++b) {
+        const int64_t u0 = b * plan.R, u1 = std::min<int64_t>(plan.nu, u0 + plan.R);
+        const int64_t r0 = plan.row_begin(b), r1 = plan.row_end(b, n);
         if (u1 > u0) {
             Stage s(h, &h->tm.rerank_ms);
             launch_sim_rows(tr, pr, pr.users.p + u0, (int32_t)(u1 - u0), pr.S.p, st);
         }
         Stage s(h, &h->tm.predict_ms);
-        launch_fold_rows(tr, pr, r1 - r0, sc.v32_b.p + r0, h->t_du.p, h->t_di.p, d_ratings, pr.slot.p, pr.S.p, d_pred, h->t_err.p,
+        launch_fold_rows(tr, pr, r1 - r0, h->prep.v32_b.p + r0, h->t_du.p, h->t_di.p, d_ratings, pr.slot.p, pr.S.p, d_pred, h->t_err.p,
                          h->t_owned.p, st);
     }
 }
@@ -2100,6 +2118,75 @@ int knncf_explain_batch(knncf_handle* h, const int32_t* users, const int32_t* it
 int knncf_explain(knncf_handle* h, int32_t user, int32_t item, int32_t order, int32_t cap, int32_t* raters, double* sims,
                   double* devs, int32_t* count, double* sums, double* prediction) {
     return knncf_explain_batch(h, &user, &item, 1, order, cap, raters, sims, devs, count, sums, prediction);
+}
+
+// ---- explanations of Personalized predictions (explain_all.hip; include/knncf.h "Explanations of Personalized predictions") ----
+// The streamed form of predict_personal_rows at every number of users: per block of the plan the users' exact rows (rerank_ms),
+// then the explain kernel over consecutive sub-ranges of the block's sorted rows (predict_ms), each one's block of outputs
+// brought back with one copy and scattered to the caller's rows.  Read-only on the kNN state.
+static void explain_personal_rows(knncf_handle* h, int64_t n, const ExplainCells& to) {
+    Train& tr = h->tr;
+    PersonalRows& pr = h->prow;
+    hipStream_t st = h->stream;
+    const PersonalPlan plan = plan_personal_rows(h, n);
+    std::vector<uint32_t> order((size_t)n);
+    KN_HIP(hipMemcpyAsync(order.data(), h->prep.v32_b.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    KN_HIP(hipStreamSynchronize(st));
+    const std::vector<int64_t> rows(order.begin(), order.end());  // sorted row -> the caller's row
+    const int64_t sub = std::min<int64_t>(n, std::max<int64_t>(1, batch_budget(h) / (int64_t)explain_all_row_bytes(to.cap)));
+    const size_t pack = ((size_t)sub * explain_row_bytes(to.cap) + 7) / 8;  // doubles
+    h->ex_pack.ensure(pack);
+    if (to.order == KNNCF_EXPLAIN_BY_WEIGHT) h->ex_stage.ensure(((size_t)sub * to.cap * 20 + 7) / 8);
+    std::vector<double> h_vals(pack);
+    for (int64_t b = 0; b < plan.n_blocks; ++b) {
+        const int64_t u0 = b * plan.R, u1 = std::min<int64_t>(plan.nu, u0 + plan.R);
+        if (u1 > u0) {
+            Stage s(h, &h->tm.rerank_ms);
+            launch_sim_rows(tr, pr, pr.users.p + u0, (int32_t)(u1 - u0), pr.S.p, st);
+        }
+        for (int64_t r0 = plan.row_begin(b), r1 = plan.row_end(b, n); r0 < r1; r0 += sub) {
+            const int64_t nr = std::min(sub, r1 - r0);
+            {
+                Stage s(h, &h->tm.predict_ms);
+                launch_explain_all(tr, pr, nr, h->prep.v32_b.p + r0, h->t_du.p, h->t_di.p, pr.slot.p, pr.S.p,
+                                   explain_pack(h->ex_pack.p, nr, to), h->ex_stage.p, st);
+            }
+            KN_HIP(hipMemcpyAsync(h_vals.data(), h->ex_pack.p, (size_t)nr * explain_row_bytes(to.cap), hipMemcpyDeviceToHost, st));
+            KN_HIP(hipStreamSynchronize(st));
+            explain_scatter(explain_pack(h_vals.data(), nr, to), nr, to, rows.data() + r0);
+        }
+    }
+}
+
+int knncf_explain_personalized_batch(knncf_handle* h, const int32_t* users, const int32_t* items, int64_t n, int32_t order, int32_t cap,
+                                     int32_t* raters, double* sims, double* devs, int32_t* counts, double* sums, double* predictions) {
+    return guarded(h, [&] {
+        require_fitted(h, false);  // (a shard handle is refused below, committed or not)
+        KN_REQUIRE(n >= 0 && cap >= 0, KNNCF_E_INVALID, "explain: n or cap < 0");
+        KN_REQUIRE(order == KNNCF_EXPLAIN_SUM_ORDER || order == KNNCF_EXPLAIN_BY_WEIGHT, KNNCF_E_INVALID, "explain: unknown order");
+        KN_REQUIRE(n < (int64_t)0xffffffffll, KNNCF_E_INVALID, "explain: 2^32-1 rows or more");
+        KN_REQUIRE(n == 0 || (users && items && counts && (cap == 0 || (raters && sims && devs))), KNNCF_E_INVALID, "explain: null argument");
+        KN_REQUIRE(h->cfg.similarity != KNNCF_SIM_ONE, KNNCF_E_UNSUPPORTED,
+                   "PERSONALIZED explanations with similarityOne: every weight is 1.0, there is nothing to explain");
+        KN_REQUIRE(h->cfg.shard_count == 1, KNNCF_E_UNSUPPORTED, "explain: single-shard handles only");
+        if (n == 0) return;
+        ensure_personal_rows(h);  // (and the fitted Personalized predictor's refusals)
+        hipStream_t st = h->stream;
+        h->t_users.ensure(n); h->t_items.ensure(n);
+        KN_HIP(hipMemcpyAsync(h->t_users.p, users, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        KN_HIP(hipMemcpyAsync(h->t_items.p, items, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        ensure_test_scratch(h, n);
+        {
+            Stage s(h, &h->tm.predict_ms);
+            launch_dense_ids(h->tr, h->t_users.p, h->t_items.p, n, h->t_du.p, h->t_di.p, st);
+        }
+        explain_personal_rows(h, n, {order, cap, raters, sims, devs, counts, sums, predictions});
+    });
+}
+
+int knncf_explain_personalized(knncf_handle* h, int32_t user, int32_t item, int32_t order, int32_t cap, int32_t* raters, double* sims,
+                               double* devs, int32_t* count, double* sums, double* prediction) {
+    return knncf_explain_personalized_batch(h, &user, &item, 1, order, cap, raters, sims, devs, count, sums, prediction);
 }
 
 int knncf_recommend(knncf_handle* h, int predictor, int32_t user, int32_t n, int32_t* items, double* predictions, int32_t* count) {

@@ -306,6 +306,18 @@ void launch_fold_rows(const Train& tr, const PersonalRows& pr, int64_t n_rows, c
                       const int32_t* d_di, const double* d_ratings, const int32_t* d_slot, const double* d_S, double* d_pred,
                       double* d_abs_err, uint8_t* d_owned, hipStream_t st);
 
+// ---- explain_all.hip: the terms behind Personalized predictions of fitted users (knncf_explain_personalized*; DESIGN.md
+// "Explanations of Personalized predictions") ----
+// bytes per row of a launch that the sub-range rule of knncf.h counts: the outputs in one block (explain_pack) and as much
+// again for the term cells that KNNCF_EXPLAIN_BY_WEIGHT stages before it ranks them
+inline size_t explain_all_row_bytes(int32_t cap) { return 40 * (size_t)cap + 28; }
+// rows d_order[0 .. n_rows) of (d_du, d_di), users of the block whose exact rows are d_S[d_slot[user]], into rows [0, n_rows) of
+// `out` (every pointer set; terms: the item's raters whose similarity is non-zero, the user itself included).  d_stage holds
+// 20 * n_rows * out.cap bytes and is read and written with KNNCF_EXPLAIN_BY_WEIGHT only.  One launch.
+void launch_explain_all(const Train& tr, const PersonalRows& pr, int64_t n_rows, const uint32_t* d_order, const int32_t* d_du,
+                        const int32_t* d_di, const int32_t* d_slot, const double* d_S, const ExplainCells& out, double* d_stage,
+                        hipStream_t st);
+
 // ---- foldin.hip: kNN queries of users outside the fit (DESIGN.md "Fold-in queries") ----------------------------------
 // Chunks of independent queries, every stage one launch over the chunk; a single call is a chunk of one.  The scratch is
 // handle-owned; the fit, its neighbour table and its sequence numbers are only read.

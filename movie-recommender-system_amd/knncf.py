@@ -119,6 +119,7 @@ EXPORTS = [
     "knncf_user_avg", "knncf_item_avg", "knncf_item_avg_dev", "knncf_item_avg_dev_rdd", "knncf_similarity",
     "knncf_knn_similarity", "knncf_neighbors", "knncf_neighbors_batch", "knncf_predict", "knncf_recommend", "knncf_recommend_batch",
     "knncf_explain", "knncf_explain_batch", "knncf_explain_batch_device",
+    "knncf_explain_personalized", "knncf_explain_personalized_batch",
     "knncf_query_neighbors", "knncf_query_predict", "knncf_query_recommend",
     "knncf_query_neighbors_batch", "knncf_query_predict_batch", "knncf_query_recommend_batch",
     "knncf_update_neighbors", "knncf_update_predict", "knncf_update_recommend",
@@ -210,6 +211,8 @@ def load_library():
     L.knncf_explain_batch.argtypes = [C.c_void_p, _i32p, _i32p, C.c_int64, C.c_int32, C.c_int32, _i32p, _f64p, _f64p, _i32p, _f64p,
                                       _f64p]
     L.knncf_explain_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 6
+    L.knncf_explain_personalized.argtypes = L.knncf_explain.argtypes
+    L.knncf_explain_personalized_batch.argtypes = L.knncf_explain_batch.argtypes
     for fam in ("query", "update"):  # fold-in queries and update queries share their argument lists
         f = lambda name: getattr(L, f"knncf_{fam}_{name}")
         f("neighbors").argtypes = [C.c_void_p, C.c_int32, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p]
@@ -453,31 +456,25 @@ class Engine:
             raise ValueError("order must be EXPLAIN_SUM_ORDER or EXPLAIN_BY_WEIGHT")
         return int(cap), int(order)
 
-    def explain(self, user, item, cap=None, order=EXPLAIN_SUM_ORDER):
-        """The terms behind predict(PRED_KNN, user, item) (knncf_explain): (raters int32, sims, devs, count, (num, den),
-        prediction) — the neighbours of `user` with a non-zero similarity that rated `item`, in `order`; the arrays hold
-        min(count, cap) terms.  cap=None: the handle's min(k, U - 1), which every row fits."""
-        if cap is None:
-            cap = max(0, min(self.k, self.num_users - 1))
+    def _explain_row(self, entry, user, item, cap, order):
         cap, order = self._explain_args(cap, order)
+        fn = getattr(self._lib, entry)
         raters = np.empty(max(1, cap), dtype=np.int32)
         sims = np.empty(max(1, cap), dtype=np.float64)
         devs = np.empty(max(1, cap), dtype=np.float64)
         c, sums, pred = C.c_int32(), np.zeros(2, dtype=np.float64), C.c_double()
         p = self._ptr
-        self._check(self._lib.knncf_explain(self._h, user, item, order, cap, p(raters, _i32p), p(sims, _f64p), p(devs, _f64p),
-                                            C.byref(c), p(sums, _f64p), C.byref(pred)))
+        self._check(fn(self._h, user, item, order, cap, p(raters, _i32p), p(sims, _f64p), p(devs, _f64p), C.byref(c), p(sums, _f64p),
+                       C.byref(pred)))
         m = min(c.value, cap)
         return raters[:m].copy(), sims[:m].copy(), devs[:m].copy(), c.value, (float(sums[0]), float(sums[1])), pred.value
 
-    def explain_batch(self, users, items, cap, order=EXPLAIN_SUM_ORDER):
-        """explain for every row (users[j], items[j]) (knncf_explain_batch): (raters [n, cap] int32, sims [n, cap], devs
-        [n, cap], counts [n] int32, sums [n, 2], predictions [n]); cells past a row's min(count, cap) terms are -1 / nan.
-        Missing neighbourhoods are built as predict_batch(PRED_KNN, users, items) builds them."""
+    def _explain_rows(self, entry, users, items, cap, order):
         cap, order = self._explain_args(cap, order)
         u, i = _i32(users), _i32(items)
         if u.ndim != 1 or u.shape != i.shape:
             raise ValueError("users and items must be 1-D arrays of one length")
+        fn = getattr(self._lib, entry)
         n = len(u)
         raters = np.full((n, cap), -1, dtype=np.int32)
         sims = np.full((n, cap), np.nan, dtype=np.float64)
@@ -486,10 +483,36 @@ class Engine:
         sums = np.zeros((n, 2), dtype=np.float64)
         preds = np.empty(n, dtype=np.float64)
         p = self._ptr
-        self._check(self._lib.knncf_explain_batch(self._h, p(u, _i32p), p(i, _i32p), n, order, cap, p(raters.reshape(-1), _i32p),
-                                                  p(sims.reshape(-1), _f64p), p(devs.reshape(-1), _f64p), p(counts, _i32p),
-                                                  p(sums.reshape(-1), _f64p), p(preds, _f64p)))
+        self._check(fn(self._h, p(u, _i32p), p(i, _i32p), n, order, cap, p(raters.reshape(-1), _i32p), p(sims.reshape(-1), _f64p),
+                       p(devs.reshape(-1), _f64p), p(counts, _i32p), p(sums.reshape(-1), _f64p), p(preds, _f64p)))
         return raters, sims, devs, counts, sums, preds
+
+    def explain(self, user, item, cap=None, order=EXPLAIN_SUM_ORDER):
+        """The terms behind predict(PRED_KNN, user, item) (knncf_explain): (raters int32, sims, devs, count, (num, den),
+        prediction) — the neighbours of `user` with a non-zero similarity that rated `item`, in `order`; the arrays hold
+        min(count, cap) terms.  cap=None: the handle's min(k, U - 1), which every row fits."""
+        if cap is None:
+            cap = max(0, min(self.k, self.num_users - 1))
+        return self._explain_row("knncf_explain", user, item, cap, order)
+
+    def explain_batch(self, users, items, cap, order=EXPLAIN_SUM_ORDER):
+        """explain for every row (users[j], items[j]) (knncf_explain_batch): (raters [n, cap] int32, sims [n, cap], devs
+        [n, cap], counts [n] int32, sums [n, 2], predictions [n]); cells past a row's min(count, cap) terms are -1 / nan.
+        Missing neighbourhoods are built as predict_batch(PRED_KNN, users, items) builds them."""
+        return self._explain_rows("knncf_explain_batch", users, items, cap, order)
+
+    def explain_personalized(self, user, item, cap=16, order=EXPLAIN_BY_WEIGHT):
+        """The terms behind predict(PRED_PERSONALIZED, user, item) (knncf_explain_personalized), as explain returns them: every
+        rater of `item` whose similarity with `user` is non-zero is a term, `user` itself included when it rated the item in
+        train.  The defaults answer "which 16 users carried this prediction"; cap=None: num_users, which every row fits."""
+        if cap is None:
+            cap = self.num_users
+        return self._explain_row("knncf_explain_personalized", user, item, cap, order)
+
+    def explain_personalized_batch(self, users, items, cap, order=EXPLAIN_SUM_ORDER):
+        """explain_personalized for every row (users[j], items[j]) (knncf_explain_personalized_batch), as explain_batch returns
+        it.  Read-only on the neighbour table."""
+        return self._explain_rows("knncf_explain_personalized_batch", users, items, cap, order)
 
     def explain_batch_device(self, users, items, cap, raters, sims, devs, counts, sums=None, predictions=None,
                              order=EXPLAIN_SUM_ORDER):
