@@ -307,7 +307,8 @@ int knncf_explain_batch_device(knncf_handle* h, const int32_t* d_users, const in
  * KNNCF_EXPLAIN_BY_WEIGHT stages the selected terms before it ranks them.  The results depend neither on the blocks nor on R,
  * and a call on a handle that has answered the same shape before allocates no device memory.
  * OUT OF SCOPE: a device-pointer form, shard handles, KNNCF_SIM_ONE, and Personalized explanations of fold-in / update / revise
- * queries (knncf_*_explain* below keep refusing KNNCF_PRED_PERSONALIZED). */
+ * queries (knncf_*_explain* below keep refusing KNNCF_PRED_PERSONALIZED).  Those have calls of their own:
+ * knncf_*_explain_personalized* ("Explanations of Personalized query predictions" below). */
 int knncf_explain_personalized(knncf_handle* h, int32_t user, int32_t item, int32_t order, int32_t cap, int32_t* raters, double* sims,
                                double* devs, int32_t* count, double* sums, double* prediction);
 int knncf_explain_personalized_batch(knncf_handle* h, const int32_t* users, const int32_t* items, int64_t n, int32_t order,
@@ -515,7 +516,8 @@ int knncf_revise_recommend_batch(knncf_handle* h, int predictor, const int32_t* 
  * num_users * the power of two >= C bytes) are allocated beside the chunk budget.  knncf_get_timings: the new fold is charged
  * to predict_ms.  A repeated call of the same shape allocates nothing.
  * Not part of this: knncf_*_explain* with KNNCF_PRED_PERSONALIZED (KNNCF_E_UNSUPPORTED, below), the *_neighbors calls (they
- * have no predictor), every other predictor (KNNCF_E_UNSUPPORTED). */
+ * have no predictor), every other predictor (KNNCF_E_UNSUPPORTED).  The terms behind these predictions are what
+ * knncf_*_explain_personalized* return ("Explanations of Personalized query predictions" below). */
 
 /* ---- Explanations of query predictions: the terms behind knncf_query_predict / knncf_update_predict / knncf_revise_predict ---
  * knncf_explain* above explains a prediction for a user as the fit holds it.  These explain what the three query families
@@ -554,7 +556,8 @@ int knncf_revise_recommend_batch(knncf_handle* h, int predictor, const int32_t* 
  * OUT OF SCOPE here as above: KNNCF_PRED_PERSONALIZED explanations (KNNCF_E_UNSUPPORTED, as the explain calls answer for any
  * predictor but KNNCF_PRED_KNN), sharded explanations (a shard handle: KNNCF_E_UNSUPPORTED), and a fused "recommend and
  * explain in one pass" call: explain the items knncf_*_recommend returned with a second call.  (Users as the fit holds them have
- * knncf_explain_personalized* above for KNNCF_PRED_PERSONALIZED.) */
+ * knncf_explain_personalized* above for KNNCF_PRED_PERSONALIZED; the query families have knncf_*_explain_personalized* below,
+ * "Explanations of Personalized query predictions".) */
 int knncf_query_explain(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
                         const int32_t* pred_items, int64_t m, int32_t order, int32_t cap, int32_t* raters, double* sims, double* devs,
                         int32_t* counts, double* sums, double* predictions);
@@ -578,6 +581,79 @@ int knncf_revise_explain_batch(knncf_handle* h, int predictor, const int32_t* us
                                int64_t n_queries, const int64_t* pred_offsets, const int32_t* pred_items, int32_t order, int32_t cap,
                                int32_t* raters, double* sims, double* devs, int32_t* counts, double* sums, double* predictions,
                                int32_t* statuses);
+
+/* ---- Explanations of Personalized query predictions: the terms behind KNNCF_PRED_PERSONALIZED on the query families -----------
+ * knncf_query_predict / knncf_update_predict / knncf_revise_predict with predictor == KNNCF_PRED_PERSONALIZED ("Personalized
+ * queries" above) fold every rating of the item in aug.  These six calls answer "which few users carried this prediction" for
+ * them, as knncf_explain_personalized* does for users as the fit holds them.  NEW CALLS, NOT A LIFTED REFUSAL:
+ * knncf_*_explain* above keep answering KNNCF_E_UNSUPPORTED for KNNCF_PRED_PERSONALIZED.
+ * Arguments.  Exactly those of the matching knncf_*_explain / knncf_*_explain_batch call without `int predictor`
+ * (knncf_explain_personalized* has none either): the query, the requested items (m of them, or the pred_offsets / pred_items
+ * CSR), order, cap and the outputs.  Row j of the call is one requested (query, raw item).
+ * Terms of row (u, i).  With aug exactly as each family defines it and S = adjustedCosineSimilarityFunction(aug) or
+ * jaccardCoefficient(aug) on fresh closures whose first argument is only ever the query user u: the elements of simVal
+ * shared/predictions.scala:513-517 on aug whose similarity is not exactly 0.0, over ALL ratings of i in aug, in aug's file order,
+ * each (the rater's raw id, S(u, rater), the rater's normalized deviation on i).
+ * THE USER IS ITS OWN TERM when it rates i in aug, as in the Personalized query predictions: weight S(u, u) on aug (for the
+ * cosine close to but not 1.0, for Jaccard exactly 1.0), u's deviation ON AUG, rater id = the query's `user`.  Its place follows
+ * the row it comes from: a surviving train row stands at its train file place; an additional row stands last, after every train
+ * row, and so does any row of a fold-in user and a re-rated item; a removed row is no term.
+ * Orders.  KNNCF_EXPLAIN_SUM_ORDER is that file order.  KNNCF_EXPLAIN_BY_WEIGHT is |similarity| descending, equal magnitudes in
+ * summation order; when cap cuts through a group of equal magnitudes, the earliest in summation order are kept.
+ * Outputs.  counts[j] = the number of terms (it may exceed cap); the first min(counts[j], cap) terms, in `order`, in row j of
+ * raters / sims / devs (row stride cap; cells beyond the terms are left untouched).  sums and predictions may be null; with
+ * cap == 0 the three term arrays may be null.  sums[2 j], sums[2 j + 1] = num and den of the fold :520-524 over all of the
+ * item's ratings in aug, independent of order and cap.  With counts[j] <= cap and KNNCF_EXPLAIN_SUM_ORDER the caller's left fold
+ * of the returned terms, (num + dev * sim, den + |sim|) from (0.0, 0.0) with the multiply and the add separate (no fused
+ * multiply-add), gives sums bit for bit: the raters that are no terms add +-0.0 to sums that start at +0.0.  The combine :578
+ * of the query's mean with (den > 0 ? num / den : 0.0) gives predictions[j], which equals the matching
+ * knncf_*_predict(..., KNNCF_PRED_PERSONALIZED, ...) answer bit for bit.
+ * Row kinds.  An item unknown to aug (an id never seen, or the item that leaves aug under a revise query): count 0, sums
+ * (0, 0), the query's mean exactly.  An item only u rates in aug (an additional item unknown to train, or the re-rated lone
+ * item): exactly one term, u's own.  A query with S(u, u) == 0.0 (the cosine with every deviation zero, e.g. a one-rating
+ * fold-in user): count 0 on every row and the mean as every prediction.  An item whose raters all have similarity 0.0: count 0
+ * and the mean.
+ * Everything else is as "Personalized queries" documents it: per-query statuses and handle-level return values, the CSR checks,
+ * n_queries == 0, the cap of 65536 rows, the negative-mean refusal, >= 5 train users, KNNCF_SIM_ONE and shard handles refused,
+ * train users with 4 or fewer ratings accepted, the handle's k without a part, the chunk rule C, the split at 32 answerable
+ * queries between the two similarity kernels, and "the results do not depend on C".  In addition, as knncf_*_explain*:
+ * KNNCF_E_INVALID for cap < 0, an unknown order, or a needed output pointer that is null; a failed query gets counts[j] = 0 on
+ * each of its rows and nothing else of those rows is written; a single call returns the query's status.
+ * Row sub-ranges inside a chunk.  The explain kernel runs over consecutive sub-ranges of
+ *     R = max(1, budget / (40 * cap + 28))
+ *     budget = workspace_bytes / 2 if workspace_bytes > 0, else min(48 GiB, free device memory / 4)
+ * rows (the budget of the other batched calls; the formula of knncf_explain_personalized*: 20 * cap + 28 bytes of outputs per
+ * row, which come back in one copy, and 20 * cap bytes in which KNNCF_EXPLAIN_BY_WEIGHT stages the selected terms before it
+ * ranks them).  The chunk's fold results stay in place between the launches.  The results do not depend on R, and a call on a
+ * handle that has answered the same shape before allocates no device memory.
+ * Handle state.  Read-only in the sense of the other families: the neighbour table, its build numbers, its epoch and the
+ * knncf_neighbors_save bytes stay as they were.  The first call after a fit builds the handle's file-order rater copies
+ * (prep_ms); knncf_get_timings: the fold and the explain kernel are charged to predict_ms.
+ * OUT OF SCOPE: a device-pointer form, shard handles, KNNCF_SIM_ONE, a fused "recommend and explain in one pass" call, and the
+ * command-line tool. */
+int knncf_query_explain_personalized(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
+                                     const int32_t* pred_items, int64_t m, int32_t order, int32_t cap, int32_t* raters, double* sims,
+                                     double* devs, int32_t* counts, double* sums, double* predictions);
+int knncf_update_explain_personalized(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
+                                      const int32_t* pred_items, int64_t m, int32_t order, int32_t cap, int32_t* raters, double* sims,
+                                      double* devs, int32_t* counts, double* sums, double* predictions);
+int knncf_revise_explain_personalized(knncf_handle* h, int32_t user, const int32_t* removed_items, int64_t n_removed,
+                                      const int32_t* items, const double* ratings, int64_t n_ratings, const int32_t* pred_items,
+                                      int64_t m, int32_t order, int32_t cap, int32_t* raters, double* sims, double* devs,
+                                      int32_t* counts, double* sums, double* predictions);
+int knncf_query_explain_personalized_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                                           const double* ratings, int64_t n_queries, const int64_t* pred_offsets,
+                                           const int32_t* pred_items, int32_t order, int32_t cap, int32_t* raters, double* sims,
+                                           double* devs, int32_t* counts, double* sums, double* predictions, int32_t* statuses);
+int knncf_update_explain_personalized_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                                            const double* ratings, int64_t n_queries, const int64_t* pred_offsets,
+                                            const int32_t* pred_items, int32_t order, int32_t cap, int32_t* raters, double* sims,
+                                            double* devs, int32_t* counts, double* sums, double* predictions, int32_t* statuses);
+int knncf_revise_explain_personalized_batch(knncf_handle* h, const int32_t* users, const int64_t* removed_offsets,
+                                            const int32_t* removed_items, const int64_t* offsets, const int32_t* items,
+                                            const double* ratings, int64_t n_queries, const int64_t* pred_offsets,
+                                            const int32_t* pred_items, int32_t order, int32_t cap, int32_t* raters, double* sims,
+                                            double* devs, int32_t* counts, double* sums, double* predictions, int32_t* statuses);
 
 /* ---- batch ---------------------------------------------------------------- */
 int knncf_predict_batch(knncf_handle* h, int predictor, const int32_t* users,

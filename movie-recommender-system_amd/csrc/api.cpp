@@ -84,11 +84,11 @@ struct knncf_handle {
     // one chunk of knncf_explain_batch's host form: [C * cap] terms, [C] counts and predictions, [2 C] sums
     DArr<int32_t> ex_raters, ex_counts;
     DArr<double> ex_sims, ex_devs, ex_sums, ex_pred;
-    // one launch of the query explanations (QB_EXPLAIN): the same outputs of its rows in ONE block, 20 * cap + 28 bytes per
+    // one launch of the query explanations (QB_EXPLAIN, QB_EXPLAIN_ALL): the same outputs of its rows in ONE block, 20 * cap + 28 bytes per
     // row, so that one copy brings a sub-range back (explain_pack)
     DArr<double> ex_pack;
-    // knncf_explain_personalized* with KNNCF_EXPLAIN_BY_WEIGHT: the selected terms of a launch's rows before they are ranked, 20 *
-    // cap bytes per row (explain_all.hip)
+    // knncf_explain_personalized* and knncf_*_explain_personalized* with KNNCF_EXPLAIN_BY_WEIGHT: the selected terms of a launch's
+    // rows before they are ranked, 20 * cap bytes per row (explain_select.h)
     DArr<double> ex_stage;
     // host mirrors for scalar queries
     std::vector<uint32_t> h_ukeys, h_ikeys;
@@ -1043,11 +1043,15 @@ void do_fit_device(knncf_handle* h, const int32_t* d_users, const int32_t* d_ite
 // Revise queries (knncf_revise_*) are update queries that also name train items of the user to REMOVE from aug: the seeding
 // leaves their rows out.  A chunk without removals is an update chunk.
 constexpr int64_t QUERY_MAX_RATINGS = 65536;
-enum QueryBatchMode { QB_NEIGHBORS, QB_PREDICT, QB_RECOMMEND, QB_EXPLAIN };
+// QB_EXPLAIN_ALL: the explanations of KNNCF_PRED_PERSONALIZED predictions (knncf_*_explain_personalized*), a mode of its own so
+// that QB_EXPLAIN keeps refusing that predictor
+enum QueryBatchMode { QB_NEIGHBORS, QB_PREDICT, QB_RECOMMEND, QB_EXPLAIN, QB_EXPLAIN_ALL };
+bool explains(QueryBatchMode mode) { return mode == QB_EXPLAIN || mode == QB_EXPLAIN_ALL; }
 enum QueryFamily { QF_FOLD_IN, QF_UPDATE, QF_REVISE };
 
 // what the handle must be for any fold-in query, single or batched
 void require_query_support(knncf_handle* h, int predictor, QueryBatchMode mode) {
+    KN_REQUIRE(mode != QB_EXPLAIN_ALL || predictor == KNNCF_PRED_PERSONALIZED, KNNCF_E_UNSUPPORTED, "query explain: only KNNCF_PRED_PERSONALIZED");
     KN_REQUIRE(predictor == KNNCF_PRED_KNN || (predictor == KNNCF_PRED_PERSONALIZED && mode != QB_EXPLAIN), KNNCF_E_UNSUPPORTED,
                mode == QB_EXPLAIN ? "query explain: only KNNCF_PRED_KNN" : "query: only KNNCF_PRED_KNN and KNNCF_PRED_PERSONALIZED");
     KN_REQUIRE(h->cfg.similarity != KNNCF_SIM_ONE, KNNCF_E_UNSUPPORTED, "query: adjusted cosine or Jaccard");
@@ -1075,6 +1079,10 @@ int64_t query_batch_chunk(knncf_handle* h, int64_t budget) {
 size_t explain_row_bytes(int32_t cap) { return 20 * (size_t)cap + 28; }
 int64_t explain_rows(int64_t budget, int32_t cap) { return std::max<int64_t>(budget / (int64_t)explain_row_bytes(cap), 1); }
 int64_t explain_batch_chunk(knncf_handle* h, int32_t cap) { return explain_rows(batch_budget(h), cap); }
+// rows per launch of a query explain mode: QB_EXPLAIN_ALL stages as many bytes again (explain_all_row_bytes)
+int64_t query_explain_rows(int64_t budget, int32_t cap, bool all) {
+    return all ? std::max<int64_t>(budget / (int64_t)explain_all_row_bytes(cap), 1) : explain_rows(budget, cap);
+}
 
 // the first query that was refused (-1: none) and why
 struct QueryFailure {
@@ -1125,14 +1133,14 @@ struct QueryCall {
     const double* ratings;
     const int64_t* removed_offsets;  // QF_REVISE (null otherwise): [B + 1] into removed_items
     const int32_t* removed_items;    // QF_REVISE: the train items each query's user drops
-    const int64_t* pred_offsets;     // QB_PREDICT, QB_EXPLAIN: [B + 1] into pred_items; row j of the call is pred_items[j]
-    const int32_t* pred_items;       // QB_PREDICT, QB_EXPLAIN: the requested items
+    const int64_t* pred_offsets;     // QB_PREDICT, explain modes: [B + 1] into pred_items; row j of the call is pred_items[j]
+    const int32_t* pred_items;       // QB_PREDICT, explain modes: the requested items
     int32_t width;                   // QB_NEIGHBORS: cap; QB_RECOMMEND: n
     int32_t* out_i;                  // QB_NEIGHBORS: ids [B * cap]; QB_RECOMMEND: items [B * n]; unused otherwise
     double* out_d;                   // QB_NEIGHBORS: sims [B * cap]; QB_RECOMMEND: predictions [B * n]; QB_PREDICT: [pred_offsets[B]]
     int32_t* counts;                 // QB_NEIGHBORS, QB_RECOMMEND: [B]
     int32_t* statuses;               // [B]
-    ExplainCells ex;                 // QB_EXPLAIN: pred_offsets[B] rows
+    ExplainCells ex;                 // explain modes: pred_offsets[B] rows
     int32_t user;                    // single forms only, from here on
     int64_t n_ratings, n_removed, m;
 };
@@ -1156,7 +1164,11 @@ QueryCall explain_call(QueryCall rows, int predictor, const ExplainCells& ex) {
     rows.mode = QB_EXPLAIN; rows.predictor = predictor; rows.ex = ex;
     return rows;
 }
-bool wants_rows(QueryBatchMode mode) { return mode == QB_PREDICT || mode == QB_EXPLAIN; }
+QueryCall explain_all_call(QueryCall rows, const ExplainCells& ex) {
+    rows.mode = QB_EXPLAIN_ALL; rows.predictor = KNNCF_PRED_PERSONALIZED; rows.ex = ex;
+    return rows;
+}
+bool wants_rows(QueryBatchMode mode) { return mode == QB_PREDICT || explains(mode); }
 
 // ---- the chunk loop ---------------------------------------------------------------------------------------------------------
 // what one call's chunks share: the host vectors are reused from chunk to chunk
@@ -1178,7 +1190,7 @@ struct ChunkState {
 void fail(const QueryCall& q, ChunkState& cs, int64_t b, int status, const char* why) {
     q.statuses[b] = status;
     if (q.counts) q.counts[b] = 0;
-    if (q.mode == QB_EXPLAIN) std::fill(q.ex.counts + q.pred_offsets[b], q.ex.counts + q.pred_offsets[b + 1], 0);
+    if (explains(q.mode)) std::fill(q.ex.counts + q.pred_offsets[b], q.ex.counts + q.pred_offsets[b + 1], 0);
     if (cs.first.query < 0 || b < cs.first.query) cs.first = {b, why};
 }
 
@@ -1264,8 +1276,8 @@ void fold_chunk(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
     foldin_batch_predictions(h->tr, h->query_batch, h->prep.sort, cs.C, cs.take, cs.ebase.data(), h->stream);
 }
 
-// QB_PREDICT, QB_EXPLAIN: the requested rows of the chunk's good queries, (item, slot) each, folded and uploaded to
-// bs.pick_items / bs.pick_slot; QB_EXPLAIN: cs.pick_row = the row of the call behind each.  Returns their number m (0: nothing
+// QB_PREDICT and the explain modes: the requested rows of the chunk's good queries, (item, slot) each, folded and uploaded to
+// bs.pick_items / bs.pick_slot; explain modes: cs.pick_row = the row of the call behind each.  Returns their number m (0: nothing
 // was launched)
 int64_t upload_picks(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
     cs.pick_slot.clear(); cs.pick_items.clear(); cs.pick_row.clear();
@@ -1273,7 +1285,7 @@ int64_t upload_picks(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
         const int64_t b = cs.slot_query[s];
         cs.pick_items.insert(cs.pick_items.end(), q.pred_items + q.pred_offsets[b], q.pred_items + q.pred_offsets[b + 1]);
         cs.pick_slot.insert(cs.pick_slot.end(), (size_t)(q.pred_offsets[b + 1] - q.pred_offsets[b]), s);
-        if (q.mode == QB_EXPLAIN)
+        if (explains(q.mode))
             for (int64_t j = q.pred_offsets[b]; j < q.pred_offsets[b + 1]; ++j) cs.pick_row.push_back(j);
     }
     const int64_t m = (int64_t)cs.pick_items.size();
@@ -1317,10 +1329,19 @@ void answer_explain(knncf_handle* h, const QueryCall& q, ChunkState& cs, int64_t
     const size_t pack = ((size_t)R * explain_row_bytes(q.ex.cap) + 7) / 8;  // doubles
     h->ex_pack.ensure(pack);
     cs.h_vals.resize(pack);
+    const bool all = q.mode == QB_EXPLAIN_ALL;  // (the terms of the Personalized fold; BY_WEIGHT stages the selected ones)
+    if (all && q.ex.order == KNNCF_EXPLAIN_BY_WEIGHT) h->ex_stage.ensure(((size_t)R * q.ex.cap * 20 + 7) / 8);
     for (int64_t r0 = 0; r0 < m; r0 += R) {
         const int64_t nr = std::min(R, m - r0);
-        const QbExplainRows rows{cs.take, cs.ebase[cs.C], bs.pick_items.p, bs.pick_slot.p, r0, nr};
-        foldin_batch_explain(h->tr, bs, rows, explain_pack(h->ex_pack.p, nr, q.ex), st);
+        if (all) {
+            Stage s(h, &h->tm.predict_ms);
+            const QbExplainRows rows{0, 0, bs.pick_items.p, bs.pick_slot.p, r0, nr};
+            foldin_batch_explain_all(h->tr, h->prow, bs, rows, q.family != QF_FOLD_IN, explain_pack(h->ex_pack.p, nr, q.ex),
+                                     h->ex_stage.p, st);
+        } else {
+            const QbExplainRows rows{cs.take, cs.ebase[cs.C], bs.pick_items.p, bs.pick_slot.p, r0, nr};
+            foldin_batch_explain(h->tr, bs, rows, explain_pack(h->ex_pack.p, nr, q.ex), st);
+        }
         KN_HIP(hipMemcpyAsync(cs.h_vals.data(), h->ex_pack.p, (size_t)nr * explain_row_bytes(q.ex.cap), hipMemcpyDeviceToHost, st));
         KN_HIP(hipStreamSynchronize(st));
         explain_scatter(explain_pack(cs.h_vals.data(), nr, q.ex), nr, q.ex, cs.pick_row.data() + r0);
@@ -1354,7 +1375,7 @@ void answer_recommend(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
 }
 
 // The validated queries of q in chunks of `chunk`: statuses[b] and, where it is KNNCF_OK, query b's answer in q's outputs.  A
-// refused query gets ex.counts = 0 on its rows (QB_EXPLAIN, answered ex_rows rows per launch)
+// refused query gets ex.counts = 0 on its rows (the explain modes, answered ex_rows rows per launch)
 QueryFailure run_query_chunks(knncf_handle* h, const QueryCall& q, int64_t chunk, int64_t ex_rows) {
     h->prep.join_commit(h->stream);
     const bool update = q.family != QF_FOLD_IN, revise = q.family == QF_REVISE;
@@ -1372,7 +1393,8 @@ QueryFailure run_query_chunks(knncf_handle* h, const QueryCall& q, int64_t chunk
         switch (q.mode) {
             case QB_NEIGHBORS: answer_neighbors(h, q, cs); break;
             case QB_PREDICT: answer_predict(h, q, cs); break;
-            case QB_EXPLAIN: answer_explain(h, q, cs, ex_rows); break;
+            case QB_EXPLAIN:
+            case QB_EXPLAIN_ALL: answer_explain(h, q, cs, ex_rows); break;
             case QB_RECOMMEND: answer_recommend(h, q, cs); break;
         }
     }
@@ -1401,7 +1423,7 @@ void do_query_batch(knncf_handle* h, const QueryCall& q) {
     require_fitted(h, false);
     KN_REQUIRE(B >= 0, KNNCF_E_INVALID, "query batch: n_queries < 0");
     KN_REQUIRE(wants_rows(q.mode) || q.width >= 0, KNNCF_E_INVALID, "query batch: cap or n < 0");
-    if (q.mode == QB_EXPLAIN) require_explain_order(q.ex);
+    if (explains(q.mode)) require_explain_order(q.ex);
     require_query_support(h, q.predictor, q.mode);
     if (B == 0) return;
     KN_REQUIRE(q.users && q.offsets && q.statuses && (wants_rows(q.mode) || q.counts), KNNCF_E_INVALID, "query batch: null argument");
@@ -1415,14 +1437,15 @@ void do_query_batch(knncf_handle* h, const QueryCall& q) {
     }
     if (wants_rows(q.mode)) {
         require_offsets(q.pred_offsets, B, "query batch: pred_offsets null or not starting at 0", "query batch: pred_offsets decrease");
-        KN_REQUIRE(q.pred_offsets[B] == 0 || (q.pred_items && (q.mode == QB_EXPLAIN || q.out_d)), KNNCF_E_INVALID,
+        KN_REQUIRE(q.pred_offsets[B] == 0 || (q.pred_items && (explains(q.mode) || q.out_d)), KNNCF_E_INVALID,
                    "query batch: null prediction arguments");
-        if (q.mode == QB_EXPLAIN) require_explain_outputs(q.ex, q.pred_offsets[B]);
+        if (explains(q.mode)) require_explain_outputs(q.ex, q.pred_offsets[B]);
     } else {
         KN_REQUIRE(q.width == 0 || (q.out_i && q.out_d), KNNCF_E_INVALID, "query batch: null output");
     }
     const int64_t budget = batch_budget(h);  // (one hipMemGetInfo for both rules)
-    const QueryFailure f = run_query_chunks(h, q, query_batch_chunk(h, budget), q.mode == QB_EXPLAIN ? explain_rows(budget, q.ex.cap) : 0);
+    const QueryFailure f = run_query_chunks(h, q, query_batch_chunk(h, budget),
+                                            explains(q.mode) ? query_explain_rows(budget, q.ex.cap, q.mode == QB_EXPLAIN_ALL) : 0);
     if (f.query >= 0) h->err = "query batch: query " + std::to_string(f.query) + ": " + f.reason;
 }
 
@@ -1442,7 +1465,7 @@ void require_single_outputs(const QueryCall& q) {
 void do_query_single(knncf_handle* h, const QueryCall& call) {
     require_single_outputs(call);
     require_fitted(h, false);
-    if (call.mode == QB_EXPLAIN) {
+    if (explains(call.mode)) {
         require_explain_order(call.ex);
         KN_REQUIRE(call.m >= 0 && (call.m == 0 || call.pred_items), KNNCF_E_INVALID, "bad prediction arguments");
         require_explain_outputs(call.ex, call.m);
@@ -1461,7 +1484,7 @@ void do_query_single(knncf_handle* h, const QueryCall& call) {
     QueryCall q = call;
     q.users = &call.user; q.B = 1; q.counts = &c; q.statuses = &status;
     q.offsets = offsets; q.removed_offsets = removed_offsets; q.pred_offsets = pred_offsets;
-    const QueryFailure f = run_query_chunks(h, q, 1, q.mode == QB_EXPLAIN ? explain_batch_chunk(h, q.ex.cap) : 0);
+    const QueryFailure f = run_query_chunks(h, q, 1, explains(q.mode) ? query_explain_rows(batch_budget(h), q.ex.cap, q.mode == QB_EXPLAIN_ALL) : 0);
     if (f.query >= 0) throw Error(status, std::string("query: ") + f.reason);
     if (call.counts) *call.counts = c;
 }
@@ -2198,7 +2221,7 @@ int knncf_recommend(knncf_handle* h, int predictor, int32_t user, int32_t n, int
     });
 }
 
-// ---- the 24 query entry points: the rows of the call by name, then the mode's builder (api.cpp "one request type") ----------
+// ---- the 30 query entry points: the rows of the call by name, then the mode's builder (api.cpp "one request type") ----------
 // fold-in queries: a user outside the fit
 int knncf_query_neighbors(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
                           int32_t cap, int32_t* ids, double* sims, int32_t* count) {
@@ -2380,6 +2403,64 @@ int knncf_revise_explain_batch(knncf_handle* h, int predictor, const int32_t* us
                                        .ratings = ratings, .removed_offsets = removed_offsets, .removed_items = removed_items,
                                        .pred_offsets = pred_offsets, .pred_items = pred_items, .statuses = statuses}, predictor, {order,
                                        cap, raters, sims, devs, counts, sums, predictions}));
+}
+
+// explanations of Personalized query predictions: the explain calls' arguments without the predictor (QB_EXPLAIN_ALL)
+int knncf_query_explain_personalized(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
+                                     const int32_t* pred_items, int64_t m, int32_t order, int32_t cap, int32_t* raters, double* sims,
+                                     double* devs, int32_t* counts, double* sums, double* predictions) {
+    return query_single(h, explain_all_call({.family = QF_FOLD_IN, .items = items, .ratings = ratings, .pred_items = pred_items,
+                                            .user = user, .n_ratings = n_ratings, .m = m},
+                                            {order, cap, raters, sims, devs, counts, sums, predictions}));
+}
+
+int knncf_update_explain_personalized(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
+                                      const int32_t* pred_items, int64_t m, int32_t order, int32_t cap, int32_t* raters, double* sims,
+                                      double* devs, int32_t* counts, double* sums, double* predictions) {
+    return query_single(h, explain_all_call({.family = QF_UPDATE, .items = items, .ratings = ratings, .pred_items = pred_items,
+                                            .user = user, .n_ratings = n_ratings, .m = m},
+                                            {order, cap, raters, sims, devs, counts, sums, predictions}));
+}
+
+int knncf_revise_explain_personalized(knncf_handle* h, int32_t user, const int32_t* removed_items, int64_t n_removed,
+                                      const int32_t* items, const double* ratings, int64_t n_ratings, const int32_t* pred_items,
+                                      int64_t m, int32_t order, int32_t cap, int32_t* raters, double* sims, double* devs,
+                                      int32_t* counts, double* sums, double* predictions) {
+    return query_single(h, explain_all_call({.family = QF_REVISE, .items = items, .ratings = ratings, .removed_items = removed_items,
+                                            .pred_items = pred_items, .user = user, .n_ratings = n_ratings, .n_removed = n_removed,
+                                            .m = m},
+                                            {order, cap, raters, sims, devs, counts, sums, predictions}));
+}
+
+int knncf_query_explain_personalized_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                                           const double* ratings, int64_t n_queries, const int64_t* pred_offsets,
+                                           const int32_t* pred_items, int32_t order, int32_t cap, int32_t* raters, double* sims,
+                                           double* devs, int32_t* counts, double* sums, double* predictions, int32_t* statuses) {
+    return query_batch(h, explain_all_call({.family = QF_FOLD_IN, .users = users, .B = n_queries, .offsets = offsets, .items = items,
+                                           .ratings = ratings, .pred_offsets = pred_offsets, .pred_items = pred_items,
+                                           .statuses = statuses},
+                                           {order, cap, raters, sims, devs, counts, sums, predictions}));
+}
+
+int knncf_update_explain_personalized_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                                            const double* ratings, int64_t n_queries, const int64_t* pred_offsets,
+                                            const int32_t* pred_items, int32_t order, int32_t cap, int32_t* raters, double* sims,
+                                            double* devs, int32_t* counts, double* sums, double* predictions, int32_t* statuses) {
+    return query_batch(h, explain_all_call({.family = QF_UPDATE, .users = users, .B = n_queries, .offsets = offsets, .items = items,
+                                           .ratings = ratings, .pred_offsets = pred_offsets, .pred_items = pred_items,
+                                           .statuses = statuses},
+                                           {order, cap, raters, sims, devs, counts, sums, predictions}));
+}
+
+int knncf_revise_explain_personalized_batch(knncf_handle* h, const int32_t* users, const int64_t* removed_offsets,
+                                            const int32_t* removed_items, const int64_t* offsets, const int32_t* items,
+                                            const double* ratings, int64_t n_queries, const int64_t* pred_offsets,
+                                            const int32_t* pred_items, int32_t order, int32_t cap, int32_t* raters, double* sims,
+                                            double* devs, int32_t* counts, double* sums, double* predictions, int32_t* statuses) {
+    return query_batch(h, explain_all_call({.family = QF_REVISE, .users = users, .B = n_queries, .offsets = offsets, .items = items,
+                                           .ratings = ratings, .removed_offsets = removed_offsets, .removed_items = removed_items,
+                                           .pred_offsets = pred_offsets, .pred_items = pred_items, .statuses = statuses},
+                                           {order, cap, raters, sims, devs, counts, sums, predictions}));
 }
 
 int knncf_neighbors_save(knncf_handle* h, const char* path) {

@@ -403,6 +403,11 @@ struct QbExplainRows {
     int64_t r0, n;
 };
 void foldin_batch_explain(const Train& tr, QueryBatchScratch& bs, const QbExplainRows& rows, const ExplainCells& out, hipStream_t st);
+// after foldin_batch_fold_all (update as it was given there): the terms behind the Personalized predictions of the chunk's rows
+// [rows.r0, rows.r0 + rows.n) (rows.take and rows.E are not read), into rows [0, n) of `out` (every pointer set).  d_stage holds
+// 20 * rows.n * out.cap bytes and is read and written with KNNCF_EXPLAIN_BY_WEIGHT only.  One launch.
+void foldin_batch_explain_all(const Train& tr, const PersonalRows& pr, QueryBatchScratch& bs, const QbExplainRows& rows, bool update,
+                              const ExplainCells& out, double* d_stage, hipStream_t st);
 // d_items / d_preds [C][n]: slot b's first min(n, I - known) recommendations (the rest untouched)
 void foldin_batch_recommend(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, int32_t n, int32_t* d_items,
                             double* d_preds, hipStream_t st);

@@ -11,15 +11,9 @@
 //           product and magnitude through LDS, added serially in file order — zero similarities add +-0.0 to sums that start
 //           at +0.0.  The non-zero entries are counted by ballot / mbcnt: the running count is the term's place in the fold.
 //           SUM_ORDER stores a term while its place is below cap.  BY_WEIGHT counts the top byte of |s| into an LDS histogram.
-//   select  (BY_WEIGHT, count > cap) radix select on the bit pattern of |s| (non-negative doubles order as unsigned integers; the
-//           sign bit is cleared, so the top byte is below 128): per 8-bit digit, from the top, the histogram of the entries that
-//           agree with the digits chosen so far, a scan from bin 255 down to the bin that holds the cap-th largest, descent into
-//           it.  It stops as soon as that bin holds no more than what is still wanted (everything >= the prefix is taken) or
-//           after the eighth digit (the prefix is the threshold magnitude t, and `want` of the entries equal to t are taken).
-//   emit    one more pass writes, in place order, every term with |s| > t and the FIRST `want` terms with |s| == t — the
-//           reference's stable order among ties — into the row's staging cells: min(count, cap) terms, places ascending.
-//   rank    the staged terms by counting under (|s| descending, staged index ascending), the strict total order of k_explain;
-//           each goes to its rank in the output row.
+//   select / emit / rank   (BY_WEIGHT) the steps of explain_select.h over this row's raters (FitTerms below): the radix select
+//           of the cap heaviest when count > cap, the staging of the selected terms in place order, their rank by counting.
+//           k_qb_explain_all (foldin.hip) runs the same steps over a query's terms.
 // Cost per row of L raters, C = count of terms, m = min(C, cap), in wave steps: the walk is ceil(L / 64) loads + L serial
 // additions (k_fold_rows's); BY_WEIGHT adds at most 7 histogram passes + 1 emit pass of ceil(L / 256) four-deep load groups each
 // (none of the 7 when C <= cap) and ceil(m / 256) * m compare steps for the rank.  Nothing grows with L^2; cap >= C ranks all C
@@ -31,13 +25,11 @@
 // the staged number.  Row w < n of the launch owns cells [w * cap, (w + 1) * cap) of the outputs and of the staging.
 #include <math.h>
 
-#include "engine.h"
+#include "explain_select.h"
 
 namespace knncf {
 
 static constexpr int XA_WAVES = 4;  // rows per workgroup
-static constexpr int XA_DEEP = 4;   // trips of 64 whose loads a select / emit pass has in flight together
-static constexpr int XA_OWN = 4;    // staged terms per lane that one sweep over the staged keys ranks
 
 struct ExplainAllArgs {
     const uint32_t* order;  // row w of the launch is row order[w] of du / di
@@ -53,43 +45,22 @@ struct ExplainAllArgs {
     double global_avg;
     const int32_t* uid;     // raw id of a dense user
     ExplainCells out;       // rows [0, n) of the launch
-    double* st_sim;         // BY_WEIGHT staging, the layout of out's term arrays
-    double* st_dev;
-    int32_t* st_rater;
+    ExplainStage st;        // BY_WEIGHT staging
 };
 
-__device__ __forceinline__ void wave_sync() {
-    // lanes of one wave exchange data through LDS: order the accesses for the compiler (the LDS queue is in order per wave)
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ int32_t lanes_below(unsigned long long mask) {
-    return (int32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-
-// |s| as an unsigned integer: the order of the magnitudes; 0 for +-0.0, which is no term
-__device__ __forceinline__ uint64_t mag_key(double s) { return (uint64_t)__double_as_longlong(s) & 0x7fffffffffffffffull; }
-
-// f(c0, rater, s) for every trip of 64 raters [c0, c0 + 64) of [rb, re) in file order, until it returns false (the same in every
-// lane); a lane past the segment's end gets rater 0 and s = 0.0.  XA_DEEP trips' loads are issued together
-template <class F>
-__device__ __forceinline__ void walk_raters(int64_t rb, int64_t re, int lane, const int32_t* pf_user, const double* row, F&& f) {
-    for (int64_t c0 = rb; c0 < re; c0 += 64 * XA_DEEP) {
-        int32_t v[XA_DEEP];
-        double s[XA_DEEP];
-#pragma unroll
-        for (int k = 0; k < XA_DEEP; ++k) v[k] = (c0 + 64 * k + lane < re) ? pf_user[c0 + 64 * k + lane] : 0;
-#pragma unroll
-        for (int k = 0; k < XA_DEEP; ++k) s[k] = (c0 + 64 * k + lane < re) ? row[v[k]] : 0.0;
-#pragma unroll
-        for (int k = 0; k < XA_DEEP; ++k) {
-            if (c0 + 64 * k < re) {  // (uniform)
-                if (!f(c0 + 64 * k, v[k], s[k])) return;
-            }
-        }
-    }
-}
+// the term reader of explain_select.h over a fitted row: position p is entry p of pf_user / pf_dev, [lo, hi) the item's raters in
+// file order
+struct FitTerms {
+    int64_t lo, hi;
+    const int32_t* pf_user;
+    const double* pf_dev;
+    const double* row;       // the user's exact similarity row
+    const int32_t* uid;
+    __device__ __forceinline__ int32_t rater(int64_t p) const { return pf_user[p]; }
+    __device__ __forceinline__ double sim(int64_t, int32_t v) const { return row[v]; }
+    __device__ __forceinline__ double dev(int64_t p, int32_t) const { return pf_dev[p]; }
+    __device__ __forceinline__ int32_t raw(int64_t, int32_t v) const { return uid[v]; }
+};
 
 __global__ void __launch_bounds__(XA_WAVES * 64) k_explain_all(ExplainAllArgs A, int64_t n) {
     __shared__ double s_prod[XA_WAVES][64], s_abs[XA_WAVES][64];
@@ -164,102 +135,8 @@ __global__ void __launch_bounds__(XA_WAVES * 64) k_explain_all(ExplainAllArgs A,
         const double wsd = (den > 0) ? num / den : 0.0;
         p = combine(ua, wsd);
         if (by_weight && total > 0) {
-            const int32_t m = min(total, cap);
-            // ---- select: every key >= ge is taken, and the first take_eq of those equal to eq
-            uint64_t ge = 1, eq = 0;
-            int32_t take_eq = 0;
-            if (total > cap) {
-                uint64_t prefix = 0;
-                int32_t want = cap;  // 1 <= want <= the entries that agree with prefix, throughout
-                for (int d = 0; d < 8; ++d) {
-                    const int shift = 56 - 8 * d;
-                    if (d > 0) {  // (the top digit was counted by the walk)
-                        for (int b = lane; b < 256; b += 64) hist[b] = 0;
-                        wave_sync();
-                        walk_raters(rb, re, lane, A.pf_user, row, [&](int64_t, int32_t, double x) {
-                            const uint64_t key = mag_key(x);
-                            if (key != 0 && (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(uint32_t)(key >> shift) & 255u], 1u);
-                            return true;
-                        });
-                    }
-                    wave_sync();
-                    int b = 255;
-                    int32_t above = 0;  // entries of the bins above b
-                    while (b > 0 && above + (int32_t)hist[b] < want) {  // (uniform: every lane reads the same bins)
-                        above += (int32_t)hist[b];
-                        --b;
-                    }
-                    const int32_t bucket = (int32_t)hist[b];
-                    want -= above;
-                    prefix |= (uint64_t)b << shift;
-                    if (bucket <= want) {  // the whole bin is wanted: no need to tell its entries apart
-                        ge = prefix;
-                        break;
-                    }
-                    if (d == 7) {
-                        ge = prefix + 1;
-                        eq = prefix;
-                        take_eq = want;
-                    }
-                    wave_sync();  // (the bins are read before the next digit clears them)
-                }
-            }
-            // ---- emit into the staging row, in place order
-            int32_t staged = 0, eq_seen = 0;
-            walk_raters(rb, re, lane, A.pf_user, row, [&](int64_t c0, int32_t x, double sx) {
-                const uint64_t key = mag_key(sx);
-                const bool is_eq = take_eq > 0 && key == eq;  // (eq != 0 when take_eq > 0)
-                const unsigned long long eqm = __ballot(is_eq);
-                const bool em = key != 0 && (key >= ge || (is_eq && eq_seen + lanes_below(eqm) < take_eq));
-                const unsigned long long emm = __ballot(em);
-                if (em) {
-                    const int32_t at = staged + lanes_below(emm);
-                    if (at < m) {
-                        A.st_sim[ob + at] = sx;
-                        A.st_dev[ob + at] = A.pf_dev[c0 + lane];
-                        A.st_rater[ob + at] = A.uid[x];
-                    }
-                }
-                staged += __popcll(emm);
-                eq_seen += __popcll(eqm);
-                return staged < m;  // (uniform) nothing further is wanted
-            });
-            staged = min(staged, m);
-            // the staged cells were written by other lanes of this wave: complete the stores before they are read back
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-            // ---- rank: lane l owns staged terms e0 + l, e0 + 64 + l, ...; every lane streams all staged magnitudes, 64 at a
-            // time through LDS (broadcast reads), and counts the terms that go first
-            for (int32_t e0 = 0; e0 < staged; e0 += 64 * XA_OWN) {
-                double a[XA_OWN];
-                uint32_t rank[XA_OWN];
-#pragma unroll
-                for (int k = 0; k < XA_OWN; ++k) {
-                    const int32_t e = e0 + 64 * k + lane;
-                    a[k] = (e < staged) ? fabs(A.st_sim[ob + e]) : 0.0;  // (past the end: precedes nothing, is not written)
-                    rank[k] = 0;
-                }
-                for (int32_t t0 = 0; t0 < staged; t0 += 64) {
-                    sa[lane] = (t0 + lane < staged) ? fabs(A.st_sim[ob + t0 + lane]) : 0.0;
-                    wave_sync();
-                    const int tm = min(64, staged - t0);
-                    for (int f = 0; f < tm; ++f) {
-                        const double b = sa[f];
-#pragma unroll
-                        for (int k = 0; k < XA_OWN; ++k) rank[k] += (uint32_t)(b > a[k] || (b == a[k] && t0 + f < e0 + 64 * k + lane));
-                    }
-                    wave_sync();
-                }
-#pragma unroll
-                for (int k = 0; k < XA_OWN; ++k) {
-                    const int32_t e = e0 + 64 * k + lane;
-                    if (e < staged && rank[k] < (uint32_t)staged) {
-                        A.out.raters[ob + rank[k]] = A.st_rater[ob + e];
-                        A.out.sims[ob + rank[k]] = A.st_sim[ob + e];
-                        A.out.devs[ob + rank[k]] = A.st_dev[ob + e];
-                    }
-                }
-            }
+            const FitTerms rd{rb, re, A.pf_user, A.pf_dev, row, A.uid};
+            explain_by_weight(rd, lane, total, A.out, A.st, ob, hist, sa);
         }
     }
     if (lane == 0) {
@@ -279,8 +156,7 @@ void launch_explain_all(const Train& tr, const PersonalRows& pr, int64_t n_rows,
     A.i_ptr = tr.i_ptr.p; A.pf_user = pr.pf_user.p; A.pf_dev = pr.pf_dev.p;
     A.user_avg = tr.user_avg.p; A.global_avg = tr.global_avg; A.uid = tr.uid.p;
     A.out = out;
-    const size_t cells = (size_t)n_rows * (size_t)out.cap;
-    A.st_sim = d_stage; A.st_dev = d_stage + cells; A.st_rater = reinterpret_cast<int32_t*>(d_stage + 2 * cells);
+    A.st = explain_stage(d_stage, n_rows, out.cap);
     KN_TRACE_DISPATCH("explain_all order=%d cap=%d rows=%lld", (int)out.order, (int)out.cap, (long long)n_rows);
     k_explain_all<<<(unsigned)ceil_div(n_rows, XA_WAVES), XA_WAVES * 64, 0, st>>>(A, n_rows);
     KN_HIP(hipGetLastError());

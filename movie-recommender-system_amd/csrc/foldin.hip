@@ -33,11 +33,14 @@
 //   k_qb_self_keys / sort / k_qb_self_sim / k_qb_sim_transpose / k_qb_fold_all / k_qb_pred<false> / k_qb_pick_all
 //                                       (KNNCF_PRED_PERSONALIZED, instead of everything from the top-k to k_qb_pred) S(u, u), the
 //                                       similarities side by side, one fold per (slot, item) over ALL raters of the item
+//   k_qb_explain_all                    (knncf_*_explain_personalized*) the terms of those folds for requested (slot, item) rows:
+//                                       one wave per row walks the item's raters, the slot's own term among them, and picks the
+//                                       cap heaviest with the steps of explain_select.h
 #include <math.h>
 
 #include <algorithm>
 
-#include "engine.h"
+#include "explain_select.h"
 
 namespace knncf {
 
@@ -1074,20 +1077,53 @@ __global__ void __launch_bounds__(TPB) k_qb_sim_transpose(int32_t U, int32_t C, 
     for (int vv = y; vv < 64 && v0 + vv < U; vv += TPB / 64) simT[(v0 + vv) * stride + x] = tile[x][vv];
 }
 
+// Slot b's own rating of dense item i as a term of aug (the Personalized mode; k_qb_fold_all folds it, k_qb_explain_all lists
+// it).  The slot rates i in aug when i's bit of its bitmap is set; its deviation ON AUG is dev_d at the bit's rank.  The row is a
+// SURVIVING TRAIN ROW when its given position is below the slot's number of surviving train rows (they come first: k_qb_seed /
+// k_qb_seed_rv; ao == nullptr, a fold-in chunk, has none): the term (suu[b], dev) then stands at the file place of the rater
+// self[b] (own_s / own_dev).  Otherwise it is an additional row — any row of a fold-in user, a re-rated item — and the term
+// comes LAST, after every train row (last, last_s / last_dev).  With neither, the rater self[b] of the item, if there is one,
+// is a removed or re-rated train row: own_s = own_dev = 0.0, no term.
+// Bounds: bit_rank of a set bit of slot b is below the slot's number of known items <= its rows, so o + r is inside the slot's
+// extent of dev_d / given_d.
+struct QbOwnTerm {
+    double own_s = 0.0, own_dev = 0.0, last_s = 0.0, last_dev = 0.0;
+    bool last = false;
+};
+__device__ __forceinline__ QbOwnTerm qb_own_term(int32_t b, int32_t i, int64_t W, const unsigned long long* __restrict__ bits,
+                                                 const int64_t* __restrict__ rank, const int64_t* __restrict__ qo,
+                                                 const int64_t* __restrict__ ao, const double* __restrict__ dev_d,
+                                                 const int32_t* __restrict__ given_d, const double* __restrict__ suu) {
+    QbOwnTerm t;
+    const unsigned long long* mb = bits + (int64_t)b * W;
+    if ((mb[i >> 6] >> (i & 63)) & 1ull) {
+        const int64_t o = qo[b];
+        const int32_t r = bit_rank(mb, rank + (int64_t)b * (W + 1), i);
+        const int64_t survivors = ao ? (qo[b + 1] - o) - (ao[b + 1] - ao[b]) : 0;
+        if (given_d[o + r] < survivors) {
+            t.own_s = suu[b];
+            t.own_dev = dev_d[o + r];
+        } else {
+            t.last = true;
+            t.last_s = suu[b];
+            t.last_dev = dev_d[o + r];
+        }
+    }
+    return t;
+}
+
 // The fold of a chunk: ONE WAVE PER TRAIN ITEM, LANE b OWNS SLOT b (the layout of k_query_sim_dual).  The wave walks the item's
 // raters in file order (pf_user / pf_dev, 64 per coalesced load), one wave-uniform entry at a time; every lane reads its own
 // similarity to that rater from the transposed row (one coalesced read per entry) and runs num = num + dev * s, den = den +
 // |s| in its own registers: the left folds of :520-524, multiply and add separate.  The similarity loads do not depend on the
 // add chains, so FA_AHEAD of them are issued before the adds that use them.
-// The slot's own user as a rater (self[b]): its train row SURVIVES in aug when the slot rates the item at a given position
-// below its number of surviving train rows (they come first: k_qb_seed / k_qb_seed_rv) — the term is then the slot's
-// deviation ON AUG (the mean changed) with S(u, u), at the row's file place.  A removed or re-rated train row is no term: it
-// adds dev 0.0 * s 0.0, an identity (the sums start at +0.0 and cannot become -0.0).  A slot that rates the item through an
-// additional row has that term last, after every train row.  Longest items first (pop_item).
+// The slot's own user as a rater (self[b]) is qb_own_term's: a surviving train row is folded at its file place with the slot's
+// deviation ON AUG (the mean changed) and S(u, u); a removed or re-rated train row is no term: it adds dev 0.0 * s 0.0, an
+// identity (the sums start at +0.0 and cannot become -0.0); a slot that rates the item through an additional row has that
+// term last, after every train row.  Longest items first (pop_item).
 // Bounds.  w < I, i = pop_item[w] is a dense item of [0, I); entries lie in [i_ptr[i], i_ptr[i + 1]) within [0, n); pf_user is
-// a dense user of [0, U), col < stride, so the read cell is inside simT [U][stride].  bit_rank of a set bit of slot b is below
-// the slot's number of known items <= its rows, so o + r is inside the slot's extent of dev_d / given_d.  Lanes >= C read
-// column 0 and write nothing.
+// a dense user of [0, U), col < stride, so the read cell is inside simT [U][stride].  Lanes >= C read column 0 and write
+// nothing.
 static constexpr int FA_WAVES = 4;  // waves (items) per workgroup
 static constexpr int FA_AHEAD = 8;  // similarity loads in flight per lane
 __global__ void __launch_bounds__(FA_WAVES * 64) k_qb_fold_all(int32_t I, int32_t C, int32_t stride, int64_t W,
@@ -1107,25 +1143,13 @@ __global__ void __launch_bounds__(FA_WAVES * 64) k_qb_fold_all(int32_t I, int32_
     const bool live = lane < C;
     const int col = live ? lane : 0;
     int32_t me = -1;
-    double own_s = 0.0, own_dev = 0.0, last_s = 0.0, last_dev = 0.0;
-    bool last = false;
+    QbOwnTerm own;
     if (live) {
         if (self) me = self[lane];
-        const unsigned long long* mb = bits + (int64_t)lane * W;
-        if ((mb[i >> 6] >> (i & 63)) & 1ull) {
-            const int64_t o = qo[lane];
-            const int32_t r = bit_rank(mb, rank + (int64_t)lane * (W + 1), i);
-            const int64_t survivors = ao ? (qo[lane + 1] - o) - (ao[lane + 1] - ao[lane]) : 0;
-            if (given_d[o + r] < survivors) {
-                own_s = suu[lane];
-                own_dev = dev_d[o + r];
-            } else {
-                last = true;
-                last_s = suu[lane];
-                last_dev = dev_d[o + r];
-            }
-        }
+        own = qb_own_term(lane, i, W, bits, rank, qo, ao, dev_d, given_d, suu);
     }
+    const double own_s = own.own_s, own_dev = own.own_dev, last_s = own.last_s, last_dev = own.last_dev;
+    const bool last = own.last;
     double a = 0.0, d = 0.0;
     const int64_t rb = i_ptr[i], re = i_ptr[i + 1];
     for (int64_t base = rb; base < re; base += 64) {
@@ -1201,6 +1225,163 @@ __global__ void k_qb_pick_all(int64_t m, const int32_t* __restrict__ items, cons
     out[j] = avg + w * scale_fn(avg + w, avg);
 }
 
+// ---- explanations of Personalized query predictions (knncf_*_explain_personalized*; DESIGN.md "Explanations of Personalized
+// query predictions") --------------------------------------------------------------------------------------------------------
+// After foldin_batch_fold_all the chunk holds everything a row (slot b, item) needs: bs.sim[b][v] = S(u, v) for every train
+// user, suu[b] = S(u, u) on aug, the fold results num / den / pred [C][I].  ONE WAVE PER REQUESTED ROW.
+//   sums, prediction   are not recomputed: a dense item's are the cell (b, c) of num / den / pred, as k_qb_fold_all and
+//           k_qb_pred<false> wrote them, so the prediction is the predict call's by construction; an item without a dense id that
+//           the slot rates has k_qb_pick_all's one-term fold, any other item without a dense id (0, 0) and the mean.
+//   terms   QueryTerms below, a reader of explain_select.h: positions [rb, re) = [i_ptr[c], i_ptr[c + 1]) are the item's raters in
+//           file order with s = sim[b * U + rater], EXCEPT the rater self[b], whose cell holds S(u, u) whether or not its train
+//           row survives: it takes qb_own_term's (own_s, own_dev) — the term on aug at its file place, or (0.0, 0.0), no term, for
+//           a removed or re-rated row.  When the slot rates the item through an additional row, position re is one more term:
+//           (the query's raw user id users[b], suu[b], the slot's deviation).  An item without a dense id has rb = re = 0.
+//   walk    classifies and counts (ballot / mbcnt: the running count of non-zero similarities is the term's place in the
+//           fold); SUM_ORDER stores a term while its place is below cap, BY_WEIGHT counts the top byte of |s| into the LDS
+//           histogram.  No serial add chain.  Then explain_by_weight: select (count > cap only), emit, rank.
+// Bounds.  Row w < n of the launch is row r0 + w of items / slot (the host uploads every row of the chunk) and owns cells
+// [w * cap, (w + 1) * cap) of the outputs and of the staging.  slot b < C; c is a dense item of [0, I) or -1.  Every pf_user /
+// pf_dev read is at a position p with rb <= p < re, inside [i_ptr[c], i_ptr[c + 1]); every similarity read is at b * U + v with v
+// a rater read there, a dense user of [0, U); uid[v] likewise.  o + r of qb_own_term is inside the slot's extent by bit_rank's
+// bound.  The search of a raw item runs over the slot's rows [qo[b], qo[b + 1]) of q_items / q_dev.  A term is stored at a
+// place < min(count, cap) inside row w's cap cells, checked at the store; lanes past the sequence contribute similarity 0.0.
+static constexpr int QXA_WAVES = 4;  // rows per workgroup
+
+struct QbExplainAllArgs {
+    const int32_t* items;  // [rows of the chunk] requested raw item and slot, as k_qb_pick_all takes them
+    const int32_t* slot;
+    const int32_t* i_table;
+    int32_t i_cells;
+    const uint32_t* ikeys;
+    int32_t I, U;
+    int64_t W;
+    const int64_t* i_ptr;
+    const int32_t* pf_user;
+    const double* pf_dev;
+    const double* sim;      // [C][U]
+    const unsigned long long* bits;
+    const int64_t* rank;
+    const int64_t* qo;
+    const int64_t* ao;      // null: a fold-in chunk
+    const int32_t* self;    // null: a fold-in chunk
+    const double* dev_d;
+    const int32_t* given_d;
+    const double* suu;      // [C]
+    const int32_t* users;   // [C] raw id of the slot's user (a fold-in user has no dense id)
+    const int32_t* q_items; // [rows of the slots] raw items and deviations in the given order
+    const double* q_dev;
+    const int32_t* uid;     // raw id of a dense user
+    const double* num;      // [C][I]
+    const double* den;
+    const double* pred;
+    const double* scal;     // [C][2]
+    ExplainCells out;       // rows [0, n) of the launch
+    ExplainStage st;        // BY_WEIGHT staging
+};
+
+struct QueryTerms {
+    int64_t lo, hi, re;      // train raters [lo, re), hi = re + (the slot's additional row on the item ? 1 : 0)
+    const int32_t* pf_user;
+    const double* pf_dev;
+    const double* row;       // sim + b * U
+    const int32_t* uid;
+    int32_t me, quser;       // self[b] (-1: not in the fit), users[b]
+    double own_s, own_dev, last_s, last_dev;
+    __device__ __forceinline__ int32_t rater(int64_t p) const { return p < re ? pf_user[p] : 0; }
+    __device__ __forceinline__ double sim(int64_t p, int32_t v) const { return p >= re ? last_s : (v == me ? own_s : row[v]); }
+    __device__ __forceinline__ double dev(int64_t p, int32_t v) const { return p >= re ? last_dev : (v == me ? own_dev : pf_dev[p]); }
+    __device__ __forceinline__ int32_t raw(int64_t p, int32_t v) const { return p >= re ? quser : uid[v]; }
+};
+
+__global__ void __launch_bounds__(QXA_WAVES * 64) k_qb_explain_all(QbExplainAllArgs A, int64_t r0, int64_t n) {
+    __shared__ double s_abs[QXA_WAVES][64];
+    __shared__ uint32_t s_hist[QXA_WAVES][256];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (wave-uniform: the row, its slot and its item are scalars)
+    const int64_t w = (int64_t)blockIdx.x * QXA_WAVES + wave;
+    if (w >= n) return;
+    const int64_t j = r0 + w;
+    const int32_t it = A.items[j], b = A.slot[j];
+    const int32_t cap = A.out.cap;
+    int32_t c;
+    if (A.i_cells > 0) c = (it >= 0 && it < A.i_cells) ? A.i_table[it] : -1;
+    else c = dense_lookup(A.ikeys, A.I, it);
+    QueryTerms rd{};
+    rd.row = A.sim + (int64_t)b * A.U;
+    rd.uid = A.uid;
+    rd.me = A.self ? A.self[b] : -1;
+    rd.quser = A.users[b];
+    double num, den, p;
+    if (c >= 0) {
+        const QbOwnTerm own = qb_own_term(b, c, A.W, A.bits, A.rank, A.qo, A.ao, A.dev_d, A.given_d, A.suu);
+        const int64_t rb = A.i_ptr[c], re = A.i_ptr[c + 1];
+        rd.lo = rb;
+        rd.re = re;
+        rd.hi = re + (own.last ? 1 : 0);
+        rd.pf_user = A.pf_user;
+        rd.pf_dev = A.pf_dev;
+        rd.own_s = own.own_s; rd.own_dev = own.own_dev; rd.last_s = own.last_s; rd.last_dev = own.last_dev;
+        const int64_t cell = (int64_t)b * A.I + c;
+        num = A.num[cell];
+        den = A.den[cell];
+        p = A.pred[cell];
+    } else {
+        // no dense id: the slot's own row on the raw item, if it has one, is the only rating of the item in aug
+        int64_t at = -1;
+        for (int64_t x = A.qo[b] + lane; x < A.qo[b + 1]; x += 64)
+            if (A.q_items[x] == it) at = x;
+        const unsigned long long found = __ballot(at >= 0);
+        num = 0.0;
+        den = 0.0;
+        if (found) {
+            const double s = A.suu[b];
+            const double dv = __shfl(at >= 0 ? A.q_dev[at] : 0.0, __ffsll((long long)found) - 1);
+            rd.hi = 1;  // (lo = re = 0: position 0 is the slot's own row)
+            rd.last_s = s;
+            rd.last_dev = dv;
+            num = num + dv * s;  // (k_qb_pick_all's one-term fold)
+            den = den + fabs(s);
+        }
+        const double avg = A.scal[2 * b];
+        const double wsd = den > 0 ? num / den : 0.0;
+        p = avg + wsd * scale_fn(avg + wsd, avg);
+    }
+    const int64_t ob = w * (int64_t)cap;
+    const bool by_weight = A.out.order == KNNCF_EXPLAIN_BY_WEIGHT && cap > 0;
+    uint32_t* hist = s_hist[wave];
+    if (by_weight) {
+        for (int x = lane; x < 256; x += 64) hist[x] = 0;
+        wave_sync();
+    }
+    int32_t total = 0;
+    walk_terms(rd, lane, [&](int64_t p0, int32_t v, double s) {
+        const bool nz = s != 0.0;
+        const unsigned long long hit = __ballot(nz);
+        if (nz) {
+            if (by_weight) {
+                atomicAdd(&hist[(uint32_t)(mag_key(s) >> 56)], 1u);
+            } else {
+                const int32_t place = total + lanes_below(hit);
+                if (place < cap) {
+                    A.out.raters[ob + place] = rd.raw(p0 + lane, v);
+                    A.out.sims[ob + place] = s;
+                    A.out.devs[ob + place] = rd.dev(p0 + lane, v);
+                }
+            }
+        }
+        total += __popcll(hit);
+        return true;
+    });
+    if (by_weight && total > 0) explain_by_weight(rd, lane, total, A.out, A.st, ob, hist, s_abs[wave]);
+    if (lane == 0) {
+        A.out.counts[w] = total;
+        A.out.sums[2 * w] = num;
+        A.out.sums[2 * w + 1] = den;
+        A.out.pred[w] = p;
+    }
+}
+
 void foldin_batch_fold_all(const Train& tr, const PersonalRows& pr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, int64_t n,
                            bool update, hipStream_t st) {
     const int32_t U = tr.U, I = tr.I;
@@ -1256,6 +1437,27 @@ void foldin_batch_explain(const Train& tr, QueryBatchScratch& bs, const QbExplai
     A.raters = out.raters; A.sims = out.sims; A.devs = out.devs; A.counts = out.counts; A.sums = out.sums; A.out_pred = out.pred;
     KN_TRACE_DISPATCH("qb_explain order=%d", (int)out.order);
     k_qb_explain<<<(unsigned)ceil_div(n, QBX_WAVES), QBX_WAVES * 64, 0, st>>>(A, rows.r0, n);
+    KN_HIP(hipGetLastError());
+}
+
+void foldin_batch_explain_all(const Train& tr, const PersonalRows& pr, QueryBatchScratch& bs, const QbExplainRows& rows, bool update,
+                              const ExplainCells& out, double* d_stage, hipStream_t st) {
+    const int64_t n = rows.n;
+    if (n <= 0) return;
+    QbExplainAllArgs A{};
+    A.items = rows.d_items; A.slot = rows.d_slot;
+    A.i_table = tr.i_table.p; A.i_cells = table_cells(tr); A.ikeys = tr.ikeys.p;
+    A.I = tr.I; A.U = tr.U; A.W = ceil_div(tr.I, 64);
+    A.i_ptr = tr.i_ptr.p; A.pf_user = pr.pf_user.p; A.pf_dev = pr.pf_dev.p;
+    A.sim = bs.sim.p; A.bits = (const unsigned long long*)bs.bits.p; A.rank = bs.rank.p; A.qo = bs.qo.p;
+    A.ao = update ? bs.ao.p : nullptr; A.self = update ? bs.self.p : nullptr;
+    A.dev_d = bs.dev_d.p; A.given_d = bs.given_d.p; A.suu = bs.suu.p; A.users = bs.users.p;
+    A.q_items = bs.items.p; A.q_dev = bs.dev.p; A.uid = tr.uid.p;
+    A.num = bs.num.p; A.den = bs.den.p; A.pred = bs.pred.p; A.scal = bs.scal.p;
+    A.out = out;
+    A.st = explain_stage(d_stage, n, out.cap);
+    KN_TRACE_DISPATCH("qb_explain_all order=%d cap=%d rows=%lld", (int)out.order, (int)out.cap, (long long)n);
+    k_qb_explain_all<<<(unsigned)ceil_div(n, QXA_WAVES), QXA_WAVES * 64, 0, st>>>(A, rows.r0, n);
     KN_HIP(hipGetLastError());
 }
 

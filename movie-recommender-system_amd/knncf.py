@@ -127,7 +127,10 @@ EXPORTS = [
     "knncf_revise_neighbors", "knncf_revise_predict", "knncf_revise_recommend",
     "knncf_revise_neighbors_batch", "knncf_revise_predict_batch", "knncf_revise_recommend_batch",
     "knncf_query_explain", "knncf_update_explain", "knncf_revise_explain",
-    "knncf_query_explain_batch", "knncf_update_explain_batch", "knncf_revise_explain_batch", "knncf_predict_batch",
+    "knncf_query_explain_batch", "knncf_update_explain_batch", "knncf_revise_explain_batch",
+    "knncf_query_explain_personalized", "knncf_update_explain_personalized", "knncf_revise_explain_personalized",
+    "knncf_query_explain_personalized_batch", "knncf_update_explain_personalized_batch", "knncf_revise_explain_personalized_batch",
+    "knncf_predict_batch",
     "knncf_predict_batch_device", "knncf_mae", "knncf_mae_device", "knncf_mae_sweep", "knncf_mae_sweep_device", "knncf_shard_view_get",
     "knncf_shard_commit", "knncf_get_timings", "knncf_reset_timings", "knncf_reset_neighbors",
     "knncf_set_k", "knncf_load_file", "knncf_load_file_cached", "knncf_free_ratings", "knncf_load_personal", "knncf_free_personal", "knncf_neighbors_save", "knncf_neighbors_load",
@@ -226,10 +229,13 @@ def load_library():
         terms = [C.c_int32, C.c_int32, _i32p, _f64p, _f64p, _i32p, _f64p, _f64p]
         f("explain").argtypes = f("predict").argtypes[:-1] + terms
         f("explain_batch").argtypes = f("predict_batch").argtypes[:-2] + terms + [_i32p]
+        # the Personalized explanations: the explain lists without the predictor
+        f("explain_personalized").argtypes = f("explain").argtypes[:1] + f("explain").argtypes[2:]
+        f("explain_personalized_batch").argtypes = f("explain_batch").argtypes[:1] + f("explain_batch").argtypes[2:]
     # revise queries: the update argument lists with the removals in front of the additional rows
     for name, at, single in (("neighbors", 2, True), ("predict", 3, True), ("recommend", 3, True), ("explain", 3, True),
-                             ("neighbors_batch", 2, False), ("predict_batch", 3, False), ("recommend_batch", 3, False),
-                             ("explain_batch", 3, False)):
+                             ("explain_personalized", 2, True), ("neighbors_batch", 2, False), ("predict_batch", 3, False),
+                             ("recommend_batch", 3, False), ("explain_batch", 3, False), ("explain_personalized_batch", 2, False)):
         base = getattr(L, f"knncf_update_{name}").argtypes
         getattr(L, f"knncf_revise_{name}").argtypes = base[:at] + ([_i32p, C.c_int64] if single else [_i64p, _i32p]) + base[at:]
     L.knncf_predict_batch.argtypes = [C.c_void_p, C.c_int, _i32p, _i32p, C.c_int64, _f64p]
@@ -683,30 +689,45 @@ class Engine:
         return (p(raters.reshape(-1), _i32p), p(sims.reshape(-1), _f64p), p(devs.reshape(-1), _f64p), p(counts, _i32p),
                 p(sums.reshape(-1), _f64p), p(preds, _f64p))
 
-    def _explain_q(self, fam, user, items, ratings, pred_items, cap, order, removed=None):
+    @staticmethod
+    def _explain_entry(fam, tail, predictor):
+        """the explain entry point of a family and its leading predictor argument: knncf_*_explain* takes PRED_KNN,
+        knncf_*_explain_personalized* (PRED_PERSONALIZED) has no predictor argument.  ValueError for any other predictor"""
+        if isinstance(predictor, (bool, np.bool_)) or not isinstance(predictor, (int, np.integer)) or predictor not in (PRED_KNN, PRED_PERSONALIZED):
+            raise ValueError("predictor must be PRED_KNN or PRED_PERSONALIZED")
+        if predictor == PRED_PERSONALIZED:
+            return f"knncf_{fam}_explain_personalized{tail}", ()
+        return f"knncf_{fam}_explain{tail}", (PRED_KNN,)
+
+    def _explain_q(self, fam, user, items, ratings, pred_items, cap, order, removed=None, predictor=PRED_KNN):
         cap, order = self._explain_args(cap, order)
+        entry, lead = self._explain_entry(fam, "", predictor)
         q, it, rt = self._query_rows(user, items, ratings, allow_empty=fam != "query")
         rm = self._rm_args(fam, removed)
         pi = self._pred_items(pred_items)
         out = self._explain_out(len(pi), cap)
         p = self._ptr
-        self._check(getattr(self._lib, f"knncf_{fam}_explain")(self._h, PRED_KNN, q, *rm, p(it, _i32p), p(rt, _f64p), len(it),
-                                                               p(pi, _i32p), len(pi), order, cap, *self._explain_ptrs(out)))
+        self._check(getattr(self._lib, entry)(self._h, *lead, q, *rm, p(it, _i32p), p(rt, _f64p), len(it),
+                                              p(pi, _i32p), len(pi), order, cap, *self._explain_ptrs(out)))
         return out
 
-    def explain_for(self, user, items, ratings, pred_items, cap, order=EXPLAIN_SUM_ORDER):
+    def explain_for(self, user, items, ratings, pred_items, cap, order=EXPLAIN_SUM_ORDER, predictor=PRED_KNN):
         """The terms behind predict_for(user, items, ratings, pred_items) (knncf_query_explain), one row per requested item:
         (raters [m, cap] int32, sims [m, cap], devs [m, cap], counts [m] int32, sums [m, 2], predictions [m]); the cells past a
-        row's min(count, cap) terms are -1 / nan.  predictions is predict_for's answer bit for bit."""
-        return self._explain_q("query", user, items, ratings, pred_items, cap, order)
+        row's min(count, cap) terms are -1 / nan.  predictions is predict_for's answer bit for bit.
+        predictor=PRED_PERSONALIZED (knncf_query_explain_personalized): the terms behind predict_for(..., predictor=
+        PRED_PERSONALIZED) — every rater of the item in aug with a non-zero similarity, the user itself among them."""
+        return self._explain_q("query", user, items, ratings, pred_items, cap, order, predictor=predictor)
 
-    def explain_with(self, user, items, ratings, pred_items, cap, order=EXPLAIN_SUM_ORDER):
-        """The terms behind predict_with(...) (knncf_update_explain): as explain_for, for any user, of the fit or not"""
-        return self._explain_q("update", user, items, ratings, pred_items, cap, order)
+    def explain_with(self, user, items, ratings, pred_items, cap, order=EXPLAIN_SUM_ORDER, predictor=PRED_KNN):
+        """The terms behind predict_with(...) (knncf_update_explain / knncf_update_explain_personalized): as explain_for, for any
+        user, of the fit or not"""
+        return self._explain_q("update", user, items, ratings, pred_items, cap, order, predictor=predictor)
 
-    def explain_revised(self, user, removed, items, ratings, pred_items, cap, order=EXPLAIN_SUM_ORDER):
-        """The terms behind predict_revised(...) (knncf_revise_explain): as explain_for, on aug without the removed rows"""
-        return self._explain_q("revise", user, items, ratings, pred_items, cap, order, removed)
+    def explain_revised(self, user, removed, items, ratings, pred_items, cap, order=EXPLAIN_SUM_ORDER, predictor=PRED_KNN):
+        """The terms behind predict_revised(...) (knncf_revise_explain / knncf_revise_explain_personalized): as explain_for, on aug
+        without the removed rows"""
+        return self._explain_q("revise", user, items, ratings, pred_items, cap, order, removed, predictor)
 
     # ---- batched forms (knncf_query_*_batch, knncf_update_*_batch, knncf_revise_*_batch) --------
     def _batch_args(self, fam, queries):
@@ -852,8 +873,9 @@ class Engine:
         """recommend_revised(n) of every query: ([(item ids, predictions)] per query, statuses).  A failed query has empty arrays."""
         return self._recommend_qb("revise", queries, n, predictor)
 
-    def _explain_qb(self, fam, queries, pred_items, cap, order):
+    def _explain_qb(self, fam, queries, pred_items, cap, order, predictor=PRED_KNN):
         cap, order = self._explain_args(cap, order)
+        entry, lead = self._explain_entry(fam, "_batch", predictor)
         qargs, keep = self._batch_args(fam, queries)
         B = qargs[-1]
         pred_items = list(pred_items)
@@ -866,22 +888,22 @@ class Engine:
         out = self._explain_out(int(poff[-1]), cap)
         st = np.zeros(B, dtype=np.int32)
         p = self._ptr
-        self._check(getattr(self._lib, f"knncf_{fam}_explain_batch")(
-            self._h, PRED_KNN, *qargs, p(poff, _i64p), p(pi, _i32p), order, cap, *self._explain_ptrs(out), p(st, _i32p)))
+        self._check(getattr(self._lib, entry)(
+            self._h, *lead, *qargs, p(poff, _i64p), p(pi, _i32p), order, cap, *self._explain_ptrs(out), p(st, _i32p)))
         return [tuple(a[poff[b]:poff[b + 1]].copy() for a in out) for b in range(B)], st
 
-    def explain_for_batch(self, queries, pred_items, cap, order=EXPLAIN_SUM_ORDER):
+    def explain_for_batch(self, queries, pred_items, cap, order=EXPLAIN_SUM_ORDER, predictor=PRED_KNN):
         """explain_for of every query; pred_items is one sequence of item ids per query: ([the explain_for tuple] per query,
-        statuses).  A failed query's arrays hold only padding (-1 / nan, counts 0)."""
-        return self._explain_qb("query", queries, pred_items, cap, order)
+        statuses).  A failed query's arrays hold only padding (-1 / nan, counts 0).  predictor as in explain_for."""
+        return self._explain_qb("query", queries, pred_items, cap, order, predictor)
 
-    def explain_with_batch(self, queries, pred_items, cap, order=EXPLAIN_SUM_ORDER):
+    def explain_with_batch(self, queries, pred_items, cap, order=EXPLAIN_SUM_ORDER, predictor=PRED_KNN):
         """explain_with of every query: ([the explain_with tuple] per query, statuses)"""
-        return self._explain_qb("update", queries, pred_items, cap, order)
+        return self._explain_qb("update", queries, pred_items, cap, order, predictor)
 
-    def explain_revised_batch(self, queries, pred_items, cap, order=EXPLAIN_SUM_ORDER):
+    def explain_revised_batch(self, queries, pred_items, cap, order=EXPLAIN_SUM_ORDER, predictor=PRED_KNN):
         """explain_revised of every (user, removed_items, items, ratings): ([the explain_revised tuple] per query, statuses)"""
-        return self._explain_qb("revise", queries, pred_items, cap, order)
+        return self._explain_qb("revise", queries, pred_items, cap, order, predictor)
 
     # ---- batch -------------------------------------------------------------------------
     def predict_batch(self, predictor, users, items):
