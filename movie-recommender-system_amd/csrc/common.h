@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <mutex>
 #include <stdexcept>
@@ -193,7 +194,17 @@ inline bool lds_bitmap_fits(int64_t words) { return words * 12 <= 48 * 1024 && !
 
 // (KNNCF_DEBUG_TRACE_DISPATCH: test hook — launch_predict (kNN kinds), launch_predict_sweep, launch_rerank and
 // launch_sort_neighbors write "knncf-dispatch <stage> <variant>" to stderr, one line per launch, so that a test can tell
-// which instantiation ran.  Unset: nothing is written.)
+// which instantiation ran.  Unset: nothing is written.
+// With the value "setup" the set-up stage reports as well, host code only (any other value leaves its lines out: the tests of
+// the launch stages assert their exact line sets, and every kNN prediction sorts its test rows): prep_fit one line per fit,
+//   "prep ids=<table|sorted> order=<segments|global> mid=<n> long=<n> uf=<0|1> uh=<0|1>"
+// (the id path, per-user LDS sorts or global radix sorts, the lengths of the two segment lists of k_classify_rows — read
+// back from the status words under the hook only — and which fold orders were built), and radix_sort one line per sort,
+//   "sort key=<32|64> n=<n> tiles=<t> passes=<p> scan=<self|kernel>".)
+inline bool trace_setup_stage() {
+    const char* v = getenv("KNNCF_DEBUG_TRACE_DISPATCH");
+    return v && strcmp(v, "setup") == 0;
+}
 #define KN_TRACE_DISPATCH(fmt, ...)                                                                                 \
     do {                                                                                                            \
         if (getenv("KNNCF_DEBUG_TRACE_DISPATCH")) fprintf(stderr, "knncf-dispatch " fmt "\n", ##__VA_ARGS__);         \

@@ -932,6 +932,15 @@ void prep_fit(Train& tr, PrepScratch& sc, int32_t shard_rank, int32_t shard_coun
         }
     }
     KN_HIP(hipGetLastError());
+    if (trace_setup_stage()) {  // (the two list lengths are read back under the hook only)
+        uint32_t lists[2] = {0, 0};
+        if (seg_sorts) {
+            KN_HIP(hipMemcpyAsync(lists, sc.status.p + 2, sizeof(lists), hipMemcpyDeviceToHost, st));
+            KN_HIP(hipStreamSynchronize(st));
+        }
+        KN_TRACE_DISPATCH("prep ids=%s order=%s mid=%u long=%u uf=%d uh=%d", small_ids ? "table" : "sorted",
+                          seg_sorts ? "segments" : "global", lists[0], lists[1], need_uf ? 1 : 0, n > 4 ? 1 : 0);
+    }
     tr.item_stats_ready = false;
 
     // K1: average :94 — left fold over the file; exact in any order for dyadic ratings

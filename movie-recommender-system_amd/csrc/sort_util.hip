@@ -220,6 +220,9 @@ void radix_sort(SortWorkspace& ws, const K* kin, K* kout, const uint32_t* vin, u
     uint32_t* vtmp = reinterpret_cast<uint32_t*>(ws.tmp.p + round_up((int64_t)table_bytes, 256) + key_bytes);
     const K* src_k = kin;
     const uint32_t* src_v = vin;
+    if (trace_setup_stage())
+        KN_TRACE_DISPATCH("sort key=%d n=%llu tiles=%lld passes=%d scan=%s", max_bits, (unsigned long long)n, (long long)n_tiles, passes,
+                          n_tiles <= RS_SELF_SCAN_TILES ? "self" : "kernel");
     for (int p = 0; p < passes; ++p) {
         const int shift = p * RS_BITS;
         const int bits = end_bit - shift < RS_BITS ? end_bit - shift : RS_BITS;
