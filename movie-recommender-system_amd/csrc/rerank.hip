@@ -261,18 +261,30 @@ __device__ unsigned long long g_rphase[8];
 #endif
 
 // exact similarities of this wave's candidates (n_c <= 64); lane j returns candidate j's.
-// The candidates' rows are read as ONE stream: position s of the stream belongs to candidate j with
-// cstart[j] <= s < cend[j] (per-wave arrays in LDS; each lane walks them forward as its positions grow by 64 per
-// piece), so every lane of every piece carries an entry whatever the row lengths are.  PIPE pieces are in flight;
-// they are consumed GRP at a time in stage order (bitmap words of all GRP pieces, then u's values, then the writes)
-// so that the dependent LDS round trips of different pieces overlap.  The loop is bound by instruction issue and
-// LDS latency, not by the volume read, so the per-piece instruction count is what is minimised here.
+// The candidates' rows are read as ONE stream: candidate j owns the stream positions [start[j], start[j + 1]) (the
+// exclusive scan of the row lengths), so every lane of every 64-entry piece carries an entry whatever the row lengths are.
+// Which candidate a position belongs to is the same question for every lane, and it is answered per WAVE, not per lane:
+// for piece p the scalar unit builds the START MASK — bit l set iff some candidate's first entry is position 64 p + l.
+// The candidates that start inside a piece are a consecutive run [J0(p), J0(p + 1)); the next start is kept in an SGPR, so a
+// piece without a boundary costs one scalar compare, and every boundary one v_readlane of lane j's start, one shift / or
+// (~1.1 boundaries per piece at the ml-25m shape).  Lane l's candidate is then J0(p) + popcount(mask & bits[0..l]) - 1:
+// v_mbcnt_lo/hi on mask >> 1, the wave-uniform rest riding in the shift-add that makes the byte offset — three VALU, no loop,
+// no LDS cursor, nothing carried per lane from piece to piece.  The entry of stream position 0 of that candidate comes from
+// its lane's register (ds_bpermute, the GRP permutes of a group issued together in front of the group's loads); "first entry
+// of its candidate" is the start mask itself, applied as EXEC; "the entry exists" (64 p + l < E) is tested only in the code
+// for the last PIPE + GRP pieces of a stream — a wave-uniform choice between two copies of the group's code.  Every real
+// candidate has at least one entry (a user of the fit has a rating); lanes >= n_c have length 0 and set no bit.
+// PIPE pieces are in flight; they are consumed GRP at a time in stage order (bitmap words of all GRP pieces, then u's
+// values of all of them, then the products and the writes) so that the dependent LDS round trips of different pieces
+// overlap.  Per 64-entry piece the path of a full group is 63 static instructions, 24 of them VALU (the per-lane cursor
+// this replaced: 90 and 47, plus an LDS round trip per trip of its walk); DESIGN.md section 4 has the counts, the registers
+// and the timings, section 8 what bounds the loop now (round trips in a row and the compiler's vmcnt counts, not issue).
 // Hits are appended to the wave's product buffer in stream order (= candidate by candidate, items ascending); the
 // lane holding a candidate's FIRST entry records where that candidate's products start (cofs), which is all the
 // fold needs: candidate j's products are [cofs[j], cofs[j+1]).
 static constexpr int PIPE = 8;
 static constexpr int GRP = 4;
-static constexpr int WMETA = 200;  // per-wave LDS words: (cend, cbase)[64] | cofs[65] (193 used)
+static constexpr int WMETA = 200;  // per-wave LDS words: cofs[65] (the rest held the stream cursor's tables once; the plans' LDS budget keeps the size)
 static constexpr uint32_t NOT_STARTED = 0xffffffffu;
 
 typedef __attribute__((address_space(3))) uint32_t* lds_u32;
@@ -285,54 +297,71 @@ template <bool JAC, int WBUF, class PreP>
 __device__ __forceinline__ double wave_sims(const Rows& R, lds_cu32x2 bp, PreP upre, int32_t nu, lds_f64 wb, lds_u32 meta,
                                             uint32_t my_b, uint32_t my_len, int n_c, int lane) {
     constexpr bool PRE_IN_LDS = !std::is_same<PreP, const double*>::value;
-    lds_u32x2 cpair = (lds_u32x2)meta;  // [64] (end of candidate j in the stream, entry of stream position 0 of j)
-    lds_u32 cofs = meta + 128;          // [65] first product of candidate j in the product buffer
+    lds_u32 cofs = meta;  // [65] first product of candidate j in the product buffer
     const uint32_t incl = wave_incl_scan(my_len);
     const uint32_t E = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-    {
-        u32x2 pr;
-        pr.x = incl;
-        pr.y = my_b - (incl - my_len);  // entry of stream position s: cbase[j] + s
-        cpair[lane] = pr;
-    }
+    // lane j's start for the scalar walk below; lanes without a candidate never start, and lane 0's start (position 0) is
+    // the walk's initial state, so that a lane select that wraps to lane 0 after candidate 63 ends the walk too
+    const uint32_t my_start = (my_len && lane) ? incl - my_len : 0xffffffffu;
+    const uint32_t my_base = my_b - (incl - my_len);  // entry of stream position s of this lane's candidate: my_base + s
     cofs[lane] = NOT_STARTED;
     if (lane == 0) cofs[64] = NOT_STARTED;
     wave_sync();
-    const uint32_t NP = (E + 63u) >> 6;
+    const uint32_t NP = (E + 63u) >> 6, NPF = E >> 6;  // pieces; pieces in which every lane has an entry
     double acc = 0.0;
     uint32_t off = 0;
-    // stream cursor of this lane: candidate jf = [c_start, c_end), never moves backwards
-    int32_t jf = 0;
-    uint32_t c_start = 0, c_end, c_base;
-    {
-        const u32x2 p0 = cpair[0];
-        c_end = p0.x;
-        c_base = p0.y;
-    }
+    // wave-level stream state (SGPRs): J candidates start before the next piece to be requested, the next one at nxt
+    uint32_t J = 0, nxt = 0;
     uint32_t pc[PIPE];
     u32x2 py[PIPE];
-    uint32_t pfl[PIPE];  // bit 0: the entry exists, bit 1: it is the first entry of its candidate; bits 8..: candidate
+    uint32_t pj[PIPE];             // the entry's candidate, times 4
+    unsigned long long pm[PIPE];   // the piece's start mask (wave-uniform)
     // The loads go through buffer descriptors and are issued UNCONDITIONALLY (a lane past the stream's end uses an
-    // out-of-range offset and gets 0): with loads under a branch the compiler cannot count what is in flight and
-    // waits for everything (vmcnt(0)) before the first use, which serialises the whole pipeline.
+    // out-of-range offset and gets 0): with loads under a divergent branch the compiler cannot count what is in flight
+    // and waits for everything (vmcnt(0)) before the first use, which serialises the whole pipeline.
     const __amdgpu_buffer_rsrc_t col_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(R.s_col), 0, R.col_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t pre_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(R.s_pre), 0, R.pre_bytes, 0x00020000);
-    auto request = [&](int d, uint32_t p) {
-        const uint32_t s = (p << 6) + lane;
-        const bool valid = s < E;
-        if (valid) {
-            while (s >= c_end) {
-                c_start = c_end;
-                ++jf;
-                const u32x2 pr = cpair[jf];
-                c_end = pr.x;
-                c_base = pr.y;
+    // TAIL: the piece may reach past the stream's end (only the last PIPE + GRP pieces are requested or consumed that way);
+    // everywhere else "the entry exists" costs nothing
+    // GRP pieces at a time, in two stages: the candidate of every entry and the permute that fetches its row's base for all
+    // GRP pieces, then the loads — one LDS round trip per group in front of the loads instead of one per piece.  The loads
+    // are kept in piece order (sched_barrier): the compiler's vmcnt counts assume the order it emitted, and a reordered
+    // prologue makes every wait of the loop wait for younger pieces too.
+    auto request = [&](auto tail, int d0, uint32_t p0) {  // pieces p0 .. p0 + GRP - 1 into slots d0 ..; p0 grows by GRP from call to call
+        constexpr bool TAIL = decltype(tail)::value;
+        uint32_t c_base[GRP];
+#pragma unroll
+        for (int k = 0; k < GRP; ++k) {
+            const uint32_t base = (p0 + k) << 6, lim = base + 64u;
+            const uint32_t j0 = J;
+            unsigned long long m = 0;
+            while (nxt < lim) {  // wave-uniform: the candidates that start inside this piece
+                m |= 1ull << (nxt - base);
+                ++J;
+                nxt = (uint32_t)__builtin_amdgcn_readlane((int)my_start, (int)(J & 63u));
             }
+            // candidates started at or before this lane's position, minus one: "bits below my lane" of mask >> 1, plus bit 0
+            // and J0 - 1, which are wave-uniform and ride in the shift-add that turns the index into a byte offset (a VALU
+            // instruction reads one SGPR: the mask words and the addend cannot share the v_mbcnt)
+            const unsigned long long mh = m >> 1;
+            const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(mh >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mh, 0u));
+            uint32_t jb4 = (j0 + (uint32_t)(m & 1ull) - 1u) << 2;
+            asm("" : "+s"(jb4));  // (opaque: stays one scalar addend of the shift-add)
+            const uint32_t jf4 = (below << 2) + jb4;
+            c_base[k] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)jf4, (int)my_base);
+            pj[d0 + k] = jf4;
+            pm[d0 + k] = m;
         }
-        const uint32_t q = valid ? c_base + s : 0x3fffffffu;  // -> byte offsets beyond both arrays
-        pc[d] = __builtin_amdgcn_raw_buffer_load_b32(col_rsrc, (int)(q << 2), 0, 0);  // (no use of the loaded values
-        py[d] = __builtin_amdgcn_raw_buffer_load_b64(pre_rsrc, (int)(q << 3), 0, 0);  //  here: a use is a wait)
-        pfl[d] = valid ? (((uint32_t)jf << 8) | (s == c_start ? 3u : 1u)) : 0u;
+#pragma unroll
+        for (int k = 0; k < GRP; ++k) {
+            const uint32_t base = (p0 + k) << 6;
+            uint32_t q;
+            if (TAIL) q = base + (uint32_t)lane < E ? c_base[k] + base + (uint32_t)lane : 0x3fffffffu;  // -> byte offsets beyond both arrays
+            else asm("v_add3_u32 %0, %1, %2, %3" : "=v"(q) : "v"(c_base[k]), "s"(base), "v"(lane));  // (the compiler's form: v_or, v_add)
+            pc[d0 + k] = __builtin_amdgcn_raw_buffer_load_b32(col_rsrc, (int)(q << 2), 0, 0);  // (no use of the loaded values
+            py[d0 + k] = __builtin_amdgcn_raw_buffer_load_b64(pre_rsrc, (int)(q << 3), 0, 0);  //  here: a use is a wait)
+            __builtin_amdgcn_sched_barrier(0);
+        }
     };
     auto fold = [&]() {  // lane j folds candidate j's products left: the reference's `.sum` order
         FOLD_T0();
@@ -344,42 +373,70 @@ __device__ __forceinline__ double wave_sims(const Rows& R, lds_cu32x2 bp, PreP u
         off = 0;
         FOLD_T1();
     };
+    auto consume = [&](auto tail, int g, uint32_t p) {  // pieces p .. p + GRP - 1, held in slots g .. g + GRP - 1
+        constexpr bool TAIL = decltype(tail)::value;
+        u32x2 wp[GRP];
+        unsigned long long mask[GRP];
+        double uval[GRP];
+        off = (uint32_t)__builtin_amdgcn_readfirstlane((int)off);  // (wave-uniform by construction: keeps the positions' addend scalar)
 #pragma unroll
-    for (int d = 0; d < PIPE; ++d) request(d, (uint32_t)d);
-    for (uint32_t p0 = 0; p0 < NP; p0 += PIPE) {
-#pragma unroll
-        for (int g = 0; g < PIPE; g += GRP) {
-            if (p0 + g < NP) {  // wave-uniform
-                if (off + 64 * GRP > WBUF) fold();
-                u32x2 wp[GRP];
-                unsigned long long mask[GRP];
-                bool hits[GRP];
-                double prod[GRP];
-#pragma unroll
-                for (int k = 0; k < GRP; ++k) wp[k] = bp[pc[g + k] >> 5];  // (an absent entry reads word 0: harmless)
-#pragma unroll
-                for (int k = 0; k < GRP; ++k) {
-                    const uint32_t c = pc[g + k];
-                    const bool hit = ((wp[k].x >> (c & 31u)) & pfl[g + k] & 1u) != 0u;
-                    mask[k] = __ballot(hit);
-                    hits[k] = hit;
-                    // position of item c in u's row (for a miss: some position of the row, its value is not used; at most nu,
-                    // which an LDS copy of the row may read — the next LDS array — but a global row must not)
-                    int32_t idx = (int32_t)(wp[k].y + __popc(wp[k].x & ((1u << (c & 31u)) - 1u)));
-                    if (!PRE_IN_LDS) idx = min(idx, nu - 1);
-                    prod[k] = JAC ? 1.0 : upre[idx] * __hiloint2double((int)py[g + k].y, (int)py[g + k].x);
-                }
-#pragma unroll
-                for (int k = 0; k < GRP; ++k) {
-                    const uint32_t pos = off + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask[k] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask[k], 0u));
-                    if (hits[k]) wb[pos] = prod[k];
-                    if (pfl[g + k] & 2u) cofs[pfl[g + k] >> 8] = pos;  // this candidate's products start here
-                    off += (uint32_t)__popcll(mask[k]);
-                }
-#pragma unroll
-                for (int k = 0; k < GRP; ++k) request(g + k, p0 + g + k + PIPE);
-            }
+        for (int k = 0; k < GRP; ++k) {
+            uint32_t w;  // pc >> 5 (an absent entry reads word 0: harmless), opaque: as an index the address is one shift-add, re-associated it takes three instructions
+            asm("v_lshrrev_b32 %0, 5, %1" : "=v"(w) : "v"(pc[g + k]));
+            wp[k] = bp[w];
         }
+#pragma unroll
+        for (int k = 0; k < GRP; ++k) {
+            const uint32_t b = pc[g + k] & 31u;
+            bool hit = __builtin_amdgcn_ubfe(wp[k].x, b, 1u) != 0u;
+            if (TAIL) hit = hit && ((p + k) << 6) + (uint32_t)lane < E;
+            mask[k] = __builtin_amdgcn_ballot_w64(hit);
+            // position of item c in u's row (for a miss: some position of the row, its value is not used; at most nu,
+            // which an LDS copy of the row may read — the next LDS array — but a global row must not).  u's values of the
+            // whole group are requested here, hit or miss, so that their LDS round trips overlap
+            int32_t idx = (int32_t)(wp[k].y + __popc(__builtin_amdgcn_ubfe(wp[k].x, 0u, b)));
+            if (!PRE_IN_LDS) idx = min(idx, nu - 1);
+            else asm("" : "+v"(idx));  // (the same: v_bcnt with its addend, one shift-add)
+            if (!JAC) uval[k] = upre[idx];
+        }
+#pragma unroll
+        for (int k = 0; k < GRP; ++k) {
+            const uint32_t pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask[k] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask[k], off));
+            // (u's value and the candidate's are used here, in front of the branch: u's values of the group are then read together
+            // instead of one by one inside the branches, and no wait for a load sits under a branch that a wave without hits skips)
+            if (!JAC) asm("" : "+v"(uval[k]), "+v"(py[g + k].x), "+v"(py[g + k].y));
+            else asm("" : "+v"(py[g + k].x), "+v"(py[g + k].y));
+            if (__builtin_amdgcn_inverse_ballot_w64(mask[k])) wb[pos] = JAC ? 1.0 : uval[k] * __hiloint2double((int)py[g + k].y, (int)py[g + k].x);
+            if (__builtin_amdgcn_inverse_ballot_w64(pm[g + k])) *(lds_u32)((__attribute__((address_space(3))) char*)cofs + pj[g + k]) = pos;  // this candidate's products start here
+            off += (uint32_t)__popcll(mask[k]);
+        }
+    };
+    const std::false_type full;
+    const std::true_type tail;
+    if (PIPE <= NPF) {
+        request(full, 0, 0u);
+        request(full, GRP, (uint32_t)GRP);
+    } else {
+        request(tail, 0, 0u);
+        request(tail, GRP, (uint32_t)GRP);
+    }
+    auto group = [&](auto slot, uint32_t p) {  // consume pieces p .. p + GRP - 1 and request their successors (all choices wave-uniform)
+        constexpr int g = decltype(slot)::value;
+        if (off + 64 * GRP > WBUF) fold();
+        if (p + GRP <= NPF) consume(full, g, p);
+        else consume(tail, g, p);
+        if (p + GRP + PIPE <= NPF) request(full, g, p + PIPE);
+        else request(tail, g, p + PIPE);
+    };
+    // Both groups of a trip run unconditionally — a stream of 8 n + 1 .. 8 n + 4 pieces consumes one group of absent pieces
+    // (no entry, no hit, loads that fetch nothing) — so that the loop is one straight body with one exit at its end: the
+    // first group's s_waitcnt vmcnt counts then wait for exactly the piece that is used (15 / 13 / 11 / 9).  With the second
+    // group skipped, or the loop left between the groups, every count assumed the other group's loads were never issued.
+    // (The second group's counts still do: DESIGN.md section 8.)
+    static_assert(PIPE == 2 * GRP, "wave_sims: the stream loop is written for two groups");
+    for (uint32_t p0 = 0; p0 < NP; p0 += PIPE) {
+        group(std::integral_constant<int, 0>(), p0);
+        group(std::integral_constant<int, GRP>(), p0 + GRP);
     }
     fold();
     return acc;
