@@ -271,14 +271,15 @@ __device__ unsigned long long g_rphase[8];
 // v_mbcnt_lo/hi on mask >> 1, the wave-uniform rest riding in the shift-add that makes the byte offset — three VALU, no loop,
 // no LDS cursor, nothing carried per lane from piece to piece.  The entry of stream position 0 of that candidate comes from
 // its lane's register (ds_bpermute, the GRP permutes of a group issued together in front of the group's loads); "first entry
-// of its candidate" is the start mask itself, applied as EXEC; "the entry exists" (64 p + l < E) is tested only in the code
-// for the last PIPE + GRP pieces of a stream — a wave-uniform choice between two copies of the group's code.  Every real
+// of its candidate" is the start mask itself, applied as EXEC; "the entry exists" (64 p + l < E) is tested only in the DRAIN
+// loop, which takes a stream's last PIPE .. 2 PIPE pieces — two copies of a trip's code, one per loop.  Every real
 // candidate has at least one entry (a user of the fit has a rating); lanes >= n_c have length 0 and set no bit.
 // PIPE pieces are in flight; they are consumed GRP at a time in stage order (bitmap words of all GRP pieces, then u's
 // values of all of them, then the products and the writes) so that the dependent LDS round trips of different pieces
 // overlap.  Per 64-entry piece the path of a full group is 63 static instructions, 24 of them VALU (the per-lane cursor
 // this replaced: 90 and 47, plus an LDS round trip per trip of its walk); DESIGN.md section 4 has the counts, the registers
-// and the timings, section 8 what bounds the loop now (round trips in a row and the compiler's vmcnt counts, not issue).
+// and the timings (and the s_waitcnt vmcnt counts of both stream loops in every instantiation: each group waits for its own
+// pieces only, so PIPE pieces really are in flight), section 8 what bounds the loops now (round trips in a row, not issue).
 // Hits are appended to the wave's product buffer in stream order (= candidate by candidate, items ascending); the
 // lane holding a candidate's FIRST entry records where that candidate's products start (cofs), which is all the
 // fold needs: candidate j's products are [cofs[j], cofs[j+1]).
@@ -321,8 +322,8 @@ __device__ __forceinline__ double wave_sims(const Rows& R, lds_cu32x2 bp, PreP u
     // and waits for everything (vmcnt(0)) before the first use, which serialises the whole pipeline.
     const __amdgpu_buffer_rsrc_t col_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(R.s_col), 0, R.col_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t pre_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(R.s_pre), 0, R.pre_bytes, 0x00020000);
-    // TAIL: the piece may reach past the stream's end (only the last PIPE + GRP pieces are requested or consumed that way);
-    // everywhere else "the entry exists" costs nothing
+    // TAIL: the piece may reach past the stream's end (only the drain loop requests or consumes that way, and the prologue of
+    // a stream of fewer than PIPE full pieces); everywhere else "the entry exists" costs nothing
     // GRP pieces at a time, in two stages: the candidate of every entry and the permute that fetches its row's base for all
     // GRP pieces, then the loads — one LDS round trip per group in front of the loads instead of one per piece.  The loads
     // are kept in piece order (sched_barrier): the compiler's vmcnt counts assume the order it emitted, and a reordered
@@ -420,24 +421,32 @@ __device__ __forceinline__ double wave_sims(const Rows& R, lds_cu32x2 bp, PreP u
         request(tail, 0, 0u);
         request(tail, GRP, (uint32_t)GRP);
     }
-    auto group = [&](auto slot, uint32_t p) {  // consume pieces p .. p + GRP - 1 and request their successors (all choices wave-uniform)
-        constexpr int g = decltype(slot)::value;
+    // A trip consumes both groups and requests their successors; TAIL is one choice for the whole trip, so its body is
+    // straight-line code (the fold in front of a group issues no load and waits for none).
+    // Two loops, each with one exit at its end: the STEADY loop runs while every piece a trip consumes or requests is full
+    // (p0 + 2 PIPE <= NPF is the conjunction of the four conditions), the DRAIN loop takes the rest with the tail copies — a
+    // superset of the full ones (they add the test 64 p + lane < E), so the full pieces it still meets come out the same.
+    // Both groups of a drain trip run unconditionally: a stream of 8 n + 1 .. 8 n + 4 pieces consumes one group of absent
+    // pieces (no entry, no hit, loads that fetch nothing).  With no join of a full and a tail copy between a trip's
+    // requests and the next trip's consumes, the compiler's s_waitcnt vmcnt counts never reach into the other group, in
+    // either group of either loop: of 16 loads in flight (pc and py of PIPE pieces) the group's first two pc words are waited
+    // for with 13, the others with 11 and 9, its last value with 8 — the other group's eight loads stay in flight.  (With
+    // u's ratings in global memory the loads of u's values are the youngest and are waited for with 2 / 1 / 0: a row of more
+    // than UPRE_LDS ratings drains the pipeline once per group, as before.)  When every choice was made per consume and per
+    // request, each join took the pessimistic side and the second group waited as if the first group's requests had never
+    // been issued: four pieces in flight in effect.  DESIGN.md section 4 has the counts of every instantiation.
+    static_assert(PIPE == 2 * GRP, "wave_sims: the stream loops are written for two groups");
+    auto trip = [&](auto tl, uint32_t p) {  // pieces p .. p + PIPE - 1 from slots 0 .. PIPE - 1, their successors into the same slots
         if (off + 64 * GRP > WBUF) fold();
-        if (p + GRP <= NPF) consume(full, g, p);
-        else consume(tail, g, p);
-        if (p + GRP + PIPE <= NPF) request(full, g, p + PIPE);
-        else request(tail, g, p + PIPE);
+        consume(tl, 0, p);
+        request(tl, 0, p + PIPE);
+        if (off + 64 * GRP > WBUF) fold();
+        consume(tl, GRP, p + GRP);
+        request(tl, GRP, p + GRP + PIPE);
     };
-    // Both groups of a trip run unconditionally — a stream of 8 n + 1 .. 8 n + 4 pieces consumes one group of absent pieces
-    // (no entry, no hit, loads that fetch nothing) — so that the loop is one straight body with one exit at its end: the
-    // first group's s_waitcnt vmcnt counts then wait for exactly the piece that is used (15 / 13 / 11 / 9).  With the second
-    // group skipped, or the loop left between the groups, every count assumed the other group's loads were never issued.
-    // (The second group's counts still do: DESIGN.md section 8.)
-    static_assert(PIPE == 2 * GRP, "wave_sims: the stream loop is written for two groups");
-    for (uint32_t p0 = 0; p0 < NP; p0 += PIPE) {
-        group(std::integral_constant<int, 0>(), p0);
-        group(std::integral_constant<int, GRP>(), p0 + GRP);
-    }
+    uint32_t p0 = 0;
+    for (; p0 + 2 * PIPE <= NPF; p0 += PIPE) trip(full, p0);
+    for (; p0 < NP; p0 += PIPE) trip(tail, p0);
     fold();
     return acc;
 }
