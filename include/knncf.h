@@ -181,6 +181,46 @@ int knncf_predict(knncf_handle* h, int predictor, int32_t user, int32_t item, do
 int knncf_recommend(knncf_handle* h, int predictor, int32_t user, int32_t n, int32_t* items,
                     double* predictions, int32_t* count);
 
+/* ---- Bulk similarities: knncf_similarity / knncf_knn_similarity for many pairs in one device pass ----------------------------
+ * knncf_similarity_batch: out[j] equals what knncf_similarity(h, us[j], vs[j], ..) writes, bit for bit (the bits of a NaN
+ * included), j < n.  Every pair is answered on a closure of its OWN: the batch keeps no memo across its pairs, (v, u) after
+ * (u, v) is computed with v as the first argument, and a pair listed twice is computed twice.  (A "one closure across the batch"
+ * mode, in which an earlier pair's memo decides a later pair's summation order, is not offered.)  Adjusted cosine :415-432: the
+ * left fold from 0.0 of pre(u, i) * pre(v, i) over the common items in the item-set order of u, the FIRST argument — ascending
+ * trie order when u has more than 4 train ratings, u's file order otherwise; multiply and add round separately.  u == v is an
+ * ordinary pair (S(u, u), close to but not 1.0); a user absent from train gives 0.0.  Jaccard :446-463: |I(u) & I(v)| /
+ * (|I(u)| + |I(v)| - |I(u) & I(v)|) as Double / Int; an absent user has the empty set, so one absent user gives 0.0 and two give
+ * 0.0 / 0 = NaN.  KNNCF_SIM_ONE: every out[j] = 1.0.
+ * Status: KNNCF_E_STATE before a fit; KNNCF_E_INVALID for n < 0 or a null pointer with n > 0; n == 0 is KNNCF_OK and touches
+ * nothing; a call that fails these checks writes nothing.  Shard handles are accepted exactly where knncf_similarity accepts
+ * them (after knncf_shard_commit every shard holds every user's preprocessed ratings).  The call only reads the handle: the
+ * neighbour table, its build numbers, the call epoch and the knncf_neighbors_save file stay as they were.  knncf_get_timings:
+ * the pair kernels are charged to rerank_ms.
+ * Chunks.  The host forms answer the pairs in chunks of consecutive positions, [0, C), [C, 2 C), ..., the last one possibly
+ * shorter, through scratch that the handle owns (two ids and one double per pair):
+ *     C = max(1, budget / 16)
+ *     budget = workspace_bytes / 2 if workspace_bytes > 0, else min(48 GiB, free device memory / 4)
+ * The results do not depend on C, and a call on a handle that has answered the same shape before allocates no device memory.
+ * knncf_similarity_batch_device: the same over device arrays (raw ids, looked up on the device; d_out [n] doubles), one pass
+ * into the caller's buffer with no scratch.  Inputs must be complete at the call, outputs are complete on return.
+ * knncf_knn_similarity_batch: getSimilarity(train, k, sim)(us[j], vs[j]) :634-648.  out[j] equals what a loop of
+ * knncf_knn_similarity over the pairs in this order returns, bit for bit: 0.0 + sim when vs[j] is in the list of us[j] (.sum
+ * from 0.0: a similarity of -0.0 comes back as +0.0), 0.0 otherwise, and 0.0 for us[j] == vs[j] and when either id is absent
+ * from train.  Order and handle state.  The reference builds the neighbourhood of us[j] only when BOTH ids are in train, and so
+ * does this call.  The missing neighbourhoods are built in ONE batch.  Let us' be us with a raw id absent from train in every
+ * position where us[j] or vs[j] is absent from train: THE HANDLE IS LEFT IN THE STATE THAT knncf_neighbors_batch OVER us'
+ * LEAVES IT IN: the same lists, the same build numbers (call, position j), the same knncf_neighbors_save file.  The lookup runs
+ * on the device, in the id-sorted copy of the lists (made when it is not current); only out comes back.
+ * Status: KNNCF_E_STATE before a fit; KNNCF_E_INVALID for n < 0 or a null pointer with n > 0; KNNCF_E_UNSUPPORTED on a
+ * KNNCF_SIM_ONE handle, as knncf_knn_similarity; KNNCF_E_INVALID when a us[j] in train (with vs[j] in train) is owned by another
+ * shard; a neighbourhood that is not built yet is refused on a shard whose train set has a <= 4-rating user, as
+ * knncf_neighbors_batch refuses it.  All of these are checked for the whole call before anything is built or written; n == 0
+ * is KNNCF_OK.  The chunk rule above applies.  knncf_get_timings: builds are charged as in knncf_neighbors_batch, the lookup to
+ * predict_ms.  There is no device form: the builds are numbered on the host, from the pairs' positions. */
+int knncf_similarity_batch(knncf_handle* h, const int32_t* us, const int32_t* vs, int64_t n, double* out);
+int knncf_similarity_batch_device(knncf_handle* h, const int32_t* d_us, const int32_t* d_vs, int64_t n, double* d_out);
+int knncf_knn_similarity_batch(knncf_handle* h, const int32_t* us, const int32_t* vs, int64_t n, double* out);
+
 /* ---- Batched recommendations: knncf_recommend for many users of the fit in one call ------------------------------------------
  * Row b of out_items / out_preds ([n_users * n], row stride n) receives exactly what
  * knncf_recommend(h, predictor, users[b], n, ...) writes, bit for bit, and counts[b] its *count = min(n, #items users[b] has

@@ -439,4 +439,17 @@ void reco_batch_mark(const Train& tr, const RecoBatchScratch& rb, int32_t C, int
 void reco_batch_select(const Train& tr, RecoBatchScratch& rb, int32_t C, int32_t n, const double* d_pred, const uint8_t* d_rated,
                        int32_t* d_items, double* d_preds, hipStream_t st);
 
+// ---- similarity_batch.hip: many fresh-closure pair similarities in one pass (knncf_similarity_batch*, knncf_knn_similarity_batch;
+// DESIGN.md "Bulk similarities") ----
+// device bytes per pair of a chunk that the chunk rule of knncf.h counts: two raw ids and one double
+static constexpr int64_t PAIR_BYTES = 16;
+// d_out[j] = sim(train)(d_us[j], d_vs[j]) on a closure of its own, j < n: raw ids, looked up on the device (adjusted cosine, or the
+// Jaccard coefficient with `jaccard`).  One launch; reads the fit only.
+void launch_pair_similarity(const Train& tr, bool jaccard, const int32_t* d_us, const int32_t* d_vs, int64_t n, double* d_out,
+                            hipStream_t st);
+// d_out[j] = 0.0 + the similarity of d_vs[j] in the neighbour list of d_us[j] (raw ids), 0.0 when it is not there or either id is
+// absent from train; every list the pairs need exists.  Makes nt's id-sorted copies when they are not current.
+void launch_pair_knn_lookup(const Train& tr, NeighborTable& nt, const int32_t* d_us, const int32_t* d_vs, int64_t n, double* d_out,
+                            hipStream_t st);
+
 }  // namespace knncf

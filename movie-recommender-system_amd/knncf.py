@@ -117,7 +117,7 @@ EXPORTS = [
     "knncf_version", "knncf_status_string", "knncf_create", "knncf_destroy", "knncf_last_error",
     "knncf_fit", "knncf_fit_device", "knncf_num_users", "knncf_num_items", "knncf_global_avg",
     "knncf_user_avg", "knncf_item_avg", "knncf_item_avg_dev", "knncf_item_avg_dev_rdd", "knncf_similarity",
-    "knncf_knn_similarity", "knncf_neighbors", "knncf_neighbors_batch", "knncf_predict", "knncf_recommend", "knncf_recommend_batch",
+    "knncf_knn_similarity", "knncf_similarity_batch", "knncf_similarity_batch_device", "knncf_knn_similarity_batch", "knncf_neighbors", "knncf_neighbors_batch", "knncf_predict", "knncf_recommend", "knncf_recommend_batch",
     "knncf_explain", "knncf_explain_batch", "knncf_explain_batch_device",
     "knncf_explain_personalized", "knncf_explain_personalized_batch",
     "knncf_query_neighbors", "knncf_query_predict", "knncf_query_recommend",
@@ -205,6 +205,9 @@ def load_library():
         getattr(L, n).argtypes = [C.c_void_p, C.c_int32, _f64p]
     for n in ("knncf_similarity", "knncf_knn_similarity"):
         getattr(L, n).argtypes = [C.c_void_p, C.c_int32, C.c_int32, _f64p]
+    for n in ("knncf_similarity_batch", "knncf_knn_similarity_batch"):
+        getattr(L, n).argtypes = [C.c_void_p, _i32p, _i32p, C.c_int64, _f64p]
+    L.knncf_similarity_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.knncf_neighbors.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _i32p, _f64p, _i32p]
     L.knncf_neighbors_batch.argtypes = [C.c_void_p, _i32p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p]
     L.knncf_predict.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int32, _f64p]
@@ -389,6 +392,55 @@ class Engine:
 
     def knn_similarity(self, u, v):
         return self._scalar(self._lib.knncf_knn_similarity, u, v)
+
+    @staticmethod
+    def _pair_ids(us, vs):
+        """validated raw ids of a batch of pairs: ValueError before any C call"""
+        out = []
+        for a in (us, vs):
+            a = np.asarray(a)
+            if a.ndim != 1:
+                raise ValueError("us and vs must be 1-D arrays of ids")
+            if len(a) and (a.dtype.kind not in "iu" or a.min() < -2**31 or a.max() >= 2**31):
+                raise ValueError("us and vs must be 32-bit integer ids")
+            out.append(_i32(a))
+        if len(out[0]) != len(out[1]):
+            raise ValueError("us and vs differ in length")
+        return out
+
+    def _pair_batch(self, entry, us, vs):
+        u, v = self._pair_ids(us, vs)
+        out = np.empty(len(u), dtype=np.float64)
+        p = self._ptr
+        self._check(getattr(self._lib, entry)(self._h, p(u, _i32p), p(v, _i32p), len(u), p(out, _f64p)))
+        return out
+
+    def similarity_batch(self, us, vs):
+        """similarity(us[j], vs[j]) for every j in one device pass (knncf_similarity_batch): float64 [n].  Every pair is
+        answered on a closure of its own, us[j] as the first argument; the handle is only read."""
+        return self._pair_batch("knncf_similarity_batch", us, vs)
+
+    def knn_similarity_batch(self, us, vs):
+        """knn_similarity(us[j], vs[j]) for every j, as if called in this order (knncf_knn_similarity_batch): float64 [n].
+        Missing neighbourhoods are built in one batch: the handle is left as neighbors_batch leaves it over us with an
+        absent id wherever us[j] or vs[j] is absent from train."""
+        return self._pair_batch("knncf_knn_similarity_batch", us, vs)
+
+    def similarity_batch_device(self, us, vs, out):
+        """similarity_batch on contiguous torch tensors of this engine's device: us, vs int32 [n], out float64 [n]"""
+        import torch
+
+        for t, dt in ((us, torch.int32), (vs, torch.int32), (out, torch.float64)):
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1:
+                raise ValueError("us, vs must be 1-D int32 tensors and out a 1-D float64 tensor")
+        if not (us.numel() == vs.numel() == out.numel()):
+            raise ValueError("us, vs and out differ in length")
+        if not (us.is_cuda and vs.is_cuda and out.is_cuda and us.is_contiguous() and vs.is_contiguous() and out.is_contiguous()):
+            raise ValueError("us, vs and out must be contiguous tensors on the device")
+        _producer_done(us)
+        self._check(self._lib.knncf_similarity_batch_device(self._h, _dev_ptr(us, "int32"), _dev_ptr(vs, "int32"), us.numel(),
+                                                            _dev_ptr(out, "float64")))
+        return out
 
     def neighbors(self, u):
         cap = max(1, self.k)
