@@ -348,7 +348,9 @@ int knncf_explain_batch_device(knncf_handle* h, const int32_t* d_users, const in
  * and a call on a handle that has answered the same shape before allocates no device memory.
  * OUT OF SCOPE: a device-pointer form, shard handles, KNNCF_SIM_ONE, and Personalized explanations of fold-in / update / revise
  * queries (knncf_*_explain* below keep refusing KNNCF_PRED_PERSONALIZED).  Those have calls of their own:
- * knncf_*_explain_personalized* ("Explanations of Personalized query predictions" below). */
+ * knncf_*_explain_personalized* ("Explanations of Personalized query predictions" below).  The query families can also have
+ * their recommendations and the terms behind them from one call: knncf_*_recommend_explain* ("Recommendations with their
+ * explanations" below). */
 int knncf_explain_personalized(knncf_handle* h, int32_t user, int32_t item, int32_t order, int32_t cap, int32_t* raters, double* sims,
                                double* devs, int32_t* count, double* sums, double* prediction);
 int knncf_explain_personalized_batch(knncf_handle* h, const int32_t* users, const int32_t* items, int64_t n, int32_t order,
@@ -597,7 +599,8 @@ int knncf_revise_recommend_batch(knncf_handle* h, int predictor, const int32_t* 
  * predictor but KNNCF_PRED_KNN), sharded explanations (a shard handle: KNNCF_E_UNSUPPORTED), and a fused "recommend and
  * explain in one pass" call: explain the items knncf_*_recommend returned with a second call.  (Users as the fit holds them have
  * knncf_explain_personalized* above for KNNCF_PRED_PERSONALIZED; the query families have knncf_*_explain_personalized* below,
- * "Explanations of Personalized query predictions".) */
+ * "Explanations of Personalized query predictions".)  That fused call has entry points of its own, which leave these calls
+ * as they are: knncf_*_recommend_explain* ("Recommendations with their explanations" below). */
 int knncf_query_explain(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
                         const int32_t* pred_items, int64_t m, int32_t order, int32_t cap, int32_t* raters, double* sims, double* devs,
                         int32_t* counts, double* sums, double* predictions);
@@ -670,7 +673,8 @@ int knncf_revise_explain_batch(knncf_handle* h, int predictor, const int32_t* us
  * knncf_neighbors_save bytes stay as they were.  The first call after a fit builds the handle's file-order rater copies
  * (prep_ms); knncf_get_timings: the fold and the explain kernel are charged to predict_ms.
  * OUT OF SCOPE: a device-pointer form, shard handles, KNNCF_SIM_ONE, a fused "recommend and explain in one pass" call, and the
- * command-line tool. */
+ * command-line tool.  The fused call has entry points of its own, which take KNNCF_PRED_PERSONALIZED as well:
+ * knncf_*_recommend_explain* ("Recommendations with their explanations" below). */
 int knncf_query_explain_personalized(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
                                      const int32_t* pred_items, int64_t m, int32_t order, int32_t cap, int32_t* raters, double* sims,
                                      double* devs, int32_t* counts, double* sums, double* predictions);
@@ -694,6 +698,73 @@ int knncf_revise_explain_personalized_batch(knncf_handle* h, const int32_t* user
                                             const double* ratings, int64_t n_queries, const int64_t* pred_offsets,
                                             const int32_t* pred_items, int32_t order, int32_t cap, int32_t* raters, double* sims,
                                             double* devs, int32_t* counts, double* sums, double* predictions, int32_t* statuses);
+
+/* ---- Recommendations with their explanations: the top n of a query and the terms behind each, in one pass over the fit -------
+ * A serving layer wants both together: n recommended items, each with the few users that carried its prediction.
+ * knncf_*_recommend followed by knncf_*_explain* on the returned items repeats the upload, the similarity pass over every train
+ * row, the top-k selection and the fold.  These six calls run the explain kernel over the rows the selection just produced: one
+ * implementation, three families, single and batched.  NEW CALLS: no refusal of the explain calls above is lifted.
+ * Arguments.  Those of the matching knncf_*_recommend / knncf_*_recommend_batch call up to n, then order and cap as the explain
+ * calls take them, the recommend outputs, and the explain outputs without a predictions array.  predictor is KNNCF_PRED_KNN or
+ * KNNCF_PRED_PERSONALIZED, as the recommend calls accept them.
+ * Recommendation outputs.  out_items / out_preds ([n_queries * n], row stride n), counts[b] and statuses[b] are exactly what
+ * knncf_*_recommend_batch writes for the same arguments, bit for bit: the cells past counts[b] are untouched, a refused query
+ * gets counts[b] = 0 and its row is untouched, and the return values are the same.
+ * Explanation rows.  Row (b, j) with j < counts[b] is explain row r = b * n + j.  It receives term_counts[r], sums[2 r] and
+ * sums[2 r + 1], and the first min(term_counts[r], cap) terms in `order` at raters / sims / devs [r * cap ..]: each of these is
+ * what the matching explain call — knncf_*_explain_batch for KNNCF_PRED_KNN, knncf_*_explain_personalized_batch for
+ * KNNCF_PRED_PERSONALIZED — writes for that query with pred_items = its recommended items.  The row's cells past its terms are
+ * untouched.  Every explain cell of a row j >= counts[b] is untouched; that includes every row of a refused query.
+ * NO PREDICTIONS ARRAY: out_preds[r] already is the explained prediction — the selection and the explain kernels read the same
+ * prediction cell of the chunk.
+ * Term properties.  Those of "Explanations of query predictions" and "Explanations of Personalized query predictions" above hold
+ * row for row and are not restated here: the caller's left fold of the returned terms gives sums, the combine :578 of the
+ * query's mean with them gives out_preds[r], the user is its own term under KNNCF_PRED_PERSONALIZED and never under
+ * KNNCF_PRED_KNN, and KNNCF_EXPLAIN_BY_WEIGHT orders equal magnitudes in summation order.
+ * Statuses.  Per-query statuses, the handle-level refusals (before a fit, KNNCF_SIM_ONE, a shard handle, fewer than 5 train
+ * users, any other predictor), the CSR checks and n_queries == 0 are those of knncf_*_recommend_batch.  In addition
+ * KNNCF_E_INVALID for cap < 0 and for an unknown order, as in the explain calls, for a null term_counts with n > 0, and for a
+ * null raters / sims / devs with n > 0 and cap > 0.  sums may be null.  n == 0 is KNNCF_OK with counts[b] = 0.  A call that
+ * fails these checks writes nothing, except that a single form has set *count = 0, as knncf_*_recommend does.  A single form
+ * returns the query's status.
+ * Chunks.  The chunk rule C is that of the families ("Batched fold-in queries").  Inside a chunk the explain kernel runs over
+ * consecutive sub-ranges of R rows of the chunk's recommended rows (slot after slot, j ascending), by the existing rules:
+ *     R = max(1, budget / (20 * cap + 28))   for KNNCF_PRED_KNN
+ *     R = max(1, budget / (40 * cap + 28))   for KNNCF_PRED_PERSONALIZED
+ *     budget = workspace_bytes / 2 if workspace_bytes > 0, else min(48 GiB, free device memory / 4)
+ * The rows are formed on the device from the selection's cells, so there is no host round trip between the selection and the
+ * first explain launch; a chunk whose rows fit in R has one stream synchronisation after the similarity stage, a chunk with
+ * more rows one per sub-range.  The results depend on neither C nor R, and a call on a handle that has answered the same shape
+ * before allocates no device memory.
+ * Handle state.  Read-only in the sense of the other families: the neighbour table, its build numbers, its epoch and the
+ * knncf_neighbors_save bytes stay as they were.  With KNNCF_PRED_PERSONALIZED the first call after a fit builds the handle's
+ * file-order rater copies (prep_ms); knncf_get_timings: everything else is charged to predict_ms.
+ * OUT OF SCOPE: a fused call for users as the fit holds them (their neighbour lists are memoised: knncf_recommend_batch then
+ * knncf_explain_batch repeats no pass), device-pointer forms, shard handles, KNNCF_SIM_ONE, returning the neighbour list from
+ * the same pass, and the command-line tool. */
+int knncf_query_recommend_explain(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
+                                  int64_t n_ratings, int32_t n, int32_t order, int32_t cap, int32_t* out_items, double* out_preds,
+                                  int32_t* count, int32_t* raters, double* sims, double* devs, int32_t* term_counts, double* sums);
+int knncf_update_recommend_explain(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
+                                   int64_t n_ratings, int32_t n, int32_t order, int32_t cap, int32_t* out_items, double* out_preds,
+                                   int32_t* count, int32_t* raters, double* sims, double* devs, int32_t* term_counts, double* sums);
+int knncf_revise_recommend_explain(knncf_handle* h, int predictor, int32_t user, const int32_t* removed_items, int64_t n_removed,
+                                   const int32_t* items, const double* ratings, int64_t n_ratings, int32_t n, int32_t order,
+                                   int32_t cap, int32_t* out_items, double* out_preds, int32_t* count, int32_t* raters, double* sims,
+                                   double* devs, int32_t* term_counts, double* sums);
+int knncf_query_recommend_explain_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets,
+                                        const int32_t* items, const double* ratings, int64_t n_queries, int32_t n, int32_t order,
+                                        int32_t cap, int32_t* out_items, double* out_preds, int32_t* counts, int32_t* raters,
+                                        double* sims, double* devs, int32_t* term_counts, double* sums, int32_t* statuses);
+int knncf_update_recommend_explain_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets,
+                                         const int32_t* items, const double* ratings, int64_t n_queries, int32_t n, int32_t order,
+                                         int32_t cap, int32_t* out_items, double* out_preds, int32_t* counts, int32_t* raters,
+                                         double* sims, double* devs, int32_t* term_counts, double* sums, int32_t* statuses);
+int knncf_revise_recommend_explain_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* removed_offsets,
+                                         const int32_t* removed_items, const int64_t* offsets, const int32_t* items,
+                                         const double* ratings, int64_t n_queries, int32_t n, int32_t order, int32_t cap,
+                                         int32_t* out_items, double* out_preds, int32_t* counts, int32_t* raters, double* sims,
+                                         double* devs, int32_t* term_counts, double* sums, int32_t* statuses);
 
 /* ---- batch ---------------------------------------------------------------- */
 int knncf_predict_batch(knncf_handle* h, int predictor, const int32_t* users,

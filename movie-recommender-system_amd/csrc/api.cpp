@@ -1050,8 +1050,11 @@ void do_fit_device(knncf_handle* h, const int32_t* d_users, const int32_t* d_ite
 constexpr int64_t QUERY_MAX_RATINGS = 65536;
 // QB_EXPLAIN_ALL: the explanations of KNNCF_PRED_PERSONALIZED predictions (knncf_*_explain_personalized*), a mode of its own so
 // that QB_EXPLAIN keeps refusing that predictor
-enum QueryBatchMode { QB_NEIGHBORS, QB_PREDICT, QB_RECOMMEND, QB_EXPLAIN, QB_EXPLAIN_ALL };
+// QB_RECOMMEND_EXPLAIN: QB_RECOMMEND, then the explain kernel of the predictor over the rows the selection produced
+// (knncf_*_recommend_explain*): no requested rows, so neither explains() nor wants_rows()
+enum QueryBatchMode { QB_NEIGHBORS, QB_PREDICT, QB_RECOMMEND, QB_EXPLAIN, QB_EXPLAIN_ALL, QB_RECOMMEND_EXPLAIN };
 bool explains(QueryBatchMode mode) { return mode == QB_EXPLAIN || mode == QB_EXPLAIN_ALL; }
+bool recommends(QueryBatchMode mode) { return mode == QB_RECOMMEND || mode == QB_RECOMMEND_EXPLAIN; }
 enum QueryFamily { QF_FOLD_IN, QF_UPDATE, QF_REVISE };
 
 // what the handle must be for any fold-in query, single or batched
@@ -1140,12 +1143,12 @@ struct QueryCall {
     const int32_t* removed_items;    // QF_REVISE: the train items each query's user drops
     const int64_t* pred_offsets;     // QB_PREDICT, explain modes: [B + 1] into pred_items; row j of the call is pred_items[j]
     const int32_t* pred_items;       // QB_PREDICT, explain modes: the requested items
-    int32_t width;                   // QB_NEIGHBORS: cap; QB_RECOMMEND: n
-    int32_t* out_i;                  // QB_NEIGHBORS: ids [B * cap]; QB_RECOMMEND: items [B * n]; unused otherwise
-    double* out_d;                   // QB_NEIGHBORS: sims [B * cap]; QB_RECOMMEND: predictions [B * n]; QB_PREDICT: [pred_offsets[B]]
-    int32_t* counts;                 // QB_NEIGHBORS, QB_RECOMMEND: [B]
+    int32_t width;                   // QB_NEIGHBORS: cap; QB_RECOMMEND, QB_RECOMMEND_EXPLAIN: n
+    int32_t* out_i;                  // QB_NEIGHBORS: ids [B * cap]; QB_RECOMMEND*: items [B * n]; unused otherwise
+    double* out_d;                   // QB_NEIGHBORS: sims [B * cap]; QB_RECOMMEND*: predictions [B * n]; QB_PREDICT: [pred_offsets[B]]
+    int32_t* counts;                 // QB_NEIGHBORS, QB_RECOMMEND*: [B]
     int32_t* statuses;               // [B]
-    ExplainCells ex;                 // explain modes: pred_offsets[B] rows
+    ExplainCells ex;                 // explain modes: pred_offsets[B] rows; QB_RECOMMEND_EXPLAIN: B * n rows, row b * n + j (pred null)
     int32_t user;                    // single forms only, from here on
     int64_t n_ratings, n_removed, m;
 };
@@ -1173,7 +1176,19 @@ QueryCall explain_all_call(QueryCall rows, const ExplainCells& ex) {
     rows.mode = QB_EXPLAIN_ALL; rows.predictor = KNNCF_PRED_PERSONALIZED; rows.ex = ex;
     return rows;
 }
+QueryCall recommend_explain_call(QueryCall rows, int predictor, int32_t n, int32_t* out_items, double* out_preds, int32_t* counts,
+                                 const ExplainCells& ex) {
+    rows = recommend_call(rows, predictor, n, out_items, out_preds, counts);
+    rows.mode = QB_RECOMMEND_EXPLAIN; rows.ex = ex;
+    return rows;
+}
 bool wants_rows(QueryBatchMode mode) { return mode == QB_PREDICT || explains(mode); }
+// the modes that launch an explain kernel, and whether it is the Personalized one; their rows per launch (0: none)
+bool runs_explain(const QueryCall& q) { return explains(q.mode) || q.mode == QB_RECOMMEND_EXPLAIN; }
+bool explains_all(const QueryCall& q) {
+    return q.mode == QB_EXPLAIN_ALL || (q.mode == QB_RECOMMEND_EXPLAIN && q.predictor == KNNCF_PRED_PERSONALIZED);
+}
+int64_t launch_rows(const QueryCall& q, int64_t budget) { return runs_explain(q) ? query_explain_rows(budget, q.ex.cap, explains_all(q)) : 0; }
 
 // ---- the chunk loop ---------------------------------------------------------------------------------------------------------
 // what one call's chunks share: the host vectors are reused from chunk to chunk
@@ -1188,8 +1203,8 @@ struct ChunkState {
     std::vector<int64_t> ebase;   // [C + 1] of foldin_batch_predictions
     // the answers on their way back
     std::vector<int32_t> h_idx, h_items, pick_slot, pick_items;
-    std::vector<int64_t> pick_row;
-    std::vector<double> h_vals;
+    std::vector<int64_t> pick_row, reco_rb;  // reco_rb: [C + 1] of foldin_batch_reco_rows
+    std::vector<double> h_vals, h_top;  // h_top: the recommend modes' predictions (h_vals is an explain launch's block)
 };
 
 void fail(const QueryCall& q, ChunkState& cs, int64_t b, int status, const char* why) {
@@ -1325,16 +1340,14 @@ void answer_predict(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
 
 // sub-ranges of at most ex_rows rows: the chunk's fold results stay where they are between the launches, and every launch's
 // block comes back in one copy
-void answer_explain(knncf_handle* h, const QueryCall& q, ChunkState& cs, int64_t ex_rows) {
-    const int64_t m = upload_picks(h, q, cs);
-    if (m == 0) return;
+void explain_picks(knncf_handle* h, const QueryCall& q, ChunkState& cs, int64_t m, int64_t ex_rows) {
     QueryBatchScratch& bs = h->query_batch;
     hipStream_t st = h->stream;
     const int64_t R = std::min(ex_rows, m);
     const size_t pack = ((size_t)R * explain_row_bytes(q.ex.cap) + 7) / 8;  // doubles
     h->ex_pack.ensure(pack);
     cs.h_vals.resize(pack);
-    const bool all = q.mode == QB_EXPLAIN_ALL;  // (the terms of the Personalized fold; BY_WEIGHT stages the selected ones)
+    const bool all = explains_all(q);  // (the terms of the Personalized fold; BY_WEIGHT stages the selected ones)
     if (all && q.ex.order == KNNCF_EXPLAIN_BY_WEIGHT) h->ex_stage.ensure(((size_t)R * q.ex.cap * 20 + 7) / 8);
     for (int64_t r0 = 0; r0 < m; r0 += R) {
         const int64_t nr = std::min(R, m - r0);
@@ -1353,30 +1366,65 @@ void answer_explain(knncf_handle* h, const QueryCall& q, ChunkState& cs, int64_t
     }
 }
 
-void answer_recommend(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
+void answer_explain(knncf_handle* h, const QueryCall& q, ChunkState& cs, int64_t ex_rows) {
+    const int64_t m = upload_picks(h, q, cs);
+    if (m > 0) explain_picks(h, q, cs, m, ex_rows);
+}
+
+// the recommend modes: counts[b] of the chunk's good queries and, when their widest is > 0, the fold and the selection into
+// bs.out_items / bs.out_preds [C][widest], on their way to cs.h_items / cs.h_top (not synchronised).  Returns widest
+int32_t select_recommendations(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
     QueryBatchScratch& bs = h->query_batch;
     hipStream_t st = h->stream;
-    const int32_t width = q.width;
     int32_t widest = 0;
     for (const int32_t s : cs.good) {
         const int64_t b = cs.slot_query[s];
-        q.counts[b] = (int32_t)std::max<int64_t>(0, std::min<int64_t>(width, (int64_t)h->tr.I - cs.info[4 * s + 1]));
+        q.counts[b] = (int32_t)std::max<int64_t>(0, std::min<int64_t>(q.width, (int64_t)h->tr.I - cs.info[4 * s + 1]));
         widest = std::max(widest, q.counts[b]);
     }
-    if (widest == 0) return;
+    if (widest == 0) return 0;
     fold_chunk(h, q, cs);
     const size_t cells = (size_t)cs.C * widest;
     bs.out_items.ensure(cells); bs.out_preds.ensure(cells);
     foldin_batch_recommend(h->tr, bs, h->prep.sort, cs.C, widest, bs.out_items.p, bs.out_preds.p, st);
-    cs.h_items.resize(cells); cs.h_vals.resize(cells);
+    cs.h_items.resize(cells); cs.h_top.resize(cells);
     KN_HIP(hipMemcpyAsync(cs.h_items.data(), bs.out_items.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    KN_HIP(hipMemcpyAsync(cs.h_vals.data(), bs.out_preds.p, cells * sizeof(double), hipMemcpyDeviceToHost, st));
-    KN_HIP(hipStreamSynchronize(st));
+    KN_HIP(hipMemcpyAsync(cs.h_top.data(), bs.out_preds.p, cells * sizeof(double), hipMemcpyDeviceToHost, st));
+    return widest;
+}
+// after the stream was synchronised: the first counts[b] cells of every good slot into row b of the caller's arrays
+void write_recommendations(const QueryCall& q, const ChunkState& cs, int32_t widest) {
     for (const int32_t s : cs.good) {
         const int64_t b = cs.slot_query[s];
-        std::copy(cs.h_items.begin() + (size_t)s * widest, cs.h_items.begin() + (size_t)s * widest + q.counts[b], q.out_i + b * width);
-        std::copy(cs.h_vals.begin() + (size_t)s * widest, cs.h_vals.begin() + (size_t)s * widest + q.counts[b], q.out_d + b * width);
+        std::copy(cs.h_items.begin() + (size_t)s * widest, cs.h_items.begin() + (size_t)s * widest + q.counts[b], q.out_i + b * q.width);
+        std::copy(cs.h_top.begin() + (size_t)s * widest, cs.h_top.begin() + (size_t)s * widest + q.counts[b], q.out_d + b * q.width);
     }
+}
+
+void answer_recommend(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
+    const int32_t widest = select_recommendations(h, q, cs);
+    if (widest == 0) return;
+    KN_HIP(hipStreamSynchronize(h->stream));
+    write_recommendations(q, cs, widest);
+}
+
+// QB_RECOMMEND_EXPLAIN: the selection's cells become explain rows on the device, slot after slot and j ascending, so the first
+// explain launch follows the selection without a round trip; its synchronisation is also the one of the top-n copies.  The
+// host knows every count (select_recommendations) and with them the row of the call behind each device row: b * n + j.
+void answer_recommend_explain(knncf_handle* h, const QueryCall& q, ChunkState& cs, int64_t ex_rows) {
+    const int32_t widest = select_recommendations(h, q, cs);
+    if (widest == 0) return;
+    cs.reco_rb.assign((size_t)cs.C + 1, 0);
+    cs.pick_row.clear();
+    for (const int32_t s : cs.good) {
+        const int64_t b = cs.slot_query[s];
+        cs.reco_rb[s + 1] = q.counts[b];
+        for (int32_t j = 0; j < q.counts[b]; ++j) cs.pick_row.push_back(b * q.width + j);
+    }
+    for (int32_t s = 0; s < cs.C; ++s) cs.reco_rb[s + 1] += cs.reco_rb[s];
+    foldin_batch_reco_rows(h->query_batch, cs.C, widest, cs.reco_rb.data(), h->query_batch.out_items.p, h->stream);
+    explain_picks(h, q, cs, cs.reco_rb[cs.C], ex_rows);
+    write_recommendations(q, cs, widest);
 }
 
 // The validated queries of q in chunks of `chunk`: statuses[b] and, where it is KNNCF_OK, query b's answer in q's outputs.  A
@@ -1401,6 +1449,7 @@ QueryFailure run_query_chunks(knncf_handle* h, const QueryCall& q, int64_t chunk
             case QB_EXPLAIN:
             case QB_EXPLAIN_ALL: answer_explain(h, q, cs, ex_rows); break;
             case QB_RECOMMEND: answer_recommend(h, q, cs); break;
+            case QB_RECOMMEND_EXPLAIN: answer_recommend_explain(h, q, cs, ex_rows); break;
         }
     }
     return cs.first;
@@ -1428,7 +1477,7 @@ void do_query_batch(knncf_handle* h, const QueryCall& q) {
     require_fitted(h, false);
     KN_REQUIRE(B >= 0, KNNCF_E_INVALID, "query batch: n_queries < 0");
     KN_REQUIRE(wants_rows(q.mode) || q.width >= 0, KNNCF_E_INVALID, "query batch: cap or n < 0");
-    if (explains(q.mode)) require_explain_order(q.ex);
+    if (runs_explain(q)) require_explain_order(q.ex);
     require_query_support(h, q.predictor, q.mode);
     if (B == 0) return;
     KN_REQUIRE(q.users && q.offsets && q.statuses && (wants_rows(q.mode) || q.counts), KNNCF_E_INVALID, "query batch: null argument");
@@ -1447,10 +1496,10 @@ void do_query_batch(knncf_handle* h, const QueryCall& q) {
         if (explains(q.mode)) require_explain_outputs(q.ex, q.pred_offsets[B]);
     } else {
         KN_REQUIRE(q.width == 0 || (q.out_i && q.out_d), KNNCF_E_INVALID, "query batch: null output");
+        if (q.mode == QB_RECOMMEND_EXPLAIN) require_explain_outputs(q.ex, q.width);
     }
     const int64_t budget = batch_budget(h);  // (one hipMemGetInfo for both rules)
-    const QueryFailure f = run_query_chunks(h, q, query_batch_chunk(h, budget),
-                                            explains(q.mode) ? query_explain_rows(budget, q.ex.cap, q.mode == QB_EXPLAIN_ALL) : 0);
+    const QueryFailure f = run_query_chunks(h, q, query_batch_chunk(h, budget), launch_rows(q, budget));
     if (f.query >= 0) h->err = "query batch: query " + std::to_string(f.query) + ": " + f.reason;
 }
 
@@ -1458,10 +1507,10 @@ void do_query_batch(knncf_handle* h, const QueryCall& q) {
 // require_fitted, in do_query_single); a recommend form's *count is 0 whatever fails later
 void require_single_outputs(const QueryCall& q) {
     if (q.mode == QB_PREDICT) KN_REQUIRE(q.m >= 0 && (q.m == 0 || (q.pred_items && q.out_d)), KNNCF_E_INVALID, "bad prediction arguments");
-    if (q.mode == QB_NEIGHBORS || q.mode == QB_RECOMMEND)
+    if (q.mode == QB_NEIGHBORS || recommends(q.mode))
         KN_REQUIRE(q.counts && q.width >= 0 && (q.width == 0 || (q.out_i && q.out_d)), KNNCF_E_INVALID,
                    q.mode == QB_NEIGHBORS ? "bad output arguments" : "bad arguments");
-    if (q.mode == QB_RECOMMEND) *q.counts = 0;
+    if (recommends(q.mode)) *q.counts = 0;
 }
 
 // One query as a chunk of one: the query's status is the call's.  *count (neighbours: min(k, U), min(k, U - 1) for a user of
@@ -1474,6 +1523,10 @@ void do_query_single(knncf_handle* h, const QueryCall& call) {
         require_explain_order(call.ex);
         KN_REQUIRE(call.m >= 0 && (call.m == 0 || call.pred_items), KNNCF_E_INVALID, "bad prediction arguments");
         require_explain_outputs(call.ex, call.m);
+    }
+    if (call.mode == QB_RECOMMEND_EXPLAIN) {
+        require_explain_order(call.ex);
+        require_explain_outputs(call.ex, call.width);
     }
     if (call.family == QF_REVISE)
         KN_REQUIRE(call.n_removed >= 0 && (call.n_removed == 0 || call.removed_items), KNNCF_E_INVALID, "query: null removed items or n_removed < 0");
@@ -1489,7 +1542,7 @@ void do_query_single(knncf_handle* h, const QueryCall& call) {
     QueryCall q = call;
     q.users = &call.user; q.B = 1; q.counts = &c; q.statuses = &status;
     q.offsets = offsets; q.removed_offsets = removed_offsets; q.pred_offsets = pred_offsets;
-    const QueryFailure f = run_query_chunks(h, q, 1, explains(q.mode) ? query_explain_rows(batch_budget(h), q.ex.cap, q.mode == QB_EXPLAIN_ALL) : 0);
+    const QueryFailure f = run_query_chunks(h, q, 1, runs_explain(q) ? launch_rows(q, batch_budget(h)) : 0);  // (no hipMemGetInfo otherwise)
     if (f.query >= 0) throw Error(status, std::string("query: ") + f.reason);
     if (call.counts) *call.counts = c;
 }
@@ -2555,6 +2608,69 @@ int knncf_revise_explain_personalized_batch(knncf_handle* h, const int32_t* user
                                            .ratings = ratings, .removed_offsets = removed_offsets, .removed_items = removed_items,
                                            .pred_offsets = pred_offsets, .pred_items = pred_items, .statuses = statuses},
                                            {order, cap, raters, sims, devs, counts, sums, predictions}));
+}
+
+// recommendations with the terms behind them in one pass (QB_RECOMMEND_EXPLAIN): the *_recommend calls' arguments, then order,
+// cap and the explain outputs of row b * n + j (no predictions array: out_preds holds them)
+int knncf_query_recommend_explain(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
+                                  int64_t n_ratings, int32_t n, int32_t order, int32_t cap, int32_t* out_items, double* out_preds,
+                                  int32_t* count, int32_t* raters, double* sims, double* devs, int32_t* term_counts, double* sums) {
+    return query_single(h, recommend_explain_call({.family = QF_FOLD_IN, .items = items, .ratings = ratings, .user = user,
+                                                  .n_ratings = n_ratings},
+                                                  predictor, n, out_items, out_preds, count,
+                                                  {order, cap, raters, sims, devs, term_counts, sums, nullptr}));
+}
+
+int knncf_update_recommend_explain(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
+                                   int64_t n_ratings, int32_t n, int32_t order, int32_t cap, int32_t* out_items, double* out_preds,
+                                   int32_t* count, int32_t* raters, double* sims, double* devs, int32_t* term_counts, double* sums) {
+    return query_single(h, recommend_explain_call({.family = QF_UPDATE, .items = items, .ratings = ratings, .user = user,
+                                                  .n_ratings = n_ratings},
+                                                  predictor, n, out_items, out_preds, count,
+                                                  {order, cap, raters, sims, devs, term_counts, sums, nullptr}));
+}
+
+int knncf_revise_recommend_explain(knncf_handle* h, int predictor, int32_t user, const int32_t* removed_items, int64_t n_removed,
+                                   const int32_t* items, const double* ratings, int64_t n_ratings, int32_t n, int32_t order,
+                                   int32_t cap, int32_t* out_items, double* out_preds, int32_t* count, int32_t* raters, double* sims,
+                                   double* devs, int32_t* term_counts, double* sums) {
+    return query_single(h, recommend_explain_call({.family = QF_REVISE, .items = items, .ratings = ratings,
+                                                  .removed_items = removed_items, .user = user, .n_ratings = n_ratings,
+                                                  .n_removed = n_removed},
+                                                  predictor, n, out_items, out_preds, count,
+                                                  {order, cap, raters, sims, devs, term_counts, sums, nullptr}));
+}
+
+int knncf_query_recommend_explain_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets,
+                                        const int32_t* items, const double* ratings, int64_t n_queries, int32_t n, int32_t order,
+                                        int32_t cap, int32_t* out_items, double* out_preds, int32_t* counts, int32_t* raters,
+                                        double* sims, double* devs, int32_t* term_counts, double* sums, int32_t* statuses) {
+    return query_batch(h, recommend_explain_call({.family = QF_FOLD_IN, .users = users, .B = n_queries, .offsets = offsets,
+                                                 .items = items, .ratings = ratings, .statuses = statuses},
+                                                 predictor, n, out_items, out_preds, counts,
+                                                 {order, cap, raters, sims, devs, term_counts, sums, nullptr}));
+}
+
+int knncf_update_recommend_explain_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets,
+                                         const int32_t* items, const double* ratings, int64_t n_queries, int32_t n, int32_t order,
+                                         int32_t cap, int32_t* out_items, double* out_preds, int32_t* counts, int32_t* raters,
+                                         double* sims, double* devs, int32_t* term_counts, double* sums, int32_t* statuses) {
+    return query_batch(h, recommend_explain_call({.family = QF_UPDATE, .users = users, .B = n_queries, .offsets = offsets,
+                                                 .items = items, .ratings = ratings, .statuses = statuses},
+                                                 predictor, n, out_items, out_preds, counts,
+                                                 {order, cap, raters, sims, devs, term_counts, sums, nullptr}));
+}
+
+int knncf_revise_recommend_explain_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* removed_offsets,
+                                         const int32_t* removed_items, const int64_t* offsets, const int32_t* items,
+                                         const double* ratings, int64_t n_queries, int32_t n, int32_t order, int32_t cap,
+                                         int32_t* out_items, double* out_preds, int32_t* counts, int32_t* raters, double* sims,
+                                         double* devs, int32_t* term_counts, double* sums, int32_t* statuses) {
+    return query_batch(h, recommend_explain_call({.family = QF_REVISE, .users = users, .B = n_queries, .offsets = offsets,
+                                                 .items = items, .ratings = ratings, .removed_offsets = removed_offsets,
+                                                 .removed_items = removed_items, .statuses = statuses},
+                                                 predictor, n, out_items, out_preds, counts,
+                                                 {order, cap, raters, sims, devs, term_counts, sums, nullptr}));
 }
 
 int knncf_neighbors_save(knncf_handle* h, const char* path) {

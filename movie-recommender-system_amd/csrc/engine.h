@@ -363,6 +363,7 @@ struct QueryBatchScratch {
     DArr<uint32_t> by_id;              // [I]
     DArr<int32_t> pick_items, pick_slot, out_items;
     DArr<double> pick_out, out_preds;
+    DArr<int64_t> reco_rb;             // [C + 1] first explain row of each slot (foldin_batch_reco_rows)
 };
 // prep + similarities + top-k (bs.nbr_idx / nbr_sim [C][min(k, U)]) of C >= 1 non-empty queries; h_info[4 b ..] = status
 // bits, known items, neighbour ratings (0 for a slot whose status is set) of slot b.  Synchronises the stream once.
@@ -411,6 +412,11 @@ void foldin_batch_explain_all(const Train& tr, const PersonalRows& pr, QueryBatc
 // d_items / d_preds [C][n]: slot b's first min(n, I - known) recommendations (the rest untouched)
 void foldin_batch_recommend(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, int32_t n, int32_t* d_items,
                             double* d_preds, hipStream_t st);
+// after foldin_batch_recommend into d_items [C][n]: the recommended cells as the rows the two explain calls above take, in
+// bs.pick_items / bs.pick_slot — cell j of slot b is row h_rb[b] + j for j < h_rb[b + 1] - h_rb[b] (h_rb [C + 1]: the exclusive
+// prefix of the slots' counts, 0 for a refused slot; every count <= what foldin_batch_recommend wrote for the slot).  One
+// upload and one launch, no round trip; nothing with h_rb[C] == 0.
+void foldin_batch_reco_rows(QueryBatchScratch& bs, int32_t C, int32_t n, const int64_t* h_rb, const int32_t* d_items, hipStream_t st);
 
 // ---- reco_batch.hip: recommendations :651-674 for users of the fit (knncf_recommend, knncf_recommend_batch; DESIGN.md "Batched
 // recommendations") ----

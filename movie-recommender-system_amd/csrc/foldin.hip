@@ -846,6 +846,24 @@ __global__ void k_qb_take(int32_t C, int32_t n, int32_t I, const long long* __re
     out_preds[g] = pred[cell];
 }
 
+// the recommended cells of a chunk as the rows the explain kernels take (knncf_*_recommend_explain*): cell j of slot b of the
+// [C][n] raw items k_qb_take wrote becomes row rb[b] + j, (raw item, slot), for j < rb[b + 1] - rb[b] — slot after slot, j
+// ascending.  rb is the host's exclusive prefix of the slots' counts: a refused slot, whose cells of `items` and of bs.pred
+// hold nothing meaningful, has count 0 and gives no row; a slot with a count below n gives its count.
+// Bounds.  One thread per cell g < C * n; b < C reads rb[b], rb[b + 1] of the [C + 1] uploaded.  A cell is read only with j <
+// its slot's count <= min(n, I - known), which k_qb_take wrote.  The row rb[b] + j < rb[b + 1] <= rb[C] = the rows both
+// outputs are sized for.
+__global__ void k_qb_reco_rows(int32_t C, int32_t n, const int64_t* __restrict__ rb, const int32_t* __restrict__ items,
+                               int32_t* __restrict__ row_items, int32_t* __restrict__ row_slot) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (int64_t)C * n) return;
+    const int32_t b = (int32_t)(g / n), j = (int32_t)(g - (int64_t)b * n);
+    const int64_t at = rb[b];
+    if (j >= rb[b + 1] - at) return;
+    row_items[at + j] = items[g];
+    row_slot[at + j] = b;
+}
+
 // [C][stride] cells ordered by (slot, 64-bit key, input order): one stable sort by the key, then one by the slot; returns
 // the ordered values (val = slot * stride + index)
 static const uint32_t* qb_segmented_sort(QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, int64_t stride, hipStream_t st) {
@@ -1472,6 +1490,16 @@ void foldin_batch_recommend(const Train& tr, QueryBatchScratch& bs, SortWorkspac
     const uint32_t* order = qb_segmented_sort(bs, ws, C, I, st);
     k_qb_take<<<(unsigned)ceil_div((int64_t)C * n, TPB), TPB, 0, st>>>(C, n, I, (const long long*)bs.info.p, order, tr.iid.p,
                                                                        bs.pred.p, d_items, d_preds);
+    KN_HIP(hipGetLastError());
+}
+
+void foldin_batch_reco_rows(QueryBatchScratch& bs, int32_t C, int32_t n, const int64_t* h_rb, const int32_t* d_items, hipStream_t st) {
+    const int64_t rows = h_rb[C];
+    if (rows <= 0) return;
+    bs.reco_rb.ensure((size_t)C + 1); bs.pick_items.ensure((size_t)rows); bs.pick_slot.ensure((size_t)rows);
+    KN_HIP(hipMemcpyAsync(bs.reco_rb.p, h_rb, ((size_t)C + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    KN_TRACE_DISPATCH("qb_reco_rows C=%d n=%d rows=%lld", (int)C, (int)n, (long long)rows);
+    k_qb_reco_rows<<<(unsigned)ceil_div((int64_t)C * n, TPB), TPB, 0, st>>>(C, n, bs.reco_rb.p, d_items, bs.pick_items.p, bs.pick_slot.p);
     KN_HIP(hipGetLastError());
 }
 

@@ -130,6 +130,8 @@ EXPORTS = [
     "knncf_query_explain_batch", "knncf_update_explain_batch", "knncf_revise_explain_batch",
     "knncf_query_explain_personalized", "knncf_update_explain_personalized", "knncf_revise_explain_personalized",
     "knncf_query_explain_personalized_batch", "knncf_update_explain_personalized_batch", "knncf_revise_explain_personalized_batch",
+    "knncf_query_recommend_explain", "knncf_update_recommend_explain", "knncf_revise_recommend_explain",
+    "knncf_query_recommend_explain_batch", "knncf_update_recommend_explain_batch", "knncf_revise_recommend_explain_batch",
     "knncf_predict_batch",
     "knncf_predict_batch_device", "knncf_mae", "knncf_mae_device", "knncf_mae_sweep", "knncf_mae_sweep_device", "knncf_shard_view_get",
     "knncf_shard_commit", "knncf_get_timings", "knncf_reset_timings", "knncf_reset_neighbors",
@@ -235,10 +237,16 @@ def load_library():
         # the Personalized explanations: the explain lists without the predictor
         f("explain_personalized").argtypes = f("explain").argtypes[:1] + f("explain").argtypes[2:]
         f("explain_personalized_batch").argtypes = f("explain_batch").argtypes[:1] + f("explain_batch").argtypes[2:]
+        # the fused calls: the recommend lists up to n, order and cap, the recommend outputs, the explain outputs without predictions
+        f("recommend_explain").argtypes = (f("recommend").argtypes[:-3] + [C.c_int32, C.c_int32] + f("recommend").argtypes[-3:]
+                                           + terms[2:-1])
+        f("recommend_explain_batch").argtypes = (f("recommend_batch").argtypes[:-4] + [C.c_int32, C.c_int32]
+                                                 + f("recommend_batch").argtypes[-4:-1] + terms[2:-1] + [_i32p])
     # revise queries: the update argument lists with the removals in front of the additional rows
     for name, at, single in (("neighbors", 2, True), ("predict", 3, True), ("recommend", 3, True), ("explain", 3, True),
                              ("explain_personalized", 2, True), ("neighbors_batch", 2, False), ("predict_batch", 3, False),
-                             ("recommend_batch", 3, False), ("explain_batch", 3, False), ("explain_personalized_batch", 2, False)):
+                             ("recommend_batch", 3, False), ("explain_batch", 3, False), ("explain_personalized_batch", 2, False),
+                             ("recommend_explain", 3, True), ("recommend_explain_batch", 3, False)):
         base = getattr(L, f"knncf_update_{name}").argtypes
         getattr(L, f"knncf_revise_{name}").argtypes = base[:at] + ([_i32p, C.c_int64] if single else [_i64p, _i32p]) + base[at:]
     L.knncf_predict_batch.argtypes = [C.c_void_p, C.c_int, _i32p, _i32p, C.c_int64, _f64p]
@@ -956,6 +964,77 @@ class Engine:
     def explain_revised_batch(self, queries, pred_items, cap, order=EXPLAIN_SUM_ORDER, predictor=PRED_KNN):
         """explain_revised of every (user, removed_items, items, ratings): ([the explain_revised tuple] per query, statuses)"""
         return self._explain_qb("revise", queries, pred_items, cap, order, predictor)
+
+    # ---- recommendations with their explanations in one pass (knncf_*_recommend_explain*) --------
+    @staticmethod
+    def _reco_explain_args(n, cap, order, predictor):
+        """validated (n, cap, order, predictor) of a fused call: the checks of the recommend and of the explain wrappers"""
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0 or n >= 2**31:
+            raise ValueError("n must be a non-negative 32-bit integer")
+        cap, order = Engine._explain_args(cap, order)
+        Engine._explain_entry("query", "", predictor)
+        return int(n), cap, order, int(predictor)
+
+    def _recommend_explain_q(self, fam, user, items, ratings, n, cap, order, removed=None, predictor=PRED_KNN):
+        n, cap, order, predictor = self._reco_explain_args(n, cap, order, predictor)
+        q, it, rt = self._query_rows(user, items, ratings, allow_empty=fam != "query")
+        rm = self._rm_args(fam, removed)
+        ids = np.empty(max(1, n), dtype=np.int32)
+        preds = np.empty(max(1, n), dtype=np.float64)
+        c = C.c_int32()
+        out = self._explain_out(n, cap)
+        p = self._ptr
+        self._check(getattr(self._lib, f"knncf_{fam}_recommend_explain")(
+            self._h, predictor, q, *rm, p(it, _i32p), p(rt, _f64p), len(it), n, order, cap, ids.ctypes.data_as(_i32p),
+            preds.ctypes.data_as(_f64p), C.byref(c), *self._explain_ptrs(out)[:-1]))
+        return (ids[:c.value].copy(), preds[:c.value].copy()) + tuple(a[:c.value].copy() for a in out[:-1])
+
+    def _recommend_explain_qb(self, fam, queries, n, cap, order, predictor=PRED_KNN):
+        n, cap, order, predictor = self._reco_explain_args(n, cap, order, predictor)
+        qargs, keep = self._batch_args(fam, queries)
+        B = qargs[-1]
+        ids = np.empty((B, n), dtype=np.int32)
+        preds = np.empty((B, n), dtype=np.float64)
+        counts = np.zeros(B, dtype=np.int32)
+        st = np.zeros(B, dtype=np.int32)
+        out = self._explain_out(B * n, cap)
+        p = self._ptr
+        self._check(getattr(self._lib, f"knncf_{fam}_recommend_explain_batch")(
+            self._h, predictor, *qargs, n, order, cap, p(ids.reshape(-1), _i32p), p(preds.reshape(-1), _f64p), p(counts, _i32p),
+            *self._explain_ptrs(out)[:-1], p(st, _i32p)))
+        return [(ids[b, :counts[b]].copy(), preds[b, :counts[b]].copy()) + tuple(a[b * n:b * n + counts[b]].copy() for a in out[:-1])
+                for b in range(B)], st
+
+    def recommend_explain_for(self, user, items, ratings, n, cap, order=EXPLAIN_SUM_ORDER, predictor=PRED_KNN):
+        """recommend_for(user, items, ratings, n) and the terms behind each recommended item from one pass over the fit
+        (knncf_query_recommend_explain): (item ids [c], predictions [c], raters [c, cap] int32, sims [c, cap], devs [c, cap],
+        term_counts [c] int32, sums [c, 2]) with c recommended items.  The first two are recommend_for's answer, the rest
+        explain_for's for pred_items = those items, both bit for bit; the cells past a row's min(count, cap) terms are -1 /
+        nan.  There is no predictions array of the explanation: the recommended predictions are the explained ones."""
+        return self._recommend_explain_q("query", user, items, ratings, n, cap, order, predictor=predictor)
+
+    def recommend_explain_with(self, user, items, ratings, n, cap, order=EXPLAIN_SUM_ORDER, predictor=PRED_KNN):
+        """recommend_with and explain_with of its items in one pass (knncf_update_recommend_explain): as recommend_explain_for,
+        for any user, of the fit or not"""
+        return self._recommend_explain_q("update", user, items, ratings, n, cap, order, predictor=predictor)
+
+    def recommend_explain_revised(self, user, removed, items, ratings, n, cap, order=EXPLAIN_SUM_ORDER, predictor=PRED_KNN):
+        """recommend_revised and explain_revised of its items in one pass (knncf_revise_recommend_explain): as
+        recommend_explain_for, on aug without the removed rows"""
+        return self._recommend_explain_q("revise", user, items, ratings, n, cap, order, removed, predictor)
+
+    def recommend_explain_for_batch(self, queries, n, cap, order=EXPLAIN_SUM_ORDER, predictor=PRED_KNN):
+        """recommend_explain_for of every query: ([the recommend_explain_for tuple] per query, statuses).  A failed query has
+        empty arrays, as in recommend_for_batch."""
+        return self._recommend_explain_qb("query", queries, n, cap, order, predictor)
+
+    def recommend_explain_with_batch(self, queries, n, cap, order=EXPLAIN_SUM_ORDER, predictor=PRED_KNN):
+        """recommend_explain_with of every query: ([the recommend_explain_with tuple] per query, statuses)"""
+        return self._recommend_explain_qb("update", queries, n, cap, order, predictor)
+
+    def recommend_explain_revised_batch(self, queries, n, cap, order=EXPLAIN_SUM_ORDER, predictor=PRED_KNN):
+        """recommend_explain_revised of every (user, removed_items, items, ratings): ([the tuple] per query, statuses)"""
+        return self._recommend_explain_qb("revise", queries, n, cap, order, predictor)
 
     # ---- batch -------------------------------------------------------------------------
     def predict_batch(self, predictor, users, items):
