@@ -160,7 +160,7 @@ struct NeighborTable {
     int32_t kcap = 0;  // min(k, U-1): stored neighbours per user
     DArr<int32_t> idx;   // [U * kcap] dense neighbour ids, reference order
     DArr<double> sim;    // [U * kcap]
-    DArr<int32_t> uidx;  // [U * kcap] the same neighbours sorted by dense id: built on demand (launch_predict) for the prediction
+    DArr<int32_t> uidx;  // [U * kcap] the same neighbours sorted by dense id: built on demand (probe_args) for the prediction
     DArr<double> usim;   // [U * kcap]   kernels that probe in global memory; the item-grouped kernel streams idx / sim as they are
     bool by_id_valid = false;  // uidx / usim hold the current lists
     DArr<int32_t> cnt;   // [U] 0 until built
@@ -233,10 +233,32 @@ void launch_full_rows(const Train& tr, bool jaccard, int32_t* d_idx, double* d_s
 void launch_exact_pair(const Train& tr, int32_t u, int32_t v, double* d_out, hipStream_t st);
 
 // ---- predict.hip: K7-K9 ----------------------------------------------------------------
-// per test row: prediction of `predictor`; rows whose user is outside [own_lo, own_hi) are
-// skipped (unknown users belong to shard 0).  d_abs_err[t] = |r - p| or 0 for skipped rows.
 // id-sorted copies of the lists of the given users (d_row_user == nullptr: of every user)
 void launch_sort_neighbors(NeighborTable& nt, int32_t U, int32_t n_rows, const int32_t* d_row_user, hipStream_t st);
+// What the kNN term kernels (knn_terms.h) probe: "which of u's neighbours rated item i, and where".  Kernel argument, embedded
+// in PredArgs, ExplainArgs and SweepArgs.
+struct ProbeArgs {
+    // neighbour table: lists of kcap cells per user, nbr_cnt[u] of them filled
+    const int32_t* nbr_idx;
+    const double* nbr_sim;
+    const int32_t* nbr_cnt;
+    int32_t kcap;
+    // item-major rows, raters ascending
+    const int64_t* i_ptr;
+    const int32_t* it_user;
+    const double* it_dev;
+    const uint32_t* it_t;
+    // per-item rater bitmaps (ib_words == 0: not built, binary search instead)
+    int64_t ib_words;
+    const unsigned long long* item_bits;
+    const uint32_t* item_rank;
+};
+// by_id: the lists sorted by neighbour id, which the kernels that probe in global memory want (neighbouring lanes on neighbouring
+// ids share cache sectors) — the copies are made here on first need (0.7 ms per step at the ml-25m shape when it was part of every
+// build); else the lists as the re-rank left them (reference order), for the kernels that probe an LDS bitmap
+ProbeArgs probe_args(const Train& tr, NeighborTable& nt, bool by_id, hipStream_t st);
+// per test row: prediction of `predictor`; rows whose user is outside [own_lo, own_hi) are
+// skipped (unknown users belong to shard 0).  d_abs_err[t] = |r - p| or 0 for skipped rows.
 void launch_predict(const Train& tr, NeighborTable* nt, int predictor, int64_t n,
                     const int32_t* d_du, const int32_t* d_di, const double* d_ratings,
                     const uint32_t* d_order, bool order_by_item, double* d_pred, double* d_abs_err, uint8_t* d_owned,
@@ -275,7 +297,7 @@ void launch_explain(const Train& tr, NeighborTable& nt, int64_t n, const int32_t
 // per test row d_order[0 .. n): the kNN prediction at every k = d_ks[q] (ascending, q < n_k <= 64) from the first k entries of the
 // row user's reference-order list in nt (kcap <= 2048); rows sorted by dense item.  Cell q * n_total + row of d_pred (may be
 // null) / d_abs_err; rows of other shards' users: abs_err 0 in every column, owned 0
-void launch_predict_sweep(const Train& tr, const NeighborTable& nt, const int32_t* d_ks, int32_t n_k, int64_t n_rows, int64_t n_total,
+void launch_predict_sweep(const Train& tr, NeighborTable& nt, const int32_t* d_ks, int32_t n_k, int64_t n_rows, int64_t n_total,
                           const int32_t* d_du, const int32_t* d_di, const double* d_ratings, const uint32_t* d_order,
                           double* d_pred, double* d_abs_err, uint8_t* d_owned, bool unknown_users_owned, hipStream_t st);
 

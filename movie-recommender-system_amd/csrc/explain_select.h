@@ -28,22 +28,12 @@
 
 #include <math.h>
 
-#include "engine.h"
+#include "knn_terms.h"
 
 namespace knncf {
 
 static constexpr int XA_DEEP = 4;  // trips of 64 whose loads a walk / select / emit pass has in flight together
 static constexpr int XA_OWN = 4;   // staged terms per lane that one sweep over the staged keys ranks
-
-__device__ __forceinline__ void wave_sync() {
-    // lanes of one wave exchange data through LDS: order the accesses for the compiler (the LDS queue is in order per wave)
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ int32_t lanes_below(unsigned long long mask) {
-    return (int32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
 
 // |s| as an unsigned integer: the order of the magnitudes; 0 for +-0.0, which is no term
 __device__ __forceinline__ uint64_t mag_key(double s) { return (uint64_t)__double_as_longlong(s) & 0x7fffffffffffffffull; }

@@ -754,7 +754,7 @@ __global__ void __launch_bounds__(QBX_WAVES * 64) k_qb_explain(QbExplainArgs A, 
         const bool keep = s != 0.0;
         const unsigned long long hit = __ballot(keep);
         if (keep && !by_weight) {
-            const int32_t place = total + (int32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(hit >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hit, 0u));
+            const int32_t place = total + lanes_below(hit);
             if (place < A.cap) {
                 A.raters[ob + place] = qb_rater(A, b, t);
                 A.sims[ob + place] = s;

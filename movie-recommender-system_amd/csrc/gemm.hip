@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "wave_helpers.h"
 
 namespace knncf {
 
@@ -396,14 +397,6 @@ k_gemm_nt_bf16(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, float
         Ag = Ag2;
         Bg = Bg2;
     }
-}
-
-// a pointer whose value is the same in every lane, moved to scalar registers (buffer descriptors must be uniform)
-template <class T>
-__device__ __forceinline__ T* uniform_ptr(T* p) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return reinterpret_cast<T*>(((uint64_t)hi << 32) | lo);
 }
 
 // stage_tile with the addressing off the vector registers: the tile origin is a uniform 64-bit pointer (scalar registers),

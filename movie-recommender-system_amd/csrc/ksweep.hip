@@ -13,7 +13,7 @@
 // its own serial fp64 fold in file order — the same additions in the same order as the one-k kernels.
 #include <math.h>
 
-#include "engine.h"
+#include "knn_terms.h"
 
 namespace knncf {
 
@@ -24,25 +24,10 @@ struct SweepArgs {
     const double* user_avg;
     double global_avg;
     int32_t own_lo, own_hi;
-    const int32_t* nbr_idx;  // [U * kcap] reference order
-    const double* nbr_sim;
-    const int32_t* nbr_cnt;
-    int32_t kcap;
-    const int64_t* i_ptr;
-    const int32_t* it_user;  // item-major (item, user ascending)
-    const double* it_dev;
-    const uint32_t* it_t;
-    int32_t ib_words;
-    const unsigned long long* item_bits;
-    const uint32_t* item_rank;
+    ProbeArgs P;  // (the lists in reference order; ib_words = 0 when the bitmaps are not used)
     const int32_t* ks;  // [n_k] ascending
     int32_t n_k;
 };
-
-__device__ __forceinline__ void sweep_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 // CAP: match slots per wave (>= kcap), BITS: the item's rater bitmap sits in LDS (dynamic shared memory)
 template <int CAP, int WAVES, bool BITS>
@@ -70,7 +55,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_sweep(SweepArgs A, i
     const int nr = (int)min((int64_t)CHUNK, n - r0);
     const int n_k = A.n_k;
     const int32_t my_k = lane < n_k ? A.ks[lane] : 0;  // lane q folds for k = ks[q]
-    const int ibw = A.ib_words;
+    const int ibw = (int)A.P.ib_words;
     const int ibw2 = (ibw + 1) >> 1;
     // as in k_predict_knn_items: the rank prefix of every second bitmap word (the odd word adds its even neighbour's popcount)
     unsigned long long* bits = reinterpret_cast<unsigned long long*>(smem);  // [2 * ibw2]
@@ -83,8 +68,8 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_sweep(SweepArgs A, i
         double ua = -1.0;  // usersAvgValue.getOrElse(u, -1.0) :572
         int32_t cnt = 0;
         uint32_t rb = 0, len = 0;
-        if (u >= 0) { ua = A.user_avg[u]; cnt = A.nbr_cnt[u]; }
-        if (i >= 0) { rb = (uint32_t)A.i_ptr[i]; len = (uint32_t)A.i_ptr[i + 1] - rb; }
+        if (u >= 0) { ua = A.user_avg[u]; cnt = A.P.nbr_cnt[u]; }
+        if (i >= 0) { rb = (uint32_t)A.P.i_ptr[i]; len = (uint32_t)A.P.i_ptr[i + 1] - rb; }
         s_row[l] = row; s_u[l] = u; s_i[l] = i; s_cnt[l] = cnt; s_rb[l] = rb; s_len[l] = len; s_ua[l] = ua;
         s_p[l] = (ua < 0.0) ? A.global_avg : combine(ua, 0.0);  // unknown user / no rater: den = 0 -> 0.0 :527-529
         s_mine[l] = mine ? 1 : 0;
@@ -104,8 +89,8 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_sweep(SweepArgs A, i
         while (rbn < nr && s_i[rbn] == item) { any = any || s_active[rbn] != 0; ++rbn; }
         if (any) {
             if (BITS) {
-                const unsigned long long* gb = A.item_bits + (int64_t)item * ibw;
-                const uint32_t* gr = A.item_rank + (int64_t)item * ibw;
+                const unsigned long long* gb = A.P.item_bits + (int64_t)item * ibw;
+                const uint32_t* gr = A.P.item_rank + (int64_t)item * ibw;
                 for (int w = threadIdx.x; w < 2 * ibw2; w += WAVES * 64) bits[w] = w < ibw ? gb[w] : 0ull;
                 for (int j = threadIdx.x; j < ibw2; j += WAVES * 64) rnk[j] = gr[2 * j];
                 __syncthreads();
@@ -115,8 +100,8 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_sweep(SweepArgs A, i
                 const int32_t u = s_u[r];
                 const int32_t cnt = s_cnt[r];
                 const uint32_t rb = s_rb[r], len = s_len[r];
-                const int32_t* lid = A.nbr_idx + (int64_t)u * A.kcap;
-                const double* lsim = A.nbr_sim + (int64_t)u * A.kcap;
+                const int32_t* lid = A.P.nbr_idx + (int64_t)u * A.P.kcap;
+                const double* lsim = A.P.nbr_sim + (int64_t)u * A.P.kcap;
                 int32_t total = 0;
                 for (int32_t j0 = 0; j0 < cnt; j0 += 64) {  // u's list in reference order: position j = rank in it
                     const int32_t j = j0 + lane;
@@ -125,26 +110,22 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_sweep(SweepArgs A, i
                     bool f;
                     uint32_t q;  // the match's entry in the item's rater list
                     if (BITS) {
-                        const uint32_t wi = x >> 6;
-                        const ulonglong2 pair = *reinterpret_cast<const ulonglong2*>(bits + (wi & ~1u));
-                        const unsigned long long word = (wi & 1u) ? pair.y : pair.x;
-                        f = have && ((word >> (x & 63u)) & 1ull);
-                        q = rnk[wi >> 1] + ((wi & 1u) ? (uint32_t)__popcll(pair.x) : 0u) + (uint32_t)__popcll(word & ((1ull << (x & 63u)) - 1ull));
+                        f = lds_pair_probe(bits, rnk, x, 0u, q) && have;
                     } else {
                         uint32_t lo = 0, hi = have ? len : 0u;
                         while (lo < hi) {
                             const uint32_t mid = (lo + hi) >> 1;
-                            if ((uint32_t)A.it_user[rb + mid] < x) lo = mid + 1;
+                            if ((uint32_t)A.P.it_user[rb + mid] < x) lo = mid + 1;
                             else hi = mid;
                         }
-                        f = have && lo < len && (uint32_t)A.it_user[rb + lo] == x;
+                        f = have && lo < len && (uint32_t)A.P.it_user[rb + lo] == x;
                         q = lo;
                     }
                     const unsigned long long hit = __ballot(f);
                     if (f) {
-                        const int32_t slot = total + (int32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(hit >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hit, 0u));
-                        mt[slot] = A.it_t[rb + q];
-                        md[slot] = A.it_dev[rb + q];
+                        const int32_t slot = total + lanes_below(hit);
+                        mt[slot] = A.P.it_t[rb + q];
+                        md[slot] = A.P.it_dev[rb + q];
                         ms[slot] = lsim[j];
                         mj[slot] = (uint16_t)j;
                     }
@@ -153,8 +134,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_sweep(SweepArgs A, i
                 if (total == 0) continue;  // no neighbour rated the item: every k predicts the user's mean (preset)
                 // order the matches by training file row (the order of ratedI(i) :508-517): rank by counting (the file rows of
                 // one item's ratings are distinct); LDS broadcast reads, 4 keys per read
-                for (int32_t c = total + lane; c < ((total + 3) & ~3); c += 64) mt[c] = 0xffffffffu;
-                sweep_wave_sync();
+                pad_file_rows(mt, total, lane);
                 const uint4* keys4 = reinterpret_cast<const uint4*>(mt);
                 const int32_t n4 = (total + 3) >> 2;
                 for (int32_t s0 = 0; s0 < total; s0 += 64) {
@@ -167,7 +147,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_sweep(SweepArgs A, i
                     }
                     if (s < total) mp[rank] = (uint16_t)s;
                 }
-                sweep_wave_sync();
+                wave_sync();
                 // lane q: the fold at k = ks[q] over the matches of position < k, in file order
                 double num = 0.0, den = 0.0;
                 for (int32_t c = 0; c < total; ++c) {
@@ -179,7 +159,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_sweep(SweepArgs A, i
                         den = den + fabs(sc);
                     }
                 }
-                sweep_wave_sync();  // (the buffers are refilled by the wave's next row)
+                wave_sync();  // (the buffers are refilled by the wave's next row)
                 if (lane < n_k) {
                     const double wsd = (den > 0) ? num / den : 0.0;
                     const double p = combine(s_ua[r], wsd);
@@ -217,7 +197,7 @@ static size_t sweep_bitmap_lds(int64_t ib_words) {
     return ibw2 * 16 + ibw2 * 4;
 }
 
-void launch_predict_sweep(const Train& tr, const NeighborTable& nt, const int32_t* d_ks, int32_t n_k, int64_t n, int64_t n_total,
+void launch_predict_sweep(const Train& tr, NeighborTable& nt, const int32_t* d_ks, int32_t n_k, int64_t n, int64_t n_total,
                           const int32_t* d_du, const int32_t* d_di, const double* d_ratings, const uint32_t* d_order,
                           double* d_pred, double* d_abs_err, uint8_t* d_owned, bool unknown_users_owned, hipStream_t st) {
     if (n <= 0) return;
@@ -226,13 +206,11 @@ void launch_predict_sweep(const Train& tr, const NeighborTable& nt, const int32_
     SweepArgs A{};
     A.user_avg = tr.user_avg.p; A.global_avg = tr.global_avg;
     A.own_lo = tr.own_lo; A.own_hi = tr.own_hi;
-    A.nbr_idx = nt.idx.p; A.nbr_sim = nt.sim.p; A.nbr_cnt = nt.cnt.p; A.kcap = nt.kcap;
-    A.i_ptr = tr.i_ptr.p; A.it_user = tr.it_user.p; A.it_dev = tr.it_dev.p; A.it_t = tr.it_t.p;
+    A.P = probe_args(tr, nt, /*by_id=*/false, st);
     A.ks = d_ks; A.n_k = n_k;
     // the item's bitmap in LDS when it is built and small enough (the bound of the item-grouped one-k kernel)
     const bool bits = tr.ib_words > 0 && lds_bitmap_fits(tr.ib_words);
-    A.ib_words = bits ? (int32_t)tr.ib_words : 0;
-    A.item_bits = reinterpret_cast<const unsigned long long*>(tr.item_bits.p); A.item_rank = tr.item_rank.p;
+    if (!bits) A.P.ib_words = 0;
     const unsigned blocks = (unsigned)ceil_div(n, SWEEP_CHUNK);
     const size_t smem = bits ? sweep_bitmap_lds(tr.ib_words) : 0;
     const int uo = unknown_users_owned ? 1 : 0;

@@ -255,4 +255,16 @@ void launch_sort_neighbors(NeighborTable& nt, int32_t U, int32_t n_rows, const i
     KN_HIP(hipGetLastError());
 }
 
+ProbeArgs probe_args(const Train& tr, NeighborTable& nt, bool by_id, hipStream_t st) {
+    ProbeArgs P{};
+    if (by_id && !nt.by_id_valid) {
+        launch_sort_neighbors(nt, tr.U, tr.U, nullptr, st);
+        nt.by_id_valid = true;
+    }
+    P.nbr_idx = by_id ? nt.uidx.p : nt.idx.p; P.nbr_sim = by_id ? nt.usim.p : nt.sim.p; P.nbr_cnt = nt.cnt.p; P.kcap = nt.kcap;
+    P.i_ptr = tr.i_ptr.p; P.it_user = tr.it_user.p; P.it_dev = tr.it_dev.p; P.it_t = tr.it_t.p;
+    P.ib_words = tr.ib_words; P.item_bits = reinterpret_cast<const unsigned long long*>(tr.item_bits.p); P.item_rank = tr.item_rank.p;
+    return P;
+}
+
 }  // namespace knncf

@@ -20,17 +20,12 @@
 #include <algorithm>
 
 #include "engine.h"
+#include "wave_helpers.h"
 
 namespace knncf {
 
 static constexpr int TPB = 256;
 static inline int nblocks(int64_t n, int per = TPB) { return (int)std::max<int64_t>(1, ceil_div(n, per)); }
-
-__device__ __forceinline__ void wave_sync() {
-    // lanes of one wave exchange data through LDS: order the accesses for the compiler (the LDS queue itself is in order per wave)
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 // ---- first-use copies ---------------------------------------------------------------------------------------------------
 __global__ void k_pcol_keys(int64_t n, const int32_t* __restrict__ s_col, uint32_t* __restrict__ key, uint32_t* __restrict__ val) {

@@ -13,7 +13,7 @@
 #include <stdio.h>
 #include <string.h>
 
-#include "engine.h"
+#include "knn_terms.h"
 
 namespace knncf {
 
@@ -29,39 +29,10 @@ struct PredArgs {
     const double* item_dev_file;
     double global_avg;
     int32_t own_lo, own_hi;
-    // neighbour table
-    const int32_t* nbr_uidx;  // neighbour ids sorted ascending
-    const double* nbr_usim;
-    const int32_t* nbr_cnt;
-    int32_t kcap;
-    // item-major rows, raters ascending
-    const int64_t* i_ptr;
-    const int32_t* it_user;
-    const double* it_dev;
-    const uint32_t* it_t;
-    // per-item rater bitmaps (ib_words == 0: not built, binary search instead)
-    int64_t ib_words;
-    const unsigned long long* item_bits;
-    const uint32_t* item_rank;
+    ProbeArgs P;          // (the item-grouped kernel takes the lists in reference order, the others sorted by id)
     uint32_t bits_bytes;  // extent of item_bits (the grouped kernel addresses it with 32-bit byte offsets)
     uint32_t n_bytes4;    // 4 * number of training ratings
 };
-
-__device__ __forceinline__ void wave_sync() {
-    // lanes of one wave exchange data through LDS: order the accesses for the compiler (the LDS
-    // queue itself is in order per wave)
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// a pointer whose value is the same in every lane, moved to scalar registers (buffer descriptors must be uniform)
-template <class T>
-__device__ __forceinline__ T* uniform_ptr(T* p) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return reinterpret_cast<T*>(((uint64_t)hi << 32) | lo);
-}
-
 
 template <int CAP, int WAVES>  // per-wave match capacity (power of two >= kcap), waves per block
 __global__ void __launch_bounds__(WAVES * 64) k_predict_knn(PredArgs A, int64_t n, const int32_t* __restrict__ du,
@@ -89,148 +60,10 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn(PredArgs A, int64_t 
     } else if (i < 0) {
         p = combine(ua, 0.0);  // no rater: den = 0 -> 0.0 :527-529
     } else {
-        uint32_t* mt = m_t[wave];
-        double* md = m_dev[wave];
-        double* ms = m_sim[wave];
-        const int32_t cnt = __builtin_amdgcn_readfirstlane(A.nbr_cnt[u]);  // (u is the same in every lane)
-        const int64_t base = (int64_t)u * A.kcap;
-        int32_t total = 0;
-        // "which of u's neighbours rated item i": u's neighbour ids (sorted ascending) are looked up in the
-        // item's rater list (sorted the same way).  All lanes search the SAME array and neighbouring lanes
-        // look for neighbouring ids, so the searches share their cache sectors (the per-neighbour-row
-        // searches they replace touched ~7 private sectors each and were bound by L2 sector bandwidth).
-        const int64_t rb = A.i_ptr[i], re = A.i_ptr[i + 1];
-        if (A.ib_words > 0) {
-            // "Which of u's neighbours rated item i, and where is that rating": item i's rater bitmap (U bits) + rank
-            // prefixes answer it with one 8-byte + one 4-byte read per neighbour.  A prediction is a chain of three
-            // dependent gathers (neighbour ids -> bitmap words -> the matched ratings); with one wave per prediction
-            // the kernel is bound by that latency, so each level is issued for ALL neighbours at once, through buffer
-            // descriptors rooted at the wave's own rows: the loads are unconditional (a lane without a neighbour, or
-            // without a match, uses an out-of-range offset and gets 0) and the compiler can count them instead of
-            // waiting for everything at every use.
-            constexpr int TR = CAP / 64;
-            const int32_t rowlen = __builtin_amdgcn_readfirstlane((int32_t)(re - rb));
-            const int32_t ibw = __builtin_amdgcn_readfirstlane((int32_t)A.ib_words);
-            const auto r_uidx = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(uniform_ptr(A.nbr_uidx + base)), 0, (uint32_t)cnt * 4u, 0x00020000);
-            const auto r_usim = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(uniform_ptr(A.nbr_usim + base)), 0, (uint32_t)cnt * 8u, 0x00020000);
-            const auto r_bits = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned long long*>(uniform_ptr(A.item_bits + (int64_t)i * A.ib_words)), 0, (uint32_t)ibw * 8u, 0x00020000);
-            const auto r_rank = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(uniform_ptr(A.item_rank + (int64_t)i * A.ib_words)), 0, (uint32_t)ibw * 4u, 0x00020000);
-            const auto r_t = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(uniform_ptr(A.it_t + rb)), 0, (uint32_t)rowlen * 4u, 0x00020000);
-            const auto r_dev = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(uniform_ptr(A.it_dev + rb)), 0, (uint32_t)rowlen * 8u, 0x00020000);
-            typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
-            uint32_t x[TR], rk[TR], mtv[TR];
-            u32x2 sv[TR], wd[TR], dv[TR];
-#pragma unroll
-            for (int k = 0; k < TR; ++k) {  // level 1: neighbour ids and similarities (offsets past cnt are out of range)
-                const uint32_t j = 64u * k + lane;
-                x[k] = __builtin_amdgcn_raw_buffer_load_b32(r_uidx, (int)(j * 4u), 0, 0);
-                sv[k] = __builtin_amdgcn_raw_buffer_load_b64(r_usim, (int)(j * 8u), 0, 0);
-            }
-#pragma unroll
-            for (int k = 0; k < TR; ++k) {  // level 2: the bitmap word of each neighbour and the raters before that word
-                const uint32_t wi = (64u * k + lane < (uint32_t)cnt) ? (x[k] >> 6) : 0x0fffffffu;
-                wd[k] = __builtin_amdgcn_raw_buffer_load_b64(r_bits, (int)(wi * 8u), 0, 0);
-                rk[k] = __builtin_amdgcn_raw_buffer_load_b32(r_rank, (int)(wi * 4u), 0, 0);
-            }
-            bool fnd[TR];
-#pragma unroll
-            for (int k = 0; k < TR; ++k) {  // level 3: the matched ratings (file row, deviation)
-                const unsigned long long word = ((unsigned long long)wd[k].y << 32) | wd[k].x;  // (absent neighbour: 0)
-                fnd[k] = (word >> (x[k] & 63u)) & 1ull;
-                const uint32_t q = fnd[k] ? rk[k] + (uint32_t)__popcll(word & ((1ull << (x[k] & 63u)) - 1ull)) : 0x0fffffffu;
-                mtv[k] = __builtin_amdgcn_raw_buffer_load_b32(r_t, (int)(q * 4u), 0, 0);
-                dv[k] = __builtin_amdgcn_raw_buffer_load_b64(r_dev, (int)(q * 8u), 0, 0);
-            }
-#pragma unroll
-            for (int k = 0; k < TR; ++k) {
-                const unsigned long long hit = __ballot(fnd[k]);
-                if (fnd[k]) {
-                    const int32_t slot = total + __builtin_amdgcn_mbcnt_hi((uint32_t)(hit >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hit, 0u));
-                    mt[slot] = mtv[k];
-                    md[slot] = __hiloint2double((int)dv[k].y, (int)dv[k].x);
-                    ms[slot] = __hiloint2double((int)sv[k].y, (int)sv[k].x);
-                }
-                total += __popcll(hit);
-            }
-        } else {
-            // bitmaps not built (they would not fit): u's neighbour ids (sorted ascending) are looked up in the item's
-            // rater list (sorted the same way) by binary search
-            for (int32_t j0 = 0; j0 < cnt; j0 += 64) {
-                const int32_t j = j0 + lane;
-                int64_t lo = rb, hi = rb;
-                int32_t x = 0;
-                double s = 0.0;
-                if (j < cnt) {
-                    x = A.nbr_uidx[base + j];
-                    s = A.nbr_usim[base + j];
-                    hi = re;
-                }
-                while (__any(lo < hi)) {
-                    if (lo < hi) {
-                        const int64_t mid = (lo + hi) >> 1;
-                        if (A.it_user[mid] < x) lo = mid + 1;
-                        else hi = mid;
-                    }
-                }
-                const bool found = j < cnt && lo < re && A.it_user[lo] == x;
-                const unsigned long long hit = __ballot(found);
-                if (found) {
-                    const int32_t slot = total + __popcll(hit & ((1ull << lane) - 1ull));
-                    mt[slot] = A.it_t[lo];
-                    md[slot] = A.it_dev[lo];
-                    ms[slot] = s;
-                }
-                total += __popcll(hit);
-            }
-        }
-        // order the matches by training file row (the order of ratedI(i) :508-517): rank by counting.  Lane l owns
-        // the matches in slots l, l + 64, ...; every lane streams all keys (LDS broadcast reads, 4 keys per read) and
-        // counts the smaller ones; then each match moves to its rank.  No dependent LDS round trips, unlike a sorting
-        // network's 20-40 compare-exchange stages.
-        {
-            constexpr int TRS = CAP / 64;
-            for (int32_t c = total + lane; c < ((total + 3) & ~3); c += 64) mt[c] = 0xffffffffu;  // pad to a multiple of 4
-            wave_sync();
-            uint32_t my_t[TRS], rank[TRS];
-            double my_d[TRS], my_s[TRS];
-#pragma unroll
-            for (int k = 0; k < TRS; ++k) {
-                const int32_t slot = 64 * k + lane;
-                rank[k] = 0;
-                my_t[k] = 0;  // (a slot past `total` counts nothing and is not written back)
-                my_d[k] = 0.0;
-                my_s[k] = 0.0;
-                if (slot < total) {
-                    my_t[k] = mt[slot];
-                    my_d[k] = md[slot];
-                    my_s[k] = ms[slot];
-                }
-            }
-            const int nslot = (total + 63) >> 6;  // wave-uniform
-            const uint4* keys4 = reinterpret_cast<const uint4*>(mt);
-            for (int32_t c = 0; c < ((total + 3) >> 2); ++c) {
-                const uint4 kq = keys4[c];
-#pragma unroll
-                for (int k = 0; k < TRS; ++k) {
-                    if (k < nslot) rank[k] += (uint32_t)(kq.x < my_t[k]) + (uint32_t)(kq.y < my_t[k]) + (uint32_t)(kq.z < my_t[k]) + (uint32_t)(kq.w < my_t[k]);
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < TRS; ++k) {
-                if (64 * k + lane < total) {
-                    md[rank[k]] = my_d[k];
-                    ms[rank[k]] = my_s[k];
-                }
-            }
-            wave_sync();
-        }
-        double num = 0.0, den = 0.0;
-        for (int32_t c = 0; c < total; ++c) {  // every lane folds the same sequence (LDS broadcast)
-            double s = ms[c];
-            num = num + md[c] * s;
-            den = den + fabs(s);
-        }
-        double wsd = (den > 0) ? num / den : 0.0;
+        // the neighbours of u that rated i, in training-file order (knn_terms.h), folded left in fp64
+        const int32_t total = wave_knn_matches<CAP, false>(A.P, u, i, A.P.i_ptr[i], A.P.i_ptr[i + 1], lane, m_t[wave], nullptr, m_dev[wave], m_sim[wave]);
+        const NumDen f = fold_terms(m_dev[wave], m_sim[wave], total);
+        double wsd = (f.den > 0) ? f.num / f.den : 0.0;
         p = combine(ua, wsd);
     }
     if (lane == 0) {
@@ -248,7 +81,9 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn(PredArgs A, int64_t 
 //   * the user's neighbour list stays in registers across all his rows;
 //   * G rows are in flight together, and each gather level is issued for all their neighbours at once, through buffer
 //     descriptors: unconditional, counted loads (a lane without a neighbour or a match reads out of range and gets 0).
-// Matches are ordered by training file row with a counting rank and folded left in fp64 exactly as in k_predict_knn.
+// Matches are ordered by training file row with a counting rank and folded left in fp64 exactly as in k_predict_knn: the probe,
+// rank and fold below are bitmap_has / bitmap_place, rank_by_file_row and fold_terms of knn_terms.h SPELLED OUT — through the helpers
+// the compiler schedules this kernel differently (DESIGN.md "The shared kNN term core"); a change to one is a change to both.
 template <int TR, int G, int WAVES>  // TR = 64-neighbour trips covering kcap; G rows in flight; waves per block
 __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_rows(PredArgs A, int64_t n, const int32_t* __restrict__ du,
                                                              const int32_t* __restrict__ di, const double* __restrict__ ratings,
@@ -280,22 +115,21 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_rows(PredArgs A, int
         my_mine = (my_u < 0) ? (unknown_owned != 0) : (my_u >= A.own_lo && my_u < A.own_hi);
         if (my_u >= 0) {
             my_ua = A.user_avg[my_u];  // usersAvgValue.getOrElse(u, -1.0) :572
-            my_cnt = A.nbr_cnt[my_u];
+            my_cnt = A.P.nbr_cnt[my_u];
         }
         if (my_i >= 0) {
-            my_rb = (uint32_t)A.i_ptr[my_i];
-            my_len = (uint32_t)A.i_ptr[my_i + 1] - my_rb;
+            my_rb = (uint32_t)A.P.i_ptr[my_i];
+            my_len = (uint32_t)A.P.i_ptr[my_i + 1] - my_rb;
         }
         my_p = (my_ua < 0.0) ? A.global_avg : combine(my_ua, 0.0);  // unknown user / no rater: den = 0 -> 0.0 :527-529
     }
     const bool my_active = lane < nr && my_mine && my_ua >= 0.0 && my_i >= 0 && my_cnt > 0 && my_len > 0;
     const unsigned long long active = __ballot(my_active);
-    const auto r_bits = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned long long*>(A.item_bits), 0, A.bits_bytes, 0x00020000);
-    const auto r_rank = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(A.item_rank), 0, A.bits_bytes / 2, 0x00020000);
-    const auto r_t = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(A.it_t), 0, A.n_bytes4, 0x00020000);
-    const auto r_dev = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(A.it_dev), 0, A.n_bytes4 * 2, 0x00020000);
-    const uint32_t ibw = (uint32_t)A.ib_words;
-    typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+    const auto r_bits = raw_buffer(A.P.item_bits, A.bits_bytes);
+    const auto r_rank = raw_buffer(A.P.item_rank, A.bits_bytes / 2);
+    const auto r_t = raw_buffer(A.P.it_t, A.n_bytes4);
+    const auto r_dev = raw_buffer(A.P.it_dev, A.n_bytes4 * 2);
+    const uint32_t ibw = (uint32_t)A.P.ib_words;
     uint32_t x[TR];
     u32x2 sv[TR];
     int32_t cur_u = -1, cur_cnt = 0;
@@ -306,9 +140,9 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_rows(PredArgs A, int
         if (u != cur_u) {  // a new user: his neighbours (ids ascending) and their similarities
             cur_u = u;
             cur_cnt = __builtin_amdgcn_readlane(my_cnt, r);
-            const int64_t base = (int64_t)u * A.kcap;
-            const auto r_uidx = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(A.nbr_uidx + base), 0, (uint32_t)cur_cnt * 4u, 0x00020000);
-            const auto r_usim = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(A.nbr_usim + base), 0, (uint32_t)cur_cnt * 8u, 0x00020000);
+            const int64_t base = (int64_t)u * A.P.kcap;
+            const auto r_uidx = raw_buffer(A.P.nbr_idx + base, (uint32_t)cur_cnt * 4u);
+            const auto r_usim = raw_buffer(A.P.nbr_sim + base, (uint32_t)cur_cnt * 8u);
 #pragma unroll
             for (int k = 0; k < TR; ++k) {
                 const uint32_t j = 64u * k + lane;
@@ -322,7 +156,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_rows(PredArgs A, int
 #pragma unroll
         for (int g = 0; g < G; ++g) {
             rows[g] = -1;
-            bbase[g] = 0x0fffffffu;
+            bbase[g] = NO_ENTRY;
             rbase[g] = 0;
             if (r < nr && ((active >> r) & 1ull) && __builtin_amdgcn_readlane(my_u, min(r, 63)) == cur_u) {
                 rows[g] = r;
@@ -337,7 +171,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_rows(PredArgs A, int
         for (int g = 0; g < G; ++g)
 #pragma unroll
             for (int k = 0; k < TR; ++k) {  // the bitmap word of each neighbour and the raters before that word
-                const uint32_t wi = (rows[g] >= 0 && 64u * k + lane < (uint32_t)cur_cnt) ? bbase[g] + (x[k] >> 6) : 0x0fffffffu;
+                const uint32_t wi = (rows[g] >= 0 && 64u * k + lane < (uint32_t)cur_cnt) ? bbase[g] + (x[k] >> 6) : NO_ENTRY;
                 wd[g][k] = __builtin_amdgcn_raw_buffer_load_b64(r_bits, (int)(wi * 8u), 0, 0);
                 rk[g][k] = __builtin_amdgcn_raw_buffer_load_b32(r_rank, (int)(wi * 4u), 0, 0);
             }
@@ -349,7 +183,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_rows(PredArgs A, int
                 const unsigned long long word = ((unsigned long long)wd[g][k].y << 32) | wd[g][k].x;  // (absent: 0)
                 const bool f = (word >> (x[k] & 63u)) & 1ull;
                 fmask[g][k] = __ballot(f);
-                const uint32_t q = f ? rbase[g] + rk[g][k] + (uint32_t)__popcll(word & ((1ull << (x[k] & 63u)) - 1ull)) : 0x0fffffffu;
+                const uint32_t q = f ? rbase[g] + rk[g][k] + (uint32_t)__popcll(word & ((1ull << (x[k] & 63u)) - 1ull)) : NO_ENTRY;
                 mtv[g][k] = __builtin_amdgcn_raw_buffer_load_b32(r_t, (int)(q * 4u), 0, 0);
                 dv[g][k] = __builtin_amdgcn_raw_buffer_load_b64(r_dev, (int)(q * 8u), 0, 0);
             }
@@ -361,15 +195,15 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_rows(PredArgs A, int
             for (int k = 0; k < TR; ++k) {
                 const unsigned long long hit = fmask[g][k];
                 if ((hit >> lane) & 1ull) {
-                    const int32_t slot = total + __builtin_amdgcn_mbcnt_hi((uint32_t)(hit >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hit, 0u));
+                    const int32_t slot = total + lanes_below(hit);
                     mt[slot] = mtv[g][k];
-                    md[slot] = __hiloint2double((int)dv[g][k].y, (int)dv[g][k].x);
-                    ms[slot] = __hiloint2double((int)sv[k].y, (int)sv[k].x);
+                    md[slot] = as_double(dv[g][k]);
+                    ms[slot] = as_double(sv[k]);
                 }
                 total += __popcll(hit);
             }
             // order the matches by training file row (the order of ratedI(i) :508-517): rank by counting
-            for (int32_t c = total + lane; c < ((total + 3) & ~3); c += 64) mt[c] = 0xffffffffu;
+            for (int32_t c = total + lane; c < ((total + 3) & ~3); c += 64) mt[c] = 0xffffffffu;  // (pad_file_rows)
             wave_sync();
             uint32_t key[TR], rank[TR];
             double kd[TR], ks[TR];
@@ -428,6 +262,10 @@ __device__ unsigned long long g_pphase[8];
 // current item's bitmap + rank prefixes in LDS (30 KB): it is fetched once per run of rows of that item, the probes
 // become LDS reads, and what remains in global memory is the coalesced stream of each row's neighbour ids and the
 // gathers of the ~14 matched ratings and similarities.
+// This is the kernel of the benchmark step and its instruction stream is kept as it is: the LDS probe, the counting loop and
+// the folds below are lds_pair_probe, rank_by_file_row's count and fold_terms of knn_terms.h SPELLED OUT — through the helpers
+// the compiler orders the probe's LDS reads differently and holds more registers (DESIGN.md "The shared kNN term core"); a
+// change to one is a change to both.
 template <int TR, int G, int WAVES>
 __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_items(PredArgs A, int64_t n, const int32_t* __restrict__ du,
                                                               const int32_t* __restrict__ di, const double* __restrict__ ratings,
@@ -442,7 +280,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_items(PredArgs A, in
     constexpr int MCAP = 64;
     constexpr int CHUNK = PRED_CHUNK;  // rows per workgroup
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int ibw = (int)A.ib_words;
+    const int ibw = (int)A.P.ib_words;
     const int ibw2 = (ibw + 1) >> 1;  // pairs of bitmap words
     // the rank prefixes are kept for every SECOND word only (the odd word adds the popcount of its even neighbour, which
     // comes with the same 16-byte LDS read): 25 instead of 30 KB, which is what lets a third workgroup onto the CU
@@ -474,8 +312,8 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_items(PredArgs A, in
         double ua = -1.0;  // usersAvgValue.getOrElse(u, -1.0) :572
         int32_t cnt = 0;
         uint32_t rb = 0, len = 0;
-        if (u >= 0) { ua = A.user_avg[u]; cnt = A.nbr_cnt[u]; }
-        if (i >= 0) { rb = (uint32_t)A.i_ptr[i]; len = (uint32_t)A.i_ptr[i + 1] - rb; }
+        if (u >= 0) { ua = A.user_avg[u]; cnt = A.P.nbr_cnt[u]; }
+        if (i >= 0) { rb = (uint32_t)A.P.i_ptr[i]; len = (uint32_t)A.P.i_ptr[i + 1] - rb; }
         s_row[l] = row; s_u[l] = u; s_i[l] = i; s_cnt[l] = cnt; s_rb[l] = rb; s_ua[l] = ua;
         s_p[l] = (ua < 0.0) ? A.global_avg : combine(ua, 0.0);  // unknown user / no rater: den = 0 -> 0.0 :527-529
         s_mine[l] = mine ? 1 : 0;
@@ -483,9 +321,8 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_items(PredArgs A, in
     }
     __syncthreads();
     PPH(0);  // the rows' own data
-    const auto r_t = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(A.it_t), 0, A.n_bytes4, 0x00020000);
-    const auto r_dev = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(A.it_dev), 0, A.n_bytes4 * 2, 0x00020000);
-    typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+    const auto r_t = raw_buffer(A.P.it_t, A.n_bytes4);
+    const auto r_dev = raw_buffer(A.P.it_dev, A.n_bytes4 * 2);
     int ra = 0;
     while (ra < nr) {  // runs of rows of one item (every thread walks the same LDS values: block-uniform)
         const int32_t item = s_i[ra];
@@ -493,8 +330,8 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_items(PredArgs A, in
         bool any = s_active[ra] != 0;
         while (rbn < nr && s_i[rbn] == item) { any = any || s_active[rbn] != 0; ++rbn; }
         if (any) {
-            const unsigned long long* gb = A.item_bits + (int64_t)item * ibw;
-            const uint32_t* gr = A.item_rank + (int64_t)item * ibw;
+            const unsigned long long* gb = A.P.item_bits + (int64_t)item * ibw;
+            const uint32_t* gr = A.P.item_rank + (int64_t)item * ibw;
             // every load of a batch is requested before the first is used (twelve bitmap words and six rank words per thread
             // and batch: ONE batch up to 196 608 users).  One word per trip of a plain loop paid ten dependent global
             // latencies per run — a third of the kernel's time by its phase counters (scripts/phase_profile.sh)
@@ -540,9 +377,9 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_items(PredArgs A, in
                     const int32_t u = __builtin_amdgcn_readfirstlane(on ? s_u[rr] : 0);
                     cnts[g] = __builtin_amdgcn_readfirstlane(on ? s_cnt[rr] : 0);
                     rbase[g] = (uint32_t)__builtin_amdgcn_readfirstlane(on ? (int)s_rb[rr] : 0);
-                    const int64_t base = (int64_t)u * A.kcap;
-                    const auto r_uidx = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(uniform_ptr(A.nbr_uidx + base)), 0, (uint32_t)cnts[g] * 4u, 0x00020000);
-                    r_usim[g] = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(uniform_ptr(A.nbr_usim + base)), 0, (uint32_t)cnts[g] * 8u, 0x00020000);
+                    const int64_t base = (int64_t)u * A.P.kcap;
+                    const auto r_uidx = raw_buffer(uniform_ptr(A.P.nbr_idx + base), (uint32_t)cnts[g] * 4u);
+                    r_usim[g] = raw_buffer(uniform_ptr(A.P.nbr_sim + base), (uint32_t)cnts[g] * 8u);
 #pragma unroll
                     for (int k = 0; k < TR; ++k) {  // the row's neighbours (ids ascending); past cnt: 0
                         const uint32_t j = 64u * k + lane;
@@ -568,7 +405,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_items(PredArgs A, in
                         const bool f = have && ((word >> (xi & 63u)) & 1ull);
                         fmask[g][k] = __ballot(f);
                         const uint32_t before = rnk[wi >> 1] + ((wi & 1u) ? (uint32_t)__popcll(pair.x) : 0u);
-                        const uint32_t q = f ? rbase[g] + before + (uint32_t)__popcll(word & ((1ull << (xi & 63u)) - 1ull)) : 0x0fffffffu;
+                        const uint32_t q = f ? rbase[g] + before + (uint32_t)__popcll(word & ((1ull << (xi & 63u)) - 1ull)) : NO_ENTRY;
                         mtv[g][k] = __builtin_amdgcn_raw_buffer_load_b32(r_t, (int)(q * 4u), 0, 0);
                         dv[g][k] = __builtin_amdgcn_raw_buffer_load_b64(r_dev, (int)(q * 8u), 0, 0);
                         // the similarity is needed for the ~5 % of neighbours that rated the item only: it is gathered
@@ -596,10 +433,10 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_items(PredArgs A, in
                         for (int k = 0; k < TR; ++k) {
                             const unsigned long long hit = fmask[g][k];
                             if ((hit >> lane) & 1ull) {
-                                const int32_t slot = seen + __builtin_amdgcn_mbcnt_hi((uint32_t)(hit >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hit, 0u));
+                                const int32_t slot = seen + lanes_below(hit);
                                 mt[slot] = mtv[g][k];
-                                md[slot] = __hiloint2double((int)dv[g][k].y, (int)dv[g][k].x);
-                                ms[slot] = __hiloint2double((int)sv[g][k].y, (int)sv[g][k].x);
+                                md[slot] = as_double(dv[g][k]);
+                                ms[slot] = as_double(sv[g][k]);
                             }
                             seen += __popcll(hit);
                         }
@@ -624,11 +461,10 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_items(PredArgs A, in
                         for (int k = 0; k < TR; ++k) {
                             const unsigned long long hit = fmask[g][k];
                             if ((hit >> lane) & 1ull)
-                                mt[seen + __builtin_amdgcn_mbcnt_hi((uint32_t)(hit >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hit, 0u))] = mtv[g][k];
+                                mt[seen + lanes_below(hit)] = mtv[g][k];
                             seen += __popcll(hit);
                         }
-                        for (int32_t c = total + lane; c < ((total + 3) & ~3); c += 64) mt[c] = 0xffffffffu;
-                        wave_sync();
+                        pad_file_rows(mt, total, lane);
                         uint32_t rank[TR];
 #pragma unroll
                         for (int k = 0; k < TR; ++k) rank[k] = 0;
@@ -646,8 +482,8 @@ __global__ void __launch_bounds__(WAVES * 64) k_predict_knn_items(PredArgs A, in
                             for (int k = 0; k < TR; ++k) {
                                 const uint32_t at = rank[k] - (uint32_t)b0;
                                 if (((fmask[g][k] >> lane) & 1ull) && at < (uint32_t)MCAP) {
-                                    md[at] = __hiloint2double((int)dv[g][k].y, (int)dv[g][k].x);
-                                    ms[at] = __hiloint2double((int)sv[g][k].y, (int)sv[g][k].x);
+                                    md[at] = as_double(dv[g][k]);
+                                    ms[at] = as_double(sv[g][k]);
                                 }
                             }
                             wave_sync();
@@ -791,23 +627,11 @@ void launch_predict(const Train& tr, NeighborTable* nt, int predictor, int64_t n
     A.own_lo = tr.own_lo; A.own_hi = tr.own_hi;
     if (predictor == KNNCF_PRED_KNN) {
         KN_REQUIRE(nt != nullptr, KNNCF_E_STATE, "predict: neighbour table missing");
-        A.nbr_cnt = nt->cnt.p; A.kcap = nt->kcap;
         // The item-grouped kernel probes an LDS bitmap and orders its matches by file row: the order of a list does not
         // matter to it, and it streams the lists as the re-rank left them (reference order).  The kernels that probe in global
-        // memory want neighbouring lanes on neighbouring ids (cache sectors): they take the id-sorted copies, made here on
-        // first need (0.7 ms per step at the ml-25m shape when it was part of every build).
+        // memory take the id-sorted copies.
         const bool items_path = d_order && order_by_item && tr.ib_words > 0 && lds_bitmap_fits(tr.ib_words) && nt->kcap <= 512;
-        if (items_path && nt->idx.p != nullptr) {
-            A.nbr_uidx = nt->idx.p; A.nbr_usim = nt->sim.p;
-        } else {
-            if (!nt->by_id_valid) {
-                launch_sort_neighbors(*nt, tr.U, tr.U, nullptr, st);
-                nt->by_id_valid = true;
-            }
-            A.nbr_uidx = nt->uidx.p; A.nbr_usim = nt->usim.p;
-        }
-        A.i_ptr = tr.i_ptr.p; A.it_user = tr.it_user.p; A.it_dev = tr.it_dev.p; A.it_t = tr.it_t.p;
-        A.ib_words = tr.ib_words; A.item_bits = reinterpret_cast<const unsigned long long*>(tr.item_bits.p); A.item_rank = tr.item_rank.p;
+        A.P = probe_args(tr, *nt, /*by_id=*/!(items_path && nt->idx.p != nullptr), st);
         const double bits_total = (double)tr.I * (double)tr.ib_words * 8.0;
         if (items_path) {
             A.n_bytes4 = (uint32_t)(tr.n * 4);

@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "engine.h"
+#include "wave_helpers.h"
 
 namespace knncf {
 
@@ -239,13 +240,6 @@ typedef const __attribute__((address_space(3))) double* lds_cf64;
 typedef __attribute__((address_space(3))) double* lds_f64;
 typedef const __attribute__((address_space(3))) uint32_t* lds_cu32;
 
-__device__ __forceinline__ void wave_sync() {
-    // lanes of one wave exchange data through LDS: order the accesses for the compiler (the LDS queue
-    // itself is in order per wave)
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 #ifdef KNNCF_RERANK_PROFILE
 __device__ unsigned long long g_rphase[8];
 #define RPH(i) do { if (threadIdx.x == 0) { const long long now_ = clock64(); atomicAdd(&g_rphase[i], (unsigned long long)(now_ - ph_t)); ph_t = now_; } } while (0)
@@ -345,7 +339,7 @@ __device__ __forceinline__ double wave_sims(const Rows& R, lds_cu32x2 bp, PreP u
             // and J0 - 1, which are wave-uniform and ride in the shift-add that turns the index into a byte offset (a VALU
             // instruction reads one SGPR: the mask words and the addend cannot share the v_mbcnt)
             const unsigned long long mh = m >> 1;
-            const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(mh >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mh, 0u));
+            const uint32_t below = (uint32_t)lanes_below(mh);
             uint32_t jb4 = (j0 + (uint32_t)(m & 1ull) - 1u) << 2;
             asm("" : "+s"(jb4));  // (opaque: stays one scalar addend of the shift-add)
             const uint32_t jf4 = (below << 2) + jb4;
