@@ -53,9 +53,11 @@ def combine(oracle, ua, num, den):
 
 
 class TermModel:
-    def __init__(self, oracle, model, sim_kind, k):
+    def __init__(self, oracle, model, sim_kind, k, pipeline=None):
+        """pipeline: an existing Pipeline(model, sim_kind, k) whose memo the terms share (tests/call_sequences.py); a fresh one
+        by default"""
         self.oracle, self.model = oracle, model
-        self.pipeline = model.pipeline(sim_kind, k)
+        self.pipeline = pipeline if pipeline is not None else model.pipeline(sim_kind, k)
         self.dev = model.normalized_deviations()
         order = np.argsort(model.items, kind="stable")  # (stable: the rows of an item stay in file order)
         items, first = np.unique(model.items[order], return_index=True)
