@@ -766,6 +766,59 @@ int knncf_revise_recommend_explain_batch(knncf_handle* h, int predictor, const i
                                          int32_t* out_items, double* out_preds, int32_t* counts, int32_t* raters, double* sims,
                                          double* devs, int32_t* term_counts, double* sums, int32_t* statuses);
 
+/* ---- Bystander queries: a FITTED user's kNN answers once a newcomer has joined the data --------------------------------------
+ * recommend/Recommender.scala:68-89 asks two things of aug = data.union(personal): the newcomer's top n (knncf_query_recommend)
+ * and predictor(aug, ...)(1, 1), the prediction of a user who was in the data all along.  The newcomer is one more candidate of
+ * that user's neighbour list, one more rater (the last in file order) of every item it rated, and it shifts average(aug).  These
+ * calls answer for such bystanders WITHOUT a refit.
+ * A query is a fold-in query exactly as above: a raw id `user` absent from train with rows (items[j], ratings[j]), and aug =
+ * train ++ those rows in order.  A ROW of the query names a bystander, a raw user id others[r] != user, and in the predict forms
+ * a raw item pred_items[r].  Every row is answered on closures of its own over aug whose first evaluation is the row's, bit for
+ * bit:
+ *   knncf_query_bystander_neighbors  getNeighbors(aug, k, sim)(others[r]) :596-617 into row r of ids / sims (row stride cap): raw
+ *                                    ids, the newcomer's own id where it is a neighbour; counts[r] = the list's length, which may
+ *                                    exceed cap: min(k, U) for a user of the fit (U - 1 train users and the newcomer), and for a
+ *                                    user unknown to aug the first min(k, U + 1) users of aug in set order with similarity +0.0,
+ *                                    as knncf_neighbors answers on train.  Cells past the written entries are untouched.
+ *   knncf_query_bystander_predict    out[r] = predictor(aug, weightedSumDeviation(aug, getSimilarity(aug, k, sim)))(others[r],
+ *                                    pred_items[r]) :489-585 for any item id.  A bystander unknown to aug or with a negative
+ *                                    mean gets average(aug) :573: the fit's running total of the train ratings in file order,
+ *                                    continued over the query's ratings in the given order, divided by n + n_ratings.
+ * The bystander owns every pair: S(v, x) folds the common items in v's item-set order (file order for a v of <= 4 ratings),
+ * also for x = the newcomer.  Rows are independent; the same bystander may occur many times.
+ * Batch forms.  Query b is (users[b], items / ratings [offsets[b], offsets[b + 1])) as in "Batched fold-in queries"; its rows
+ * are others / pred_items [row_offsets[b], row_offsets[b + 1]) (row_offsets: a CSR like pred_offsets, fewer than 2^31 rows), and
+ * ids / sims / counts / out are indexed by row.  The single forms are the batch of one query and return the query's status.
+ * Statuses.  Per-query statuses and the return values are those of knncf_query_predict_batch, and in addition a query with a
+ * row whose others[r] == users[b] gets KNNCF_E_INVALID (ask knncf_query_predict), a query with a bystander of more than 65536
+ * train ratings KNNCF_E_UNSUPPORTED.  predictor must be KNNCF_PRED_KNN (KNNCF_E_UNSUPPORTED otherwise).  KNNCF_E_INVALID for
+ * cap < 0.  A failed query leaves its rows of out / ids / sims untouched and gets counts = 0 on its rows.  n_queries == 0, or a
+ * query without rows, is fine and writes nothing (the query still gets its status).
+ * Chunks.  The unit is a SLOT.  An answerable query takes one slot for its own prepared row, plus one per distinct bystander that
+ * is known to train and — in the predict forms — whose mean is not negative; the other bystanders need none.
+ *     C = max(2, min(64, budget / (64 * num_users + 96 * num_items), (2^31 - 1) / max(num_users, num_items)))
+ *     budget = workspace_bytes / 2 if workspace_bytes > 0, else min(48 GiB, free device memory / 4)
+ * Queries are packed into chunks of C slots in order; a query with more bystanders than fit beside its own slot continues in the
+ * next chunk, where its row is prepared again.  (The gathered neighbour ratings are allocated beside the budget, as in "Batched
+ * fold-in queries".)  The results do not depend on C, and a call on a handle that has answered the same shape before allocates
+ * no device memory.
+ * Handle state.  Read-only in the sense of the other families: the neighbour table, its build numbers, its epoch and the
+ * knncf_neighbors_save bytes stay as they were.  knncf_get_timings: charged as the fold-in calls charge theirs.
+ * OUT OF SCOPE: bystanders of update and revise queries (a newcomer that is in the fit changes its own mean, and with it the
+ * deviation of every one of its train rows in other users' folds); KNNCF_PRED_PERSONALIZED and the other predictors;
+ * recommendations and explanations for a bystander; "which fitted users does the newcomer enter"; device-pointer forms; shard
+ * handles and knncf_group_*. */
+int knncf_query_bystander_neighbors(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
+                                    const int32_t* others, int64_t m, int32_t cap, int32_t* ids, double* sims, int32_t* counts);
+int knncf_query_bystander_predict(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
+                                  int64_t n_ratings, const int32_t* others, const int32_t* pred_items, int64_t m, double* out);
+int knncf_query_bystander_neighbors_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                                          const double* ratings, int64_t n_queries, const int64_t* row_offsets, const int32_t* others,
+                                          int32_t cap, int32_t* ids, double* sims, int32_t* counts, int32_t* statuses);
+int knncf_query_bystander_predict_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets,
+                                        const int32_t* items, const double* ratings, int64_t n_queries, const int64_t* row_offsets,
+                                        const int32_t* others, const int32_t* pred_items, double* out, int32_t* statuses);
+
 /* ---- batch ---------------------------------------------------------------- */
 int knncf_predict_batch(knncf_handle* h, int predictor, const int32_t* users,
                         const int32_t* items, int64_t n, double* out);

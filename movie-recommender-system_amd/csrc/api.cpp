@@ -1052,13 +1052,17 @@ constexpr int64_t QUERY_MAX_RATINGS = 65536;
 // that QB_EXPLAIN keeps refusing that predictor
 // QB_RECOMMEND_EXPLAIN: QB_RECOMMEND, then the explain kernel of the predictor over the rows the selection produced
 // (knncf_*_recommend_explain*): no requested rows, so neither explains() nor wants_rows()
-enum QueryBatchMode { QB_NEIGHBORS, QB_PREDICT, QB_RECOMMEND, QB_EXPLAIN, QB_EXPLAIN_ALL, QB_RECOMMEND_EXPLAIN };
+// QB_BY_NEIGHBORS / QB_BY_PREDICT: bystander queries (knncf_query_bystander_*) — the rows of a query name fitted users, and the
+// chunk loop is run_bystander_chunks
+enum QueryBatchMode { QB_NEIGHBORS, QB_PREDICT, QB_RECOMMEND, QB_EXPLAIN, QB_EXPLAIN_ALL, QB_RECOMMEND_EXPLAIN, QB_BY_NEIGHBORS, QB_BY_PREDICT };
+bool bystanders(QueryBatchMode mode) { return mode == QB_BY_NEIGHBORS || mode == QB_BY_PREDICT; }
 bool explains(QueryBatchMode mode) { return mode == QB_EXPLAIN || mode == QB_EXPLAIN_ALL; }
 bool recommends(QueryBatchMode mode) { return mode == QB_RECOMMEND || mode == QB_RECOMMEND_EXPLAIN; }
 enum QueryFamily { QF_FOLD_IN, QF_UPDATE, QF_REVISE };
 
 // what the handle must be for any fold-in query, single or batched
 void require_query_support(knncf_handle* h, int predictor, QueryBatchMode mode) {
+    KN_REQUIRE(!bystanders(mode) || predictor == KNNCF_PRED_KNN, KNNCF_E_UNSUPPORTED, "query bystander: only KNNCF_PRED_KNN");
     KN_REQUIRE(mode != QB_EXPLAIN_ALL || predictor == KNNCF_PRED_PERSONALIZED, KNNCF_E_UNSUPPORTED, "query explain: only KNNCF_PRED_PERSONALIZED");
     KN_REQUIRE(predictor == KNNCF_PRED_KNN || (predictor == KNNCF_PRED_PERSONALIZED && mode != QB_EXPLAIN), KNNCF_E_UNSUPPORTED,
                mode == QB_EXPLAIN ? "query explain: only KNNCF_PRED_KNN" : "query: only KNNCF_PRED_KNN and KNNCF_PRED_PERSONALIZED");
@@ -1143,6 +1147,8 @@ struct QueryCall {
     const int32_t* removed_items;    // QF_REVISE: the train items each query's user drops
     const int64_t* pred_offsets;     // QB_PREDICT, explain modes: [B + 1] into pred_items; row j of the call is pred_items[j]
     const int32_t* pred_items;       // QB_PREDICT, explain modes: the requested items
+    const int32_t* others;           // bystander modes: the fitted user of each row (rows: pred_offsets; QB_BY_PREDICT: with pred_items)
+    int32_t* row_counts;             // QB_BY_NEIGHBORS: [pred_offsets[B]] (counts stays null: the answers are per row)
     int32_t width;                   // QB_NEIGHBORS: cap; QB_RECOMMEND, QB_RECOMMEND_EXPLAIN: n
     int32_t* out_i;                  // QB_NEIGHBORS: ids [B * cap]; QB_RECOMMEND*: items [B * n]; unused otherwise
     double* out_d;                   // QB_NEIGHBORS: sims [B * cap]; QB_RECOMMEND*: predictions [B * n]; QB_PREDICT: [pred_offsets[B]]
@@ -1450,6 +1456,8 @@ QueryFailure run_query_chunks(knncf_handle* h, const QueryCall& q, int64_t chunk
             case QB_EXPLAIN_ALL: answer_explain(h, q, cs, ex_rows); break;
             case QB_RECOMMEND: answer_recommend(h, q, cs); break;
             case QB_RECOMMEND_EXPLAIN: answer_recommend_explain(h, q, cs, ex_rows); break;
+            case QB_BY_NEIGHBORS:
+            case QB_BY_PREDICT: break;  // (run_bystander_chunks answers these)
         }
     }
     return cs.first;
@@ -1549,6 +1557,233 @@ void do_query_single(knncf_handle* h, const QueryCall& call) {
 
 int query_batch(knncf_handle* h, const QueryCall& q) { return guarded(h, [&] { do_query_batch(h, q); }); }
 int query_single(knncf_handle* h, const QueryCall& q) { return guarded(h, [&] { do_query_single(h, q); }); }
+
+// ---- bystander queries: fitted users' answers on aug = train ++ a newcomer's rows (bystander.hip) ----------------------------
+// A query is a fold-in query (pack_chunk admits it, settle_statuses gives it its status); its rows name bystanders.  The unit
+// of a chunk is a slot: the newcomer's own, then one per distinct bystander that needs the device — a user of the fit, in
+// QB_BY_PREDICT with a mean >= 0.  The rows of the other bystanders are answered on the host once the query's status is known.
+constexpr int32_t BY_NO_SLOT = -1;
+struct ByRow {
+    int64_t row;   // of the call
+    int32_t slot;  // the bystander's slot in the chunk, or BY_NO_SLOT
+    int32_t own;   // the newcomer's slot in the chunk
+};
+struct ByChunkState {
+    std::vector<int32_t> qslot, qrank;
+    std::vector<ByRow> rows;
+    void clear() { qslot.clear(); qrank.clear(); rows.clear(); }
+};
+
+// slots per chunk: the rule of knncf.h ("Bystander queries")
+int64_t bystander_chunk(knncf_handle* h, int64_t budget) { return std::max<int64_t>(2, query_batch_chunk(h, budget)); }
+
+// average(aug) :18: the fit's left fold of the train ratings, continued over query b's ratings in the given order
+double aug_average(knncf_handle* h, const QueryCall& q, int64_t b) {
+    double t = h->tr.total;
+    for (int64_t j = q.offsets[b]; j < q.offsets[b + 1]; ++j) t = t + q.ratings[j];
+    return t / (double)(h->tr.n + (q.offsets[b + 1] - q.offsets[b]));
+}
+
+// the chunk in cs / bc through the device, then the answers of its rows
+void answer_bystander_chunk(knncf_handle* h, const QueryCall& q, ChunkState& cs, ByChunkState& bc) {
+    if (cs.C == 0) return;
+    QueryBatchScratch& bs = h->query_batch;
+    hipStream_t st = h->stream;
+    const int32_t U = h->tr.U, take = cs.take;
+    cs.info.assign((size_t)4 * cs.C, 0);
+    const ByChunk by{bc.qslot.data(), bc.qrank.data()};
+    foldin_batch_neighbors(h->tr, bs, h->prep.sort, cs.C, cs.s_users.data(), cs.qo.data(), cs.s_items.data(), cs.s_ratings.data(),
+                           cs.s_self.data(), cs.ao.data(), h->cfg.k, cs.info.data(), st, nullptr, nullptr, true, &by);
+    // a bystander slot stands or falls with its newcomer: the slot's own bits (a negative mean of the bystander, which
+    // getNeighbors does not look at) are no status of the query
+    for (int32_t s = 0; s < cs.C; ++s)
+        if (bc.qslot[s] != s) cs.info[4 * s] = cs.info[4 * bc.qslot[s]];
+    if (settle_statuses(q, cs) == 0) return;
+    auto good = [&](const ByRow& r) { return q.statuses[cs.slot_query[r.own]] == KNNCF_OK; };
+    if (q.mode == QB_BY_NEIGHBORS) {
+        const int32_t width = q.width, c = std::min(take, width);
+        if (c > 0) {
+            cs.h_idx.resize((size_t)cs.C * take); cs.h_vals.resize((size_t)cs.C * take);
+            KN_HIP(hipMemcpyAsync(cs.h_idx.data(), bs.nbr_idx.p, cs.h_idx.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            KN_HIP(hipMemcpyAsync(cs.h_vals.data(), bs.nbr_sim.p, cs.h_vals.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+            KN_HIP(hipStreamSynchronize(st));
+        }
+        for (const ByRow& r : bc.rows) {
+            if (!good(r)) continue;
+            const int32_t newcomer = cs.s_users[r.own], at = bc.qrank[r.own];
+            int32_t* ids = q.out_i + r.row * width;
+            double* sims = q.out_d + r.row * width;
+            if (r.slot == BY_NO_SLOT) {  // unknown to aug: every similarity is 0.0, ties keep the set order of aug's users
+                const int32_t n = (int32_t)std::min<int64_t>(h->cfg.k, (int64_t)U + 1);
+                for (int32_t j = 0; j < std::min(n, width); ++j) {
+                    ids[j] = j < at ? h->h_uid[j] : j == at ? newcomer : h->h_uid[j - 1];
+                    sims[j] = 0.0;
+                }
+                q.row_counts[r.row] = std::max(n, 0);
+                continue;
+            }
+            for (int32_t j = 0; j < c; ++j) {
+                const int32_t v = cs.h_idx[(size_t)r.slot * take + j];
+                ids[j] = v == U ? newcomer : h->h_uid[v];
+                sims[j] = cs.h_vals[(size_t)r.slot * take + j];
+            }
+            q.row_counts[r.row] = take;
+        }
+        return;
+    }
+    cs.pick_slot.clear(); cs.pick_items.clear(); cs.pick_row.clear();
+    for (const ByRow& r : bc.rows) {
+        if (!good(r)) continue;
+        if (r.slot == BY_NO_SLOT) {
+            q.out_d[r.row] = aug_average(h, q, cs.slot_query[r.own]);
+            continue;
+        }
+        cs.pick_items.push_back(q.pred_items[r.row]);
+        cs.pick_slot.push_back(r.slot);
+        cs.pick_row.push_back(r.row);
+    }
+    const int64_t m = (int64_t)cs.pick_items.size();
+    if (m == 0) return;
+    cs.ebase.assign((size_t)cs.C + 1, 0);
+    for (int32_t s = 0; s < cs.C; ++s) cs.ebase[s + 1] = cs.ebase[s] + cs.info[4 * s + 2];
+    foldin_batch_predictions(h->tr, bs, h->prep.sort, cs.C, take, cs.ebase.data(), st, true);
+    bs.pick_items.ensure(m); bs.pick_slot.ensure(m); bs.pick_out.ensure(m);
+    KN_HIP(hipMemcpyAsync(bs.pick_items.p, cs.pick_items.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    KN_HIP(hipMemcpyAsync(bs.pick_slot.p, cs.pick_slot.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    bystander_pick(h->tr, bs, bs.pick_items.p, bs.pick_slot.p, m, bs.pick_out.p, st);
+    cs.h_vals.resize((size_t)m);
+    KN_HIP(hipMemcpyAsync(cs.h_vals.data(), bs.pick_out.p, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
+    KN_HIP(hipStreamSynchronize(st));
+    for (int64_t j = 0; j < m; ++j) q.out_d[cs.pick_row[j]] = cs.h_vals[(size_t)j];
+}
+
+// The validated queries of q in chunks of `chunk` >= 2 slots: statuses[b] and, where it is KNNCF_OK, the answers of query b's
+// rows.  (q.counts is null: fail() writes no per-query count; the rows' counts were zeroed by the caller.)
+QueryFailure run_bystander_chunks(knncf_handle* h, const QueryCall& q, int64_t chunk) {
+    h->prep.join_commit(h->stream);
+    load_host_ids(h);
+    KN_REQUIRE(h->tr.n + QUERY_MAX_RATINGS < ((int64_t)1 << 32), KNNCF_E_UNSUPPORTED, "query bystander: the newcomer's file rows pass 2^32");
+    const bool predict = q.mode == QB_BY_PREDICT;
+    ChunkState cs, one;  // one: pack_chunk's admission of a single query
+    ByChunkState bc;
+    cs.take = std::max(0, std::min(h->cfg.k, h->tr.U));
+    cs.qo.assign(1, 0); cs.ao.assign(1, 0);
+    auto flush = [&] {
+        answer_bystander_chunk(h, q, cs, bc);
+        cs.slot_query.clear(); cs.s_users.clear(); cs.s_items.clear(); cs.s_ratings.clear(); cs.s_self.clear();
+        cs.qo.assign(1, 0); cs.ao.assign(1, 0);
+        cs.C = 0;
+        bc.clear();
+    };
+    auto refuse = [&](int64_t b, int status, const char* why) {
+        fail(q, one, b, status, why);
+    };
+    std::vector<int32_t> dist, row_at;  // query b's distinct slot bystanders (dense) in order of appearance; per row its index or -1
+    std::vector<std::pair<int32_t, int32_t>> seen;
+    for (int64_t b = 0; b < q.B; ++b) {
+        const int64_t r0 = q.pred_offsets[b], r1 = q.pred_offsets[b + 1];
+        if (pack_chunk(h, q, one, b, b + 1) == 0) continue;
+        bool self_row = false, long_row = false;
+        dist.clear(); row_at.assign((size_t)(r1 - r0), -1); seen.clear();
+        for (int64_t r = r0; r < r1; ++r) {
+            if (q.others[r] == q.users[b]) { self_row = true; break; }
+            const int32_t dv = dense_user(h, q.others[r]);
+            if (dv < 0 || (predict && train_user_avg(h, dv) < 0.0)) continue;
+            if (train_row_length(h, dv) > QUERY_MAX_RATINGS) { long_row = true; break; }
+            seen.push_back({dv, (int32_t)(r - r0)});
+        }
+        if (self_row) { refuse(b, KNNCF_E_INVALID, "a row names the query's own user (ask knncf_query_predict)"); continue; }
+        if (long_row) { refuse(b, KNNCF_E_UNSUPPORTED, "a bystander with more than 65536 ratings"); continue; }
+        std::stable_sort(seen.begin(), seen.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
+        // distinct bystanders, numbered in order of first appearance
+        std::vector<std::pair<int32_t, int32_t>> firsts;  // (first row, dense user)
+        for (size_t x = 0; x < seen.size(); ++x)
+            if (x == 0 || seen[x].first != seen[x - 1].first) firsts.push_back({seen[x].second, seen[x].first});
+        std::sort(firsts.begin(), firsts.end());
+        for (const auto& f : firsts) dist.push_back(f.second);
+        // (seen is grouped by user: one search per distinct bystander)
+        for (size_t x = 0, d = 0; x < seen.size(); ++x) {
+            if (x == 0 || seen[x].first != seen[x - 1].first) d = (size_t)(std::find(dist.begin(), dist.end(), seen[x].first) - dist.begin());
+            row_at[(size_t)seen[x].second] = (int32_t)d;
+        }
+        const uint32_t qkey = int_trie_key(q.users[b]);
+        const int32_t at = (int32_t)(std::lower_bound(h->h_ukeys.begin(), h->h_ukeys.end(), qkey) - h->h_ukeys.begin());
+        size_t pos = 0;
+        do {
+            if (chunk - cs.C < (dist.empty() ? 1 : 2)) flush();
+            const int32_t own = cs.C;
+            cs.slot_query.push_back(b);
+            cs.s_users.push_back(q.users[b]);
+            cs.s_self.push_back(-1);
+            cs.s_items.insert(cs.s_items.end(), q.items + q.offsets[b], q.items + q.offsets[b + 1]);
+            cs.s_ratings.insert(cs.s_ratings.end(), q.ratings + q.offsets[b], q.ratings + q.offsets[b + 1]);
+            cs.ao.push_back((int64_t)cs.s_items.size());
+            cs.qo.push_back(cs.qo.back() + (q.offsets[b + 1] - q.offsets[b]));
+            bc.qslot.push_back(own); bc.qrank.push_back(at);
+            ++cs.C;
+            const size_t cnt = std::min<size_t>(dist.size() - pos, (size_t)(chunk - cs.C));
+            for (size_t d = pos; d < pos + cnt; ++d) {
+                cs.slot_query.push_back(b);
+                cs.s_users.push_back(h->h_uid[dist[d]]);
+                cs.s_self.push_back(dist[d]);
+                cs.ao.push_back(cs.ao.back());
+                cs.qo.push_back(cs.qo.back() + train_row_length(h, dist[d]));
+                bc.qslot.push_back(own); bc.qrank.push_back(at);
+                ++cs.C;
+            }
+            for (int64_t r = r0; r < r1; ++r) {
+                const int32_t d = row_at[(size_t)(r - r0)];
+                if (d < 0) { if (pos == 0) bc.rows.push_back({r, BY_NO_SLOT, own}); }
+                else if ((size_t)d >= pos && (size_t)d < pos + cnt) bc.rows.push_back({r, own + 1 + (int32_t)((size_t)d - pos), own});
+            }
+            pos += cnt;
+        } while (pos < dist.size());
+    }
+    flush();
+    if (one.first.query >= 0 && (cs.first.query < 0 || one.first.query < cs.first.query)) cs.first = one.first;
+    return cs.first;
+}
+
+// batch forms, and the single forms as a batch of one (single: the query's status is thrown as the call's)
+void do_bystander_batch(knncf_handle* h, QueryCall q, bool single) {
+    const char* what = single ? "query" : "query batch";
+    auto text = [&](const char* t) { return std::string(what) + ": " + t; };
+    require_fitted(h, false);
+    KN_REQUIRE(q.B >= 0, KNNCF_E_INVALID, text("n_queries < 0"));
+    KN_REQUIRE(q.mode != QB_BY_NEIGHBORS || q.width >= 0, KNNCF_E_INVALID, text("cap < 0"));
+    require_query_support(h, q.predictor, q.mode);
+    if (q.B == 0) return;
+    KN_REQUIRE(q.users && q.offsets && q.statuses, KNNCF_E_INVALID, text("null argument"));
+    require_offsets(q.offsets, q.B, "query batch: offsets[0] != 0", "query batch: offsets decrease");
+    KN_REQUIRE(q.offsets[q.B] < ((int64_t)1 << 31), KNNCF_E_INVALID, text("2^31 or more ratings in one call"));
+    KN_REQUIRE(q.offsets[q.B] == 0 || (q.items && q.ratings), KNNCF_E_INVALID, text("null ratings"));
+    require_offsets(q.pred_offsets, q.B, "query batch: row_offsets null or not starting at 0", "query batch: row_offsets decrease");
+    const int64_t rows = q.pred_offsets[q.B];
+    KN_REQUIRE(rows < ((int64_t)1 << 31), KNNCF_E_INVALID, text("2^31 or more rows in one call"));
+    if (q.mode == QB_BY_PREDICT) {
+        KN_REQUIRE(rows == 0 || (q.others && q.pred_items && q.out_d), KNNCF_E_INVALID, text("null row arguments"));
+    } else {
+        KN_REQUIRE(rows == 0 || (q.others && q.row_counts && (q.width == 0 || (q.out_i && q.out_d))), KNNCF_E_INVALID, text("null row arguments"));
+        std::fill(q.row_counts, q.row_counts + rows, 0);
+    }
+    const QueryFailure f = run_bystander_chunks(h, q, bystander_chunk(h, batch_budget(h)));
+    if (f.query < 0) return;
+    if (single) throw Error(q.statuses[0], std::string("query: ") + f.reason);
+    h->err = "query batch: query " + std::to_string(f.query) + ": " + f.reason;
+}
+
+int bystander_batch(knncf_handle* h, const QueryCall& q) { return guarded(h, [&] { do_bystander_batch(h, q, false); }); }
+int bystander_single(knncf_handle* h, QueryCall q, int64_t n_ratings, int64_t m) {
+    return guarded(h, [&] {
+        require_fitted(h, false);
+        KN_REQUIRE(n_ratings > 0 && q.items && q.ratings, KNNCF_E_INVALID, "query: null ratings or n_ratings <= 0");
+        KN_REQUIRE(m >= 0, KNNCF_E_INVALID, "query: m < 0");
+        const int64_t offsets[2] = {0, n_ratings}, row_offsets[2] = {0, m};
+        int32_t status = KNNCF_OK;
+        q.users = &q.user; q.B = 1; q.offsets = offsets; q.pred_offsets = row_offsets; q.statuses = &status;
+        do_bystander_batch(h, q, true);
+    });
+}
 
 // ---- checkpoint / resume of the neighbour table ------------------------------------------------------
 struct NbrFileHeader {
@@ -2671,6 +2906,37 @@ int knncf_revise_recommend_explain_batch(knncf_handle* h, int predictor, const i
                                                  .removed_items = removed_items, .statuses = statuses},
                                                  predictor, n, out_items, out_preds, counts,
                                                  {order, cap, raters, sims, devs, term_counts, sums, nullptr}));
+}
+
+// bystander queries: fitted users' answers once the fold-in query's user has joined (knncf.h "Bystander queries")
+int knncf_query_bystander_neighbors(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
+                                    const int32_t* others, int64_t m, int32_t cap, int32_t* ids, double* sims, int32_t* counts) {
+    return bystander_single(h, {.family = QF_FOLD_IN, .mode = QB_BY_NEIGHBORS, .predictor = KNNCF_PRED_KNN, .items = items, .ratings = ratings,
+                                .others = others, .row_counts = counts, .width = cap, .out_i = ids, .out_d = sims, .user = user},
+                            n_ratings, m);
+}
+
+int knncf_query_bystander_predict(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
+                                  int64_t n_ratings, const int32_t* others, const int32_t* pred_items, int64_t m, double* out) {
+    return bystander_single(h, {.family = QF_FOLD_IN, .mode = QB_BY_PREDICT, .predictor = predictor, .items = items, .ratings = ratings,
+                                .pred_items = pred_items, .others = others, .out_d = out, .user = user},
+                            n_ratings, m);
+}
+
+int knncf_query_bystander_neighbors_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                                          const double* ratings, int64_t n_queries, const int64_t* row_offsets, const int32_t* others,
+                                          int32_t cap, int32_t* ids, double* sims, int32_t* counts, int32_t* statuses) {
+    return bystander_batch(h, {.family = QF_FOLD_IN, .mode = QB_BY_NEIGHBORS, .predictor = KNNCF_PRED_KNN, .users = users, .B = n_queries,
+                               .offsets = offsets, .items = items, .ratings = ratings, .pred_offsets = row_offsets, .others = others,
+                               .row_counts = counts, .width = cap, .out_i = ids, .out_d = sims, .statuses = statuses});
+}
+
+int knncf_query_bystander_predict_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets,
+                                        const int32_t* items, const double* ratings, int64_t n_queries, const int64_t* row_offsets,
+                                        const int32_t* others, const int32_t* pred_items, double* out, int32_t* statuses) {
+    return bystander_batch(h, {.family = QF_FOLD_IN, .mode = QB_BY_PREDICT, .predictor = predictor, .users = users, .B = n_queries,
+                               .offsets = offsets, .items = items, .ratings = ratings, .pred_offsets = row_offsets,
+                               .pred_items = pred_items, .others = others, .out_d = out, .statuses = statuses});
 }
 
 int knncf_neighbors_save(knncf_handle* h, const char* path) {

@@ -1,0 +1,294 @@
+// bystander.hip — bystander queries: the neighbours and kNN predictions of a FITTED user v once a newcomer q has joined the
+// data, without a refit (DESIGN.md "Bystander queries"; knncf_query_bystander_*).
+//
+// The answers are those of the reference on aug = train ++ q's rows with fresh closures whose first evaluation is v's, so v
+// owns every pair.  A chunk of foldin.hip carries both kinds of slot: the newcomer's own (a fold-in slot: its prepared row is
+// what k_qb_prep makes) and one per bystander (an update slot with no additional row: v's train rows seeded on the device,
+// S(v, x) for every train user x in bs.sim, v's top list without v itself in bs.nbr_idx / bs.nbr_sim).  What q adds to a
+// bystander slot is computed here:
+//   k_by_pair      S(v, q) from the two prepared rows, folded in v's item-set order
+//   k_by_merge     (q, S(v, q)) into v's sorted list under (similarity descending, set order ascending); q is index U
+//   k_by_offsets / k_by_gather   k_qb_offsets / k_qb_gather in which index U reads q's prepared row; its file rows are
+//                  n_train + position, behind every train row: q's term is the last of an item's fold :520-524
+//   k_by_pick      k_qb_pick in which an item that only q rates has that one term
+// The sort of the gathered entries, k_q_fold and k_qb_pred of foldin.hip run between them unchanged.
+#include <math.h>
+
+#include <algorithm>
+
+#include "engine.h"
+#include "qb_helpers.h"
+#include "wave_helpers.h"
+
+namespace knncf {
+
+static constexpr int TPB = 256;
+
+// the order key of a similarity in a neighbour list, as k_fallback_keys of neighbours.hip makes it: ascending key <=> descending
+// similarity, -0.0 with +0.0
+__device__ __forceinline__ uint64_t by_sim_key(double s) {
+    if (s == 0.0) s = 0.0;
+    const uint64_t b = (uint64_t)__double_as_longlong(s);
+    return ~((b >> 63) ? ~b : (b | 0x8000000000000000ull));
+}
+
+// One wave per bystander slot b (qslot[b] != b): S(v, q), v = the slot's fitted user and q = the newcomer of slot qslot[b].
+// The wave walks q's known items in dense-item order 64 at a time (rank r of q's bitmap -> given position -> dense item),
+// probes v's bitmap and folds pre_v * pre_q left in that order = v's trie order (v with > 4 ratings).  A v of <= 4 ratings
+// iterates in its file order (Set1..Set4): the <= 4 products are kept by v's position and folded at the end, as k_query_sim
+// does for the query side.  Jaccard counts the matches: |I(v) & I(q)| / (|I(v)| + |I(q)| - |I(v) & I(q)|) :446-463, |I(q)| with
+// q's items unknown to train.
+// Bounds.  b < C.  q's distinct known items number rank[qs][W] (the bitmap's population), and k_qb_scatter wrote given_d /
+// pre_d of exactly those ranks; a given position is < the slot's rows, di of a known row is a dense item of [0, I).  A hit's
+// rank in v's bitmap is < v's rows.  (info[4 qs + 1] is NOT used: it counts a repeated item twice.)
+__global__ void __launch_bounds__(TPB) k_by_pair(int32_t C, int64_t W, bool jaccard, const int32_t* __restrict__ qslot,
+                                                 const int64_t* __restrict__ qo, const int32_t* __restrict__ di,
+                                                 const int32_t* __restrict__ given_d, const double* __restrict__ pre_d,
+                                                 const unsigned long long* __restrict__ bits, const int64_t* __restrict__ rank,
+                                                 double* __restrict__ pair) {
+    const int lane = threadIdx.x & 63;
+    const int32_t b = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
+    if (b >= C) return;
+    const int32_t qs = qslot[b];
+    if (qs == b) return;
+    const int64_t oq = qo[qs], ov = qo[b];
+    const int32_t nq = (int32_t)(qo[qs + 1] - oq), nv = (int32_t)(qo[b + 1] - ov);
+    const int32_t kq = (int32_t)rank[(int64_t)qs * (W + 1) + W];
+    const unsigned long long* vb = bits + (int64_t)b * W;
+    const int64_t* vr = rank + (int64_t)b * (W + 1);
+    const bool small = nv <= 4;
+    double s = 0.0, x0 = 0.0, x1 = 0.0, x2 = 0.0, x3 = 0.0;
+    uint32_t found = 0;
+    int64_t both = 0;
+    for (int32_t base = 0; base < kq; base += 64) {
+        const int32_t r = base + lane;
+        int32_t c = 0;
+        bool hit = false;
+        if (r < kq) {
+            c = di[oq + given_d[oq + r]];
+            hit = (vb[c >> 6] >> (c & 63)) & 1ull;
+        }
+        unsigned long long mask = __ballot(hit);
+        if (jaccard) {
+            both += __popcll(mask);
+            continue;
+        }
+        double prod = 0.0;
+        int32_t g = 0;
+        if (hit) {
+            const int32_t rv = bit_rank(vb, vr, c);
+            prod = pre_d[ov + rv] * pre_d[oq + r];
+            if (small) g = given_d[ov + rv];
+        }
+        while (mask) {
+            const int l = __ffsll((long long)mask) - 1;
+            const double xv = __shfl(prod, l);
+            if (small) {
+                const int gg = __shfl(g, l);
+                if (gg == 0) x0 = xv;
+                else if (gg == 1) x1 = xv;
+                else if (gg == 2) x2 = xv;
+                else x3 = xv;
+                found |= 1u << gg;
+            } else {
+                s = s + xv;
+            }
+            mask &= mask - 1ull;
+        }
+    }
+    if (jaccard) {
+        s = (double)both / (double)((int64_t)nv + (int64_t)nq - both);
+    } else if (small) {
+        if (found & 1u) s = s + x0;
+        if (found & 2u) s = s + x1;
+        if (found & 4u) s = s + x2;
+        if (found & 8u) s = s + x3;
+    }
+    if (lane == 0) pair[b] = s;
+}
+
+// One wave per bystander slot b: (q, pair[b]) enters the slot's sorted list of L = min(take, U - 1) train users (k_qb_write;
+// v itself is masked out).  (allUsers(aug) - v).toSeq is the train users in dense order with q in front of dense user
+// qrank[b], and the stable sortWith keeps that order among equal similarities: an entry goes before q when its key is smaller,
+// or equal with a dense index < qrank.  The list is sorted, so those entries are its first `pos`.  pos == take: q is not a
+// neighbour (in_list[b] = +0.0).  Otherwise the entries from pos move one cell up — the last one drops out when the list was
+// full (L == take), the list grows to L + 1 <= take when it was not (k >= U) — and q goes to cell pos as index U.
+// The move runs from the top in blocks of 64 cells: every lane's store takes the value its own load returned, so a block's
+// loads have all completed before its first store, and a block only writes cells that blocks above it have read already.
+// Bounds.  Cells [0, L) are read, cells [pos, min(L + 1, take)) of the slot's `take` cells are written.
+__global__ void __launch_bounds__(TPB) k_by_merge(int32_t C, int32_t take, int32_t U, const int32_t* __restrict__ qslot,
+                                                  const int32_t* __restrict__ qrank, const double* __restrict__ pair,
+                                                  int32_t* __restrict__ nbr_idx, double* __restrict__ nbr_sim,
+                                                  double* __restrict__ in_list) {
+    const int lane = threadIdx.x & 63;
+    const int32_t b = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
+    if (b >= C || qslot[b] == b) return;
+    const int32_t L = min(take, U - 1), at = qrank[b];
+    const double s = pair[b];
+    const uint64_t ks = by_sim_key(s);
+    int32_t* idx = nbr_idx + (int64_t)b * take;
+    double* sim = nbr_sim + (int64_t)b * take;
+    int32_t pos = 0;
+    for (int32_t base = 0; base < L; base += 64) {
+        const int32_t j = base + lane;
+        bool first = false;
+        if (j < L) {
+            const uint64_t kj = by_sim_key(sim[j]);
+            first = kj < ks || (kj == ks && idx[j] < at);
+        }
+        pos += __popcll(__ballot(first));
+    }
+    if (pos >= take) {
+        if (lane == 0) in_list[b] = 0.0;
+        return;
+    }
+    const int32_t last = min(L + 1, take) - 1;  // the top cell of the list afterwards
+    for (int32_t top = last; top > pos; top -= 64) {
+        const int32_t j = top - lane;
+        if (j > pos) {
+            const int32_t vi = idx[j - 1];
+            const double vs = sim[j - 1];
+            idx[j] = vi;
+            sim[j] = vs;
+        }
+    }
+    if (lane == 0) {
+        idx[pos] = U;
+        sim[pos] = s;
+        in_list[b] = s;
+    }
+}
+
+// k_qb_offsets for a chunk with bystander slots: off[b][0 .. take] and info[4 b + 2] of the slot's `take` neighbours, where
+// index U stands for the newcomer's distinct known items.  A newcomer's own slot, a slot whose status is set and a bystander
+// slot whose newcomer's status is set take no part in the prediction pass (0 entries).
+__global__ void __launch_bounds__(ONE_BLOCK) k_by_offsets(int32_t take, int32_t U, int64_t W, const int32_t* __restrict__ qslot,
+                                                          const int32_t* __restrict__ nbr, const int64_t* __restrict__ u_ptr,
+                                                          const int64_t* __restrict__ rank, int64_t* __restrict__ off,
+                                                          long long* __restrict__ info) {
+    const int32_t b = blockIdx.x, qs = qslot[b];
+    const int32_t* mine = nbr + (int64_t)b * take;
+    const int64_t live = (qs == b || info[4 * b] != 0 || info[4 * qs] != 0) ? 0 : take;
+    const int64_t kq = rank[(int64_t)qs * (W + 1) + W];
+    const int64_t total = block_exclusive_scan(
+        take,
+        [&](int64_t j) {
+            if (j >= live) return (int64_t)0;
+            const int32_t v = mine[j];
+            return v == U ? kq : u_ptr[v + 1] - u_ptr[v];
+        },
+        off + (int64_t)b * (take + 1));
+    if (threadIdx.x == 0) info[4 * b + 2] = total;
+}
+
+// k_qb_gather in which neighbour index U is the newcomer: entry r of its extent is its r-th known item in dense order, with
+// the deviation k_qb_scatter put there; the file row of its given position g is n_train + g (q's rows are the last of aug)
+__global__ void __launch_bounds__(TPB) k_by_gather(int32_t C, int32_t take, int32_t U, int32_t I, uint32_t n_train,
+                                                   const int32_t* __restrict__ qslot, const int64_t* __restrict__ qo,
+                                                   const int32_t* __restrict__ di, const int32_t* __restrict__ given_d,
+                                                   const double* __restrict__ dev_d, const int32_t* __restrict__ nbr,
+                                                   const double* __restrict__ nsim, const int64_t* __restrict__ off,
+                                                   const int64_t* __restrict__ ebase, const int64_t* __restrict__ u_ptr,
+                                                   const int32_t* __restrict__ s_col, const uint32_t* __restrict__ s_t,
+                                                   const double* __restrict__ s_dev, uint64_t* __restrict__ key,
+                                                   uint32_t* __restrict__ val, double* __restrict__ edev, double* __restrict__ esim) {
+    const int64_t g = (int64_t)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
+    if (g >= (int64_t)C * take) return;
+    const int32_t sb = (int32_t)(g / take), j = (int32_t)(g - (int64_t)sb * take);
+    const int64_t lo = off[(int64_t)sb * (take + 1) + j], hi = off[(int64_t)sb * (take + 1) + j + 1];
+    if (hi == lo) return;  // (a slot that takes no part, or a neighbour without ratings)
+    const int32_t v = nbr[g];
+    const int64_t o = ebase[sb] + lo;
+    const double sj = nsim[g];
+    if (v == U) {
+        const int64_t oq = qo[qslot[sb]];
+        for (int64_t r = threadIdx.x & 63; r < hi - lo; r += 64) {
+            const int32_t gv = given_d[oq + r];
+            const int64_t x = o + r;
+            key[x] = ((uint64_t)((uint32_t)sb * (uint32_t)I + (uint32_t)di[oq + gv]) << 32) | (uint64_t)(n_train + (uint32_t)gv);
+            val[x] = (uint32_t)x;
+            edev[x] = dev_d[oq + r];
+            esim[x] = sj;
+        }
+        return;
+    }
+    const int64_t b = u_ptr[v], e = u_ptr[v + 1];
+    for (int64_t p = b + (threadIdx.x & 63); p < e; p += 64) {
+        const int64_t x = o + (p - b);
+        key[x] = ((uint64_t)((uint32_t)sb * (uint32_t)I + (uint32_t)s_col[p]) << 32) | (uint64_t)s_t[p];
+        val[x] = (uint32_t)x;
+        edev[x] = s_dev[p];
+        esim[x] = sj;
+    }
+}
+
+// requested raw items with their (bystander) slot: the dense item's prediction of k_qb_pred.  An item unknown to train has at
+// most one rater in aug, the newcomer: its term dev_q(i) * S(v, q) when q is in v's list (in_list = S, else +0.0) is the whole
+// fold :520-524, and without a non-zero S the answer is v's mean exactly (den = 0), as for an item unknown to aug
+__global__ void k_by_pick(int64_t m, const int32_t* __restrict__ items, const int32_t* __restrict__ slot,
+                          const int32_t* __restrict__ i_table, int32_t i_cells, const uint32_t* __restrict__ ikeys, int32_t I,
+                          const int32_t* __restrict__ qslot, const int64_t* __restrict__ qo, const int32_t* __restrict__ q_items,
+                          const double* __restrict__ q_dev, const double* __restrict__ in_list, const double* __restrict__ pred,
+                          const double* __restrict__ scal, double* __restrict__ out) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const int32_t it = items[j], b = slot[j];
+    int32_t c;
+    if (i_cells > 0) c = (it >= 0 && it < i_cells) ? i_table[it] : -1;
+    else c = dense_lookup(ikeys, I, it);
+    if (c >= 0) {
+        out[j] = pred[(int64_t)b * I + c];
+        return;
+    }
+    const double avg = scal[2 * b], s = in_list[b];
+    double a = 0.0, d = 0.0;
+    const int32_t qs = qslot[b];
+    for (int64_t x = qo[qs]; x < qo[qs + 1]; ++x) {
+        if (q_items[x] == it) {
+            a = a + q_dev[x] * s;
+            d = d + fabs(s);
+            break;
+        }
+    }
+    const double w = d > 0 ? a / d : 0.0;
+    out[j] = avg + w * scale_fn(avg + w, avg);
+}
+
+static int32_t table_cells(const Train& tr) { return (tr.u_table_n > 0 && tr.i_table_n > 0) ? tr.i_table_n : 0; }
+
+void bystander_upload(QueryBatchScratch& bs, int32_t C, const ByChunk& by, hipStream_t st) {
+    bs.by_qslot.ensure(C); bs.by_qrank.ensure(C); bs.by_pair.ensure(C); bs.by_in.ensure(C);
+    KN_HIP(hipMemcpyAsync(bs.by_qslot.p, by.h_qslot, (size_t)C * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    KN_HIP(hipMemcpyAsync(bs.by_qrank.p, by.h_qrank, (size_t)C * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    KN_HIP(hipMemsetAsync(bs.by_pair.p, 0, (size_t)C * sizeof(double), st));
+    KN_HIP(hipMemsetAsync(bs.by_in.p, 0, (size_t)C * sizeof(double), st));
+}
+
+void bystander_merge(const Train& tr, QueryBatchScratch& bs, int32_t C, int32_t take, hipStream_t st) {
+    const int64_t W = ceil_div(tr.I, 64);
+    const unsigned grid = (unsigned)ceil_div(C, TPB / 64);
+    k_by_pair<<<grid, TPB, 0, st>>>(C, W, tr.jaccard, bs.by_qslot.p, bs.qo.p, bs.di.p, bs.given_d.p, bs.pre_d.p,
+                                    (const unsigned long long*)bs.bits.p, bs.rank.p, bs.by_pair.p);
+    if (take > 0)
+        k_by_merge<<<grid, TPB, 0, st>>>(C, take, tr.U, bs.by_qslot.p, bs.by_qrank.p, bs.by_pair.p, bs.nbr_idx.p, bs.nbr_sim.p,
+                                         bs.by_in.p);
+    k_by_offsets<<<C, ONE_BLOCK, 0, st>>>(take, tr.U, W, bs.by_qslot.p, bs.nbr_idx.p, tr.u_ptr.p, bs.rank.p, bs.off.p,
+                                          (long long*)bs.info.p);
+    KN_HIP(hipGetLastError());
+}
+
+void bystander_gather(const Train& tr, QueryBatchScratch& bs, int32_t C, int32_t take, hipStream_t st) {
+    k_by_gather<<<(unsigned)ceil_div((int64_t)C * take, TPB / 64), TPB, 0, st>>>(
+        C, take, tr.U, tr.I, (uint32_t)tr.n, bs.by_qslot.p, bs.qo.p, bs.di.p, bs.given_d.p, bs.dev_d.p, bs.nbr_idx.p, bs.nbr_sim.p,
+        bs.off.p, bs.ebase.p, tr.u_ptr.p, tr.s_col.p, tr.s_t.p, tr.s_dev.p, bs.e_k64_a.p, bs.e_v32_a.p, bs.e_dev.p, bs.e_sim.p);
+}
+
+void bystander_pick(const Train& tr, QueryBatchScratch& bs, const int32_t* d_items, const int32_t* d_slot, int64_t m, double* d_out,
+                    hipStream_t st) {
+    k_by_pick<<<(unsigned)ceil_div(m, TPB), TPB, 0, st>>>(m, d_items, d_slot, tr.i_table.p, table_cells(tr), tr.ikeys.p, tr.I,
+                                                          bs.by_qslot.p, bs.qo.p, bs.items.p, bs.dev.p, bs.by_in.p, bs.pred.p,
+                                                          bs.scal.p, d_out);
+    KN_HIP(hipGetLastError());
+}
+
+}  // namespace knncf

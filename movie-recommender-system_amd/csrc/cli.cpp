@@ -220,7 +220,7 @@ double timed_ms(const std::function<void()>& f) {
 struct Args {
     std::string cmd, train, test, separator = "\t", json, master, data, personal;
     int num_measurements = 0, k = 300, device = 0;
-    bool any_size = false;
+    bool any_size = false, no_refit = false;
 };
 
 Json meta(const Args& a, bool with_master) {
@@ -366,19 +366,34 @@ bool load_personal(const std::string& path, Ratings* out, std::vector<std::pair<
 
 Json run_recommend(const Args& a, const Ratings& data, const Ratings& personal,
                    const std::vector<std::pair<int32_t, std::string>>& names) {  // recommend/Recommender.scala:68-89
-    Ratings aug = data;  // data.union(personal): file order, personal rows last
-    aug.users.insert(aug.users.end(), personal.users.begin(), personal.users.end());
-    aug.items.insert(aug.items.end(), personal.items.begin(), personal.items.end());
-    aug.ratings.insert(aug.ratings.end(), personal.ratings.begin(), personal.ratings.end());
     Engine e(a.device, 300, KNNCF_SIM_COSINE);
-    e.fit(aug);
     Json out = Json::Obj();
     out.set("Meta", Json::Obj().set("data", Json::Str(a.data)).set("personal", Json::Str(a.personal)));
-    out.set("R.1", Json::Obj().set("PredUser1Item1", Json::Num(e.predict(KNNCF_PRED_KNN, 1, 1))));
-    check(e.h, knncf_reset_neighbors(e.h), "reset");  // R.2 builds fresh closures (:85-88)
     int32_t ids[3], cnt = 0;
     double preds[3];
-    check(e.h, knncf_recommend(e.h, KNNCF_PRED_KNN, 944, 3, ids, preds, &cnt), "recommend");
+    if (a.no_refit) {
+        // the fit holds --data alone; user 944 joins as a fold-in query: R.1 is the bystander (1, 1) of that query, R.2 the
+        // query's own top 3.  Both are answered on fresh closures over data.union(personal), as the refitting path answers them.
+        for (const int32_t u : data.users)
+            if (u == 944) throw Fail{"recommend --no-refit: user 944 occurs in --data (run without --no-refit)"};
+        e.fit(data);
+        const int32_t other = 1, item = 1;
+        double r1 = 0.0;
+        check(e.h, knncf_query_bystander_predict(e.h, KNNCF_PRED_KNN, 944, personal.items.data(), personal.ratings.data(), personal.size(),
+                                                 &other, &item, 1, &r1), "bystander predict");
+        out.set("R.1", Json::Obj().set("PredUser1Item1", Json::Num(r1)));
+        check(e.h, knncf_query_recommend(e.h, KNNCF_PRED_KNN, 944, personal.items.data(), personal.ratings.data(), personal.size(), 3, ids,
+                                         preds, &cnt), "query recommend");
+    } else {
+        Ratings aug = data;  // data.union(personal): file order, personal rows last
+        aug.users.insert(aug.users.end(), personal.users.begin(), personal.users.end());
+        aug.items.insert(aug.items.end(), personal.items.begin(), personal.items.end());
+        aug.ratings.insert(aug.ratings.end(), personal.ratings.begin(), personal.ratings.end());
+        e.fit(aug);
+        out.set("R.1", Json::Obj().set("PredUser1Item1", Json::Num(e.predict(KNNCF_PRED_KNN, 1, 1))));
+        check(e.h, knncf_reset_neighbors(e.h), "reset");  // R.2 builds fresh closures (:85-88)
+        check(e.h, knncf_recommend(e.h, KNNCF_PRED_KNN, 944, 3, ids, preds, &cnt), "recommend");
+    }
     Json r2 = Json::Arr();
     for (int32_t j = 0; j < cnt; ++j) {
         std::string name;
@@ -397,7 +412,8 @@ int usage() {
             "usage: knncf {baseline|personalized|knn|distributed-baseline|load-check} --train FILE --test FILE\n"
             "             [--separator SEP] [--num_measurements N] [--json FILE] [--master M] [--k K] [--device D]\n"
             "             [--cache-dir DIR]   (binary cache of the parsed files, read back while they are unchanged)\n"
-            "       knncf recommend --data FILE --personal FILE [--separator SEP] [--json FILE] [--any-size]\n");
+            "       knncf recommend --data FILE --personal FILE [--separator SEP] [--json FILE] [--any-size]\n"
+            "             [--no-refit]   (fit --data alone and answer for user 944 as a fold-in query)\n");
     return 2;
 }
 
@@ -424,6 +440,7 @@ int main(int argc, char** argv) {
         else if (k == "--data") a.data = need("--data");
         else if (k == "--personal") a.personal = need("--personal");
         else if (k == "--any-size") a.any_size = true;
+        else if (k == "--no-refit") a.no_refit = true;
         else if (k == "--cache-dir") g_cache_dir = need("--cache-dir");
         else { fprintf(stderr, "[knncf] unknown option %s\n", k.c_str()); return usage(); }
     }

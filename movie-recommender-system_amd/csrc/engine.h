@@ -81,6 +81,7 @@ struct Train {
     DArr<int32_t> pop_item;  // [I] dense items by descending number of raters
     std::vector<int64_t> pop_count;  // host: rater counts in that order
     double global_avg = 0.0;
+    double total = 0.0;  // the left fold of the ratings in file order that global_avg divides (average :18): bystander queries continue it
     int32_t own_lo = 0, own_hi = 0;  // owned dense users [lo, hi)
     int64_t own_p0 = 0, own_p1 = 0;  // their positions in the canonical order (everything when not sharded)
     // the handle's similarity is jaccardCoefficient :440-464: the similarity stage then counts common items — 0/1 operand
@@ -386,6 +387,17 @@ struct QueryBatchScratch {
     DArr<int32_t> pick_items, pick_slot, out_items;
     DArr<double> pick_out, out_preds;
     DArr<int64_t> reco_rb;             // [C + 1] first explain row of each slot (foldin_batch_reco_rows)
+    // bystander queries (bystander.hip): [C] the newcomer's slot of each slot (its own index for a newcomer's slot), the
+    // newcomer's place in set order, S(v, q), and S(v, q) again where q entered v's list (else +0.0)
+    DArr<int32_t> by_qslot, by_qrank;
+    DArr<double> by_pair, by_in;
+};
+// A chunk of bystander queries (DESIGN.md "Bystander queries"): slot b is either a newcomer's own fold-in slot (h_qslot[b] == b,
+// h_self[b] == -1) or a bystander's — a fitted user with no additional row (h_self[b] >= 0) whose newcomer is slot h_qslot[b] of
+// the same chunk.  h_qrank[b] = the number of train users in front of slot b's newcomer in set order.
+struct ByChunk {
+    const int32_t* h_qslot;
+    const int32_t* h_qrank;
 };
 // prep + similarities + top-k (bs.nbr_idx / nbr_sim [C][min(k, U)]) of C >= 1 non-empty queries; h_info[4 b ..] = status
 // bits, known items, neighbour ratings (0 for a slot whose status is set) of slot b.  Synchronises the stream once.
@@ -400,12 +412,16 @@ struct QueryBatchScratch {
 void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, const int32_t* h_users,
                             const int64_t* h_qo, const int32_t* h_items, const double* h_ratings, const int32_t* h_self,
                             const int64_t* h_ao, int32_t k, long long* h_info, hipStream_t st, const int64_t* h_ro = nullptr,
-                            const int32_t* h_removed = nullptr, bool topk = true);
+                            const int32_t* h_removed = nullptr, bool topk = true, const ByChunk* by = nullptr);
 // (topk = false, the Personalized mode: stops after the similarities — no keys, no sorts, bs.nbr_idx / nbr_sim / off are not
 // written and the neighbour ratings of h_info are 0)
+// (by != nullptr, an update chunk with topk: after the top lists every bystander slot's list takes its newcomer in — index U,
+// min(k, U) entries — and the neighbour ratings of h_info count the newcomer's known items; a newcomer's own slot and the
+// bystander slots of a newcomer whose status is set have 0)
 // bs.pred / bs.rated [C][I]; h_ebase[C + 1] = exclusive prefix of the slots' neighbour ratings
 void foldin_batch_predictions(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, int32_t take,
-                              const int64_t* h_ebase, hipStream_t st);
+                              const int64_t* h_ebase, hipStream_t st, bool bystander = false);
+// (bystander: the chunk went through foldin_batch_neighbors with a ByChunk; neighbour index U gathers the newcomer's row)
 void foldin_batch_pick(const Train& tr, QueryBatchScratch& bs, const int32_t* d_items, const int32_t* d_slot, int64_t m,
                        double* d_out, hipStream_t st);
 // KNNCF_PRED_PERSONALIZED instead of foldin_batch_predictions, after foldin_batch_neighbors(topk = false) on the chunk of n rows
@@ -439,6 +455,18 @@ void foldin_batch_recommend(const Train& tr, QueryBatchScratch& bs, SortWorkspac
 // prefix of the slots' counts, 0 for a refused slot; every count <= what foldin_batch_recommend wrote for the slot).  One
 // upload and one launch, no round trip; nothing with h_rb[C] == 0.
 void foldin_batch_reco_rows(QueryBatchScratch& bs, int32_t C, int32_t n, const int64_t* h_rb, const int32_t* d_items, hipStream_t st);
+
+// ---- bystander.hip: what a newcomer adds to the slots of fitted users (knncf_query_bystander_*; DESIGN.md "Bystander queries")
+// the chunk's slot map, before any kernel of the chunk
+void bystander_upload(QueryBatchScratch& bs, int32_t C, const ByChunk& by, hipStream_t st);
+// after k_qb_write: S(v, q) per bystander slot, q into v's list, then bs.off and the neighbour ratings of bs.info (instead of
+// k_qb_offsets)
+void bystander_merge(const Train& tr, QueryBatchScratch& bs, int32_t C, int32_t take, hipStream_t st);
+// k_qb_gather's launch for such a chunk
+void bystander_gather(const Train& tr, QueryBatchScratch& bs, int32_t C, int32_t take, hipStream_t st);
+// foldin_batch_pick for rows of bystander slots: an item that only the newcomer rates has its one term
+void bystander_pick(const Train& tr, QueryBatchScratch& bs, const int32_t* d_items, const int32_t* d_slot, int64_t m, double* d_out,
+                    hipStream_t st);
 
 // ---- reco_batch.hip: recommendations :651-674 for users of the fit (knncf_recommend, knncf_recommend_batch; DESIGN.md "Batched
 // recommendations") ----

@@ -41,6 +41,7 @@
 #include <algorithm>
 
 #include "explain_select.h"
+#include "qb_helpers.h"
 
 namespace knncf {
 
@@ -48,7 +49,6 @@ namespace knncf {
 void launch_fallback_keys(int32_t U, const double* d_exact, uint64_t* d_keys, uint32_t* d_vals, hipStream_t st);
 
 static constexpr int TPB = 256;
-static constexpr int ONE_BLOCK = 1024;
 // query bitmap + rank prefixes held in LDS by k_query_sim up to this many words (16 B each: 64 KB = 262 144 items);
 // beyond that the waves probe them in global memory (L2-resident)
 static constexpr int64_t SIM_LDS_WORDS = 4096;
@@ -56,38 +56,6 @@ static constexpr int64_t SIM_LDS_WORDS = 4096;
 static constexpr uint32_t ST_NEG_MEAN = QUERY_ST_NEG_MEAN;
 // revise queries: a removed item that is no train item of the user / that is listed twice
 static constexpr uint32_t ST_RM_UNRATED = QUERY_ST_RM_UNRATED, ST_RM_TWICE = QUERY_ST_RM_TWICE;
-
-// one workgroup: exclusive prefix of cnt(i) over i < m (cnt = popcount of a bitmap word, or a neighbour's row length);
-// out[m] = the total, which every thread returns
-template <class F>
-__device__ int64_t block_exclusive_scan(int64_t m, F cnt, int64_t* __restrict__ out) {
-    __shared__ int64_t part[ONE_BLOCK];
-    const int t = threadIdx.x;
-    const int64_t per = (m + ONE_BLOCK - 1) / ONE_BLOCK;
-    const int64_t lo = std::min<int64_t>(m, t * per), hi = std::min<int64_t>(m, lo + per);
-    int64_t c = 0;
-    for (int64_t i = lo; i < hi; ++i) c += cnt(i);
-    part[t] = c;
-    __syncthreads();
-    for (int off = 1; off < ONE_BLOCK; off <<= 1) {
-        const int64_t add = t >= off ? part[t - off] : 0;
-        __syncthreads();
-        part[t] += add;
-        __syncthreads();
-    }
-    int64_t run = part[t] - c;
-    for (int64_t i = lo; i < hi; ++i) {
-        out[i] = run;
-        run += cnt(i);
-    }
-    if (t == ONE_BLOCK - 1) out[m] = part[t];
-    return part[ONE_BLOCK - 1];
-}
-
-__device__ __forceinline__ int32_t bit_rank(const unsigned long long* bits, const int64_t* rank, int32_t c) {
-    const unsigned long long below = bits[c >> 6] & ((1ull << (c & 63)) - 1ull);
-    return (int32_t)rank[c >> 6] + __popcll(below);
-}
 
 // exact similarity of q (first argument, fresh closure: it owns every pair) against every train user, one wave per
 // user: the wave reads the user's row 64 entries at a time (coalesced), probes the query bitmap, and folds the products of
@@ -193,23 +161,8 @@ static PerDeviceState g_sim_lds;
 
 static int32_t table_cells(const Train& tr) { return (tr.u_table_n > 0 && tr.i_table_n > 0) ? tr.i_table_n : 0; }
 
-// slot of chunk row j: the last b with qo[b] <= j
-__device__ __forceinline__ int32_t qb_slot(const int64_t* __restrict__ qo, int32_t C, int64_t j) {
-    int32_t lo = 0, hi = C - 1;
-    while (lo < hi) {
-        const int32_t mid = (lo + hi + 1) >> 1;
-        if (qo[mid] <= j) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
 // ---- update queries (knncf_update_*): the query user may be in the fit.  self[b] = its dense index, -1 when it is not.
-// neighbours a slot returns: (allUsers - u) :608 has U - 1 users for a user of the fit.  self == nullptr: fold-in queries.
-__device__ __forceinline__ int32_t qb_take(const int32_t* __restrict__ self, int32_t b, int32_t take, int32_t U) {
-    return (self && self[b] >= 0) ? min(take, U - 1) : take;
-}
-
+// (qb_take of qb_helpers.h: the neighbours a slot returns.)
 // Chunk row j of slot b is row r = j - qo[b] of the slot: r < (train row length of self[b]) is the user's train entry at
 // position u_ptr[self] + r, the others are the additional rows in their given order.  The key orders a slot's rows as aug
 // holds them: train rows by file row (s_t), then the additional ones.
@@ -878,7 +831,7 @@ static const uint32_t* qb_segmented_sort(QueryBatchScratch& bs, SortWorkspace& w
 void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, const int32_t* h_users,
                             const int64_t* h_qo, const int32_t* h_items, const double* h_ratings, const int32_t* h_self,
                             const int64_t* h_ao, int32_t k, long long* h_info, hipStream_t st, const int64_t* h_ro,
-                            const int32_t* h_removed, bool topk) {
+                            const int32_t* h_removed, bool topk, const ByChunk* by) {
     const int32_t U = tr.U, I = tr.I;
     const int64_t W = ceil_div(I, 64), n = h_qo[C];
     const int64_t cells = (int64_t)C * std::max(U, I);
@@ -903,6 +856,7 @@ void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspac
     KN_HIP(hipMemcpyAsync(bs.qo.p, h_qo, ((size_t)C + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
     // (the status words are cleared before the seeding: k_qb_mark sets bits in them)
     KN_HIP(hipMemsetAsync(bs.info.p, 0, (size_t)4 * C * sizeof(int64_t), st));
+    if (by) bystander_upload(bs, C, *by, st);
     long long* info = (long long*)bs.info.p;
     const int32_t* self = nullptr;
     if (!h_self) {
@@ -997,7 +951,8 @@ void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspac
             k_qb_write<<<(unsigned)ceil_div((int64_t)C * take, TPB), TPB, 0, st>>>(C, take, U, self, order, bs.sim.p, bs.nbr_idx.p,
                                                                                    bs.nbr_sim.p);
         }
-        k_qb_offsets<<<C, ONE_BLOCK, 0, st>>>(take, U, self, bs.nbr_idx.p, tr.u_ptr.p, bs.off.p, info);
+        if (by) bystander_merge(tr, bs, C, take, st);
+        else k_qb_offsets<<<C, ONE_BLOCK, 0, st>>>(take, U, self, bs.nbr_idx.p, tr.u_ptr.p, bs.off.p, info);
         KN_HIP(hipGetLastError());
     }
     // the chunk's one round trip: statuses, known items and the sizes of the prediction pass
@@ -1006,7 +961,7 @@ void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspac
 }
 
 void foldin_batch_predictions(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, int32_t take,
-                              const int64_t* h_ebase, hipStream_t st) {
+                              const int64_t* h_ebase, hipStream_t st, bool bystander) {
     const int32_t I = tr.I;
     const int64_t W = ceil_div(I, 64), E = h_ebase[C], cells = (int64_t)C * I;
     bs.num.ensure(cells); bs.den.ensure(cells); bs.pred.ensure(cells); bs.rated.ensure(cells);
@@ -1018,7 +973,8 @@ void foldin_batch_predictions(const Train& tr, QueryBatchScratch& bs, SortWorksp
         bs.e_k64_a.ensure(E); bs.e_k64_b.ensure(E); bs.e_v32_a.ensure(E); bs.e_v32_b.ensure(E);
         bs.e_dev.ensure(E); bs.e_sim.ensure(E);
         KN_HIP(hipMemcpyAsync(bs.ebase.p, h_ebase, ((size_t)C + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        k_qb_gather<<<(unsigned)ceil_div((int64_t)C * take, TPB / 64), TPB, 0, st>>>(
+        if (bystander) bystander_gather(tr, bs, C, take, st);
+        else k_qb_gather<<<(unsigned)ceil_div((int64_t)C * take, TPB / 64), TPB, 0, st>>>(
             C, take, I, bs.nbr_idx.p, bs.nbr_sim.p, bs.off.p, bs.ebase.p, tr.u_ptr.p, tr.s_col.p, tr.s_t.p, tr.s_dev.p, bs.e_k64_a.p,
             bs.e_v32_a.p, bs.e_dev.p, bs.e_sim.p);
         sort_pairs_u64_u32(ws, bs.e_k64_a.p, bs.e_k64_b.p, bs.e_v32_a.p, bs.e_v32_b.p, (size_t)E, 32 + bits_for((uint64_t)cells), st);

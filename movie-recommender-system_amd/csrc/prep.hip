@@ -958,6 +958,7 @@ void prep_fit(Train& tr, PrepScratch& sc, int32_t shard_rank, int32_t shard_coun
     double total = 0.0;
     KN_HIP(hipMemcpyAsync(&total, sc.dsum.p, sizeof(double), hipMemcpyDeviceToHost, st));
     KN_HIP(hipStreamSynchronize(st));
+    tr.total = total;
     tr.global_avg = total / (double)n;
 
     tr.user_avg.alloc(U); tr.user_norm.alloc(U);

@@ -132,6 +132,8 @@ EXPORTS = [
     "knncf_query_explain_personalized_batch", "knncf_update_explain_personalized_batch", "knncf_revise_explain_personalized_batch",
     "knncf_query_recommend_explain", "knncf_update_recommend_explain", "knncf_revise_recommend_explain",
     "knncf_query_recommend_explain_batch", "knncf_update_recommend_explain_batch", "knncf_revise_recommend_explain_batch",
+    "knncf_query_bystander_neighbors", "knncf_query_bystander_predict",
+    "knncf_query_bystander_neighbors_batch", "knncf_query_bystander_predict_batch",
     "knncf_predict_batch",
     "knncf_predict_batch_device", "knncf_mae", "knncf_mae_device", "knncf_mae_sweep", "knncf_mae_sweep_device", "knncf_shard_view_get",
     "knncf_shard_commit", "knncf_get_timings", "knncf_reset_timings", "knncf_reset_neighbors",
@@ -242,6 +244,14 @@ def load_library():
                                            + terms[2:-1])
         f("recommend_explain_batch").argtypes = (f("recommend_batch").argtypes[:-4] + [C.c_int32, C.c_int32]
                                                  + f("recommend_batch").argtypes[-4:-1] + terms[2:-1] + [_i32p])
+    # bystander queries: the fold-in query, then its rows (a fitted user each; the predict forms: with an item)
+    L.knncf_query_bystander_neighbors.argtypes = [C.c_void_p, C.c_int32, _i32p, _f64p, C.c_int64, _i32p, C.c_int64, C.c_int32, _i32p,
+                                                  _f64p, _i32p]
+    L.knncf_query_bystander_predict.argtypes = [C.c_void_p, C.c_int, C.c_int32, _i32p, _f64p, C.c_int64, _i32p, _i32p, C.c_int64, _f64p]
+    L.knncf_query_bystander_neighbors_batch.argtypes = [C.c_void_p, _i32p, _i64p, _i32p, _f64p, C.c_int64, _i64p, _i32p, C.c_int32,
+                                                        _i32p, _f64p, _i32p, _i32p]
+    L.knncf_query_bystander_predict_batch.argtypes = [C.c_void_p, C.c_int, _i32p, _i64p, _i32p, _f64p, C.c_int64, _i64p, _i32p, _i32p,
+                                                      _f64p, _i32p]
     # revise queries: the update argument lists with the removals in front of the additional rows
     for name, at, single in (("neighbors", 2, True), ("predict", 3, True), ("recommend", 3, True), ("explain", 3, True),
                              ("explain_personalized", 2, True), ("neighbors_batch", 2, False), ("predict_batch", 3, False),
@@ -1109,6 +1119,115 @@ class Engine:
     def set_k(self, k):
         self._check(self._lib.knncf_set_k(self._h, k))
         self.k = k
+
+
+class BystanderQueries:
+    """Bystander queries (knncf_query_bystander_*) on a fitted Engine: a FITTED user's kNN answers once the user of a fold-in query
+    has joined the data, without a refit.  A query is (user, items, ratings) as Engine.neighbors_for takes it; a row names the
+    fitted user (`others`), the predict forms an item beside it (`pred_items`).  Read-only on the engine's handle: the
+    neighbour lists and their build history stay as they were.
+
+        by = BystanderQueries(engine)
+        by.predict_for(944, items, ratings, [1], [1])"""
+
+    def __init__(self, engine):
+        self._e = engine
+
+    @staticmethod
+    def _row_ids(a, what):
+        """validated 32-bit ids of the rows of a bystander query: ValueError before any C call"""
+        x = np.asarray(a)
+        if x.ndim != 1:
+            raise ValueError(f"{what} must be 1-D")
+        if len(x) == 0:
+            return np.empty(0, dtype=np.int32)
+        if x.dtype.kind not in "iu" or x.min() < -2**31 or x.max() >= 2**31:
+            raise ValueError(f"{what} must be 32-bit integer ids")
+        return _i32(x)
+
+    @staticmethod
+    def _row_cap(cap, k):
+        if cap is None:
+            cap = max(1, k)
+        if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or cap < 0 or cap >= 2**31:
+            raise ValueError("cap must be a non-negative integer")
+        return int(cap)
+
+    def _rows(self, B, others, pred_items):
+        """the rows of a batched bystander call: (row_offsets, others, pred_items or None), one sequence per query"""
+        oth = [self._row_ids(x, "others") for x in others]
+        if len(oth) != B:
+            raise ValueError("one others sequence per query")
+        roff = np.zeros(B + 1, dtype=np.int64)
+        roff[1:] = np.cumsum([len(x) for x in oth])
+        if roff[-1] >= 2**31:
+            raise ValueError("fewer than 2^31 rows per call")
+        cat = lambda parts: np.ascontiguousarray(np.concatenate(parts) if parts else np.empty(0), dtype=np.int32)
+        if pred_items is None:
+            return roff, cat(oth), None
+        pis = [self._row_ids(x, "pred_items") for x in pred_items]
+        if len(pis) != B:
+            raise ValueError("one pred_items sequence per query")
+        if any(len(a) != len(b) for a, b in zip(oth, pis)):
+            raise ValueError("others and pred_items must be of the same length")
+        return roff, cat(oth), cat(pis)
+
+    def neighbors_for(self, user, items, ratings, others, cap=None):
+        """getNeighbors(train ++ user's ratings, k, sim)(v) for every v of `others`, fitted users (or unknown ids) other than the
+        newcomer `user`: [(ids, sims)] per row; the newcomer's own id where it is a neighbour"""
+        q, it, rt = self._e._query_rows(user, items, ratings)
+        oth = self._row_ids(others, "others")
+        cap, m = self._row_cap(cap, self._e.k), len(oth)
+        ids = np.empty((m, cap), dtype=np.int32)
+        sims = np.empty((m, cap), dtype=np.float64)
+        counts = np.zeros(m, dtype=np.int32)
+        p = self._e._ptr
+        self._e._check(self._e._lib.knncf_query_bystander_neighbors(self._e._h, q, p(it, _i32p), p(rt, _f64p), len(it), p(oth, _i32p), m, cap,
+                                                              p(ids.reshape(-1), _i32p), p(sims.reshape(-1), _f64p), p(counts, _i32p)))
+        return [(ids[r, :min(counts[r], cap)].copy(), sims[r, :min(counts[r], cap)].copy()) for r in range(m)]
+
+    def predict_for(self, user, items, ratings, others, pred_items):
+        """kNN predictions of (others[r], pred_items[r]) on train ++ user's ratings: a float64 array, one cell per row"""
+        q, it, rt = self._e._query_rows(user, items, ratings)
+        oth, pi = self._row_ids(others, "others"), self._row_ids(pred_items, "pred_items")
+        if len(oth) != len(pi):
+            raise ValueError("others and pred_items must be of the same length")
+        out = np.full(len(oth), np.nan, dtype=np.float64)
+        p = self._e._ptr
+        self._e._check(self._e._lib.knncf_query_bystander_predict(self._e._h, PRED_KNN, q, p(it, _i32p), p(rt, _f64p), len(it), p(oth, _i32p),
+                                                            p(pi, _i32p), len(oth), p(out, _f64p)))
+        return out
+
+    def neighbors_for_batch(self, queries, others, cap=None):
+        """neighbors_for of every (user, items, ratings) of `queries` with others[b] its rows:
+        ([[(ids, sims)] per row] per query, statuses int32 [B]).  A failed query's rows have empty arrays."""
+        qargs, keep = self._e._batch_args("query", queries)
+        B = qargs[-1]
+        roff, oth, _ = self._rows(B, others, None)
+        cap, m = self._row_cap(cap, self._e.k), int(roff[-1])
+        ids = np.empty((m, cap), dtype=np.int32)
+        sims = np.empty((m, cap), dtype=np.float64)
+        counts = np.zeros(m, dtype=np.int32)
+        st = np.zeros(B, dtype=np.int32)
+        p = self._e._ptr
+        self._e._check(self._e._lib.knncf_query_bystander_neighbors_batch(
+            self._e._h, *qargs, p(roff, _i64p), p(oth, _i32p), cap, p(ids.reshape(-1), _i32p), p(sims.reshape(-1), _f64p),
+            p(counts, _i32p), p(st, _i32p)))
+        row = lambda r: (ids[r, :min(counts[r], cap)].copy(), sims[r, :min(counts[r], cap)].copy())
+        return [[row(r) for r in range(roff[b], roff[b + 1])] for b in range(B)], st
+
+    def predict_for_batch(self, queries, others, pred_items):
+        """predict_for of every query; others / pred_items hold one sequence per query:
+        ([float64 array] per query, statuses).  A failed query's array holds NaN."""
+        qargs, keep = self._e._batch_args("query", queries)
+        B = qargs[-1]
+        roff, oth, pi = self._rows(B, others, pred_items)
+        out = np.full(int(roff[-1]), np.nan, dtype=np.float64)
+        st = np.zeros(B, dtype=np.int32)
+        p = self._e._ptr
+        self._e._check(self._e._lib.knncf_query_bystander_predict_batch(
+            self._e._h, PRED_KNN, *qargs, p(roff, _i64p), p(oth, _i32p), p(pi, _i32p), p(out, _f64p), p(st, _i32p)))
+        return [out[roff[b]:roff[b + 1]].copy() for b in range(B)], st
 
 
 class Group:
