@@ -101,7 +101,7 @@ struct PrepScratch {
     DArr<uint32_t> status;  // [4] device status words
     DArr<int32_t> idrange;  // [4] min / max raw user id, min / max raw item id
     DArr<uint32_t> ucnt, utile;  // [U] ratings per user (then the scatter cursors), [U / 2048] their sums per tile
-    DArr<int32_t> long_rows;  // [2 (U + 1)] users whose segment is sorted by the wider classes of k_user_hash_order
+    DArr<int32_t> long_rows;  // [2 (U + 1)] users whose segment is sorted by the list classes of k_user_setup
     DArr<double> dsum;      // small reduction scratch
     DArr<uint4> rec;        // [2 n] (preprocessed rating, deviation | user, file row) records: one 32-byte gather per entry
     // second stream of the fit: the per-user LDS sorts of the few long rows run beside those of everybody else

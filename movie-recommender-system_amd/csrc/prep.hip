@@ -13,6 +13,7 @@
 #include <stdlib.h>
 
 #include "engine.h"
+#include "wave_helpers.h"
 
 namespace knncf {
 
@@ -199,52 +200,126 @@ __global__ void k_slice_hash_keys(int64_t m, int32_t lo, const uint32_t* __restr
     key[j] = ((uint64_t)(uint32_t)(s_user[p] - lo) << 32) | tuple_trie_key(users[t], items[t]);
 }
 
-// ---- (user, HashMap order) positions by a sort of every user's own segment in LDS ---------------------------------
+// ---- (user, HashMap order) positions by a sort of every user's own segment on chip --------------------------------
 // perm_uh is the canonical positions re-ordered, inside every user, by (trie key of the (user, item) tuple hash, file row).
 // As a global radix sort that is 7 passes over 20 M (64-bit key, value) pairs; but the canonical order already groups the
-// positions by user, and a user's segment (123 ratings on average) fits in LDS: one wave sorts one segment (bitonic network
-// over 64-bit keys (trie key << 32 | file row) with the local index riding along; no workgroup barrier), a whole workgroup
-// the few segments beyond SEG_WAVE_CAP.  A segment longer than SEG_BLOCK_CAP sets ST_LONG_ROW and the fit falls back to
-// the global sort.
-static constexpr int SEG_SHORT_CAP = 512;    // class 0: one wave per segment, every user (5 KB of LDS per wave)
+// positions by user, and a user's segment (123 ratings on average) fits in the registers of one wave: one wave sorts one
+// segment (bitonic network over 64-bit keys (trie key << 32 | file row) with the local index riding along; no workgroup
+// barrier), a whole workgroup the few segments beyond SEG_SHORT_CAP.  A segment longer than SEG_BLOCK_CAP sets ST_LONG_ROW
+// and the fit falls back to the global sort.
+static constexpr int SEG_SHORT_CAP = 512;    // class 0: one wave per segment, every user (4 KB of LDS per wave)
 static constexpr int SEG_MID_CAP = 2048;     // class 1: one workgroup per segment of the middle list (20 KB: eight per CU)
 static constexpr int SEG_BLOCK_CAP = 8192;   // class 2: one workgroup per segment of the long list (80 KB)
 // (powers of two: a segment is padded to the next one for the network)
 
-// The network's stages with a stride of at most 64 pair elements inside one 128-element chunk, and the chunk of pair index t
-// belongs to the wave that t's 64-group maps to (THREADS is a multiple of 64): those stages need no workgroup barrier, only
-// the wave's own ordering.  A workgroup barrier is due before a stage whose pairs cross chunks and before the first
-// wave-local stage after one (27 of the 91 stages of an 8192-element segment instead of all of them).
-template <int THREADS, bool BLOCK, bool VAL>
-__device__ __forceinline__ void segment_bitonic(unsigned long long* key, uint16_t* val, int32_t N, int tid) {
-    auto wave_sync = [] {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    };
-    bool prev_wide = true;  // (the segment was loaded by arbitrary threads)
-    for (int32_t size = 2; size <= N; size <<= 1) {
-        for (int32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            const bool wide = stride >= 128;
-            if (BLOCK && (wide || prev_wide)) __syncthreads();
-            else wave_sync();
-            prev_wide = wide;
-            for (int32_t t = tid; t < (N >> 1); t += THREADS) {
-                const int32_t lo = 2 * t - (t & (stride - 1));
-                const int32_t hi = lo + stride;
-                const bool up = (lo & size) == 0;
-                const unsigned long long a = key[lo], b = key[hi];
+// The network keeps a segment of N = 64 W R elements in R registers of each of the 64 W threads and only ever compares
+// (a) two registers of one thread or (b) one register of two lanes of a wave.  Which element a register holds is a layout,
+// element = base + unit * r:
+//   blocked   base = lane + 64 R wave, unit = 64       a wave owns 64 R consecutive elements: strides 1 .. 32 are (b),
+//                                                       strides 64 .. 32 R are (a)
+//   striped   base = thread,           unit = 64 W     strides 64 W .. N / 2 are (a)
+// A wave sorts its own block without LDS.  Every later merge (W > 1) runs its strides down to 64 R striped and the rest
+// blocked (R >= W: the two layouts cover every stride); the change of layout is the only use of LDS: two per merge, four
+// workgroup barriers — 12 for a segment of 8192, whose 91 stages were 27 barriers and 91 LDS round trips as an LDS network.
+// (lane_xor is rerank.hip's; a second copy, so that the re-rank kernels' code does not move.)
+template <int STRIDE>
+__device__ __forceinline__ uint32_t seg_lane_xor(uint32_t v, int lane) {
+    typedef __attribute__((ext_vector_type(2))) unsigned int u2v;
+    if constexpr (STRIDE == 1) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);        // quad_perm:[1,0,3,2]
+    else if constexpr (STRIDE == 2) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false);   // quad_perm:[2,3,0,1]
+    else if constexpr (STRIDE == 4) {
+        const uint32_t below = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x124, 0xF, 0xF, false);  // row_ror:4: from lane l - 4
+        const uint32_t above = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x12C, 0xF, 0xF, false);  // row_ror:12: from lane l + 4
+        return (lane & 4) ? below : above;
+    } else if constexpr (STRIDE == 8) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, false);  // row_ror:8
+    else if constexpr (STRIDE == 16) {
+        const u2v r = __builtin_amdgcn_permlane16_swap(v, v, false, false);  // x: rows 0 0 2 2, y: rows 1 1 3 3
+        return (lane & 16) ? r.x : r.y;
+    } else {
+        static_assert(STRIDE == 32, "seg_lane_xor: stride");
+        const u2v r = __builtin_amdgcn_permlane32_swap(v, v, false, false);  // x: lower half twice, y: upper half twice
+        return (lane & 32) ? r.x : r.y;
+    }
+}
+// (b) at lane stride S of the merge of `size`, every register.  Keys are unique but for the padding, whose values nobody reads.
+template <int R, int S, bool VAL>
+__device__ __forceinline__ void seg_lane_stage(unsigned long long (&k)[R], uint32_t (&v)[R], int lane, int32_t base, int32_t size) {
+    const bool is_lo = (lane & S) == 0;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const unsigned long long p = ((unsigned long long)seg_lane_xor<S>((uint32_t)(k[r] >> 32), lane) << 32) | seg_lane_xor<S>((uint32_t)k[r], lane);
+        const uint32_t pv = VAL ? seg_lane_xor<S>(v[r], lane) : 0u;
+        const bool keep_min = is_lo == (((base + 64 * r) & size) == 0);
+        if ((p < k[r]) == keep_min) {
+            k[r] = p;
+            if (VAL) v[r] = pv;
+        }
+    }
+}
+// (a) at register strides M .. LAST of the merge of `size` (a stride that reaches `size` belongs to a later merge)
+template <int R, int M, int LAST, bool VAL>
+__device__ __forceinline__ void seg_regs_from(unsigned long long (&k)[R], uint32_t (&v)[R], int32_t base, int32_t unit, int32_t size) {
+    if constexpr (M >= 1 && M >= LAST) {
+        if (unit * M < size) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if ((r & M) != 0) continue;
+                const bool up = ((base + unit * r) & size) == 0;
+                const unsigned long long a = k[r], b = k[r | M];
                 if ((a > b) == up) {
-                    key[lo] = b; key[hi] = a;
+                    k[r] = b; k[r | M] = a;
                     if (VAL) {
-                        const uint16_t va = val[lo], vb = val[hi];
-                        val[lo] = vb; val[hi] = va;
+                        const uint32_t va = v[r];
+                        v[r] = v[r | M]; v[r | M] = va;
                     }
                 }
             }
         }
+        seg_regs_from<R, M / 2, LAST, VAL>(k, v, base, unit, size);
     }
-    if (BLOCK) __syncthreads();
-    else wave_sync();
+}
+// one layout to the other through LDS: every thread of the workgroup, two barriers (the second frees the buffer again)
+template <int R, bool VAL>
+__device__ __forceinline__ void seg_relayout(unsigned long long (&k)[R], uint32_t (&v)[R], int32_t from, int32_t from_unit, int32_t to,
+                                             int32_t to_unit, unsigned long long* xk, uint16_t* xv) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        xk[from + from_unit * r] = k[r];
+        if (VAL) xv[from + from_unit * r] = (uint16_t)v[r];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        k[r] = xk[to + to_unit * r];
+        if (VAL) v[r] = xv[to + to_unit * r];
+    }
+    __syncthreads();
+}
+// in: any order, blocked; out: ascending, blocked.  W > 1: every thread of the workgroup must call; xk [64 W R], xv [64 W R].
+// The merges are one loop over one copy of every stage (a stride that reaches `size` is skipped): the code stays small.
+template <int R, int W, bool VAL>
+__device__ __forceinline__ void seg_sort(unsigned long long (&k)[R], uint32_t (&v)[R], int tid, unsigned long long* xk, uint16_t* xv) {
+    constexpr int THREADS = 64 * W, N = THREADS * R;
+    static_assert(R >= W, "seg_sort: the two layouts must cover every stride");
+    const int lane = tid & 63;
+    const int32_t base = lane + 64 * R * (tid >> 6);
+#pragma unroll 1
+    for (int32_t size = 2; size <= N; size <<= 1) {
+        if constexpr (W > 1) {
+            if (size > 64 * R) {
+                seg_relayout<R, VAL>(k, v, base, 64, tid, THREADS, xk, xv);
+                seg_regs_from<R, R / 2, R / W, VAL>(k, v, tid, THREADS, size);
+                seg_relayout<R, VAL>(k, v, tid, THREADS, base, 64, xk, xv);
+            }
+        }
+        seg_regs_from<R, R / 2, 1, VAL>(k, v, base, 64, size);
+        if (size > 32) seg_lane_stage<R, 32, VAL>(k, v, lane, base, size);
+        if (size > 16) seg_lane_stage<R, 16, VAL>(k, v, lane, base, size);
+        if (size > 8) seg_lane_stage<R, 8, VAL>(k, v, lane, base, size);
+        if (size > 4) seg_lane_stage<R, 4, VAL>(k, v, lane, base, size);
+        if (size > 2) seg_lane_stage<R, 2, VAL>(k, v, lane, base, size);
+        seg_lane_stage<R, 1, VAL>(k, v, lane, base, size);
+    }
 }
 
 struct SegLists {
@@ -262,58 +337,6 @@ __global__ void k_classify_rows(int32_t U, const int64_t* __restrict__ u_ptr, Se
     else if (n > SEG_MID_CAP && n <= SEG_BLOCK_CAP) L.longs[atomicAdd(&L.counts[1], 1u)] = u;
 }
 static constexpr int seg_threads(int cls) { return cls == 2 ? 512 : TPB; }
-
-// CLASS 0 walks the users [u_lo, u_hi) (one wave each, skipping the longer segments); CLASS 1 / 2 walk their list
-// (k_classify_rows; a workgroup per entry, grid-stride: the list's length stays on the device) and keep to the same user
-// range.  The three classes touch disjoint users, so prep_fit runs the two list classes on a second stream beside class 0:
-// a segment of 8192 is one workgroup's chain of 91 barrier-separated network stages, 0.2 ms during which it needs no CU
-// but its own.  The host only takes this path when no segment exceeds SEG_BLOCK_CAP (prep_fit reads the longest row's
-// length back); ST_LONG_ROW is a consistency check.
-// FILE_ORDER: the key is the file row alone — perm_uf, the (user, file row) order of usersAvg :113.
-template <int CLASS, bool FILE_ORDER>
-__global__ void __launch_bounds__(seg_threads(CLASS)) k_user_hash_order(const int64_t* __restrict__ u_ptr, int32_t u_lo, int32_t u_hi, SegLists L,
-                                                         const int32_t* __restrict__ uid, const int32_t* __restrict__ iid,
-                                                         const int32_t* __restrict__ s_col, const uint32_t* __restrict__ s_t,
-                                                         uint32_t* __restrict__ perm_out, uint32_t* __restrict__ status) {
-    extern __shared__ __attribute__((aligned(16))) char seg_smem[];
-    constexpr bool BLOCK = CLASS >= 1;
-    constexpr int CAP = CLASS == 0 ? SEG_SHORT_CAP : CLASS == 1 ? SEG_MID_CAP : SEG_BLOCK_CAP;
-    constexpr int THREADS = BLOCK ? seg_threads(CLASS) : 64;
-    constexpr int SEGS = BLOCK ? 1 : TPB / 64;  // segments in flight per workgroup
-    const int wave = BLOCK ? 0 : (int)(threadIdx.x >> 6);
-    const int tid = BLOCK ? (int)threadIdx.x : (int)(threadIdx.x & 63);
-    unsigned long long* key = reinterpret_cast<unsigned long long*>(seg_smem) + (size_t)wave * CAP;
-    uint16_t* val = reinterpret_cast<uint16_t*>(reinterpret_cast<unsigned long long*>(seg_smem) + (size_t)SEGS * CAP) + (size_t)wave * CAP;
-    const int64_t total = CLASS == 0 ? (int64_t)(u_hi - u_lo) : (int64_t)L.counts[CLASS - 1];
-    for (int64_t idx = (int64_t)blockIdx.x * SEGS + wave; idx < total; idx += (int64_t)gridDim.x * SEGS) {
-        const int32_t u = CLASS == 0 ? u_lo + (int32_t)idx : (CLASS == 1 ? L.mid[idx] : L.longs[idx]);
-        if (CLASS > 0 && (u < u_lo || u >= u_hi)) continue;  // (workgroup-uniform)
-        const int64_t b = u_ptr[u], e = u_ptr[u + 1];
-        const int64_t n64 = e - b;
-        if (n64 > CAP) {  // (only class 0 meets these: they are on the lists)
-            if (n64 > SEG_BLOCK_CAP && tid == 0) atomicOr(status, (uint32_t)ST_LONG_ROW);
-            continue;
-        }
-        const int32_t n = (int32_t)n64;
-        int32_t N = 2;
-        while (N < n) N <<= 1;
-        const int32_t user_raw = uid[u];
-        for (int32_t i = tid; i < N; i += THREADS) {
-            unsigned long long k = ~0ull;
-            if (i < n) {
-                if (FILE_ORDER) k = s_t[b + i];
-                else k = ((unsigned long long)tuple_trie_key(user_raw, iid[s_col[b + i]]) << 32) | s_t[b + i];
-            }
-            key[i] = k;
-            val[i] = (uint16_t)i;
-        }
-        segment_bitonic<THREADS, BLOCK, true>(key, val, N, tid);
-        for (int32_t i = tid; i < n; i += THREADS) perm_out[b + i] = (uint32_t)(b + val[i]);
-        // (the next segment's stores into key / val follow this wave's / workgroup's reads in program order; the workgroup
-        // form needs its barrier)
-        if (BLOCK) __syncthreads();
-    }
-}
 
 // ---- the canonical (user, item) order by a counting scatter + a sort of every user's own segment in LDS ---------------
 // As a global radix sort the canonical order is 5 passes over 20 M (64-bit key, value) pairs.  Dense user indices make the
@@ -431,44 +454,248 @@ __global__ void k_scatter_rows(int64_t n, const int32_t* __restrict__ du, const 
     const int64_t slot = u_ptr[u] + base + (uint32_t)((int)(threadIdx.x & 63) - r.head_lane);
     rows[slot] = ((unsigned long long)(uint32_t)di[t] << 32) | (uint32_t)t;
 }
-template <int CLASS>
-__global__ void __launch_bounds__(seg_threads(CLASS)) k_user_item_order(const int64_t* __restrict__ u_ptr, int32_t U, SegLists L,
-                                                         const unsigned long long* __restrict__ rows, const double* __restrict__ rating,
-                                                         int32_t* __restrict__ s_user, int32_t* __restrict__ s_col,
-                                                         uint32_t* __restrict__ s_t, double* __restrict__ s_rating,
-                                                         uint32_t* __restrict__ status) {
+// One kernel per size class does everything that is a function of one user's segment alone, with the segment on chip:
+//   1. the scattered rows (item << 32 | file row), sorted by item: s_user, s_col, s_t, s_rating; equal neighbours are a
+//      duplicate (user, item) pair;
+//   2. the owned users [o_lo, o_hi): perm_uf (key: the file row) and perm_uh (key: trie key of the tuple << 32 | file row),
+//      each where the fit wants it, sorted with the local index riding along;
+//   3. FUSED — a whole-file fit of dyadic ratings, the benchmark's path and every MovieLens file — K2 and K3 as well: the
+//      mean (an exact sum in any order, divided as k_divide_by_count does), the deviations (k_deviation's expression), the
+//      norm (the left fold 0.0 + d0^2 + d1^2 .. in perm_uh order, every square rounded before it is added: one lane's chain
+//      out of LDS, fed a batch ahead like k_ordered_fold's, then k_sqrt's step) and the preprocessed ratings.
+// CLASS 0 walks all users, one wave each, skipping the longer segments; CLASS 1 / 2 walk their list (k_classify_rows; a
+// workgroup per entry, grid-stride: the list's length stays on the device).  The three classes touch disjoint users, so
+// prep_fit runs the two list classes on a second stream beside class 0: a long segment is one workgroup's chain, during
+// which it needs no CU but its own.  The host only takes this path when no segment exceeds SEG_BLOCK_CAP (prep_fit reads
+// the longest row's length back); ST_LONG_ROW is a consistency check.
+struct SetupArgs {
+    const int64_t* u_ptr;
+    const unsigned long long* rows;
+    const double* rating;
+    const int32_t* uid;
+    const int32_t* iid;
+    int32_t* s_user;
+    int32_t* s_col;
+    uint32_t* s_t;
+    double* s_rating;
+    uint32_t* perm_uf;  // nullptr: not wanted
+    uint32_t* perm_uh;  // nullptr: not wanted
+    double* s_dev;      // FUSED only, like the three below
+    double* s_pre;
+    double* user_avg;
+    double* user_norm;
+    uint32_t* status;
+    int32_t U, o_lo, o_hi;
+};
+static constexpr int SETUP_MISC = 32;  // doubles of LDS beside the exchange buffers: per-wave partial sums, the fold's result
+
+// the left fold 0.0 + sq[0] + sq[1] .. of one thread: the LDS reads of the next FB values are issued before the current
+// FB are added (k_ordered_fold)
+__device__ __forceinline__ double seg_serial_fold(const double* sq, int32_t n) {
+    constexpr int FB = 16;
+    double acc = 0.0;
+    int32_t q = 0;
+    if (FB <= n) {
+        double a[FB], c[FB];
+#pragma unroll
+        for (int j = 0; j < FB; ++j) a[j] = sq[j];
+        for (; q + 2 * FB <= n; q += FB) {
+#pragma unroll
+            for (int j = 0; j < FB; ++j) c[j] = sq[q + FB + j];
+#pragma unroll
+            for (int j = 0; j < FB; ++j) acc = acc + a[j];
+#pragma unroll
+            for (int j = 0; j < FB; ++j) a[j] = c[j];
+        }
+#pragma unroll
+        for (int j = 0; j < FB; ++j) acc = acc + a[j];
+        q += FB;
+    }
+    for (; q < n; ++q) acc = acc + sq[q];
+    return acc;
+}
+
+// one segment of n <= 64 W R ratings at [b, b + n).  W > 1: called by every thread of the workgroup (it holds barriers);
+// W == 1: by the 64 lanes of a wave, xk is the wave's own.  xk [64 W R] (doubles as the deviations / squares), xv [64 W R]
+template <int R, int W, bool FUSED>
+__device__ __forceinline__ void setup_segment(const SetupArgs& A, int32_t u, int64_t b, uint32_t n, int tid, unsigned long long* xk,
+                                              uint16_t* xv, double* misc) {
+    const int lane = tid & 63, wave = tid >> 6;
+    const int32_t base = lane + 64 * R * wave;  // this thread's elements: base + 64 r (blocked layout)
+    auto sync = [] {
+        if constexpr (W > 1) __syncthreads();
+        else wave_sync();
+    };
+    // (b is uniform: the segment's arrays are addressed as a scalar base + a 32-bit offset; uniform_ptr keeps the compiler
+    // from folding the lane's offset into the base ahead of the loop over the segments, 64 bits per register and array)
+    const unsigned long long* rows = uniform_ptr(A.rows + b);
+    int32_t* s_user = uniform_ptr(A.s_user + b);
+    int32_t* s_col = uniform_ptr(A.s_col + b);
+    uint32_t* s_t = uniform_ptr(A.s_t + b);
+    double* s_rating = uniform_ptr(A.s_rating + b);
+    unsigned long long k[R];
+    uint32_t v[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const uint32_t e = (uint32_t)(base + 64 * r);
+        k[r] = e < n ? rows[e] : ~0ull;
+        v[r] = 0;
+    }
+    seg_sort<R, W, false>(k, v, tid, xk, xv);
+    uint32_t* wave_last = reinterpret_cast<uint32_t*>(misc + 16);  // the last item of every wave's block
+    if constexpr (W > 1) {
+        if (lane == 63) wave_last[wave] = (uint32_t)(k[R - 1] >> 32);
+    }
+    double rt[R];
+    double sum = 0.0;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const uint32_t e = (uint32_t)(base + 64 * r);
+        const uint32_t t = (uint32_t)k[r];
+        rt[r] = 0.0;
+        if (e < n) {
+            rt[r] = A.rating[t];
+            s_user[e] = u;
+            s_col[e] = (int32_t)(k[r] >> 32);
+            s_t[e] = t;
+            s_rating[e] = rt[r];
+        }
+        sum += rt[r];  // (dyadic ratings: exact in any order)
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    if constexpr (W > 1) {
+        if (lane == 0) misc[wave] = sum;
+        __syncthreads();
+        sum = 0.0;
+#pragma unroll
+        for (int w = 0; w < W; ++w) sum += misc[w];
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {  // element e - 1 sits one lane below, or in lane 63 of the register / the wave below
+        const uint32_t e = (uint32_t)(base + 64 * r);
+        const uint32_t item = (uint32_t)(k[r] >> 32);
+        uint32_t prev = __shfl_up(item, 1);
+        if (r > 0) {
+            const uint32_t wrap = __shfl((uint32_t)(k[r > 0 ? r - 1 : 0] >> 32), 63);
+            if (lane == 0) prev = wrap;
+        } else if (W > 1) {
+            if (lane == 0 && wave > 0) prev = wave_last[wave - 1];
+        }
+        if (e > 0 && e < n && prev == item) atomicOr(A.status, (uint32_t)ST_DUPLICATE);
+    }
+    double mean = 0.0;
+    double d[R];
+    if constexpr (FUSED) {
+        mean = sum / (double)n;
+        double* s_dev = uniform_ptr(A.s_dev + b);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const uint32_t e = (uint32_t)(base + 64 * r);
+            d[r] = 0.0;
+            if (e < n) {
+                d[r] = (rt[r] - mean) / scale_fn(rt[r], mean);
+                s_dev[e] = d[r];
+                if (!isfinite(d[r])) atomicOr(A.status, (uint32_t)ST_NONFINITE);
+            }
+        }
+    }
+    const bool own = u >= A.o_lo && u < A.o_hi;  // (uniform over the segment's threads, like the loop's conditions)
+    // the fold orders, one copy of the network for both: 0 = perm_uf (key: the file row), 1 = perm_uh
+    unsigned long long h[R];
+#pragma unroll 1
+    for (int order = FUSED ? 1 : 0; order < 2; ++order) {
+        uint32_t* perm = order == 0 ? A.perm_uf : A.perm_uh;
+        if (!own || !perm) continue;
+        perm = uniform_ptr(perm + b);
+        const int32_t user_raw = A.uid[u];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const uint32_t e = (uint32_t)(base + 64 * r);
+            h[r] = ~0ull;
+            if (e < n) {
+                const uint32_t top = order == 0 ? 0u : tuple_trie_key(user_raw, A.iid[(int32_t)(k[r] >> 32)]);
+                h[r] = ((unsigned long long)top << 32) | (uint32_t)k[r];
+            }
+            v[r] = (uint32_t)e;
+        }
+        seg_sort<R, W, true>(h, v, tid, xk, xv);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const uint32_t e = (uint32_t)(base + 64 * r);
+            if (e < n) perm[e] = (uint32_t)b + v[r];
+        }
+    }
+    if constexpr (FUSED) {  // (perm_uh is wanted: v is the hash order's local index; the sort is done with its buffer)
+        double* cell = reinterpret_cast<double*>(xk);
+#pragma unroll
+        for (int r = 0; r < R; ++r) cell[base + 64 * r] = d[r];
+        sync();
+        double sq[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const uint32_t e = (uint32_t)(base + 64 * r);
+            const double g = e < n ? cell[v[r]] : 0.0;
+            sq[r] = g * g;
+        }
+        sync();
+#pragma unroll
+        for (int r = 0; r < R; ++r) cell[base + 64 * r] = sq[r];
+        sync();
+        if (tid == 0) misc[8] = seg_serial_fold(cell, n);
+        sync();
+        const double w = sqrt(misc[8]);
+        double* s_pre = uniform_ptr(A.s_pre + b);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const uint32_t e = (uint32_t)(base + 64 * r);
+            if (e < n) s_pre[e] = (w != 0) ? d[r] / w : 0.0;
+        }
+        if (tid == 0) {
+            A.user_avg[u] = mean;
+            A.user_norm[u] = w;
+        }
+    }
+    sync();  // (the next segment writes xk and misc)
+}
+
+template <int CLASS, bool FUSED>
+__global__ void __launch_bounds__(seg_threads(CLASS)) k_user_setup(SetupArgs A, SegLists L) {
     extern __shared__ __attribute__((aligned(16))) char seg_smem[];
     constexpr bool BLOCK = CLASS >= 1;
     constexpr int CAP = CLASS == 0 ? SEG_SHORT_CAP : CLASS == 1 ? SEG_MID_CAP : SEG_BLOCK_CAP;
-    constexpr int THREADS = BLOCK ? seg_threads(CLASS) : 64;
-    constexpr int SEGS = BLOCK ? 1 : TPB / 64;
-    const int wave = BLOCK ? 0 : (int)(threadIdx.x >> 6);
+    constexpr int W = BLOCK ? seg_threads(CLASS) / 64 : 1;
+    constexpr int SEGS = BLOCK ? 1 : TPB / 64;  // segments in flight per workgroup
+    constexpr int RMAX = CAP / (64 * W);
+    const int wave = BLOCK ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (uniform, and known to be)
     const int tid = BLOCK ? (int)threadIdx.x : (int)(threadIdx.x & 63);
-    unsigned long long* key = reinterpret_cast<unsigned long long*>(seg_smem) + (size_t)wave * CAP;
-    const int64_t total = CLASS == 0 ? (int64_t)U : (int64_t)L.counts[CLASS - 1];
+    // [SEGS][CAP] keys, [SEGS][CAP] values (the list classes only), [SEGS][SETUP_MISC] doubles
+    unsigned long long* xk = reinterpret_cast<unsigned long long*>(seg_smem) + (size_t)wave * CAP;
+    uint16_t* xv = reinterpret_cast<uint16_t*>(reinterpret_cast<unsigned long long*>(seg_smem) + (size_t)SEGS * CAP);
+    double* misc = reinterpret_cast<double*>(seg_smem + (size_t)SEGS * CAP * (BLOCK ? 10 : 8)) + (size_t)wave * SETUP_MISC;
+    const int64_t total = CLASS == 0 ? (int64_t)A.U : (int64_t)L.counts[CLASS - 1];
     for (int64_t idx = (int64_t)blockIdx.x * SEGS + wave; idx < total; idx += (int64_t)gridDim.x * SEGS) {
         const int32_t u = CLASS == 0 ? (int32_t)idx : (CLASS == 1 ? L.mid[idx] : L.longs[idx]);
-        const int64_t b = u_ptr[u], e = u_ptr[u + 1];
+        const int64_t b = A.u_ptr[u], e = A.u_ptr[u + 1];
         const int64_t n64 = e - b;
         if (n64 > CAP) {  // (only class 0 meets these: they are on the lists)
-            if (n64 > SEG_BLOCK_CAP && tid == 0) atomicOr(status, (uint32_t)ST_LONG_ROW);
+            if (n64 > SEG_BLOCK_CAP && tid == 0) atomicOr(A.status, (uint32_t)ST_LONG_ROW);
             continue;
         }
+        // (uniform over the segment's threads: u is the wave's in class 0, the workgroup's in the list classes)
         const int32_t n = (int32_t)n64;
-        int32_t N = 2;
-        while (N < n) N <<= 1;
-        for (int32_t i = tid; i < N; i += THREADS) key[i] = i < n ? rows[b + i] : ~0ull;
-        segment_bitonic<THREADS, BLOCK, false>(key, nullptr, N, tid);
-        for (int32_t i = tid; i < n; i += THREADS) {
-            const unsigned long long k = key[i];
-            const uint32_t t = (uint32_t)k;
-            s_user[b + i] = u;
-            s_col[b + i] = (int32_t)(k >> 32);
-            s_t[b + i] = t;
-            s_rating[b + i] = rating[t];
-            if (i > 0 && (key[i - 1] >> 32) == (k >> 32)) atomicOr(status, (uint32_t)ST_DUPLICATE);
+        if constexpr (!BLOCK) {  // (the network is instantiated per padded size: 64 and 128 here, 256 and 512 below)
+            if (n <= CAP / 8) {
+                setup_segment<RMAX / 8, W, FUSED>(A, u, b, n, tid, xk, xv, misc);
+                continue;
+            }
+            if (n <= CAP / 4) {
+                setup_segment<RMAX / 4, W, FUSED>(A, u, b, n, tid, xk, xv, misc);
+                continue;
+            }
         }
-        if (BLOCK) __syncthreads();
+        if (n <= CAP / 2) setup_segment<RMAX / 2, W, FUSED>(A, u, b, n, tid, xk, xv, misc);
+        else setup_segment<RMAX, W, FUSED>(A, u, b, n, tid, xk, xv, misc);
     }
 }
 
@@ -840,8 +1067,9 @@ void prep_fit(Train& tr, PrepScratch& sc, int32_t shard_rank, int32_t shard_coun
     const bool seg_sorts = max_len <= (uint32_t)SEG_BLOCK_CAP && !getenv("KNNCF_DEBUG_GLOBAL_HASH_ORDER");
     sc.long_rows.ensure(2 * (size_t)U + 2);
     SegLists L{sc.long_rows.p, sc.long_rows.p + U + 1, sc.status.p + 2};
-    constexpr size_t smem_pair0 = (size_t)(TPB / 64) * SEG_SHORT_CAP * 10, smem_pair1 = (size_t)SEG_MID_CAP * 10, smem_pair2 = (size_t)SEG_BLOCK_CAP * 10;
-    constexpr size_t smem_key0 = (size_t)(TPB / 64) * SEG_SHORT_CAP * 8, smem_key1 = (size_t)SEG_MID_CAP * 8, smem_key2 = (size_t)SEG_BLOCK_CAP * 8;
+    // (exchange buffers of the per-segment kernels: keys, 16-bit values for the list classes, SETUP_MISC doubles per segment)
+    constexpr size_t smem_seg0 = (size_t)(TPB / 64) * (SEG_SHORT_CAP * 8 + SETUP_MISC * 8);
+    constexpr size_t smem_seg1 = (size_t)SEG_MID_CAP * 10 + SETUP_MISC * 8, smem_seg2 = (size_t)SEG_BLOCK_CAP * 10 + SETUP_MISC * 8;
 
     // canonical user-major order: file rows by (user, item)
     bool have_perm_f = false;
@@ -860,15 +1088,15 @@ void prep_fit(Train& tr, PrepScratch& sc, int32_t shard_rank, int32_t shard_coun
     else tr.perm_uf.release();
     if (n > 4) tr.perm_uh.alloc(n);  // a Map of <= 4 entries (Map1..Map4) iterates in insertion = file order (N4)
     else tr.perm_uh.release();
+    // K2 and K3 inside the per-segment kernels (k_user_setup): a whole-file fit of dyadic ratings
+    const bool fused = seg_sorts && !need_uf && U > 4;
+    tr.user_avg.alloc(U); tr.user_norm.alloc(U);
     if (seg_sorts) {
-        // Every user's segment sorted in LDS: by item (the canonical order, all users), then — the owned users — by file row
+        // Every user's segment sorted on chip: by item (the canonical order, all users), then — the owned users — by file row
         // and by (trie key of the tuple hash, file row).  Three size classes; the two list classes run on the second stream.
-        static PerDeviceState lds2i, lds1h, lds2h, lds1f, lds2f;
-        ensure_dynamic_lds(lds2i, (const void*)k_user_item_order<2>, smem_key2);
-        ensure_dynamic_lds(lds1h, (const void*)k_user_hash_order<1, false>, smem_pair1);
-        ensure_dynamic_lds(lds2h, (const void*)k_user_hash_order<2, false>, smem_pair2);
-        ensure_dynamic_lds(lds1f, (const void*)k_user_hash_order<1, true>, smem_pair1);
-        ensure_dynamic_lds(lds2f, (const void*)k_user_hash_order<2, true>, smem_pair2);
+        static PerDeviceState lds2, lds2f;
+        ensure_dynamic_lds(lds2, (const void*)k_user_setup<2, false>, smem_seg2);
+        ensure_dynamic_lds(lds2f, (const void*)k_user_setup<2, true>, smem_seg2);
         sc.ensure_aux();
         hipStream_t sx = sc.aux;
         k_scatter_rows<<<nblocks(n), TPB, 0, st>>>(n, sc.du_row.p, sc.di_row.p, tr.u_ptr.p, sc.ucnt.p,
@@ -878,20 +1106,18 @@ void prep_fit(Train& tr, PrepScratch& sc, int32_t shard_rank, int32_t shard_coun
         KN_HIP(hipGetLastError());
         KN_HIP(hipEventRecord(sc.ev_fork, st));
         KN_HIP(hipStreamWaitEvent(sx, sc.ev_fork, 0));
-        const unsigned long long* rows = reinterpret_cast<const unsigned long long*>(sc.k64_a.p);
-        const bool own = hi > lo;
-        k_user_item_order<2><<<1024, seg_threads(2), smem_key2, sx>>>(tr.u_ptr.p, tr.U, L, rows, tr.rating.p, tr.s_user.p, tr.s_col.p, tr.s_t.p, tr.s_rating.p, sc.status.p);
-        k_user_item_order<1><<<2048, TPB, smem_key1, sx>>>(tr.u_ptr.p, tr.U, L, rows, tr.rating.p, tr.s_user.p, tr.s_col.p, tr.s_t.p, tr.s_rating.p, sc.status.p);
-        k_user_item_order<0><<<nblocks(U, TPB / 64), TPB, smem_key0, st>>>(tr.u_ptr.p, tr.U, L, rows, tr.rating.p, tr.s_user.p, tr.s_col.p, tr.s_t.p, tr.s_rating.p, sc.status.p);
-        if (need_uf && own) {
-            k_user_hash_order<2, true><<<1024, seg_threads(2), smem_pair2, sx>>>(tr.u_ptr.p, lo, hi, L, tr.uid.p, tr.iid.p, tr.s_col.p, tr.s_t.p, tr.perm_uf.p, sc.status.p);
-            k_user_hash_order<1, true><<<2048, TPB, smem_pair1, sx>>>(tr.u_ptr.p, lo, hi, L, tr.uid.p, tr.iid.p, tr.s_col.p, tr.s_t.p, tr.perm_uf.p, sc.status.p);
-            k_user_hash_order<0, true><<<nblocks(hi - lo, TPB / 64), TPB, smem_pair0, st>>>(tr.u_ptr.p, lo, hi, L, tr.uid.p, tr.iid.p, tr.s_col.p, tr.s_t.p, tr.perm_uf.p, sc.status.p);
-        }
-        if (n > 4 && own) {
-            k_user_hash_order<2, false><<<1024, seg_threads(2), smem_pair2, sx>>>(tr.u_ptr.p, lo, hi, L, tr.uid.p, tr.iid.p, tr.s_col.p, tr.s_t.p, tr.perm_uh.p, sc.status.p);
-            k_user_hash_order<1, false><<<2048, TPB, smem_pair1, sx>>>(tr.u_ptr.p, lo, hi, L, tr.uid.p, tr.iid.p, tr.s_col.p, tr.s_t.p, tr.perm_uh.p, sc.status.p);
-            k_user_hash_order<0, false><<<nblocks(hi - lo, TPB / 64), TPB, smem_pair0, st>>>(tr.u_ptr.p, lo, hi, L, tr.uid.p, tr.iid.p, tr.s_col.p, tr.s_t.p, tr.perm_uh.p, sc.status.p);
+        const SetupArgs A{tr.u_ptr.p, reinterpret_cast<const unsigned long long*>(sc.k64_a.p), tr.rating.p, tr.uid.p, tr.iid.p,
+                          tr.s_user.p, tr.s_col.p, tr.s_t.p, tr.s_rating.p, need_uf ? tr.perm_uf.p : nullptr,
+                          n > 4 ? tr.perm_uh.p : nullptr, tr.s_dev.p, tr.s_pre.p, tr.user_avg.p, tr.user_norm.p, sc.status.p,
+                          tr.U, lo, hi};
+        if (fused) {
+            k_user_setup<2, true><<<1024, seg_threads(2), smem_seg2, sx>>>(A, L);
+            k_user_setup<1, true><<<2048, TPB, smem_seg1, sx>>>(A, L);
+            k_user_setup<0, true><<<nblocks(U, TPB / 64), TPB, smem_seg0, st>>>(A, L);
+        } else {
+            k_user_setup<2, false><<<1024, seg_threads(2), smem_seg2, sx>>>(A, L);
+            k_user_setup<1, false><<<2048, TPB, smem_seg1, sx>>>(A, L);
+            k_user_setup<0, false><<<nblocks(U, TPB / 64), TPB, smem_seg0, st>>>(A, L);
         }
         KN_HIP(hipGetLastError());
         KN_HIP(hipEventRecord(sc.ev_join, sx));
@@ -944,41 +1170,49 @@ void prep_fit(Train& tr, PrepScratch& sc, int32_t shard_rank, int32_t shard_coun
     tr.item_stats_ready = false;
 
     // K1: average :94 — left fold over the file; exact in any order for dyadic ratings
-    uint32_t status = read_status(sc, st);
-    KN_REQUIRE(!(status & ST_DUPLICATE), KNNCF_E_DUPLICATE, "fit: duplicate (user,item) training rows");
-    KN_REQUIRE(!(status & ST_LONG_ROW), KNNCF_E_STATE, "fit: a row longer than the segment sorts take reached them");
+    // (fused: the status word is read once, with the total, after everything that can set it)
+    uint32_t status = fused ? 0u : read_status(sc, st);
+    auto check_orders = [&] {
+        KN_REQUIRE(!(status & ST_DUPLICATE), KNNCF_E_DUPLICATE, "fit: duplicate (user,item) training rows");
+        KN_REQUIRE(!(status & ST_LONG_ROW), KNNCF_E_STATE, "fit: a row longer than the segment sorts take reached them");
+    };
+    if (!fused) check_orders();
     // (A pair with a <= 4-rating user is summed in the order of whichever closure evaluated it first, SURVEY N6.  Sharded
     // handles follow that history too: the test set is replicated, so every shard assigns EVERY user its build sequence
     // number — api.cpp: ensure_neighbors_for_rows — and rerank.hip applies the owner rule with no exchange.)
     sc.dsum.ensure(2);
     KN_HIP(hipMemsetAsync(sc.dsum.p, 0, 2 * sizeof(double), st));
-    if (status & ST_NOT_DYADIC) k_sequential_sum<<<1, TPB, 0, st>>>(n, tr.rating.p, sc.dsum.p);
+    if (!dyadic) k_sequential_sum<<<1, TPB, 0, st>>>(n, tr.rating.p, sc.dsum.p);
     else k_exact_sum<<<1024, TPB, 0, st>>>(n, tr.rating.p, sc.dsum.p);
     KN_HIP(hipGetLastError());
     double total = 0.0;
     KN_HIP(hipMemcpyAsync(&total, sc.dsum.p, sizeof(double), hipMemcpyDeviceToHost, st));
+    if (fused) KN_HIP(hipMemcpyAsync(&status, sc.status.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     KN_HIP(hipStreamSynchronize(st));
     tr.total = total;
     tr.global_avg = total / (double)n;
 
-    tr.user_avg.alloc(U); tr.user_norm.alloc(U);
     if (shard_count > 1) {  // the host all-gathers the other shards' (mean, norm) segments in place; prep_complete_rows then
                             // fills in the other users' deviations and preprocessed ratings
         KN_HIP(hipMemsetAsync(tr.user_avg.p, 0, U * sizeof(double), st));
         KN_HIP(hipMemsetAsync(tr.user_norm.p, 0, U * sizeof(double), st));
     }
-    if (hi > lo) {
-        // K2: usersAvg :113 (groupBy keeps file order; mean = reduce(_+_) / length)
-        fold<false>(tr.u_ptr.p, lo, hi, need_uf ? tr.perm_uf.p : nullptr, tr.s_rating.p, tr.user_norm.p, st);
-        k_divide_by_count<<<nblocks(hi - lo), TPB, 0, st>>>(tr.u_ptr.p, lo, hi, tr.user_norm.p, tr.user_avg.p);
-        // K3: deviations, norms (HashMap order), preprocessed ratings
-        k_deviation<<<nblocks(p1 - p0), TPB, 0, st>>>(p0, p1, tr.s_user.p, tr.s_rating.p, tr.user_avg.p, tr.s_dev.p, sc.status.p);
-        fold<true>(tr.u_ptr.p, lo, hi, n > 4 ? tr.perm_uh.p : tr.perm_uf.p, tr.s_dev.p, tr.user_norm.p, st);
-        k_sqrt<<<nblocks(hi - lo), TPB, 0, st>>>(lo, hi, tr.user_norm.p, tr.user_norm.p);
-        k_preprocess<<<nblocks(p1 - p0), TPB, 0, st>>>(p0, p1, tr.s_user.p, tr.s_dev.p, tr.user_norm.p, tr.s_pre.p);
-        KN_HIP(hipGetLastError());
+    if (fused) {
+        check_orders();
+    } else {
+        if (hi > lo) {
+            // K2: usersAvg :113 (groupBy keeps file order; mean = reduce(_+_) / length)
+            fold<false>(tr.u_ptr.p, lo, hi, need_uf ? tr.perm_uf.p : nullptr, tr.s_rating.p, tr.user_norm.p, st);
+            k_divide_by_count<<<nblocks(hi - lo), TPB, 0, st>>>(tr.u_ptr.p, lo, hi, tr.user_norm.p, tr.user_avg.p);
+            // K3: deviations, norms (HashMap order), preprocessed ratings
+            k_deviation<<<nblocks(p1 - p0), TPB, 0, st>>>(p0, p1, tr.s_user.p, tr.s_rating.p, tr.user_avg.p, tr.s_dev.p, sc.status.p);
+            fold<true>(tr.u_ptr.p, lo, hi, n > 4 ? tr.perm_uh.p : tr.perm_uf.p, tr.s_dev.p, tr.user_norm.p, st);
+            k_sqrt<<<nblocks(hi - lo), TPB, 0, st>>>(lo, hi, tr.user_norm.p, tr.user_norm.p);
+            k_preprocess<<<nblocks(p1 - p0), TPB, 0, st>>>(p0, p1, tr.s_user.p, tr.s_dev.p, tr.user_norm.p, tr.s_pre.p);
+            KN_HIP(hipGetLastError());
+        }
+        status = read_status(sc, st);
     }
-    status = read_status(sc, st);
     KN_REQUIRE(!(status & ST_NONFINITE), KNNCF_E_NONFINITE,
                "fit: non-finite normalized deviation (a user's mean is 1 or 5 with a rating beyond it: scale() == 0)");
 }

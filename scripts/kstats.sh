@@ -1,7 +1,7 @@
 # usage (GPU box, repo root): bash scripts/kstats.sh <tag> [grep pattern]
 # rocprofv3 kernel summary of a 3-step bench run; prints the rows matching the pattern (default: the prep kernels)
 TAG=${1:-ks}
-PAT=${2:-"k_user_hash_order|k_item|k_pack|k_make_keys|k_unpack|k_gather|k_invert|k_ordered_fold|onesweep|k_dev|k_pre|k_mark|k_dense|k_table|k_resolve|k_raw|k_segment|k_col_keys|k_id_range|k_check|k_exact"}
+PAT=${2:-"k_user_setup|k_item|k_pack|k_make_keys|k_unpack|k_gather|k_invert|k_ordered_fold|onesweep|k_dev|k_pre|k_mark|k_dense|k_table|k_resolve|k_raw|k_segment|k_col_keys|k_id_range|k_check|k_exact"}
 R=$(pwd)
 O=$R/gpurun_out/$TAG
 mkdir -p $O
