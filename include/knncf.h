@@ -806,8 +806,8 @@ int knncf_revise_recommend_explain_batch(knncf_handle* h, int predictor, const i
  * knncf_neighbors_save bytes stay as they were.  knncf_get_timings: charged as the fold-in calls charge theirs.
  * OUT OF SCOPE: bystanders of update and revise queries (a newcomer that is in the fit changes its own mean, and with it the
  * deviation of every one of its train rows in other users' folds); KNNCF_PRED_PERSONALIZED and the other predictors;
- * recommendations and explanations for a bystander; "which fitted users does the newcomer enter"; device-pointer forms; shard
- * handles and knncf_group_*. */
+ * recommendations and explanations for a bystander; device-pointer forms; shard handles and knncf_group_*.  ("Which fitted
+ * users does the newcomer enter" is knncf_query_entered, below.) */
 int knncf_query_bystander_neighbors(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
                                     const int32_t* others, int64_t m, int32_t cap, int32_t* ids, double* sims, int32_t* counts);
 int knncf_query_bystander_predict(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
@@ -818,6 +818,57 @@ int knncf_query_bystander_neighbors_batch(knncf_handle* h, const int32_t* users,
 int knncf_query_bystander_predict_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets,
                                         const int32_t* items, const double* ratings, int64_t n_queries, const int64_t* row_offsets,
                                         const int32_t* others, const int32_t* pred_items, double* out, int32_t* statuses);
+
+/* ---- Entered queries: which fitted users' neighbour lists a newcomer joins ---------------------------------------------------
+ * Under KNNCF_PRED_KNN a fitted user v's predictions change when a newcomer joins only if the newcomer enters
+ * getNeighbors(aug, k, sim)(v) (the shift of average(aug) matters only to users who are answered with it).  These calls name
+ * those v in one pass over the fit, where knncf_query_bystander_neighbors would take one slot per fitted user.
+ * A query is a fold-in query exactly as knncf_query_neighbors_batch defines it: the raw id users[b] is absent from train, its rows
+ * are the CSR offsets / items / ratings, and aug_b = train ++ those rows in order.  Queries are independent.
+ * Which users are reported.  Fitted user v is ENTERED by query b iff users[b] occurs in getNeighbors(aug_b, k, sim)(v) :596-617,
+ * the list evaluated on closures of v's own, so that v owns every pair.  For every accepted handle this equals, bit for bit,
+ * "users[b] occurs in the row that knncf_query_bystander_neighbors answers for (query b, v) with cap = k".
+ * Outputs.  Row b of out_users / out_sims / out_pos / out_displaced ([n_queries * cap], row stride cap) receives the first
+ * min(counts[b], cap) entered users of query b in the fit's user set order (dense order, the order allUsers iterates).  counts[b]
+ * is the number of entered users and may exceed cap.  Cells past the written ones are untouched.  With cap == 0 the four arrays
+ * may be null: a count-only call.  Per entered user v:
+ *   out_users      the raw id of v
+ *   out_sims       S(v, q) as it stands in v's list — the cell knncf_query_bystander_neighbors writes, the bits of a +-0.0
+ *                  included.  Adjusted cosine: the left fold from 0.0 of pre(v, i) * pre(q, i) over the common items in dense-item
+ *                  order, multiply and add separate.  Jaccard: |I(v) & I(q)| / (|I(v)| + |I(q)| - |I(v) & I(q)|), |I(q)| with q's
+ *                  items unknown to train.
+ *   out_pos        the 0-based position of q in v's list on aug_b
+ *   out_displaced  the raw id that is in getNeighbors(train, k, sim)(v) and no longer in the list on aug_b: the last entry of a
+ *                  full list; -1 when the list grew (k >= num_users, where every fitted user is entered)
+ * Place rule.  An entry (x, s_x) of v's stored list goes before q iff its order key is smaller (similarity descending, -0.0 with
+ * +0.0), or the keys are equal and x comes before q in the set order of aug's users (q's rank: the lower bound of its trie key
+ * over the fit's user keys).  q is entered iff fewer than take = min(k, num_users) entries go before it.  A fitted user with a
+ * negative mean is reported like any other: getNeighbors does not look at the mean.
+ * Refusals of the handle: those of knncf_query_neighbors_batch — KNNCF_E_STATE before a fit; KNNCF_E_UNSUPPORTED for
+ * KNNCF_SIM_ONE, a shard handle, fewer than 5 train users; KNNCF_E_INVALID for null pointers, n_queries < 0, cap < 0, bad CSR
+ * offsets; n_queries == 0 is KNNCF_OK and touches nothing — and one more: KNNCF_E_UNSUPPORTED on a KNNCF_SIM_COSINE handle whose
+ * train set has a user with 4 or fewer ratings (there a pair's summation order depends on who owns it, SURVEY N6, and the stored
+ * lists are not the fresh-closure lists).  Jaccard handles are accepted with such users: a ratio of counts has no order.
+ * Per-query statuses: exactly those of knncf_query_neighbors_batch (the user occurs in train or the query is empty, a duplicate
+ * item, a non-finite deviation, a negative mean, more than 65536 ratings).  A failed query gets counts[b] = 0, its rows are
+ * untouched, and it does not disturb the others; knncf_last_error names the first failed query.  The single form is the batch of
+ * one and returns the query's status; it has set *count = 0 first, once the argument checks pass.
+ * Handle state.  NOT read-only.  Let M be the train users whose neighbourhood the handle has not built, in ascending raw id.
+ * When the call passes its handle-level checks, n_queries > 0 and M is not empty, it first builds them in ONE batch and LEAVES
+ * THE HANDLE IN THE STATE THAT knncf_neighbors_batch OVER M LEAVES IT IN: the same lists, the same build numbers (call, position
+ * in M), the same knncf_neighbors_save file — whether or not any query is answerable.  With M empty the call touches nothing.
+ * knncf_get_timings: the build is charged as knncf_neighbors_batch charges it, the rest as the fold-in calls charge theirs.
+ * Chunks.  C of "Batched fold-in queries", one slot per query.  The entered-list scratch (20 bytes * min(cap, num_users) + 4 per
+ * slot, at most 20 bytes * num_users) is allocated beside the budget, as the gathered ratings are.  The results do not depend on
+ * C, and a repeated call of the same shape allocates no device memory.
+ * OUT OF SCOPE: newcomers that are in the fit (update and revise queries); KNNCF_PRED_PERSONALIZED; cosine fits with users of 4
+ * or fewer ratings; an ordering by similarity; device-pointer forms; shard handles and knncf_group_*; the command-line tool. */
+int knncf_query_entered(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
+                        int32_t cap, int32_t* out_users, double* out_sims, int32_t* out_pos, int32_t* out_displaced,
+                        int32_t* count);
+int knncf_query_entered_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                              const double* ratings, int64_t n_queries, int32_t cap, int32_t* out_users, double* out_sims,
+                              int32_t* out_pos, int32_t* out_displaced, int32_t* counts, int32_t* statuses);
 
 /* ---- batch ---------------------------------------------------------------- */
 int knncf_predict_batch(knncf_handle* h, int predictor, const int32_t* users,

@@ -230,12 +230,8 @@ int32_t dense_item(knncf_handle* h, int32_t raw) {
     return dense_lookup(h->h_ikeys.data(), h->tr.I, raw);
 }
 
-// A neighbour query that builds a list numbers that build on the queried shard only (the other shards never see the call).
-// With a <= 4-rating user in train the owner rule of rerank.hip (pair_sim: seq_v < seq_u) reads those numbers on every shard,
-// so such a query would let the shards disagree on a pair's summation order (SURVEY N6): refused.  The mae / predict path
-// numbers every user on every shard (ensure_neighbors_for_rows) and stays open.
-void require_shard_numbering(knncf_handle* h) {
-    if (h->cfg.shard_count == 1) return;
+// the train set has a user with <= 4 ratings: looked up once per fit
+bool has_short_rows(knncf_handle* h) {
     if (h->short_rows < 0) {
         Train& tr = h->tr;
         std::vector<int64_t> ptr((size_t)tr.U + 1);
@@ -245,7 +241,16 @@ void require_shard_numbering(knncf_handle* h) {
         for (int32_t u = 0; u < tr.U; ++u)
             if (ptr[u + 1] - ptr[u] <= 4) { h->short_rows = 1; break; }
     }
-    KN_REQUIRE(h->short_rows == 0, KNNCF_E_UNSUPPORTED,
+    return h->short_rows == 1;
+}
+
+// A neighbour query that builds a list numbers that build on the queried shard only (the other shards never see the call).
+// With a <= 4-rating user in train the owner rule of rerank.hip (pair_sim: seq_v < seq_u) reads those numbers on every shard,
+// so such a query would let the shards disagree on a pair's summation order (SURVEY N6): refused.  The mae / predict path
+// numbers every user on every shard (ensure_neighbors_for_rows) and stays open.
+void require_shard_numbering(knncf_handle* h) {
+    if (h->cfg.shard_count == 1) return;
+    KN_REQUIRE(!has_short_rows(h), KNNCF_E_UNSUPPORTED,
                "neighbours: on a shard handle whose train set has a user with <= 4 ratings, a neighbourhood that knncf_mae / "
                "knncf_predict_batch has not built yet cannot be built by a query (its build number would exist on this shard only)");
 }
@@ -1054,7 +1059,8 @@ constexpr int64_t QUERY_MAX_RATINGS = 65536;
 // (knncf_*_recommend_explain*): no requested rows, so neither explains() nor wants_rows()
 // QB_BY_NEIGHBORS / QB_BY_PREDICT: bystander queries (knncf_query_bystander_*) — the rows of a query name fitted users, and the
 // chunk loop is run_bystander_chunks
-enum QueryBatchMode { QB_NEIGHBORS, QB_PREDICT, QB_RECOMMEND, QB_EXPLAIN, QB_EXPLAIN_ALL, QB_RECOMMEND_EXPLAIN, QB_BY_NEIGHBORS, QB_BY_PREDICT };
+// QB_ENTERED: entered queries (knncf_query_entered*) — no rows; the chunk loop is run_entered_chunks
+enum QueryBatchMode { QB_NEIGHBORS, QB_PREDICT, QB_RECOMMEND, QB_EXPLAIN, QB_EXPLAIN_ALL, QB_RECOMMEND_EXPLAIN, QB_BY_NEIGHBORS, QB_BY_PREDICT, QB_ENTERED };
 bool bystanders(QueryBatchMode mode) { return mode == QB_BY_NEIGHBORS || mode == QB_BY_PREDICT; }
 bool explains(QueryBatchMode mode) { return mode == QB_EXPLAIN || mode == QB_EXPLAIN_ALL; }
 bool recommends(QueryBatchMode mode) { return mode == QB_RECOMMEND || mode == QB_RECOMMEND_EXPLAIN; }
@@ -1155,6 +1161,8 @@ struct QueryCall {
     int32_t* counts;                 // QB_NEIGHBORS, QB_RECOMMEND*: [B]
     int32_t* statuses;               // [B]
     ExplainCells ex;                 // explain modes: pred_offsets[B] rows; QB_RECOMMEND_EXPLAIN: B * n rows, row b * n + j (pred null)
+    int32_t* out_pos;                // QB_ENTERED: [B * cap] beside out_i (users) and out_d (sims), width = cap
+    int32_t* out_displaced;          // QB_ENTERED: [B * cap]
     int32_t user;                    // single forms only, from here on
     int64_t n_ratings, n_removed, m;
 };
@@ -1458,6 +1466,7 @@ QueryFailure run_query_chunks(knncf_handle* h, const QueryCall& q, int64_t chunk
             case QB_RECOMMEND_EXPLAIN: answer_recommend_explain(h, q, cs, ex_rows); break;
             case QB_BY_NEIGHBORS:
             case QB_BY_PREDICT: break;  // (run_bystander_chunks answers these)
+            case QB_ENTERED: break;     // (run_entered_chunks)
         }
     }
     return cs.first;
@@ -2199,6 +2208,120 @@ static void do_neighbors_batch(knncf_handle* h, const int32_t* users, int64_t n,
 
 int knncf_neighbors_batch(knncf_handle* h, const int32_t* users, int64_t n, int32_t cap, int32_t* ids, double* sims, int32_t* counts) {
     return guarded(h, [&] { do_neighbors_batch(h, users, n, cap, ids, sims, counts); });
+}
+
+// ---- entered queries: the fitted users whose neighbour lists a newcomer joins (entered.hip; knncf.h "Entered queries") --------
+// A query is a fold-in query (pack_chunk admits it, settle_statuses gives it its status), one slot each.  The place rule reads
+// the handle's stored lists, so the call first builds the lists that are missing: M = the train users without one in ascending
+// raw id, in ONE batch numbered (call, position in M) — the state knncf_neighbors_batch over M leaves.
+static void build_unbuilt_neighbors(knncf_handle* h) {
+    Train& tr = h->tr;
+    if (tr.U < 2 || h->nt.kcap <= 0) return;
+    load_host_ids(h);
+    std::vector<int64_t> seq((size_t)tr.U);
+    KN_HIP(hipMemcpyAsync(seq.data(), h->nt.seq.p, seq.size() * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    KN_HIP(hipStreamSynchronize(h->stream));
+    std::vector<int32_t> M;
+    for (int32_t u = 0; u < tr.U; ++u)
+        if (seq[u] < 0) M.push_back(u);
+    if (M.empty()) return;
+    std::sort(M.begin(), M.end(), [&](int32_t a, int32_t b) { return h->h_uid[a] < h->h_uid[b]; });
+    build_missing_neighbors(h, M);
+}
+
+// The validated queries of q in chunks of `chunk` slots: statuses[b], counts[b] and, where the status is KNNCF_OK, the first
+// min(counts[b], cap) entered users of query b in row b of the four output arrays.  One copy back per chunk.
+static QueryFailure run_entered_chunks(knncf_handle* h, const QueryCall& q, int64_t chunk) {
+    h->prep.join_commit(h->stream);
+    load_host_ids(h);
+    QueryBatchScratch& bs = h->query_batch;
+    hipStream_t st = h->stream;
+    ChunkState cs;
+    cs.take = std::max(0, std::min(h->cfg.k, h->tr.U));
+    const int32_t width = std::min(q.width, h->tr.U);
+    std::vector<int32_t> qrank;
+    for (int64_t c0 = 0; c0 < q.B; c0 += chunk) {
+        if (pack_chunk(h, q, cs, c0, std::min(q.B, c0 + chunk)) == 0) continue;
+        cs.info.assign((size_t)4 * cs.C, 0);
+        foldin_batch_neighbors(h->tr, bs, h->prep.sort, cs.C, cs.s_users.data(), cs.qo.data(), cs.s_items.data(), cs.s_ratings.data(),
+                               nullptr, nullptr, h->cfg.k, cs.info.data(), st, nullptr, nullptr, false);
+        if (settle_statuses(q, cs) == 0) continue;
+        if (cs.take == 0) {  // (k <= 0: no list has a cell)
+            for (const int32_t s : cs.good) q.counts[cs.slot_query[s]] = 0;
+            continue;
+        }
+        qrank.resize((size_t)cs.C);
+        for (int32_t s = 0; s < cs.C; ++s) {
+            const uint32_t qkey = int_trie_key(cs.s_users[s]);
+            qrank[s] = (int32_t)(std::lower_bound(h->h_ukeys.begin(), h->h_ukeys.end(), qkey) - h->h_ukeys.begin());
+        }
+        entered_chunk(h->tr, h->nt, bs, cs.C, cs.take, width, cs.qo.data(), qrank.data(), st);
+        const size_t bytes = entered_pack_bytes(cs.C, width);
+        cs.h_vals.resize((bytes + 7) / 8);
+        KN_HIP(hipMemcpyAsync(cs.h_vals.data(), bs.en_pack.p, bytes, hipMemcpyDeviceToHost, st));
+        KN_HIP(hipStreamSynchronize(st));
+        const EnteredPack got = entered_pack(cs.h_vals.data(), cs.C, width);
+        for (const int32_t s : cs.good) {
+            const int64_t b = cs.slot_query[s];
+            const size_t at = (size_t)s * width, dst = (size_t)b * q.width;
+            const int64_t t = std::min<int64_t>(got.counts[s], width);
+            q.counts[b] = got.counts[s];
+            std::copy(got.users + at, got.users + at + t, q.out_i + dst);
+            std::copy(got.sims + at, got.sims + at + t, q.out_d + dst);
+            std::copy(got.pos + at, got.pos + at + t, q.out_pos + dst);
+            std::copy(got.displaced + at, got.displaced + at + t, q.out_displaced + dst);
+        }
+    }
+    return cs.first;
+}
+
+// the batch form, and the single form as a batch of one (single: the query's status is thrown as the call's)
+static void do_entered_batch(knncf_handle* h, const QueryCall& q, bool single) {
+    const char* what = single ? "query" : "query batch";
+    auto text = [&](const char* t) { return std::string(what) + ": " + t; };
+    require_fitted(h, false);
+    KN_REQUIRE(q.B >= 0, KNNCF_E_INVALID, text("n_queries < 0"));
+    KN_REQUIRE(q.width >= 0, KNNCF_E_INVALID, text("cap < 0"));
+    require_query_support(h, q.predictor, q.mode);
+    KN_REQUIRE(h->cfg.similarity != KNNCF_SIM_COSINE || !has_short_rows(h), KNNCF_E_UNSUPPORTED,
+               "query entered with the adjusted cosine: a user with <= 4 ratings makes the reference's summation order depend on its memo history pair by pair (SURVEY N6); the stored lists are not the fresh-closure lists");
+    if (q.B == 0) return;
+    KN_REQUIRE(q.users && q.offsets && q.statuses && q.counts, KNNCF_E_INVALID, text("null argument"));
+    require_offsets(q.offsets, q.B, "query batch: offsets[0] != 0", "query batch: offsets decrease");
+    KN_REQUIRE(q.offsets[q.B] < ((int64_t)1 << 31), KNNCF_E_INVALID, text("2^31 or more ratings in one call"));
+    KN_REQUIRE(q.offsets[q.B] == 0 || (q.items && q.ratings), KNNCF_E_INVALID, text("null ratings"));
+    KN_REQUIRE(q.width == 0 || (q.out_i && q.out_d && q.out_pos && q.out_displaced), KNNCF_E_INVALID, text("null output"));
+    build_unbuilt_neighbors(h);
+    const QueryFailure f = run_entered_chunks(h, q, query_batch_chunk(h, batch_budget(h)));
+    if (f.query < 0) return;
+    if (single) throw Error(q.statuses[0], std::string("query: ") + f.reason);
+    h->err = "query batch: query " + std::to_string(f.query) + ": " + f.reason;
+}
+
+int knncf_query_entered_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                              const double* ratings, int64_t n_queries, int32_t cap, int32_t* out_users, double* out_sims,
+                              int32_t* out_pos, int32_t* out_displaced, int32_t* counts, int32_t* statuses) {
+    return guarded(h, [&] {
+        do_entered_batch(h, {.family = QF_FOLD_IN, .mode = QB_ENTERED, .predictor = KNNCF_PRED_KNN, .users = users, .B = n_queries,
+                             .offsets = offsets, .items = items, .ratings = ratings, .width = cap, .out_i = out_users, .out_d = out_sims,
+                             .counts = counts, .statuses = statuses, .out_pos = out_pos, .out_displaced = out_displaced}, false);
+    });
+}
+
+int knncf_query_entered(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings, int32_t cap,
+                        int32_t* out_users, double* out_sims, int32_t* out_pos, int32_t* out_displaced, int32_t* count) {
+    return guarded(h, [&] {
+        require_fitted(h, false);
+        KN_REQUIRE(count && cap >= 0 && (cap == 0 || (out_users && out_sims && out_pos && out_displaced)), KNNCF_E_INVALID,
+                   "bad output arguments");
+        KN_REQUIRE(n_ratings > 0 && items && ratings, KNNCF_E_INVALID, "query: null ratings or n_ratings <= 0");
+        *count = 0;
+        const int64_t offsets[2] = {0, n_ratings};
+        int32_t status = KNNCF_OK;
+        do_entered_batch(h, {.family = QF_FOLD_IN, .mode = QB_ENTERED, .predictor = KNNCF_PRED_KNN, .users = &user, .B = 1,
+                             .offsets = offsets, .items = items, .ratings = ratings, .width = cap, .out_i = out_users, .out_d = out_sims,
+                             .counts = count, .statuses = &status, .out_pos = out_pos, .out_displaced = out_displaced}, true);
+    });
 }
 
 // users per chunk of knncf_recommend_batch: the rule of knncf.h ("Batched recommendations")

@@ -24,14 +24,6 @@ namespace knncf {
 
 static constexpr int TPB = 256;
 
-// the order key of a similarity in a neighbour list, as k_fallback_keys of neighbours.hip makes it: ascending key <=> descending
-// similarity, -0.0 with +0.0
-__device__ __forceinline__ uint64_t by_sim_key(double s) {
-    if (s == 0.0) s = 0.0;
-    const uint64_t b = (uint64_t)__double_as_longlong(s);
-    return ~((b >> 63) ? ~b : (b | 0x8000000000000000ull));
-}
-
 // One wave per bystander slot b (qslot[b] != b): S(v, q), v = the slot's fitted user and q = the newcomer of slot qslot[b].
 // The wave walks q's known items in dense-item order 64 at a time (rank r of q's bitmap -> given position -> dense item),
 // probes v's bitmap and folds pre_v * pre_q left in that order = v's trie order (v with > 4 ratings).  A v of <= 4 ratings

@@ -391,6 +391,8 @@ struct QueryBatchScratch {
     // newcomer's place in set order, S(v, q), and S(v, q) again where q entered v's list (else +0.0)
     DArr<int32_t> by_qslot, by_qrank;
     DArr<double> by_pair, by_in;
+    // entered queries (entered.hip): the answers of a chunk in ONE block (entered_pack), 20 * width + 4 bytes per slot
+    DArr<double> en_pack;
 };
 // A chunk of bystander queries (DESIGN.md "Bystander queries"): slot b is either a newcomer's own fold-in slot (h_qslot[b] == b,
 // h_self[b] == -1) or a bystander's — a fitted user with no additional row (h_self[b] >= 0) whose newcomer is slot h_qslot[b] of
@@ -467,6 +469,33 @@ void bystander_gather(const Train& tr, QueryBatchScratch& bs, int32_t C, int32_t
 // foldin_batch_pick for rows of bystander slots: an item that only the newcomer rates has its one term
 void bystander_pick(const Train& tr, QueryBatchScratch& bs, const int32_t* d_items, const int32_t* d_slot, int64_t m, double* d_out,
                     hipStream_t st);
+
+// ---- entered.hip: the fitted users whose neighbour lists a newcomer joins (knncf_query_entered*; DESIGN.md "Entered queries")
+// The answers of a chunk of C slots lie in one block, so that one copy brings them back: sims [C * width] as doubles, then
+// users, pos, displaced [C * width] and counts [C] as int32 — row s holds the first min(counts[s], width) entered users of slot s
+// in dense order.  The same layout over a device or a host address.
+struct EnteredPack {
+    double* sims;
+    int32_t* users;
+    int32_t* pos;
+    int32_t* displaced;
+    int32_t* counts;
+};
+inline size_t entered_pack_bytes(int32_t C, int32_t width) { return (size_t)C * ((size_t)width * 20 + 4); }
+inline EnteredPack entered_pack(double* base, int32_t C, int32_t width) {
+    const size_t cells = (size_t)C * (size_t)width;
+    EnteredPack o;
+    o.sims = base;
+    o.users = reinterpret_cast<int32_t*>(base + cells);
+    o.pos = o.users + cells; o.displaced = o.pos + cells; o.counts = o.displaced + cells;
+    return o;
+}
+// after foldin_batch_neighbors(topk = false) on a fold-in chunk of C slots, with every list of nt built and take = min(k, U) > 0:
+// the answers of the chunk into bs.en_pack (width = min(cap, U) cells per slot; h_qrank[b] = the train users in front of slot b's
+// newcomer in set order; h_qo as the chunk was given it).  Three or four launches, no round trip: the caller copies the block
+// back.
+void entered_chunk(const Train& tr, const NeighborTable& nt, QueryBatchScratch& bs, int32_t C, int32_t take, int32_t width,
+                   const int64_t* h_qo, const int32_t* h_qrank, hipStream_t st);
 
 // ---- reco_batch.hip: recommendations :651-674 for users of the fit (knncf_recommend, knncf_recommend_batch; DESIGN.md "Batched
 // recommendations") ----

@@ -1,4 +1,4 @@
-// qb_helpers.h — the device helpers that the query kernels of foldin.hip and bystander.hip share, each defined once.
+// qb_helpers.h — the device helpers that the query kernels of foldin.hip, bystander.hip and entered.hip share, each defined once.
 #pragma once
 
 #include <algorithm>
@@ -55,6 +55,14 @@ __device__ __forceinline__ int32_t qb_slot(const int64_t* __restrict__ qo, int32
 // neighbours a slot returns: (allUsers - u) :608 has U - 1 users for a user of the fit.  self == nullptr: fold-in queries.
 __device__ __forceinline__ int32_t qb_take(const int32_t* __restrict__ self, int32_t b, int32_t take, int32_t U) {
     return (self && self[b] >= 0) ? min(take, U - 1) : take;
+}
+
+// the order key of a similarity in a neighbour list, as k_fallback_keys of neighbours.hip makes it: ascending key <=> descending
+// similarity, -0.0 with +0.0
+__device__ __forceinline__ uint64_t by_sim_key(double s) {
+    if (s == 0.0) s = 0.0;
+    const uint64_t b = (uint64_t)__double_as_longlong(s);
+    return ~((b >> 63) ? ~b : (b | 0x8000000000000000ull));
 }
 
 }  // namespace knncf

@@ -134,6 +134,7 @@ EXPORTS = [
     "knncf_query_recommend_explain_batch", "knncf_update_recommend_explain_batch", "knncf_revise_recommend_explain_batch",
     "knncf_query_bystander_neighbors", "knncf_query_bystander_predict",
     "knncf_query_bystander_neighbors_batch", "knncf_query_bystander_predict_batch",
+    "knncf_query_entered", "knncf_query_entered_batch",
     "knncf_predict_batch",
     "knncf_predict_batch_device", "knncf_mae", "knncf_mae_device", "knncf_mae_sweep", "knncf_mae_sweep_device", "knncf_shard_view_get",
     "knncf_shard_commit", "knncf_get_timings", "knncf_reset_timings", "knncf_reset_neighbors",
@@ -252,6 +253,10 @@ def load_library():
                                                         _i32p, _f64p, _i32p, _i32p]
     L.knncf_query_bystander_predict_batch.argtypes = [C.c_void_p, C.c_int, _i32p, _i64p, _i32p, _f64p, C.c_int64, _i64p, _i32p, _i32p,
                                                       _f64p, _i32p]
+    # entered queries: the fold-in query, cap, then users / sims / positions / displaced and the count(s)
+    L.knncf_query_entered.argtypes = [C.c_void_p, C.c_int32, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p, _i32p, _i32p]
+    L.knncf_query_entered_batch.argtypes = [C.c_void_p, _i32p, _i64p, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p, _i32p,
+                                            _i32p, _i32p]
     # revise queries: the update argument lists with the removals in front of the additional rows
     for name, at, single in (("neighbors", 2, True), ("predict", 3, True), ("recommend", 3, True), ("explain", 3, True),
                              ("explain_personalized", 2, True), ("neighbors_batch", 2, False), ("predict_batch", 3, False),
@@ -1228,6 +1233,75 @@ class BystanderQueries:
         self._e._check(self._e._lib.knncf_query_bystander_predict_batch(
             self._e._h, PRED_KNN, *qargs, p(roff, _i64p), p(oth, _i32p), p(pi, _i32p), p(out, _f64p), p(st, _i32p)))
         return [out[roff[b]:roff[b + 1]].copy() for b in range(B)], st
+
+
+class EnteredQueries:
+    """Entered queries (knncf_query_entered*) on a fitted Engine: the FITTED users whose neighbour list the user of a fold-in
+    query joins, without a refit.  A query is (user, items, ratings) as Engine.neighbors_for takes it.  NOT read-only on the
+    engine's handle: a call first BUILDS THE NEIGHBOUR LISTS THAT ARE MISSING, all in one batch in ascending raw id, as
+    Engine.neighbors_batch over those users would.
+
+        users, sims, positions, displaced = EnteredQueries(engine).entered(944, items, ratings)"""
+
+    def __init__(self, engine):
+        self._e = engine
+
+    @staticmethod
+    def _cap(cap):
+        if cap is None:
+            return None
+        if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or cap < 0 or cap >= 2**31:
+            raise ValueError("cap must be a non-negative integer")
+        return int(cap)
+
+    def _call(self, qargs, B, cap):
+        """one knncf_query_entered_batch call: (users, sims, positions, displaced) [B, cap], counts, statuses"""
+        us = np.empty((B, cap), dtype=np.int32)
+        sims = np.empty((B, cap), dtype=np.float64)
+        pos = np.empty((B, cap), dtype=np.int32)
+        disp = np.empty((B, cap), dtype=np.int32)
+        counts = np.zeros(B, dtype=np.int32)
+        st = np.zeros(B, dtype=np.int32)
+        p = self._e._ptr
+        self._e._check(self._e._lib.knncf_query_entered_batch(
+            self._e._h, *qargs, cap, p(us.reshape(-1), _i32p), p(sims.reshape(-1), _f64p), p(pos.reshape(-1), _i32p),
+            p(disp.reshape(-1), _i32p), p(counts, _i32p), p(st, _i32p)))
+        return (us, sims, pos, disp), counts, st
+
+    def entered_batch(self, queries, cap=None):
+        """entered() of every (user, items, ratings) of `queries`: ([(users, sims, positions, displaced)] per query, statuses
+        int32 [B]); a failed query has empty arrays.  cap=None asks for the counts first, then for all entries.  Builds the
+        neighbour lists the handle has not built yet."""
+        qargs, keep = self._e._batch_args("query", queries)
+        B, cap = qargs[-1], self._cap(cap)
+        if cap is None:
+            _, counts, _ = self._call(qargs, B, 0)
+            cap = int(counts.max()) if B else 0
+        out, counts, st = self._call(qargs, B, cap)
+        return [tuple(a[b, :min(counts[b], cap)].copy() for a in out) for b in range(B)], st
+
+    def entered(self, user, items, ratings, cap=None):
+        """the fitted users v with `user` in getNeighbors(train ++ user's ratings, k, sim)(v), in the fit's set order:
+        (users, sims = S(v, user), positions of `user` in v's list, displaced = the raw id that leaves v's list or -1).
+        cap=None asks for the count first, then for all entries.  Builds the neighbour lists the handle has not built yet."""
+        q, it, rt = self._e._query_rows(user, items, ratings)
+        cap = self._cap(cap)
+        p = self._e._ptr
+
+        def call(cap):
+            us = np.empty(cap, dtype=np.int32)
+            sims = np.empty(cap, dtype=np.float64)
+            pos = np.empty(cap, dtype=np.int32)
+            disp = np.empty(cap, dtype=np.int32)
+            c = C.c_int32()
+            self._e._check(self._e._lib.knncf_query_entered(self._e._h, q, p(it, _i32p), p(rt, _f64p), len(it), cap, p(us, _i32p),
+                                                            p(sims, _f64p), p(pos, _i32p), p(disp, _i32p), C.byref(c)))
+            m = min(c.value, cap)
+            return (us[:m].copy(), sims[:m].copy(), pos[:m].copy(), disp[:m].copy()), c.value
+
+        if cap is None:
+            cap = call(0)[1]
+        return call(cap)[0]
 
 
 class Group:
