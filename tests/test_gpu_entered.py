@@ -277,8 +277,10 @@ def _scaled(synth, n_users):
 
 @pytest.mark.parametrize("n_users,k", [(255, 7), (256, 7), (257, 7), (255, 300), (256, 300), (257, 300), (257, 256), (257, 100)])
 def test_scan_block_edges(kn, synth, oracle, n_users, k):
-    """fits of 255, 256 and 257 users: the edges of the scan's per-thread ranges; k >= U enters everybody (counts of 255 .. 257,
-    across 64 and 256), k = U - 1 = 256 has full lists, k = 100 a count in between"""
+    """fits of 255, 256 and 257 users: 4 | 5 words of the entered-user bitmap that k_en_compact scans (not the scan's
+    per-thread edge: a thread owns more than one word only beyond 65 536 users; tests/test_gpu_query_edges.py covers that edge
+    through the shared block_exclusive_scan); k >= U enters everybody (counts of 255 .. 257, across 64 and 256), k = U - 1 = 256
+    has full lists, k = 100 a count in between"""
     train = _scaled(synth, n_users)
     c = bc.near_clone(synth, k=k, train=train)
     want = ec.expected_for(oracle, train, c.q, c.items, c.ratings, k, ec.COS)

@@ -17,6 +17,7 @@ import os
 import numpy as np
 import pytest
 
+from tests.query_edges import wide_train as _wide_train
 from tests.query_helpers import MAX_CHUNK, UNKNOWN_ITEM, _aug, _bits, _chunk, _same_pair, _workspace_for
 
 pytestmark = pytest.mark.gpu
@@ -171,21 +172,6 @@ def test_switches_of_the_similarity_pass(kn, syn100k, latency_script, chunk, cou
         queries[1] = (queries[1][0], queries[1][1][:3], queries[1][2][:3])  # a <= 4-rating slot beside long ones
         _batch_vs_singles(kn, e, queries, np.unique(train[1])[::11].astype(np.int32))
         e.close()
-
-
-def _wide_train(n_items, n_users=400):
-    """every item of 0 .. n_items-1 rated, so the dense item count is n_items exactly; (user, item) pairs distinct"""
-    items = np.arange(n_items, dtype=np.int64)
-    users = items % n_users
-    extra = np.arange(30_000, dtype=np.int64)
-    e_items = extra * 7
-    e_users = (e_items % n_users + 1 + extra % (n_users - 1)) % n_users
-    u = np.concatenate([users, e_users]).astype(np.int32) + 1
-    i = np.concatenate([items, e_items]).astype(np.int32)
-    rng = np.random.default_rng(19)
-    r = rng.integers(1, 11, len(u)).astype(np.float64) / 2
-    order = rng.permutation(len(u))
-    return u[order], i[order], r[order]
 
 
 @pytest.mark.parametrize("n_items", [262_144, 262_145 + 64])
