@@ -194,7 +194,9 @@ inline bool lds_bitmap_fits(int64_t words) { return words * 12 <= 48 * 1024 && !
 
 // (KNNCF_DEBUG_TRACE_DISPATCH: test hook — launch_predict (kNN kinds), launch_predict_sweep, launch_rerank and
 // launch_sort_neighbors write "knncf-dispatch <stage> <variant>" to stderr, one line per launch, so that a test can tell
-// which instantiation ran.  Unset: nothing is written.
+// which instantiation ran.  The streamed PERSONALIZED rows report how the plan cut the batch, host code only:
+// launch_sim_rows "sim_rows sim=<cosine|jaccard> users=<n> tiles=<t>" and launch_fold_rows "fold_rows rows=<n>", one line per
+// launch (a fold of no rows launches nothing and writes nothing).  Unset: nothing is written.
 // With the value "setup" the set-up stage reports as well, host code only (any other value leaves its lines out: the tests of
 // the launch stages assert their exact line sets, and every kNN prediction sorts its test rows): prep_fit one line per fit,
 //   "prep ids=<table|sorted> order=<segments|global> mid=<n> long=<n> uf=<0|1> uh=<0|1>"

@@ -204,6 +204,7 @@ void launch_sim_rows(const Train& tr, const PersonalRows& pr, const int32_t* d_u
     if (n_users <= 0) return;
     const int64_t grid = (int64_t)n_users * pr.tiles;
     KN_REQUIRE(grid < (1ll << 31), KNNCF_E_UNSUPPORTED, "PERSONALIZED: too many similarity rows in one block");
+    KN_TRACE_DISPATCH("sim_rows sim=%s users=%d tiles=%d", tr.jaccard ? "jaccard" : "cosine", (int)n_users, (int)pr.tiles);
     if (tr.jaccard)
         k_sim_rows<true><<<(int)grid, ROW_TPB, 0, st>>>(tr.u_ptr.p, tr.s_col.p, tr.s_pre.p, pr.tile.p, pr.tiles, tr.it_user.p,
                                                          pr.pi_pre.p, d_users, tr.U, d_S);
@@ -279,6 +280,7 @@ void launch_fold_rows(const Train& tr, const PersonalRows& pr, int64_t n_rows, c
                       const int32_t* d_di, const double* d_ratings, const int32_t* d_slot, const double* d_S, double* d_pred,
                       double* d_abs_err, uint8_t* d_owned, hipStream_t st) {
     if (n_rows <= 0) return;
+    KN_TRACE_DISPATCH("fold_rows rows=%lld", (long long)n_rows);
     k_fold_rows<<<nblocks(n_rows, FOLD_WAVES), FOLD_WAVES * 64, 0, st>>>(
         n_rows, d_order, d_du, d_di, d_ratings, d_slot, d_S, tr.U, tr.i_ptr.p, pr.pf_user.p, pr.pf_dev.p, tr.user_avg.p,
         tr.global_avg, d_pred, d_abs_err, d_owned);
