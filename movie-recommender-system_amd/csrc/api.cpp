@@ -327,7 +327,12 @@ int32_t choose_head(knncf_handle* h, int32_t rows_total, bool symmetric) {
         // round 3 with the overlapped GEMM and the 6-VALU drain: 0.0195 ms per dense column on the symmetric path = 2.7e15
         // full-square flops per second, 4.2e-13 s per tail pair product — the optimum stays at 384 / 256): full-square
         // flops per second bought by one more dense column — the symmetric launch computes half of them — and tail pair
-        // products per second through k_tail_select
+        // products per second through k_tail_select.  Re-measured with the re-scheduled k-loop of k_gemm_nt_ov
+        // (profiles/gemm_kloop_syn25m_1gpu.json).  Symmetric, head sweep 256 .. 768 of the step: the launch is 0.7 ms shorter
+        // at every width, a column costs 0.0164 ms on average and 0.0189 ms between 384 and 448 (2.8e15 .. 3.2e15; 2.6e15 by
+        // gemm_bench on a slower device), the tail gives back 0.0178 ms there — 384 stays the fastest head by 0.16 ms per
+        // step.  Row blocks of 16 384, gemm_bench K = 128 .. 768: 1.3e15 .. 1.4e15 (the parent 1.28e15 in the same job), two
+        // sweeps that differ by up to 0.35 ms per launch; no step sweep was run on that path.  Both rates stay as they are.
         const double RATE_DENSE = symmetric ? 2.8e15 : 1.2e15;
         const double RATE_SPARSE = 2.3e12;
         const double frac = (double)rows_total / (double)tr.U;

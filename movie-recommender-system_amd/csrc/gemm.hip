@@ -15,7 +15,9 @@
 // ring; the LDS image is lane-linear as the DMA requires, with the bank swizzle applied on the
 // SOURCE address (16-B chunk c of row r sits in slot c ^ ((r >> 1) & 7), conflict-free for
 // ds_read_b128: the 16 lanes of a read group hit 16 distinct slots of the 256-B bank row).
-// Tile t+1 stays in flight across the barrier behind a counted vmcnt.
+// k_gemm_nt_bf16: tile t+1 stays in flight across the barrier behind a counted vmcnt, two barriers per k-step.
+// k_gemm_nt_ov: one barrier per k-step, placed in its last k-substep; the k-tile after the next is requested behind it,
+// the fragment reads are asm with counted lgkmcnt waits, a whole k-substep ahead of the MFMAs that use them.
 #include <algorithm>
 #include <type_traits>
 #include <vector>
@@ -442,9 +444,11 @@ __device__ __forceinline__ void stage_tile_u(const bf16_t* g_uniform, uint32_t l
 //                  back as 16-byte pieces, 4 global stores of 8 rows x 128 contiguous bytes;
 //   unit 2 i + 1 : the same block MIRRORED (symmetric launches, off-diagonal tiles): 32 ds_write_b16 into the 64 x 32
 //                  transposed image, 4 global stores of 16 rows x 64 contiguous bytes, into tile (tn, tm).
-// The stores are spread evenly over the k-steps and the counted waits allow the stores of the previous k-step to stay
-// in flight (vmcnt(loads of the next stage + stores issued since)): the launch takes max(MFMA, stores) per tile instead
-// of their sum.  LDS: the 128 KiB operand ring + 8 x 4 KiB = all 160 KiB.  The stored values are k_gemm_nt_bf16's fp32
+// The stores are spread over the k-steps; a wave waits for its vector-memory operations once per k-step, in front of
+// the k-step's one barrier (vmcnt(0): the k-tile it waits for is the youngest load, and the stores in front of it were
+// issued most of a k-step earlier — measured against counted waits that let the stores pass, K = 384: 13.05 ms per launch
+// against 13.21 with a three-way choice of the immediate and 13.58 with the nine-way one; the scalar compare-and-branch
+// ladder in front of every barrier cost more than the stores it let through).  LDS: the 128 KiB operand ring + 8 x 4 KiB = all 160 KiB.  The stored values are k_gemm_nt_bf16's fp32
 // sums (same MFMA order) clamped to [-clamp_hi, clamp_hi] and rounded to the nearest even fp16.
 // The global stores are non-temporal ("nt"; measured at H = 384: 14.3 ms per launch, plain stores and sc1 17.9 ms).
 template <bool F16, bool SYM, bool SPREAD>
@@ -453,8 +457,6 @@ k_gemm_nt_ov(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, _Float1
              int k_tiles, int64_t lda, int64_t ldb, int64_t ldc, const uint32_t* __restrict__ tile_list, int n_listed, float clamp_hi) {
     constexpr int WM = 4, WN = 2, WAVES_N = 4, WAVES = 8, TB = 256;
     constexpr int TILE_BYTES = TileGeom<TB>::TILE_BYTES, STAGE_BYTES = TileGeom<TB>::STAGE_BYTES;
-    constexpr int LOADS_PER_STAGE = 2 * (TB / 8 / WAVES);  // 8 LDS-DMA instructions per wave per stage
-    static_assert(LOADS_PER_STAGE == 8, "the counted waits below assume 8 LDS-DMA instructions per wave per stage");
     extern __shared__ __attribute__((aligned(1024))) char lds[];
     char* const ring = lds;
 
@@ -509,7 +511,7 @@ k_gemm_nt_ov(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, _Float1
             for (int h = 0; h < 8; ++h) P[i][j][h] = 0u;
     // Register plan (2 waves per SIMD: 256 registers each, one unified file on gfx950): the 128 accumulators of the running
     // tile, P, one fragment set and the addressing.  hipcc allocates all of them as architectural VGPRs (the code object
-    // reports 220 - 227 VGPRs and agpr_count 0); nothing spills.
+    // reports 234 - 244 VGPRs and agpr_count 0); nothing spills.
     int ptm = 0, ptn = 0;
     int unit = 1000;  // next unit of the previous tile to drain (>= UNITS: none left)
 
@@ -622,41 +624,69 @@ k_gemm_nt_ov(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, _Float1
 #endif
     int tm, tn;
     tile_of(t, tm, tn);
-    const bf16_t* Ag = A + (int64_t)KN_OV_ROW(tm) * TB * lda;
-    const bf16_t* Bg = B + (int64_t)KN_OV_ROW(tn) * TB * ldb;
-    stage_tile_u<TB, WAVES>(Ag, lda2, ring, uwave, voff_a);
-    stage_tile_u<TB, WAVES>(Bg, ldb2, ring + TILE_BYTES, uwave, voff_b);
     int slot = 0;
-    // Counted waits by bookkeeping instead of by position: `ops` counts every vector-memory operation this wave has issued
-    // (8 LDS-DMAs per operand stage, 4 stores per unit), mark[s] is its value right after the stage into slot s was issued —
-    // so when k-tile `slot` is needed, exactly ops - mark[slot] younger operations may still be in flight (vmcnt retires
-    // in order: loads, LDS-DMAs and stores together).  A smaller immediate only waits longer; the immediates are multiples
-    // of 4 up to 32.
-    uint32_t ops = LOADS_PER_STAGE, mark[2] = {LOADS_PER_STAGE, 0u};
-    auto wait_for = [&](int s) {
-        const uint32_t allow = ops - mark[s];
-        if (allow >= 32) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
-        else if (allow >= 28) asm volatile("s_waitcnt vmcnt(28)" ::: "memory");
-        else if (allow >= 24) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-        else if (allow >= 20) asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
-        else if (allow >= 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-        else if (allow >= 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-        else if (allow >= 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else if (allow >= 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // The k-tiles of this workgroup's tiles are ONE stream through the two slots, and the request cursor runs two stream
+    // elements ahead of the k-step being computed, across tile ends (also with one k-tile per tile, where it is two TILES ahead).
+    int s_t = t, s_kt = 0;
+    const bf16_t* s_A = A + (int64_t)KN_OV_ROW(tm) * TB * lda;
+    const bf16_t* s_B = B + (int64_t)KN_OV_ROW(tn) * TB * ldb;
+    auto stage_next = [&](int s) {
+        if (s_t >= xcd_end) return;
+        char* dst = ring + s * STAGE_BYTES;
+        stage_tile_u<TB, WAVES>(s_A + (int64_t)s_kt * BK, lda2, dst, uwave, voff_a);
+        stage_tile_u<TB, WAVES>(s_B + (int64_t)s_kt * BK, ldb2, dst + TILE_BYTES, uwave, voff_b);
+        if (++s_kt < k_tiles) return;
+        s_kt = 0;
+        s_t += stride;
+        if (s_t >= xcd_end) return;
+        int sm, sn;
+        tile_of(s_t, sm, sn);
+        s_A = A + (int64_t)KN_OV_ROW(sm) * TB * lda;
+        s_B = B + (int64_t)KN_OV_ROW(sn) * TB * ldb;
     };
-    bool pre_issued = false;  // the second k-tile of this tile was requested at the end of the previous one
     // Where the four deferred units go: with six or more k-steps one per k-step from the third on — the 16 stores of the
     // tile's end then have two k-steps of their own to drain — otherwise two per k-step from the first.
     constexpr bool spread = SPREAD;  // (the launcher: k_tiles >= 6)
+
+    stage_next(0);
+    stage_next(1);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();  // the first k-tile is in LDS, everyone's share of it
+    asm volatile("" ::: "memory");
+    // the younger half of the workgroup loses every arbitration against the older one: one static priority for it
+    if (uwave >= WAVES / 2) __builtin_amdgcn_s_setprio(1);
+
+    // The fragments of one k-substep: four A fragments (one per row block) and a B pair — and the B pair of the next
+    // k-substep (even and odd k-substeps own one pair each: no value is ever renamed while its read is in flight).  They
+    // live ACROSS k-steps: the last k-substep of a k-tile refills them from the next k-tile of the same tile.
+    //
+    // The fragment reads and their waits are asm statements.  hipcc waits for every LDS read of this kernel with
+    // lgkmcnt(0) right in front of the first MFMA that uses it, however far ahead the source requests it (while an LDS-DMA
+    // is in flight — here always — it does not count LDS operations), which made the loop a chain of exposed LDS latencies:
+    // four reads, their latency, four MFMAs.  LDS reads return in order, so a counted wait names exactly the reads that may
+    // still be in flight; each wait statement passes the fragments it covers through ("+v"), so that no MFMA can be
+    // scheduled in front of it.  Addresses: row * 128 + (chunk ^ ((row >> 1) & 7)) * 16 as in read_frag — the row blocks of a
+    // wave are multiples of 32 rows, so the swizzle is the lane's alone and a k-substep's chunk pair 2 ks | fhalf enters as
+    // an XOR of ks * 32; the row block rides in the immediate offset.
+    // The statements pin the ORDER of reads, waits and MFMAs, not the register allocation: between a read and its wait the
+    // compiler still believes the fragment is there, and a copy of it (a v_mov, a spill) would move stale data on most waves
+    // without any error.  After every change to this kernel, compile with -save-temps and check in the listing of each
+    // instantiation that nothing but MFMAs, reads, waits and address arithmetic stands between a ds_read_b128 and the
+    // s_waitcnt that covers it, and that -Rpass-analysis=kernel-resource-usage still reports no scratch.
+    const uint32_t ring_a = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)ring;
+    const uint32_t fr_lane = (uint32_t)frow * 128u + (uint32_t)((fhalf ^ ((frow >> 1) & 7)) * 16);
+    const uint32_t fr_a = ring_a + (uint32_t)wr * (WM * 32 * 128) + fr_lane;                  // + slot * STAGE_BYTES, ^ ks * 32
+    const uint32_t fr_b = ring_a + TILE_BYTES + (uint32_t)wc * (WN * 32 * 128) + fr_lane;
+    bf16x8 a[WM], bq[2][WN];
+#define KN_FRAG_READ(f, addr, off) asm volatile("ds_read_b128 %0, %1 offset:" #off : "=v"(f) : "v"(addr) : "memory")
+#define KN_FRAG_WAIT1(n, x) asm volatile("s_waitcnt lgkmcnt(" #n ")" : "+v"(x) : : "memory")
+#define KN_FRAG_WAIT3(n, x, y, z) asm volatile("s_waitcnt lgkmcnt(" #n ")" : "+v"(x), "+v"(y), "+v"(z) : : "memory")
 
     for (;;) {
         const int t_next = t + stride;
         const bool more = t_next < xcd_end;
         int tm2 = 0, tn2 = 0;
         if (more) tile_of(t_next, tm2, tn2);
-        const bf16_t* Ag2 = A + (int64_t)KN_OV_ROW(tm2) * TB * lda;
-        const bf16_t* Bg2 = B + (int64_t)KN_OV_ROW(tn2) * TB * ldb;
 
         f32x16 acc[WM][WN];
 #pragma unroll
@@ -665,86 +695,114 @@ k_gemm_nt_ov(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, _Float1
             for (int j = 0; j < WN; ++j)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-        for (int kt = 0; kt < k_tiles; ++kt) {
-            char* cur = ring + slot * STAGE_BYTES;
-            char* nxt = ring + (slot ^ 1) * STAGE_BYTES;
-            const bool in_tile = kt + 1 < k_tiles;
-            if (kt == 0 && pre_issued) {
-                pre_issued = false;  // (k-tile 1 is already on its way into `nxt`)
-            } else if (in_tile) {
-                stage_tile_u<TB, WAVES>(Ag + (int64_t)(kt + 1) * BK, lda2, nxt, uwave, voff_a);
-                stage_tile_u<TB, WAVES>(Bg + (int64_t)(kt + 1) * BK, ldb2, nxt + TILE_BYTES, uwave, voff_b);
-                ops += LOADS_PER_STAGE;
-                mark[slot ^ 1] = ops;
-            } else if (more) {
-                stage_tile_u<TB, WAVES>(Ag2, lda2, nxt, uwave, voff_a);
-                stage_tile_u<TB, WAVES>(Bg2, ldb2, nxt + TILE_BYTES, uwave, voff_b);
-                ops += LOADS_PER_STAGE;
-                mark[slot ^ 1] = ops;
-            }
-            wait_for(slot);
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            // Fragments: one A fragment ahead of the MFMA pair that uses the current one, the B pair of the next k-substep
-            // behind the last A fragment of this one — 24 registers.
-            {
-                const char* ca = cur;
-                const char* cb = cur + TILE_BYTES;
-                const int arow = wr * (WM * 32) + frow, brow = wc * (WN * 32) + frow;
-                bf16x8 b0 = read_frag(cb, brow, fhalf), b1 = read_frag(cb, brow + 32, fhalf);
-                bf16x8 a_cur = read_frag(ca, arow, fhalf);
-                const bool unit_step = !spread || kt >= 2;
-#pragma unroll
-                for (int ks = 0; ks < BK / 16; ++ks) {
-                    bf16x8 b0n = b0, b1n = b1;
-#pragma unroll
-                    for (int i = 0; i < WM; ++i) {
-                        bf16x8 a_next = a_cur;
-                        if (i + 1 < WM) {
-                            a_next = read_frag(ca, arow + (i + 1) * 32, ks * 2 + fhalf);
-                        } else if (ks + 1 < BK / 16) {
-                            a_next = read_frag(ca, arow, (ks + 1) * 2 + fhalf);
-                            b0n = read_frag(cb, brow, (ks + 1) * 2 + fhalf);
-                            b1n = read_frag(cb, brow + 32, (ks + 1) * 2 + fhalf);
-                        }
-#ifndef KNNCF_OV_ABL_NOMFMA  /* timing-only ablation (results are wrong): no MFMA work */
-                        acc[i][0] = mfma<F16>(b0, a_cur, acc[i][0]);
-                        acc[i][1] = mfma<F16>(b1, a_cur, acc[i][1]);
-#else
-                        acc[i][0][0] += (float)a_cur[0] + (float)b0[0];
-                        acc[i][1][0] += (float)a_cur[1] + (float)b1[0];
+#ifdef KNNCF_OV_ABL_NOMFMA
+        float abl_sink = 0.f;
 #endif
-                        a_cur = a_next;
-                    }
-                    b0 = b0n;
-                    b1 = b1n;
-                    // units of the previous tile, behind the first (and, when they come two to a k-step, the third) MFMA
-                    // group; the next k-substep's fragments are already requested
-                    if ((ks == 0 || (ks == 2 && !spread)) && unit_step && unit < UNITS) {
-                        ops += (uint32_t)drain_unit(unit);
-                        ++unit;
-                    }
-                }
+
+        // One k-step = four k-substeps of four MFMA pairs, ONE workgroup barrier.  A fragment is requested four MFMA pairs
+        // (a whole k-substep: 256 cycles of this wave's MFMAs plus the partner wave's) ahead of the pair that uses it — a[i]
+        // right behind the pair that read it last, the B pair at the start of the k-substep before.  In a k-substep that
+        // requests a B pair, five younger reads stand behind the fragment a pair waits for (the rest of the A fragments,
+        // old or new, and the B pair): lgkmcnt(5).  The barrier stands in the LAST k-substep, behind its second pair: in
+        // front of it every wave has waited for its own reads of this k-tile (lgkmcnt(0): the two youngest are two pairs
+        // old) and for its own LDS-DMAs of the next one (vmcnt(0)), so behind it the next k-tile is complete and visible and
+        // this one's slot is free: the k-tile after the next is requested into it, and the fragments of the next k-tile's
+        // first k-substep are read under the last two pairs.  Only a tile's first k-step reads its first fragments with
+        // nothing to cover them.
+        for (int kt = 0; kt < k_tiles; ++kt) {
+            const uint32_t ca = fr_a + (uint32_t)slot * STAGE_BYTES, cb = fr_b + (uint32_t)slot * STAGE_BYTES;
+            const uint32_t na = fr_a + (uint32_t)(slot ^ 1) * STAGE_BYTES, nb = fr_b + (uint32_t)(slot ^ 1) * STAGE_BYTES;
+            const bool last = kt + 1 == k_tiles;
+            const bool unit_step = !spread || kt >= 2;
+            if (kt == 0) {
+                KN_FRAG_READ(bq[0][0], cb, 0);
+                KN_FRAG_READ(bq[0][1], cb, 4096);
+                KN_FRAG_READ(a[0], ca, 0);
+                KN_FRAG_READ(a[1], ca, 4096);
+                KN_FRAG_READ(a[2], ca, 8192);
+                KN_FRAG_READ(a[3], ca, 12288);
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();  // everyone is done reading `cur` before it is restaged
-            asm volatile("" ::: "memory");
+            auto pair = [&](auto KS_, auto I_) {
+                constexpr int ks = decltype(KS_)::value, i = decltype(I_)::value;
+#ifndef KNNCF_OV_ABL_NOMFMA  /* timing-only ablation (results are wrong): no MFMA work */
+                acc[i][0] = mfma<F16>(bq[ks & 1][0], a[i], acc[i][0]);
+                acc[i][1] = mfma<F16>(bq[ks & 1][1], a[i], acc[i][1]);
+#else
+                (void)i;  // (the fragments are still waited for and read; one scalar per wave-lane instead of the accumulators)
+                abl_sink += (float)a[i][0] + (float)bq[ks & 1][0][0] + (float)bq[ks & 1][1][0];
+#endif
+            };
+            // k-substeps 0, 1, 2: request the B pair of the next one, then four pairs, each followed by its next A fragment
+            auto substep = [&](auto KS_) {
+                constexpr int ks = decltype(KS_)::value;
+                const uint32_t xa = ca ^ (uint32_t)((ks + 1) * 32), xb = cb ^ (uint32_t)((ks + 1) * 32);
+                KN_FRAG_READ(bq[(ks + 1) & 1][0], xb, 0);
+                KN_FRAG_READ(bq[(ks + 1) & 1][1], xb, 4096);
+                __builtin_amdgcn_sched_barrier(0);  // (pins the MFMAs between the statements they are written between)
+                KN_FRAG_WAIT3(5, bq[ks & 1][0], bq[ks & 1][1], a[0]);
+                pair(KS_, std::integral_constant<int, 0>{});
+                KN_FRAG_READ(a[0], xa, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                KN_FRAG_WAIT1(5, a[1]);
+                pair(KS_, std::integral_constant<int, 1>{});
+                KN_FRAG_READ(a[1], xa, 4096);
+                __builtin_amdgcn_sched_barrier(0);
+                KN_FRAG_WAIT1(5, a[2]);
+                pair(KS_, std::integral_constant<int, 2>{});
+                KN_FRAG_READ(a[2], xa, 8192);
+                __builtin_amdgcn_sched_barrier(0);
+                KN_FRAG_WAIT1(5, a[3]);
+                pair(KS_, std::integral_constant<int, 3>{});
+                KN_FRAG_READ(a[3], xa, 12288);
+                __builtin_amdgcn_sched_barrier(0);
+                // a unit of the previous tile, behind the first (and, when they come two to a k-step, the third) MFMA
+                // group; the next k-substep's fragments are already requested (the unit ends with lgkmcnt(0))
+                if ((ks == 0 || (ks == 2 && !spread)) && unit_step && unit < UNITS) {
+                    (void)drain_unit(unit);
+                    ++unit;
+                }
+            };
+            substep(std::integral_constant<int, 0>{});
+            substep(std::integral_constant<int, 1>{});
+            substep(std::integral_constant<int, 2>{});
+            {   // the last k-substep (its B pair and A fragments are the only reads in flight: 3 and 2 younger ones)
+                typedef std::integral_constant<int, 3> K3;
+                static_assert(BK / 16 == 4 && WM == 4 && WN == 2, "the k-step is written out for four k-substeps of four pairs");
+                KN_FRAG_WAIT3(3, bq[1][0], bq[1][1], a[0]);
+                pair(K3{}, std::integral_constant<int, 0>{});
+                __builtin_amdgcn_sched_barrier(0);
+                KN_FRAG_WAIT1(2, a[1]);
+                pair(K3{}, std::integral_constant<int, 1>{});
+                __builtin_amdgcn_sched_barrier(0);
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[2]), "+v"(a[3]) : : "memory");  // this wave is done reading the k-tile
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                             // and its share of the next one has landed
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+                stage_next(slot);
+                if (!last) {
+                    KN_FRAG_READ(bq[0][0], nb, 0);
+                    KN_FRAG_READ(bq[0][1], nb, 4096);
+                    KN_FRAG_READ(a[0], na, 0);
+                    KN_FRAG_READ(a[1], na, 4096);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                pair(K3{}, std::integral_constant<int, 2>{});
+                if (!last) KN_FRAG_READ(a[2], na, 8192);
+                __builtin_amdgcn_sched_barrier(0);
+                pair(K3{}, std::integral_constant<int, 3>{});
+                if (!last) KN_FRAG_READ(a[3], na, 12288);
+                __builtin_amdgcn_sched_barrier(0);
+            }
             slot ^= 1;
         }
-        // The slot just consumed is free: the next tile's SECOND k-tile is requested before this tile's end stores are
-        // queued, so that they stand behind it in the in-order count and the next tile's first two k-steps do not wait for them.
-        if (more && k_tiles >= 2) {
-            char* nxt = ring + (slot ^ 1) * STAGE_BYTES;
-            stage_tile_u<TB, WAVES>(Ag2 + BK, lda2, nxt, uwave, voff_a);
-            stage_tile_u<TB, WAVES>(Bg2 + BK, ldb2, nxt + TILE_BYTES, uwave, voff_b);
-            ops += LOADS_PER_STAGE;
-            mark[slot ^ 1] = ops;
-            pre_issued = true;
-        }
+        // (The next tile's first TWO k-tiles were requested by this tile's last two k-steps, in front of the tile's end
+        // stores; those have the next tile's first k-step to themselves before its barrier waits for them.)
+#ifdef KNNCF_OV_ABL_NOMFMA
+        acc[0][0][0] += abl_sink;
+#endif
         // short K (fewer k-steps than units): what is left of the previous tile leaves here, not overlapped
         while (unit < UNITS) {
-            ops += (uint32_t)drain_unit(unit);
+            (void)drain_unit(unit);
             ++unit;
         }
         ptm = tm;
@@ -768,11 +826,11 @@ k_gemm_nt_ov(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, _Float1
         {
             uint32_t Q0[WN][8], Q1[WN][8];
             convert(Q0, std::integral_constant<int, 0>{});
-            ops += (uint32_t)drain_normal(Q0, 0);
+            (void)drain_normal(Q0, 0);
             convert(Q1, std::integral_constant<int, 1>{});
-            ops += (uint32_t)drain_normal(Q1, 1);
-            ops += (uint32_t)drain_mirror(Q0, Q1, 0, std::integral_constant<int, 0>{});
-            ops += (uint32_t)drain_mirror(Q0, Q1, 0, std::integral_constant<int, 1>{});
+            (void)drain_normal(Q1, 1);
+            (void)drain_mirror(Q0, Q1, 0, std::integral_constant<int, 0>{});
+            (void)drain_mirror(Q0, Q1, 0, std::integral_constant<int, 1>{});
         }
         convert(P[0], std::integral_constant<int, 2>{});
         convert(P[1], std::integral_constant<int, 3>{});
@@ -781,8 +839,6 @@ k_gemm_nt_ov(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, _Float1
         t = t_next;
         tm = tm2;
         tn = tn2;
-        Ag = Ag2;
-        Bg = Bg2;
     }
     while (unit < UNITS) {  // the last tile of this workgroup
         (void)drain_unit(unit);
