@@ -804,8 +804,8 @@ int knncf_revise_recommend_explain_batch(knncf_handle* h, int predictor, const i
  * no device memory.
  * Handle state.  Read-only in the sense of the other families: the neighbour table, its build numbers, its epoch and the
  * knncf_neighbors_save bytes stay as they were.  knncf_get_timings: charged as the fold-in calls charge theirs.
- * OUT OF SCOPE: bystanders of update and revise queries (a newcomer that is in the fit changes its own mean, and with it the
- * deviation of every one of its train rows in other users' folds); KNNCF_PRED_PERSONALIZED and the other predictors;
+ * OUT OF SCOPE: a `user` that is in the fit (update queries: "Bystanders of update queries" below; revise queries: not
+ * served); KNNCF_PRED_PERSONALIZED and the other predictors;
  * recommendations and explanations for a bystander; device-pointer forms; shard handles and knncf_group_*.  ("Which fitted
  * users does the newcomer enter" is knncf_query_entered, below.) */
 int knncf_query_bystander_neighbors(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
@@ -818,6 +818,62 @@ int knncf_query_bystander_neighbors_batch(knncf_handle* h, const int32_t* users,
 int knncf_query_bystander_predict_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets,
                                         const int32_t* items, const double* ratings, int64_t n_queries, const int64_t* row_offsets,
                                         const int32_t* others, const int32_t* pred_items, double* out, int32_t* statuses);
+
+/* ---- Bystanders of update queries: a FITTED user's kNN answers once another user, fitted or not, has added ratings ------------
+ * Most ratings come from users the fit knows.  When fitted user c rates more items its mean moves, and with it every deviation
+ * and the norm: every S(v, c) changes, c can climb, sink, enter or leave the list of any other user v, and the terms c gives
+ * to v's folds change on the items it rated long ago too.  These calls answer for such v WITHOUT a refit.
+ * A query is an update query exactly as knncf_update_* defines it: any raw id `user` with ADDITIONAL rows (items[j],
+ * ratings[j]), aug = train ++ those rows in order.  A ROW names a bystander others[r] != user, the predict forms a raw item
+ * pred_items[r] beside it.  Every row is answered on closures of its own over aug whose first evaluation is the row's — the
+ * bystander owns every pair — bit for bit:
+ *   knncf_update_bystander_neighbors  getNeighbors(aug, k, sim)(others[r]) :596-617: raw ids, row stride cap, counts[r] = the
+ *                                     list's length (may exceed cap), cells past the written ones untouched.  A fitted `user`
+ *                                     is an ordinary train candidate at its place in set order: min(k, U - 1) for a fitted
+ *                                     bystander; for a bystander unknown to aug the first min(k, |users(aug)|) users of aug
+ *                                     in set order with +0.0, |users(aug)| = U for a fitted `user`, U + 1 otherwise.
+ *   knncf_update_bystander_predict    predictor(aug, weightedSumDeviation(aug, getSimilarity(aug, k, sim)))(others[r],
+ *                                     pred_items[r]) :489-585 for any item id; a bystander unknown to aug or with a negative
+ *                                     mean gets average(aug) :573, the fit's running total continued over the additional
+ *                                     ratings in the given order, over n + n_ratings.
+ * What a fitted changer c does to bystander v:
+ *   S(v, c) on aug, owned by v: the left fold from 0.0 of pre_v(i) * pre_c^aug(i) over the common items in v's item-set order
+ *     (ascending dense item for a v of more than 4 train ratings, else v's file order); Jaccard |I(v) & I(c)| / (|I(v)| +
+ *     |I(c)| - |I(v) & I(c)|) with |I(c)| counting all of c's items on aug.  Every other S(v, x) is the train value.
+ *   The list: that value replaces the train value in v's similarity row before the list is cut.  c keeps its place in set
+ *     order; a c that leaves a full list is replaced by the next candidate.
+ *   The fold: where c is in v's list its terms carry its deviations on aug and the list's similarity; a train row of c stays
+ *     at its train file row, an additional row comes behind every train row in the given order.
+ *   An item unknown to train that c rates in an additional row has exactly one rater in aug: the one-term fold 0.0 + dev_c(i) *
+ *     S(v, c) over 0.0 + |S(v, c)| where c is in v's list, v's mean exactly otherwise.
+ * A `user` absent from train is the fold-in case: the answers are knncf_query_bystander_*'s bit for bit, except that an empty
+ * query is KNNCF_E_INVALID as in knncf_update_*.  n_ratings == 0 for a fitted `user` is valid and aug is train: every row is then
+ * knncf_update_neighbors / knncf_update_predict of the bystander without rows.  Users of 4 or fewer ratings are accepted on both
+ * sides and both similarities: the closures are fresh.
+ * Batch forms, outputs, untouched rows: those of knncf_query_bystander_*.  A failed query gets counts = 0 on its rows.
+ * Per-query statuses: those of knncf_update_predict_batch (KNNCF_E_DUPLICATE, also against the user's train items;
+ * KNNCF_E_NONFINITE; KNNCF_E_UNSUPPORTED for a negative mean of the combined rows or more than 65536 of them; KNNCF_E_INVALID for
+ * an empty query of an absent user), and KNNCF_E_INVALID for a row with others[r] == users[b], KNNCF_E_UNSUPPORTED for a
+ * bystander of more than 65536 train ratings.  Refusals of the handle: those of knncf_query_bystander_*_batch.
+ * Chunks: the slots and C of "Bystander queries".  The changer's own slot is an update slot (its train rows seeded, then the
+ * additional rows), each distinct bystander that needs the device takes an update slot without rows; a query with more
+ * bystanders than fit beside its own slot continues in the next chunk, where its row is prepared again.  A chunk may mix fitted
+ * changers and newcomers.  Results do not depend on C; a repeated call of the same shape allocates no device memory.
+ * Handle state: read-only, as "Bystander queries".  knncf_get_timings: charged as the fold-in calls charge theirs.
+ * OUT OF SCOPE: bystanders of revise queries (with removals average(aug) is no continuation of the fit's running total, and an
+ * item can leave aug); the entered question for update queries (a changer that leaves a list needs that user's full row);
+ * KNNCF_PRED_PERSONALIZED and the other predictors; recommendations and explanations for a bystander; device-pointer forms; shard
+ * handles and knncf_group_*; the command-line tool. */
+int knncf_update_bystander_neighbors(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
+                                     const int32_t* others, int64_t m, int32_t cap, int32_t* ids, double* sims, int32_t* counts);
+int knncf_update_bystander_predict(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
+                                   int64_t n_ratings, const int32_t* others, const int32_t* pred_items, int64_t m, double* out);
+int knncf_update_bystander_neighbors_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                                           const double* ratings, int64_t n_queries, const int64_t* row_offsets, const int32_t* others,
+                                           int32_t cap, int32_t* ids, double* sims, int32_t* counts, int32_t* statuses);
+int knncf_update_bystander_predict_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets,
+                                         const int32_t* items, const double* ratings, int64_t n_queries, const int64_t* row_offsets,
+                                         const int32_t* others, const int32_t* pred_items, double* out, int32_t* statuses);
 
 /* ---- Entered queries: which fitted users' neighbour lists a newcomer joins ---------------------------------------------------
  * Under KNNCF_PRED_KNN a fitted user v's predictions change when a newcomer joins only if the newcomer enters
@@ -861,7 +917,8 @@ int knncf_query_bystander_predict_batch(knncf_handle* h, int predictor, const in
  * Chunks.  C of "Batched fold-in queries", one slot per query.  The entered-list scratch (20 bytes * min(cap, num_users) + 4 per
  * slot, at most 20 bytes * num_users) is allocated beside the budget, as the gathered ratings are.  The results do not depend on
  * C, and a repeated call of the same shape allocates no device memory.
- * OUT OF SCOPE: newcomers that are in the fit (update and revise queries); KNNCF_PRED_PERSONALIZED; cosine fits with users of 4
+ * OUT OF SCOPE: newcomers that are in the fit (their bystanders' lists: "Bystanders of update queries" above; the entered
+ * question itself is not served for them, nor for revise queries); KNNCF_PRED_PERSONALIZED; cosine fits with users of 4
  * or fewer ratings; an ordering by similarity; device-pointer forms; shard handles and knncf_group_*; the command-line tool. */
 int knncf_query_entered(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
                         int32_t cap, int32_t* out_users, double* out_sims, int32_t* out_pos, int32_t* out_displaced,

@@ -1576,6 +1576,8 @@ int query_single(knncf_handle* h, const QueryCall& q) { return guarded(h, [&] { 
 // A query is a fold-in query (pack_chunk admits it, settle_statuses gives it its status); its rows name bystanders.  The unit
 // of a chunk is a slot: the newcomer's own, then one per distinct bystander that needs the device — a user of the fit, in
 // QB_BY_PREDICT with a mean >= 0.  The rows of the other bystanders are answered on the host once the query's status is known.
+// knncf_update_bystander_* run the same loop with family QF_UPDATE: the query is an update query, and where its user is of the
+// fit (a fitted CHANGER) its own slot is an update slot and no list takes a newcomer in (bystander.hip).
 constexpr int32_t BY_NO_SLOT = -1;
 struct ByRow {
     int64_t row;   // of the call
@@ -1583,9 +1585,10 @@ struct ByRow {
     int32_t own;   // the newcomer's slot in the chunk
 };
 struct ByChunkState {
-    std::vector<int32_t> qslot, qrank;
+    std::vector<int32_t> qslot, qrank, qidx;  // qidx: the changer's index in a list, U for a newcomer (ByChunk)
     std::vector<ByRow> rows;
-    void clear() { qslot.clear(); qrank.clear(); rows.clear(); }
+    int32_t fitted = 0, merged = 0;
+    void clear() { qslot.clear(); qrank.clear(); qidx.clear(); rows.clear(); fitted = merged = 0; }
 };
 
 // slots per chunk: the rule of knncf.h ("Bystander queries")
@@ -1605,7 +1608,7 @@ void answer_bystander_chunk(knncf_handle* h, const QueryCall& q, ChunkState& cs,
     hipStream_t st = h->stream;
     const int32_t U = h->tr.U, take = cs.take;
     cs.info.assign((size_t)4 * cs.C, 0);
-    const ByChunk by{bc.qslot.data(), bc.qrank.data()};
+    const ByChunk by{bc.qslot.data(), bc.qrank.data(), bc.qidx.data(), bc.fitted, bc.merged};
     foldin_batch_neighbors(h->tr, bs, h->prep.sort, cs.C, cs.s_users.data(), cs.qo.data(), cs.s_items.data(), cs.s_ratings.data(),
                            cs.s_self.data(), cs.ao.data(), h->cfg.k, cs.info.data(), st, nullptr, nullptr, true, &by);
     // a bystander slot stands or falls with its newcomer: the slot's own bits (a negative mean of the bystander, which
@@ -1624,11 +1627,12 @@ void answer_bystander_chunk(knncf_handle* h, const QueryCall& q, ChunkState& cs,
         }
         for (const ByRow& r : bc.rows) {
             if (!good(r)) continue;
-            const int32_t newcomer = cs.s_users[r.own], at = bc.qrank[r.own];
+            const bool fitted = cs.s_self[r.own] >= 0;  // the changer is a user of the fit: aug has the fit's users
+            const int32_t newcomer = cs.s_users[r.own], at = fitted ? U : bc.qrank[r.own];
             int32_t* ids = q.out_i + r.row * width;
             double* sims = q.out_d + r.row * width;
             if (r.slot == BY_NO_SLOT) {  // unknown to aug: every similarity is 0.0, ties keep the set order of aug's users
-                const int32_t n = (int32_t)std::min<int64_t>(h->cfg.k, (int64_t)U + 1);
+                const int32_t n = (int32_t)std::min<int64_t>(h->cfg.k, (int64_t)U + (fitted ? 0 : 1));
                 for (int32_t j = 0; j < std::min(n, width); ++j) {
                     ids[j] = j < at ? h->h_uid[j] : j == at ? newcomer : h->h_uid[j - 1];
                     sims[j] = 0.0;
@@ -1636,12 +1640,13 @@ void answer_bystander_chunk(knncf_handle* h, const QueryCall& q, ChunkState& cs,
                 q.row_counts[r.row] = std::max(n, 0);
                 continue;
             }
-            for (int32_t j = 0; j < c; ++j) {
+            const int32_t mine = fitted ? std::min(take, U - 1) : take;  // (a fitted changer is one of the U - 1 candidates)
+            for (int32_t j = 0; j < std::min(c, mine); ++j) {
                 const int32_t v = cs.h_idx[(size_t)r.slot * take + j];
                 ids[j] = v == U ? newcomer : h->h_uid[v];
                 sims[j] = cs.h_vals[(size_t)r.slot * take + j];
             }
-            q.row_counts[r.row] = take;
+            q.row_counts[r.row] = mine;
         }
         return;
     }
@@ -1706,7 +1711,7 @@ QueryFailure run_bystander_chunks(knncf_handle* h, const QueryCall& q, int64_t c
             if (train_row_length(h, dv) > QUERY_MAX_RATINGS) { long_row = true; break; }
             seen.push_back({dv, (int32_t)(r - r0)});
         }
-        if (self_row) { refuse(b, KNNCF_E_INVALID, "a row names the query's own user (ask knncf_query_predict)"); continue; }
+        if (self_row) { refuse(b, KNNCF_E_INVALID, "a row names the query's own user (ask the query's own predict call)"); continue; }
         if (long_row) { refuse(b, KNNCF_E_UNSUPPORTED, "a bystander with more than 65536 ratings"); continue; }
         std::stable_sort(seen.begin(), seen.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
         // distinct bystanders, numbered in order of first appearance
@@ -1722,18 +1727,25 @@ QueryFailure run_bystander_chunks(knncf_handle* h, const QueryCall& q, int64_t c
         }
         const uint32_t qkey = int_trie_key(q.users[b]);
         const int32_t at = (int32_t)(std::lower_bound(h->h_ukeys.begin(), h->h_ukeys.end(), qkey) - h->h_ukeys.begin());
+        // the changer: a newcomer (index U in a list), or with knncf_update_bystander_* a user of the fit whose own slot is an
+        // update slot — its train rows seeded in front of the given ones
+        const int32_t dc = q.family == QF_FOLD_IN ? -1 : one.s_self[0];
+        const int32_t ci = dc >= 0 ? dc : h->tr.U;
         size_t pos = 0;
         do {
             if (chunk - cs.C < (dist.empty() ? 1 : 2)) flush();
             const int32_t own = cs.C;
             cs.slot_query.push_back(b);
             cs.s_users.push_back(q.users[b]);
-            cs.s_self.push_back(-1);
-            cs.s_items.insert(cs.s_items.end(), q.items + q.offsets[b], q.items + q.offsets[b + 1]);
-            cs.s_ratings.insert(cs.s_ratings.end(), q.ratings + q.offsets[b], q.ratings + q.offsets[b + 1]);
+            cs.s_self.push_back(dc);
+            if (q.offsets[b + 1] > q.offsets[b]) {
+                cs.s_items.insert(cs.s_items.end(), q.items + q.offsets[b], q.items + q.offsets[b + 1]);
+                cs.s_ratings.insert(cs.s_ratings.end(), q.ratings + q.offsets[b], q.ratings + q.offsets[b + 1]);
+            }
             cs.ao.push_back((int64_t)cs.s_items.size());
-            cs.qo.push_back(cs.qo.back() + (q.offsets[b + 1] - q.offsets[b]));
-            bc.qslot.push_back(own); bc.qrank.push_back(at);
+            cs.qo.push_back(cs.qo.back() + (q.offsets[b + 1] - q.offsets[b]) + (dc >= 0 ? train_row_length(h, dc) : 0));
+            bc.qslot.push_back(own); bc.qrank.push_back(at); bc.qidx.push_back(ci);
+            if (dc >= 0) ++bc.fitted;
             ++cs.C;
             const size_t cnt = std::min<size_t>(dist.size() - pos, (size_t)(chunk - cs.C));
             for (size_t d = pos; d < pos + cnt; ++d) {
@@ -1742,7 +1754,8 @@ QueryFailure run_bystander_chunks(knncf_handle* h, const QueryCall& q, int64_t c
                 cs.s_self.push_back(dist[d]);
                 cs.ao.push_back(cs.ao.back());
                 cs.qo.push_back(cs.qo.back() + train_row_length(h, dist[d]));
-                bc.qslot.push_back(own); bc.qrank.push_back(at);
+                bc.qslot.push_back(own); bc.qrank.push_back(at); bc.qidx.push_back(ci);
+                if (dc < 0) ++bc.merged;
                 ++cs.C;
             }
             for (int64_t r = r0; r < r1; ++r) {
@@ -1790,7 +1803,11 @@ int bystander_batch(knncf_handle* h, const QueryCall& q) { return guarded(h, [&]
 int bystander_single(knncf_handle* h, QueryCall q, int64_t n_ratings, int64_t m) {
     return guarded(h, [&] {
         require_fitted(h, false);
-        KN_REQUIRE(n_ratings > 0 && q.items && q.ratings, KNNCF_E_INVALID, "query: null ratings or n_ratings <= 0");
+        if (q.family == QF_FOLD_IN) {
+            KN_REQUIRE(n_ratings > 0 && q.items && q.ratings, KNNCF_E_INVALID, "query: null ratings or n_ratings <= 0");
+        } else {  // (an update query may come without rows: whether the user is in the fit is the chunk loop's to say)
+            KN_REQUIRE(n_ratings >= 0 && (n_ratings == 0 || (q.items && q.ratings)), KNNCF_E_INVALID, "query: null ratings or n_ratings < 0");
+        }
         KN_REQUIRE(m >= 0, KNNCF_E_INVALID, "query: m < 0");
         const int64_t offsets[2] = {0, n_ratings}, row_offsets[2] = {0, m};
         int32_t status = KNNCF_OK;
@@ -3063,6 +3080,38 @@ int knncf_query_bystander_predict_batch(knncf_handle* h, int predictor, const in
                                         const int32_t* items, const double* ratings, int64_t n_queries, const int64_t* row_offsets,
                                         const int32_t* others, const int32_t* pred_items, double* out, int32_t* statuses) {
     return bystander_batch(h, {.family = QF_FOLD_IN, .mode = QB_BY_PREDICT, .predictor = predictor, .users = users, .B = n_queries,
+                               .offsets = offsets, .items = items, .ratings = ratings, .pred_offsets = row_offsets,
+                               .pred_items = pred_items, .others = others, .out_d = out, .statuses = statuses});
+}
+
+// bystanders of update queries: the same four calls for a user that may be in the fit, whose given rows are then additional to
+// its train rows (knncf.h "Bystanders of update queries")
+int knncf_update_bystander_neighbors(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
+                                     const int32_t* others, int64_t m, int32_t cap, int32_t* ids, double* sims, int32_t* counts) {
+    return bystander_single(h, {.family = QF_UPDATE, .mode = QB_BY_NEIGHBORS, .predictor = KNNCF_PRED_KNN, .items = items, .ratings = ratings,
+                                .others = others, .row_counts = counts, .width = cap, .out_i = ids, .out_d = sims, .user = user},
+                            n_ratings, m);
+}
+
+int knncf_update_bystander_predict(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
+                                   int64_t n_ratings, const int32_t* others, const int32_t* pred_items, int64_t m, double* out) {
+    return bystander_single(h, {.family = QF_UPDATE, .mode = QB_BY_PREDICT, .predictor = predictor, .items = items, .ratings = ratings,
+                                .pred_items = pred_items, .others = others, .out_d = out, .user = user},
+                            n_ratings, m);
+}
+
+int knncf_update_bystander_neighbors_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                                           const double* ratings, int64_t n_queries, const int64_t* row_offsets, const int32_t* others,
+                                           int32_t cap, int32_t* ids, double* sims, int32_t* counts, int32_t* statuses) {
+    return bystander_batch(h, {.family = QF_UPDATE, .mode = QB_BY_NEIGHBORS, .predictor = KNNCF_PRED_KNN, .users = users, .B = n_queries,
+                               .offsets = offsets, .items = items, .ratings = ratings, .pred_offsets = row_offsets, .others = others,
+                               .row_counts = counts, .width = cap, .out_i = ids, .out_d = sims, .statuses = statuses});
+}
+
+int knncf_update_bystander_predict_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets,
+                                         const int32_t* items, const double* ratings, int64_t n_queries, const int64_t* row_offsets,
+                                         const int32_t* others, const int32_t* pred_items, double* out, int32_t* statuses) {
+    return bystander_batch(h, {.family = QF_UPDATE, .mode = QB_BY_PREDICT, .predictor = predictor, .users = users, .B = n_queries,
                                .offsets = offsets, .items = items, .ratings = ratings, .pred_offsets = row_offsets,
                                .pred_items = pred_items, .others = others, .out_d = out, .statuses = statuses});
 }

@@ -12,6 +12,16 @@
 //                  n_train + position, behind every train row: q's term is the last of an item's fold :520-524
 //   k_by_pick      k_qb_pick in which an item that only q rates has that one term
 // The sort of the gathered entries, k_q_fold and k_qb_pred of foldin.hip run between them unchanged.
+//
+// The changer may also be a user c of the fit that adds ratings (DESIGN.md "Bystanders of update queries";
+// knncf_update_bystander_*).  Its own slot is then an update slot — train rows seeded, the additional rows behind them — and
+// qidx[b], the changer's index of slot b, is dense(c) instead of U.  c is a train candidate of every bystander already:
+//   k_by_pair      as above: c's side is its prepared row on aug
+//   k_by_place     that value into cell [b][dense(c)] of bs.sim BEFORE the keys and the sorts: c keeps its place in set order,
+//                  and when it leaves a full list the next candidate of the slot's row comes in.  No merge.
+//   k_by_merge     for such a slot only looks c up in the written list (in_list for k_by_pick)
+//   k_by_offsets / k_by_gather   index dense(c) reads c's prepared row: deviations on aug, a train row at its train file row,
+//                  an additional row at n_train + its position among the additional rows
 #include <math.h>
 
 #include <algorithm>
@@ -99,6 +109,17 @@ __global__ void __launch_bounds__(TPB) k_by_pair(int32_t C, int64_t W, bool jacc
     if (lane == 0) pair[b] = s;
 }
 
+// A fitted changer c of bystander slot b: S(v, c) on aug into the slot's similarity row, over the train value that the
+// similarity kernel put there.  Runs after that kernel and before the keys, k_qb_mask_self and the sorts.
+// Bounds.  b < C; qidx[b] < U is a dense user, so the cell is inside row b of sim [C][U].
+__global__ void k_by_place(int32_t C, int32_t U, const int32_t* __restrict__ qslot, const int32_t* __restrict__ qidx,
+                           const double* __restrict__ pair, double* __restrict__ sim) {
+    const int32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= C || qslot[b] == b) return;
+    const int32_t ci = qidx[b];
+    if (ci >= 0 && ci < U) sim[(int64_t)b * U + ci] = pair[b];
+}
+
 // One wave per bystander slot b: (q, pair[b]) enters the slot's sorted list of L = min(take, U - 1) train users (k_qb_write;
 // v itself is masked out).  (allUsers(aug) - v).toSeq is the train users in dense order with q in front of dense user
 // qrank[b], and the stable sortWith keeps that order among equal similarities: an entry goes before q when its key is smaller,
@@ -108,18 +129,28 @@ __global__ void __launch_bounds__(TPB) k_by_pair(int32_t C, int64_t W, bool jacc
 // The move runs from the top in blocks of 64 cells: every lane's store takes the value its own load returned, so a block's
 // loads have all completed before its first store, and a block only writes cells that blocks above it have read already.
 // Bounds.  Cells [0, L) are read, cells [pos, min(L + 1, take)) of the slot's `take` cells are written.
+// A fitted changer (qidx[b] < U) sits in the list already where it belongs, or not at all: the wave only looks for it among
+// the L written cells, in_list[b] = its similarity there (the list's, which is pair[b]) or +0.0.
 __global__ void __launch_bounds__(TPB) k_by_merge(int32_t C, int32_t take, int32_t U, const int32_t* __restrict__ qslot,
-                                                  const int32_t* __restrict__ qrank, const double* __restrict__ pair,
-                                                  int32_t* __restrict__ nbr_idx, double* __restrict__ nbr_sim,
-                                                  double* __restrict__ in_list) {
+                                                  const int32_t* __restrict__ qidx, const int32_t* __restrict__ qrank,
+                                                  const double* __restrict__ pair, int32_t* __restrict__ nbr_idx,
+                                                  double* __restrict__ nbr_sim, double* __restrict__ in_list) {
     const int lane = threadIdx.x & 63;
     const int32_t b = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
     if (b >= C || qslot[b] == b) return;
     const int32_t L = min(take, U - 1), at = qrank[b];
-    const double s = pair[b];
-    const uint64_t ks = by_sim_key(s);
     int32_t* idx = nbr_idx + (int64_t)b * take;
     double* sim = nbr_sim + (int64_t)b * take;
+    const int32_t ci = qidx[b];
+    if (ci != U) {
+        for (int32_t base = 0; base < L; base += 64) {
+            const int32_t j = base + lane;
+            if (j < L && idx[j] == ci) in_list[b] = sim[j];  // (at most one cell holds c)
+        }
+        return;
+    }
+    const double s = pair[b];
+    const uint64_t ks = by_sim_key(s);
     int32_t pos = 0;
     for (int32_t base = 0; base < L; base += 64) {
         const int32_t j = base + lane;
@@ -151,32 +182,39 @@ __global__ void __launch_bounds__(TPB) k_by_merge(int32_t C, int32_t take, int32
     }
 }
 
-// k_qb_offsets for a chunk with bystander slots: off[b][0 .. take] and info[4 b + 2] of the slot's `take` neighbours, where
-// index U stands for the newcomer's distinct known items.  A newcomer's own slot, a slot whose status is set and a bystander
-// slot whose newcomer's status is set take no part in the prediction pass (0 entries).
+// k_qb_offsets for a chunk with bystander slots: off[b][0 .. take] and info[4 b + 2] of the slot's neighbours, where the
+// changer's index qidx[b] stands for its distinct known items on aug.  The list of a newcomer's bystander has `take` cells,
+// that of a fitted changer's min(take, U - 1).  A changer's own slot, a slot whose status is set and a bystander slot whose
+// changer's status is set take no part in the prediction pass (0 entries).
 __global__ void __launch_bounds__(ONE_BLOCK) k_by_offsets(int32_t take, int32_t U, int64_t W, const int32_t* __restrict__ qslot,
-                                                          const int32_t* __restrict__ nbr, const int64_t* __restrict__ u_ptr,
-                                                          const int64_t* __restrict__ rank, int64_t* __restrict__ off,
-                                                          long long* __restrict__ info) {
-    const int32_t b = blockIdx.x, qs = qslot[b];
+                                                          const int32_t* __restrict__ qidx, const int32_t* __restrict__ nbr,
+                                                          const int64_t* __restrict__ u_ptr, const int64_t* __restrict__ rank,
+                                                          int64_t* __restrict__ off, long long* __restrict__ info) {
+    const int32_t b = blockIdx.x, qs = qslot[b], ci = qidx[b];
     const int32_t* mine = nbr + (int64_t)b * take;
-    const int64_t live = (qs == b || info[4 * b] != 0 || info[4 * qs] != 0) ? 0 : take;
+    const int64_t live = (qs == b || info[4 * b] != 0 || info[4 * qs] != 0) ? 0 : (ci == U ? take : min(take, U - 1));
     const int64_t kq = rank[(int64_t)qs * (W + 1) + W];
     const int64_t total = block_exclusive_scan(
         take,
         [&](int64_t j) {
             if (j >= live) return (int64_t)0;
             const int32_t v = mine[j];
-            return v == U ? kq : u_ptr[v + 1] - u_ptr[v];
+            return v == ci ? kq : u_ptr[v + 1] - u_ptr[v];
         },
         off + (int64_t)b * (take + 1));
     if (threadIdx.x == 0) info[4 * b + 2] = total;
 }
 
-// k_qb_gather in which neighbour index U is the newcomer: entry r of its extent is its r-th known item in dense order, with
-// the deviation k_qb_scatter put there; the file row of its given position g is n_train + g (q's rows are the last of aug)
+// k_qb_gather in which neighbour index qidx[slot] is the changer: entry r of its extent is its r-th known item in dense order,
+// with the deviation k_qb_scatter put there.  A newcomer's file row of given position g is n_train + g (q's rows are the last
+// of aug).  A fitted changer c's row of the item is either a train row — it stays at its train file row s_t, found in c's
+// row of the fit (sorted by dense item) — or an additional one: n_train + (g - c's train rows), the given order of an update
+// slot being the train rows, then the additional rows.
+// Bounds.  The search stays inside [u_ptr[c], u_ptr[c + 1]); gv >= tl for an item it does not find: every train row of c is
+// among the slot's first tl given positions.
 __global__ void __launch_bounds__(TPB) k_by_gather(int32_t C, int32_t take, int32_t U, int32_t I, uint32_t n_train,
-                                                   const int32_t* __restrict__ qslot, const int64_t* __restrict__ qo,
+                                                   const int32_t* __restrict__ qslot, const int32_t* __restrict__ qidx,
+                                                   const int64_t* __restrict__ qo,
                                                    const int32_t* __restrict__ di, const int32_t* __restrict__ given_d,
                                                    const double* __restrict__ dev_d, const int32_t* __restrict__ nbr,
                                                    const double* __restrict__ nsim, const int64_t* __restrict__ off,
@@ -192,12 +230,20 @@ __global__ void __launch_bounds__(TPB) k_by_gather(int32_t C, int32_t take, int3
     const int32_t v = nbr[g];
     const int64_t o = ebase[sb] + lo;
     const double sj = nsim[g];
-    if (v == U) {
+    if (v == qidx[sb]) {
         const int64_t oq = qo[qslot[sb]];
+        const int64_t c0 = v == U ? 0 : u_ptr[v], tl = v == U ? 0 : u_ptr[v + 1] - c0;
         for (int64_t r = threadIdx.x & 63; r < hi - lo; r += 64) {
-            const int32_t gv = given_d[oq + r];
+            const int32_t gv = given_d[oq + r], d = di[oq + gv];
             const int64_t x = o + r;
-            key[x] = ((uint64_t)((uint32_t)sb * (uint32_t)I + (uint32_t)di[oq + gv]) << 32) | (uint64_t)(n_train + (uint32_t)gv);
+            int64_t a = 0, e = tl;
+            while (a < e) {
+                const int64_t mid = (a + e) >> 1;
+                if (s_col[c0 + mid] < d) a = mid + 1;
+                else e = mid;
+            }
+            const uint32_t row = (a < tl && s_col[c0 + a] == d) ? s_t[c0 + a] : n_train + (uint32_t)(gv - tl);
+            key[x] = ((uint64_t)((uint32_t)sb * (uint32_t)I + (uint32_t)d) << 32) | (uint64_t)row;
             val[x] = (uint32_t)x;
             edev[x] = dev_d[oq + r];
             esim[x] = sj;
@@ -215,8 +261,9 @@ __global__ void __launch_bounds__(TPB) k_by_gather(int32_t C, int32_t take, int3
 }
 
 // requested raw items with their (bystander) slot: the dense item's prediction of k_qb_pred.  An item unknown to train has at
-// most one rater in aug, the newcomer: its term dev_q(i) * S(v, q) when q is in v's list (in_list = S, else +0.0) is the whole
-// fold :520-524, and without a non-zero S the answer is v's mean exactly (den = 0), as for an item unknown to aug
+// most one rater in aug, the changer (a fitted one rates it in an additional row): its term dev_q(i) * S(v, q) when q is in
+// v's list (in_list = S, else +0.0) is the whole fold :520-524, and without a non-zero S the answer is v's mean exactly
+// (den = 0), as for an item unknown to aug
 __global__ void k_by_pick(int64_t m, const int32_t* __restrict__ items, const int32_t* __restrict__ slot,
                           const int32_t* __restrict__ i_table, int32_t i_cells, const uint32_t* __restrict__ ikeys, int32_t I,
                           const int32_t* __restrict__ qslot, const int64_t* __restrict__ qo, const int32_t* __restrict__ q_items,
@@ -249,29 +296,42 @@ __global__ void k_by_pick(int64_t m, const int32_t* __restrict__ items, const in
 static int32_t table_cells(const Train& tr) { return (tr.u_table_n > 0 && tr.i_table_n > 0) ? tr.i_table_n : 0; }
 
 void bystander_upload(QueryBatchScratch& bs, int32_t C, const ByChunk& by, hipStream_t st) {
-    bs.by_qslot.ensure(C); bs.by_qrank.ensure(C); bs.by_pair.ensure(C); bs.by_in.ensure(C);
+    bs.by_qslot.ensure(C); bs.by_qidx.ensure(C); bs.by_qrank.ensure(C); bs.by_pair.ensure(C); bs.by_in.ensure(C);
+    KN_TRACE_DISPATCH("bystander slots=%d fitted=%d merge=%d", (int)C, (int)by.fitted, (int)by.merged);
     KN_HIP(hipMemcpyAsync(bs.by_qslot.p, by.h_qslot, (size_t)C * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    KN_HIP(hipMemcpyAsync(bs.by_qidx.p, by.h_qidx, (size_t)C * sizeof(int32_t), hipMemcpyHostToDevice, st));
     KN_HIP(hipMemcpyAsync(bs.by_qrank.p, by.h_qrank, (size_t)C * sizeof(int32_t), hipMemcpyHostToDevice, st));
     KN_HIP(hipMemsetAsync(bs.by_pair.p, 0, (size_t)C * sizeof(double), st));
     KN_HIP(hipMemsetAsync(bs.by_in.p, 0, (size_t)C * sizeof(double), st));
 }
 
-void bystander_merge(const Train& tr, QueryBatchScratch& bs, int32_t C, int32_t take, hipStream_t st) {
+static void launch_pair(const Train& tr, QueryBatchScratch& bs, int32_t C, hipStream_t st) {
+    k_by_pair<<<(unsigned)ceil_div(C, TPB / 64), TPB, 0, st>>>(C, ceil_div(tr.I, 64), tr.jaccard, bs.by_qslot.p, bs.qo.p, bs.di.p,
+                                                               bs.given_d.p, bs.pre_d.p, (const unsigned long long*)bs.bits.p,
+                                                               bs.rank.p, bs.by_pair.p);
+}
+
+void bystander_place(const Train& tr, QueryBatchScratch& bs, int32_t C, hipStream_t st) {
+    launch_pair(tr, bs, C, st);
+    k_by_place<<<(unsigned)ceil_div(C, TPB), TPB, 0, st>>>(C, tr.U, bs.by_qslot.p, bs.by_qidx.p, bs.by_pair.p, bs.sim.p);
+    KN_HIP(hipGetLastError());
+}
+
+void bystander_merge(const Train& tr, QueryBatchScratch& bs, int32_t C, int32_t take, bool placed, hipStream_t st) {
     const int64_t W = ceil_div(tr.I, 64);
     const unsigned grid = (unsigned)ceil_div(C, TPB / 64);
-    k_by_pair<<<grid, TPB, 0, st>>>(C, W, tr.jaccard, bs.by_qslot.p, bs.qo.p, bs.di.p, bs.given_d.p, bs.pre_d.p,
-                                    (const unsigned long long*)bs.bits.p, bs.rank.p, bs.by_pair.p);
+    if (!placed) launch_pair(tr, bs, C, st);
     if (take > 0)
-        k_by_merge<<<grid, TPB, 0, st>>>(C, take, tr.U, bs.by_qslot.p, bs.by_qrank.p, bs.by_pair.p, bs.nbr_idx.p, bs.nbr_sim.p,
-                                         bs.by_in.p);
-    k_by_offsets<<<C, ONE_BLOCK, 0, st>>>(take, tr.U, W, bs.by_qslot.p, bs.nbr_idx.p, tr.u_ptr.p, bs.rank.p, bs.off.p,
+        k_by_merge<<<grid, TPB, 0, st>>>(C, take, tr.U, bs.by_qslot.p, bs.by_qidx.p, bs.by_qrank.p, bs.by_pair.p, bs.nbr_idx.p,
+                                         bs.nbr_sim.p, bs.by_in.p);
+    k_by_offsets<<<C, ONE_BLOCK, 0, st>>>(take, tr.U, W, bs.by_qslot.p, bs.by_qidx.p, bs.nbr_idx.p, tr.u_ptr.p, bs.rank.p, bs.off.p,
                                           (long long*)bs.info.p);
     KN_HIP(hipGetLastError());
 }
 
 void bystander_gather(const Train& tr, QueryBatchScratch& bs, int32_t C, int32_t take, hipStream_t st) {
     k_by_gather<<<(unsigned)ceil_div((int64_t)C * take, TPB / 64), TPB, 0, st>>>(
-        C, take, tr.U, tr.I, (uint32_t)tr.n, bs.by_qslot.p, bs.qo.p, bs.di.p, bs.given_d.p, bs.dev_d.p, bs.nbr_idx.p, bs.nbr_sim.p,
+        C, take, tr.U, tr.I, (uint32_t)tr.n, bs.by_qslot.p, bs.by_qidx.p, bs.qo.p, bs.di.p, bs.given_d.p, bs.dev_d.p, bs.nbr_idx.p, bs.nbr_sim.p,
         bs.off.p, bs.ebase.p, tr.u_ptr.p, tr.s_col.p, tr.s_t.p, tr.s_dev.p, bs.e_k64_a.p, bs.e_v32_a.p, bs.e_dev.p, bs.e_sim.p);
 }
 

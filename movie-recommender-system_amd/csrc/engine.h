@@ -387,9 +387,10 @@ struct QueryBatchScratch {
     DArr<int32_t> pick_items, pick_slot, out_items;
     DArr<double> pick_out, out_preds;
     DArr<int64_t> reco_rb;             // [C + 1] first explain row of each slot (foldin_batch_reco_rows)
-    // bystander queries (bystander.hip): [C] the newcomer's slot of each slot (its own index for a newcomer's slot), the
-    // newcomer's place in set order, S(v, q), and S(v, q) again where q entered v's list (else +0.0)
-    DArr<int32_t> by_qslot, by_qrank;
+    // bystander queries (bystander.hip): [C] the changer's slot of each slot (its own index for a changer's slot), the changer's
+    // index (U for a newcomer, its dense user for a user of the fit), a newcomer's place in set order, S(v, q), and S(v, q) again
+    // where q is in v's list (else +0.0)
+    DArr<int32_t> by_qslot, by_qidx, by_qrank;
     DArr<double> by_pair, by_in;
     // entered queries (entered.hip): the answers of a chunk in ONE block (entered_pack), 20 * width + 4 bytes per slot
     DArr<double> en_pack;
@@ -397,9 +398,15 @@ struct QueryBatchScratch {
 // A chunk of bystander queries (DESIGN.md "Bystander queries"): slot b is either a newcomer's own fold-in slot (h_qslot[b] == b,
 // h_self[b] == -1) or a bystander's — a fitted user with no additional row (h_self[b] >= 0) whose newcomer is slot h_qslot[b] of
 // the same chunk.  h_qrank[b] = the number of train users in front of slot b's newcomer in set order.
+// The changer may instead be a user c of the fit with additional rows (DESIGN.md "Bystanders of update queries"): its own slot
+// is an update slot (h_self[b] == dense(c), h_qslot[b] == b).  h_qidx[b] = the index of slot b's changer in neighbour lists: U
+// for a newcomer, dense(c) for a fitted one (h_qrank is not read then).  fitted = the chunk's changer slots of the second kind,
+// merged = its bystander slots of newcomers (the trace line).
 struct ByChunk {
     const int32_t* h_qslot;
     const int32_t* h_qrank;
+    const int32_t* h_qidx;
+    int32_t fitted, merged;
 };
 // prep + similarities + top-k (bs.nbr_idx / nbr_sim [C][min(k, U)]) of C >= 1 non-empty queries; h_info[4 b ..] = status
 // bits, known items, neighbour ratings (0 for a slot whose status is set) of slot b.  Synchronises the stream once.
@@ -419,11 +426,12 @@ void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspac
 // written and the neighbour ratings of h_info are 0)
 // (by != nullptr, an update chunk with topk: after the top lists every bystander slot's list takes its newcomer in — index U,
 // min(k, U) entries — and the neighbour ratings of h_info count the newcomer's known items; a newcomer's own slot and the
-// bystander slots of a newcomer whose status is set have 0)
+// bystander slots of a newcomer whose status is set have 0.  The bystander slots of a fitted changer get S(v, c) on aug into
+// their similarity row ahead of the sorts instead: min(k, U - 1) entries, c among them at index dense(c))
 // bs.pred / bs.rated [C][I]; h_ebase[C + 1] = exclusive prefix of the slots' neighbour ratings
 void foldin_batch_predictions(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, int32_t take,
                               const int64_t* h_ebase, hipStream_t st, bool bystander = false);
-// (bystander: the chunk went through foldin_batch_neighbors with a ByChunk; neighbour index U gathers the newcomer's row)
+// (bystander: the chunk went through foldin_batch_neighbors with a ByChunk; the changer's index gathers its prepared row)
 void foldin_batch_pick(const Train& tr, QueryBatchScratch& bs, const int32_t* d_items, const int32_t* d_slot, int64_t m,
                        double* d_out, hipStream_t st);
 // KNNCF_PRED_PERSONALIZED instead of foldin_batch_predictions, after foldin_batch_neighbors(topk = false) on the chunk of n rows
@@ -461,9 +469,12 @@ void foldin_batch_reco_rows(QueryBatchScratch& bs, int32_t C, int32_t n, const i
 // ---- bystander.hip: what a newcomer adds to the slots of fitted users (knncf_query_bystander_*; DESIGN.md "Bystander queries")
 // the chunk's slot map, before any kernel of the chunk
 void bystander_upload(QueryBatchScratch& bs, int32_t C, const ByChunk& by, hipStream_t st);
-// after k_qb_write: S(v, q) per bystander slot, q into v's list, then bs.off and the neighbour ratings of bs.info (instead of
-// k_qb_offsets)
-void bystander_merge(const Train& tr, QueryBatchScratch& bs, int32_t C, int32_t take, hipStream_t st);
+// a chunk with fitted changers, after the similarity kernel and before the keys: S(v, c) per bystander slot, and that value
+// into cell dense(c) of the slot's row of bs.sim where c is of the fit
+void bystander_place(const Train& tr, QueryBatchScratch& bs, int32_t C, hipStream_t st);
+// after k_qb_write: S(v, q) per bystander slot (placed: bystander_place computed it), a newcomer q into v's list, a fitted one
+// looked up in it, then bs.off and the neighbour ratings of bs.info (instead of k_qb_offsets)
+void bystander_merge(const Train& tr, QueryBatchScratch& bs, int32_t C, int32_t take, bool placed, hipStream_t st);
 // k_qb_gather's launch for such a chunk
 void bystander_gather(const Train& tr, QueryBatchScratch& bs, int32_t C, int32_t take, hipStream_t st);
 // foldin_batch_pick for rows of bystander slots: an item that only the newcomer rates has its one term

@@ -22,6 +22,7 @@
 //                                       bitmap with rank prefixes
 //   k_qb_transpose + k_query_sim_dual   (C >= QB_DUAL_MIN) every train row read once for the whole chunk, lane b = slot b
 //   k_query_sim per slot                (C <  QB_DUAL_MIN) one exact fp64 similarity per train user (one streaming pass of s_col)
+//   (bystander_place of bystander.hip)  (a bystander chunk with a changer of the fit) S(v, c) on aug over the train value
 //   fallback keys over [C][U] / sort 64 bits / stable sort by slot / k_qb_write   top-k (similarity desc, dense user asc);
 //                                       k_qb_mask_self keys a fitted user's own cell behind every other: (allUsers - u) :608
 //   k_qb_offsets / k_qb_gather / sort (slot * I + item, file row) / k_q_fold      the neighbours' ratings grouped by (item,
@@ -942,6 +943,8 @@ void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspac
         }
     }
     KN_HIP(hipGetLastError());
+    const bool placed = by && by->fitted > 0;
+    if (placed) bystander_place(tr, bs, C, st);
     if (topk) {  // (the Personalized mode has no neighbourhood cut: foldin_batch_fold_all reads bs.sim as it is)
         // top-k of every slot: (similarity desc, dense user asc)
         launch_fallback_keys((int32_t)((int64_t)C * U), bs.sim.p, bs.k64_a.p, bs.v32_a.p, st);
@@ -951,7 +954,7 @@ void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspac
             k_qb_write<<<(unsigned)ceil_div((int64_t)C * take, TPB), TPB, 0, st>>>(C, take, U, self, order, bs.sim.p, bs.nbr_idx.p,
                                                                                    bs.nbr_sim.p);
         }
-        if (by) bystander_merge(tr, bs, C, take, st);
+        if (by) bystander_merge(tr, bs, C, take, placed, st);
         else k_qb_offsets<<<C, ONE_BLOCK, 0, st>>>(take, U, self, bs.nbr_idx.p, tr.u_ptr.p, bs.off.p, info);
         KN_HIP(hipGetLastError());
     }

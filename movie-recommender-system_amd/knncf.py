@@ -134,6 +134,8 @@ EXPORTS = [
     "knncf_query_recommend_explain_batch", "knncf_update_recommend_explain_batch", "knncf_revise_recommend_explain_batch",
     "knncf_query_bystander_neighbors", "knncf_query_bystander_predict",
     "knncf_query_bystander_neighbors_batch", "knncf_query_bystander_predict_batch",
+    "knncf_update_bystander_neighbors", "knncf_update_bystander_predict",
+    "knncf_update_bystander_neighbors_batch", "knncf_update_bystander_predict_batch",
     "knncf_query_entered", "knncf_query_entered_batch",
     "knncf_predict_batch",
     "knncf_predict_batch_device", "knncf_mae", "knncf_mae_device", "knncf_mae_sweep", "knncf_mae_sweep_device", "knncf_shard_view_get",
@@ -245,14 +247,16 @@ def load_library():
                                            + terms[2:-1])
         f("recommend_explain_batch").argtypes = (f("recommend_batch").argtypes[:-4] + [C.c_int32, C.c_int32]
                                                  + f("recommend_batch").argtypes[-4:-1] + terms[2:-1] + [_i32p])
-    # bystander queries: the fold-in query, then its rows (a fitted user each; the predict forms: with an item)
-    L.knncf_query_bystander_neighbors.argtypes = [C.c_void_p, C.c_int32, _i32p, _f64p, C.c_int64, _i32p, C.c_int64, C.c_int32, _i32p,
-                                                  _f64p, _i32p]
-    L.knncf_query_bystander_predict.argtypes = [C.c_void_p, C.c_int, C.c_int32, _i32p, _f64p, C.c_int64, _i32p, _i32p, C.c_int64, _f64p]
-    L.knncf_query_bystander_neighbors_batch.argtypes = [C.c_void_p, _i32p, _i64p, _i32p, _f64p, C.c_int64, _i64p, _i32p, C.c_int32,
-                                                        _i32p, _f64p, _i32p, _i32p]
-    L.knncf_query_bystander_predict_batch.argtypes = [C.c_void_p, C.c_int, _i32p, _i64p, _i32p, _f64p, C.c_int64, _i64p, _i32p, _i32p,
-                                                      _f64p, _i32p]
+    # bystander queries: the fold-in or update query, then its rows (a fitted user each; the predict forms: with an item)
+    for fam in ("query", "update"):
+        getattr(L, f"knncf_{fam}_bystander_neighbors").argtypes = [C.c_void_p, C.c_int32, _i32p, _f64p, C.c_int64, _i32p, C.c_int64,
+                                                                  C.c_int32, _i32p, _f64p, _i32p]
+        getattr(L, f"knncf_{fam}_bystander_predict").argtypes = [C.c_void_p, C.c_int, C.c_int32, _i32p, _f64p, C.c_int64, _i32p, _i32p,
+                                                                C.c_int64, _f64p]
+        getattr(L, f"knncf_{fam}_bystander_neighbors_batch").argtypes = [C.c_void_p, _i32p, _i64p, _i32p, _f64p, C.c_int64, _i64p, _i32p,
+                                                                        C.c_int32, _i32p, _f64p, _i32p, _i32p]
+        getattr(L, f"knncf_{fam}_bystander_predict_batch").argtypes = [C.c_void_p, C.c_int, _i32p, _i64p, _i32p, _f64p, C.c_int64, _i64p,
+                                                                      _i32p, _i32p, _f64p, _i32p]
     # entered queries: the fold-in query, cap, then users / sims / positions / displaced and the count(s)
     L.knncf_query_entered.argtypes = [C.c_void_p, C.c_int32, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p, _i32p, _i32p]
     L.knncf_query_entered_batch.argtypes = [C.c_void_p, _i32p, _i64p, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p, _i32p,
@@ -1127,8 +1131,9 @@ class Engine:
 
 
 class BystanderQueries:
-    """Bystander queries (knncf_query_bystander_*) on a fitted Engine: a FITTED user's kNN answers once the user of a fold-in query
-    has joined the data, without a refit.  A query is (user, items, ratings) as Engine.neighbors_for takes it; a row names the
+    """Bystander queries (knncf_query_bystander_*, knncf_update_bystander_*) on a fitted Engine: a FITTED user's kNN answers once
+    the user of a fold-in query has joined the data (*_for), or a user that may be in the fit has added ratings (*_with), without
+    a refit.  A query is (user, items, ratings) as Engine.neighbors_for takes it; a row names the
     fitted user (`others`), the predict forms an item beside it (`pred_items`).  Read-only on the engine's handle: the
     neighbour lists and their build history stay as they were.
 
@@ -1177,36 +1182,34 @@ class BystanderQueries:
             raise ValueError("others and pred_items must be of the same length")
         return roff, cat(oth), cat(pis)
 
-    def neighbors_for(self, user, items, ratings, others, cap=None):
-        """getNeighbors(train ++ user's ratings, k, sim)(v) for every v of `others`, fitted users (or unknown ids) other than the
-        newcomer `user`: [(ids, sims)] per row; the newcomer's own id where it is a neighbour"""
-        q, it, rt = self._e._query_rows(user, items, ratings)
+    def _fn(self, fam, name):
+        return getattr(self._e._lib, f"knncf_{fam}_bystander_{name}")
+
+    def _neighbors(self, fam, user, items, ratings, others, cap):
+        q, it, rt = self._e._query_rows(user, items, ratings, allow_empty=fam == "update")
         oth = self._row_ids(others, "others")
         cap, m = self._row_cap(cap, self._e.k), len(oth)
         ids = np.empty((m, cap), dtype=np.int32)
         sims = np.empty((m, cap), dtype=np.float64)
         counts = np.zeros(m, dtype=np.int32)
         p = self._e._ptr
-        self._e._check(self._e._lib.knncf_query_bystander_neighbors(self._e._h, q, p(it, _i32p), p(rt, _f64p), len(it), p(oth, _i32p), m, cap,
-                                                              p(ids.reshape(-1), _i32p), p(sims.reshape(-1), _f64p), p(counts, _i32p)))
+        self._e._check(self._fn(fam, "neighbors")(self._e._h, q, p(it, _i32p), p(rt, _f64p), len(it), p(oth, _i32p), m, cap,
+                                                  p(ids.reshape(-1), _i32p), p(sims.reshape(-1), _f64p), p(counts, _i32p)))
         return [(ids[r, :min(counts[r], cap)].copy(), sims[r, :min(counts[r], cap)].copy()) for r in range(m)]
 
-    def predict_for(self, user, items, ratings, others, pred_items):
-        """kNN predictions of (others[r], pred_items[r]) on train ++ user's ratings: a float64 array, one cell per row"""
-        q, it, rt = self._e._query_rows(user, items, ratings)
+    def _predict(self, fam, user, items, ratings, others, pred_items):
+        q, it, rt = self._e._query_rows(user, items, ratings, allow_empty=fam == "update")
         oth, pi = self._row_ids(others, "others"), self._row_ids(pred_items, "pred_items")
         if len(oth) != len(pi):
             raise ValueError("others and pred_items must be of the same length")
         out = np.full(len(oth), np.nan, dtype=np.float64)
         p = self._e._ptr
-        self._e._check(self._e._lib.knncf_query_bystander_predict(self._e._h, PRED_KNN, q, p(it, _i32p), p(rt, _f64p), len(it), p(oth, _i32p),
-                                                            p(pi, _i32p), len(oth), p(out, _f64p)))
+        self._e._check(self._fn(fam, "predict")(self._e._h, PRED_KNN, q, p(it, _i32p), p(rt, _f64p), len(it), p(oth, _i32p),
+                                                p(pi, _i32p), len(oth), p(out, _f64p)))
         return out
 
-    def neighbors_for_batch(self, queries, others, cap=None):
-        """neighbors_for of every (user, items, ratings) of `queries` with others[b] its rows:
-        ([[(ids, sims)] per row] per query, statuses int32 [B]).  A failed query's rows have empty arrays."""
-        qargs, keep = self._e._batch_args("query", queries)
+    def _neighbors_batch(self, fam, queries, others, cap):
+        qargs, keep = self._e._batch_args(fam, queries)
         B = qargs[-1]
         roff, oth, _ = self._rows(B, others, None)
         cap, m = self._row_cap(cap, self._e.k), int(roff[-1])
@@ -1215,24 +1218,59 @@ class BystanderQueries:
         counts = np.zeros(m, dtype=np.int32)
         st = np.zeros(B, dtype=np.int32)
         p = self._e._ptr
-        self._e._check(self._e._lib.knncf_query_bystander_neighbors_batch(
+        self._e._check(self._fn(fam, "neighbors_batch")(
             self._e._h, *qargs, p(roff, _i64p), p(oth, _i32p), cap, p(ids.reshape(-1), _i32p), p(sims.reshape(-1), _f64p),
             p(counts, _i32p), p(st, _i32p)))
         row = lambda r: (ids[r, :min(counts[r], cap)].copy(), sims[r, :min(counts[r], cap)].copy())
         return [[row(r) for r in range(roff[b], roff[b + 1])] for b in range(B)], st
 
-    def predict_for_batch(self, queries, others, pred_items):
-        """predict_for of every query; others / pred_items hold one sequence per query:
-        ([float64 array] per query, statuses).  A failed query's array holds NaN."""
-        qargs, keep = self._e._batch_args("query", queries)
+    def _predict_batch(self, fam, queries, others, pred_items):
+        qargs, keep = self._e._batch_args(fam, queries)
         B = qargs[-1]
         roff, oth, pi = self._rows(B, others, pred_items)
         out = np.full(int(roff[-1]), np.nan, dtype=np.float64)
         st = np.zeros(B, dtype=np.int32)
         p = self._e._ptr
-        self._e._check(self._e._lib.knncf_query_bystander_predict_batch(
+        self._e._check(self._fn(fam, "predict_batch")(
             self._e._h, PRED_KNN, *qargs, p(roff, _i64p), p(oth, _i32p), p(pi, _i32p), p(out, _f64p), p(st, _i32p)))
         return [out[roff[b]:roff[b + 1]].copy() for b in range(B)], st
+
+    def neighbors_for(self, user, items, ratings, others, cap=None):
+        """getNeighbors(train ++ user's ratings, k, sim)(v) for every v of `others`, fitted users (or unknown ids) other than the
+        newcomer `user`: [(ids, sims)] per row; the newcomer's own id where it is a neighbour"""
+        return self._neighbors("query", user, items, ratings, others, cap)
+
+    def predict_for(self, user, items, ratings, others, pred_items):
+        """kNN predictions of (others[r], pred_items[r]) on train ++ user's ratings: a float64 array, one cell per row"""
+        return self._predict("query", user, items, ratings, others, pred_items)
+
+    def neighbors_for_batch(self, queries, others, cap=None):
+        """neighbors_for of every (user, items, ratings) of `queries` with others[b] its rows:
+        ([[(ids, sims)] per row] per query, statuses int32 [B]).  A failed query's rows have empty arrays."""
+        return self._neighbors_batch("query", queries, others, cap)
+
+    def predict_for_batch(self, queries, others, pred_items):
+        """predict_for of every query; others / pred_items hold one sequence per query:
+        ([float64 array] per query, statuses).  A failed query's array holds NaN."""
+        return self._predict_batch("query", queries, others, pred_items)
+
+    # the same four for a `user` that may be in the fit (knncf_update_bystander_*): the given rows are ADDITIONAL to its train
+    # rows, as Engine.neighbors_with takes them, and may be empty for a fitted user
+    def neighbors_with(self, user, items, ratings, others, cap=None):
+        """getNeighbors(train ++ user's additional ratings, k, sim)(v) for every v of `others`: [(ids, sims)] per row"""
+        return self._neighbors("update", user, items, ratings, others, cap)
+
+    def predict_with(self, user, items, ratings, others, pred_items):
+        """kNN predictions of (others[r], pred_items[r]) on train ++ user's additional ratings: a float64 array"""
+        return self._predict("update", user, items, ratings, others, pred_items)
+
+    def neighbors_with_batch(self, queries, others, cap=None):
+        """neighbors_with of every query: ([[(ids, sims)] per row] per query, statuses)"""
+        return self._neighbors_batch("update", queries, others, cap)
+
+    def predict_with_batch(self, queries, others, pred_items):
+        """predict_with of every query: ([float64 array] per query, statuses)"""
+        return self._predict_batch("update", queries, others, pred_items)
 
 
 class EnteredQueries:
