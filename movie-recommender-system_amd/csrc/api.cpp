@@ -105,6 +105,8 @@ struct knncf_handle {
     std::vector<hipEvent_t> event_pool;
 };
 
+extern "C" { static void build_unbuilt_neighbors(knncf_handle* h); }  // (beside knncf_neighbors_batch, whose batch build it shares)
+
 namespace {
 
 hipEvent_t get_event(knncf_handle* h) {
@@ -1062,9 +1064,8 @@ constexpr int64_t QUERY_MAX_RATINGS = 65536;
 // that QB_EXPLAIN keeps refusing that predictor
 // QB_RECOMMEND_EXPLAIN: QB_RECOMMEND, then the explain kernel of the predictor over the rows the selection produced
 // (knncf_*_recommend_explain*): no requested rows, so neither explains() nor wants_rows()
-// QB_BY_NEIGHBORS / QB_BY_PREDICT: bystander queries (knncf_query_bystander_*) — the rows of a query name fitted users, and the
-// chunk loop is run_bystander_chunks
-// QB_ENTERED: entered queries (knncf_query_entered*) — no rows; the chunk loop is run_entered_chunks
+// QB_BY_NEIGHBORS / QB_BY_PREDICT: bystander queries (knncf_*_bystander_*) — a query's rows name fitted users; run_bystander_chunks
+// QB_ENTERED: entered queries (knncf_query_entered*) — no rows; an answer step of run_query_chunks (answer_entered)
 enum QueryBatchMode { QB_NEIGHBORS, QB_PREDICT, QB_RECOMMEND, QB_EXPLAIN, QB_EXPLAIN_ALL, QB_RECOMMEND_EXPLAIN, QB_BY_NEIGHBORS, QB_BY_PREDICT, QB_ENTERED };
 bool bystanders(QueryBatchMode mode) { return mode == QB_BY_NEIGHBORS || mode == QB_BY_PREDICT; }
 bool explains(QueryBatchMode mode) { return mode == QB_EXPLAIN || mode == QB_EXPLAIN_ALL; }
@@ -1143,8 +1144,11 @@ void explain_scatter(const ExplainCells& from, int64_t nr, const ExplainCells& t
 
 // ---- one request type for every family, mode and form ---------------------------------------------------------------------
 // A batch form fills users, B and the offsets arrays and leaves the last four fields 0.  A single form fills user, n_ratings,
-// n_removed and m instead and leaves users, B and the three offsets arrays 0: do_query_single makes them (a chunk of one); its
+// n_removed and m instead and leaves users, B and the three offsets arrays 0: BatchOfOne makes them (a chunk of one); its
 // counts is the caller's *count.
+// The bystander modes read their rows from pred_offsets (the calls' row_offsets; single: m) and others, QB_BY_PREDICT also from
+// pred_items, and answer per ROW: QB_BY_NEIGHBORS into out_i / out_d / row_counts with width = cap, QB_BY_PREDICT into out_d; counts
+// stays null.  QB_ENTERED has no rows and answers per QUERY into out_i / out_d / out_pos / out_displaced (width = cap) and counts.
 struct QueryCall {
     QueryFamily family;
     QueryBatchMode mode;
@@ -1195,13 +1199,32 @@ QueryCall explain_all_call(QueryCall rows, const ExplainCells& ex) {
     rows.mode = QB_EXPLAIN_ALL; rows.predictor = KNNCF_PRED_PERSONALIZED; rows.ex = ex;
     return rows;
 }
-QueryCall recommend_explain_call(QueryCall rows, int predictor, int32_t n, int32_t* out_items, double* out_preds, int32_t* counts,
-                                 const ExplainCells& ex) {
-    rows = recommend_call(rows, predictor, n, out_items, out_preds, counts);
-    rows.mode = QB_RECOMMEND_EXPLAIN; rows.ex = ex;
+// (reco: a recommend_call)
+QueryCall recommend_explain_call(QueryCall reco, const ExplainCells& ex) {
+    reco.mode = QB_RECOMMEND_EXPLAIN; reco.ex = ex;
+    return reco;
+}
+// (rows: with pred_offsets = the call's row_offsets, or m)
+QueryCall bystander_neighbors_call(QueryCall rows, const int32_t* others, int32_t cap, int32_t* ids, double* sims, int32_t* row_counts) {
+    rows.mode = QB_BY_NEIGHBORS; rows.predictor = KNNCF_PRED_KNN; rows.others = others; rows.width = cap;
+    rows.out_i = ids; rows.out_d = sims; rows.row_counts = row_counts;
+    return rows;
+}
+QueryCall bystander_predict_call(QueryCall rows, int predictor, const int32_t* others, double* out) {
+    rows.mode = QB_BY_PREDICT; rows.predictor = predictor; rows.others = others; rows.out_d = out;
+    return rows;
+}
+// (rows: with out_pos and out_displaced, which only this mode has)
+QueryCall entered_call(QueryCall rows, int32_t cap, int32_t* out_users, double* out_sims, int32_t* counts) {
+    rows.mode = QB_ENTERED; rows.predictor = KNNCF_PRED_KNN; rows.width = cap;
+    rows.out_i = out_users; rows.out_d = out_sims; rows.counts = counts;
     return rows;
 }
 bool wants_rows(QueryBatchMode mode) { return mode == QB_PREDICT || explains(mode); }
+// the modes that answer one count per query (the bystander modes count per row, the others have nothing to count)
+bool counts_queries(QueryBatchMode mode) { return !wants_rows(mode) && !bystanders(mode); }
+// whether the mode reads its slots' top-k lists (the Personalized fold has no cut, entered reads the similarity rows themselves)
+bool needs_topk(const QueryCall& q) { return q.predictor != KNNCF_PRED_PERSONALIZED && q.mode != QB_ENTERED; }
 // the modes that launch an explain kernel, and whether it is the Personalized one; their rows per launch (0: none)
 bool runs_explain(const QueryCall& q) { return explains(q.mode) || q.mode == QB_RECOMMEND_EXPLAIN; }
 bool explains_all(const QueryCall& q) {
@@ -1210,16 +1233,48 @@ bool explains_all(const QueryCall& q) {
 int64_t launch_rows(const QueryCall& q, int64_t budget) { return runs_explain(q) ? query_explain_rows(budget, q.ex.cap, explains_all(q)) : 0; }
 
 // ---- the chunk loop ---------------------------------------------------------------------------------------------------------
+// one slot as admit() or the bystander loop describes it: the query of the call, the raw user and its dense index in the fit (-1
+// outside), its given rows q.items / q.ratings [a0, a1), the train items it drops q.removed_items [r0, r1), its rows in aug
+struct Slot {
+    int64_t query;
+    int32_t user, self;
+    int64_t a0, a1, r0, r1, rows;
+};
 // what one call's chunks share: the host vectors are reused from chunk to chunk
 struct ChunkState {
     QueryFailure first;
-    int32_t take = 0, C = 0;  // min(k, U); pack_chunk: the chunk's C answerable queries, slot after slot
+    int32_t take = 0, C = 0;  // min(k, U); the chunk's C slots
     std::vector<int64_t> slot_query, qo, ao, ro;
     std::vector<int32_t> s_users, s_items, s_self, s_removed;
     std::vector<double> s_ratings;
+    void reset() {  // an empty chunk (first and take stay)
+        slot_query.clear(); s_users.clear(); s_items.clear(); s_ratings.clear(); s_self.clear(); s_removed.clear();
+        qo.assign(1, 0); ao.assign(1, 0); ro.assign(1, 0);
+        C = 0;
+    }
+    int32_t append(const QueryCall& q, const Slot& s) {  // one more slot; returns its index
+        if (s.r1 > s.r0) s_removed.insert(s_removed.end(), q.removed_items + s.r0, q.removed_items + s.r1);
+        ro.push_back((int64_t)s_removed.size());
+        slot_query.push_back(s.query);
+        s_users.push_back(s.user);
+        s_self.push_back(s.self);
+        if (s.a1 > s.a0) s_items.insert(s_items.end(), q.items + s.a0, q.items + s.a1);
+        if (s.a1 > s.a0) s_ratings.insert(s_ratings.end(), q.ratings + s.a0, q.ratings + s.a1);
+        ao.push_back((int64_t)s_items.size());
+        qo.push_back(qo.back() + s.rows);
+        return C++;
+    }
+    // as foldin_batch_neighbors takes it (a bystander chunk is an update chunk whatever the family: its bystander slots are)
+    QueryChunk chunk(const QueryCall& q, const ByChunk* by) const {
+        const bool update = q.family != QF_FOLD_IN || by, revise = q.family == QF_REVISE;
+        return {.C = C, .users = s_users.data(), .qo = qo.data(), .items = s_items.data(), .ratings = s_ratings.data(),
+                .self = update ? s_self.data() : nullptr, .ao = update ? ao.data() : nullptr, .ro = revise ? ro.data() : nullptr,
+                .removed = revise ? s_removed.data() : nullptr, .topk = needs_topk(q), .by = by};
+    }
     std::vector<long long> info;  // [4 C] of foldin_batch_neighbors
     std::vector<int32_t> good;    // settle_statuses: the slots whose query is KNNCF_OK
     std::vector<int64_t> ebase;   // [C + 1] of foldin_batch_predictions
+    std::vector<int32_t> qrank;   // [C] of entered_chunk
     // the answers on their way back
     std::vector<int32_t> h_idx, h_items, pick_slot, pick_items;
     std::vector<int64_t> pick_row, reco_rb;  // reco_rb: [C + 1] of foldin_batch_reco_rows
@@ -1233,35 +1288,35 @@ void fail(const QueryCall& q, ChunkState& cs, int64_t b, int status, const char*
     if (cs.first.query < 0 || b < cs.first.query) cs.first = {b, why};
 }
 
-// the per-query admission checks of queries [c0, c1) and the slots of those that pass; returns their number
-int32_t pack_chunk(knncf_handle* h, const QueryCall& q, ChunkState& cs, int64_t c0, int64_t c1) {
+// the per-query admission checks of query b: its slot, or false with the refusal recorded (fail)
+bool admit(knncf_handle* h, const QueryCall& q, ChunkState& cs, int64_t b, Slot& slot) {
     const bool update = q.family != QF_FOLD_IN, revise = q.family == QF_REVISE;
-    cs.slot_query.clear(); cs.s_users.clear(); cs.s_items.clear(); cs.s_ratings.clear(); cs.s_self.clear(); cs.s_removed.clear();
-    cs.qo.assign(1, 0); cs.ao.assign(1, 0); cs.ro.assign(1, 0);
-    for (int64_t b = c0; b < c1; ++b) {
-        const int64_t nb = q.offsets[b + 1] - q.offsets[b];
-        const int64_t nr = revise ? q.removed_offsets[b + 1] - q.removed_offsets[b] : 0;
-        const int32_t du = dense_user(h, q.users[b]);
-        // rows of the user in aug: its train rows (update queries) without the removed ones (revise queries), and the
-        // given ones; every train row is seeded, so all of them count against the cap
-        const int64_t seeded = nb + (update && du >= 0 ? train_row_length(h, du) : 0);
-        if (nr > 0 && du < 0) { fail(q, cs, b, KNNCF_E_INVALID, "a removed item for a user that is not in the training set"); continue; }
-        if (nr > seeded - nb) { fail(q, cs, b, KNNCF_E_INVALID, "more removed items than the user has train rows (one is not rated in train or listed twice)"); continue; }
-        const int64_t rows = seeded - nr;
-        if (rows <= 0) { fail(q, cs, b, KNNCF_E_INVALID, nr > 0 ? "the removals leave the user without a row" : "null ratings or n_ratings <= 0"); continue; }
-        if (seeded > QUERY_MAX_RATINGS) { fail(q, cs, b, KNNCF_E_UNSUPPORTED, "more than 65536 ratings"); continue; }
-        if (!update && du >= 0) { fail(q, cs, b, KNNCF_E_INVALID, "the user occurs in the training set"); continue; }
-        if (nr > 0) cs.s_removed.insert(cs.s_removed.end(), q.removed_items + q.removed_offsets[b], q.removed_items + q.removed_offsets[b + 1]);
-        cs.ro.push_back((int64_t)cs.s_removed.size());
-        cs.slot_query.push_back(b);
-        cs.s_users.push_back(q.users[b]);
-        cs.s_self.push_back(du);
-        cs.s_items.insert(cs.s_items.end(), q.items + q.offsets[b], q.items + q.offsets[b + 1]);
-        cs.s_ratings.insert(cs.s_ratings.end(), q.ratings + q.offsets[b], q.ratings + q.offsets[b + 1]);
-        cs.ao.push_back((int64_t)cs.s_items.size());
-        cs.qo.push_back(cs.qo.back() + rows);
-    }
-    return cs.C = (int32_t)cs.slot_query.size();
+    const int64_t nb = q.offsets[b + 1] - q.offsets[b];
+    const int64_t nr = revise ? q.removed_offsets[b + 1] - q.removed_offsets[b] : 0;
+    const int32_t du = dense_user(h, q.users[b]);
+    // rows of the user in aug: its train rows (update queries) without the removed ones (revise queries), and the
+    // given ones; every train row is seeded, so all of them count against the cap
+    const int64_t seeded = nb + (update && du >= 0 ? train_row_length(h, du) : 0);
+    const int64_t rows = seeded - nr;
+    int status = KNNCF_E_INVALID; const char* why = nullptr;
+    if (nr > 0 && du < 0) why = "a removed item for a user that is not in the training set";
+    else if (nr > seeded - nb) why = "more removed items than the user has train rows (one is not rated in train or listed twice)";
+    else if (rows <= 0) why = nr > 0 ? "the removals leave the user without a row" : "null ratings or n_ratings <= 0";
+    else if (seeded > QUERY_MAX_RATINGS) { status = KNNCF_E_UNSUPPORTED; why = "more than 65536 ratings"; }
+    else if (!update && du >= 0) why = "the user occurs in the training set";
+    if (why) { fail(q, cs, b, status, why); return false; }
+    slot = {.query = b, .user = q.users[b], .self = du, .a0 = q.offsets[b], .a1 = q.offsets[b + 1],
+            .r0 = nr > 0 ? q.removed_offsets[b] : 0, .r1 = nr > 0 ? q.removed_offsets[b + 1] : 0, .rows = rows};
+    return true;
+}
+
+// queries [c0, c1): the slots of those that admit() passes; returns their number
+int32_t pack_chunk(knncf_handle* h, const QueryCall& q, ChunkState& cs, int64_t c0, int64_t c1) {
+    cs.reset();
+    Slot slot;
+    for (int64_t b = c0; b < c1; ++b)
+        if (admit(h, q, cs, b, slot)) cs.append(q, slot);
+    return cs.C;
 }
 
 // the device's status bits of every slot as the query's status, in this order of precedence; cs.good = the slots left to
@@ -1281,14 +1336,44 @@ size_t settle_statuses(const QueryCall& q, ChunkState& cs) {
     return cs.good.size();
 }
 
+// what a bystander chunk has beside its slots (run_bystander_chunks packs it and answers its rows)
+constexpr int32_t BY_NO_SLOT = -1;
+struct ByRow {
+    int64_t row;   // of the call
+    int32_t slot;  // the bystander's slot in the chunk, or BY_NO_SLOT
+    int32_t own;   // the newcomer's slot in the chunk
+};
+struct ByChunkState {
+    std::vector<int32_t> qslot, qrank, qidx;  // qidx: the changer's index in a list, U for a newcomer (ByChunk)
+    std::vector<ByRow> rows;
+    int32_t fitted = 0, merged = 0;
+    void clear() { qslot.clear(); qrank.clear(); qidx.clear(); rows.clear(); fitted = merged = 0; }
+};
+
+// between packing and answering: the chunk (C > 0; bc: its bystander side, else null) through the neighbour pass and settle_statuses
+size_t settle_chunk(knncf_handle* h, const QueryCall& q, ChunkState& cs, const ByChunkState* bc) {
+    cs.info.assign((size_t)4 * cs.C, 0);
+    const ByChunk by = bc ? ByChunk{bc->qslot.data(), bc->qrank.data(), bc->qidx.data(), bc->fitted, bc->merged} : ByChunk{};
+    foldin_batch_neighbors(h->tr, h->query_batch, h->prep.sort, cs.chunk(q, bc ? &by : nullptr), h->cfg.k, cs.info.data(), h->stream);
+    // a bystander slot stands or falls with its newcomer: the slot's own bits (a negative mean of the bystander, which
+    // getNeighbors does not look at) are no status of the query
+    for (int32_t s = 0; bc && s < cs.C; ++s)
+        if (bc->qslot[s] != s) cs.info[4 * s] = cs.info[4 * bc->qslot[s]];
+    return settle_statuses(q, cs);
+}
+
+// bs.nbr_idx / bs.nbr_sim [C][take] into cs.h_idx / cs.h_vals (synchronised)
+void fetch_neighbor_lists(knncf_handle* h, ChunkState& cs) {
+    cs.h_idx.resize((size_t)cs.C * cs.take); cs.h_vals.resize((size_t)cs.C * cs.take);
+    KN_HIP(hipMemcpyAsync(cs.h_idx.data(), h->query_batch.nbr_idx.p, cs.h_idx.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    KN_HIP(hipMemcpyAsync(cs.h_vals.data(), h->query_batch.nbr_sim.p, cs.h_vals.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    KN_HIP(hipStreamSynchronize(h->stream));
+}
+
 void answer_neighbors(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
-    const QueryBatchScratch& bs = h->query_batch;
     const int32_t take = cs.take, width = q.width, c = std::min(take, width);
     if (c > 0) {
-        cs.h_idx.resize((size_t)cs.C * take); cs.h_vals.resize((size_t)cs.C * take);
-        KN_HIP(hipMemcpyAsync(cs.h_idx.data(), bs.nbr_idx.p, cs.h_idx.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        KN_HIP(hipMemcpyAsync(cs.h_vals.data(), bs.nbr_sim.p, cs.h_vals.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        KN_HIP(hipStreamSynchronize(h->stream));
+        fetch_neighbor_lists(h, cs);
         load_host_ids(h);
     }
     for (const int32_t s : cs.good) {
@@ -1315,10 +1400,29 @@ void fold_chunk(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
     foldin_batch_predictions(h->tr, h->query_batch, h->prep.sort, cs.C, cs.take, cs.ebase.data(), h->stream);
 }
 
-// QB_PREDICT and the explain modes: the requested rows of the chunk's good queries, (item, slot) each, folded and uploaded to
-// bs.pick_items / bs.pick_slot; explain modes: cs.pick_row = the row of the call behind each.  Returns their number m (0: nothing
-// was launched)
-int64_t upload_picks(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
+// the fold, then cs.pick_items / cs.pick_slot (m > 0 rows) uploaded to bs.pick_items / bs.pick_slot and, unless an explain kernel
+// answers them, through the mode's pick kernel into cs.h_vals [m] (synchronised)
+void answer_picks(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
+    fold_chunk(h, q, cs);
+    QueryBatchScratch& bs = h->query_batch;
+    hipStream_t st = h->stream;
+    const int64_t m = (int64_t)cs.pick_items.size();
+    bs.pick_items.ensure(m); bs.pick_slot.ensure(m);
+    if (!explains(q.mode)) bs.pick_out.ensure(m);
+    KN_HIP(hipMemcpyAsync(bs.pick_items.p, cs.pick_items.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    KN_HIP(hipMemcpyAsync(bs.pick_slot.p, cs.pick_slot.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (explains(q.mode)) return;
+    if (bystanders(q.mode)) bystander_pick(h->tr, bs, bs.pick_items.p, bs.pick_slot.p, m, bs.pick_out.p, st);
+    else if (q.predictor == KNNCF_PRED_PERSONALIZED) foldin_batch_pick_all(h->tr, bs, bs.pick_items.p, bs.pick_slot.p, m, bs.pick_out.p, st);
+    else foldin_batch_pick(h->tr, bs, bs.pick_items.p, bs.pick_slot.p, m, bs.pick_out.p, st);
+    cs.h_vals.resize((size_t)m);
+    KN_HIP(hipMemcpyAsync(cs.h_vals.data(), bs.pick_out.p, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
+    KN_HIP(hipStreamSynchronize(st));
+}
+
+// QB_PREDICT and the explain modes: the requested rows of the chunk's good queries, (item, slot) each, through answer_picks;
+// explain modes: cs.pick_row = the row of the call behind each.  Returns their number m (0: nothing was launched)
+int64_t pick_requested_rows(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
     cs.pick_slot.clear(); cs.pick_items.clear(); cs.pick_row.clear();
     for (const int32_t s : cs.good) {
         const int64_t b = cs.slot_query[s];
@@ -1328,26 +1432,12 @@ int64_t upload_picks(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
             for (int64_t j = q.pred_offsets[b]; j < q.pred_offsets[b + 1]; ++j) cs.pick_row.push_back(j);
     }
     const int64_t m = (int64_t)cs.pick_items.size();
-    if (m == 0) return 0;
-    fold_chunk(h, q, cs);
-    QueryBatchScratch& bs = h->query_batch;
-    bs.pick_items.ensure(m); bs.pick_slot.ensure(m);
-    if (q.mode == QB_PREDICT) bs.pick_out.ensure(m);
-    KN_HIP(hipMemcpyAsync(bs.pick_items.p, cs.pick_items.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    KN_HIP(hipMemcpyAsync(bs.pick_slot.p, cs.pick_slot.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    if (m > 0) answer_picks(h, q, cs);
     return m;
 }
 
 void answer_predict(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
-    const int64_t m = upload_picks(h, q, cs);
-    if (m == 0) return;
-    QueryBatchScratch& bs = h->query_batch;
-    hipStream_t st = h->stream;
-    if (q.predictor == KNNCF_PRED_PERSONALIZED) foldin_batch_pick_all(h->tr, bs, bs.pick_items.p, bs.pick_slot.p, m, bs.pick_out.p, st);
-    else foldin_batch_pick(h->tr, bs, bs.pick_items.p, bs.pick_slot.p, m, bs.pick_out.p, st);
-    cs.h_vals.resize((size_t)m);
-    KN_HIP(hipMemcpyAsync(cs.h_vals.data(), bs.pick_out.p, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
-    KN_HIP(hipStreamSynchronize(st));
+    if (pick_requested_rows(h, q, cs) == 0) return;
     int64_t at = 0;
     for (const int32_t s : cs.good) {
         const int64_t b = cs.slot_query[s];
@@ -1386,7 +1476,7 @@ void explain_picks(knncf_handle* h, const QueryCall& q, ChunkState& cs, int64_t 
 }
 
 void answer_explain(knncf_handle* h, const QueryCall& q, ChunkState& cs, int64_t ex_rows) {
-    const int64_t m = upload_picks(h, q, cs);
+    const int64_t m = pick_requested_rows(h, q, cs);
     if (m > 0) explain_picks(h, q, cs, m, ex_rows);
 }
 
@@ -1446,22 +1536,50 @@ void answer_recommend_explain(knncf_handle* h, const QueryCall& q, ChunkState& c
     write_recommendations(q, cs, widest);
 }
 
-// The validated queries of q in chunks of `chunk`: statuses[b] and, where it is KNNCF_OK, query b's answer in q's outputs.  A
-// refused query gets ex.counts = 0 on its rows (the explain modes, answered ex_rows rows per launch)
+// QB_ENTERED (entered.hip; knncf.h "Entered queries"): counts[b] and the first min(counts[b], cap) entered users of every good
+// query in row b of the four output arrays.  One copy back per chunk.
+void answer_entered(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
+    if (cs.take == 0) {  // (k <= 0: no list has a cell)
+        for (const int32_t s : cs.good) q.counts[cs.slot_query[s]] = 0;
+        return;
+    }
+    QueryBatchScratch& bs = h->query_batch;
+    hipStream_t st = h->stream;
+    const int32_t width = std::min(q.width, h->tr.U);
+    load_host_ids(h);
+    cs.qrank.resize((size_t)cs.C);
+    for (int32_t s = 0; s < cs.C; ++s) {
+        const uint32_t qkey = int_trie_key(cs.s_users[s]);
+        cs.qrank[s] = (int32_t)(std::lower_bound(h->h_ukeys.begin(), h->h_ukeys.end(), qkey) - h->h_ukeys.begin());
+    }
+    entered_chunk(h->tr, h->nt, bs, cs.C, cs.take, width, cs.qo.data(), cs.qrank.data(), st);
+    const size_t bytes = entered_pack_bytes(cs.C, width);
+    cs.h_vals.resize((bytes + 7) / 8);
+    KN_HIP(hipMemcpyAsync(cs.h_vals.data(), bs.en_pack.p, bytes, hipMemcpyDeviceToHost, st));
+    KN_HIP(hipStreamSynchronize(st));
+    const EnteredPack got = entered_pack(cs.h_vals.data(), cs.C, width);
+    for (const int32_t s : cs.good) {
+        const int64_t b = cs.slot_query[s];
+        const size_t at = (size_t)s * width, dst = (size_t)b * q.width;
+        const int64_t t = std::min<int64_t>(got.counts[s], width);
+        q.counts[b] = got.counts[s];
+        std::copy(got.users + at, got.users + at + t, q.out_i + dst);
+        std::copy(got.sims + at, got.sims + at + t, q.out_d + dst);
+        std::copy(got.pos + at, got.pos + at + t, q.out_pos + dst);
+        std::copy(got.displaced + at, got.displaced + at + t, q.out_displaced + dst);
+    }
+}
+
+// The validated queries of q in chunks of `chunk`, one slot per query: statuses[b] and, where it is KNNCF_OK, query b's answer
+// in q's outputs.  A refused query gets ex.counts = 0 on its rows (the explain modes, answered ex_rows rows per launch)
 QueryFailure run_query_chunks(knncf_handle* h, const QueryCall& q, int64_t chunk, int64_t ex_rows) {
     h->prep.join_commit(h->stream);
-    const bool update = q.family != QF_FOLD_IN, revise = q.family == QF_REVISE;
-    const bool personalized = q.predictor == KNNCF_PRED_PERSONALIZED;
-    if (personalized) ensure_personal_rows(h, false);
+    if (q.predictor == KNNCF_PRED_PERSONALIZED) ensure_personal_rows(h, false);
     ChunkState cs;
     cs.take = std::max(0, std::min(h->cfg.k, h->tr.U));
     for (int64_t c0 = 0; c0 < q.B; c0 += chunk) {
         if (pack_chunk(h, q, cs, c0, std::min(q.B, c0 + chunk)) == 0) continue;
-        cs.info.assign((size_t)4 * cs.C, 0);
-        foldin_batch_neighbors(h->tr, h->query_batch, h->prep.sort, cs.C, cs.s_users.data(), cs.qo.data(), cs.s_items.data(), cs.s_ratings.data(),
-                               update ? cs.s_self.data() : nullptr, update ? cs.ao.data() : nullptr, h->cfg.k, cs.info.data(), h->stream,
-                               revise ? cs.ro.data() : nullptr, revise ? cs.s_removed.data() : nullptr, !personalized);
-        if (settle_statuses(q, cs) == 0) continue;
+        if (settle_chunk(h, q, cs, nullptr) == 0) continue;
         switch (q.mode) {
             case QB_NEIGHBORS: answer_neighbors(h, q, cs); break;
             case QB_PREDICT: answer_predict(h, q, cs); break;
@@ -1469,11 +1587,153 @@ QueryFailure run_query_chunks(knncf_handle* h, const QueryCall& q, int64_t chunk
             case QB_EXPLAIN_ALL: answer_explain(h, q, cs, ex_rows); break;
             case QB_RECOMMEND: answer_recommend(h, q, cs); break;
             case QB_RECOMMEND_EXPLAIN: answer_recommend_explain(h, q, cs, ex_rows); break;
+            case QB_ENTERED: answer_entered(h, q, cs); break;
             case QB_BY_NEIGHBORS:
-            case QB_BY_PREDICT: break;  // (run_bystander_chunks answers these)
-            case QB_ENTERED: break;     // (run_entered_chunks)
+            case QB_BY_PREDICT: throw Error(KNNCF_E_INVALID, "query: a bystander mode in run_query_chunks (run_bystander_chunks answers them)");
         }
     }
+    return cs.first;
+}
+
+// ---- bystander queries: fitted users' answers on aug = train ++ a newcomer's rows (bystander.hip) ----------------------------
+// A query is a fold-in query (admit admits it, settle_statuses gives it its status); its rows name bystanders.  The unit
+// of a chunk is a slot: the newcomer's own, then one per distinct bystander that needs the device — a user of the fit, in
+// QB_BY_PREDICT with a mean >= 0.  The rows of the other bystanders are answered on the host once the query's status is known.
+// knncf_update_bystander_* run the same loop with family QF_UPDATE: the query is an update query, and where its user is of the
+// fit (a fitted CHANGER) its own slot is an update slot and no list takes a newcomer in (bystander.hip).
+
+// slots per chunk: the rule of knncf.h ("Bystander queries")
+int64_t bystander_chunk(knncf_handle* h, int64_t budget) { return std::max<int64_t>(2, query_batch_chunk(h, budget)); }
+
+// average(aug) :18: the fit's left fold of the train ratings, continued over query b's ratings in the given order
+double aug_average(knncf_handle* h, const QueryCall& q, int64_t b) {
+    double t = h->tr.total;
+    for (int64_t j = q.offsets[b]; j < q.offsets[b + 1]; ++j) t = t + q.ratings[j];
+    return t / (double)(h->tr.n + (q.offsets[b + 1] - q.offsets[b]));
+}
+
+// QB_BY_NEIGHBORS: the lists of the rows whose query is good
+void answer_bystander_neighbors(knncf_handle* h, const QueryCall& q, ChunkState& cs, const ByChunkState& bc) {
+    const int32_t U = h->tr.U, take = cs.take, width = q.width, c = std::min(take, width);
+    if (c > 0) fetch_neighbor_lists(h, cs);
+    for (const ByRow& r : bc.rows) {
+        if (q.statuses[cs.slot_query[r.own]] != KNNCF_OK) continue;
+        const bool fitted = cs.s_self[r.own] >= 0;  // the changer is a user of the fit: aug has the fit's users
+        const int32_t newcomer = cs.s_users[r.own], at = fitted ? U : bc.qrank[r.own];
+        int32_t* ids = q.out_i + r.row * width;
+        double* sims = q.out_d + r.row * width;
+        if (r.slot == BY_NO_SLOT) {  // unknown to aug: every similarity is 0.0, ties keep the set order of aug's users
+            const int32_t n = (int32_t)std::min<int64_t>(h->cfg.k, (int64_t)U + (fitted ? 0 : 1));
+            for (int32_t j = 0; j < std::min(n, width); ++j) {
+                ids[j] = j < at ? h->h_uid[j] : j == at ? newcomer : h->h_uid[j - 1];
+                sims[j] = 0.0;
+            }
+            q.row_counts[r.row] = std::max(n, 0);
+            continue;
+        }
+        const int32_t mine = fitted ? std::min(take, U - 1) : take;  // (a fitted changer is one of the U - 1 candidates)
+        for (int32_t j = 0; j < std::min(c, mine); ++j) {
+            const int32_t v = cs.h_idx[(size_t)r.slot * take + j];
+            ids[j] = v == U ? newcomer : h->h_uid[v];
+            sims[j] = cs.h_vals[(size_t)r.slot * take + j];
+        }
+        q.row_counts[r.row] = mine;
+    }
+}
+
+// QB_BY_PREDICT: the rows whose query is good — on the host where the bystander has no slot, else through answer_picks
+void answer_bystander_predict(knncf_handle* h, const QueryCall& q, ChunkState& cs, const ByChunkState& bc) {
+    cs.pick_slot.clear(); cs.pick_items.clear(); cs.pick_row.clear();
+    for (const ByRow& r : bc.rows) {
+        if (q.statuses[cs.slot_query[r.own]] != KNNCF_OK) continue;
+        if (r.slot == BY_NO_SLOT) {
+            q.out_d[r.row] = aug_average(h, q, cs.slot_query[r.own]);
+            continue;
+        }
+        cs.pick_items.push_back(q.pred_items[r.row]);
+        cs.pick_slot.push_back(r.slot);
+        cs.pick_row.push_back(r.row);
+    }
+    if (cs.pick_items.empty()) return;
+    answer_picks(h, q, cs);
+    for (size_t j = 0; j < cs.pick_row.size(); ++j) q.out_d[cs.pick_row[j]] = cs.h_vals[j];
+}
+
+// The validated queries of q in chunks of `chunk` >= 2 slots: statuses[b] and, where it is KNNCF_OK, the answers of query b's
+// rows.  (q.counts is null: fail() writes no per-query count; the rows' counts were zeroed by the caller.)  The packing is this
+// loop's own: a query takes a varying number of slots and may span chunks
+QueryFailure run_bystander_chunks(knncf_handle* h, const QueryCall& q, int64_t chunk) {
+    h->prep.join_commit(h->stream);
+    load_host_ids(h);
+    KN_REQUIRE(h->tr.n + QUERY_MAX_RATINGS < ((int64_t)1 << 32), KNNCF_E_UNSUPPORTED, "query bystander: the newcomer's file rows pass 2^32");
+    const bool predict = q.mode == QB_BY_PREDICT;
+    ChunkState cs;
+    ByChunkState bc;
+    std::vector<int32_t> dist, row_at;  // query b's distinct slot bystanders (dense) in order of appearance; per row its index or -1
+    std::vector<std::pair<int32_t, int32_t>> seen, firsts;  // (dense user, row) grouped by user; (first row, dense user)
+    cs.take = std::max(0, std::min(h->cfg.k, h->tr.U));
+    cs.reset();
+    auto flush = [&] {  // the chunk in cs / bc through the device, then the answers of its rows
+        if (cs.C > 0 && settle_chunk(h, q, cs, &bc) > 0)
+            q.mode == QB_BY_NEIGHBORS ? answer_bystander_neighbors(h, q, cs, bc) : answer_bystander_predict(h, q, cs, bc);
+        cs.reset(); bc.clear();
+    };
+    // one more slot of changer `own`'s (its own included): what the device reads beside the slot
+    auto append = [&](const Slot& slot, int32_t own, int32_t at, int32_t ci) {
+        bc.qslot.push_back(own); bc.qrank.push_back(at); bc.qidx.push_back(ci);
+        return cs.append(q, slot);
+    };
+    for (int64_t b = 0; b < q.B; ++b) {
+        const int64_t r0 = q.pred_offsets[b], r1 = q.pred_offsets[b + 1];
+        Slot mine;
+        if (!admit(h, q, cs, b, mine)) continue;
+        bool self_row = false, long_row = false;
+        dist.clear(); row_at.assign((size_t)(r1 - r0), -1); seen.clear(); firsts.clear();
+        for (int64_t r = r0; r < r1; ++r) {
+            if (q.others[r] == q.users[b]) { self_row = true; break; }
+            const int32_t dv = dense_user(h, q.others[r]);
+            if (dv < 0 || (predict && train_user_avg(h, dv) < 0.0)) continue;
+            if (train_row_length(h, dv) > QUERY_MAX_RATINGS) { long_row = true; break; }
+            seen.push_back({dv, (int32_t)(r - r0)});
+        }
+        if (self_row) { fail(q, cs, b, KNNCF_E_INVALID, "a row names the query's own user (ask the query's own predict call)"); continue; }
+        if (long_row) { fail(q, cs, b, KNNCF_E_UNSUPPORTED, "a bystander with more than 65536 ratings"); continue; }
+        std::stable_sort(seen.begin(), seen.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
+        // distinct bystanders, numbered in order of first appearance
+        for (size_t x = 0; x < seen.size(); ++x)
+            if (x == 0 || seen[x].first != seen[x - 1].first) firsts.push_back({seen[x].second, seen[x].first});
+        std::sort(firsts.begin(), firsts.end());
+        for (const auto& f : firsts) dist.push_back(f.second);
+        // (seen is grouped by user: one search per distinct bystander)
+        for (size_t x = 0, d = 0; x < seen.size(); ++x) {
+            if (x == 0 || seen[x].first != seen[x - 1].first) d = (size_t)(std::find(dist.begin(), dist.end(), seen[x].first) - dist.begin());
+            row_at[(size_t)seen[x].second] = (int32_t)d;
+        }
+        const uint32_t qkey = int_trie_key(q.users[b]);
+        const int32_t at = (int32_t)(std::lower_bound(h->h_ukeys.begin(), h->h_ukeys.end(), qkey) - h->h_ukeys.begin());
+        // the changer: a newcomer (index U in a list), or with knncf_update_bystander_* a user of the fit whose own slot is an
+        // update slot — its train rows seeded in front of the given ones.  (admit leaves no fold-in query with a user of the fit)
+        const int32_t dc = mine.self, ci = dc >= 0 ? dc : h->tr.U;
+        size_t pos = 0;
+        do {
+            if (chunk - cs.C < (dist.empty() ? 1 : 2)) flush();
+            const int32_t own = append(mine, cs.C, at, ci);
+            if (dc >= 0) ++bc.fitted;
+            const size_t cnt = std::min<size_t>(dist.size() - pos, (size_t)(chunk - cs.C));
+            for (size_t d = pos; d < pos + cnt; ++d) {
+                const int32_t dv = dist[d];  // (a fitted user without rows of the call)
+                append({.query = b, .user = h->h_uid[dv], .self = dv, .rows = train_row_length(h, dv)}, own, at, ci);
+                if (dc < 0) ++bc.merged;
+            }
+            for (int64_t r = r0; r < r1; ++r) {
+                const int32_t d = row_at[(size_t)(r - r0)];
+                if (d < 0) { if (pos == 0) bc.rows.push_back({r, BY_NO_SLOT, own}); }
+                else if ((size_t)d >= pos && (size_t)d < pos + cnt) bc.rows.push_back({r, own + 1 + (int32_t)((size_t)d - pos), own});
+            }
+            pos += cnt;
+        } while (pos < dist.size());
+    }
+    flush();
     return cs.first;
 }
 
@@ -1494,36 +1754,83 @@ void require_offsets(const int64_t* o, int64_t B, const char* no_start, const ch
     for (int64_t b = 0; b < B; ++b) KN_REQUIRE(o[b] <= o[b + 1], KNNCF_E_INVALID, decrease);
 }
 
-void do_query_batch(knncf_handle* h, const QueryCall& q) {
+// the first refused query as the call's error: thrown with the query's status by a single form (a batch of one), left in
+// knncf_last_error by a batch form, whose return value stays KNNCF_OK
+void report_failure(knncf_handle* h, const QueryCall& q, const QueryFailure& f, bool single) {
+    if (f.query < 0) return;
+    if (single) throw Error(q.statuses[0], std::string("query: ") + f.reason);
+    h->err = "query batch: query " + std::to_string(f.query) + ": " + f.reason;
+}
+
+// Every batch form, and the bystander and entered single forms as a batch of one (single: the texts say "query", and the
+// query's status is thrown as the call's).  The checks come in the order the call-level record pins
+void do_query_batch(knncf_handle* h, const QueryCall& q, bool single) {
     const int64_t B = q.B;
+    auto text = [&](const char* t) { return std::string(single ? "query: " : "query batch: ") + t; };
     require_fitted(h, false);
-    KN_REQUIRE(B >= 0, KNNCF_E_INVALID, "query batch: n_queries < 0");
-    KN_REQUIRE(wants_rows(q.mode) || q.width >= 0, KNNCF_E_INVALID, "query batch: cap or n < 0");
+    KN_REQUIRE(B >= 0, KNNCF_E_INVALID, text("n_queries < 0"));
+    KN_REQUIRE(wants_rows(q.mode) || q.mode == QB_BY_PREDICT || q.width >= 0, KNNCF_E_INVALID,
+               text(bystanders(q.mode) || q.mode == QB_ENTERED ? "cap < 0" : "cap or n < 0"));
     if (runs_explain(q)) require_explain_order(q.ex);
     require_query_support(h, q.predictor, q.mode);
+    KN_REQUIRE(q.mode != QB_ENTERED || h->cfg.similarity != KNNCF_SIM_COSINE || !has_short_rows(h), KNNCF_E_UNSUPPORTED,
+               "query entered with the adjusted cosine: a user with <= 4 ratings makes the reference's summation order depend on its memo history pair by pair (SURVEY N6); the stored lists are not the fresh-closure lists");
     if (B == 0) return;
-    KN_REQUIRE(q.users && q.offsets && q.statuses && (wants_rows(q.mode) || q.counts), KNNCF_E_INVALID, "query batch: null argument");
+    KN_REQUIRE(q.users && q.offsets && q.statuses && (!counts_queries(q.mode) || q.counts), KNNCF_E_INVALID, text("null argument"));
     require_offsets(q.offsets, B, "query batch: offsets[0] != 0", "query batch: offsets decrease");
-    KN_REQUIRE(q.offsets[B] < ((int64_t)1 << 31), KNNCF_E_INVALID, "query batch: 2^31 or more ratings in one call");
-    KN_REQUIRE(q.offsets[B] == 0 || (q.items && q.ratings), KNNCF_E_INVALID, "query batch: null ratings");
+    KN_REQUIRE(q.offsets[B] < ((int64_t)1 << 31), KNNCF_E_INVALID, text("2^31 or more ratings in one call"));
+    KN_REQUIRE(q.offsets[B] == 0 || (q.items && q.ratings), KNNCF_E_INVALID, text("null ratings"));
     if (q.family == QF_REVISE) {
         require_offsets(q.removed_offsets, B, "query batch: removed_offsets null or not starting at 0", "query batch: removed_offsets decrease");
         KN_REQUIRE(q.removed_offsets[B] < ((int64_t)1 << 31), KNNCF_E_INVALID, "query batch: 2^31 or more removed items in one call");
         KN_REQUIRE(q.removed_offsets[B] == 0 || q.removed_items, KNNCF_E_INVALID, "query batch: null removed items");
     }
-    if (wants_rows(q.mode)) {
+    if (bystanders(q.mode)) {
+        require_offsets(q.pred_offsets, B, "query batch: row_offsets null or not starting at 0", "query batch: row_offsets decrease");
+        const int64_t rows = q.pred_offsets[B];
+        KN_REQUIRE(rows < ((int64_t)1 << 31), KNNCF_E_INVALID, text("2^31 or more rows in one call"));
+        const bool outputs = q.mode == QB_BY_PREDICT ? q.pred_items && q.out_d : q.row_counts && (q.width == 0 || (q.out_i && q.out_d));
+        KN_REQUIRE(rows == 0 || (q.others && outputs), KNNCF_E_INVALID, text("null row arguments"));
+        if (q.mode == QB_BY_NEIGHBORS) std::fill(q.row_counts, q.row_counts + rows, 0);
+    } else if (wants_rows(q.mode)) {
         require_offsets(q.pred_offsets, B, "query batch: pred_offsets null or not starting at 0", "query batch: pred_offsets decrease");
         KN_REQUIRE(q.pred_offsets[B] == 0 || (q.pred_items && (explains(q.mode) || q.out_d)), KNNCF_E_INVALID,
                    "query batch: null prediction arguments");
         if (explains(q.mode)) require_explain_outputs(q.ex, q.pred_offsets[B]);
     } else {
-        KN_REQUIRE(q.width == 0 || (q.out_i && q.out_d), KNNCF_E_INVALID, "query batch: null output");
+        KN_REQUIRE(q.width == 0 || (q.out_i && q.out_d && (q.mode != QB_ENTERED || (q.out_pos && q.out_displaced))), KNNCF_E_INVALID,
+                   text("null output"));
         if (q.mode == QB_RECOMMEND_EXPLAIN) require_explain_outputs(q.ex, q.width);
     }
+    if (q.mode == QB_ENTERED) build_unbuilt_neighbors(h);  // (the place rule reads the handle's stored lists)
     const int64_t budget = batch_budget(h);  // (one hipMemGetInfo for both rules)
-    const QueryFailure f = run_query_chunks(h, q, query_batch_chunk(h, budget), launch_rows(q, budget));
-    if (f.query >= 0) h->err = "query batch: query " + std::to_string(f.query) + ": " + f.reason;
+    report_failure(h, q, bystanders(q.mode) ? run_bystander_chunks(h, q, bystander_chunk(h, budget))
+                                           : run_query_chunks(h, q, query_batch_chunk(h, budget), launch_rows(q, budget)), single);
 }
+
+// the rows a single form brings: a fold-in query needs some; an update query may come without (whether the user is in the fit
+// is the chunk loop's to say)
+void require_single_ratings(const QueryCall& call) {
+    if (call.family != QF_FOLD_IN) {
+        KN_REQUIRE(call.n_ratings >= 0 && (call.n_ratings == 0 || (call.items && call.ratings)), KNNCF_E_INVALID,
+                   "query: null ratings or n_ratings < 0");
+    } else {
+        KN_REQUIRE(call.items && call.ratings && call.n_ratings > 0, KNNCF_E_INVALID, "query: null ratings or n_ratings <= 0");
+    }
+}
+
+// a single form's call as a batch of one: q = the call with users, B, statuses and the offsets arrays made from its last four fields
+struct BatchOfOne {
+    int64_t offsets[2], pred_offsets[2], removed_offsets[2];
+    int32_t status = KNNCF_OK;
+    QueryCall q;
+    explicit BatchOfOne(const QueryCall& call)
+        : offsets{0, call.n_ratings}, pred_offsets{0, call.m}, removed_offsets{0, call.n_removed}, q(call) {
+        q.users = &q.user; q.B = 1; q.statuses = &status;
+        q.offsets = offsets; q.pred_offsets = pred_offsets; q.removed_offsets = removed_offsets;
+    }
+    BatchOfOne(const BatchOfOne&) = delete;  // (q points into this object)
+};
 
 // the single forms' own output arguments, checked in front of everything else (the explain forms check theirs after
 // require_fitted, in do_query_single); a recommend form's *count is 0 whatever fails later
@@ -1536,8 +1843,7 @@ void require_single_outputs(const QueryCall& q) {
 }
 
 // One query as a chunk of one: the query's status is the call's.  *count (neighbours: min(k, U), min(k, U - 1) for a user of
-// the fit; recommendations: min(n, I - known items)) is written on success.  An update query may come without rows (whether
-// the user is in the fit is the chunk loop's to say).
+// the fit; recommendations: min(n, I - known items)) is written on success.
 void do_query_single(knncf_handle* h, const QueryCall& call) {
     require_single_outputs(call);
     require_fitted(h, false);
@@ -1552,267 +1858,29 @@ void do_query_single(knncf_handle* h, const QueryCall& call) {
     }
     if (call.family == QF_REVISE)
         KN_REQUIRE(call.n_removed >= 0 && (call.n_removed == 0 || call.removed_items), KNNCF_E_INVALID, "query: null removed items or n_removed < 0");
-    if (call.family != QF_FOLD_IN) {
-        KN_REQUIRE(call.n_ratings >= 0 && (call.n_ratings == 0 || (call.items && call.ratings)), KNNCF_E_INVALID,
-                   "query: null ratings or n_ratings < 0");
-    } else {
-        KN_REQUIRE(call.items && call.ratings && call.n_ratings > 0, KNNCF_E_INVALID, "query: null ratings or n_ratings <= 0");
-    }
+    require_single_ratings(call);
     require_query_support(h, call.predictor, call.mode);
-    const int64_t offsets[2] = {0, call.n_ratings}, pred_offsets[2] = {0, call.m}, removed_offsets[2] = {0, call.n_removed};
-    int32_t status = KNNCF_OK, c = 0;
-    QueryCall q = call;
-    q.users = &call.user; q.B = 1; q.counts = &c; q.statuses = &status;
-    q.offsets = offsets; q.removed_offsets = removed_offsets; q.pred_offsets = pred_offsets;
-    const QueryFailure f = run_query_chunks(h, q, 1, runs_explain(q) ? launch_rows(q, batch_budget(h)) : 0);  // (no hipMemGetInfo otherwise)
-    if (f.query >= 0) throw Error(status, std::string("query: ") + f.reason);
+    BatchOfOne one(call);
+    int32_t c = 0; one.q.counts = &c;  // (the caller's *count is written on success only)
+    const int64_t ex_rows = runs_explain(call) ? launch_rows(call, batch_budget(h)) : 0;  // (no hipMemGetInfo otherwise)
+    report_failure(h, one.q, run_query_chunks(h, one.q, 1, ex_rows), true);
     if (call.counts) *call.counts = c;
 }
 
-int query_batch(knncf_handle* h, const QueryCall& q) { return guarded(h, [&] { do_query_batch(h, q); }); }
+int query_batch(knncf_handle* h, const QueryCall& q) { return guarded(h, [&] { do_query_batch(h, q, false); }); }
 int query_single(knncf_handle* h, const QueryCall& q) { return guarded(h, [&] { do_query_single(h, q); }); }
-
-// ---- bystander queries: fitted users' answers on aug = train ++ a newcomer's rows (bystander.hip) ----------------------------
-// A query is a fold-in query (pack_chunk admits it, settle_statuses gives it its status); its rows name bystanders.  The unit
-// of a chunk is a slot: the newcomer's own, then one per distinct bystander that needs the device — a user of the fit, in
-// QB_BY_PREDICT with a mean >= 0.  The rows of the other bystanders are answered on the host once the query's status is known.
-// knncf_update_bystander_* run the same loop with family QF_UPDATE: the query is an update query, and where its user is of the
-// fit (a fitted CHANGER) its own slot is an update slot and no list takes a newcomer in (bystander.hip).
-constexpr int32_t BY_NO_SLOT = -1;
-struct ByRow {
-    int64_t row;   // of the call
-    int32_t slot;  // the bystander's slot in the chunk, or BY_NO_SLOT
-    int32_t own;   // the newcomer's slot in the chunk
-};
-struct ByChunkState {
-    std::vector<int32_t> qslot, qrank, qidx;  // qidx: the changer's index in a list, U for a newcomer (ByChunk)
-    std::vector<ByRow> rows;
-    int32_t fitted = 0, merged = 0;
-    void clear() { qslot.clear(); qrank.clear(); qidx.clear(); rows.clear(); fitted = merged = 0; }
-};
-
-// slots per chunk: the rule of knncf.h ("Bystander queries")
-int64_t bystander_chunk(knncf_handle* h, int64_t budget) { return std::max<int64_t>(2, query_batch_chunk(h, budget)); }
-
-// average(aug) :18: the fit's left fold of the train ratings, continued over query b's ratings in the given order
-double aug_average(knncf_handle* h, const QueryCall& q, int64_t b) {
-    double t = h->tr.total;
-    for (int64_t j = q.offsets[b]; j < q.offsets[b + 1]; ++j) t = t + q.ratings[j];
-    return t / (double)(h->tr.n + (q.offsets[b + 1] - q.offsets[b]));
-}
-
-// the chunk in cs / bc through the device, then the answers of its rows
-void answer_bystander_chunk(knncf_handle* h, const QueryCall& q, ChunkState& cs, ByChunkState& bc) {
-    if (cs.C == 0) return;
-    QueryBatchScratch& bs = h->query_batch;
-    hipStream_t st = h->stream;
-    const int32_t U = h->tr.U, take = cs.take;
-    cs.info.assign((size_t)4 * cs.C, 0);
-    const ByChunk by{bc.qslot.data(), bc.qrank.data(), bc.qidx.data(), bc.fitted, bc.merged};
-    foldin_batch_neighbors(h->tr, bs, h->prep.sort, cs.C, cs.s_users.data(), cs.qo.data(), cs.s_items.data(), cs.s_ratings.data(),
-                           cs.s_self.data(), cs.ao.data(), h->cfg.k, cs.info.data(), st, nullptr, nullptr, true, &by);
-    // a bystander slot stands or falls with its newcomer: the slot's own bits (a negative mean of the bystander, which
-    // getNeighbors does not look at) are no status of the query
-    for (int32_t s = 0; s < cs.C; ++s)
-        if (bc.qslot[s] != s) cs.info[4 * s] = cs.info[4 * bc.qslot[s]];
-    if (settle_statuses(q, cs) == 0) return;
-    auto good = [&](const ByRow& r) { return q.statuses[cs.slot_query[r.own]] == KNNCF_OK; };
-    if (q.mode == QB_BY_NEIGHBORS) {
-        const int32_t width = q.width, c = std::min(take, width);
-        if (c > 0) {
-            cs.h_idx.resize((size_t)cs.C * take); cs.h_vals.resize((size_t)cs.C * take);
-            KN_HIP(hipMemcpyAsync(cs.h_idx.data(), bs.nbr_idx.p, cs.h_idx.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            KN_HIP(hipMemcpyAsync(cs.h_vals.data(), bs.nbr_sim.p, cs.h_vals.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-            KN_HIP(hipStreamSynchronize(st));
-        }
-        for (const ByRow& r : bc.rows) {
-            if (!good(r)) continue;
-            const bool fitted = cs.s_self[r.own] >= 0;  // the changer is a user of the fit: aug has the fit's users
-            const int32_t newcomer = cs.s_users[r.own], at = fitted ? U : bc.qrank[r.own];
-            int32_t* ids = q.out_i + r.row * width;
-            double* sims = q.out_d + r.row * width;
-            if (r.slot == BY_NO_SLOT) {  // unknown to aug: every similarity is 0.0, ties keep the set order of aug's users
-                const int32_t n = (int32_t)std::min<int64_t>(h->cfg.k, (int64_t)U + (fitted ? 0 : 1));
-                for (int32_t j = 0; j < std::min(n, width); ++j) {
-                    ids[j] = j < at ? h->h_uid[j] : j == at ? newcomer : h->h_uid[j - 1];
-                    sims[j] = 0.0;
-                }
-                q.row_counts[r.row] = std::max(n, 0);
-                continue;
-            }
-            const int32_t mine = fitted ? std::min(take, U - 1) : take;  // (a fitted changer is one of the U - 1 candidates)
-            for (int32_t j = 0; j < std::min(c, mine); ++j) {
-                const int32_t v = cs.h_idx[(size_t)r.slot * take + j];
-                ids[j] = v == U ? newcomer : h->h_uid[v];
-                sims[j] = cs.h_vals[(size_t)r.slot * take + j];
-            }
-            q.row_counts[r.row] = mine;
-        }
-        return;
-    }
-    cs.pick_slot.clear(); cs.pick_items.clear(); cs.pick_row.clear();
-    for (const ByRow& r : bc.rows) {
-        if (!good(r)) continue;
-        if (r.slot == BY_NO_SLOT) {
-            q.out_d[r.row] = aug_average(h, q, cs.slot_query[r.own]);
-            continue;
-        }
-        cs.pick_items.push_back(q.pred_items[r.row]);
-        cs.pick_slot.push_back(r.slot);
-        cs.pick_row.push_back(r.row);
-    }
-    const int64_t m = (int64_t)cs.pick_items.size();
-    if (m == 0) return;
-    cs.ebase.assign((size_t)cs.C + 1, 0);
-    for (int32_t s = 0; s < cs.C; ++s) cs.ebase[s + 1] = cs.ebase[s] + cs.info[4 * s + 2];
-    foldin_batch_predictions(h->tr, bs, h->prep.sort, cs.C, take, cs.ebase.data(), st, true);
-    bs.pick_items.ensure(m); bs.pick_slot.ensure(m); bs.pick_out.ensure(m);
-    KN_HIP(hipMemcpyAsync(bs.pick_items.p, cs.pick_items.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    KN_HIP(hipMemcpyAsync(bs.pick_slot.p, cs.pick_slot.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    bystander_pick(h->tr, bs, bs.pick_items.p, bs.pick_slot.p, m, bs.pick_out.p, st);
-    cs.h_vals.resize((size_t)m);
-    KN_HIP(hipMemcpyAsync(cs.h_vals.data(), bs.pick_out.p, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
-    KN_HIP(hipStreamSynchronize(st));
-    for (int64_t j = 0; j < m; ++j) q.out_d[cs.pick_row[j]] = cs.h_vals[(size_t)j];
-}
-
-// The validated queries of q in chunks of `chunk` >= 2 slots: statuses[b] and, where it is KNNCF_OK, the answers of query b's
-// rows.  (q.counts is null: fail() writes no per-query count; the rows' counts were zeroed by the caller.)
-QueryFailure run_bystander_chunks(knncf_handle* h, const QueryCall& q, int64_t chunk) {
-    h->prep.join_commit(h->stream);
-    load_host_ids(h);
-    KN_REQUIRE(h->tr.n + QUERY_MAX_RATINGS < ((int64_t)1 << 32), KNNCF_E_UNSUPPORTED, "query bystander: the newcomer's file rows pass 2^32");
-    const bool predict = q.mode == QB_BY_PREDICT;
-    ChunkState cs, one;  // one: pack_chunk's admission of a single query
-    ByChunkState bc;
-    cs.take = std::max(0, std::min(h->cfg.k, h->tr.U));
-    cs.qo.assign(1, 0); cs.ao.assign(1, 0);
-    auto flush = [&] {
-        answer_bystander_chunk(h, q, cs, bc);
-        cs.slot_query.clear(); cs.s_users.clear(); cs.s_items.clear(); cs.s_ratings.clear(); cs.s_self.clear();
-        cs.qo.assign(1, 0); cs.ao.assign(1, 0);
-        cs.C = 0;
-        bc.clear();
-    };
-    auto refuse = [&](int64_t b, int status, const char* why) {
-        fail(q, one, b, status, why);
-    };
-    std::vector<int32_t> dist, row_at;  // query b's distinct slot bystanders (dense) in order of appearance; per row its index or -1
-    std::vector<std::pair<int32_t, int32_t>> seen;
-    for (int64_t b = 0; b < q.B; ++b) {
-        const int64_t r0 = q.pred_offsets[b], r1 = q.pred_offsets[b + 1];
-        if (pack_chunk(h, q, one, b, b + 1) == 0) continue;
-        bool self_row = false, long_row = false;
-        dist.clear(); row_at.assign((size_t)(r1 - r0), -1); seen.clear();
-        for (int64_t r = r0; r < r1; ++r) {
-            if (q.others[r] == q.users[b]) { self_row = true; break; }
-            const int32_t dv = dense_user(h, q.others[r]);
-            if (dv < 0 || (predict && train_user_avg(h, dv) < 0.0)) continue;
-            if (train_row_length(h, dv) > QUERY_MAX_RATINGS) { long_row = true; break; }
-            seen.push_back({dv, (int32_t)(r - r0)});
-        }
-        if (self_row) { refuse(b, KNNCF_E_INVALID, "a row names the query's own user (ask the query's own predict call)"); continue; }
-        if (long_row) { refuse(b, KNNCF_E_UNSUPPORTED, "a bystander with more than 65536 ratings"); continue; }
-        std::stable_sort(seen.begin(), seen.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
-        // distinct bystanders, numbered in order of first appearance
-        std::vector<std::pair<int32_t, int32_t>> firsts;  // (first row, dense user)
-        for (size_t x = 0; x < seen.size(); ++x)
-            if (x == 0 || seen[x].first != seen[x - 1].first) firsts.push_back({seen[x].second, seen[x].first});
-        std::sort(firsts.begin(), firsts.end());
-        for (const auto& f : firsts) dist.push_back(f.second);
-        // (seen is grouped by user: one search per distinct bystander)
-        for (size_t x = 0, d = 0; x < seen.size(); ++x) {
-            if (x == 0 || seen[x].first != seen[x - 1].first) d = (size_t)(std::find(dist.begin(), dist.end(), seen[x].first) - dist.begin());
-            row_at[(size_t)seen[x].second] = (int32_t)d;
-        }
-        const uint32_t qkey = int_trie_key(q.users[b]);
-        const int32_t at = (int32_t)(std::lower_bound(h->h_ukeys.begin(), h->h_ukeys.end(), qkey) - h->h_ukeys.begin());
-        // the changer: a newcomer (index U in a list), or with knncf_update_bystander_* a user of the fit whose own slot is an
-        // update slot — its train rows seeded in front of the given ones
-        const int32_t dc = q.family == QF_FOLD_IN ? -1 : one.s_self[0];
-        const int32_t ci = dc >= 0 ? dc : h->tr.U;
-        size_t pos = 0;
-        do {
-            if (chunk - cs.C < (dist.empty() ? 1 : 2)) flush();
-            const int32_t own = cs.C;
-            cs.slot_query.push_back(b);
-            cs.s_users.push_back(q.users[b]);
-            cs.s_self.push_back(dc);
-            if (q.offsets[b + 1] > q.offsets[b]) {
-                cs.s_items.insert(cs.s_items.end(), q.items + q.offsets[b], q.items + q.offsets[b + 1]);
-                cs.s_ratings.insert(cs.s_ratings.end(), q.ratings + q.offsets[b], q.ratings + q.offsets[b + 1]);
-            }
-            cs.ao.push_back((int64_t)cs.s_items.size());
-            cs.qo.push_back(cs.qo.back() + (q.offsets[b + 1] - q.offsets[b]) + (dc >= 0 ? train_row_length(h, dc) : 0));
-            bc.qslot.push_back(own); bc.qrank.push_back(at); bc.qidx.push_back(ci);
-            if (dc >= 0) ++bc.fitted;
-            ++cs.C;
-            const size_t cnt = std::min<size_t>(dist.size() - pos, (size_t)(chunk - cs.C));
-            for (size_t d = pos; d < pos + cnt; ++d) {
-                cs.slot_query.push_back(b);
-                cs.s_users.push_back(h->h_uid[dist[d]]);
-                cs.s_self.push_back(dist[d]);
-                cs.ao.push_back(cs.ao.back());
-                cs.qo.push_back(cs.qo.back() + train_row_length(h, dist[d]));
-                bc.qslot.push_back(own); bc.qrank.push_back(at); bc.qidx.push_back(ci);
-                if (dc < 0) ++bc.merged;
-                ++cs.C;
-            }
-            for (int64_t r = r0; r < r1; ++r) {
-                const int32_t d = row_at[(size_t)(r - r0)];
-                if (d < 0) { if (pos == 0) bc.rows.push_back({r, BY_NO_SLOT, own}); }
-                else if ((size_t)d >= pos && (size_t)d < pos + cnt) bc.rows.push_back({r, own + 1 + (int32_t)((size_t)d - pos), own});
-            }
-            pos += cnt;
-        } while (pos < dist.size());
-    }
-    flush();
-    if (one.first.query >= 0 && (cs.first.query < 0 || one.first.query < cs.first.query)) cs.first = one.first;
-    return cs.first;
-}
-
-// batch forms, and the single forms as a batch of one (single: the query's status is thrown as the call's)
-void do_bystander_batch(knncf_handle* h, QueryCall q, bool single) {
-    const char* what = single ? "query" : "query batch";
-    auto text = [&](const char* t) { return std::string(what) + ": " + t; };
-    require_fitted(h, false);
-    KN_REQUIRE(q.B >= 0, KNNCF_E_INVALID, text("n_queries < 0"));
-    KN_REQUIRE(q.mode != QB_BY_NEIGHBORS || q.width >= 0, KNNCF_E_INVALID, text("cap < 0"));
-    require_query_support(h, q.predictor, q.mode);
-    if (q.B == 0) return;
-    KN_REQUIRE(q.users && q.offsets && q.statuses, KNNCF_E_INVALID, text("null argument"));
-    require_offsets(q.offsets, q.B, "query batch: offsets[0] != 0", "query batch: offsets decrease");
-    KN_REQUIRE(q.offsets[q.B] < ((int64_t)1 << 31), KNNCF_E_INVALID, text("2^31 or more ratings in one call"));
-    KN_REQUIRE(q.offsets[q.B] == 0 || (q.items && q.ratings), KNNCF_E_INVALID, text("null ratings"));
-    require_offsets(q.pred_offsets, q.B, "query batch: row_offsets null or not starting at 0", "query batch: row_offsets decrease");
-    const int64_t rows = q.pred_offsets[q.B];
-    KN_REQUIRE(rows < ((int64_t)1 << 31), KNNCF_E_INVALID, text("2^31 or more rows in one call"));
-    if (q.mode == QB_BY_PREDICT) {
-        KN_REQUIRE(rows == 0 || (q.others && q.pred_items && q.out_d), KNNCF_E_INVALID, text("null row arguments"));
-    } else {
-        KN_REQUIRE(rows == 0 || (q.others && q.row_counts && (q.width == 0 || (q.out_i && q.out_d))), KNNCF_E_INVALID, text("null row arguments"));
-        std::fill(q.row_counts, q.row_counts + rows, 0);
-    }
-    const QueryFailure f = run_bystander_chunks(h, q, bystander_chunk(h, batch_budget(h)));
-    if (f.query < 0) return;
-    if (single) throw Error(q.statuses[0], std::string("query: ") + f.reason);
-    h->err = "query batch: query " + std::to_string(f.query) + ": " + f.reason;
-}
-
-int bystander_batch(knncf_handle* h, const QueryCall& q) { return guarded(h, [&] { do_bystander_batch(h, q, false); }); }
-int bystander_single(knncf_handle* h, QueryCall q, int64_t n_ratings, int64_t m) {
+// the bystander and entered single forms: their own arguments' checks (an entered call's *count is 0 once they pass), then the batch of one
+int rows_single(knncf_handle* h, const QueryCall& call) {
     return guarded(h, [&] {
         require_fitted(h, false);
-        if (q.family == QF_FOLD_IN) {
-            KN_REQUIRE(n_ratings > 0 && q.items && q.ratings, KNNCF_E_INVALID, "query: null ratings or n_ratings <= 0");
-        } else {  // (an update query may come without rows: whether the user is in the fit is the chunk loop's to say)
-            KN_REQUIRE(n_ratings >= 0 && (n_ratings == 0 || (q.items && q.ratings)), KNNCF_E_INVALID, "query: null ratings or n_ratings < 0");
-        }
-        KN_REQUIRE(m >= 0, KNNCF_E_INVALID, "query: m < 0");
-        const int64_t offsets[2] = {0, n_ratings}, row_offsets[2] = {0, m};
-        int32_t status = KNNCF_OK;
-        q.users = &q.user; q.B = 1; q.offsets = offsets; q.pred_offsets = row_offsets; q.statuses = &status;
-        do_bystander_batch(h, q, true);
+        if (call.mode == QB_ENTERED)
+            KN_REQUIRE(call.counts && call.width >= 0 && (call.width == 0 || (call.out_i && call.out_d && call.out_pos && call.out_displaced)),
+                       KNNCF_E_INVALID, "bad output arguments");
+        require_single_ratings(call);
+        KN_REQUIRE(call.m >= 0, KNNCF_E_INVALID, "query: m < 0");
+        if (call.mode == QB_ENTERED) *call.counts = 0;
+        BatchOfOne one(call);
+        do_query_batch(h, one.q, true);
     });
 }
 
@@ -2232,10 +2300,9 @@ int knncf_neighbors_batch(knncf_handle* h, const int32_t* users, int64_t n, int3
     return guarded(h, [&] { do_neighbors_batch(h, users, n, cap, ids, sims, counts); });
 }
 
-// ---- entered queries: the fitted users whose neighbour lists a newcomer joins (entered.hip; knncf.h "Entered queries") --------
-// A query is a fold-in query (pack_chunk admits it, settle_statuses gives it its status), one slot each.  The place rule reads
-// the handle's stored lists, so the call first builds the lists that are missing: M = the train users without one in ascending
-// raw id, in ONE batch numbered (call, position in M) — the state knncf_neighbors_batch over M leaves.
+// entered queries (knncf.h "Entered queries"): the place rule reads the handle's stored lists, so the call first builds the lists
+// that are missing: M = the train users without one in ascending raw id, in ONE batch numbered (call, position in M) — the state
+// knncf_neighbors_batch over M leaves.
 static void build_unbuilt_neighbors(knncf_handle* h) {
     Train& tr = h->tr;
     if (tr.U < 2 || h->nt.kcap <= 0) return;
@@ -2249,101 +2316,6 @@ static void build_unbuilt_neighbors(knncf_handle* h) {
     if (M.empty()) return;
     std::sort(M.begin(), M.end(), [&](int32_t a, int32_t b) { return h->h_uid[a] < h->h_uid[b]; });
     build_missing_neighbors(h, M);
-}
-
-// The validated queries of q in chunks of `chunk` slots: statuses[b], counts[b] and, where the status is KNNCF_OK, the first
-// min(counts[b], cap) entered users of query b in row b of the four output arrays.  One copy back per chunk.
-static QueryFailure run_entered_chunks(knncf_handle* h, const QueryCall& q, int64_t chunk) {
-    h->prep.join_commit(h->stream);
-    load_host_ids(h);
-    QueryBatchScratch& bs = h->query_batch;
-    hipStream_t st = h->stream;
-    ChunkState cs;
-    cs.take = std::max(0, std::min(h->cfg.k, h->tr.U));
-    const int32_t width = std::min(q.width, h->tr.U);
-    std::vector<int32_t> qrank;
-    for (int64_t c0 = 0; c0 < q.B; c0 += chunk) {
-        if (pack_chunk(h, q, cs, c0, std::min(q.B, c0 + chunk)) == 0) continue;
-        cs.info.assign((size_t)4 * cs.C, 0);
-        foldin_batch_neighbors(h->tr, bs, h->prep.sort, cs.C, cs.s_users.data(), cs.qo.data(), cs.s_items.data(), cs.s_ratings.data(),
-                               nullptr, nullptr, h->cfg.k, cs.info.data(), st, nullptr, nullptr, false);
-        if (settle_statuses(q, cs) == 0) continue;
-        if (cs.take == 0) {  // (k <= 0: no list has a cell)
-            for (const int32_t s : cs.good) q.counts[cs.slot_query[s]] = 0;
-            continue;
-        }
-        qrank.resize((size_t)cs.C);
-        for (int32_t s = 0; s < cs.C; ++s) {
-            const uint32_t qkey = int_trie_key(cs.s_users[s]);
-            qrank[s] = (int32_t)(std::lower_bound(h->h_ukeys.begin(), h->h_ukeys.end(), qkey) - h->h_ukeys.begin());
-        }
-        entered_chunk(h->tr, h->nt, bs, cs.C, cs.take, width, cs.qo.data(), qrank.data(), st);
-        const size_t bytes = entered_pack_bytes(cs.C, width);
-        cs.h_vals.resize((bytes + 7) / 8);
-        KN_HIP(hipMemcpyAsync(cs.h_vals.data(), bs.en_pack.p, bytes, hipMemcpyDeviceToHost, st));
-        KN_HIP(hipStreamSynchronize(st));
-        const EnteredPack got = entered_pack(cs.h_vals.data(), cs.C, width);
-        for (const int32_t s : cs.good) {
-            const int64_t b = cs.slot_query[s];
-            const size_t at = (size_t)s * width, dst = (size_t)b * q.width;
-            const int64_t t = std::min<int64_t>(got.counts[s], width);
-            q.counts[b] = got.counts[s];
-            std::copy(got.users + at, got.users + at + t, q.out_i + dst);
-            std::copy(got.sims + at, got.sims + at + t, q.out_d + dst);
-            std::copy(got.pos + at, got.pos + at + t, q.out_pos + dst);
-            std::copy(got.displaced + at, got.displaced + at + t, q.out_displaced + dst);
-        }
-    }
-    return cs.first;
-}
-
-// the batch form, and the single form as a batch of one (single: the query's status is thrown as the call's)
-static void do_entered_batch(knncf_handle* h, const QueryCall& q, bool single) {
-    const char* what = single ? "query" : "query batch";
-    auto text = [&](const char* t) { return std::string(what) + ": " + t; };
-    require_fitted(h, false);
-    KN_REQUIRE(q.B >= 0, KNNCF_E_INVALID, text("n_queries < 0"));
-    KN_REQUIRE(q.width >= 0, KNNCF_E_INVALID, text("cap < 0"));
-    require_query_support(h, q.predictor, q.mode);
-    KN_REQUIRE(h->cfg.similarity != KNNCF_SIM_COSINE || !has_short_rows(h), KNNCF_E_UNSUPPORTED,
-               "query entered with the adjusted cosine: a user with <= 4 ratings makes the reference's summation order depend on its memo history pair by pair (SURVEY N6); the stored lists are not the fresh-closure lists");
-    if (q.B == 0) return;
-    KN_REQUIRE(q.users && q.offsets && q.statuses && q.counts, KNNCF_E_INVALID, text("null argument"));
-    require_offsets(q.offsets, q.B, "query batch: offsets[0] != 0", "query batch: offsets decrease");
-    KN_REQUIRE(q.offsets[q.B] < ((int64_t)1 << 31), KNNCF_E_INVALID, text("2^31 or more ratings in one call"));
-    KN_REQUIRE(q.offsets[q.B] == 0 || (q.items && q.ratings), KNNCF_E_INVALID, text("null ratings"));
-    KN_REQUIRE(q.width == 0 || (q.out_i && q.out_d && q.out_pos && q.out_displaced), KNNCF_E_INVALID, text("null output"));
-    build_unbuilt_neighbors(h);
-    const QueryFailure f = run_entered_chunks(h, q, query_batch_chunk(h, batch_budget(h)));
-    if (f.query < 0) return;
-    if (single) throw Error(q.statuses[0], std::string("query: ") + f.reason);
-    h->err = "query batch: query " + std::to_string(f.query) + ": " + f.reason;
-}
-
-int knncf_query_entered_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
-                              const double* ratings, int64_t n_queries, int32_t cap, int32_t* out_users, double* out_sims,
-                              int32_t* out_pos, int32_t* out_displaced, int32_t* counts, int32_t* statuses) {
-    return guarded(h, [&] {
-        do_entered_batch(h, {.family = QF_FOLD_IN, .mode = QB_ENTERED, .predictor = KNNCF_PRED_KNN, .users = users, .B = n_queries,
-                             .offsets = offsets, .items = items, .ratings = ratings, .width = cap, .out_i = out_users, .out_d = out_sims,
-                             .counts = counts, .statuses = statuses, .out_pos = out_pos, .out_displaced = out_displaced}, false);
-    });
-}
-
-int knncf_query_entered(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings, int32_t cap,
-                        int32_t* out_users, double* out_sims, int32_t* out_pos, int32_t* out_displaced, int32_t* count) {
-    return guarded(h, [&] {
-        require_fitted(h, false);
-        KN_REQUIRE(count && cap >= 0 && (cap == 0 || (out_users && out_sims && out_pos && out_displaced)), KNNCF_E_INVALID,
-                   "bad output arguments");
-        KN_REQUIRE(n_ratings > 0 && items && ratings, KNNCF_E_INVALID, "query: null ratings or n_ratings <= 0");
-        *count = 0;
-        const int64_t offsets[2] = {0, n_ratings};
-        int32_t status = KNNCF_OK;
-        do_entered_batch(h, {.family = QF_FOLD_IN, .mode = QB_ENTERED, .predictor = KNNCF_PRED_KNN, .users = &user, .B = 1,
-                             .offsets = offsets, .items = items, .ratings = ratings, .width = cap, .out_i = out_users, .out_d = out_sims,
-                             .counts = count, .statuses = &status, .out_pos = out_pos, .out_displaced = out_displaced}, true);
-    });
 }
 
 // users per chunk of knncf_recommend_batch: the rule of knncf.h ("Batched recommendations")
@@ -2748,7 +2720,7 @@ int knncf_recommend(knncf_handle* h, int predictor, int32_t user, int32_t n, int
     });
 }
 
-// ---- the 30 query entry points: the rows of the call by name, then the mode's builder (api.cpp "one request type") ----------
+// ---- the 46 query entry points: the rows of the call by name, then the mode's builder (api.cpp "one request type") ----------
 // fold-in queries: a user outside the fit
 int knncf_query_neighbors(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
                           int32_t cap, int32_t* ids, double* sims, int32_t* count) {
@@ -2995,18 +2967,18 @@ int knncf_revise_explain_personalized_batch(knncf_handle* h, const int32_t* user
 int knncf_query_recommend_explain(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
                                   int64_t n_ratings, int32_t n, int32_t order, int32_t cap, int32_t* out_items, double* out_preds,
                                   int32_t* count, int32_t* raters, double* sims, double* devs, int32_t* term_counts, double* sums) {
-    return query_single(h, recommend_explain_call({.family = QF_FOLD_IN, .items = items, .ratings = ratings, .user = user,
+    return query_single(h, recommend_explain_call(recommend_call({.family = QF_FOLD_IN, .items = items, .ratings = ratings, .user = user,
                                                   .n_ratings = n_ratings},
-                                                  predictor, n, out_items, out_preds, count,
+                                                  predictor, n, out_items, out_preds, count),
                                                   {order, cap, raters, sims, devs, term_counts, sums, nullptr}));
 }
 
 int knncf_update_recommend_explain(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
                                    int64_t n_ratings, int32_t n, int32_t order, int32_t cap, int32_t* out_items, double* out_preds,
                                    int32_t* count, int32_t* raters, double* sims, double* devs, int32_t* term_counts, double* sums) {
-    return query_single(h, recommend_explain_call({.family = QF_UPDATE, .items = items, .ratings = ratings, .user = user,
+    return query_single(h, recommend_explain_call(recommend_call({.family = QF_UPDATE, .items = items, .ratings = ratings, .user = user,
                                                   .n_ratings = n_ratings},
-                                                  predictor, n, out_items, out_preds, count,
+                                                  predictor, n, out_items, out_preds, count),
                                                   {order, cap, raters, sims, devs, term_counts, sums, nullptr}));
 }
 
@@ -3014,10 +2986,10 @@ int knncf_revise_recommend_explain(knncf_handle* h, int predictor, int32_t user,
                                    const int32_t* items, const double* ratings, int64_t n_ratings, int32_t n, int32_t order,
                                    int32_t cap, int32_t* out_items, double* out_preds, int32_t* count, int32_t* raters, double* sims,
                                    double* devs, int32_t* term_counts, double* sums) {
-    return query_single(h, recommend_explain_call({.family = QF_REVISE, .items = items, .ratings = ratings,
+    return query_single(h, recommend_explain_call(recommend_call({.family = QF_REVISE, .items = items, .ratings = ratings,
                                                   .removed_items = removed_items, .user = user, .n_ratings = n_ratings,
                                                   .n_removed = n_removed},
-                                                  predictor, n, out_items, out_preds, count,
+                                                  predictor, n, out_items, out_preds, count),
                                                   {order, cap, raters, sims, devs, term_counts, sums, nullptr}));
 }
 
@@ -3025,9 +2997,9 @@ int knncf_query_recommend_explain_batch(knncf_handle* h, int predictor, const in
                                         const int32_t* items, const double* ratings, int64_t n_queries, int32_t n, int32_t order,
                                         int32_t cap, int32_t* out_items, double* out_preds, int32_t* counts, int32_t* raters,
                                         double* sims, double* devs, int32_t* term_counts, double* sums, int32_t* statuses) {
-    return query_batch(h, recommend_explain_call({.family = QF_FOLD_IN, .users = users, .B = n_queries, .offsets = offsets,
+    return query_batch(h, recommend_explain_call(recommend_call({.family = QF_FOLD_IN, .users = users, .B = n_queries, .offsets = offsets,
                                                  .items = items, .ratings = ratings, .statuses = statuses},
-                                                 predictor, n, out_items, out_preds, counts,
+                                                 predictor, n, out_items, out_preds, counts),
                                                  {order, cap, raters, sims, devs, term_counts, sums, nullptr}));
 }
 
@@ -3035,9 +3007,9 @@ int knncf_update_recommend_explain_batch(knncf_handle* h, int predictor, const i
                                          const int32_t* items, const double* ratings, int64_t n_queries, int32_t n, int32_t order,
                                          int32_t cap, int32_t* out_items, double* out_preds, int32_t* counts, int32_t* raters,
                                          double* sims, double* devs, int32_t* term_counts, double* sums, int32_t* statuses) {
-    return query_batch(h, recommend_explain_call({.family = QF_UPDATE, .users = users, .B = n_queries, .offsets = offsets,
+    return query_batch(h, recommend_explain_call(recommend_call({.family = QF_UPDATE, .users = users, .B = n_queries, .offsets = offsets,
                                                  .items = items, .ratings = ratings, .statuses = statuses},
-                                                 predictor, n, out_items, out_preds, counts,
+                                                 predictor, n, out_items, out_preds, counts),
                                                  {order, cap, raters, sims, devs, term_counts, sums, nullptr}));
 }
 
@@ -3046,74 +3018,85 @@ int knncf_revise_recommend_explain_batch(knncf_handle* h, int predictor, const i
                                          const double* ratings, int64_t n_queries, int32_t n, int32_t order, int32_t cap,
                                          int32_t* out_items, double* out_preds, int32_t* counts, int32_t* raters, double* sims,
                                          double* devs, int32_t* term_counts, double* sums, int32_t* statuses) {
-    return query_batch(h, recommend_explain_call({.family = QF_REVISE, .users = users, .B = n_queries, .offsets = offsets,
+    return query_batch(h, recommend_explain_call(recommend_call({.family = QF_REVISE, .users = users, .B = n_queries, .offsets = offsets,
                                                  .items = items, .ratings = ratings, .removed_offsets = removed_offsets,
                                                  .removed_items = removed_items, .statuses = statuses},
-                                                 predictor, n, out_items, out_preds, counts,
+                                                 predictor, n, out_items, out_preds, counts),
                                                  {order, cap, raters, sims, devs, term_counts, sums, nullptr}));
 }
 
 // bystander queries: fitted users' answers once the fold-in query's user has joined (knncf.h "Bystander queries")
 int knncf_query_bystander_neighbors(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
                                     const int32_t* others, int64_t m, int32_t cap, int32_t* ids, double* sims, int32_t* counts) {
-    return bystander_single(h, {.family = QF_FOLD_IN, .mode = QB_BY_NEIGHBORS, .predictor = KNNCF_PRED_KNN, .items = items, .ratings = ratings,
-                                .others = others, .row_counts = counts, .width = cap, .out_i = ids, .out_d = sims, .user = user},
-                            n_ratings, m);
+    return rows_single(h, bystander_neighbors_call({.family = QF_FOLD_IN, .items = items, .ratings = ratings, .user = user,
+                                                         .n_ratings = n_ratings, .m = m}, others, cap, ids, sims, counts));
 }
 
 int knncf_query_bystander_predict(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
                                   int64_t n_ratings, const int32_t* others, const int32_t* pred_items, int64_t m, double* out) {
-    return bystander_single(h, {.family = QF_FOLD_IN, .mode = QB_BY_PREDICT, .predictor = predictor, .items = items, .ratings = ratings,
-                                .pred_items = pred_items, .others = others, .out_d = out, .user = user},
-                            n_ratings, m);
+    return rows_single(h, bystander_predict_call({.family = QF_FOLD_IN, .items = items, .ratings = ratings, .pred_items = pred_items,
+                                                       .user = user, .n_ratings = n_ratings, .m = m}, predictor, others, out));
 }
 
 int knncf_query_bystander_neighbors_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
                                           const double* ratings, int64_t n_queries, const int64_t* row_offsets, const int32_t* others,
                                           int32_t cap, int32_t* ids, double* sims, int32_t* counts, int32_t* statuses) {
-    return bystander_batch(h, {.family = QF_FOLD_IN, .mode = QB_BY_NEIGHBORS, .predictor = KNNCF_PRED_KNN, .users = users, .B = n_queries,
-                               .offsets = offsets, .items = items, .ratings = ratings, .pred_offsets = row_offsets, .others = others,
-                               .row_counts = counts, .width = cap, .out_i = ids, .out_d = sims, .statuses = statuses});
+    return query_batch(h, bystander_neighbors_call({.family = QF_FOLD_IN, .users = users, .B = n_queries, .offsets = offsets,
+                                                        .items = items, .ratings = ratings, .pred_offsets = row_offsets,
+                                                        .statuses = statuses}, others, cap, ids, sims, counts));
 }
 
 int knncf_query_bystander_predict_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets,
                                         const int32_t* items, const double* ratings, int64_t n_queries, const int64_t* row_offsets,
                                         const int32_t* others, const int32_t* pred_items, double* out, int32_t* statuses) {
-    return bystander_batch(h, {.family = QF_FOLD_IN, .mode = QB_BY_PREDICT, .predictor = predictor, .users = users, .B = n_queries,
-                               .offsets = offsets, .items = items, .ratings = ratings, .pred_offsets = row_offsets,
-                               .pred_items = pred_items, .others = others, .out_d = out, .statuses = statuses});
+    return query_batch(h, bystander_predict_call({.family = QF_FOLD_IN, .users = users, .B = n_queries, .offsets = offsets,
+                                                      .items = items, .ratings = ratings, .pred_offsets = row_offsets,
+                                                      .pred_items = pred_items, .statuses = statuses}, predictor, others, out));
 }
 
 // bystanders of update queries: the same four calls for a user that may be in the fit, whose given rows are then additional to
 // its train rows (knncf.h "Bystanders of update queries")
 int knncf_update_bystander_neighbors(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
-                                     const int32_t* others, int64_t m, int32_t cap, int32_t* ids, double* sims, int32_t* counts) {
-    return bystander_single(h, {.family = QF_UPDATE, .mode = QB_BY_NEIGHBORS, .predictor = KNNCF_PRED_KNN, .items = items, .ratings = ratings,
-                                .others = others, .row_counts = counts, .width = cap, .out_i = ids, .out_d = sims, .user = user},
-                            n_ratings, m);
+                                    const int32_t* others, int64_t m, int32_t cap, int32_t* ids, double* sims, int32_t* counts) {
+    return rows_single(h, bystander_neighbors_call({.family = QF_UPDATE, .items = items, .ratings = ratings, .user = user,
+                                                         .n_ratings = n_ratings, .m = m}, others, cap, ids, sims, counts));
 }
 
 int knncf_update_bystander_predict(knncf_handle* h, int predictor, int32_t user, const int32_t* items, const double* ratings,
-                                   int64_t n_ratings, const int32_t* others, const int32_t* pred_items, int64_t m, double* out) {
-    return bystander_single(h, {.family = QF_UPDATE, .mode = QB_BY_PREDICT, .predictor = predictor, .items = items, .ratings = ratings,
-                                .pred_items = pred_items, .others = others, .out_d = out, .user = user},
-                            n_ratings, m);
+                                  int64_t n_ratings, const int32_t* others, const int32_t* pred_items, int64_t m, double* out) {
+    return rows_single(h, bystander_predict_call({.family = QF_UPDATE, .items = items, .ratings = ratings, .pred_items = pred_items,
+                                                       .user = user, .n_ratings = n_ratings, .m = m}, predictor, others, out));
 }
 
 int knncf_update_bystander_neighbors_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
-                                           const double* ratings, int64_t n_queries, const int64_t* row_offsets, const int32_t* others,
-                                           int32_t cap, int32_t* ids, double* sims, int32_t* counts, int32_t* statuses) {
-    return bystander_batch(h, {.family = QF_UPDATE, .mode = QB_BY_NEIGHBORS, .predictor = KNNCF_PRED_KNN, .users = users, .B = n_queries,
-                               .offsets = offsets, .items = items, .ratings = ratings, .pred_offsets = row_offsets, .others = others,
-                               .row_counts = counts, .width = cap, .out_i = ids, .out_d = sims, .statuses = statuses});
+                                          const double* ratings, int64_t n_queries, const int64_t* row_offsets, const int32_t* others,
+                                          int32_t cap, int32_t* ids, double* sims, int32_t* counts, int32_t* statuses) {
+    return query_batch(h, bystander_neighbors_call({.family = QF_UPDATE, .users = users, .B = n_queries, .offsets = offsets,
+                                                        .items = items, .ratings = ratings, .pred_offsets = row_offsets,
+                                                        .statuses = statuses}, others, cap, ids, sims, counts));
 }
 
 int knncf_update_bystander_predict_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets,
-                                         const int32_t* items, const double* ratings, int64_t n_queries, const int64_t* row_offsets,
-                                         const int32_t* others, const int32_t* pred_items, double* out, int32_t* statuses) {
-    return bystander_batch(h, {.family = QF_UPDATE, .mode = QB_BY_PREDICT, .predictor = predictor, .users = users, .B = n_queries,
-                               .offsets = offsets, .items = items, .ratings = ratings, .pred_offsets = row_offsets,
-                               .pred_items = pred_items, .others = others, .out_d = out, .statuses = statuses});
+                                        const int32_t* items, const double* ratings, int64_t n_queries, const int64_t* row_offsets,
+                                        const int32_t* others, const int32_t* pred_items, double* out, int32_t* statuses) {
+    return query_batch(h, bystander_predict_call({.family = QF_UPDATE, .users = users, .B = n_queries, .offsets = offsets,
+                                                      .items = items, .ratings = ratings, .pred_offsets = row_offsets,
+                                                      .pred_items = pred_items, .statuses = statuses}, predictor, others, out));
+}
+
+// entered queries: the fitted users whose lists the fold-in query's user joins (knncf.h "Entered queries")
+int knncf_query_entered(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings, int32_t cap,
+                        int32_t* out_users, double* out_sims, int32_t* out_pos, int32_t* out_displaced, int32_t* count) {
+    return rows_single(h, entered_call({.family = QF_FOLD_IN, .items = items, .ratings = ratings, .out_pos = out_pos,
+                                        .out_displaced = out_displaced, .user = user, .n_ratings = n_ratings}, cap, out_users, out_sims, count));
+}
+
+int knncf_query_entered_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                              const double* ratings, int64_t n_queries, int32_t cap, int32_t* out_users, double* out_sims,
+                              int32_t* out_pos, int32_t* out_displaced, int32_t* counts, int32_t* statuses) {
+    return query_batch(h, entered_call({.family = QF_FOLD_IN, .users = users, .B = n_queries, .offsets = offsets, .items = items,
+                                        .ratings = ratings, .statuses = statuses, .out_pos = out_pos, .out_displaced = out_displaced},
+                                       cap, out_users, out_sims, counts));
 }
 
 int knncf_neighbors_save(knncf_handle* h, const char* path) {

@@ -392,6 +392,7 @@ struct QueryBatchScratch {
     // where q is in v's list (else +0.0)
     DArr<int32_t> by_qslot, by_qidx, by_qrank;
     DArr<double> by_pair, by_in;
+    bool by_chunk = false;             // the chunk answered last was a bystander chunk (QueryChunk::by)
     // entered queries (entered.hip): the answers of a chunk in ONE block (entered_pack), 20 * width + 4 bytes per slot
     DArr<double> en_pack;
 };
@@ -408,30 +409,41 @@ struct ByChunk {
     const int32_t* h_qidx;
     int32_t fitted, merged;
 };
-// prep + similarities + top-k (bs.nbr_idx / nbr_sim [C][min(k, U)]) of C >= 1 non-empty queries; h_info[4 b ..] = status
-// bits, known items, neighbour ratings (0 for a slot whose status is set) of slot b.  Synchronises the stream once.
-// h_self == nullptr (fold-in queries): h_items / h_ratings are the chunk's rows [h_qo[C]].  Otherwise (update queries) h_self[b]
-// is the dense index of slot b's user in the fit or -1, h_items / h_ratings are the additional rows [h_ao[C]] only, and slot b
-// has h_qo[b + 1] - h_qo[b] = (train rows of h_self[b]) + (h_ao[b + 1] - h_ao[b]) rows: the train rows are seeded on the
-// device, a fitted user is left out of its own candidates and gets min(k, U - 1) neighbours.
-// h_ro != nullptr with h_ro[C] > 0 (revise queries): h_removed [h_ro[b], h_ro[b + 1]) are raw items whose train rows slot b's
-// user drops, at most as many as it has train rows, none for a slot with h_self[b] < 0; slot b then has (train rows) -
-// (removed items) + (additional rows) rows.  A removal that names no train row of the user, or one twice, sets
-// QUERY_ST_RM_UNRATED / QUERY_ST_RM_TWICE in the slot's status bits.  The known items of h_info count the items that left aug.
-void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, const int32_t* h_users,
-                            const int64_t* h_qo, const int32_t* h_items, const double* h_ratings, const int32_t* h_self,
-                            const int64_t* h_ao, int32_t k, long long* h_info, hipStream_t st, const int64_t* h_ro = nullptr,
-                            const int32_t* h_removed = nullptr, bool topk = true, const ByChunk* by = nullptr);
-// (topk = false, the Personalized mode: stops after the similarities — no keys, no sorts, bs.nbr_idx / nbr_sim / off are not
-// written and the neighbour ratings of h_info are 0)
-// (by != nullptr, an update chunk with topk: after the top lists every bystander slot's list takes its newcomer in — index U,
-// min(k, U) entries — and the neighbour ratings of h_info count the newcomer's known items; a newcomer's own slot and the
-// bystander slots of a newcomer whose status is set have 0.  The bystander slots of a fitted changer get S(v, c) on aug into
-// their similarity row ahead of the sorts instead: min(k, U - 1) entries, c among them at index dense(c))
+// A packed chunk of C >= 1 non-empty queries on the host, slot after slot: what foldin_batch_neighbors uploads.
+struct QueryChunk {
+    int32_t C;
+    const int32_t* users;  // [C] raw ids
+    const int64_t* qo;     // [C + 1] slot b has qo[b + 1] - qo[b] rows in aug
+    // self == nullptr (a fold-in chunk; ao is null with it): items / ratings are the chunk's rows [qo[C]].  Otherwise (an update
+    // chunk) self[b] is the dense index of slot b's user in the fit or -1, items / ratings are the ADDITIONAL rows [ao[C]] only,
+    // and slot b has (train rows of self[b]) + (ao[b + 1] - ao[b]) rows: the train rows are seeded on the device, a fitted user
+    // is left out of its own candidates and gets min(k, U - 1) neighbours.
+    const int32_t* items;
+    const double* ratings;
+    const int32_t* self;  // [C]
+    const int64_t* ao;    // [C + 1]
+    // ro != nullptr with ro[C] > 0 (a revise chunk, which is an update chunk): removed [ro[b], ro[b + 1]) are raw items whose
+    // train rows slot b's user drops, at most as many as it has train rows, none for a slot with self[b] < 0; slot b then has
+    // (train rows) - (removed items) + (additional rows) rows.  A removal that names no train row of the user, or one twice, sets
+    // QUERY_ST_RM_UNRATED / QUERY_ST_RM_TWICE in the slot's status bits; the known items of h_info count the items that left aug.
+    const int64_t* ro;
+    const int32_t* removed;
+    // false (the Personalized and the entered modes): the pass stops after the similarities — no keys, no sorts, bs.nbr_idx /
+    // nbr_sim / off are not written and the neighbour ratings of h_info are 0
+    bool topk;
+    // != nullptr (a bystander chunk: an update chunk with topk and without removals): after the top lists every bystander slot's
+    // list takes its newcomer in — index U, min(k, U) entries — and the neighbour ratings of h_info count the newcomer's known
+    // items; a newcomer's own slot and the bystander slots of a newcomer whose status is set have 0.  The bystander slots of a
+    // fitted changer get S(v, c) on aug into their similarity row ahead of the sorts instead: min(k, U - 1) entries, c among
+    // them at index dense(c).  foldin_batch_predictions then gathers the changer's prepared row by its index (bs.by_chunk)
+    const ByChunk* by;
+};
+// prep + similarities + top-k (bs.nbr_idx / nbr_sim [C][min(k, U)]) of the chunk; h_info[4 b ..] = status bits, known items,
+// neighbour ratings (0 for a slot whose status is set) of slot b.  Synchronises the stream once.
+void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, const QueryChunk& q, int32_t k, long long* h_info, hipStream_t st);
 // bs.pred / bs.rated [C][I]; h_ebase[C + 1] = exclusive prefix of the slots' neighbour ratings
 void foldin_batch_predictions(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, int32_t take,
-                              const int64_t* h_ebase, hipStream_t st, bool bystander = false);
-// (bystander: the chunk went through foldin_batch_neighbors with a ByChunk; the changer's index gathers its prepared row)
+                              const int64_t* h_ebase, hipStream_t st);
 void foldin_batch_pick(const Train& tr, QueryBatchScratch& bs, const int32_t* d_items, const int32_t* d_slot, int64_t m,
                        double* d_out, hipStream_t st);
 // KNNCF_PRED_PERSONALIZED instead of foldin_batch_predictions, after foldin_batch_neighbors(topk = false) on the chunk of n rows

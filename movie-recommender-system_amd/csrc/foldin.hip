@@ -829,10 +829,14 @@ static const uint32_t* qb_segmented_sort(QueryBatchScratch& bs, SortWorkspace& w
     return bs.v32_a.p;
 }
 
-void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, const int32_t* h_users,
-                            const int64_t* h_qo, const int32_t* h_items, const double* h_ratings, const int32_t* h_self,
-                            const int64_t* h_ao, int32_t k, long long* h_info, hipStream_t st, const int64_t* h_ro,
-                            const int32_t* h_removed, bool topk, const ByChunk* by) {
+void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, const QueryChunk& q, int32_t k, long long* h_info, hipStream_t st) {
+    const int32_t C = q.C, *h_users = q.users, *h_items = q.items, *h_self = q.self, *h_removed = q.removed;
+    const int64_t *h_qo = q.qo, *h_ao = q.ao, *h_ro = q.ro;
+    const double* h_ratings = q.ratings;
+    const ByChunk* by = q.by;
+    const bool topk = q.topk;
+    KN_REQUIRE(!h_self == !h_ao && (!h_ro || h_self) && (!by || (h_self && topk && !h_ro)), KNNCF_E_INVALID, "query chunk: fields that do not go together");
+    bs.by_chunk = by != nullptr;
     const int32_t U = tr.U, I = tr.I;
     const int64_t W = ceil_div(I, 64), n = h_qo[C];
     const int64_t cells = (int64_t)C * std::max(U, I);
@@ -964,7 +968,7 @@ void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspac
 }
 
 void foldin_batch_predictions(const Train& tr, QueryBatchScratch& bs, SortWorkspace& ws, int32_t C, int32_t take,
-                              const int64_t* h_ebase, hipStream_t st, bool bystander) {
+                              const int64_t* h_ebase, hipStream_t st) {
     const int32_t I = tr.I;
     const int64_t W = ceil_div(I, 64), E = h_ebase[C], cells = (int64_t)C * I;
     bs.num.ensure(cells); bs.den.ensure(cells); bs.pred.ensure(cells); bs.rated.ensure(cells);
@@ -976,7 +980,7 @@ void foldin_batch_predictions(const Train& tr, QueryBatchScratch& bs, SortWorksp
         bs.e_k64_a.ensure(E); bs.e_k64_b.ensure(E); bs.e_v32_a.ensure(E); bs.e_v32_b.ensure(E);
         bs.e_dev.ensure(E); bs.e_sim.ensure(E);
         KN_HIP(hipMemcpyAsync(bs.ebase.p, h_ebase, ((size_t)C + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        if (bystander) bystander_gather(tr, bs, C, take, st);
+        if (bs.by_chunk) bystander_gather(tr, bs, C, take, st);
         else k_qb_gather<<<(unsigned)ceil_div((int64_t)C * take, TPB / 64), TPB, 0, st>>>(
             C, take, I, bs.nbr_idx.p, bs.nbr_sim.p, bs.off.p, bs.ebase.p, tr.u_ptr.p, tr.s_col.p, tr.s_t.p, tr.s_dev.p, bs.e_k64_a.p,
             bs.e_v32_a.p, bs.e_dev.p, bs.e_sim.p);
