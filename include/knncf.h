@@ -861,7 +861,8 @@ int knncf_query_bystander_predict_batch(knncf_handle* h, int predictor, const in
  * changers and newcomers.  Results do not depend on C; a repeated call of the same shape allocates no device memory.
  * Handle state: read-only, as "Bystander queries".  knncf_get_timings: charged as the fold-in calls charge theirs.
  * OUT OF SCOPE: bystanders of revise queries (with removals average(aug) is no continuation of the fit's running total, and an
- * item can leave aug); the entered question for update queries (a changer that leaves a list needs that user's full row);
+ * item can leave aug); the entered question for update queries is served by knncf_update_entered* ("Entered queries of update
+ * queries" below), which rebuilds a user's full row through these calls only where the stored list cannot decide;
  * KNNCF_PRED_PERSONALIZED and the other predictors; recommendations and explanations for a bystander; device-pointer forms; shard
  * handles and knncf_group_*; the command-line tool. */
 int knncf_update_bystander_neighbors(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
@@ -918,7 +919,7 @@ int knncf_update_bystander_predict_batch(knncf_handle* h, int predictor, const i
  * slot, at most 20 bytes * num_users) is allocated beside the budget, as the gathered ratings are.  The results do not depend on
  * C, and a repeated call of the same shape allocates no device memory.
  * OUT OF SCOPE: newcomers that are in the fit (their bystanders' lists: "Bystanders of update queries" above; the entered
- * question itself is not served for them, nor for revise queries); KNNCF_PRED_PERSONALIZED; cosine fits with users of 4
+ * question for them: "Entered queries of update queries" below; it is not served for revise queries); KNNCF_PRED_PERSONALIZED; cosine fits with users of 4
  * or fewer ratings; an ordering by similarity; device-pointer forms; shard handles and knncf_group_*; the command-line tool. */
 int knncf_query_entered(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
                         int32_t cap, int32_t* out_users, double* out_sims, int32_t* out_pos, int32_t* out_displaced,
@@ -926,6 +927,50 @@ int knncf_query_entered(knncf_handle* h, int32_t user, const int32_t* items, con
 int knncf_query_entered_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
                               const double* ratings, int64_t n_queries, int32_t cap, int32_t* out_users, double* out_sims,
                               int32_t* out_pos, int32_t* out_displaced, int32_t* counts, int32_t* statuses);
+
+/* ---- Entered queries of update queries: whose kNN lists a user's new ratings change ------------------------------------------
+ * The entered question for a changer that may be IN the fit: when fitted user c rates more items, which other fitted users'
+ * cached kNN answers are stale?  One pass over the fit, where knncf_update_bystander_neighbors would take one slot per fitted user.
+ * A query is an update query exactly as knncf_update_neighbors_batch defines it: any raw id c = users[b] with ADDITIONAL rows,
+ * aug_b = train ++ those rows.  Queries are independent.
+ * Which users are reported.  For a fitted v != c let L0 = getNeighbors(train, k, sim)(v) and L1 = getNeighbors(aug_b, k, sim)(v)
+ * :596-617, each evaluated on closures of v's own, so that v owns every pair.  v is REPORTED iff c occurs in L0 or in L1, with
+ * two exceptions: (a) a fitted c with n_ratings == 0 — aug is train; the query is valid (KNNCF_OK) and reports nothing; (b) c
+ * stands in both lists at the same position with a similarity of +-0.0 of identical bits — a zero weight, no term of any fold.
+ * Guarantee for an unreported v: L1 == L0 in ids and similarity bits, and every KNNCF_PRED_KNN prediction of v on aug_b equals
+ * its prediction on train bit for bit — but for users answered with the global average, as in "Entered queries".
+ * Outputs.  Row b of the five arrays ([n_queries * cap], row stride cap) receives the first min(counts[b], cap) reported users of
+ * query b in the fit's user set order.  counts[b] is the number of reported users and may exceed cap.  Cells past the written
+ * ones are untouched.  With cap == 0 every output array may be null: a count-only call.  Per reported user v:
+ *   out_users  the raw id of v
+ *   out_sims   S(v, c) on aug_b, owned by v, whether or not c is in L1; where c is in L1, the bits of that cell
+ *   out_pos    the 0-based position of c in L1, -1 if c left
+ *   out_prev   the 0-based position of c in L0, -1 if c entered
+ *   out_other  entered: the raw id that drops out of L0, -1 where the list grew; left: the raw id that comes into L1 (its last
+ *              cell); otherwise -1
+ * A c absent from train is the fold-in case: out_users / out_sims / out_pos / out_other are knncf_query_entered's answer bit for
+ * bit, out_prev = -1.  An empty query of an absent user stays KNNCF_E_INVALID, as in knncf_update_*.
+ * Tail rows.  A reported v whose stored list is full and in which c, stored on train, now sorts behind every other stored entry
+ * cannot be decided from the stored list: whether c keeps the last cell depends on v's best candidate outside it.  Such rows
+ * within cap are resolved through knncf_update_bystander_neighbors_batch internally (one update slot per tail row); a
+ * count-only call and tail rows beyond cap cost nothing.  Per-query statuses are those of knncf_update_neighbors_batch, and
+ * one more: KNNCF_E_UNSUPPORTED when a tail user within cap has more than 65536 train ratings — counts[b] = 0 and the rows
+ * untouched, as for every failed query (a query's rows are written once all of them are resolved).
+ * Refusals of the handle and handle state: those of knncf_query_entered_batch.  NOT read-only: the missing lists M are built
+ * first, in one batch in ascending raw id, which leaves the state knncf_neighbors_batch over M leaves; a KNNCF_SIM_COSINE handle
+ * whose train set has a user of 4 or fewer ratings is refused, Jaccard is accepted.
+ * The single form is the batch of one and returns the query's status; it has set *count = 0 once the argument checks pass.
+ * Chunks.  C of "Batched fold-in queries", one slot per query in phase 1 (24 bytes * min(cap, num_users) + 4 per slot of answer
+ * scratch beside the budget); the tail rows of a chunk then travel as "Bystanders of update queries" describes.  Results do not
+ * depend on C; a repeated call of the same shape allocates no device memory.
+ * OUT OF SCOPE: revise queries; KNNCF_PRED_PERSONALIZED; cosine fits with users of 4 or fewer ratings; device-pointer forms;
+ * shard handles and knncf_group_*; the command-line tool. */
+int knncf_update_entered(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
+                         int32_t cap, int32_t* out_users, double* out_sims, int32_t* out_pos, int32_t* out_prev,
+                         int32_t* out_other, int32_t* count);
+int knncf_update_entered_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                               const double* ratings, int64_t n_queries, int32_t cap, int32_t* out_users, double* out_sims,
+                               int32_t* out_pos, int32_t* out_prev, int32_t* out_other, int32_t* counts, int32_t* statuses);
 
 /* ---- batch ---------------------------------------------------------------- */
 int knncf_predict_batch(knncf_handle* h, int predictor, const int32_t* users,

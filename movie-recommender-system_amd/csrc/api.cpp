@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <chrono>
 #include <functional>
 #include <vector>
 
@@ -1065,7 +1066,8 @@ constexpr int64_t QUERY_MAX_RATINGS = 65536;
 // QB_RECOMMEND_EXPLAIN: QB_RECOMMEND, then the explain kernel of the predictor over the rows the selection produced
 // (knncf_*_recommend_explain*): no requested rows, so neither explains() nor wants_rows()
 // QB_BY_NEIGHBORS / QB_BY_PREDICT: bystander queries (knncf_*_bystander_*) — a query's rows name fitted users; run_bystander_chunks
-// QB_ENTERED: entered queries (knncf_query_entered*) — no rows; an answer step of run_query_chunks (answer_entered)
+// QB_ENTERED: entered queries (knncf_query_entered*) — no rows; an answer step of run_query_chunks (answer_entered); under
+// QF_UPDATE the entered queries of update queries (knncf_update_entered*; answer_entered_update)
 enum QueryBatchMode { QB_NEIGHBORS, QB_PREDICT, QB_RECOMMEND, QB_EXPLAIN, QB_EXPLAIN_ALL, QB_RECOMMEND_EXPLAIN, QB_BY_NEIGHBORS, QB_BY_PREDICT, QB_ENTERED };
 bool bystanders(QueryBatchMode mode) { return mode == QB_BY_NEIGHBORS || mode == QB_BY_PREDICT; }
 bool explains(QueryBatchMode mode) { return mode == QB_EXPLAIN || mode == QB_EXPLAIN_ALL; }
@@ -1172,6 +1174,7 @@ struct QueryCall {
     ExplainCells ex;                 // explain modes: pred_offsets[B] rows; QB_RECOMMEND_EXPLAIN: B * n rows, row b * n + j (pred null)
     int32_t* out_pos;                // QB_ENTERED: [B * cap] beside out_i (users) and out_d (sims), width = cap
     int32_t* out_displaced;          // QB_ENTERED: [B * cap]
+    int32_t* out_prev;               // QB_ENTERED under QF_UPDATE (knncf_update_entered*): [B * cap]; null otherwise
     int32_t user;                    // single forms only, from here on
     int64_t n_ratings, n_removed, m;
 };
@@ -1570,6 +1573,101 @@ void answer_entered(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
     }
 }
 
+QueryFailure run_bystander_chunks(knncf_handle* h, const QueryCall& q, int64_t chunk);
+int64_t bystander_chunk(knncf_handle* h, int64_t budget);
+
+// QB_ENTERED under QF_UPDATE (entered.hip; knncf.h "Entered queries of update queries"): phase 1 is answer_entered's with the
+// chunk's update slots — counts[b] and the first min(counts[b], cap) reported users of every good query on the host.  Phase 2
+// resolves the tail rows among them (pos == EN_TAIL: the changer sorts behind every other stored entry of a full list, and the
+// best candidate outside the list decides) through the bystander path: one internal knncf_update_bystander_neighbors_batch over
+// the chunk's queries that have some, rows = their tail users, cap = take.  A query's rows are written once all of them are
+// resolved; a query whose tail user the bystander path refuses takes that status and keeps its rows untouched.
+void answer_entered_update(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
+    if (cs.take == 0) {  // (k <= 0: no list has a cell)
+        for (const int32_t s : cs.good) q.counts[cs.slot_query[s]] = 0;
+        return;
+    }
+    QueryBatchScratch& bs = h->query_batch;
+    hipStream_t st = h->stream;
+    const int32_t width = std::min(q.width, h->tr.U), take = cs.take;
+    load_host_ids(h);
+    cs.qrank.resize((size_t)cs.C);
+    for (int32_t s = 0; s < cs.C; ++s) {
+        const uint32_t qkey = int_trie_key(cs.s_users[s]);
+        cs.qrank[s] = (int32_t)(std::lower_bound(h->h_ukeys.begin(), h->h_ukeys.end(), qkey) - h->h_ukeys.begin());
+    }
+    entered_update_chunk(h->tr, h->nt, bs, cs.C, take, width, cs.qo.data(), cs.s_self.data(), cs.qrank.data(), st);
+    const size_t bytes = entered_update_pack_bytes(cs.C, width);
+    cs.h_vals.resize((bytes + 7) / 8);
+    KN_HIP(hipMemcpyAsync(cs.h_vals.data(), bs.en_pack.p, bytes, hipMemcpyDeviceToHost, st));
+    KN_HIP(hipStreamSynchronize(st));
+    const EnteredPack got = entered_pack(cs.h_vals.data(), cs.C, width);
+    int32_t* prev = entered_pack_prev(got, cs.C);
+    // phase 2: the tail rows within the written cells, query after query
+    std::vector<int32_t> t_users, t_items, t_others, t_cell, t_status;
+    std::vector<int64_t> t_off(1, 0), t_rows(1, 0);
+    std::vector<double> t_ratings;
+    std::vector<int32_t> t_of((size_t)cs.C, -1);  // the slot's query of the internal call
+    for (const int32_t s : cs.good) {
+        const size_t at = (size_t)s * width;
+        const int64_t t = std::min<int64_t>(got.counts[s], width), b = cs.slot_query[s];
+        for (int64_t j = 0; j < t; ++j) {
+            if (got.pos[at + j] != EN_TAIL) continue;
+            t_others.push_back(got.users[at + j]);
+            t_cell.push_back((int32_t)j);
+        }
+        if ((int64_t)t_others.size() == t_rows.back()) continue;
+        t_of[s] = (int32_t)t_users.size();
+        t_users.push_back(q.users[b]);
+        t_items.insert(t_items.end(), q.items + q.offsets[b], q.items + q.offsets[b + 1]);
+        t_ratings.insert(t_ratings.end(), q.ratings + q.offsets[b], q.ratings + q.offsets[b + 1]);
+        t_off.push_back((int64_t)t_items.size());
+        t_rows.push_back((int64_t)t_others.size());
+    }
+    std::vector<int32_t> l_ids((size_t)t_others.size() * take), l_counts(t_others.size(), 0);
+    std::vector<double> l_sims((size_t)t_others.size() * take);
+    if (!t_users.empty()) {
+        t_status.assign(t_users.size(), KNNCF_OK);
+        const QueryCall inner = bystander_neighbors_call({.family = QF_UPDATE, .users = t_users.data(), .B = (int64_t)t_users.size(),
+                                                          .offsets = t_off.data(), .items = t_items.data(), .ratings = t_ratings.data(),
+                                                          .pred_offsets = t_rows.data(), .statuses = t_status.data()},
+                                                         t_others.data(), take, l_ids.data(), l_sims.data(), l_counts.data());
+        const auto t0 = std::chrono::steady_clock::now();  // (the hook also says what phase 2 took: it ends synchronised)
+        run_bystander_chunks(h, inner, bystander_chunk(h, batch_budget(h)));  // (reuses the chunk's device scratch: its answers are on the host)
+        KN_TRACE_DISPATCH("entered_update tails queries=%d rows=%d ms=%.3f", (int)t_users.size(), (int)t_others.size(),
+                          std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    }
+    for (const int32_t s : cs.good) {
+        const int64_t b = cs.slot_query[s];
+        const size_t at = (size_t)s * width, dst = (size_t)b * q.width;
+        const int64_t t = std::min<int64_t>(got.counts[s], width);
+        if (t_of[s] >= 0) {
+            const int32_t tq = t_of[s];
+            if (t_status[tq] != KNNCF_OK) {
+                fail(q, cs, b, t_status[tq], "a tail row's user that the bystander path refuses (more than 65536 ratings)");
+                continue;
+            }
+            for (int64_t r = t_rows[tq]; r < t_rows[tq + 1]; ++r) {
+                const size_t cell = at + (size_t)t_cell[r];
+                const int32_t* ids = l_ids.data() + (size_t)r * take;
+                const int32_t n = std::min(l_counts[r], take);
+                const int32_t p = (int32_t)(std::find(ids, ids + n, q.users[b]) - ids);
+                if (p < n) {  // the changer kept the last cell: the cell's own bits
+                    got.pos[cell] = p; got.displaced[cell] = -1; got.sims[cell] = l_sims[(size_t)r * take + p];
+                } else {      // it left: the user that came into the last cell
+                    got.pos[cell] = -1; got.displaced[cell] = n > 0 ? ids[n - 1] : -1;
+                }
+            }
+        }
+        q.counts[b] = got.counts[s];
+        std::copy(got.users + at, got.users + at + t, q.out_i + dst);
+        std::copy(got.sims + at, got.sims + at + t, q.out_d + dst);
+        std::copy(got.pos + at, got.pos + at + t, q.out_pos + dst);
+        std::copy(got.displaced + at, got.displaced + at + t, q.out_displaced + dst);
+        std::copy(prev + at, prev + at + t, q.out_prev + dst);
+    }
+}
+
 // The validated queries of q in chunks of `chunk`, one slot per query: statuses[b] and, where it is KNNCF_OK, query b's answer
 // in q's outputs.  A refused query gets ex.counts = 0 on its rows (the explain modes, answered ex_rows rows per launch)
 QueryFailure run_query_chunks(knncf_handle* h, const QueryCall& q, int64_t chunk, int64_t ex_rows) {
@@ -1587,7 +1685,7 @@ QueryFailure run_query_chunks(knncf_handle* h, const QueryCall& q, int64_t chunk
             case QB_EXPLAIN_ALL: answer_explain(h, q, cs, ex_rows); break;
             case QB_RECOMMEND: answer_recommend(h, q, cs); break;
             case QB_RECOMMEND_EXPLAIN: answer_recommend_explain(h, q, cs, ex_rows); break;
-            case QB_ENTERED: answer_entered(h, q, cs); break;
+            case QB_ENTERED: q.family == QF_UPDATE ? answer_entered_update(h, q, cs) : answer_entered(h, q, cs); break;
             case QB_BY_NEIGHBORS:
             case QB_BY_PREDICT: throw Error(KNNCF_E_INVALID, "query: a bystander mode in run_query_chunks (run_bystander_chunks answers them)");
         }
@@ -1798,7 +1896,7 @@ void do_query_batch(knncf_handle* h, const QueryCall& q, bool single) {
                    "query batch: null prediction arguments");
         if (explains(q.mode)) require_explain_outputs(q.ex, q.pred_offsets[B]);
     } else {
-        KN_REQUIRE(q.width == 0 || (q.out_i && q.out_d && (q.mode != QB_ENTERED || (q.out_pos && q.out_displaced))), KNNCF_E_INVALID,
+        KN_REQUIRE(q.width == 0 || (q.out_i && q.out_d && (q.mode != QB_ENTERED || (q.out_pos && q.out_displaced && (q.family == QF_FOLD_IN || q.out_prev)))), KNNCF_E_INVALID,
                    text("null output"));
         if (q.mode == QB_RECOMMEND_EXPLAIN) require_explain_outputs(q.ex, q.width);
     }
@@ -1874,7 +1972,7 @@ int rows_single(knncf_handle* h, const QueryCall& call) {
     return guarded(h, [&] {
         require_fitted(h, false);
         if (call.mode == QB_ENTERED)
-            KN_REQUIRE(call.counts && call.width >= 0 && (call.width == 0 || (call.out_i && call.out_d && call.out_pos && call.out_displaced)),
+            KN_REQUIRE(call.counts && call.width >= 0 && (call.width == 0 || (call.out_i && call.out_d && call.out_pos && call.out_displaced && (call.family == QF_FOLD_IN || call.out_prev))),
                        KNNCF_E_INVALID, "bad output arguments");
         require_single_ratings(call);
         KN_REQUIRE(call.m >= 0, KNNCF_E_INVALID, "query: m < 0");
@@ -3097,6 +3195,22 @@ int knncf_query_entered_batch(knncf_handle* h, const int32_t* users, const int64
     return query_batch(h, entered_call({.family = QF_FOLD_IN, .users = users, .B = n_queries, .offsets = offsets, .items = items,
                                         .ratings = ratings, .statuses = statuses, .out_pos = out_pos, .out_displaced = out_displaced},
                                        cap, out_users, out_sims, counts));
+}
+
+// the same question for an update query's user, which may be of the fit (knncf.h "Entered queries of update queries")
+int knncf_update_entered(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings, int32_t cap,
+                         int32_t* out_users, double* out_sims, int32_t* out_pos, int32_t* out_prev, int32_t* out_other, int32_t* count) {
+    return rows_single(h, entered_call({.family = QF_UPDATE, .items = items, .ratings = ratings, .out_pos = out_pos,
+                                        .out_displaced = out_other, .out_prev = out_prev, .user = user, .n_ratings = n_ratings},
+                                       cap, out_users, out_sims, count));
+}
+
+int knncf_update_entered_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
+                               const double* ratings, int64_t n_queries, int32_t cap, int32_t* out_users, double* out_sims,
+                               int32_t* out_pos, int32_t* out_prev, int32_t* out_other, int32_t* counts, int32_t* statuses) {
+    return query_batch(h, entered_call({.family = QF_UPDATE, .users = users, .B = n_queries, .offsets = offsets, .items = items,
+                                        .ratings = ratings, .statuses = statuses, .out_pos = out_pos, .out_displaced = out_other,
+                                        .out_prev = out_prev}, cap, out_users, out_sims, counts));
 }
 
 int knncf_neighbors_save(knncf_handle* h, const char* path) {

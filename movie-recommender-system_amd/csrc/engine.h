@@ -519,6 +519,17 @@ inline EnteredPack entered_pack(double* base, int32_t C, int32_t width) {
 // back.
 void entered_chunk(const Train& tr, const NeighborTable& nt, QueryBatchScratch& bs, int32_t C, int32_t take, int32_t width,
                    const int64_t* h_qo, const int32_t* h_qrank, hipStream_t st);
+// Entered queries of update queries (knncf_update_entered*; DESIGN.md "Entered queries of update queries"): the same after
+// foldin_batch_neighbors(topk = false) on an UPDATE chunk.  h_self[b] = the dense index of slot b's changer in the fit or -1,
+// h_qrank[b] = its place in set order (dense(c) for a fitted one).  A slot without additional rows (bs.ao, the chunk's) reports
+// nothing.  The block is an EnteredPack followed by prev [C * width] (entered_pack_prev): the changer's position in the
+// stored list or -1; `displaced` holds out_other of an entered cell and -1 otherwise.  pos == EN_TAIL marks a cell that the
+// stored list cannot decide (a tail row): the caller resolves it.  Up to six launches, no round trip.
+static constexpr int32_t EN_TAIL = -2;
+inline size_t entered_update_pack_bytes(int32_t C, int32_t width) { return (size_t)C * ((size_t)width * 24 + 4); }
+inline int32_t* entered_pack_prev(const EnteredPack& p, int32_t C) { return p.counts + C; }
+void entered_update_chunk(const Train& tr, const NeighborTable& nt, QueryBatchScratch& bs, int32_t C, int32_t take, int32_t width,
+                          const int64_t* h_qo, const int32_t* h_self, const int32_t* h_qrank, hipStream_t st);
 
 // ---- reco_batch.hip: recommendations :651-674 for users of the fit (knncf_recommend, knncf_recommend_batch; DESIGN.md "Batched
 // recommendations") ----

@@ -178,4 +178,171 @@ void entered_chunk(const Train& tr, const NeighborTable& nt, QueryBatchScratch& 
     KN_HIP(hipGetLastError());
 }
 
+// ---- entered queries of update queries (DESIGN.md "Entered queries of update queries"; knncf_update_entered*) ----------------
+// The changer c of a slot may be a user of the fit (self[b] = dense(c) >= 0): it stands in stored lists already, so it can move
+// or leave as well as enter.  Adding rows to c changes c's mean and deviations only: S(v, x) of every other pair is the fit's,
+// and v's list on aug is v's list on train with one candidate's key changed.  bs.sim [C][U] holds S(c, v) on aug (an update
+// chunk of foldin.hip), which is S(v, c) bit for bit under the handles the call accepts.  The stages:
+//   k_enu_locate  was[b][v] = the cell of v's stored list that holds dense(c_b), one pass over nt.idx for the whole chunk
+//   k_enu_flag    one thread per (slot, v): the report rule; the ballots are the slot's bitmap (k_en_compact is reused)
+//   k_enu_place   one wave per reported cell: the five outputs; a cell the stored list cannot decide is marked EN_TAIL
+// A slot with self[b] < 0 is a newcomer's: was = -1 everywhere, and the three kernels do what k_en_flag / k_en_place do.
+
+static constexpr int LOC_BITS = 32768;  // cells of k_enu_locate's filter: 4 KB of LDS whatever U is
+
+// One wave per fitted user v (grid-stride), a workgroup's four waves share the chunk's changers: who[b] = self[b] and a filter
+// of LOC_BITS bits over dense user mod LOC_BITS.  A cell of v's list probes the filter; a hit (a changer, or one of the C / 32768
+// of the other users that share a changer's bit) is compared with the <= 64 changers themselves, and each slot whose changer it
+// is gets the cell's position.  One raw id may be the changer of several slots.  was [C][U] is -1 beforehand (the launcher's).
+// Bounds.  C <= QB_MAX_CHUNK = 64 <= TPB.  v < U; cells [0, min(cnt[v], kcap)) of v's kcap are read; a stored id is a dense
+// user of [0, U), so the filter index is < LOC_BITS and the written cell b * U + v < C * U.
+__global__ void __launch_bounds__(TPB) k_enu_locate(int32_t C, int32_t U, int32_t kcap, const int32_t* __restrict__ self,
+                                                    const int32_t* __restrict__ cnt, const int32_t* __restrict__ idx,
+                                                    int32_t* __restrict__ was) {
+    __shared__ uint32_t filt[LOC_BITS / 32];
+    __shared__ int32_t who[QB_MAX_CHUNK];
+    for (int i = threadIdx.x; i < LOC_BITS / 32; i += TPB) filt[i] = 0u;
+    __syncthreads();
+    if ((int32_t)threadIdx.x < C) {
+        const int32_t c = self[threadIdx.x];
+        who[threadIdx.x] = c;
+        if (c >= 0) atomicOr(&filt[((uint32_t)c & (LOC_BITS - 1)) >> 5], 1u << (c & 31));
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    for (int64_t v = (int64_t)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6); v < U; v += (int64_t)gridDim.x * (TPB / 64)) {
+        const int32_t L = min(cnt[v], kcap);
+        const int32_t* li = idx + v * kcap;
+        for (int32_t j = lane; j < L; j += 64) {
+            const int32_t x = li[j];
+            if (!((filt[((uint32_t)x & (LOC_BITS - 1)) >> 5] >> (x & 31)) & 1u)) continue;
+            for (int32_t b = 0; b < C; ++b)
+                if (who[b] == x) was[(int64_t)b * U + v] = j;
+        }
+    }
+}
+
+// One thread per (slot b, dense user v), laid out as k_en_flag's.  v is reported iff c occurs in its list on train or on aug,
+// but for a c that stays where it is with a similarity of +-0.0 of the same bits (no term of any fold), and for a fitted c
+// without additional rows (aug is train; ao [C + 1] = the first additional row of each slot, as the update chunk uploaded it).
+//   was < 0   c is not in the stored list: it enters under k_en_flag's rule, `at` = dense(c) for a fitted c (its place in set
+//             order), the number of train users in front of it for a newcomer
+//   was >= 0  c is in the stored list, so v is reported unless the new similarity has the stored cell's bits (the same key, the
+//             same place) and is +-0.0
+// Bounds.  As k_en_flag; was[b * U + v] and sim[b * U + v] with b < C, v < U; the stored cell v * kcap + was < U * kcap.
+__global__ void __launch_bounds__(TPB) k_enu_flag(int32_t C, int32_t U, int32_t take, int32_t kcap, const int32_t* __restrict__ self,
+                                                  const int32_t* __restrict__ qrank, const int64_t* __restrict__ ao,
+                                                  const double* __restrict__ sim, const int32_t* __restrict__ was,
+                                                  const int32_t* __restrict__ cnt, const int32_t* __restrict__ idx,
+                                                  const double* __restrict__ nsim, unsigned long long* __restrict__ bits) {
+    const int64_t Wu = ((int64_t)U + 63) >> 6, Upad = Wu << 6;
+    const int64_t g = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (g >= (int64_t)C * Upad) return;  // (whole waves: C * Upad is a multiple of 64)
+    const int32_t b = (int32_t)(g / Upad), v = (int32_t)(g - (int64_t)b * Upad);
+    bool f = false;
+    if (v < U && v != self[b] && ao[b + 1] > ao[b]) {
+        const double s = sim[(int64_t)b * U + v];
+        const int32_t w = was[(int64_t)b * U + v];
+        if (w >= 0) {
+            f = __double_as_longlong(s) != __double_as_longlong(nsim[(int64_t)v * kcap + w]) || s != 0.0;
+        } else {
+            f = true;
+            if (cnt[v] >= take) {
+                const int64_t last = (int64_t)v * kcap + take - 1;
+                f = !en_before(nsim[last], idx[last], by_sim_key(s), qrank[b]);
+            }
+        }
+    }
+    const unsigned long long word = __ballot(f);
+    if ((threadIdx.x & 63) == 0) bits[(int64_t)b * Wu + (v >> 6)] = word;
+}
+
+// One wave per reported cell (slot b, j), as k_en_place.  p = the OTHER entries of v's stored list that go before c's new key
+// (the list is sorted, c's own cell is skipped), counted 64 cells at a time.
+//   was < 0   k_en_place's answer: pos = p, other = the last entry of a full list; prev = -1
+//   was >= 0  prev = was.  The list is not full, or p < take - 1: c stands at p on aug.  Otherwise c sorts behind every other
+//             stored entry of a full list.  It keeps the last cell when no user is outside the list (take >= U - 1), or when it
+//             held the last cell on train and its key did not get worse: every user outside goes behind c's old place.
+//             Else the best candidate outside decides, which the handle does not have: pos = EN_TAIL, for the host to resolve.
+// Bounds.  As k_en_place.
+__global__ void __launch_bounds__(TPB) k_enu_place(int32_t C, int32_t U, int32_t take, int32_t kcap, int32_t width,
+                                                   const int32_t* __restrict__ qrank, const double* __restrict__ sim,
+                                                   const int32_t* __restrict__ was, const int32_t* __restrict__ cnt,
+                                                   const int32_t* __restrict__ idx, const double* __restrict__ nsim,
+                                                   const int32_t* __restrict__ uid, const int32_t* __restrict__ counts,
+                                                   int32_t* __restrict__ ent, double* __restrict__ osim, int32_t* __restrict__ opos,
+                                                   int32_t* __restrict__ oother, int32_t* __restrict__ oprev) {
+    const int lane = threadIdx.x & 63;
+    const int64_t g = (int64_t)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
+    if (g >= (int64_t)C * width) return;
+    const int32_t b = (int32_t)(g / width), j = (int32_t)(g - (int64_t)b * width);
+    if (j >= counts[b]) return;
+    const int32_t v = __builtin_amdgcn_readfirstlane(ent[g]);
+    const int32_t L = __builtin_amdgcn_readfirstlane(min(cnt[v], kcap)), at = qrank[b];
+    const int32_t w = __builtin_amdgcn_readfirstlane(was[(int64_t)b * U + v]);
+    const double s = sim[(int64_t)b * U + v];
+    const uint64_t ks = by_sim_key(s);
+    const int32_t* li = idx + (int64_t)v * kcap;
+    const double* ls = nsim + (int64_t)v * kcap;
+    int32_t p = 0;
+    for (int32_t base = 0; base < L; base += 64) {
+        const int32_t c = base + lane;
+        const bool first = c < L && c != w && en_before(ls[c], li[c], ks, at);
+        p += __popcll(__ballot(first));
+    }
+    if (lane != 0) return;
+    const bool full = L >= take && L > 0;
+    int32_t pos = p, other = -1;
+    if (w < 0) {
+        if (full) other = uid[li[L - 1]];
+    } else if (full && p >= take - 1) {
+        const bool kept = take >= U - 1 || (w == take - 1 && ks <= by_sim_key(ls[w]));
+        if (!kept) pos = EN_TAIL;
+    }
+    ent[g] = uid[v];
+    osim[g] = s;
+    opos[g] = pos;
+    oother[g] = other;
+    oprev[g] = w;
+}
+
+void entered_update_chunk(const Train& tr, const NeighborTable& nt, QueryBatchScratch& bs, int32_t C, int32_t take, int32_t width,
+                          const int64_t* h_qo, const int32_t* h_self, const int32_t* h_qrank, hipStream_t st) {
+    const int32_t U = tr.U;
+    const int64_t W = ceil_div(tr.I, 64);
+    bs.by_qrank.ensure(C);
+    bs.en_pack.ensure((entered_update_pack_bytes(C, width) + 7) / 8);
+    const EnteredPack out = entered_pack(bs.en_pack.p, C, width);
+    int32_t* prev = entered_pack_prev(out, C);
+    KN_HIP(hipMemcpyAsync(bs.by_qrank.p, h_qrank, (size_t)C * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    // a newcomer of <= 4 rows folds in its given order (k_en_pair); a fitted cosine changer has > 4 rows on the accepted handles
+    bool small = false;
+    int32_t fitted = 0;
+    for (int32_t b = 0; b < C; ++b) {
+        small |= h_self[b] < 0 && h_qo[b + 1] - h_qo[b] <= 4;
+        fitted += h_self[b] >= 0;
+    }
+    KN_TRACE_DISPATCH("entered_update slots=%d fitted=%d pair=%d width=%d", (int)C, (int)fitted, (int)(small && !tr.jaccard), (int)width);
+    if (small && !tr.jaccard)  // (slots of > 4 rows return at once: a fitted changer's cell stays)
+        k_en_pair<<<(unsigned)ceil_div((int64_t)C * U, TPB), TPB, 0, st>>>(C, U, W, bs.qo.p, bs.di.p, bs.given_d.p, bs.pre_d.p, bs.rank.p,
+                                                                           tr.u_ptr.p, tr.s_col.p, tr.s_pre.p, bs.sim.p);
+    // the bitmaps and their prefixes as entered_chunk keeps them; was [C][U] lies in the chunk's sort values ([C * max(U, I)]
+    // 32-bit cells), free like the keys
+    const int64_t Wu = ceil_div(U, 64);
+    unsigned long long* ebits = (unsigned long long*)bs.k64_b.p;
+    int32_t* was = (int32_t*)bs.v32_a.p;
+    KN_HIP(hipMemsetAsync(was, 0xff, (size_t)C * U * sizeof(int32_t), st));  // -1
+    if (fitted > 0)
+        k_enu_locate<<<(unsigned)std::min<int64_t>(ceil_div(U, TPB / 64), 4096), TPB, 0, st>>>(C, U, nt.kcap, bs.self.p, nt.cnt.p,
+                                                                                              nt.idx.p, was);
+    k_enu_flag<<<(unsigned)ceil_div((int64_t)C * Wu * 64, TPB), TPB, 0, st>>>(C, U, take, nt.kcap, bs.self.p, bs.by_qrank.p, bs.ao.p,
+                                                                              bs.sim.p, was, nt.cnt.p, nt.idx.p, nt.sim.p, ebits);
+    k_en_compact<<<C, ONE_BLOCK, 0, st>>>(U, width, ebits, (int64_t*)bs.k64_a.p, out.users, out.counts);
+    if (width > 0)
+        k_enu_place<<<(unsigned)ceil_div((int64_t)C * width, TPB / 64), TPB, 0, st>>>(C, U, take, nt.kcap, width, bs.by_qrank.p, bs.sim.p,
+                                                                                     was, nt.cnt.p, nt.idx.p, nt.sim.p, tr.uid.p, out.counts,
+                                                                                     out.users, out.sims, out.pos, out.displaced, prev);
+    KN_HIP(hipGetLastError());
+}
+
 }  // namespace knncf

@@ -137,6 +137,7 @@ EXPORTS = [
     "knncf_update_bystander_neighbors", "knncf_update_bystander_predict",
     "knncf_update_bystander_neighbors_batch", "knncf_update_bystander_predict_batch",
     "knncf_query_entered", "knncf_query_entered_batch",
+    "knncf_update_entered", "knncf_update_entered_batch",
     "knncf_predict_batch",
     "knncf_predict_batch_device", "knncf_mae", "knncf_mae_device", "knncf_mae_sweep", "knncf_mae_sweep_device", "knncf_shard_view_get",
     "knncf_shard_commit", "knncf_get_timings", "knncf_reset_timings", "knncf_reset_neighbors",
@@ -259,6 +260,11 @@ def load_library():
                                                                       _i32p, _i32p, _f64p, _i32p]
     # entered queries: the fold-in query, cap, then users / sims / positions / displaced and the count(s)
     L.knncf_query_entered.argtypes = [C.c_void_p, C.c_int32, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p, _i32p, _i32p]
+    # the same for update queries: users / sims / positions / previous / other and the count(s)
+    L.knncf_update_entered.argtypes = [C.c_void_p, C.c_int32, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p, _i32p, _i32p,
+                                       _i32p]
+    L.knncf_update_entered_batch.argtypes = [C.c_void_p, _i32p, _i64p, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p, _i32p,
+                                             _i32p, _i32p, _i32p]
     L.knncf_query_entered_batch.argtypes = [C.c_void_p, _i32p, _i64p, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p, _i32p,
                                             _i32p, _i32p]
     # revise queries: the update argument lists with the removals in front of the additional rows
@@ -1336,6 +1342,52 @@ class EnteredQueries:
                                                             p(sims, _f64p), p(pos, _i32p), p(disp, _i32p), C.byref(c)))
             m = min(c.value, cap)
             return (us[:m].copy(), sims[:m].copy(), pos[:m].copy(), disp[:m].copy()), c.value
+
+        if cap is None:
+            cap = call(0)[1]
+        return call(cap)[0]
+
+    def _call_with(self, qargs, B, cap):
+        """one knncf_update_entered_batch call: (users, sims, positions, previous, other) [B, cap], counts, statuses"""
+        out = (np.empty((B, cap), dtype=np.int32), np.empty((B, cap), dtype=np.float64), np.empty((B, cap), dtype=np.int32),
+               np.empty((B, cap), dtype=np.int32), np.empty((B, cap), dtype=np.int32))
+        counts = np.zeros(B, dtype=np.int32)
+        st = np.zeros(B, dtype=np.int32)
+        p = self._e._ptr
+        self._e._check(self._e._lib.knncf_update_entered_batch(
+            self._e._h, *qargs, cap, *(p(a.reshape(-1), _f64p if a.dtype == np.float64 else _i32p) for a in out), p(counts, _i32p),
+            p(st, _i32p)))
+        return out, counts, st
+
+    def entered_with_batch(self, queries, cap=None):
+        """entered_with() of every (user, items, ratings) of `queries`: ([(users, sims, positions, previous, other)] per query,
+        statuses int32 [B]); a failed query has empty arrays.  cap=None asks for the counts first, then for all entries."""
+        qargs, keep = self._e._batch_args("update", queries)
+        B, cap = qargs[-1], self._cap(cap)
+        if cap is None:
+            _, counts, _ = self._call_with(qargs, B, 0)
+            cap = int(counts.max()) if B else 0
+        out, counts, st = self._call_with(qargs, B, cap)
+        return [tuple(a[b, :min(counts[b], cap)].copy() for a in out) for b in range(B)], st
+
+    def entered_with(self, user, items, ratings, cap=None):
+        """knncf_update_entered: `user` may be IN the fit and (items, ratings) are its ADDITIONAL ratings.  The fitted users v
+        whose kNN list holds `user` on train or on train ++ those ratings, in the fit's set order: (users, sims = S(v, user) on
+        aug, positions of `user` in v's list on aug or -1 if it left, previous = its position on train or -1 if it entered,
+        other = the raw id that left the list (entered) or came into it (left), else -1).  cap=None asks for the count first."""
+        q, it, rt = self._e._query_rows(user, items, ratings, allow_empty=True)
+        cap = self._cap(cap)
+        p = self._e._ptr
+
+        def call(cap):
+            us, pos, prev, other = (np.empty(cap, dtype=np.int32) for _ in range(4))
+            sims = np.empty(cap, dtype=np.float64)
+            c = C.c_int32()
+            self._e._check(self._e._lib.knncf_update_entered(self._e._h, q, p(it, _i32p), p(rt, _f64p), len(it), cap, p(us, _i32p),
+                                                             p(sims, _f64p), p(pos, _i32p), p(prev, _i32p), p(other, _i32p),
+                                                             C.byref(c)))
+            m = min(c.value, cap)
+            return (us[:m].copy(), sims[:m].copy(), pos[:m].copy(), prev[:m].copy(), other[:m].copy()), c.value
 
         if cap is None:
             cap = call(0)[1]
