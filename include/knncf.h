@@ -972,6 +972,50 @@ int knncf_update_entered_batch(knncf_handle* h, const int32_t* users, const int6
                                const double* ratings, int64_t n_queries, int32_t cap, int32_t* out_users, double* out_sims,
                                int32_t* out_pos, int32_t* out_prev, int32_t* out_other, int32_t* counts, int32_t* statuses);
 
+/* ---- Append: new ratings into the fit, the kNN lists they cannot change kept ---------------------------------------------------
+ * The query families above say what new ratings would change; knncf_append makes the n rows (users[j], items[j], ratings[j])
+ * part of the fit.  Rows of several users may interleave; a user may be new or of the fit; items may be new.
+ * Answers.  With aug = train ++ the n rows in the given order, every later call on the handle answers bit for bit as a handle
+ * on which knncf_fit(aug) was called.
+ * Handle state.  B = the users whose neighbour list was built before the call.  S = the changers (the distinct users of the
+ * rows) and every fitted user that knncf_update_entered_batch reports on the handle as it stood before the call for the query
+ * (changer c, c's rows of the append in order), each changer on its own; a tail row is reported, hence in S.  K = B \ S.  The
+ * handle is left in the state that knncf_fit(aug) followed by knncf_neighbors_batch over K in ascending raw id leaves: the same
+ * lists, the same build numbers (call 1, position in K), the call counter of the next build, the same knncf_neighbors_save
+ * bytes wherever the state defines them.  With K empty that is the state of knncf_fit(aug).  No list outside K is built, not
+ * for a user of S and not for a user that had none: the next call that needs one builds it, as after any fit.
+ * Why S is enough.  A list of v outside S holds no changer on train; every changer's similarity to v on aug is the one on the
+ * changer's own aug (v's rows did not move) and sorts behind v's stored last cell; new users and new items keep the relative
+ * set order of the old ones.  So v's list on aug is its list on train.
+ * Outputs.  *n_carried = |K|, *n_dropped = |B ∩ S|; dropped receives the first min(*n_dropped, dropped_cap) raw ids of B ∩ S in
+ * the new fit's user set order and may be null with dropped_cap == 0; cells past the written ones are untouched.
+ * Plain refits.  Nothing is carried (*n_carried = 0, dropped = B; the answers are still those of knncf_fit(aug)) when
+ *   - min(k, num_users' - 1) is not the stored lists' length (a user joined a fit with k >= num_users - 1),
+ *   - the handle is KNNCF_SIM_COSINE and train or aug has a user of 4 or fewer ratings (as the entered calls refuse it; Jaccard
+ *     carries),
+ *   - a changer's update query is KNNCF_E_UNSUPPORTED: a negative mean of its combined rows, more than 65536 of them, or a fit
+ *     of fewer than 5 users or items,
+ *   - the rows have more than KNNCF_APPEND_MAX_CHANGERS distinct users: marking that many costs more than the rebuild it saves
+ *     (DESIGN.md "Append" has the measurement behind the constant),
+ *   - the handle is KNNCF_SIM_ONE: it has no lists, 0 / 0.
+ * Statuses.  KNNCF_E_STATE before a fit; KNNCF_E_UNSUPPORTED on a shard handle; KNNCF_E_INVALID for a null pointer with n > 0
+ * (dropped with dropped_cap > 0), n < 0, dropped_cap < 0, null n_carried / n_dropped; KNNCF_E_DUPLICATE when a row repeats a
+ * (user, item) of train or of the rows; KNNCF_E_NONFINITE for a non-finite deviation.  After any of the last three the handle
+ * answers exactly as before the call: the new fit is built beside the old one and swapped in on success, so a SECOND copy of the
+ * fit's arrays lives on the device during the call.  (The new fit decides from the free device memory at that moment — the old fit's
+ * arrays, its per-item rater bitmaps among them, still allocated — whether it builds its own rater bitmaps: near that threshold an
+ * appended handle can take the no-bitmap prediction path where knncf_fit(aug) would not.  The answers are the same; the speed is
+ * not.)  n == 0 is KNNCF_OK and touches nothing: *n_carried = |B|, *n_dropped = 0.
+ * Everything a refit drops is dropped: the Personalized table, the rater copies, the item statistics.
+ * Timings: the refit and the carry are charged to prep_ms; the marking runs the update queries' neighbour pass, which charges
+ * no stage.
+ * Measurement hook: the environment variable KNNCF_DEBUG_APPEND_MAX_CHANGERS, read at every call, replaces the constant below for
+ * that call (0: every append is a plain refit); scripts/append_latency.py brackets the crossover with it.  Not for production use.
+ * OUT OF SCOPE: removals; a device-pointer form; shard handles and knncf_group_*; the command-line tool. */
+#define KNNCF_APPEND_MAX_CHANGERS 128
+int knncf_append(knncf_handle* h, const int32_t* users, const int32_t* items, const double* ratings, int64_t n,
+                 int64_t* n_carried, int64_t* n_dropped, int32_t* dropped, int64_t dropped_cap);
+
 /* ---- batch ---------------------------------------------------------------- */
 int knncf_predict_batch(knncf_handle* h, int predictor, const int32_t* users,
                         const int32_t* items, int64_t n, double* out);

@@ -74,6 +74,7 @@ struct knncf_handle {
     bool prow_ready = false, prow_checked = false;  // the copies are built; the fitted path's refusals were checked
     QueryBatchScratch query_batch;  // fold-in queries (foldin.hip)
     RecoBatchScratch reco_batch;  // knncf_recommend / knncf_recommend_batch (reco_batch.hip); lends query_batch's prediction and sort buffers
+    AppendScratch append;   // knncf_append (append.hip)
     DArr<int32_t> build_list, build_count;
     DArr<uint32_t> first_row;
     // test scratch
@@ -1020,17 +1021,23 @@ void run_mae_sweep(knncf_handle* h, const int32_t* ks, int32_t n_k, const int32_
     }
 }
 
-void do_fit_device(knncf_handle* h, const int32_t* d_users, const int32_t* d_items, const double* d_ratings, int64_t n) {
-    KN_REQUIRE(n > 0 && d_users && d_items && d_ratings, KNNCF_E_INVALID, "fit: null or empty input");
-    Train& tr = h->tr;
-    hipStream_t st = h->stream;
-    h->fitted = h->committed = false;
+// what the handle derives from a Train and a new one invalidates: the operand panel, the Personalized table and rater copies,
+// the host id caches (a fit and knncf_append's swap)
+void drop_fit_caches(knncf_handle* h) {
     h->short_rows = -1;
     h->b_ready = false;
     h->pt_ready = false;
     h->prow_ready = false;
     h->prow_checked = false;
     h->h_ukeys.clear(); h->h_ikeys.clear(); h->h_uid.clear(); h->h_uptr.clear(); h->h_uavg.clear(); h->h_utable.clear();
+}
+
+void do_fit_device(knncf_handle* h, const int32_t* d_users, const int32_t* d_items, const double* d_ratings, int64_t n) {
+    KN_REQUIRE(n > 0 && d_users && d_items && d_ratings, KNNCF_E_INVALID, "fit: null or empty input");
+    Train& tr = h->tr;
+    hipStream_t st = h->stream;
+    h->fitted = h->committed = false;
+    drop_fit_caches(h);
     tr.n = n;
     tr.jaccard = h->cfg.similarity == KNNCF_SIM_JACCARD;
     {
@@ -2089,6 +2096,205 @@ void do_neighbors_load(knncf_handle* h, const char* path) {
     nt.by_id_valid = false;
     KN_HIP(hipStreamSynchronize(st));
     h->epoch = std::max<int64_t>(hd.epoch, 1);
+}
+
+// ---- knncf_append: new ratings into the fit, the neighbour lists they cannot change kept (append.hip; DESIGN.md "Append") ----
+// The rows are grouped per user in file order: a changer's rows are one update query.  Marking: the changers run through update
+// chunks on the OLD fit, each chunk's report bitmaps (entered_update_flags: the users knncf_update_entered_batch would report,
+// tail rows included) and its fitted changers are ORed into one stale mask on the device.  Then the new Train is built beside
+// the old one from the concatenated rows; the lists of K = built and not stale are carried into the new numbering; the swap
+// comes last, so a refusal on the way leaves the handle as it was.
+struct AppendRows {
+    std::vector<int32_t> changers, items;
+    std::vector<int64_t> offsets;
+    std::vector<double> ratings;
+};
+AppendRows group_append_rows(const int32_t* users, const int32_t* items, const double* ratings, int64_t n) {
+    AppendRows g;
+    std::vector<int32_t> slot_of((size_t)n);
+    std::vector<std::pair<int32_t, int64_t>> by_user((size_t)n);  // (raw user, row): a stable order finds each user's rows
+    for (int64_t j = 0; j < n; ++j) by_user[j] = {users[j], j};
+    std::sort(by_user.begin(), by_user.end());
+    // changers in the order of their first row
+    std::vector<int64_t> first;  // first row of every distinct user, then sorted
+    for (int64_t j = 0; j < n; ++j)
+        if (j == 0 || by_user[j].first != by_user[j - 1].first) first.push_back(by_user[j].second);
+    std::sort(first.begin(), first.end());
+    std::vector<int64_t> count(first.size(), 0);
+    for (int64_t j = 0, s = -1; j < n; ++j) {
+        if (j == 0 || by_user[j].first != by_user[j - 1].first)
+            s = std::lower_bound(first.begin(), first.end(), by_user[j].second) - first.begin();
+        slot_of[by_user[j].second] = (int32_t)s;
+        count[s] += 1;
+    }
+    g.offsets.assign(first.size() + 1, 0);
+    for (size_t s = 0; s < first.size(); ++s) {
+        g.changers.push_back(users[first[s]]);
+        g.offsets[s + 1] = g.offsets[s] + count[s];
+    }
+    g.items.resize((size_t)n); g.ratings.resize((size_t)n);
+    std::vector<int64_t> at(g.offsets.begin(), g.offsets.end() - 1);
+    for (int64_t j = 0; j < n; ++j) {
+        const int64_t p = at[slot_of[j]]++;
+        g.items[p] = items[j];
+        g.ratings[p] = ratings[j];
+    }
+    return g;
+}
+
+// the marking; false: a changer's update query is KNNCF_E_UNSUPPORTED (the plain refit).  Throws a duplicate or a non-finite
+// deviation as the call's status.
+bool mark_stale_lists(knncf_handle* h, const AppendRows& g) {
+    const int64_t B = (int64_t)g.changers.size();
+    std::vector<int32_t> statuses((size_t)B, KNNCF_OK);
+    QueryCall q{};
+    q.family = QF_UPDATE; q.mode = QB_ENTERED; q.predictor = KNNCF_PRED_KNN;
+    q.users = g.changers.data(); q.B = B; q.offsets = g.offsets.data(); q.items = g.items.data(); q.ratings = g.ratings.data();
+    q.statuses = statuses.data();
+    ChunkState cs;
+    cs.take = std::max(0, std::min(h->cfg.k, h->tr.U));
+    const int64_t chunk = query_batch_chunk(h, batch_budget(h));
+    load_host_ids(h);
+    for (int64_t c0 = 0; c0 < B; c0 += chunk) {
+        const int64_t c1 = std::min(B, c0 + chunk);
+        const bool all = pack_chunk(h, q, cs, c0, c1) == c1 - c0 && settle_chunk(h, q, cs, nullptr) == (size_t)cs.C;
+        if (!all) {
+            for (const int status : {KNNCF_E_DUPLICATE, KNNCF_E_NONFINITE})  // (the fit's order of precedence)
+                for (int64_t b = c0; b < c1; ++b)
+                    if (statuses[b] == status)
+                        throw Error(status, "append: user " + std::to_string(g.changers[b]) +
+                                                (status == KNNCF_E_DUPLICATE ? ": a row repeats a (user, item) of train or of the rows"
+                                                                             : ": scale() == 0 gives a non-finite deviation"));
+            return false;
+        }
+        cs.qrank.resize((size_t)cs.C);
+        for (int32_t s = 0; s < cs.C; ++s) {
+            const uint32_t qkey = int_trie_key(cs.s_users[s]);
+            cs.qrank[s] = (int32_t)(std::lower_bound(h->h_ukeys.begin(), h->h_ukeys.end(), qkey) - h->h_ukeys.begin());
+        }
+        const unsigned long long* bits = entered_update_flags(h->tr, h->nt, h->query_batch, cs.C, cs.take, cs.qo.data(), cs.s_self.data(),
+                                                              cs.qrank.data(), h->stream);
+        append_mark(h->append, h->tr.U, cs.C, bits, h->query_batch.self.p, h->stream);
+    }
+    return true;
+}
+
+void do_append(knncf_handle* h, const int32_t* users, const int32_t* items, const double* ratings, int64_t n, int64_t* n_carried,
+               int64_t* n_dropped, int32_t* dropped, int64_t dropped_cap) {
+    require_fitted(h, false);
+    KN_REQUIRE(h->cfg.shard_count == 1, KNNCF_E_UNSUPPORTED, "append: single-shard handles only");
+    KN_REQUIRE(n >= 0 && n_carried && n_dropped && dropped_cap >= 0 && (dropped_cap == 0 || dropped) &&
+                   (n == 0 || (users && items && ratings)),
+               KNNCF_E_INVALID, "append: null argument, n < 0 or dropped_cap < 0");
+    Train& tr = h->tr;
+    NeighborTable& nt = h->nt;
+    AppendScratch& as = h->append;
+    hipStream_t st = h->stream;
+    const int32_t U = tr.U;
+    h->prep.join_commit(st);
+    append_begin(as, U, st);
+    int64_t totals[2] = {0, 0};
+    auto fetch_totals = [&] {
+        KN_HIP(hipMemcpyAsync(totals, as.totals.p, sizeof totals, hipMemcpyDeviceToHost, st));
+        KN_HIP(hipStreamSynchronize(st));
+    };
+    if (n == 0) {  // touches nothing: |B| from the build numbers
+        append_sets(as, tr, nt, false, 0, st);
+        fetch_totals();
+        *n_carried = totals[0];
+        *n_dropped = 0;
+        return;
+    }
+    KN_REQUIRE(tr.n + n < ((int64_t)1 << 29), KNNCF_E_UNSUPPORTED, "append: more than 2^29-1 ratings");
+    const AppendRows g = group_append_rows(users, items, ratings, n);
+    const int64_t n_changers = (int64_t)g.changers.size();
+    // ---- the plain refits that the rows alone decide
+    load_host_ids(h);
+    int32_t joined = 0;
+    bool short_newcomer = false;
+    for (int64_t b = 0; b < n_changers; ++b)
+        if (dense_lookup(h->h_ukeys.data(), U, g.changers[b]) < 0) {
+            joined += 1;
+            short_newcomer |= g.offsets[b + 1] - g.offsets[b] <= 4;
+        }
+    // (KNNCF_DEBUG_APPEND_MAX_CHANGERS: measurement hook of scripts/append_latency.py, which locates the crossover behind the
+    // constant — another limit, 0 = every append is a plain refit)
+    const char* limit = getenv("KNNCF_DEBUG_APPEND_MAX_CHANGERS");
+    const int64_t max_changers = limit ? atoll(limit) : KNNCF_APPEND_MAX_CHANGERS;
+    const int32_t new_kcap = std::max(0, std::min(h->cfg.k, U + joined - 1));
+    const bool no_lists = h->cfg.similarity == KNNCF_SIM_ONE || nt.kcap <= 0 || h->epoch == 1;  // (no call has built one since the fit)
+    bool plain = h->cfg.similarity == KNNCF_SIM_ONE || new_kcap != nt.kcap || nt.k != h->cfg.k ||
+                 n_changers > max_changers ||
+                 // (the update queries refuse such a fit: the id sets change their iteration class below five members)
+                 U < 5 || tr.I < 5 ||
+                 (h->cfg.similarity == KNNCF_SIM_COSINE && (short_newcomer || has_short_rows(h)));
+    // ---- marking, on the old fit
+    if (!plain && !no_lists) plain = !mark_stale_lists(h, g);
+    // ---- the new Train beside the old one
+    Train next;
+    next.n = tr.n + n;
+    next.jaccard = tr.jaccard;
+    {
+        Stage s(h, &h->tm.prep_ms);
+        next.user_raw.alloc(next.n); next.item_raw.alloc(next.n); next.rating.alloc(next.n);
+        KN_HIP(hipMemcpyAsync(next.user_raw.p, tr.user_raw.p, tr.n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        KN_HIP(hipMemcpyAsync(next.item_raw.p, tr.item_raw.p, tr.n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        KN_HIP(hipMemcpyAsync(next.rating.p, tr.rating.p, tr.n * sizeof(double), hipMemcpyDeviceToDevice, st));
+        KN_HIP(hipMemcpyAsync(next.user_raw.p + tr.n, users, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        KN_HIP(hipMemcpyAsync(next.item_raw.p + tr.n, items, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        KN_HIP(hipMemcpyAsync(next.rating.p + tr.n, ratings, n * sizeof(double), hipMemcpyHostToDevice, st));
+        prep_fit(next, h->prep, h->cfg.shard_rank, h->cfg.shard_count, st);  // (throws a duplicate or a non-finite deviation)
+        prep_commit(next, h->prep, st);
+    }
+    KN_REQUIRE(next.U == U + joined, KNNCF_E_STATE, "append: the new fit's users are not the old ones and the newcomers");
+    // ---- K, B ∩ S, the dropped ids (old dense order = new set order: the map is monotone)
+    const bool tiny = U < 5 && next.U >= 5;  // (the user set changed its iteration class: the few ids are ordered on the host)
+    append_sets(as, tr, nt, plain, tiny ? U : dropped_cap, st);
+    const bool moved = !plain && next.U != U;
+    NeighborTable table;
+    if (!plain) {
+        Stage s(h, &h->tm.prep_ms);
+        if (moved) {
+            const size_t cells = (size_t)next.U * (size_t)std::max(nt.kcap, 1);
+            table.idx.alloc(cells); table.sim.alloc(cells); table.cnt.alloc(next.U); table.seq.alloc(next.U);
+            KN_HIP(hipMemsetAsync(table.cnt.p, 0, next.U * sizeof(int32_t), st));
+            KN_HIP(hipMemsetAsync(table.seq.p, 0xff, next.U * sizeof(int64_t), st));  // -1
+            append_remap(as, tr, next.ukeys.p, next.U, st);
+            append_number(as, h->prep.sort, tr, as.map.p, table.seq.p, st);
+            append_carry(as, U, nt, table, st);
+        } else {
+            append_clear(as, U, nt.cnt.p, nt.seq.p, st);
+            append_number(as, h->prep.sort, tr, nullptr, nt.seq.p, st);
+        }
+    }
+    fetch_totals();
+    const int64_t built = totals[0] + totals[1];
+    std::vector<int32_t> ids((size_t)std::min<int64_t>(totals[1], tiny ? U : dropped_cap));
+    if (!ids.empty()) {
+        KN_HIP(hipMemcpyAsync(ids.data(), as.dropped.p, ids.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        KN_HIP(hipStreamSynchronize(st));
+        if (tiny) {
+            std::sort(ids.begin(), ids.end(), [](int32_t a, int32_t b) { return int_trie_key(a) < int_trie_key(b); });
+            ids.resize((size_t)std::min<int64_t>((int64_t)ids.size(), dropped_cap));
+        }
+        std::copy(ids.begin(), ids.end(), dropped);
+    }
+    // ---- the swap
+    h->tr = std::move(next);
+    drop_fit_caches(h);
+    if (plain) {
+        reset_neighbors(h);
+    } else {
+        if (moved) {
+            nt.idx = std::move(table.idx); nt.sim = std::move(table.sim); nt.cnt = std::move(table.cnt); nt.seq = std::move(table.seq);
+        }
+        nt.by_id_valid = false;
+        h->epoch = totals[0] > 0 ? 2 : 1;
+    }
+    *n_carried = totals[0];
+    *n_dropped = totals[1];
+    KN_TRACE_DISPATCH("append changers=%lld built=%lld carried=%lld dropped=%lld moved=%d plain=%d", (long long)n_changers,
+                      (long long)built, (long long)totals[0], (long long)totals[1], (int)moved, (int)plain);
 }
 
 }  // namespace
@@ -3211,6 +3417,11 @@ int knncf_update_entered_batch(knncf_handle* h, const int32_t* users, const int6
     return query_batch(h, entered_call({.family = QF_UPDATE, .users = users, .B = n_queries, .offsets = offsets, .items = items,
                                         .ratings = ratings, .statuses = statuses, .out_pos = out_pos, .out_displaced = out_other,
                                         .out_prev = out_prev}, cap, out_users, out_sims, counts));
+}
+
+int knncf_append(knncf_handle* h, const int32_t* users, const int32_t* items, const double* ratings, int64_t n, int64_t* n_carried,
+                 int64_t* n_dropped, int32_t* dropped, int64_t dropped_cap) {
+    return guarded(h, [&] { do_append(h, users, items, ratings, n, n_carried, n_dropped, dropped, dropped_cap); });
 }
 
 int knncf_neighbors_save(knncf_handle* h, const char* path) {

@@ -110,6 +110,16 @@ struct DArr {
     DArr() = default;
     DArr(const DArr&) = delete;
     DArr& operator=(const DArr&) = delete;
+    // (moves: knncf_append builds a second Train beside the handle's and swaps it in)
+    DArr(DArr&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    DArr& operator=(DArr&& o) noexcept {
+        if (this != &o) {
+            release();
+            p = o.p; n = o.n;
+            o.p = nullptr; o.n = 0;
+        }
+        return *this;
+    }
     ~DArr() { release(); }
     void release() {
         if (p) (void)hipFree(p);
@@ -203,6 +213,8 @@ inline bool lds_bitmap_fits(int64_t words) { return words * 12 <= 48 * 1024 && !
 // (the id path, per-user LDS sorts or global radix sorts, the lengths of the two segment lists of k_classify_rows — read
 // back from the status words under the hook only — and which fold orders were built), and radix_sort one line per sort,
 //   "sort key=<32|64> n=<n> tiles=<t> passes=<p> scan=<self|kernel>".)
+// (KNNCF_DEBUG_APPEND_MAX_CHANGERS: measurement hook of knncf_append — api.cpp: do_append reads it at every call in place of
+// KNNCF_APPEND_MAX_CHANGERS; 0 makes every append a plain refit.  include/knncf.h "Append".)
 inline bool trace_setup_stage() {
     const char* v = getenv("KNNCF_DEBUG_TRACE_DISPATCH");
     return v && strcmp(v, "setup") == 0;

@@ -530,6 +530,40 @@ inline size_t entered_update_pack_bytes(int32_t C, int32_t width) { return (size
 inline int32_t* entered_pack_prev(const EnteredPack& p, int32_t C) { return p.counts + C; }
 void entered_update_chunk(const Train& tr, const NeighborTable& nt, QueryBatchScratch& bs, int32_t C, int32_t take, int32_t width,
                           const int64_t* h_qo, const int32_t* h_self, const int32_t* h_qrank, hipStream_t st);
+// the first stage of entered_update_chunk alone: the chunk's report bitmaps [C][ceil(U / 64)], bit v of row b = fitted user v is
+// reported for slot b (tail rows included; a user without a built list is reported whenever the changer is not in it).  They
+// lie in the chunk's sort keys until the next chunk.  No trace line, no round trip.
+const unsigned long long* entered_update_flags(const Train& tr, const NeighborTable& nt, QueryBatchScratch& bs, int32_t C, int32_t take,
+                                               const int64_t* h_qo, const int32_t* h_self, const int32_t* h_qrank, hipStream_t st);
+
+// ---- append.hip: new ratings into the fit, the neighbour lists they cannot change kept (knncf_append; DESIGN.md "Append") ----
+// Everything here is over the OLD fit's dense users (U of them, Wu = ceil(U / 64) bitmap words) unless said otherwise.
+struct AppendScratch {
+    DArr<unsigned long long> stale;  // [Wu] users whose list the append may change: the changers and every reported user
+    DArr<unsigned long long> kept, gone;  // [Wu] built and not stale (K) / built and stale (B ∩ S)
+    DArr<int64_t> pre;               // [max(U, Wu) + 1] scan cells
+    DArr<uint32_t> k_a, k_b, v_a, v_b;  // [U] the users by ascending raw id (keys: the raw id with its sign bit flipped)
+    DArr<int32_t> map;               // [U] old dense user -> new dense user
+    DArr<int32_t> dropped;           // [min(cap, U)] raw ids of B ∩ S in dense order
+    DArr<int64_t> totals;            // [2] |K|, |B ∩ S|
+};
+// stale = 0
+void append_begin(AppendScratch& as, int32_t U, hipStream_t st);
+// stale |= the OR of a chunk's report bitmaps (entered_update_flags) and the chunk's fitted changers (d_self [C], -1: a newcomer)
+void append_mark(AppendScratch& as, int32_t U, int32_t C, const unsigned long long* d_bits, const int32_t* d_self, hipStream_t st);
+// as.kept / as.gone from nt.seq (all: every built list counts as stale — the plain refit), as.totals, and the first
+// min(|B ∩ S|, cap) raw ids of B ∩ S in dense order into as.dropped.  Two launches.
+void append_sets(AppendScratch& as, const Train& tr, const NeighborTable& nt, bool all, int64_t cap, hipStream_t st);
+// as.map: the place of every old user among new_ukeys [new_U] (the new fit's trie keys in dense order, new_U > 4)
+void append_remap(AppendScratch& as, const Train& tr, const uint32_t* new_ukeys, int32_t new_U, hipStream_t st);
+// the build numbers knncf_neighbors_batch over K in ascending raw id gives: seq[map[v]] = 1 << 32 | rank of uid[v] among K, for
+// v in K (map == nullptr: the identity).  One sort of U keys, one single-block scan.
+void append_number(AppendScratch& as, SortWorkspace& ws, const Train& tr, const int32_t* d_map, int64_t* d_seq, hipStream_t st);
+// the table stays (no user joined): cnt = 0 and seq = -1 for every user outside K
+void append_clear(AppendScratch& as, int32_t U, int32_t* d_cnt, int64_t* d_seq, hipStream_t st);
+// the table moves: row map[v] of `to` (cleared beforehand: cnt 0, seq -1) = row v of `from` for v in K, ids through the map,
+// similarities verbatim; both tables have from.kcap cells per row
+void append_carry(AppendScratch& as, int32_t U, const NeighborTable& from, NeighborTable& to, hipStream_t st);
 
 // ---- reco_batch.hip: recommendations :651-674 for users of the fit (knncf_recommend, knncf_recommend_batch; DESIGN.md "Batched
 // recommendations") ----

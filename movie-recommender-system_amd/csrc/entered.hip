@@ -306,14 +306,15 @@ __global__ void __launch_bounds__(TPB) k_enu_place(int32_t C, int32_t U, int32_t
     oprev[g] = w;
 }
 
-void entered_update_chunk(const Train& tr, const NeighborTable& nt, QueryBatchScratch& bs, int32_t C, int32_t take, int32_t width,
-                          const int64_t* h_qo, const int32_t* h_self, const int32_t* h_qrank, hipStream_t st) {
+// phase 1 of an update chunk: S(v, c) where it is not bs.sim's cell, the stored cell of every fitted changer (was [C][U]) and
+// the report bitmaps [C][ceil(U / 64)], which are returned.  *was_out = was; *fitted_out / *pair_out = the chunk's fitted changers and
+// whether k_en_pair ran (the caller's trace line).
+static unsigned long long* enu_phase1(const Train& tr, const NeighborTable& nt, QueryBatchScratch& bs, int32_t C, int32_t take,
+                                      const int64_t* h_qo, const int32_t* h_self, const int32_t* h_qrank, int32_t** was_out,
+                                      int32_t* fitted_out, bool* pair_out, hipStream_t st) {
     const int32_t U = tr.U;
     const int64_t W = ceil_div(tr.I, 64);
     bs.by_qrank.ensure(C);
-    bs.en_pack.ensure((entered_update_pack_bytes(C, width) + 7) / 8);
-    const EnteredPack out = entered_pack(bs.en_pack.p, C, width);
-    int32_t* prev = entered_pack_prev(out, C);
     KN_HIP(hipMemcpyAsync(bs.by_qrank.p, h_qrank, (size_t)C * sizeof(int32_t), hipMemcpyHostToDevice, st));
     // a newcomer of <= 4 rows folds in its given order (k_en_pair); a fitted cosine changer has > 4 rows on the accepted handles
     bool small = false;
@@ -322,7 +323,6 @@ void entered_update_chunk(const Train& tr, const NeighborTable& nt, QueryBatchSc
         small |= h_self[b] < 0 && h_qo[b + 1] - h_qo[b] <= 4;
         fitted += h_self[b] >= 0;
     }
-    KN_TRACE_DISPATCH("entered_update slots=%d fitted=%d pair=%d width=%d", (int)C, (int)fitted, (int)(small && !tr.jaccard), (int)width);
     if (small && !tr.jaccard)  // (slots of > 4 rows return at once: a fitted changer's cell stays)
         k_en_pair<<<(unsigned)ceil_div((int64_t)C * U, TPB), TPB, 0, st>>>(C, U, W, bs.qo.p, bs.di.p, bs.given_d.p, bs.pre_d.p, bs.rank.p,
                                                                            tr.u_ptr.p, tr.s_col.p, tr.s_pre.p, bs.sim.p);
@@ -337,12 +337,38 @@ void entered_update_chunk(const Train& tr, const NeighborTable& nt, QueryBatchSc
                                                                                               nt.idx.p, was);
     k_enu_flag<<<(unsigned)ceil_div((int64_t)C * Wu * 64, TPB), TPB, 0, st>>>(C, U, take, nt.kcap, bs.self.p, bs.by_qrank.p, bs.ao.p,
                                                                               bs.sim.p, was, nt.cnt.p, nt.idx.p, nt.sim.p, ebits);
+    KN_HIP(hipGetLastError());
+    *was_out = was;
+    *pair_out = small && !tr.jaccard;
+    *fitted_out = fitted;
+    return ebits;
+}
+
+void entered_update_chunk(const Train& tr, const NeighborTable& nt, QueryBatchScratch& bs, int32_t C, int32_t take, int32_t width,
+                          const int64_t* h_qo, const int32_t* h_self, const int32_t* h_qrank, hipStream_t st) {
+    const int32_t U = tr.U;
+    bs.en_pack.ensure((entered_update_pack_bytes(C, width) + 7) / 8);
+    const EnteredPack out = entered_pack(bs.en_pack.p, C, width);
+    int32_t* prev = entered_pack_prev(out, C);
+    int32_t* was = nullptr;
+    int32_t fitted = 0;
+    bool pair = false;
+    unsigned long long* ebits = enu_phase1(tr, nt, bs, C, take, h_qo, h_self, h_qrank, &was, &fitted, &pair, st);
+    KN_TRACE_DISPATCH("entered_update slots=%d fitted=%d pair=%d width=%d", (int)C, (int)fitted, (int)pair, (int)width);
     k_en_compact<<<C, ONE_BLOCK, 0, st>>>(U, width, ebits, (int64_t*)bs.k64_a.p, out.users, out.counts);
     if (width > 0)
         k_enu_place<<<(unsigned)ceil_div((int64_t)C * width, TPB / 64), TPB, 0, st>>>(C, U, take, nt.kcap, width, bs.by_qrank.p, bs.sim.p,
                                                                                      was, nt.cnt.p, nt.idx.p, nt.sim.p, tr.uid.p, out.counts,
                                                                                      out.users, out.sims, out.pos, out.displaced, prev);
     KN_HIP(hipGetLastError());
+}
+
+const unsigned long long* entered_update_flags(const Train& tr, const NeighborTable& nt, QueryBatchScratch& bs, int32_t C, int32_t take,
+                                               const int64_t* h_qo, const int32_t* h_self, const int32_t* h_qrank, hipStream_t st) {
+    int32_t* was = nullptr;
+    int32_t fitted = 0;
+    bool pair = false;
+    return enu_phase1(tr, nt, bs, C, take, h_qo, h_self, h_qrank, &was, &fitted, &pair, st);
 }
 
 }  // namespace knncf

@@ -22,6 +22,7 @@ FLAG_BF16_FILTER = 4  # default filter operand type is fp16 (narrower error band
 FLAG_F32_PANEL = 8    # default similarity panel storage is fp16
 HEAD_ALL = 0xFFFFFFFF
 EXPLAIN_SUM_ORDER, EXPLAIN_BY_WEIGHT = 0, 1  # KNNCF_EXPLAIN_*: the order of the terms of Engine.explain*
+APPEND_MAX_CHANGERS = 128  # KNNCF_APPEND_MAX_CHANGERS: Appends.append with more distinct users carries no list (a plain refit)
 
 _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
@@ -138,6 +139,7 @@ EXPORTS = [
     "knncf_update_bystander_neighbors_batch", "knncf_update_bystander_predict_batch",
     "knncf_query_entered", "knncf_query_entered_batch",
     "knncf_update_entered", "knncf_update_entered_batch",
+    "knncf_append",
     "knncf_predict_batch",
     "knncf_predict_batch_device", "knncf_mae", "knncf_mae_device", "knncf_mae_sweep", "knncf_mae_sweep_device", "knncf_shard_view_get",
     "knncf_shard_commit", "knncf_get_timings", "knncf_reset_timings", "knncf_reset_neighbors",
@@ -267,6 +269,8 @@ def load_library():
                                              _i32p, _i32p, _i32p]
     L.knncf_query_entered_batch.argtypes = [C.c_void_p, _i32p, _i64p, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p, _i32p,
                                             _i32p, _i32p]
+    # append: the rows, then |K|, |B ∩ S| and the dropped raw ids with their cap
+    L.knncf_append.argtypes = [C.c_void_p, _i32p, _i32p, _f64p, C.c_int64, _i64p, _i64p, _i32p, C.c_int64]
     # revise queries: the update argument lists with the removals in front of the additional rows
     for name, at, single in (("neighbors", 2, True), ("predict", 3, True), ("recommend", 3, True), ("explain", 3, True),
                              ("explain_personalized", 2, True), ("neighbors_batch", 2, False), ("predict_batch", 3, False),
@@ -1277,6 +1281,41 @@ class BystanderQueries:
     def predict_with_batch(self, queries, others, pred_items):
         """predict_with of every query: ([float64 array] per query, statuses)"""
         return self._predict_batch("update", queries, others, pred_items)
+
+
+class Appends:
+    """knncf_append on a fitted Engine: new ratings go INTO the fit.  NOT read-only on the engine's handle: the fit becomes
+    train ++ the rows, the neighbour lists the rows cannot change are kept and the other ones dropped.
+
+        carried, dropped = Appends(engine).append(users, items, ratings)"""
+
+    def __init__(self, engine):
+        self._e = engine
+
+    def append(self, users, items, ratings, return_dropped=False):
+        """knncf_append: the rows become part of the fit, and the neighbour lists they cannot change are kept.  Every later
+        answer is that of fit(train ++ rows).  Returns (carried, dropped_count): the built lists that were kept, and those of the
+        changers and of the users whose list holds a changer before or after, which the next call rebuilds; with return_dropped
+        also their raw ids in the new fit's set order (int32 [dropped_count])."""
+        e = self._e
+        u, i, r = np.asarray(users), np.asarray(items), np.asarray(ratings)
+        if not (u.ndim == i.ndim == r.ndim == 1 and len(u) == len(i) == len(r)):
+            raise ValueError("users, items and ratings must be 1-D arrays of one length")
+        for a in (u, i):
+            if len(a) and (a.dtype.kind not in "iu" or a.min() < -2**31 or a.max() >= 2**31):
+                raise ValueError("users and items must be 32-bit integer ids")
+        if len(r) and r.dtype.kind not in "iuf":
+            raise ValueError("ratings must be numbers")
+        u, i, r = _i32(u), _i32(i), _f64(r)
+        carried, gone = C.c_int64(), C.c_int64()
+        cap = e.num_users if return_dropped else 0  # (B ∩ S are users of the fit as it stands)
+        ids = np.empty(max(1, cap), dtype=np.int32)
+        p = e._ptr
+        e._check(e._lib.knncf_append(e._h, p(u, _i32p), p(i, _i32p), p(r, _f64p), len(u), C.byref(carried), C.byref(gone),
+                                           p(ids, _i32p) if cap else None, cap))
+        if return_dropped:
+            return carried.value, gone.value, ids[:gone.value].copy()
+        return carried.value, gone.value
 
 
 class EnteredQueries:
