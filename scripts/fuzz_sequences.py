@@ -1,8 +1,10 @@
 """Randomised call sequences on one handle against the stateful model (run on an MI355X): the hand-run companion of
 scripts/fuzz_parity.py for tests/test_gpu_call_sequences.py.  Fresh seeds beyond the committed ones go through the same
 generator and model (tests/call_sequences.py): per seed an order-sensitive fit (40 users, 18 of them with <= 4 ratings), a
-similarity, a first k and 60 ops.  Stops at the first mismatch or unexpected status and prints the seed and the op to replay;
-nothing is started after an error and nothing is tried twice.
+similarity, a first k and cs.N_OPS ops over every kind of cs.KINDS — those of the classes beside Engine among them: appends
+(which replace the fit and keep lists), entered calls (which build every missing list) and bystander calls.  Stops at the first
+mismatch or unexpected status and prints the seed and the op to replay; nothing is started after an error and nothing is tried
+twice.
 usage: python scripts/fuzz_sequences.py [first_seed] [count]"""
 import importlib
 import os

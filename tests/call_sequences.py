@@ -9,20 +9,31 @@ which the earlier calls built their neighbourhoods: the model plays that history
 
 A call kind is an Engine method with "_device" taken off; the thirty query methods ({neighbors, predict, recommend, explain,
 recommend_explain}_{for, with, revised}[_batch]) are the ten kinds *_q / *_q_batch, the family being an argument; the five
-statistic getters are the kind `statistics`.  kind_of() maps a method name, NOT_MODELLED names the methods left out."""
+statistic getters are the kind `statistics`.  The classes beside Engine that wrap one give the kinds `append` (Appends),
+entered / entered_batch / entered_with / entered_with_batch (EnteredQueries) and bystander_{neighbors, predict}[_batch]
+(BystanderQueries, the family "for" or "with" an argument).  kind_of() maps a method name, NOT_MODELLED names the methods left
+out.
+
+HandleModel.built is the set of raw ids whose neighbourhood the handle has built since the last drop, kept by the rules the
+header states per call; the GPU tests compare it with the build numbers of the parsed checkpoint after every op."""
+import hashlib
 import re
 from dataclasses import dataclass
 
 import numpy as np
 
+from tests import append_cases as ac
+from tests import entered_cases as ec
 from tests import explain_model
 from tests import personalized_explain_model as pm
 from tests import personalized_query_cases as pc
 from tests import query_explain_cases as qc
 from tests import revise_cases as rc
+from tests import update_entered_cases as uc
 from tests.test_oracle_semantics import _cols, _no_zero_scale, _random_case
 
-OK, E_INVALID, E_NONFINITE, E_UNSUPPORTED = 0, -1, -2, -7
+OK, E_INVALID, E_NONFINITE, E_DUPLICATE, E_STATE, E_UNSUPPORTED = 0, -1, -2, -3, -6, -7
+APPEND_MAX_CHANGERS = 128                       # KNNCF_APPEND_MAX_CHANGERS
 PRED_BASELINE, PRED_KNN, PRED_PERSONALIZED = 3, 5, 6
 SUM_ORDER, BY_WEIGHT = explain_model.SUM_ORDER, explain_model.BY_WEIGHT
 MAE_TOL = 1e-9
@@ -30,14 +41,22 @@ ABSENT_USERS = (2_000_000_011, 2_000_000_029)   # ids no fit holds
 ABSENT_ITEM = 2_000_000_017
 NEW_USER = 3_000_000                            # fold-in users: NEW_USER + j, in no fit (small: the oracle's tables span the ids)
 NEW_ITEM = 5_003                                # unknown to every fit, given by some queries
+NEWCOMER = 3_020_000                            # appended newcomers: NEWCOMER + j, a range no query id uses
+APPEND_ITEM = 5_100                             # items that an append brings into the fit: APPEND_ITEM + j (NEW_ITEM itself must
+                                                # stay unknown to every fit: the queries rely on it)
 QB_DUAL_MIN = 32                                # answerable queries from which a batch takes the dual similarity kernel
 FAMILIES = ("for", "with", "revised")
 QUERY_WHATS = ("neighbors", "predict", "recommend", "explain", "recommend_explain")
 
 # what the handle keeps: these advance the memo; the drops replace it; everything else only reads
+ENTERED = ("entered", "entered_batch", "entered_with", "entered_with_batch")  # build every missing list, then only read
 MUTATING = ("neighbors", "neighbors_batch", "predict", "predict_batch", "mae", "recommend", "recommend_batch", "knn_similarity",
-            "knn_similarity_batch", "explain", "explain_batch")
+            "knn_similarity_batch", "explain", "explain_batch") + ENTERED
 DROPS = ("set_k", "reset_neighbors", "mae_sweep", "fit")
+REFITS = ("append",)  # replaces the fit as `fit` does, and keeps some lists
+BYSTANDER = ("bystander_neighbors", "bystander_neighbors_batch", "bystander_predict", "bystander_predict_batch")
+BYSTANDER_FAMILIES = ("for", "with")
+APPEND_SHAPES = ("changer", "newcomer", "both")
 CHECKPOINT = ("neighbors_save", "neighbors_load")
 STATISTICS = ("global_avg", "user_avg", "item_avg", "item_avg_dev", "item_avg_dev_rdd")
 NOT_MODELLED = {
@@ -49,8 +68,13 @@ NOT_MODELLED = {
 DEVICE_FORMS = ("fit", "similarity_batch", "explain_batch", "mae", "mae_sweep")  # kinds with an Engine.<kind>_device
 
 
-def kind_of(method):
-    """the call kind of a public Engine method, None for one of NOT_MODELLED"""
+def kind_of(method, owner="Engine"):
+    """the call kind of a public method of Engine or of a class beside it that wraps one, None for one of NOT_MODELLED"""
+    if owner == "BystanderQueries":
+        m = re.fullmatch(r"(neighbors|predict)_(for|with)(_batch)?", method)
+        return f"bystander_{m.group(1)}{m.group(3) or ''}" if m else method
+    if owner != "Engine":
+        return method  # (Appends.append, EnteredQueries.entered*: the kind is the method; anything else is no kind of KINDS)
     if method in NOT_MODELLED:
         return None
     name = method[:-len("_device")] if method.endswith("_device") else method
@@ -63,7 +87,7 @@ def kind_of(method):
 
 
 def is_read_only(kind):
-    return kind not in MUTATING and kind not in DROPS and kind != "neighbors_load"
+    return kind not in MUTATING and kind not in DROPS and kind not in REFITS and kind != "neighbors_load"
 
 
 # ---- ops ---------------------------------------------------------------------------------------------------------------------
@@ -153,22 +177,38 @@ class HandleModel:
     def __init__(self, oracle, train, sim, k, wrong=""):
         self.oracle, self.sim, self.k, self.wrong = oracle, sim, int(k), wrong
         self.saved = None
+        self.appends, self.entered_missing = [], []  # what every accepted append carried; |M| of every entered call that could build
         self.fit(train)
 
     # ---- plumbing ----
     def call(self, op):
+        """the op's answer.  Afterwards self.definition is None, or — for the kinds that are DEFINED by older calls (append, entered*) —
+        the list of ops through those older calls that leaves a handle in the same state: what a replaying handle plays instead"""
         if self.wrong == "stateless":
-            self._drop()
+            self._closures()  # (the summation history is gone; which lists exist is not a matter of order and stays)
+        self.definition = None
         out = getattr(self, op.kind)(*op.args)
-        if op.kind in MUTATING:
+        if op.kind in MUTATING and op.kind not in ENTERED:  # (an entered call logs the neighbors_batch it is defined by)
             self.log.append(op)
         return out
 
-    def _drop(self):
+    def _closures(self):
         """fresh closures: one pipeline, and the term model that shares its memo"""
         self.p = self.m.pipeline(self.sim, self.k)
         self.tm = explain_model.TermModel(self.oracle, self.m, self.sim, self.k, pipeline=self.p)
+
+    def _drop(self):
+        """fresh closures and no list built"""
+        self._closures()
         self.log = []
+        self.built = set()
+
+    def _builds(self, users):
+        """the known users of `users` have their neighbourhood built from here on"""
+        self.built |= {int(u) for u in np.asarray(users).reshape(-1).tolist() if int(u) in self.known_users}
+
+    def _sim_name(self):
+        return ac.COS if self.sim == self.oracle.SIM_COSINE else ac.JAC
 
     def replica(self):
         """the model of a second handle that loaded this one's checkpoint: a new pipeline onto which the mutating calls so far
@@ -194,12 +234,20 @@ class HandleModel:
         train = train.train if isinstance(train, Fit) else train
         self.train = (np.ascontiguousarray(train[0], np.int32), np.ascontiguousarray(train[1], np.int32),
                       np.ascontiguousarray(train[2], np.float64))
-        self.m = self.oracle.Model(*self.train)
+        self._refit(self.oracle.Model(*self.train), caches=True)
+
+    def _refit(self, m, caches):
+        """everything that follows the fit, from self.train and its Model m.  caches: the statistics and the Personalized answers
+        move to the new fit too (they do not under the wrong model "append_keeps_fit_caches")"""
+        self.m = m
         users, counts = np.unique(self.train[0], return_counts=True)
         self.known_users, self.known_items = set(users.tolist()), set(np.unique(self.train[1]).tolist())
         self.short_fit = bool(counts.min() <= 4)
         assert all(self.m.users_avg(int(u)) >= 0 for u in users), "the model has no clause for fitted users with a negative mean"
-        self._ptm = None
+        if caches:
+            self.mc, self.items_c = m, self.known_items  # the fit behind the statistics getters and the Personalized predictor
+            self._ptm = None
+        self.train_key = hashlib.sha1(b"".join(a.tobytes() for a in self.train)).hexdigest()
         self.saved = None
         self._drop()
 
@@ -241,11 +289,13 @@ class HandleModel:
 
     # ---- knncf_neighbors: getNeighbors(train, k, sim)(u), memoised ----
     def neighbors(self, u):
+        self._builds([u])
         return self.p.neighbors(int(u))
 
     # ---- knncf_neighbors_batch: "numbers every user it is asked about", in the given order, repeated users included ----
     def neighbors_batch(self, users):
         users = np.asarray(users)
+        self._builds(users)
         return self._in_order(users, lambda j: self.p.neighbors(int(users[j])))
 
     # ---- knncf_predict / knncf_predict_batch / knncf_mae: KNNCF_PRED_KNN evaluates the rows in order on the handle's closures;
@@ -255,13 +305,19 @@ class HandleModel:
         users, items = np.asarray(users, np.int32), np.asarray(items, np.int32)
         ratings = np.zeros(len(users)) if ratings is None else np.asarray(ratings, np.float64)
         if predictor == PRED_KNN:
+            self._builds_rows(users, items)
             return self.p.mae(users, items, ratings, True)
         if predictor == PRED_BASELINE:
-            return self.m.mae(self.oracle.KIND_BASELINE, users, items, ratings, True)
+            return self.mc.mae(self.oracle.KIND_BASELINE, users, items, ratings, True)
         assert predictor == PRED_PERSONALIZED
         if self._personalized_refused():
             return None
-        return self.m.pipeline(self.sim, -1).mae(users, items, ratings, True)
+        return self.mc.pipeline(self.sim, -1).mae(users, items, ratings, True)
+
+    def _builds_rows(self, users, items):
+        """the rows of a kNN prediction or explanation where the reference's lazy closure is evaluated (explain_model.TermModel.row):
+        the user is known and the item has raters"""
+        self._builds([u for u, i in zip(np.asarray(users).tolist(), np.asarray(items).tolist()) if int(i) in self.known_items])
 
     def _personalized_refused(self):
         return self.short_fit and self.sim == self.oracle.SIM_COSINE
@@ -283,12 +339,13 @@ class HandleModel:
     # "the other predictors leave the neighbour table alone" ----
     def recommend(self, predictor, u, n):
         if predictor == PRED_KNN:
+            self._builds([u])  # (a known user; fit() has asserted that no mean is negative)
             return self.p.recommend(int(u), int(n))
         if predictor == PRED_BASELINE:
-            return self.m.recommend(self.oracle.KIND_BASELINE, int(u), int(n))
+            return self.mc.recommend(self.oracle.KIND_BASELINE, int(u), int(n))
         if self._personalized_refused():
             return Refused(E_UNSUPPORTED)
-        return self.m.pipeline(self.sim, -1).recommend(int(u), int(n))
+        return self.mc.pipeline(self.sim, -1).recommend(int(u), int(n))
 
     def recommend_batch(self, predictor, users, n):
         if predictor == PRED_PERSONALIZED and self._personalized_refused():
@@ -301,6 +358,7 @@ class HandleModel:
     def knn_similarity(self, u, v):
         if not (self._known(u) and self._known(v)):
             return 0.0
+        self._builds([u])
         return self.p.knn_similarity(int(u), int(v))
 
     def knn_similarity_batch(self, us, vs):
@@ -313,12 +371,14 @@ class HandleModel:
         return self.explain_batch([u], [i], cap, order)[0]
 
     def explain_batch(self, users, items, cap, order):
+        self._builds_rows(users, items)
         return unpad(qc.expected(self.tm.rows(users, items), cap, order), cap)
 
     # ---- read-only from here on: answers from fresh closures, the pipeline is untouched ----
     def _reads(self, u):
         """the wrong model whose read-only calls build: a fitted user's neighbourhood is evaluated on the handle's closures"""
         if self.wrong == "read_only_builds" and self._known(u):
+            self._builds([u])
             self.p.neighbors(int(u))
 
     # knncf_similarity / knncf_similarity_batch: "Every pair is answered on a closure of its OWN", us[j] the first argument
@@ -333,11 +393,12 @@ class HandleModel:
 
     # the fit's statistics: (global_avg, user_avg(u), item_avg_dev(i)[, item_avg(i), item_avg_dev_rdd(i) for an item of the fit])
     def statistics(self, u, i):
-        ua = self.m.users_avg(int(u))
-        dev = self.m.items_avg_dev(int(i))
-        out = (self.m.average(), self.m.average() if ua is None else ua, 0.0 if dev is None else dev)
-        if int(i) in self.known_items:
-            out += (self.m.items_avg(int(i)), self.m.items_avg_dev_spark(int(i)))
+        m = self.mc
+        ua = m.users_avg(int(u))
+        dev = m.items_avg_dev(int(i))
+        out = (m.average(), m.average() if ua is None else ua, 0.0 if dev is None else dev)
+        if int(i) in self.known_items:  # (what the player asks for: the items of the fit as it stands)
+            out += tuple(0.0 if x is None else x for x in (m.items_avg(int(i)), m.items_avg_dev_spark(int(i))))
         return out
 
     # knncf_explain_personalized*: "KNNCF_E_UNSUPPORTED exactly where the fitted KNNCF_PRED_PERSONALIZED refuses"; read-only
@@ -349,7 +410,7 @@ class HandleModel:
         if self._personalized_refused():
             return Refused(E_UNSUPPORTED)
         if self._ptm is None:
-            self._ptm = pm.PersonalTermModel(self.oracle, self.m, self.sim)
+            self._ptm = pm.PersonalTermModel(self.oracle, self.mc, self.sim)
         out = unpad(qc.expected(self._ptm.rows(users, items), cap, order), cap)
         for u in users:
             self._reads(u)
@@ -413,6 +474,138 @@ class HandleModel:
         return [self._query(what, fam, predictor, query, *((params[0][b],) + params[1:] if per_query else params))
                 for b, query in enumerate(queries)]
 
+    # ---- knncf_append: "every later call on the handle answers bit for bit as a handle on which knncf_fit(aug) was called"; "The
+    # handle is left in the state that knncf_fit(aug) followed by knncf_neighbors_batch over K in ascending raw id leaves" ----
+    def append(self, users, items, ratings):
+        users, items = np.asarray(users, np.int32), np.asarray(items, np.int32)
+        ratings = np.asarray(ratings, np.float64)
+        assert len(users), "the generator appends at least one row"
+        self.definition = []
+        pairs = list(zip(users.tolist(), items.tolist()))
+        if len(set(pairs)) < len(pairs) or set(pairs) & set(zip(self.train[0].tolist(), self.train[1].tolist())):
+            return Refused(E_DUPLICATE)  # "the handle answers exactly as before the call"
+        case = ac.Append("append", self.train, users, items, ratings, self.k)
+        aug = case.aug
+        try:
+            m = self.oracle.Model(*aug)
+        except self.oracle.OracleError as ex:
+            if ex.status != E_NONFINITE:
+                raise
+            return Refused(E_NONFINITE)
+        sim, built = self._sim_name(), sorted(self.built)
+        assert len(self.known_users) >= 5 and len(self.known_items) >= 5, "the model has no clause for fits that the update queries refuse"
+        negative = any(aug[2][aug[0] == c].sum() < 0 for c, _, _ in case.changers)  # "a negative mean of its combined rows"
+        plain = (ac.is_plain(case, sim) or (sim == ac.COS and self.short_fit) or negative or len(case.changers) > APPEND_MAX_CHANGERS)
+        order = m.user_iteration_order().tolist()
+        if plain or not built:
+            keep, gone = [], [v for v in order if v in self.built]
+        else:
+            stale = _memo(("stale", self.train_key, users.tobytes(), items.tobytes(), ratings.tobytes(), self.k, sim),
+                          lambda: ac.stale(self.oracle, case, sim))
+            keep, gone = sorted(self.built - stale), [v for v in order if v in self.built and v in stale]
+            if self.wrong == "append_keeps_every_list":
+                keep, gone = built, []
+        self.appends.append({"plain": bool(plain), "built": len(built), "carried": len(keep), "dropped": len(gone)})
+        self.train = aug
+        self._refit(m, caches=self.wrong != "append_keeps_fit_caches")
+        self.definition = [Op("fit", (Fit("aug", aug),))]
+        if keep:
+            op = Op("neighbors_batch", (np.asarray(keep, np.int32),))
+            self.neighbors_batch(*op.args)
+            self.log, self.definition = [op], self.definition + [op]
+        return (len(keep), len(gone), np.asarray(gone, np.int32))
+
+    # ---- knncf_query_entered* / knncf_update_entered*: "Let M be the train users whose neighbourhood the handle has not built, in
+    # ascending raw id.  When the call passes its handle-level checks, n_queries > 0 and M is not empty, it first builds them in ONE
+    # batch and LEAVES THE HANDLE IN THE STATE THAT knncf_neighbors_batch OVER M LEAVES IT IN ... whether or not any query is
+    # answerable"; refused on "a KNNCF_SIM_COSINE handle whose train set has a user with 4 or fewer ratings" ----
+    def _entered(self, fam, queries):
+        self.definition = []
+        if self._personalized_refused():  # (the same condition: the adjusted cosine on a fit with a <= 4-rating user)
+            return Refused(E_UNSUPPORTED)
+        missing = sorted(self.known_users - self.built)
+        if len(queries):
+            self.entered_missing.append(len(missing))
+        if missing and len(queries) and self.wrong != "entered_builds_nothing":
+            op = Op("neighbors_batch", (np.asarray(missing, np.int32),))
+            self.neighbors_batch(*op.args)
+            self.log.append(op)
+            self.definition = [op]
+        out = []
+        for q, removed, items, ratings in queries:
+            q, items, ratings = int(q), np.asarray(items, np.int32), np.asarray(ratings, np.float64)
+            st = self._query_status(fam, (q, removed, items, ratings))
+            if st != OK:
+                out.append(Refused(st))
+                continue
+            key = ("entered", fam, self.train_key, q, items.tobytes(), ratings.tobytes(), self.k, self._sim_name())
+            want = ec.expected_for if fam == "for" else uc.expected_for
+            try:
+                out.append(_memo(key, lambda: want(self.oracle, self.train, q, items, ratings, self.k, self._sim_name())))
+            except self.oracle.OracleError as ex:
+                if ex.status != E_NONFINITE:
+                    raise
+                out.append(Refused(E_NONFINITE))
+        return out
+
+    def entered(self, query):
+        out = self._entered("for", [query])
+        return out if isinstance(out, Refused) else out[0]
+
+    def entered_batch(self, queries):
+        return self._entered("for", queries)
+
+    def entered_with(self, query):
+        out = self._entered("with", [query])
+        return out if isinstance(out, Refused) else out[0]
+
+    def entered_with_batch(self, queries):
+        return self._entered("with", queries)
+
+    # ---- knncf_query_bystander_* / knncf_update_bystander_*: "Every row is answered on closures of its own over aug whose first
+    # evaluation is the row's"; "a query with a row whose others[r] == users[b] gets KNNCF_E_INVALID"; read-only ----
+    def _bystander(self, what, fam, query, others, pred_items=None):
+        q, removed, items, ratings = query
+        q = int(q)
+        st = self._query_status(fam, (q, removed, items, ratings))
+        if st == OK and q in set(np.asarray(others).tolist()):
+            st = E_INVALID
+        if st != OK:
+            return Refused(st)
+        try:
+            m = self.oracle.Model(*rc.aug_of(self.train, q, removed, items, ratings))
+        except self.oracle.OracleError as ex:
+            if ex.status != E_NONFINITE:
+                raise
+            return Refused(E_NONFINITE)
+        self._reads(q)
+        if what == "neighbors":
+            return [m.pipeline(self.sim, self.k).neighbors(int(v)) for v in others]
+        return np.asarray([m.pipeline(self.sim, self.k).predict(int(v), int(i)) for v, i in zip(others, pred_items)], np.float64)
+
+    def bystander_neighbors(self, fam, query, others):
+        return self._bystander("neighbors", fam, query, others)
+
+    def bystander_predict(self, fam, query, others, pred_items):
+        return self._bystander("predict", fam, query, others, pred_items)
+
+    def bystander_neighbors_batch(self, fam, queries, others):
+        return [self._bystander("neighbors", fam, query, others[b]) for b, query in enumerate(queries)]
+
+    def bystander_predict_batch(self, fam, queries, others, pred_items):
+        return [self._bystander("predict", fam, query, others[b], pred_items[b]) for b, query in enumerate(queries)]
+
+
+_memo_cache = {}
+
+
+def _memo(key, make):
+    """make() once per key: the sequences are played many times (premises, both similarities, every GPU test) and the oracle's
+    side of an append or an entered query on a large fit costs seconds"""
+    if key not in _memo_cache:
+        _memo_cache[key] = make()
+    return _memo_cache[key]
+
 
 def _bind_queries():
     for what in QUERY_WHATS:
@@ -422,7 +615,11 @@ def _bind_queries():
 
 _bind_queries()
 KINDS = tuple(sorted(n for n in vars(HandleModel) if not n.startswith("_") and n not in ("call", "replica")))
-WRONG_MODELS = ("stateless", "keeps_after_reset", "keeps_after_sweep", "read_only_builds", "sorted_batches")
+# the last three differ where the new fit of an append or the lists that an entered call builds matter: under Jaccard on the memo
+# fits (under the adjusted cosine every append there is a plain refit and every entered call refused), in an answer or in `built`
+WRONG_MODELS = ("stateless", "keeps_after_reset", "keeps_after_sweep", "read_only_builds", "sorted_batches",
+                "append_keeps_every_list", "append_keeps_fit_caches", "entered_builds_nothing")
+WRONG_AFTER_APPEND = WRONG_MODELS[5:]
 
 
 # ---- playing an op on an Engine ------------------------------------------------------------------------------------------------
@@ -596,6 +793,50 @@ class Player:
         return rows
 
 
+    # the classes beside Engine
+    def append(self, dev, users, items, ratings):
+        carried, dropped, ids = self.kn.Appends(self.e).append(users, items, ratings, return_dropped=True)
+        self.known_items |= set(np.asarray(items).tolist())
+        return (carried, dropped, ids)
+
+    def _entered(self, fam, batch, arg):
+        eq = self.kn.EnteredQueries(self.e)
+        name = "entered" if fam == "for" else "entered_with"
+        if not batch:
+            return tuple(getattr(eq, name)(*self._fam_args(fam, arg)))
+        outs, st = getattr(eq, name + "_batch")([self._fam_args(fam, q) for q in arg])
+        return [tuple(out) if s == OK else Refused(s) for out, s in zip(outs, st.tolist())]
+
+    def entered(self, dev, query):
+        return self._entered("for", False, query)
+
+    def entered_batch(self, dev, queries):
+        return self._entered("for", True, queries)
+
+    def entered_with(self, dev, query):
+        return self._entered("with", False, query)
+
+    def entered_with_batch(self, dev, queries):
+        return self._entered("with", True, queries)
+
+    def bystander_neighbors(self, dev, fam, query, others):
+        return getattr(self.kn.BystanderQueries(self.e), f"neighbors_{fam}")(*self._fam_args(fam, query), np.asarray(others, np.int32))
+
+    def bystander_predict(self, dev, fam, query, others, pred_items):
+        return getattr(self.kn.BystanderQueries(self.e), f"predict_{fam}")(*self._fam_args(fam, query), np.asarray(others, np.int32),
+                                                                          np.asarray(pred_items, np.int32))
+
+    def bystander_neighbors_batch(self, dev, fam, queries, others):
+        outs, st = getattr(self.kn.BystanderQueries(self.e), f"neighbors_{fam}_batch")(
+            [self._fam_args(fam, q) for q in queries], [np.asarray(x, np.int32) for x in others])
+        return [out if s == OK else Refused(s) for out, s in zip(outs, st.tolist())]
+
+    def bystander_predict_batch(self, dev, fam, queries, others, pred_items):
+        outs, st = getattr(self.kn.BystanderQueries(self.e), f"predict_{fam}_batch")(
+            [self._fam_args(fam, q) for q in queries], [np.asarray(x, np.int32) for x in others], [np.asarray(x, np.int32) for x in pred_items])
+        return [out if s == OK else Refused(s) for out, s in zip(outs, st.tolist())]
+
+
 def _bind_player():
     for what in QUERY_WHATS:
         setattr(Player, f"{what}_q", lambda self, *a, _w=what: self._q(_w, *a))
@@ -611,6 +852,7 @@ class _Draw:
         self.rng, self.model, self.k_pool, self.batch_sizes, self.fits, self.life = rng, model, k_pool, batch_sizes, fits, life
         self.big_pairs = {"similarity_batch", "knn_similarity_batch"} if life else set()
         self.new_user, self.k = NEW_USER, model.k
+        self.newcomer, self.append_item = NEWCOMER, APPEND_ITEM
         self.set_train(model.train)
 
     def set_train(self, train):
@@ -618,7 +860,7 @@ class _Draw:
         self.users, counts = np.unique(train[0], return_counts=True)
         self.items = np.unique(train[1])
         assert NEW_ITEM not in self.items and ABSENT_ITEM not in self.items and not np.isin(ABSENT_USERS, self.users).any()
-        assert not ((self.users > NEW_USER) & (self.users < NEW_USER + 10_000)).any()
+        assert not ((self.users > NEW_USER) & (self.users < NEW_USER + 10_000)).any() and NEWCOMER > NEW_USER + 10_000
         self.count = dict(zip(self.users.tolist(), counts.tolist()))
         short = self.users[counts <= 4]
         self.short = short if len(short) else self.users
@@ -709,6 +951,51 @@ class _Draw:
         own = self.train[1][self.train[0] == query[0]][:2]
         return np.concatenate([[self.item() for _ in range(4)], own, query[1][:1], query[2][:1], [ABSENT_ITEM]]).astype(np.int32)
 
+    def append_rows(self, shape):
+        """(users, items, ratings) of an append.  "changer": a fitted user adds 1-3 items it has not rated; "newcomer": a new user
+        of 5-7 rows, sometimes with an item new to the fit; "both": the two interleaved; "duplicate": a changer's rows and a row
+        of train again, which is refused.  An accepted append (the oracle can scale aug) becomes the train set of the later ops."""
+        rng, o = self.rng, self.model.oracle
+        for _ in range(50):
+            parts = []
+            if shape in ("changer", "both", "duplicate"):
+                c = self.fitted()
+                free = np.setdiff1d(self.items, self.train[1][self.train[0] == c])
+                n = min(int(rng.integers(1, 4)), len(free))
+                if n == 0:
+                    continue
+                parts.append((c, rng.choice(free, n, replace=False).astype(np.int32), rng.integers(1, 6, n).astype(np.float64)))
+            if shape in ("newcomer", "both"):
+                self.newcomer += 1
+                items = rng.choice(self.items, min(int(rng.integers(5, 8)), len(self.items)), replace=False).astype(np.int32)
+                if rng.random() < 0.4:
+                    self.append_item += 1
+                    items[int(rng.integers(0, len(items)))] = self.append_item
+                parts.append((self.newcomer, items, rng.integers(1, 6, len(items)).astype(np.float64)))
+            u, i, r = ac.interleave(parts)
+            rows = (np.asarray(u, np.int32), np.asarray(i, np.int32), np.asarray(r, np.float64))
+            aug = tuple(np.concatenate([a, b]).astype(a.dtype) for a, b in zip(self.train, rows))
+            try:
+                o.Model(*aug)
+            except o.OracleError:
+                continue  # (a scale() == 0 input: drawn again)
+            if shape == "duplicate":  # (the duplicate is all that is wrong with the rows)
+                t, at = int(rng.integers(0, len(self.train[0]))), int(rng.integers(0, len(u) + 1))
+                return tuple(np.insert(a, at, self.train[x][t] if x < 2 else 3.0).astype(a.dtype) for x, a in enumerate(rows))
+            self.set_train(aug)
+            return rows
+        raise AssertionError(("no acceptable append", shape))
+
+    def bystander_rows(self, query, refused=False):
+        """(others, pred_items) of a bystander query: fitted users (an absent id among them at times) other than the query's user
+        — but for a refused query, which names its own user — and an item each"""
+        n = int(self.rng.integers(2, 7))
+        others = [u for u in self.users_n(n + 2).tolist() if u != query[0]][:n]
+        if refused:
+            others.insert(int(self.rng.integers(0, len(others) + 1)), int(query[0]))
+        items = [self.item() if self.rng.random() < 0.7 else int(query[2][0]) if len(query[2]) else NEW_ITEM for _ in others]
+        return np.asarray(others, np.int32), np.asarray(items, np.int32)
+
     def op(self, kind, variant=None):
         """one op of `kind`; variant: a predictor, a (family, predictor) pair or a refusal where the slot fixes one"""
         rng, d = self.rng, self
@@ -755,6 +1042,28 @@ class _Draw:
             if variant == "cap64":  # more rows than the host form's term scratch of LIFE_WORKSPACE holds at this cap
                 return Op(kind, d.rows(150)[:2] + (64, int(rng.choice([SUM_ORDER, BY_WEIGHT]))), "host")
             return Op(kind, d.rows(d.size())[:2] + d.explain_args(), form)
+        if kind == "append":
+            return Op(kind, d.append_rows(variant or APPEND_SHAPES[int(rng.integers(0, 3))]))
+        if kind in ENTERED:
+            fam = "with" if "with" in kind else "for"
+            if not kind.endswith("_batch"):
+                return Op(kind, (d.query(fam),))
+            queries = [d.query(fam) for _ in range(int(rng.choice(self.batch_sizes)))]
+            if rng.random() < 0.5:  # a refused query inside the batch: a fitted user as a newcomer, an absent one without rows
+                at = len(queries) // 2
+                queries[at] = (d.fitted(),) + queries[at][1:] if fam == "for" else (int(rng.choice(ABSENT_USERS)), queries[at][1], queries[at][1], np.empty(0))
+            return Op(kind, (queries,))
+        if kind in BYSTANDER:
+            fam = variant if variant is not None else BYSTANDER_FAMILIES[int(rng.integers(0, 2))]
+            predict = "predict" in kind
+            if not kind.endswith("_batch"):
+                query = d.query(fam)
+                rows = d.bystander_rows(query)
+                return Op(kind, (fam, query) + (rows if predict else rows[:1]))
+            queries = [d.query(fam) for _ in range(int(rng.choice(self.batch_sizes)))]
+            refused = len(queries) // 2 if rng.random() < 0.5 else -1  # a query that names its own user among its rows
+            rows = [d.bystander_rows(q, refused=b == refused) for b, q in enumerate(queries)]
+            return Op(kind, (fam, queries, [x[0] for x in rows]) + (([x[1] for x in rows],) if predict else ()))
         what, batch = kind[:kind.index("_q")], kind.endswith("_batch")
         refusal = variant if isinstance(variant, str) else None
         fam, predictor = variant[:2] if isinstance(variant, tuple) else (FAMILIES[int(rng.integers(0, 3))], int(rng.choice([PRED_KNN, PRED_PERSONALIZED])))
@@ -799,7 +1108,14 @@ def sequence(seed, model, n_ops, k_pool=(2, 6), fits=None, batch_sizes=(2, 3, 5)
     slots += [("predict_q", "negative_mean"), ("recommend_q_batch", "negative_mean"), ("explain_q", "removes_unrated"),
               ("neighbors_q_batch", "removes_unrated"), ("predict_batch", PRED_PERSONALIZED), ("recommend", PRED_PERSONALIZED),
               ("mae", PRED_KNN), ("predict_batch", PRED_KNN), ("recommend_batch", PRED_KNN)]
+    # appends: the slot of the kind draws a shape, one is a fitted changer's, one is refused and leaves no trace, and in the memo
+    # sequences a third one interleaves a changer and a newcomer (on the 2 100 users of a life the oracle's side of an append costs
+    # seconds)
+    slots += [("append", "changer"), ("append", "duplicate")] + ([] if every_variant else [("append", "both")])
+    if not every_variant:  # ... and the kind's own slot is the third shape, a newcomer alone
+        slots[slots.index(("append", None))] = ("append", "newcomer")
     if every_variant:
+        slots = [s for s in slots if s[0] not in BYSTANDER] + [(kind, fam) for kind in BYSTANDER for fam in BYSTANDER_FAMILIES]
         for what in QUERY_WHATS:
             for fam in FAMILIES:
                 for predictor in (PRED_KNN,) if what == "neighbors" else (PRED_KNN, PRED_PERSONALIZED):
@@ -816,9 +1132,15 @@ def sequence(seed, model, n_ops, k_pool=(2, 6), fits=None, batch_sizes=(2, 3, 5)
         slots.append((extra[int(rng.integers(0, len(extra)))], PRED_KNN if rng.random() < 0.8 else None))
     order = rng.permutation(len(slots))
     slots = [slots[j] for j in order]
-    # the checkpoint: a save, and its load before the next call after which it no longer loads (set_k, fit)
+    accepted = lambda s: s[0] == "append" and s[1] != "duplicate"
+    if every_variant:  # an accepted append in the first half, so that a full pass of kinds runs on the appended fit
+        first = min(j for j, s in enumerate(slots) if accepted(s))
+        if first >= len(slots) // 2:
+            to = int(rng.integers(0, len(slots) // 2))
+            slots[to], slots[first] = slots[first], slots[to]
+    # the checkpoint: a save, and its load before the next call after which it no longer loads (set_k, fit, an accepted append)
     at = int(rng.integers(1, max(2, len(slots) // 2)))
-    ends = [j for j in range(at, len(slots)) if slots[j][0] in ("set_k", "fit")]
+    ends = [j for j in range(at, len(slots)) if slots[j][0] in ("set_k", "fit") or accepted(slots[j])]
     end = ends[0] if ends else len(slots)
     load_at = int(rng.integers(at, end + 1))
     slots = slots[:at] + [("neighbors_save", None)] + slots[at:load_at] + [("neighbors_load", None)] + slots[load_at:]
@@ -845,7 +1167,7 @@ def refusals_in(ops, model_factory):
 
 
 # ---- the committed cases -----------------------------------------------------------------------------------------------------
-N_OPS = 60
+N_OPS = 72
 
 
 def memo_fit(seed, half=True):
@@ -891,10 +1213,10 @@ K_ALL = 60  # >= U - 1 of every memo fit (40 users)
 # fit and sequence seeds searched on the CPU (differing_ops over a few dozen seeds each) so that the premises of
 # test_call_sequence_premises.py hold
 MEMO_CASES = [
-    Case("k2-a", 20, 2, 6),
-    Case("k2-b", 13, 2, 11),
-    Case("k6", 4, 6, 10),
-    Case("kall", 5, K_ALL, 6),
+    Case("k2-a", 20, 2, 3),
+    Case("k2-b", 13, 2, 8),
+    Case("k6", 4, 6, 6),
+    Case("kall", 5, K_ALL, 8),
 ]
 
 
@@ -938,8 +1260,15 @@ def play_on_model(model, ops):
     return [model.call(op) for op in ops]
 
 
-def differing_ops(oracle, case, wrong, ops=None):
-    """indices of the ops whose expected output differs between the reference model and the wrong one"""
+def play_with_built(model, ops):
+    """[(answer, the built users after the op in ascending raw id)]"""
+    return [(model.call(op), sorted(model.built)) for op in ops]
+
+
+def differing_ops(oracle, case, wrong, ops=None, sim="cosine", with_built=False):
+    """indices of the ops whose expected output — with_built: or the set of built lists after it — differs between the reference
+    model and the wrong one"""
     ops = case.ops(oracle) if ops is None else ops
-    good, bad = play_on_model(case.model(oracle), ops), play_on_model(case.model(oracle, wrong=wrong), ops)
+    play = play_with_built if with_built else play_on_model
+    good, bad = play(case.model(oracle, sim), ops), play(case.model(oracle, sim, wrong=wrong), ops)
     return [j for j, (g, b) in enumerate(zip(good, bad)) if not same(b, g)]

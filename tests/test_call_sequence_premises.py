@@ -13,23 +13,44 @@ _counts = {}
 
 
 def _differs(oracle, case, wrong):
+    """the ops that the wrong model changes: in the answer under the adjusted cosine, and for the wrong models of
+    cs.WRONG_AFTER_APPEND in the answer or in the set of built lists under Jaccard (where the memo fits carry lists)"""
     key = (case.name, wrong)
     if key not in _counts:
-        _counts[key] = cs.differing_ops(oracle, case, wrong)
+        late = wrong in cs.WRONG_AFTER_APPEND
+        _counts[key] = cs.differing_ops(oracle, case, wrong, sim="jaccard" if late else "cosine", with_built=late)
     return _counts[key]
+
+
+def _public(cls):
+    return [n for n, f in inspect.getmembers(cls, inspect.isfunction) if not n.startswith("_")]
 
 
 @pytest.fixture(scope="module")
 def engine_methods(pkg):
     kn = importlib.import_module(pkg.__name__ + ".knncf")
-    return [n for n, f in inspect.getmembers(kn.Engine, inspect.isfunction) if not n.startswith("_")]
+    return _public(kn.Engine)
+
+
+@pytest.fixture(scope="module")
+def wrapper_methods(pkg):
+    """{class name: public methods} of every public class of knncf.py that wraps an engine: its constructor takes one"""
+    kn = importlib.import_module(pkg.__name__ + ".knncf")
+    found = {}
+    for name, c in inspect.getmembers(kn, inspect.isclass):
+        if c.__module__ != kn.__name__ or name.startswith("_") or c is kn.Engine:
+            continue
+        params = list(inspect.signature(c.__init__).parameters.values())[1:]
+        if any(p.name == "engine" or p.annotation is kn.Engine for p in params):
+            found[name] = _public(c)
+    return found
 
 
 def test_counts_table(oracle):
-    """prints, per case, how many of the 60 ops each wrong model changes"""
-    print("\ncase      " + " ".join(f"{w:>18}" for w in cs.WRONG_MODELS))
+    """prints, per case, how many of the ops each wrong model changes"""
+    print("\ncase      " + " ".join(f"{w:>{max(18, len(w))}}" for w in cs.WRONG_MODELS))
     for case in cs.MEMO_CASES:
-        print(f"{case.name:<10}" + " ".join(f"{len(_differs(oracle, case, w)):>18}" for w in cs.WRONG_MODELS))
+        print(f"{case.name:<10}" + " ".join(f"{len(_differs(oracle, case, w)):>{max(18, len(w))}}" for w in cs.WRONG_MODELS))
 
 
 @pytest.mark.parametrize("case", cs.MEMO_CASES, ids=lambda c: c.name)
@@ -80,14 +101,111 @@ def test_sorted_batch_differs(oracle):
     assert any(_differs(oracle, case, "sorted_batches") for case in cs.MEMO_CASES)
 
 
-def test_every_engine_method_has_a_kind(engine_methods):
-    """a family added to the Engine without a model method fails here instead of being skipped silently"""
+def _played(oracle, case, sim):
+    model = case.model(oracle, sim)
+    return model, cs.play_on_model(model, case.ops(oracle))
+
+
+@pytest.mark.parametrize("wrong", cs.WRONG_AFTER_APPEND)
+def test_wrong_fit_after_an_append_differs_later(oracle, wrong):
+    """an append that keeps every built list, one that keeps the old fit's statistics and Personalized answers, and an entered
+    call that builds nothing: each shows in an op AFTER the first append or entered call of some sequence, in the answer or in
+    the set of built lists"""
+    starts = ("append",) if wrong.startswith("append") else cs.ENTERED
+    hits = []
+    for case in cs.MEMO_CASES:
+        ops = case.ops(oracle)
+        first = min(j for j, op in enumerate(ops) if op.kind in starts)
+        d = _differs(oracle, case, wrong)
+        assert all(j >= first for j in d), (case.name, d, first)
+        hits += [(case.name, j) for j in d if j > first]
+    assert hits, wrong
+    if wrong == "entered_builds_nothing":  # ... and in what a later append carries
+        assert any(case.ops(oracle)[j].kind == "append" for case in cs.MEMO_CASES
+                   for j in cs.differing_ops(oracle, case, wrong, sim="jaccard"))
+
+
+@pytest.mark.parametrize("case", cs.MEMO_CASES, ids=lambda c: c.name)
+def test_memo_appends_carry_and_drop(oracle, case):
+    """under Jaccard some append of every sequence meets built lists, keeps some and drops some; under the adjusted cosine every
+    append of a memo fit (users of <= 4 ratings) is a plain refit; one append of every sequence is refused and leaves no trace"""
+    model, out = _played(oracle, case, "jaccard")
+    assert any(a["carried"] >= 1 and a["dropped"] >= 1 for a in model.appends), (case.name, model.appends)
+    assert all(a["carried"] + a["dropped"] == a["built"] for a in model.appends)
+    cosine, out_c = _played(oracle, case, "cosine")
+    assert cosine.appends and all(a["plain"] and a["carried"] == 0 for a in cosine.appends), (case.name, cosine.appends)
+    ops = case.ops(oracle)
+    for o in (out, out_c):
+        refused = [x for op, x in zip(ops, o) if op.kind == "append" and isinstance(x, cs.Refused)]
+        assert [x.status for x in refused] == [cs.E_DUPLICATE], case.name
+    assert len(model.appends) == len(cosine.appends) == sum(op.kind == "append" for op in ops) - 1 >= 3
+    # the rows come in all three shapes: a fitted changer, a newcomer, both interleaved
+    fitted = set(case.train()[0].tolist())
+    shapes = set()
+    for op, x in zip(ops, out):
+        if op.kind == "fit":
+            fitted = set(op.args[0].train[0].tolist())
+        if op.kind == "append" and not isinstance(x, cs.Refused):
+            users = list(dict.fromkeys(op.args[0].tolist()))
+            new = [u for u in users if u not in fitted]
+            assert all(u > cs.NEWCOMER for u in new) and len(new) <= 1
+            shapes.add("both" if new and len(users) > 1 else "newcomer" if new else "changer")
+            fitted |= set(users)
+    assert shapes == set(cs.APPEND_SHAPES), (case.name, shapes)
+
+
+def test_entered_calls_meet_missing_and_complete_tables(oracle):
+    """some entered call finds every list built (M empty) and in every sequence one finds lists to build (M not empty), under
+    Jaccard; under the adjusted cosine the memo fits refuse the entered calls and nothing is built"""
+    missing = []
+    for case in cs.MEMO_CASES:
+        model, _ = _played(oracle, case, "jaccard")
+        assert max(model.entered_missing) > 0, (case.name, model.entered_missing)
+        missing += model.entered_missing
+        cosine, out = _played(oracle, case, "cosine")
+        assert cosine.entered_missing == []
+        assert all(isinstance(x, cs.Refused) and x.status == cs.E_UNSUPPORTED for op, x in zip(case.ops(oracle), out) if op.kind in cs.ENTERED)
+    assert 0 in missing, missing
+
+
+@pytest.mark.parametrize("life", range(len(cs.LIVES)))
+def test_lives_append_early_and_carry(oracle, life):
+    """every life has an accepted append in the first half of its body; on the fits without short rows (A, B, D) some append
+    under the adjusted cosine keeps lists and drops lists; on the memo fit C every append is a plain refit"""
+    fit, k0, _ = cs.LIVES[life]
+    ops = cs.life_ops(oracle, life)
+    model = cs.HandleModel(oracle, fit.train, oracle.SIM_COSINE, k0)
+    out = cs.play_on_model(model, ops)
+    body = ops[2:]
+    accepted = [j for j, (op, x) in enumerate(zip(body, out[2:])) if op.kind == "append" and not isinstance(x, cs.Refused)]
+    assert accepted and accepted[0] < len(body) // 2, (life, accepted, len(body))
+    if model.short_fit:
+        assert all(a["plain"] for a in model.appends), (life, model.appends)
+    else:
+        assert any(a["carried"] >= 1 and a["dropped"] >= 1 for a in model.appends), (life, model.appends)
+        assert max(model.entered_missing) > 0, (life, model.entered_missing)
+
+
+def test_every_engine_method_has_a_kind(engine_methods, wrapper_methods):
+    """a family added to the Engine, or in a class beside it that wraps one, without a model method fails here instead of being
+    skipped silently"""
     for name in engine_methods:
         kind = cs.kind_of(name)
         assert (kind is None) == (name in cs.NOT_MODELLED), name
         if kind is not None:
             assert kind in cs.KINDS and callable(getattr(cs.HandleModel, kind)) and callable(getattr(cs.Player, kind)), name
     kinds = {cs.kind_of(n) for n in engine_methods} - {None}
+    assert {"BystanderQueries", "EnteredQueries", "Appends"} <= set(wrapper_methods), sorted(wrapper_methods)
+    for owner, names in wrapper_methods.items():
+        assert names, owner
+        for name in names:
+            kind = cs.kind_of(name, owner)
+            assert kind in cs.KINDS and callable(getattr(cs.HandleModel, kind)) and callable(getattr(cs.Player, kind)), (owner, name)
+            assert kind not in kinds, (owner, name, "the kind of another class's method")
+        kinds |= {cs.kind_of(n, owner) for n in names}
+    for kind in cs.BYSTANDER:  # both families of every bystander kind exist
+        what, tail = kind[len("bystander_"):].replace("_batch", ""), "_batch" if kind.endswith("_batch") else ""
+        assert {f"{what}_{fam}{tail}" for fam in cs.BYSTANDER_FAMILIES} <= set(wrapper_methods["BystanderQueries"]), kind
     assert kinds == set(cs.KINDS), (kinds ^ set(cs.KINDS))
     for kind in cs.DEVICE_FORMS:
         assert f"{kind}_device" in engine_methods, kind
@@ -112,7 +230,12 @@ def test_memo_sequences_hold_every_kind_and_refusal(oracle, case):
     assert {op.form for op in ops} == {"host", "device"}
     _check_coverage(ops, cs.refusals_in(ops, lambda: case.model(oracle)), True, case.name)
     # the fitted Personalized forms are refused under the cosine only: under Jaccard the same ops are answered
-    assert not [k for k, s in cs.refusals_in(ops, lambda: case.model(oracle, "jaccard")) if "_q" not in k]
+    # (of the kinds beside the Engine's only what the generator plants is refused: the duplicate append, and a query inside a batch
+    # of entered or bystander queries that is invalid as such)
+    beside = ("append",) + cs.ENTERED + cs.BYSTANDER
+    jaccard = cs.refusals_in(ops, lambda: case.model(oracle, "jaccard"))
+    assert not [k for k, s in jaccard if "_q" not in k and k not in beside]
+    assert {(k, s) for k, s in jaccard if k in beside} <= {("append", cs.E_DUPLICATE)} | {(k, cs.E_INVALID) for k in beside if k.endswith("_batch")}
     # the query forms are answered where the fitted forms refuse
     out = cs.play_on_model(case.model(oracle), ops)
     assert any(op.kind in ("predict_q", "recommend_q", "explain_q") and op.args[1] == cs.PRED_PERSONALIZED and not isinstance(o, cs.Refused)

@@ -1,9 +1,11 @@
 """Random call sequences on ONE handle against the stateful model of tests/call_sequences.py (what the sequences can tell
 apart: tests/test_call_sequence_premises.py).  Each family's own test checks what its call leaves in the handle on a fresh
 handle; here the clauses of include/knncf.h are composed: after every op the ids are == and the floats bit-equal to the
-model's, a refused call leaves no trace, a read-only call leaves the knncf_neighbors_save bytes alone, a checkpoint carries the
-memo history to a second handle in the middle of a sequence, and one handle lives through five fits of very different
-shapes.  The mae scalars are compared within MAE_TOL of test_gpu_handle_reuse; the predictions behind them in bits."""
+model's, a refused call leaves no trace, a read-only call leaves the knncf_neighbors_save bytes alone, the users with a built
+list are the model's, a checkpoint carries the memo history to a second handle in the middle of a sequence, and one handle
+lives through five fits of very different shapes.  The sequences hold knncf_append, which replaces the fit and keeps lists,
+the entered calls, which build every missing list, and the bystander calls, which must only read.  The mae scalars are
+compared within MAE_TOL of test_gpu_handle_reuse; the predictions behind them in bits."""
 import importlib
 import shutil
 import os
@@ -25,7 +27,9 @@ def kn(pkg):
     mod = importlib.import_module(pkg.__name__ + ".knncf")
     mod.load_library()
     assert cs.MAE_TOL == 1e-9 and (mod.OK, mod.E_INVALID, mod.E_UNSUPPORTED) == (cs.OK, cs.E_INVALID, cs.E_UNSUPPORTED)
+    assert (mod.E_NONFINITE, mod.E_DUPLICATE, mod.E_STATE) == (cs.E_NONFINITE, cs.E_DUPLICATE, cs.E_STATE)
     assert (mod.PRED_BASELINE, mod.PRED_KNN, mod.PRED_PERSONALIZED) == (cs.PRED_BASELINE, cs.PRED_KNN, cs.PRED_PERSONALIZED)
+    assert mod.APPEND_MAX_CHANGERS == cs.APPEND_MAX_CHANGERS
     return mod
 
 
@@ -33,17 +37,42 @@ def _ksim(kn, sim):
     return {"cosine": kn.SIM_COSINE, "jaccard": kn.SIM_JACCARD}[sim]
 
 
+def _built(table, order):
+    """the raw ids with a build number in a parsed checkpoint; order: the fit's users in set order (dense index -> raw id)"""
+    assert len(table["seq"]) == len(order)
+    return sorted(int(u) for u, s in zip(order, table["seq"]) if s >= 0)
+
+
+def _same_built(table, built, order, what):
+    got = _built(table, order)
+    assert got == sorted(built), f"{what}: the handle has built {got}, the model {sorted(built)}"
+
+
 def _step(player, model, j, op, tmp_path, what, table=None):
     """op j on the handle and on its model; returns the handle's defined checkpoint bytes afterwards when `table` (those
-    before the op) is given"""
+    before the op) is given, having compared the users that have a list with the model's"""
     got, want = player.play(op), model.call(op)
     assert cs.same(got, want), f"{what} op {j}: {op!r}"
     if table is None:
         return None
     after = _table(player.e, tmp_path, "state.bin")
-    if cs.is_read_only(op.kind):
-        assert after == table, f"{what} op {j} is read-only and changed the checkpoint: {op!r}"
+    # (a single entered call whose query is refused has still built the missing lists: its definition is not empty)
+    if cs.is_read_only(op.kind) or (isinstance(want, cs.Refused) and not model.definition):
+        assert after == table, f"{what} op {j} is read-only or refused and changed the checkpoint: {op!r}"
+    _same_built(after, model.built, model.m.user_iteration_order().tolist(), f"{what} op {j}: {op!r}")
     return after
+
+
+def _replay(player, op, definition):
+    """what a handle that is independent of the code under test plays for an op: nothing for a read-only one, the older calls
+    that define it for an append (fit(aug), neighbors_batch(K)) and an entered call (neighbors_batch(M)) — K and M are the
+    model's — and the op itself otherwise"""
+    if definition is not None:
+        for x in definition:
+            out = player.play(x)
+            assert not isinstance(out, cs.Refused), (op, x)
+    elif not cs.is_read_only(op.kind) or op.kind == "neighbors_save":
+        player.play(op)
 
 
 @pytest.mark.parametrize("case, sim", MEMO, ids=MEMO_IDS)
@@ -53,22 +82,36 @@ def test_memo_sequences(kn, oracle, tmp_path, case, sim):
     e = kn.Engine(k=case.k, similarity=_ksim(kn, sim)).fit(*case.train())
     player = cs.Player(kn, e, tmp_path, "e", case.train())
     table = _table(e, tmp_path, "state.bin")
+    definitions = []
     for j, op in enumerate(ops):
         table = _step(player, model, j, op, tmp_path, case.name, table)
+        definitions.append(model.definition)
+        assert (model.definition is not None) == (op.kind == "append" or op.kind in cs.ENTERED), op
     # a fresh handle that replays only what the model says the handle keeps: the same defined checkpoint bytes
     f = kn.Engine(k=case.k, similarity=_ksim(kn, sim)).fit(*case.train())
     replay = cs.Player(kn, f, tmp_path, "f", case.train())
-    for op in ops:
-        if not cs.is_read_only(op.kind) or op.kind == "neighbors_save":
-            replay.play(op)
+    for op, definition in zip(ops, definitions):
+        _replay(replay, op, definition)
     assert _table(f, tmp_path, "replay.bin") == table, case.name
     f.close()
     e.close()
 
 
+def _second_handle(kn, model, sim, path, tmp_path, first):
+    """a handle fitted on the model's rows as they stand (the aug after an append) that loads the checkpoint at `path`, with
+    the model of its state"""
+    e2 = kn.Engine(k=model.k, similarity=_ksim(kn, sim)).fit(*model.train)
+    e2.neighbors_load(path)
+    second = cs.Player(kn, e2, tmp_path, "e2", model.train)
+    if os.path.exists(first.path):  # the sequence's own checkpoint, should its load come later
+        shutil.copy(first.path, second.path)
+    return e2, second, model.replica()
+
+
 @pytest.mark.parametrize("case, sim", MEMO, ids=MEMO_IDS)
 def test_checkpoint_mid_sequence(kn, oracle, tmp_path, case, sim):
-    """save at op n / 2, load into a second handle fitted on the same rows: both finish the sequence against their models"""
+    """save at op n / 2, load into a second handle fitted on the rows as they stand then: both finish the sequence against their
+    models"""
     ops = case.ops(oracle)
     half = len(ops) // 2
     model = case.model(oracle, sim)
@@ -78,15 +121,45 @@ def test_checkpoint_mid_sequence(kn, oracle, tmp_path, case, sim):
         _step(first, model, j, op, tmp_path, case.name)
     path = str(tmp_path / "half.nbr")
     e.neighbors_save(path)
-    e2 = kn.Engine(k=model.k, similarity=_ksim(kn, sim)).fit(*model.train)
-    e2.neighbors_load(path)
-    model2 = model.replica()
-    second = cs.Player(kn, e2, tmp_path, "e2", model.train)
-    if os.path.exists(first.path):  # the sequence's own checkpoint, should its load come in the second half
-        shutil.copy(first.path, second.path)
+    e2, second, model2 = _second_handle(kn, model, sim, path, tmp_path, first)
     for j, op in enumerate(ops[half:], half):
         _step(first, model, j, op, tmp_path, case.name + " first handle")
         _step(second, model2, j, op, tmp_path, case.name + " second handle")
+    e.close()
+    e2.close()
+
+
+@pytest.mark.parametrize("sim", SIMS)
+def test_checkpoint_around_an_append(kn, oracle, tmp_path, sim):
+    """a checkpoint saved before an append no longer loads afterwards (KNNCF_E_STATE: the fit is another one) and the refused
+    load leaves the handle as it was; one saved after the append loads into a fresh handle fitted on aug, and both handles
+    finish the sequence.  The append is the first of the sequence that meets built lists."""
+    case = cs.MEMO_CASES[0]
+    ops = case.ops(oracle)
+    probe = case.model(oracle, sim)
+    at = next(j for j, op in enumerate(ops) if not isinstance(probe.call(op), cs.Refused) and op.kind == "append" and probe.appends[-1]["built"])
+    model = case.model(oracle, sim)
+    e = kn.Engine(k=case.k, similarity=_ksim(kn, sim)).fit(*case.train())
+    first = cs.Player(kn, e, tmp_path, "e", case.train())
+    for j, op in enumerate(ops[:at]):
+        _step(first, model, j, op, tmp_path, case.name)
+    before = str(tmp_path / "before.nbr")
+    e.neighbors_save(before)
+    table = _step(first, model, at, ops[at], tmp_path, case.name, _table(e, tmp_path, "state.bin"))
+    with pytest.raises(kn.KnncfError) as refused:
+        e.neighbors_load(before)
+    assert refused.value.status == kn.E_STATE
+    assert _table(e, tmp_path, "state.bin") == table
+    after = str(tmp_path / "after.nbr")
+    e.neighbors_save(after)
+    if os.path.exists(first.path):
+        os.remove(first.path)  # (the sequence's own checkpoint is of the fit before the append: its load lies before `at`)
+    e2, second, model2 = _second_handle(kn, model, sim, after, tmp_path, first)
+    assert _table(e2, tmp_path, "second.bin") == table
+    for j, op in enumerate(ops[at + 1:], at + 1):
+        table = _step(first, model, j, op, tmp_path, case.name + " first handle", table)
+        _step(second, model2, j, op, tmp_path, case.name + " second handle")
+    assert _table(e2, tmp_path, "second.bin") == table
     e.close()
     e2.close()
 
@@ -95,10 +168,17 @@ _expected = {}
 
 
 def _life_expected(oracle, sim, life):
-    """the model's answers of one life (the oracle on the CURRENT fit), computed once per similarity"""
+    """the model's answers of one life (the oracle on the CURRENT fit), computed once per similarity: (answers, {op index of an
+    accepted append: (built users, the users of the fit in set order) after it}, the train set at the end of the life)"""
     if (sim, life) not in _expected:
         fit, k0, _ = cs.LIVES[life]
-        _expected[sim, life] = cs.play_on_model(cs.HandleModel(oracle, fit.train, cs.sim_of(oracle, sim), k0), cs.life_ops(oracle, life))
+        model = cs.HandleModel(oracle, fit.train, cs.sim_of(oracle, sim), k0)
+        out, appended = [], {}
+        for j, op in enumerate(cs.life_ops(oracle, life)):
+            out.append(model.call(op))
+            if op.kind == "append" and not isinstance(out[-1], cs.Refused):
+                appended[j] = (sorted(model.built), model.m.user_iteration_order().tolist())
+        _expected[sim, life] = (out, appended, model.train)
     return _expected[sim, life]
 
 
@@ -106,7 +186,8 @@ def _life_expected(oracle, sim, life):
 def test_handle_lives(kn, oracle, tmp_path, monkeypatch, variant):
     """one handle through the fits A (300 users), B (2 100 users: the streamed Personalized path, k = 1000 and 10), C (a memo fit:
     everything shrinks, short rows, the Personalized cosine refused), D (A's rows under large raw ids) and A again, each life a
-    shuffled pass over every call kind, family and predictor.  After each life a fresh handle on the same rows repeats the
+    shuffled pass over every call kind, family and predictor with appends among them: the fit grows within a life.  After every
+    append the users with a list are the model's.  After each life a fresh handle on the rows as they stand then repeats the
     life's kNN predictions bit for bit."""
     sim = "jaccard" if variant == "jaccard" else "cosine"
     if variant == "no_item_bitmaps":
@@ -116,16 +197,19 @@ def test_handle_lives(kn, oracle, tmp_path, monkeypatch, variant):
     player = cs.Player(kn, e, tmp_path, "e")
     for life, (fit, k0, _) in enumerate(cs.LIVES):
         ops = cs.life_ops(oracle, life)
-        want = _life_expected(oracle, sim, life)
+        want, appended, train = _life_expected(oracle, sim, life)
         k = k0
         for j, op in enumerate(ops):
             assert cs.same(player.play(op), want[j]), f"life {life} ({fit.name}) op {j}: {op!r}"
             k = op.args[0] if op.kind == "set_k" else k
+            if j in appended:
+                _same_built(_table(e, tmp_path, "life.bin"), *appended[j], f"life {life} ({fit.name}) op {j}: {op!r}")
+        assert appended and len(train[0]) > len(fit.train[0]), life
         rows = [op.args[1:3] for op in ops if op.kind in ("predict_batch", "mae") and op.args[0] == cs.PRED_KNN]
         users, items = (np.concatenate([r[c] for r in rows]) for c in (0, 1))
-        if (np.unique(fit.train[0], return_counts=True)[1] <= 4).any():
+        if (np.unique(train[0], return_counts=True)[1] <= 4).any():
             e.reset_neighbors()  # (a <= 4-rating fit: the handle's memo history is not a fresh handle's)
-        f = kn.Engine(k=k, similarity=_ksim(kn, sim)).fit(*fit.train)
+        f = kn.Engine(k=k, similarity=_ksim(kn, sim)).fit(*train)
         assert cs.same(e.predict_batch(kn.PRED_KNN, users, items), f.predict_batch(kn.PRED_KNN, users, items)), f"life {life} ({fit.name})"
         f.close()
     e.close()
