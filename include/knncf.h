@@ -804,8 +804,8 @@ int knncf_revise_recommend_explain_batch(knncf_handle* h, int predictor, const i
  * no device memory.
  * Handle state.  Read-only in the sense of the other families: the neighbour table, its build numbers, its epoch and the
  * knncf_neighbors_save bytes stay as they were.  knncf_get_timings: charged as the fold-in calls charge theirs.
- * OUT OF SCOPE: a `user` that is in the fit (update queries: "Bystanders of update queries" below; revise queries: not
- * served); KNNCF_PRED_PERSONALIZED and the other predictors;
+ * OUT OF SCOPE: a `user` that is in the fit (update queries: "Bystanders of update queries" below; revise queries:
+ * "Bystanders of revise queries" below); KNNCF_PRED_PERSONALIZED and the other predictors;
  * recommendations and explanations for a bystander; device-pointer forms; shard handles and knncf_group_*.  ("Which fitted
  * users does the newcomer enter" is knncf_query_entered, below.) */
 int knncf_query_bystander_neighbors(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
@@ -860,8 +860,8 @@ int knncf_query_bystander_predict_batch(knncf_handle* h, int predictor, const in
  * bystanders than fit beside its own slot continues in the next chunk, where its row is prepared again.  A chunk may mix fitted
  * changers and newcomers.  Results do not depend on C; a repeated call of the same shape allocates no device memory.
  * Handle state: read-only, as "Bystander queries".  knncf_get_timings: charged as the fold-in calls charge theirs.
- * OUT OF SCOPE: bystanders of revise queries (with removals average(aug) is no continuation of the fit's running total, and an
- * item can leave aug); the entered question for update queries is served by knncf_update_entered* ("Entered queries of update
+ * OUT OF SCOPE: removals (bystanders of revise queries: "Bystanders of revise queries" below); the entered question for update
+ * queries is served by knncf_update_entered* ("Entered queries of update
  * queries" below), which rebuilds a user's full row through these calls only where the stored list cannot decide;
  * KNNCF_PRED_PERSONALIZED and the other predictors; recommendations and explanations for a bystander; device-pointer forms; shard
  * handles and knncf_group_*; the command-line tool. */
@@ -875,6 +875,58 @@ int knncf_update_bystander_neighbors_batch(knncf_handle* h, const int32_t* users
 int knncf_update_bystander_predict_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* offsets,
                                          const int32_t* items, const double* ratings, int64_t n_queries, const int64_t* row_offsets,
                                          const int32_t* others, const int32_t* pred_items, double* out, int32_t* statuses);
+
+/* ---- Bystanders of revise queries: a FITTED user's kNN answers once another user has removed or re-rated items ---------------
+ * A user of the fit who deletes a rating, or rates an item again, changes its mean, its deviations and its norm like one who
+ * adds ratings — and takes terms OUT of other users' folds.  These calls are knncf_update_bystander_* for such a user WITHOUT a
+ * refit; the argument lists are those calls' with the removals in front of the additional rows, where knncf_revise_* puts them.
+ * A query is a revise query exactly as knncf_revise_* defines it: any raw id `user`, the train items it takes out
+ * (removed_items), its additional rows (items[j], ratings[j]);
+ *     aug = train without the removed rows of `user`, in file order, ++ the additional rows in order.
+ * A ROW names a bystander others[r] != user, the predict forms a raw item beside it.  Every row is answered on closures of its
+ * own over aug whose first evaluation is the row's — the bystander owns every pair — bit for bit: getNeighbors(aug, k,
+ * sim)(others[r]) and the kNN predictor, as "Bystanders of update queries" describes them.  Row outputs, counts, untouched cells,
+ * slots and chunks (a revise query that continues in the next chunk has its revise row prepared again), per-query and
+ * handle-level statuses, read-only handle state and timings: everything knncf_update_bystander_* documents holds unchanged.
+ * What a fitted changer c with removals does to bystander v:
+ *   S(v, c) and the list: as for an update query, with c's row on aug (live train rows in file order, then the additional
+ *     rows).  c stays a user of aug: the list lengths are those of the update case.
+ *   The fold: c's term on an item stands where c's row of that item stands in aug's file order.  A live train row stays at
+ *     its train file row with the deviation on aug; a removed row is no term; a re-rated item has its train row gone and its
+ *     additional row behind every train row.
+ *   An item that leaves aug (c was its only train rater, removed it and did not give it again) has no rater: the prediction
+ *     is the bystander's mean exactly, as for an item unknown to aug.  A lone item that c re-rates has exactly one rater, the
+ *     last of aug: the one-term fold where c is in v's list, v's mean otherwise.
+ *   average(aug), the answer for a bystander unknown to aug or with a negative mean: the left fold from 0.0 of the SURVIVING
+ *     train ratings in file order, continued over the additional ratings in the given order, over n - n_removed + n_ratings.
+ *     It is no continuation of the fit's running total.  On a fit whose ratings are all dyadic (multiples of 1/16: every
+ *     MovieLens file) every partial sum is exact and the surviving fold is the total minus the removed ratings; on any other
+ *     fit a predict call folds the file again on the device — one dependent chain over the n train ratings, what the fit's own
+ *     sequential sum costs — once per query that has removals AND a row answered with the average.
+ * Per-query statuses: those of knncf_update_bystander_*, and the refusals of knncf_revise_* on top — KNNCF_E_INVALID for a
+ * removed item the user did not rate in train, a removed item listed twice, any removal for a user absent from train, and a
+ * fitted user left without a row; the 65536-row cap counts the removed rows too.  KNNCF_E_INVALID for n_removed < 0, null
+ * removed items with n_removed > 0, and removed_offsets that are null, do not start at 0 or decrease.
+ * n_removed == 0 in every query of a call gives the knncf_update_bystander_* answer bit for bit through the same code.
+ * KNNCF_DEBUG_TRACE_DISPATCH prints, after the `bystander` line of a chunk that holds a changer with removals,
+ *     knncf-dispatch bystander-revise slots=<such changer slots> removed=<their removed items> refold=<sequential folds>
+ * OUT OF SCOPE: the entered question for revise queries (knncf_revise_entered*) and removals in knncf_append; prefix checkpoints
+ * that would shorten the sequential fold; KNNCF_PRED_PERSONALIZED and the other predictors; device-pointer forms; shard handles
+ * and knncf_group_*; the command-line tool. */
+int knncf_revise_bystander_neighbors(knncf_handle* h, int32_t user, const int32_t* removed_items, int64_t n_removed,
+                                     const int32_t* items, const double* ratings, int64_t n_ratings, const int32_t* others, int64_t m,
+                                     int32_t cap, int32_t* ids, double* sims, int32_t* counts);
+int knncf_revise_bystander_predict(knncf_handle* h, int predictor, int32_t user, const int32_t* removed_items, int64_t n_removed,
+                                   const int32_t* items, const double* ratings, int64_t n_ratings, const int32_t* others,
+                                   const int32_t* pred_items, int64_t m, double* out);
+int knncf_revise_bystander_neighbors_batch(knncf_handle* h, const int32_t* users, const int64_t* removed_offsets,
+                                           const int32_t* removed_items, const int64_t* offsets, const int32_t* items,
+                                           const double* ratings, int64_t n_queries, const int64_t* row_offsets, const int32_t* others,
+                                           int32_t cap, int32_t* ids, double* sims, int32_t* counts, int32_t* statuses);
+int knncf_revise_bystander_predict_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* removed_offsets,
+                                         const int32_t* removed_items, const int64_t* offsets, const int32_t* items,
+                                         const double* ratings, int64_t n_queries, const int64_t* row_offsets, const int32_t* others,
+                                         const int32_t* pred_items, double* out, int32_t* statuses);
 
 /* ---- Entered queries: which fitted users' neighbour lists a newcomer joins ---------------------------------------------------
  * Under KNNCF_PRED_KNN a fitted user v's predictions change when a newcomer joins only if the newcomer enters

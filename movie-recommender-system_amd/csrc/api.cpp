@@ -1357,7 +1357,8 @@ struct ByChunkState {
     std::vector<int32_t> qslot, qrank, qidx;  // qidx: the changer's index in a list, U for a newcomer (ByChunk)
     std::vector<ByRow> rows;
     int32_t fitted = 0, merged = 0;
-    void clear() { qslot.clear(); qrank.clear(); qidx.clear(); rows.clear(); fitted = merged = 0; }
+    int32_t refolds = 0;  // revise queries whose average(aug) took a sequential fold over the file (answer_bystander_predict)
+    void clear() { qslot.clear(); qrank.clear(); qidx.clear(); rows.clear(); fitted = merged = refolds = 0; }
 };
 
 // between packing and answering: the chunk (C > 0; bc: its bystander side, else null) through the neighbour pass and settle_statuses
@@ -1706,6 +1707,8 @@ QueryFailure run_query_chunks(knncf_handle* h, const QueryCall& q, int64_t chunk
 // QB_BY_PREDICT with a mean >= 0.  The rows of the other bystanders are answered on the host once the query's status is known.
 // knncf_update_bystander_* run the same loop with family QF_UPDATE: the query is an update query, and where its user is of the
 // fit (a fitted CHANGER) its own slot is an update slot and no list takes a newcomer in (bystander.hip).
+// knncf_revise_bystander_* run it with family QF_REVISE: a fitted changer's own slot leaves out the train rows it removes (a
+// revise slot; the chunk carries the removed CSR), and average(aug) of such a query is folded anew (revised_average).
 
 // slots per chunk: the rule of knncf.h ("Bystander queries")
 int64_t bystander_chunk(knncf_handle* h, int64_t budget) { return std::max<int64_t>(2, query_batch_chunk(h, budget)); }
@@ -1715,6 +1718,15 @@ double aug_average(knncf_handle* h, const QueryCall& q, int64_t b) {
     double t = h->tr.total;
     for (int64_t j = q.offsets[b]; j < q.offsets[b + 1]; ++j) t = t + q.ratings[j];
     return t / (double)(h->tr.n + (q.offsets[b + 1] - q.offsets[b]));
+}
+// the removals of query b (revise queries)
+int64_t removals(const QueryCall& q, int64_t b) { return q.family == QF_REVISE ? q.removed_offsets[b + 1] - q.removed_offsets[b] : 0; }
+// average(aug) of a revise query with removals: `survivors` = the fold of the surviving train ratings in file order
+// (bystander_survivor_totals), continued over query b's ratings in the given order, over n - n_removed + n_ratings
+double revised_average(knncf_handle* h, const QueryCall& q, int64_t b, double survivors) {
+    double t = survivors;
+    for (int64_t j = q.offsets[b]; j < q.offsets[b + 1]; ++j) t = t + q.ratings[j];
+    return t / (double)(h->tr.n - removals(q, b) + (q.offsets[b + 1] - q.offsets[b]));
 }
 
 // QB_BY_NEIGHBORS: the lists of the rows whose query is good
@@ -1747,17 +1759,32 @@ void answer_bystander_neighbors(knncf_handle* h, const QueryCall& q, ChunkState&
 }
 
 // QB_BY_PREDICT: the rows whose query is good — on the host where the bystander has no slot, else through answer_picks
-void answer_bystander_predict(knncf_handle* h, const QueryCall& q, ChunkState& cs, const ByChunkState& bc) {
+// A revise query with removals and a row answered with average(aug) has its surviving train ratings folded on the device, once
+// per query (the slot-less rows of a query all stand in the chunk of its first slot); bc.refolds counts the sequential folds
+void answer_bystander_predict(knncf_handle* h, const QueryCall& q, ChunkState& cs, ByChunkState& bc) {
     cs.pick_slot.clear(); cs.pick_items.clear(); cs.pick_row.clear();
+    std::vector<int32_t> fold_slots;  // the changer slots whose average is not the running total's continuation
     for (const ByRow& r : bc.rows) {
         if (q.statuses[cs.slot_query[r.own]] != KNNCF_OK) continue;
         if (r.slot == BY_NO_SLOT) {
-            q.out_d[r.row] = aug_average(h, q, cs.slot_query[r.own]);
+            if (removals(q, cs.slot_query[r.own]) == 0) q.out_d[r.row] = aug_average(h, q, cs.slot_query[r.own]);
+            else if (fold_slots.empty() || fold_slots.back() != r.own) fold_slots.push_back(r.own);  // (rows come query after query)
             continue;
         }
         cs.pick_items.push_back(q.pred_items[r.row]);
         cs.pick_slot.push_back(r.slot);
         cs.pick_row.push_back(r.row);
+    }
+    if (!fold_slots.empty()) {
+        std::vector<double> survivors(fold_slots.size());
+        bystander_survivor_totals(h->tr, h->query_batch, fold_slots.data(), (int32_t)fold_slots.size(), survivors.data(), h->stream);
+        if (!h->tr.exact_total) bc.refolds += (int32_t)fold_slots.size();
+        size_t x = 0;
+        for (const ByRow& r : bc.rows) {
+            if (r.slot != BY_NO_SLOT || q.statuses[cs.slot_query[r.own]] != KNNCF_OK || removals(q, cs.slot_query[r.own]) == 0) continue;
+            while (fold_slots[x] != r.own) ++x;
+            q.out_d[r.row] = revised_average(h, q, cs.slot_query[r.own], survivors[x]);
+        }
     }
     if (cs.pick_items.empty()) return;
     answer_picks(h, q, cs);
@@ -1781,6 +1808,11 @@ QueryFailure run_bystander_chunks(knncf_handle* h, const QueryCall& q, int64_t c
     auto flush = [&] {  // the chunk in cs / bc through the device, then the answers of its rows
         if (cs.C > 0 && settle_chunk(h, q, cs, &bc) > 0)
             q.mode == QB_BY_NEIGHBORS ? answer_bystander_neighbors(h, q, cs, bc) : answer_bystander_predict(h, q, cs, bc);
+        if (cs.C > 0 && cs.ro[cs.C] > 0) {  // (a chunk that holds a changer with removals)
+            int32_t revise_slots = 0;
+            for (int32_t s = 0; s < cs.C; ++s) revise_slots += cs.ro[s + 1] > cs.ro[s];
+            KN_TRACE_DISPATCH("bystander-revise slots=%d removed=%lld refold=%d", (int)revise_slots, (long long)cs.ro[cs.C], (int)bc.refolds);
+        }
         cs.reset(); bc.clear();
     };
     // one more slot of changer `own`'s (its own included): what the device reads beside the slot
@@ -1981,6 +2013,8 @@ int rows_single(knncf_handle* h, const QueryCall& call) {
         if (call.mode == QB_ENTERED)
             KN_REQUIRE(call.counts && call.width >= 0 && (call.width == 0 || (call.out_i && call.out_d && call.out_pos && call.out_displaced && (call.family == QF_FOLD_IN || call.out_prev))),
                        KNNCF_E_INVALID, "bad output arguments");
+        if (call.family == QF_REVISE)
+            KN_REQUIRE(call.n_removed >= 0 && (call.n_removed == 0 || call.removed_items), KNNCF_E_INVALID, "query: null removed items or n_removed < 0");
         require_single_ratings(call);
         KN_REQUIRE(call.m >= 0, KNNCF_E_INVALID, "query: m < 0");
         if (call.mode == QB_ENTERED) *call.counts = 0;
@@ -3386,6 +3420,44 @@ int knncf_update_bystander_predict_batch(knncf_handle* h, int predictor, const i
     return query_batch(h, bystander_predict_call({.family = QF_UPDATE, .users = users, .B = n_queries, .offsets = offsets,
                                                       .items = items, .ratings = ratings, .pred_offsets = row_offsets,
                                                       .pred_items = pred_items, .statuses = statuses}, predictor, others, out));
+}
+
+// bystanders of revise queries: the same four calls for a user that also removes train rows (knncf.h "Bystanders of revise
+// queries")
+int knncf_revise_bystander_neighbors(knncf_handle* h, int32_t user, const int32_t* removed_items, int64_t n_removed,
+                                     const int32_t* items, const double* ratings, int64_t n_ratings, const int32_t* others, int64_t m,
+                                     int32_t cap, int32_t* ids, double* sims, int32_t* counts) {
+    return rows_single(h, bystander_neighbors_call({.family = QF_REVISE, .items = items, .ratings = ratings, .removed_items = removed_items,
+                                                    .user = user, .n_ratings = n_ratings, .n_removed = n_removed, .m = m},
+                                                   others, cap, ids, sims, counts));
+}
+
+int knncf_revise_bystander_predict(knncf_handle* h, int predictor, int32_t user, const int32_t* removed_items, int64_t n_removed,
+                                   const int32_t* items, const double* ratings, int64_t n_ratings, const int32_t* others,
+                                   const int32_t* pred_items, int64_t m, double* out) {
+    return rows_single(h, bystander_predict_call({.family = QF_REVISE, .items = items, .ratings = ratings, .removed_items = removed_items,
+                                                  .pred_items = pred_items, .user = user, .n_ratings = n_ratings,
+                                                  .n_removed = n_removed, .m = m}, predictor, others, out));
+}
+
+int knncf_revise_bystander_neighbors_batch(knncf_handle* h, const int32_t* users, const int64_t* removed_offsets,
+                                           const int32_t* removed_items, const int64_t* offsets, const int32_t* items,
+                                           const double* ratings, int64_t n_queries, const int64_t* row_offsets, const int32_t* others,
+                                           int32_t cap, int32_t* ids, double* sims, int32_t* counts, int32_t* statuses) {
+    return query_batch(h, bystander_neighbors_call({.family = QF_REVISE, .users = users, .B = n_queries, .offsets = offsets,
+                                                    .items = items, .ratings = ratings, .removed_offsets = removed_offsets,
+                                                    .removed_items = removed_items, .pred_offsets = row_offsets,
+                                                    .statuses = statuses}, others, cap, ids, sims, counts));
+}
+
+int knncf_revise_bystander_predict_batch(knncf_handle* h, int predictor, const int32_t* users, const int64_t* removed_offsets,
+                                         const int32_t* removed_items, const int64_t* offsets, const int32_t* items,
+                                         const double* ratings, int64_t n_queries, const int64_t* row_offsets, const int32_t* others,
+                                         const int32_t* pred_items, double* out, int32_t* statuses) {
+    return query_batch(h, bystander_predict_call({.family = QF_REVISE, .users = users, .B = n_queries, .offsets = offsets,
+                                                  .items = items, .ratings = ratings, .removed_offsets = removed_offsets,
+                                                  .removed_items = removed_items, .pred_offsets = row_offsets,
+                                                  .pred_items = pred_items, .statuses = statuses}, predictor, others, out));
 }
 
 // entered queries: the fitted users whose lists the fold-in query's user joins (knncf.h "Entered queries")

@@ -22,6 +22,13 @@
 //   k_by_merge     for such a slot only looks c up in the written list (in_list for k_by_pick)
 //   k_by_offsets / k_by_gather   index dense(c) reads c's prepared row: deviations on aug, a train row at its train file row,
 //                  an additional row at n_train + its position among the additional rows
+//
+// A fitted changer may also REMOVE train rows (DESIGN.md "Bystanders of revise queries"; knncf_revise_bystander_*).  Its own slot
+// is then a revise slot — k_qb_mark / k_qb_seed_rv leave the removed rows out — and everything above reads that prepared row:
+//   k_by_gather    decides "train row or additional row" by the given position against the slot's LIVE train rows, so a removed
+//                  row is no term and a re-rated item's term stands behind every train row
+//   k_by_survivors average(aug) for the rows answered with it: the fold of the surviving train ratings in file order
+// An item that only c rated and that c removed has no rater in aug: its cell of bs.pred folds nothing (den = 0: v's mean).
 #include <math.h>
 
 #include <algorithm>
@@ -206,15 +213,17 @@ __global__ void __launch_bounds__(ONE_BLOCK) k_by_offsets(int32_t take, int32_t 
 }
 
 // k_qb_gather in which neighbour index qidx[slot] is the changer: entry r of its extent is its r-th known item in dense order,
-// with the deviation k_qb_scatter put there.  A newcomer's file row of given position g is n_train + g (q's rows are the last
-// of aug).  A fitted changer c's row of the item is either a train row — it stays at its train file row s_t, found in c's
-// row of the fit (sorted by dense item) — or an additional one: n_train + (g - c's train rows), the given order of an update
-// slot being the train rows, then the additional rows.
-// Bounds.  The search stays inside [u_ptr[c], u_ptr[c + 1]); gv >= tl for an item it does not find: every train row of c is
-// among the slot's first tl given positions.
+// with the deviation k_qb_scatter put there.  The given order of the changer's slot is its LIVE train rows in file order, then
+// its additional rows (k_qb_seed / k_qb_seed_rv): live = the slot's rows - its additional rows, 0 for a newcomer, c's train
+// rows for an update slot, fewer for a revise slot.  A given position g < live is a live train row: it stays at its train file
+// row s_t, found in c's row of the fit (sorted by dense item) — removals keep the relative order of the other rows.  g >= live
+// is an additional row, behind every train row: n_train + (g - live).  So a removed row is no term, and a re-rated item's term
+// stands at its additional row, whatever c's row of the fit holds for the item.
+// Bounds.  g < live only for a fitted c, whose live rows are rows of [u_ptr[c], u_ptr[c + 1]): the search finds the item there
+// (tl >= live > 0; the index is clamped all the same).  g - live < the slot's additional rows <= 65536.
 __global__ void __launch_bounds__(TPB) k_by_gather(int32_t C, int32_t take, int32_t U, int32_t I, uint32_t n_train,
                                                    const int32_t* __restrict__ qslot, const int32_t* __restrict__ qidx,
-                                                   const int64_t* __restrict__ qo,
+                                                   const int64_t* __restrict__ qo, const int64_t* __restrict__ ao,
                                                    const int32_t* __restrict__ di, const int32_t* __restrict__ given_d,
                                                    const double* __restrict__ dev_d, const int32_t* __restrict__ nbr,
                                                    const double* __restrict__ nsim, const int64_t* __restrict__ off,
@@ -231,18 +240,22 @@ __global__ void __launch_bounds__(TPB) k_by_gather(int32_t C, int32_t take, int3
     const int64_t o = ebase[sb] + lo;
     const double sj = nsim[g];
     if (v == qidx[sb]) {
-        const int64_t oq = qo[qslot[sb]];
+        const int32_t qs = qslot[sb];
+        const int64_t oq = qo[qs], live = (qo[qs + 1] - oq) - (ao[qs + 1] - ao[qs]);
         const int64_t c0 = v == U ? 0 : u_ptr[v], tl = v == U ? 0 : u_ptr[v + 1] - c0;
         for (int64_t r = threadIdx.x & 63; r < hi - lo; r += 64) {
             const int32_t gv = given_d[oq + r], d = di[oq + gv];
             const int64_t x = o + r;
-            int64_t a = 0, e = tl;
-            while (a < e) {
-                const int64_t mid = (a + e) >> 1;
-                if (s_col[c0 + mid] < d) a = mid + 1;
-                else e = mid;
+            uint32_t row = n_train + (uint32_t)(gv - live);
+            if (gv < live && tl > 0) {
+                int64_t a = 0, e = tl;
+                while (a < e) {
+                    const int64_t mid = (a + e) >> 1;
+                    if (s_col[c0 + mid] < d) a = mid + 1;
+                    else e = mid;
+                }
+                row = s_t[c0 + min(a, tl - 1)];
             }
-            const uint32_t row = (a < tl && s_col[c0 + a] == d) ? s_t[c0 + a] : n_train + (uint32_t)(gv - tl);
             key[x] = ((uint64_t)((uint32_t)sb * (uint32_t)I + (uint32_t)d) << 32) | (uint64_t)row;
             val[x] = (uint32_t)x;
             edev[x] = dev_d[oq + r];
@@ -293,7 +306,82 @@ __global__ void k_by_pick(int64_t m, const int32_t* __restrict__ items, const in
     out[j] = avg + w * scale_fn(avg + w, avg);
 }
 
+// average(aug) :18 of a revise query with removals divides the left fold from 0.0 of the SURVIVING train ratings in file order,
+// continued over the additional ratings (the host continues it).  One workgroup per changer slot b = slots[blockIdx.x], a fitted
+// user's revise slot whose status is clear: mark[so[b] + r] != 0 says that row r of its train row [u_ptr, u_ptr + tl) is removed
+// (k_qb_mark), s_t its file row.
+// EXACT (tr.exact_total: every rating is dyadic, the premise under which the fit itself sums with k_exact_sum): every partial
+//   sum is exact, so the fold over the surviving rows is total - (the removed ratings summed in any order).
+// otherwise: the removed file rows are collected into rows[so[b] ..) (any order), then k_sequential_sum's fold over the file in
+//   which a removed rating is replaced by +0.0.  That is the fold without the row bit for bit: x + (+0.0) == x for every x but
+//   -0.0, and a fold from +0.0 never holds -0.0 (a sum is -0.0 only when both operands are).
+// Bounds.  r < tl <= so[b + 1] - so[b] (the slot's source rows are its train rows, then its additional rows), so the marks read
+// and the cells of `rows` written — at most one per mark — lie inside the slot's extent of [so[C]].  A removed file row t is
+// zeroed in buf only when c <= t < c + len.
+static constexpr int AVG_CHUNK = 2048;
+template <bool EXACT>
+__global__ void __launch_bounds__(TPB) k_by_survivors(const int32_t* __restrict__ slots, const int64_t* __restrict__ so,
+                                                      const int32_t* __restrict__ self, const int64_t* __restrict__ u_ptr,
+                                                      const uint32_t* __restrict__ s_t, const double* __restrict__ s_rating,
+                                                      const uint32_t* __restrict__ mark, int64_t n, const double* __restrict__ rating,
+                                                      double total, uint32_t* __restrict__ rows, double* __restrict__ out) {
+    __shared__ double buf[AVG_CHUNK];
+    __shared__ int32_t gone;
+    const int32_t b = slots[blockIdx.x], sd = self[b];
+    const int64_t p0 = u_ptr[sd], tl = u_ptr[sd + 1] - p0, s0 = so[b];
+    if (EXACT) {
+        double acc = 0.0;
+        for (int64_t r = threadIdx.x; r < tl; r += TPB)
+            if (mark[s0 + r] != 0u) acc += s_rating[p0 + r];
+        buf[threadIdx.x] = acc;
+        __syncthreads();
+        for (int o = TPB / 2; o > 0; o >>= 1) {
+            if ((int)threadIdx.x < o) buf[threadIdx.x] += buf[threadIdx.x + o];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) out[blockIdx.x] = total - buf[0];
+        return;
+    }
+    if (threadIdx.x == 0) gone = 0;
+    __syncthreads();
+    for (int64_t r = threadIdx.x; r < tl; r += TPB)
+        if (mark[s0 + r] != 0u) rows[s0 + atomicAdd(&gone, 1)] = s_t[p0 + r];
+    __syncthreads();
+    const int32_t m = gone;
+    double acc = 0.0;
+    for (int64_t c = 0; c < n; c += AVG_CHUNK) {
+        const int32_t len = (int32_t)min((int64_t)AVG_CHUNK, n - c);
+        for (int32_t j = threadIdx.x; j < len; j += TPB) buf[j] = rating[c + j];
+        __syncthreads();
+        for (int32_t x = threadIdx.x; x < m; x += TPB) {
+            const int64_t t = (int64_t)rows[s0 + x] - c;
+            if (t >= 0 && t < len) buf[t] = 0.0;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int32_t j = 0; j < len; ++j) acc = acc + buf[j];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[blockIdx.x] = acc;
+}
+
 static int32_t table_cells(const Train& tr) { return (tr.u_table_n > 0 && tr.i_table_n > 0) ? tr.i_table_n : 0; }
+
+void bystander_survivor_totals(const Train& tr, QueryBatchScratch& bs, const int32_t* h_slots, int32_t n_slots, double* h_out,
+                               hipStream_t st) {
+    KN_REQUIRE(n_slots > 0 && bs.by_chunk && bs.n_removed > 0, KNNCF_E_STATE, "bystander: survivor totals of a chunk without removals");
+    bs.by_rf_slot.ensure(n_slots); bs.by_rf_out.ensure(n_slots); bs.by_rf_rows.ensure(bs.h_so.back());
+    KN_HIP(hipMemcpyAsync(bs.by_rf_slot.p, h_slots, (size_t)n_slots * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (tr.exact_total)
+        k_by_survivors<true><<<n_slots, TPB, 0, st>>>(bs.by_rf_slot.p, bs.so.p, bs.self.p, tr.u_ptr.p, tr.s_t.p, tr.s_rating.p,
+                                                      bs.rm_mark.p, tr.n, tr.rating.p, tr.total, bs.by_rf_rows.p, bs.by_rf_out.p);
+    else
+        k_by_survivors<false><<<n_slots, TPB, 0, st>>>(bs.by_rf_slot.p, bs.so.p, bs.self.p, tr.u_ptr.p, tr.s_t.p, tr.s_rating.p,
+                                                       bs.rm_mark.p, tr.n, tr.rating.p, tr.total, bs.by_rf_rows.p, bs.by_rf_out.p);
+    KN_HIP(hipGetLastError());
+    KN_HIP(hipMemcpyAsync(h_out, bs.by_rf_out.p, (size_t)n_slots * sizeof(double), hipMemcpyDeviceToHost, st));
+    KN_HIP(hipStreamSynchronize(st));
+}
 
 void bystander_upload(QueryBatchScratch& bs, int32_t C, const ByChunk& by, hipStream_t st) {
     bs.by_qslot.ensure(C); bs.by_qidx.ensure(C); bs.by_qrank.ensure(C); bs.by_pair.ensure(C); bs.by_in.ensure(C);
@@ -331,7 +419,7 @@ void bystander_merge(const Train& tr, QueryBatchScratch& bs, int32_t C, int32_t 
 
 void bystander_gather(const Train& tr, QueryBatchScratch& bs, int32_t C, int32_t take, hipStream_t st) {
     k_by_gather<<<(unsigned)ceil_div((int64_t)C * take, TPB / 64), TPB, 0, st>>>(
-        C, take, tr.U, tr.I, (uint32_t)tr.n, bs.by_qslot.p, bs.by_qidx.p, bs.qo.p, bs.di.p, bs.given_d.p, bs.dev_d.p, bs.nbr_idx.p, bs.nbr_sim.p,
+        C, take, tr.U, tr.I, (uint32_t)tr.n, bs.by_qslot.p, bs.by_qidx.p, bs.qo.p, bs.ao.p, bs.di.p, bs.given_d.p, bs.dev_d.p, bs.nbr_idx.p, bs.nbr_sim.p,
         bs.off.p, bs.ebase.p, tr.u_ptr.p, tr.s_col.p, tr.s_t.p, tr.s_dev.p, bs.e_k64_a.p, bs.e_v32_a.p, bs.e_dev.p, bs.e_sim.p);
 }
 

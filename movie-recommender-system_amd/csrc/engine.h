@@ -82,6 +82,7 @@ struct Train {
     std::vector<int64_t> pop_count;  // host: rater counts in that order
     double global_avg = 0.0;
     double total = 0.0;  // the left fold of the ratings in file order that global_avg divides (average :18): bystander queries continue it
+    bool exact_total = false;  // every rating is dyadic (k_check_dyadic): total and every partial sum of it are exact (k_exact_sum)
     int32_t own_lo = 0, own_hi = 0;  // owned dense users [lo, hi)
     int64_t own_p0 = 0, own_p1 = 0;  // their positions in the canonical order (everything when not sharded)
     // the handle's similarity is jaccardCoefficient :440-464: the similarity stage then counts common items — 0/1 operand
@@ -393,6 +394,11 @@ struct QueryBatchScratch {
     DArr<int32_t> by_qslot, by_qidx, by_qrank;
     DArr<double> by_pair, by_in;
     bool by_chunk = false;             // the chunk answered last was a bystander chunk (QueryChunk::by)
+    // bystanders of revise queries: the changer slots whose surviving train ratings are folded (bystander_survivor_totals), the
+    // removed file rows of each ([so[C]], a slot's at so[b]) and the folds
+    DArr<int32_t> by_rf_slot;
+    DArr<uint32_t> by_rf_rows;
+    DArr<double> by_rf_out;
     // entered queries (entered.hip): the answers of a chunk in ONE block (entered_pack), 20 * width + 4 bytes per slot
     DArr<double> en_pack;
 };
@@ -431,7 +437,7 @@ struct QueryChunk {
     // false (the Personalized and the entered modes): the pass stops after the similarities — no keys, no sorts, bs.nbr_idx /
     // nbr_sim / off are not written and the neighbour ratings of h_info are 0
     bool topk;
-    // != nullptr (a bystander chunk: an update chunk with topk and without removals): after the top lists every bystander slot's
+    // != nullptr (a bystander chunk: an update chunk with topk; with removals where the changers are revise slots): after the top lists every bystander slot's
     // list takes its newcomer in — index U, min(k, U) entries — and the neighbour ratings of h_info count the newcomer's known
     // items; a newcomer's own slot and the bystander slots of a newcomer whose status is set have 0.  The bystander slots of a
     // fitted changer get S(v, c) on aug into their similarity row ahead of the sorts instead: min(k, U - 1) entries, c among
@@ -492,6 +498,12 @@ void bystander_gather(const Train& tr, QueryBatchScratch& bs, int32_t C, int32_t
 // foldin_batch_pick for rows of bystander slots: an item that only the newcomer rates has its one term
 void bystander_pick(const Train& tr, QueryBatchScratch& bs, const int32_t* d_items, const int32_t* d_slot, int64_t m, double* d_out,
                     hipStream_t st);
+// bystanders of revise queries: h_out[x] = the left fold from 0.0 of the train ratings in file order without the rows that
+// changer slot h_slots[x] (a fitted user's, with removals, status clear) of the chunk answered last removed — what average(aug)
+// continues over the additional ratings.  tr.exact_total: total - (the removed ratings), exact; otherwise one sequential
+// fold over the file per slot.  Synchronises the stream.
+void bystander_survivor_totals(const Train& tr, QueryBatchScratch& bs, const int32_t* h_slots, int32_t n_slots, double* h_out,
+                               hipStream_t st);
 
 // ---- entered.hip: the fitted users whose neighbour lists a newcomer joins (knncf_query_entered*; DESIGN.md "Entered queries")
 // The answers of a chunk of C slots lie in one block, so that one copy brings them back: sims [C * width] as doubles, then

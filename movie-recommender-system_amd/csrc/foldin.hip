@@ -835,7 +835,7 @@ void foldin_batch_neighbors(const Train& tr, QueryBatchScratch& bs, SortWorkspac
     const double* h_ratings = q.ratings;
     const ByChunk* by = q.by;
     const bool topk = q.topk;
-    KN_REQUIRE(!h_self == !h_ao && (!h_ro || h_self) && (!by || (h_self && topk && !h_ro)), KNNCF_E_INVALID, "query chunk: fields that do not go together");
+    KN_REQUIRE(!h_self == !h_ao && (!h_ro || h_self) && (!by || (h_self && topk)), KNNCF_E_INVALID, "query chunk: fields that do not go together");
     bs.by_chunk = by != nullptr;
     const int32_t U = tr.U, I = tr.I;
     const int64_t W = ceil_div(I, 64), n = h_qo[C];

@@ -1190,6 +1190,7 @@ void prep_fit(Train& tr, PrepScratch& sc, int32_t shard_rank, int32_t shard_coun
     if (fused) KN_HIP(hipMemcpyAsync(&status, sc.status.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     KN_HIP(hipStreamSynchronize(st));
     tr.total = total;
+    tr.exact_total = dyadic;
     tr.global_avg = total / (double)n;
 
     if (shard_count > 1) {  // the host all-gathers the other shards' (mean, norm) segments in place; prep_complete_rows then

@@ -137,6 +137,8 @@ EXPORTS = [
     "knncf_query_bystander_neighbors_batch", "knncf_query_bystander_predict_batch",
     "knncf_update_bystander_neighbors", "knncf_update_bystander_predict",
     "knncf_update_bystander_neighbors_batch", "knncf_update_bystander_predict_batch",
+    "knncf_revise_bystander_neighbors", "knncf_revise_bystander_predict",
+    "knncf_revise_bystander_neighbors_batch", "knncf_revise_bystander_predict_batch",
     "knncf_query_entered", "knncf_query_entered_batch",
     "knncf_update_entered", "knncf_update_entered_batch",
     "knncf_append",
@@ -260,6 +262,12 @@ def load_library():
                                                                         C.c_int32, _i32p, _f64p, _i32p, _i32p]
         getattr(L, f"knncf_{fam}_bystander_predict_batch").argtypes = [C.c_void_p, C.c_int, _i32p, _i64p, _i32p, _f64p, C.c_int64, _i64p,
                                                                       _i32p, _i32p, _f64p, _i32p]
+    # bystanders of revise queries: the removals in front of the additional rows, as knncf_revise_* take them
+    rm_single, rm_batch = [_i32p, C.c_int64], [_i64p, _i32p]
+    for name, head in (("neighbors", 2), ("predict", 3)):
+        single, batch = getattr(L, f"knncf_update_bystander_{name}").argtypes, getattr(L, f"knncf_update_bystander_{name}_batch").argtypes
+        getattr(L, f"knncf_revise_bystander_{name}").argtypes = single[:head] + rm_single + single[head:]
+        getattr(L, f"knncf_revise_bystander_{name}_batch").argtypes = batch[:head] + rm_batch + batch[head:]
     # entered queries: the fold-in query, cap, then users / sims / positions / displaced and the count(s)
     L.knncf_query_entered.argtypes = [C.c_void_p, C.c_int32, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p, _i32p, _i32p]
     # the same for update queries: users / sims / positions / previous / other and the count(s)
@@ -1141,9 +1149,9 @@ class Engine:
 
 
 class BystanderQueries:
-    """Bystander queries (knncf_query_bystander_*, knncf_update_bystander_*) on a fitted Engine: a FITTED user's kNN answers once
-    the user of a fold-in query has joined the data (*_for), or a user that may be in the fit has added ratings (*_with), without
-    a refit.  A query is (user, items, ratings) as Engine.neighbors_for takes it; a row names the
+    """Bystander queries (knncf_query_bystander_*, knncf_update_bystander_*, knncf_revise_bystander_*) on a fitted Engine: a FITTED
+    user's kNN answers once the user of a fold-in query has joined the data (*_for), or a user that may be in the fit has added
+    ratings (*_with) or has removed or re-rated items as well (*_with(..., removed=...)), without a refit.  A query is (user, items, ratings) as Engine.neighbors_for takes it; a row names the
     fitted user (`others`), the predict forms an item beside it (`pred_items`).  Read-only on the engine's handle: the
     neighbour lists and their build history stay as they were.
 
@@ -1195,26 +1203,28 @@ class BystanderQueries:
     def _fn(self, fam, name):
         return getattr(self._e._lib, f"knncf_{fam}_bystander_{name}")
 
-    def _neighbors(self, fam, user, items, ratings, others, cap):
-        q, it, rt = self._e._query_rows(user, items, ratings, allow_empty=fam == "update")
+    def _neighbors(self, fam, user, items, ratings, others, cap, removed=None):
+        q, it, rt = self._e._query_rows(user, items, ratings, allow_empty=fam != "query")
+        rm = self._e._rm_args(fam, removed)
         oth = self._row_ids(others, "others")
         cap, m = self._row_cap(cap, self._e.k), len(oth)
         ids = np.empty((m, cap), dtype=np.int32)
         sims = np.empty((m, cap), dtype=np.float64)
         counts = np.zeros(m, dtype=np.int32)
         p = self._e._ptr
-        self._e._check(self._fn(fam, "neighbors")(self._e._h, q, p(it, _i32p), p(rt, _f64p), len(it), p(oth, _i32p), m, cap,
+        self._e._check(self._fn(fam, "neighbors")(self._e._h, q, *rm, p(it, _i32p), p(rt, _f64p), len(it), p(oth, _i32p), m, cap,
                                                   p(ids.reshape(-1), _i32p), p(sims.reshape(-1), _f64p), p(counts, _i32p)))
         return [(ids[r, :min(counts[r], cap)].copy(), sims[r, :min(counts[r], cap)].copy()) for r in range(m)]
 
-    def _predict(self, fam, user, items, ratings, others, pred_items):
-        q, it, rt = self._e._query_rows(user, items, ratings, allow_empty=fam == "update")
+    def _predict(self, fam, user, items, ratings, others, pred_items, removed=None):
+        q, it, rt = self._e._query_rows(user, items, ratings, allow_empty=fam != "query")
+        rm = self._e._rm_args(fam, removed)
         oth, pi = self._row_ids(others, "others"), self._row_ids(pred_items, "pred_items")
         if len(oth) != len(pi):
             raise ValueError("others and pred_items must be of the same length")
         out = np.full(len(oth), np.nan, dtype=np.float64)
         p = self._e._ptr
-        self._e._check(self._fn(fam, "predict")(self._e._h, PRED_KNN, q, p(it, _i32p), p(rt, _f64p), len(it), p(oth, _i32p),
+        self._e._check(self._fn(fam, "predict")(self._e._h, PRED_KNN, q, *rm, p(it, _i32p), p(rt, _f64p), len(it), p(oth, _i32p),
                                                 p(pi, _i32p), len(oth), p(out, _f64p)))
         return out
 
@@ -1265,22 +1275,47 @@ class BystanderQueries:
         return self._predict_batch("query", queries, others, pred_items)
 
     # the same four for a `user` that may be in the fit (knncf_update_bystander_*): the given rows are ADDITIONAL to its train
-    # rows, as Engine.neighbors_with takes them, and may be empty for a fitted user
-    def neighbors_with(self, user, items, ratings, others, cap=None):
-        """getNeighbors(train ++ user's additional ratings, k, sim)(v) for every v of `others`: [(ids, sims)] per row"""
-        return self._neighbors("update", user, items, ratings, others, cap)
+    # rows, as Engine.neighbors_with takes them, and may be empty for a fitted user.  With `removed` (knncf_revise_bystander_*) the
+    # user also takes train items OUT, as Engine.neighbors_revised takes them: aug = train without the user's rows on the removed
+    # items ++ the additional rows, and an item both removed and given again is re-rated.  removed=None is the update call itself;
+    # a batch takes one sequence of removed items per query.  (The family is an argument and not four more methods: the public
+    # methods of this class are the call kinds of the stateful model in tests/call_sequences.py.)
+    def _revise_queries(self, queries, removed):
+        """the (user, removed_items, items, ratings) of a batch whose queries are (user, items, ratings)"""
+        queries, removed = list(queries), list(removed)
+        if len(removed) != len(queries):
+            raise ValueError("one removed sequence per query")
+        for q in queries:
+            if not isinstance(q, (tuple, list)) or len(q) != 3:
+                raise ValueError("a query is (user, items, ratings)")
+        return [(q[0], rm, q[1], q[2]) for q, rm in zip(queries, removed)]
 
-    def predict_with(self, user, items, ratings, others, pred_items):
-        """kNN predictions of (others[r], pred_items[r]) on train ++ user's additional ratings: a float64 array"""
-        return self._predict("update", user, items, ratings, others, pred_items)
+    def neighbors_with(self, user, items, ratings, others, cap=None, removed=None):
+        """getNeighbors(train ++ user's additional ratings, k, sim)(v) for every v of `others`: [(ids, sims)] per row; with
+        `removed`, on train without the user's rows on those items ++ the additional ratings"""
+        if removed is None:
+            return self._neighbors("update", user, items, ratings, others, cap)
+        return self._neighbors("revise", user, items, ratings, others, cap, removed)
 
-    def neighbors_with_batch(self, queries, others, cap=None):
-        """neighbors_with of every query: ([[(ids, sims)] per row] per query, statuses)"""
-        return self._neighbors_batch("update", queries, others, cap)
+    def predict_with(self, user, items, ratings, others, pred_items, removed=None):
+        """kNN predictions of (others[r], pred_items[r]) on train ++ user's additional ratings: a float64 array; with `removed`,
+        on train without the user's rows on those items ++ the additional ratings"""
+        if removed is None:
+            return self._predict("update", user, items, ratings, others, pred_items)
+        return self._predict("revise", user, items, ratings, others, pred_items, removed)
 
-    def predict_with_batch(self, queries, others, pred_items):
-        """predict_with of every query: ([float64 array] per query, statuses)"""
-        return self._predict_batch("update", queries, others, pred_items)
+    def neighbors_with_batch(self, queries, others, cap=None, removed=None):
+        """neighbors_with of every query (removed: one sequence of removed items per query): ([[(ids, sims)] per row] per query,
+        statuses)"""
+        if removed is None:
+            return self._neighbors_batch("update", queries, others, cap)
+        return self._neighbors_batch("revise", self._revise_queries(queries, removed), others, cap)
+
+    def predict_with_batch(self, queries, others, pred_items, removed=None):
+        """predict_with of every query (removed: one sequence of removed items per query): ([float64 array] per query, statuses)"""
+        if removed is None:
+            return self._predict_batch("update", queries, others, pred_items)
+        return self._predict_batch("revise", self._revise_queries(queries, removed), others, pred_items)
 
 
 class Appends:
