@@ -910,7 +910,8 @@ int knncf_update_bystander_predict_batch(knncf_handle* h, int predictor, const i
  * n_removed == 0 in every query of a call gives the knncf_update_bystander_* answer bit for bit through the same code.
  * KNNCF_DEBUG_TRACE_DISPATCH prints, after the `bystander` line of a chunk that holds a changer with removals,
  *     knncf-dispatch bystander-revise slots=<such changer slots> removed=<their removed items> refold=<sequential folds>
- * OUT OF SCOPE: the entered question for revise queries (knncf_revise_entered*) and removals in knncf_append; prefix checkpoints
+ * OUT OF SCOPE: removals in knncf_append (the entered question for revise queries is served by knncf_revise_entered*: "Entered
+ * queries of revise queries" below); prefix checkpoints
  * that would shorten the sequential fold; KNNCF_PRED_PERSONALIZED and the other predictors; device-pointer forms; shard handles
  * and knncf_group_*; the command-line tool. */
 int knncf_revise_bystander_neighbors(knncf_handle* h, int32_t user, const int32_t* removed_items, int64_t n_removed,
@@ -971,7 +972,7 @@ int knncf_revise_bystander_predict_batch(knncf_handle* h, int predictor, const i
  * slot, at most 20 bytes * num_users) is allocated beside the budget, as the gathered ratings are.  The results do not depend on
  * C, and a repeated call of the same shape allocates no device memory.
  * OUT OF SCOPE: newcomers that are in the fit (their bystanders' lists: "Bystanders of update queries" above; the entered
- * question for them: "Entered queries of update queries" below; it is not served for revise queries); KNNCF_PRED_PERSONALIZED; cosine fits with users of 4
+ * question for them: "Entered queries of update queries" below; for revise queries: "Entered queries of revise queries" below); KNNCF_PRED_PERSONALIZED; cosine fits with users of 4
  * or fewer ratings; an ordering by similarity; device-pointer forms; shard handles and knncf_group_*; the command-line tool. */
 int knncf_query_entered(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
                         int32_t cap, int32_t* out_users, double* out_sims, int32_t* out_pos, int32_t* out_displaced,
@@ -1015,14 +1016,68 @@ int knncf_query_entered_batch(knncf_handle* h, const int32_t* users, const int64
  * Chunks.  C of "Batched fold-in queries", one slot per query in phase 1 (24 bytes * min(cap, num_users) + 4 per slot of answer
  * scratch beside the budget); the tail rows of a chunk then travel as "Bystanders of update queries" describes.  Results do not
  * depend on C; a repeated call of the same shape allocates no device memory.
- * OUT OF SCOPE: revise queries; KNNCF_PRED_PERSONALIZED; cosine fits with users of 4 or fewer ratings; device-pointer forms;
- * shard handles and knncf_group_*; the command-line tool. */
+ * OUT OF SCOPE: revise queries (a changer that also removes train rows: "Entered queries of revise queries" below);
+ * KNNCF_PRED_PERSONALIZED; cosine fits with users of 4 or fewer ratings; device-pointer forms; shard handles and knncf_group_*;
+ * the command-line tool. */
 int knncf_update_entered(knncf_handle* h, int32_t user, const int32_t* items, const double* ratings, int64_t n_ratings,
                          int32_t cap, int32_t* out_users, double* out_sims, int32_t* out_pos, int32_t* out_prev,
                          int32_t* out_other, int32_t* count);
 int knncf_update_entered_batch(knncf_handle* h, const int32_t* users, const int64_t* offsets, const int32_t* items,
                                const double* ratings, int64_t n_queries, int32_t cap, int32_t* out_users, double* out_sims,
                                int32_t* out_pos, int32_t* out_prev, int32_t* out_other, int32_t* counts, int32_t* statuses);
+
+/* ---- Entered queries of revise queries: whose kNN lists a user's removals change ----------------------------------------------
+ * The entered question for a changer that also takes ratings OUT: when fitted user c deletes a rating, or rates an item again,
+ * its mean, every deviation and its norm move — which other fitted users' cached kNN answers are stale?  One pass over the fit,
+ * where knncf_revise_bystander_neighbors would take one slot per fitted user.  The argument lists are knncf_update_entered*'s
+ * with the removals in front of the additional rows, where knncf_revise_bystander_* puts them.
+ * A query is a revise query exactly as knncf_revise_* defines it: c = users[b], the train items it takes out (removed_items rows
+ * [removed_offsets[b], removed_offsets[b + 1])), its additional rows;
+ *     aug_b = train without c's rows on the removed items, in file order, ++ the additional rows in order.
+ * Queries are independent.
+ * Which users are reported: as "Entered queries of update queries" above.  For a fitted v != c, L0 = getNeighbors(train, k,
+ * sim)(v) and L1 = getNeighbors(aug_b, k, sim)(v) on closures of v's own; v is REPORTED iff c occurs in L0 or in L1, with two
+ * exceptions: (a) a fitted c with n_removed == 0 AND n_ratings == 0 — aug is train; KNNCF_OK, nothing reported.  A fitted c that
+ * only removes is an ordinary query: aug is not train; (b) c stands in both lists at the same position with a similarity of
+ * +-0.0 of identical bits.  Only (b) silences a row: a re-rating with the SAME value is an ordinary query too (the row moves
+ * behind every train row, and the bits of c's mean may move with it), and equal non-zero bits at the same position are reported.
+ * Guarantee for an unreported v: L1 == L0 in ids and similarity bits, and every KNNCF_PRED_KNN prediction of v on aug_b equals
+ * its prediction on train bit for bit — but for users answered with the global average.
+ * Outputs, their set order, counts[b] that may exceed cap, untouched cells, cap == 0 as a count-only call with null arrays, tail
+ * rows and the single form (the batch of one; *count = 0 once the argument checks pass): those of knncf_update_entered*.
+ *   out_sims   S(v, c) on aug_b, owned by v: the left fold in v's dense-item order over c's row on aug, whatever c's size class
+ *              there.  A FITTED COSINE CHANGER THAT FALLS TO 4 OR FEWER ROWS ON aug_b IS ACCEPTED: v owns the pair and has more
+ *              than 4 ratings on the accepted handles, so the fold order is v's (c's own answers, knncf_revise_neighbors, fold
+ *              such a pair in c's given order: their bits may differ from out_sims).
+ * An item that leaves aug (c was its only train rater, removed it and did not give it again) changes no list: nobody else rated
+ * it, so it was a term of no pair.
+ * Tail rows within cap are resolved through knncf_revise_bystander_neighbors_batch internally with the query's removed items
+ * (knncf_update_bystander_neighbors_batch for a call whose queries all have n_removed == 0).
+ * Per-query statuses: those of knncf_revise_neighbors_batch — KNNCF_E_INVALID for a removed item that c did not rate in train, a
+ * removed item listed twice, any removal for a user absent from train, a fitted user left without a row (and an empty query of
+ * an absent user); KNNCF_E_DUPLICATE for an additional row on an unremoved train item or a repeated item; KNNCF_E_NONFINITE;
+ * KNNCF_E_UNSUPPORTED for a negative mean on aug or more than 65536 rows, removed rows included — and KNNCF_E_UNSUPPORTED when a
+ * tail user within cap has more than 65536 train ratings.  A failed query gets counts[b] = 0 and untouched rows.
+ * Refusals of the handle and handle state: those of knncf_update_entered_batch.  NOT read-only: the missing lists M are built
+ * first, in one batch in ascending raw id, which leaves the state knncf_neighbors_batch over M leaves.  A KNNCF_SIM_COSINE handle
+ * whose TRAIN set has a user of 4 or fewer ratings is refused, Jaccard is accepted.  KNNCF_E_INVALID for n_removed < 0, null
+ * removed items with n_removed > 0, and removed_offsets that are null, do not start at 0 or decrease.
+ * n_removed == 0 in every query of a call gives the knncf_update_entered* answer bit for bit through the same code and with the
+ * same trace lines.  KNNCF_DEBUG_TRACE_DISPATCH prints, after the `entered_update` line of a chunk that holds a changer with
+ * removals,
+ *     knncf-dispatch entered_revise slots=<changer slots with removals> removed=<their removed items> small=<fitted slots of <= 4 rows on aug>
+ * Chunks.  C of "Batched fold-in queries", one revise slot per query in phase 1 and the answer scratch of the update form; the
+ * tail rows of a chunk then travel as "Bystanders of revise queries" describes.  Results do not depend on C; a repeated call of
+ * the same shape allocates no device memory.
+ * OUT OF SCOPE: removals in knncf_append; KNNCF_PRED_PERSONALIZED; cosine fits with train users of 4 or fewer ratings;
+ * device-pointer forms; shard handles and knncf_group_*; the command-line tool. */
+int knncf_revise_entered(knncf_handle* h, int32_t user, const int32_t* removed_items, int64_t n_removed, const int32_t* items,
+                         const double* ratings, int64_t n_ratings, int32_t cap, int32_t* out_users, double* out_sims,
+                         int32_t* out_pos, int32_t* out_prev, int32_t* out_other, int32_t* count);
+int knncf_revise_entered_batch(knncf_handle* h, const int32_t* users, const int64_t* removed_offsets,
+                               const int32_t* removed_items, const int64_t* offsets, const int32_t* items, const double* ratings,
+                               int64_t n_queries, int32_t cap, int32_t* out_users, double* out_sims, int32_t* out_pos,
+                               int32_t* out_prev, int32_t* out_other, int32_t* counts, int32_t* statuses);
 
 /* ---- Append: new ratings into the fit, the kNN lists they cannot change kept ---------------------------------------------------
  * The query families above say what new ratings would change; knncf_append makes the n rows (users[j], items[j], ratings[j])

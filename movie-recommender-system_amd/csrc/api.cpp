@@ -1074,7 +1074,8 @@ constexpr int64_t QUERY_MAX_RATINGS = 65536;
 // (knncf_*_recommend_explain*): no requested rows, so neither explains() nor wants_rows()
 // QB_BY_NEIGHBORS / QB_BY_PREDICT: bystander queries (knncf_*_bystander_*) — a query's rows name fitted users; run_bystander_chunks
 // QB_ENTERED: entered queries (knncf_query_entered*) — no rows; an answer step of run_query_chunks (answer_entered); under
-// QF_UPDATE the entered queries of update queries (knncf_update_entered*; answer_entered_update)
+// QF_UPDATE / QF_REVISE the entered queries of update and revise queries (knncf_update_entered*, knncf_revise_entered*;
+// answer_entered_update)
 enum QueryBatchMode { QB_NEIGHBORS, QB_PREDICT, QB_RECOMMEND, QB_EXPLAIN, QB_EXPLAIN_ALL, QB_RECOMMEND_EXPLAIN, QB_BY_NEIGHBORS, QB_BY_PREDICT, QB_ENTERED };
 bool bystanders(QueryBatchMode mode) { return mode == QB_BY_NEIGHBORS || mode == QB_BY_PREDICT; }
 bool explains(QueryBatchMode mode) { return mode == QB_EXPLAIN || mode == QB_EXPLAIN_ALL; }
@@ -1181,7 +1182,7 @@ struct QueryCall {
     ExplainCells ex;                 // explain modes: pred_offsets[B] rows; QB_RECOMMEND_EXPLAIN: B * n rows, row b * n + j (pred null)
     int32_t* out_pos;                // QB_ENTERED: [B * cap] beside out_i (users) and out_d (sims), width = cap
     int32_t* out_displaced;          // QB_ENTERED: [B * cap]
-    int32_t* out_prev;               // QB_ENTERED under QF_UPDATE (knncf_update_entered*): [B * cap]; null otherwise
+    int32_t* out_prev;               // QB_ENTERED under QF_UPDATE / QF_REVISE (knncf_update_entered*, knncf_revise_entered*): [B * cap]; null otherwise
     int32_t user;                    // single forms only, from here on
     int64_t n_ratings, n_removed, m;
 };
@@ -1590,6 +1591,8 @@ int64_t bystander_chunk(knncf_handle* h, int64_t budget);
 // best candidate outside the list decides) through the bystander path: one internal knncf_update_bystander_neighbors_batch over
 // the chunk's queries that have some, rows = their tail users, cap = take.  A query's rows are written once all of them are
 // resolved; a query whose tail user the bystander path refuses takes that status and keeps its rows untouched.
+// Under QF_REVISE (knncf.h "Entered queries of revise queries") the chunk's slots are revise slots, and the internal call is
+// knncf_revise_bystander_neighbors_batch with each query's removed items.
 void answer_entered_update(knncf_handle* h, const QueryCall& q, ChunkState& cs) {
     if (cs.take == 0) {  // (k <= 0: no list has a cell)
         for (const int32_t s : cs.good) q.counts[cs.slot_query[s]] = 0;
@@ -1604,7 +1607,7 @@ void answer_entered_update(knncf_handle* h, const QueryCall& q, ChunkState& cs) 
         const uint32_t qkey = int_trie_key(cs.s_users[s]);
         cs.qrank[s] = (int32_t)(std::lower_bound(h->h_ukeys.begin(), h->h_ukeys.end(), qkey) - h->h_ukeys.begin());
     }
-    entered_update_chunk(h->tr, h->nt, bs, cs.C, take, width, cs.qo.data(), cs.s_self.data(), cs.qrank.data(), st);
+    entered_update_chunk(h->tr, h->nt, bs, cs.C, take, width, cs.qo.data(), cs.s_self.data(), cs.ro.data(), cs.qrank.data(), st);
     const size_t bytes = entered_update_pack_bytes(cs.C, width);
     cs.h_vals.resize((bytes + 7) / 8);
     KN_HIP(hipMemcpyAsync(cs.h_vals.data(), bs.en_pack.p, bytes, hipMemcpyDeviceToHost, st));
@@ -1613,8 +1616,10 @@ void answer_entered_update(knncf_handle* h, const QueryCall& q, ChunkState& cs) 
     int32_t* prev = entered_pack_prev(got, cs.C);
     // phase 2: the tail rows within the written cells, query after query
     std::vector<int32_t> t_users, t_items, t_others, t_cell, t_status;
-    std::vector<int64_t> t_off(1, 0), t_rows(1, 0);
+    std::vector<int32_t> t_removed;
+    std::vector<int64_t> t_off(1, 0), t_rows(1, 0), t_roff(1, 0);
     std::vector<double> t_ratings;
+    const bool revise = q.family == QF_REVISE;
     std::vector<int32_t> t_of((size_t)cs.C, -1);  // the slot's query of the internal call
     for (const int32_t s : cs.good) {
         const size_t at = (size_t)s * width;
@@ -1630,14 +1635,18 @@ void answer_entered_update(knncf_handle* h, const QueryCall& q, ChunkState& cs) 
         t_items.insert(t_items.end(), q.items + q.offsets[b], q.items + q.offsets[b + 1]);
         t_ratings.insert(t_ratings.end(), q.ratings + q.offsets[b], q.ratings + q.offsets[b + 1]);
         t_off.push_back((int64_t)t_items.size());
+        if (revise) t_removed.insert(t_removed.end(), q.removed_items + q.removed_offsets[b], q.removed_items + q.removed_offsets[b + 1]);
+        t_roff.push_back((int64_t)t_removed.size());
         t_rows.push_back((int64_t)t_others.size());
     }
     std::vector<int32_t> l_ids((size_t)t_others.size() * take), l_counts(t_others.size(), 0);
     std::vector<double> l_sims((size_t)t_others.size() * take);
     if (!t_users.empty()) {
         t_status.assign(t_users.size(), KNNCF_OK);
-        const QueryCall inner = bystander_neighbors_call({.family = QF_UPDATE, .users = t_users.data(), .B = (int64_t)t_users.size(),
+        const QueryCall inner = bystander_neighbors_call({.family = q.family, .users = t_users.data(), .B = (int64_t)t_users.size(),
                                                           .offsets = t_off.data(), .items = t_items.data(), .ratings = t_ratings.data(),
+                                                          .removed_offsets = revise ? t_roff.data() : nullptr,
+                                                          .removed_items = revise ? t_removed.data() : nullptr,
                                                           .pred_offsets = t_rows.data(), .statuses = t_status.data()},
                                                          t_others.data(), take, l_ids.data(), l_sims.data(), l_counts.data());
         const auto t0 = std::chrono::steady_clock::now();  // (the hook also says what phase 2 took: it ends synchronised)
@@ -1693,7 +1702,7 @@ QueryFailure run_query_chunks(knncf_handle* h, const QueryCall& q, int64_t chunk
             case QB_EXPLAIN_ALL: answer_explain(h, q, cs, ex_rows); break;
             case QB_RECOMMEND: answer_recommend(h, q, cs); break;
             case QB_RECOMMEND_EXPLAIN: answer_recommend_explain(h, q, cs, ex_rows); break;
-            case QB_ENTERED: q.family == QF_UPDATE ? answer_entered_update(h, q, cs) : answer_entered(h, q, cs); break;
+            case QB_ENTERED: q.family != QF_FOLD_IN ? answer_entered_update(h, q, cs) : answer_entered(h, q, cs); break;
             case QB_BY_NEIGHBORS:
             case QB_BY_PREDICT: throw Error(KNNCF_E_INVALID, "query: a bystander mode in run_query_chunks (run_bystander_chunks answers them)");
         }
@@ -3489,6 +3498,25 @@ int knncf_update_entered_batch(knncf_handle* h, const int32_t* users, const int6
     return query_batch(h, entered_call({.family = QF_UPDATE, .users = users, .B = n_queries, .offsets = offsets, .items = items,
                                         .ratings = ratings, .statuses = statuses, .out_pos = out_pos, .out_displaced = out_other,
                                         .out_prev = out_prev}, cap, out_users, out_sims, counts));
+}
+
+// the same question for a revise query's user, which may also remove train rows (knncf.h "Entered queries of revise queries")
+int knncf_revise_entered(knncf_handle* h, int32_t user, const int32_t* removed_items, int64_t n_removed, const int32_t* items,
+                         const double* ratings, int64_t n_ratings, int32_t cap, int32_t* out_users, double* out_sims, int32_t* out_pos,
+                         int32_t* out_prev, int32_t* out_other, int32_t* count) {
+    return rows_single(h, entered_call({.family = QF_REVISE, .items = items, .ratings = ratings, .removed_items = removed_items,
+                                        .out_pos = out_pos, .out_displaced = out_other, .out_prev = out_prev, .user = user,
+                                        .n_ratings = n_ratings, .n_removed = n_removed}, cap, out_users, out_sims, count));
+}
+
+int knncf_revise_entered_batch(knncf_handle* h, const int32_t* users, const int64_t* removed_offsets, const int32_t* removed_items,
+                               const int64_t* offsets, const int32_t* items, const double* ratings, int64_t n_queries, int32_t cap,
+                               int32_t* out_users, double* out_sims, int32_t* out_pos, int32_t* out_prev, int32_t* out_other,
+                               int32_t* counts, int32_t* statuses) {
+    return query_batch(h, entered_call({.family = QF_REVISE, .users = users, .B = n_queries, .offsets = offsets, .items = items,
+                                        .ratings = ratings, .removed_offsets = removed_offsets, .removed_items = removed_items,
+                                        .statuses = statuses, .out_pos = out_pos, .out_displaced = out_other, .out_prev = out_prev},
+                                       cap, out_users, out_sims, counts));
 }
 
 int knncf_append(knncf_handle* h, const int32_t* users, const int32_t* items, const double* ratings, int64_t n, int64_t* n_carried,

@@ -537,11 +537,14 @@ void entered_chunk(const Train& tr, const NeighborTable& nt, QueryBatchScratch& 
 // nothing.  The block is an EnteredPack followed by prev [C * width] (entered_pack_prev): the changer's position in the
 // stored list or -1; `displaced` holds out_other of an entered cell and -1 otherwise.  pos == EN_TAIL marks a cell that the
 // stored list cannot decide (a tail row): the caller resolves it.  Up to six launches, no round trip.
+// Entered queries of revise queries (knncf_revise_entered*; DESIGN.md "Entered queries of revise queries"): the same call after
+// a REVISE chunk.  h_ro [C + 1] = the chunk's removed CSR on the host (all 0 for a chunk without removals, which is an update
+// chunk); a fitted slot with removals reports even without additional rows.
 static constexpr int32_t EN_TAIL = -2;
 inline size_t entered_update_pack_bytes(int32_t C, int32_t width) { return (size_t)C * ((size_t)width * 24 + 4); }
 inline int32_t* entered_pack_prev(const EnteredPack& p, int32_t C) { return p.counts + C; }
 void entered_update_chunk(const Train& tr, const NeighborTable& nt, QueryBatchScratch& bs, int32_t C, int32_t take, int32_t width,
-                          const int64_t* h_qo, const int32_t* h_self, const int32_t* h_qrank, hipStream_t st);
+                          const int64_t* h_qo, const int32_t* h_self, const int64_t* h_ro, const int32_t* h_qrank, hipStream_t st);
 // the first stage of entered_update_chunk alone: the chunk's report bitmaps [C][ceil(U / 64)], bit v of row b = fitted user v is
 // reported for slot b (tail rows included; a user without a built list is reported whenever the changer is not in it).  They
 // lie in the chunk's sort keys until the next chunk.  No trace line, no round trip.

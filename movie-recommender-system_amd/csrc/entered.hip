@@ -32,9 +32,18 @@ static constexpr int TPB = 256;
 // q's <= 4 known items are walked in dense order (rank r -> given position -> dense item) and looked up in v's row, which is
 // sorted by dense item.  A slot with more rows keeps bs.sim's cell: k_query_sim / k_query_sim_dual folded it in v's row order =
 // dense-item order, the same products in the same order.
+// The slot may be a newcomer's or a fitted changer's that its removals leave with <= 4 rows on aug (a revise slot): the fold-in
+// kernels folded that cell in the slot's given order — live train rows in file order, then the additional rows — like a
+// newcomer's, and pre_d holds c's preprocessed values ON AUG.  (Cell [b][self[b]] gets c's row on aug against its row of the
+// fit: no stage reads it.)
 // Bounds.  g < C * U, so b < C and v < U.  q's distinct known items number kq = rank[b][W] <= its rows <= 4, and k_qb_scatter
 // wrote given_d / pre_d of exactly those ranks; a given position is < the slot's rows and di of a known row is in [0, I).  The
 // search stays inside [u_ptr[v], u_ptr[v + 1]).
+// A revise slot: the sorted SOURCE rows of the slot are [live train rows by file row, additional rows, dropped rows], of which
+// k_qb_seed_rv copies the first qo[b + 1] - qo[b] into the chunk — the dropped rows never become chunk rows, whatever the
+// removals were (a bad removal included: its slot keeps its declared extent).  So qo, di, given_d, pre_d and rank describe the
+// live and additional rows only, exactly as for a newcomer: the bitmap's population counts distinct known items among those
+// qo[b + 1] - qo[b] <= 4 rows, k_qb_scatter wrote ranks [0, kq) of the slot's extent, and every given position is < that extent.
 __global__ void __launch_bounds__(TPB) k_en_pair(int32_t C, int32_t U, int64_t W, const int64_t* __restrict__ qo,
                                                  const int32_t* __restrict__ di, const int32_t* __restrict__ given_d,
                                                  const double* __restrict__ pre_d, const int64_t* __restrict__ rank,
@@ -187,6 +196,13 @@ void entered_chunk(const Train& tr, const NeighborTable& nt, QueryBatchScratch& 
 //   k_enu_flag    one thread per (slot, v): the report rule; the ballots are the slot's bitmap (k_en_compact is reused)
 //   k_enu_place   one wave per reported cell: the five outputs; a cell the stored list cannot decide is marked EN_TAIL
 // A slot with self[b] < 0 is a newcomer's: was = -1 everywhere, and the three kernels do what k_en_flag / k_en_place do.
+//
+// ---- entered queries of revise queries (DESIGN.md "Entered queries of revise queries"; knncf_revise_entered*) ----------------
+// A fitted changer may also REMOVE train rows: its slot is a revise slot of foldin.hip, and bs.sim holds S(c, v) on aug = train
+// without those rows ++ the additional ones.  Removing rows of c changes c's mean, deviations and norm only, like adding some:
+// every other pair, c's place in set order and the stored lists are the fit's, so the stages above answer it.  Two things differ:
+//   k_en_pair   also runs for a fitted changer that falls to <= 4 rows on aug — its cell was folded in c's given order
+//   k_enu_flag  is silent for a fitted slot only when it has neither additional rows nor removals (aug is train)
 
 static constexpr int LOC_BITS = 32768;  // cells of k_enu_locate's filter: 4 KB of LDS whatever U is
 
@@ -224,15 +240,18 @@ __global__ void __launch_bounds__(TPB) k_enu_locate(int32_t C, int32_t U, int32_
 
 // One thread per (slot b, dense user v), laid out as k_en_flag's.  v is reported iff c occurs in its list on train or on aug,
 // but for a c that stays where it is with a similarity of +-0.0 of the same bits (no term of any fold), and for a fitted c
-// without additional rows (aug is train; ao [C + 1] = the first additional row of each slot, as the update chunk uploaded it).
+// without additional rows and without removals (aug is train; ao [C + 1] = the first additional row of each slot, as the
+// update chunk uploaded it; ro [C + 1] = the first removed item of each slot, null for a chunk without removals).
 //   was < 0   c is not in the stored list: it enters under k_en_flag's rule, `at` = dense(c) for a fitted c (its place in set
 //             order), the number of train users in front of it for a newcomer
 //   was >= 0  c is in the stored list, so v is reported unless the new similarity has the stored cell's bits (the same key, the
 //             same place) and is +-0.0
-// Bounds.  As k_en_flag; was[b * U + v] and sim[b * U + v] with b < C, v < U; the stored cell v * kcap + was < U * kcap.
+// Bounds.  As k_en_flag; was[b * U + v] and sim[b * U + v] with b < C, v < U; the stored cell v * kcap + was < U * kcap; ao and
+// ro hold C + 1 cells.
 __global__ void __launch_bounds__(TPB) k_enu_flag(int32_t C, int32_t U, int32_t take, int32_t kcap, const int32_t* __restrict__ self,
                                                   const int32_t* __restrict__ qrank, const int64_t* __restrict__ ao,
-                                                  const double* __restrict__ sim, const int32_t* __restrict__ was,
+                                                  const int64_t* __restrict__ ro, const double* __restrict__ sim,
+                                                  const int32_t* __restrict__ was,
                                                   const int32_t* __restrict__ cnt, const int32_t* __restrict__ idx,
                                                   const double* __restrict__ nsim, unsigned long long* __restrict__ bits) {
     const int64_t Wu = ((int64_t)U + 63) >> 6, Upad = Wu << 6;
@@ -240,7 +259,7 @@ __global__ void __launch_bounds__(TPB) k_enu_flag(int32_t C, int32_t U, int32_t 
     if (g >= (int64_t)C * Upad) return;  // (whole waves: C * Upad is a multiple of 64)
     const int32_t b = (int32_t)(g / Upad), v = (int32_t)(g - (int64_t)b * Upad);
     bool f = false;
-    if (v < U && v != self[b] && ao[b + 1] > ao[b]) {
+    if (v < U && v != self[b] && (ao[b + 1] > ao[b] || (ro && ro[b + 1] > ro[b]))) {
         const double s = sim[(int64_t)b * U + v];
         const int32_t w = was[(int64_t)b * U + v];
         if (w >= 0) {
@@ -306,24 +325,27 @@ __global__ void __launch_bounds__(TPB) k_enu_place(int32_t C, int32_t U, int32_t
     oprev[g] = w;
 }
 
-// phase 1 of an update chunk: S(v, c) where it is not bs.sim's cell, the stored cell of every fitted changer (was [C][U]) and
-// the report bitmaps [C][ceil(U / 64)], which are returned.  *was_out = was; *fitted_out / *pair_out = the chunk's fitted changers and
-// whether k_en_pair ran (the caller's trace line).
+// phase 1 of an update or revise chunk: S(v, c) where it is not bs.sim's cell, the stored cell of every fitted changer (was
+// [C][U]) and the report bitmaps [C][ceil(U / 64)], which are returned.  *was_out = was; *fitted_out / *pair_out / *small_out =
+// the chunk's fitted changers, whether k_en_pair ran and the fitted changers of <= 4 rows on aug (the caller's trace lines).
 static unsigned long long* enu_phase1(const Train& tr, const NeighborTable& nt, QueryBatchScratch& bs, int32_t C, int32_t take,
                                       const int64_t* h_qo, const int32_t* h_self, const int32_t* h_qrank, int32_t** was_out,
-                                      int32_t* fitted_out, bool* pair_out, hipStream_t st) {
+                                      int32_t* fitted_out, bool* pair_out, int32_t* small_out, hipStream_t st) {
     const int32_t U = tr.U;
     const int64_t W = ceil_div(tr.I, 64);
     bs.by_qrank.ensure(C);
     KN_HIP(hipMemcpyAsync(bs.by_qrank.p, h_qrank, (size_t)C * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    // a newcomer of <= 4 rows folds in its given order (k_en_pair); a fitted cosine changer has > 4 rows on the accepted handles
+    // a slot of <= 4 rows on aug folds in its given order (k_en_pair): a newcomer, or a fitted changer whose removals leave it
+    // that few (a fitted cosine changer has > 4 TRAIN rows on the accepted handles, so without removals there is none)
     bool small = false;
-    int32_t fitted = 0;
+    int32_t fitted = 0, small_fitted = 0;
     for (int32_t b = 0; b < C; ++b) {
-        small |= h_self[b] < 0 && h_qo[b + 1] - h_qo[b] <= 4;
+        const bool few = h_qo[b + 1] - h_qo[b] <= 4;
+        small |= few;
         fitted += h_self[b] >= 0;
+        small_fitted += h_self[b] >= 0 && few;
     }
-    if (small && !tr.jaccard)  // (slots of > 4 rows return at once: a fitted changer's cell stays)
+    if (small && !tr.jaccard)  // (slots of > 4 rows return at once: their cell stays)
         k_en_pair<<<(unsigned)ceil_div((int64_t)C * U, TPB), TPB, 0, st>>>(C, U, W, bs.qo.p, bs.di.p, bs.given_d.p, bs.pre_d.p, bs.rank.p,
                                                                            tr.u_ptr.p, tr.s_col.p, tr.s_pre.p, bs.sim.p);
     // the bitmaps and their prefixes as entered_chunk keeps them; was [C][U] lies in the chunk's sort values ([C * max(U, I)]
@@ -335,26 +357,34 @@ static unsigned long long* enu_phase1(const Train& tr, const NeighborTable& nt, 
     if (fitted > 0)
         k_enu_locate<<<(unsigned)std::min<int64_t>(ceil_div(U, TPB / 64), 4096), TPB, 0, st>>>(C, U, nt.kcap, bs.self.p, nt.cnt.p,
                                                                                               nt.idx.p, was);
-    k_enu_flag<<<(unsigned)ceil_div((int64_t)C * Wu * 64, TPB), TPB, 0, st>>>(C, U, take, nt.kcap, bs.self.p, bs.by_qrank.p, bs.ao.p,
+    // (bs.ro holds the chunk's removed CSR only when the chunk has removals: foldin_batch_neighbors uploads it then)
+    const int64_t* ro = bs.n_removed > 0 ? bs.ro.p : nullptr;
+    k_enu_flag<<<(unsigned)ceil_div((int64_t)C * Wu * 64, TPB), TPB, 0, st>>>(C, U, take, nt.kcap, bs.self.p, bs.by_qrank.p, bs.ao.p, ro,
                                                                               bs.sim.p, was, nt.cnt.p, nt.idx.p, nt.sim.p, ebits);
     KN_HIP(hipGetLastError());
     *was_out = was;
     *pair_out = small && !tr.jaccard;
     *fitted_out = fitted;
+    *small_out = small_fitted;
     return ebits;
 }
 
 void entered_update_chunk(const Train& tr, const NeighborTable& nt, QueryBatchScratch& bs, int32_t C, int32_t take, int32_t width,
-                          const int64_t* h_qo, const int32_t* h_self, const int32_t* h_qrank, hipStream_t st) {
+                          const int64_t* h_qo, const int32_t* h_self, const int64_t* h_ro, const int32_t* h_qrank, hipStream_t st) {
     const int32_t U = tr.U;
     bs.en_pack.ensure((entered_update_pack_bytes(C, width) + 7) / 8);
     const EnteredPack out = entered_pack(bs.en_pack.p, C, width);
     int32_t* prev = entered_pack_prev(out, C);
     int32_t* was = nullptr;
-    int32_t fitted = 0;
+    int32_t fitted = 0, small = 0;
     bool pair = false;
-    unsigned long long* ebits = enu_phase1(tr, nt, bs, C, take, h_qo, h_self, h_qrank, &was, &fitted, &pair, st);
+    unsigned long long* ebits = enu_phase1(tr, nt, bs, C, take, h_qo, h_self, h_qrank, &was, &fitted, &pair, &small, st);
     KN_TRACE_DISPATCH("entered_update slots=%d fitted=%d pair=%d width=%d", (int)C, (int)fitted, (int)pair, (int)width);
+    if (h_ro[C] > 0) {  // (a chunk that holds a changer with removals)
+        int32_t revise_slots = 0;
+        for (int32_t b = 0; b < C; ++b) revise_slots += h_ro[b + 1] > h_ro[b];
+        KN_TRACE_DISPATCH("entered_revise slots=%d removed=%lld small=%d", (int)revise_slots, (long long)h_ro[C], (int)small);
+    }
     k_en_compact<<<C, ONE_BLOCK, 0, st>>>(U, width, ebits, (int64_t*)bs.k64_a.p, out.users, out.counts);
     if (width > 0)
         k_enu_place<<<(unsigned)ceil_div((int64_t)C * width, TPB / 64), TPB, 0, st>>>(C, U, take, nt.kcap, width, bs.by_qrank.p, bs.sim.p,
@@ -366,9 +396,9 @@ void entered_update_chunk(const Train& tr, const NeighborTable& nt, QueryBatchSc
 const unsigned long long* entered_update_flags(const Train& tr, const NeighborTable& nt, QueryBatchScratch& bs, int32_t C, int32_t take,
                                                const int64_t* h_qo, const int32_t* h_self, const int32_t* h_qrank, hipStream_t st) {
     int32_t* was = nullptr;
-    int32_t fitted = 0;
+    int32_t fitted = 0, small = 0;
     bool pair = false;
-    return enu_phase1(tr, nt, bs, C, take, h_qo, h_self, h_qrank, &was, &fitted, &pair, st);
+    return enu_phase1(tr, nt, bs, C, take, h_qo, h_self, h_qrank, &was, &fitted, &pair, &small, st);
 }
 
 }  // namespace knncf

@@ -140,7 +140,7 @@ EXPORTS = [
     "knncf_revise_bystander_neighbors", "knncf_revise_bystander_predict",
     "knncf_revise_bystander_neighbors_batch", "knncf_revise_bystander_predict_batch",
     "knncf_query_entered", "knncf_query_entered_batch",
-    "knncf_update_entered", "knncf_update_entered_batch",
+    "knncf_update_entered", "knncf_update_entered_batch", "knncf_revise_entered", "knncf_revise_entered_batch",
     "knncf_append",
     "knncf_predict_batch",
     "knncf_predict_batch_device", "knncf_mae", "knncf_mae_device", "knncf_mae_sweep", "knncf_mae_sweep_device", "knncf_shard_view_get",
@@ -277,6 +277,10 @@ def load_library():
                                              _i32p, _i32p, _i32p]
     L.knncf_query_entered_batch.argtypes = [C.c_void_p, _i32p, _i64p, _i32p, _f64p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p, _i32p,
                                             _i32p, _i32p]
+    # the same for revise queries: the removals in front of the additional rows
+    L.knncf_revise_entered.argtypes = L.knncf_update_entered.argtypes[:2] + rm_single + L.knncf_update_entered.argtypes[2:]
+    L.knncf_revise_entered_batch.argtypes = (L.knncf_update_entered_batch.argtypes[:2] + rm_batch +
+                                             L.knncf_update_entered_batch.argtypes[2:])
     # append: the rows, then |K|, |B ∩ S| and the dropped raw ids with their cap
     L.knncf_append.argtypes = [C.c_void_p, _i32p, _i32p, _f64p, C.c_int64, _i64p, _i64p, _i32p, C.c_int64]
     # revise queries: the update argument lists with the removals in front of the additional rows
@@ -1354,7 +1358,7 @@ class Appends:
 
 
 class EnteredQueries:
-    """Entered queries (knncf_query_entered*) on a fitted Engine: the FITTED users whose neighbour list the user of a fold-in
+    """Entered queries (knncf_query_entered*, knncf_update_entered*, knncf_revise_entered*) on a fitted Engine: the FITTED users whose neighbour list the user of a fold-in
     query joins, without a refit.  A query is (user, items, ratings) as Engine.neighbors_for takes it.  NOT read-only on the
     engine's handle: a call first BUILDS THE NEIGHBOUR LISTS THAT ARE MISSING, all in one batch in ascending raw id, as
     Engine.neighbors_batch over those users would.
@@ -1421,35 +1425,46 @@ class EnteredQueries:
             cap = call(0)[1]
         return call(cap)[0]
 
-    def _call_with(self, qargs, B, cap):
-        """one knncf_update_entered_batch call: (users, sims, positions, previous, other) [B, cap], counts, statuses"""
+    # entered_with* take `removed` as BystanderQueries.*_with do: removed=None is the update call itself (knncf_update_entered*);
+    # otherwise the user also takes train items OUT (knncf_revise_entered*), one sequence of removed items per query in the batch
+    # form.  (A keyword and not two more methods: the public methods of this class are call kinds of tests/call_sequences.py.)
+    def _call_with(self, qargs, B, cap, fam="update"):
+        """one knncf_update_entered_batch / knncf_revise_entered_batch call: (users, sims, positions, previous, other) [B, cap],
+        counts, statuses"""
         out = (np.empty((B, cap), dtype=np.int32), np.empty((B, cap), dtype=np.float64), np.empty((B, cap), dtype=np.int32),
                np.empty((B, cap), dtype=np.int32), np.empty((B, cap), dtype=np.int32))
         counts = np.zeros(B, dtype=np.int32)
         st = np.zeros(B, dtype=np.int32)
         p = self._e._ptr
-        self._e._check(self._e._lib.knncf_update_entered_batch(
+        self._e._check(getattr(self._e._lib, f"knncf_{fam}_entered_batch")(
             self._e._h, *qargs, cap, *(p(a.reshape(-1), _f64p if a.dtype == np.float64 else _i32p) for a in out), p(counts, _i32p),
             p(st, _i32p)))
         return out, counts, st
 
-    def entered_with_batch(self, queries, cap=None):
-        """entered_with() of every (user, items, ratings) of `queries`: ([(users, sims, positions, previous, other)] per query,
-        statuses int32 [B]); a failed query has empty arrays.  cap=None asks for the counts first, then for all entries."""
-        qargs, keep = self._e._batch_args("update", queries)
+    def entered_with_batch(self, queries, cap=None, removed=None):
+        """entered_with() of every (user, items, ratings) of `queries` (removed: one sequence of removed items per query):
+        ([(users, sims, positions, previous, other)] per query, statuses int32 [B]); a failed query has empty arrays.  cap=None
+        asks for the counts first, then for all entries."""
+        fam = "update" if removed is None else "revise"
+        if removed is not None:
+            queries = BystanderQueries._revise_queries(None, queries, removed)
+        qargs, keep = self._e._batch_args(fam, queries)
         B, cap = qargs[-1], self._cap(cap)
         if cap is None:
-            _, counts, _ = self._call_with(qargs, B, 0)
+            _, counts, _ = self._call_with(qargs, B, 0, fam)
             cap = int(counts.max()) if B else 0
-        out, counts, st = self._call_with(qargs, B, cap)
+        out, counts, st = self._call_with(qargs, B, cap, fam)
         return [tuple(a[b, :min(counts[b], cap)].copy() for a in out) for b in range(B)], st
 
-    def entered_with(self, user, items, ratings, cap=None):
+    def entered_with(self, user, items, ratings, cap=None, removed=None):
         """knncf_update_entered: `user` may be IN the fit and (items, ratings) are its ADDITIONAL ratings.  The fitted users v
         whose kNN list holds `user` on train or on train ++ those ratings, in the fit's set order: (users, sims = S(v, user) on
         aug, positions of `user` in v's list on aug or -1 if it left, previous = its position on train or -1 if it entered,
-        other = the raw id that left the list (entered) or came into it (left), else -1).  cap=None asks for the count first."""
+        other = the raw id that left the list (entered) or came into it (left), else -1).  cap=None asks for the count first.
+        With `removed` (knncf_revise_entered) aug is train without the user's rows on those items ++ the additional ratings."""
         q, it, rt = self._e._query_rows(user, items, ratings, allow_empty=True)
+        fam = "update" if removed is None else "revise"
+        rm = self._e._rm_args(fam, removed)
         cap = self._cap(cap)
         p = self._e._ptr
 
@@ -1457,9 +1472,9 @@ class EnteredQueries:
             us, pos, prev, other = (np.empty(cap, dtype=np.int32) for _ in range(4))
             sims = np.empty(cap, dtype=np.float64)
             c = C.c_int32()
-            self._e._check(self._e._lib.knncf_update_entered(self._e._h, q, p(it, _i32p), p(rt, _f64p), len(it), cap, p(us, _i32p),
-                                                             p(sims, _f64p), p(pos, _i32p), p(prev, _i32p), p(other, _i32p),
-                                                             C.byref(c)))
+            fn = getattr(self._e._lib, f"knncf_{fam}_entered")
+            self._e._check(fn(self._e._h, q, *rm, p(it, _i32p), p(rt, _f64p), len(it), cap, p(us, _i32p), p(sims, _f64p), p(pos, _i32p),
+                              p(prev, _i32p), p(other, _i32p), C.byref(c)))
             m = min(c.value, cap)
             return (us[:m].copy(), sims[:m].copy(), pos[:m].copy(), prev[:m].copy(), other[:m].copy()), c.value
 
