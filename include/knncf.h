@@ -910,8 +910,8 @@ int knncf_update_bystander_predict_batch(knncf_handle* h, int predictor, const i
  * n_removed == 0 in every query of a call gives the knncf_update_bystander_* answer bit for bit through the same code.
  * KNNCF_DEBUG_TRACE_DISPATCH prints, after the `bystander` line of a chunk that holds a changer with removals,
  *     knncf-dispatch bystander-revise slots=<such changer slots> removed=<their removed items> refold=<sequential folds>
- * OUT OF SCOPE: removals in knncf_append (the entered question for revise queries is served by knncf_revise_entered*: "Entered
- * queries of revise queries" below); prefix checkpoints
+ * OUT OF SCOPE: removals in knncf_append (knncf_amend takes them; the entered question for revise queries is served by
+ * knncf_revise_entered*: "Entered queries of revise queries" below); prefix checkpoints
  * that would shorten the sequential fold; KNNCF_PRED_PERSONALIZED and the other predictors; device-pointer forms; shard handles
  * and knncf_group_*; the command-line tool. */
 int knncf_revise_bystander_neighbors(knncf_handle* h, int32_t user, const int32_t* removed_items, int64_t n_removed,
@@ -1069,8 +1069,8 @@ int knncf_update_entered_batch(knncf_handle* h, const int32_t* users, const int6
  * Chunks.  C of "Batched fold-in queries", one revise slot per query in phase 1 and the answer scratch of the update form; the
  * tail rows of a chunk then travel as "Bystanders of revise queries" describes.  Results do not depend on C; a repeated call of
  * the same shape allocates no device memory.
- * OUT OF SCOPE: removals in knncf_append; KNNCF_PRED_PERSONALIZED; cosine fits with train users of 4 or fewer ratings;
- * device-pointer forms; shard handles and knncf_group_*; the command-line tool. */
+ * OUT OF SCOPE: removals in knncf_append (knncf_amend takes them: "Amend" below); KNNCF_PRED_PERSONALIZED; cosine fits with
+ * train users of 4 or fewer ratings; device-pointer forms; shard handles and knncf_group_*; the command-line tool. */
 int knncf_revise_entered(knncf_handle* h, int32_t user, const int32_t* removed_items, int64_t n_removed, const int32_t* items,
                          const double* ratings, int64_t n_ratings, int32_t cap, int32_t* out_users, double* out_sims,
                          int32_t* out_pos, int32_t* out_prev, int32_t* out_other, int32_t* count);
@@ -1118,10 +1118,69 @@ int knncf_revise_entered_batch(knncf_handle* h, const int32_t* users, const int6
  * no stage.
  * Measurement hook: the environment variable KNNCF_DEBUG_APPEND_MAX_CHANGERS, read at every call, replaces the constant below for
  * that call (0: every append is a plain refit); scripts/append_latency.py brackets the crossover with it.  Not for production use.
- * OUT OF SCOPE: removals; a device-pointer form; shard handles and knncf_group_*; the command-line tool. */
+ * OUT OF SCOPE: removals (knncf_amend below takes them); a device-pointer form; shard handles and knncf_group_*; the
+ * command-line tool. */
 #define KNNCF_APPEND_MAX_CHANGERS 128
 int knncf_append(knncf_handle* h, const int32_t* users, const int32_t* items, const double* ratings, int64_t n,
                  int64_t* n_carried, int64_t* n_dropped, int32_t* dropped, int64_t dropped_cap);
+
+/* ---- Amend: removals and re-ratings into the fit, the kNN lists they cannot change kept -------------------------------------------
+ * knncf_append with removals in front: the train rows (removed_users[j], removed_items[j]), j < n_removed, leave the fit, then
+ * the n rows join it.  aug is built in two steps: train in file order without the removed rows; then the n rows in the given
+ * order.  Everything else is knncf_append's contract, read on this aug.
+ * Answers.  Every later call on the handle answers bit for bit as a handle on which knncf_fit(aug) was called.
+ * Changers.  The distinct users of the removals and of the rows.  Changer c is the revise query (c, its removed items, its rows
+ * of the call in order) on the handle as it stood before the call.
+ * Handle state.  B = the users whose neighbour list was built before the call.  S = the changers and every fitted user that
+ * knncf_revise_entered_batch reports for that query, each changer on its own; a tail row is reported, hence in S.  K = B \ S.
+ * The handle is left in the state that knncf_fit(aug) followed by knncf_neighbors_batch over K in ascending raw id leaves: the
+ * lists, the build numbers, the call counter, the knncf_neighbors_save bytes.  Nothing outside K is built.
+ * Why S is still enough.  A list that holds c on train is reported for c; S(v, c) on the joint aug reads v's rows, which did
+ * not move, and c's rows on c's own aug, so it is the value c's own query saw and sorts behind v's stored last cell; no pair of
+ * two non-changers moves — items that leave, users and items that join keep the relative set order of the rest.  Removing rows
+ * shifts the file rows of everyone behind them and moves the global and the item averages: the lists read neither, and what
+ * does is rebuilt by the refit (DESIGN.md "Amend").
+ * Semantics.
+ *   - A re-rating is a removal plus a row for the same (user, item): the row moves behind every train row.  A re-rating with the
+ *     same value is an ordinary change (the bits of the user's mean may move with the row): the lists of S are dropped.
+ *   - A removed item whose only rater was the changer leaves the fit: num_items shrinks, the item is no recommendation candidate
+ *     any more and predicts as an unknown item; no list changes because of it.
+ *   - A fitted user whose train rows are all removed and who gives no row leaves the fit: num_users shrinks (a plain refit).
+ * Outputs.  *n_carried = |K|, *n_dropped = |B ∩ S| and dropped as in knncf_append: the first min(*n_dropped, dropped_cap) raw ids
+ * of B ∩ S in the new fit's user set order.  A user that left stands where its id would stand in that order; where the new fit
+ * has fewer than 5 users (their order is that of first occurrence) it stands behind them.
+ * Plain refits.  Nothing is carried (*n_carried = 0, dropped = B; the answers are still those of knncf_fit(aug)) under every rule
+ * of knncf_append, read on the revise queries — the stored list length min(k, num_users' - 1) changes; KNNCF_SIM_ONE; more than
+ * KNNCF_APPEND_MAX_CHANGERS changers; a changer's revise query is KNNCF_E_UNSUPPORTED (a negative mean on aug, more than 65536
+ * rows with the removed ones included, a fit of fewer than 5 users or items) — and when
+ *   - a user leaves the fit (the carry maps every old user into the new fit),
+ *   - the handle is KNNCF_SIM_COSINE and train or aug has a user of 4 or fewer ratings, a changer that its removals bring down to
+ *     4 rows or fewer included.  Jaccard carries in that case.
+ * Statuses.  KNNCF_E_STATE before a fit; KNNCF_E_UNSUPPORTED on a shard handle; KNNCF_E_INVALID for a null pointer that is needed
+ * (removed_users / removed_items with n_removed > 0, the rows with n > 0, dropped with dropped_cap > 0, n_carried, n_dropped) or a
+ * negative n_removed, n or dropped_cap; KNNCF_E_INVALID for a removal whose (user, item) is not a train row — a user or an item
+ * unknown to train and a newcomer of the same call included —, for a removal listed twice, and for an aug without any row;
+ * KNNCF_E_DUPLICATE for a row on a (user, item) that aug already holds: an unremoved train row, or one repeated within the rows;
+ * KNNCF_E_NONFINITE for a non-finite deviation.  Precedence: the argument checks, then the removal checks, then the duplicate,
+ * then the non-finite deviation.  The removal checks are the removal stage's own (every removal must match exactly one train
+ * row) and run whether or not the marking runs.  After any refusal the handle is exactly as before the call: the new fit is
+ * built beside the old one and swapped in last, as in knncf_append (a SECOND copy of the fit's arrays during the call).
+ * Trivial calls.  n_removed == 0 && n == 0 is KNNCF_OK and touches nothing: *n_carried = |B|, *n_dropped = 0.  n_removed == 0 is
+ * knncf_append bit for bit through the same code: knncf_append is the call without removals.
+ * The removal stage.  The old fit's three file-order arrays are compacted on the device, in tiles of KNNCF_AMEND_TILE rows, into
+ * the new fit's: every train row looks its (user, item) up in the sorted table of the removals, a scan of the tiles' survivor
+ * counts gives each tile its place, and the surviving rows are written in file order — stable, without atomics.  The old arrays
+ * stay intact until the swap; a repeated call of the same shape allocates nothing for this stage.
+ * Timings: the removal stage, the refit and the carry are charged to prep_ms.
+ * KNNCF_DEBUG_TRACE_DISPATCH prints knncf_append's `append` line for every call and, after it, for a call with removals
+ *     knncf-dispatch amend removers=<changers with removals> removed=<n_removed> kept_rows=<train rows that went into aug>
+ * KNNCF_DEBUG_APPEND_MAX_CHANGERS applies as in knncf_append.
+ * OUT OF SCOPE: carrying when a user leaves; a device-pointer form; shard handles and knncf_group_*; the command-line tool;
+ * KNNCF_PRED_PERSONALIZED state (a refit drops it, as before). */
+#define KNNCF_AMEND_TILE 2048
+int knncf_amend(knncf_handle* h, const int32_t* removed_users, const int32_t* removed_items, int64_t n_removed,
+                const int32_t* users, const int32_t* items, const double* ratings, int64_t n,
+                int64_t* n_carried, int64_t* n_dropped, int32_t* dropped, int64_t dropped_cap);
 
 /* ---- batch ---------------------------------------------------------------- */
 int knncf_predict_batch(knncf_handle* h, int predictor, const int32_t* users,

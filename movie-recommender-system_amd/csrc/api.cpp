@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <chrono>
 #include <functional>
+#include <map>
 #include <vector>
 
 #include "engine.h"
@@ -2147,10 +2148,20 @@ void do_neighbors_load(knncf_handle* h, const char* path) {
 // tail rows included) and its fitted changers are ORed into one stale mask on the device.  Then the new Train is built beside
 // the old one from the concatenated rows; the lists of K = built and not stale are carried into the new numbering; the swap
 // comes last, so a refusal on the way leaves the handle as it was.
+// knncf_amend (DESIGN.md "Amend") is the same call with removals in front: the changers are the users of the removals too and run
+// through REVISE chunks, and the new Train's first part is the old file order without the removed rows (amend_flag, which also
+// decides whether every removal is a train row, and amend_compact).  knncf_append is the call without removals.
 struct AppendRows {
     std::vector<int32_t> changers, items;
     std::vector<int64_t> offsets;
     std::vector<double> ratings;
+    // the removals (knncf_amend; all empty without any): per changer beside its rows, and as the table amend_flag searches
+    std::vector<int64_t> removed_offsets;  // [changers + 1] into removed
+    std::vector<int32_t> removed;          // the removed items of each changer, in the given order
+    std::vector<uint64_t> keys;            // [n_removed] (user << 32 | item, both as uint32), ascending
+    std::vector<int64_t> given;            // keys[j] is removal given[j] of the call
+    std::vector<uint32_t> removers;        // the distinct users of keys, ascending
+    std::vector<int64_t> roff;             // [removers + 1] into keys
 };
 AppendRows group_append_rows(const int32_t* users, const int32_t* items, const double* ratings, int64_t n) {
     AppendRows g;
@@ -2185,14 +2196,54 @@ AppendRows group_append_rows(const int32_t* users, const int32_t* items, const d
     return g;
 }
 
-// the marking; false: a changer's update query is KNNCF_E_UNSUPPORTED (the plain refit).  Throws a duplicate or a non-finite
-// deviation as the call's status.
+// the removals into g: users that only remove become changers behind those of the rows, in the order of their first removal.
+// Throws a removal listed twice.
+void group_removals(AppendRows& g, const int32_t* users, const int32_t* items, int64_t n) {
+    std::vector<std::pair<uint64_t, int64_t>> table((size_t)n);
+    for (int64_t j = 0; j < n; ++j) table[j] = {((uint64_t)(uint32_t)users[j] << 32) | (uint32_t)items[j], j};
+    std::sort(table.begin(), table.end());
+    g.roff.assign(1, 0);
+    for (int64_t j = 0; j < n; ++j) {
+        if (j > 0 && table[j].first == table[j - 1].first)
+            throw Error(KNNCF_E_INVALID, "amend: removal " + std::to_string(table[j].second) + " (user " + std::to_string(users[table[j].second]) +
+                                             ", item " + std::to_string(items[table[j].second]) + ") is listed twice");
+        g.keys.push_back(table[j].first);
+        g.given.push_back(table[j].second);
+        const uint32_t user = (uint32_t)(table[j].first >> 32);
+        if (g.removers.empty() || g.removers.back() != user) {
+            g.removers.push_back(user);
+            g.roff.push_back(j);
+        }
+        g.roff.back() = j + 1;
+    }
+    std::map<int32_t, int32_t> slot_of;  // a changer's slot by its raw id
+    for (size_t s = 0; s < g.changers.size(); ++s) slot_of[g.changers[s]] = (int32_t)s;
+    std::vector<int32_t> slot((size_t)n);
+    for (int64_t j = 0; j < n; ++j) {
+        const auto [at, fresh] = slot_of.try_emplace(users[j], (int32_t)g.changers.size());
+        if (fresh) {
+            g.changers.push_back(users[j]);
+            g.offsets.push_back(g.offsets.back());  // (no rows)
+        }
+        slot[j] = at->second;
+    }
+    g.removed_offsets.assign(g.changers.size() + 1, 0);
+    for (int64_t j = 0; j < n; ++j) g.removed_offsets[slot[j] + 1] += 1;
+    for (size_t s = 0; s < g.changers.size(); ++s) g.removed_offsets[s + 1] += g.removed_offsets[s];
+    g.removed.resize((size_t)n);
+    std::vector<int64_t> at(g.removed_offsets.begin(), g.removed_offsets.end() - 1);
+    for (int64_t j = 0; j < n; ++j) g.removed[at[slot[j]]++] = items[j];
+}
+
+// the marking; false: a changer's update query — its revise query when the call has removals — is KNNCF_E_UNSUPPORTED (the plain
+// refit).  Throws a duplicate or a non-finite deviation as the call's status.
 bool mark_stale_lists(knncf_handle* h, const AppendRows& g) {
     const int64_t B = (int64_t)g.changers.size();
     std::vector<int32_t> statuses((size_t)B, KNNCF_OK);
     QueryCall q{};
-    q.family = QF_UPDATE; q.mode = QB_ENTERED; q.predictor = KNNCF_PRED_KNN;
+    q.family = g.removed.empty() ? QF_UPDATE : QF_REVISE; q.mode = QB_ENTERED; q.predictor = KNNCF_PRED_KNN;
     q.users = g.changers.data(); q.B = B; q.offsets = g.offsets.data(); q.items = g.items.data(); q.ratings = g.ratings.data();
+    if (q.family == QF_REVISE) { q.removed_offsets = g.removed_offsets.data(); q.removed_items = g.removed.data(); }
     q.statuses = statuses.data();
     ChunkState cs;
     cs.take = std::max(0, std::min(h->cfg.k, h->tr.U));
@@ -2222,13 +2273,14 @@ bool mark_stale_lists(knncf_handle* h, const AppendRows& g) {
     return true;
 }
 
-void do_append(knncf_handle* h, const int32_t* users, const int32_t* items, const double* ratings, int64_t n, int64_t* n_carried,
-               int64_t* n_dropped, int32_t* dropped, int64_t dropped_cap) {
+void do_amend(knncf_handle* h, const int32_t* removed_users, const int32_t* removed_items, int64_t n_removed, const int32_t* users,
+              const int32_t* items, const double* ratings, int64_t n, int64_t* n_carried, int64_t* n_dropped, int32_t* dropped,
+              int64_t dropped_cap) {
     require_fitted(h, false);
     KN_REQUIRE(h->cfg.shard_count == 1, KNNCF_E_UNSUPPORTED, "append: single-shard handles only");
-    KN_REQUIRE(n >= 0 && n_carried && n_dropped && dropped_cap >= 0 && (dropped_cap == 0 || dropped) &&
-                   (n == 0 || (users && items && ratings)),
-               KNNCF_E_INVALID, "append: null argument, n < 0 or dropped_cap < 0");
+    KN_REQUIRE(n >= 0 && n_removed >= 0 && n_carried && n_dropped && dropped_cap >= 0 && (dropped_cap == 0 || dropped) &&
+                   (n == 0 || (users && items && ratings)) && (n_removed == 0 || (removed_users && removed_items)),
+               KNNCF_E_INVALID, "append: null argument, n < 0, n_removed < 0 or dropped_cap < 0");
     Train& tr = h->tr;
     NeighborTable& nt = h->nt;
     AppendScratch& as = h->append;
@@ -2241,57 +2293,91 @@ void do_append(knncf_handle* h, const int32_t* users, const int32_t* items, cons
         KN_HIP(hipMemcpyAsync(totals, as.totals.p, sizeof totals, hipMemcpyDeviceToHost, st));
         KN_HIP(hipStreamSynchronize(st));
     };
-    if (n == 0) {  // touches nothing: |B| from the build numbers
+    if (n == 0 && n_removed == 0) {  // touches nothing: |B| from the build numbers
         append_sets(as, tr, nt, false, 0, st);
         fetch_totals();
         *n_carried = totals[0];
         *n_dropped = 0;
         return;
     }
-    KN_REQUIRE(tr.n + n < ((int64_t)1 << 29), KNNCF_E_UNSUPPORTED, "append: more than 2^29-1 ratings");
-    const AppendRows g = group_append_rows(users, items, ratings, n);
+    AppendRows g = group_append_rows(users, items, ratings, n);
+    // ---- the removals: which file rows go, and whether every removal is a train row
+    int64_t kept_rows = tr.n;
+    if (n_removed > 0) {
+        group_removals(g, removed_users, removed_items, n_removed);
+        int64_t verdict[2] = {0, 0};
+        {
+            Stage s(h, &h->tm.prep_ms);
+            amend_flag(as, tr, g.keys.data(), n_removed, g.removers.data(), g.roff.data(), (int32_t)g.removers.size(), st);
+        }
+        KN_HIP(hipMemcpyAsync(verdict, as.totals.p + 2, sizeof verdict, hipMemcpyDeviceToHost, st));
+        KN_HIP(hipStreamSynchronize(st));
+        if (verdict[1] >= 0) {
+            const int64_t j = g.given[(size_t)verdict[1]];
+            throw Error(KNNCF_E_INVALID, "amend: removal " + std::to_string(j) + " (user " + std::to_string(removed_users[j]) + ", item " +
+                                             std::to_string(removed_items[j]) + ") is not a row of the training set");
+        }
+        kept_rows = verdict[0];
+        KN_REQUIRE(kept_rows == tr.n - n_removed, KNNCF_E_STATE, "amend: the surviving rows are not the train rows without the removals");
+        KN_REQUIRE(kept_rows + n > 0, KNNCF_E_INVALID, "amend: the removals leave the training set without a row");
+    }
+    KN_REQUIRE(kept_rows + n < ((int64_t)1 << 29), KNNCF_E_UNSUPPORTED, "append: more than 2^29-1 ratings");
     const int64_t n_changers = (int64_t)g.changers.size();
     // ---- the plain refits that the rows alone decide
     load_host_ids(h);
-    int32_t joined = 0;
-    bool short_newcomer = false;
-    for (int64_t b = 0; b < n_changers; ++b)
-        if (dense_lookup(h->h_ukeys.data(), U, g.changers[b]) < 0) {
-            joined += 1;
-            short_newcomer |= g.offsets[b + 1] - g.offsets[b] <= 4;
-        }
+    int32_t joined = 0, left = 0;
+    int64_t removers = 0;
+    bool short_changer = false;  // a newcomer of <= 4 rows, or a fitted changer that its removals leave that few
+    for (int64_t b = 0; b < n_changers; ++b) {
+        const int32_t du = dense_lookup(h->h_ukeys.data(), U, g.changers[b]);
+        const int64_t nr = n_removed > 0 ? g.removed_offsets[b + 1] - g.removed_offsets[b] : 0;
+        // (its rows on aug; a fitted changer without removals keeps its train rows, which nothing below asks for)
+        const int64_t rows = g.offsets[b + 1] - g.offsets[b] - nr + (du >= 0 && nr > 0 ? train_row_length(h, du) : 0);
+        removers += nr > 0;
+        joined += du < 0;
+        left += du >= 0 && nr > 0 && rows == 0;
+        short_changer |= (du < 0 || nr > 0) && rows <= 4;
+    }
     // (KNNCF_DEBUG_APPEND_MAX_CHANGERS: measurement hook of scripts/append_latency.py, which locates the crossover behind the
     // constant — another limit, 0 = every append is a plain refit)
     const char* limit = getenv("KNNCF_DEBUG_APPEND_MAX_CHANGERS");
     const int64_t max_changers = limit ? atoll(limit) : KNNCF_APPEND_MAX_CHANGERS;
-    const int32_t new_kcap = std::max(0, std::min(h->cfg.k, U + joined - 1));
+    const int32_t new_kcap = std::max(0, std::min(h->cfg.k, U + joined - left - 1));
     const bool no_lists = h->cfg.similarity == KNNCF_SIM_ONE || nt.kcap <= 0 || h->epoch == 1;  // (no call has built one since the fit)
     bool plain = h->cfg.similarity == KNNCF_SIM_ONE || new_kcap != nt.kcap || nt.k != h->cfg.k ||
                  n_changers > max_changers ||
+                 left > 0 ||  // (k_ap_remap: every old user is in the new fit)
                  // (the update queries refuse such a fit: the id sets change their iteration class below five members)
                  U < 5 || tr.I < 5 ||
-                 (h->cfg.similarity == KNNCF_SIM_COSINE && (short_newcomer || has_short_rows(h)));
+                 (h->cfg.similarity == KNNCF_SIM_COSINE && (short_changer || has_short_rows(h)));
     // ---- marking, on the old fit
     if (!plain && !no_lists) plain = !mark_stale_lists(h, g);
     // ---- the new Train beside the old one
     Train next;
-    next.n = tr.n + n;
+    next.n = kept_rows + n;
     next.jaccard = tr.jaccard;
     {
         Stage s(h, &h->tm.prep_ms);
         next.user_raw.alloc(next.n); next.item_raw.alloc(next.n); next.rating.alloc(next.n);
-        KN_HIP(hipMemcpyAsync(next.user_raw.p, tr.user_raw.p, tr.n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        KN_HIP(hipMemcpyAsync(next.item_raw.p, tr.item_raw.p, tr.n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        KN_HIP(hipMemcpyAsync(next.rating.p, tr.rating.p, tr.n * sizeof(double), hipMemcpyDeviceToDevice, st));
-        KN_HIP(hipMemcpyAsync(next.user_raw.p + tr.n, users, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        KN_HIP(hipMemcpyAsync(next.item_raw.p + tr.n, items, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        KN_HIP(hipMemcpyAsync(next.rating.p + tr.n, ratings, n * sizeof(double), hipMemcpyHostToDevice, st));
+        if (n_removed > 0) {
+            amend_compact(as, tr, next.user_raw.p, next.item_raw.p, next.rating.p, st);
+        } else {
+            KN_HIP(hipMemcpyAsync(next.user_raw.p, tr.user_raw.p, tr.n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+            KN_HIP(hipMemcpyAsync(next.item_raw.p, tr.item_raw.p, tr.n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+            KN_HIP(hipMemcpyAsync(next.rating.p, tr.rating.p, tr.n * sizeof(double), hipMemcpyDeviceToDevice, st));
+        }
+        if (n > 0) {
+            KN_HIP(hipMemcpyAsync(next.user_raw.p + kept_rows, users, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            KN_HIP(hipMemcpyAsync(next.item_raw.p + kept_rows, items, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            KN_HIP(hipMemcpyAsync(next.rating.p + kept_rows, ratings, n * sizeof(double), hipMemcpyHostToDevice, st));
+        }
         prep_fit(next, h->prep, h->cfg.shard_rank, h->cfg.shard_count, st);  // (throws a duplicate or a non-finite deviation)
         prep_commit(next, h->prep, st);
     }
-    KN_REQUIRE(next.U == U + joined, KNNCF_E_STATE, "append: the new fit's users are not the old ones and the newcomers");
+    KN_REQUIRE(next.U == U + joined - left, KNNCF_E_STATE, "append: the new fit's users are not the old ones, the newcomers and the leavers");
     // ---- K, B ∩ S, the dropped ids (old dense order = new set order: the map is monotone)
-    const bool tiny = U < 5 && next.U >= 5;  // (the user set changed its iteration class: the few ids are ordered on the host)
+    // (the user set changed its iteration class, upwards or — users left — downwards: every id is fetched and ordered on the host)
+    const bool tiny = (U < 5) != (next.U < 5);
     append_sets(as, tr, nt, plain, tiny ? U : dropped_cap, st);
     const bool moved = !plain && next.U != U;
     NeighborTable table;
@@ -2316,10 +2402,16 @@ void do_append(knncf_handle* h, const int32_t* users, const int32_t* items, cons
     if (!ids.empty()) {
         KN_HIP(hipMemcpyAsync(ids.data(), as.dropped.p, ids.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         KN_HIP(hipStreamSynchronize(st));
-        if (tiny) {
+        if (tiny && next.U >= 5) {
             std::sort(ids.begin(), ids.end(), [](int32_t a, int32_t b) { return int_trie_key(a) < int_trie_key(b); });
-            ids.resize((size_t)std::min<int64_t>((int64_t)ids.size(), dropped_cap));
+        } else if (tiny) {  // the new fit's few users in their order, then the users that left
+            std::vector<int32_t> order((size_t)next.U);
+            KN_HIP(hipMemcpyAsync(order.data(), next.uid.p, order.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            KN_HIP(hipStreamSynchronize(st));
+            auto place = [&](int32_t id) { return std::find(order.begin(), order.end(), id) - order.begin(); };
+            std::stable_sort(ids.begin(), ids.end(), [&](int32_t a, int32_t b) { return place(a) < place(b); });
         }
+        if (tiny) ids.resize((size_t)std::min<int64_t>((int64_t)ids.size(), dropped_cap));
         std::copy(ids.begin(), ids.end(), dropped);
     }
     // ---- the swap
@@ -2338,6 +2430,8 @@ void do_append(knncf_handle* h, const int32_t* users, const int32_t* items, cons
     *n_dropped = totals[1];
     KN_TRACE_DISPATCH("append changers=%lld built=%lld carried=%lld dropped=%lld moved=%d plain=%d", (long long)n_changers,
                       (long long)built, (long long)totals[0], (long long)totals[1], (int)moved, (int)plain);
+    if (n_removed > 0)
+        KN_TRACE_DISPATCH("amend removers=%lld removed=%lld kept_rows=%lld", (long long)removers, (long long)n_removed, (long long)kept_rows);
 }
 
 }  // namespace
@@ -3521,7 +3615,15 @@ int knncf_revise_entered_batch(knncf_handle* h, const int32_t* users, const int6
 
 int knncf_append(knncf_handle* h, const int32_t* users, const int32_t* items, const double* ratings, int64_t n, int64_t* n_carried,
                  int64_t* n_dropped, int32_t* dropped, int64_t dropped_cap) {
-    return guarded(h, [&] { do_append(h, users, items, ratings, n, n_carried, n_dropped, dropped, dropped_cap); });
+    return guarded(h, [&] { do_amend(h, nullptr, nullptr, 0, users, items, ratings, n, n_carried, n_dropped, dropped, dropped_cap); });
+}
+
+int knncf_amend(knncf_handle* h, const int32_t* removed_users, const int32_t* removed_items, int64_t n_removed, const int32_t* users,
+                const int32_t* items, const double* ratings, int64_t n, int64_t* n_carried, int64_t* n_dropped, int32_t* dropped,
+                int64_t dropped_cap) {
+    return guarded(h, [&] {
+        do_amend(h, removed_users, removed_items, n_removed, users, items, ratings, n, n_carried, n_dropped, dropped, dropped_cap);
+    });
 }
 
 int knncf_neighbors_save(knncf_handle* h, const char* path) {

@@ -12,7 +12,9 @@
 //   k_ap_remap    old dense user -> new dense user: the lower bound of its trie key among the new fit's keys (monotone)
 //   k_ap_carry    the table moves (a user joined): one wave per kept row, ids through the map, similarities verbatim
 //   k_ap_clear    the table stays: the rows outside K lose their length and build number
-// Stores are vector stores and atomicOr on global memory.
+// knncf_amend (DESIGN.md "Amend") is the same call with removals: its changers run through REVISE chunks, and the k_am_* kernels
+// below take the removed rows out of the file-order arrays that the new fit is built from.
+// Stores are vector stores, atomicOr and atomicAdd on global memory.
 #include <algorithm>
 
 #include "engine.h"
@@ -149,13 +151,159 @@ __global__ void __launch_bounds__(TPB) k_ap_carry(int32_t U, int32_t kcap, const
     }
 }
 
+// ---- knncf_amend: the removed rows leave the file order (DESIGN.md "Amend") -----------------------------------------------------
+// The removals are one table of keys (raw user as uint32) << 32 | (raw item as uint32), ascending, with a CSR over its distinct
+// users (removers [R] ascending, roff [R + 1]).  The train rows go in tiles of AM_TILE file rows, one workgroup each:
+//   k_am_flag     every row looks its (user, item) up: the removed-row bitmap, one hit per found removal, the tile's survivors
+//   k_am_offsets  one workgroup: the exclusive scan of the tiles' survivors, and "every removal was hit exactly once"
+//   k_am_compact  the surviving rows of the three file-order arrays to tile offset + rank within the tile: stable, no atomics
+static constexpr int AM_TILE = KNNCF_AMEND_TILE;
+static constexpr int AM_WORDS = AM_TILE / 64;  // bitmap words of a tile
+static_assert(AM_TILE % TPB == 0 && AM_WORDS <= 64, "a tile is whole passes of the workgroup, and one wave scans its words");
+
+// the place of (user, item) in the table, or -1: the user among the removers first, where almost every row ends
+__device__ __forceinline__ int64_t am_find(uint32_t user, uint32_t item, int32_t R, const uint32_t* __restrict__ removers,
+                                           const int64_t* __restrict__ roff, const uint64_t* __restrict__ keys) {
+    int32_t lo = 0, hi = R;
+    while (lo < hi) {
+        const int32_t mid = (lo + hi) >> 1;
+        if (removers[mid] < user) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo >= R || removers[lo] != user) return -1;
+    const uint64_t key = ((uint64_t)user << 32) | item;
+    int64_t a = roff[lo];
+    const int64_t end = roff[lo + 1];
+    int64_t b = end;
+    while (a < b) {
+        const int64_t mid = (a + b) >> 1;
+        if (keys[mid] < key) a = mid + 1;
+        else b = mid;
+    }
+    return (a < end && keys[a] == key) ? a : -1;
+}
+
+// One workgroup per tile, AM_TILE / TPB passes; a wave's ballot of the hits is word i / 64 of the removed-row bitmap.
+// Bounds.  Row i < n reads user_raw[i], item_raw[i]; am_find stays inside removers [R], roff [R + 1] and keys [roff[R]], so a
+// hit's cell of hits is < roff[R] = the removals; lane 0 writes word i / 64 only with i < n, which is < ceil(n / 64); cell
+// blockIdx.x < the tiles = ceil(n / AM_TILE).
+__global__ void __launch_bounds__(TPB) k_am_flag(int64_t n, int32_t R, const uint32_t* __restrict__ removers,
+                                                 const int64_t* __restrict__ roff, const uint64_t* __restrict__ keys,
+                                                 const int32_t* __restrict__ user_raw, const int32_t* __restrict__ item_raw,
+                                                 int32_t* __restrict__ hits, unsigned long long* __restrict__ bits,
+                                                 int32_t* __restrict__ tile_cnt) {
+    __shared__ int32_t part[TPB / 64];
+    const int64_t base = (int64_t)blockIdx.x * AM_TILE;
+    int32_t mine = 0;  // the survivors of this wave's rows (the same in every lane)
+    for (int it = 0; it < AM_TILE / TPB; ++it) {
+        const int64_t i = base + it * TPB + threadIdx.x;
+        bool hit = false;
+        if (i < n) {
+            const int64_t at = am_find((uint32_t)user_raw[i], (uint32_t)item_raw[i], R, removers, roff, keys);
+            if (at >= 0) {
+                hit = true;
+                atomicAdd(&hits[at], 1);
+            }
+        }
+        const unsigned long long word = __ballot(hit), live = __ballot(i < n);
+        if ((threadIdx.x & 63) == 0 && i < n) bits[i >> 6] = word;
+        mine += __popcll(live & ~word);
+    }
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int32_t c = 0;
+        for (int w = 0; w < TPB / 64; ++w) c += part[w];
+        tile_cnt[blockIdx.x] = c;
+    }
+}
+
+// One workgroup.  tile_off [tiles + 1] = the exclusive scan of tile_cnt; verdict[0] = the surviving rows, verdict[1] = the first
+// cell of hits that is not 1 (a removal that is no train row), or -1.
+// Bounds.  tile_cnt holds `tiles` cells and tile_off tiles + 1 (block_exclusive_scan writes cell `tiles`); j < n_removed.
+__global__ void __launch_bounds__(ONE_BLOCK) k_am_offsets(int64_t tiles, const int32_t* __restrict__ tile_cnt,
+                                                          int64_t* __restrict__ tile_off, int64_t n_removed,
+                                                          const int32_t* __restrict__ hits, int64_t* __restrict__ verdict) {
+    __shared__ unsigned long long first;
+    if (threadIdx.x == 0) first = ~0ull;
+    const int64_t total = block_exclusive_scan(tiles, [&](int64_t t) { return (int64_t)tile_cnt[t]; }, tile_off);
+    __syncthreads();
+    for (int64_t j = threadIdx.x; j < n_removed; j += ONE_BLOCK)
+        if (hits[j] != 1) atomicMin(&first, (unsigned long long)j);  // (an LDS cell)
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        verdict[0] = total;
+        verdict[1] = first == ~0ull ? -1 : (int64_t)first;
+    }
+}
+
+// One workgroup per tile.  Wave 0 scans the survivors of the tile's AM_WORDS bitmap words into LDS; the rank of a surviving row
+// within the tile is its word's prefix plus the survivors below its lane.  File order is kept: tile offsets, word prefixes and
+// lanes all ascend with the row.
+// Bounds.  Words w < ceil(n / 64) are read; row i < n reads the three arrays; its place is tile_off[tile] + rank < tile_off[tiles]
+// = the surviving rows (k_am_flag counted the same bitmap), and the three outputs hold at least that many cells.
+__global__ void __launch_bounds__(TPB) k_am_compact(int64_t n, const unsigned long long* __restrict__ bits,
+                                                    const int64_t* __restrict__ tile_off, const int32_t* __restrict__ user_raw,
+                                                    const int32_t* __restrict__ item_raw, const double* __restrict__ rating,
+                                                    int32_t* __restrict__ out_user, int32_t* __restrict__ out_item,
+                                                    double* __restrict__ out_rating) {
+    __shared__ int32_t wpre[AM_WORDS];
+    const int64_t base = (int64_t)blockIdx.x * AM_TILE, Wn = (n + 63) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (threadIdx.x < 64) {  // (a whole wave: the scan runs over all 64 lanes)
+        const int64_t w = (base >> 6) + lane;
+        uint32_t c = 0;
+        if (lane < AM_WORDS && w < Wn) {
+            const int64_t rows = std::min<int64_t>(64, n - w * 64);
+            const unsigned long long valid = rows == 64 ? ~0ull : (1ull << rows) - 1ull;
+            c = (uint32_t)__popcll(~bits[w] & valid);
+        }
+        const uint32_t upto = wave_incl_scan(c);
+        if (lane < AM_WORDS) wpre[lane] = (int32_t)(upto - c);
+    }
+    __syncthreads();
+    const int64_t off = tile_off[blockIdx.x];
+    for (int it = 0; it < AM_TILE / TPB; ++it) {
+        const int64_t i = base + it * TPB + threadIdx.x;
+        if (i >= n) break;
+        const unsigned long long word = bits[i >> 6];
+        if ((word >> lane) & 1ull) continue;
+        const int64_t to = off + wpre[(i - base) >> 6] + __popcll(~word & ((1ull << lane) - 1ull));
+        out_user[to] = user_raw[i];
+        out_item[to] = item_raw[i];
+        out_rating[to] = rating[i];
+    }
+}
+
 static inline unsigned blocks_for(int64_t n, int per = TPB) { return (unsigned)std::max<int64_t>(1, ceil_div(n, per)); }
+
+void amend_flag(AppendScratch& as, const Train& tr, const uint64_t* h_keys, int64_t n_removed, const uint32_t* h_removers,
+                const int64_t* h_roff, int32_t R, hipStream_t st) {
+    const int64_t tiles = ceil_div(tr.n, AM_TILE);
+    as.am_keys.ensure(n_removed); as.am_hits.ensure(n_removed);
+    as.am_removers.ensure(R); as.am_roff.ensure((size_t)R + 1);
+    as.am_bits.ensure(ceil_div(tr.n, 64)); as.am_tile_cnt.ensure(tiles); as.am_tile_off.ensure((size_t)tiles + 1);
+    KN_HIP(hipMemcpyAsync(as.am_keys.p, h_keys, (size_t)n_removed * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    KN_HIP(hipMemcpyAsync(as.am_removers.p, h_removers, (size_t)R * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    KN_HIP(hipMemcpyAsync(as.am_roff.p, h_roff, ((size_t)R + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    KN_HIP(hipMemsetAsync(as.am_hits.p, 0, (size_t)n_removed * sizeof(int32_t), st));
+    k_am_flag<<<(unsigned)tiles, TPB, 0, st>>>(tr.n, R, as.am_removers.p, as.am_roff.p, as.am_keys.p, tr.user_raw.p, tr.item_raw.p,
+                                               as.am_hits.p, as.am_bits.p, as.am_tile_cnt.p);
+    k_am_offsets<<<1, ONE_BLOCK, 0, st>>>(tiles, as.am_tile_cnt.p, as.am_tile_off.p, n_removed, as.am_hits.p, as.totals.p + 2);
+    KN_HIP(hipGetLastError());
+}
+
+void amend_compact(AppendScratch& as, const Train& tr, int32_t* d_user, int32_t* d_item, double* d_rating, hipStream_t st) {
+    k_am_compact<<<(unsigned)ceil_div(tr.n, AM_TILE), TPB, 0, st>>>(tr.n, as.am_bits.p, as.am_tile_off.p, tr.user_raw.p, tr.item_raw.p,
+                                                                    tr.rating.p, d_user, d_item, d_rating);
+    KN_HIP(hipGetLastError());
+}
 
 void append_begin(AppendScratch& as, int32_t U, hipStream_t st) {
     const int64_t Wu = ceil_div(U, 64);
     as.stale.ensure(Wu); as.kept.ensure(Wu); as.gone.ensure(Wu);
     as.pre.ensure((size_t)std::max<int64_t>(U, Wu) + 1);
-    as.totals.ensure(2);
+    as.totals.ensure(4);  // (|K|, |B ∩ S|; the removal stage's verdict)
     KN_HIP(hipMemsetAsync(as.stale.p, 0, (size_t)Wu * sizeof(unsigned long long), st));
 }
 

@@ -213,7 +213,7 @@ inline bool lds_bitmap_fits(int64_t words) { return words * 12 <= 48 * 1024 && !
 // (the id path, per-user LDS sorts or global radix sorts, the lengths of the two segment lists of k_classify_rows — read
 // back from the status words under the hook only — and which fold orders were built), and radix_sort one line per sort,
 //   "sort key=<32|64> n=<n> tiles=<t> passes=<p> scan=<self|kernel>".)
-// (KNNCF_DEBUG_APPEND_MAX_CHANGERS: measurement hook of knncf_append — api.cpp: do_append reads it at every call in place of
+// (KNNCF_DEBUG_APPEND_MAX_CHANGERS: measurement hook of knncf_append — api.cpp: do_amend reads it at every call in place of
 // KNNCF_APPEND_MAX_CHANGERS; 0 makes every append a plain refit.  include/knncf.h "Append".)
 inline bool trace_setup_stage() {
     const char* v = getenv("KNNCF_DEBUG_TRACE_DISPATCH");

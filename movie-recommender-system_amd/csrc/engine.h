@@ -560,7 +560,16 @@ struct AppendScratch {
     DArr<uint32_t> k_a, k_b, v_a, v_b;  // [U] the users by ascending raw id (keys: the raw id with its sign bit flipped)
     DArr<int32_t> map;               // [U] old dense user -> new dense user
     DArr<int32_t> dropped;           // [min(cap, U)] raw ids of B ∩ S in dense order
-    DArr<int64_t> totals;            // [2] |K|, |B ∩ S|
+    DArr<int64_t> totals;            // [4] |K|, |B ∩ S|; the removal stage's verdict: the surviving rows, the first missed removal or -1
+    // knncf_amend's removal stage: the table of removals and, over the old fit's n file rows in tiles of KNNCF_AMEND_TILE, the
+    // removed-row bitmap with the tiles' survivor counts and offsets
+    DArr<uint64_t> am_keys;          // [n_removed] (user << 32 | item, both as uint32), ascending
+    DArr<uint32_t> am_removers;      // [R] the distinct users of the removals, ascending as uint32
+    DArr<int64_t> am_roff;           // [R + 1] remover r's keys are am_keys [am_roff[r], am_roff[r + 1])
+    DArr<int32_t> am_hits;           // [n_removed] train rows that matched each removal
+    DArr<unsigned long long> am_bits;  // [ceil(n / 64)] bit i: file row i is removed
+    DArr<int32_t> am_tile_cnt;       // [tiles]
+    DArr<int64_t> am_tile_off;       // [tiles + 1]
 };
 // stale = 0
 void append_begin(AppendScratch& as, int32_t U, hipStream_t st);
@@ -579,6 +588,15 @@ void append_clear(AppendScratch& as, int32_t U, int32_t* d_cnt, int64_t* d_seq, 
 // the table moves: row map[v] of `to` (cleared beforehand: cnt 0, seq -1) = row v of `from` for v in K, ids through the map,
 // similarities verbatim; both tables have from.kcap cells per row
 void append_carry(AppendScratch& as, int32_t U, const NeighborTable& from, NeighborTable& to, hipStream_t st);
+// knncf_amend's removal stage, after append_begin.  The table as the host sorted it (h_keys [n_removed] ascending and distinct,
+// n_removed > 0; h_removers [R] and h_roff [R + 1] its CSR by user): the removed-row bitmap of tr's file rows, the tile offsets
+// and the verdict in as.totals[2..3] — [2] = the surviving rows, [3] = the first cell of the table that did not match exactly
+// one train row, or -1.  Two launches; the host arrays must live until the stream has passed the copies.
+void amend_flag(AppendScratch& as, const Train& tr, const uint64_t* h_keys, int64_t n_removed, const uint32_t* h_removers,
+                const int64_t* h_roff, int32_t R, hipStream_t st);
+// after amend_flag: tr's surviving file rows, in file order, to the front of the three arrays (as.totals[2] cells each); tr's
+// own arrays are only read.  No atomics.
+void amend_compact(AppendScratch& as, const Train& tr, int32_t* d_user, int32_t* d_item, double* d_rating, hipStream_t st);
 
 // ---- reco_batch.hip: recommendations :651-674 for users of the fit (knncf_recommend, knncf_recommend_batch; DESIGN.md "Batched
 // recommendations") ----

@@ -23,6 +23,7 @@ FLAG_F32_PANEL = 8    # default similarity panel storage is fp16
 HEAD_ALL = 0xFFFFFFFF
 EXPLAIN_SUM_ORDER, EXPLAIN_BY_WEIGHT = 0, 1  # KNNCF_EXPLAIN_*: the order of the terms of Engine.explain*
 APPEND_MAX_CHANGERS = 128  # KNNCF_APPEND_MAX_CHANGERS: Appends.append with more distinct users carries no list (a plain refit)
+AMEND_TILE = 2048  # KNNCF_AMEND_TILE: the train rows that one workgroup of knncf_amend's removal stage takes
 
 _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
@@ -141,7 +142,7 @@ EXPORTS = [
     "knncf_revise_bystander_neighbors_batch", "knncf_revise_bystander_predict_batch",
     "knncf_query_entered", "knncf_query_entered_batch",
     "knncf_update_entered", "knncf_update_entered_batch", "knncf_revise_entered", "knncf_revise_entered_batch",
-    "knncf_append",
+    "knncf_append", "knncf_amend",
     "knncf_predict_batch",
     "knncf_predict_batch_device", "knncf_mae", "knncf_mae_device", "knncf_mae_sweep", "knncf_mae_sweep_device", "knncf_shard_view_get",
     "knncf_shard_commit", "knncf_get_timings", "knncf_reset_timings", "knncf_reset_neighbors",
@@ -283,6 +284,10 @@ def load_library():
                                              L.knncf_update_entered_batch.argtypes[2:])
     # append: the rows, then |K|, |B ∩ S| and the dropped raw ids with their cap
     L.knncf_append.argtypes = [C.c_void_p, _i32p, _i32p, _f64p, C.c_int64, _i64p, _i64p, _i32p, C.c_int64]
+    # amend: the removals (users, items, their number) in front of knncf_append's arguments.  The C call only: a method of Appends
+    # needs its model in tests/call_sequences.py first (test_call_sequence_premises.py: every public method of a wrapper class
+    # has a call kind), which is the step after this one
+    L.knncf_amend.argtypes = [C.c_void_p, _i32p, _i32p, C.c_int64] + L.knncf_append.argtypes[1:]
     # revise queries: the update argument lists with the removals in front of the additional rows
     for name, at, single in (("neighbors", 2, True), ("predict", 3, True), ("recommend", 3, True), ("explain", 3, True),
                              ("explain_personalized", 2, True), ("neighbors_batch", 2, False), ("predict_batch", 3, False),

@@ -1,0 +1,197 @@
+"""Latency of knncf_amend (csrc/append.hip) at the ml-25m shape: removed ratings leave the fit, re-rated ones move behind every
+train row, and the kNN lists the change cannot touch are kept — against the refit it replaces.  append_latency.py for removals.
+The call goes through the C ABI: the binding has no method for it yet.
+
+Fits syn-25m once (k = 300) and builds every list.  A step amends the fit for C changers — users of the fit with 15 .. 400 train
+ratings that each remove 1 .. 5 and re-rate 1 .. 5 others of their last ten train ratings (another half-star value), every changer used once
+— and then runs mae(PRED_KNN) over the test set, which rebuilds the lists the amend dropped; every list is built again before the
+next step (the fit changes from step to step).  Timed per step, wall time with the profiler off:
+  * amend: knncf_amend alone, with the lists it carried and dropped and the prep_ms it charged (the removal stage included);
+  * amend + mae;
+  * plain: the same amend under KNNCF_DEBUG_APPEND_MAX_CHANGERS=0 (nothing carried) + mae, on a second engine that holds the
+    same fit: the path knncf_amend itself takes beyond KNNCF_APPEND_MAX_CHANGERS;
+  * refit: that second engine's fit(aug) + the same mae call, aug = what the first engine now holds — same process, same job.
+C = 1, 8, 64 and APPEND_MAX_CHANGERS are the rows (--reps steps each, medians, with the [min, max] of the sums).  With
+--sweep-max above 64 a sweep then takes C upward in powers of two with the limit lifted (--sweep-reps steps each) until amend + mae
+is no cheaper than plain + mae: the crossover with removers, to hold against append_latency.py's with adders.  Prints one JSON line.
+
+    python scripts/amend_latency.py [--reps 5] [--sweep-reps 2] [--sweep-max 0] [--out bench_out/amend]
+
+The GPU work runs in a child process under `timeout -k 10`."""
+import argparse
+import importlib
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+PKG = "movie-recommender-system_amd"
+LIMIT = "KNNCF_DEBUG_APPEND_MAX_CHANGERS"
+
+
+class Pool:
+    """changers of the fit, each used once, with their last train rows in file order"""
+
+    def __init__(self, train, seed):
+        import numpy as np
+
+        self.np = np
+        u, i, r = train
+        order = np.argsort(u, kind="stable")
+        users, start, counts = np.unique(u[order], return_index=True, return_counts=True)
+        self.last = {int(c): (i[order[s + n - 10:s + n]], r[order[s + n - 10:s + n]]) for c, s, n in zip(users, start, counts) if 15 <= n <= 400}
+        self.rng = np.random.default_rng(seed)
+        self.fitted = self.rng.permutation(np.asarray(sorted(self.last), dtype=np.int64)).tolist()
+
+    def take(self, n_fitted):
+        """(removed users, removed items, users, items, ratings) of one amend: per changer 1 .. 5 of its last ten train rows
+        removed and 1 .. 5 others of them re-rated, the removals and the rows of several users interleaved"""
+        np, rng = self.np, self.rng
+        ru, ri, u, it, rt = [], [], [], [], []
+        for _ in range(n_fitted):
+            c = self.fitted.pop()
+            items, vals = self.last[c]
+            n_rm, n_re = int(rng.integers(1, 6)), int(rng.integers(1, 6))
+            pick = rng.permutation(10)[:n_rm + n_re]
+            ru += [c] * (n_rm + n_re); ri += items[pick].tolist()
+            u += [c] * n_re; it += items[pick[n_rm:]].tolist()
+            rt += [float(v - 2 if v >= 3 else v + 2) for v in vals[pick[n_rm:]]]
+        a, b = rng.permutation(len(ru)), rng.permutation(len(u))
+        return (np.asarray(ru, dtype=np.int32)[a], np.asarray(ri, dtype=np.int32)[a], np.asarray(u, dtype=np.int32)[b],
+                np.asarray(it, dtype=np.int32)[b], np.asarray(rt, dtype=np.float64)[b])
+
+
+def aug_of(np, train, call):
+    """train in file order without the removed rows ++ the rows"""
+    ru, ri, u, it, rt = call
+    key = lambda a, b: (a.astype(np.int64) << 32) | (b.astype(np.int64) & 0xFFFFFFFF)
+    keep = ~np.isin(key(train[0], train[1]), key(ru, ri))
+    assert int((~keep).sum()) == len(ru)
+    return [np.concatenate([train[0][keep], u]), np.concatenate([train[1][keep], it]), np.concatenate([train[2][keep], rt])]
+
+
+def amend(e, removed_users, removed_items, users, items, ratings):
+    """knncf_amend on Engine e: (carried, dropped)"""
+    import ctypes as C
+
+    i32p, f64p = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+    carried, gone = C.c_int64(), C.c_int64()
+    p = e._ptr
+    e._check(e._lib.knncf_amend(e._h, p(removed_users, i32p), p(removed_items, i32p), len(removed_users), p(users, i32p), p(items, i32p),
+                                p(ratings, f64p), len(users), C.byref(carried), C.byref(gone), None, 0))
+    return carried.value, gone.value
+
+
+def _ms(call):
+    t0 = time.perf_counter()
+    out = call()
+    return (time.perf_counter() - t0) * 1e3, out
+
+
+def _median(xs):
+    xs = sorted(xs)
+    return xs[len(xs) // 2] if len(xs) % 2 else 0.5 * (xs[len(xs) // 2 - 1] + xs[len(xs) // 2])
+
+
+def inner(args):
+    """runs on the GPU"""
+    import numpy as np
+
+    kn = importlib.import_module(PKG + ".knncf")
+    synth = importlib.import_module(PKG + ".synth")
+    d = synth.syn_25m()
+    train = [d.train.users, d.train.items, d.train.ratings]
+    test = (d.test.users, d.test.items, d.test.ratings)
+    pool = Pool(train, seed=29)
+    e, other = kn.Engine(k=300), kn.Engine(k=300)
+    first_user = int(train[0][0])
+    build_all = lambda eng: kn.EnteredQueries(eng).entered_with(first_user, [], [], cap=0)  # (builds every missing list)
+    for eng in (e, other):
+        eng.fit(*train)
+        eng.mae(kn.PRED_KNN, *test)
+        build_all(eng)
+    res = {"k": 300, "U": e.num_users, "I": e.num_items, "train_ratings": len(train[0]), "test_ratings": len(test[0]),
+           "max_changers": kn.APPEND_MAX_CHANGERS, "tile": kn.AMEND_TILE}
+
+    def step(n_fitted, lifted):
+        nonlocal train
+        call = pool.take(n_fitted)
+        if lifted:
+            os.environ[LIMIT] = str(1 << 30)
+        before = e.timings()["prep_ms"]
+        t_amend, (carried, dropped) = _ms(lambda: amend(e, *call))
+        prep = e.timings()["prep_ms"] - before
+        os.environ.pop(LIMIT, None)
+        t_mae, mae = _ms(lambda: e.mae(kn.PRED_KNN, *test))
+        os.environ[LIMIT] = "0"
+        t_plain, (c0, _) = _ms(lambda: amend(other, *call))
+        os.environ.pop(LIMIT, None)
+        t_plain_mae, mae_plain = _ms(lambda: other.mae(kn.PRED_KNN, *test))
+        train = aug_of(np, train, call)
+        t_fit, _ = _ms(lambda: other.fit(*train))
+        t_fit_mae, mae_refit = _ms(lambda: other.mae(kn.PRED_KNN, *test))
+        assert c0 == 0 and mae == mae_plain == mae_refit, (mae, mae_plain, mae_refit)
+        build_all(e)
+        return {"removed": len(call[0]), "rows": len(call[2]), "carried": carried, "dropped": dropped, "amend_ms": t_amend,
+                "amend_prep_ms": prep, "mae_after_amend_ms": t_mae, "amend_plus_mae_ms": t_amend + t_mae, "plain_amend_ms": t_plain,
+                "plain_plus_mae_ms": t_plain + t_plain_mae, "refit_ms": t_fit, "refit_plus_mae_ms": t_fit + t_fit_mae, "mae": mae}
+
+    def row(n_fitted, reps, lifted=False):
+        steps = [step(n_fitted, lifted) for _ in range(reps)]
+        out = {k: _median([s[k] for s in steps]) for k in steps[0]}
+        out["spread"] = {k: [min(s[k] for s in steps), max(s[k] for s in steps)]
+                         for k in ("amend_ms", "amend_plus_mae_ms", "plain_plus_mae_ms", "refit_plus_mae_ms")}
+        out["dropped_per_step"] = [s["dropped"] for s in steps]
+        out.update({"changers": n_fitted, "steps": reps})
+        return out
+
+    step(1, False)  # warm-up: every launch shape and scratch size
+    res["headline"] = [row(c, args.reps) for c in (1, 8, 64, kn.APPEND_MAX_CHANGERS)]
+    sweep, c = [], 64
+    while c <= args.sweep_max and len(pool.fitted) >= c * args.sweep_reps:
+        sweep.append(row(c, args.sweep_reps, lifted=True))
+        if sweep[-1]["amend_plus_mae_ms"] >= sweep[-1]["plain_plus_mae_ms"]:
+            break
+        c *= 2
+    res["sweep"] = sweep
+    gain = [s["plain_plus_mae_ms"] - s["amend_plus_mae_ms"] for s in sweep]
+    if len(sweep) > 1 and gain[-1] <= 0:
+        a, b = sweep[-2]["changers"], sweep[-1]["changers"]
+        res["crossover_changers"] = a + (b - a) * gain[-2] / (gain[-2] - gain[-1])
+    else:
+        res["crossover_changers"] = None  # (no sweep, not reached below --sweep-max, or already behind at the first C)
+    for eng in (e, other):
+        eng.close()
+    print(json.dumps(res), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--sweep-reps", type=int, default=2)
+    ap.add_argument("--sweep-max", type=int, default=0)
+    ap.add_argument("--timeout", type=int, default=900)
+    ap.add_argument("--out", default=os.path.join(ROOT, "bench_out", "amend"))
+    ap.add_argument("--inner", action="store_true", help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.inner:
+        return inner(args)
+    os.makedirs(args.out, exist_ok=True)
+    cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--inner", "--reps", str(args.reps),
+           "--sweep-reps", str(args.sweep_reps), "--sweep-max", str(args.sweep_max)]
+    log = os.path.join(args.out, "timing.log")
+    with open(log, "w") as f:
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=f, text=True, cwd=ROOT)
+    if r.returncode != 0:
+        raise SystemExit(f"the timed run failed with status {r.returncode} (log: {log})")
+    res = json.loads(r.stdout.strip().splitlines()[-1])
+    with open(os.path.join(args.out, "amend_latency.json"), "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
