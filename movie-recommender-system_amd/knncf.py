@@ -284,9 +284,7 @@ def load_library():
                                              L.knncf_update_entered_batch.argtypes[2:])
     # append: the rows, then |K|, |B ∩ S| and the dropped raw ids with their cap
     L.knncf_append.argtypes = [C.c_void_p, _i32p, _i32p, _f64p, C.c_int64, _i64p, _i64p, _i32p, C.c_int64]
-    # amend: the removals (users, items, their number) in front of knncf_append's arguments.  The C call only: a method of Appends
-    # needs its model in tests/call_sequences.py first (test_call_sequence_premises.py: every public method of a wrapper class
-    # has a call kind), which is the step after this one
+    # amend: the removals (users, items, their number) in front of knncf_append's arguments
     L.knncf_amend.argtypes = [C.c_void_p, _i32p, _i32p, C.c_int64] + L.knncf_append.argtypes[1:]
     # revise queries: the update argument lists with the removals in front of the additional rows
     for name, at, single in (("neighbors", 2, True), ("predict", 3, True), ("recommend", 3, True), ("explain", 3, True),
@@ -1328,38 +1326,65 @@ class BystanderQueries:
 
 
 class Appends:
-    """knncf_append on a fitted Engine: new ratings go INTO the fit.  NOT read-only on the engine's handle: the fit becomes
-    train ++ the rows, the neighbour lists the rows cannot change are kept and the other ones dropped.
+    """knncf_append and knncf_amend on a fitted Engine: new ratings go INTO the fit, and train rows come OUT of it.  NOT read-only
+    on the engine's handle: the fit becomes train (without the removed rows) ++ the rows, the neighbour lists the call cannot
+    change are kept and the other ones dropped.
 
-        carried, dropped = Appends(engine).append(users, items, ratings)"""
+        carried, dropped = Appends(engine).append(users, items, ratings)
+        carried, dropped = Appends(engine).amend(removed_users, removed_items, users, items, ratings)"""
 
     def __init__(self, engine):
         self._e = engine
+
+    @staticmethod
+    def _ids(pair, what):
+        """validated 32-bit ids of two 1-D arrays of one length: ValueError before any C call"""
+        for a in pair:
+            if a.ndim != 1 or len(a) != len(pair[0]):
+                raise ValueError(f"{what} must be 1-D arrays of one length")
+            if len(a) and (a.dtype.kind not in "iu" or a.min() < -2**31 or a.max() >= 2**31):
+                raise ValueError(f"{what} must be 32-bit integer ids")
+        return tuple(_i32(a) if len(a) else np.empty(0, dtype=np.int32) for a in pair)
+
+    def _rows(self, users, items, ratings):
+        u, i, r = np.asarray(users), np.asarray(items), np.asarray(ratings)
+        if not (u.ndim == i.ndim == r.ndim == 1 and len(u) == len(i) == len(r)):
+            raise ValueError("users, items and ratings must be 1-D arrays of one length")
+        u, i = self._ids((u, i), "users and items")
+        if len(r) and r.dtype.kind not in "iuf":
+            raise ValueError("ratings must be numbers")
+        return u, i, _f64(r) if len(r) else np.empty(0, dtype=np.float64)
+
+    def _call(self, fn, front, rows, return_dropped):
+        e = self._e
+        u, i, r = rows
+        carried, gone = C.c_int64(), C.c_int64()
+        cap = e.num_users if return_dropped else 0  # (B ∩ S are users of the fit as it stands)
+        ids = np.empty(max(1, cap), dtype=np.int32)
+        p = e._ptr
+        e._check(fn(e._h, *front, p(u, _i32p), p(i, _i32p), p(r, _f64p), len(u), C.byref(carried), C.byref(gone),
+                    p(ids, _i32p) if cap else None, cap))
+        if return_dropped:
+            return carried.value, gone.value, ids[:gone.value].copy()
+        return carried.value, gone.value
 
     def append(self, users, items, ratings, return_dropped=False):
         """knncf_append: the rows become part of the fit, and the neighbour lists they cannot change are kept.  Every later
         answer is that of fit(train ++ rows).  Returns (carried, dropped_count): the built lists that were kept, and those of the
         changers and of the users whose list holds a changer before or after, which the next call rebuilds; with return_dropped
         also their raw ids in the new fit's set order (int32 [dropped_count])."""
-        e = self._e
-        u, i, r = np.asarray(users), np.asarray(items), np.asarray(ratings)
-        if not (u.ndim == i.ndim == r.ndim == 1 and len(u) == len(i) == len(r)):
-            raise ValueError("users, items and ratings must be 1-D arrays of one length")
-        for a in (u, i):
-            if len(a) and (a.dtype.kind not in "iu" or a.min() < -2**31 or a.max() >= 2**31):
-                raise ValueError("users and items must be 32-bit integer ids")
-        if len(r) and r.dtype.kind not in "iuf":
-            raise ValueError("ratings must be numbers")
-        u, i, r = _i32(u), _i32(i), _f64(r)
-        carried, gone = C.c_int64(), C.c_int64()
-        cap = e.num_users if return_dropped else 0  # (B ∩ S are users of the fit as it stands)
-        ids = np.empty(max(1, cap), dtype=np.int32)
-        p = e._ptr
-        e._check(e._lib.knncf_append(e._h, p(u, _i32p), p(i, _i32p), p(r, _f64p), len(u), C.byref(carried), C.byref(gone),
-                                           p(ids, _i32p) if cap else None, cap))
-        if return_dropped:
-            return carried.value, gone.value, ids[:gone.value].copy()
-        return carried.value, gone.value
+        rows = self._rows(users, items, ratings)
+        return self._call(self._e._lib.knncf_append, (), rows, return_dropped)
+
+    def amend(self, removed_users, removed_items, users, items, ratings, return_dropped=False):
+        """knncf_amend: the train rows (removed_users[j], removed_items[j]) leave the fit and the rows join it, in one call; an
+        item both removed and given again is re-rated.  Every later answer is that of fit(train without the removed rows ++ rows).
+        Both parts may be empty.  Returns what append returns: (carried, dropped_count[, the dropped raw ids]), a user that left
+        the fit standing among the dropped ids where its id would stand."""
+        ru, ri = self._ids((np.asarray(removed_users), np.asarray(removed_items)), "removed_users and removed_items")
+        rows = self._rows(users, items, ratings)
+        p = self._e._ptr
+        return self._call(self._e._lib.knncf_amend, (p(ru, _i32p), p(ri, _i32p), len(ru)), rows, return_dropped)
 
 
 class EnteredQueries:

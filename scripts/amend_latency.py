@@ -1,6 +1,5 @@
 """Latency of knncf_amend (csrc/append.hip) at the ml-25m shape: removed ratings leave the fit, re-rated ones move behind every
 train row, and the kNN lists the change cannot touch are kept — against the refit it replaces.  append_latency.py for removals.
-The call goes through the C ABI: the binding has no method for it yet.
 
 Fits syn-25m once (k = 300) and builds every list.  A step amends the fit for C changers — users of the fit with 15 .. 400 train
 ratings that each remove 1 .. 5 and re-rate 1 .. 5 others of their last ten train ratings (another half-star value), every changer used once
@@ -73,16 +72,9 @@ def aug_of(np, train, call):
     return [np.concatenate([train[0][keep], u]), np.concatenate([train[1][keep], it]), np.concatenate([train[2][keep], rt])]
 
 
-def amend(e, removed_users, removed_items, users, items, ratings):
+def amend(kn, e, removed_users, removed_items, users, items, ratings):
     """knncf_amend on Engine e: (carried, dropped)"""
-    import ctypes as C
-
-    i32p, f64p = C.POINTER(C.c_int32), C.POINTER(C.c_double)
-    carried, gone = C.c_int64(), C.c_int64()
-    p = e._ptr
-    e._check(e._lib.knncf_amend(e._h, p(removed_users, i32p), p(removed_items, i32p), len(removed_users), p(users, i32p), p(items, i32p),
-                                p(ratings, f64p), len(users), C.byref(carried), C.byref(gone), None, 0))
-    return carried.value, gone.value
+    return kn.Appends(e).amend(removed_users, removed_items, users, items, ratings)
 
 
 def _ms(call):
@@ -122,12 +114,12 @@ def inner(args):
         if lifted:
             os.environ[LIMIT] = str(1 << 30)
         before = e.timings()["prep_ms"]
-        t_amend, (carried, dropped) = _ms(lambda: amend(e, *call))
+        t_amend, (carried, dropped) = _ms(lambda: amend(kn, e, *call))
         prep = e.timings()["prep_ms"] - before
         os.environ.pop(LIMIT, None)
         t_mae, mae = _ms(lambda: e.mae(kn.PRED_KNN, *test))
         os.environ[LIMIT] = "0"
-        t_plain, (c0, _) = _ms(lambda: amend(other, *call))
+        t_plain, (c0, _) = _ms(lambda: amend(kn, other, *call))
         os.environ.pop(LIMIT, None)
         t_plain_mae, mae_plain = _ms(lambda: other.mae(kn.PRED_KNN, *test))
         train = aug_of(np, train, call)

@@ -2,7 +2,9 @@
 scripts/fuzz_parity.py for tests/test_gpu_call_sequences.py.  Fresh seeds beyond the committed ones go through the same
 generator and model (tests/call_sequences.py): per seed an order-sensitive fit (40 users, 18 of them with <= 4 ratings), a
 similarity, a first k and cs.N_OPS ops over every kind of cs.KINDS — those of the classes beside Engine among them: appends
-(which replace the fit and keep lists), entered calls (which build every missing list) and bystander calls.  Stops at the first
+and amends (which replace the fit and keep lists; an amend also takes a user or an item out of it, and num_users / num_items
+are compared after each), entered calls (which build every missing list, with and without removals) and bystander calls of the
+three families.  Stops at the first
 mismatch or unexpected status and prints the seed and the op to replay; nothing is started after an error and nothing is tried
 twice.
 usage: python scripts/fuzz_sequences.py [first_seed] [count]"""
@@ -38,6 +40,11 @@ for seed in range(first, first + count):
         if not cs.same(got, want):
             print(f"MISMATCH seed {seed} (fit and sequence), {sim}, first k {case.k}, op {j}: {op!r}", flush=True)
             print(f"  engine {got!r}\n  model  {want!r}", flush=True)
+            print(f"fuzz sequences: {done} cases without a mismatch, stopped at seed {seed}", flush=True)
+            sys.exit(1)
+        if op.kind in cs.REFITS and (e.num_users, e.num_items) != (len(model.known_users), len(model.known_items)):
+            print(f"MISMATCH seed {seed} (fit and sequence), {sim}, first k {case.k}, op {j}: {op!r}", flush=True)
+            print(f"  engine users, items {(e.num_users, e.num_items)}\n  model  {(len(model.known_users), len(model.known_items))}", flush=True)
             print(f"fuzz sequences: {done} cases without a mismatch, stopped at seed {seed}", flush=True)
             sys.exit(1)
     e.close()

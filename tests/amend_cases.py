@@ -5,7 +5,7 @@ A case is an Amend: the train set, the removals (user, item) in the given order,
 may interleave), and the handle's k.  aug = train in file order without the removed rows ++ the rows: revise_cases.aug_of for
 several changers.  The builders are those of revise_entered_cases (one changer with removals) and append_cases (several
 changers, a newcomer, the fixed-size fits), put into one call."""
-import ctypes as C
+import sys
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -163,19 +163,10 @@ def crowd(synth, n_removers, k=5):
 
 # ---- the call --------------------------------------------------------------------------------------------------------------------
 def amend(e, removed_users, removed_items, users, items, ratings, return_dropped=False):
-    """knncf_amend on Engine e through the C ABI, with Appends.append's return shape: (carried, dropped_count[, the dropped raw
-    ids]); a refusal raises the binding's error.  (The binding has no method for the call yet: knncf.py says why.)"""
-    i32p, f64p = C.POINTER(C.c_int32), C.POINTER(C.c_double)
-    ru, ri, u, i = (np.ascontiguousarray(a, dtype=np.int32) for a in (removed_users, removed_items, users, items))
-    r = np.ascontiguousarray(ratings, dtype=np.float64)
-    assert len(ru) == len(ri) and len(u) == len(i) == len(r)
-    carried, gone = C.c_int64(), C.c_int64()
-    cap = e.num_users if return_dropped else 0  # (B ∩ S are users of the fit as it stands)
-    ids = np.empty(max(1, cap), dtype=np.int32)
-    p = e._ptr
-    e._check(e._lib.knncf_amend(e._h, p(ru, i32p), p(ri, i32p), len(ru), p(u, i32p), p(i, i32p), p(r, f64p), len(u), C.byref(carried),
-                                C.byref(gone), p(ids, i32p) if cap else None, cap))
-    return (carried.value, gone.value, ids[:gone.value].copy()) if return_dropped else (carried.value, gone.value)
+    """knncf_amend on Engine e through the binding's Appends.amend: (carried, dropped_count[, the dropped raw ids]); a refusal
+    raises the binding's error"""
+    kn = sys.modules[type(e).__module__]
+    return kn.Appends(e).amend(removed_users, removed_items, users, items, ratings, return_dropped=return_dropped)
 
 
 # ---- the oracle's side -----------------------------------------------------------------------------------------------------------

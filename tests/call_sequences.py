@@ -9,26 +9,30 @@ which the earlier calls built their neighbourhoods: the model plays that history
 
 A call kind is an Engine method with "_device" taken off; the thirty query methods ({neighbors, predict, recommend, explain,
 recommend_explain}_{for, with, revised}[_batch]) are the ten kinds *_q / *_q_batch, the family being an argument; the five
-statistic getters are the kind `statistics`.  The classes beside Engine that wrap one give the kinds `append` (Appends),
-entered / entered_batch / entered_with / entered_with_batch (EnteredQueries) and bystander_{neighbors, predict}[_batch]
-(BystanderQueries, the family "for" or "with" an argument).  kind_of() maps a method name, NOT_MODELLED names the methods left
-out.
+statistic getters are the kind `statistics`.  The classes beside Engine that wrap one give the kinds `append` and `amend`
+(Appends), entered / entered_batch / entered_with / entered_with_batch (EnteredQueries; a query of the last two with removals
+is played with removed=, knncf_revise_entered*) and bystander_{neighbors, predict}[_batch] (BystanderQueries, the family an
+argument: "for", "with", or "revised" for the *_with methods with removed=).  kind_of() maps a method name, method_of() an op to
+the method and keyword it is played through, NOT_MODELLED names the methods left out.
 
 HandleModel.built is the set of raw ids whose neighbourhood the handle has built since the last drop, kept by the rules the
 header states per call; the GPU tests compare it with the build numbers of the parsed checkpoint after every op."""
 import hashlib
 import re
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 import numpy as np
 
+from tests import amend_cases as am
 from tests import append_cases as ac
+from tests import bystander_cases as bc
 from tests import entered_cases as ec
 from tests import explain_model
 from tests import personalized_explain_model as pm
 from tests import personalized_query_cases as pc
 from tests import query_explain_cases as qc
 from tests import revise_cases as rc
+from tests import revise_entered_cases as rec
 from tests import update_entered_cases as uc
 from tests.test_oracle_semantics import _cols, _no_zero_scale, _random_case
 
@@ -53,10 +57,13 @@ ENTERED = ("entered", "entered_batch", "entered_with", "entered_with_batch")  # 
 MUTATING = ("neighbors", "neighbors_batch", "predict", "predict_batch", "mae", "recommend", "recommend_batch", "knn_similarity",
             "knn_similarity_batch", "explain", "explain_batch") + ENTERED
 DROPS = ("set_k", "reset_neighbors", "mae_sweep", "fit")
-REFITS = ("append",)  # replaces the fit as `fit` does, and keeps some lists
+REFITS = ("append", "amend")  # replace the fit as `fit` does, and keep some lists
 BYSTANDER = ("bystander_neighbors", "bystander_neighbors_batch", "bystander_predict", "bystander_predict_batch")
-BYSTANDER_FAMILIES = ("for", "with")
+BYSTANDER_FAMILIES = ("for", "with", "revised")  # "revised": the *_with methods with removed=
 APPEND_SHAPES = ("changer", "newcomer", "both")
+AMEND_SHAPES = ("remover", "rerate", "mixed", "leaver", "lone_item", "trivial")  # accepted amends
+AMEND_REFUSALS = {"not_a_row": E_INVALID, "twice": E_INVALID, "duplicate": E_DUPLICATE, "both_wrong": E_INVALID}
+AMEND_SHRINKS = ("leaver", "lone_item")
 CHECKPOINT = ("neighbors_save", "neighbors_load")
 STATISTICS = ("global_avg", "user_avg", "item_avg", "item_avg_dev", "item_avg_dev_rdd")
 NOT_MODELLED = {
@@ -116,6 +123,7 @@ class Op:
     kind: str
     args: tuple
     form: str = "host"  # "host" or "device", where the kind has both
+    shape: str = field(default="", compare=False)  # the generator's name for what it drew (the shape of an amend), for the premises
 
     def __repr__(self):
         return f"Op({self.kind!r}, {_plain(self.args)!r}, {self.form!r})"
@@ -375,9 +383,10 @@ class HandleModel:
         return unpad(qc.expected(self.tm.rows(users, items), cap, order), cap)
 
     # ---- read-only from here on: answers from fresh closures, the pipeline is untouched ----
-    def _reads(self, u):
-        """the wrong model whose read-only calls build: a fitted user's neighbourhood is evaluated on the handle's closures"""
-        if self.wrong == "read_only_builds" and self._known(u):
+    def _reads(self, u, revised_bystander=False):
+        """the wrong models whose read-only calls build: a fitted user's neighbourhood is evaluated on the handle's closures
+        (every read-only call, or the revised bystander forms alone)"""
+        if (self.wrong == "read_only_builds" or (revised_bystander and self.wrong == "bystander_revised_builds")) and self._known(u):
             self._builds([u])
             self.p.neighbors(int(u))
 
@@ -445,9 +454,9 @@ class HandleModel:
         try:
             m = self.oracle.Model(*aug)
         except self.oracle.OracleError as ex:  # "KNNCF_E_NONFINITE for a non-finite deviation": scale() == 0 on the user's rows in aug
-            if ex.status != E_NONFINITE:
+            if ex.status not in (E_NONFINITE, E_DUPLICATE):  # (a duplicate: only a wrong model's fit can hold the row already)
                 raise
-            return Refused(E_NONFINITE)
+            return Refused(ex.status)
         if predictor == PRED_KNN:
             p = m.pipeline(self.sim, self.k)
             near = p.neighbors(q)  # first evaluation: the query user's
@@ -475,45 +484,99 @@ class HandleModel:
                 for b, query in enumerate(queries)]
 
     # ---- knncf_append: "every later call on the handle answers bit for bit as a handle on which knncf_fit(aug) was called"; "The
-    # handle is left in the state that knncf_fit(aug) followed by knncf_neighbors_batch over K in ascending raw id leaves" ----
+    # handle is left in the state that knncf_fit(aug) followed by knncf_neighbors_batch over K in ascending raw id leaves";
+    # "knncf_append is the call without removals" ----
     def append(self, users, items, ratings):
+        assert len(users), "the generator appends at least one row"
+        none = np.empty(0, np.int32)
+        return self._amend("append", none, none, users, items, ratings)
+
+    # ---- knncf_amend: "aug is built in two steps: train in file order without the removed rows; then the n rows in the given
+    # order.  Everything else is knncf_append's contract, read on this aug"; "Precedence: the argument checks, then the removal
+    # checks, then the duplicate, then the non-finite deviation"; "n_removed == 0 && n == 0 is KNNCF_OK and touches nothing" ----
+    def amend(self, removed_users, removed_items, users, items, ratings):
+        return self._amend("amend", removed_users, removed_items, users, items, ratings)
+
+    def _wrong_aug(self, case):
+        """aug under the wrong models that build it otherwise (None: the reference's)"""
+        gone = list(zip(case.removed_users.tolist(), case.removed_items.tolist()))
+        rows = list(zip(case.users.tolist(), case.items.tolist()))
+        tu, ti, tr = (a.copy() for a in case.train)
+        pairs = list(zip(tu.tolist(), ti.tolist()))
+        if self.wrong == "amend_keeps_removed_rows":  # aug = train ++ rows: only what is rated again goes
+            keep = np.asarray([not (p in gone and p in rows) for p in pairs], dtype=bool)
+            add = np.ones(len(rows), dtype=bool)
+        elif self.wrong == "amend_rerates_in_place":  # a re-rated row keeps its file position
+            keep = np.asarray([not (p in gone and p not in rows) for p in pairs], dtype=bool)
+            add = np.asarray([p not in gone for p in rows], dtype=bool)
+            for p, r in zip(rows, case.ratings.tolist()):
+                if p in gone:
+                    tr[pairs.index(p)] = r
+        elif self.wrong == "amend_leaver_stays":  # the rows of a user that would leave stay
+            left = set(tu.tolist()) - set(case.aug[0].tolist())
+            keep = np.asarray([not (p in gone and p[0] not in left) for p in pairs], dtype=bool)
+            add = np.ones(len(rows), dtype=bool)
+        else:
+            return None
+        return (np.concatenate([tu[keep], case.users[add]]).astype(np.int32), np.concatenate([ti[keep], case.items[add]]).astype(np.int32),
+                np.concatenate([tr[keep], case.ratings[add]]).astype(np.float64))
+
+    def _amend(self, kind, removed_users, removed_items, users, items, ratings):
+        ru, ri = np.asarray(removed_users, np.int32), np.asarray(removed_items, np.int32)
         users, items = np.asarray(users, np.int32), np.asarray(items, np.int32)
         ratings = np.asarray(ratings, np.float64)
-        assert len(users), "the generator appends at least one row"
         self.definition = []
+        if len(ru) == 0 and len(users) == 0:
+            return (len(self.built), 0, np.empty(0, np.int32))  # the trivial call: a saved checkpoint still loads
+        train_pairs = set(zip(self.train[0].tolist(), self.train[1].tolist()))
+        gone = list(zip(ru.tolist(), ri.tolist()))
+        if not set(gone) <= train_pairs or len(set(gone)) < len(gone) or (len(gone) == len(train_pairs) and len(users) == 0):
+            return Refused(E_INVALID)  # "is not a train row", "listed twice", "an aug without any row"
         pairs = list(zip(users.tolist(), items.tolist()))
-        if len(set(pairs)) < len(pairs) or set(pairs) & set(zip(self.train[0].tolist(), self.train[1].tolist())):
+        if len(set(pairs)) < len(pairs) or set(pairs) & (train_pairs - set(gone)):
             return Refused(E_DUPLICATE)  # "the handle answers exactly as before the call"
-        case = ac.Append("append", self.train, users, items, ratings, self.k)
-        aug = case.aug
+        case = am.Amend(kind, self.train, ru, ri, users, items, ratings, self.k)
+        aug = (self._wrong_aug(case) if kind == "amend" else None) or case.aug
         try:
             m = self.oracle.Model(*aug)
         except self.oracle.OracleError as ex:
-            if ex.status != E_NONFINITE:
+            if ex.status not in (E_NONFINITE, E_DUPLICATE):  # (a duplicate: only a wrong model's fit can hold the row already)
                 raise
-            return Refused(E_NONFINITE)
+            return Refused(ex.status)
         sim, built = self._sim_name(), sorted(self.built)
         assert len(self.known_users) >= 5 and len(self.known_items) >= 5, "the model has no clause for fits that the update queries refuse"
-        negative = any(aug[2][aug[0] == c].sum() < 0 for c, _, _ in case.changers)  # "a negative mean of its combined rows"
-        plain = (ac.is_plain(case, sim) or (sim == ac.COS and self.short_fit) or negative or len(case.changers) > APPEND_MAX_CHANGERS)
-        order = m.user_iteration_order().tolist()
+        negative = any(aug[2][aug[0] == c].sum() < 0 for c, _, _, _ in case.changers)  # "a negative mean of its combined rows"
+        plain = (am.is_plain(case, sim) or (sim == ac.COS and self.short_fit) or negative or len(case.changers) > APPEND_MAX_CHANGERS)
+        left = sorted(self.known_users - set(aug[0].tolist()))
+        # the new fit's set order, a user that left "where its id would stand in that order"
+        order = bc.trie_sorted(self.oracle, set(m.user_iteration_order().tolist()) | set(left)) if left else m.user_iteration_order().tolist()
         if plain or not built:
-            keep, gone = [], [v for v in order if v in self.built]
+            keep, gone_lists = [], [v for v in order if v in self.built]
         else:
-            stale = _memo(("stale", self.train_key, users.tobytes(), items.tobytes(), ratings.tobytes(), self.k, sim),
-                          lambda: ac.stale(self.oracle, case, sim))
-            keep, gone = sorted(self.built - stale), [v for v in order if v in self.built and v in stale]
-            if self.wrong == "append_keeps_every_list":
-                keep, gone = built, []
-        self.appends.append({"plain": bool(plain), "built": len(built), "carried": len(keep), "dropped": len(gone)})
+            if self.wrong == "amend_reports_as_update" and kind == "amend":  # the removals ignored: what the rows alone report
+                new = np.asarray([p not in train_pairs for p in pairs], dtype=bool)  # (a re-rating would be a duplicate there)
+                find = lambda: ac.stale(self.oracle, ac.Append(kind, self.train, users[new], items[new], ratings[new], self.k), sim)
+            else:
+                find = lambda: am.stale(self.oracle, case, sim)
+            stale = _memo(("stale", self.wrong == "amend_reports_as_update" and kind == "amend", self.train_key, ru.tobytes(), ri.tobytes(),
+                           users.tobytes(), items.tobytes(), ratings.tobytes(), self.k, sim), find)
+            keep, gone_lists = sorted(self.built - stale), [v for v in order if v in self.built and v in stale]
+            if self.wrong == f"{kind}_keeps_every_list":
+                keep, gone_lists = built, []
+        if self.wrong == "amend_leaver_stays" and kind == "amend":  # ... and its list with them
+            keep = sorted(set(keep) | (set(self.built) & (self.known_users - set(case.aug[0].tolist()))))
+            gone_lists = [v for v in gone_lists if v not in keep]
+        left_items = len(self.known_items - set(aug[1].tolist()))
+        self.appends.append({"kind": kind, "plain": bool(plain), "built": len(built), "carried": len(keep), "dropped": len(gone_lists),
+                             "left_users": len(left), "left_items": left_items})
         self.train = aug
-        self._refit(m, caches=self.wrong != "append_keeps_fit_caches")
+        self._refit(m, caches=not (self.wrong == "append_keeps_fit_caches" and kind == "append"))
         self.definition = [Op("fit", (Fit("aug", aug),))]
         if keep:
             op = Op("neighbors_batch", (np.asarray(keep, np.int32),))
             self.neighbors_batch(*op.args)
             self.log, self.definition = [op], self.definition + [op]
-        return (len(keep), len(gone), np.asarray(gone, np.int32))
+        return (len(keep), len(gone_lists), np.asarray(gone_lists, np.int32))
 
     # ---- knncf_query_entered* / knncf_update_entered*: "Let M be the train users whose neighbourhood the handle has not built, in
     # ascending raw id.  When the call passes its handle-level checks, n_queries > 0 and M is not empty, it first builds them in ONE
@@ -538,14 +601,18 @@ class HandleModel:
             if st != OK:
                 out.append(Refused(st))
                 continue
-            key = ("entered", fam, self.train_key, q, items.tobytes(), ratings.tobytes(), self.k, self._sim_name())
-            want = ec.expected_for if fam == "for" else uc.expected_for
+            removed = np.asarray(removed, np.int32)
+            key = ("entered", fam, self.train_key, q, removed.tobytes(), items.tobytes(), ratings.tobytes(), self.k, self._sim_name())
+            if len(removed):  # knncf_revise_entered*: the removals in front of the rows
+                want = lambda *a: rec.expected_for(self.oracle, self.train, q, removed, *a[3:])
+            else:
+                want = ec.expected_for if fam == "for" else uc.expected_for
             try:
                 out.append(_memo(key, lambda: want(self.oracle, self.train, q, items, ratings, self.k, self._sim_name())))
             except self.oracle.OracleError as ex:
-                if ex.status != E_NONFINITE:
+                if ex.status not in (E_NONFINITE, E_DUPLICATE):  # (a duplicate: only a wrong model's fit can hold the row already)
                     raise
-                out.append(Refused(E_NONFINITE))
+                out.append(Refused(ex.status))
         return out
 
     def entered(self, query):
@@ -575,10 +642,10 @@ class HandleModel:
         try:
             m = self.oracle.Model(*rc.aug_of(self.train, q, removed, items, ratings))
         except self.oracle.OracleError as ex:
-            if ex.status != E_NONFINITE:
+            if ex.status not in (E_NONFINITE, E_DUPLICATE):  # (a duplicate: only a wrong model's fit can hold the row already)
                 raise
-            return Refused(E_NONFINITE)
-        self._reads(q)
+            return Refused(ex.status)
+        self._reads(q, revised_bystander=fam == "revised")
         if what == "neighbors":
             return [m.pipeline(self.sim, self.k).neighbors(int(v)) for v in others]
         return np.asarray([m.pipeline(self.sim, self.k).predict(int(v), int(i)) for v, i in zip(others, pred_items)], np.float64)
@@ -618,8 +685,26 @@ KINDS = tuple(sorted(n for n in vars(HandleModel) if not n.startswith("_") and n
 # the last three differ where the new fit of an append or the lists that an entered call builds matter: under Jaccard on the memo
 # fits (under the adjusted cosine every append there is a plain refit and every entered call refused), in an answer or in `built`
 WRONG_MODELS = ("stateless", "keeps_after_reset", "keeps_after_sweep", "read_only_builds", "sorted_batches",
-                "append_keeps_every_list", "append_keeps_fit_caches", "entered_builds_nothing")
-WRONG_AFTER_APPEND = WRONG_MODELS[5:]
+                "append_keeps_every_list", "append_keeps_fit_caches", "entered_builds_nothing",
+                "amend_keeps_every_list", "amend_reports_as_update", "amend_keeps_removed_rows", "amend_rerates_in_place",
+                "amend_leaver_stays", "bystander_revised_builds")
+WRONG_AFTER_APPEND = WRONG_MODELS[5:8]
+WRONG_AFTER_AMEND = WRONG_MODELS[8:13]  # each wrong in one clause of "Amend": they show after the first amend, under Jaccard
+
+
+def method_of(op):
+    """(owner class, method, whether removals are passed) of the binding call through which the Player plays an op of a kind
+    whose method takes `removed`; None for the other kinds"""
+    tail = "_batch" if op.kind.endswith("_batch") else ""
+    if "_q" in op.kind:
+        return ("Engine", f"{op.kind[:op.kind.index('_q')]}_{op.args[0]}{tail}", op.args[0] == "revised")
+    if op.kind in BYSTANDER:
+        what, fam = op.kind[len("bystander_"):].replace("_batch", ""), op.args[0]
+        return ("BystanderQueries", f"{what}_{'with' if fam == 'revised' else fam}{tail}", fam == "revised")
+    if op.kind in ("entered_with", "entered_with_batch"):
+        queries = op.args[0] if tail else [op.args[0]]
+        return ("EnteredQueries", op.kind, any(len(q[1]) for q in queries))
+    return None
 
 
 # ---- playing an op on an Engine ------------------------------------------------------------------------------------------------
@@ -629,7 +714,13 @@ class Player:
 
     def __init__(self, kn, engine, tmp, name="e", train=None):
         self.kn, self.e, self.path = kn, engine, f"{tmp}/{name}_sequence.nbr"
-        self.known_items = set() if train is None else set(np.unique(train[1]).tolist())
+        self._stands(np.empty(0, np.int32) if train is None else train[0], np.empty(0, np.int32) if train is None else train[1])
+
+    def _stands(self, users, items):
+        """the player's own record of the (user, item) rows as they stand in the handle's fit: what the statistics getters of an item
+        are asked for follows it, also when an amend takes an item out"""
+        self.row_users, self.row_items = np.asarray(users, np.int32).copy(), np.asarray(items, np.int32).copy()
+        self.known_items = set(np.unique(self.row_items).tolist())
 
     def _dev(self, a, dtype):
         import torch
@@ -648,11 +739,11 @@ class Player:
 
     def fit(self, dev, train):
         t = train.train if isinstance(train, Fit) else train
-        self.known_items = set(np.unique(t[1]).tolist())
         if dev:
             self.e.fit_device(self._dev(t[0], np.int32), self._dev(t[1], np.int32), self._dev(t[2], np.float64))
         else:
             self.e.fit(*t)
+        self._stands(t[0], t[1])
 
     def set_k(self, dev, k):
         self.e.set_k(int(k))
@@ -796,15 +887,33 @@ class Player:
     # the classes beside Engine
     def append(self, dev, users, items, ratings):
         carried, dropped, ids = self.kn.Appends(self.e).append(users, items, ratings, return_dropped=True)
-        self.known_items |= set(np.asarray(items).tolist())
+        self._stands(np.concatenate([self.row_users, users]), np.concatenate([self.row_items, items]))
         return (carried, dropped, ids)
+
+    def amend(self, dev, removed_users, removed_items, users, items, ratings):
+        carried, dropped, ids = self.kn.Appends(self.e).amend(removed_users, removed_items, users, items, ratings, return_dropped=True)
+        key = lambda u, i: (np.asarray(u, np.int64) << 32) | (np.asarray(i, np.int64) & 0xFFFFFFFF)
+        keep = ~np.isin(key(self.row_users, self.row_items), key(removed_users, removed_items))
+        self._stands(np.concatenate([self.row_users[keep], np.asarray(users, np.int32)]),
+                     np.concatenate([self.row_items[keep], np.asarray(items, np.int32)]))
+        return (carried, dropped, ids)
+
+    @staticmethod
+    def _removed_kw(op_kind, arg, batch):
+        """the removed= keyword of a *_with method: absent without removals (the update call), one sequence per query in a batch —
+        an empty one for a query without removals"""
+        queries = arg if batch else [arg]
+        if not method_of(Op(op_kind, (arg,)))[2]:
+            return {}
+        return {"removed": [np.asarray(q[1], np.int32) for q in queries] if batch else np.asarray(arg[1], np.int32)}
 
     def _entered(self, fam, batch, arg):
         eq = self.kn.EnteredQueries(self.e)
         name = "entered" if fam == "for" else "entered_with"
+        kw = self._removed_kw(name + ("_batch" if batch else ""), arg, batch) if fam == "with" else {}
         if not batch:
-            return tuple(getattr(eq, name)(*self._fam_args(fam, arg)))
-        outs, st = getattr(eq, name + "_batch")([self._fam_args(fam, q) for q in arg])
+            return tuple(getattr(eq, name)(*self._fam_args(fam, arg), **kw))
+        outs, st = getattr(eq, name + "_batch")([self._fam_args(fam, q) for q in arg], **kw)
         return [tuple(out) if s == OK else Refused(s) for out, s in zip(outs, st.tolist())]
 
     def entered(self, dev, query):
@@ -819,21 +928,34 @@ class Player:
     def entered_with_batch(self, dev, queries):
         return self._entered("with", True, queries)
 
+    def _by(self, kind, fam, arg, batch):
+        """(the BystanderQueries method, the query arguments, the removed= keyword) of a bystander op: the family "revised" is the
+        *_with method with removed= (one sequence per query in a batch, an empty one for a query without removals)"""
+        owner, name, with_removed = method_of(Op(kind, (fam, arg)))
+        short = "with" if fam == "revised" else fam
+        queries = arg if batch else [arg]
+        kw = {}
+        if with_removed:
+            kw = {"removed": [np.asarray(q[1], np.int32) for q in queries] if batch else np.asarray(arg[1], np.int32)}
+        args = [self._fam_args(short, q) for q in queries]
+        return getattr(self.kn.BystanderQueries(self.e), name), args if batch else args[0], kw
+
     def bystander_neighbors(self, dev, fam, query, others):
-        return getattr(self.kn.BystanderQueries(self.e), f"neighbors_{fam}")(*self._fam_args(fam, query), np.asarray(others, np.int32))
+        fn, args, kw = self._by("bystander_neighbors", fam, query, False)
+        return fn(*args, np.asarray(others, np.int32), **kw)
 
     def bystander_predict(self, dev, fam, query, others, pred_items):
-        return getattr(self.kn.BystanderQueries(self.e), f"predict_{fam}")(*self._fam_args(fam, query), np.asarray(others, np.int32),
-                                                                          np.asarray(pred_items, np.int32))
+        fn, args, kw = self._by("bystander_predict", fam, query, False)
+        return fn(*args, np.asarray(others, np.int32), np.asarray(pred_items, np.int32), **kw)
 
     def bystander_neighbors_batch(self, dev, fam, queries, others):
-        outs, st = getattr(self.kn.BystanderQueries(self.e), f"neighbors_{fam}_batch")(
-            [self._fam_args(fam, q) for q in queries], [np.asarray(x, np.int32) for x in others])
+        fn, args, kw = self._by("bystander_neighbors_batch", fam, queries, True)
+        outs, st = fn(args, [np.asarray(x, np.int32) for x in others], **kw)
         return [out if s == OK else Refused(s) for out, s in zip(outs, st.tolist())]
 
     def bystander_predict_batch(self, dev, fam, queries, others, pred_items):
-        outs, st = getattr(self.kn.BystanderQueries(self.e), f"predict_{fam}_batch")(
-            [self._fam_args(fam, q) for q in queries], [np.asarray(x, np.int32) for x in others], [np.asarray(x, np.int32) for x in pred_items])
+        fn, args, kw = self._by("bystander_predict_batch", fam, queries, True)
+        outs, st = fn(args, [np.asarray(x, np.int32) for x in others], [np.asarray(x, np.int32) for x in pred_items], **kw)
         return [out if s == OK else Refused(s) for out, s in zip(outs, st.tolist())]
 
 
@@ -862,6 +984,9 @@ class _Draw:
         assert NEW_ITEM not in self.items and ABSENT_ITEM not in self.items and not np.isin(ABSENT_USERS, self.users).any()
         assert not ((self.users > NEW_USER) & (self.users < NEW_USER + 10_000)).any() and NEWCOMER > NEW_USER + 10_000
         self.count = dict(zip(self.users.tolist(), counts.tolist()))
+        raters = np.unique(train[1], return_counts=True)[1]
+        self.lone = self.items[raters == 1]    # items of one rater: kept for the amend that takes such an item out of the fit
+        self.common = self.items[raters > 1]   # what the appends and the other amends draw their items from
         short = self.users[counts <= 4]
         self.short = short if len(short) else self.users
         self.hot = self._order_shows(train, short) if len(short) else self.users
@@ -954,21 +1079,23 @@ class _Draw:
     def append_rows(self, shape):
         """(users, items, ratings) of an append.  "changer": a fitted user adds 1-3 items it has not rated; "newcomer": a new user
         of 5-7 rows, sometimes with an item new to the fit; "both": the two interleaved; "duplicate": a changer's rows and a row
-        of train again, which is refused.  An accepted append (the oracle can scale aug) becomes the train set of the later ops."""
+        of train again, which is refused; "newcomer_item": a newcomer that brings an item for sure.  Items come from those of more
+        than one rater, so that an item of one rater stays one.  An accepted append (the oracle can scale aug) becomes the train
+        set of the later ops."""
         rng, o = self.rng, self.model.oracle
         for _ in range(50):
             parts = []
             if shape in ("changer", "both", "duplicate"):
                 c = self.fitted()
-                free = np.setdiff1d(self.items, self.train[1][self.train[0] == c])
+                free = np.setdiff1d(self.common, self.train[1][self.train[0] == c])
                 n = min(int(rng.integers(1, 4)), len(free))
                 if n == 0:
                     continue
                 parts.append((c, rng.choice(free, n, replace=False).astype(np.int32), rng.integers(1, 6, n).astype(np.float64)))
-            if shape in ("newcomer", "both"):
+            if shape in ("newcomer", "both", "newcomer_item"):
                 self.newcomer += 1
-                items = rng.choice(self.items, min(int(rng.integers(5, 8)), len(self.items)), replace=False).astype(np.int32)
-                if rng.random() < 0.4:
+                items = rng.choice(self.common, min(int(rng.integers(5, 8)), len(self.common)), replace=False).astype(np.int32)
+                if rng.random() < 0.4 or shape == "newcomer_item":
                     self.append_item += 1
                     items[int(rng.integers(0, len(items)))] = self.append_item
                 parts.append((self.newcomer, items, rng.integers(1, 6, len(items)).astype(np.float64)))
@@ -985,6 +1112,128 @@ class _Draw:
             self.set_train(aug)
             return rows
         raise AssertionError(("no acceptable append", shape))
+
+    def _own(self, c):
+        at = self.train[0] == c
+        return self.train[1][at], self.train[2][at]
+
+    def _original(self, min_rows=1):
+        """a fitted user of the first fit (no appended newcomer) of at least min_rows rows"""
+        for _ in range(200):
+            u = self.fitted(min_rows)
+            if u < NEWCOMER and self.count.get(u, 0) >= min_rows:
+                return u
+        raise AssertionError(("no fitted user of so many rows", min_rows))
+
+    def _removals_of(self, c, n):
+        """n train items of c that other users rated too, in a random order"""
+        mine = self._own(c)[0]
+        mine = mine[np.isin(mine, self.common)]
+        return self.rng.choice(mine, min(n, len(mine)), replace=False).astype(np.int32)
+
+    def _other_value(self, v):
+        return float(v - 2 if v >= 3 else v + 2)
+
+    def amend_rows(self, shape):
+        """(removed users, removed items, users, items, ratings) of an amend.
+        "remover": a fitted user of more than 6 rows removes 1-2 of them; "rerate": a removal and a row on the same item (half of
+        them with the same value), sometimes a second removal; "mixed": a remover that re-rates, a fitted user that only adds and a
+        newcomer (sometimes with a new item), rows interleaved, removals shuffled; "leaver": a fitted user — a <= 4-rating one where
+        the fit has some — removes all its rows; "lone_item": the only rating of an item goes, and the item with it; "trivial":
+        nothing.  Refused and without a trace: "not_a_row" (an item the user did not rate; in every other draw the call's own
+        newcomer), "twice" (a removal listed twice), "duplicate" (a row on an unremoved train row), "both_wrong" (a bad removal
+        and a duplicate row: the removal checks come first).  An accepted draw — aug keeps 5 users and 5 items, no fitted user's
+        mean is negative, the oracle can scale it — becomes the train set of the later ops."""
+        rng, o = self.rng, self.model.oracle
+        none, nof = np.empty(0, np.int32), np.empty(0, np.float64)
+        if shape == "trivial":
+            return (none, none, none, none, nof)
+        self.amend_draws = getattr(self, "amend_draws", 0) + 1
+        for _ in range(50):
+            rm, parts = [], []  # [(user, item)], [(user, items, ratings)]
+            if shape in ("remover", "twice"):
+                c = self._original(7)
+                rm = [(c, int(i)) for i in self._removals_of(c, int(rng.integers(1, 3)))]
+                if shape == "twice":
+                    rm.insert(int(rng.integers(0, len(rm) + 1)), rm[int(rng.integers(0, len(rm)))])
+            elif shape in ("rerate", "duplicate", "both_wrong"):
+                c = self._original(3)
+                gone = self._removals_of(c, 1 + int(rng.random() < 0.5))
+                if len(gone) == 0:
+                    continue
+                rm = [(c, int(i)) for i in gone]
+                mine, vals = self._own(c)
+                v = float(vals[mine == gone[0]][0])
+                parts = [(c, gone[:1], np.asarray([v if rng.random() < 0.5 else self._other_value(v)]))]
+                if shape != "rerate":  # a row on a train row of c that stays
+                    stays = np.setdiff1d(mine, gone)
+                    parts[0] = (c, np.append(gone[:1], rng.choice(stays)).astype(np.int32), np.append(parts[0][2], 3.0))
+                if shape == "both_wrong":
+                    free = np.setdiff1d(self.items, mine)
+                    rm.append((c, int(rng.choice(free)) if len(free) else ABSENT_ITEM))
+            elif shape == "not_a_row":
+                if self.amend_draws % 2:
+                    c = self.fitted()
+                    free = np.setdiff1d(self.items, self._own(c)[0])
+                    rm = [(c, int(rng.choice(free)) if len(free) and rng.random() < 0.7 else ABSENT_ITEM)]
+                else:  # the removal names the call's own newcomer
+                    self.newcomer += 1
+                    items = rng.choice(self.common, min(5, len(self.common)), replace=False).astype(np.int32)
+                    parts = [(self.newcomer, items, rng.integers(1, 6, len(items)).astype(np.float64))]
+                    rm = [(self.newcomer, int(items[0]))]
+            elif shape == "mixed":
+                a = self._original(5)
+                gone = self._removals_of(a, int(rng.integers(2, 4)))
+                b = self._original()
+                free = np.setdiff1d(self.common, self._own(b)[0])
+                if len(gone) < 2 or b == a or len(free) == 0:
+                    continue
+                rm = [(a, int(i)) for i in gone]
+                mine, vals = self._own(a)
+                parts.append((a, gone[:1], np.asarray([self._other_value(float(vals[mine == gone[0]][0]))])))
+                n = min(int(rng.integers(1, 4)), len(free))
+                parts.append((b, rng.choice(free, n, replace=False).astype(np.int32), rng.integers(1, 6, n).astype(np.float64)))
+                self.newcomer += 1
+                items = rng.choice(self.common, min(int(rng.integers(5, 8)), len(self.common)), replace=False).astype(np.int32)
+                if rng.random() < 0.4:
+                    self.append_item += 1
+                    items[int(rng.integers(0, len(items)))] = self.append_item
+                parts.insert(1, (self.newcomer, items, rng.integers(1, 6, len(items)).astype(np.float64)))  # (between the two: its rows
+                rm = [rm[j] for j in rng.permutation(len(rm))]                                              # interleave with theirs)
+            elif shape == "leaver":
+                few = [int(u) for u in self.users if self.count[int(u)] <= 4 and u < NEWCOMER]
+                c = int(rng.choice(few)) if few else self._original()
+                mine = self._own(c)[0]
+                if np.isin(mine, self.lone).any():
+                    continue
+                rm = [(c, int(i)) for i in mine[rng.permutation(len(mine))]]
+            elif shape == "lone_item":
+                assert len(self.lone), "no item of one rater: the slot lies behind a newcomer append that brings one"
+                i = int(rng.choice(self.lone))
+                c = int(self.train[0][self.train[1] == i][0])
+                assert self.count[c] > 1
+                rm = [(c, i)]
+            else:
+                raise AssertionError(shape)
+            if not rm:
+                continue
+            u, i, r = ac.interleave(parts) if parts else ([], [], [])
+            call = (np.asarray([x[0] for x in rm], np.int32), np.asarray([x[1] for x in rm], np.int32),
+                    np.asarray(u, np.int32), np.asarray(i, np.int32), np.asarray(r, np.float64))
+            if shape in AMEND_REFUSALS:
+                return call
+            aug = am.Amend(shape, self.train, *call, self.k).aug
+            if len(np.unique(aug[0])) < 5 or len(np.unique(aug[1])) < 5:
+                continue
+            try:
+                m = o.Model(*aug)
+            except o.OracleError:
+                continue  # (a scale() == 0 input: drawn again)
+            if any(m.users_avg(int(x)) < 0 for x in np.unique(aug[0])):
+                continue
+            self.set_train(aug)
+            return call
+        raise AssertionError(("no acceptable amend", shape))
 
     def bystander_rows(self, query, refused=False):
         """(others, pred_items) of a bystander query: fitted users (an absent id among them at times) other than the query's user
@@ -1044,23 +1293,32 @@ class _Draw:
             return Op(kind, d.rows(d.size())[:2] + d.explain_args(), form)
         if kind == "append":
             return Op(kind, d.append_rows(variant or APPEND_SHAPES[int(rng.integers(0, 3))]))
+        if kind == "amend":
+            shape = variant or AMEND_SHAPES[int(rng.integers(0, 3))]
+            return Op(kind, d.amend_rows(shape), shape=shape)
         if kind in ENTERED:
             fam = "with" if "with" in kind else "for"
+            drawn = "revised" if variant == "removed" else fam  # entered_with*(..., removed=...): the queries of the revise family
             if not kind.endswith("_batch"):
-                return Op(kind, (d.query(fam),))
-            queries = [d.query(fam) for _ in range(int(rng.choice(self.batch_sizes)))]
+                return Op(kind, (d.query(drawn),))
+            queries = [d.query(drawn) for _ in range(int(rng.choice(self.batch_sizes)))]
+            if drawn == "revised" and rng.random() < 0.5:  # a query without removals inside the revise call
+                queries[-1] = d.query("with")
             if rng.random() < 0.5:  # a refused query inside the batch: a fitted user as a newcomer, an absent one without rows
                 at = len(queries) // 2
-                queries[at] = (d.fitted(),) + queries[at][1:] if fam == "for" else (int(rng.choice(ABSENT_USERS)), queries[at][1], queries[at][1], np.empty(0))
+                gone = queries[at][1]  # (with removals: "any removal for a user absent from train")
+                queries[at] = (d.fitted(),) + queries[at][1:] if fam == "for" else (int(rng.choice(ABSENT_USERS)), gone, gone[:0], np.empty(0))
             return Op(kind, (queries,))
         if kind in BYSTANDER:
-            fam = variant if variant is not None else BYSTANDER_FAMILIES[int(rng.integers(0, 2))]
+            fam = variant if variant is not None else BYSTANDER_FAMILIES[int(rng.integers(0, 3))]
             predict = "predict" in kind
             if not kind.endswith("_batch"):
                 query = d.query(fam)
                 rows = d.bystander_rows(query)
                 return Op(kind, (fam, query) + (rows if predict else rows[:1]))
             queries = [d.query(fam) for _ in range(int(rng.choice(self.batch_sizes)))]
+            if fam == "revised" and rng.random() < 0.5:  # a query without removals inside the revise call
+                queries[-1] = d.query("with")
             refused = len(queries) // 2 if rng.random() < 0.5 else -1  # a query that names its own user among its rows
             rows = [d.bystander_rows(q, refused=b == refused) for b, q in enumerate(queries)]
             return Op(kind, (fam, queries, [x[0] for x in rows]) + (([x[1] for x in rows],) if predict else ()))
@@ -1108,12 +1366,23 @@ def sequence(seed, model, n_ops, k_pool=(2, 6), fits=None, batch_sizes=(2, 3, 5)
     slots += [("predict_q", "negative_mean"), ("recommend_q_batch", "negative_mean"), ("explain_q", "removes_unrated"),
               ("neighbors_q_batch", "removes_unrated"), ("predict_batch", PRED_PERSONALIZED), ("recommend", PRED_PERSONALIZED),
               ("mae", PRED_KNN), ("predict_batch", PRED_KNN), ("recommend_batch", PRED_KNN)]
-    # appends: the slot of the kind draws a shape, one is a fitted changer's, one is refused and leaves no trace, and in the memo
-    # sequences a third one interleaves a changer and a newcomer (on the 2 100 users of a life the oracle's side of an append costs
-    # seconds)
+    # appends: the slot of the kind is a newcomer that brings an item of its own (which the "lone_item" amend later takes out again),
+    # one is a fitted changer's, one is refused and leaves no trace, and in the memo sequences a fourth one interleaves a changer and
+    # a newcomer (on the 2 100 users of a life the oracle's side of an append costs seconds)
     slots += [("append", "changer"), ("append", "duplicate")] + ([] if every_variant else [("append", "both")])
-    if not every_variant:  # ... and the kind's own slot is the third shape, a newcomer alone
-        slots[slots.index(("append", None))] = ("append", "newcomer")
+    slots[slots.index(("append", None))] = ("append", "newcomer_item")
+    # amends: every shape and every refusal once in the memo sequences; the lives leave out the lone remover and two refusals, and
+    # a life on more than 1 000 users (the oracle's side costs seconds per changer there) keeps one changer that carries, what
+    # shrinks and what is refused
+    slots.remove(("amend", None))
+    if not every_variant:
+        slots += [("amend", x) for x in AMEND_SHAPES + tuple(AMEND_REFUSALS)]
+    elif len(d.users) > 1000:
+        slots += [("amend", x) for x in ("rerate", "leaver", "trivial", "not_a_row", "duplicate")]
+    else:
+        slots += [("amend", x) for x in ("rerate", "mixed", "leaver", "lone_item", "trivial", "not_a_row", "duplicate")]
+    # the entered_with forms once more with removals (knncf_revise_entered*)
+    slots += [("entered_with", "removed"), ("entered_with_batch", "removed")]
     if every_variant:
         slots = [s for s in slots if s[0] not in BYSTANDER] + [(kind, fam) for kind in BYSTANDER for fam in BYSTANDER_FAMILIES]
         for what in QUERY_WHATS:
@@ -1132,13 +1401,30 @@ def sequence(seed, model, n_ops, k_pool=(2, 6), fits=None, batch_sizes=(2, 3, 5)
         slots.append((extra[int(rng.integers(0, len(extra)))], PRED_KNN if rng.random() < 0.8 else None))
     order = rng.permutation(len(slots))
     slots = [slots[j] for j in order]
-    accepted = lambda s: s[0] == "append" and s[1] != "duplicate"
+    # the fit changes with an accepted append and with an accepted amend other than the trivial one
+    accepted = lambda s: (s[0] == "append" and s[1] != "duplicate") or (s[0] == "amend" and s[1] in AMEND_SHAPES and s[1] != "trivial")
+
+    def swap(a, b):
+        slots[a], slots[b] = slots[b], slots[a]
+
     if every_variant:  # an accepted append in the first half, so that a full pass of kinds runs on the appended fit
-        first = min(j for j, s in enumerate(slots) if accepted(s))
+        first = min(j for j, s in enumerate(slots) if accepted(s) and s[0] == "append")
         if first >= len(slots) // 2:
-            to = int(rng.integers(0, len(slots) // 2))
-            slots[to], slots[first] = slots[first], slots[to]
-    # the checkpoint: a save, and its load before the next call after which it no longer loads (set_k, fit, an accepted append)
+            swap(int(rng.integers(0, len(slots) // 2)), first)
+    if ("amend", "lone_item") in slots:  # behind the newcomer whose item it removes
+        brings, lone = slots.index(("append", "newcomer_item")), slots.index(("amend", "lone_item"))
+        if lone < brings:
+            swap(lone, brings)
+            brings, lone = lone, brings
+        if any(s[0] == "fit" for s in slots[brings:lone]):  # (a fit takes the newcomer and its item away again)
+            swap(lone, brings + 1)
+    if every_variant:  # ... and an amend that shrinks the fit there too: every kind runs on a fit smaller than the one before
+        first = min(j for j, s in enumerate(slots) if s[0] == "amend" and s[1] in AMEND_SHRINKS)
+        if first >= len(slots) // 2:
+            free = [j for j in range(len(slots) // 2) if slots[j][0] not in REFITS + ("fit",)]
+            swap(free[int(rng.integers(0, len(free)))], slots.index(("amend", "leaver")))
+    # the checkpoint: a save, and its load before the next call after which it no longer loads (set_k, fit, an accepted append or
+    # amend)
     at = int(rng.integers(1, max(2, len(slots) // 2)))
     ends = [j for j in range(at, len(slots)) if slots[j][0] in ("set_k", "fit") or accepted(slots[j])]
     end = ends[0] if ends else len(slots)
@@ -1167,7 +1453,7 @@ def refusals_in(ops, model_factory):
 
 
 # ---- the committed cases -----------------------------------------------------------------------------------------------------
-N_OPS = 72
+N_OPS = 84
 
 
 def memo_fit(seed, half=True):
@@ -1210,13 +1496,13 @@ def sim_of(oracle, name):
 
 
 K_ALL = 60  # >= U - 1 of every memo fit (40 users)
-# fit and sequence seeds searched on the CPU (differing_ops over a few dozen seeds each) so that the premises of
+# fit and sequence seeds searched on the CPU (differing_ops over the sequence seeds 0 .. 29 of each fit) so that the premises of
 # test_call_sequence_premises.py hold
 MEMO_CASES = [
     Case("k2-a", 20, 2, 3),
-    Case("k2-b", 13, 2, 8),
-    Case("k6", 4, 6, 6),
-    Case("kall", 5, K_ALL, 8),
+    Case("k2-b", 13, 2, 23),
+    Case("k6", 4, 6, 23),
+    Case("kall", 5, K_ALL, 11),
 ]
 
 

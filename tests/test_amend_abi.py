@@ -1,9 +1,8 @@
 """knncf_amend at the C boundary and in the binding, without a GPU: the symbol is declared, exported and listed in EXPORTS with
 the documented argument types — the removals in front of knncf_append's arguments; the header has its section and the constant
 KNNCF_AMEND_TILE, which the binding exports with the same value; a null handle gets KNNCF_E_INVALID (a handle needs a device, so
-KNNCF_E_STATE before a fit is test_gpu_amend.py's); Appends.append stays what it was.  The binding declares the C call only: a
-public method of a wrapper class needs its call kind in tests/call_sequences.py (test_call_sequence_premises.py), which this
-step does not touch — the tests call through amend_cases.amend."""
+KNNCF_E_STATE before a fit is test_gpu_amend.py's); Appends.append stays what it was and Appends.amend beside it refuses bad
+shapes and dtypes with ValueError before the library is called."""
 import ctypes as C
 import importlib
 import inspect
@@ -79,3 +78,45 @@ def _call(lib, h, removals, rows):
 
 def test_null_handle(kn):
     assert _call(kn.load_library(), None, ([5], [1]), ([5, 5], [1, 2], [3.0, 4.0])) == (kn.E_INVALID, -7, -7)
+
+
+class _NoLibrary:
+    """an engine whose every attribute access fails: the method must refuse before it touches the handle or the library"""
+
+    def __getattr__(self, name):
+        raise AssertionError(f"the engine was touched ({name}) before the arguments were validated")
+
+
+def test_the_method_validates_before_the_library_is_called(kn):
+    assert list(inspect.signature(kn.Appends.amend).parameters) == ["self", "removed_users", "removed_items", "users", "items", "ratings",
+                                                                    "return_dropped"]
+    assert inspect.signature(kn.Appends.amend).parameters["return_dropped"].default is False
+    a = kn.Appends(_NoLibrary())
+    good = ([5], [1], [5, 5], [1, 2], [3.0, 4.0])
+    bad = [
+        ([5, 6], [1]) + good[2:],                                   # removals of two lengths
+        ([[5]], [[1]]) + good[2:],                                  # 2-D removals
+        ([5.0], [1]) + good[2:],                                    # float ids
+        ([5], [2**31]) + good[2:],                                  # an id past 32 bits
+        ([5], [-2**31 - 1]) + good[2:],
+        good[:2] + ([5, 5], [1], [3.0, 4.0]),                       # rows of two lengths
+        good[:2] + ([5, 5], [1, 2], [3.0]),
+        good[:2] + ([[5, 5]], [[1, 2]], [[3.0, 4.0]]),              # 2-D rows
+        good[:2] + ([5, 5], [1.5, 2], [3.0, 4.0]),                  # float ids
+        good[:2] + ([2**31, 5], [1, 2], [3.0, 4.0]),
+        good[:2] + ([5, 5], [1, 2], ["3", "4"]),                    # ratings that are no numbers
+        good[:2] + (5, 1, 3.0),                                     # scalars
+    ]
+    for args in bad:
+        with pytest.raises(ValueError):
+            a.amend(*args)
+        with pytest.raises(ValueError):
+            a.amend(*args, return_dropped=True)
+    # the same checks as append's on the rows
+    for args in bad[5:]:
+        with pytest.raises(ValueError):
+            a.append(*args[2:])
+    # good arguments, empty parts included, pass the validation and reach the engine
+    for args in (good, ([], []) + good[2:], good[:2] + ([], [], []), ([], [], [], [], [])):
+        with pytest.raises(AssertionError, match="the engine was touched"):
+            a.amend(*args)

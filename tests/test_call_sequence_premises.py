@@ -14,10 +14,11 @@ _counts = {}
 
 def _differs(oracle, case, wrong):
     """the ops that the wrong model changes: in the answer under the adjusted cosine, and for the wrong models of
-    cs.WRONG_AFTER_APPEND in the answer or in the set of built lists under Jaccard (where the memo fits carry lists)"""
+    cs.WRONG_AFTER_APPEND, cs.WRONG_AFTER_AMEND and "bystander_revised_builds" in the answer or in the set of built lists under
+    Jaccard (where the memo fits carry lists)"""
     key = (case.name, wrong)
     if key not in _counts:
-        late = wrong in cs.WRONG_AFTER_APPEND
+        late = wrong in cs.WRONG_MODELS[5:]  # (the models of an append, an entered call, an amend and the revised bystanders)
         _counts[key] = cs.differing_ops(oracle, case, wrong, sim="jaccard" if late else "cosine", with_built=late)
     return _counts[key]
 
@@ -48,9 +49,10 @@ def wrapper_methods(pkg):
 
 def test_counts_table(oracle):
     """prints, per case, how many of the ops each wrong model changes"""
-    print("\ncase      " + " ".join(f"{w:>{max(18, len(w))}}" for w in cs.WRONG_MODELS))
-    for case in cs.MEMO_CASES:
-        print(f"{case.name:<10}" + " ".join(f"{len(_differs(oracle, case, w)):>{max(18, len(w))}}" for w in cs.WRONG_MODELS))
+    for models in (cs.WRONG_MODELS[:8], cs.WRONG_MODELS[8:]):
+        print("\ncase      " + " ".join(f"{w:>{max(18, len(w))}}" for w in models))
+        for case in cs.MEMO_CASES:
+            print(f"{case.name:<10}" + " ".join(f"{len(_differs(oracle, case, w)):>{max(18, len(w))}}" for w in models))
 
 
 @pytest.mark.parametrize("case", cs.MEMO_CASES, ids=lambda c: c.name)
@@ -130,15 +132,17 @@ def test_memo_appends_carry_and_drop(oracle, case):
     """under Jaccard some append of every sequence meets built lists, keeps some and drops some; under the adjusted cosine every
     append of a memo fit (users of <= 4 ratings) is a plain refit; one append of every sequence is refused and leaves no trace"""
     model, out = _played(oracle, case, "jaccard")
-    assert any(a["carried"] >= 1 and a["dropped"] >= 1 for a in model.appends), (case.name, model.appends)
+    appends = [a for a in model.appends if a["kind"] == "append"]  # (model.appends holds the accepted amends too)
+    assert any(a["carried"] >= 1 and a["dropped"] >= 1 for a in appends), (case.name, appends)
     assert all(a["carried"] + a["dropped"] == a["built"] for a in model.appends)
     cosine, out_c = _played(oracle, case, "cosine")
-    assert cosine.appends and all(a["plain"] and a["carried"] == 0 for a in cosine.appends), (case.name, cosine.appends)
+    appends_c = [a for a in cosine.appends if a["kind"] == "append"]
+    assert appends_c and all(a["plain"] and a["carried"] == 0 for a in appends_c), (case.name, appends_c)
     ops = case.ops(oracle)
     for o in (out, out_c):
         refused = [x for op, x in zip(ops, o) if op.kind == "append" and isinstance(x, cs.Refused)]
         assert [x.status for x in refused] == [cs.E_DUPLICATE], case.name
-    assert len(model.appends) == len(cosine.appends) == sum(op.kind == "append" for op in ops) - 1 >= 3
+    assert len(appends) == len(appends_c) == sum(op.kind == "append" for op in ops) - 1 >= 3
     # the rows come in all three shapes: a fitted changer, a newcomer, both interleaved
     fitted = set(case.train()[0].tolist())
     shapes = set()
@@ -151,6 +155,8 @@ def test_memo_appends_carry_and_drop(oracle, case):
             assert all(u > cs.NEWCOMER for u in new) and len(new) <= 1
             shapes.add("both" if new and len(users) > 1 else "newcomer" if new else "changer")
             fitted |= set(users)
+        if op.kind == "amend" and not isinstance(x, cs.Refused):  # (its newcomer joins; the user that leaves is no changer later)
+            fitted |= set(op.args[2].tolist())
     assert shapes == set(cs.APPEND_SHAPES), (case.name, shapes)
 
 
@@ -179,10 +185,11 @@ def test_lives_append_early_and_carry(oracle, life):
     body = ops[2:]
     accepted = [j for j, (op, x) in enumerate(zip(body, out[2:])) if op.kind == "append" and not isinstance(x, cs.Refused)]
     assert accepted and accepted[0] < len(body) // 2, (life, accepted, len(body))
+    appends = [a for a in model.appends if a["kind"] == "append"]
     if model.short_fit:
-        assert all(a["plain"] for a in model.appends), (life, model.appends)
+        assert all(a["plain"] for a in appends), (life, appends)
     else:
-        assert any(a["carried"] >= 1 and a["dropped"] >= 1 for a in model.appends), (life, model.appends)
+        assert any(a["carried"] >= 1 and a["dropped"] >= 1 for a in appends), (life, appends)
         assert max(model.entered_missing) > 0, (life, model.entered_missing)
 
 
@@ -203,13 +210,58 @@ def test_every_engine_method_has_a_kind(engine_methods, wrapper_methods):
             assert kind in cs.KINDS and callable(getattr(cs.HandleModel, kind)) and callable(getattr(cs.Player, kind)), (owner, name)
             assert kind not in kinds, (owner, name, "the kind of another class's method")
         kinds |= {cs.kind_of(n, owner) for n in names}
-    for kind in cs.BYSTANDER:  # both families of every bystander kind exist
+    for kind in cs.BYSTANDER:  # every family of every bystander kind exists: "revised" is the *_with method with removed=
         what, tail = kind[len("bystander_"):].replace("_batch", ""), "_batch" if kind.endswith("_batch") else ""
-        assert {f"{what}_{fam}{tail}" for fam in cs.BYSTANDER_FAMILIES} <= set(wrapper_methods["BystanderQueries"]), kind
+        for fam in cs.BYSTANDER_FAMILIES:
+            owner, name, with_removed = cs.method_of(cs.Op(kind, (fam, (0, [], [], []))))
+            assert owner == "BystanderQueries" and name in wrapper_methods[owner], (kind, fam)
+            assert with_removed == (fam == "revised") and name == f"{what}_{'with' if fam == 'revised' else fam}{tail}"
     assert kinds == set(cs.KINDS), (kinds ^ set(cs.KINDS))
     for kind in cs.DEVICE_FORMS:
         assert f"{kind}_device" in engine_methods, kind
     assert {n[:-7] for n in engine_methods if n.endswith("_device")} == set(cs.DEVICE_FORMS)
+
+
+def _takes_removed(pkg):
+    """{(class, method): whether `removed` is optional} of every public method of Engine and of the wrapper classes whose
+    signature has a parameter `removed` — the keyword or argument that switches the method to a knncf_revise_* entry point — or
+    whose name says *_revised*"""
+    kn = importlib.import_module(pkg.__name__ + ".knncf")
+    found = {}
+    for owner, c in inspect.getmembers(kn, inspect.isclass):
+        if c.__module__ != kn.__name__ or owner.startswith("_"):
+            continue
+        for name in _public(c):
+            p = inspect.signature(getattr(c, name)).parameters.get("removed")
+            if p is not None:
+                found[owner, name] = p.default is not inspect.Parameter.empty
+            elif "_revised" in name:  # (the batch forms take the removals inside their queries)
+                found[owner, name] = False
+    return found
+
+
+def test_every_method_with_removed_is_played_both_ways(oracle, pkg, wrapper_methods):
+    """a method's name says nothing about a keyword that switches its C entry point (knncf_update_* to knncf_revise_*): every
+    public method with a parameter `removed` is played in EVERY life with removals and, where the parameter is optional, without"""
+    takes = _takes_removed(pkg)
+    by, en = ("BystanderQueries", "EnteredQueries")
+    assert {(by, f"{w}_with{t}") for w in ("neighbors", "predict") for t in ("", "_batch")} <= set(takes)
+    assert {(en, "entered_with"), (en, "entered_with_batch")} <= set(takes) and all(takes[o, n] for o, n in takes if o in (by, en))
+    revised = {("Engine", f"{w}_revised{t}") for w in cs.QUERY_WHATS for t in ("", "_batch")}
+    assert revised <= set(takes) and not any(takes[x] for x in revised)
+    assert set(takes) == revised | {x for x in takes if x[0] in (by, en)}, "a method with `removed` that no call kind plays"
+    for life in range(len(cs.LIVES)):
+        seen = {cs.method_of(op) for op in cs.life_ops(oracle, life)} - {None}
+        for (owner, name), optional in takes.items():
+            assert (owner, name, True) in seen, (life, owner, name, "never played with removals")
+            if optional:
+                assert (owner, name, False) in seen, (life, owner, name, "never played without removals")
+        # a query with removals is what the flag says: the Player passes removed= exactly then
+        for op in cs.life_ops(oracle, life):
+            m = cs.method_of(op)
+            if m is not None and m[0] == en:
+                queries = op.args[0] if op.kind.endswith("_batch") else [op.args[0]]
+                assert m[2] == any(len(q[1]) for q in queries)
 
 
 def _check_coverage(ops, refusals, short_fit, what):
@@ -230,12 +282,14 @@ def test_memo_sequences_hold_every_kind_and_refusal(oracle, case):
     assert {op.form for op in ops} == {"host", "device"}
     _check_coverage(ops, cs.refusals_in(ops, lambda: case.model(oracle)), True, case.name)
     # the fitted Personalized forms are refused under the cosine only: under Jaccard the same ops are answered
-    # (of the kinds beside the Engine's only what the generator plants is refused: the duplicate append, and a query inside a batch
-    # of entered or bystander queries that is invalid as such)
-    beside = ("append",) + cs.ENTERED + cs.BYSTANDER
+    # (of the kinds beside the Engine's only what the generator plants is refused: the duplicate append, the amends with a bad
+    # removal or a duplicate row, and a query inside a batch of entered or bystander queries that is invalid as such)
+    beside = ("append", "amend") + cs.ENTERED + cs.BYSTANDER
     jaccard = cs.refusals_in(ops, lambda: case.model(oracle, "jaccard"))
     assert not [k for k, s in jaccard if "_q" not in k and k not in beside]
-    assert {(k, s) for k, s in jaccard if k in beside} <= {("append", cs.E_DUPLICATE)} | {(k, cs.E_INVALID) for k in beside if k.endswith("_batch")}
+    planted = {("append", cs.E_DUPLICATE), ("amend", cs.E_INVALID), ("amend", cs.E_DUPLICATE)}
+    assert {(k, s) for k, s in jaccard if k in beside} <= planted | {(k, cs.E_INVALID) for k in beside if k.endswith("_batch")}
+    assert planted <= jaccard
     # the query forms are answered where the fitted forms refuse
     out = cs.play_on_model(case.model(oracle), ops)
     assert any(op.kind in ("predict_q", "recommend_q", "explain_q") and op.args[1] == cs.PRED_PERSONALIZED and not isinstance(o, cs.Refused)
@@ -263,7 +317,140 @@ def test_lives_hold_every_kind_variant_and_refusal(oracle, life):
             seen = {(op.args[0], op.args[1]) for op in ops if op.kind == f"{what}_q{tail}"}
             want = {(f, p) for f in cs.FAMILIES for p in ((cs.PRED_KNN,) if what == "neighbors" else (cs.PRED_KNN, cs.PRED_PERSONALIZED))}
             assert seen >= want, (life, what, tail, want - seen)
+    # the three bystander families of every bystander kind, and the entered `with` forms with and without removals
+    for kind in cs.BYSTANDER:
+        assert {op.args[0] for op in ops if op.kind == kind} >= set(cs.BYSTANDER_FAMILIES), (life, kind)
+    for kind in ("entered_with", "entered_with_batch"):
+        assert {cs.method_of(op)[2] for op in ops if op.kind == kind} == {False, True}, (life, kind)
     # query batches on both sides of the split between the two similarity kernels
     out = cs.play_on_model(model(), ops)
     answerable = {sum(not isinstance(x, cs.Refused) for x in o) for op, o in zip(ops, out) if op.kind.endswith("_q_batch")}
     assert {cs.QB_DUAL_MIN - 1, cs.QB_DUAL_MIN} <= answerable, (life, sorted(answerable))
+
+
+# ---- knncf_amend and the removed= forms ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("wrong", cs.WRONG_AFTER_AMEND)
+def test_wrong_amend_differs_after_the_first_amend(oracle, wrong):
+    """an amend that keeps every built list, one whose S comes from the update reports of the rows alone, one that keeps the
+    removed rows, one that re-rates in place, and one after which the user that left is still there: each shows in an op AFTER the
+    first amend of some sequence — in the answer or in the set of built lists — and in none before it.  (Half-star sums are exact
+    in fp64, so a re-rating in place shows only where the row's place is read: in the order of a <= 4-rating user's fold and in
+    the rank of tied deviations; seeds 0 .. 29 of every memo fit were searched, and it shows in most of them.)"""
+    hits = []
+    for case in cs.MEMO_CASES:
+        ops = case.ops(oracle)
+        first = min(j for j, op in enumerate(ops) if op.kind == "amend")
+        d = _differs(oracle, case, wrong)
+        assert all(j >= first for j in d), (case.name, d, first)
+        hits += [(case.name, j) for j in d if j > first]
+    assert hits, wrong
+
+
+def test_revised_bystander_call_that_builds_differs_later(oracle):
+    """read_only_builds restricted to the revised bystander forms: the call's own answer is right, a LATER op differs"""
+    hits = []
+    for case in cs.MEMO_CASES:
+        ops = case.ops(oracle)
+        d = _differs(oracle, case, "bystander_revised_builds")
+        readers = [j for j, op in enumerate(ops) if op.kind in cs.BYSTANDER and op.args[0] == "revised"]
+        assert readers and all(j >= readers[0] for j in d), (case.name, d, readers)
+        hits += [(case.name, j) for j in d if any(r < j for r in readers) and j not in readers]
+    assert hits
+
+
+def _amends(ops, out):
+    return [(op, x) for op, x in zip(ops, out) if op.kind == "amend"]
+
+
+@pytest.mark.parametrize("case", cs.MEMO_CASES, ids=lambda c: c.name)
+def test_memo_amends_hold_every_shape_and_refusal(oracle, case):
+    """every memo sequence plays every amend shape and every refusal once, each with its status under both similarities; a refused
+    amend and the trivial one leave model.appends as it was; the shapes are what their names say"""
+    import numpy as np
+
+    ops = case.ops(oracle)
+    assert sorted(op.shape for op in ops if op.kind == "amend") == sorted(cs.AMEND_SHAPES + tuple(cs.AMEND_REFUSALS))
+    assert {"not_a_row": cs.E_INVALID, "twice": cs.E_INVALID, "duplicate": cs.E_DUPLICATE, "both_wrong": cs.E_INVALID} == cs.AMEND_REFUSALS
+    for sim in ("jaccard", "cosine"):
+        model = case.model(oracle, sim)
+        for op in ops:
+            before, train, built = list(model.appends), model.train, set(model.built)
+            users, items = set(model.known_users), set(model.known_items)
+            x = model.call(op)
+            if op.kind != "amend":
+                continue
+            ru, ri, u, i, r = op.args
+            if op.shape in cs.AMEND_REFUSALS:
+                assert isinstance(x, cs.Refused) and x.status == cs.AMEND_REFUSALS[op.shape], (case.name, sim, op)
+                assert model.appends == before and model.train is train and model.built == built and model.definition == []
+                if op.shape == "twice":
+                    assert len(set(zip(ru.tolist(), ri.tolist()))) < len(ru)
+                if op.shape == "both_wrong":  # without its bad removal the call is a duplicate, without its duplicate row E_INVALID
+                    pairs = set(zip(train[0].tolist(), train[1].tolist()))
+                    good = np.asarray([p in pairs for p in zip(ru.tolist(), ri.tolist())])
+                    assert not good.all() and good.any()
+                    again = case.model(oracle, sim)
+                    again.fit(train)
+                    assert again.amend(ru[good], ri[good], u, i, r).status == cs.E_DUPLICATE
+                continue
+            assert not isinstance(x, cs.Refused), (case.name, sim, op)
+            if op.shape == "trivial":
+                assert len(ru) == len(u) == 0 and x[:2] == (len(built), 0) and model.appends == before and model.train is train
+                continue
+            a = model.appends[-1]
+            assert model.appends[:-1] == before and a["kind"] == "amend" and x[:2] == (a["carried"], a["dropped"])
+            assert a["left_users"] == len(users - model.known_users) and a["left_items"] == len(items - model.known_items)
+            if op.shape == "remover":
+                assert len(u) == 0 and 1 <= len(ru) <= 2 and len(set(ru.tolist())) == 1
+            if op.shape == "rerate":
+                assert len(u) == 1 and (int(u[0]), int(i[0])) in set(zip(ru.tolist(), ri.tolist())) and 1 <= len(ru) <= 2
+            if op.shape == "mixed":
+                new = set(u.tolist()) - users
+                assert len(set(u.tolist())) == 3 and len(new) == 1 and min(new) > cs.NEWCOMER and len(set(ru.tolist())) == 1
+                assert set(ru.tolist()) < set(u.tolist()) and u.tolist() != sorted(u.tolist())  # a remover that re-rates; interleaved
+            if op.shape == "leaver":
+                assert a["left_users"] == 1 and a["plain"] and a["carried"] == 0 and len(u) == 0
+            if op.shape == "lone_item":
+                assert a["left_items"] == 1 and a["left_users"] == 0 and len(ru) == 1 and len(u) == 0
+
+
+def test_memo_amends_carry_drop_and_shrink(oracle):
+    """under Jaccard some amend of every memo sequence carries lists and drops lists, the amend of a lone item carries in some
+    sequence while num_items shrinks; under the adjusted cosine every amend of a memo fit (users of <= 4 ratings) is plain"""
+    lone = []
+    for case in cs.MEMO_CASES:
+        model, _ = _played(oracle, case, "jaccard")
+        amends = [a for a in model.appends if a["kind"] == "amend"]
+        assert any(a["carried"] >= 1 and a["dropped"] >= 1 for a in amends), (case.name, amends)
+        assert any(a["plain"] and a["left_users"] == 1 for a in amends), (case.name, amends)
+        lone += [a for a in amends if a["left_items"] == 1]
+        cosine, _ = _played(oracle, case, "cosine")
+        amends_c = [a for a in cosine.appends if a["kind"] == "amend"]
+        assert len(amends_c) == len(amends) == len(cs.AMEND_SHAPES) - 1
+        assert all(a["plain"] and a["carried"] == 0 for a in amends_c), (case.name, amends_c)
+    assert len(lone) == len(cs.MEMO_CASES) and any(a["carried"] >= 1 and not a["plain"] for a in lone), lone
+
+
+@pytest.mark.parametrize("life", range(len(cs.LIVES)))
+def test_lives_amend_early_carry_and_shrink(oracle, life):
+    """every life has an amend that shrinks the fit in the first half of its body, a trivial one and two refused ones; on the fits
+    without short rows some amend under the adjusted cosine keeps lists and drops lists"""
+    fit, k0, _ = cs.LIVES[life]
+    ops = cs.life_ops(oracle, life)
+    model = cs.HandleModel(oracle, fit.train, oracle.SIM_COSINE, k0)
+    out = cs.play_on_model(model, ops)
+    body = ops[2:]
+    shapes = [op.shape for op in body if op.kind == "amend"]
+    assert {"leaver", "trivial", "not_a_row", "duplicate"} < set(shapes) and len(shapes) == len(set(shapes)), (life, shapes)
+    assert set(shapes) >= ({"rerate"} if len(set(fit.train[0].tolist())) > 1000 else {"rerate", "mixed", "lone_item"}), (life, shapes)
+    shrinks = [j for j, op in enumerate(body) if op.kind == "amend" and op.shape in cs.AMEND_SHRINKS]
+    assert shrinks[0] < len(body) // 2, (life, shrinks, len(body))
+    for op, x in _amends(ops, out):
+        want = cs.AMEND_REFUSALS.get(op.shape)
+        assert (x.status == want) if want else not isinstance(x, cs.Refused), (life, op)
+    amends = [a for a in model.appends if a["kind"] == "amend"]
+    assert any(a["left_users"] == 1 for a in amends) and ("lone_item" not in shapes or any(a["left_items"] == 1 for a in amends))
+    if model.short_fit:
+        assert all(a["plain"] for a in amends), (life, amends)
+    else:
+        assert any(a["carried"] >= 1 and a["dropped"] >= 1 for a in amends), (life, amends)
