@@ -1175,14 +1175,62 @@ int knncf_append(knncf_handle* h, const int32_t* users, const int32_t* items, co
  * KNNCF_DEBUG_TRACE_DISPATCH prints knncf_append's `append` line for every call and, after it, for a call with removals
  *     knncf-dispatch amend removers=<changers with removals> removed=<n_removed> kept_rows=<train rows that went into aug>
  * KNNCF_DEBUG_APPEND_MAX_CHANGERS applies as in knncf_append.
- * OUT OF SCOPE: carrying when a user leaves; a device-pointer form; shard handles and knncf_group_*; the command-line tool;
+ * OUT OF SCOPE: carrying when a user leaves (knncf_remove_users below carries: "Remove users"); a device-pointer form; shard handles and knncf_group_*; the command-line tool;
  * KNNCF_PRED_PERSONALIZED state (a refit drops it, as before). */
 #define KNNCF_AMEND_TILE 2048
 int knncf_amend(knncf_handle* h, const int32_t* removed_users, const int32_t* removed_items, int64_t n_removed,
                 const int32_t* users, const int32_t* items, const double* ratings, int64_t n,
                 int64_t* n_carried, int64_t* n_dropped, int32_t* dropped, int64_t dropped_cap);
 
-/* ---- batch ---------------------------------------------------------------- */
+/* ---- Remove users: users leave the fit, the kNN lists that do not hold them kept -----------------------------------------------
+ * The n_users fitted users users[j] leave the fit with every row they have.  The caller keeps no rows: the ids are enough.
+ * aug = train in file order without every row whose user is in `users`.
+ * Answers.  Every later call on the handle answers bit for bit as a handle on which knncf_fit(aug) was called.  These are also
+ * the answers of knncf_amend given every row of those users.
+ * Handle state.  B = the users whose neighbour list was built before the call.  S = the leavers and every fitted user whose
+ * STORED list holds a leaver in one of its min(count, min(k, num_users - 1)) cells, whatever the similarity there, +0.0 and -0.0
+ * included.  K = B \ S.  The handle is left in the state that knncf_fit(aug) followed by knncf_neighbors_batch over K in
+ * ascending raw id leaves: the same lists, the same build numbers (call 1, position in K), the same call counter, the same
+ * knncf_neighbors_save bytes.  Nothing outside K is built.
+ * Why the lists that hold a leaver are enough.  A list that does not hold leaver l has l behind its cut: taking l out of
+ * allUsers - u changes nothing in front of the cut.  No similarity between two remaining users reads l's rows.  Users and items
+ * that leave keep the relative set order of the rest: the trie key of an id does not depend on the set.  So the list of v outside
+ * S on aug is its list on train (tests/test_remove_users_premises.py checks it on the oracle; DESIGN.md "Remove users").
+ * Outputs.  As knncf_append: *n_carried = |K|, *n_dropped = |B ∩ S|; dropped receives the first min(*n_dropped, dropped_cap) raw
+ * ids of B ∩ S in the new fit's user set order, a leaver that had a list standing where its id would stand in that order (where
+ * the new fit has fewer than 5 users: behind them, as in knncf_amend).  A leaver without a list is not counted.
+ * Plain refits.  Nothing is carried (*n_carried = 0, dropped = B; the answers are still those of knncf_fit(aug)) when
+ *   - min(k, num_users' - 1) is not the stored lists' length, or the stored lists were built for another k (knncf_set_k),
+ *   - the handle is KNNCF_SIM_ONE: it has no lists, 0 / 0,
+ *   - more than KNNCF_APPEND_MAX_CHANGERS leavers are given (KNNCF_DEBUG_APPEND_MAX_CHANGERS applies as in knncf_append),
+ *   - train or aug has fewer than 5 users or fewer than 5 items (the id sets change their iteration class there),
+ *   - the handle is KNNCF_SIM_COSINE and train has a user of 4 or fewer ratings: the owner rule of such pairs reads the build
+ *     numbers.  Jaccard carries.
+ * Statuses.  KNNCF_E_STATE before a fit; KNNCF_E_UNSUPPORTED on a shard handle; KNNCF_E_INVALID for a null n_carried or
+ * n_dropped, a null users with n_users > 0, a null dropped with dropped_cap > 0, a negative n_users or dropped_cap; KNNCF_E_INVALID
+ * for an id that is no user of train, for an id listed twice, and for a call that leaves no row.  Precedence: the arguments, then
+ * the ids, then the empty aug.  After any refusal the handle is exactly as before the call: the new fit is built beside the old
+ * one and swapped in last, as in knncf_append (a SECOND copy of the fit's arrays during the call).
+ * Trivial calls.  n_users == 0 is KNNCF_OK and touches nothing: *n_carried = |B|, *n_dropped = 0.
+ * Everything a refit drops is dropped: the Personalized table, the rater copies, the item statistics.
+ * The stages.  Removal: the host sorts the ids, looks them up among the fit's users and knows the surviving row count from the row
+ * lengths; the device flags every file row of a leaver, in knncf_amend's tiles of KNNCF_AMEND_TILE rows, and compacts the three
+ * file-order arrays as knncf_amend does — stable, no atomics; the counted survivors must be the host's number (KNNCF_E_STATE).
+ * Marking: one pass over the stored lists, one wave per fitted user, each stored id tested against a bitmap of the leavers (in
+ * LDS where it fits; KNNCF_DEBUG_NO_LDS_BITMAPS takes the global-memory variant).  Carry: knncf_append's, through a map in which
+ * a leaver is "gone".
+ * Timings: the removal, the refit and the carry are charged to prep_ms.
+ * KNNCF_DEBUG_TRACE_DISPATCH prints knncf_append's `append` line (changers = the leavers) and after it
+ *     knncf-dispatch remove users=<n_users> removed=<rows taken out> kept_rows=<rows of aug>
+ *                           holders=<|B ∩ S| without the leavers> bitmap=<lds|global>
+ * on one line.
+ * OUT OF SCOPE: a device-pointer form; shard handles and knncf_group_*; the command-line tool; leavers mixed with other changers
+ * in one call (knncf_amend takes a leaver's rows among its removals and then refits plainly: its own leaver rule is unchanged);
+ * the call-sequence model of the tests. */
+int knncf_remove_users(knncf_handle* h, const int32_t* users, int64_t n_users,
+                       int64_t* n_carried, int64_t* n_dropped, int32_t* dropped, int64_t dropped_cap);
+
+/* ---- batch---------------------------------------------------------------- */
 int knncf_predict_batch(knncf_handle* h, int predictor, const int32_t* users,
                         const int32_t* items, int64_t n, double* out);
 int knncf_predict_batch_device(knncf_handle* h, int predictor, const int32_t* d_users,

@@ -2151,6 +2151,9 @@ void do_neighbors_load(knncf_handle* h, const char* path) {
 // knncf_amend (DESIGN.md "Amend") is the same call with removals in front: the changers are the users of the removals too and run
 // through REVISE chunks, and the new Train's first part is the old file order without the removed rows (amend_flag, which also
 // decides whether every removal is a train row, and amend_compact).  knncf_append is the call without removals.
+// knncf_remove_users (DESIGN.md "Remove users") is the call whose changers are users that leave.  Three things differ: the removal
+// source is the list of users (amend_flag_users: no (user, item) table), the marking is one pass over the stored lists
+// (append_holders: the lists that hold a leaver) and a user that leaves is no reason for a plain refit — the map gives it -1.
 struct AppendRows {
     std::vector<int32_t> changers, items;
     std::vector<int64_t> offsets;
@@ -2273,14 +2276,43 @@ bool mark_stale_lists(knncf_handle* h, const AppendRows& g) {
     return true;
 }
 
+// the leavers of knncf_remove_users as the stages want them: raw ids as uint32 ascending (amend_flag_users), their dense users on
+// the old fit, the train rows they take with them.  Throws an id that is no user of train and an id listed twice.
+struct Leavers {
+    std::vector<uint32_t> raw;
+    std::vector<int32_t> dense;
+    int64_t rows = 0;
+};
+Leavers look_up_leavers(knncf_handle* h, const int32_t* users, int64_t n_users) {
+    Leavers lv;
+    load_host_ids(h);
+    std::vector<std::pair<uint32_t, int64_t>> by_id((size_t)n_users);
+    for (int64_t j = 0; j < n_users; ++j) by_id[j] = {(uint32_t)users[j], j};
+    std::sort(by_id.begin(), by_id.end());
+    for (int64_t j = 0; j < n_users; ++j) {
+        const int32_t raw = users[by_id[j].second];
+        const int32_t du = dense_lookup(h->h_ukeys.data(), h->tr.U, raw);
+        KN_REQUIRE(du >= 0, KNNCF_E_INVALID, "remove_users: user " + std::to_string(raw) + " is no user of the training set");
+        KN_REQUIRE(j == 0 || by_id[j].first != by_id[j - 1].first, KNNCF_E_INVALID,
+                   "remove_users: user " + std::to_string(raw) + " is listed twice");
+        lv.raw.push_back(by_id[j].first);
+        lv.dense.push_back(du);
+        lv.rows += train_row_length(h, du);
+    }
+    return lv;
+}
+
+// leavers / n_leavers: knncf_remove_users (then the call has neither removals nor rows)
 void do_amend(knncf_handle* h, const int32_t* removed_users, const int32_t* removed_items, int64_t n_removed, const int32_t* users,
               const int32_t* items, const double* ratings, int64_t n, int64_t* n_carried, int64_t* n_dropped, int32_t* dropped,
-              int64_t dropped_cap) {
+              int64_t dropped_cap, const int32_t* leavers = nullptr, int64_t n_leavers = 0) {
     require_fitted(h, false);
     KN_REQUIRE(h->cfg.shard_count == 1, KNNCF_E_UNSUPPORTED, "append: single-shard handles only");
     KN_REQUIRE(n >= 0 && n_removed >= 0 && n_carried && n_dropped && dropped_cap >= 0 && (dropped_cap == 0 || dropped) &&
                    (n == 0 || (users && items && ratings)) && (n_removed == 0 || (removed_users && removed_items)),
                KNNCF_E_INVALID, "append: null argument, n < 0, n_removed < 0 or dropped_cap < 0");
+    KN_REQUIRE(n_leavers >= 0 && (n_leavers == 0 || leavers), KNNCF_E_INVALID, "remove_users: null users or n_users < 0");
+    const bool whole_users = n_leavers > 0;
     Train& tr = h->tr;
     NeighborTable& nt = h->nt;
     AppendScratch& as = h->append;
@@ -2288,12 +2320,12 @@ void do_amend(knncf_handle* h, const int32_t* removed_users, const int32_t* remo
     const int32_t U = tr.U;
     h->prep.join_commit(st);
     append_begin(as, U, st);
-    int64_t totals[2] = {0, 0};
+    int64_t totals[5] = {0, 0, 0, 0, 0};  // (|K|, |B ∩ S|; [4], fetched for knncf_remove_users only: the leavers in B ∩ S)
     auto fetch_totals = [&] {
-        KN_HIP(hipMemcpyAsync(totals, as.totals.p, sizeof totals, hipMemcpyDeviceToHost, st));
+        KN_HIP(hipMemcpyAsync(totals, as.totals.p, (whole_users ? 5 : 2) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
         KN_HIP(hipStreamSynchronize(st));
     };
-    if (n == 0 && n_removed == 0) {  // touches nothing: |B| from the build numbers
+    if (n == 0 && n_removed == 0 && !whole_users) {  // touches nothing: |B| from the build numbers
         append_sets(as, tr, nt, false, 0, st);
         fetch_totals();
         *n_carried = totals[0];
@@ -2321,14 +2353,29 @@ void do_amend(knncf_handle* h, const int32_t* removed_users, const int32_t* remo
         KN_REQUIRE(kept_rows == tr.n - n_removed, KNNCF_E_STATE, "amend: the surviving rows are not the train rows without the removals");
         KN_REQUIRE(kept_rows + n > 0, KNNCF_E_INVALID, "amend: the removals leave the training set without a row");
     }
+    // ---- the users that leave: which file rows go; the host knows their number from the row lengths
+    Leavers lv;
+    if (whole_users) {
+        lv = look_up_leavers(h, leavers, n_leavers);
+        KN_REQUIRE(lv.rows < tr.n, KNNCF_E_INVALID, "remove_users: the users leave the training set without a row");
+        int64_t verdict[2] = {0, 0};
+        {
+            Stage s(h, &h->tm.prep_ms);
+            amend_flag_users(as, tr, lv.raw.data(), (int32_t)n_leavers, st);
+        }
+        KN_HIP(hipMemcpyAsync(verdict, as.totals.p + 2, sizeof verdict, hipMemcpyDeviceToHost, st));
+        KN_HIP(hipStreamSynchronize(st));
+        kept_rows = verdict[0];
+        KN_REQUIRE(kept_rows == tr.n - lv.rows, KNNCF_E_STATE, "remove_users: the surviving rows are not the train rows without the users' rows");
+    }
     KN_REQUIRE(kept_rows + n < ((int64_t)1 << 29), KNNCF_E_UNSUPPORTED, "append: more than 2^29-1 ratings");
-    const int64_t n_changers = (int64_t)g.changers.size();
+    const int64_t n_changers = whole_users ? n_leavers : (int64_t)g.changers.size();
     // ---- the plain refits that the rows alone decide
     load_host_ids(h);
-    int32_t joined = 0, left = 0;
+    int32_t joined = 0, left = (int32_t)n_leavers;
     int64_t removers = 0;
     bool short_changer = false;  // a newcomer of <= 4 rows, or a fitted changer that its removals leave that few
-    for (int64_t b = 0; b < n_changers; ++b) {
+    for (int64_t b = 0; b < (int64_t)g.changers.size(); ++b) {  // (none for leavers: they are no rows of g)
         const int32_t du = dense_lookup(h->h_ukeys.data(), U, g.changers[b]);
         const int64_t nr = n_removed > 0 ? g.removed_offsets[b + 1] - g.removed_offsets[b] : 0;
         // (its rows on aug; a fitted changer without removals keeps its train rows, which nothing below asks for)
@@ -2346,12 +2393,18 @@ void do_amend(knncf_handle* h, const int32_t* removed_users, const int32_t* remo
     const bool no_lists = h->cfg.similarity == KNNCF_SIM_ONE || nt.kcap <= 0 || h->epoch == 1;  // (no call has built one since the fit)
     bool plain = h->cfg.similarity == KNNCF_SIM_ONE || new_kcap != nt.kcap || nt.k != h->cfg.k ||
                  n_changers > max_changers ||
-                 left > 0 ||  // (k_ap_remap: every old user is in the new fit)
+                 (left > 0 && !whole_users) ||  // (a leaver among other changers: its holders are not marked)
+                 (whole_users && U - left < 5) ||
                  // (the update queries refuse such a fit: the id sets change their iteration class below five members)
                  U < 5 || tr.I < 5 ||
                  (h->cfg.similarity == KNNCF_SIM_COSINE && (short_changer || has_short_rows(h)));
     // ---- marking, on the old fit
-    if (!plain && !no_lists) plain = !mark_stale_lists(h, g);
+    const bool lds_bitmap = lds_bitmap_fits(ceil_div(U, 64));  // (of append_holders)
+    if (whole_users) append_leavers(as, U, lv.dense.data(), (int32_t)n_leavers, st);
+    if (!plain && !no_lists) {
+        if (whole_users) append_holders(as, tr, nt, lds_bitmap, st);
+        else plain = !mark_stale_lists(h, g);
+    }
     // ---- the new Train beside the old one
     Train next;
     next.n = kept_rows + n;
@@ -2359,7 +2412,7 @@ void do_amend(knncf_handle* h, const int32_t* removed_users, const int32_t* remo
     {
         Stage s(h, &h->tm.prep_ms);
         next.user_raw.alloc(next.n); next.item_raw.alloc(next.n); next.rating.alloc(next.n);
-        if (n_removed > 0) {
+        if (n_removed > 0 || whole_users) {
             amend_compact(as, tr, next.user_raw.p, next.item_raw.p, next.rating.p, st);
         } else {
             KN_HIP(hipMemcpyAsync(next.user_raw.p, tr.user_raw.p, tr.n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
@@ -2378,7 +2431,9 @@ void do_amend(knncf_handle* h, const int32_t* removed_users, const int32_t* remo
     // ---- K, B ∩ S, the dropped ids (old dense order = new set order: the map is monotone)
     // (the user set changed its iteration class, upwards or — users left — downwards: every id is fetched and ordered on the host)
     const bool tiny = (U < 5) != (next.U < 5);
+    if (whole_users && next.I < 5) plain = true;  // (the leavers took items with them: the item set changed its iteration class)
     append_sets(as, tr, nt, plain, tiny ? U : dropped_cap, st);
+    if (whole_users) append_leavers_gone(as, (int32_t)n_leavers, st);
     const bool moved = !plain && next.U != U;
     NeighborTable table;
     if (!plain) {
@@ -2432,6 +2487,9 @@ void do_amend(knncf_handle* h, const int32_t* removed_users, const int32_t* remo
                       (long long)built, (long long)totals[0], (long long)totals[1], (int)moved, (int)plain);
     if (n_removed > 0)
         KN_TRACE_DISPATCH("amend removers=%lld removed=%lld kept_rows=%lld", (long long)removers, (long long)n_removed, (long long)kept_rows);
+    if (whole_users)
+        KN_TRACE_DISPATCH("remove users=%lld removed=%lld kept_rows=%lld holders=%lld bitmap=%s", (long long)n_leavers, (long long)lv.rows,
+                          (long long)kept_rows, (long long)(totals[1] - totals[4]), lds_bitmap ? "lds" : "global");
 }
 
 }  // namespace
@@ -3616,6 +3674,11 @@ int knncf_revise_entered_batch(knncf_handle* h, const int32_t* users, const int6
 int knncf_append(knncf_handle* h, const int32_t* users, const int32_t* items, const double* ratings, int64_t n, int64_t* n_carried,
                  int64_t* n_dropped, int32_t* dropped, int64_t dropped_cap) {
     return guarded(h, [&] { do_amend(h, nullptr, nullptr, 0, users, items, ratings, n, n_carried, n_dropped, dropped, dropped_cap); });
+}
+
+int knncf_remove_users(knncf_handle* h, const int32_t* users, int64_t n_users, int64_t* n_carried, int64_t* n_dropped, int32_t* dropped,
+                       int64_t dropped_cap) {
+    return guarded(h, [&] { do_amend(h, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, n_carried, n_dropped, dropped, dropped_cap, users, n_users); });
 }
 
 int knncf_amend(knncf_handle* h, const int32_t* removed_users, const int32_t* removed_items, int64_t n_removed, const int32_t* users,

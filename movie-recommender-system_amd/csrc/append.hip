@@ -14,6 +14,12 @@
 //   k_ap_clear    the table stays: the rows outside K lose their length and build number
 // knncf_amend (DESIGN.md "Amend") is the same call with removals: its changers run through REVISE chunks, and the k_am_* kernels
 // below take the removed rows out of the file-order arrays that the new fit is built from.
+// knncf_remove_users (DESIGN.md "Remove users") is the call whose changers leave the fit: k_am_flag_users flags every file row of
+// a leaver, and the marking is one pass over the stored lists:
+//   k_ap_leaver_bits   the leavers as a bitmap over the old fit's dense users
+//   k_ap_holders       stale |= every user whose stored list holds a leaver, and the leavers themselves
+//   k_ap_leavers_gone  how many leavers are in B ∩ S (the trace line's holders = |B ∩ S| without them)
+// k_ap_remap gives a user that left -1; the carry never reads that cell for a kept row.
 // Stores are vector stores, atomicOr and atomicAdd on global memory.
 #include <algorithm>
 
@@ -95,7 +101,8 @@ __global__ void __launch_bounds__(TPB) k_ap_raw_keys(int32_t U, const int32_t* _
 
 // One workgroup.  by_raw [U] = the dense users by ascending raw id; the exclusive count of kept users in front of place i is the
 // rank among K of the user there.  A kept user v gets seq[map[v]] = 1 << 32 | rank: epoch 1, position in K.
-// Bounds.  pre holds U + 1 cells; by_raw[i] < U; map[v] < the new fit's users (k_ap_remap), or v itself without a map.
+// Bounds.  pre holds U + 1 cells; by_raw[i] < U; map[v] < the new fit's users (k_ap_remap), or v itself without a map.  map is
+// read for kept users only, and a kept user is no leaver: map[v] >= 0.
 __global__ void __launch_bounds__(ONE_BLOCK) k_ap_number(int32_t U, const uint32_t* __restrict__ by_raw,
                                                          const unsigned long long* __restrict__ kept, const int32_t* __restrict__ map,
                                                          int64_t* __restrict__ pre, int64_t* __restrict__ seq) {
@@ -107,8 +114,10 @@ __global__ void __launch_bounds__(ONE_BLOCK) k_ap_number(int32_t U, const uint32
     }
 }
 
-// One thread per old dense user: the lower bound of its trie key among the new keys, which hold it (no user leaves a fit).
-// Bounds.  v < U; the search stays inside [0, new_U) and ends on the key itself.
+// One thread per old dense user: the lower bound of its trie key among the new keys — its place where they hold the key, -1
+// ("gone") where they do not: the user left the fit (knncf_remove_users; in knncf_append and knncf_amend no user leaves a carried
+// fit, and every key is found).
+// Bounds.  v < U; the search stays inside [0, new_U), and new_ukeys[lo] is read only with lo < new_U.
 __global__ void __launch_bounds__(TPB) k_ap_remap(int32_t U, const uint32_t* __restrict__ ukeys, const uint32_t* __restrict__ new_ukeys,
                                                   int32_t new_U, int32_t* __restrict__ map) {
     const int32_t v = blockIdx.x * TPB + threadIdx.x;
@@ -120,7 +129,7 @@ __global__ void __launch_bounds__(TPB) k_ap_remap(int32_t U, const uint32_t* __r
         if (new_ukeys[mid] < key) lo = mid + 1;
         else hi = mid;
     }
-    map[v] = min(lo, new_U - 1);
+    map[v] = (lo < new_U && new_ukeys[lo] == key) ? lo : -1;
 }
 
 __global__ void __launch_bounds__(TPB) k_ap_clear(int32_t U, const unsigned long long* __restrict__ kept, int32_t* __restrict__ cnt,
@@ -133,7 +142,9 @@ __global__ void __launch_bounds__(TPB) k_ap_clear(int32_t U, const unsigned long
 
 // One wave per old dense user (grid-stride); a kept row's filled cells go to row map[v] of the new table.
 // Bounds.  v < U; cells [0, min(cnt[v], kcap)) of row v are read, a stored id is a dense user of [0, U); map[.] < the new fit's
-// users, so the written cells lie in row map[v] of a table of as many rows with kcap cells each.
+// users, so the written cells lie in row map[v] of a table of as many rows with kcap cells each.  map[v] >= 0: a kept user did
+// not leave.  A stored id of a kept row did not leave either (k_ap_holders put every holder of a leaver into stale), so no
+// written id is -1.
 __global__ void __launch_bounds__(TPB) k_ap_carry(int32_t U, int32_t kcap, const unsigned long long* __restrict__ kept,
                                                   const int32_t* __restrict__ map, const int32_t* __restrict__ cnt,
                                                   const int32_t* __restrict__ idx, const double* __restrict__ sim,
@@ -149,6 +160,56 @@ __global__ void __launch_bounds__(TPB) k_ap_carry(int32_t U, int32_t kcap, const
         }
         if (lane == 0) ncnt[map[v]] = cnt[v];
     }
+}
+
+// ---- knncf_remove_users: the marking (DESIGN.md "Remove users") -----------------------------------------------------------------
+// One thread per leaver: its bit in the leaver bitmap (zeroed beforehand).
+// Bounds.  j < L; dense[j] is a dense user of [0, U) (the host looked it up), whose word is < Wu.
+__global__ void __launch_bounds__(TPB) k_ap_leaver_bits(int32_t L, const int32_t* __restrict__ dense, unsigned long long* __restrict__ leaver) {
+    const int32_t j = blockIdx.x * TPB + threadIdx.x;
+    if (j >= L) return;
+    const int32_t d = dense[j];
+    atomicOr(&leaver[d >> 6], 1ull << (d & 63));
+}
+
+// One wave per fitted user v (grid-stride, as k_enu_locate walks the table): the lanes read the filled cells of v's stored row in
+// strides of 64 and test each stored dense id against the leaver bitmap, whatever similarity stands beside it.  A wave with a
+// hit, and the wave of a leaver, sets v's bit in the stale mask: one atomicOr per wave, as in k_ap_mark.  IN_LDS: every workgroup
+// first copies the bitmap's Wu words into LDS (dynamic, Wu * 8 bytes); otherwise the tests read global memory.
+// Bounds.  v < U; cells [0, min(cnt[v], kcap)) of row v are read, inside the table's U * kcap cells; a stored id is a dense user
+// of [0, U), whose word is < Wu = the words of `leaver`, of the LDS copy and of `stale`.
+template <bool IN_LDS>
+__global__ void __launch_bounds__(TPB) k_ap_holders(int32_t U, int32_t kcap, const int32_t* __restrict__ cnt, const int32_t* __restrict__ idx,
+                                                    const unsigned long long* __restrict__ leaver, unsigned long long* __restrict__ stale) {
+    extern __shared__ unsigned long long s_leaver[];
+    if (IN_LDS) {
+        const int32_t Wu = (U + 63) >> 6;
+        for (int32_t w = threadIdx.x; w < Wu; w += TPB) s_leaver[w] = leaver[w];
+        __syncthreads();
+    }
+    auto left = [&](int32_t x) -> bool { return IN_LDS ? (s_leaver[x >> 6] >> (x & 63)) & 1ull : ap_bit(leaver, x); };
+    const int lane = threadIdx.x & 63;
+    for (int64_t v = (int64_t)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6); v < U; v += (int64_t)gridDim.x * (TPB / 64)) {
+        const int32_t L = min(cnt[v], kcap);
+        const int64_t from = v * kcap;
+        bool hit = lane == 0 && left((int32_t)v);
+        for (int32_t j = lane; j < L; j += 64) hit |= left(idx[from + j]);
+        if (__ballot(hit) != 0ull && lane == 0) atomicOr(&stale[v >> 6], 1ull << (v & 63));
+    }
+}
+
+// One workgroup: out[0] = the leavers whose bit is set in gone (a leaver that had a list).
+// Bounds.  j < L; dense[j] < U, whose word of gone is < Wu.
+__global__ void __launch_bounds__(ONE_BLOCK) k_ap_leavers_gone(int32_t L, const int32_t* __restrict__ dense, const unsigned long long* __restrict__ gone,
+                                                               int64_t* __restrict__ out) {
+    __shared__ int32_t found;
+    if (threadIdx.x == 0) found = 0;
+    __syncthreads();
+    int32_t mine = 0;
+    for (int32_t j = threadIdx.x; j < L; j += ONE_BLOCK) mine += ap_bit(gone, dense[j]) ? 1 : 0;
+    if (mine) atomicAdd(&found, mine);  // (an LDS cell)
+    __syncthreads();
+    if (threadIdx.x == 0) out[0] = found;
 }
 
 // ---- knncf_amend: the removed rows leave the file order (DESIGN.md "Amend") -----------------------------------------------------
@@ -204,6 +265,42 @@ __global__ void __launch_bounds__(TPB) k_am_flag(int64_t n, int32_t R, const uin
                 hit = true;
                 atomicAdd(&hits[at], 1);
             }
+        }
+        const unsigned long long word = __ballot(hit), live = __ballot(i < n);
+        if ((threadIdx.x & 63) == 0 && i < n) bits[i >> 6] = word;
+        mine += __popcll(live & ~word);
+    }
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int32_t c = 0;
+        for (int w = 0; w < TPB / 64; ++w) c += part[w];
+        tile_cnt[blockIdx.x] = c;
+    }
+}
+
+// k_am_flag for whole users (knncf_remove_users): a row is removed when its user is one of the L leavers (ascending as uint32).
+// The same tiles, the same removed-row bitmap and the same per-tile survivor counts; no table of (user, item), no hits.
+// Bounds.  Row i < n reads user_raw[i]; the search stays inside leavers [L]; lane 0 writes word i / 64 only with i < n, which is
+// < ceil(n / 64); cell blockIdx.x < the tiles = ceil(n / AM_TILE).
+__global__ void __launch_bounds__(TPB) k_am_flag_users(int64_t n, int32_t L, const uint32_t* __restrict__ leavers,
+                                                       const int32_t* __restrict__ user_raw, unsigned long long* __restrict__ bits,
+                                                       int32_t* __restrict__ tile_cnt) {
+    __shared__ int32_t part[TPB / 64];
+    const int64_t base = (int64_t)blockIdx.x * AM_TILE;
+    int32_t mine = 0;  // the survivors of this wave's rows (the same in every lane)
+    for (int it = 0; it < AM_TILE / TPB; ++it) {
+        const int64_t i = base + it * TPB + threadIdx.x;
+        bool hit = false;
+        if (i < n) {
+            const uint32_t user = (uint32_t)user_raw[i];
+            int32_t lo = 0, hi = L;
+            while (lo < hi) {
+                const int32_t mid = (lo + hi) >> 1;
+                if (leavers[mid] < user) lo = mid + 1;
+                else hi = mid;
+            }
+            hit = lo < L && leavers[lo] == user;
         }
         const unsigned long long word = __ballot(hit), live = __ballot(i < n);
         if ((threadIdx.x & 63) == 0 && i < n) bits[i >> 6] = word;
@@ -293,6 +390,41 @@ void amend_flag(AppendScratch& as, const Train& tr, const uint64_t* h_keys, int6
     KN_HIP(hipGetLastError());
 }
 
+void amend_flag_users(AppendScratch& as, const Train& tr, const uint32_t* h_leavers, int32_t L, hipStream_t st) {
+    const int64_t tiles = ceil_div(tr.n, AM_TILE);
+    as.am_removers.ensure(L);
+    as.am_bits.ensure(ceil_div(tr.n, 64)); as.am_tile_cnt.ensure(tiles); as.am_tile_off.ensure((size_t)tiles + 1);
+    KN_HIP(hipMemcpyAsync(as.am_removers.p, h_leavers, (size_t)L * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    k_am_flag_users<<<(unsigned)tiles, TPB, 0, st>>>(tr.n, L, as.am_removers.p, tr.user_raw.p, as.am_bits.p, as.am_tile_cnt.p);
+    k_am_offsets<<<1, ONE_BLOCK, 0, st>>>(tiles, as.am_tile_cnt.p, as.am_tile_off.p, 0, nullptr, as.totals.p + 2);
+    KN_HIP(hipGetLastError());
+}
+
+void append_leavers(AppendScratch& as, int32_t U, const int32_t* h_dense, int32_t L, hipStream_t st) {
+    const int64_t Wu = ceil_div(U, 64);
+    as.leaver.ensure(Wu); as.leaver_dense.ensure(L);
+    KN_HIP(hipMemsetAsync(as.leaver.p, 0, (size_t)Wu * sizeof(unsigned long long), st));
+    KN_HIP(hipMemcpyAsync(as.leaver_dense.p, h_dense, (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    k_ap_leaver_bits<<<blocks_for(L), TPB, 0, st>>>(L, as.leaver_dense.p, as.leaver.p);
+    KN_HIP(hipGetLastError());
+}
+
+void append_holders(AppendScratch& as, const Train& tr, const NeighborTable& nt, bool in_lds, hipStream_t st) {
+    const int32_t U = tr.U;
+    const unsigned grid = (unsigned)std::min<int64_t>(blocks_for(U, TPB / 64), 2048);
+    if (in_lds)
+        k_ap_holders<true><<<grid, TPB, (size_t)ceil_div(U, 64) * sizeof(unsigned long long), st>>>(U, nt.kcap, nt.cnt.p, nt.idx.p, as.leaver.p,
+                                                                                                   as.stale.p);
+    else
+        k_ap_holders<false><<<grid, TPB, 0, st>>>(U, nt.kcap, nt.cnt.p, nt.idx.p, as.leaver.p, as.stale.p);
+    KN_HIP(hipGetLastError());
+}
+
+void append_leavers_gone(AppendScratch& as, int32_t L, hipStream_t st) {
+    k_ap_leavers_gone<<<1, ONE_BLOCK, 0, st>>>(L, as.leaver_dense.p, as.gone.p, as.totals.p + 4);
+    KN_HIP(hipGetLastError());
+}
+
 void amend_compact(AppendScratch& as, const Train& tr, int32_t* d_user, int32_t* d_item, double* d_rating, hipStream_t st) {
     k_am_compact<<<(unsigned)ceil_div(tr.n, AM_TILE), TPB, 0, st>>>(tr.n, as.am_bits.p, as.am_tile_off.p, tr.user_raw.p, tr.item_raw.p,
                                                                     tr.rating.p, d_user, d_item, d_rating);
@@ -303,7 +435,7 @@ void append_begin(AppendScratch& as, int32_t U, hipStream_t st) {
     const int64_t Wu = ceil_div(U, 64);
     as.stale.ensure(Wu); as.kept.ensure(Wu); as.gone.ensure(Wu);
     as.pre.ensure((size_t)std::max<int64_t>(U, Wu) + 1);
-    as.totals.ensure(4);  // (|K|, |B ∩ S|; the removal stage's verdict)
+    as.totals.ensure(5);  // (|K|, |B ∩ S|; the removal stage's verdict; knncf_remove_users: the leavers in B ∩ S)
     KN_HIP(hipMemsetAsync(as.stale.p, 0, (size_t)Wu * sizeof(unsigned long long), st));
 }
 

@@ -560,7 +560,11 @@ struct AppendScratch {
     DArr<uint32_t> k_a, k_b, v_a, v_b;  // [U] the users by ascending raw id (keys: the raw id with its sign bit flipped)
     DArr<int32_t> map;               // [U] old dense user -> new dense user
     DArr<int32_t> dropped;           // [min(cap, U)] raw ids of B ∩ S in dense order
-    DArr<int64_t> totals;            // [4] |K|, |B ∩ S|; the removal stage's verdict: the surviving rows, the first missed removal or -1
+    DArr<int64_t> totals;            // [5] |K|, |B ∩ S|; the removal stage's verdict: the surviving rows, the first missed removal or -1;
+                                     // knncf_remove_users: the leavers in B ∩ S
+    // knncf_remove_users' marking: the leavers as dense users of the old fit
+    DArr<unsigned long long> leaver; // [Wu] bit v: dense user v leaves
+    DArr<int32_t> leaver_dense;      // [L]
     // knncf_amend's removal stage: the table of removals and, over the old fit's n file rows in tiles of KNNCF_AMEND_TILE, the
     // removed-row bitmap with the tiles' survivor counts and offsets
     DArr<uint64_t> am_keys;          // [n_removed] (user << 32 | item, both as uint32), ascending
@@ -578,7 +582,8 @@ void append_mark(AppendScratch& as, int32_t U, int32_t C, const unsigned long lo
 // as.kept / as.gone from nt.seq (all: every built list counts as stale — the plain refit), as.totals, and the first
 // min(|B ∩ S|, cap) raw ids of B ∩ S in dense order into as.dropped.  Two launches.
 void append_sets(AppendScratch& as, const Train& tr, const NeighborTable& nt, bool all, int64_t cap, hipStream_t st);
-// as.map: the place of every old user among new_ukeys [new_U] (the new fit's trie keys in dense order, new_U > 4)
+// as.map: the place of every old user among new_ukeys [new_U] (the new fit's trie keys in dense order, new_U > 4), -1 for a user
+// whose key they do not hold (it left the fit: knncf_remove_users)
 void append_remap(AppendScratch& as, const Train& tr, const uint32_t* new_ukeys, int32_t new_U, hipStream_t st);
 // the build numbers knncf_neighbors_batch over K in ascending raw id gives: seq[map[v]] = 1 << 32 | rank of uid[v] among K, for
 // v in K (map == nullptr: the identity).  One sort of U keys, one single-block scan.
@@ -597,6 +602,17 @@ void amend_flag(AppendScratch& as, const Train& tr, const uint64_t* h_keys, int6
 // after amend_flag: tr's surviving file rows, in file order, to the front of the three arrays (as.totals[2] cells each); tr's
 // own arrays are only read.  No atomics.
 void amend_compact(AppendScratch& as, const Train& tr, int32_t* d_user, int32_t* d_item, double* d_rating, hipStream_t st);
+// knncf_remove_users' removal stage, after append_begin: amend_flag for whole users.  h_leavers [L] the raw ids of the leavers as
+// uint32, ascending and distinct, L > 0: every file row of one of them is flagged; as.totals[2] = the surviving rows, [3] = -1.
+// amend_compact follows as after amend_flag.  Two launches; the host array must live until the stream has passed the copy.
+void amend_flag_users(AppendScratch& as, const Train& tr, const uint32_t* h_leavers, int32_t L, hipStream_t st);
+// knncf_remove_users' marking.  append_leavers: as.leaver / as.leaver_dense from the leavers' dense users h_dense [L] (distinct,
+// of [0, U)).  append_holders: stale |= every user whose stored list holds a leaver in one of its min(cnt, kcap) cells, and the
+// leavers; one pass over nt.idx, no read-back (in_lds: the bitmap is copied into LDS by every workgroup — ceil(U / 64) * 8 bytes
+// must fit).  append_leavers_gone, after append_sets: as.totals[4] = the leavers in B ∩ S.
+void append_leavers(AppendScratch& as, int32_t U, const int32_t* h_dense, int32_t L, hipStream_t st);
+void append_holders(AppendScratch& as, const Train& tr, const NeighborTable& nt, bool in_lds, hipStream_t st);
+void append_leavers_gone(AppendScratch& as, int32_t L, hipStream_t st);
 
 // ---- reco_batch.hip: recommendations :651-674 for users of the fit (knncf_recommend, knncf_recommend_batch; DESIGN.md "Batched
 // recommendations") ----

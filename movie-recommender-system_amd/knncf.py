@@ -142,7 +142,7 @@ EXPORTS = [
     "knncf_revise_bystander_neighbors_batch", "knncf_revise_bystander_predict_batch",
     "knncf_query_entered", "knncf_query_entered_batch",
     "knncf_update_entered", "knncf_update_entered_batch", "knncf_revise_entered", "knncf_revise_entered_batch",
-    "knncf_append", "knncf_amend",
+    "knncf_append", "knncf_amend", "knncf_remove_users",
     "knncf_predict_batch",
     "knncf_predict_batch_device", "knncf_mae", "knncf_mae_device", "knncf_mae_sweep", "knncf_mae_sweep_device", "knncf_shard_view_get",
     "knncf_shard_commit", "knncf_get_timings", "knncf_reset_timings", "knncf_reset_neighbors",
@@ -286,6 +286,8 @@ def load_library():
     L.knncf_append.argtypes = [C.c_void_p, _i32p, _i32p, _f64p, C.c_int64, _i64p, _i64p, _i32p, C.c_int64]
     # amend: the removals (users, items, their number) in front of knncf_append's arguments
     L.knncf_amend.argtypes = [C.c_void_p, _i32p, _i32p, C.c_int64] + L.knncf_append.argtypes[1:]
+    # remove users: the ids and their number, then knncf_append's outputs
+    L.knncf_remove_users.argtypes = [C.c_void_p, _i32p, C.c_int64] + L.knncf_append.argtypes[5:]
     # revise queries: the update argument lists with the removals in front of the additional rows
     for name, at, single in (("neighbors", 2, True), ("predict", 3, True), ("recommend", 3, True), ("explain", 3, True),
                              ("explain_personalized", 2, True), ("neighbors_batch", 2, False), ("predict_batch", 3, False),
@@ -1385,6 +1387,26 @@ class Appends:
         rows = self._rows(users, items, ratings)
         p = self._e._ptr
         return self._call(self._e._lib.knncf_amend, (p(ru, _i32p), p(ri, _i32p), len(ru)), rows, return_dropped)
+
+
+def remove_users(engine, users, return_dropped=False):
+    """knncf_remove_users: the fitted users `users` leave the fit with every row they have; the neighbour lists that hold none of
+    them are kept.  Every later answer is that of fit(train without those users' rows).  Returns what Appends.append returns:
+    (carried, dropped_count[, the dropped raw ids]), a leaver that had a list standing among the dropped ids where its id would
+    stand.  The ids are validated as Appends.amend validates its removals: ValueError before any C call.
+
+    A module-level function on purpose, not a method of Engine or Appends: every public method of those classes has a kind in
+    the tests' call-sequence model, which does not know this call yet."""
+    (u,) = Appends._ids((np.asarray(users),), "users")
+    e = engine
+    carried, gone = C.c_int64(), C.c_int64()
+    cap = e.num_users if return_dropped else 0  # (B ∩ S are users of the fit as it stands)
+    ids = np.empty(max(1, cap), dtype=np.int32)
+    e._check(e._lib.knncf_remove_users(e._h, e._ptr(u, _i32p), len(u), C.byref(carried), C.byref(gone),
+                                       e._ptr(ids, _i32p) if cap else None, cap))
+    if return_dropped:
+        return carried.value, gone.value, ids[:gone.value].copy()
+    return carried.value, gone.value
 
 
 class EnteredQueries:
